@@ -1,7 +1,18 @@
 #!/usr/bin/env python3
 """Headline benchmark: alignments/s of the Phyloformer forward on synthetic LG+GC-like MSAs.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up (W steps), times K steps, writes the distances of the last timed step if
+``--dump-outputs`` is given, and prints the JSON line: ``metric``, ``value`` (alignments/s), ``unit``,
+``higher_is_better``, ``dtype``, ``ms_per_step`` (milliseconds of one timed step), the run's configuration and the
+build of the library.  ``--full`` adds every other figure and check described below: the roofline region, the
+host-buffer rate, the parity leg, the other BASELINE configurations, the CPU baseline and the power samples (and,
+for N > 1, the configs[3] and strong-scaling regions).
+
+``--dump-outputs DIR`` writes ``DIR/distances.npy``: float32 ``[batch, pairs]``, what the timed entry point left in
+its output buffer after the last timed step (rank 0's; a seeded sample of whole alignments if it exceeds 64 MB).
+The inputs are seeded, so two builds given the same arguments can be compared output for output.
 
 N = 1 runs in this process.  N > 1 *without* a launcher environment (``WORLD_SIZE`` unset) makes this process
 a launcher: before any HIP call and without importing the engine it picks a free ``MASTER_PORT`` and starts N
@@ -26,10 +37,10 @@ Fallback ladder: the supervisors run rung 1 = sites on two streams / two communi
 rank dies, no rank makes progress (``--stall-timeout``) or the rung exceeds ``--rung-timeout``, those ranks are
 killed and FRESH ones are started for rung 2 = ``--one-stream`` (serial collectives on one stream), then rung 3 =
 ``--shard alignments`` (no collective).  A rank is never re-exec'ed.  The line records ``config.rung`` and why
-earlier rungs were abandoned.  Exit codes: 0 ok; 3 = the parity bound failed (the line is still printed, no
+earlier rungs were abandoned.  Exit codes: 0 ok; 3 = the parity bound failed (``--full``; the line is still printed, no
 further rung is tried); 4 = more ranks than GPUs without ``--allow-shared-devices``; 124 = every rung timed out.
 
-Parity (BASELINE's metric is "alignments/sec + max-abs distance error"): after the timed regions and outside them
+Parity (``--full``; BASELINE's metric is "alignments/sec + max-abs distance error"): after the timed regions and outside them
 every rank runs the SAME entry point it timed on the reference outputs committed under ``tests/golden/`` (data
 written by oracle/gen_golden.py from the reference's CPU forward; not the oracle): configs[2] 60x500 always,
 for N > 1 also configs[3] 60x2000 with L / N sites per rank over real RCCL (and its rate, as
@@ -39,8 +50,9 @@ and the per-case ``parity`` object.
 
 Rank 0 prints ONE JSON line (contract in the task statement).  ``value`` is the rate with the indices resident
 in HBM when the timed region starts (the task statement: the PCIe-inclusive rate "is never `value`");
-``value_pcie_inclusive`` is the same step through ``pf_forward`` with host buffers (H2D of the indices, D2H of
-the distances, one synchronisation per call) - the rate SURVEY.md 8d words its metric on.  Extra objects:
+``value_pcie_inclusive`` (``--full``) is the same step through ``pf_forward`` with host buffers (H2D of the indices,
+D2H of the distances, one synchronisation per call) - the rate SURVEY.md 8d words its metric on.  Extra objects
+(``--full``):
 ``roofline`` (dominant kernel ``k_main``: algorithmic flops / HIP-event time vs the dense bf16 / fp16 MFMA peak),
 ``configs`` (N = 1: the other BASELINE configurations, a few hundred ms each), ``cpu_baseline`` (torch
 op-order port of the reference on this host's cores; N = 1, rank 0 only) and ``power`` (socket power / clock
@@ -94,7 +106,7 @@ EXIT_PARITY, EXIT_DEVICES, EXIT_WATCHDOG = 3, 4, 124
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=16, help="alignments per GPU per step")
     ap.add_argument("--n-seqs", type=int, default=60)
@@ -119,12 +131,21 @@ def parse_args(argv=None):
                     help="let several ranks share a GPU when there are more ranks than devices (the line is then "
                          "marked as not a scaling result); without it such a run exits with code 4")
     ap.add_argument("--no-parity", action="store_true", help="skip the parity leg (max_abs_err vs the committed reference outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: roofline and host-buffer regions, "
+                         "parity against the committed reference outputs, the other BASELINE configurations, the CPU "
+                         "baseline, power samples (each --no-* option still turns its part off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the distances of the last timed step to DIR/distances.npy (float32)")
     ap.add_argument("--launch-timeout", type=float, default=400.0,
                     help="self-launch (--gpus N > 1 without a launcher): seconds for all rungs of the fallback ladder together")
     ap.add_argument("--rung-timeout", type=float, default=150.0, help="self-launch: seconds one rung of the ladder may take")
     ap.add_argument("--stall-timeout", type=float, default=75.0,
                     help="self-launch: a rung whose ranks report no progress for this long is abandoned")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def workload_label(n_seqs, n_sites, ckpt):
@@ -298,6 +319,23 @@ def configs_leg(eng, make_engine_for, device, parity=None):
         finally:
             e2.close()
     return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """``name -> array`` as ``directory/<name>.npy`` in float32 / float64, at most DUMP_LIMIT_BYTES in all: an array
+    over its share keeps a seeded sample of its rows (the same rows for the same shape, run after run)."""
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a if a.dtype in (np.float32, np.float64) else a.astype(np.float32)
+        if a.nbytes > share:
+            rows = max(1, share // max(1, a.nbytes // a.shape[0]))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], rows, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
 
 
 _LAST_TICK = [0.0]
@@ -527,12 +565,12 @@ def run(args, rank, world, local_rank, group, make_engine, weights, out=sys.stdo
         eng.synchronize()
     if args.warmup:
         est["step"] = (time.perf_counter() - t_w) / max(1, args.warmup - 1)
-        # three regions of `steps` (two-stream, one-stream, host buffers) + parity / configs / baseline allowance
-        beat("warm-up", budget_s=est["step"] * args.steps * 3.5 + 60.0)
+        # --full: three regions of `steps` (two-stream, one-stream, host buffers) + parity / configs / baseline allowance
+        beat("warm-up", budget_s=est["step"] * args.steps * (3.5 if args.full else 1.5) + 60.0)
     else:
         beat("warm-up")
     sampler = None
-    if rank == 0 and not args.no_power:
+    if rank == 0 and args.full and not args.no_power:
         try:
             sampler = PowerSampler(pci=eng.device_pci() if hasattr(eng, "device_pci") else None)
         except Exception:  # noqa: BLE001 - evidence only
@@ -543,6 +581,27 @@ def run(args, rank, world, local_rank, group, make_engine, weights, out=sys.stdo
     dt = timed(step, args.steps)
     collectives_per_step = (eng.collective_count() - coll0) / max(args.steps, 1)
     beat("timed region")
+    result = None
+    if args.full or args.dump_outputs:
+        result = np.empty((B, P), np.float32)       # what the last timed step left in the output buffer
+        eng.d2h(result, d_out)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"distances": result})
+    total_alignments = (B if args.shard == "sites" else B * world) * args.steps
+    value = total_alignments / dt
+    if not args.full:
+        # a plain run: the headline and nothing else
+        if rank == 0:
+            line = headline(args, eng, world, n_devices, B, N, L, dt, comm, comm_note, collectives_per_step,
+                            build_of(eng))
+            print(json.dumps(line), file=out, flush=True)
+        eng.free(d_idx)
+        eng.free(d_out)
+        eng.close()
+        if group is not None:
+            group.barrier()
+        beat("done")
+        return value, True
     # The roofline of the dominant kernel is taken in a second timed region of the same length with the batch
     # on ONE stream: there a k_main launch has the chip to itself and covers the whole batch, so its HIP-event
     # duration is the kernel's own.  (In the two-stream schedule a half-batch launch shares the CUs with the
@@ -558,19 +617,14 @@ def run(args, rank, world, local_rank, group, make_engine, weights, out=sys.stdo
         eng.set_option("profile", 0)
         streams(not args.one_stream)
         beat("roofline region")
-    result = np.empty((B, P), np.float32)
-    eng.d2h(result, d_out)
     assert np.isfinite(result).all() and (result > 0).all()
     # the same step with host buffers: H2D + forward + D2H + synchronisation per call
     step_host()
     dt_host = timed(step_host, args.steps, "host-buffer region", 1.2)
     if sampler:
         sampler.__exit__(None, None, None)
-    info = eng.device_info()
     beat("host-buffer region")
 
-    total_alignments = (B if args.shard == "sites" else B * world) * args.steps
-    value = total_alignments / dt
     multi = world > 1 or args.force_dist
     sharded = args.shard == "sites"          # the entry point the timed regions used
     how = f"{args.shard}-sharded x{world}"
@@ -672,10 +726,7 @@ def run(args, rank, world, local_rank, group, make_engine, weights, out=sys.stdo
     if rank == 0:
         tokens_per_launch = B * P * (hi - lo)
         roof = None
-        try:
-            build = eng.build_info()
-        except Exception:  # noqa: BLE001 - stand-in engines have no native library
-            build = None
+        build = build_of(eng)
         if prof.get("main", (0, 0))[0]:
             n_main, ms_main = prof["main"]
             avg_s = ms_main / n_main * 1e-3
@@ -693,30 +744,8 @@ def run(args, rank, world, local_rank, group, make_engine, weights, out=sys.stdo
                                 if not args.one_stream else "one stream (--one-stream)",
                     "note": "algorithmic flops (1 pass); the split-fp16 scheme issues 3 MFMA passes, "
                             "so frac tops out at 1/3"}
-        metric, workload = workload_label(N, L, args.ckpt)
-        line = {
-            "metric": metric,
-            "value": round(value, 3), "unit": "alignments/s", "n_gpus": n_devices, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f16x3-split MFMA (two fp16 limbs per operand, 3 passes), fp32 accumulate/residual", "data": "synthetic",
-            "config": {"workload": workload,
-                       "global_batch": B if args.shard == "sites" else B * world,
-                       "n_seqs": N, "n_sites": L, "parallelism": how,
-                       "device": info["name"].strip(),
-                       "n_ranks_in_comm": world if comm else 0,
-                       "communicators": 2 if comm else 0,
-                       "collectives_per_step": round(collectives_per_step, 2),
-                       "reserve_cus": args.reserve_cus if comm else None,
-                       "rccl_max_nchannels": os.environ.get("NCCL_MAX_NCHANNELS") if comm else None,
-                       "rung": rung_info(),
-                       # what the timed library was built from (pf_build_info): compiler, the scheduling strategy that
-                       # REALLY compiled the kernels (sched_fallback: true = hipcc could not use the intended one),
-                       # hashes of the sources
-                       "build": build},
-            "value_definition": "indices resident in HBM when the timed region starts (task statement, "
-                                "Measurement: the PCIe-inclusive rate is never `value`); value_pcie_inclusive is "
-                                "the rate SURVEY.md 8d words its metric on",
+        line = headline(args, eng, world, n_devices, B, N, L, dt, comm, comm_note, collectives_per_step, build)
+        line.update({
             "value_pcie_inclusive": round(total_alignments / dt_host, 3),
             "value_one_stream": round(total_alignments / dt_one, 3) if dt_one else None,
             "value_host_buffers": round(total_alignments / dt_host, 3),
@@ -728,15 +757,7 @@ def run(args, rank, world, local_rank, group, make_engine, weights, out=sys.stdo
             "power": sampler.summary() if sampler else None,
             "configs": extra_configs,
             "cpu_baseline": None,
-        }
-        if comm:
-            line["config"]["rccl"] = comm
-        if comm_note:
-            line["config"]["note"] = comm_note
-        if n_devices != world:
-            line["n_ranks"] = world
-            line["ranks_per_device"] = round(world / n_devices, 2)
-            line["scaling_result"] = False
+        })
         if world == 1 and not multi and not args.no_configs and make_engine_for is not None:
             eng.free(d_idx)
             eng.free(d_out)
@@ -771,6 +792,55 @@ def run(args, rank, world, local_rank, group, make_engine, weights, out=sys.stdo
     if not parity_ok and rank == 0:
         print(f"bench: PARITY FAILED: {json.dumps(parity)}", file=sys.stderr)
     return value, parity_ok
+
+
+def build_of(eng):
+    """What the engine's library was built from (pf_build_info), or None for a stand-in engine."""
+    try:
+        return eng.build_info()
+    except Exception:  # noqa: BLE001 - stand-in engines have no native library
+        return None
+
+
+def headline(args, eng, world, n_devices, B, N, L, dt, comm, comm_note, collectives_per_step, build):
+    """The keys of every line, plain or --full: the rate and the time of one step of the timed region, the
+    workload, the schedule and the library that ran."""
+    metric, workload = workload_label(N, L, args.ckpt)
+    global_batch = B if args.shard == "sites" else B * world
+    line = {
+        "metric": metric,
+        "value": round(global_batch * args.steps / dt, 3), "unit": "alignments/s", "n_gpus": n_devices,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f16x3-split MFMA (two fp16 limbs per operand, 3 passes), fp32 accumulate/residual", "data": "synthetic",
+        "full": bool(args.full),
+        "config": {"workload": workload,
+                   "global_batch": global_batch,
+                   "n_seqs": N, "n_sites": L, "parallelism": f"{args.shard}-sharded x{world}",
+                   "device": eng.device_info()["name"].strip(),
+                   "n_ranks_in_comm": world if comm else 0,
+                   "communicators": 2 if comm else 0,
+                   "collectives_per_step": round(collectives_per_step, 2),
+                   "reserve_cus": args.reserve_cus if comm else None,
+                   "rccl_max_nchannels": os.environ.get("NCCL_MAX_NCHANNELS") if comm else None,
+                   "rung": rung_info(),
+                   # what the timed library was built from (pf_build_info): compiler, the scheduling strategy that
+                   # REALLY compiled the kernels (sched_fallback: true = hipcc could not use the intended one),
+                   # hashes of the sources
+                   "build": build},
+        "value_definition": "indices resident in HBM when the timed region starts (task statement, "
+                            "Measurement: the PCIe-inclusive rate is never `value`); value_pcie_inclusive (--full) "
+                            "is the rate SURVEY.md 8d words its metric on",
+    }
+    if comm:
+        line["config"]["rccl"] = comm
+    if comm_note:
+        line["config"]["note"] = comm_note
+    if n_devices != world:
+        line["n_ranks"] = world
+        line["ranks_per_device"] = round(world / n_devices, 2)
+        line["scaling_result"] = False
+    return line
 
 
 # ---- self-launch: `python3 bench.py --gpus N` without a launcher -------------------------------------------

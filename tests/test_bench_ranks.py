@@ -22,7 +22,7 @@ def _worker(rank, world, key, tmp, fail_comm_on, q):
     import bench
     from phyloformer_amd.rendezvous import TcpGroup
     args = bench.parse_args(["--gpus", str(world), "--steps", "3", "--warmup", "1", "--batch", "2", "--n-seqs", "6",
-                             "--n-sites", "45", "--no-power"])
+                             "--n-sites", "45", "--no-power", "--full"])
     log, out = [], io.StringIO()
     with TcpGroup(rank, world, key=key, directory=tmp, timeout=30) as g:
         _value, ok = bench.run(args, rank, world, rank, g, lambda dev: FakeEngine(rank, log, fail_comm_on), _W(), out=out)
@@ -94,6 +94,50 @@ def test_bench_rank_logic_world2(fail_comm_on, tmp_path):
     assert line["parity"]["bound"] == 1e-4 and line["n_gpus"] == 2 and "scaling_result" not in line
 
 
+def test_a_plain_run_is_the_headline_and_the_outputs_of_its_last_step(tmp_path):
+    """Without --full a run sets up, warms up, times --steps steps, writes what the last timed step computed
+    (--dump-outputs) and prints the line: no other region, no parity leg, no other configuration, no baseline."""
+    sys.path.insert(0, REPO)
+    import bench
+    from helpers.fake_engine import FakeEngine, _answer
+    args = bench.parse_args(["--steps", "5", "--warmup", "2", "--batch", "3", "--n-seqs", "20", "--n-sites", "200",
+                             "--shard", "alignments", "--dump-outputs", str(tmp_path / "out")])
+    log, out = [], io.StringIO()
+
+    def no_other_engine(ckpt, device):
+        raise AssertionError("a plain run opened an engine for " + ckpt)
+    _value, ok = bench.run(args, 0, 1, 0, None, lambda dev: FakeEngine(0, log), _W(), out=out,
+                           make_engine_for=no_other_engine)
+    assert ok
+    assert [e for e in log if e[0] in ("plain", "sharded")] == [("plain", 3, 20, 200)] * 7      # 2 warm-up + 5 timed
+    assert not [e for e in log if e[0] == "opt" and e[1] == "profile"]
+    line = json.loads(out.getvalue())
+    assert line["steps"] == 5 and line["warmup"] == 2 and line["full"] is False and line["ms_per_step"] > 0
+    assert line["unit"] == "alignments/s" and line["higher_is_better"] is True and line["value"] > 0
+    assert line["metric"].startswith("alignments/sec, 20-leaf/200-site") and "fp16" in line["dtype"]
+    for key in ("roofline", "parity", "configs", "cpu_baseline", "power", "value_pcie_inclusive", "max_abs_err"):
+        assert key not in line, key
+    got = np.load(tmp_path / "out" / "distances.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, _answer(3, 20, 200))
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+def test_dumped_outputs_stay_under_64_mb_as_a_seeded_sample(tmp_path):
+    sys.path.insert(0, REPO)
+    import bench
+    big = np.arange(9 << 20, dtype=np.float64).reshape(-1, 1024)                  # 72 MiB, rows 0..9215
+    small = np.arange(6, dtype=np.int32).reshape(2, 3)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"big": big, "small": small})
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert np.array_equal(a, b) and a.dtype == np.float64 and 0 < a.shape[0] < big.shape[0]
+    assert a.nbytes + np.load(tmp_path / "a" / "small.npy").nbytes <= 64 << 20
+    rows = (a[:, 0] // 1024).astype(np.int64)
+    assert np.array_equal(a, big[rows]) and (np.diff(rows) > 0).all()              # whole rows, in order
+    assert np.load(tmp_path / "a" / "small.npy").dtype == np.float32
+
+
 def _run_bench(argv, env_extra, timeout=120):
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
@@ -109,7 +153,7 @@ def test_bench_self_launch_world2(fail_comm_on, tmp_path):
     ranks (fresh children, rendezvous over 127.0.0.1), relays rank 0's one JSON line and exits 0.  Fake engine:
     this is the launch / rank logic, not the GPU."""
     res = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "2", "--n-seqs", "6", "--n-sites", "45",
-                      "--no-power", "--launch-timeout", "60"],
+                      "--no-power", "--launch-timeout", "60", "--full"],
                      {"PF_BENCH_ENGINE_FACTORY": "helpers.fake_engine:make_for_bench", "PF_FAKE_LOG_DIR": str(tmp_path),
                       "PF_FAKE_FAIL_COMM_ON": fail_comm_on, "TMPDIR": str(tmp_path)})
     assert res.returncode == 0, res.stderr[-2000:]
@@ -224,7 +268,8 @@ def test_power_sampler_is_evidence_only():
     assert '"rocm-smi"' not in src and "['rocm-smi" not in src, "power is read in-process, not through the rocm-smi script"
 
 
-LADDER_ARGS = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2", "--n-seqs", "6", "--n-sites", "45", "--no-power"]
+LADDER_ARGS = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2", "--n-seqs", "6", "--n-sites", "45", "--no-power",
+               "--full"]
 
 
 def test_ladder_a_stalled_collective_falls_to_the_one_stream_rung(tmp_path):

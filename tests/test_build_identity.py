@@ -75,7 +75,7 @@ def test_fallback_build_is_marked_in_the_library_and_on_the_bench_line(fallback_
             return info
 
     args = bench.parse_args(["--steps", "2", "--warmup", "1", "--batch", "2", "--n-seqs", "6", "--n-sites", "45", "--no-power",
-                             "--no-parity", "--no-configs", "--no-cpu-baseline", "--shard", "alignments"])
+                             "--no-parity", "--no-configs", "--no-cpu-baseline", "--shard", "alignments", "--full"])
     out = io.StringIO()
     bench.run(args, 0, 1, 0, None, lambda dev: OnFallbackLibrary(0, []), FakeWeights(), out=out)
     line = json.loads(out.getvalue())

@@ -22,7 +22,7 @@ def _bench(argv, env_extra=None, timeout=600):
 
 
 GPUS2 = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2", "--n-seqs", "20", "--n-sites", "200",
-         "--no-cpu-baseline", "--no-power", "--launch-timeout", "300"]
+         "--no-cpu-baseline", "--no-power", "--launch-timeout", "300", "--full"]
 
 
 @pytest.mark.parametrize("pin", [True, False])
@@ -59,7 +59,7 @@ def test_bench_gpus2_shared_device_falls_back_together():
 def test_bench_force_dist_runs_fourteen_collectives():
     """The N > 1 code path of bench.py (rendezvous, two RCCL communicators, two streams) with one rank."""
     res = _bench(["--force-dist", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-power",
-                  "--batch", "4", "--n-seqs", "20", "--n-sites", "200"])
+                  "--batch", "4", "--n-seqs", "20", "--n-sites", "200", "--full"])
     assert res.returncode == 0, res.stderr[-3000:]
     line = json.loads(res.stdout.strip().splitlines()[-1])
     cfg = line["config"]
@@ -112,10 +112,9 @@ def test_two_engines_first_forward_from_two_threads(weights, golden):
 
 
 def test_bench_default_line_carries_the_contract():
-    """`python bench.py` as the driver runs it at N = 1 (shortened: 3 steps, no CPU baseline): ONE JSON line on
-    stdout with the contract's keys, the roofline object of the dominant kernel and every other BASELINE
-    configuration."""
-    res = _bench(["--steps", "3", "--warmup", "1", "--no-cpu-baseline"])
+    """`python bench.py --full` at N = 1 (shortened: 3 steps, no CPU baseline): ONE JSON line on stdout with the
+    contract's keys, the roofline object of the dominant kernel and every other BASELINE configuration."""
+    res = _bench(["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full"])
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, res.stdout[:2000]
@@ -144,6 +143,30 @@ def test_bench_default_line_carries_the_contract():
     print("parity on the bench line:", {k: c["max_abs_err"] for k, c in cases.items()})
 
 
+def test_bench_plain_run_dumps_the_same_outputs_every_time(engines, tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`, the run every change is measured with: the
+    headline line without the --full figures, and the distances of the last timed step - the same bits from a
+    second run with the same arguments, and what the engine computes for the same seeded alignments."""
+    from phyloformer_amd.msa_sim import simulate_batch
+    outs = []
+    for i in range(2):
+        res = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / f"run{i}")])
+        assert res.returncode == 0, res.stderr[-3000:]
+        lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, res.stdout[:2000]
+        d = json.loads(lines[0])
+        assert d["full"] is False and d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "alignments/s"
+        assert "60-leaf/500-site" in d["metric"] and d["higher_is_better"] is True and d["value"] > 0
+        assert abs(d["value"] * d["ms_per_step"] * 1e-3 - d["config"]["global_batch"]) < 0.02 * d["config"]["global_batch"]
+        assert "roofline" not in d and "parity" not in d and "cpu_baseline" not in d
+        outs.append(np.load(tmp_path / f"run{i}" / "distances.npy"))
+    assert outs[0].dtype == np.float32 and outs[0].shape == (16, 60 * 59 // 2)
+    assert np.isfinite(outs[0]).all() and (outs[0] > 0).all() and np.array_equal(outs[0], outs[1])
+    idx = simulate_batch(8, 60, 500, seed=3)                       # bench.py's inputs: 8 alignments, repeated to 16
+    want = engines("pf").forward(np.ascontiguousarray(idx[np.arange(16) % 8]))
+    assert float(np.abs(outs[0] - want).max()) <= 2e-5
+
+
 def test_bench_under_torchrun_two_ranks_share_the_gpu():
     """The task statement's N > 1 form - `python -m torch.distributed.run --nproc-per-node 2 ... bench.py --gpus 2` - on
     the 1-GPU box: torchrun's processes become supervisors (no HIP), their fresh children are the ranks; RCCL refuses
@@ -169,7 +192,7 @@ def test_bench_force_dist_one_stream_is_rung_two():
     """Rung 2 of the ladder (`--one-stream`: one stream, one communicator in use, serial collectives) with real
     single-rank RCCL: 7 collectives per step and per parity case, the same distances."""
     res = _bench(["--force-dist", "--one-stream", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-power",
-                  "--no-configs", "--batch", "4", "--n-seqs", "20", "--n-sites", "200"])
+                  "--no-configs", "--batch", "4", "--n-seqs", "20", "--n-sites", "200", "--full"])
     assert res.returncode == 0, res.stderr[-3000:]
     line = json.loads(res.stdout.strip().splitlines()[-1])
     assert line["config"]["collectives_per_step"] == 7 and "one stream" in line["roofline"]["schedule"]

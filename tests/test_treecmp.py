@@ -9,7 +9,9 @@ from phyloformer_amd import fasta, treecmp
 from phyloformer_amd.nj import neighbor_joining
 from phyloformer_amd.phylip import vec_to_matrix
 
-FASTME = "/root/reference/bin/bin_linux/fastme"
+# FastME --nni --spr trees of the README pipeline, stored by the sha256 of the PHYLIP text they were built from
+# (oracle/gen_golden_fastme.py, with the FastME binary of the reference checkout)
+FASTME_GOLDEN = "fastme_nni_spr.json"
 
 
 def test_newick_parser_and_splits():
@@ -102,40 +104,37 @@ def test_end_to_end_tree_check_on_reference_distances(repo, golden):
     assert rf == pytest.approx(11.4) and nrf == pytest.approx(0.1857, abs=5e-4) and kf == pytest.approx(0.3964, abs=5e-4)
 
 
-@pytest.mark.skipif(not os.path.exists(FASTME), reason="FastME binary of the reference checkout not present")
-def test_end_to_end_tree_check_with_fastme(repo, golden, tmp_path):
+def test_end_to_end_tree_check_with_fastme(repo, golden):
     """README.md:83-96 of the reference: FastME --nni --spr on the predicted matrices.  The README's
     'average KF 0.333' comes from `phylocompare`, which is missing from the checkout, so that figure is
-    unpinned; this pins the build's own comparison on the same pipeline instead."""
-    import subprocess
-    from phyloformer_amd.hostio import format_phylip
-
-    def fastme(dm, ids):
-        n = len(ids)
-        (tmp_path / "m.phy").write_bytes(format_phylip(dm[np.triu_indices(n, 1)], ids))
-        subprocess.run([FASTME, "-i", str(tmp_path / "m.phy"), "-o", str(tmp_path / "t.nwk"), "--nni", "--spr"],
-                       check=True, capture_output=True)
-        return (tmp_path / "t.nwk").read_text()
-    rf, nrf, kf = _tree_check(repo, golden, fastme)
+    unpinned; this pins the build's own comparison on the same pipeline instead (FastME's trees of exactly the
+    PHYLIP text this build writes, tests/golden/fastme_nni_spr.json)."""
+    rf, nrf, kf = _tree_check(repo, golden, _fastme_tree(repo))
     assert rf == pytest.approx(11.2) and nrf == pytest.approx(0.1837, abs=5e-4) and kf == pytest.approx(0.3935, abs=5e-4)
 
 
-def _fastme_tree(tmp_path, dm, ids):
-    import subprocess
+def _fastme_tree(repo):
+    """dm, ids -> the tree FastME --nni --spr built from this build's PHYLIP text of dm (looked up by its sha256:
+    a PHYLIP text FastME never saw is a KeyError, not another matrix's tree)."""
+    import hashlib
+    import json
     from phyloformer_amd.hostio import format_phylip
-    n = len(ids)
-    (tmp_path / "m.phy").write_bytes(format_phylip(dm[np.triu_indices(n, 1)], ids))
-    subprocess.run([FASTME, "-i", str(tmp_path / "m.phy"), "-o", str(tmp_path / "t.nwk"), "--nni", "--spr"],
-                   check=True, capture_output=True)
-    return (tmp_path / "t.nwk").read_text()
+    with open(os.path.join(repo, "tests", "golden", FASTME_GOLDEN)) as fh:
+        trees = json.load(fh)
+
+    def tree(dm, ids):
+        n = len(ids)
+        text = format_phylip(dm[np.triu_indices(n, 1)], ids)
+        return trees[hashlib.sha256(text).hexdigest()]["tree"]
+    return tree
 
 
-def test_gpu_distances_give_the_reference_distances_trees(repo, golden, tmp_path):
+def test_gpu_distances_give_the_reference_distances_trees(repo, golden):
     """tests/golden/gpu_distances_r02.npz = what `infer_alns.py models/pf.ckpt data/testdata/msas` wrote on an
     MI355X (round 2, as printed in the .phy files).  They differ from the reference's distances by at most
     1.2e-5, and the trees built from them are the trees built from the reference's: same neighbour-joining
-    topology and the same summary against the true trees - with the build's NJ here, and with the README's
-    FastME pipeline where the reference checkout (its binary) is present."""
+    topology and the same summary against the true trees - with the build's NJ, and with the README's
+    FastME pipeline (tests/golden/fastme_nni_spr.json)."""
     gpu, ref = golden("gpu_distances_r02.npz"), golden("e2e_testdata.npz")
     for name in sorted(os.listdir(os.path.join(repo, "data/testdata/msas"))):
         stem = name[:-3]
@@ -149,7 +148,5 @@ def test_gpu_distances_give_the_reference_distances_trees(repo, golden, tmp_path
         assert treecmp.branch_score(a, b) <= 2e-5, stem
     rf, nrf, kf = _tree_check(repo, golden, neighbor_joining, "gpu_distances_r02.npz", "{}")
     assert rf == pytest.approx(11.4) and nrf == pytest.approx(0.1857, abs=5e-4) and kf == pytest.approx(0.3964, abs=5e-4)
-    if os.path.exists(FASTME):
-        rf, nrf, kf = _tree_check(repo, golden, lambda dm, ids: _fastme_tree(tmp_path, dm, ids),
-                                  "gpu_distances_r02.npz", "{}")
-        assert rf == pytest.approx(11.2) and nrf == pytest.approx(0.1837, abs=5e-4) and kf == pytest.approx(0.3935, abs=5e-4)
+    rf, nrf, kf = _tree_check(repo, golden, _fastme_tree(repo), "gpu_distances_r02.npz", "{}")
+    assert rf == pytest.approx(11.2) and nrf == pytest.approx(0.1837, abs=5e-4) and kf == pytest.approx(0.3935, abs=5e-4)

@@ -2,7 +2,7 @@
 import json, os, subprocess, sys
 for name in sys.argv[1:]:
     env = dict(os.environ, PHYLOFORMER_AMD_LIB=os.path.abspath(os.path.join("phyloformer_amd", name)))
-    out = subprocess.run([sys.executable, "bench.py", "--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--no-power"],
+    out = subprocess.run([sys.executable, "bench.py", "--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--no-power", "--full"],
                          env=env, capture_output=True, text=True).stdout
     try:
         d = json.loads(out.strip().splitlines()[-1])
