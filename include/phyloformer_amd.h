@@ -68,8 +68,9 @@ typedef enum pf_status {
  *     then ffn_norm.weight [E], ffn_norm.bias [E],
  *       ffn.0.weight [4E][E], ffn.0.bias [4E], ffn.3.weight [E][4E], ffn.3.bias [E];
  *   pwFNN.0.weight [E], pwFNN.0.bias [1].
- * The kernels are specialised for E = 64, H = 4 (all shipped checkpoints);
- * other values are refused with PF_EINVAL. */
+ * Supported: n_alphabet 22, 1 <= n_blocks <= 64, 1 <= E <= 256 and E divisible by H (the reference's own
+ * rule); the FFN width is 4 E.  E = 64, H = 4 (all shipped checkpoints) runs on the default kernels; every other
+ * architecture on the generic float64 kernels (option "generic").  Anything else is refused with PF_EINVAL. */
 typedef struct pf_weights_t {
     int32_t n_blocks;
     int32_t n_heads;
@@ -96,7 +97,12 @@ const char* pf_build_info(void);
 
 /* Create a handle on HIP device `device`: uploads the weights, builds the
  * embedding table and the fp16 hi/lo MFMA operand images.  Fails with PF_EHIP
- * if no gfx950 device is present: there is no CPU fallback. */
+ * if no gfx950 device is present: there is no CPU fallback.
+ * An architecture outside the supported set (pf_weights_t) fails with PF_EINVAL before any device access
+ * ("embed_dim must be 1..256 and divisible by n_heads").  For E = 64, H = 4 the default and float64 "precise"
+ * images are built (the generic image waits for the first forward with option "generic" = 1); for any other
+ * supported architecture only the generic float64 image (csrc/pf_generic.hip.h) is built, and every forward entry
+ * point runs on the generic kernels. */
 int pf_create(const pf_weights_t* w, int device, pf_handle_t** out);
 int pf_destroy(pf_handle_t* h);
 const char* pf_last_error(const pf_handle_t* h);
@@ -135,6 +141,13 @@ const char* pf_last_error(const pf_handle_t* h);
  *                      (<= 5 on the reference's test data), uniformly random residues do not (9-13).  Per alignment,
  *                      never a function of the batch; pf_profile_get("rechecked") counts them.  The device entry
  *                      points do not re-check (their results never pass through the host).
+ *   "generic"    int   the generic float64 kernels (csrc/pf_generic.hip.h: any embed_dim / n_heads, reference op order,
+ *                      fp64 matrix cores).  On an E = 64, H = 4 handle: 0 (default) = the routing above, 1 = every
+ *                      forward on the generic kernels (cross-check against the shipped checkpoints; the image is built
+ *                      on the first such forward).  On any other handle they are the only path: 1 is accepted, 0 is
+ *                      refused with PF_EINVAL, and "precise" / "recheck_above" are accepted but have no effect (float64
+ *                      throughout needs neither).  Site-sharded runs issue n_blocks + 1 float64 all-reduces on one
+ *                      stream; batches are chunked under "ws_limit_mb"; pf_profile_get("generic") counts the launches.
  * Test / tool switches, not part of the contract:
  *   "colstats_ring" int  0 = k_colstats prefetches its rows through registers instead of the per-wave LDS ring (the
  *                      same bits; A/B and counter runs)

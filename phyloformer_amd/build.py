@@ -35,16 +35,18 @@ ARCH = "gfx950"
 # ahead of the MFMAs and is 1.3 % faster on the forward (k_colstats gains too).
 SCHED = ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
-# source -> extra flags.  pf_precise.hip (float64 kernels) and pf_mha.hip (softmax attention operator) are their own
+# source -> extra flags.  pf_precise.hip / pf_generic.hip (float64 kernels) and pf_mha.hip (softmax attention operator) are their own
 # translation units with the default strategy: iterative-ilp crashes hipcc's register allocator on them (ROCm 7.2,
 # kp_head / k_mha_qkv).
 UNITS: Dict[str, List[str]] = {
     "pf_lib.hip": [f"--offload-arch={ARCH}", "-fno-slp-vectorize"] + SCHED,
     "pf_precise.hip": [f"--offload-arch={ARCH}"],
+    "pf_generic.hip": [f"--offload-arch={ARCH}"],
     "pf_mha.hip": [f"--offload-arch={ARCH}", "-fno-slp-vectorize"],
     "pf_hostio.cpp": [],
 }
-HEADERS = ["pf_device.hip.h", "pf_mha.hip.h", "pf_precise.hip.h", "pf_precise_host.hip.h", "pf_layout.h", "pf_host_prep.h"]
+HEADERS = ["pf_device.hip.h", "pf_mha.hip.h", "pf_precise.hip.h", "pf_precise_host.hip.h", "pf_generic.hip.h",
+           "pf_generic_host.hip.h", "pf_layout.h", "pf_host_prep.h"]
 # what decides the bits and the speed of the dominant kernels (k_main, k_colstats): the PMC traffic file under
 # profiles/ is tied to this hash (bench.py: a mismatch means the counters are stale -> traffic null)
 KERNEL_FILES = ["pf_device.hip.h", "pf_layout.h"]

@@ -25,6 +25,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
@@ -34,6 +35,7 @@
 #include "pf_device.hip.h"
 #include "pf_mha.hip.h"
 #include "pf_precise.hip.h"
+#include "pf_generic.hip.h"
 #include "pf_host_prep.h"
 
 using namespace pfk;
@@ -132,8 +134,8 @@ struct BlockDev {
 
 struct ProfSlot { int kid; hipEvent_t a, b; };
 const char* const KNAMES[] = {"embed", "rowfin", "colstats", "colfin", "main", "allreduce",
-                              "mha_qkv", "mha_attn", "mha_out", "precise"};
-enum { K_EMBED = 0, K_ROWFIN, K_COLSTATS, K_COLFIN, K_MAIN, K_ALLREDUCE, K_MHA_QKV, K_MHA_ATTN, K_MHA_OUT, K_PRECISE, K_COUNT };
+                              "mha_qkv", "mha_attn", "mha_out", "precise", "generic"};
+enum { K_EMBED = 0, K_ROWFIN, K_COLSTATS, K_COLFIN, K_MAIN, K_ALLREDUCE, K_MHA_QKV, K_MHA_ATTN, K_MHA_OUT, K_PRECISE, K_GENERIC, K_COUNT };
 
 // weights of the float64 path (pf_precise.hip.h), widened and transposed at pf_create
 struct PreciseWeights {
@@ -141,6 +143,16 @@ struct PreciseWeights {
     const double* table = nullptr;                 // [22][64] relu(W + b), formed in double
     std::vector<pfp::AttnW> row, col;
     std::vector<pfp::FfnW> ffn;
+    const double *hw = nullptr, *hb = nullptr;
+};
+
+// weights of the generic path (pf_generic.hip.h): padded, widened, in A-fragment order; built at pf_create for
+// architectures other than (64, 4), on the first forced forward (option "generic") for (64, 4)
+struct GenericWeights {
+    bool ready = false;
+    const double* table = nullptr;                 // [22][Ep] relu(W + b), formed in double
+    std::vector<pfg::AttnW> row, col;
+    std::vector<pfg::FfnW> ffn;
     const double *hw = nullptr, *hb = nullptr;
 };
 
@@ -225,7 +237,14 @@ struct pf_handle {
     char f16_why[160] = {0};
     bool precise_ffn_valu = false;   // option "precise_ffn_valu": the float64 FFN on the VALU instead of the matrix cores (cross-check)
     PreciseWeights pw;
-    char* wsp = nullptr; size_t wsp_bytes = 0;
+    char* wsp = nullptr; size_t wsp_bytes = 0;     // workspace of the float64 paths (precise and generic)
+    // generic path (pf_generic.hip.h): arch_generic = the architecture is not (64, 4), every forward runs there;
+    // option "generic" = 1 sends a (64, 4) handle's forwards there too (its image is built from blob_copy then)
+    bool arch_generic = false;
+    int generic = 0;
+    pfg::Arch garch{};
+    GenericWeights gw;
+    std::vector<float> blob_copy;
     // sticky "residue byte > 21 seen" flag: pinned host memory the kernels write through its device alias
     unsigned* bad_idx_host = nullptr;
     unsigned* bad_idx_dev = nullptr;
@@ -839,6 +858,7 @@ int forward_chunk(pf_handle* h, const uint8_t* d_idx, int B, int N, int Lloc, in
 }
 
 #include "pf_precise_host.hip.h"
+#include "pf_generic_host.hip.h"
 
 int check_dims(pf_handle* h, int B, int N, int Lloc, int L_total) {
     if (!h) return PF_EINVAL;
@@ -914,6 +934,7 @@ int forward_device_impl(pf_handle* h, const uint8_t* d_idx, int B, int N, int l_
         // tests/test_gpu_sharding.py runs it on one GPU.)
         if (h->n_blocks == 0) return fail(h, PF_ESTATE, "handle was created without Phyloformer weights (pf_create_bare)");
         HIPCHK(h, hipSetDevice(h->device));
+        if (use_generic(h)) return forward_device_generic(h, d_idx, B, N, l_begin, l_end, L_total, d_out);
         if (use_precise(h, N, L_total)) return forward_device_precise(h, d_idx, B, N, l_begin, l_end, L_total, d_out);
         const int P0 = N * (N - 1) / 2;
         const int cb0 = chunk_batch(h, B, P0, (L_total + h->world - 1) / h->world);
@@ -957,6 +978,7 @@ int forward_device_impl(pf_handle* h, const uint8_t* d_idx, int B, int N, int l_
     if (rc) return rc;
     if (l_begin < 0 || l_end > L_total) return fail(h, PF_EINVAL, "site range [%d, %d) outside [0, %d)", l_begin, l_end, L_total);
     HIPCHK(h, hipSetDevice(h->device));
+    if (use_generic(h)) return forward_device_generic(h, d_idx, B, N, l_begin, l_end, L_total, d_out);
     if (use_precise(h, N, L_total)) return forward_device_precise(h, d_idx, B, N, l_begin, l_end, L_total, d_out);
     const int P = N * (N - 1) / 2;
     // every rank must cut the batch into the same chunks (one all-reduce sequence per chunk), so the
@@ -1015,7 +1037,7 @@ int forward_host_impl(pf_handle* h, const uint8_t* idx, int B, int N, int l_begi
         h->d_out_bytes = nout;
     }
     if (nidx) HIPCHK(h, hipMemcpyAsync(h->d_idx, idx, nidx, hipMemcpyHostToDevice, h->stream));
-    const bool default_kernels = !use_precise(h, N, L_total);
+    const bool default_kernels = !use_generic(h) && !use_precise(h, N, L_total);
     rc = forward_device_impl(h, h->d_idx, B, N, l_begin, l_end, L_total, h->d_out);
     if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(out, h->d_out, nout, hipMemcpyDeviceToHost, h->stream));
@@ -1132,10 +1154,11 @@ int pf_create_bare(int device, pf_handle_t** out) {
 int pf_create(const pf_weights_t* w, int device, pf_handle_t** out) {
     if (!w || !out || !w->blob) return fail(nullptr, PF_EINVAL, "null argument");
     *out = nullptr;
-    if (w->embed_dim != E || w->n_heads != NH || w->n_alphabet != NA || w->n_blocks < 1 || w->n_blocks > 64)
+    // (refused before any device access: the rule holds on a machine without a GPU too)
+    if (!generic_arch_ok(w))
         return fail(nullptr, PF_EINVAL,
                     "unsupported architecture: n_blocks=%d n_heads=%d embed_dim=%d n_alphabet=%d "
-                    "(kernels are specialised for n_heads=4, embed_dim=64, n_alphabet=22)",
+                    "(n_alphabet must be 22, n_blocks 1..64, embed_dim must be 1..256 and divisible by n_heads)",
                     w->n_blocks, w->n_heads, w->embed_dim, w->n_alphabet);
     if (w->blob_len != pf_blob_len(w->n_blocks, w->n_heads, w->embed_dim))
         return fail(nullptr, PF_EINVAL, "weight blob has %llu floats, expected %llu",
@@ -1145,8 +1168,19 @@ int pf_create(const pf_weights_t* w, int device, pf_handle_t** out) {
     int rc = open_device(device, &h);
     if (rc) return rc;
     h->n_blocks = w->n_blocks;
-    rc = prepare_weights(h, w);
-    if (!rc) rc = prepare_precise_weights(h, w, &h->pw);
+    h->garch = pfg::make_arch(w->embed_dim, w->n_heads);
+    if (w->embed_dim == E && w->n_heads == NH) {
+        // the default and precise kernels; the generic image waits for the first forward with option "generic" = 1
+        rc = prepare_weights(h, w);
+        if (!rc) rc = prepare_precise_weights(h, w, &h->pw);
+        if (!rc) {
+            try { h->blob_copy.assign(w->blob, w->blob + w->blob_len); }
+            catch (const std::bad_alloc&) { rc = fail(h, PF_ENOMEM, "out of host memory copying the weights"); }
+        }
+    } else {
+        h->arch_generic = true;          // the kernels of the other two paths are specialised for (64, 4)
+        rc = prepare_generic_weights(h, w->blob);
+    }
     if (rc) g_create_error = h->err;
     if (rc) { pf_destroy(h); return rc; }
     *out = h;
@@ -1198,6 +1232,12 @@ int pf_set_option(pf_handle_t* h, const char* key, int64_t value) {
     else if (k == "precise") h->precise = value < 0 ? -1 : (value != 0);
     else if (k == "recheck_above") h->recheck_above = value > 0 ? (double)value : 0.0;
     else if (k == "precise_ffn_valu") h->precise_ffn_valu = value != 0;
+    else if (k == "generic") {
+        if (h->arch_generic && !value)
+            return fail(h, PF_EINVAL, "embed_dim %d / n_heads %d runs on the generic kernels only (option generic cannot be 0)",
+                        h->garch.E, h->garch.NH);
+        h->generic = value != 0;
+    }
     else if (k == "phase_prof") {
         if (value && !h->phase_prof) { HIPCHK(h, hipMalloc((void**)&h->phase_prof, 64)); h->owned.push_back(h->phase_prof); }
         if (h->phase_prof) HIPCHK(h, hipMemset(h->phase_prof, 0, 64));
@@ -1421,6 +1461,7 @@ int pf_forward_shards_emulated(pf_handle_t* h, const uint8_t* idx, int32_t B, in
     if (rc) return rc;
     if (nshards < 1 || nshards > 64 || !idx || !out) return fail(h, PF_EINVAL, "bad shard count or null buffer");
     HIPCHK(h, hipSetDevice(h->device));
+    if (use_generic(h)) return forward_shards_emulated_generic(h, idx, B, N, L, nshards, out);
     if (use_precise(h, N, L)) return forward_shards_emulated_precise(h, idx, B, N, L, nshards, out);
     if ((rc = ensure_pairs(h, N))) return rc;
     const int P = N * (N - 1) / 2;

@@ -159,6 +159,13 @@ class Engine:
         self.device = device
         self.world = 1
         self.rank = 0
+        self._arch = (int(weights.n_blocks), int(weights.n_heads), int(weights.embed_dim))
+
+    @property
+    def architecture(self) -> Tuple[int, int, int]:
+        """``(n_blocks, n_heads, embed_dim)`` of the weights this handle was created with.  Anything but
+        ``(n, 4, 64)`` runs on the generic float64 kernels (option "generic" in include/phyloformer_amd.h)."""
+        return self._arch
 
     # -- plumbing ---------------------------------------------------------------------------
     def _check(self, rc: int):
