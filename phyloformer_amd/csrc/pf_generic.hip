@@ -1,5 +1,5 @@
 // Kernels of the GENERIC (float64, any embed_dim / n_heads) path; rationale and layouts: pf_generic.hip.h, the
-// host-side sequence: pf_generic_host.hip.h.
+// host-side sequence: pf_f64_host.hip.h.
 #include "pf_generic.hip.h"
 
 namespace pfg {

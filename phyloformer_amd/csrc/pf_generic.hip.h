@@ -88,7 +88,8 @@ size_t ffn_lds(const Arch& a);
 // raise the kernels' dynamic-LDS limit to the supported set's worst case (before the first launch)
 hipError_t set_lds_limits();
 
-// Launchers (own translation unit: see phyloformer_amd/build.py).  Asynchronous on `s`.
+// Launchers (own translation unit: see phyloformer_amd/build.py).  Asynchronous on `s`.  launch_stats_fin, launch_out,
+// launch_accumulate and launch_narrow serve both float64 paths (the precise one with SR = 72, Ep = E = 64).
 void launch_embed(hipStream_t s, size_t grid, const EmbedArgs& a);
 void launch_attn_stats(hipStream_t s, size_t nblocks, const StatsArgs& a);
 void launch_stats_fin(hipStream_t s, const double* part, double* stats, int nlines, int nchunk, int SR);

@@ -857,8 +857,49 @@ int forward_chunk(pf_handle* h, const uint8_t* d_idx, int B, int N, int Lloc, in
     return PF_OK;
 }
 
-#include "pf_precise_host.hip.h"
-#include "pf_generic_host.hip.h"
+// Shard emulation's common part (pf_forward_shards_emulated and its float64 twin): the site ranges of
+// phyloformer_amd/dist.py::site_range, each non-empty shard's idx[b][n][lo:hi] uploaded (an empty shard contributes
+// zeros to every sum and is skipped), and on every exit a stream sync, the device allocations freed and debug_keep,
+// off while emulating, restored.
+struct ShardStage {
+    struct Shard { int Lloc; const uint8_t* d_idx; };
+    pf_handle* h;
+    const bool keep;
+    std::vector<void*> allocs;
+    std::vector<Shard> shards;
+    explicit ShardStage(pf_handle* h_) : h(h_), keep(h_->debug_keep) { h->debug_keep = false; }
+    ShardStage(const ShardStage&) = delete;
+    ~ShardStage() {
+        hipStreamSynchronize(h->stream);
+        for (void* p : allocs) hipFree(p);
+        h->debug_keep = keep;
+    }
+    void* alloc(size_t bytes) {
+        void* p = nullptr;
+        if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) return nullptr;
+        allocs.push_back(p);
+        return p;
+    }
+    int upload(const uint8_t* idx, int B, int N, int L, int nshards) {
+        const int step = (L + nshards - 1) / nshards;
+        for (int s = 0; s < nshards; ++s) {
+            const int lo = std::min(s * step, L), hi = std::min((s + 1) * step, L);
+            if (hi <= lo) continue;
+            const int Lloc = hi - lo;
+            uint8_t* di = (uint8_t*)alloc((size_t)B * N * Lloc);
+            if (!di) return fail(h, PF_ENOMEM, "shard workspace allocation failed");
+            std::vector<uint8_t> local((size_t)B * N * Lloc);
+            for (int b = 0; b < B; ++b)
+                for (int n = 0; n < N; ++n)
+                    std::memcpy(&local[((size_t)b * N + n) * Lloc], &idx[((size_t)b * N + n) * L + lo], Lloc);
+            if (hipMemcpy(di, local.data(), local.size(), hipMemcpyHostToDevice) != hipSuccess) return fail(h, PF_EHIP, "idx upload failed");
+            shards.push_back({Lloc, di});
+        }
+        return PF_OK;
+    }
+};
+
+#include "pf_f64_host.hip.h"
 
 int check_dims(pf_handle* h, int B, int N, int Lloc, int L_total) {
     if (!h) return PF_EINVAL;
@@ -934,8 +975,7 @@ int forward_device_impl(pf_handle* h, const uint8_t* d_idx, int B, int N, int l_
         // tests/test_gpu_sharding.py runs it on one GPU.)
         if (h->n_blocks == 0) return fail(h, PF_ESTATE, "handle was created without Phyloformer weights (pf_create_bare)");
         HIPCHK(h, hipSetDevice(h->device));
-        if (use_generic(h)) return forward_device_generic(h, d_idx, B, N, l_begin, l_end, L_total, d_out);
-        if (use_precise(h, N, L_total)) return forward_device_precise(h, d_idx, B, N, l_begin, l_end, L_total, d_out);
+        if (const F64Path* f = f64_path_of(h, N, L_total)) return forward_device_f64(h, *f, d_idx, B, N, l_begin, l_end, L_total, d_out);
         const int P0 = N * (N - 1) / 2;
         const int cb0 = chunk_batch(h, B, P0, (L_total + h->world - 1) / h->world);
         ForwardScope scope(h, true);
@@ -978,8 +1018,7 @@ int forward_device_impl(pf_handle* h, const uint8_t* d_idx, int B, int N, int l_
     if (rc) return rc;
     if (l_begin < 0 || l_end > L_total) return fail(h, PF_EINVAL, "site range [%d, %d) outside [0, %d)", l_begin, l_end, L_total);
     HIPCHK(h, hipSetDevice(h->device));
-    if (use_generic(h)) return forward_device_generic(h, d_idx, B, N, l_begin, l_end, L_total, d_out);
-    if (use_precise(h, N, L_total)) return forward_device_precise(h, d_idx, B, N, l_begin, l_end, L_total, d_out);
+    if (const F64Path* f = f64_path_of(h, N, L_total)) return forward_device_f64(h, *f, d_idx, B, N, l_begin, l_end, L_total, d_out);
     const int P = N * (N - 1) / 2;
     // every rank must cut the batch into the same chunks (one all-reduce sequence per chunk), so the
     // chunk size is derived from the largest shard, not from this rank's own
@@ -1037,7 +1076,7 @@ int forward_host_impl(pf_handle* h, const uint8_t* idx, int B, int N, int l_begi
         h->d_out_bytes = nout;
     }
     if (nidx) HIPCHK(h, hipMemcpyAsync(h->d_idx, idx, nidx, hipMemcpyHostToDevice, h->stream));
-    const bool default_kernels = !use_generic(h) && !use_precise(h, N, L_total);
+    const bool default_kernels = !f64_path_of(h, N, L_total);
     rc = forward_device_impl(h, h->d_idx, B, N, l_begin, l_end, L_total, h->d_out);
     if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(out, h->d_out, nout, hipMemcpyDeviceToHost, h->stream));
@@ -1065,7 +1104,7 @@ int forward_host_impl(pf_handle* h, const uint8_t* idx, int B, int N, int l_begi
             for (size_t i = 0; i < nr; ++i)
                 if (per) std::memcpy(&sub[i * per], idx + (size_t)redo[i] * per, per);
             if (per) HIPCHK(h, hipMemcpyAsync(h->d_idx, sub.data(), nr * per, hipMemcpyHostToDevice, h->stream));
-            rc = forward_device_precise(h, per ? h->d_idx : nullptr, (int)nr, N, l_begin, l_end, L_total, h->d_out);
+            rc = forward_device_f64(h, PRECISE_F64, per ? h->d_idx : nullptr, (int)nr, N, l_begin, l_end, L_total, h->d_out);
             if (rc) return rc;
             HIPCHK(h, hipMemcpyAsync(res.data(), h->d_out, nr * (size_t)P * sizeof(float), hipMemcpyDeviceToHost, h->stream));
             HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1461,46 +1500,32 @@ int pf_forward_shards_emulated(pf_handle_t* h, const uint8_t* idx, int32_t B, in
     if (rc) return rc;
     if (nshards < 1 || nshards > 64 || !idx || !out) return fail(h, PF_EINVAL, "bad shard count or null buffer");
     HIPCHK(h, hipSetDevice(h->device));
-    if (use_generic(h)) return forward_shards_emulated_generic(h, idx, B, N, L, nshards, out);
-    if (use_precise(h, N, L)) return forward_shards_emulated_precise(h, idx, B, N, L, nshards, out);
+    if (const F64Path* f = f64_path_of(h, N, L)) return forward_shards_emulated_f64(h, *f, idx, B, N, L, nshards, out);
     if ((rc = ensure_pairs(h, N))) return rc;
     const int P = N * (N - 1) / 2;
-    const int step = (L + nshards - 1) / nshards;
+    ShardStage stage(h);
+    if ((rc = stage.upload(idx, B, N, L, nshards))) return rc;
     std::vector<ShardRun> runs;
-    std::vector<void*> allocs;
-    auto cleanup = [&]() { hipStreamSynchronize(h->stream); for (void* p : allocs) hipFree(p); };
-    for (int sidx = 0; sidx < nshards; ++sidx) {
-        const int lo = std::min(sidx * step, (int)L), hi = std::min((sidx + 1) * step, (int)L);
-        if (hi <= lo) continue;   // an empty rank contributes zeros to both sums
+    for (const ShardStage::Shard& s : stage.shards) {
         ShardRun r{};
-        r.B = B; r.N = N; r.P = P; r.Lloc = hi - lo; r.L_total = L;
+        r.B = B; r.N = N; r.P = P; r.Lloc = s.Lloc; r.L_total = L;
         size_t off[WS_BUFS];
         colstats_plan(h, B, P, r.Lloc, &r.w);
         r.tp = tile_plan(h, P, r.Lloc);
-        const size_t need = workspace_bytes(h, B, P, r.Lloc, r.w.nparts(), off);
-        char* ws = nullptr; uint8_t* di = nullptr; float* dout = nullptr;
-        hipError_t e1 = hipMalloc((void**)&ws, need), e2 = hipMalloc((void**)&di, (size_t)B * N * r.Lloc),
-                   e3 = hipMalloc((void**)&dout, (size_t)B * P * sizeof(float));
-        if (ws) allocs.push_back(ws); if (di) allocs.push_back(di); if (dout) allocs.push_back(dout);
-        if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) { cleanup(); return fail(h, PF_ENOMEM, "shard workspace allocation failed"); }
+        char* ws = (char*)stage.alloc(workspace_bytes(h, B, P, r.Lloc, r.w.nparts(), off));
+        float* dout = (float*)stage.alloc((size_t)B * P * sizeof(float));
+        if (!ws || !dout) return fail(h, PF_ENOMEM, "shard workspace allocation failed");
         r.w.x = (float*)(ws + off[0]); r.w.qrow = (float*)(ws + off[1]); r.w.qcol = (float*)(ws + off[2]);
         r.w.srow = (float*)(ws + off[3]); r.w.mrow = (float*)(ws + off[4]); r.w.part = (float*)(ws + off[5]);
         r.w.ctx = (float*)(ws + off[6]); r.w.mfrag = (float*)(ws + off[7]);
         r.w.spart = (float*)(ws + off[8]); r.w.outpart = (float*)(ws + off[9]);
         r.w.rq = (float*)(ws + off[10]);
-        std::vector<uint8_t> local((size_t)B * N * r.Lloc);
-        for (int b = 0; b < B; ++b)
-            for (int n = 0; n < N; ++n)
-                std::memcpy(&local[((size_t)b * N + n) * r.Lloc], &idx[((size_t)b * N + n) * L + lo], r.Lloc);
-        if (hipMemcpy(di, local.data(), local.size(), hipMemcpyHostToDevice) != hipSuccess) { cleanup(); return fail(h, PF_EHIP, "idx upload failed"); }
-        r.d_idx = di; r.d_out = dout;
+        r.d_idx = s.d_idx; r.d_out = dout;
         runs.push_back(r);
     }
-    const bool keep = h->debug_keep;
-    h->debug_keep = false;
-    float* total = nullptr;   // the "all-reduced" buffer every emulated rank reads
-    if (hipMalloc((void**)&total, (size_t)B * P * SROW * sizeof(float)) != hipSuccess) { cleanup(); return fail(h, PF_ENOMEM, "shard sum buffer"); }
-    allocs.push_back(total);
+    // the "all-reduced" buffer every emulated rank reads
+    float* total = (float*)stage.alloc((size_t)B * P * SROW * sizeof(float));
+    if (!total) return fail(h, PF_ENOMEM, "shard sum buffer");
     auto sum_all = [&](size_t count, bool is_out) {
         hipMemsetAsync(total, 0, count * sizeof(float), h->stream);
         for (auto& r : runs)
@@ -1524,8 +1549,6 @@ int pf_forward_shards_emulated(pf_handle_t* h, const uint8_t* idx, int32_t B, in
             hipStreamSynchronize(h->stream) != hipSuccess)
             rc = fail(h, PF_EHIP, "result copy failed");
     }
-    h->debug_keep = keep;
-    cleanup();
     return rc;
 }
 

@@ -1,5 +1,5 @@
 // Kernels of the PRECISE (float64) path; rationale, layout and the host-side sequence: pf_precise.hip.h,
-// pf_precise_host.hip.h.
+// pf_f64_host.hip.h.  The tail kernels (statistics finish, out, shard sums, taps) are pf_generic.hip's.
 #include "pf_precise.hip.h"
 
 namespace pfp {
@@ -177,16 +177,6 @@ __global__ void __launch_bounds__(PT) kp_attn_stats_mfma(StatsArgs a) {
     if (tid < SROW) a.part[((size_t)line * a.nchunk + ch) * SROW + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
 }
 
-// part[line][nchunk][72] -> stats[line][72], chunks in index order
-__global__ void __launch_bounds__(PT) kp_stats_fin(const double* part, double* stats, int nlines, int nchunk) {
-    const int i = blockIdx.x * PT + threadIdx.x;
-    if (i >= nlines * SROW) return;
-    const int line = i / SROW, j = i - line * SROW;
-    double s = 0.0;
-    for (int c = 0; c < nchunk; ++c) s += part[((size_t)line * nchunk + c) * SROW + j];
-    stats[i] = s;
-}
-
 // ---- attention apply (attention.py:183-195) + residual --------------------------------------------
 // o[h, d] = q'[h] / (S_q[h] / count) * S_kv[h, d] / S_k[h];  y = Wo o + bo;  x += y.
 // The line's mix M[h][c] = sum_d Wo[c][16 h + d] ctx[16 h + d], ctx = S_kv / S_k / (S_q / count), is formed once
@@ -269,7 +259,7 @@ __global__ void __launch_bounds__(PT) kp_ffn(FfnArgs a) {
 //   GEMM2  K step (T, r) takes hidden unit 16 T + kq + 4 r from lane group kq  -> B operand = GELU of D register r
 //   GEMM2  D tile Tc: row i stands for channel 16 (i & 3) + 4 Tc + (i >> 2), so register r of lane (g, j) is channel
 //          16 g + 4 Tc + r: the residual's own layout
-// (the A fragments are packed accordingly on the host, pf_precise_host.hip.h).  512 MFMAs per 16 tokens; the
+// (the A fragments are packed accordingly on the host, pf_f64_host.hip.h).  512 MFMAs per 16 tokens; the
 // 256 erf evaluations per token run on the VALU beside another wave's MFMAs.
 // erf-GELU in double without ocml's erf (four divergent ranges, ~2,000 cycles per wave: it was 70 % of the FFN kernel):
 //   gelu(h) = max(h, 0) - |h| Q(|h|),  Q(u) = erfc(u / sqrt 2) / 2 = exp(-u^2 / 2) R(u),
@@ -383,28 +373,11 @@ __global__ void __launch_bounds__(PT) kp_head(HeadArgs a) {
     }
     if (lane == 0) a.osum[line] = acc;
 }
-__global__ void __launch_bounds__(PT) kp_out(const double* osum, float* out, int n, double l_total) {
-    const int i = blockIdx.x * PT + threadIdx.x;
-    if (i < n) out[i] = (float)(osum[i] / l_total);               // model.py:185: mean over ALL sites
-}
-__global__ void __launch_bounds__(PT) kp_accumulate(double* dst, const double* src, size_t n) {   // shard emulation
-    const size_t i = (size_t)blockIdx.x * PT + threadIdx.x;
-    if (i < n) dst[i] += src[i];
-}
-__global__ void __launch_bounds__(PT) kp_to_float(const double* src, float* dst, size_t n) {      // debug taps
-    const size_t i = (size_t)blockIdx.x * PT + threadIdx.x;
-    if (i < n) dst[i] = (float)src[i];
-}
 
-
-#define PFP_GRID(n) dim3((unsigned)(((n) + PT - 1) / PT))
 void launch_embed(hipStream_t s, size_t grid, const EmbedArgs& a) { hipLaunchKernelGGL(kp_embed, dim3((unsigned)grid), dim3(PT), 0, s, a); }
 void launch_attn_stats(hipStream_t s, size_t grid, const StatsArgs& a, bool valu) {
     if (valu) hipLaunchKernelGGL(kp_attn_stats, dim3((unsigned)grid), dim3(PT), 0, s, a);
     else hipLaunchKernelGGL(kp_attn_stats_mfma, dim3((unsigned)grid), dim3(PT), 0, s, a);
-}
-void launch_stats_fin(hipStream_t s, const double* part, double* stats, int nlines, int nchunk) {
-    hipLaunchKernelGGL(kp_stats_fin, PFP_GRID((size_t)nlines * SROW), dim3(PT), 0, s, part, stats, nlines, nchunk);
 }
 void launch_attn_apply(hipStream_t s, size_t grid, const ApplyArgs& a) { hipLaunchKernelGGL(kp_attn_apply, dim3((unsigned)grid), dim3(PT), 0, s, a); }
 void launch_ffn(hipStream_t s, const FfnArgs& a, bool valu) {
@@ -412,10 +385,5 @@ void launch_ffn(hipStream_t s, const FfnArgs& a, bool valu) {
     else hipLaunchKernelGGL(kp_ffn_mfma, dim3((unsigned)((a.ntok + 63) / 64)), dim3(PT), 0, s, a);
 }
 void launch_head(hipStream_t s, const HeadArgs& a) { hipLaunchKernelGGL(kp_head, dim3((unsigned)((a.nlines + 3) / 4)), dim3(PT), 0, s, a); }
-void launch_out(hipStream_t s, const double* osum, float* out, int n, double l_total) {
-    hipLaunchKernelGGL(kp_out, PFP_GRID((size_t)n), dim3(PT), 0, s, osum, out, n, l_total);
-}
-void launch_accumulate(hipStream_t s, double* dst, const double* src, size_t n) { hipLaunchKernelGGL(kp_accumulate, PFP_GRID(n), dim3(PT), 0, s, dst, src, n); }
-void launch_to_float(hipStream_t s, const double* src, float* dst, size_t n) { hipLaunchKernelGGL(kp_to_float, PFP_GRID(n), dim3(PT), 0, s, src, dst, n); }
 
 }  // namespace pfp

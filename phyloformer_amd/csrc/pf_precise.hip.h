@@ -7,7 +7,7 @@
 // 2^-17-per-operand products add 1e-4 ... 2e-3 on top.  No fp32 formulation can promise to sit within a fixed bound
 // of another fp32 formulation on such input (both are a rounding cloud around the exact value); float64 sits at
 // the cloud's centre, so its distance to the reference is the reference's own rounding error and nothing else.
-// The host selects this path from the alignment's SHAPE only (pf_lib.hip::use_precise), never from the batch, so
+// The host selects this path from the alignment's SHAPE only (pf_f64_host.hip.h::use_precise), never from the batch, so
 // an alignment gets the same bits wherever it travels.  Fixed-order sums, no atomics.
 //
 // Arithmetic follows the reference's own op order (un-collapsed LayerNorm affine, separate q / k / v / out
@@ -81,12 +81,8 @@ struct HeadArgs { const double* x; const double* hw; const double* hb; double* o
 // grid = number of 256-thread blocks; asynchronous on `s`.
 void launch_embed(hipStream_t s, size_t grid, const EmbedArgs& a);
 void launch_attn_stats(hipStream_t s, size_t grid, const StatsArgs& a, bool valu);    // a.nchunk chunks of CHUNK (valu) / CHUNK_MFMA
-void launch_stats_fin(hipStream_t s, const double* part, double* stats, int nlines, int nchunk);
 void launch_attn_apply(hipStream_t s, size_t grid, const ApplyArgs& a);
 void launch_ffn(hipStream_t s, const FfnArgs& a, bool valu);      // valu: the cross-check kernel instead of the MFMA one
 void launch_head(hipStream_t s, const HeadArgs& a);
-void launch_out(hipStream_t s, const double* osum, float* out, int n, double l_total);
-void launch_accumulate(hipStream_t s, double* dst, const double* src, size_t n);
-void launch_to_float(hipStream_t s, const double* src, float* dst, size_t n);
 
 }  // namespace pfp

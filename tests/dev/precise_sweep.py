@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """GPU box: where does the DEFAULT (split-bf16) path lose the 1e-4 bound?  Sweeps small shapes with the float64 path
 switched off (precise = 0) and prints, per (N, L), the worst |GPU - fp32 oracle|, |fp32 oracle - fp64 oracle| and
-|GPU - fp64 oracle| over checkpoints / seeds / input kinds.  The thresholds of pf_precise_host.hip.h::use_precise come
+|GPU - fp64 oracle| over checkpoints / seeds / input kinds.  The thresholds of pf_f64_host.hip.h::use_precise come
 from this table (profiles/r05_precise_sweep.txt).
     python tests/dev/precise_sweep.py [out.json]"""
 import json, os, sys, time

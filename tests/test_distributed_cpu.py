@@ -78,7 +78,7 @@ def test_site_sharded_ranks_match_unsharded(world, L, weights):
 
 
 def test_float64_ranks_match_the_float64_forward(weights):
-    """The float64 path's collective schedule (csrc/pf_precise_host.hip.h: n_blocks double all-reduces of [P, 72] and one
+    """The float64 path's collective schedule (csrc/pf_f64_host.hip.h: n_blocks double all-reduces of [P, 72] and one
     of [P], never cut into halves) at world 2 with real gloo all-reduces of doubles: 7 x 45 sites split 23 + 22, every
     rank ends with the unsharded float64 forward to 1e-12."""
     import torch.multiprocessing as mp

@@ -146,7 +146,7 @@ def test_checkpoint_outside_the_fp16_operand_ranges_runs_in_float64(weights):
 
 
 def _routed_to_float64(n, l):
-    return l < 32 or n * (n - 1) // 2 * l < 8192                  # pf_precise_host.hip.h::use_precise
+    return l < 32 or n * (n - 1) // 2 * l < 8192                  # pf_f64_host.hip.h::use_precise
 
 
 def _soak_cases(n_cases, seed):
