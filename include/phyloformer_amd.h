@@ -176,6 +176,25 @@ int pf_forward(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, int32_t
 int pf_forward_device(pf_handle_t* h, const uint8_t* d_idx, int32_t B, int32_t N, int32_t L,
                       float* d_out);
 
+/* ---- Felsenstein's bootstrap over alignment sites (additive to ABI 5) ------------------------------
+ *
+ * The replicate stream: replicate r (0-based) of an alignment of L sites takes, at output position l, the source site
+ *   mix64(z) = SplitMix64's finaliser (z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB;
+ *              z ^= z >> 31, mod 2^64);  key = mix64(seed + 0x9E3779B97F4A7C15);
+ *   site = ((mix64(key ^ ((r << 32) | l)) >> 32) * L) >> 32.
+ * It depends on (seed, r, l, L) only (phyloformer_amd/bootstrap.py::resample_sites is its host twin). */
+/* d_src uint8 [B][N][L] -> d_dst uint8 [B][R][N][L], replicates r_begin .. r_begin+R-1 of the stream above; async. */
+int pf_resample_sites_device(pf_handle_t* h, const uint8_t* d_src, int32_t B, int32_t N, int32_t L,
+                             int32_t r_begin, int32_t R, uint64_t seed, uint8_t* d_dst);
+/* idx host uint8 [B][N][L] -> out host float [B][R][P]: the distances of R bootstrap replicates of every alignment.
+ * Synchronous.  out[b][r] equals, bit for bit, pf_forward of the host-resampled replicate r of idx[b], on the path
+ * pf_forward would take (options "precise", "generic", "ws_limit_mb", "max_seqs" and the range re-check
+ * "recheck_above" per replicate included) for any B, R and chunking.  The sources are uploaded once; replicate bytes
+ * are built on the device one forward chunk at a time.  Validated before any device work, with pf_forward's
+ * messages, plus R >= 1 and no size_t overflow of B*R*P or B*R*N*L.  Never communicates. */
+int pf_bootstrap(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, int32_t L, int32_t R,
+                 uint64_t seed, float* out);
+
 /* Site-sharded forward: this rank holds sites [l_begin, l_end) of an alignment
  * with L_total sites.  idx: host uint8 [B][N][l_end - l_begin].  Every rank
  * receives the full result in out [B][P].  The row-attention statistics are all-reduced once per
@@ -218,8 +237,8 @@ int pf_memcpy_h2d(pf_handle_t* h, void* dst, const void* src, size_t bytes);
 int pf_memcpy_d2h(pf_handle_t* h, void* dst, const void* src, size_t bytes);
 
 /* Per-kernel HIP-event timing ("profile" = 1).  Names: "embed", "rowfin",
- * "colstats", "colfin", "main", "allreduce", "mha_qkv", "mha_attn", "mha_out".  Totals accumulate
- * until reset.  "collectives" returns the number of all-reduces issued since the last reset in
+ * "colstats", "colfin", "main", "allreduce", "mha_qkv", "mha_attn", "mha_out", "precise", "generic",
+ * "resample" (k_resample of pf_bootstrap / pf_resample_sites_device).  Totals accumulate until reset.  "collectives" returns the number of all-reduces issued since the last reset in
  * *launches (counted always, no profiling option needed; *total_ms = 0); "rechecked" likewise the number of
  * alignments the range re-check (option "recheck_above") computed again on the float64 kernels. */
 int pf_profile_reset(pf_handle_t* h);

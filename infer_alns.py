@@ -15,7 +15,8 @@ process per GPU; ``--shard files`` - the default - deals the files to the GPUs, 
 spreads every alignment over them: each rank holds a block of sites, RCCL all-reduces inside
 ``pf_forward_sharded``, rank 0 writes the outputs), ``--batch`` (same-shape alignments per launch;
 default: fill a token budget per shape), ``--io-threads``, ``--gpu-streams``, ``--precise``, ``--python-io``,
-``--bench`` (print a JSON timing line).  Scheduling lives in
+``--bench`` (print a JSON timing line), ``--bootstrap R`` / ``--seed S`` (``OUTDIR/<stem>.sup.nwk``: the NJ tree with
+site-bootstrap supports, R replicates resampled and inferred on the GPU; not with ``--shard sites``).  Scheduling lives in
 ``phyloformer_amd/scheduler.py``: files are bucketed by shape, parsed ahead of the
 GPU and written behind it.  A directory entry without a FASTA extension, or a file that does
 not parse, has the reference's side effects (infer_alns.py:97-117): every entry in front of it
@@ -66,6 +67,13 @@ def build_parser():
                              "ill-conditioned) and, after the fact, for any alignment with a predicted distance above 8 substitutions per "
                              "site (never an alignment; an absolute 1e-4 there is fp32's own rounding level); always = every alignment (3-9 x slower); never = the split-fp16 MFMA kernels "
                              "on every shape")
+    parser.add_argument("--bootstrap", type=int, default=0, metavar="R",
+                        help="site-bootstrap replicates per alignment, resampled and inferred on the GPU: writes "
+                             "<stem>.sup.nwk, the NJ tree of the alignment's distances with the percent of replicate "
+                             "trees that contain each internal branch's split; 0 (default) = off")
+    parser.add_argument("--seed", type=int, default=0,
+                        help="seed of the bootstrap replicate stream (default 0): a file's supports depend on the "
+                             "weights, the alignment, R and the seed only")
     parser.add_argument("--python-io", action="store_true",
                         help="use the pure-Python FASTA parser and PHYLIP writer instead of the native ones")
     parser.add_argument("--worker", default=None, help=argparse.SUPPRESS)   # "r/W": share r of W of the files
@@ -75,7 +83,13 @@ def build_parser():
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.bootstrap < 0:
+        parser.error(f"--bootstrap must be >= 0 (got {args.bootstrap})")
+    if args.bootstrap and args.shard == "sites":
+        parser.error("--bootstrap is not supported with --shard sites (every replicate would need its own collectives); "
+                     "use --shard files")
 
     from phyloformer_amd import scheduler
 
@@ -107,6 +121,8 @@ def main(argv=None):
                 rate = (reports[0]["alignments_per_s"] or 0) if (sites and reports) else sum(r["alignments_per_s"] or 0 for r in reports)
                 print(json.dumps({"alignments": n, "devices": devices, "shard": args.shard if sites or args.shard == "files" else "files (fallback)",
                                   "wall_s_incl_startup": round(wall, 4), "alignments_per_s": round(rate, 3),
+                                  "replicates": args.bootstrap,
+                                  "bootstrap_s": round(sum(r.get("bootstrap_s", 0.0) for r in reports), 6),
                                   "workers": reports}), file=sys.stderr)
             return rc
         args.device = devices[0]
@@ -152,7 +168,8 @@ def main(argv=None):
             e.set_option("two_streams", 0)
     runner = scheduler.DirectoryRunner(engines, out_dir, trees=args.trees, batch=args.batch,
                                        io_threads=args.io_threads, native_io=not args.python_io,
-                                       progress=bar.update if bar is not None else None)
+                                       progress=bar.update if bar is not None else None,
+                                       bootstrap=args.bootstrap, seed=args.seed)
     try:
         stats = runner.run(paths)
     finally:

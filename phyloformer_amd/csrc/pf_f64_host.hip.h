@@ -448,6 +448,13 @@ int forward_chunk_f64(pf_handle* h, const F64Path& path, const uint8_t* d_idx, i
     return f64_schedule(h, &r, 1, reduce, d_out);
 }
 
+// alignments per chunk of a float64 forward of B alignments under "ws_limit_mb" (Lmax: the largest shard's sites)
+int f64_chunk_batch(const pf_handle* h, const F64Path& path, int B, int P, int Lmax) {
+    size_t off[F64_BUFS];
+    const size_t per = f64_bytes(path.dims(h), 1, P, std::max(Lmax, 1), off);
+    return (int)std::max<size_t>(1, std::min<size_t>((size_t)B, (size_t)h->ws_limit_bytes / std::max<size_t>(per, 1)));
+}
+
 int forward_device_f64(pf_handle* h, const F64Path& path, const uint8_t* d_idx, int B, int N, int l_begin, int l_end,
                        int L_total, float* d_out) {
     int rc = path.prepare(h);
@@ -456,9 +463,7 @@ int forward_device_f64(pf_handle* h, const F64Path& path, const uint8_t* d_idx, 
     // alignments per chunk under "ws_limit_mb": every rank derives it from the largest shard (one collective
     // sequence per chunk)
     const int Lmax = h->world > 1 ? std::max(Lloc, (L_total + h->world - 1) / h->world) : Lloc;
-    size_t off[F64_BUFS];
-    const size_t per = f64_bytes(path.dims(h), 1, P, std::max(Lmax, 1), off);
-    const int cb = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, (size_t)h->ws_limit_bytes / std::max<size_t>(per, 1)));
+    const int cb = f64_chunk_batch(h, path, B, P, Lmax);
     for (int b0 = 0; b0 < B; b0 += cb) {
         const int nb = std::min(cb, B - b0);
         rc = forward_chunk_f64(h, path, d_idx ? d_idx + (size_t)b0 * N * Lloc : nullptr, nb, N, Lloc, L_total,

@@ -302,36 +302,32 @@ void append_repr(std::string& out, double x) {
     }
 }
 
-// preds [n(n-1)/2] (pairs i < j, lexicographic) -> Newick text of the neighbour-joining tree, as nj.py writes it
-void nj_newick(const float* preds, int32_t n, const char* const* ids, const int64_t* id_lens, bool clamp, std::string& out) {
-    std::vector<std::string> labels((size_t)n);
-    for (int32_t i = 0; i < n; ++i) {
-        const char* id = ids[i] ? ids[i] : "";
-        labels[(size_t)i].assign(id, (size_t)(id_lens ? id_lens[i] : (int64_t)strlen(id)));
-    }
-    out.clear();
-    if (n == 1) { out = "(" + labels[0] + ");\n"; return; }
-    auto at = [&](int64_t i, int64_t j) -> double {      // the symmetric matrix vec_to_phylip builds (float32, dm + dm.T)
-        if (i == j) return 0.0;
-        if (i > j) { const int64_t t = i; i = j; j = t; }
-        return (double)(preds[i * n - i * (i + 1) / 2 + (j - i - 1)] + 0.0f);
-    };
-    if (n == 2) {
-        char num[64];
-        snprintf(num, sizeof num, "%.6g", at(0, 1) / 2);
-        out = "(" + labels[0] + ":" + num + "," + labels[1] + ":" + num + ");\n";
-        return;
-    }
-    auto fmt = [&](std::string& dst, double x) {
-        if (clamp && x < 0) x = 0.0;
-        append_repr(dst, x);
-    };
+// preds [n(n-1)/2] (pairs i < j, lexicographic): the symmetric matrix vec_to_phylip builds (float32, dm + dm.T)
+double pair_at(const float* preds, int64_t n, int64_t i, int64_t j) {
+    if (i == j) return 0.0;
+    if (i > j) { const int64_t t = i; i = j; j = t; }
+    return (double)(preds[i * n - i * (i + 1) / 2 + (j - i - 1)] + 0.0f);
+}
+
+// The join sequence of neighbour joining (nj.py::nj_joins): join t merges slots a < b into slot a; the last three
+// slots meet at the trifurcation.
+struct NjJoin { int32_t a, b; double la, lb; };
+struct NjTree {
+    std::vector<NjJoin> joins;
+    int32_t i = 0, j = 0, k = 0;
+    double li = 0, lj = 0, lk = 0;
+};
+
+// n >= 3
+void nj_core(const float* preds, int32_t n, NjTree& t) {
     const size_t N = (size_t)n;
     std::vector<double> d(N * N), sub, r, dn(N);
     for (size_t i = 0; i < N; ++i)
-        for (size_t j = 0; j < N; ++j) d[i * N + j] = at((int64_t)i, (int64_t)j);
+        for (size_t j = 0; j < N; ++j) d[i * N + j] = pair_at(preds, n, (int64_t)i, (int64_t)j);
     std::vector<int32_t> active((size_t)n);
     for (int32_t i = 0; i < n; ++i) active[(size_t)i] = i;
+    t.joins.clear();
+    t.joins.reserve(N - 3);
     while (active.size() > 3) {
         const size_t m = active.size();
         sub.resize(m * m);
@@ -350,28 +346,90 @@ void nj_newick(const float* preds, int32_t n, const char* const* ids, const int6
                 if (q != q) { ba = a; bb = b; saw_nan = true; have = true; break; }     // np.argmin: the first NaN wins
                 if (!have || q < best) { best = q; ba = a; bb = b; have = true; }
             }
-        if (ba > bb) { const size_t t = ba; ba = bb; bb = t; }
+        if (ba > bb) { const size_t tmp = ba; ba = bb; bb = tmp; }
         const size_t ia = (size_t)active[ba], ib = (size_t)active[bb];
         const double dab = sub[ba * m + bb];
         const double la = 0.5 * dab + (r[ba] - r[bb]) / (double)(2 * ((int64_t)m - 2));
         const double lb = dab - la;
-        std::string nl;
-        nl.reserve(labels[ia].size() + labels[ib].size() + 64);
-        nl += '('; nl += labels[ia]; nl += ':'; fmt(nl, la); nl += ','; nl += labels[ib]; nl += ':'; fmt(nl, lb); nl += ')';
+        t.joins.push_back({(int32_t)ia, (int32_t)ib, la, lb});
         for (size_t k = 0; k < N; ++k) dn[k] = 0.5 * ((d[ia * N + k] + d[ib * N + k]) - dab);
         for (size_t k = 0; k < N; ++k) { d[ia * N + k] = dn[k]; d[k * N + ia] = dn[k]; }
         d[ia * N + ia] = 0.0;
-        labels[ia].swap(nl);
-        std::string().swap(labels[ib]);
         active.erase(active.begin() + (std::ptrdiff_t)bb);
     }
     const size_t i = (size_t)active[0], j = (size_t)active[1], k = (size_t)active[2];
-    const double li = 0.5 * ((d[i * N + j] + d[i * N + k]) - d[j * N + k]);
-    const double lj = 0.5 * ((d[i * N + j] + d[j * N + k]) - d[i * N + k]);
-    const double lk = 0.5 * ((d[i * N + k] + d[j * N + k]) - d[i * N + j]);
+    t.i = (int32_t)i; t.j = (int32_t)j; t.k = (int32_t)k;
+    t.li = 0.5 * ((d[i * N + j] + d[i * N + k]) - d[j * N + k]);
+    t.lj = 0.5 * ((d[i * N + j] + d[j * N + k]) - d[i * N + k]);
+    t.lk = 0.5 * ((d[i * N + k] + d[j * N + k]) - d[i * N + j]);
+}
+
+// Newick text of a join sequence (nj.py::newick_of_joins); support[t], when not NULL, follows the ')' of join t's node
+void nj_format(const NjTree& t, int32_t n, const char* const* ids, const int64_t* id_lens, bool clamp,
+               const int32_t* support, std::string& out) {
+    std::vector<std::string> labels((size_t)n);
+    for (int32_t i = 0; i < n; ++i) {
+        const char* id = ids[i] ? ids[i] : "";
+        labels[(size_t)i].assign(id, (size_t)(id_lens ? id_lens[i] : (int64_t)strlen(id)));
+    }
+    auto fmt = [&](std::string& dst, double x) {
+        if (clamp && x < 0) x = 0.0;
+        append_repr(dst, x);
+    };
+    for (size_t s = 0; s < t.joins.size(); ++s) {
+        const NjJoin& jn = t.joins[s];
+        const size_t ia = (size_t)jn.a, ib = (size_t)jn.b;
+        std::string nl;
+        nl.reserve(labels[ia].size() + labels[ib].size() + 64);
+        nl += '('; nl += labels[ia]; nl += ':'; fmt(nl, jn.la); nl += ','; nl += labels[ib]; nl += ':'; fmt(nl, jn.lb); nl += ')';
+        if (support) nl += std::to_string(support[s]);
+        labels[ia].swap(nl);
+        std::string().swap(labels[ib]);
+    }
+    const size_t i = (size_t)t.i, j = (size_t)t.j, k = (size_t)t.k;
+    out.clear();
     out.reserve(labels[i].size() + labels[j].size() + labels[k].size() + 96);
-    out += '('; out += labels[i]; out += ':'; fmt(out, li); out += ','; out += labels[j]; out += ':'; fmt(out, lj);
-    out += ','; out += labels[k]; out += ':'; fmt(out, lk); out += ");\n";
+    out += '('; out += labels[i]; out += ':'; fmt(out, t.li); out += ','; out += labels[j]; out += ':'; fmt(out, t.lj);
+    out += ','; out += labels[k]; out += ':'; fmt(out, t.lk); out += ");\n";
+}
+
+// preds [n(n-1)/2] -> Newick text of the neighbour-joining tree, as nj.py::neighbor_joining writes it
+void nj_newick(const float* preds, int32_t n, const char* const* ids, const int64_t* id_lens, bool clamp, std::string& out) {
+    out.clear();
+    auto label = [&](int32_t i) {
+        const char* id = ids[i] ? ids[i] : "";
+        return std::string(id, (size_t)(id_lens ? id_lens[i] : (int64_t)strlen(id)));
+    };
+    if (n == 1) { out = "(" + label(0) + ");\n"; return; }
+    if (n == 2) {
+        char num[64];
+        snprintf(num, sizeof num, "%.6g", pair_at(preds, n, 0, 1) / 2);
+        out = "(" + label(0) + ":" + num + "," + label(1) + ":" + num + ");\n";
+        return;
+    }
+    NjTree t;
+    nj_core(preds, n, t);
+    nj_format(t, n, ids, id_lens, clamp, nullptr, out);
+}
+
+// The split each join creates: a bitset over sequence indices (W words each), normalised to the side without
+// sequence 0 (bootstrap.py::join_splits).  splits [joins][W]
+void nj_splits(const NjTree& t, int32_t n, std::vector<uint64_t>& splits) {
+    const size_t W = ((size_t)n + 63) / 64;
+    std::vector<uint64_t> members((size_t)n * W, 0);
+    for (int32_t i = 0; i < n; ++i) members[(size_t)i * W + (size_t)i / 64] = 1ull << (i % 64);
+    splits.assign(t.joins.size() * W, 0);
+    for (size_t s = 0; s < t.joins.size(); ++s) {
+        uint64_t* ma = &members[(size_t)t.joins[s].a * W];
+        const uint64_t* mb = &members[(size_t)t.joins[s].b * W];
+        for (size_t w = 0; w < W; ++w) ma[w] |= mb[w];
+        const bool flip = ma[0] & 1u;
+        for (size_t w = 0; w < W; ++w) {
+            const int bits = (int)std::min<size_t>(64, (size_t)n - 64 * w);
+            const uint64_t mask = bits == 64 ? ~0ull : ((1ull << bits) - 1);
+            splits[s * W + w] = flip ? (~ma[w] & mask) : ma[w];
+        }
+    }
 }
 
 }  // namespace
@@ -589,6 +647,64 @@ int pf_phylip_write_batch(const pf_fasta_batch_t* const* batches, const int32_t*
         });
     } catch (...) { return PF_ENOMEM; }
     return PF_OK;
+}
+
+// Bootstrap supports (bound by phyloformer_amd/hostio.py::nj_support; not part of the public header): the pf_nj_newick_n
+// text of preds [n(n-1)/2] with, after the ')' of every internal node, the integer percent (200 c + R) / (2 R) of the
+// R replicate trees of reps [R][n(n-1)/2] that contain the node's split.  The replicates are joined on up to `threads`
+// threads.  Twin of phyloformer_amd/bootstrap.py::support_newick_py, byte for byte.  Sizing protocol as
+// pf_format_phylip; every call joins all R replicates, so size with pf_nj_newick_n (the labels add at most 3 bytes
+// per internal node).
+int64_t pf_nj_support_n(const float* preds, const float* reps, int32_t R, int32_t n, const char* const* ids,
+                        const int64_t* id_lens, int32_t clamp_negative, int32_t threads, char* out, int64_t cap) {
+    if (!preds || !reps || R < 1 || n < 1 || !ids || !id_lens || (!out && cap > 0)) return PF_EINVAL;
+    for (int32_t i = 0; i < n; ++i) if (id_lens[i] < 0) return PF_EINVAL;
+    try {
+        std::string text;
+        if (n <= 3) {                               // no internal split
+            nj_newick(preds, n, ids, id_lens, clamp_negative != 0, text);
+        } else {
+            const size_t P = (size_t)n * (size_t)(n - 1) / 2, W = ((size_t)n + 63) / 64;
+            NjTree tree;
+            nj_core(preds, n, tree);
+            std::vector<uint64_t> splits;
+            nj_splits(tree, n, splits);
+            const size_t S = tree.joins.size();
+            std::vector<uint8_t> hit((size_t)R * S, 0);
+            std::atomic<bool> failed{false};
+            run_pool(R, threads, [&](int32_t r) {
+                try {
+                    NjTree rt;
+                    nj_core(reps + (size_t)r * P, n, rt);
+                    std::vector<uint64_t> rs;
+                    nj_splits(rt, n, rs);
+                    // sorted replicate splits, then one binary search per split of the tree
+                    std::vector<size_t> order(rt.joins.size());
+                    for (size_t s = 0; s < order.size(); ++s) order[s] = s;
+                    auto less = [&](const uint64_t* x, const uint64_t* y) {
+                        return std::lexicographical_compare(x, x + W, y, y + W);
+                    };
+                    std::sort(order.begin(), order.end(), [&](size_t x, size_t y) { return less(&rs[x * W], &rs[y * W]); });
+                    for (size_t s = 0; s < S; ++s) {
+                        const uint64_t* key = &splits[s * W];
+                        auto it = std::lower_bound(order.begin(), order.end(), key,
+                                                   [&](size_t x, const uint64_t* k) { return less(&rs[x * W], k); });
+                        hit[(size_t)r * S + s] = it != order.end() && std::equal(key, key + W, &rs[*it * W]);
+                    }
+                } catch (...) { failed = true; }
+            });
+            if (failed) return PF_ENOMEM;
+            std::vector<int32_t> support(S);
+            for (size_t s = 0; s < S; ++s) {
+                int64_t c = 0;
+                for (int32_t r = 0; r < R; ++r) c += hit[(size_t)r * S + s];
+                support[s] = (int32_t)((200 * c + R) / (2 * (int64_t)R));
+            }
+            nj_format(tree, n, ids, id_lens, clamp_negative != 0, support.data(), text);
+        }
+        if (out && (int64_t)text.size() <= cap) memcpy(out, text.data(), text.size());
+        return (int64_t)text.size();
+    } catch (...) { return PF_ENOMEM; }
 }
 
 }  // extern "C"

@@ -36,6 +36,7 @@
 #include "pf_mha.hip.h"
 #include "pf_precise.hip.h"
 #include "pf_generic.hip.h"
+#include "pf_boot.hip.h"
 #include "pf_host_prep.h"
 
 using namespace pfk;
@@ -134,8 +135,9 @@ struct BlockDev {
 
 struct ProfSlot { int kid; hipEvent_t a, b; };
 const char* const KNAMES[] = {"embed", "rowfin", "colstats", "colfin", "main", "allreduce",
-                              "mha_qkv", "mha_attn", "mha_out", "precise", "generic"};
-enum { K_EMBED = 0, K_ROWFIN, K_COLSTATS, K_COLFIN, K_MAIN, K_ALLREDUCE, K_MHA_QKV, K_MHA_ATTN, K_MHA_OUT, K_PRECISE, K_GENERIC, K_COUNT };
+                              "mha_qkv", "mha_attn", "mha_out", "precise", "generic", "resample"};
+enum { K_EMBED = 0, K_ROWFIN, K_COLSTATS, K_COLFIN, K_MAIN, K_ALLREDUCE, K_MHA_QKV, K_MHA_ATTN, K_MHA_OUT, K_PRECISE, K_GENERIC,
+       K_RESAMPLE, K_COUNT };
 
 // weights of the float64 path (pf_precise.hip.h), widened and transposed at pf_create
 struct PreciseWeights {
@@ -200,6 +202,7 @@ struct pf_handle {
     int reserve_cus = 8;          // option "reserve_cus": CUs the persistent kernels leave to RCCL then
     uint8_t* d_idx = nullptr; size_t d_idx_bytes = 0;
     float* d_out = nullptr; size_t d_out_bytes = 0;
+    uint8_t* d_rep = nullptr; size_t d_rep_bytes = 0;       // pf_bootstrap: one chunk of replicate bytes (grow-only)
     // comm: one RCCL communicator per stream (comm[1] serves stream2), created together by pf_comm_init, so that
     // RCCL never has to order one half-batch's collectives behind the other's with an implicit cross-stream wait
     void* comm[2] = {nullptr, nullptr};
@@ -1043,6 +1046,66 @@ int check_bad_idx(pf_handle* h) {
                               "those of a valid alignment)");
 }
 
+// residues of a host batch: one branch-free pass the compiler vectorises (an early-exit byte loop cost 0.2 ms per
+// batch of 16 x 60 x 500: most of what separated the host-buffer rate from the device-resident one); the offender is
+// looked for only if there is one
+int check_residues(pf_handle* h, const uint8_t* idx, size_t nidx) {
+    unsigned bad = 0;
+    for (size_t i = 0; i < nidx; ++i) bad |= (unsigned)(idx[i] >= NA);
+    if (bad)
+        for (size_t i = 0; i < nidx; ++i)
+            if (idx[i] >= NA) return fail(h, PF_EINVAL, "residue index %d at offset %zu is outside 0..21", (int)idx[i], i);
+    return PF_OK;
+}
+
+// grow-only device buffer
+template <class T>
+int ensure_buffer(pf_handle* h, T** p, size_t* have, size_t bytes) {
+    if (*p && bytes <= *have) return PF_OK;
+    if (*p) hipFree(*p);
+    *p = nullptr; *have = 0;
+    HIPCHK(h, hipMalloc((void**)p, bytes ? bytes : 1));
+    *have = bytes;
+    return PF_OK;
+}
+
+// Range re-check (pf_handle::recheck_above) of `count` alignments whose results are in host `out` [count][P], on the
+// default kernels' results only.  An alignment whose largest distance exceeds recheck_above, or is not finite, is
+// computed again on the float64 kernels: stage(list, k, d_buf) puts the bytes [k][N][Lloc] of the alignments `list`
+// into d_buf (on h->stream), which holds `cap` of them; h->d_out must hold cap x P floats.  Every rank of a site-
+// sharded call holds the same `out` (the all-reduced site sums through the same kernel), so all of them pick the same
+// alignments and issue the same collectives of the float64 forward.
+template <class Stage>
+int range_recheck(pf_handle* h, float* out, int count, int N, int l_begin, int l_end, int L_total, uint8_t* d_buf, size_t cap,
+                  Stage&& stage) {
+    if (h->precise >= 0 || h->recheck_above <= 0.0) return PF_OK;
+    const int P = N * (N - 1) / 2;
+    const size_t per = (size_t)N * (size_t)(l_end - l_begin);
+    std::vector<int> redo;
+    std::vector<float> res;
+    try {           // (nothing may throw across the C ABI)
+        for (int b = 0; b < count; ++b) {
+            const float* ob = out + (size_t)b * P;
+            bool inside = true;
+            for (int p = 0; p < P; ++p) inside &= ob[p] <= (float)h->recheck_above;      // (false for NaN)
+            if (!inside) redo.push_back(b);
+        }
+        res.resize(std::min(redo.size(), cap) * (size_t)P);
+    } catch (const std::bad_alloc&) { return fail(h, PF_ENOMEM, "out of host memory in the range re-check"); }
+    for (size_t g0 = 0; g0 < redo.size(); g0 += cap) {
+        const size_t nr = std::min(cap, redo.size() - g0);
+        int rc;
+        if (per && (rc = stage(&redo[g0], nr, d_buf))) return rc;
+        rc = forward_device_f64(h, PRECISE_F64, per ? d_buf : nullptr, (int)nr, N, l_begin, l_end, L_total, h->d_out);
+        if (rc) return rc;
+        HIPCHK(h, hipMemcpyAsync(res.data(), h->d_out, nr * (size_t)P * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        for (size_t i = 0; i < nr; ++i) std::memcpy(out + (size_t)redo[g0 + i] * P, &res[i * P], (size_t)P * sizeof(float));
+    }
+    h->rechecked += (int64_t)redo.size();
+    return PF_OK;
+}
+
 int forward_host_impl(pf_handle* h, const uint8_t* idx, int B, int N, int l_begin, int l_end,
                       int L_total, float* out) {
     const int Lloc = l_end - l_begin;
@@ -1050,69 +1113,91 @@ int forward_host_impl(pf_handle* h, const uint8_t* idx, int B, int N, int l_begi
     if (rc) return rc;
     if (!out || (!idx && Lloc > 0)) return fail(h, PF_EINVAL, "null buffer");
     const size_t nidx = (size_t)B * N * Lloc;
-    {
-        // one branch-free pass the compiler vectorises (an early-exit byte loop cost 0.2 ms per batch of 16 x 60 x 500:
-        // most of what separated the host-buffer rate from the device-resident one); the offender is looked for only
-        // if there is one
-        unsigned bad = 0;
-        for (size_t i = 0; i < nidx; ++i) bad |= (unsigned)(idx[i] >= NA);
-        if (bad)
-            for (size_t i = 0; i < nidx; ++i)
-                if (idx[i] >= NA) return fail(h, PF_EINVAL, "residue index %d at offset %zu is outside 0..21", (int)idx[i], i);
-    }
+    if ((rc = check_residues(h, idx, nidx))) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     const int P = N * (N - 1) / 2;
-    if (nidx > h->d_idx_bytes || !h->d_idx) {
-        if (h->d_idx) hipFree(h->d_idx);
-        h->d_idx = nullptr; h->d_idx_bytes = 0;
-        HIPCHK(h, hipMalloc((void**)&h->d_idx, nidx ? nidx : 1));
-        h->d_idx_bytes = nidx;
-    }
+    if ((rc = ensure_buffer(h, &h->d_idx, &h->d_idx_bytes, nidx))) return rc;
     const size_t nout = (size_t)B * P * sizeof(float);
-    if (nout > h->d_out_bytes) {
-        if (h->d_out) hipFree(h->d_out);
-        h->d_out = nullptr; h->d_out_bytes = 0;
-        HIPCHK(h, hipMalloc((void**)&h->d_out, nout));
-        h->d_out_bytes = nout;
-    }
+    if ((rc = ensure_buffer(h, &h->d_out, &h->d_out_bytes, nout))) return rc;
     if (nidx) HIPCHK(h, hipMemcpyAsync(h->d_idx, idx, nidx, hipMemcpyHostToDevice, h->stream));
     const bool default_kernels = !f64_path_of(h, N, L_total);
     rc = forward_device_impl(h, h->d_idx, B, N, l_begin, l_end, L_total, h->d_out);
     if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(out, h->d_out, nout, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (default_kernels && h->precise < 0 && h->recheck_above > 0.0) {
-        // Range re-check (pf_handle::recheck_above).  Every rank of a site-sharded call holds the same `out` (the
-        // all-reduced site sums through the same kernel), so all of them pick the same alignments and issue the same
-        // collectives of the float64 forward.  A non-finite value is recomputed as well.
-        std::vector<int> redo;
-        std::vector<uint8_t> sub;
-        std::vector<float> res;
-        const size_t per = (size_t)N * Lloc;
-        try {           // (nothing may throw across the C ABI)
-            for (int b = 0; b < B; ++b) {
-                const float* ob = out + (size_t)b * P;
-                bool inside = true;
-                for (int p = 0; p < P; ++p) inside &= ob[p] <= (float)h->recheck_above;      // (false for NaN)
-                if (!inside) redo.push_back(b);
-            }
-            sub.resize(redo.size() * per);
-            res.resize(redo.size() * (size_t)P);
-        } catch (const std::bad_alloc&) { return fail(h, PF_ENOMEM, "out of host memory in the range re-check"); }
-        if (!redo.empty()) {
-            const size_t nr = redo.size();
-            for (size_t i = 0; i < nr; ++i)
-                if (per) std::memcpy(&sub[i * per], idx + (size_t)redo[i] * per, per);
-            if (per) HIPCHK(h, hipMemcpyAsync(h->d_idx, sub.data(), nr * per, hipMemcpyHostToDevice, h->stream));
-            rc = forward_device_f64(h, PRECISE_F64, per ? h->d_idx : nullptr, (int)nr, N, l_begin, l_end, L_total, h->d_out);
-            if (rc) return rc;
-            HIPCHK(h, hipMemcpyAsync(res.data(), h->d_out, nr * (size_t)P * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            for (size_t i = 0; i < nr; ++i) std::memcpy(out + (size_t)redo[i] * P, &res[i * P], (size_t)P * sizeof(float));
-            h->rechecked += (int64_t)nr;
-        }
-    }
+    if (!default_kernels) return PF_OK;
+    std::vector<uint8_t> sub;
+    const size_t per = (size_t)N * Lloc;
+    return range_recheck(h, out, B, N, l_begin, l_end, L_total, h->d_idx, (size_t)B,
+                         [&](const int* list, size_t k, uint8_t* d_buf) -> int {
+        try { sub.resize(k * per); }
+        catch (const std::bad_alloc&) { return fail(h, PF_ENOMEM, "out of host memory in the range re-check"); }
+        for (size_t i = 0; i < k; ++i) std::memcpy(&sub[i * per], idx + (size_t)list[i] * per, per);
+        HIPCHK(h, hipMemcpyAsync(d_buf, sub.data(), k * per, hipMemcpyHostToDevice, h->stream));
+        return PF_OK;
+    });
+}
+
+int launch_resample(pf_handle* h, const uint8_t* d_src, int B, int N, int L, int r_begin, int R, uint64_t seed, uint8_t* d_dst) {
+    h->cur = h->stream;
+    ProfScope ps(h, K_RESAMPLE);
+    const hipError_t e = pfb::launch_resample(h->stream, d_src, B, N, L, r_begin, R, seed, d_dst);
+    if (e != hipSuccess) return fail(h, PF_EHIP, "k_resample launch failed: %s", hipGetErrorString(e));
     return PF_OK;
+}
+
+// a * b * c as size_t, false on overflow
+bool mul_size(size_t a, size_t b, size_t c, size_t* out) {
+    size_t t;
+    return !__builtin_mul_overflow(a, b, &t) && !__builtin_mul_overflow(t, c, out);
+}
+
+// pf_bootstrap.  The B sources are uploaded once; the B x R replicates run in chunks of the size the forward's own
+// chunking picks for B x R alignments (chunk_batch, or the float64 path's), cut to a rectangle - whole sources with
+// all their replicates, or a run of one source's replicates - so that one k_resample launch builds a chunk's bytes in
+// the grow-only h->d_rep; the forward then reads them there.  A replicate's distances are those of pf_forward on its
+// host-resampled bytes, bit for bit: the forward is batch invariant and routes on (N, L) alone.
+int bootstrap_impl(pf_handle* h, const uint8_t* idx, int B, int N, int L, int R, uint64_t seed, float* out) {
+    int rc = check_dims(h, B, N, L, L);
+    if (rc) return rc;
+    if (R < 1) return fail(h, PF_EINVAL, "bootstrap needs R >= 1 replicates (got %d)", R);
+    if (!out || !idx) return fail(h, PF_EINVAL, "null buffer");
+    const int P = N * (N - 1) / 2;
+    size_t nout = 0, nrep = 0;
+    if (!mul_size((size_t)B, (size_t)R, (size_t)P * sizeof(float), &nout) || !mul_size((size_t)B, (size_t)R, (size_t)N * L, &nrep))
+        return fail(h, PF_EINVAL, "B=%d x R=%d replicates of %d x %d overflow the address space", B, R, N, L);
+    const size_t nidx = (size_t)B * N * L, per = (size_t)N * L;
+    if ((rc = check_residues(h, idx, nidx))) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    if ((rc = ensure_buffer(h, &h->d_idx, &h->d_idx_bytes, nidx))) return rc;
+    if ((rc = ensure_buffer(h, &h->d_out, &h->d_out_bytes, nout))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->d_idx, idx, nidx, hipMemcpyHostToDevice, h->stream));
+    const F64Path* f = f64_path_of(h, N, L);
+    const int total = (int)std::min<int64_t>((int64_t)B * R, INT32_MAX);
+    const int cb = f ? f64_chunk_batch(h, *f, total, P, L) : chunk_batch(h, total, P, L);
+    const int spc = cb >= R ? cb / R : 0;                  // whole sources per chunk, or
+    const int rpc = spc ? R : cb;                          // replicates of one source per chunk
+    const size_t cap = spc ? (size_t)spc * R : (size_t)rpc;
+    if ((rc = ensure_buffer(h, &h->d_rep, &h->d_rep_bytes, cap * per))) return rc;
+    for (int b0 = 0; b0 < B; b0 += std::max(spc, 1))
+        for (int r0 = 0; r0 < R; r0 += rpc) {
+            const int nb = spc ? std::min(spc, B - b0) : 1, nr = std::min(rpc, R - r0);
+            if ((rc = launch_resample(h, h->d_idx + (size_t)b0 * per, nb, N, L, r0, nr, seed, h->d_rep))) return rc;
+            rc = forward_device_impl(h, h->d_rep, nb * nr, N, 0, L, L, h->d_out + ((size_t)b0 * R + r0) * P);
+            if (rc) return rc;
+        }
+    HIPCHK(h, hipMemcpyAsync(out, h->d_out, nout, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (f) return PF_OK;
+    // a flagged replicate is rebuilt from the resident source bytes
+    return range_recheck(h, out, B * R, N, 0, L, L, h->d_rep, cap, [&](const int* list, size_t k, uint8_t* d_buf) -> int {
+        for (size_t i = 0; i < k; ++i) {
+            const int b = list[i] / R, r = list[i] % R;
+            const int rc2 = launch_resample(h, h->d_idx + (size_t)b * per, 1, N, L, r, 1, seed, d_buf + i * per);
+            if (rc2) return rc2;
+        }
+        return PF_OK;
+    });
 }
 
 }  // namespace
@@ -1245,6 +1330,7 @@ int pf_destroy(pf_handle_t* h) {
     if (h->ev_join) hipEventDestroy(h->ev_join);
     if (h->d_idx) hipFree(h->d_idx);
     if (h->d_out) hipFree(h->d_out);
+    if (h->d_rep) hipFree(h->d_rep);
     if (h->stream) hipStreamDestroy(h->stream);
     if (h->bad_idx_host) hipHostFree(h->bad_idx_host);
     delete h;
@@ -1290,6 +1376,24 @@ int pf_set_option(pf_handle_t* h, const char* key, int64_t value) {
 int pf_forward(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, int32_t L, float* out) {
     if (!h) return PF_EINVAL;
     return forward_host_impl(h, idx, B, N, 0, L, L, out);
+}
+
+int pf_resample_sites_device(pf_handle_t* h, const uint8_t* d_src, int32_t B, int32_t N, int32_t L, int32_t r_begin, int32_t R,
+                             uint64_t seed, uint8_t* d_dst) {
+    if (!h) return PF_EINVAL;
+    if (!d_src || !d_dst) return fail(h, PF_EINVAL, "null buffer");
+    if (B < 1 || N < 1 || L < 1 || R < 1 || r_begin < 0)
+        return fail(h, PF_EINVAL, "bad dimensions B=%d N=%d L=%d r_begin=%d R=%d", B, N, L, r_begin, R);
+    size_t n = 0;
+    if (!mul_size((size_t)B, (size_t)R, (size_t)N * L, &n))
+        return fail(h, PF_EINVAL, "B=%d x R=%d replicates of %d x %d overflow the address space", B, R, N, L);
+    HIPCHK(h, hipSetDevice(h->device));
+    return launch_resample(h, d_src, B, N, L, r_begin, R, seed, d_dst);
+}
+
+int pf_bootstrap(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, int32_t L, int32_t R, uint64_t seed, float* out) {
+    if (!h) return PF_EINVAL;
+    return bootstrap_impl(h, idx, B, N, L, R, seed, out);
 }
 
 int pf_forward_device(pf_handle_t* h, const uint8_t* d_idx, int32_t B, int32_t N, int32_t L, float* d_out) {

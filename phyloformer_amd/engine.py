@@ -57,6 +57,9 @@ SIGNATURES = {
     "pf_set_option": (C.c_int, [_H, C.c_char_p, C.c_int64]),
     "pf_forward": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "pf_forward_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "pf_resample_sites_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_uint64, C.c_void_p]),
+    "pf_bootstrap": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p]),
     "pf_forward_sharded": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_int32, C.c_void_p]),
     "pf_forward_sharded_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
@@ -228,6 +231,30 @@ class Engine:
         out = np.empty((B, N * (N - 1) // 2), dtype=np.float32)
         self._check(self._lib.pf_forward(self._h, idx.ctypes.data, B, N, L, out.ctypes.data))
         return out[0] if single else out
+
+    def bootstrap(self, idx: np.ndarray, replicates: int, seed: int = 0) -> np.ndarray:
+        """Distances of ``replicates`` site-bootstrap replicates (``pf_bootstrap``): ``uint8[B, N, L]`` →
+        ``float32[B, R, P]`` (``[N, L]`` → ``[R, P]``).  Replicate ``r`` of an alignment is
+        ``idx[..., bootstrap.resample_sites(L, R, seed)[r]]``; its distances are ``forward`` of those bytes, bit for bit."""
+        idx = _u8(idx)
+        single = idx.ndim == 2
+        if single:
+            idx = idx[None]
+        if idx.ndim != 3:
+            raise ValueError(f"idx must be [B, N, L] or [N, L], got shape {idx.shape}")
+        B, N, L = idx.shape
+        _refuse_single_sequence(B, N)
+        R = int(replicates)
+        out = np.empty((B, max(R, 0), N * (N - 1) // 2), dtype=np.float32)
+        self._check(self._lib.pf_bootstrap(self._h, idx.ctypes.data, B, N, L, R, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                           out.ctypes.data if out.size else None))
+        return out[0] if single else out
+
+    def resample_sites_device(self, d_src: int, B: int, N: int, L: int, r_begin: int, R: int, seed: int, d_dst: int):
+        """``pf_resample_sites_device``: replicates ``r_begin .. r_begin + R - 1`` of ``d_src [B][N][L]`` into
+        ``d_dst [B][R][N][L]`` (device buffers, asynchronous on the handle's stream)."""
+        self._check(self._lib.pf_resample_sites_device(self._h, C.c_void_p(d_src), B, N, L, r_begin, R,
+                                                       int(seed) & 0xFFFFFFFFFFFFFFFF, C.c_void_p(d_dst)))
 
     def forward_sharded(self, idx_local: np.ndarray, l_begin: int, l_end: int, L_total: int) -> np.ndarray:
         """This rank's sites ``[l_begin, l_end)`` of ``uint8[B, N, L_total]`` alignments."""

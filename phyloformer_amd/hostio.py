@@ -16,6 +16,22 @@ import numpy as np
 
 from .engine import load_library
 
+# library functions of this module that are not part of include/phyloformer_amd.h (bound here, not in
+# engine.SIGNATURES, whose set must equal the header's)
+_PRIVATE = {
+    "pf_nj_support_n": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_char_p), C.c_void_p,
+                                    C.c_int32, C.c_int32, C.c_char_p, C.c_int64]),
+}
+
+
+def _lib():
+    lib = load_library()
+    for name, (res, args) in _PRIVATE.items():
+        fn = getattr(lib, name)
+        if fn.argtypes is None:
+            fn.restype, fn.argtypes = res, args
+    return lib
+
 PF_FASTA_EBYTE, PF_FASTA_ERAGGED, PF_FASTA_ENOHEADER, PF_FASTA_EEMPTY, PF_FASTA_ECAP, PF_FASTA_EUTF8 = -16, -17, -18, -19, -20, -21
 
 
@@ -111,6 +127,35 @@ def nj_newick(preds: np.ndarray, ids: Sequence[str], clamp_negative: bool = True
         raise RuntimeError(f"pf_nj_newick_n failed with status {need}")
     buf = C.create_string_buffer(int(need) + 1)
     w = lib.pf_nj_newick_n(p.ctypes.data, n, arr, lens.ctypes.data, int(clamp_negative), buf, need)
+    return buf.raw[:w]
+
+
+def nj_support(preds: np.ndarray, reps: np.ndarray, ids: Sequence[str], clamp_negative: bool = True,
+               threads: int = 1) -> bytes:
+    """``pf_nj_support_n``: the ``nj_newick`` text of ``preds [P]`` with the bootstrap support of every internal node,
+    counted over the NJ trees of ``reps [R][P]`` (joined on ``threads`` native threads, GIL released) - byte-identical
+    to ``bootstrap.support_newick_py``."""
+    lib = _lib()
+    n = len(ids)
+    p = np.ascontiguousarray(np.asarray(preds, dtype=np.float32).reshape(-1))
+    if p.size != n * (n - 1) // 2:
+        raise ValueError(f"expected {n * (n - 1) // 2} distances for {n} sequences, got {p.shape}")
+    r = np.ascontiguousarray(np.asarray(reps, dtype=np.float32))
+    if r.ndim != 2 or r.shape[0] < 1 or r.shape[1] != p.size:
+        raise ValueError(f"expected replicates [R >= 1][{p.size}], got {r.shape}")
+    enc = [s.encode("utf8") for s in ids]
+    arr = (C.c_char_p * n)(*enc)
+    lens = np.array([len(e) for e in enc], dtype=np.int64)
+    # one NJ sizes the text: the labels add at most "100" per internal node
+    base = lib.pf_nj_newick_n(p.ctypes.data, n, arr, lens.ctypes.data, int(clamp_negative), None, 0)
+    if base < 0:
+        raise RuntimeError(f"pf_nj_newick_n failed with status {base}")
+    cap = int(base) + 3 * n + 16
+    buf = C.create_string_buffer(cap)
+    w = lib.pf_nj_support_n(p.ctypes.data, r.ctypes.data, r.shape[0], n, arr, lens.ctypes.data, int(clamp_negative),
+                            int(threads), buf, cap)
+    if w < 0 or w > cap:
+        raise RuntimeError(f"pf_nj_support_n failed with status {w}")
     return buf.raw[:w]
 
 

@@ -53,6 +53,11 @@ TOKEN_BUDGET = 16 * 1770 * 500
 FILES_PER_LOAD = 256
 # a partial shape bucket is launched after this many further load calls (bounds what the native pipeline keeps parsed)
 STALE_LOADS = 16
+# --bootstrap: replicate distances per pf_bootstrap call, in floats (16 MiB).  This bounds host memory, not GPU work:
+# the results wait in the writer queue (up to 8 x io_threads entries) until their supports are written, so the cap
+# keeps that queue to a few hundred MB even at 200 taxa (R = 100 x 19,900 floats = 8 MB per alignment).  The GPU stays
+# fed: one alignment's R = 100 replicates at 60 x 500 are already 6 x TOKEN_BUDGET, and pf_bootstrap chunks them itself.
+BOOT_FLOATS = 1 << 22
 
 
 def auto_batch(n_seqs: int, n_sites: int, max_batch: int = 4096, token_budget: int = TOKEN_BUDGET) -> int:
@@ -110,7 +115,7 @@ class DirectoryRunner:
     calls) are filled by the other's kernels — measured 486 -> 501 alignments/s at 60 x 500 with two."""
 
     def __init__(self, engine, out_dir: str, trees: bool = False, batch: int = 0,
-                 io_threads: int = 4, native_io: bool = True, progress=None):
+                 io_threads: int = 4, native_io: bool = True, progress=None, bootstrap: int = 0, seed: int = 0):
         self.engines = list(engine) if isinstance(engine, (list, tuple)) else [engine]
         self.out_dir = out_dir
         self.trees = trees
@@ -118,8 +123,12 @@ class DirectoryRunner:
         self.io_threads = max(1, io_threads)
         self.native_io = native_io
         self.progress = progress
+        self.bootstrap = max(0, int(bootstrap))   # replicates per alignment (0 = off): <stem>.sup.nwk
+        self.seed = int(seed)
         self.stats = {"alignments": 0, "launches": 0, "forward_s": 0.0, "load_wait_s": 0.0,
                       "write_wait_s": 0.0, "shapes": {}, "gpu_streams": len(self.engines)}
+        if self.bootstrap:
+            self.stats.update({"replicates": self.bootstrap, "bootstrap_s": 0.0})
         self._lock = threading.Lock()
 
     # -- stages -----------------------------------------------------------------------------
@@ -149,6 +158,48 @@ class DirectoryRunner:
             with open(os.path.join(self.out_dir, f"{stem}.nj.nwk"), "w") as fh:
                 fh.write(neighbor_joining(dm.astype("float64"), ids))
 
+    def _writer_cap(self) -> int:
+        # (at most 4 threads: creating files in ONE directory from 8 / 16 threads is a lock convoy on the directory -
+        # 4,096 outputs took 0.98 / 1.19 s instead of 0.01 s, profiles/r05c_cli_bench.txt.  The neighbour joining of
+        # --trees rides on the same threads: 64 us per 20-taxon tree, 18 ms at 200 taxa, against 90 us / 22 ms of GPU time
+        # per alignment.  PF_WRITER_THREADS moves the cap for experiments, profiles/r06r_cli_bench_overlay_writer_threads.txt.)
+        return max(1, min(self.io_threads, int(os.environ.get("PF_WRITER_THREADS", "4"))))
+
+    def _support(self, path: str, pred: np.ndarray, reps: np.ndarray, ids: List[str]):
+        """``<stem>.sup.nwk`` (``--bootstrap``): the NJ tree of ``pred`` with the supports of ``reps``."""
+        out = os.path.join(self.out_dir, f"{Path(path).stem}.sup.nwk")
+        if self.native_io:
+            from .hostio import nj_support
+            with open(out, "wb") as fh:
+                fh.write(nj_support(pred, reps, ids, threads=self._writer_cap()))
+            return
+        from .bootstrap import support_newick_py
+        with open(out, "w") as fh:
+            fh.write(support_newick_py(pred, reps, ids))
+
+    def _support_native(self, group: list, preds: np.ndarray, reps: np.ndarray):
+        for (path, (fb, i), _none), pred, rep in zip(group, preds, reps):
+            self._support(path, pred, rep, fb.ids(i))
+
+    def _bootstrap(self, engine, shape: Tuple[int, int], group: list, batch: np.ndarray, preds: np.ndarray,
+                   writers: ThreadPoolExecutor, pending: deque, native: bool):
+        """Replicate distances of a launch group, in sub-batches of at most BOOT_FLOATS floats; their supports are
+        computed and written on the writer threads, like the trees."""
+        P = shape[0] * (shape[0] - 1) // 2
+        sub = max(1, BOOT_FLOATS // max(1, self.bootstrap * P))
+        for s0 in range(0, len(group), sub):
+            t0 = time.perf_counter()
+            reps = engine.bootstrap(batch[s0:s0 + sub], self.bootstrap, self.seed)
+            dt = time.perf_counter() - t0
+            part = group[s0:s0 + sub]
+            with self._lock:
+                self.stats["bootstrap_s"] += dt
+                if native:
+                    pending.append(writers.submit(self._support_native, part, preds[s0:s0 + sub], reps))
+                else:
+                    for (path, _idx, ids), pred, rep in zip(part, preds[s0:s0 + sub], reps):
+                        pending.append(writers.submit(self._support, path, pred, rep, ids))
+
     def _launch(self, engine, shape: Tuple[int, int], group: list, writers: ThreadPoolExecutor, pending: deque):
         native = group[0][2] is None              # entries of _feed_native: (path, (FastaBatch, file), None)
         t0 = time.perf_counter()
@@ -170,11 +221,16 @@ class DirectoryRunner:
             else:
                 for (path, _idx, ids), pred in zip(group, preds):
                     pending.append(writers.submit(self._write, path, pred, ids))
+            if self.progress is not None and not self.bootstrap:
+                self.progress(len(group))
+        if self.bootstrap:
+            self._bootstrap(engine, shape, group, batch, preds, writers, pending, native)
             if self.progress is not None:
                 self.progress(len(group))
+        with self._lock:
             drain = []
             # bound the write queue so results do not pile up in memory
-            while len(pending) > 8 * self.io_threads + (1 if native else len(group)):
+            while len(pending) > 8 * self.io_threads + (1 if native else len(group)) * (2 if self.bootstrap else 1):
                 drain.append(pending.popleft())
         t0 = time.perf_counter()
         for f in drain:
@@ -188,12 +244,7 @@ class DirectoryRunner:
         from .hostio import write_phylip
         outs = [os.path.join(self.out_dir, f"{Path(g[0]).stem}.phy") for g in group]
         trees = [os.path.join(self.out_dir, f"{Path(g[0]).stem}.nj.nwk") for g in group] if self.trees else None
-        # (at most 4 threads: creating files in ONE directory from 8 / 16 threads is a lock convoy on the directory -
-        # 4,096 outputs took 0.98 / 1.19 s instead of 0.01 s, profiles/r05c_cli_bench.txt.  The neighbour joining of
-        # --trees rides on the same threads: 64 us per 20-taxon tree, 18 ms at 200 taxa, against 90 us / 22 ms of GPU time
-        # per alignment.  PF_WRITER_THREADS moves the cap for experiments, profiles/r06r_cli_bench_overlay_writer_threads.txt.)
-        cap = int(os.environ.get("PF_WRITER_THREADS", "4"))
-        write_phylip([g[1] for g in group], n, preds, outs, max(1, min(self.io_threads, cap)), trees)
+        write_phylip([g[1] for g in group], n, preds, outs, self._writer_cap(), trees)
 
     def _gpu_worker(self, engine, jobs: "queue.Queue", writers, pending, errors: list):
         while True:
@@ -477,7 +528,8 @@ def summarize(stats: dict, load_s: float = 0.0) -> dict:
             "load_wait_s": round(stats["load_wait_s"], 6), "write_wait_s": round(stats["write_wait_s"], 6),
             "alignments_per_s": round(n / wall, 3) if wall > 0 else None,
             "alignments_per_s_forward_only": round(n * stats.get("gpu_streams", 1) / stats["forward_s"], 3)
-            if stats["forward_s"] > 0 else None}
+            if stats["forward_s"] > 0 else None,
+            "replicates": stats.get("replicates", 0), "bootstrap_s": round(stats.get("bootstrap_s", 0.0), 6)}
 
 
 def run_multi_device(script: str, argv: List[str], devices: Sequence[int], shard: str = "files") -> Tuple[int, List[dict]]:
