@@ -152,7 +152,11 @@ const char* pf_last_error(const pf_handle_t* h);
  *   "colstats_ring" int  0 = k_colstats prefetches its rows through registers instead of the per-wave LDS ring (the
  *                      same bits; A/B and counter runs)
  *   "precise_ffn_valu" int 1 = the float64 FFN on the plain VALU kernel instead of the fp64 matrix cores (cross-check)
- *   "phase_prof"  int  1 = in-kernel phase timers of k_main (pf_debug_read "phase_prof")
+ *   "phase_prof"  int  1 = in-kernel phase timers of k_main (pf_debug_read "phase_prof"); 2 = of the last
+ *                      block's launch only
+ *   "head_fold"   int  default 1: the last block's FFN output projection is folded into the softplus head (one dot
+ *                      product per token instead of the 256 -> 64 GEMM); 0 = the full last FFN (cross-check).
+ *                      With debug_keep = 1 the full last FFN runs as well, for the "x<n_blocks>" tap only
  *   "ablate"      int  energy experiments: phases of k_main switched off - RESULTS INVALID
  */
 int pf_set_option(pf_handle_t* h, const char* key, int64_t value);

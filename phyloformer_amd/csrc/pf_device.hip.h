@@ -466,7 +466,7 @@ struct MainArgs {
                             // 4 no next-row phase, 8 no apply phase, 16 no FFN (2 is unused now)
 };
 
-enum { MODE_FIRST = 0, MODE_MID = 1, MODE_LAST = 2, MODE_MID0 = 3 };
+enum { MODE_FIRST = 0, MODE_MID = 1, MODE_LAST = 2, MODE_MID0 = 3, MODE_LAST_FOLD = 4 };
 
 // Two tilings of an alignment's P x L tokens into work items of 32 tokens share the kernel:
 //   row tiling  (flat = 0): every pair row is cut into ceil(L / 32) tiles of its own; the last tile of a row is
@@ -526,6 +526,18 @@ __device__ __forceinline__ void part_range(int flat, int pr, int nparts, int P, 
     *count = k1 - k0 + 1;
 }
 
+// fragments [LO, HI) of the LDS image, 16 bytes per lane per request (see k_main)
+template <int LO, int HI>
+__device__ __forceinline__ void image_to_lds(const frag_t* src, unsigned char* smem) {
+    static_assert(LO % 64 == 0 && HI % 64 == 0, "the image is copied in whole waves");
+    const int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
+#pragma unroll
+    for (int k = 0; k < (HI - LO + MAIN_THREADS - 1) / MAIN_THREADS; ++k) {
+        const int f0 = LO + k * MAIN_THREADS + wv * 64;            // wave-uniform first fragment of this request
+        if (f0 < HI) __builtin_amdgcn_global_load_lds(src + f0 + ln, smem + (size_t)f0 * 16, 16, 0, 0);
+    }
+}
+
 // Work item = one tile of 32 tokens (see above).  The tiles
 // are dealt to the waves in short runs of consecutive tiles, round-robin; waves never synchronise with
 // each other after the LDS image is loaded.  Row statistics leave the kernel as one
@@ -539,10 +551,16 @@ __device__ __forceinline__ void part_range(int flat, int pr, int nparts, int P, 
 //               fly from the 5.6 KB embedding table (L1-resident) instead of being read from HBM: x0 is
 //               never materialised (3.6 GB less written and 2 x 3.6 GB less read per batch of 16)
 //   MODE_LAST : row-apply + col-apply + FFN of the last block -> softplus head, site mean
+//   MODE_LAST_FOLD: the same with the FFN's output projection folded into the head (pf_host_prep.h, fold_head):
+//               z = hw . x_attn + u . gelu(h) + c0 - GEMM1 and the GELU only, no hi/lo split of the GELU values,
+//               no GEMM2 (96 of the launch's ~216 MFMAs per tile) and no W2 in LDS.  x6 is never formed: for the
+//               debug taps a MODE_LAST launch (store_x_last) follows it
 //   FLAT      : the tiling (a.flat), a template parameter so that the row tiling carries none of the flat
 //               tiling's bookkeeping (shapes with L % 32 == 0, rows shorter than a tile)
 template <int MODE, bool FLAT>
 __global__ void __launch_bounds__(MAIN_THREADS, MAIN_WAVES / 4) k_main(MainArgs a) {
+    constexpr bool LAST = MODE == MODE_LAST || MODE == MODE_LAST_FOLD;
+    constexpr bool FOLD = MODE == MODE_LAST_FOLD;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     lds_frag_t lw = (lds_frag_t)smem;
     lds_f32_t lc = (lds_f32_t)(smem + FRAG_END * 16);
@@ -554,17 +572,14 @@ __global__ void __launch_bounds__(MAIN_THREADS, MAIN_WAVES / 4) k_main(MainArgs 
         // registers, all ~20 requests of a wave in flight before the single wait.  Until round 4 this was a
         // load - wait - ds_write loop, one L2 round trip per step: ~10 us per launch - nothing in a 4 ms launch,
         // a third of k_main's 28 us when a lone 20 x 200 alignment gives every wave one tile.
-        // MODE_FIRST only needs the row-statistics operands; the last block only the FFN / out_proj
-        constexpr int lo = (MODE == MODE_FIRST) ? FRAG_WV : 0;
-        constexpr int hi = (MODE == MODE_LAST) ? FRAG_WV : FRAG_END;
-        static_assert(lo % 64 == 0 && hi % 64 == 0 && FRAG_END % 64 == 0, "the image is copied in whole waves");
-        const frag_t* src = a.wimg;
-        const int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
+        // MODE_FIRST only needs the row-statistics operands; the last block only the FFN / out_proj, and the
+        // folded head W1', out_proj and u (W2 stays out)
         const float cv = a.consts[min((int)threadIdx.x, CONST_LEN - 1)];
-#pragma unroll
-        for (int k = 0; k < (hi - lo + MAIN_THREADS - 1) / MAIN_THREADS; ++k) {
-            const int f0 = lo + k * MAIN_THREADS + wv * 64;            // wave-uniform first fragment of this request
-            if (f0 < hi) __builtin_amdgcn_global_load_lds(src + f0 + ln, smem + (size_t)f0 * 16, 16, 0, 0);
+        if (FOLD) {
+            image_to_lds<FRAG_W1, FRAG_W2>(a.wimg, smem);
+            image_to_lds<FRAG_WO, FRAG_U + U_FRAGS>(a.wimg, smem);
+        } else {
+            image_to_lds<(MODE == MODE_FIRST) ? FRAG_WV : 0, LAST ? FRAG_WV : FRAG_END>(a.wimg, smem);
         }
         static_assert(CONST_LEN <= MAIN_THREADS, "one constant per thread");
         if (threadIdx.x < CONST_LEN) reinterpret_cast<float*>(smem + FRAG_END * 16)[threadIdx.x] = cv;
@@ -593,6 +608,7 @@ __global__ void __launch_bounds__(MAIN_THREADS, MAIN_WAVES / 4) k_main(MainArgs 
     // Wv' hi sits 16 KB behind Wo in the image: the same per-lane base, the distance in the 16-bit offset field of
     // ds_read_b128 (one base register less to keep alive across the tile loop)
     lds_frag_t wvp = wop + (FRAG_WV - FRAG_WO);
+    lds_f32_t luh = (lds_f32_t)(smem + FRAG_U * 16) + 16 * h;      // MODE_LAST_FOLD: u of lane half h
 
     {
         // Tiles are dealt in short RUNS of consecutive tiles, round-robin over the waves: at any moment the
@@ -679,6 +695,7 @@ __global__ void __launch_bounds__(MAIN_THREADS, MAIN_WAVES / 4) k_main(MainArgs 
             const int lc_ = lp.l;                      // (clamped) site for gathers
             const size_t tok = lp.tok0 + lp.toff;
             float x[32];
+            float zh[4] = {0.f, 0.f, 0.f, 0.f};        // MODE_LAST_FOLD: the head's pre-activation, four partial chains
 
             if (MODE == MODE_FIRST) {
                 // embedding lookup + pair expansion (model.py:173-175): x = T[a_i] + T[a_j]
@@ -770,8 +787,54 @@ __global__ void __launch_bounds__(MAIN_THREADS, MAIN_WAVES / 4) k_main(MainArgs 
                 }
 
                 PF_TICK(1);
+                if (FOLD) {
+                    // folded head, residual part: hw . x_attn over this lane's 32 channels, in four chains
+                    // (j mod 4) that the hidden loop continues with u . gelu
+#pragma unroll
+                    for (int g = 0; g < 8; ++g) {
+                        const f32x4 w4 = *(lds_f32x4_t)(lch + CONST_HW + 8 * g);
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) zh[i] = fmaf(w4[i], x[4 * g + i], zh[i]);
+                    }
+                }
                 // ---- feed-forward (model.py:101-104): x += W2 gelu(W1' x~ + b1') + b2
-                if (!(a.ablate & 16)) {
+                if (FOLD && !(a.ablate & 16)) {
+                    // folded: GEMM1 + GELU only, z += u . gelu(h), u[r] = (W2^T hw)[row(r, h)] of hidden tile T
+                    // (fp32, lane order: four 16-byte LDS reads per tile, the same for a whole half-wave)
+                    frag_t xb_hi[4], xb_lo[4];
+                    {
+                        float xn[32];
+                        ln_pair(x, xn);
+#pragma unroll
+                        for (int s = 0; s < 4; ++s) split8(&xn[8 * s], xb_hi[s], xb_lo[s]);
+                    }
+                    if (ntask < task1) prefetch(nxt);
+                    PF_TICK(2);
+#pragma unroll 1
+                    for (int T = 0; T < 8; ++T) {
+                        f32x16 ha;
+                        lds_frag_t f1 = w1p + T * 512;
+                        lds_f32_t bp = lch + CONST_B1 + 32 * T;
+                        lds_f32_t up = luh + 32 * T;
+                        PF_OPAQUE(f1); PF_OPAQUE(bp); PF_OPAQUE(up);
+                        load_acc_bias(ha, bp);
+                        frag_t fh = f1[0], fl = f1[64];
+#pragma unroll
+                        for (int s = 0; s < 4; ++s) {
+                            frag_t nh = fh, nl = fl;
+                            if (s < 3) { nh = f1[(s + 1) * 128]; nl = f1[(s + 1) * 128 + 64]; }
+                            mfma3(ha, fh, fl, xb_hi[s], xb_lo[s]);
+                            fh = nh; fl = nl;
+                        }
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) {
+                            const f32x4 u4 = *(lds_f32x4_t)(up + 4 * q);
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) zh[i] = fmaf(u4[i], gelu_scaled(ha[4 * q + i]), zh[i]);
+                        }
+                    }
+                    PF_TICK(3);
+                } else if (!(a.ablate & 16)) {
                     frag_t xb_hi[4], xb_lo[4];
                     {
                         float xn[32];
@@ -830,7 +893,7 @@ __global__ void __launch_bounds__(MAIN_THREADS, MAIN_WAVES / 4) k_main(MainArgs 
                 }
             }
 
-            if (MODE != MODE_LAST && !(a.ablate & 4)) {
+            if (!LAST && !(a.ablate & 4)) {
                 // ---- statistics of the next block's row attention (attention.py:163-190)
                 // Wv' lo fragments (L2) are requested before the residual store for the same reason
                 // (the first WVLO_LDS of the eight live in LDS - all the image has room for; each fragment taken out of
@@ -920,23 +983,27 @@ __global__ void __launch_bounds__(MAIN_THREADS, MAIN_WAVES / 4) k_main(MainArgs 
                         sp[kmap(t, h)] = treduce32(kv, t);      // lane (t, h) owns S_kv[kmap(t, h)]
                     }
                 }
-            } else if (MODE == MODE_LAST) {
+            } else if (LAST) {
                 // ---- head: softplus(w.x + b) summed over sites (model.py:182-185)
                 float z = 0.f;
+                if (FOLD) {
+                    z = pair_sum((zh[0] + zh[1]) + (zh[2] + zh[3])) + lc[CONST_C0];
+                } else {
 #pragma unroll
-                for (int g = 0; g < 8; ++g) {
-                    const f32x4 w4 = *(lds_f32x4_t)(lch + CONST_HW + 8 * g);
+                    for (int g = 0; g < 8; ++g) {
+                        const f32x4 w4 = *(lds_f32x4_t)(lch + CONST_HW + 8 * g);
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) z = fmaf(w4[i], x[4 * g + i], z);
+                        for (int i = 0; i < 4; ++i) z = fmaf(w4[i], x[4 * g + i], z);
+                    }
+                    z = pair_sum(z) + lc[CONST_HB];
                 }
-                z = pair_sum(z) + lc[CONST_HB];
                 const float spz = softplus20(z);
                 const long slot0 = (long)b * a.slots_aln + cur.kt + (FLAT ? cur.r0 : 0);
                 for (int part = 0; part < (straddle ? 2 : 1); ++part) {
                     const float so = half32_sum((valid && lp.in_r1 == (part == 1)) ? spz : 0.f);
                     if (lane == 0) a.outpart[slot0 + part] = so;
                 }
-                if (a.store_x_last && valid) {
+                if (!FOLD && a.store_x_last && valid) {
                     f32x4* xo = reinterpret_cast<f32x4*>(a.x + tok * 64 + 4 * h);
 #pragma unroll
                     for (int g = 0; g < 8; ++g) {

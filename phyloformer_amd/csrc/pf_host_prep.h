@@ -124,6 +124,27 @@ inline void pack_row_stats(const float* wv, const float* wq, const float* wk, ui
     pack_qk_frags(wq, wk, img_tail + (size_t)(FRAG_QK - FRAG_WV) * 8);
 }
 
+// Head fold of the last block (k_main<MODE_LAST_FOLD>).  The head is Conv2d(64 -> 1) + softplus straight on the last
+// block's output x = x_attn + b2 + W2 gelu(h), so its pre-activation is
+//   z = hw . x + hb = hw . x_attn + u . gelu(h) + c0,   u = W2^T hw,  c0 = hw . b2 + hb,
+// and the FFN's output projection is never needed.  `w2_scale` is the factor the image applies to W2 (the device's
+// GELU returns 2 a gelu(h): 1 / (2 a)).  u is stored in lane order u_img[(T * 2 + h) * 16 + r] = u[32 T + kmap(r, h)],
+// the hidden row GEMM1's accumulator register r holds in lane half h; double accumulation, stored as fp32.
+inline void fold_head(const float* w2 /* [E][FF] */, const float* b2, const float* hw, float hb, double w2_scale,
+                      float* u_img /* [FF] */, float* c0) {
+    for (int T = 0; T < FF / 32; ++T)
+        for (int h = 0; h < 2; ++h)
+            for (int r = 0; r < 16; ++r) {
+                const int k = 32 * T + kmap_h(r, h);
+                double acc = 0.0;
+                for (int c = 0; c < E; ++c) acc += (double)hw[c] * (double)w2[(size_t)c * FF + k];
+                u_img[(T * 2 + h) * 16 + r] = (float)(acc * w2_scale);
+            }
+    double acc = (double)hb;
+    for (int c = 0; c < E; ++c) acc += (double)hw[c] * (double)b2[c];
+    *c0 = (float)acc;
+}
+
 struct AttnHost {
     const float *g, *b, *wq, *bq, *wk, *bk, *wv, *bv, *wo, *bo;
 };

@@ -28,7 +28,10 @@ constexpr float LN_EPS = 1e-5f;
 //   Wv' : [2 T][4 s][64] hi only              8 KB   (next block's row V projection; lo: below / L2)
 //   Wqk : [4 s][2][16]                         2 KB   (next block's row q/k rows, 8 of 32 rows)
 //   Wv' lo : [WVLO_LDS of 2 T x 4 s][64]       4 KB   (the first four of the eight lo fragments; the rest from L2)
-//   consts (floats): b1'[256] | b2[64] | bqk[8] | head_w[64] | head_b[1] | pad | bo_col[64]
+//   consts (floats): b1'[256] | b2[64] | bqk[8] | head_w[64] | head_b[1] | c0[1] | pad | bo_col[64]
+// The last block has no next row attention: its [FRAG_WV, FRAG_END) tail holds the folded head instead (FRAG_U),
+// u = W2^T head_w as fp32 in lane order [8 T][2 h][16 r] (hidden row 32 T + kmap(r, h), the row GEMM1's accumulator
+// register r holds), and c0 = head_w . b2 + head_b (pf_host_prep.h, fold_head; k_main<MODE_LAST_FOLD>).
 constexpr int FRAG_W1 = 0;                                   // [8 T][4 s][2 hi/lo][64]
 constexpr int FRAG_W2 = FRAG_W1 + 8 * 4 * 2 * 64;            // [2 To][16 s][2][64]
 constexpr int FRAG_WO = FRAG_W2 + 2 * 16 * 2 * 64;           // [2 To][4 s][2][64]
@@ -41,9 +44,12 @@ constexpr int FRAG_QK = FRAG_WV + 2 * 4 * 64;                // next row attn [W
 constexpr int WVLO_LDS = PF_WVLO_LDS;
 constexpr int FRAG_WVLO = FRAG_QK + 4 * 2 * 16;              // the first WVLO_LDS of Wv' lo's [2 T][4 s] fragments: [..][64]
 constexpr int FRAG_END = FRAG_WVLO + WVLO_LDS * 64;          // in fragment (16-byte) units
+constexpr int FRAG_U = FRAG_WV;                              // last block only: u[8 T][2 h][16 r] fp32 (1 KB)
+constexpr int U_FRAGS = FF * 4 / 16;
+static_assert(FRAG_U + U_FRAGS <= FRAG_END, "the folded head fits the last block's tail");
 constexpr int WVLO_FRAGS = 2 * 4 * 64;                       // lo part of Wv', read from global
 constexpr int CONST_B1 = 0, CONST_B2 = 256, CONST_BQK = 320, CONST_HW = 328, CONST_HB = 392,
-              CONST_BOC = 400;
+              CONST_C0 = 393, CONST_BOC = 400;
 constexpr int CONST_LEN = 464;                                // floats
 constexpr int MAIN_LDS_BYTES = FRAG_END * 16 + CONST_LEN * 4; // 163,648 B of the 163,840 B LDS (159,552 without Wv' lo)
 constexpr int MFRAG_PER_PAIR = 2 * 2 * 32;                    // row-mix fragments per pair (lanes h=0)

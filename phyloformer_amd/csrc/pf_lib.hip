@@ -13,7 +13,7 @@
 //       k_rowfin(k)      per-tile row statistics -> row-mix matrices / fragments of every pair
 //       k_colstats(k)    x (block 0: the embedding table), qrow, mrow -> qcol, column partials (groups or runs)
 //       k_colfin(k)      partials -> ctx
-//       k_main<MID0|MID|LAST>(k)          row + column attention applied, FFN, next block's row statistics / head
+//       k_main<MID0|MID|LAST_FOLD>(k)     row + column attention applied, FFN, next block's row statistics / head
 //   k_outsum                              per-tile head sums -> distances
 //   [all-reduce out]                      site-sharded runs only
 #include <hip/hip_runtime.h>
@@ -176,6 +176,9 @@ struct pf_handle {
     bool debug_keep = false;
     int ablate = 0;
     unsigned long long* phase_prof = nullptr;  // device [8]: k_main per-phase cycle totals (experiments)
+    bool phase_prof_last = false;              // phase_prof = 2: the last block's k_main launch only
+    bool head_fold = true;        // option "head_fold": the last block's FFN output projection folded into the head
+                                  // (k_main<MODE_LAST_FOLD>); 0 = the full FFN (k_main<MODE_LAST>, cross-check)
     bool force_rccl = false;  // tests: create a real 1-rank communicator and run the collectives
     int64_t ws_limit_bytes = (int64_t)24 << 30;  // per-chunk workspace budget
     // weights
@@ -449,6 +452,13 @@ int prepare_weights(pf_handle* h, const pf_weights_t* w) {
         pack_frags(w2s.data(), E, FF, E, img.data() + (size_t)FRAG_W2 * 8);
         pack_frags(cols[k].wo, E, E, E, img.data() + (size_t)FRAG_WO * 8, COLAPPLY_A_SCALE);   // B side carries the inverse
         if (k + 1 < nb) std::copy(row_tail[k + 1].begin(), row_tail[k + 1].end(), img.begin() + (size_t)FRAG_WV * 8);
+        float c0 = 0.f;
+        if (k + 1 == nb) {
+            // the last block's tail (no next row attention) carries the folded head: u = W2^T head_w, c0
+            float u[FF];
+            fold_head(ffn[k].w2, ffn[k].b2, head_w, head_b[0], 1.0 / alpha * 0.5, u, &c0);
+            std::memcpy(img.data() + (size_t)FRAG_U * 8, u, sizeof(u));
+        }
         if ((rc = upload(h, img, &d.wimg))) return rc;
         std::vector<float> cst(CONST_LEN, 0.f);
         std::copy(b1f.begin(), b1f.end(), cst.begin() + CONST_B1);
@@ -456,6 +466,7 @@ int prepare_weights(pf_handle* h, const pf_weights_t* w) {
         if (k + 1 < nb) std::copy(row_bqk[k + 1].begin(), row_bqk[k + 1].end(), cst.begin() + CONST_BQK);
         std::copy(head_w, head_w + E, cst.begin() + CONST_HW);
         cst[CONST_HB] = head_b[0];
+        cst[CONST_C0] = c0;
         std::copy(cols[k].bo, cols[k].bo + E, cst.begin() + CONST_BOC);
         if ((rc = upload(h, cst, &d.consts))) return rc;
     }
@@ -630,7 +641,7 @@ MainArgs main_args(pf_handle* h, const ShardRun& r) {
     m.store_x_last = h->debug_keep ? 1 : 0;
     m.trash_tok = (size_t)r.B * r.P * r.Lloc;
     m.ablate = h->ablate;
-    m.prof = h->phase_prof;
+    m.prof = h->phase_prof_last ? nullptr : h->phase_prof;
     return m;
 }
 
@@ -764,7 +775,20 @@ int phase_block(pf_handle* h, const ShardRun& r, int k, RowStats rs) {
         if (rc) return rc;
     } else {
         m.wv_lo = nullptr;
-        if ((rc = launch_main<MODE_LAST>(h, m, K_MAIN))) return rc;
+        if (h->phase_prof_last) m.prof = h->phase_prof;
+        if (!h->head_fold) {
+            if ((rc = launch_main<MODE_LAST>(h, m, K_MAIN))) return rc;
+        } else {
+            if ((rc = launch_main<MODE_LAST_FOLD>(h, m, K_MAIN))) return rc;
+            if (h->debug_keep) {
+                // the folded head never forms x6: the full FFN writes it for the tap (in place, after the folded
+                // launch has read x5), its head sums go to spart, dead since k_rowfin - the distances stay the folded ones
+                MainArgs md = m;
+                md.outpart = w.spart;
+                md.prof = nullptr;
+                if ((rc = launch_main<MODE_LAST>(h, md, K_MAIN))) return rc;
+            }
+        }
     }
     if (h->debug_keep && (rc = save_tap(h, "x" + std::to_string(k + 1), w.x, (size_t)B * P * Lloc * 64))) return rc;
     return PF_OK;
@@ -1251,10 +1275,12 @@ static int open_device(int device, pf_handle** out) {
             {reinterpret_cast<const void*>(&k_main<MODE_MID, false>), MAIN_LDS_BYTES},
             {reinterpret_cast<const void*>(&k_main<MODE_MID0, false>), MAIN_LDS_BYTES},
             {reinterpret_cast<const void*>(&k_main<MODE_LAST, false>), MAIN_LDS_BYTES},
+            {reinterpret_cast<const void*>(&k_main<MODE_LAST_FOLD, false>), MAIN_LDS_BYTES},
             {reinterpret_cast<const void*>(&k_main<MODE_FIRST, true>), MAIN_LDS_BYTES},
             {reinterpret_cast<const void*>(&k_main<MODE_MID, true>), MAIN_LDS_BYTES},
             {reinterpret_cast<const void*>(&k_main<MODE_MID0, true>), MAIN_LDS_BYTES},
             {reinterpret_cast<const void*>(&k_main<MODE_LAST, true>), MAIN_LDS_BYTES},
+            {reinterpret_cast<const void*>(&k_main<MODE_LAST_FOLD, true>), MAIN_LDS_BYTES},
             {reinterpret_cast<const void*>(&k_embed), EMBED_LDS_BYTES},
         };
         for (const auto& k : big_lds)
@@ -1352,6 +1378,7 @@ int pf_set_option(pf_handle_t* h, const char* key, int64_t value) {
     else if (k == "two_streams") h->two_streams = value != 0;
     else if (k == "reserve_cus") h->reserve_cus = (int)std::max<int64_t>(0, std::min<int64_t>(value, 128));
     else if (k == "ablate") h->ablate = (int)value;
+    else if (k == "head_fold") h->head_fold = value != 0;
     else if (k == "force_rccl") h->force_rccl = value != 0;
     else if (k == "colstats_ring") h->colstats_ring = value != 0;
     else if (k == "precise") h->precise = value < 0 ? -1 : (value != 0);
@@ -1367,6 +1394,7 @@ int pf_set_option(pf_handle_t* h, const char* key, int64_t value) {
         if (value && !h->phase_prof) { HIPCHK(h, hipMalloc((void**)&h->phase_prof, 64)); h->owned.push_back(h->phase_prof); }
         if (h->phase_prof) HIPCHK(h, hipMemset(h->phase_prof, 0, 64));
         if (!value) h->phase_prof = nullptr;
+        h->phase_prof_last = value == 2;
     }
     else if (k == "ws_limit_mb") h->ws_limit_bytes = value << 20;
     else return fail(h, PF_EINVAL, "unknown option '%s'", key);
