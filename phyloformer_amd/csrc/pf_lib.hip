@@ -6,7 +6,7 @@
 // (reference: phyloformer/model.py:166-187).
 //
 // Launch sequence for one batch chunk (nb = n_blocks); a chunk of >= 2 alignments runs it twice, for its two
-// halves, on the two streams (forward_chunk):
+// halves, on the two streams (schedule(), driven by forward_chunk and pf_forward_shards_emulated):
 //   k_embed                               row statistics of block 0 and q' by table lookup (x0 is not written)
 //   for k in 0..nb-1:
 //       [k_rowsum, all-reduce srow]       site-sharded runs only
@@ -508,12 +508,13 @@ struct Workspace {
 };
 constexpr int WS_BUFS = 11;
 
-void colstats_plan(const pf_handle* h, int B, int P, int Lloc, Workspace* w) {
+// The column-statistics plan into w and the buffer offsets of a workspace for B alignments of P pairs x Lloc sites.
+// An empty shard (Lloc = 0) is laid out as one site: it launches nothing and only zero-fills srow.
+size_t workspace_bytes(const pf_handle* h, int B, int P, int Lloc, Workspace* w, size_t off[WS_BUFS]) {
+    Lloc = std::max(Lloc, 1);
     const ColPlan c = colstats_plan_core(B, P, Lloc, h->colstats_fine);
     w->G = c.G; w->sub = c.sub; w->S = c.S; w->fine = c.fine;
-}
-
-size_t workspace_bytes(const pf_handle* h, int B, int P, int Lloc, int nparts, size_t off[WS_BUFS]) {
+    const int nparts = w->nparts();
     const size_t tok = (size_t)B * P * Lloc;
     size_t o = 0;
     off[0] = o; o = align_up(o + (tok + 32) * 64 * 4, 256);              // x (+ 32-token trash area)
@@ -530,11 +531,19 @@ size_t workspace_bytes(const pf_handle* h, int B, int P, int Lloc, int nparts, s
     off[10] = o; o = align_up(o + (size_t)B * P * 4 * 4, 256);         // rq: L / S_q per pair and head
     return o;
 }
+void carve_workspace(char* ws, const size_t off[WS_BUFS], Workspace* w) {
+    w->x = (float*)(ws + off[0]); w->qrow = (float*)(ws + off[1]);
+    w->qcol = (float*)(ws + off[2]); w->srow = (float*)(ws + off[3]);
+    w->mrow = (float*)(ws + off[4]); w->part = (float*)(ws + off[5]);
+    w->ctx = (float*)(ws + off[6]);
+    w->mfrag = (float*)(ws + off[7]);
+    w->spart = (float*)(ws + off[8]); w->outpart = (float*)(ws + off[9]);
+    w->rq = (float*)(ws + off[10]);
+}
 
 int ensure_workspace(pf_handle* h, int B, int P, int Lloc, Workspace* w, bool second = false) {
     size_t off[WS_BUFS];
-    colstats_plan(h, B, P, Lloc, w);
-    const size_t need = workspace_bytes(h, B, P, Lloc, w->nparts(), off);
+    const size_t need = workspace_bytes(h, B, P, Lloc, w, off);
     char*& ws = second ? h->ws2 : h->ws;
     size_t& have = second ? h->ws2_bytes : h->ws_bytes;
     if (need > have) {
@@ -546,13 +555,7 @@ int ensure_workspace(pf_handle* h, int B, int P, int Lloc, Workspace* w, bool se
         HIPCHK(h, hipMalloc((void**)&ws, need));
         have = need;
     }
-    w->x = (float*)(ws + off[0]); w->qrow = (float*)(ws + off[1]);
-    w->qcol = (float*)(ws + off[2]); w->srow = (float*)(ws + off[3]);
-    w->mrow = (float*)(ws + off[4]); w->part = (float*)(ws + off[5]);
-    w->ctx = (float*)(ws + off[6]);
-    w->mfrag = (float*)(ws + off[7]);
-    w->spart = (float*)(ws + off[8]); w->outpart = (float*)(ws + off[9]);
-    w->rq = (float*)(ws + off[10]);
+    carve_workspace(ws, off, w);
     return PF_OK;
 }
 
@@ -623,13 +626,26 @@ int launch_main(pf_handle* h, const MainArgs& a, int kid) {
 }
 
 // ---- the forward pass as phases over one shard's workspace -------------------------------------
+// Row statistics feeding a block: `nparts` partial sums of 72 floats per pair (k_main leaves one per tile,
+// k_embed and the reduced / all-reduced form one).
+struct RowStats { const float* p; int nparts; int flat; };   // flat: k_main's per-part slots (part_range) instead of
+                                                            // nparts consecutive partials per pair
+// An empty shard (Lloc = 0: a rank of L_total < world) launches no kernel; where its kernels would leave row
+// statistics or site sums it leaves zeros, its share of every sum.
 struct ShardRun {
     Workspace w;
     const uint8_t* d_idx;
     float* d_out;
     int B, N, P, Lloc, L_total;
     TilePlan tp;       // k_main's tiling of (P, Lloc), computed once per run
+    hipStream_t stream;    // the stream the run's launches go to
+    RowStats rs;           // where the next block's row statistics are
 };
+
+int zero_fill(pf_handle* h, float* p, size_t n) {
+    HIPCHK(h, hipMemsetAsync(p, 0, n * sizeof(float), h->cur));
+    return PF_OK;
+}
 
 MainArgs main_args(pf_handle* h, const ShardRun& r) {
     MainArgs m{};
@@ -653,6 +669,7 @@ bool x0_on_the_fly(const pf_handle* h) {
 
 // embedding + pair expansion + row statistics of block 0
 int phase_first(pf_handle* h, const ShardRun& r) {
+    if (!r.Lloc) return zero_fill(h, r.w.srow, (size_t)r.B * r.P * SROW);
     int rc;
     if (h->embed_mfma) {
         MainArgs m = main_args(h, r);
@@ -675,17 +692,13 @@ int phase_first(pf_handle* h, const ShardRun& r) {
     return PF_OK;
 }
 
-// Row statistics feeding a block: `nparts` partial sums of 72 floats per pair (k_main leaves one per tile,
-// k_embed and the reduced / all-reduced form one).
-struct RowStats { const float* p; int nparts; int flat; };   // flat: k_main's per-part slots (part_range) instead of
-                                                            // nparts consecutive partials per pair
-
 int tiles_of(int Lloc) { return (Lloc + 31) / 32; }
 
 // per-tile partials -> w.srow (one row per pair): what an all-reduce or a debug tap wants
 int launch_rowsum(pf_handle* h, const ShardRun& r, RowStats* rs) {
     if (rs->p == r.w.srow) return PF_OK;             // already one row per pair, in place
     const int n = r.B * r.P * SROW;
+    if (!r.Lloc) { *rs = RowStats{r.w.srow, 1, 0}; return zero_fill(h, r.w.srow, n); }
     ProfScope ps(h, K_ROWFIN);
     hipLaunchKernelGGL(k_rowsum, dim3((n + 255) / 256), dim3(256), 0, h->cur, rs->p, r.w.srow, r.B * r.P, rs->nparts,
                        rs->flat, r.P, r.Lloc, r.tp.slots_aln);
@@ -697,6 +710,7 @@ int launch_rowsum(pf_handle* h, const ShardRun& r, RowStats* rs) {
 // per-tile head sums of the last block -> distances
 int launch_outsum(pf_handle* h, const ShardRun& r) {
     const int n = r.B * r.P;
+    if (!r.Lloc) return zero_fill(h, r.d_out, n);
     ProfScope ps(h, K_ROWFIN);
     const TilePlan& tp = r.tp;
     hipLaunchKernelGGL(k_outsum, dim3((n + 255) / 256), dim3(256), 0, h->cur, r.w.outpart, r.d_out, n,
@@ -716,6 +730,7 @@ RowStats first_stats(pf_handle* h, const ShardRun& r) {
 
 // block k given its row statistics (already reduced over ranks in a site-sharded run)
 int phase_block(pf_handle* h, const ShardRun& r, int k, RowStats rs) {
+    if (!r.Lloc) return PF_OK;
     const BlockDev& d = h->blk[k];
     const Workspace& w = r.w;
     const int B = r.B, P = r.P, Lloc = r.Lloc;
@@ -794,7 +809,6 @@ int phase_block(pf_handle* h, const ShardRun& r, int k, RowStats rs) {
     return PF_OK;
 }
 
-// one batch chunk, everything resident on the device
 // Does this forward issue collectives?  Only the site-sharded entry points on a handle with a communicator.
 bool reduces_now(const pf_handle* h) { return h->sharded_call && (h->world > 1 || h->comm[0]); }
 // A site-sharded call for an empty site range on a handle whose forward communicates: the rank holds no token
@@ -825,13 +839,42 @@ struct ForwardScope {
     ~ForwardScope() { h->cur = h->stream; h->reducing = false; }
 };
 
+// The schedule of the default kernels over one rank's runs - the one or two half-batches of a chunk, each on its own
+// stream - or over every emulated rank's in rank order.  reduce(site_sums) stands in for the all-reduce of the row
+// statistics (false: it leaves every run's `rs` at the reduced sums) or of the site sums (true: into the buffer the
+// caller reads); without collectives it does nothing and k_rowfin reads the per-tile partials directly.
+template <class Reduce>
+int schedule(pf_handle* h, ShardRun* runs, size_t nruns, Reduce reduce) {
+    ShardRun* const end = runs + nruns;
+    int rc;
+    for (ShardRun* r = runs; r != end; ++r) {
+        h->cur = r->stream;
+        if ((rc = phase_first(h, *r))) return rc;
+        r->rs = first_stats(h, *r);
+    }
+    for (int k = 0; k < h->n_blocks; ++k) {
+        if ((rc = reduce(false))) return rc;
+        for (ShardRun* r = runs; r != end; ++r) {
+            h->cur = r->stream;
+            if ((rc = phase_block(h, *r, k, r->rs))) return rc;
+            r->rs = main_stats(*r);
+        }
+    }
+    for (ShardRun* r = runs; r != end; ++r) {
+        h->cur = r->stream;
+        if ((rc = launch_outsum(h, *r))) return rc;
+    }
+    return reduce(true);
+}
+
 // One batch chunk, everything resident on the device.
 // Site-sharded runs with >= 2 alignments are cut into two half-batches on two streams: the all-reduce of one
 // half (RCCL kernels on a few CUs; the persistent compute kernels leave `reserve_cus` free) runs beside the
 // column statistics / FFN of the other.  Each half is an independent forward, so the results are those of
 // the serial schedule bit for bit; the collectives double in number (2 x (n_blocks + 1)) and halve in size.
 // Single-GPU forwards are cut the same way (option "two_streams"): the halves run free, and whichever is in a
-// kernel tail, a small kernel or a launch gap leaves its CUs to the other.
+// kernel tail, a small kernel or a launch gap leaves its CUs to the other.  An empty rank (Lloc = 0) cuts and
+// reduces exactly as its peers do.
 int forward_chunk(pf_handle* h, const uint8_t* d_idx, int B, int N, int Lloc, int L_total, float* d_out) {
     const int P = N * (N - 1) / 2;
     const bool reduces = reduces_now(h);
@@ -839,44 +882,31 @@ int forward_chunk(pf_handle* h, const uint8_t* d_idx, int B, int N, int Lloc, in
     int rc = ensure_pairs(h, N);
     if (rc) return rc;
     ShardRun r[2]{};
-    RowStats rs[2];
-    hipStream_t st[2] = {h->stream, h->stream};
     int b0 = 0;
     for (int i = 0; i < nh; ++i) {
         const int nb = (nh == 2) ? (i == 0 ? (B + 1) / 2 : B / 2) : B;
-        r[i].d_idx = d_idx + (size_t)b0 * N * Lloc; r[i].d_out = d_out + (size_t)b0 * P;
-        r[i].B = nb; r[i].N = N; r[i].P = P; r[i].Lloc = Lloc; r[i].L_total = L_total;
-        r[i].tp = tile_plan(h, P, Lloc);
+        r[i] = ShardRun{{}, d_idx + (size_t)b0 * N * Lloc, d_out + (size_t)b0 * P, nb, N, P, Lloc, L_total,
+                        tile_plan(h, P, Lloc), h->stream, {}};
         if ((rc = ensure_workspace(h, nb, P, Lloc, &r[i].w, i == 1))) return rc;
         b0 += nb;
     }
     ForwardScope scope(h, reduces);
     if (nh == 2) {
         if ((rc = ensure_second_stream(h))) return rc;
-        st[1] = h->stream2;
+        r[1].stream = h->stream2;
         HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));          // inputs were produced on the main stream
         HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
     }
-    for (int i = 0; i < nh; ++i) {
-        h->cur = st[i];
-        if ((rc = phase_first(h, r[i]))) return rc;
-        rs[i] = first_stats(h, r[i]);
-    }
-    for (int k = 0; k < h->n_blocks; ++k)
-        for (int i = 0; i < nh; ++i) {
-            h->cur = st[i];
-            if (reduces) {                                                 // site-sharded runs only
-                if ((rc = launch_rowsum(h, r[i], &rs[i]))) return rc;
-                if ((rc = allreduce(h, r[i].w.srow, (size_t)r[i].B * P * SROW))) return rc;
-            }
-            if ((rc = phase_block(h, r[i], k, rs[i]))) return rc;
-            rs[i] = main_stats(r[i]);
+    auto reduce = [&](bool site_sums) -> int {                        // site-sharded runs only
+        if (!reduces) return PF_OK;
+        for (ShardRun* q = r; q != r + nh; ++q) {                         // each half on its own stream and communicator
+            h->cur = q->stream;
+            if (!site_sums && (rc = launch_rowsum(h, *q, &q->rs))) return rc;
+            if ((rc = allreduce(h, site_sums ? q->d_out : q->w.srow, (size_t)q->B * P * (site_sums ? 1 : SROW)))) return rc;
         }
-    for (int i = 0; i < nh; ++i) {
-        h->cur = st[i];
-        if ((rc = launch_outsum(h, r[i]))) return rc;
-        if ((rc = allreduce(h, r[i].d_out, (size_t)r[i].B * P))) return rc;
-    }
+        return PF_OK;
+    };
+    if ((rc = schedule(h, r, nh, reduce))) return rc;
     if (nh == 2) {
         HIPCHK(h, hipEventRecord(h->ev_join, h->stream2));         // the caller continues on the main stream
         HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_join, 0));
@@ -928,10 +958,12 @@ struct ShardStage {
 
 #include "pf_f64_host.hip.h"
 
+// What every entry point refuses.  An empty site range (Lloc = 0) is allowed only to a rank that joins its peers'
+// collectives, and it refuses what they refuse - before any collective, so that no peer is left waiting.
 int check_dims(pf_handle* h, int B, int N, int Lloc, int L_total) {
     if (!h) return PF_EINVAL;
     if (h->n_blocks == 0) return fail(h, PF_ESTATE, "handle was created without Phyloformer weights (pf_create_bare)");
-    if (B < 1 || N < 2 || Lloc < 1 || L_total < Lloc)
+    if (B < 1 || N < 2 || Lloc < (empty_rank_call(h, Lloc) ? 0 : 1) || L_total < std::max(Lloc, 1))
         return fail(h, PF_EINVAL, "bad dimensions B=%d N=%d L=%d (L_total=%d)", B, N, Lloc, L_total);
     if (h->max_seqs > 0 && N > h->max_seqs)
         // same condition and wording as adaptable_seq2pair, phyloformer/model.py:24-28
@@ -954,8 +986,7 @@ size_t chunk_bytes(const pf_handle* h, int cb, int P, int Lloc) {
     for (int nb : {b0, b1}) {
         if (nb < 1) continue;
         Workspace w;
-        colstats_plan(h, nb, P, Lloc, &w);
-        total += workspace_bytes(h, nb, P, Lloc, w.nparts(), off);
+        total += workspace_bytes(h, nb, P, Lloc, &w, off);
     }
     return total;
 }
@@ -995,52 +1026,6 @@ int forward_device_impl(pf_handle* h, const uint8_t* d_idx, int B, int N, int l_
         // a partial site range without a communicator would return partial sums divided by L_total
         return fail(h, PF_ESTATE, "site range [%d, %d) of %d needs a communicator (pf_comm_init) to be reduced",
                     l_begin, l_end, L_total);
-    if (h && empty_rank_call(h, Lloc) && B >= 1 && N >= 2 && L_total >= 1) {
-        // A rank that owns no sites (L_total < world) still joins every collective with zeros: the same
-        // chunks, the same halves on the same two streams / communicators and the same counts as its peers
-        // issue (forward_chunk).  (A single-rank `force_rccl` communicator takes the same branch: that is how
-        // tests/test_gpu_sharding.py runs it on one GPU.)
-        if (h->n_blocks == 0) return fail(h, PF_ESTATE, "handle was created without Phyloformer weights (pf_create_bare)");
-        HIPCHK(h, hipSetDevice(h->device));
-        if (const F64Path* f = f64_path_of(h, N, L_total)) return forward_device_f64(h, *f, d_idx, B, N, l_begin, l_end, L_total, d_out);
-        const int P0 = N * (N - 1) / 2;
-        const int cb0 = chunk_batch(h, B, P0, (L_total + h->world - 1) / h->world);
-        ForwardScope scope(h, true);
-        for (int b0 = 0; b0 < B; b0 += cb0) {
-            const int nb0 = std::min(cb0, B - b0);
-            Workspace w0;
-            int rc0 = ensure_workspace(h, nb0, P0, 1, &w0);
-            if (rc0) return rc0;
-            const int nh = halves_of(h, nb0);
-            const int hb[2] = {nh == 2 ? (nb0 + 1) / 2 : nb0, nh == 2 ? nb0 / 2 : 0};
-            hipStream_t st[2] = {h->stream, h->stream};
-            float* zs[2] = {w0.srow, w0.srow + (size_t)hb[0] * P0 * SROW};      // one zero buffer per half
-            float* zo[2] = {d_out + (size_t)b0 * P0, d_out + ((size_t)b0 + hb[0]) * P0};
-            if (nh == 2) {
-                if ((rc0 = ensure_second_stream(h))) return rc0;
-                st[1] = h->stream2;
-                HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));
-                HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
-            }
-            for (int k = 0; k < h->n_blocks; ++k)
-                for (int i = 0; i < nh; ++i) {
-                    h->cur = st[i];
-                    const size_t ns = (size_t)hb[i] * P0 * SROW;
-                    if (hipMemsetAsync(zs[i], 0, ns * sizeof(float), st[i]) != hipSuccess) return fail(h, PF_EHIP, "hipMemsetAsync failed");
-                    if ((rc0 = allreduce(h, zs[i], ns))) return rc0;
-                }
-            for (int i = 0; i < nh; ++i) {
-                h->cur = st[i];
-                if (hipMemsetAsync(zo[i], 0, (size_t)hb[i] * P0 * sizeof(float), st[i]) != hipSuccess) return fail(h, PF_EHIP, "hipMemsetAsync failed");
-                if ((rc0 = allreduce(h, zo[i], (size_t)hb[i] * P0))) return rc0;
-            }
-            if (nh == 2) {
-                HIPCHK(h, hipEventRecord(h->ev_join, h->stream2));
-                HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_join, 0));
-            }
-        }
-        return PF_OK;
-    }
     int rc = check_dims(h, B, N, Lloc, L_total);
     if (rc) return rc;
     if (l_begin < 0 || l_end > L_total) return fail(h, PF_EINVAL, "site range [%d, %d) outside [0, %d)", l_begin, l_end, L_total);
@@ -1048,10 +1033,10 @@ int forward_device_impl(pf_handle* h, const uint8_t* d_idx, int B, int N, int l_
     if (const F64Path* f = f64_path_of(h, N, L_total)) return forward_device_f64(h, *f, d_idx, B, N, l_begin, l_end, L_total, d_out);
     const int P = N * (N - 1) / 2;
     // every rank must cut the batch into the same chunks (one all-reduce sequence per chunk), so the
-    // chunk size is derived from the largest shard, not from this rank's own
-    const int Lmax = h->world > 1 ? (L_total + h->world - 1) / h->world : Lloc;
-    const int cb = chunk_batch(h, B, P, std::max(Lloc, Lmax));
-    if ((rc = trim_workspaces(h, chunk_bytes(h, cb, P, std::max(Lloc, Lmax))))) return rc;
+    // chunk size is derived from the largest shard, not from this rank's own (an empty rank has none)
+    const int Lmax = std::max(Lloc, h->world > 1 || !Lloc ? (L_total + h->world - 1) / h->world : Lloc);
+    const int cb = chunk_batch(h, B, P, Lmax);
+    if ((rc = trim_workspaces(h, chunk_bytes(h, cb, P, Lmax)))) return rc;
     for (int b0 = 0; b0 < B; b0 += cb) {
         const int nbch = std::min(cb, B - b0);
         rc = forward_chunk(h, d_idx + (size_t)b0 * N * Lloc, nbch, N, Lloc, L_total, d_out + (size_t)b0 * P);
@@ -1133,7 +1118,7 @@ int range_recheck(pf_handle* h, float* out, int count, int N, int l_begin, int l
 int forward_host_impl(pf_handle* h, const uint8_t* idx, int B, int N, int l_begin, int l_end,
                       int L_total, float* out) {
     const int Lloc = l_end - l_begin;
-    int rc = empty_rank_call(h, Lloc) ? PF_OK : check_dims(h, B, N, Lloc, L_total);
+    int rc = check_dims(h, B, N, Lloc, L_total);
     if (rc) return rc;
     if (!out || (!idx && Lloc > 0)) return fail(h, PF_EINVAL, "null buffer");
     const size_t nidx = (size_t)B * N * Lloc;
@@ -1623,8 +1608,8 @@ int pf_device_pci(pf_handle_t* h, int32_t* domain, int32_t* bus, int32_t* device
 
 // Single-GPU emulation of the site-sharded forward ("fake backend" for tests): the alignment's
 // sites are split into `nshards` ranges exactly as phyloformer_amd/dist.py::site_range does, every
-// shard gets its own workspace and runs the same kernels as a real rank, and the two collectives
-// are replaced by a device-side sum over the shards' buffers.  idx: host uint8 [B][N][L].
+// non-empty shard gets its own workspace, and the schedule of a real rank runs over all of them in rank order
+// on the main stream, the collectives replaced by device-side sums in rank order.  idx: host uint8 [B][N][L].
 int pf_forward_shards_emulated(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, int32_t L,
                                int32_t nshards, float* out) {
     if (!h) return PF_EINVAL;
@@ -1639,48 +1624,33 @@ int pf_forward_shards_emulated(pf_handle_t* h, const uint8_t* idx, int32_t B, in
     if ((rc = stage.upload(idx, B, N, L, nshards))) return rc;
     std::vector<ShardRun> runs;
     for (const ShardStage::Shard& s : stage.shards) {
-        ShardRun r{};
-        r.B = B; r.N = N; r.P = P; r.Lloc = s.Lloc; r.L_total = L;
+        ShardRun r{{}, s.d_idx, nullptr, B, N, P, s.Lloc, L, tile_plan(h, P, s.Lloc), h->stream, {}};
         size_t off[WS_BUFS];
-        colstats_plan(h, B, P, r.Lloc, &r.w);
-        r.tp = tile_plan(h, P, r.Lloc);
-        char* ws = (char*)stage.alloc(workspace_bytes(h, B, P, r.Lloc, r.w.nparts(), off));
-        float* dout = (float*)stage.alloc((size_t)B * P * sizeof(float));
-        if (!ws || !dout) return fail(h, PF_ENOMEM, "shard workspace allocation failed");
-        r.w.x = (float*)(ws + off[0]); r.w.qrow = (float*)(ws + off[1]); r.w.qcol = (float*)(ws + off[2]);
-        r.w.srow = (float*)(ws + off[3]); r.w.mrow = (float*)(ws + off[4]); r.w.part = (float*)(ws + off[5]);
-        r.w.ctx = (float*)(ws + off[6]); r.w.mfrag = (float*)(ws + off[7]);
-        r.w.spart = (float*)(ws + off[8]); r.w.outpart = (float*)(ws + off[9]);
-        r.w.rq = (float*)(ws + off[10]);
-        r.d_idx = s.d_idx; r.d_out = dout;
+        char* ws = (char*)stage.alloc(workspace_bytes(h, B, P, r.Lloc, &r.w, off));
+        r.d_out = (float*)stage.alloc((size_t)B * P * sizeof(float));
+        if (!ws || !r.d_out) return fail(h, PF_ENOMEM, "shard workspace allocation failed");
+        carve_workspace(ws, off, &r.w);
         runs.push_back(r);
     }
     // the "all-reduced" buffer every emulated rank reads
     float* total = (float*)stage.alloc((size_t)B * P * SROW * sizeof(float));
     if (!total) return fail(h, PF_ENOMEM, "shard sum buffer");
-    auto sum_all = [&](size_t count, bool is_out) {
+    auto reduce = [&](bool site_sums) -> int {
+        const size_t count = (size_t)B * P * (site_sums ? 1 : SROW);
+        for (ShardRun& r : runs)                                   // every rank reduces its own tiles first
+            if (!site_sums && (rc = launch_rowsum(h, r, &r.rs))) return rc;
         hipMemsetAsync(total, 0, count * sizeof(float), h->stream);
-        for (auto& r : runs)
+        for (ShardRun& r : runs) {
             hipLaunchKernelGGL(k_accumulate, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, h->stream,
-                               total, is_out ? r.d_out : r.w.srow, count);
-    };
-    for (auto& r : runs) if ((rc = phase_first(h, r))) break;
-    for (int k = 0; !rc && k < h->n_blocks; ++k) {
-        for (auto& r : runs) {                                     // every rank reduces its own tiles first
-            RowStats rs = k == 0 ? first_stats(h, r) : main_stats(r);
-            if ((rc = launch_rowsum(h, r, &rs))) break;
+                               total, site_sums ? r.d_out : r.w.srow, count);
+            r.rs = RowStats{total, 1, 0};
         }
-        if (rc) break;
-        sum_all((size_t)B * P * SROW, false);                      // stands in for all-reduce #k
-        for (auto& r : runs) if ((rc = phase_block(h, r, k, RowStats{total, 1, 0}))) break;
-    }
-    if (!rc) for (auto& r : runs) if ((rc = launch_outsum(h, r))) break;
-    if (!rc) {
-        sum_all((size_t)B * P, true);                              // final all-reduce of the site sums
-        if (hipMemcpyAsync(out, total, (size_t)B * P * sizeof(float), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-            hipStreamSynchronize(h->stream) != hipSuccess)
-            rc = fail(h, PF_EHIP, "result copy failed");
-    }
+        return PF_OK;
+    };
+    rc = schedule(h, runs.data(), runs.size(), reduce);
+    if (!rc && (hipMemcpyAsync(out, total, (size_t)B * P * sizeof(float), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+                hipStreamSynchronize(h->stream) != hipSuccess))
+        rc = fail(h, PF_EHIP, "result copy failed");
     return rc;
 }
 

@@ -212,3 +212,22 @@ def test_empty_rank_joins_every_collective_with_zeros(weights, golden):
         assert np.array_equal(e.forward_sharded(a, 0, 200, 200), ref)       # full range again: a normal forward
         e.comm_destroy()
         assert np.array_equal(e.forward(a), ref)
+
+
+def test_empty_rank_refuses_what_its_peers_refuse(weights):
+    """An empty rank runs its peers' validation: where the ranks that hold sites return PF_EINVAL before any
+    collective (here n_seqs above max_seqs, or a site range past L_total), the empty rank does too, instead of
+    waiting in all-reduces that no peer will join."""
+    from phyloformer_amd.engine import Engine
+    with Engine(weights("pf"), 0) as e:
+        e.set_option("force_rccl", 1)
+        e.comm_init(e.unique_id(), 0, 1)
+        e.profile_reset()
+        with pytest.raises(ValueError):
+            e.forward_sharded(np.zeros((1, 201, 0), np.uint8), 200, 200, 200)
+        d_out = e.malloc(190 * 4)
+        with pytest.raises(ValueError):
+            e.forward_sharded_device(0, 1, 20, 201, 201, 200, d_out)
+        e.free(d_out)
+        assert e.collective_count() == 0
+        e.comm_destroy()
