@@ -10,8 +10,8 @@
 //   head -> [all-reduce osum, double] -> out
 // One stream, n_blocks + 1 collectives in a site-sharded run (never cut into halves: every rank selects the path from
 // (N, L_total) and the architecture alone, so all ranks issue the same sequence).  The two paths differ only in the
-// leaves (F64Path): the launches of embed, attention statistics, apply, FFN and head with their own kernels; the tail
-// kernels (stats_fin, out, accumulate, narrow) are pfg's for both.
+// leaves (F64Path): the launches of attention statistics, apply and FFN with their own kernels; embed, head and the
+// tail kernels (stats_fin, out, accumulate, narrow) are pfg's for both.
 
 // Which alignments take the float64 path: a function of the alignment's global shape only (never of the batch).
 //   L_total < PRECISE_MAX_SITES : rows shorter than one 32-site tile of k_main.  The distance is a MEAN over sites, and
@@ -52,7 +52,7 @@ bool use_generic(const pf_handle* h) { return h->arch_generic || h->generic; }
 
 // ---- precise weights: widened to double, transposed for lane = channel access ---------------------------
 
-int prepare_precise_weights(pf_handle* h, const pf_weights_t* w, PreciseWeights* out) {
+int prepare_precise_weights(pf_handle* h, const BlobView& view, PreciseWeights* out) {
     std::vector<double> D;
     auto put = [&D](size_t n) { const size_t o = D.size(); D.resize(o + n); return o; };
     auto copy = [&](const float* src, size_t n) { const size_t o = put(n); for (size_t i = 0; i < n; ++i) D[o + i] = (double)src[i]; return o; };
@@ -61,19 +61,14 @@ int prepare_precise_weights(pf_handle* h, const pf_weights_t* w, PreciseWeights*
         for (int m = 0; m < M; ++m) for (int k = 0; k < K; ++k) D[o + (size_t)k * M + m] = (double)src[(size_t)m * K + k];
         return o;
     };
-    Blob bl{w->blob};
-    const float* emb_w = bl.take((size_t)E * NA);
-    const float* emb_b = bl.take(E);
     const size_t o_table = put((size_t)NA * E);
-    for (int a = 0; a < NA; ++a)
-        for (int c = 0; c < E; ++c) D[o_table + (size_t)a * E + c] = std::max((double)emb_w[c * NA + a] + (double)emb_b[c], 0.0);
+    build_embed_table(view, E, E, &D[o_table]);
     struct AO { size_t g, b, wqk, bqk, wvT, bv, woT, bo, a72; };
     struct FO { size_t g, b, w1T, b1, w2T, b2, a1, a2; };
-    const int nb = w->n_blocks;
+    const int nb = (int)view.ffn.size();
     std::vector<AO> ro(nb), co(nb);
     std::vector<FO> fo(nb);
-    auto attn = [&](AO& o) {
-        const AttnHost a = take_attn(bl);
+    auto attn = [&](const AttnHost& a, AO& o) {
         o.g = copy(a.g, E); o.b = copy(a.b, E);
         o.wqk = copy(a.wq, (size_t)NH * E); copy(a.wk, (size_t)NH * E);      // rows 0..3 Wq, 4..7 Wk, contiguous
         o.bqk = copy(a.bq, NH); copy(a.bk, NH);
@@ -93,13 +88,13 @@ int prepare_precise_weights(pf_handle* h, const pf_weights_t* w, PreciseWeights*
                 }
     };
     for (int k = 0; k < nb; ++k) {
-        attn(ro[k]);
-        attn(co[k]);
-        const float *g = bl.take(E), *b = bl.take(E), *w1 = bl.take((size_t)FF * E), *b1 = bl.take(FF),
-                    *w2 = bl.take((size_t)E * FF), *b2 = bl.take(E);
-        fo[k].g = copy(g, E); fo[k].b = copy(b, E);
-        fo[k].w1T = transposed(w1, FF, E); fo[k].b1 = copy(b1, FF);
-        fo[k].w2T = transposed(w2, E, FF); fo[k].b2 = copy(b2, E);
+        attn(view.row[k], ro[k]);
+        attn(view.col[k], co[k]);
+        const FfnHost& f = view.ffn[k];
+        const float *w1 = f.w1, *w2 = f.w2;
+        fo[k].g = copy(f.g, E); fo[k].b = copy(f.b, E);
+        fo[k].w1T = transposed(w1, FF, E); fo[k].b1 = copy(f.b1, FF);
+        fo[k].w2T = transposed(w2, E, FF); fo[k].b2 = copy(f.b2, E);
         // v_mfma_f64_16x16x4_f64 A fragments of kp_ffn_mfma (layouts: pf_precise.hip.h::FfnW)
         fo[k].a1 = put((size_t)16 * 16 * 64);
         for (int T = 0; T < 16; ++T)
@@ -116,13 +111,13 @@ int prepare_precise_weights(pf_handle* h, const pf_weights_t* w, PreciseWeights*
                             (double)w2[(size_t)(16 * (i & 3) + 4 * tc + (i >> 2)) * FF + 16 * T + kq + 4 * r];
                     }
     }
-    const size_t o_hw = copy(bl.take(E), E), o_hb = copy(bl.take(1), 1);
+    const size_t o_hw = copy(view.head_w, E), o_hb = copy(view.head_b, 1);
     float* dev = nullptr;
     int rc = upload(h, D, &dev);
     if (rc) return rc;
     const double* base = reinterpret_cast<const double*>(dev);
     out->blob = reinterpret_cast<double*>(dev);
-    out->table = base + o_table;
+    out->ends = {base + o_table, base + o_hw, base + o_hb};
     auto A = [&](const AO& o) { return pfp::AttnW{base + o.g, base + o.b, base + o.wqk, base + o.bqk, base + o.wvT, base + o.bv, base + o.woT, base + o.bo, base + o.a72}; };
     for (int k = 0; k < nb; ++k) {
         out->row.push_back(A(ro[k]));
@@ -130,12 +125,11 @@ int prepare_precise_weights(pf_handle* h, const pf_weights_t* w, PreciseWeights*
         out->ffn.push_back(pfp::FfnW{base + fo[k].g, base + fo[k].b, base + fo[k].w1T, base + fo[k].b1, base + fo[k].w2T, base + fo[k].b2,
                                     base + fo[k].a1, base + fo[k].a2});
     }
-    out->hw = base + o_hw; out->hb = base + o_hb;
     return PF_OK;
 }
 
 // ---- generic weights: widened to double, padded, swizzled into A-fragment order -------------------------
-int prepare_generic_weights(pf_handle* h, const float* blob) {
+int prepare_generic_weights(pf_handle* h, const BlobView& view) {
     const pfg::Arch& ar = h->garch;
     const int E = ar.E, H = ar.NH, Ep = ar.Ep, FF = 4 * E, FFp = ar.FFp, S = Ep / 4;
     std::vector<double> D;
@@ -152,22 +146,16 @@ int prepare_generic_weights(pf_handle* h, const float* blob) {
                 }
         return o;
     };
-    Blob bl{blob};
-    const float* emb_w = bl.take((size_t)E * NA);
-    const float* emb_b = bl.take(E);
     const size_t o_table = put((size_t)NA * Ep);
-    for (int a = 0; a < NA; ++a)
-        for (int c = 0; c < E; ++c) D[o_table + (size_t)a * Ep + c] = std::max((double)emb_w[c * NA + a] + (double)emb_b[c], 0.0);
+    build_embed_table(view, E, Ep, &D[o_table]);
     struct AO { size_t g, b, af, bf, ao, bo; };
     struct FO { size_t g, b, a1, b1, a2, b2; };
     const int nb = h->n_blocks;
     std::vector<AO> ro(nb), co(nb);
     std::vector<FO> fo(nb);
-    auto attn = [&](AO& o) {
-        const float *g = bl.take(E), *b = bl.take(E), *wq = bl.take((size_t)H * E), *bq = bl.take(H),
-                    *wk = bl.take((size_t)H * E), *bk = bl.take(H), *wv = bl.take((size_t)E * E), *bv = bl.take(E),
-                    *wo = bl.take((size_t)E * E), *bo = bl.take(E);
-        o.g = padded(g, E, Ep); o.b = padded(b, E, Ep);
+    auto attn = [&](const AttnHost& a, AO& o) {
+        const float *wq = a.wq, *wk = a.wk, *wv = a.wv, *wo = a.wo;
+        o.g = padded(a.g, E, Ep); o.b = padded(a.b, E, Ep);
         // fused [Wv (rows 0..Ep-1, zero past E); Wq (rows Ep..Ep+H-1); Wk (rows Ep+H..Ep+2H-1)]
         o.af = frags(ar.MF / 16, ar.MF, E, [&](int i, int k) {
             if (i < Ep) return i < E ? (double)wv[(size_t)i * E + k] : 0.0;
@@ -175,19 +163,19 @@ int prepare_generic_weights(pf_handle* h, const float* blob) {
             return r < H ? (double)wq[(size_t)r * E + k] : r < 2 * H ? (double)wk[(size_t)(r - H) * E + k] : 0.0;
         });
         o.bf = put(ar.MF);
-        for (int c = 0; c < E; ++c) D[o.bf + c] = (double)bv[c];
-        for (int r = 0; r < H; ++r) { D[o.bf + Ep + r] = (double)bq[r]; D[o.bf + Ep + H + r] = (double)bk[r]; }
+        for (int c = 0; c < E; ++c) D[o.bf + c] = (double)a.bv[c];
+        for (int r = 0; r < H; ++r) { D[o.bf + Ep + r] = (double)a.bq[r]; D[o.bf + Ep + H + r] = (double)a.bk[r]; }
         o.ao = frags(Ep / 16, E, E, [&](int i, int k) { return (double)wo[(size_t)i * E + k]; });
-        o.bo = padded(bo, E, Ep);
+        o.bo = padded(a.bo, E, Ep);
     };
     for (int k = 0; k < nb; ++k) {
-        attn(ro[k]);
-        attn(co[k]);
-        const float *g = bl.take(E), *b = bl.take(E), *w1 = bl.take((size_t)FF * E), *b1 = bl.take(FF),
-                    *w2 = bl.take((size_t)E * FF), *b2 = bl.take(E);
-        fo[k].g = padded(g, E, Ep); fo[k].b = padded(b, E, Ep);
+        attn(view.row[k], ro[k]);
+        attn(view.col[k], co[k]);
+        const FfnHost& f = view.ffn[k];
+        const float *w1 = f.w1, *w2 = f.w2;
+        fo[k].g = padded(f.g, E, Ep); fo[k].b = padded(f.b, E, Ep);
         fo[k].a1 = frags(FFp / 16, FF, E, [&](int i, int kk) { return (double)w1[(size_t)i * E + kk]; });
-        fo[k].b1 = padded(b1, FF, FFp);
+        fo[k].b1 = padded(f.b1, FF, FFp);
         // a2[T][Tc][r][lane] = W2[16 Tc + (lane & 15)][16 T + (lane >> 4) + 4 r]
         const int TV = Ep / 16, TH = FFp / 16;
         fo[k].a2 = put((size_t)TH * TV * 4 * 64);
@@ -199,23 +187,22 @@ int prepare_generic_weights(pf_handle* h, const float* blob) {
                         if (c < E && hu < FF)
                             D[fo[k].a2 + (((size_t)T * TV + Tc) * 4 + r) * 64 + lane] = (double)w2[(size_t)c * FF + hu];
                     }
-        fo[k].b2 = padded(b2, E, Ep);
+        fo[k].b2 = padded(f.b2, E, Ep);
     }
-    const size_t o_hw = padded(bl.take(E), E, Ep), o_hb = padded(bl.take(1), 1, 1);
+    const size_t o_hw = padded(view.head_w, E, Ep), o_hb = padded(view.head_b, 1, 1);
     HIPCHK(h, pfg::set_lds_limits());
     float* dev = nullptr;
     int rc = upload(h, D, &dev);
     if (rc) return rc;
     const double* base = reinterpret_cast<const double*>(dev);
     GenericWeights& gw = h->gw;
-    gw.table = base + o_table;
+    gw.ends = {base + o_table, base + o_hw, base + o_hb};
     for (int k = 0; k < nb; ++k) {
         auto A = [&](const AO& o) { return pfg::AttnW{base + o.g, base + o.b, base + o.af, base + o.bf, base + o.ao, base + o.bo}; };
         gw.row.push_back(A(ro[k]));
         gw.col.push_back(A(co[k]));
         gw.ffn.push_back(pfg::FfnW{base + fo[k].g, base + fo[k].b, base + fo[k].a1, base + fo[k].b1, base + fo[k].a2, base + fo[k].b2});
     }
-    gw.hw = base + o_hw; gw.hb = base + o_hb;
     gw.ready = true;
     h->blob_copy.clear();
     h->blob_copy.shrink_to_fit();
@@ -226,7 +213,7 @@ int prepare_generic_weights(pf_handle* h, const float* blob) {
 int ensure_generic_weights(pf_handle* h) {
     if (h->gw.ready) return PF_OK;
     if (h->blob_copy.empty()) return fail(h, PF_ESTATE, "generic weight image unavailable");
-    return prepare_generic_weights(h, h->blob_copy.data());
+    return prepare_generic_weights(h, read_blob(h->blob_copy.data(), h->n_blocks, h->garch.E, h->garch.NH));
 }
 
 // ---- workspace (the float64 paths share h->wsp: a handle runs one of them at a time, on one stream) -------
@@ -259,15 +246,8 @@ int ensure_f64_workspace(pf_handle* h, const F64Dims& d, int B, int P, int Lloc,
     size_t off[F64_BUFS];
     const size_t need = f64_bytes(d, B, P, Lloc, off);
     if (need > h->wsp_bytes) {
-        if (h->wsp) { HIPCHK(h, hipStreamSynchronize(h->stream)); hipFree(h->wsp); h->wsp = nullptr; h->wsp_bytes = 0; }
-        // the default path's workspaces give way when the three would not fit the budget together (trim_workspaces
-        // does the same for this one from the other side)
-        if (h->ws_bytes + h->ws2_bytes + need > std::max(need, (size_t)h->ws_limit_bytes)) {
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            if (h->stream2) HIPCHK(h, hipStreamSynchronize(h->stream2));
-            if (h->ws) { hipFree(h->ws); h->ws = nullptr; h->ws_bytes = 0; }
-            if (h->ws2) { hipFree(h->ws2); h->ws2 = nullptr; h->ws2_bytes = 0; }
-        }
+        const int rc = make_room(h, true, need);
+        if (rc) return rc;
         HIPCHK(h, hipMalloc((void**)&h->wsp, need));
         h->wsp_bytes = need;
     }
@@ -285,27 +265,25 @@ struct F64Run {
     size_t ntok() const { return (size_t)B * P * Lloc; }
 };
 
-// What differs between the two float64 paths: the launches of their own kernels with their own argument structs.
+// What differs between the two float64 paths: their weight images and the launches of their own kernels with their
+// own argument structs.
 // The launches are asynchronous on h->cur; the shared code below brackets and checks them.
 struct F64Path {
     int prof;                                       // profile slot: K_PRECISE / K_GENERIC
     F64Dims (*dims)(const pf_handle*);
     int (*prepare)(pf_handle*);                     // the weight image is ready before any forward
     int (*stats_chunk)(const pf_handle*);           // elements of the reduce axis per statistics block
-    void (*embed)(pf_handle*, const F64Run&, size_t grid);
+    const F64Ends* (*ends)(const pf_handle*);       // what the shared embed and head kernels read
     void (*stats)(pf_handle*, const F64Run&, int k, int col, size_t grid, int nchunk);
     void (*apply)(pf_handle*, const F64Run&, int k, int col, const double* stats, size_t grid, int nchunk);
     void (*ffn)(pf_handle*, const F64Run&, int k);
-    void (*head)(pf_handle*, const F64Run&);
 };
 
 F64Dims precise_dims(const pf_handle*) { return {pfp::E, pfp::E, pfp::NH, pfp::SROW}; }
 int precise_prepare(pf_handle*) { return PF_OK; }
 // the VALU statistics kernel (option "precise_ffn_valu") reduces chunks of CHUNK elements, the MFMA one of CHUNK_MFMA
 int precise_stats_chunk(const pf_handle* h) { return h->precise_ffn_valu ? pfp::CHUNK : pfp::CHUNK_MFMA; }
-void precise_embed(pf_handle* h, const F64Run& r, size_t grid) {
-    pfp::launch_embed(h->cur, grid, {r.d_idx, h->pair_i, h->pair_j, h->pw.table, r.w.x, r.B, r.N, r.P, r.Lloc, h->bad_idx_dev});
-}
+const F64Ends* precise_ends(const pf_handle* h) { return &h->pw.ends; }
 void precise_stats(pf_handle* h, const F64Run& r, int k, int col, size_t grid, int nchunk) {
     const pfp::AttnW& w = col ? h->pw.col[k] : h->pw.row[k];
     pfp::launch_attn_stats(h->cur, grid, {r.w.x, r.w.q, r.w.part, w, col, r.P, r.Lloc, nchunk}, h->precise_ffn_valu);
@@ -317,17 +295,12 @@ void precise_apply(pf_handle* h, const F64Run& r, int k, int col, const double* 
 void precise_ffn(pf_handle* h, const F64Run& r, int k) {
     pfp::launch_ffn(h->cur, {r.w.x, h->pw.ffn[k], r.ntok()}, h->precise_ffn_valu);
 }
-void precise_head(pf_handle* h, const F64Run& r) {
-    pfp::launch_head(h->cur, {r.w.x, h->pw.hw, h->pw.hb, r.w.osum, r.B * r.P, r.Lloc});
-}
-const F64Path PRECISE_F64 = {K_PRECISE, precise_dims, precise_prepare, precise_stats_chunk, precise_embed,
-                             precise_stats, precise_apply, precise_ffn, precise_head};
+const F64Path PRECISE_F64 = {K_PRECISE, precise_dims, precise_prepare, precise_stats_chunk, precise_ends,
+                             precise_stats, precise_apply, precise_ffn};
 
 F64Dims generic_dims(const pf_handle* h) { return {h->garch.Ep, h->garch.E, h->garch.NH, h->garch.SR}; }
 int generic_stats_chunk(const pf_handle*) { return pfg::CHUNK; }
-void generic_embed(pf_handle* h, const F64Run& r, size_t grid) {
-    pfg::launch_embed(h->cur, grid, {r.d_idx, h->pair_i, h->pair_j, h->gw.table, r.w.x, r.B, r.N, r.P, r.Lloc, h->garch.Ep, h->bad_idx_dev});
-}
+const F64Ends* generic_ends(const pf_handle* h) { return &h->gw.ends; }
 void generic_stats(pf_handle* h, const F64Run& r, int k, int col, size_t grid, int nchunk) {
     const pfg::AttnW& w = col ? h->gw.col[k] : h->gw.row[k];
     pfg::launch_attn_stats(h->cur, grid, {r.w.x, r.w.q, r.w.part, w, h->garch, col, r.P, r.Lloc, nchunk});
@@ -337,11 +310,8 @@ void generic_apply(pf_handle* h, const F64Run& r, int k, int col, const double* 
     pfg::launch_attn_apply(h->cur, grid, {r.w.x, r.w.q, stats, w, h->garch, col, r.P, r.Lloc, nchunk, col ? (double)r.P : (double)r.L_total});
 }
 void generic_ffn(pf_handle* h, const F64Run& r, int k) { pfg::launch_ffn(h->cur, {r.w.x, h->gw.ffn[k], h->garch, r.ntok()}); }
-void generic_head(pf_handle* h, const F64Run& r) {
-    pfg::launch_head(h->cur, {r.w.x, h->gw.hw, h->gw.hb, r.w.osum, r.B * r.P, r.Lloc, h->garch.Ep});
-}
-const F64Path GENERIC_F64 = {K_GENERIC, generic_dims, ensure_generic_weights, generic_stats_chunk, generic_embed,
-                             generic_stats, generic_apply, generic_ffn, generic_head};
+const F64Path GENERIC_F64 = {K_GENERIC, generic_dims, ensure_generic_weights, generic_stats_chunk, generic_ends,
+                             generic_stats, generic_apply, generic_ffn};
 
 // The kernels an alignment of (N, L_total) runs on: a float64 path, or nullptr for the default kernels.
 const F64Path* f64_path_of(const pf_handle* h, int N, int L_total) {
@@ -362,7 +332,9 @@ const F64Path* f64_path_of(const pf_handle* h, int N, int L_total) {
 int f64_embed(pf_handle* h, const F64Run& r) {
     if (!r.ntok()) return PF_OK;
     const size_t blocks = (r.ntok() * r.d.C + 255) / 256;
-    PF_F64LAUNCH(h, r, r.path->embed(h, r, std::min<size_t>(blocks, 1u << 20)));
+    const pfg::EmbedArgs a{r.d_idx, h->pair_i, h->pair_j, r.path->ends(h)->table, r.w.x, r.B, r.N, r.P, r.Lloc, r.d.C,
+                           h->bad_idx_dev};
+    PF_F64LAUNCH(h, r, pfg::launch_embed(h->cur, std::min<size_t>(blocks, 1u << 20), a));
     return PF_OK;
 }
 // statistics of one axis into `stats` ([lines][SR]); an empty shard contributes zeros
@@ -405,7 +377,10 @@ int f64_local(pf_handle* h, const F64Run& r, int k) {
 }
 int f64_head(pf_handle* h, const F64Run& r) {
     if (!r.ntok()) { HIPCHK(h, hipMemsetAsync(r.w.osum, 0, (size_t)r.B * r.P * 8, h->cur)); return PF_OK; }
-    PF_F64LAUNCH(h, r, r.path->head(h, r));
+    const F64Ends& e = *r.path->ends(h);
+    // (the precise path keeps its own instance: its dot product rounds differently from the generic one's at Ep = 64)
+    PF_F64LAUNCH(h, r, pfg::launch_head(h->cur, {r.w.x, e.hw, e.hb, r.w.osum, r.B * r.P, r.Lloc, r.d.C},
+                                        r.path->prof == K_PRECISE));
     return PF_OK;
 }
 // The schedule, over one rank's run or over every emulated rank's in rank order.  reduce(osum, &sum) stands in for

@@ -1,48 +1,10 @@
 // Kernels of the GENERIC (float64, any embed_dim / n_heads) path; rationale and layouts: pf_generic.hip.h, the
 // host-side sequence: pf_f64_host.hip.h.
 #include "pf_generic.hip.h"
+#include "pf_f64_common.hip.h"
 
 namespace pfg {
-
-typedef double d4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-// sum over the 16 token lanes j of a lane group (fixed butterfly: the same bits on every run)
-__device__ __forceinline__ double sum16(double v) {
-#pragma unroll
-    for (int m = 1; m < 16; m <<= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-__device__ __forceinline__ double elu1(double z) { return z > 0.0 ? z + 1.0 : exp(z); }   // attention.py:179-180
-
-// erf-GELU in double, branch-free (the approximation and its error bound are those of pf_precise.hip::gelu_f64:
-// |error| <= 1.8e-15 over |h| <= 40 against 0.5 h (1 + erf(h / sqrt 2)) evaluated in double)
-__device__ __forceinline__ double gelu_f64(double h) {
-    constexpr double Q[23] = {0x1.e361ea6fba145p-2, -0x1.8c18f2086e47cp-4, 0x1.cabd72a6120b9p-7, 0x1.d4969f10f90d4p-6,
-                              -0x1.07c3c25842975p-5, 0x1.25dd720375999p-6, -0x1.47d5fc6944b2cp-8, -0x1.2b7f5644197fap-12,
-                              0x1.6c5380196e928p-11, -0x1.8c1283b1235e3p-14, -0x1.707b3dae24d79p-14, 0x1.64919115d4a57p-16,
-                              0x1.c9344f4725c3dp-17, -0x1.cdc5363466f39p-19, -0x1.5e69413cc4adcp-19, 0x1.c1cd90ff96cf7p-22,
-                              0x1.26fb2b6228421p-21, -0x1.005dbc607bf3dp-26, -0x1.d50a583370aa4p-24, -0x1.1cca57b6a492fp-27,
-                              0x1.241e7aeedd9aap-26, 0x1.b830e247ca68bp-30, -0x1.925d735408ab7p-30};
-    const double u = fabs(h);
-    const double r = 1.0 / ((u + 4.0) * (u + 1.0));
-    const double t = (u - 4.0) * (u + 1.0) * r;
-    double p = Q[22];
-#pragma unroll
-    for (int k = 21; k >= 0; --k) p = fma(p, t, Q[k]);
-    const double q = exp(-0.5 * u * u) * p * (u + 4.0) * r;
-    return fmax(h, 0.0) - u * q;
-}
-
-__device__ __forceinline__ size_t token_of(int col, int line, int e, int P, int L) {
-    if (!col) return (size_t)line * L + e;                       // line = b * P + p, e = l
-    const int b = line / L, l = line - b * L;                    // line = b * L + l, e = p
-    return ((size_t)b * P + e) * L + l;
-}
+using namespace pf64;
 
 // Stage the 16 tokens tok[0..15] (valid[j] = 0: a zero row) into xs[j][c] (row stride Ep + 1) and apply
 // nn.LayerNorm(E) (biased variance, eps inside the sqrt, model.py:64-66) with the TRUE E: channels E..Ep-1 become 0.
@@ -58,14 +20,10 @@ __device__ void stage_ln(double* xs, const double* x, const size_t* tok, const i
     double* row = xs + j * XS;
     double s = 0.0;
     for (int c = g; c < E; c += 4) s += row[c];
-    s += __shfl_xor(s, 16, 64);
-    s += __shfl_xor(s, 32, 64);
-    const double mu = s / (double)E;
+    const double mu = ln_mean(s, Over{E});
     double v = 0.0;
     for (int c = g; c < E; c += 4) { const double d = row[c] - mu; v = fma(d, d, v); }
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    const double sd = sqrt(v / (double)E + 1e-5);
+    const double sd = ln_sd(v, Over{E});
     for (int c = g; c < Ep; c += 4) row[c] = c < E ? (row[c] - mu) / sd * gam[c] + bet[c] : 0.0;
     __syncthreads();
 }
@@ -81,18 +39,22 @@ __device__ __forceinline__ d4 tile_mfma(const double* frag, const double* xs, in
 }
 
 // ---- embedding + pair expansion (model.py:138-143, 173-175) ------------------------------------
+// EP: the channel count at compile time (64: the precise path and a generic (64, 4) handle keep shifts and masks
+// instead of divisions), 0 = a.Ep at run time.
+template <int EP>
 __global__ void __launch_bounds__(256) kg_embed(EmbedArgs a) {
-    const size_t total = (size_t)a.B * a.P * a.L * a.Ep;
+    const int Ep = EP ? EP : a.Ep;
+    const size_t total = (size_t)a.B * a.P * a.L * Ep;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const size_t tok = i / a.Ep;
-        const int c = (int)(i - tok * a.Ep);
+        const size_t tok = i / Ep;
+        const int c = (int)(i - tok * Ep);
         const int l = (int)(tok % a.L);
         const size_t bp = tok / a.L;
         const int p = (int)(bp % a.P), b = (int)(bp / a.P);
         int ri = a.idx[((size_t)b * a.N + a.pi[p]) * a.L + l], rj = a.idx[((size_t)b * a.N + a.pj[p]) * a.L + l];
         if ((ri >= NA || rj >= NA) && a.bad) *a.bad = 1u;          // sticky flag, as k_embed (pf_device.hip.h)
         ri = min(ri, NA - 1); rj = min(rj, NA - 1);
-        a.x[i] = a.table[ri * a.Ep + c] + a.table[rj * a.Ep + c];
+        a.x[i] = a.table[ri * Ep + c] + a.table[rj * Ep + c];
     }
 }
 
@@ -274,15 +236,20 @@ __global__ void __launch_bounds__(WAVE) kg_ffn(FfnArgs a) {
 }
 
 // ---- head (model.py:158-164, 182-185): per pair, sum over this rank's sites of softplus(w . x + b) ------
+// EP = 0: any a.Ep, a lane's channels by an FMA chain from 0 (the generic path, at Ep = 64 too).  EP = 64: the precise
+// path, lane = channel: the lane's term is a plain product, which hipcc contracts into wave_sum's first addition
+// (fma(w, x, the partner lane's rounded product)) - other bits than the chain's, and the precise path's since round 5.
+template <int EP>
 __global__ void __launch_bounds__(256) kg_head(HeadArgs a) {
+    const int Ep = EP ? EP : a.Ep;
     const int lane = threadIdx.x & 63, line = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (line >= a.nlines) return;
     const double hb = a.hb[0];
     double acc = 0.0;
     for (int l = 0; l < a.L; ++l) {
-        const double* xt = a.x + ((size_t)line * a.L + l) * a.Ep;
-        double d = 0.0;
-        for (int c = lane; c < a.Ep; c += 64) d = fma(a.hw[c], xt[c], d);
+        const double* xt = a.x + ((size_t)line * a.L + l) * Ep;
+        double d = EP ? a.hw[lane] * xt[lane] : 0.0;
+        for (int c = EP ? EP : lane; c < Ep; c += 64) d = fma(a.hw[c], xt[c], d);
         const double z = wave_sum(d) + hb;
         acc += z > 20.0 ? z : log1p(exp(z));                      // nn.Softplus(beta = 1, threshold = 20)
     }
@@ -321,7 +288,9 @@ hipError_t set_lds_limits() {
 }
 
 static dim3 grid_of(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
-void launch_embed(hipStream_t s, size_t grid, const EmbedArgs& a) { hipLaunchKernelGGL(kg_embed, dim3((unsigned)grid), dim3(256), 0, s, a); }
+void launch_embed(hipStream_t s, size_t grid, const EmbedArgs& a) {
+    hipLaunchKernelGGL(a.Ep == 64 ? kg_embed<64> : kg_embed<0>, dim3((unsigned)grid), dim3(256), 0, s, a);
+}
 void launch_attn_stats(hipStream_t s, size_t nblocks, const StatsArgs& a) {
     hipLaunchKernelGGL(kg_attn_stats, dim3((unsigned)nblocks), dim3(WAVE), stats_lds(a.ar), s, a);
 }
@@ -334,7 +303,9 @@ void launch_attn_apply(hipStream_t s, size_t nblocks, const ApplyArgs& a) {
 void launch_ffn(hipStream_t s, const FfnArgs& a) {
     hipLaunchKernelGGL(kg_ffn, dim3((unsigned)((a.ntok + 15) / 16)), dim3(WAVE), ffn_lds(a.ar), s, a);
 }
-void launch_head(hipStream_t s, const HeadArgs& a) { hipLaunchKernelGGL(kg_head, dim3((unsigned)((a.nlines + 3) / 4)), dim3(256), 0, s, a); }
+void launch_head(hipStream_t s, const HeadArgs& a, bool precise) {
+    hipLaunchKernelGGL(precise ? kg_head<64> : kg_head<0>, dim3((unsigned)((a.nlines + 3) / 4)), dim3(256), 0, s, a);
+}
 void launch_out(hipStream_t s, const double* osum, float* out, int n, double l_total) {
     hipLaunchKernelGGL(kg_out, grid_of((size_t)n), dim3(256), 0, s, osum, out, n, l_total);
 }

@@ -88,14 +88,15 @@ size_t ffn_lds(const Arch& a);
 // raise the kernels' dynamic-LDS limit to the supported set's worst case (before the first launch)
 hipError_t set_lds_limits();
 
-// Launchers (own translation unit: see phyloformer_amd/build.py).  Asynchronous on `s`.  launch_stats_fin, launch_out,
-// launch_accumulate and launch_narrow serve both float64 paths (the precise one with SR = 72, Ep = E = 64).
+// Launchers (own translation unit: see phyloformer_amd/build.py).  Asynchronous on `s`.  launch_embed, launch_head,
+// launch_stats_fin, launch_out, launch_accumulate and launch_narrow serve both float64 paths (the precise one with
+// SR = 72, Ep = E = 64).
 void launch_embed(hipStream_t s, size_t grid, const EmbedArgs& a);
 void launch_attn_stats(hipStream_t s, size_t nblocks, const StatsArgs& a);
 void launch_stats_fin(hipStream_t s, const double* part, double* stats, int nlines, int nchunk, int SR);
 void launch_attn_apply(hipStream_t s, size_t nblocks, const ApplyArgs& a);
 void launch_ffn(hipStream_t s, const FfnArgs& a);
-void launch_head(hipStream_t s, const HeadArgs& a);
+void launch_head(hipStream_t s, const HeadArgs& a, bool precise);     // precise: kg_head<64>, the precise path's bits (Ep = 64)
 void launch_out(hipStream_t s, const double* osum, float* out, int n, double l_total);
 void launch_accumulate(hipStream_t s, double* dst, const double* src, size_t n);
 // debug taps: [ntok][Ep] double -> [ntok][E] float

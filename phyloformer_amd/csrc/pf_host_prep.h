@@ -1,5 +1,6 @@
 // Host-side preparation of the device operands: 16-bit hi/lo MFMA fragment images (fp16; bf16 with PF_F16 = 0), LayerNorm folding, the block-0
-// residue-pair table, and the shape-only launch plans (k_main's tiling, k_colstats' summation tree).
+// residue-pair table, the shape-only launch plans (k_main's tiling, k_colstats' summation tree), and the reader of the
+// checkpoint blob (read_blob) with the embedding table all three weight images start from.
 // Plain C++ (no HIP): included by pf_lib.hip, and compiled on its own with g++ -fsanitize=address,undefined for the
 // fuzz tests (tests/test_native_sanitizers.py, tests/native/pf_host_prep_shim.cpp).
 #pragma once
@@ -148,6 +149,57 @@ inline void fold_head(const float* w2 /* [E][FF] */, const float* b2, const floa
 struct AttnHost {
     const float *g, *b, *wq, *bq, *wk, *bk, *wv, *bv, *wo, *bo;
 };
+struct FfnHost {
+    const float *g, *b, *w1, *b1, *w2, *b2;
+};
+
+// The checkpoint blob's fields in the order of weights.py::blob_layout - the one place in C++ that states it.
+// E = embed_dim, NH = n_heads (FFN width 4 E).  A null `blob` yields null fields: `len`, the number of floats the
+// layout holds, is all such a view is good for (pf_blob_len).
+struct BlobView {
+    const float *emb_w, *emb_b;           // [E][22], [E]
+    std::vector<AttnHost> row, col;       // per block
+    std::vector<FfnHost> ffn;
+    const float *head_w, *head_b;         // [E], [1]
+    size_t len;
+};
+inline BlobView read_blob(const float* blob, int n_blocks, int E, int NH) {
+    BlobView v{};
+    const size_t e = (size_t)E, h = (size_t)NH;
+    auto take = [&](size_t n) { const float* p = blob ? blob + v.len : nullptr; v.len += n; return p; };
+    auto attn = [&] {
+        AttnHost a;
+        a.g = take(e); a.b = take(e);
+        a.wq = take(h * e); a.bq = take(h);
+        a.wk = take(h * e); a.bk = take(h);
+        a.wv = take(e * e); a.bv = take(e);
+        a.wo = take(e * e); a.bo = take(e);
+        return a;
+    };
+    v.emb_w = take(e * NA); v.emb_b = take(e);
+    for (int k = 0; k < n_blocks; ++k) {
+        v.row.push_back(attn());
+        v.col.push_back(attn());
+        FfnHost f;
+        f.g = take(e); f.b = take(e);
+        f.w1 = take(4 * e * e); f.b1 = take(4 * e);
+        f.w2 = take(e * 4 * e); f.b2 = take(e);
+        v.ffn.push_back(f);
+    }
+    v.head_w = take(e); v.head_b = take(1);
+    return v;
+}
+
+// The embedding table: conv on a one-hot = W[c][a] + b[c] (model.py:139-141), then ReLU (:142), formed in T;
+// out[a * stride + c], stride >= E.  (The two ReLUs are what the float and the double tables always used: they differ
+// on -0 and NaN only.)
+inline float relu(float v) { return v > 0.f ? v : 0.f; }
+inline double relu(double v) { return std::max(v, 0.0); }
+template <class T>
+inline void build_embed_table(const BlobView& v, int E, int stride, T* out) {
+    for (int a = 0; a < NA; ++a)
+        for (int c = 0; c < E; ++c) out[(size_t)a * stride + c] = relu((T)v.emb_w[c * NA + a] + (T)v.emb_b[c]);
+}
 
 // fold the LayerNorm affine into a projection: W' = W diag(g), b' = b + W beta  (double accumulate)
 inline void fold(const float* W, const float* bias, const float* g, const float* beta, int M, int K,

@@ -139,23 +139,27 @@ const char* const KNAMES[] = {"embed", "rowfin", "colstats", "colfin", "main", "
 enum { K_EMBED = 0, K_ROWFIN, K_COLSTATS, K_COLFIN, K_MAIN, K_ALLREDUCE, K_MHA_QKV, K_MHA_ATTN, K_MHA_OUT, K_PRECISE, K_GENERIC,
        K_RESAMPLE, K_COUNT };
 
+// what the embed and head kernels (pfg's, for both float64 paths) read: C = 64 (precise) or Ep (generic)
+struct F64Ends {
+    const double* table = nullptr;                 // [22][C] relu(W + b), formed in double
+    const double *hw = nullptr, *hb = nullptr;     // [C], [1]
+};
+
 // weights of the float64 path (pf_precise.hip.h), widened and transposed at pf_create
 struct PreciseWeights {
+    F64Ends ends;
     double* blob = nullptr;
-    const double* table = nullptr;                 // [22][64] relu(W + b), formed in double
     std::vector<pfp::AttnW> row, col;
     std::vector<pfp::FfnW> ffn;
-    const double *hw = nullptr, *hb = nullptr;
 };
 
 // weights of the generic path (pf_generic.hip.h): padded, widened, in A-fragment order; built at pf_create for
 // architectures other than (64, 4), on the first forced forward (option "generic") for (64, 4)
 struct GenericWeights {
+    F64Ends ends;
     bool ready = false;
-    const double* table = nullptr;                 // [22][Ep] relu(W + b), formed in double
     std::vector<pfg::AttnW> row, col;
     std::vector<pfg::FfnW> ffn;
-    const double *hw = nullptr, *hb = nullptr;
 };
 
 }  // namespace
@@ -286,22 +290,6 @@ int upload(pf_handle* h, const std::vector<T>& v, float** out) {
     return PF_OK;
 }
 
-// view into the flat blob following weights.py::blob_layout
-struct Blob {
-    const float* p;
-    const float* take(size_t n) { const float* r = p; p += n; return r; }
-};
-
-AttnHost take_attn(Blob& bl) {
-    AttnHost a;
-    a.g = bl.take(E); a.b = bl.take(E);
-    a.wq = bl.take(NH * E); a.bq = bl.take(NH);
-    a.wk = bl.take(NH * E); a.bk = bl.take(NH);
-    a.wv = bl.take(E * E); a.bv = bl.take(E);
-    a.wo = bl.take(E * E); a.bo = bl.take(E);
-    return a;
-}
-
 // fp16 operand ranges (pf_device.hip.h): the split MFMA operands must stay below 65504.  LayerNorm output is bounded
 // by construction (|x~| <= sqrt(63), ||x~||_2 <= 8); everything else by the checkpoint's weights:
 //   hidden   2 a |W1' x~ + b1'| <= 2 (||W1' a row||_2 * 8 + |b1' a|)           (gelu_scaled returns at most 2 |x|)
@@ -350,41 +338,22 @@ bool f16_range_ok(const pf_handle* h, int N, int L_total) {
     return h->f16_ok && P * h->f16_vmax_col * COLAPPLY_B_SCALE < F16_LIMIT && L_total <= (1 << 20);
 }
 
-int prepare_weights(pf_handle* h, const pf_weights_t* w) {
-    Blob bl{w->blob};
-    const float* emb_w = bl.take((size_t)E * NA);
-    const float* emb_b = bl.take(E);
+// the default kernels' operands from a (64, 4) checkpoint; blob_len: the floats the caller's blob really holds
+int prepare_weights(pf_handle* h, const BlobView& view, uint64_t blob_len) {
+    if ((uint64_t)view.len != blob_len)
+        return fail(h, PF_EINVAL, "weight blob has %llu floats, expected %llu",
+                    (unsigned long long)blob_len, (unsigned long long)view.len);
     std::vector<float> table((size_t)NA * E);
-    for (int a = 0; a < NA; ++a)
-        for (int c = 0; c < E; ++c) {
-            // conv on a one-hot = W[c][a] + b[c] (model.py:139-141), then ReLU (:142)
-            const float v = emb_w[c * NA + a] + emb_b[c];
-            table[(size_t)a * E + c] = v > 0.f ? v : 0.f;
-        }
+    build_embed_table(view, E, E, table.data());
     int rc = upload(h, table, &h->table);
     if (rc) return rc;
 
-    const int nb = w->n_blocks;
+    const int nb = (int)view.ffn.size();
     h->blk.resize(nb);
-    std::vector<AttnHost> rows(nb), cols(nb);
-    struct FfnHost { const float *g, *b, *w1, *b1, *w2, *b2; };
-    std::vector<FfnHost> ffn(nb);
-    for (int k = 0; k < nb; ++k) {
-        rows[k] = take_attn(bl);
-        cols[k] = take_attn(bl);
-        ffn[k].g = bl.take(E); ffn[k].b = bl.take(E);
-        ffn[k].w1 = bl.take((size_t)FF * E); ffn[k].b1 = bl.take(FF);
-        ffn[k].w2 = bl.take((size_t)E * FF); ffn[k].b2 = bl.take(E);
-    }
-    const float* head_w = bl.take(E);
-    const float* head_b = bl.take(1);
-    if ((uint64_t)(bl.p - w->blob) != w->blob_len)
-        return fail(h, PF_EINVAL, "weight blob has %llu floats, expected %llu",
-                    (unsigned long long)w->blob_len, (unsigned long long)(bl.p - w->blob));
 
     {
         std::vector<float> ptab;
-        build_pair_table(table.data(), rows[0], ptab);
+        build_pair_table(table.data(), view.row[0], ptab);
         if ((rc = upload(h, ptab, &h->pair_table))) return rc;
     }
     F16Ranges ranges;
@@ -392,8 +361,8 @@ int prepare_weights(pf_handle* h, const pf_weights_t* w) {
     std::vector<std::vector<uint16_t>> row_tail(nb);
     for (int k = 0; k < nb; ++k) {
         BlockDev& d = h->blk[k];
-        const AttnHost& r = rows[k];
-        const AttnHost& c = cols[k];
+        const AttnHost& r = view.row[k];
+        const AttnHost& c = view.col[k];
         // ---- row attention of block k
         std::vector<float> wq, bq, wk, bk, wv, bv;
         fold(r.wq, r.bq, r.g, r.b, NH, E, wq, bq);
@@ -437,37 +406,38 @@ int prepare_weights(pf_handle* h, const pf_weights_t* w) {
     for (int k = 0; k < nb; ++k) {
         BlockDev& d = h->blk[k];
         // ---- LDS image of k_main(k): FFN + column out_proj
+        const FfnHost& f = view.ffn[k];
         std::vector<float> w1f, b1f;
-        fold(ffn[k].w1, ffn[k].b1, ffn[k].g, ffn[k].b, FF, E, w1f, b1f);
+        fold(f.w1, f.b1, f.g, f.b, FF, E, w1f, b1f);
         // hidden pre-activations are carried as a*h, a = sqrt(log2(e)/2) (see gelu_split_pair);
         // W2 absorbs 1/a
         const double alpha = std::sqrt(0.5 * 1.4426950408889634074);
         for (auto& v : w1f) v = (float)((double)v * alpha);
         for (auto& v : b1f) v = (float)((double)v * alpha);
         std::vector<float> w2s((size_t)E * FF);
-        for (size_t i = 0; i < w2s.size(); ++i) w2s[i] = (float)((double)ffn[k].w2[i] / alpha * 0.5);   // gelu_scaled returns 2*a*gelu
+        for (size_t i = 0; i < w2s.size(); ++i) w2s[i] = (float)((double)f.w2[i] / alpha * 0.5);   // gelu_scaled returns 2*a*gelu
         f16_note_ffn(w1f, b1f, w2s, &ranges);
         std::vector<uint16_t> img((size_t)FRAG_END * 8);
         pack_frags(w1f.data(), FF, E, FF, img.data() + (size_t)FRAG_W1 * 8);
         pack_frags(w2s.data(), E, FF, E, img.data() + (size_t)FRAG_W2 * 8);
-        pack_frags(cols[k].wo, E, E, E, img.data() + (size_t)FRAG_WO * 8, COLAPPLY_A_SCALE);   // B side carries the inverse
+        pack_frags(view.col[k].wo, E, E, E, img.data() + (size_t)FRAG_WO * 8, COLAPPLY_A_SCALE);   // B side carries the inverse
         if (k + 1 < nb) std::copy(row_tail[k + 1].begin(), row_tail[k + 1].end(), img.begin() + (size_t)FRAG_WV * 8);
         float c0 = 0.f;
         if (k + 1 == nb) {
             // the last block's tail (no next row attention) carries the folded head: u = W2^T head_w, c0
             float u[FF];
-            fold_head(ffn[k].w2, ffn[k].b2, head_w, head_b[0], 1.0 / alpha * 0.5, u, &c0);
+            fold_head(f.w2, f.b2, view.head_w, view.head_b[0], 1.0 / alpha * 0.5, u, &c0);
             std::memcpy(img.data() + (size_t)FRAG_U * 8, u, sizeof(u));
         }
         if ((rc = upload(h, img, &d.wimg))) return rc;
         std::vector<float> cst(CONST_LEN, 0.f);
         std::copy(b1f.begin(), b1f.end(), cst.begin() + CONST_B1);
-        std::copy(ffn[k].b2, ffn[k].b2 + E, cst.begin() + CONST_B2);
+        std::copy(f.b2, f.b2 + E, cst.begin() + CONST_B2);
         if (k + 1 < nb) std::copy(row_bqk[k + 1].begin(), row_bqk[k + 1].end(), cst.begin() + CONST_BQK);
-        std::copy(head_w, head_w + E, cst.begin() + CONST_HW);
-        cst[CONST_HB] = head_b[0];
+        std::copy(view.head_w, view.head_w + E, cst.begin() + CONST_HW);
+        cst[CONST_HB] = view.head_b[0];
         cst[CONST_C0] = c0;
-        std::copy(cols[k].bo, cols[k].bo + E, cst.begin() + CONST_BOC);
+        std::copy(view.col[k].bo, view.col[k].bo + E, cst.begin() + CONST_BOC);
         if ((rc = upload(h, cst, &d.consts))) return rc;
     }
     std::vector<float> cst0(CONST_LEN, 0.f);
@@ -956,6 +926,29 @@ struct ShardStage {
     }
 };
 
+// The one rule for the three grow-only workspaces: ws / ws2 (default kernels) and wsp (float64 paths) together stay
+// inside "ws_limit_mb" (or inside the grower's own need, if that is larger).  Called before a forward lays out its
+// workspace - a float64 one (`f64`) that has to regrow wsp to `need` bytes, or a default-path one whose chunk takes
+// `need` bytes of ws + ws2 - whichever path runs next releases what the other left behind: a handle that alternates
+// large default-path and large float64 shapes would otherwise hold twice the budget.  On the default
+// side ws / ws2 themselves go too when they alone exceed the budget (a one-stream call may have left `ws` sized for a
+// whole chunk that now runs as two halves).
+int make_room(pf_handle* h, bool f64, size_t need) {
+    const size_t budget = std::max(need, (size_t)h->ws_limit_bytes);
+    auto drop = [](char*& p, size_t& n) { if (p) { hipFree(p); p = nullptr; n = 0; } };
+    if (f64 && h->wsp) { HIPCHK(h, hipStreamSynchronize(h->stream)); drop(h->wsp, h->wsp_bytes); }   // regrown by the caller
+    if (h->ws_bytes + h->ws2_bytes + (f64 ? need : h->wsp_bytes) <= budget) return PF_OK;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (h->stream2) HIPCHK(h, hipStreamSynchronize(h->stream2));
+    if (!f64) {
+        drop(h->wsp, h->wsp_bytes);
+        if (h->ws_bytes + h->ws2_bytes <= budget) return PF_OK;
+    }
+    drop(h->ws, h->ws_bytes);
+    drop(h->ws2, h->ws2_bytes);
+    return PF_OK;
+}
+
 #include "pf_f64_host.hip.h"
 
 // What every entry point refuses.  An empty site range (Lloc = 0) is allowed only to a rank that joins its peers'
@@ -1003,22 +996,6 @@ int chunk_batch(pf_handle* h, int B, int P, int Lloc) {
     return lo;
 }
 
-// Grow-only workspaces that no longer fit the budget together are released before a chunk is laid out
-// (a one-stream call may have left `ws` sized for a whole chunk that now runs as two halves).
-// The float64 path's workspace (wsp) counts too: a handle that alternates large default-path and large float64
-// shapes would otherwise hold ws + ws2 + wsp, twice the budget - whichever path runs next releases what
-// the other left behind when the three together exceed the budget.
-int trim_workspaces(pf_handle* h, size_t need_total) {
-    if (h->ws_bytes + h->ws2_bytes + h->wsp_bytes <= std::max(need_total, (size_t)h->ws_limit_bytes)) return PF_OK;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->stream2) HIPCHK(h, hipStreamSynchronize(h->stream2));
-    if (h->wsp) { hipFree(h->wsp); h->wsp = nullptr; h->wsp_bytes = 0; }
-    if (h->ws_bytes + h->ws2_bytes <= std::max(need_total, (size_t)h->ws_limit_bytes)) return PF_OK;
-    if (h->ws) { hipFree(h->ws); h->ws = nullptr; h->ws_bytes = 0; }
-    if (h->ws2) { hipFree(h->ws2); h->ws2 = nullptr; h->ws2_bytes = 0; }
-    return PF_OK;
-}
-
 int forward_device_impl(pf_handle* h, const uint8_t* d_idx, int B, int N, int l_begin, int l_end,
                         int L_total, float* d_out) {
     const int Lloc = l_end - l_begin;
@@ -1036,7 +1013,7 @@ int forward_device_impl(pf_handle* h, const uint8_t* d_idx, int B, int N, int l_
     // chunk size is derived from the largest shard, not from this rank's own (an empty rank has none)
     const int Lmax = std::max(Lloc, h->world > 1 || !Lloc ? (L_total + h->world - 1) / h->world : Lloc);
     const int cb = chunk_batch(h, B, P, Lmax);
-    if ((rc = trim_workspaces(h, chunk_bytes(h, cb, P, Lmax)))) return rc;
+    if ((rc = make_room(h, false, chunk_bytes(h, cb, P, Lmax)))) return rc;
     for (int b0 = 0; b0 < B; b0 += cb) {
         const int nbch = std::min(cb, B - b0);
         rc = forward_chunk(h, d_idx + (size_t)b0 * N * Lloc, nbch, N, Lloc, L_total, d_out + (size_t)b0 * P);
@@ -1216,10 +1193,7 @@ extern "C" {
 int pf_abi_version(void) { return PF_ABI_VERSION; }
 
 uint64_t pf_blob_len(int32_t n_blocks, int32_t n_heads, int32_t embed_dim) {
-    const uint64_t Ed = embed_dim, Hd = n_heads;
-    const uint64_t attn = 2 * Ed + 2 * (Hd * Ed + Hd) + 2 * (Ed * Ed + Ed);
-    const uint64_t ffn = 2 * Ed + (4 * Ed * Ed + 4 * Ed) + (4 * Ed * Ed + Ed);
-    return Ed * NA + Ed + (uint64_t)n_blocks * (2 * attn + ffn) + Ed + 1;
+    return read_blob(nullptr, n_blocks, embed_dim, n_heads).len;
 }
 
 // device + stream, no weights yet
@@ -1304,17 +1278,18 @@ int pf_create(const pf_weights_t* w, int device, pf_handle_t** out) {
     if (rc) return rc;
     h->n_blocks = w->n_blocks;
     h->garch = pfg::make_arch(w->embed_dim, w->n_heads);
+    const BlobView bv = read_blob(w->blob, w->n_blocks, w->embed_dim, w->n_heads);
     if (w->embed_dim == E && w->n_heads == NH) {
         // the default and precise kernels; the generic image waits for the first forward with option "generic" = 1
-        rc = prepare_weights(h, w);
-        if (!rc) rc = prepare_precise_weights(h, w, &h->pw);
+        rc = prepare_weights(h, bv, w->blob_len);
+        if (!rc) rc = prepare_precise_weights(h, bv, &h->pw);
         if (!rc) {
             try { h->blob_copy.assign(w->blob, w->blob + w->blob_len); }
             catch (const std::bad_alloc&) { rc = fail(h, PF_ENOMEM, "out of host memory copying the weights"); }
         }
     } else {
         h->arch_generic = true;          // the kernels of the other two paths are specialised for (64, 4)
-        rc = prepare_generic_weights(h, w->blob);
+        rc = prepare_generic_weights(h, bv);
     }
     if (rc) g_create_error = h->err;
     if (rc) { pf_destroy(h); return rc; }

@@ -1,20 +1,11 @@
 // Kernels of the PRECISE (float64) path; rationale, layout and the host-side sequence: pf_precise.hip.h,
-// pf_f64_host.hip.h.  The tail kernels (statistics finish, out, shard sums, taps) are pf_generic.hip's.
+// pf_f64_host.hip.h.  Embedding, head and the tail kernels (statistics finish, out, shard sums, taps) are
+// pf_generic.hip's.
 #include "pf_precise.hip.h"
+#include "pf_f64_common.hip.h"
 
 namespace pfp {
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-__device__ __forceinline__ double bcast(double v, int lane) {      // `lane` is wave-uniform
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double elu1(double z) { return z > 0.0 ? z + 1.0 : exp(z); }   // attention.py:179-180
+using namespace pf64;
 
 // nn.LayerNorm(64), biased variance, eps inside the sqrt (model.py:64-66); lane c holds channel c
 __device__ __forceinline__ double layer_norm(double x, double g, double b) {
@@ -24,32 +15,10 @@ __device__ __forceinline__ double layer_norm(double x, double g, double b) {
     return xc / sqrt(var + 1e-5) * g + b;
 }
 
-// ---- embedding + pair expansion (model.py:138-143, 173-175) ------------------------------------
-__global__ void __launch_bounds__(PT) kp_embed(EmbedArgs a) {
-    const size_t total = (size_t)a.B * a.P * a.L * E;
-    for (size_t i = (size_t)blockIdx.x * PT + threadIdx.x; i < total; i += (size_t)gridDim.x * PT) {
-        const int c = (int)(i & 63);
-        const size_t tok = i >> 6;
-        const int l = (int)(tok % a.L);
-        const size_t bp = tok / a.L;
-        const int p = (int)(bp % a.P), b = (int)(bp / a.P);
-        int ri = a.idx[((size_t)b * a.N + a.pi[p]) * a.L + l], rj = a.idx[((size_t)b * a.N + a.pj[p]) * a.L + l];
-        if ((ri >= NA || rj >= NA) && a.bad) *a.bad = 1u;          // sticky flag, as k_embed (pf_device.hip.h)
-        ri = min(ri, NA - 1); rj = min(rj, NA - 1);
-        a.x[i] = a.table[ri * E + c] + a.table[rj * E + c];
-    }
-}
-
 // ---- attention statistics over one axis (attention.py:163-190) ------------------------------------
-// A "line" is what the attention reduces over: the Lloc sites of a pair (row attention, model.py:91) or the P
-// pairs of a site (column attention, model.py:97).  Block = (line, chunk of CHUNK elements); its four waves take
+// Block = (line, chunk of CHUNK elements; lines: pf_f64_common.hip.h::token_of); its four waves take
 // the chunk's elements round-robin and leave part[line][chunk][72] = S_kv[64] | S_q[4] | S_k[4] summed in the
 // fixed order wave 0 + wave 1 + wave 2 + wave 3.  q' is kept per token for the apply kernel.
-__device__ __forceinline__ size_t token_of(int col, int line, int e, int P, int L) {
-    if (!col) return (size_t)line * L + e;                       // line = b * P + p, e = l
-    const int b = line / L, l = line - b * L;                    // line = b * L + l, e = p
-    return ((size_t)b * P + e) * L + l;
-}
 __global__ void __launch_bounds__(PT) kp_attn_stats(StatsArgs a) {
     __shared__ double wv[E * E];          // 32 KB: WvT
     __shared__ double red[4][SROW];
@@ -96,7 +65,6 @@ __global__ void __launch_bounds__(PT) kp_attn_stats(StatsArgs a) {
 // 16 T + g + 4 r), tile 4 leaves q[g] in register 0 and k[g] in register 1 of lane (g, j).  Each lane accumulates the
 // contributions of its own elements (k'[T] comes from lane (T, j) by one shuffle); the 16 element lanes of a lane group
 // are summed once per wave at the end, the four waves in fixed order.  Block = (line, chunk of CHUNK_MFMA elements).
-typedef double d4s __attribute__((ext_vector_type(4)));
 __global__ void __launch_bounds__(PT) kp_attn_stats_mfma(StatsArgs a) {
     __shared__ double red[4][SROW];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, j = lane & 15;
@@ -105,9 +73,9 @@ __global__ void __launch_bounds__(PT) kp_attn_stats_mfma(StatsArgs a) {
     const double* gam = a.w.g + 16 * g;       // (re-read per tile from L1: 64 registers are worth more than 32 loads)
     const double* bet = a.w.b + 16 * g;
     const double bq = a.w.bqk[g], bk = a.w.bqk[4 + g];
-    d4s skv[4];
+    d4 skv[4];
 #pragma unroll
-    for (int T = 0; T < 4; ++T) skv[T] = d4s{0.0, 0.0, 0.0, 0.0};
+    for (int T = 0; T < 4; ++T) skv[T] = d4{0.0, 0.0, 0.0, 0.0};
     double sq = 0.0, sk = 0.0;
     const int e_end = min(nelem, (ch + 1) * CHUNK_MFMA);
     for (int e0 = ch * CHUNK_MFMA + 16 * w; e0 < e_end; e0 += 64) {
@@ -120,19 +88,15 @@ __global__ void __launch_bounds__(PT) kp_attn_stats_mfma(StatsArgs a) {
             double s = 0.0;
 #pragma unroll
             for (int m = 0; m < 16; ++m) { xn[m] = p[m]; s += xn[m]; }
-            s += __shfl_xor(s, 16, 64);
-            s += __shfl_xor(s, 32, 64);
-            const double mu = s * (1.0 / 64.0);
+            const double mu = ln_mean(s, Times64th());
             double v = 0.0;
 #pragma unroll
             for (int m = 0; m < 16; ++m) { xn[m] -= mu; v = fma(xn[m], xn[m], v); }
-            v += __shfl_xor(v, 16, 64);
-            v += __shfl_xor(v, 32, 64);
-            const double sd = sqrt(v * (1.0 / 64.0) + 1e-5);
+            const double sd = ln_sd(v, Times64th());
 #pragma unroll
             for (int m = 0; m < 16; ++m) xn[m] = xn[m] / sd * gam[m] + bet[m];
         }
-        d4s qk = d4s{bq, bk, 0.0, 0.0};
+        d4 qk = d4{bq, bk, 0.0, 0.0};
         {
             const double* a4 = a.w.a72 + (size_t)4 * 16 * 64 + lane;
 #pragma unroll 4
@@ -144,7 +108,7 @@ __global__ void __launch_bounds__(PT) kp_attn_stats_mfma(StatsArgs a) {
         if (valid) a.q[tok * 4 + g] = qp;
 #pragma unroll
         for (int T = 0; T < 4; ++T) {
-            d4s v;
+            d4 v;
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = a.w.bv[16 * T + g + 4 * r];
             const double* aT = a.w.a72 + (size_t)T * 16 * 64 + lane;
@@ -261,29 +225,7 @@ __global__ void __launch_bounds__(PT) kp_ffn(FfnArgs a) {
 //          16 g + 4 Tc + r: the residual's own layout
 // (the A fragments are packed accordingly on the host, pf_f64_host.hip.h).  512 MFMAs per 16 tokens; the
 // 256 erf evaluations per token run on the VALU beside another wave's MFMAs.
-// erf-GELU in double without ocml's erf (four divergent ranges, ~2,000 cycles per wave: it was 70 % of the FFN kernel):
-//   gelu(h) = max(h, 0) - |h| Q(|h|),  Q(u) = erfc(u / sqrt 2) / 2 = exp(-u^2 / 2) R(u),
-//   R(u) (1 + u) = a degree-22 polynomial in t = (u - 4) / (u + 4)  (Chebyshev fit on u in [0, inf), |relative error|
-//   of R <= 2.4e-15, coefficients generated with scipy's erfcx; |gelu error| <= 1.8e-15 over |h| <= 40 against
-//   0.5 h (1 + erf(h / sqrt 2)) evaluated in double).  Branch-free: one division, one exp, 23 FMAs.
-__device__ __forceinline__ double gelu_f64(double h) {
-    constexpr double Q[23] = {0x1.e361ea6fba145p-2, -0x1.8c18f2086e47cp-4, 0x1.cabd72a6120b9p-7, 0x1.d4969f10f90d4p-6,
-                              -0x1.07c3c25842975p-5, 0x1.25dd720375999p-6, -0x1.47d5fc6944b2cp-8, -0x1.2b7f5644197fap-12,
-                              0x1.6c5380196e928p-11, -0x1.8c1283b1235e3p-14, -0x1.707b3dae24d79p-14, 0x1.64919115d4a57p-16,
-                              0x1.c9344f4725c3dp-17, -0x1.cdc5363466f39p-19, -0x1.5e69413cc4adcp-19, 0x1.c1cd90ff96cf7p-22,
-                              0x1.26fb2b6228421p-21, -0x1.005dbc607bf3dp-26, -0x1.d50a583370aa4p-24, -0x1.1cca57b6a492fp-27,
-                              0x1.241e7aeedd9aap-26, 0x1.b830e247ca68bp-30, -0x1.925d735408ab7p-30};
-    const double u = fabs(h);
-    const double r = 1.0 / ((u + 4.0) * (u + 1.0));
-    const double t = (u - 4.0) * (u + 1.0) * r;
-    double p = Q[22];
-#pragma unroll
-    for (int k = 21; k >= 0; --k) p = fma(p, t, Q[k]);
-    const double q = exp(-0.5 * u * u) * p * (u + 4.0) * r;
-    return fmax(h, 0.0) - u * q;
-}
-
-typedef double d4 __attribute__((ext_vector_type(4)));
+// (erf-GELU: pf_f64_common.hip.h::gelu_f64)
 __global__ void __launch_bounds__(PT) kp_ffn_mfma(FfnArgs a) {
     const int lane = threadIdx.x & 63, g = lane >> 4, j = lane & 15;
     const size_t tok = ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16 + j;
@@ -298,15 +240,11 @@ __global__ void __launch_bounds__(PT) kp_ffn_mfma(FfnArgs a) {
         double s = 0.0;
 #pragma unroll
         for (int m = 0; m < 16; ++m) s += x[m];
-        s += __shfl_xor(s, 16, 64);
-        s += __shfl_xor(s, 32, 64);
-        const double mu = s * (1.0 / 64.0);
+        const double mu = ln_mean(s, Times64th());
         double v = 0.0;
 #pragma unroll
         for (int m = 0; m < 16; ++m) { xn[m] = x[m] - mu; v = fma(xn[m], xn[m], v); }
-        v += __shfl_xor(v, 16, 64);
-        v += __shfl_xor(v, 32, 64);
-        const double sd = sqrt(v * (1.0 / 64.0) + 1e-5);
+        const double sd = ln_sd(v, Times64th());
 #pragma unroll
         for (int m = 0; m < 16; ++m) xn[m] = xn[m] / sd * a.w.g[16 * g + m] + a.w.b[16 * g + m];
     }
@@ -361,20 +299,6 @@ __global__ void __launch_bounds__(PT) kp_ffn_mfma(FfnArgs a) {
     }
 }
 
-// ---- head (model.py:158-164, 182-185): per pair, sum over this rank's sites of softplus(w . x + b) ------
-__global__ void __launch_bounds__(PT) kp_head(HeadArgs a) {
-    const int lane = threadIdx.x & 63, line = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (line >= a.nlines) return;
-    const double hw = a.hw[lane], hb = a.hb[0];
-    double acc = 0.0;
-    for (int l = 0; l < a.L; ++l) {
-        const double z = wave_sum(hw * a.x[((size_t)line * a.L + l) * E + lane]) + hb;
-        acc += z > 20.0 ? z : log1p(exp(z));                      // nn.Softplus(beta = 1, threshold = 20)
-    }
-    if (lane == 0) a.osum[line] = acc;
-}
-
-void launch_embed(hipStream_t s, size_t grid, const EmbedArgs& a) { hipLaunchKernelGGL(kp_embed, dim3((unsigned)grid), dim3(PT), 0, s, a); }
 void launch_attn_stats(hipStream_t s, size_t grid, const StatsArgs& a, bool valu) {
     if (valu) hipLaunchKernelGGL(kp_attn_stats, dim3((unsigned)grid), dim3(PT), 0, s, a);
     else hipLaunchKernelGGL(kp_attn_stats_mfma, dim3((unsigned)grid), dim3(PT), 0, s, a);
@@ -384,6 +308,5 @@ void launch_ffn(hipStream_t s, const FfnArgs& a, bool valu) {
     if (valu) hipLaunchKernelGGL(kp_ffn, dim3((unsigned)((a.ntok + FFN_NT - 1) / FFN_NT)), dim3(PT), 0, s, a);
     else hipLaunchKernelGGL(kp_ffn_mfma, dim3((unsigned)((a.ntok + 63) / 64)), dim3(PT), 0, s, a);
 }
-void launch_head(hipStream_t s, const HeadArgs& a) { hipLaunchKernelGGL(kp_head, dim3((unsigned)((a.nlines + 3) / 4)), dim3(PT), 0, s, a); }
 
 }  // namespace pfp

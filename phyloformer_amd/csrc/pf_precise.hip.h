@@ -1,11 +1,11 @@
 // The PRECISE path: the same forward (phyloformer/model.py:166-187) evaluated in float64, for the shapes on which
-// the split-bf16 MFMA path cannot hold the north star's 1e-4.
+// no fp32-level evaluation can hold the north star's 1e-4.
 //
 // Why it exists.  Alignments of a handful of sites (or of 2-4 sequences) are nothing the model was trained on: the
 // residual stream reaches |x| ~ 500, the distances 5-40, and the forward is ill-conditioned in fp32 itself - the
-// fp32 reference is 3e-5 ... 7e-4 away from its own float64 evaluation there.  The default path's
-// 2^-17-per-operand products add 1e-4 ... 2e-3 on top.  No fp32 formulation can promise to sit within a fixed bound
-// of another fp32 formulation on such input (both are a rounding cloud around the exact value); float64 sits at
+// fp32 reference is 3e-5 ... 7e-4 away from its own float64 evaluation there.  The default
+// kernels' two-fp16-limb operands round at fp32's own level, so they sit in the same rounding cloud around the exact
+// value as the reference, and two points of that cloud can be further apart than the bound; float64 sits at
 // the cloud's centre, so its distance to the reference is the reference's own rounding error and nothing else.
 // The host selects this path from the alignment's SHAPE only (pf_f64_host.hip.h::use_precise), never from the batch, so
 // an alignment gets the same bits wherever it travels.  Fixed-order sums, no atomics.
@@ -55,11 +55,6 @@ struct FfnW {
     const double *a2;          // [16 T][4 r][4 Tc][64]: W2[16 (i & 3) + 4 Tc + (i >> 2)][16 T + kq + 4 r]
 };
 
-struct EmbedArgs {
-    const uint8_t* idx; const int16_t *pi, *pj; const double* table; double* x;
-    int B, N, P, L; unsigned* bad;
-};
-
 struct StatsArgs {
     const double* x; double* q; double* part; AttnW w;
     int col;            // 0: line = (b, p), elements = sites;  1: line = (b, l), elements = pairs
@@ -74,15 +69,11 @@ struct ApplyArgs {
 
 struct FfnArgs { double* x; FfnW w; size_t ntok; };
 
-struct HeadArgs { const double* x; const double* hw; const double* hb; double* osum; int nlines, L; };
-
 // Launchers (pf_precise.hip is its own translation unit: hipcc's iterative-ILP scheduling strategy, which
 // pf_lib.hip is built with for k_main's sake, crashes the register allocator on these kernels).
-// grid = number of 256-thread blocks; asynchronous on `s`.
-void launch_embed(hipStream_t s, size_t grid, const EmbedArgs& a);
+// grid = number of 256-thread blocks; asynchronous on `s`.  Embedding and head: pfg::launch_embed / launch_head.
 void launch_attn_stats(hipStream_t s, size_t grid, const StatsArgs& a, bool valu);    // a.nchunk chunks of CHUNK (valu) / CHUNK_MFMA
 void launch_attn_apply(hipStream_t s, size_t grid, const ApplyArgs& a);
 void launch_ffn(hipStream_t s, const FfnArgs& a, bool valu);      // valu: the cross-check kernel instead of the MFMA one
-void launch_head(hipStream_t s, const HeadArgs& a);
 
 }  // namespace pfp

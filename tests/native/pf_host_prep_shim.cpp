@@ -48,5 +48,22 @@ void t_colstats_plan(int B, int P, int Lloc, int fine_opt, int* G, int* sub, int
     const ColPlan c = colstats_plan_core(B, P, Lloc, fine_opt);
     *G = c.G; *sub = c.sub; *S = c.S; *fine = c.fine;
 }
+// The blob reader's fields in blob order, as offsets in floats from `blob` (a buffer of the blob's length): embedding
+// weight, bias; per block row attention (10), column attention (10), FFN (6); head weight, bias.  out: 4 + 26 n_blocks
+// entries; returns the floats the reader consumed.
+long long t_blob_offsets(const float* blob, int n_blocks, int embed_dim, int n_heads, long long* out) {
+    const BlobView v = read_blob(blob, n_blocks, embed_dim, n_heads);
+    auto put = [&](const float* p) { *out++ = p - blob; };
+    auto attn = [&](const AttnHost& a) { for (const float* p : {a.g, a.b, a.wq, a.bq, a.wk, a.bk, a.wv, a.bv, a.wo, a.bo}) put(p); };
+    put(v.emb_w); put(v.emb_b);
+    for (int k = 0; k < n_blocks; ++k) {
+        attn(v.row[k]);
+        attn(v.col[k]);
+        const FfnHost& f = v.ffn[k];
+        for (const float* p : {f.g, f.b, f.w1, f.b1, f.w2, f.b2}) put(p);
+    }
+    put(v.head_w); put(v.head_b);
+    return (long long)v.len;
+}
 
 }  // extern "C"

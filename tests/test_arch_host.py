@@ -4,12 +4,16 @@ pf_create enforces before it touches a device."""
 import ctypes as C
 import hashlib
 import os
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import pf_oracle as O
 from phyloformer_amd.weights import random_weights
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def arch_weights(g, k):
@@ -86,3 +90,31 @@ def test_unsupported_architectures_refused_before_device_access(E, H, nb, alphab
     if alphabet == 22 and nb == 1:
         with pytest.raises(ValueError, match="embed_dim must be 1..256 and divisible by n_heads"):
             engine.Engine(random_weights(0, n_blocks=nb, n_heads=H, embed_dim=E))
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+def test_blob_reader_follows_blob_layout(golden, tmp_path):
+    """The C++ side's one reader of the checkpoint blob (csrc/pf_host_prep.h::read_blob) against
+    weights.py::blob_layout: every field's offset in blob order and the total length, for the shipped (64, 4, 6) and the
+    six architectures of arch_variants.npz (embed_dim 40 is no multiple of 16), and two with n_heads = embed_dim."""
+    from phyloformer_amd.weights import blob_layout
+    lib_path = str(tmp_path / "libpf_host_prep_shim.so")
+    res = subprocess.run(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", "-Werror",
+                          os.path.join(REPO, "tests", "native", "pf_host_prep_shim.cpp"), "-o", lib_path],
+                         capture_output=True, text=True)
+    assert res.returncode == 0, res.stderr[-3000:]
+    shim = C.CDLL(lib_path)
+    shim.t_blob_offsets.restype = C.c_longlong
+    shim.t_blob_offsets.argtypes = [C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong)]
+    archs = [(64, 4, 6), (16, 16, 1), (256, 256, 2)] + [tuple(int(v) for v in a) for a in golden("arch_variants.npz")["archs"]]
+    assert any(E % 16 for E, _, _ in archs) and any(E == H for E, H, _ in archs)
+    for E, H, nb in archs:
+        sizes = [int(np.prod(shape)) for _, shape in blob_layout(nb, H, E)]
+        want = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        blob = np.zeros(int(want[-1]), np.float32)
+        got = np.full(len(sizes), -1, np.int64)
+        n = shim.t_blob_offsets(blob.ctypes.data_as(C.POINTER(C.c_float)), nb, E, H,
+                                got.ctypes.data_as(C.POINTER(C.c_longlong)))
+        assert len(sizes) == 4 + 26 * nb
+        assert n == want[-1], (E, H, nb)
+        assert np.array_equal(got, want[:-1]), (E, H, nb)
