@@ -199,6 +199,41 @@ int pf_resample_sites_device(pf_handle_t* h, const uint8_t* d_src, int32_t B, in
 int pf_bootstrap(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, int32_t L, int32_t R,
                  uint64_t seed, float* out);
 
+/* ---- derived alignments as lists of source sites: site tables and window scans (additive to ABI 5) ----
+ *
+ * A derived alignment is a list of K source sites of an alignment of L sites; S of them per source, all of one K (a
+ * forward launch needs one shape).  Two maps:
+ *   table   set s takes sites[s][l], l = 0..K-1: any indices in [0, L), repeats and any order allowed;
+ *   affine  set s takes start[s] + l: a window of K consecutive sites.
+ * The window rule (phyloformer_amd/windows.py::window_starts is its host twin): windows of W sites start at
+ * 0, step, 2 step, ... while start + W <= L; if the last of them ends before L, one more window is anchored at L - W,
+ * so that every site is covered.  W == L gives one window. */
+/* Number of windows, and the first site (0-based) of window s; PF_EINVAL for W < 1, W > L, step < 1 or s outside
+ * [0, pf_window_count).  No handle, no GPU. */
+int pf_window_count(int32_t L, int32_t W, int32_t step);
+int pf_window_start(int32_t L, int32_t W, int32_t step, int32_t s);
+/* d_src uint8 [B][N][L] -> d_dst uint8 [B][S][N][K] (k_gather_sites, csrc/pf_sites.hip.h); async on the handle's
+ * stream.  Exactly one of d_sites (device int32 [S][K], table) and d_start (device int32 [S], affine) is not NULL;
+ * 1 <= K <= L.  The map never passes through the host, so it is not validated here: an entry outside [0, L) (a start
+ * outside [0, L - K]) is never dereferenced - site 0 is read in its place - and is reported late, like a residue > 21
+ * of pf_forward_device: the next pf_synchronize / pf_memcpy_d2h on the handle returns PF_EINVAL once. */
+int pf_gather_sites_device(pf_handle_t* h, const uint8_t* d_src, int32_t B, int32_t N, int32_t L, const int32_t* d_sites,
+                           const int32_t* d_start, int32_t S, int32_t K, uint8_t* d_dst);
+/* idx host uint8 [B][N][L], sites host int32 [S][K] -> out host float [B][S][P].  Synchronous.  out[b][s] equals, bit
+ * for bit, pf_forward of the host-cut alignment idx[b][:, sites[s]], on the path pf_forward would take for shape (N, K)
+ * (the float64 route for K < 32 or fewer than 8,192 pair-site tokens; options "precise", "generic", "ws_limit_mb",
+ * "max_seqs" and the range re-check "recheck_above" per derived alignment included) for any B, S and chunking.  The
+ * sources are uploaded once; derived bytes are built on the device one forward chunk at a time and never exceed one
+ * chunk.  Validated before any device work, with pf_forward's messages where they apply: 1 <= K <= L, S >= 1, every
+ * table entry in [0, L) (refused, never clamped), no size_t overflow of B*S*P or B*S*N*K, and everything pf_forward
+ * checks (residues > 21 included); every failure is PF_EINVAL and leaves `out` untouched.  Never communicates. */
+int pf_forward_sites(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, int32_t L, const int32_t* sites, int32_t S,
+                     int32_t K, float* out);
+/* The same for the S = pf_window_count(L, W, step) windows of the rule above (K = W): out host float [B][S][P] holds
+ * S_cap windows per source; step < 1, W outside [1, L] and S_cap < S are PF_EINVAL. */
+int pf_forward_windows(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, int32_t L, int32_t W, int32_t step,
+                       float* out, int32_t S_cap);
+
 /* Site-sharded forward: this rank holds sites [l_begin, l_end) of an alignment
  * with L_total sites.  idx: host uint8 [B][N][l_end - l_begin].  Every rank
  * receives the full result in out [B][P].  The row-attention statistics are all-reduced once per
@@ -242,7 +277,8 @@ int pf_memcpy_d2h(pf_handle_t* h, void* dst, const void* src, size_t bytes);
 
 /* Per-kernel HIP-event timing ("profile" = 1).  Names: "embed", "rowfin",
  * "colstats", "colfin", "main", "allreduce", "mha_qkv", "mha_attn", "mha_out", "precise", "generic",
- * "resample" (k_resample of pf_bootstrap / pf_resample_sites_device).  Totals accumulate until reset.  "collectives" returns the number of all-reduces issued since the last reset in
+ * "resample" (k_resample of pf_bootstrap / pf_resample_sites_device), "gather" (k_gather_sites of pf_forward_sites /
+ * pf_forward_windows / pf_gather_sites_device).  Totals accumulate until reset.  "collectives" returns the number of all-reduces issued since the last reset in
  * *launches (counted always, no profiling option needed; *total_ms = 0); "rechecked" likewise the number of
  * alignments the range re-check (option "recheck_above") computed again on the float64 kernels. */
 int pf_profile_reset(pf_handle_t* h);

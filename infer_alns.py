@@ -16,7 +16,10 @@ spreads every alignment over them: each rank holds a block of sites, RCCL all-re
 ``pf_forward_sharded``, rank 0 writes the outputs), ``--batch`` (same-shape alignments per launch;
 default: fill a token budget per shape), ``--io-threads``, ``--gpu-streams``, ``--precise``, ``--python-io``,
 ``--bench`` (print a JSON timing line), ``--bootstrap R`` / ``--seed S`` (``OUTDIR/<stem>.sup.nwk``: the NJ tree with
-site-bootstrap supports, R replicates resampled and inferred on the GPU; not with ``--shard sites``).  Scheduling lives in
+site-bootstrap supports, R replicates resampled and inferred on the GPU; not with ``--shard sites``), ``--windows W[:STEP]``
+(a scan along the alignment: ``OUTDIR/<stem>.w<first>-<last>.phy`` - with ``-t`` also ``.nj.nwk`` - per window of W sites,
+1-based inclusive site numbers, and ``OUTDIR/<stem>.windows.tsv`` comparing the windows' NJ trees; the windows are cut and
+inferred on the GPU from one upload of the alignment; not with ``--bootstrap`` or ``--shard sites``).  Scheduling lives in
 ``phyloformer_amd/scheduler.py``: files are bucketed by shape, parsed ahead of the
 GPU and written behind it.  A directory entry without a FASTA extension, or a file that does
 not parse, has the reference's side effects (infer_alns.py:97-117): every entry in front of it
@@ -74,6 +77,13 @@ def build_parser():
     parser.add_argument("--seed", type=int, default=0,
                         help="seed of the bootstrap replicate stream (default 0): a file's supports depend on the "
                              "weights, the alignment, R and the seed only")
+    parser.add_argument("--windows", default=None, metavar="W[:STEP]",
+                        help="scan along every alignment: the distances (with -t the NJ tree) of every window of W sites, "
+                             "STEP sites apart (default STEP = W: non-overlapping; a last window is anchored at L - W so that "
+                             "every site is covered), cut and inferred on the GPU: writes <stem>.w<first>-<last>.phy per "
+                             "window (1-based inclusive sites) and <stem>.windows.tsv (first, last, mean_distance, and the "
+                             "Robinson-Foulds distances of the window's NJ tree to the previous window's and to the whole "
+                             "alignment's); <stem>.phy is unchanged; a file with fewer than W sites is an error")
     parser.add_argument("--python-io", action="store_true",
                         help="use the pure-Python FASTA parser and PHYLIP writer instead of the native ones")
     parser.add_argument("--worker", default=None, help=argparse.SUPPRESS)   # "r/W": share r of W of the files
@@ -90,6 +100,19 @@ def main(argv=None):
     if args.bootstrap and args.shard == "sites":
         parser.error("--bootstrap is not supported with --shard sites (every replicate would need its own collectives); "
                      "use --shard files")
+
+    windows = None
+    if args.windows is not None:
+        from phyloformer_amd.windows import parse_windows_arg
+        try:
+            windows = parse_windows_arg(args.windows)
+        except ValueError as exc:
+            parser.error(f"--windows: {exc}")
+        if args.bootstrap:
+            parser.error("--windows is not supported with --bootstrap (replicates of windows are out of scope)")
+        if args.shard == "sites":
+            parser.error("--windows is not supported with --shard sites (every window would need its own collectives); "
+                         "use --shard files")
 
     from phyloformer_amd import scheduler
 
@@ -169,7 +192,7 @@ def main(argv=None):
     runner = scheduler.DirectoryRunner(engines, out_dir, trees=args.trees, batch=args.batch,
                                        io_threads=args.io_threads, native_io=not args.python_io,
                                        progress=bar.update if bar is not None else None,
-                                       bootstrap=args.bootstrap, seed=args.seed)
+                                       bootstrap=args.bootstrap, seed=args.seed, windows=windows)
     try:
         stats = runner.run(paths)
     finally:

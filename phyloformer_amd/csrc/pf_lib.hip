@@ -37,6 +37,8 @@
 #include "pf_precise.hip.h"
 #include "pf_generic.hip.h"
 #include "pf_boot.hip.h"
+#include "pf_sites.hip.h"
+#include "pf_sites_host.h"
 #include "pf_host_prep.h"
 
 using namespace pfk;
@@ -135,9 +137,9 @@ struct BlockDev {
 
 struct ProfSlot { int kid; hipEvent_t a, b; };
 const char* const KNAMES[] = {"embed", "rowfin", "colstats", "colfin", "main", "allreduce",
-                              "mha_qkv", "mha_attn", "mha_out", "precise", "generic", "resample"};
+                              "mha_qkv", "mha_attn", "mha_out", "precise", "generic", "resample", "gather"};
 enum { K_EMBED = 0, K_ROWFIN, K_COLSTATS, K_COLFIN, K_MAIN, K_ALLREDUCE, K_MHA_QKV, K_MHA_ATTN, K_MHA_OUT, K_PRECISE, K_GENERIC,
-       K_RESAMPLE, K_COUNT };
+       K_RESAMPLE, K_GATHER, K_COUNT };
 
 // what the embed and head kernels (pfg's, for both float64 paths) read: C = 64 (precise) or Ep (generic)
 struct F64Ends {
@@ -209,7 +211,8 @@ struct pf_handle {
     int reserve_cus = 8;          // option "reserve_cus": CUs the persistent kernels leave to RCCL then
     uint8_t* d_idx = nullptr; size_t d_idx_bytes = 0;
     float* d_out = nullptr; size_t d_out_bytes = 0;
-    uint8_t* d_rep = nullptr; size_t d_rep_bytes = 0;       // pf_bootstrap: one chunk of replicate bytes (grow-only)
+    uint8_t* d_rep = nullptr; size_t d_rep_bytes = 0;       // forward_derived: one chunk of derived alignments (grow-only)
+    int32_t* d_map = nullptr; size_t d_map_bytes = 0;       // pf_forward_sites / pf_forward_windows: the site map (grow-only)
     // comm: one RCCL communicator per stream (comm[1] serves stream2), created together by pf_comm_init, so that
     // RCCL never has to order one half-batch's collectives behind the other's with an implicit cross-stream wait
     void* comm[2] = {nullptr, nullptr};
@@ -256,6 +259,7 @@ struct pf_handle {
     GenericWeights gw;
     std::vector<float> blob_copy;
     // sticky "residue byte > 21 seen" flag: pinned host memory the kernels write through its device alias
+    // ([1]: "site map entry out of range seen", k_gather_sites of pf_gather_sites_device)
     unsigned* bad_idx_host = nullptr;
     unsigned* bad_idx_dev = nullptr;
 };
@@ -1025,7 +1029,14 @@ int forward_device_impl(pf_handle* h, const uint8_t* d_idx, int B, int N, int l_
 // After a stream synchronisation: did a kernel of the forwards since the last check see a residue byte > 21?
 // (Only the device entry points can get there: pf_forward / pf_forward_sharded validate on the host first.)
 int check_bad_idx(pf_handle* h) {
-    if (!h->bad_idx_host || !*h->bad_idx_host) return PF_OK;
+    if (!h->bad_idx_host) return PF_OK;
+    if (h->bad_idx_host[1]) {
+        h->bad_idx_host[1] = 0u;
+        return fail(h, PF_EINVAL, "a site map passed to pf_gather_sites_device held an entry outside the source alignment "
+                                  "(read as site 0; the bytes gathered since the last synchronisation are not those of "
+                                  "the map)");
+    }
+    if (!*h->bad_idx_host) return PF_OK;
     *h->bad_idx_host = 0u;
     return fail(h, PF_EINVAL, "a residue index outside 0..21 was passed to pf_forward_device / pf_forward_sharded_device "
                               "(treated as 21, '-'; results of the forwards since the last synchronisation are not "
@@ -1138,51 +1149,116 @@ bool mul_size(size_t a, size_t b, size_t c, size_t* out) {
     return !__builtin_mul_overflow(a, b, &t) && !__builtin_mul_overflow(t, c, out);
 }
 
-// pf_bootstrap.  The B sources are uploaded once; the B x R replicates run in chunks of the size the forward's own
-// chunking picks for B x R alignments (chunk_batch, or the float64 path's), cut to a rectangle - whole sources with
-// all their replicates, or a run of one source's replicates - so that one k_resample launch builds a chunk's bytes in
-// the grow-only h->d_rep; the forward then reads them there.  A replicate's distances are those of pf_forward on its
-// host-resampled bytes, bit for bit: the forward is batch invariant and routes on (N, L) alone.
-int bootstrap_impl(pf_handle* h, const uint8_t* idx, int B, int N, int L, int R, uint64_t seed, float* out) {
-    int rc = check_dims(h, B, N, L, L);
-    if (rc) return rc;
-    if (R < 1) return fail(h, PF_EINVAL, "bootstrap needs R >= 1 replicates (got %d)", R);
+// map: device int32 - rows [..][K] of a site table (sites) or window starts [..] (start); sets s_begin .. s_begin + S - 1
+int launch_gather(pf_handle* h, const uint8_t* d_src, int B, int N, int L, const int32_t* d_sites, const int32_t* d_start,
+                  int s_begin, int S, int K, uint8_t* d_dst) {
+    h->cur = h->stream;
+    ProfScope ps(h, K_GATHER);
+    const hipError_t e = pfs::launch_gather(h->stream, d_src, B, N, L, d_sites, d_start, s_begin, S, K, d_dst, h->bad_idx_dev + 1);
+    if (e != hipSuccess) return fail(h, PF_EHIP, "k_gather_sites launch failed: %s", hipGetErrorString(e));
+    return PF_OK;
+}
+
+// The one loop of every entry point that forwards alignments DERIVED from resident sources (pf_bootstrap,
+// pf_forward_sites, pf_forward_windows): source b of idx [B][N][L] has S derived alignments of N x K, and
+// fill(d_src, nb, j0, nj, d_dst) builds the derived alignments [j0, j0 + nj) of nb consecutive sources at d_src into
+// d_dst [nb][nj][N][K] on h->stream (k_resample for the bootstrap, k_gather_sites for site maps).  The B sources are
+// uploaded once; the B x S derived alignments run in chunks of the size the forward's own chunking picks for B x S
+// alignments of N x K (chunk_batch, or the float64 path's), cut to a rectangle - whole sources with all their derived
+// alignments, or a run of one source's - so that one fill builds a chunk's bytes in the grow-only h->d_rep; the forward
+// then reads them there.  A derived alignment's distances are those of pf_forward on its host-built bytes, bit for bit:
+// the forward is batch invariant and routes on (N, K) alone.  The caller has checked its own arguments; what
+// pf_forward checks is checked here, before any device work.  `what` names the derived alignments in messages.
+template <class Fill>
+int forward_derived(pf_handle* h, const uint8_t* idx, int B, int N, int L, int S, int K, float* out, const char* what,
+                    Fill&& fill) {
     if (!out || !idx) return fail(h, PF_EINVAL, "null buffer");
     const int P = N * (N - 1) / 2;
     size_t nout = 0, nrep = 0;
-    if (!mul_size((size_t)B, (size_t)R, (size_t)P * sizeof(float), &nout) || !mul_size((size_t)B, (size_t)R, (size_t)N * L, &nrep))
-        return fail(h, PF_EINVAL, "B=%d x R=%d replicates of %d x %d overflow the address space", B, R, N, L);
-    const size_t nidx = (size_t)B * N * L, per = (size_t)N * L;
-    if ((rc = check_residues(h, idx, nidx))) return rc;
+    if (!mul_size((size_t)B, (size_t)S, (size_t)P * sizeof(float), &nout) || !mul_size((size_t)B, (size_t)S, (size_t)N * K, &nrep))
+        return fail(h, PF_EINVAL, "B=%d x S=%d %s of %d x %d overflow the address space", B, S, what, N, K);
+    const size_t nidx = (size_t)B * N * L, per_src = (size_t)N * L, per = (size_t)N * K;
+    int rc = check_residues(h, idx, nidx);
+    if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     if ((rc = ensure_buffer(h, &h->d_idx, &h->d_idx_bytes, nidx))) return rc;
     if ((rc = ensure_buffer(h, &h->d_out, &h->d_out_bytes, nout))) return rc;
     HIPCHK(h, hipMemcpyAsync(h->d_idx, idx, nidx, hipMemcpyHostToDevice, h->stream));
-    const F64Path* f = f64_path_of(h, N, L);
-    const int total = (int)std::min<int64_t>((int64_t)B * R, INT32_MAX);
-    const int cb = f ? f64_chunk_batch(h, *f, total, P, L) : chunk_batch(h, total, P, L);
-    const int spc = cb >= R ? cb / R : 0;                  // whole sources per chunk, or
-    const int rpc = spc ? R : cb;                          // replicates of one source per chunk
-    const size_t cap = spc ? (size_t)spc * R : (size_t)rpc;
+    const F64Path* f = f64_path_of(h, N, K);
+    const int total = (int)std::min<int64_t>((int64_t)B * S, INT32_MAX);
+    const int cb = f ? f64_chunk_batch(h, *f, total, P, K) : chunk_batch(h, total, P, K);
+    const int spc = cb >= S ? cb / S : 0;                  // whole sources per chunk, or
+    const int jpc = spc ? S : cb;                          // derived alignments of one source per chunk
+    const size_t cap = spc ? (size_t)spc * S : (size_t)jpc;
     if ((rc = ensure_buffer(h, &h->d_rep, &h->d_rep_bytes, cap * per))) return rc;
     for (int b0 = 0; b0 < B; b0 += std::max(spc, 1))
-        for (int r0 = 0; r0 < R; r0 += rpc) {
-            const int nb = spc ? std::min(spc, B - b0) : 1, nr = std::min(rpc, R - r0);
-            if ((rc = launch_resample(h, h->d_idx + (size_t)b0 * per, nb, N, L, r0, nr, seed, h->d_rep))) return rc;
-            rc = forward_device_impl(h, h->d_rep, nb * nr, N, 0, L, L, h->d_out + ((size_t)b0 * R + r0) * P);
+        for (int j0 = 0; j0 < S; j0 += jpc) {
+            const int nb = spc ? std::min(spc, B - b0) : 1, nj = std::min(jpc, S - j0);
+            if ((rc = fill(h->d_idx + (size_t)b0 * per_src, nb, j0, nj, h->d_rep))) return rc;
+            rc = forward_device_impl(h, h->d_rep, nb * nj, N, 0, K, K, h->d_out + ((size_t)b0 * S + j0) * P);
             if (rc) return rc;
         }
     HIPCHK(h, hipMemcpyAsync(out, h->d_out, nout, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (f) return PF_OK;
-    // a flagged replicate is rebuilt from the resident source bytes
-    return range_recheck(h, out, B * R, N, 0, L, L, h->d_rep, cap, [&](const int* list, size_t k, uint8_t* d_buf) -> int {
+    // a flagged derived alignment is rebuilt from the resident source bytes
+    return range_recheck(h, out, B * S, N, 0, K, K, h->d_rep, cap, [&](const int* list, size_t k, uint8_t* d_buf) -> int {
         for (size_t i = 0; i < k; ++i) {
-            const int b = list[i] / R, r = list[i] % R;
-            const int rc2 = launch_resample(h, h->d_idx + (size_t)b * per, 1, N, L, r, 1, seed, d_buf + i * per);
+            const int b = list[i] / S, j = list[i] % S;
+            const int rc2 = fill(h->d_idx + (size_t)b * per_src, 1, j, 1, d_buf + i * per);
             if (rc2) return rc2;
         }
         return PF_OK;
+    });
+}
+
+// pf_bootstrap: the derived alignments are the R replicates of the stream (pf_boot.hip.h), K = L.
+int bootstrap_impl(pf_handle* h, const uint8_t* idx, int B, int N, int L, int R, uint64_t seed, float* out) {
+    int rc = check_dims(h, B, N, L, L);
+    if (rc) return rc;
+    if (R < 1) return fail(h, PF_EINVAL, "bootstrap needs R >= 1 replicates (got %d)", R);
+    return forward_derived(h, idx, B, N, L, R, L, out, "replicates", [&](const uint8_t* d_src, int nb, int r0, int nr, uint8_t* d_dst) {
+        return launch_resample(h, d_src, nb, N, L, r0, nr, seed, d_dst);
+    });
+}
+
+// pf_forward_sites / pf_forward_windows: the derived alignments are the S site sets of a host map - a table
+// sites [S][K], or (sites == nullptr) the S windows of K sites, `step` apart, of the window rule - uploaded once into
+// the grow-only h->d_map.  Sizes are checked before the map is read or built: a caller's S is not trusted further than
+// its own table.
+int sites_impl(pf_handle* h, const uint8_t* idx, int B, int N, int L, const int32_t* sites, int step, int S, int K, float* out) {
+    int rc = check_dims(h, B, N, L, L);
+    if (rc) return rc;
+    if (S < 1) return fail(h, PF_EINVAL, "a site map needs S >= 1 sets (got %d)", S);
+    if (K < 1 || K > L) return fail(h, PF_EINVAL, "a site set needs 1 <= K <= L sites (got K=%d, L=%d)", K, L);
+    const int P = N * (N - 1) / 2;
+    size_t nmap = 0, n = 0;
+    if (!mul_size((size_t)B, (size_t)S, (size_t)P * sizeof(float), &n) || !mul_size((size_t)B, (size_t)S, (size_t)N * K, &n) ||
+        !mul_size((size_t)S, sites ? (size_t)K : 1, sizeof(int32_t), &nmap))
+        return fail(h, PF_EINVAL, "B=%d x S=%d site sets of %d x %d overflow the address space", B, S, N, K);
+    if (!out || !idx) return fail(h, PF_EINVAL, "null buffer");
+    std::vector<int32_t> start;
+    if (sites) {
+        const int64_t at = pfsites::first_bad_site(sites, (size_t)S * K, L);
+        if (at >= 0)
+            return fail(h, PF_EINVAL, "site %d at set %lld, position %lld is outside [0, %d)", (int)sites[at],
+                        (long long)(at / K), (long long)(at % K), L);
+    } else {
+        try { start.resize((size_t)S); }
+        catch (const std::bad_alloc&) { return fail(h, PF_ENOMEM, "out of host memory for %d window starts", S); }
+        for (int s = 0; s < S; ++s) start[s] = pfsites::window_start(L, K, step, s);
+    }
+    const int32_t* map = sites ? sites : start.data();
+    // (what is left - the residues - is refused by forward_derived before its first device call)
+    bool uploaded = false;
+    return forward_derived(h, idx, B, N, L, S, K, out, "site sets", [&](const uint8_t* d_src, int nb, int j0, int nj, uint8_t* d_dst) -> int {
+        if (!uploaded) {
+            const int rc2 = ensure_buffer(h, &h->d_map, &h->d_map_bytes, nmap);
+            if (rc2) return rc2;
+            HIPCHK(h, hipMemcpyAsync(h->d_map, map, nmap, hipMemcpyHostToDevice, h->stream));
+            uploaded = true;
+        }
+        return launch_gather(h, d_src, nb, N, L, sites ? h->d_map : nullptr, sites ? nullptr : h->d_map, j0, nj, K, d_dst);
     });
 }
 
@@ -1220,12 +1296,12 @@ static int open_device(int device, pf_handle** out) {
         }
         if ((e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess) { rc = fail(nullptr, PF_EHIP, "hipStreamCreate: %s", hipGetErrorString(e)); break; }
         h->cur = h->stream;
-        if ((e = hipHostMalloc((void**)&h->bad_idx_host, sizeof(unsigned), hipHostMallocMapped | hipHostMallocCoherent)) != hipSuccess ||
+        if ((e = hipHostMalloc((void**)&h->bad_idx_host, 2 * sizeof(unsigned), hipHostMallocMapped | hipHostMallocCoherent)) != hipSuccess ||
             (e = hipHostGetDevicePointer((void**)&h->bad_idx_dev, h->bad_idx_host, 0)) != hipSuccess) {
             rc = fail(nullptr, PF_EHIP, "hipHostMalloc (residue flag): %s", hipGetErrorString(e));
             break;
         }
-        *h->bad_idx_host = 0u;
+        h->bad_idx_host[0] = h->bad_idx_host[1] = 0u;
         // Kernels that need more than the default 64 KB of dynamic LDS: the attribute is set here, once per
         // handle and before any launch, so that no launch path carries mutable state shared between handles
         // (the CLI drives two engines per GPU from two host threads).
@@ -1317,6 +1393,7 @@ int pf_destroy(pf_handle_t* h) {
     if (h->d_idx) hipFree(h->d_idx);
     if (h->d_out) hipFree(h->d_out);
     if (h->d_rep) hipFree(h->d_rep);
+    if (h->d_map) hipFree(h->d_map);
     if (h->stream) hipStreamDestroy(h->stream);
     if (h->bad_idx_host) hipHostFree(h->bad_idx_host);
     delete h;
@@ -1382,6 +1459,50 @@ int pf_resample_sites_device(pf_handle_t* h, const uint8_t* d_src, int32_t B, in
 int pf_bootstrap(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, int32_t L, int32_t R, uint64_t seed, float* out) {
     if (!h) return PF_EINVAL;
     return bootstrap_impl(h, idx, B, N, L, R, seed, out);
+}
+
+int pf_window_count(int32_t L, int32_t W, int32_t step) {
+    const int n = pfsites::window_count(L, W, step);
+    return n < 0 ? PF_EINVAL : n;
+}
+
+int pf_window_start(int32_t L, int32_t W, int32_t step, int32_t s) {
+    const int st = pfsites::window_start(L, W, step, s);
+    return st < 0 ? PF_EINVAL : st;
+}
+
+int pf_gather_sites_device(pf_handle_t* h, const uint8_t* d_src, int32_t B, int32_t N, int32_t L, const int32_t* d_sites,
+                           const int32_t* d_start, int32_t S, int32_t K, uint8_t* d_dst) {
+    if (!h) return PF_EINVAL;
+    if (!d_src || !d_dst) return fail(h, PF_EINVAL, "null buffer");
+    if (!d_sites == !d_start) return fail(h, PF_EINVAL, "exactly one of d_sites (table) and d_start (affine) must be given");
+    if (B < 1 || N < 1 || L < 1 || S < 1 || K < 1 || K > L)
+        return fail(h, PF_EINVAL, "bad dimensions B=%d N=%d L=%d S=%d K=%d (1 <= K <= L)", B, N, L, S, K);
+    size_t n = 0;
+    if (!mul_size((size_t)B, (size_t)S, (size_t)N * K, &n) || !mul_size((size_t)S, (size_t)K, sizeof(int32_t), &n))
+        return fail(h, PF_EINVAL, "B=%d x S=%d site sets of %d x %d overflow the address space", B, S, N, K);
+    HIPCHK(h, hipSetDevice(h->device));
+    return launch_gather(h, d_src, B, N, L, d_sites, d_start, 0, S, K, d_dst);
+}
+
+int pf_forward_sites(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, int32_t L, const int32_t* sites, int32_t S,
+                     int32_t K, float* out) {
+    if (!h) return PF_EINVAL;
+    if (!sites) return fail(h, PF_EINVAL, "null buffer");
+    return sites_impl(h, idx, B, N, L, sites, 0, S, K, out);
+}
+
+int pf_forward_windows(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, int32_t L, int32_t W, int32_t step, float* out,
+                       int32_t S_cap) {
+    if (!h) return PF_EINVAL;
+    if (step < 1) return fail(h, PF_EINVAL, "windows need step >= 1 (got %d)", step);
+    int rc = check_dims(h, B, N, L, L);
+    if (rc) return rc;
+    if (W < 1 || W > L) return fail(h, PF_EINVAL, "a site set needs 1 <= K <= L sites (got K=%d, L=%d)", W, L);
+    const int S = pfsites::window_count(L, W, step);
+    if (S < 0) return fail(h, PF_EINVAL, "bad window rule L=%d W=%d step=%d", L, W, step);
+    if (S_cap < S) return fail(h, PF_EINVAL, "out holds %d windows, L=%d W=%d step=%d gives %d", S_cap, L, W, step, S);
+    return sites_impl(h, idx, B, N, L, nullptr, step, S, W, out);
 }
 
 int pf_forward_device(pf_handle_t* h, const uint8_t* d_idx, int32_t B, int32_t N, int32_t L, float* d_out) {

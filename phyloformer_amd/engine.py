@@ -60,6 +60,14 @@ SIGNATURES = {
     "pf_resample_sites_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                            C.c_uint64, C.c_void_p]),
     "pf_bootstrap": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p]),
+    "pf_window_count": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
+    "pf_window_start": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "pf_gather_sites_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                         C.c_int32, C.c_int32, C.c_void_p]),
+    "pf_forward_sites": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                   C.c_void_p]),
+    "pf_forward_windows": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                     C.c_int32]),
     "pf_forward_sharded": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_int32, C.c_void_p]),
     "pf_forward_sharded_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
@@ -255,6 +263,54 @@ class Engine:
         ``d_dst [B][R][N][L]`` (device buffers, asynchronous on the handle's stream)."""
         self._check(self._lib.pf_resample_sites_device(self._h, C.c_void_p(d_src), B, N, L, r_begin, R,
                                                        int(seed) & 0xFFFFFFFFFFFFFFFF, C.c_void_p(d_dst)))
+
+    def _sources(self, idx: np.ndarray):
+        idx = _u8(idx)
+        single = idx.ndim == 2
+        if single:
+            idx = idx[None]
+        if idx.ndim != 3:
+            raise ValueError(f"idx must be [B, N, L] or [N, L], got shape {idx.shape}")
+        _refuse_single_sequence(idx.shape[0], idx.shape[1])
+        return idx, single
+
+    def forward_sites(self, idx: np.ndarray, sites: np.ndarray) -> np.ndarray:
+        """Distances of the alignments cut out of ``idx`` by a site table (``pf_forward_sites``): ``uint8[B, N, L]``,
+        ``int[S, K]`` → ``float32[B, S, P]`` (``[N, L]`` → ``[S, P]``).  ``out[b, s]`` is ``forward`` of
+        ``idx[b][:, sites[s]]`` (``windows.cut_sites``), bit for bit; entries outside ``[0, L)`` raise ``ValueError``."""
+        idx, single = self._sources(idx)
+        B, N, L = idx.shape
+        tab = np.asarray(sites)
+        if tab.ndim != 2 or tab.dtype.kind not in "iu":
+            raise ValueError(f"sites must be an integer array [S, K], got {tab.dtype} {tab.shape}")
+        if tab.size and (tab.min() < -2 ** 31 or tab.max() >= 2 ** 31):
+            raise ValueError(f"site {int(tab.max() if tab.max() >= 2 ** 31 else tab.min())} is outside [0, {L})")
+        tab = np.ascontiguousarray(tab, dtype=np.int32)
+        S, K = tab.shape
+        out = np.empty((B, S, N * (N - 1) // 2), dtype=np.float32)
+        self._check(self._lib.pf_forward_sites(self._h, idx.ctypes.data, B, N, L, tab.ctypes.data if tab.size else None,
+                                               S, K, out.ctypes.data if out.size else None))
+        return out[0] if single else out
+
+    def forward_windows(self, idx: np.ndarray, W: int, step: "int | None" = None) -> np.ndarray:
+        """Distances of every window of ``W`` sites, ``step`` apart (default ``W``: non-overlapping), of ``idx``
+        (``pf_forward_windows``): ``uint8[B, N, L]`` → ``float32[B, S, P]`` (``[N, L]`` → ``[S, P]``), window ``s``
+        starting at ``windows.window_starts(L, W, step)[s]``; bit for bit ``forward`` of the host-cut window."""
+        idx, single = self._sources(idx)
+        B, N, L = idx.shape
+        W, step = int(W), int(W if step is None else step)
+        S = max(0, self._lib.pf_window_count(L, W, step))
+        out = np.empty((B, S, N * (N - 1) // 2), dtype=np.float32)
+        self._check(self._lib.pf_forward_windows(self._h, idx.ctypes.data, B, N, L, W, step,
+                                                 out.ctypes.data if out.size else None, S))
+        return out[0] if single else out
+
+    def gather_sites_device(self, d_src: int, B: int, N: int, L: int, d_sites: "int | None", d_start: "int | None", S: int,
+                            K: int, d_dst: int):
+        """``pf_gather_sites_device``: ``d_src [B][N][L]`` → ``d_dst [B][S][N][K]`` by a device site table ``d_sites
+        int32 [S][K]`` or device window starts ``d_start int32 [S]`` (device buffers, asynchronous on the handle's stream)."""
+        self._check(self._lib.pf_gather_sites_device(self._h, C.c_void_p(d_src), B, N, L, C.c_void_p(d_sites), C.c_void_p(d_start),
+                                                     S, K, C.c_void_p(d_dst)))
 
     def forward_sharded(self, idx_local: np.ndarray, l_begin: int, l_end: int, L_total: int) -> np.ndarray:
         """This rank's sites ``[l_begin, l_end)`` of ``uint8[B, N, L_total]`` alignments."""

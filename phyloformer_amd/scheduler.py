@@ -58,6 +58,8 @@ STALE_LOADS = 16
 # keeps that queue to a few hundred MB even at 200 taxa (R = 100 x 19,900 floats = 8 MB per alignment).  The GPU stays
 # fed: one alignment's R = 100 replicates at 60 x 500 are already 6 x TOKEN_BUDGET, and pf_bootstrap chunks them itself.
 BOOT_FLOATS = 1 << 22
+# --windows: the same bound on the window distances of one pf_forward_windows call (pf_forward_windows chunks them itself)
+WINDOW_FLOATS = BOOT_FLOATS
 
 
 def auto_batch(n_seqs: int, n_sites: int, max_batch: int = 4096, token_budget: int = TOKEN_BUDGET) -> int:
@@ -115,7 +117,8 @@ class DirectoryRunner:
     calls) are filled by the other's kernels — measured 486 -> 501 alignments/s at 60 x 500 with two."""
 
     def __init__(self, engine, out_dir: str, trees: bool = False, batch: int = 0,
-                 io_threads: int = 4, native_io: bool = True, progress=None, bootstrap: int = 0, seed: int = 0):
+                 io_threads: int = 4, native_io: bool = True, progress=None, bootstrap: int = 0, seed: int = 0,
+                 windows: Optional[Tuple[int, int]] = None):
         self.engines = list(engine) if isinstance(engine, (list, tuple)) else [engine]
         self.out_dir = out_dir
         self.trees = trees
@@ -129,6 +132,9 @@ class DirectoryRunner:
                       "write_wait_s": 0.0, "shapes": {}, "gpu_streams": len(self.engines)}
         if self.bootstrap:
             self.stats.update({"replicates": self.bootstrap, "bootstrap_s": 0.0})
+        self.windows = (int(windows[0]), int(windows[1])) if windows else None    # (W, step): the --windows scan
+        if self.windows:
+            self.stats.update({"windows": 0, "windows_s": 0.0})
         self._lock = threading.Lock()
 
     # -- stages -----------------------------------------------------------------------------
@@ -200,6 +206,80 @@ class DirectoryRunner:
                     for (path, _idx, ids), pred, rep in zip(part, preds[s0:s0 + sub], reps):
                         pending.append(writers.submit(self._support, path, pred, rep, ids))
 
+    # -- --windows W[:STEP] -------------------------------------------------------------------
+    def _window_error(self, path: str, n_sites: int) -> Optional[Exception]:
+        """A file shorter than the window is an error for that file, raised where the loop reaches it."""
+        if self.windows and n_sites < self.windows[0]:
+            return ValueError(f"--windows: {path} has L = {n_sites} sites, fewer than the window width W = {self.windows[0]}")
+        return None
+
+    def _window_paths(self, path: str, n_sites: int, starts: Sequence[int], ext: str) -> List[str]:
+        from .windows import window_label
+        stem = Path(path).stem
+        return [os.path.join(self.out_dir, f"{stem}.{window_label(n_sites, st, self.windows[0])}.{ext}") for st in starts]
+
+    def _window_table(self, path: str, starts: Sequence[int], wpred: np.ndarray, wtrees: Sequence[str], full_tree: str):
+        from .windows import summary_tsv
+        with open(os.path.join(self.out_dir, f"{Path(path).stem}.windows.tsv"), "w") as fh:
+            fh.write(summary_tsv(starts, self.windows[0], wpred, wtrees, full_tree))
+
+    def _write_windows(self, path: str, n_sites: int, starts: Sequence[int], pred: np.ndarray, wpred: np.ndarray,
+                       ids: List[str]):
+        """One file's window outputs through the Python writers: ``<stem>.w<first>-<last>.phy`` (``.nj.nwk`` with
+        ``--trees``) per window and ``<stem>.windows.tsv``."""
+        from .nj import neighbor_joining
+        from .phylip import vec_to_phylip
+        wtrees = []
+        for out, tree, wp in zip(self._window_paths(path, n_sites, starts, "phy"),
+                                 self._window_paths(path, n_sites, starts, "nj.nwk"), wpred):
+            dm, text = vec_to_phylip(wp, ids)
+            with open(out, "w") as fh:
+                fh.write(text)
+            wtrees.append(neighbor_joining(dm.astype("float64"), ids))
+            if self.trees:
+                with open(tree, "w") as fh:
+                    fh.write(wtrees[-1])
+        dm, _text = vec_to_phylip(pred, ids)
+        self._window_table(path, starts, wpred, wtrees, neighbor_joining(dm.astype("float64"), ids))
+
+    def _write_windows_native(self, n: int, n_sites: int, starts: Sequence[int], part: list, preds: np.ndarray,
+                              wpreds: np.ndarray):
+        """The same files for a sub-batch: the window matrices (and trees) of all its files in one native call, the
+        tables from the native neighbour joining."""
+        from .hostio import nj_newick, write_phylip
+        entries = [g[1] for g in part for _ in starts]
+        outs = [q for g in part for q in self._window_paths(g[0], n_sites, starts, "phy")]
+        trees = [q for g in part for q in self._window_paths(g[0], n_sites, starts, "nj.nwk")] if self.trees else None
+        write_phylip(entries, n, wpreds.reshape(len(entries), -1), outs, self._writer_cap(), trees)
+        for (path, (fb, i), _none), pred, wp in zip(part, preds, wpreds):
+            ids = fb.ids(i)
+            self._window_table(path, starts, wp, [nj_newick(w, ids).decode("utf8") for w in wp],
+                               nj_newick(pred, ids).decode("utf8"))
+
+    def _windows(self, engine, shape: Tuple[int, int], group: list, batch: np.ndarray, preds: np.ndarray,
+                 writers: ThreadPoolExecutor, pending: deque, native: bool):
+        """Window distances of a launch group (``pf_forward_windows``: the sources go up once, the windows are cut on
+        the device), in sub-batches of at most WINDOW_FLOATS floats; written on the writer threads."""
+        from .windows import window_starts
+        W, step = self.windows
+        starts = window_starts(shape[1], W, step)
+        P = shape[0] * (shape[0] - 1) // 2
+        sub = max(1, WINDOW_FLOATS // max(1, len(starts) * P))
+        for s0 in range(0, len(group), sub):
+            t0 = time.perf_counter()
+            wp = engine.forward_windows(batch[s0:s0 + sub], W, step)
+            dt = time.perf_counter() - t0
+            part = group[s0:s0 + sub]
+            with self._lock:
+                self.stats["windows_s"] += dt
+                self.stats["windows"] += len(part) * len(starts)
+                if native:
+                    pending.append(writers.submit(self._write_windows_native, shape[0], shape[1], starts, part,
+                                                  preds[s0:s0 + sub], wp))
+                else:
+                    for (path, _idx, ids), pred, w in zip(part, preds[s0:s0 + sub], wp):
+                        pending.append(writers.submit(self._write_windows, path, shape[1], starts, pred, w, ids))
+
     def _launch(self, engine, shape: Tuple[int, int], group: list, writers: ThreadPoolExecutor, pending: deque):
         native = group[0][2] is None              # entries of _feed_native: (path, (FastaBatch, file), None)
         t0 = time.perf_counter()
@@ -221,16 +301,18 @@ class DirectoryRunner:
             else:
                 for (path, _idx, ids), pred in zip(group, preds):
                     pending.append(writers.submit(self._write, path, pred, ids))
-            if self.progress is not None and not self.bootstrap:
+            if self.progress is not None and not self.bootstrap and not self.windows:
                 self.progress(len(group))
         if self.bootstrap:
             self._bootstrap(engine, shape, group, batch, preds, writers, pending, native)
-            if self.progress is not None:
-                self.progress(len(group))
+        if self.windows:
+            self._windows(engine, shape, group, batch, preds, writers, pending, native)
+        if self.progress is not None and (self.bootstrap or self.windows):
+            self.progress(len(group))
         with self._lock:
             drain = []
             # bound the write queue so results do not pile up in memory
-            while len(pending) > 8 * self.io_threads + (1 if native else len(group)) * (2 if self.bootstrap else 1):
+            while len(pending) > 8 * self.io_threads + (1 if native else len(group)) * (2 if self.bootstrap or self.windows else 1):
                 drain.append(pending.popleft())
         t0 = time.perf_counter()
         for f in drain:
@@ -332,7 +414,7 @@ class DirectoryRunner:
             finally:
                 self.stats["load_wait_s"] += time.perf_counter() - t0
             shape = (int(idx.shape[0]), int(idx.shape[1]))
-            bad = too_many_seqs(shape[0])
+            bad = too_many_seqs(shape[0]) or self._window_error(path, shape[1])
             if bad is not None:
                 for _p, f in inflight:
                     f.cancel()
@@ -369,9 +451,12 @@ class DirectoryRunner:
             fb = inflight.popleft().result()
             self.stats["load_wait_s"] += time.perf_counter() - t0
             ok = (fb.status == 0) & (fb.l > 0) & (fb.n <= MAX_SEQS) & (fb.n != 1)
+            if self.windows:
+                ok &= fb.l >= self.windows[0]
             stop = len(fb) if ok.all() else int(np.argmin(ok))
             if stop < len(fb):
-                bad = fb.error(stop) or too_many_seqs(int(fb.n[stop]))
+                bad = (fb.error(stop) or too_many_seqs(int(fb.n[stop])) or
+                       self._window_error(fb.paths[stop], int(fb.l[stop])))
             ns, ls = fb.n.tolist(), fb.l.tolist()
             for i in range(stop):
                 shape = (ns[i], ls[i])
@@ -529,7 +614,8 @@ def summarize(stats: dict, load_s: float = 0.0) -> dict:
             "alignments_per_s": round(n / wall, 3) if wall > 0 else None,
             "alignments_per_s_forward_only": round(n * stats.get("gpu_streams", 1) / stats["forward_s"], 3)
             if stats["forward_s"] > 0 else None,
-            "replicates": stats.get("replicates", 0), "bootstrap_s": round(stats.get("bootstrap_s", 0.0), 6)}
+            "replicates": stats.get("replicates", 0), "bootstrap_s": round(stats.get("bootstrap_s", 0.0), 6),
+            "windows": stats.get("windows", 0), "windows_s": round(stats.get("windows_s", 0.0), 6)}
 
 
 def run_multi_device(script: str, argv: List[str], devices: Sequence[int], shard: str = "files") -> Tuple[int, List[dict]]:
