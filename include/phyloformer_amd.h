@@ -234,6 +234,41 @@ int pf_forward_sites(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, i
 int pf_forward_windows(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, int32_t L, int32_t W, int32_t step,
                        float* out, int32_t S_cap);
 
+/* ---- site-resolved distances: site map, standard errors, site profile (additive to ABI 5) ----
+ *
+ * The head computes one value per (pair, site), d[p][l] = softplus(w . x[p][l] + b), and a distance is their mean
+ * over sites: distance[p] = mean_l d[p][l] is an exact, additive decomposition of the output over the sites of the
+ * WHOLE alignment (a window of pf_forward_windows is the network's output on a CUT alignment: another question).
+ * The calls below keep d from the one forward pf_forward runs anyway:
+ *   map     float [B][P][L]   map[b][p][l] = d of pair p at site l
+ *   se      float [B][P]      sqrt( sum_l (d[p][l] - m[p])^2 / (L (L - 1)) ), m[p] = mean_l d[p][l]; 0 for L = 1.  The
+ *                             spread of the site mean: a descriptive statistic of the model's own terms, NOT a
+ *                             calibrated confidence interval (sites are not independent after column attention)
+ *   profile float [B][L]      mean_p d[p][l]: how much site l contributes to the distances
+ * `out` equals pf_forward / pf_forward_device of the same input bit for bit, on the path that call takes for (N, L)
+ * (default kernels with or without "head_fold", the float64 routes; "precise", "generic", "ws_limit_mb", "max_seqs"
+ * apply unchanged).  map, se and profile are batch invariant: an alignment gets the same bits alone and anywhere in a
+ * batch, whatever the chunking (a chunk's map bytes count inside "ws_limit_mb" for these calls).  The host calls are
+ * synchronous and re-check ranges like pf_forward: an alignment recomputed on the float64 kernels ("recheck_above")
+ * has its map / se / profile replaced together with its out; the _device calls are asynchronous on the handle's
+ * stream and do not re-check.  Refused before any device work: what pf_forward refuses, NULL buffers, sizes that
+ * overflow size_t, and (PF_ESTATE) a handle whose communicator has more than one rank - there is no site-sharded
+ * variant, a rank would hold a slice of the map. */
+/* out [B][P] as pf_forward; map [B][P][L] (host; copied one forward chunk at a time) */
+int pf_forward_site_map(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, int32_t L, float* out, float* map);
+/* device buffers; every chunk writes its slice of d_map directly */
+int pf_forward_site_map_device(pf_handle_t* h, const uint8_t* d_idx, int32_t B, int32_t N, int32_t L, float* d_out,
+                               float* d_map);
+/* out [B][P], se [B][P], profile [B][L] (host): the moments of pf_forward_site_map's map, bit for bit; the map never
+ * leaves the device and never exceeds one chunk */
+int pf_forward_site_profile(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, int32_t L, float* out, float* se,
+                            float* profile);
+/* The reduction alone (csrc/pf_sitemap.hip.h), on any device map float [B][P][L] -> d_se [B][P], d_profile [B][L];
+ * async on the handle's stream.  Accumulated in double, rounded to float once, no atomics: the bits are a function
+ * of (P, L) and the values only.  B, P, L >= 1. */
+int pf_site_moments_device(pf_handle_t* h, const float* d_map, int32_t B, int32_t P, int32_t L, float* d_se,
+                           float* d_profile);
+
 /* Site-sharded forward: this rank holds sites [l_begin, l_end) of an alignment
  * with L_total sites.  idx: host uint8 [B][N][l_end - l_begin].  Every rank
  * receives the full result in out [B][P].  The row-attention statistics are all-reduced once per
@@ -278,7 +313,8 @@ int pf_memcpy_d2h(pf_handle_t* h, void* dst, const void* src, size_t bytes);
 /* Per-kernel HIP-event timing ("profile" = 1).  Names: "embed", "rowfin",
  * "colstats", "colfin", "main", "allreduce", "mha_qkv", "mha_attn", "mha_out", "precise", "generic",
  * "resample" (k_resample of pf_bootstrap / pf_resample_sites_device), "gather" (k_gather_sites of pf_forward_sites /
- * pf_forward_windows / pf_gather_sites_device).  Totals accumulate until reset.  "collectives" returns the number of all-reduces issued since the last reset in
+ * pf_forward_windows / pf_gather_sites_device), "site_moments" (the reduction of pf_forward_site_profile /
+ * pf_site_moments_device).  Totals accumulate until reset.  "collectives" returns the number of all-reduces issued since the last reset in
  * *launches (counted always, no profiling option needed; *total_ms = 0); "rechecked" likewise the number of
  * alignments the range re-check (option "recheck_above") computed again on the float64 kernels. */
 int pf_profile_reset(pf_handle_t* h);

@@ -19,7 +19,10 @@ default: fill a token budget per shape), ``--io-threads``, ``--gpu-streams``, ``
 site-bootstrap supports, R replicates resampled and inferred on the GPU; not with ``--shard sites``), ``--windows W[:STEP]``
 (a scan along the alignment: ``OUTDIR/<stem>.w<first>-<last>.phy`` - with ``-t`` also ``.nj.nwk`` - per window of W sites,
 1-based inclusive site numbers, and ``OUTDIR/<stem>.windows.tsv`` comparing the windows' NJ trees; the windows are cut and
-inferred on the GPU from one upload of the alignment; not with ``--bootstrap`` or ``--shard sites``).  Scheduling lives in
+inferred on the GPU from one upload of the alignment; not with ``--bootstrap`` or ``--shard sites``), ``--site-profile``
+(``OUTDIR/<stem>.sites.tsv`` and ``OUTDIR/<stem>.se.phy``: every site's share of the distances and every distance's
+standard error over sites, from the forward that computes the distances; not with ``--bootstrap``, ``--windows`` or
+``--shard sites``).  Scheduling lives in
 ``phyloformer_amd/scheduler.py``: files are bucketed by shape, parsed ahead of the
 GPU and written behind it.  A directory entry without a FASTA extension, or a file that does
 not parse, has the reference's side effects (infer_alns.py:97-117): every entry in front of it
@@ -84,6 +87,12 @@ def build_parser():
                              "window (1-based inclusive sites) and <stem>.windows.tsv (first, last, mean_distance, and the "
                              "Robinson-Foulds distances of the window's NJ tree to the previous window's and to the whole "
                              "alignment's); <stem>.phy is unchanged; a file with fewer than W sites is an error")
+    parser.add_argument("--site-profile", action="store_true",
+                        help="site-resolved distances from the same forward: writes <stem>.sites.tsv (site, profile = the "
+                             "mean over pairs of the site's term of the distances, relative = profile / its mean over sites) "
+                             "and <stem>.se.phy, the standard error of every distance's mean over sites as a PHYLIP matrix (a "
+                             "descriptive statistic of the model's own per-site terms, not a calibrated confidence interval); "
+                             "<stem>.phy is unchanged")
     parser.add_argument("--python-io", action="store_true",
                         help="use the pure-Python FASTA parser and PHYLIP writer instead of the native ones")
     parser.add_argument("--worker", default=None, help=argparse.SUPPRESS)   # "r/W": share r of W of the files
@@ -112,6 +121,15 @@ def main(argv=None):
             parser.error("--windows is not supported with --bootstrap (replicates of windows are out of scope)")
         if args.shard == "sites":
             parser.error("--windows is not supported with --shard sites (every window would need its own collectives); "
+                         "use --shard files")
+
+    if args.site_profile:
+        if args.bootstrap:
+            parser.error("--site-profile is not supported with --bootstrap (site maps of replicates are out of scope)")
+        if windows is not None:
+            parser.error("--site-profile is not supported with --windows (site maps of windows are out of scope)")
+        if args.shard == "sites":
+            parser.error("--site-profile is not supported with --shard sites (a rank would hold a slice of the site map); "
                          "use --shard files")
 
     from phyloformer_amd import scheduler
@@ -192,7 +210,8 @@ def main(argv=None):
     runner = scheduler.DirectoryRunner(engines, out_dir, trees=args.trees, batch=args.batch,
                                        io_threads=args.io_threads, native_io=not args.python_io,
                                        progress=bar.update if bar is not None else None,
-                                       bootstrap=args.bootstrap, seed=args.seed, windows=windows)
+                                       bootstrap=args.bootstrap, seed=args.seed, windows=windows,
+                                       site_profile=args.site_profile)
     try:
         stats = runner.run(paths)
     finally:

@@ -464,6 +464,8 @@ struct MainArgs {
     unsigned long long* prof;   // optional: per-phase cycle totals [8] (s_memtime), perf experiments
     int ablate;             // perf experiments only (results invalid): 1 no x load, 2 no stores,
                             // 4 no next-row phase, 8 no apply phase, 16 no FFN (2 is unused now)
+    float* sitemap;         // [B][P][Lloc]        out (last block, SITEMAP launches only): softplus of every token's
+                            //                     head logit, the terms of the site mean (no padding, no trash area)
 };
 
 enum { MODE_FIRST = 0, MODE_MID = 1, MODE_LAST = 2, MODE_MID0 = 3, MODE_LAST_FOLD = 4 };
@@ -557,10 +559,14 @@ __device__ __forceinline__ void image_to_lds(const frag_t* src, unsigned char* s
 //               debug taps a MODE_LAST launch (store_x_last) follows it
 //   FLAT      : the tiling (a.flat), a template parameter so that the row tiling carries none of the flat
 //               tiling's bookkeeping (shapes with L % 32 == 0, rows shorter than a tile)
-template <int MODE, bool FLAT>
+//   SITEMAP   : the last block also keeps what the head sums: a.sitemap[token] = softplus(head logit), one 4-byte
+//               store per token (pf_forward_site_map / pf_forward_site_profile).  A template parameter, not a run-time
+//               branch: the launches of pf_forward are the SITEMAP = false instantiations, unchanged
+template <int MODE, bool FLAT, bool SITEMAP = false>
 __global__ void __launch_bounds__(MAIN_THREADS, MAIN_WAVES / 4) k_main(MainArgs a) {
     constexpr bool LAST = MODE == MODE_LAST || MODE == MODE_LAST_FOLD;
     constexpr bool FOLD = MODE == MODE_LAST_FOLD;
+    static_assert(!SITEMAP || LAST, "the site map is the head's: last block only");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     lds_frag_t lw = (lds_frag_t)smem;
     lds_f32_t lc = (lds_f32_t)(smem + FRAG_END * 16);
@@ -1003,6 +1009,9 @@ __global__ void __launch_bounds__(MAIN_THREADS, MAIN_WAVES / 4) k_main(MainArgs 
                     const float so = half32_sum((valid && lp.in_r1 == (part == 1)) ? spz : 0.f);
                     if (lane == 0) a.outpart[slot0 + part] = so;
                 }
+                // both lanes of a pair_sum pair hold spz: the lower one stores it.  Tokens of a tile are consecutive in
+                // both tilings - one run of up to 128 bytes per tile; lanes without a token store nothing
+                if (SITEMAP && valid && h == 0) a.sitemap[lp.tok0 + lp.toff] = spz;
                 if (!FOLD && a.store_x_last && valid) {
                     f32x4* xo = reinterpret_cast<f32x4*>(a.x + tok * 64 + 4 * h);
 #pragma unroll

@@ -262,6 +262,7 @@ struct F64Run {
     F64Workspace w;
     const uint8_t* d_idx;
     int B, N, P, Lloc, L_total;
+    float* d_smap = nullptr;       // [B][P][Lloc] site map of the head's terms (unsharded site-map calls), or null
     size_t ntok() const { return (size_t)B * P * Lloc; }
 };
 
@@ -379,7 +380,7 @@ int f64_head(pf_handle* h, const F64Run& r) {
     if (!r.ntok()) { HIPCHK(h, hipMemsetAsync(r.w.osum, 0, (size_t)r.B * r.P * 8, h->cur)); return PF_OK; }
     const F64Ends& e = *r.path->ends(h);
     // (the precise path keeps its own instance: its dot product rounds differently from the generic one's at Ep = 64)
-    PF_F64LAUNCH(h, r, pfg::launch_head(h->cur, {r.w.x, e.hw, e.hb, r.w.osum, r.B * r.P, r.Lloc, r.d.C},
+    PF_F64LAUNCH(h, r, pfg::launch_head(h->cur, {r.w.x, e.hw, e.hb, r.w.osum, r.B * r.P, r.Lloc, r.d.C, r.d_smap},
                                         r.path->prof == K_PRECISE));
     return PF_OK;
 }
@@ -407,10 +408,10 @@ int f64_schedule(pf_handle* h, F64Run* runs, size_t nruns, Reduce reduce, float*
 
 // One chunk of a (possibly site-sharded, possibly empty-shard) forward on the handle's main stream.
 int forward_chunk_f64(pf_handle* h, const F64Path& path, const uint8_t* d_idx, int B, int N, int Lloc, int L_total,
-                      float* d_out) {
+                      float* d_out, float* d_smap = nullptr) {
     int rc = ensure_pairs(h, N);
     if (rc) return rc;
-    F64Run r{&path, path.dims(h), {}, d_idx, B, N, N * (N - 1) / 2, Lloc, L_total};
+    F64Run r{&path, path.dims(h), {}, d_idx, B, N, N * (N - 1) / 2, Lloc, L_total, d_smap};
     if ((rc = ensure_f64_workspace(h, r.d, B, r.P, Lloc, &r.w))) return rc;
     const bool reduces = reduces_now(h);
     ForwardScope scope(h, reduces);

@@ -251,7 +251,9 @@ __global__ void __launch_bounds__(256) kg_head(HeadArgs a) {
         double d = EP ? a.hw[lane] * xt[lane] : 0.0;
         for (int c = EP ? EP : lane; c < Ep; c += 64) d = fma(a.hw[c], xt[c], d);
         const double z = wave_sum(d) + hb;
-        acc += z > 20.0 ? z : log1p(exp(z));                      // nn.Softplus(beta = 1, threshold = 20)
+        const double sp = z > 20.0 ? z : log1p(exp(z));           // nn.Softplus(beta = 1, threshold = 20)
+        acc += sp;
+        if (a.sitemap && lane == 0) a.sitemap[(size_t)line * a.L + l] = (float)sp;   // (outside the accumulation chain)
     }
     if (lane == 0) a.osum[line] = acc;
 }

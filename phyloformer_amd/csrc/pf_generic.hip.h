@@ -79,7 +79,8 @@ struct ApplyArgs {
     double count;       // L_total (row attention) or P (column attention): q / q.mean(dim = -2)
 };
 struct FfnArgs { double* x; FfnW w; Arch ar; size_t ntok; };
-struct HeadArgs { const double* x; const double* hw; const double* hb; double* osum; int nlines, L, Ep; };
+// sitemap (nullable): float [nlines][L], the softplus term of every token narrowed to float (pf_forward_site_map)
+struct HeadArgs { const double* x; const double* hw; const double* hb; double* osum; int nlines, L, Ep; float* sitemap; };
 
 // dynamic LDS of the three MFMA kernels for an architecture (bytes)
 size_t stats_lds(const Arch& a);

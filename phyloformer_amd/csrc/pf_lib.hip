@@ -38,6 +38,7 @@
 #include "pf_generic.hip.h"
 #include "pf_boot.hip.h"
 #include "pf_sites.hip.h"
+#include "pf_sitemap.hip.h"
 #include "pf_sites_host.h"
 #include "pf_host_prep.h"
 
@@ -137,9 +138,9 @@ struct BlockDev {
 
 struct ProfSlot { int kid; hipEvent_t a, b; };
 const char* const KNAMES[] = {"embed", "rowfin", "colstats", "colfin", "main", "allreduce",
-                              "mha_qkv", "mha_attn", "mha_out", "precise", "generic", "resample", "gather"};
+                              "mha_qkv", "mha_attn", "mha_out", "precise", "generic", "resample", "gather", "site_moments"};
 enum { K_EMBED = 0, K_ROWFIN, K_COLSTATS, K_COLFIN, K_MAIN, K_ALLREDUCE, K_MHA_QKV, K_MHA_ATTN, K_MHA_OUT, K_PRECISE, K_GENERIC,
-       K_RESAMPLE, K_GATHER, K_COUNT };
+       K_RESAMPLE, K_GATHER, K_SITE_MOMENTS, K_COUNT };
 
 // what the embed and head kernels (pfg's, for both float64 paths) read: C = 64 (precise) or Ep (generic)
 struct F64Ends {
@@ -213,6 +214,12 @@ struct pf_handle {
     float* d_out = nullptr; size_t d_out_bytes = 0;
     uint8_t* d_rep = nullptr; size_t d_rep_bytes = 0;       // forward_derived: one chunk of derived alignments (grow-only)
     int32_t* d_map = nullptr; size_t d_map_bytes = 0;       // pf_forward_sites / pf_forward_windows: the site map (grow-only)
+    // pf_forward_site_map / pf_forward_site_profile (grow-only): one chunk's map of head terms, the partial column sums
+    // of its reduction, and the reduced se [B][P] / profile [B][L] of a host call
+    float* d_smap = nullptr; size_t d_smap_bytes = 0;
+    double* d_mpart = nullptr; size_t d_mpart_bytes = 0;
+    float* d_se = nullptr; size_t d_se_bytes = 0;
+    float* d_prof = nullptr; size_t d_prof_bytes = 0;
     // comm: one RCCL communicator per stream (comm[1] serves stream2), created together by pf_comm_init, so that
     // RCCL never has to order one half-batch's collectives behind the other's with an implicit cross-stream wait
     void* comm[2] = {nullptr, nullptr};
@@ -587,14 +594,14 @@ int allreduce(pf_handle* h, void* buf, size_t count, int dtype = NCCL_FLOAT) {
     return PF_OK;
 }
 
-template <int MODE>
+template <int MODE, bool SITEMAP = false>
 int launch_main(pf_handle* h, const MainArgs& a, int kid) {
     const long ntasks = (long)a.B * a.nt_aln;                        // one work item per 32-token tile
     const int cus = std::max(1, h->prop.multiProcessorCount - (h->reducing ? h->reserve_cus : 0));
     const int grid = (int)std::max<long>(1, std::min<long>(cus, (ntasks + MAIN_WAVES - 1) / MAIN_WAVES));
     ProfScope ps(h, kid);
-    if (a.flat) hipLaunchKernelGGL((k_main<MODE, true>), dim3(grid), dim3(MAIN_THREADS), MAIN_LDS_BYTES, h->cur, a);
-    else hipLaunchKernelGGL((k_main<MODE, false>), dim3(grid), dim3(MAIN_THREADS), MAIN_LDS_BYTES, h->cur, a);
+    if (a.flat) hipLaunchKernelGGL((k_main<MODE, true, SITEMAP>), dim3(grid), dim3(MAIN_THREADS), MAIN_LDS_BYTES, h->cur, a);
+    else hipLaunchKernelGGL((k_main<MODE, false, SITEMAP>), dim3(grid), dim3(MAIN_THREADS), MAIN_LDS_BYTES, h->cur, a);
     HIPCHK(h, hipGetLastError());
     return PF_OK;
 }
@@ -614,6 +621,7 @@ struct ShardRun {
     TilePlan tp;       // k_main's tiling of (P, Lloc), computed once per run
     hipStream_t stream;    // the stream the run's launches go to
     RowStats rs;           // where the next block's row statistics are
+    float* d_smap = nullptr;   // [B][P][Lloc] site map of the head's terms (pf_forward_site_map*), or null
 };
 
 int zero_fill(pf_handle* h, float* p, size_t n) {
@@ -765,10 +773,12 @@ int phase_block(pf_handle* h, const ShardRun& r, int k, RowStats rs) {
     } else {
         m.wv_lo = nullptr;
         if (h->phase_prof_last) m.prof = h->phase_prof;
+        m.sitemap = r.d_smap;
         if (!h->head_fold) {
-            if ((rc = launch_main<MODE_LAST>(h, m, K_MAIN))) return rc;
+            if ((rc = r.d_smap ? launch_main<MODE_LAST, true>(h, m, K_MAIN) : launch_main<MODE_LAST>(h, m, K_MAIN))) return rc;
         } else {
-            if ((rc = launch_main<MODE_LAST_FOLD>(h, m, K_MAIN))) return rc;
+            if ((rc = r.d_smap ? launch_main<MODE_LAST_FOLD, true>(h, m, K_MAIN) : launch_main<MODE_LAST_FOLD>(h, m, K_MAIN)))
+                return rc;
             if (h->debug_keep) {
                 // the folded head never forms x6: the full FFN writes it for the tap (in place, after the folded
                 // launch has read x5), its head sums go to spart, dead since k_rowfin - the distances stay the folded ones
@@ -849,7 +859,9 @@ int schedule(pf_handle* h, ShardRun* runs, size_t nruns, Reduce reduce) {
 // Single-GPU forwards are cut the same way (option "two_streams"): the halves run free, and whichever is in a
 // kernel tail, a small kernel or a launch gap leaves its CUs to the other.  An empty rank (Lloc = 0) cuts and
 // reduces exactly as its peers do.
-int forward_chunk(pf_handle* h, const uint8_t* d_idx, int B, int N, int Lloc, int L_total, float* d_out) {
+// d_smap (site-map entry points, unsharded): the chunk's [B][P][Lloc] map of head terms, written by the last block.
+int forward_chunk(pf_handle* h, const uint8_t* d_idx, int B, int N, int Lloc, int L_total, float* d_out,
+                  float* d_smap = nullptr) {
     const int P = N * (N - 1) / 2;
     const bool reduces = reduces_now(h);
     const int nh = halves_of(h, B);
@@ -861,6 +873,7 @@ int forward_chunk(pf_handle* h, const uint8_t* d_idx, int B, int N, int Lloc, in
         const int nb = (nh == 2) ? (i == 0 ? (B + 1) / 2 : B / 2) : B;
         r[i] = ShardRun{{}, d_idx + (size_t)b0 * N * Lloc, d_out + (size_t)b0 * P, nb, N, P, Lloc, L_total,
                         tile_plan(h, P, Lloc), h->stream, {}};
+        if (d_smap) r[i].d_smap = d_smap + (size_t)b0 * P * Lloc;
         if ((rc = ensure_workspace(h, nb, P, Lloc, &r[i].w, i == 1))) return rc;
         b0 += nb;
     }
@@ -988,14 +1001,16 @@ size_t chunk_bytes(const pf_handle* h, int cb, int P, int Lloc) {
     return total;
 }
 
-int chunk_batch(pf_handle* h, int B, int P, int Lloc) {
+// `extra`: bytes per alignment a chunk holds beside its workspace (the site-map calls' map), 0 for the plain forward.
+int chunk_batch(pf_handle* h, int B, int P, int Lloc, size_t extra = 0) {
     // k_main counts tiles in 32 bits
     B = (int)std::min<long>(B, std::max<long>(1, 0x7fffffffL / std::max(1, tile_plan(h, P, Lloc).nt_aln) - 1));
-    if (B <= 1 || chunk_bytes(h, B, P, Lloc) <= (size_t)h->ws_limit_bytes) return std::max(B, 1);
+    auto fits = [&](int cb) { return chunk_bytes(h, cb, P, Lloc) + (size_t)cb * extra <= (size_t)h->ws_limit_bytes; };
+    if (B <= 1 || fits(B)) return std::max(B, 1);
     int lo = 1, hi = B;                     // largest cb in [1, B) that fits (cb = 1 always runs)
     while (hi - lo > 1) {
         const int mid = lo + (hi - lo) / 2;
-        if (chunk_bytes(h, mid, P, Lloc) <= (size_t)h->ws_limit_bytes) lo = mid; else hi = mid;
+        if (fits(mid)) lo = mid; else hi = mid;
     }
     return lo;
 }
@@ -1072,35 +1087,44 @@ int ensure_buffer(pf_handle* h, T** p, size_t* have, size_t bytes) {
 // into d_buf (on h->stream), which holds `cap` of them; h->d_out must hold cap x P floats.  Every rank of a site-
 // sharded call holds the same `out` (the all-reduced site sums through the same kernel), so all of them pick the same
 // alignments and issue the same collectives of the float64 forward.
-template <class Stage>
+// redo(d_idx, list, k) is that float64 forward of the k staged alignments, distances into h->d_out; an entry point
+// that returns more than distances (the site-map calls) replaces the rest of alignments `list` there, together with
+// their `out`.
+template <class Stage, class Redo>
 int range_recheck(pf_handle* h, float* out, int count, int N, int l_begin, int l_end, int L_total, uint8_t* d_buf, size_t cap,
-                  Stage&& stage) {
+                  Stage&& stage, Redo&& redo) {
     if (h->precise >= 0 || h->recheck_above <= 0.0) return PF_OK;
     const int P = N * (N - 1) / 2;
     const size_t per = (size_t)N * (size_t)(l_end - l_begin);
-    std::vector<int> redo;
+    std::vector<int> list;
     std::vector<float> res;
     try {           // (nothing may throw across the C ABI)
         for (int b = 0; b < count; ++b) {
             const float* ob = out + (size_t)b * P;
             bool inside = true;
             for (int p = 0; p < P; ++p) inside &= ob[p] <= (float)h->recheck_above;      // (false for NaN)
-            if (!inside) redo.push_back(b);
+            if (!inside) list.push_back(b);
         }
-        res.resize(std::min(redo.size(), cap) * (size_t)P);
+        res.resize(std::min(list.size(), cap) * (size_t)P);
     } catch (const std::bad_alloc&) { return fail(h, PF_ENOMEM, "out of host memory in the range re-check"); }
-    for (size_t g0 = 0; g0 < redo.size(); g0 += cap) {
-        const size_t nr = std::min(cap, redo.size() - g0);
+    for (size_t g0 = 0; g0 < list.size(); g0 += cap) {
+        const size_t nr = std::min(cap, list.size() - g0);
         int rc;
-        if (per && (rc = stage(&redo[g0], nr, d_buf))) return rc;
-        rc = forward_device_f64(h, PRECISE_F64, per ? d_buf : nullptr, (int)nr, N, l_begin, l_end, L_total, h->d_out);
-        if (rc) return rc;
+        if (per && (rc = stage(&list[g0], nr, d_buf))) return rc;
+        if ((rc = redo(per ? d_buf : nullptr, &list[g0], nr))) return rc;
         HIPCHK(h, hipMemcpyAsync(res.data(), h->d_out, nr * (size_t)P * sizeof(float), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        for (size_t i = 0; i < nr; ++i) std::memcpy(out + (size_t)redo[g0 + i] * P, &res[i * P], (size_t)P * sizeof(float));
+        for (size_t i = 0; i < nr; ++i) std::memcpy(out + (size_t)list[g0 + i] * P, &res[i * P], (size_t)P * sizeof(float));
     }
-    h->rechecked += (int64_t)redo.size();
+    h->rechecked += (int64_t)list.size();
     return PF_OK;
+}
+template <class Stage>
+int range_recheck(pf_handle* h, float* out, int count, int N, int l_begin, int l_end, int L_total, uint8_t* d_buf, size_t cap,
+                  Stage&& stage) {
+    return range_recheck(h, out, count, N, l_begin, l_end, L_total, d_buf, cap, stage, [&](const uint8_t* d_idx, const int*, size_t k) {
+        return forward_device_f64(h, PRECISE_F64, d_idx, (int)k, N, l_begin, l_end, L_total, h->d_out);
+    });
 }
 
 int forward_host_impl(pf_handle* h, const uint8_t* idx, int B, int N, int l_begin, int l_end,
@@ -1262,6 +1286,148 @@ int sites_impl(pf_handle* h, const uint8_t* idx, int B, int N, int L, const int3
     });
 }
 
+// ---- site-resolved distances (pf_forward_site_map*, pf_forward_site_profile, pf_site_moments_device) ----------------
+// The head's terms map[b][p][l] = softplus(logit of pair p at site l) - distance[p] is their mean over l - are kept by
+// the last block's launch (k_main<MODE_LAST*, .., SITEMAP>, kg_head with a map pointer) and reduced by pf_sitemap.hip.h.
+
+// se [B][P], profile [B][L] of a device map [B][P][L], asynchronous on h->stream.  The partial column sums live in the
+// grow-only h->d_mpart, at most 64 MB of them (or one alignment's): larger batches are reduced in pieces - every
+// alignment's bits are its own, wherever a piece starts.
+int launch_site_moments(pf_handle* h, const float* d_map, int B, int P, int L, float* d_se, float* d_prof) {
+    h->cur = h->stream;
+    const size_t per = pfm::part_count(1, P, L) * sizeof(double);
+    const int nbc = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(B, 65535), ((size_t)64 << 20) / per));
+    int rc = ensure_buffer(h, &h->d_mpart, &h->d_mpart_bytes, (size_t)nbc * per);
+    if (rc) return rc;
+    for (int b0 = 0; b0 < B; b0 += nbc) {
+        ProfScope ps(h, K_SITE_MOMENTS);
+        const hipError_t e = pfm::launch_site_moments(h->stream, d_map + (size_t)b0 * P * L, std::min(nbc, B - b0), P, L, h->d_mpart,
+                                                      d_se + (size_t)b0 * P, d_prof + (size_t)b0 * L);
+        if (e != hipSuccess) return fail(h, PF_EHIP, "k_site_moments launch failed: %s", hipGetErrorString(e));
+    }
+    return PF_OK;
+}
+
+// What the site-map entry points refuse beside what pf_forward refuses, before any device work.
+int check_site_call(pf_handle* h, int B, int N, int L, size_t* nmap) {
+    int rc = check_dims(h, B, N, L, L);
+    if (rc) return rc;
+    if (h->world > 1)
+        return fail(h, PF_ESTATE, "site maps are not site-sharded: this handle's communicator has %d ranks, and a rank would "
+                                  "hold a slice of the map (use a handle without a communicator)", h->world);
+    const size_t P = (size_t)N * (N - 1) / 2;
+    if (!mul_size((size_t)B, P * (size_t)L, sizeof(float), nmap))
+        return fail(h, PF_EINVAL, "a site map of B=%d x %zu pairs x %d sites overflows the address space", B, P, L);
+    return PF_OK;
+}
+
+// The forward of B resident alignments on the kernels `f` (nullptr: the default ones) that keeps the site map: the
+// chunks of pf_forward_device, sized so that a chunk's workspace AND its map stay inside "ws_limit_mb".  d_map
+// [B][P][L]: every chunk writes its slice; nullptr: a chunk's map lives in the grow-only h->d_smap.  each(b0, nb, dm)
+// follows every chunk on h->stream: dm is the map of alignments [b0, b0 + nb).
+template <class Each>
+int forward_sitemap_device(pf_handle* h, const F64Path* f, const uint8_t* d_idx, int B, int N, int L, float* d_out,
+                           float* d_map, Each&& each) {
+    const int P = N * (N - 1) / 2;
+    const size_t map_per = (size_t)P * L * sizeof(float);
+    int rc, cb;
+    if (f) {
+        if ((rc = f->prepare(h))) return rc;
+        size_t off[F64_BUFS];
+        const size_t per = f64_bytes(f->dims(h), 1, P, L, off) + map_per;
+        cb = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, (size_t)h->ws_limit_bytes / per));
+    } else {
+        cb = chunk_batch(h, B, P, L, map_per);
+        if ((rc = make_room(h, false, chunk_bytes(h, cb, P, L)))) return rc;
+    }
+    if (!d_map && (rc = ensure_buffer(h, &h->d_smap, &h->d_smap_bytes, (size_t)cb * map_per))) return rc;
+    for (int b0 = 0; b0 < B; b0 += cb) {
+        const int nb = std::min(cb, B - b0);
+        float* dm = d_map ? d_map + (size_t)b0 * P * L : h->d_smap;
+        const uint8_t* di = d_idx + (size_t)b0 * N * L;
+        rc = f ? forward_chunk_f64(h, *f, di, nb, N, L, L, d_out + (size_t)b0 * P, dm)
+               : forward_chunk(h, di, nb, N, L, L, d_out + (size_t)b0 * P, dm);
+        if (rc) return rc;
+        if ((rc = each(b0, nb, dm))) return rc;
+    }
+    return PF_OK;
+}
+
+int site_map_device_impl(pf_handle* h, const uint8_t* d_idx, int B, int N, int L, float* d_out, float* d_map) {
+    size_t nmap = 0;
+    int rc = check_site_call(h, B, N, L, &nmap);
+    if (rc) return rc;
+    if (!d_idx || !d_out || !d_map) return fail(h, PF_EINVAL, "null buffer");
+    HIPCHK(h, hipSetDevice(h->device));
+    return forward_sitemap_device(h, f64_path_of(h, N, L), d_idx, B, N, L, d_out, d_map, [](int, int, float*) { return PF_OK; });
+}
+
+// pf_forward_site_map (map given) and pf_forward_site_profile (se and profile given): pf_forward's upload, chunks and
+// range re-check; what a chunk leaves beside its distances is its map, copied to the host, or the map's moments.
+int site_host_impl(pf_handle* h, const uint8_t* idx, int B, int N, int L, float* out, float* map, float* se, float* profile) {
+    size_t nmap = 0;
+    int rc = check_site_call(h, B, N, L, &nmap);
+    if (rc) return rc;
+    if (!out || !idx || (!map && (!se || !profile))) return fail(h, PF_EINVAL, "null buffer");
+    const int P = N * (N - 1) / 2;
+    const size_t nidx = (size_t)B * N * L, per = (size_t)N * L, tok = (size_t)P * L;
+    if ((rc = check_residues(h, idx, nidx))) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t nout = (size_t)B * P * sizeof(float), nprof = (size_t)B * L * sizeof(float);
+    if ((rc = ensure_buffer(h, &h->d_idx, &h->d_idx_bytes, nidx))) return rc;
+    if ((rc = ensure_buffer(h, &h->d_out, &h->d_out_bytes, nout))) return rc;
+    if (!map) {
+        if ((rc = ensure_buffer(h, &h->d_se, &h->d_se_bytes, nout))) return rc;
+        if ((rc = ensure_buffer(h, &h->d_prof, &h->d_prof_bytes, nprof))) return rc;
+    }
+    HIPCHK(h, hipMemcpyAsync(h->d_idx, idx, nidx, hipMemcpyHostToDevice, h->stream));
+    const F64Path* f = f64_path_of(h, N, L);
+    rc = forward_sitemap_device(h, f, h->d_idx, B, N, L, h->d_out, nullptr, [&](int b0, int nb, float* dm) -> int {
+        if (!map) return launch_site_moments(h, dm, nb, P, L, h->d_se + (size_t)b0 * P, h->d_prof + (size_t)b0 * L);
+        HIPCHK(h, hipMemcpyAsync(map + (size_t)b0 * tok, dm, (size_t)nb * tok * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));            // the next chunk writes the same buffer
+        return PF_OK;
+    });
+    if (rc) return rc;
+    HIPCHK(h, hipMemcpyAsync(out, h->d_out, nout, hipMemcpyDeviceToHost, h->stream));
+    if (!map) {
+        HIPCHK(h, hipMemcpyAsync(se, h->d_se, nout, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(profile, h->d_prof, nprof, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (f) return PF_OK;
+    std::vector<uint8_t> sub;
+    auto stage = [&](const int* list, size_t k, uint8_t* d_buf) -> int {
+        try { sub.resize(k * per); }
+        catch (const std::bad_alloc&) { return fail(h, PF_ENOMEM, "out of host memory in the range re-check"); }
+        for (size_t i = 0; i < k; ++i) std::memcpy(&sub[i * per], idx + (size_t)list[i] * per, per);
+        HIPCHK(h, hipMemcpyAsync(d_buf, sub.data(), k * per, hipMemcpyHostToDevice, h->stream));
+        return PF_OK;
+    };
+    // a flagged alignment's map / se / profile leave with its distances (everything else is on the host by now, so the
+    // device buffers are reused from their start)
+    auto redo = [&](const uint8_t* d_idx, const int* list, size_t k) -> int {
+        return forward_sitemap_device(h, &PRECISE_F64, d_idx, (int)k, N, L, h->d_out, nullptr, [&](int b0, int nb, float* dm) -> int {
+            if (!map) {
+                const int rc2 = launch_site_moments(h, dm, nb, P, L, h->d_se + (size_t)b0 * P, h->d_prof + (size_t)b0 * L);
+                if (rc2) return rc2;
+            }
+            for (int i = 0; i < nb; ++i) {
+                const size_t hb = (size_t)list[b0 + i], db = (size_t)(b0 + i);
+                if (map) {
+                    HIPCHK(h, hipMemcpyAsync(map + hb * tok, dm + (size_t)i * tok, tok * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+                } else {
+                    HIPCHK(h, hipMemcpyAsync(se + hb * P, h->d_se + db * P, (size_t)P * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+                    HIPCHK(h, hipMemcpyAsync(profile + hb * L, h->d_prof + db * L, (size_t)L * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+                }
+            }
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            return PF_OK;
+        });
+    };
+    return range_recheck(h, out, B, N, 0, L, L, h->d_idx, (size_t)B, stage, redo);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1316,6 +1482,10 @@ static int open_device(int device, pf_handle** out) {
             {reinterpret_cast<const void*>(&k_main<MODE_MID0, true>), MAIN_LDS_BYTES},
             {reinterpret_cast<const void*>(&k_main<MODE_LAST, true>), MAIN_LDS_BYTES},
             {reinterpret_cast<const void*>(&k_main<MODE_LAST_FOLD, true>), MAIN_LDS_BYTES},
+            {reinterpret_cast<const void*>(&k_main<MODE_LAST, false, true>), MAIN_LDS_BYTES},
+            {reinterpret_cast<const void*>(&k_main<MODE_LAST_FOLD, false, true>), MAIN_LDS_BYTES},
+            {reinterpret_cast<const void*>(&k_main<MODE_LAST, true, true>), MAIN_LDS_BYTES},
+            {reinterpret_cast<const void*>(&k_main<MODE_LAST_FOLD, true, true>), MAIN_LDS_BYTES},
             {reinterpret_cast<const void*>(&k_embed), EMBED_LDS_BYTES},
         };
         for (const auto& k : big_lds)
@@ -1394,6 +1564,10 @@ int pf_destroy(pf_handle_t* h) {
     if (h->d_out) hipFree(h->d_out);
     if (h->d_rep) hipFree(h->d_rep);
     if (h->d_map) hipFree(h->d_map);
+    if (h->d_smap) hipFree(h->d_smap);
+    if (h->d_mpart) hipFree(h->d_mpart);
+    if (h->d_se) hipFree(h->d_se);
+    if (h->d_prof) hipFree(h->d_prof);
     if (h->stream) hipStreamDestroy(h->stream);
     if (h->bad_idx_host) hipHostFree(h->bad_idx_host);
     delete h;
@@ -1508,6 +1682,35 @@ int pf_forward_windows(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N,
 int pf_forward_device(pf_handle_t* h, const uint8_t* d_idx, int32_t B, int32_t N, int32_t L, float* d_out) {
     if (!h) return PF_EINVAL;
     return forward_device_impl(h, d_idx, B, N, 0, L, L, d_out);
+}
+
+int pf_forward_site_map(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, int32_t L, float* out, float* map) {
+    if (!h) return PF_EINVAL;
+    if (!map) return fail(h, PF_EINVAL, "null buffer");
+    return site_host_impl(h, idx, B, N, L, out, map, nullptr, nullptr);
+}
+
+int pf_forward_site_map_device(pf_handle_t* h, const uint8_t* d_idx, int32_t B, int32_t N, int32_t L, float* d_out, float* d_map) {
+    if (!h) return PF_EINVAL;
+    return site_map_device_impl(h, d_idx, B, N, L, d_out, d_map);
+}
+
+int pf_forward_site_profile(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, int32_t L, float* out, float* se,
+                            float* profile) {
+    if (!h) return PF_EINVAL;
+    if (!se || !profile) return fail(h, PF_EINVAL, "null buffer");
+    return site_host_impl(h, idx, B, N, L, out, nullptr, se, profile);
+}
+
+int pf_site_moments_device(pf_handle_t* h, const float* d_map, int32_t B, int32_t P, int32_t L, float* d_se, float* d_profile) {
+    if (!h) return PF_EINVAL;
+    if (!d_map || !d_se || !d_profile) return fail(h, PF_EINVAL, "null buffer");
+    if (B < 1 || P < 1 || L < 1) return fail(h, PF_EINVAL, "bad dimensions B=%d P=%d L=%d", B, P, L);
+    size_t n = 0;
+    if (!mul_size((size_t)B, (size_t)P * (size_t)L, sizeof(float), &n))
+        return fail(h, PF_EINVAL, "a site map of B=%d x %d pairs x %d sites overflows the address space", B, P, L);
+    HIPCHK(h, hipSetDevice(h->device));
+    return launch_site_moments(h, d_map, B, P, L, d_se, d_profile);
 }
 
 int pf_forward_sharded(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, int32_t l_begin,

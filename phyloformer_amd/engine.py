@@ -109,7 +109,17 @@ SIGNATURES = {
                                         C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_int32, C.c_void_p]),
     "pf_forward_shards_emulated": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              C.c_void_p]),
+    "pf_forward_site_map": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "pf_forward_site_map_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "pf_forward_site_profile": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
+    "pf_site_moments_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
 }
+
+# Additions to ABI 5 that a library built before them lacks: bound when present; a call through a missing one raises
+# EngineError at call time (loading such a library stays possible).
+CALL_TIME_SYMBOLS = frozenset({"pf_forward_site_map", "pf_forward_site_map_device", "pf_forward_site_profile",
+                               "pf_site_moments_device"})
 
 _lib: Optional[C.CDLL] = None
 
@@ -125,6 +135,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
                           "`python -m phyloformer_amd.build` (there is no CPU fallback)")
     lib = C.CDLL(p)
     for name, (res, args) in SIGNATURES.items():
+        if name in CALL_TIME_SYMBOLS and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)  # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args
@@ -311,6 +323,53 @@ class Engine:
         int32 [S][K]`` or device window starts ``d_start int32 [S]`` (device buffers, asynchronous on the handle's stream)."""
         self._check(self._lib.pf_gather_sites_device(self._h, C.c_void_p(d_src), B, N, L, C.c_void_p(d_sites), C.c_void_p(d_start),
                                                      S, K, C.c_void_p(d_dst)))
+
+    # -- site-resolved distances ------------------------------------------------------------
+    def _optional(self, name: str):
+        fn = getattr(self._lib, name, None)
+        if fn is None:
+            raise EngineError(PF_ESTATE, f"the loaded native library does not export {name} (it was built before the "
+                              "site-map entry points); rebuild with `python -m phyloformer_amd.build --force`")
+        return fn
+
+    def forward_site_map(self, idx: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """Distances and their decomposition over sites (``pf_forward_site_map``): ``uint8[B, N, L]`` →
+        ``(float32[B, P], float32[B, P, L])`` (``[N, L]`` → ``([P], [P, L])``).  ``map[b, p, l]`` is the softplus of the
+        head's logit of pair ``p`` at site ``l``; ``dist[b, p]``, their mean over ``l``, is ``forward``'s, bit for bit."""
+        fn = self._optional("pf_forward_site_map")
+        idx, single = self._sources(idx)
+        B, N, L = idx.shape
+        P = N * (N - 1) // 2
+        out = np.empty((B, P), dtype=np.float32)
+        smap = np.empty((B, P, L), dtype=np.float32)
+        self._check(fn(self._h, idx.ctypes.data, B, N, L, out.ctypes.data, smap.ctypes.data if smap.size else None))
+        return (out[0], smap[0]) if single else (out, smap)
+
+    def forward_site_profile(self, idx: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Distances, their standard errors over sites and the site profile (``pf_forward_site_profile``):
+        ``uint8[B, N, L]`` → ``(dist float32[B, P], se float32[B, P], profile float32[B, L])``: the moments
+        (``siteprofile.site_moments``) of ``forward_site_map``'s map, reduced on the GPU."""
+        fn = self._optional("pf_forward_site_profile")
+        idx, single = self._sources(idx)
+        B, N, L = idx.shape
+        P = N * (N - 1) // 2
+        out = np.empty((B, P), dtype=np.float32)
+        se = np.empty((B, P), dtype=np.float32)
+        prof = np.empty((B, L), dtype=np.float32)
+        self._check(fn(self._h, idx.ctypes.data, B, N, L, out.ctypes.data, se.ctypes.data,
+                       prof.ctypes.data if prof.size else None))
+        return (out[0], se[0], prof[0]) if single else (out, se, prof)
+
+    def forward_site_map_device(self, d_idx: int, B: int, N: int, L: int, d_out: int, d_map: int):
+        """``pf_forward_site_map_device``: device buffers ``d_idx [B][N][L]`` → ``d_out [B][P]``, ``d_map [B][P][L]``."""
+        self._check(self._optional("pf_forward_site_map_device")(self._h, C.c_void_p(d_idx), B, N, L, C.c_void_p(d_out),
+                                                                 C.c_void_p(d_map)))
+
+    def site_moments_device(self, d_map: int, B: int, P: int, L: int, d_se: int, d_profile: int):
+        """``pf_site_moments_device``: device map ``float32 [B][P][L]`` → ``d_se [B][P]``, ``d_profile [B][L]``
+        (asynchronous on the handle's stream)."""
+        self._check(self._optional("pf_site_moments_device")(self._h, C.c_void_p(d_map), B, P, L, C.c_void_p(d_se),
+                                                             C.c_void_p(d_profile)))
 
     def forward_sharded(self, idx_local: np.ndarray, l_begin: int, l_end: int, L_total: int) -> np.ndarray:
         """This rank's sites ``[l_begin, l_end)`` of ``uint8[B, N, L_total]`` alignments."""

@@ -118,7 +118,7 @@ class DirectoryRunner:
 
     def __init__(self, engine, out_dir: str, trees: bool = False, batch: int = 0,
                  io_threads: int = 4, native_io: bool = True, progress=None, bootstrap: int = 0, seed: int = 0,
-                 windows: Optional[Tuple[int, int]] = None):
+                 windows: Optional[Tuple[int, int]] = None, site_profile: bool = False):
         self.engines = list(engine) if isinstance(engine, (list, tuple)) else [engine]
         self.out_dir = out_dir
         self.trees = trees
@@ -135,6 +135,7 @@ class DirectoryRunner:
         self.windows = (int(windows[0]), int(windows[1])) if windows else None    # (W, step): the --windows scan
         if self.windows:
             self.stats.update({"windows": 0, "windows_s": 0.0})
+        self.site_profile = bool(site_profile)    # --site-profile: <stem>.sites.tsv, <stem>.se.phy
         self._lock = threading.Lock()
 
     # -- stages -----------------------------------------------------------------------------
@@ -280,6 +281,25 @@ class DirectoryRunner:
                     for (path, _idx, ids), pred, w in zip(part, preds[s0:s0 + sub], wp):
                         pending.append(writers.submit(self._write_windows, path, shape[1], starts, pred, w, ids))
 
+    # -- --site-profile ---------------------------------------------------------------------
+    def _write_site_profile(self, path: str, se: np.ndarray, profile: np.ndarray, ids: List[str]):
+        """``<stem>.sites.tsv`` and ``<stem>.se.phy`` of one file (ids and number format of ``<stem>.phy``)."""
+        from .siteprofile import se_phylip, sites_tsv
+        stem = Path(path).stem
+        with open(os.path.join(self.out_dir, f"{stem}.sites.tsv"), "w") as fh:
+            fh.write(sites_tsv(profile))
+        if self.native_io:
+            from .hostio import format_phylip
+            with open(os.path.join(self.out_dir, f"{stem}.se.phy"), "wb") as fh:
+                fh.write(format_phylip(se, ids))
+            return
+        with open(os.path.join(self.out_dir, f"{stem}.se.phy"), "w") as fh:
+            fh.write(se_phylip(se, ids))
+
+    def _write_site_profile_native(self, group: list, ses: np.ndarray, profiles: np.ndarray):
+        for (path, (fb, i), _none), se, prof in zip(group, ses, profiles):
+            self._write_site_profile(path, se, prof, fb.ids(i))
+
     def _launch(self, engine, shape: Tuple[int, int], group: list, writers: ThreadPoolExecutor, pending: deque):
         native = group[0][2] is None              # entries of _feed_native: (path, (FastaBatch, file), None)
         t0 = time.perf_counter()
@@ -288,7 +308,11 @@ class DirectoryRunner:
             batch = gather([g[1] for g in group], shape[0], shape[1])
         else:
             batch = np.stack([g[1] for g in group])
-        preds = engine.forward(batch)
+        if self.site_profile:
+            # the same forward (its distances are forward's, bit for bit) also leaves se and the site profile
+            preds, ses, profiles = engine.forward_site_profile(batch)
+        else:
+            preds = engine.forward(batch)
         dt = time.perf_counter() - t0
         with self._lock:
             self.stats["forward_s"] += dt
@@ -301,6 +325,12 @@ class DirectoryRunner:
             else:
                 for (path, _idx, ids), pred in zip(group, preds):
                     pending.append(writers.submit(self._write, path, pred, ids))
+            if self.site_profile:
+                if native:
+                    pending.append(writers.submit(self._write_site_profile_native, group, ses, profiles))
+                else:
+                    for (path, _idx, ids), se, prof in zip(group, ses, profiles):
+                        pending.append(writers.submit(self._write_site_profile, path, se, prof, ids))
             if self.progress is not None and not self.bootstrap and not self.windows:
                 self.progress(len(group))
         if self.bootstrap:
@@ -312,7 +342,7 @@ class DirectoryRunner:
         with self._lock:
             drain = []
             # bound the write queue so results do not pile up in memory
-            while len(pending) > 8 * self.io_threads + (1 if native else len(group)) * (2 if self.bootstrap or self.windows else 1):
+            while len(pending) > 8 * self.io_threads + (1 if native else len(group)) * (2 if self.bootstrap or self.windows or self.site_profile else 1):
                 drain.append(pending.popleft())
         t0 = time.perf_counter()
         for f in drain:
