@@ -234,6 +234,52 @@ int pf_forward_sites(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, i
 int pf_forward_windows(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, int32_t L, int32_t W, int32_t step,
                        float* out, int32_t S_cap);
 
+/* ---- derived alignments as lists of source rows: taxon subsets and leave-one-out (additive to ABI 5) ----
+ *
+ * A derived alignment is a list of M source rows of an alignment of N sequences, all L sites; S of them per source,
+ * all of one M (a forward launch needs one shape).  Set s takes the rows taxa[s][m], m = 0..M-1: any rows in [0, N),
+ * repeats and any order allowed, M may exceed N.  Phyloformer's distances are context dependent - column attention
+ * mixes all pairs - so the distance between two sequences changes when a third leaves the alignment; these calls
+ * compute that from one upload of the sources.
+ * Pair order everywhere: the reference's, the row-major upper triangle - pair (i, j), i < j, of N rows has index
+ * i (2N - i - 1) / 2 + (j - i - 1).  Leave-one-out set t is the alignment without row t, the remaining rows in order:
+ * pair (i, j), neither of them t, has there the index of (i - (i > t), j - (j > t)) among N - 1 rows. */
+/* d_src uint8 [B][N][L] -> d_dst uint8 [B][S][M][L] (k_gather_taxa, csrc/pf_taxa.hip.h), d_taxa device int32 [S][M], the
+ * same table for all B sources; async on the handle's stream.  The table never passes through the host, so it is not
+ * validated here: an entry outside [0, N) is never dereferenced - row 0 is read in its place - and is reported late,
+ * like pf_gather_sites_device's: the next pf_synchronize / pf_memcpy_d2h on the handle returns PF_EINVAL once. */
+int pf_gather_taxa_device(pf_handle_t* h, const uint8_t* d_src, int32_t B, int32_t N, int32_t L, const int32_t* d_taxa,
+                          int32_t S, int32_t M, uint8_t* d_dst);
+/* idx host uint8 [B][N][L], taxa host int32 [S][M] -> out host float [B][S][M (M - 1) / 2].  Synchronous.  out[b][s]
+ * equals, bit for bit, pf_forward of the host-cut alignment idx[b][taxa[s], :], on the path pf_forward would take for
+ * shape (M, L) (options "precise", "generic", "ws_limit_mb", "max_seqs" and the range re-check "recheck_above" per
+ * derived alignment included) for any B, S and chunking.  The sources are uploaded once; derived bytes are built on the
+ * device one forward chunk at a time.  Refused before any device work, `out` untouched: everything pf_forward checks, at
+ * shape (M, L) as well as (N, L) (residues > 21 included); S < 1; M < 2; a table entry outside [0, N) (refused, never
+ * clamped; the message names set and position); NULL buffers; sizes that overflow size_t; and (PF_ESTATE) a handle
+ * whose communicator has more than one rank.  Never communicates. */
+int pf_forward_taxa(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, int32_t L, const int32_t* taxa, int32_t S,
+                    int32_t M, float* out);
+/* Leave-one-out taxon influence.  idx host uint8 [B][N][L], N >= 3.  Synchronous.  With P = N (N - 1) / 2 and
+ * P1 = (N - 1)(N - 2) / 2:
+ *   out       float [B][P]       pf_forward's result, bit for bit
+ *   loo       float [B][N][P1]   (may be NULL) loo[b][t] = pf_forward_taxa of the set "all rows but t", bit for bit
+ *   and, with delta_t(i, j) = loo[t][index of (i, j) in set t] - out[(i, j)] (exact in double),
+ *   influence float [B][N]       sqrt( mean over the P1 pairs of delta_t^2 ): how far removing t moves the others
+ *   shift     float [B][N]       mean over the P1 pairs of delta_t: signed - did t's presence stretch or shrink them
+ *   context   float [B][P]       sqrt( sum_{t != i, j} delta_t(i, j)^2 / (N - 2) ): how much a distance depends on who
+ *                                else is in the alignment
+ * The statistics are reduced on the device after the range re-check has replaced flagged sets, in double, rounded to
+ * float once, no atomics: their bits are a function of (N, out, loo) only, batch invariant.  They are descriptive, not
+ * a test statistic.  The N cuts of every source run through the same driver as pf_forward_taxa, in sub-calls, so
+ * that loo on the device never exceeds one sub-call.  Refusals as pf_forward_taxa's, plus N < 3. */
+int pf_forward_leave_one_out(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, int32_t L, float* out, float* loo,
+                             float* influence, float* shift, float* context);
+/* The reduction alone (k_loo_taxon, k_loo_pair) on device arrays d_full float [B][P], d_loo float [B][N][P1] ->
+ * d_influence [B][N], d_shift [B][N], d_context [B][P]; async on the handle's stream.  B >= 1, N >= 3. */
+int pf_loo_stats_device(pf_handle_t* h, const float* d_full, const float* d_loo, int32_t B, int32_t N, float* d_influence,
+                        float* d_shift, float* d_context);
+
 /* ---- site-resolved distances: site map, standard errors, site profile (additive to ABI 5) ----
  *
  * The head computes one value per (pair, site), d[p][l] = softplus(w . x[p][l] + b), and a distance is their mean
@@ -314,7 +360,8 @@ int pf_memcpy_d2h(pf_handle_t* h, void* dst, const void* src, size_t bytes);
  * "colstats", "colfin", "main", "allreduce", "mha_qkv", "mha_attn", "mha_out", "precise", "generic",
  * "resample" (k_resample of pf_bootstrap / pf_resample_sites_device), "gather" (k_gather_sites of pf_forward_sites /
  * pf_forward_windows / pf_gather_sites_device), "site_moments" (the reduction of pf_forward_site_profile /
- * pf_site_moments_device).  Totals accumulate until reset.  "collectives" returns the number of all-reduces issued since the last reset in
+ * pf_site_moments_device), "gather_taxa" (k_gather_taxa of pf_forward_taxa / pf_forward_leave_one_out /
+ * pf_gather_taxa_device), "loo_stats" (the reduction of pf_forward_leave_one_out / pf_loo_stats_device).  Totals accumulate until reset.  "collectives" returns the number of all-reduces issued since the last reset in
  * *launches (counted always, no profiling option needed; *total_ms = 0); "rechecked" likewise the number of
  * alignments the range re-check (option "recheck_above") computed again on the float64 kernels. */
 int pf_profile_reset(pf_handle_t* h);

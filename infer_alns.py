@@ -22,7 +22,10 @@ site-bootstrap supports, R replicates resampled and inferred on the GPU; not wit
 inferred on the GPU from one upload of the alignment; not with ``--bootstrap`` or ``--shard sites``), ``--site-profile``
 (``OUTDIR/<stem>.sites.tsv`` and ``OUTDIR/<stem>.se.phy``: every site's share of the distances and every distance's
 standard error over sites, from the forward that computes the distances; not with ``--bootstrap``, ``--windows`` or
-``--shard sites``).  Scheduling lives in
+``--shard sites``), ``--leave-one-out`` (``OUTDIR/<stem>.taxa.tsv`` and ``OUTDIR/<stem>.context.phy``: how far removing each
+sequence moves the distances of the others, and how much each distance depends on who else is in the alignment; the N
+cuts of an alignment are made and inferred on the GPU from one upload; not with ``--bootstrap``, ``--windows``,
+``--site-profile`` or ``--shard sites``).  Scheduling lives in
 ``phyloformer_amd/scheduler.py``: files are bucketed by shape, parsed ahead of the
 GPU and written behind it.  A directory entry without a FASTA extension, or a file that does
 not parse, has the reference's side effects (infer_alns.py:97-117): every entry in front of it
@@ -93,6 +96,14 @@ def build_parser():
                              "and <stem>.se.phy, the standard error of every distance's mean over sites as a PHYLIP matrix (a "
                              "descriptive statistic of the model's own per-site terms, not a calibrated confidence interval); "
                              "<stem>.phy is unchanged")
+    parser.add_argument("--leave-one-out", action="store_true",
+                        help="taxon influence: every alignment is inferred again without each of its sequences in turn (cut and "
+                             "inferred on the GPU): writes <stem>.taxa.tsv (index, id, influence = RMS move of the other "
+                             "distances when the sequence leaves, shift = their mean move, relative = influence / its mean; with "
+                             "-t rf_pruned = Robinson-Foulds distance of the cut's NJ tree to the whole alignment's NJ tree "
+                             "without that leaf) and <stem>.context.phy, how much each distance depends on the other sequences, "
+                             "as a PHYLIP matrix (descriptive statistics, not a test); <stem>.phy is unchanged; a file with "
+                             "fewer than 3 sequences is an error")
     parser.add_argument("--python-io", action="store_true",
                         help="use the pure-Python FASTA parser and PHYLIP writer instead of the native ones")
     parser.add_argument("--worker", default=None, help=argparse.SUPPRESS)   # "r/W": share r of W of the files
@@ -130,6 +141,17 @@ def main(argv=None):
             parser.error("--site-profile is not supported with --windows (site maps of windows are out of scope)")
         if args.shard == "sites":
             parser.error("--site-profile is not supported with --shard sites (a rank would hold a slice of the site map); "
+                         "use --shard files")
+
+    if args.leave_one_out:
+        if args.bootstrap:
+            parser.error("--leave-one-out is not supported with --bootstrap (replicates of taxon subsets are out of scope)")
+        if windows is not None:
+            parser.error("--leave-one-out is not supported with --windows (taxon subsets of windows are out of scope)")
+        if args.site_profile:
+            parser.error("--leave-one-out is not supported with --site-profile (site maps of taxon subsets are out of scope)")
+        if args.shard == "sites":
+            parser.error("--leave-one-out is not supported with --shard sites (every cut would need its own collectives); "
                          "use --shard files")
 
     from phyloformer_amd import scheduler
@@ -211,7 +233,7 @@ def main(argv=None):
                                        io_threads=args.io_threads, native_io=not args.python_io,
                                        progress=bar.update if bar is not None else None,
                                        bootstrap=args.bootstrap, seed=args.seed, windows=windows,
-                                       site_profile=args.site_profile)
+                                       site_profile=args.site_profile, leave_one_out=args.leave_one_out)
     try:
         stats = runner.run(paths)
     finally:

@@ -40,6 +40,7 @@
 #include "pf_sites.hip.h"
 #include "pf_sitemap.hip.h"
 #include "pf_sites_host.h"
+#include "pf_taxa.hip.h"
 #include "pf_host_prep.h"
 
 using namespace pfk;
@@ -138,9 +139,9 @@ struct BlockDev {
 
 struct ProfSlot { int kid; hipEvent_t a, b; };
 const char* const KNAMES[] = {"embed", "rowfin", "colstats", "colfin", "main", "allreduce",
-                              "mha_qkv", "mha_attn", "mha_out", "precise", "generic", "resample", "gather", "site_moments"};
+                              "mha_qkv", "mha_attn", "mha_out", "precise", "generic", "resample", "gather", "site_moments", "gather_taxa", "loo_stats"};
 enum { K_EMBED = 0, K_ROWFIN, K_COLSTATS, K_COLFIN, K_MAIN, K_ALLREDUCE, K_MHA_QKV, K_MHA_ATTN, K_MHA_OUT, K_PRECISE, K_GENERIC,
-       K_RESAMPLE, K_GATHER, K_SITE_MOMENTS, K_COUNT };
+       K_RESAMPLE, K_GATHER, K_SITE_MOMENTS, K_GATHER_TAXA, K_LOO_STATS, K_COUNT };
 
 // what the embed and head kernels (pfg's, for both float64 paths) read: C = 64 (precise) or Ep (generic)
 struct F64Ends {
@@ -220,6 +221,8 @@ struct pf_handle {
     double* d_mpart = nullptr; size_t d_mpart_bytes = 0;
     float* d_se = nullptr; size_t d_se_bytes = 0;
     float* d_prof = nullptr; size_t d_prof_bytes = 0;
+    // pf_forward_leave_one_out (grow-only): one sub-call's full distances and its influence / shift / context
+    float* d_loo = nullptr; size_t d_loo_bytes = 0;
     // comm: one RCCL communicator per stream (comm[1] serves stream2), created together by pf_comm_init, so that
     // RCCL never has to order one half-batch's collectives behind the other's with an implicit cross-stream wait
     void* comm[2] = {nullptr, nullptr};
@@ -1047,9 +1050,9 @@ int check_bad_idx(pf_handle* h) {
     if (!h->bad_idx_host) return PF_OK;
     if (h->bad_idx_host[1]) {
         h->bad_idx_host[1] = 0u;
-        return fail(h, PF_EINVAL, "a site map passed to pf_gather_sites_device held an entry outside the source alignment "
-                                  "(read as site 0; the bytes gathered since the last synchronisation are not those of "
-                                  "the map)");
+        return fail(h, PF_EINVAL, "a site map passed to pf_gather_sites_device, or a taxon table passed to "
+                                  "pf_gather_taxa_device, held an entry outside the source alignment (read as site / row 0; "
+                                  "the bytes gathered since the last synchronisation are not those of the map)");
     }
     if (!*h->bad_idx_host) return PF_OK;
     *h->bad_idx_host = 0u;
@@ -1184,31 +1187,33 @@ int launch_gather(pf_handle* h, const uint8_t* d_src, int B, int N, int L, const
 }
 
 // The one loop of every entry point that forwards alignments DERIVED from resident sources (pf_bootstrap,
-// pf_forward_sites, pf_forward_windows): source b of idx [B][N][L] has S derived alignments of N x K, and
+// pf_forward_sites, pf_forward_windows, pf_forward_taxa, pf_forward_leave_one_out): source b of idx [B][N][L] has S
+// derived alignments of Nd x K (Nd = N for everything that cuts the site axis), and
 // fill(d_src, nb, j0, nj, d_dst) builds the derived alignments [j0, j0 + nj) of nb consecutive sources at d_src into
-// d_dst [nb][nj][N][K] on h->stream (k_resample for the bootstrap, k_gather_sites for site maps).  The B sources are
+// d_dst [nb][nj][Nd][K] on h->stream (k_resample for the bootstrap, k_gather_sites for site maps, k_gather_taxa for
+// taxon subsets).  The B sources are
 // uploaded once; the B x S derived alignments run in chunks of the size the forward's own chunking picks for B x S
-// alignments of N x K (chunk_batch, or the float64 path's), cut to a rectangle - whole sources with all their derived
+// alignments of Nd x K (chunk_batch, or the float64 path's), cut to a rectangle - whole sources with all their derived
 // alignments, or a run of one source's - so that one fill builds a chunk's bytes in the grow-only h->d_rep; the forward
 // then reads them there.  A derived alignment's distances are those of pf_forward on its host-built bytes, bit for bit:
-// the forward is batch invariant and routes on (N, K) alone.  The caller has checked its own arguments; what
+// the forward is batch invariant and routes on (Nd, K) alone.  The caller has checked its own arguments; what
 // pf_forward checks is checked here, before any device work.  `what` names the derived alignments in messages.
 template <class Fill>
-int forward_derived(pf_handle* h, const uint8_t* idx, int B, int N, int L, int S, int K, float* out, const char* what,
+int forward_derived(pf_handle* h, const uint8_t* idx, int B, int N, int L, int S, int Nd, int K, float* out, const char* what,
                     Fill&& fill) {
     if (!out || !idx) return fail(h, PF_EINVAL, "null buffer");
-    const int P = N * (N - 1) / 2;
+    const int P = Nd * (Nd - 1) / 2;
     size_t nout = 0, nrep = 0;
-    if (!mul_size((size_t)B, (size_t)S, (size_t)P * sizeof(float), &nout) || !mul_size((size_t)B, (size_t)S, (size_t)N * K, &nrep))
-        return fail(h, PF_EINVAL, "B=%d x S=%d %s of %d x %d overflow the address space", B, S, what, N, K);
-    const size_t nidx = (size_t)B * N * L, per_src = (size_t)N * L, per = (size_t)N * K;
+    if (!mul_size((size_t)B, (size_t)S, (size_t)P * sizeof(float), &nout) || !mul_size((size_t)B, (size_t)S, (size_t)Nd * K, &nrep))
+        return fail(h, PF_EINVAL, "B=%d x S=%d %s of %d x %d overflow the address space", B, S, what, Nd, K);
+    const size_t nidx = (size_t)B * N * L, per_src = (size_t)N * L, per = (size_t)Nd * K;
     int rc = check_residues(h, idx, nidx);
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     if ((rc = ensure_buffer(h, &h->d_idx, &h->d_idx_bytes, nidx))) return rc;
     if ((rc = ensure_buffer(h, &h->d_out, &h->d_out_bytes, nout))) return rc;
     HIPCHK(h, hipMemcpyAsync(h->d_idx, idx, nidx, hipMemcpyHostToDevice, h->stream));
-    const F64Path* f = f64_path_of(h, N, K);
+    const F64Path* f = f64_path_of(h, Nd, K);
     const int total = (int)std::min<int64_t>((int64_t)B * S, INT32_MAX);
     const int cb = f ? f64_chunk_batch(h, *f, total, P, K) : chunk_batch(h, total, P, K);
     const int spc = cb >= S ? cb / S : 0;                  // whole sources per chunk, or
@@ -1219,14 +1224,14 @@ int forward_derived(pf_handle* h, const uint8_t* idx, int B, int N, int L, int S
         for (int j0 = 0; j0 < S; j0 += jpc) {
             const int nb = spc ? std::min(spc, B - b0) : 1, nj = std::min(jpc, S - j0);
             if ((rc = fill(h->d_idx + (size_t)b0 * per_src, nb, j0, nj, h->d_rep))) return rc;
-            rc = forward_device_impl(h, h->d_rep, nb * nj, N, 0, K, K, h->d_out + ((size_t)b0 * S + j0) * P);
+            rc = forward_device_impl(h, h->d_rep, nb * nj, Nd, 0, K, K, h->d_out + ((size_t)b0 * S + j0) * P);
             if (rc) return rc;
         }
     HIPCHK(h, hipMemcpyAsync(out, h->d_out, nout, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (f) return PF_OK;
     // a flagged derived alignment is rebuilt from the resident source bytes
-    return range_recheck(h, out, B * S, N, 0, K, K, h->d_rep, cap, [&](const int* list, size_t k, uint8_t* d_buf) -> int {
+    return range_recheck(h, out, B * S, Nd, 0, K, K, h->d_rep, cap, [&](const int* list, size_t k, uint8_t* d_buf) -> int {
         for (size_t i = 0; i < k; ++i) {
             const int b = list[i] / S, j = list[i] % S;
             const int rc2 = fill(h->d_idx + (size_t)b * per_src, 1, j, 1, d_buf + i * per);
@@ -1241,7 +1246,7 @@ int bootstrap_impl(pf_handle* h, const uint8_t* idx, int B, int N, int L, int R,
     int rc = check_dims(h, B, N, L, L);
     if (rc) return rc;
     if (R < 1) return fail(h, PF_EINVAL, "bootstrap needs R >= 1 replicates (got %d)", R);
-    return forward_derived(h, idx, B, N, L, R, L, out, "replicates", [&](const uint8_t* d_src, int nb, int r0, int nr, uint8_t* d_dst) {
+    return forward_derived(h, idx, B, N, L, R, N, L, out, "replicates", [&](const uint8_t* d_src, int nb, int r0, int nr, uint8_t* d_dst) {
         return launch_resample(h, d_src, nb, N, L, r0, nr, seed, d_dst);
     });
 }
@@ -1275,7 +1280,7 @@ int sites_impl(pf_handle* h, const uint8_t* idx, int B, int N, int L, const int3
     const int32_t* map = sites ? sites : start.data();
     // (what is left - the residues - is refused by forward_derived before its first device call)
     bool uploaded = false;
-    return forward_derived(h, idx, B, N, L, S, K, out, "site sets", [&](const uint8_t* d_src, int nb, int j0, int nj, uint8_t* d_dst) -> int {
+    return forward_derived(h, idx, B, N, L, S, N, K, out, "site sets", [&](const uint8_t* d_src, int nb, int j0, int nj, uint8_t* d_dst) -> int {
         if (!uploaded) {
             const int rc2 = ensure_buffer(h, &h->d_map, &h->d_map_bytes, nmap);
             if (rc2) return rc2;
@@ -1428,6 +1433,119 @@ int site_host_impl(pf_handle* h, const uint8_t* idx, int B, int N, int L, float*
     return range_recheck(h, out, B, N, 0, L, L, h->d_idx, (size_t)B, stage, redo);
 }
 
+// ---- the taxon axis (pf_gather_taxa_device, pf_forward_taxa, pf_forward_leave_one_out, pf_loo_stats_device) ---------
+// A derived alignment is a list of source ROWS (pf_taxa.hip.h); its distances are pf_forward's of the host-cut rows,
+// on the path its own shape (M, L) takes.
+
+// taxa: device int32 [..][M]; sets s_begin .. s_begin + S - 1
+int launch_gather_taxa(pf_handle* h, const uint8_t* d_src, int B, int N, int L, const int32_t* d_taxa, int s_begin, int S, int M,
+                       uint8_t* d_dst) {
+    h->cur = h->stream;
+    ProfScope ps(h, K_GATHER_TAXA);
+    const hipError_t e = pft::launch_gather_taxa(h->stream, d_src, B, N, L, d_taxa, s_begin, S, M, d_dst, h->bad_idx_dev + 1);
+    if (e != hipSuccess) return fail(h, PF_EHIP, "k_gather_taxa launch failed: %s", hipGetErrorString(e));
+    return PF_OK;
+}
+
+int launch_loo_stats(pf_handle* h, const float* d_full, const float* d_loo, int B, int N, float* d_infl, float* d_shift, float* d_ctx) {
+    h->cur = h->stream;
+    ProfScope ps(h, K_LOO_STATS);
+    const hipError_t e = pft::launch_loo_stats(h->stream, d_full, d_loo, B, N, d_infl, d_shift, d_ctx);
+    if (e != hipSuccess) return fail(h, PF_EHIP, "k_loo_taxon / k_loo_pair launch failed: %s", hipGetErrorString(e));
+    return PF_OK;
+}
+
+// What the taxon calls refuse beside what pf_forward refuses at the source's shape, before any device work: the same
+// at the derived shape (M, L), sizes that overflow, and a communicator of more than one rank.
+int check_taxa_call(pf_handle* h, int B, int N, int L, int S, int M, size_t* ntab) {
+    int rc = check_dims(h, B, N, L, L);
+    if (rc) return rc;
+    if (S < 1) return fail(h, PF_EINVAL, "a taxon table needs S >= 1 sets (got %d)", S);
+    if (M < 2) return fail(h, PF_EINVAL, "a taxon set needs M >= 2 rows (got %d)", M);
+    if ((rc = check_dims(h, B, M, L, L))) return rc;
+    if (h->world > 1)
+        return fail(h, PF_ESTATE, "taxon subsets are not site-sharded: this handle's communicator has %d ranks (use a handle "
+                                  "without a communicator)", h->world);
+    const size_t P = (size_t)M * (M - 1) / 2;
+    size_t n = 0;
+    if (!mul_size((size_t)B, (size_t)S, P * sizeof(float), &n) || !mul_size((size_t)B, (size_t)S, (size_t)M * L, &n) ||
+        !mul_size((size_t)S, (size_t)M, sizeof(int32_t), ntab))
+        return fail(h, PF_EINVAL, "B=%d x S=%d taxon sets of %d x %d overflow the address space", B, S, M, L);
+    return PF_OK;
+}
+
+// the S sets of a validated host table taxa [S][M], uploaded once into the grow-only h->d_map, through forward_derived
+int taxa_derived(pf_handle* h, const uint8_t* idx, int B, int N, int L, const int32_t* taxa, size_t ntab, int S, int M, float* out) {
+    bool uploaded = false;
+    return forward_derived(h, idx, B, N, L, S, M, L, out, "taxon sets", [&](const uint8_t* d_src, int nb, int j0, int nj, uint8_t* d_dst) -> int {
+        if (!uploaded) {
+            const int rc2 = ensure_buffer(h, &h->d_map, &h->d_map_bytes, ntab);
+            if (rc2) return rc2;
+            HIPCHK(h, hipMemcpyAsync(h->d_map, taxa, ntab, hipMemcpyHostToDevice, h->stream));
+            uploaded = true;
+        }
+        return launch_gather_taxa(h, d_src, nb, N, L, h->d_map, j0, nj, M, d_dst);
+    });
+}
+
+int taxa_impl(pf_handle* h, const uint8_t* idx, int B, int N, int L, const int32_t* taxa, int S, int M, float* out) {
+    size_t ntab = 0;
+    int rc = check_taxa_call(h, B, N, L, S, M, &ntab);
+    if (rc) return rc;
+    if (!out || !idx || !taxa) return fail(h, PF_EINVAL, "null buffer");
+    const int64_t at = pftaxa::first_bad_taxon(taxa, (size_t)S * M, N);
+    if (at >= 0)
+        return fail(h, PF_EINVAL, "taxon %d at set %lld, position %lld is outside [0, %d)", (int)taxa[at], (long long)(at / M),
+                    (long long)(at % M), N);
+    // (what is left - the residues - is refused by forward_derived before its first device call)
+    return taxa_derived(h, idx, B, N, L, taxa, ntab, S, M, out);
+}
+
+// pf_forward_leave_one_out: pf_forward of the B sources, then their N cuts each (row t of the table: 0 .. N - 1 without
+// t) through forward_derived, in sub-calls of whole sources holding at most LOO_SUB_FLOATS distances - what `loo`
+// occupies on the device - and each sub-call's reduction on the device.  The reduction reads what the range re-check
+// left: if it replaced a set on the host, the sub-call's distances go up again first.
+constexpr size_t LOO_SUB_FLOATS = (size_t)1 << 22;
+
+int loo_impl(pf_handle* h, const uint8_t* idx, int B, int N, int L, float* out, float* loo, float* influence, float* shift,
+             float* context) {
+    int rc = check_dims(h, B, N, L, L);
+    if (rc) return rc;
+    if (N < 3) return fail(h, PF_EINVAL, "leave-one-out needs N >= 3 sequences (got %d): a cut keeps at least one pair", N);
+    size_t ntab = 0;
+    if ((rc = check_taxa_call(h, B, N, L, N, N - 1, &ntab))) return rc;
+    if (!out || !idx || !influence || !shift || !context) return fail(h, PF_EINVAL, "null buffer");
+    if ((rc = check_residues(h, idx, (size_t)B * N * L))) return rc;
+    const size_t P = (size_t)N * (N - 1) / 2, P1 = (size_t)(N - 1) * (N - 2) / 2, per_loo = (size_t)N * P1;
+    const int sub = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, LOO_SUB_FLOATS / per_loo));
+    std::vector<int32_t> table;
+    std::vector<float> tmp;
+    try {
+        table.resize((size_t)N * (N - 1));
+        if (!loo) tmp.resize((size_t)sub * per_loo);
+    } catch (const std::bad_alloc&) { return fail(h, PF_ENOMEM, "out of host memory for the leave-one-out sets of %d sequences", N); }
+    for (int t = 0; t < N; ++t)
+        for (int m = 0; m < N - 1; ++m) table[(size_t)t * (N - 1) + m] = m + (m >= t ? 1 : 0);
+    if ((rc = forward_host_impl(h, idx, B, N, 0, L, L, out))) return rc;
+    for (int b0 = 0; b0 < B; b0 += sub) {
+        const int nb = std::min(sub, B - b0);
+        float* hl = loo ? loo + (size_t)b0 * per_loo : tmp.data();
+        const int64_t before = h->rechecked;
+        if ((rc = taxa_derived(h, idx + (size_t)b0 * N * L, nb, N, L, table.data(), ntab, N, N - 1, hl))) return rc;
+        const size_t nloo = (size_t)nb * per_loo * sizeof(float), nfull = (size_t)nb * P, nrow = (size_t)nb * N;
+        if (h->rechecked != before) HIPCHK(h, hipMemcpyAsync(h->d_out, hl, nloo, hipMemcpyHostToDevice, h->stream));
+        if ((rc = ensure_buffer(h, &h->d_loo, &h->d_loo_bytes, (2 * nfull + 2 * nrow) * sizeof(float)))) return rc;
+        float *d_full = h->d_loo, *d_ctx = d_full + nfull, *d_infl = d_ctx + nfull, *d_shift = d_infl + nrow;
+        HIPCHK(h, hipMemcpyAsync(d_full, out + (size_t)b0 * P, nfull * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        if ((rc = launch_loo_stats(h, d_full, h->d_out, nb, N, d_infl, d_shift, d_ctx))) return rc;
+        HIPCHK(h, hipMemcpyAsync(context + (size_t)b0 * P, d_ctx, nfull * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(influence + (size_t)b0 * N, d_infl, nrow * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(shift + (size_t)b0 * N, d_shift, nrow * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return PF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1568,6 +1686,7 @@ int pf_destroy(pf_handle_t* h) {
     if (h->d_mpart) hipFree(h->d_mpart);
     if (h->d_se) hipFree(h->d_se);
     if (h->d_prof) hipFree(h->d_prof);
+    if (h->d_loo) hipFree(h->d_loo);
     if (h->stream) hipStreamDestroy(h->stream);
     if (h->bad_idx_host) hipHostFree(h->bad_idx_host);
     delete h;
@@ -1677,6 +1796,43 @@ int pf_forward_windows(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N,
     if (S < 0) return fail(h, PF_EINVAL, "bad window rule L=%d W=%d step=%d", L, W, step);
     if (S_cap < S) return fail(h, PF_EINVAL, "out holds %d windows, L=%d W=%d step=%d gives %d", S_cap, L, W, step, S);
     return sites_impl(h, idx, B, N, L, nullptr, step, S, W, out);
+}
+
+int pf_gather_taxa_device(pf_handle_t* h, const uint8_t* d_src, int32_t B, int32_t N, int32_t L, const int32_t* d_taxa, int32_t S,
+                          int32_t M, uint8_t* d_dst) {
+    if (!h) return PF_EINVAL;
+    if (!d_src || !d_dst || !d_taxa) return fail(h, PF_EINVAL, "null buffer");
+    if (B < 1 || N < 1 || L < 1 || S < 1 || M < 1) return fail(h, PF_EINVAL, "bad dimensions B=%d N=%d L=%d S=%d M=%d", B, N, L, S, M);
+    size_t n = 0;
+    if (!mul_size((size_t)B, (size_t)S, (size_t)M * L, &n) || !mul_size((size_t)S, (size_t)M, sizeof(int32_t), &n) ||
+        !mul_size((size_t)B, (size_t)N, (size_t)L, &n))
+        return fail(h, PF_EINVAL, "B=%d x S=%d taxon sets of %d x %d overflow the address space", B, S, M, L);
+    HIPCHK(h, hipSetDevice(h->device));
+    return launch_gather_taxa(h, d_src, B, N, L, d_taxa, 0, S, M, d_dst);
+}
+
+int pf_forward_taxa(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, int32_t L, const int32_t* taxa, int32_t S, int32_t M,
+                    float* out) {
+    if (!h) return PF_EINVAL;
+    return taxa_impl(h, idx, B, N, L, taxa, S, M, out);
+}
+
+int pf_forward_leave_one_out(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, int32_t L, float* out, float* loo,
+                             float* influence, float* shift, float* context) {
+    if (!h) return PF_EINVAL;
+    return loo_impl(h, idx, B, N, L, out, loo, influence, shift, context);
+}
+
+int pf_loo_stats_device(pf_handle_t* h, const float* d_full, const float* d_loo, int32_t B, int32_t N, float* d_influence,
+                        float* d_shift, float* d_context) {
+    if (!h) return PF_EINVAL;
+    if (!d_full || !d_loo || !d_influence || !d_shift || !d_context) return fail(h, PF_EINVAL, "null buffer");
+    if (B < 1 || N < 3 || N > 32767) return fail(h, PF_EINVAL, "bad dimensions B=%d N=%d (leave-one-out needs 3 <= N <= 32767)", B, N);
+    size_t n = 0;
+    if (!mul_size((size_t)B, (size_t)N, (size_t)(N - 1) * (N - 2) / 2 * sizeof(float), &n))
+        return fail(h, PF_EINVAL, "B=%d x %d leave-one-out sets of %d sequences overflow the address space", B, N, N - 1);
+    HIPCHK(h, hipSetDevice(h->device));
+    return launch_loo_stats(h, d_full, d_loo, B, N, d_influence, d_shift, d_context);
 }
 
 int pf_forward_device(pf_handle_t* h, const uint8_t* d_idx, int32_t B, int32_t N, int32_t L, float* d_out) {

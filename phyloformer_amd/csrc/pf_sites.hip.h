@@ -24,6 +24,8 @@
 
 #include <algorithm>
 
+#include "pf_bytes.hip.h"
+
 namespace pfs {
 
 constexpr int GS_THREADS = 256;
@@ -43,14 +45,7 @@ struct GatherArgs {
     int vec;               // 1: K % 4 == 0 and dst 4-byte aligned (32-bit stores)
 };
 
-// four contiguous source bytes at any address, as the little-endian dword a 4-byte store writes
-__device__ inline uint32_t load_run4(const uint8_t* p) {
-    const uintptr_t ad = reinterpret_cast<uintptr_t>(p);
-    if ((ad & 3) == 0) return *reinterpret_cast<const uint32_t*>(p);
-    if ((ad & 1) == 0)
-        return (uint32_t)*reinterpret_cast<const uint16_t*>(p) | ((uint32_t)*reinterpret_cast<const uint16_t*>(p + 2) << 16);
-    return (uint32_t)p[0] | ((uint32_t)*reinterpret_cast<const uint16_t*>(p + 1) << 8) | ((uint32_t)p[3] << 24);
-}
+using pfbytes::load_run4;      // four contiguous source bytes at any address (pf_bytes.hip.h)
 
 // grid (ceil(K / GS_TILE), sets of this launch), block GS_THREADS
 template <bool TABLE>

@@ -114,12 +114,21 @@ SIGNATURES = {
     "pf_forward_site_profile": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                           C.c_void_p]),
     "pf_site_moments_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "pf_gather_taxa_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                        C.c_void_p]),
+    "pf_forward_taxa": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                  C.c_void_p]),
+    "pf_forward_leave_one_out": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pf_loo_stats_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
 }
 
 # Additions to ABI 5 that a library built before them lacks: bound when present; a call through a missing one raises
 # EngineError at call time (loading such a library stays possible).
 CALL_TIME_SYMBOLS = frozenset({"pf_forward_site_map", "pf_forward_site_map_device", "pf_forward_site_profile",
-                               "pf_site_moments_device"})
+                               "pf_site_moments_device", "pf_gather_taxa_device", "pf_forward_taxa",
+                               "pf_forward_leave_one_out", "pf_loo_stats_device"})
 
 _lib: Optional[C.CDLL] = None
 
@@ -328,8 +337,8 @@ class Engine:
     def _optional(self, name: str):
         fn = getattr(self._lib, name, None)
         if fn is None:
-            raise EngineError(PF_ESTATE, f"the loaded native library does not export {name} (it was built before the "
-                              "site-map entry points); rebuild with `python -m phyloformer_amd.build --force`")
+            raise EngineError(PF_ESTATE, f"the loaded native library does not export {name} (it was built before that "
+                              "entry point was added); rebuild with `python -m phyloformer_amd.build --force`")
         return fn
 
     def forward_site_map(self, idx: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
@@ -370,6 +379,58 @@ class Engine:
         (asynchronous on the handle's stream)."""
         self._check(self._optional("pf_site_moments_device")(self._h, C.c_void_p(d_map), B, P, L, C.c_void_p(d_se),
                                                              C.c_void_p(d_profile)))
+
+    # -- the taxon axis ---------------------------------------------------------------------
+    def forward_taxa(self, idx: np.ndarray, taxa: np.ndarray) -> np.ndarray:
+        """Distances of the alignments cut out of ``idx`` by a taxon table (``pf_forward_taxa``): ``uint8[B, N, L]``,
+        ``int[S, M]`` → ``float32[B, S, M (M - 1) / 2]`` (``[N, L]`` → ``[S, ...]``).  ``out[b, s]`` is ``forward`` of
+        ``idx[b][taxa[s], :]`` (``taxa.cut_taxa``), bit for bit; entries outside ``[0, N)`` raise ``ValueError``."""
+        fn = self._optional("pf_forward_taxa")
+        idx, single = self._sources(idx)
+        B, N, L = idx.shape
+        tab = np.asarray(taxa)
+        if tab.ndim != 2 or tab.dtype.kind not in "iu":
+            raise ValueError(f"taxa must be an integer array [S, M], got {tab.dtype} {tab.shape}")
+        if tab.size and (tab.min() < -2 ** 31 or tab.max() >= 2 ** 31):
+            raise ValueError(f"taxon {int(tab.max() if tab.max() >= 2 ** 31 else tab.min())} is outside [0, {N})")
+        tab = np.ascontiguousarray(tab, dtype=np.int32)
+        S, M = tab.shape
+        out = np.empty((B, S, max(M, 0) * max(M - 1, 0) // 2), dtype=np.float32)
+        self._check(fn(self._h, idx.ctypes.data, B, N, L, tab.ctypes.data if tab.size else None, S, M,
+                       out.ctypes.data if out.size else None))
+        return out[0] if single else out
+
+    def forward_leave_one_out(self, idx: np.ndarray, keep_loo: bool = False):
+        """Leave-one-out taxon influence (``pf_forward_leave_one_out``): ``uint8[B, N, L]``, ``N >= 3`` →
+        ``(dist float32[B, P], influence float32[B, N], shift float32[B, N], context float32[B, P])``, with
+        ``keep_loo`` a fifth array ``loo float32[B, N, P1]`` (``[N, L]`` drops ``B`` everywhere).  ``dist`` is
+        ``forward``'s, ``loo[b, t]`` is ``forward_taxa`` of ``taxa.leave_one_out_sets(N)[t]``, both bit for bit; the
+        statistics are ``taxa.loo_stats(dist, loo)``, reduced on the GPU."""
+        fn = self._optional("pf_forward_leave_one_out")
+        idx, single = self._sources(idx)
+        B, N, L = idx.shape
+        P, P1 = N * (N - 1) // 2, max(N - 1, 0) * max(N - 2, 0) // 2
+        out = np.empty((B, P), dtype=np.float32)
+        loo = np.empty((B, N, P1), dtype=np.float32) if keep_loo else None
+        infl = np.empty((B, N), dtype=np.float32)
+        shift = np.empty((B, N), dtype=np.float32)
+        ctx = np.empty((B, P), dtype=np.float32)
+        self._check(fn(self._h, idx.ctypes.data, B, N, L, out.ctypes.data, loo.ctypes.data if keep_loo and loo.size else None,
+                       infl.ctypes.data, shift.ctypes.data, ctx.ctypes.data))
+        res = (out, infl, shift, ctx) + ((loo,) if keep_loo else ())
+        return tuple(r[0] for r in res) if single else res
+
+    def gather_taxa_device(self, d_src: int, B: int, N: int, L: int, d_taxa: int, S: int, M: int, d_dst: int):
+        """``pf_gather_taxa_device``: ``d_src [B][N][L]`` → ``d_dst [B][S][M][L]`` by a device taxon table ``d_taxa int32
+        [S][M]`` (device buffers, asynchronous on the handle's stream)."""
+        self._check(self._optional("pf_gather_taxa_device")(self._h, C.c_void_p(d_src), B, N, L, C.c_void_p(d_taxa), S, M,
+                                                            C.c_void_p(d_dst)))
+
+    def loo_stats_device(self, d_full: int, d_loo: int, B: int, N: int, d_influence: int, d_shift: int, d_context: int):
+        """``pf_loo_stats_device``: device ``full float32 [B][P]``, ``loo float32 [B][N][P1]`` → ``d_influence [B][N]``,
+        ``d_shift [B][N]``, ``d_context [B][P]`` (asynchronous on the handle's stream)."""
+        self._check(self._optional("pf_loo_stats_device")(self._h, C.c_void_p(d_full), C.c_void_p(d_loo), B, N,
+                                                          C.c_void_p(d_influence), C.c_void_p(d_shift), C.c_void_p(d_context)))
 
     def forward_sharded(self, idx_local: np.ndarray, l_begin: int, l_end: int, L_total: int) -> np.ndarray:
         """This rank's sites ``[l_begin, l_end)`` of ``uint8[B, N, L_total]`` alignments."""

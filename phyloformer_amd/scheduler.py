@@ -60,6 +60,8 @@ STALE_LOADS = 16
 BOOT_FLOATS = 1 << 22
 # --windows: the same bound on the window distances of one pf_forward_windows call (pf_forward_windows chunks them itself)
 WINDOW_FLOATS = BOOT_FLOATS
+# --leave-one-out: the same bound on the distances of the cuts (N x P1 floats per alignment) of one pf_forward_leave_one_out call
+LOO_FLOATS = BOOT_FLOATS
 
 
 def auto_batch(n_seqs: int, n_sites: int, max_batch: int = 4096, token_budget: int = TOKEN_BUDGET) -> int:
@@ -118,7 +120,7 @@ class DirectoryRunner:
 
     def __init__(self, engine, out_dir: str, trees: bool = False, batch: int = 0,
                  io_threads: int = 4, native_io: bool = True, progress=None, bootstrap: int = 0, seed: int = 0,
-                 windows: Optional[Tuple[int, int]] = None, site_profile: bool = False):
+                 windows: Optional[Tuple[int, int]] = None, site_profile: bool = False, leave_one_out: bool = False):
         self.engines = list(engine) if isinstance(engine, (list, tuple)) else [engine]
         self.out_dir = out_dir
         self.trees = trees
@@ -136,6 +138,9 @@ class DirectoryRunner:
         if self.windows:
             self.stats.update({"windows": 0, "windows_s": 0.0})
         self.site_profile = bool(site_profile)    # --site-profile: <stem>.sites.tsv, <stem>.se.phy
+        self.leave_one_out = bool(leave_one_out)  # --leave-one-out: <stem>.taxa.tsv, <stem>.context.phy
+        if self.leave_one_out:
+            self.stats.update({"loo_sets": 0})
         self._lock = threading.Lock()
 
     # -- stages -----------------------------------------------------------------------------
@@ -300,6 +305,60 @@ class DirectoryRunner:
         for (path, (fb, i), _none), se, prof in zip(group, ses, profiles):
             self._write_site_profile(path, se, prof, fb.ids(i))
 
+    # -- --leave-one-out --------------------------------------------------------------------
+    def _loo_error(self, path: str, n_seqs: int) -> Optional[Exception]:
+        """A file with fewer than 3 sequences has no leave-one-out cut with a pair: an error for that file, raised where
+        the loop reaches it."""
+        if self.leave_one_out and n_seqs < 3:
+            return ValueError(f"--leave-one-out: {path} has N = {n_seqs} sequences, fewer than the 3 a cut with one pair needs")
+        return None
+
+    def _forward_loo(self, engine, shape: Tuple[int, int], batch: np.ndarray):
+        """``forward_leave_one_out`` of a launch group in sub-batches of at most LOO_FLOATS distances of cuts; the cuts'
+        distances are kept only for the trees of ``rf_pruned`` (``--trees``)."""
+        N = shape[0]
+        sub = max(1, LOO_FLOATS // max(1, N * (N - 1) * (N - 2) // 2))
+        parts = [engine.forward_leave_one_out(batch[s0:s0 + sub], keep_loo=self.trees) for s0 in range(0, len(batch), sub)]
+        return [np.concatenate([p[k] for p in parts]) for k in range(len(parts[0]))]
+
+    def _write_taxa(self, path: str, pred: np.ndarray, infl: np.ndarray, shift: np.ndarray, ctx: np.ndarray,
+                    loo: Optional[np.ndarray], ids: List[str]):
+        """``<stem>.taxa.tsv`` and ``<stem>.context.phy`` of one file (ids and number format of ``<stem>.phy``); with
+        ``--trees`` the column ``rf_pruned`` from NJ trees on index labels."""
+        from .taxa import context_phylip, rf_pruned, taxa_tsv
+        stem, N = Path(path).stem, len(ids)
+        rf = None
+        if self.trees:
+            labels = [str(k) for k in range(N)]
+            if N - 1 < 4:
+                rf = ["NA"] * N
+            else:
+                if self.native_io:
+                    from .hostio import nj_newick
+
+                    def nj(vec, names):
+                        return nj_newick(vec, names).decode("utf8")
+                else:
+                    from .nj import neighbor_joining
+                    from .phylip import vec_to_phylip
+
+                    def nj(vec, names):
+                        return neighbor_joining(vec_to_phylip(vec, names)[0].astype("float64"), names)
+                rf = rf_pruned(nj(pred, labels), [nj(loo[t], labels[:t] + labels[t + 1:]) for t in range(N)], N)
+        with open(os.path.join(self.out_dir, f"{stem}.taxa.tsv"), "w") as fh:
+            fh.write(taxa_tsv(ids, infl, shift, rf))
+        if self.native_io:
+            from .hostio import format_phylip
+            with open(os.path.join(self.out_dir, f"{stem}.context.phy"), "wb") as fh:
+                fh.write(format_phylip(ctx, ids))
+            return
+        with open(os.path.join(self.out_dir, f"{stem}.context.phy"), "w") as fh:
+            fh.write(context_phylip(ctx, ids))
+
+    def _write_taxa_native(self, group: list, preds, infls, shifts, ctxs, loos):
+        for k, (path, (fb, i), _none) in enumerate(group):
+            self._write_taxa(path, preds[k], infls[k], shifts[k], ctxs[k], None if loos is None else loos[k], fb.ids(i))
+
     def _launch(self, engine, shape: Tuple[int, int], group: list, writers: ThreadPoolExecutor, pending: deque):
         native = group[0][2] is None              # entries of _feed_native: (path, (FastaBatch, file), None)
         t0 = time.perf_counter()
@@ -311,6 +370,10 @@ class DirectoryRunner:
         if self.site_profile:
             # the same forward (its distances are forward's, bit for bit) also leaves se and the site profile
             preds, ses, profiles = engine.forward_site_profile(batch)
+        elif self.leave_one_out:
+            # the same distances (forward's, bit for bit), then the N cuts of every alignment and their statistics
+            preds, infls, shifts, ctxs, *loos = self._forward_loo(engine, shape, batch)
+            loos = loos[0] if loos else None
         else:
             preds = engine.forward(batch)
         dt = time.perf_counter() - t0
@@ -331,6 +394,14 @@ class DirectoryRunner:
                 else:
                     for (path, _idx, ids), se, prof in zip(group, ses, profiles):
                         pending.append(writers.submit(self._write_site_profile, path, se, prof, ids))
+            if self.leave_one_out:
+                self.stats["loo_sets"] += len(group) * shape[0]
+                if native:
+                    pending.append(writers.submit(self._write_taxa_native, group, preds, infls, shifts, ctxs, loos))
+                else:
+                    for k, (path, _idx, ids) in enumerate(group):
+                        pending.append(writers.submit(self._write_taxa, path, preds[k], infls[k], shifts[k], ctxs[k],
+                                                      None if loos is None else loos[k], ids))
             if self.progress is not None and not self.bootstrap and not self.windows:
                 self.progress(len(group))
         if self.bootstrap:
@@ -342,7 +413,7 @@ class DirectoryRunner:
         with self._lock:
             drain = []
             # bound the write queue so results do not pile up in memory
-            while len(pending) > 8 * self.io_threads + (1 if native else len(group)) * (2 if self.bootstrap or self.windows or self.site_profile else 1):
+            while len(pending) > 8 * self.io_threads + (1 if native else len(group)) * (2 if self.bootstrap or self.windows or self.site_profile or self.leave_one_out else 1):
                 drain.append(pending.popleft())
         t0 = time.perf_counter()
         for f in drain:
@@ -444,7 +515,7 @@ class DirectoryRunner:
             finally:
                 self.stats["load_wait_s"] += time.perf_counter() - t0
             shape = (int(idx.shape[0]), int(idx.shape[1]))
-            bad = too_many_seqs(shape[0]) or self._window_error(path, shape[1])
+            bad = too_many_seqs(shape[0]) or self._window_error(path, shape[1]) or self._loo_error(path, shape[0])
             if bad is not None:
                 for _p, f in inflight:
                     f.cancel()
@@ -483,10 +554,13 @@ class DirectoryRunner:
             ok = (fb.status == 0) & (fb.l > 0) & (fb.n <= MAX_SEQS) & (fb.n != 1)
             if self.windows:
                 ok &= fb.l >= self.windows[0]
+            if self.leave_one_out:
+                ok &= fb.n >= 3
             stop = len(fb) if ok.all() else int(np.argmin(ok))
             if stop < len(fb):
                 bad = (fb.error(stop) or too_many_seqs(int(fb.n[stop])) or
-                       self._window_error(fb.paths[stop], int(fb.l[stop])))
+                       self._window_error(fb.paths[stop], int(fb.l[stop])) or
+                       self._loo_error(fb.paths[stop], int(fb.n[stop])))
             ns, ls = fb.n.tolist(), fb.l.tolist()
             for i in range(stop):
                 shape = (ns[i], ls[i])
