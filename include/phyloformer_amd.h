@@ -280,6 +280,52 @@ int pf_forward_leave_one_out(pf_handle_t* h, const uint8_t* idx, int32_t B, int3
 int pf_loo_stats_device(pf_handle_t* h, const float* d_full, const float* d_loo, int32_t B, int32_t N, float* d_influence,
                         float* d_shift, float* d_context);
 
+/* ---- site weights: weighted forward, pattern compression, bootstrap on distinct sites (additive to ABI 5) ----
+ *
+ * Nothing in the network depends on a site's position, and every reduction over sites is a plain sum (the row-attention
+ * statistics and the head's site mean); column attention, LayerNorm and the feed-forward act per site.  An alignment in
+ * which site l occurs w_l times is therefore the alignment of its distinct sites with every sum over sites weighted by
+ * w_l and L replaced by W = sum_l w_l.  Weights are floats, finite and >= 0, W > 0 per alignment;
+ * a site of weight 0 is computed and counts nothing.  W is the float sum of an alignment's weights in site order, formed
+ * on the device by one thread per alignment (k_weight_sums) for every entry point.
+ * Bit identity: with every weight 1 the weighted calls return their unweighted twins' bits on every path; weights
+ * scaled by a power of two return the same bits (short of under- / overflow).  Integer weights agree with the forward
+ * of the expanded alignment to rounding - not bit for bit: the sums associate differently.
+ * Path, chunking and options ("precise", "generic", "ws_limit_mb", "max_seqs", the range re-check) as for the unweighted
+ * twin, chosen by the shape (N, L) of what is forwarded - never by W. */
+/* idx host uint8 [B][N][L], w host float [B][L] -> out host float [B][P].  Synchronous.  Refused before any device work,
+ * `out` untouched: everything pf_forward refuses; NULL weights; a negative or non-finite weight (the message names
+ * alignment and position); an alignment whose weights sum to 0 (or to inf); and (PF_ESTATE) a handle whose communicator
+ * has more than one rank, or option "embed_mfma". */
+int pf_forward_weighted(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, int32_t L, const float* w, float* out);
+/* The same on device buffers d_idx [B][N][L], d_w float [B][L] -> d_out [B][P]; async on the handle's stream.  The
+ * weights never pass through the host: a bad weight or W == 0 is reported late, like a residue byte > 21 - the next
+ * pf_synchronize / pf_memcpy_d2h on the handle returns PF_EINVAL once (results since the last one are not valid). */
+int pf_forward_weighted_device(pf_handle_t* h, const uint8_t* d_idx, int32_t B, int32_t N, int32_t L, const float* d_w,
+                               float* d_out);
+/* pf_forward_sites with a weight per table entry: sites host int32 [S][K], w host float [S][K] -> out [B][S][P];
+ * out[b][s] equals, bit for bit, pf_forward_weighted of the host-cut alignment idx[b][:, sites[s]] with weights w[s].
+ * Refusals: pf_forward_sites' and pf_forward_weighted's (a bad weight is named by set and position). */
+int pf_forward_sites_weighted(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, int32_t L, const int32_t* sites,
+                              const float* w, int32_t S, int32_t K, float* out);
+/* pf_bootstrap on distinct sites: out[b][r] is replicate r of pf_bootstrap's stream for `seed`, computed as
+ * pf_forward_sites_weighted with the tables of pf_boot_counts - the replicate's distinct sites, ascending, weighted by
+ * their multiplicities - every replicate padded with (site 0, weight 0) to K = pf_padded_sites(max_r distinct_r, L).
+ * About 0.63 L sites per replicate instead of L; the tables are built on the host.  It routes by (N, K).  Equal to
+ * pf_bootstrap to rounding, not bit for bit; one call with B sources equals B calls with one, bit for bit. */
+int pf_bootstrap_weighted(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, int32_t L, int32_t R, uint64_t seed,
+                          float* out);
+/* Host helpers (no device, no handle; csrc/pf_weights_host.h, Python twins in phyloformer_amd/weights_sites.py).
+ * pf_padded_sites: min(L, 32 * ceil(K / 32)) - a launch needs one shape and a tile is 32 tokens - or PF_EINVAL for
+ * K < 1 or K > L.  Padding entries are site 0 with weight 0. */
+int pf_padded_sites(int32_t K, int32_t L);
+/* Replicate r (0 <= r < R) of the stream of `seed` over L sites: sites[0..K) its distinct source sites, ascending,
+ * counts[0..K) their multiplicities (summing to L); both buffers hold L entries.  Returns K, or PF_EINVAL. */
+int pf_boot_counts(int32_t L, int32_t R, uint64_t seed, int32_t r, int32_t* sites, int32_t* counts);
+/* The distinct columns of idx host uint8 [N][L] in order of first occurrence: first[0..K) the site where each first
+ * stands, count[0..K) how often it occurs; both buffers hold L entries.  Returns K, PF_EINVAL or PF_ENOMEM. */
+int pf_compress_sites(const uint8_t* idx, int32_t N, int32_t L, int32_t* first, int32_t* count);
+
 /* ---- site-resolved distances: site map, standard errors, site profile (additive to ABI 5) ----
  *
  * The head computes one value per (pair, site), d[p][l] = softplus(w . x[p][l] + b), and a distance is their mean
@@ -361,7 +407,8 @@ int pf_memcpy_d2h(pf_handle_t* h, void* dst, const void* src, size_t bytes);
  * "resample" (k_resample of pf_bootstrap / pf_resample_sites_device), "gather" (k_gather_sites of pf_forward_sites /
  * pf_forward_windows / pf_gather_sites_device), "site_moments" (the reduction of pf_forward_site_profile /
  * pf_site_moments_device), "gather_taxa" (k_gather_taxa of pf_forward_taxa / pf_forward_leave_one_out /
- * pf_gather_taxa_device), "loo_stats" (the reduction of pf_forward_leave_one_out / pf_loo_stats_device).  Totals accumulate until reset.  "collectives" returns the number of all-reduces issued since the last reset in
+ * pf_gather_taxa_device), "loo_stats" (the reduction of pf_forward_leave_one_out / pf_loo_stats_device).
+ * "weight_sums" (k_weight_sums of the weighted forwards).  Totals accumulate until reset.  "collectives" returns the number of all-reduces issued since the last reset in
  * *launches (counted always, no profiling option needed; *total_ms = 0); "rechecked" likewise the number of
  * alignments the range re-check (option "recheck_above") computed again on the float64 kernels. */
 int pf_profile_reset(pf_handle_t* h);

@@ -104,6 +104,12 @@ def build_parser():
                              "without that leaf) and <stem>.context.phy, how much each distance depends on the other sequences, "
                              "as a PHYLIP matrix (descriptive statistics, not a test); <stem>.phy is unchanged; a file with "
                              "fewer than 3 sequences is an error")
+    parser.add_argument("--compress-sites", action="store_true",
+                        help="site-pattern compression: every alignment is inferred on its distinct columns with their "
+                             "counts as site weights (the same distances to rounding, fewer tokens where columns repeat); "
+                             "with --bootstrap R it is the R replicates that run on their distinct sites with their "
+                             "multiplicities (about a third fewer tokens per replicate; the alignment itself is inferred "
+                             "as without the flag, so only the support values of <stem>.sup.nwk can differ)")
     parser.add_argument("--python-io", action="store_true",
                         help="use the pure-Python FASTA parser and PHYLIP writer instead of the native ones")
     parser.add_argument("--worker", default=None, help=argparse.SUPPRESS)   # "r/W": share r of W of the files
@@ -152,6 +158,17 @@ def main(argv=None):
             parser.error("--leave-one-out is not supported with --site-profile (site maps of taxon subsets are out of scope)")
         if args.shard == "sites":
             parser.error("--leave-one-out is not supported with --shard sites (every cut would need its own collectives); "
+                         "use --shard files")
+
+    if args.compress_sites:
+        if windows is not None:
+            parser.error("--compress-sites is not supported with --windows (a window is a run of sites, not of patterns)")
+        if args.site_profile:
+            parser.error("--compress-sites is not supported with --site-profile (the profile is per site, not per pattern)")
+        if args.leave_one_out:
+            parser.error("--compress-sites is not supported with --leave-one-out (weighted taxon subsets are out of scope)")
+        if args.shard == "sites":
+            parser.error("--compress-sites is not supported with --shard sites (weighted forwards are not site-sharded); "
                          "use --shard files")
 
     from phyloformer_amd import scheduler
@@ -233,7 +250,8 @@ def main(argv=None):
                                        io_threads=args.io_threads, native_io=not args.python_io,
                                        progress=bar.update if bar is not None else None,
                                        bootstrap=args.bootstrap, seed=args.seed, windows=windows,
-                                       site_profile=args.site_profile, leave_one_out=args.leave_one_out)
+                                       site_profile=args.site_profile, leave_one_out=args.leave_one_out,
+                                       compress_sites=args.compress_sites)
     try:
         stats = runner.run(paths)
     finally:

@@ -466,6 +466,8 @@ struct MainArgs {
                             // 4 no next-row phase, 8 no apply phase, 16 no FFN (2 is unused now)
     float* sitemap;         // [B][P][Lloc]        out (last block, SITEMAP launches only): softplus of every token's
                             //                     head logit, the terms of the site mean (no padding, no trash area)
+    const float* w;         // [B][Lloc]           site weights (WEIGHTED launches only): what a site counts in the row
+                            //                     statistics and in the head's site sum
 };
 
 enum { MODE_FIRST = 0, MODE_MID = 1, MODE_LAST = 2, MODE_MID0 = 3, MODE_LAST_FOLD = 4 };
@@ -562,11 +564,17 @@ __device__ __forceinline__ void image_to_lds(const frag_t* src, unsigned char* s
 //   SITEMAP   : the last block also keeps what the head sums: a.sitemap[token] = softplus(head logit), one 4-byte
 //               store per token (pf_forward_site_map / pf_forward_site_profile).  A template parameter, not a run-time
 //               branch: the launches of pf_forward are the SITEMAP = false instantiations, unchanged
-template <int MODE, bool FLAT, bool SITEMAP = false>
+//   WEIGHTED  : site l of alignment b counts a.w[b][l] times (pf_forward_weighted and its kin): the validity mask vm of
+//               the row statistics carries the weight instead of 1, and the head's softplus term is multiplied by it
+//               before the part sum.  One 4-byte read per token; everything else - the token's own x, q', the column
+//               attention, the FFN - does not know the weight.  A template parameter for the same reason as SITEMAP;
+//               weight 1 multiplies exactly, so unit weights give the unweighted launch's bits
+template <int MODE, bool FLAT, bool SITEMAP = false, bool WEIGHTED = false>
 __global__ void __launch_bounds__(MAIN_THREADS, MAIN_WAVES / 4) k_main(MainArgs a) {
     constexpr bool LAST = MODE == MODE_LAST || MODE == MODE_LAST_FOLD;
     constexpr bool FOLD = MODE == MODE_LAST_FOLD;
     static_assert(!SITEMAP || LAST, "the site map is the head's: last block only");
+    static_assert(!WEIGHTED || (!SITEMAP && MODE != MODE_FIRST), "weighted launches: blocks' own modes, no site map");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     lds_frag_t lw = (lds_frag_t)smem;
     lds_f32_t lc = (lds_f32_t)(smem + FRAG_END * 16);
@@ -702,6 +710,8 @@ __global__ void __launch_bounds__(MAIN_THREADS, MAIN_WAVES / 4) k_main(MainArgs 
             const size_t tok = lp.tok0 + lp.toff;
             float x[32];
             float zh[4] = {0.f, 0.f, 0.f, 0.f};        // MODE_LAST_FOLD: the head's pre-activation, four partial chains
+            float wt = 1.f;                            // WEIGHTED: the token's site weight (a clamped lane's is masked)
+            if (WEIGHTED && LAST) wt = a.w[(size_t)b * a.Lloc + lc_];      // (in flight across the whole tile)
 
             if (MODE == MODE_FIRST) {
                 // embedding lookup + pair expansion (model.py:173-175): x = T[a_i] + T[a_j]
@@ -907,6 +917,7 @@ __global__ void __launch_bounds__(MAIN_THREADS, MAIN_WAVES / 4) k_main(MainArgs 
                 frag_t wl[8];
 #pragma unroll
                 for (int i = WVLO_LDS; i < 8; ++i) wl[i] = a.wv_lo[i * 64 + lane];
+                if (WEIGHTED) wt = a.w[(size_t)b * a.Lloc + lc_];      // (arrives with the Wv' lo fragments)
                 __builtin_amdgcn_sched_barrier(0);
                 {
                     // Branch-free store: a divergent `if (valid)` makes hipcc merge the vmcnt state of
@@ -970,7 +981,7 @@ __global__ void __launch_bounds__(MAIN_THREADS, MAIN_WAVES / 4) k_main(MainArgs 
                 const long slot0 = (long)b * a.slots_aln + cur.kt + (FLAT ? cur.r0 : 0);
                 for (int part = 0; part < (straddle ? 2 : 1); ++part) {
                     float* sp = a.spart + (size_t)(slot0 + part) * SROW;
-                    const float vm = (valid && lp.in_r1 == (part == 1)) ? 1.f : 0.f;
+                    const float vm = (valid && lp.in_r1 == (part == 1)) ? (WEIGHTED ? wt : 1.f) : 0.f;
                     float km[4];
 #pragma unroll
                     for (int i = 0; i < 4; ++i) km[i] = kn[i] * vm;
@@ -1006,7 +1017,7 @@ __global__ void __launch_bounds__(MAIN_THREADS, MAIN_WAVES / 4) k_main(MainArgs 
                 const float spz = softplus20(z);
                 const long slot0 = (long)b * a.slots_aln + cur.kt + (FLAT ? cur.r0 : 0);
                 for (int part = 0; part < (straddle ? 2 : 1); ++part) {
-                    const float so = half32_sum((valid && lp.in_r1 == (part == 1)) ? spz : 0.f);
+                    const float so = half32_sum((valid && lp.in_r1 == (part == 1)) ? (WEIGHTED ? wt * spz : spz) : 0.f);
                     if (lane == 0) a.outpart[slot0 + part] = so;
                 }
                 // both lanes of a pair_sum pair hold spz: the lower one stores it.  Tokens of a tile are consecutive in
@@ -1055,8 +1066,12 @@ struct EmbedArgs {
     float* srow;             // [B*P][72]
     int B, N, P, Lloc;
     unsigned* bad_idx;       // host-mapped sticky flag: set when a residue byte > 21 is seen (then clamped to 21)
+    const float* w;          // [B][Lloc] site weights (WEIGHTED only): a site's table rows count w times in srow
 };
 
+// WEIGHTED: block 0's statistics are the weighted sums; the weights travel like the residues,
+// 64 sites per wave register, one shuffle per iteration.  q' per token is stored unweighted.
+template <bool WEIGHTED = false>
 __global__ void __launch_bounds__(EMBED_THREADS) k_embed(EmbedArgs a) {
     extern __shared__ __attribute__((aligned(16))) float esm[];
     float* tab = esm;
@@ -1106,10 +1121,13 @@ __global__ void __launch_bounds__(EMBED_THREADS) k_embed(EmbedArgs a) {
             bad |= max(ra, rb) >= NA;
             return residue(ra) * 22 + residue(rb);
         };
+        auto fetch_w = [&](int blk) { return WEIGHTED ? a.w[(size_t)b * a.Lloc + min(blk * 64 + lane, a.Lloc - 1)] : 1.f; };
         const int nblk = (a.Lloc + 63) >> 6;
         int cur = fetch(0);
+        float wcur = fetch_w(0);
         for (int blk = 0; blk < nblk; ++blk) {
             const int nxt = fetch(min(blk + 1, nblk - 1));
+            const float wnxt = fetch_w(min(blk + 1, nblk - 1));
             const int lbase = blk * 64;
             const int nit = min(16, (a.Lloc - lbase + 3) >> 2);
             auto site = [&](int it, bool valid) {
@@ -1118,9 +1136,15 @@ __global__ void __launch_bounds__(EMBED_THREADS) k_embed(EmbedArgs a) {
                 const float* tr = tab + rr * PAIRTAB_W;
                 const f32x4 s = *reinterpret_cast<const f32x4*>(tr + 4 * cl);
                 const f32x4 e = *reinterpret_cast<const f32x4*>(tr + 64 + 4 * (cl & 1));   // even lanes q', odd k'
+                const float wl = WEIGHTED ? __shfl(wcur, 4 * it + sg) : 1.f;      // (all lanes: a shuffle reads no masked lane)
                 if (valid) {
-                    acc += s;
-                    acce += e;
+                    if (WEIGHTED) {
+                        acc += wl * s;
+                        acce += wl * e;
+                    } else {
+                        acc += s;
+                        acce += e;
+                    }
                     const size_t tok = row0 + l;
                     if (a.x) {       // wave-uniform: only the round-1 path / the debug tap materialise x0
                         const int ra = rr / 22, rb = rr - 22 * ra;
@@ -1138,6 +1162,7 @@ __global__ void __launch_bounds__(EMBED_THREADS) k_embed(EmbedArgs a) {
                 for (int it = 0; it < nit; ++it) site(it, lbase + 4 * it + sg < a.Lloc);   // (a lane past the end reads the clamped last site, unused)
             }
             cur = nxt;
+            wcur = wnxt;
         }
         // sum the four site sub-groups (lanes 16 and 32 apart)
 #pragma unroll
@@ -1176,6 +1201,8 @@ struct RowFinArgs {
     float* rq;           // [B*P][4]  L / S_q[h] * b_scale
     float a_scale, b_scale;   // powers of two, a_scale * b_scale = 1: b_scale < 1 only when L_total > 16,384 (q' / mean(q')
                               // can reach L_total; M_base is bounded by the weights, pf_lib.hip::check_f16_ranges)
+    const float* wst;    // [B][4] weighted forwards (pf_weights.hip.h): W, 1 / W, b_scale, a_scale of pair pr's alignment
+                         //        stand for L_total, b_scale and a_scale; null: an unweighted forward
 };
 
 // A block handles `iters` groups of four pairs one after the other: the 64 out_proj weights a thread holds are
@@ -1234,9 +1261,10 @@ __global__ void __launch_bounds__(256) k_rowfin(RowFinArgs a) {
         ctx[sub][c] = (s[c] + bvc * sk) / sk;
         // q / mean(q), attention.py:183: the factor k_main multiplies q' with
         if (c < 4) {
-            const float r = a.L_total / s[64 + c];
+            const float* ws = a.wst ? a.wst + (size_t)(pr / a.P) * 4 : nullptr;
+            const float r = (ws ? ws[0] : a.L_total) / s[64 + c];
             rqs[sub][c] = r;
-            a.rq[(size_t)pr * 4 + c] = r * a.b_scale;
+            a.rq[(size_t)pr * 4 + c] = r * (ws ? ws[2] : a.b_scale);
         }
     }
     __syncthreads();
@@ -1248,7 +1276,7 @@ __global__ void __launch_bounds__(256) k_rowfin(RowFinArgs a) {
 #pragma unroll
             for (int d = 0; d < 16; ++d) acc = fmaf(wo[hh][d], ctx[sub][16 * hh + d], acc);
             if (m) m[hh * 64 + c] = acc * rqs[sub][hh];
-            mm[sub][hh][c] = acc * a.a_scale;
+            mm[sub][hh][c] = acc * (a.wst ? a.wst[(size_t)(pr / a.P) * 4 + 3] : a.a_scale);
         }
         mm[sub][4][c] = biasc;
         mm[sub][5][c] = biascol;
@@ -1292,8 +1320,9 @@ __global__ void k_rowsum(const float* spart, float* srow, int npairs, int nparts
 }
 
 // per-tile softplus sums of the last block -> distances (site mean, model.py:185)
+// wst (weighted forwards, else null): [B][4], 1 / W of the pair's alignment at [1] stands for inv_L_total
 __global__ void k_outsum(const float* outpart, float* out, int npairs, int nparts_, float inv_L_total, int flat, int P,
-                         int Lloc, int slots_aln) {
+                         int Lloc, int slots_aln, const float* wst) {
     const int pr = blockIdx.x * blockDim.x + threadIdx.x;
     if (pr >= npairs) return;
     long first;
@@ -1308,7 +1337,7 @@ __global__ void k_outsum(const float* outpart, float* out, int npairs, int npart
 #pragma unroll
         for (int q = 0; q < 8; ++q) acc += v[q];
     }
-    out[pr] = acc * inv_L_total;
+    out[pr] = acc * (wst ? wst[(size_t)(pr / P) * 4 + 1] : inv_L_total);
 }
 
 // ---- column statistics -------------------------------------------------------------------

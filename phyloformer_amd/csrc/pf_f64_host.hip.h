@@ -263,6 +263,8 @@ struct F64Run {
     const uint8_t* d_idx;
     int B, N, P, Lloc, L_total;
     float* d_smap = nullptr;       // [B][P][Lloc] site map of the head's terms (unsharded site-map calls), or null
+    const float* d_w = nullptr;    // weighted forwards (unsharded): site weights [B][Lloc] and what k_weight_sums made
+    const float* d_wst = nullptr;  // of them, [B][4] (pf_weights.hip.h); null: an unweighted forward
     size_t ntok() const { return (size_t)B * P * Lloc; }
 };
 
@@ -287,11 +289,11 @@ int precise_stats_chunk(const pf_handle* h) { return h->precise_ffn_valu ? pfp::
 const F64Ends* precise_ends(const pf_handle* h) { return &h->pw.ends; }
 void precise_stats(pf_handle* h, const F64Run& r, int k, int col, size_t grid, int nchunk) {
     const pfp::AttnW& w = col ? h->pw.col[k] : h->pw.row[k];
-    pfp::launch_attn_stats(h->cur, grid, {r.w.x, r.w.q, r.w.part, w, col, r.P, r.Lloc, nchunk}, h->precise_ffn_valu);
+    pfp::launch_attn_stats(h->cur, grid, {r.w.x, r.w.q, r.w.part, w, col, r.P, r.Lloc, nchunk, r.d_w}, h->precise_ffn_valu);
 }
 void precise_apply(pf_handle* h, const F64Run& r, int k, int col, const double* stats, size_t grid, int nchunk) {
     const pfp::AttnW& w = col ? h->pw.col[k] : h->pw.row[k];
-    pfp::launch_attn_apply(h->cur, grid, {r.w.x, r.w.q, stats, w, col, r.P, r.Lloc, nchunk, col ? (double)r.P : (double)r.L_total});
+    pfp::launch_attn_apply(h->cur, grid, {r.w.x, r.w.q, stats, w, col, r.P, r.Lloc, nchunk, col ? (double)r.P : (double)r.L_total, r.d_wst});
 }
 void precise_ffn(pf_handle* h, const F64Run& r, int k) {
     pfp::launch_ffn(h->cur, {r.w.x, h->pw.ffn[k], r.ntok()}, h->precise_ffn_valu);
@@ -304,11 +306,11 @@ int generic_stats_chunk(const pf_handle*) { return pfg::CHUNK; }
 const F64Ends* generic_ends(const pf_handle* h) { return &h->gw.ends; }
 void generic_stats(pf_handle* h, const F64Run& r, int k, int col, size_t grid, int nchunk) {
     const pfg::AttnW& w = col ? h->gw.col[k] : h->gw.row[k];
-    pfg::launch_attn_stats(h->cur, grid, {r.w.x, r.w.q, r.w.part, w, h->garch, col, r.P, r.Lloc, nchunk});
+    pfg::launch_attn_stats(h->cur, grid, {r.w.x, r.w.q, r.w.part, w, h->garch, col, r.P, r.Lloc, nchunk, r.d_w});
 }
 void generic_apply(pf_handle* h, const F64Run& r, int k, int col, const double* stats, size_t grid, int nchunk) {
     const pfg::AttnW& w = col ? h->gw.col[k] : h->gw.row[k];
-    pfg::launch_attn_apply(h->cur, grid, {r.w.x, r.w.q, stats, w, h->garch, col, r.P, r.Lloc, nchunk, col ? (double)r.P : (double)r.L_total});
+    pfg::launch_attn_apply(h->cur, grid, {r.w.x, r.w.q, stats, w, h->garch, col, r.P, r.Lloc, nchunk, col ? (double)r.P : (double)r.L_total, r.d_wst});
 }
 void generic_ffn(pf_handle* h, const F64Run& r, int k) { pfg::launch_ffn(h->cur, {r.w.x, h->gw.ffn[k], h->garch, r.ntok()}); }
 const F64Path GENERIC_F64 = {K_GENERIC, generic_dims, ensure_generic_weights, generic_stats_chunk, generic_ends,
@@ -380,7 +382,7 @@ int f64_head(pf_handle* h, const F64Run& r) {
     if (!r.ntok()) { HIPCHK(h, hipMemsetAsync(r.w.osum, 0, (size_t)r.B * r.P * 8, h->cur)); return PF_OK; }
     const F64Ends& e = *r.path->ends(h);
     // (the precise path keeps its own instance: its dot product rounds differently from the generic one's at Ep = 64)
-    PF_F64LAUNCH(h, r, pfg::launch_head(h->cur, {r.w.x, e.hw, e.hb, r.w.osum, r.B * r.P, r.Lloc, r.d.C, r.d_smap},
+    PF_F64LAUNCH(h, r, pfg::launch_head(h->cur, {r.w.x, e.hw, e.hb, r.w.osum, r.B * r.P, r.Lloc, r.d.C, r.d_smap, r.d_w, r.P},
                                         r.path->prof == K_PRECISE));
     return PF_OK;
 }
@@ -402,16 +404,17 @@ int f64_schedule(pf_handle* h, F64Run* runs, size_t nruns, Reduce reduce, float*
     }
     for (F64Run* r = runs; r != end; ++r) if ((rc = f64_head(h, *r))) return rc;
     if ((rc = reduce(true, &sum))) return rc;
-    PF_F64LAUNCH(h, *runs, pfg::launch_out(h->cur, sum, d_out, runs->B * runs->P, (double)runs->L_total));
+    PF_F64LAUNCH(h, *runs, pfg::launch_out(h->cur, sum, d_out, runs->B * runs->P, (double)runs->L_total, runs->d_wst, runs->P));
     return PF_OK;
 }
 
 // One chunk of a (possibly site-sharded, possibly empty-shard) forward on the handle's main stream.
+// d_w, d_wst (weighted forwards, unsharded): the chunk's weight rows [B][Lloc] and their sums [B][4].
 int forward_chunk_f64(pf_handle* h, const F64Path& path, const uint8_t* d_idx, int B, int N, int Lloc, int L_total,
-                      float* d_out, float* d_smap = nullptr) {
+                      float* d_out, float* d_smap = nullptr, const float* d_w = nullptr, const float* d_wst = nullptr) {
     int rc = ensure_pairs(h, N);
     if (rc) return rc;
-    F64Run r{&path, path.dims(h), {}, d_idx, B, N, N * (N - 1) / 2, Lloc, L_total, d_smap};
+    F64Run r{&path, path.dims(h), {}, d_idx, B, N, N * (N - 1) / 2, Lloc, L_total, d_smap, d_w, d_wst};
     if ((rc = ensure_f64_workspace(h, r.d, B, r.P, Lloc, &r.w))) return rc;
     const bool reduces = reduces_now(h);
     ForwardScope scope(h, reduces);
@@ -432,7 +435,7 @@ int f64_chunk_batch(const pf_handle* h, const F64Path& path, int B, int P, int L
 }
 
 int forward_device_f64(pf_handle* h, const F64Path& path, const uint8_t* d_idx, int B, int N, int l_begin, int l_end,
-                       int L_total, float* d_out) {
+                       int L_total, float* d_out, const float* d_w = nullptr, const float* d_wst = nullptr) {
     int rc = path.prepare(h);
     if (rc) return rc;
     const int Lloc = l_end - l_begin, P = N * (N - 1) / 2;
@@ -443,7 +446,8 @@ int forward_device_f64(pf_handle* h, const F64Path& path, const uint8_t* d_idx, 
     for (int b0 = 0; b0 < B; b0 += cb) {
         const int nb = std::min(cb, B - b0);
         rc = forward_chunk_f64(h, path, d_idx ? d_idx + (size_t)b0 * N * Lloc : nullptr, nb, N, Lloc, L_total,
-                               d_out + (size_t)b0 * P);
+                               d_out + (size_t)b0 * P, nullptr, d_w ? d_w + (size_t)b0 * Lloc : nullptr,
+                               d_wst ? d_wst + (size_t)b0 * pfw::WST : nullptr);
         if (rc) return rc;
     }
     return PF_OK;

@@ -78,6 +78,8 @@ __global__ void __launch_bounds__(WAVE) kg_attn_stats(StatsArgs a) {
     const int S = ar.Ep / 4, TV = ar.Ep / 16, TF = ar.MF / 16;
     for (int i = lane; i < ar.SR; i += WAVE) sacc[i] = 0.0;
     const int e_end = min(nelem, (ch + 1) * CHUNK);
+    // weighted forwards, row attention: site e counts wt times (times 1.0 - exactly - everywhere else)
+    const float* wrow = (a.wt && !a.col) ? a.wt + (size_t)(line / a.P) * a.L : nullptr;
     for (int e0 = ch * CHUNK; e0 < e_end; e0 += 16) {
         if (lane < 16) {
             const int e = e0 + lane;
@@ -88,6 +90,7 @@ __global__ void __launch_bounds__(WAVE) kg_attn_stats(StatsArgs a) {
         stage_ln(xs, a.x, tok, valid, a.w.g, a.w.b, ar.E, ar.Ep, lane);
         const bool vj = valid[j] != 0;
         const size_t tj = tok[j];
+        const double wt = (wrow && vj) ? (double)wrow[e0 + j] : 1.0;
         for (int T = TV; T < TF; ++T) {                 // q and k: rows 0..NH-1 Wq, NH..2NH-1 Wk
             d4 acc;
 #pragma unroll
@@ -97,9 +100,10 @@ __global__ void __launch_bounds__(WAVE) kg_attn_stats(StatsArgs a) {
             for (int r = 0; r < 4; ++r) {
                 const int qr = 16 * (T - TV) + g + 4 * r;
                 const double val = (vj && qr < 2 * ar.NH) ? elu1(acc[r]) : 0.0;
+                const double valw = val * wt;
                 if (qr < ar.NH) { if (vj) a.q[tj * ar.NH + qr] = val; }
-                else if (qr < 2 * ar.NH) kl[j * ar.NH + qr - ar.NH] = val;
-                const double s = sum16(val);
+                else if (qr < 2 * ar.NH) kl[j * ar.NH + qr - ar.NH] = valw;
+                const double s = sum16(valw);
                 if (j == 0 && qr < 2 * ar.NH) sacc[ar.Ep + qr] += s;
             }
         }
@@ -149,7 +153,8 @@ __global__ void __launch_bounds__(WAVE) kg_attn_apply(ApplyArgs a) {
     const int S = ar.Ep / 4, TV = ar.Ep / 16;
     const double* st = a.stats + (size_t)line * ar.SR;
     for (int c = lane; c < ar.Ep; c += WAVE) ctx[c] = c < ar.E ? st[c] / st[ar.Ep + ar.NH + c / ar.HD] : 0.0;
-    for (int h = lane; h < ar.NH; h += WAVE) rq[h] = st[ar.Ep + h] / a.count;
+    const double count = (a.wst && !a.col) ? (double)a.wst[(size_t)(line / a.P) * 4] : a.count;
+    for (int h = lane; h < ar.NH; h += WAVE) rq[h] = st[ar.Ep + h] / count;
     const int e_end = min(nelem, (ch + 1) * CHUNK);
     for (int e0 = ch * CHUNK; e0 < e_end; e0 += 16) {
         if (lane < 16) {
@@ -245,6 +250,7 @@ __global__ void __launch_bounds__(256) kg_head(HeadArgs a) {
     const int lane = threadIdx.x & 63, line = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (line >= a.nlines) return;
     const double hb = a.hb[0];
+    const float* wrow = a.wt ? a.wt + (size_t)(line / a.P) * a.L : nullptr;     // weighted forwards: site l counts wt times
     double acc = 0.0;
     for (int l = 0; l < a.L; ++l) {
         const double* xt = a.x + ((size_t)line * a.L + l) * Ep;
@@ -252,14 +258,14 @@ __global__ void __launch_bounds__(256) kg_head(HeadArgs a) {
         for (int c = EP ? EP : lane; c < Ep; c += 64) d = fma(a.hw[c], xt[c], d);
         const double z = wave_sum(d) + hb;
         const double sp = z > 20.0 ? z : log1p(exp(z));           // nn.Softplus(beta = 1, threshold = 20)
-        acc += sp;
+        acc += wrow ? sp * (double)wrow[l] : sp;
         if (a.sitemap && lane == 0) a.sitemap[(size_t)line * a.L + l] = (float)sp;   // (outside the accumulation chain)
     }
     if (lane == 0) a.osum[line] = acc;
 }
-__global__ void __launch_bounds__(256) kg_out(const double* osum, float* out, int n, double l_total) {
+__global__ void __launch_bounds__(256) kg_out(const double* osum, float* out, int n, double l_total, const float* wst, int P) {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = (float)(osum[i] / l_total);               // model.py:185: mean over ALL sites
+    if (i < n) out[i] = (float)(osum[i] / (wst ? (double)wst[(size_t)(i / P) * 4] : l_total));   // model.py:185: mean over ALL sites
 }
 __global__ void __launch_bounds__(256) kg_accumulate(double* dst, const double* src, size_t n) {   // shard emulation
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -308,8 +314,8 @@ void launch_ffn(hipStream_t s, const FfnArgs& a) {
 void launch_head(hipStream_t s, const HeadArgs& a, bool precise) {
     hipLaunchKernelGGL(precise ? kg_head<64> : kg_head<0>, dim3((unsigned)((a.nlines + 3) / 4)), dim3(256), 0, s, a);
 }
-void launch_out(hipStream_t s, const double* osum, float* out, int n, double l_total) {
-    hipLaunchKernelGGL(kg_out, grid_of((size_t)n), dim3(256), 0, s, osum, out, n, l_total);
+void launch_out(hipStream_t s, const double* osum, float* out, int n, double l_total, const float* wst, int P) {
+    hipLaunchKernelGGL(kg_out, grid_of((size_t)n), dim3(256), 0, s, osum, out, n, l_total, wst, P);
 }
 void launch_accumulate(hipStream_t s, double* dst, const double* src, size_t n) { hipLaunchKernelGGL(kg_accumulate, grid_of(n), dim3(256), 0, s, dst, src, n); }
 void launch_narrow(hipStream_t s, const double* src, float* dst, size_t ntok, int Ep, int E) {

@@ -72,15 +72,21 @@ struct StatsArgs {
     const double* x; double* q; double* part; AttnW w; Arch ar;
     int col;            // 0: line = (b, p), elements = sites;  1: line = (b, l), elements = pairs
     int P, L, nchunk;
+    const float* wt;    // site weights [B][L] of a weighted forward, or null: a site's
+                        // contribution to the ROW statistics counts wt times (the column reductions run over pairs)
 };
 struct ApplyArgs {
     double* x; const double* q; const double* stats; AttnW w; Arch ar;
     int col, P, L, nchunk;
     double count;       // L_total (row attention) or P (column attention): q / q.mean(dim = -2)
+    const float* wst;   // weighted forwards (else null): [B][4], W of the line's alignment at [0] stands for L_total
+                        // in the row attention
 };
 struct FfnArgs { double* x; FfnW w; Arch ar; size_t ntok; };
 // sitemap (nullable): float [nlines][L], the softplus term of every token narrowed to float (pf_forward_site_map)
-struct HeadArgs { const double* x; const double* hw; const double* hb; double* osum; int nlines, L, Ep; float* sitemap; };
+// wt (nullable): site weights float [B][L] of a weighted forward, P pairs per alignment: a site's term counts wt times
+struct HeadArgs { const double* x; const double* hw; const double* hb; double* osum; int nlines, L, Ep; float* sitemap;
+                  const float* wt; int P; };
 
 // dynamic LDS of the three MFMA kernels for an architecture (bytes)
 size_t stats_lds(const Arch& a);
@@ -98,7 +104,8 @@ void launch_stats_fin(hipStream_t s, const double* part, double* stats, int nlin
 void launch_attn_apply(hipStream_t s, size_t nblocks, const ApplyArgs& a);
 void launch_ffn(hipStream_t s, const FfnArgs& a);
 void launch_head(hipStream_t s, const HeadArgs& a, bool precise);     // precise: kg_head<64>, the precise path's bits (Ep = 64)
-void launch_out(hipStream_t s, const double* osum, float* out, int n, double l_total);
+// wst (nullable; P pairs per alignment): [B][4] of a weighted forward, W at [0] stands for l_total
+void launch_out(hipStream_t s, const double* osum, float* out, int n, double l_total, const float* wst = nullptr, int P = 1);
 void launch_accumulate(hipStream_t s, double* dst, const double* src, size_t n);
 // debug taps: [ntok][Ep] double -> [ntok][E] float
 void launch_narrow(hipStream_t s, const double* src, float* dst, size_t ntok, int Ep, int E);

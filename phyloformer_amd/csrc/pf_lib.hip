@@ -29,6 +29,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/phyloformer_amd.h"
@@ -41,6 +42,8 @@
 #include "pf_sitemap.hip.h"
 #include "pf_sites_host.h"
 #include "pf_taxa.hip.h"
+#include "pf_weights.hip.h"
+#include "pf_weights_host.h"
 #include "pf_host_prep.h"
 
 using namespace pfk;
@@ -139,9 +142,10 @@ struct BlockDev {
 
 struct ProfSlot { int kid; hipEvent_t a, b; };
 const char* const KNAMES[] = {"embed", "rowfin", "colstats", "colfin", "main", "allreduce",
-                              "mha_qkv", "mha_attn", "mha_out", "precise", "generic", "resample", "gather", "site_moments", "gather_taxa", "loo_stats"};
+                              "mha_qkv", "mha_attn", "mha_out", "precise", "generic", "resample", "gather", "site_moments", "gather_taxa", "loo_stats",
+                              "weight_sums"};
 enum { K_EMBED = 0, K_ROWFIN, K_COLSTATS, K_COLFIN, K_MAIN, K_ALLREDUCE, K_MHA_QKV, K_MHA_ATTN, K_MHA_OUT, K_PRECISE, K_GENERIC,
-       K_RESAMPLE, K_GATHER, K_SITE_MOMENTS, K_GATHER_TAXA, K_LOO_STATS, K_COUNT };
+       K_RESAMPLE, K_GATHER, K_SITE_MOMENTS, K_GATHER_TAXA, K_LOO_STATS, K_WEIGHT_SUMS, K_COUNT };
 
 // what the embed and head kernels (pfg's, for both float64 paths) read: C = 64 (precise) or Ep (generic)
 struct F64Ends {
@@ -223,6 +227,11 @@ struct pf_handle {
     float* d_prof = nullptr; size_t d_prof_bytes = 0;
     // pf_forward_leave_one_out (grow-only): one sub-call's full distances and its influence / shift / context
     float* d_loo = nullptr; size_t d_loo_bytes = 0;
+    // weighted forwards (grow-only): the weight rows of a host call or of one chunk of derived alignments, what
+    // k_weight_sums made of a call's rows ([..][4], pf_weights.hip.h), and the weight table of pf_forward_sites_weighted
+    float* d_w = nullptr; size_t d_w_bytes = 0;
+    float* d_wst = nullptr; size_t d_wst_bytes = 0;
+    float* d_wtab = nullptr; size_t d_wtab_bytes = 0;
     // comm: one RCCL communicator per stream (comm[1] serves stream2), created together by pf_comm_init, so that
     // RCCL never has to order one half-batch's collectives behind the other's with an implicit cross-stream wait
     void* comm[2] = {nullptr, nullptr};
@@ -269,7 +278,8 @@ struct pf_handle {
     GenericWeights gw;
     std::vector<float> blob_copy;
     // sticky "residue byte > 21 seen" flag: pinned host memory the kernels write through its device alias
-    // ([1]: "site map entry out of range seen", k_gather_sites of pf_gather_sites_device)
+    // ([1]: "site map entry out of range seen", k_gather_sites of pf_gather_sites_device; [2]: "bad site weight seen",
+    // k_weight_sums of pf_forward_weighted_device)
     unsigned* bad_idx_host = nullptr;
     unsigned* bad_idx_dev = nullptr;
 };
@@ -597,14 +607,14 @@ int allreduce(pf_handle* h, void* buf, size_t count, int dtype = NCCL_FLOAT) {
     return PF_OK;
 }
 
-template <int MODE, bool SITEMAP = false>
+template <int MODE, bool SITEMAP = false, bool WEIGHTED = false>
 int launch_main(pf_handle* h, const MainArgs& a, int kid) {
     const long ntasks = (long)a.B * a.nt_aln;                        // one work item per 32-token tile
     const int cus = std::max(1, h->prop.multiProcessorCount - (h->reducing ? h->reserve_cus : 0));
     const int grid = (int)std::max<long>(1, std::min<long>(cus, (ntasks + MAIN_WAVES - 1) / MAIN_WAVES));
     ProfScope ps(h, kid);
-    if (a.flat) hipLaunchKernelGGL((k_main<MODE, true, SITEMAP>), dim3(grid), dim3(MAIN_THREADS), MAIN_LDS_BYTES, h->cur, a);
-    else hipLaunchKernelGGL((k_main<MODE, false, SITEMAP>), dim3(grid), dim3(MAIN_THREADS), MAIN_LDS_BYTES, h->cur, a);
+    if (a.flat) hipLaunchKernelGGL((k_main<MODE, true, SITEMAP, WEIGHTED>), dim3(grid), dim3(MAIN_THREADS), MAIN_LDS_BYTES, h->cur, a);
+    else hipLaunchKernelGGL((k_main<MODE, false, SITEMAP, WEIGHTED>), dim3(grid), dim3(MAIN_THREADS), MAIN_LDS_BYTES, h->cur, a);
     HIPCHK(h, hipGetLastError());
     return PF_OK;
 }
@@ -625,6 +635,8 @@ struct ShardRun {
     hipStream_t stream;    // the stream the run's launches go to
     RowStats rs;           // where the next block's row statistics are
     float* d_smap = nullptr;   // [B][P][Lloc] site map of the head's terms (pf_forward_site_map*), or null
+    const float* d_w = nullptr;     // weighted forwards (unsharded): site weights [B][Lloc] and what k_weight_sums made
+    const float* d_wst = nullptr;   // of them, [B][4] (pf_weights.hip.h); null: an unweighted forward
 };
 
 int zero_fill(pf_handle* h, float* p, size_t n) {
@@ -643,6 +655,7 @@ MainArgs main_args(pf_handle* h, const ShardRun& r) {
     m.trash_tok = (size_t)r.B * r.P * r.Lloc;
     m.ablate = h->ablate;
     m.prof = h->phase_prof_last ? nullptr : h->phase_prof;
+    m.w = r.d_w;
     return m;
 }
 
@@ -666,11 +679,12 @@ int phase_first(pf_handle* h, const ShardRun& r) {
         // x0 is written only for those who read it: the round-1 consumers or the "x0" debug tap
         float* x0 = (x0_on_the_fly(h) && !h->debug_keep) ? nullptr : r.w.x;
         EmbedArgs e{r.d_idx, h->pair_i, h->pair_j, h->pair_table, h->table, x0, r.w.qrow, r.w.srow,
-                    r.B, r.N, r.P, r.Lloc, h->bad_idx_dev};
+                    r.B, r.N, r.P, r.Lloc, h->bad_idx_dev, r.d_w};
         const int ntasks = r.B * r.P, wpb = EMBED_THREADS / 64;
         const int grid = std::max(1, std::min(h->prop.multiProcessorCount, (ntasks + wpb - 1) / wpb));
         ProfScope ps(h, K_EMBED);
-        hipLaunchKernelGGL(k_embed, dim3(grid), dim3(EMBED_THREADS), EMBED_LDS_BYTES, h->cur, e);
+        if (r.d_w) hipLaunchKernelGGL(k_embed<true>, dim3(grid), dim3(EMBED_THREADS), EMBED_LDS_BYTES, h->cur, e);
+        else hipLaunchKernelGGL(k_embed<false>, dim3(grid), dim3(EMBED_THREADS), EMBED_LDS_BYTES, h->cur, e);
         HIPCHK(h, hipGetLastError());
     }
     if (h->debug_keep) return save_tap(h, "x0", r.w.x, (size_t)r.B * r.P * r.Lloc * 64);
@@ -699,7 +713,7 @@ int launch_outsum(pf_handle* h, const ShardRun& r) {
     ProfScope ps(h, K_ROWFIN);
     const TilePlan& tp = r.tp;
     hipLaunchKernelGGL(k_outsum, dim3((n + 255) / 256), dim3(256), 0, h->cur, r.w.outpart, r.d_out, n,
-                       tiles_of(r.Lloc), 1.0f / (float)r.L_total, tp.flat, r.P, r.Lloc, tp.slots_aln);
+                       tiles_of(r.Lloc), 1.0f / (float)r.L_total, tp.flat, r.P, r.Lloc, tp.slots_aln, r.d_wst);
     HIPCHK(h, hipGetLastError());
     return PF_OK;
 }
@@ -738,6 +752,7 @@ int phase_block(pf_handle* h, const ShardRun& r, int k, RowStats rs) {
         a.b_scale = 1.f;
         for (long lim = 16384; lim < (long)r.L_total && a.b_scale > 1.f / 256.f; lim *= 2) a.b_scale *= 0.5f;
         a.a_scale = 1.f / a.b_scale;
+        a.wst = r.d_wst;                  // weighted: W and the scales per alignment (k_weight_sums) instead
         ProfScope ps(h, K_ROWFIN);
         hipLaunchKernelGGL(k_rowfin, dim3((groups + a.iters - 1) / a.iters), dim3(256), 0, h->cur, a);
         HIPCHK(h, hipGetLastError());
@@ -770,17 +785,20 @@ int phase_block(pf_handle* h, const ShardRun& r, int k, RowStats rs) {
     m.consts = d.consts;
     if (k + 1 < h->n_blocks) {
         m.wv_lo = reinterpret_cast<const frag_t*>(h->blk[k + 1].wv_lo);
-        if (k == 0 && x0_on_the_fly(h)) rc = launch_main<MODE_MID0>(h, m, K_MAIN);
-        else rc = launch_main<MODE_MID>(h, m, K_MAIN);
+        const bool first = k == 0 && x0_on_the_fly(h);
+        if (r.d_w) rc = first ? launch_main<MODE_MID0, false, true>(h, m, K_MAIN) : launch_main<MODE_MID, false, true>(h, m, K_MAIN);
+        else rc = first ? launch_main<MODE_MID0>(h, m, K_MAIN) : launch_main<MODE_MID>(h, m, K_MAIN);
         if (rc) return rc;
     } else {
         m.wv_lo = nullptr;
         if (h->phase_prof_last) m.prof = h->phase_prof;
         m.sitemap = r.d_smap;
         if (!h->head_fold) {
-            if ((rc = r.d_smap ? launch_main<MODE_LAST, true>(h, m, K_MAIN) : launch_main<MODE_LAST>(h, m, K_MAIN))) return rc;
+            if ((rc = r.d_w      ? launch_main<MODE_LAST, false, true>(h, m, K_MAIN)
+                      : r.d_smap ? launch_main<MODE_LAST, true>(h, m, K_MAIN) : launch_main<MODE_LAST>(h, m, K_MAIN))) return rc;
         } else {
-            if ((rc = r.d_smap ? launch_main<MODE_LAST_FOLD, true>(h, m, K_MAIN) : launch_main<MODE_LAST_FOLD>(h, m, K_MAIN)))
+            if ((rc = r.d_w      ? launch_main<MODE_LAST_FOLD, false, true>(h, m, K_MAIN)
+                      : r.d_smap ? launch_main<MODE_LAST_FOLD, true>(h, m, K_MAIN) : launch_main<MODE_LAST_FOLD>(h, m, K_MAIN)))
                 return rc;
             if (h->debug_keep) {
                 // the folded head never forms x6: the full FFN writes it for the tap (in place, after the folded
@@ -788,7 +806,7 @@ int phase_block(pf_handle* h, const ShardRun& r, int k, RowStats rs) {
                 MainArgs md = m;
                 md.outpart = w.spart;
                 md.prof = nullptr;
-                if ((rc = launch_main<MODE_LAST>(h, md, K_MAIN))) return rc;
+                if ((rc = r.d_w ? launch_main<MODE_LAST, false, true>(h, md, K_MAIN) : launch_main<MODE_LAST>(h, md, K_MAIN))) return rc;
             }
         }
     }
@@ -863,8 +881,9 @@ int schedule(pf_handle* h, ShardRun* runs, size_t nruns, Reduce reduce) {
 // kernel tail, a small kernel or a launch gap leaves its CUs to the other.  An empty rank (Lloc = 0) cuts and
 // reduces exactly as its peers do.
 // d_smap (site-map entry points, unsharded): the chunk's [B][P][Lloc] map of head terms, written by the last block.
+// d_w, d_wst (weighted forwards, unsharded): the chunk's weight rows [B][Lloc] and their sums [B][4].
 int forward_chunk(pf_handle* h, const uint8_t* d_idx, int B, int N, int Lloc, int L_total, float* d_out,
-                  float* d_smap = nullptr) {
+                  float* d_smap = nullptr, const float* d_w = nullptr, const float* d_wst = nullptr) {
     const int P = N * (N - 1) / 2;
     const bool reduces = reduces_now(h);
     const int nh = halves_of(h, B);
@@ -877,6 +896,7 @@ int forward_chunk(pf_handle* h, const uint8_t* d_idx, int B, int N, int Lloc, in
         r[i] = ShardRun{{}, d_idx + (size_t)b0 * N * Lloc, d_out + (size_t)b0 * P, nb, N, P, Lloc, L_total,
                         tile_plan(h, P, Lloc), h->stream, {}};
         if (d_smap) r[i].d_smap = d_smap + (size_t)b0 * P * Lloc;
+        if (d_w) { r[i].d_w = d_w + (size_t)b0 * Lloc; r[i].d_wst = d_wst + (size_t)b0 * pfw::WST; }
         if ((rc = ensure_workspace(h, nb, P, Lloc, &r[i].w, i == 1))) return rc;
         b0 += nb;
     }
@@ -1018,8 +1038,58 @@ int chunk_batch(pf_handle* h, int B, int P, int Lloc, size_t extra = 0) {
     return lo;
 }
 
+// grow-only device buffer
+template <class T>
+int ensure_buffer(pf_handle* h, T** p, size_t* have, size_t bytes) {
+    if (*p && bytes <= *have) return PF_OK;
+    if (*p) hipFree(*p);
+    *p = nullptr; *have = 0;
+    HIPCHK(h, hipMalloc((void**)p, bytes ? bytes : 1));
+    *have = bytes;
+    return PF_OK;
+}
+
+// ---- site weights (pf_forward_weighted*, pf_forward_sites_weighted, pf_bootstrap_weighted) ------
+// What k_weight_sums makes of the weight rows d_w [B][L] of a call, into the grow-only h->d_wst: asynchronous on
+// h->stream, behind whatever read the buffer before.
+int launch_weight_sums(pf_handle* h, const float* d_w, int B, int L, const float** d_wst) {
+    int rc = ensure_buffer(h, &h->d_wst, &h->d_wst_bytes, (size_t)B * pfw::WST * sizeof(float));
+    if (rc) return rc;
+    h->cur = h->stream;
+    ProfScope ps(h, K_WEIGHT_SUMS);
+    const hipError_t e = pfw::launch_weight_sums(h->stream, d_w, h->d_wst, B, L, h->bad_idx_dev + 2);
+    if (e != hipSuccess) return fail(h, PF_EHIP, "k_weight_sums launch failed: %s", hipGetErrorString(e));
+    *d_wst = h->d_wst;
+    return PF_OK;
+}
+
+// What the weighted entry points refuse beside their unweighted twins, before any device work: a handle whose
+// communicator has more than one rank (W and the weighted sums are not site-sharded) and the MFMA cross-check embedding.
+int check_weighted_handle(pf_handle* h) {
+    if (h->world > 1)
+        return fail(h, PF_ESTATE, "weighted forwards are not site-sharded: this handle's communicator has %d ranks (use a "
+                                  "handle without a communicator)", h->world);
+    if (h->embed_mfma) return fail(h, PF_ESTATE, "option embed_mfma has no weighted kernel (set it to 0 for weighted forwards)");
+    return PF_OK;
+}
+
+// host weights w [rows][K]: every one finite and >= 0, every row's sum W > 0 (and finite); `what` names a row
+int check_weights(pf_handle* h, const float* w, size_t rows, int K, const char* what) {
+    const int64_t at = pfweights::first_bad_weight(w, rows * (size_t)K);
+    if (at >= 0)
+        return fail(h, PF_EINVAL, "weight %g of %s %lld, position %lld is negative or not finite", (double)w[at], what,
+                    (long long)(at / K), (long long)(at % K));
+    for (size_t r = 0; r < rows; ++r) {
+        const float W = pfweights::weight_sum(w + r * (size_t)K, K);
+        if (!(W > 0.f && W <= 3.402823466e38f))
+            return fail(h, PF_EINVAL, "the weights of %s %zu sum to %g: W must be positive and finite", what, r, (double)W);
+    }
+    return PF_OK;
+}
+
+// d_w (weighted forwards, unsharded): site weights [B][Lloc] on the device, or null.
 int forward_device_impl(pf_handle* h, const uint8_t* d_idx, int B, int N, int l_begin, int l_end,
-                        int L_total, float* d_out) {
+                        int L_total, float* d_out, const float* d_w = nullptr) {
     const int Lloc = l_end - l_begin;
     if (h && h->sharded_call && Lloc < L_total && !h->comm[0])
         // a partial site range without a communicator would return partial sums divided by L_total
@@ -1029,7 +1099,10 @@ int forward_device_impl(pf_handle* h, const uint8_t* d_idx, int B, int N, int l_
     if (rc) return rc;
     if (l_begin < 0 || l_end > L_total) return fail(h, PF_EINVAL, "site range [%d, %d) outside [0, %d)", l_begin, l_end, L_total);
     HIPCHK(h, hipSetDevice(h->device));
-    if (const F64Path* f = f64_path_of(h, N, L_total)) return forward_device_f64(h, *f, d_idx, B, N, l_begin, l_end, L_total, d_out);
+    const float* d_wst = nullptr;
+    if (d_w && (rc = launch_weight_sums(h, d_w, B, Lloc, &d_wst))) return rc;
+    if (const F64Path* f = f64_path_of(h, N, L_total))
+        return forward_device_f64(h, *f, d_idx, B, N, l_begin, l_end, L_total, d_out, d_w, d_wst);
     const int P = N * (N - 1) / 2;
     // every rank must cut the batch into the same chunks (one all-reduce sequence per chunk), so the
     // chunk size is derived from the largest shard, not from this rank's own (an empty rank has none)
@@ -1038,7 +1111,8 @@ int forward_device_impl(pf_handle* h, const uint8_t* d_idx, int B, int N, int l_
     if ((rc = make_room(h, false, chunk_bytes(h, cb, P, Lmax)))) return rc;
     for (int b0 = 0; b0 < B; b0 += cb) {
         const int nbch = std::min(cb, B - b0);
-        rc = forward_chunk(h, d_idx + (size_t)b0 * N * Lloc, nbch, N, Lloc, L_total, d_out + (size_t)b0 * P);
+        rc = forward_chunk(h, d_idx + (size_t)b0 * N * Lloc, nbch, N, Lloc, L_total, d_out + (size_t)b0 * P, nullptr,
+                           d_w ? d_w + (size_t)b0 * Lloc : nullptr, d_wst ? d_wst + (size_t)b0 * pfw::WST : nullptr);
         if (rc) return rc;
     }
     return PF_OK;
@@ -1053,6 +1127,12 @@ int check_bad_idx(pf_handle* h) {
         return fail(h, PF_EINVAL, "a site map passed to pf_gather_sites_device, or a taxon table passed to "
                                   "pf_gather_taxa_device, held an entry outside the source alignment (read as site / row 0; "
                                   "the bytes gathered since the last synchronisation are not those of the map)");
+    }
+    if (h->bad_idx_host[2]) {
+        h->bad_idx_host[2] = 0u;
+        return fail(h, PF_EINVAL, "weights passed to pf_forward_weighted_device held a negative or non-finite entry, or an "
+                                  "alignment's weights summed to 0 (results of the weighted forwards since the last "
+                                  "synchronisation are not valid)");
     }
     if (!*h->bad_idx_host) return PF_OK;
     *h->bad_idx_host = 0u;
@@ -1070,17 +1150,6 @@ int check_residues(pf_handle* h, const uint8_t* idx, size_t nidx) {
     if (bad)
         for (size_t i = 0; i < nidx; ++i)
             if (idx[i] >= NA) return fail(h, PF_EINVAL, "residue index %d at offset %zu is outside 0..21", (int)idx[i], i);
-    return PF_OK;
-}
-
-// grow-only device buffer
-template <class T>
-int ensure_buffer(pf_handle* h, T** p, size_t* have, size_t bytes) {
-    if (*p && bytes <= *have) return PF_OK;
-    if (*p) hipFree(*p);
-    *p = nullptr; *have = 0;
-    HIPCHK(h, hipMalloc((void**)p, bytes ? bytes : 1));
-    *have = bytes;
     return PF_OK;
 }
 
@@ -1130,35 +1199,58 @@ int range_recheck(pf_handle* h, float* out, int count, int N, int l_begin, int l
     });
 }
 
+// weighted (pf_forward_weighted): w float [B][Lloc] rides along - checked, uploaded into the grow-only h->d_w, and
+// staged again with the bytes of an alignment the range re-check sends to the float64 kernels.
 int forward_host_impl(pf_handle* h, const uint8_t* idx, int B, int N, int l_begin, int l_end,
-                      int L_total, float* out) {
+                      int L_total, float* out, const float* w = nullptr, bool weighted = false) {
     const int Lloc = l_end - l_begin;
     int rc = check_dims(h, B, N, Lloc, L_total);
     if (rc) return rc;
     if (!out || (!idx && Lloc > 0)) return fail(h, PF_EINVAL, "null buffer");
     const size_t nidx = (size_t)B * N * Lloc;
     if ((rc = check_residues(h, idx, nidx))) return rc;
+    if (weighted) {
+        if (!w) return fail(h, PF_EINVAL, "null buffer");
+        if ((rc = check_weights(h, w, (size_t)B, Lloc, "alignment"))) return rc;
+        if ((rc = check_weighted_handle(h))) return rc;
+    }
     HIPCHK(h, hipSetDevice(h->device));
+    const size_t nw = (size_t)B * Lloc * sizeof(float);
+    if (weighted) {
+        if ((rc = ensure_buffer(h, &h->d_w, &h->d_w_bytes, nw))) return rc;
+        HIPCHK(h, hipMemcpyAsync(h->d_w, w, nw, hipMemcpyHostToDevice, h->stream));
+    }
     const int P = N * (N - 1) / 2;
     if ((rc = ensure_buffer(h, &h->d_idx, &h->d_idx_bytes, nidx))) return rc;
     const size_t nout = (size_t)B * P * sizeof(float);
     if ((rc = ensure_buffer(h, &h->d_out, &h->d_out_bytes, nout))) return rc;
     if (nidx) HIPCHK(h, hipMemcpyAsync(h->d_idx, idx, nidx, hipMemcpyHostToDevice, h->stream));
     const bool default_kernels = !f64_path_of(h, N, L_total);
-    rc = forward_device_impl(h, h->d_idx, B, N, l_begin, l_end, L_total, h->d_out);
+    rc = forward_device_impl(h, h->d_idx, B, N, l_begin, l_end, L_total, h->d_out, weighted ? h->d_w : nullptr);
     if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(out, h->d_out, nout, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (!default_kernels) return PF_OK;
     std::vector<uint8_t> sub;
+    std::vector<float> wsub;
     const size_t per = (size_t)N * Lloc;
-    return range_recheck(h, out, B, N, l_begin, l_end, L_total, h->d_idx, (size_t)B,
-                         [&](const int* list, size_t k, uint8_t* d_buf) -> int {
-        try { sub.resize(k * per); }
+    auto stage = [&](const int* list, size_t k, uint8_t* d_buf) -> int {
+        try { sub.resize(k * per); if (weighted) wsub.resize(k * (size_t)Lloc); }
         catch (const std::bad_alloc&) { return fail(h, PF_ENOMEM, "out of host memory in the range re-check"); }
         for (size_t i = 0; i < k; ++i) std::memcpy(&sub[i * per], idx + (size_t)list[i] * per, per);
         HIPCHK(h, hipMemcpyAsync(d_buf, sub.data(), k * per, hipMemcpyHostToDevice, h->stream));
+        if (weighted) {          // the flagged alignments' weight rows, in the same order (everything else is on the host by now)
+            for (size_t i = 0; i < k; ++i) std::memcpy(&wsub[i * Lloc], w + (size_t)list[i] * Lloc, (size_t)Lloc * sizeof(float));
+            HIPCHK(h, hipMemcpyAsync(h->d_w, wsub.data(), k * (size_t)Lloc * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        }
         return PF_OK;
+    };
+    if (!weighted) return range_recheck(h, out, B, N, l_begin, l_end, L_total, h->d_idx, (size_t)B, stage);
+    return range_recheck(h, out, B, N, l_begin, l_end, L_total, h->d_idx, (size_t)B, stage, [&](const uint8_t* d_idx, const int*, size_t k) -> int {
+        const float* d_wst = nullptr;
+        const int rc2 = launch_weight_sums(h, h->d_w, (int)k, Lloc, &d_wst);
+        if (rc2) return rc2;
+        return forward_device_f64(h, PRECISE_F64, d_idx, (int)k, N, l_begin, l_end, L_total, h->d_out, h->d_w, d_wst);
     });
 }
 
@@ -1198,9 +1290,13 @@ int launch_gather(pf_handle* h, const uint8_t* d_src, int B, int N, int L, const
 // then reads them there.  A derived alignment's distances are those of pf_forward on its host-built bytes, bit for bit:
 // the forward is batch invariant and routes on (Nd, K) alone.  The caller has checked its own arguments; what
 // pf_forward checks is checked here, before any device work.  `what` names the derived alignments in messages.
-template <class Fill>
+// Weighted derived alignments (pf_forward_sites_weighted): wfill(nb, j0, nj, d_wdst) writes the same rectangle's weight
+// rows float [nb][nj][K] into d_wdst on h->stream - a chunk's live in the grow-only h->d_w - and the forward is the
+// weighted one; without wfill nothing changes.
+template <class Fill, class WFill = std::nullptr_t>
 int forward_derived(pf_handle* h, const uint8_t* idx, int B, int N, int L, int S, int Nd, int K, float* out, const char* what,
-                    Fill&& fill) {
+                    Fill&& fill, WFill&& wfill = nullptr) {
+    constexpr bool weighted = !std::is_same<typename std::decay<WFill>::type, std::nullptr_t>::value;
     if (!out || !idx) return fail(h, PF_EINVAL, "null buffer");
     const int P = Nd * (Nd - 1) / 2;
     size_t nout = 0, nrep = 0;
@@ -1220,24 +1316,35 @@ int forward_derived(pf_handle* h, const uint8_t* idx, int B, int N, int L, int S
     const int jpc = spc ? S : cb;                          // derived alignments of one source per chunk
     const size_t cap = spc ? (size_t)spc * S : (size_t)jpc;
     if ((rc = ensure_buffer(h, &h->d_rep, &h->d_rep_bytes, cap * per))) return rc;
+    if (weighted && (rc = ensure_buffer(h, &h->d_w, &h->d_w_bytes, cap * (size_t)K * sizeof(float)))) return rc;
     for (int b0 = 0; b0 < B; b0 += std::max(spc, 1))
         for (int j0 = 0; j0 < S; j0 += jpc) {
             const int nb = spc ? std::min(spc, B - b0) : 1, nj = std::min(jpc, S - j0);
             if ((rc = fill(h->d_idx + (size_t)b0 * per_src, nb, j0, nj, h->d_rep))) return rc;
-            rc = forward_device_impl(h, h->d_rep, nb * nj, Nd, 0, K, K, h->d_out + ((size_t)b0 * S + j0) * P);
+            if constexpr (weighted) { if ((rc = wfill(nb, j0, nj, h->d_w))) return rc; }
+            rc = forward_device_impl(h, h->d_rep, nb * nj, Nd, 0, K, K, h->d_out + ((size_t)b0 * S + j0) * P,
+                                     weighted ? h->d_w : nullptr);
             if (rc) return rc;
         }
     HIPCHK(h, hipMemcpyAsync(out, h->d_out, nout, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (f) return PF_OK;
-    // a flagged derived alignment is rebuilt from the resident source bytes
-    return range_recheck(h, out, B * S, Nd, 0, K, K, h->d_rep, cap, [&](const int* list, size_t k, uint8_t* d_buf) -> int {
+    // a flagged derived alignment is rebuilt from the resident source bytes (and its weight row with it)
+    auto stage = [&](const int* list, size_t k, uint8_t* d_buf) -> int {
         for (size_t i = 0; i < k; ++i) {
             const int b = list[i] / S, j = list[i] % S;
-            const int rc2 = fill(h->d_idx + (size_t)b * per_src, 1, j, 1, d_buf + i * per);
+            int rc2 = fill(h->d_idx + (size_t)b * per_src, 1, j, 1, d_buf + i * per);
             if (rc2) return rc2;
+            if constexpr (weighted) { if ((rc2 = wfill(1, j, 1, h->d_w + i * (size_t)K))) return rc2; }
         }
         return PF_OK;
+    };
+    if constexpr (!weighted) return range_recheck(h, out, B * S, Nd, 0, K, K, h->d_rep, cap, stage);
+    return range_recheck(h, out, B * S, Nd, 0, K, K, h->d_rep, cap, stage, [&](const uint8_t* d_buf, const int*, size_t k) -> int {
+        const float* d_wst = nullptr;
+        const int rc2 = launch_weight_sums(h, h->d_w, (int)k, K, &d_wst);
+        if (rc2) return rc2;
+        return forward_device_f64(h, PRECISE_F64, d_buf, (int)k, Nd, 0, K, K, h->d_out, h->d_w, d_wst);
     });
 }
 
@@ -1255,7 +1362,10 @@ int bootstrap_impl(pf_handle* h, const uint8_t* idx, int B, int N, int L, int R,
 // sites [S][K], or (sites == nullptr) the S windows of K sites, `step` apart, of the window rule - uploaded once into
 // the grow-only h->d_map.  Sizes are checked before the map is read or built: a caller's S is not trusted further than
 // its own table.
-int sites_impl(pf_handle* h, const uint8_t* idx, int B, int N, int L, const int32_t* sites, int step, int S, int K, float* out) {
+// weighted (pf_forward_sites_weighted): w float [S][K], one weight per table entry, uploaded once into the grow-only
+// h->d_wtab; a chunk's weight rows are device-to-device copies of its sets' rows.
+int sites_impl(pf_handle* h, const uint8_t* idx, int B, int N, int L, const int32_t* sites, int step, int S, int K, float* out,
+               const float* w = nullptr, bool weighted = false) {
     int rc = check_dims(h, B, N, L, L);
     if (rc) return rc;
     if (S < 1) return fail(h, PF_EINVAL, "a site map needs S >= 1 sets (got %d)", S);
@@ -1278,17 +1388,71 @@ int sites_impl(pf_handle* h, const uint8_t* idx, int B, int N, int L, const int3
         for (int s = 0; s < S; ++s) start[s] = pfsites::window_start(L, K, step, s);
     }
     const int32_t* map = sites ? sites : start.data();
+    size_t nwt = 0;
+    if (weighted) {
+        if (!w) return fail(h, PF_EINVAL, "null buffer");
+        if (!mul_size((size_t)S, (size_t)K, sizeof(float), &nwt))
+            return fail(h, PF_EINVAL, "B=%d x S=%d site sets of %d x %d overflow the address space", B, S, N, K);
+        if ((rc = check_weights(h, w, (size_t)S, K, "set"))) return rc;
+        if ((rc = check_weighted_handle(h))) return rc;
+    }
     // (what is left - the residues - is refused by forward_derived before its first device call)
     bool uploaded = false;
-    return forward_derived(h, idx, B, N, L, S, N, K, out, "site sets", [&](const uint8_t* d_src, int nb, int j0, int nj, uint8_t* d_dst) -> int {
+    auto fill = [&](const uint8_t* d_src, int nb, int j0, int nj, uint8_t* d_dst) -> int {
         if (!uploaded) {
-            const int rc2 = ensure_buffer(h, &h->d_map, &h->d_map_bytes, nmap);
+            int rc2 = ensure_buffer(h, &h->d_map, &h->d_map_bytes, nmap);
             if (rc2) return rc2;
             HIPCHK(h, hipMemcpyAsync(h->d_map, map, nmap, hipMemcpyHostToDevice, h->stream));
+            if (weighted) {
+                if ((rc2 = ensure_buffer(h, &h->d_wtab, &h->d_wtab_bytes, nwt))) return rc2;
+                HIPCHK(h, hipMemcpyAsync(h->d_wtab, w, nwt, hipMemcpyHostToDevice, h->stream));
+            }
             uploaded = true;
         }
         return launch_gather(h, d_src, nb, N, L, sites ? h->d_map : nullptr, sites ? nullptr : h->d_map, j0, nj, K, d_dst);
+    };
+    if (!weighted) return forward_derived(h, idx, B, N, L, S, N, K, out, "site sets", fill);
+    // every source of the rectangle takes the same rows j0 .. j0 + nj - 1 of the table (fill ran first: it is uploaded)
+    return forward_derived(h, idx, B, N, L, S, N, K, out, "site sets", fill, [&](int nb, int j0, int nj, float* d_wdst) -> int {
+        for (int b = 0; b < nb; ++b)
+            HIPCHK(h, hipMemcpyAsync(d_wdst + (size_t)b * nj * K, h->d_wtab + (size_t)j0 * K, (size_t)nj * K * sizeof(float),
+                                     hipMemcpyDeviceToDevice, h->stream));
+        return PF_OK;
     });
+}
+
+// pf_bootstrap_weighted: replicate r of pf_bootstrap's stream as the table of its distinct sites and their counts
+// (pfweights::boot_counts), every replicate padded with (site 0, weight 0) to K = padded_sites(max_r distinct_r, L);
+// built on the host (R x L draws), forwarded by pf_forward_sites_weighted's path, which routes on (N, K).
+int bootstrap_weighted_impl(pf_handle* h, const uint8_t* idx, int B, int N, int L, int R, uint64_t seed, float* out) {
+    int rc = check_dims(h, B, N, L, L);
+    if (rc) return rc;
+    if (R < 1) return fail(h, PF_EINVAL, "bootstrap needs R >= 1 replicates (got %d)", R);
+    if (!out || !idx) return fail(h, PF_EINVAL, "null buffer");
+    size_t n = 0;
+    if (!mul_size((size_t)R, (size_t)L, sizeof(int32_t) * 2, &n))
+        return fail(h, PF_EINVAL, "B=%d x R=%d replicates of %d x %d overflow the address space", B, R, N, L);
+    std::vector<int32_t> all_sites, all_counts, tab;
+    std::vector<int> distinct;
+    std::vector<float> wt;
+    int K = 0;
+    try {
+        all_sites.resize((size_t)R * L); all_counts.resize((size_t)R * L); distinct.resize((size_t)R);
+        int kmax = 1;
+        for (int r = 0; r < R; ++r) {
+            distinct[r] = pfweights::boot_counts(L, seed, r, &all_sites[(size_t)r * L], &all_counts[(size_t)r * L]);
+            kmax = std::max(kmax, distinct[r]);
+        }
+        K = pfweights::padded_sites(kmax, L);
+        tab.assign((size_t)R * K, 0);
+        wt.assign((size_t)R * K, 0.f);
+        for (int r = 0; r < R; ++r)
+            for (int k = 0; k < distinct[r]; ++k) {
+                tab[(size_t)r * K + k] = all_sites[(size_t)r * L + k];
+                wt[(size_t)r * K + k] = (float)all_counts[(size_t)r * L + k];
+            }
+    } catch (const std::bad_alloc&) { return fail(h, PF_ENOMEM, "out of host memory for the tables of %d replicates", R); }
+    return sites_impl(h, idx, B, N, L, tab.data(), 0, R, K, out, wt.data(), true);
 }
 
 // ---- site-resolved distances (pf_forward_site_map*, pf_forward_site_profile, pf_site_moments_device) ----------------
@@ -1580,12 +1744,12 @@ static int open_device(int device, pf_handle** out) {
         }
         if ((e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess) { rc = fail(nullptr, PF_EHIP, "hipStreamCreate: %s", hipGetErrorString(e)); break; }
         h->cur = h->stream;
-        if ((e = hipHostMalloc((void**)&h->bad_idx_host, 2 * sizeof(unsigned), hipHostMallocMapped | hipHostMallocCoherent)) != hipSuccess ||
+        if ((e = hipHostMalloc((void**)&h->bad_idx_host, 3 * sizeof(unsigned), hipHostMallocMapped | hipHostMallocCoherent)) != hipSuccess ||
             (e = hipHostGetDevicePointer((void**)&h->bad_idx_dev, h->bad_idx_host, 0)) != hipSuccess) {
             rc = fail(nullptr, PF_EHIP, "hipHostMalloc (residue flag): %s", hipGetErrorString(e));
             break;
         }
-        h->bad_idx_host[0] = h->bad_idx_host[1] = 0u;
+        h->bad_idx_host[0] = h->bad_idx_host[1] = h->bad_idx_host[2] = 0u;
         // Kernels that need more than the default 64 KB of dynamic LDS: the attribute is set here, once per
         // handle and before any launch, so that no launch path carries mutable state shared between handles
         // (the CLI drives two engines per GPU from two host threads).
@@ -1604,7 +1768,16 @@ static int open_device(int device, pf_handle** out) {
             {reinterpret_cast<const void*>(&k_main<MODE_LAST_FOLD, false, true>), MAIN_LDS_BYTES},
             {reinterpret_cast<const void*>(&k_main<MODE_LAST, true, true>), MAIN_LDS_BYTES},
             {reinterpret_cast<const void*>(&k_main<MODE_LAST_FOLD, true, true>), MAIN_LDS_BYTES},
-            {reinterpret_cast<const void*>(&k_embed), EMBED_LDS_BYTES},
+            {reinterpret_cast<const void*>(&k_main<MODE_MID, false, false, true>), MAIN_LDS_BYTES},
+            {reinterpret_cast<const void*>(&k_main<MODE_MID0, false, false, true>), MAIN_LDS_BYTES},
+            {reinterpret_cast<const void*>(&k_main<MODE_LAST, false, false, true>), MAIN_LDS_BYTES},
+            {reinterpret_cast<const void*>(&k_main<MODE_LAST_FOLD, false, false, true>), MAIN_LDS_BYTES},
+            {reinterpret_cast<const void*>(&k_main<MODE_MID, true, false, true>), MAIN_LDS_BYTES},
+            {reinterpret_cast<const void*>(&k_main<MODE_MID0, true, false, true>), MAIN_LDS_BYTES},
+            {reinterpret_cast<const void*>(&k_main<MODE_LAST, true, false, true>), MAIN_LDS_BYTES},
+            {reinterpret_cast<const void*>(&k_main<MODE_LAST_FOLD, true, false, true>), MAIN_LDS_BYTES},
+            {reinterpret_cast<const void*>(&k_embed<false>), EMBED_LDS_BYTES},
+            {reinterpret_cast<const void*>(&k_embed<true>), EMBED_LDS_BYTES},
         };
         for (const auto& k : big_lds)
             if ((e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.bytes)) != hipSuccess) {
@@ -1687,6 +1860,9 @@ int pf_destroy(pf_handle_t* h) {
     if (h->d_se) hipFree(h->d_se);
     if (h->d_prof) hipFree(h->d_prof);
     if (h->d_loo) hipFree(h->d_loo);
+    if (h->d_w) hipFree(h->d_w);
+    if (h->d_wst) hipFree(h->d_wst);
+    if (h->d_wtab) hipFree(h->d_wtab);
     if (h->stream) hipStreamDestroy(h->stream);
     if (h->bad_idx_host) hipHostFree(h->bad_idx_host);
     delete h;
@@ -1838,6 +2014,52 @@ int pf_loo_stats_device(pf_handle_t* h, const float* d_full, const float* d_loo,
 int pf_forward_device(pf_handle_t* h, const uint8_t* d_idx, int32_t B, int32_t N, int32_t L, float* d_out) {
     if (!h) return PF_EINVAL;
     return forward_device_impl(h, d_idx, B, N, 0, L, L, d_out);
+}
+
+int pf_forward_weighted(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, int32_t L, const float* w, float* out) {
+    if (!h) return PF_EINVAL;
+    return forward_host_impl(h, idx, B, N, 0, L, L, out, w, true);
+}
+
+int pf_forward_weighted_device(pf_handle_t* h, const uint8_t* d_idx, int32_t B, int32_t N, int32_t L, const float* d_w,
+                               float* d_out) {
+    if (!h) return PF_EINVAL;
+    int rc = check_dims(h, B, N, L, L);
+    if (rc) return rc;
+    if (!d_idx || !d_w || !d_out) return fail(h, PF_EINVAL, "null buffer");
+    if ((rc = check_weighted_handle(h))) return rc;
+    return forward_device_impl(h, d_idx, B, N, 0, L, L, d_out, d_w);
+}
+
+int pf_forward_sites_weighted(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, int32_t L, const int32_t* sites,
+                              const float* w, int32_t S, int32_t K, float* out) {
+    if (!h) return PF_EINVAL;
+    if (!sites) return fail(h, PF_EINVAL, "null buffer");
+    return sites_impl(h, idx, B, N, L, sites, 0, S, K, out, w, true);
+}
+
+int pf_bootstrap_weighted(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, int32_t L, int32_t R, uint64_t seed,
+                          float* out) {
+    if (!h) return PF_EINVAL;
+    return bootstrap_weighted_impl(h, idx, B, N, L, R, seed, out);
+}
+
+int pf_padded_sites(int32_t K, int32_t L) {
+    const int n = pfweights::padded_sites(K, L);
+    return n < 0 ? PF_EINVAL : n;
+}
+
+int pf_boot_counts(int32_t L, int32_t R, uint64_t seed, int32_t r, int32_t* sites, int32_t* counts) {
+    if (L < 1 || R < 1 || r < 0 || r >= R || !sites || !counts) return PF_EINVAL;
+    return pfweights::boot_counts(L, seed, r, sites, counts);
+}
+
+int pf_compress_sites(const uint8_t* idx, int32_t N, int32_t L, int32_t* first, int32_t* count) {
+    if (N < 1 || L < 1 || !idx || !first || !count) return PF_EINVAL;
+    std::vector<int32_t> slot;
+    try { slot.resize(pfweights::compress_slots(L)); }
+    catch (const std::bad_alloc&) { return PF_ENOMEM; }
+    return pfweights::compress_sites(idx, N, L, first, count, slot.data());
 }
 
 int pf_forward_site_map(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, int32_t L, float* out, float* map) {

@@ -34,8 +34,11 @@ __global__ void __launch_bounds__(PT) kp_attn_stats(StatsArgs a) {
     __syncthreads();
     double skv = 0.0, s8 = 0.0;           // lane c: S_kv[c];  lanes 0..7: S_q[0..3], S_k[0..3]
     const int e_end = min(nelem, (ch + 1) * CHUNK);
+    // weighted forwards, row attention: site e counts wt times (times 1.0 - exactly - everywhere else)
+    const float* wrow = (a.wt && !a.col) ? a.wt + (size_t)(line / a.P) * a.L : nullptr;
     for (int e = ch * CHUNK + w; e < e_end; e += 4) {
         const size_t tok = token_of(a.col, line, e, a.P, a.L);
+        const double wt = wrow ? (double)wrow[e] : 1.0;
         const double xn = layer_norm(a.x[tok * E + lane], g, beta);
         double qk = 0.0;                  // lane m < 8 ends up with elu(.)+1 of projection m
 #pragma unroll
@@ -49,8 +52,8 @@ __global__ void __launch_bounds__(PT) kp_attn_stats(StatsArgs a) {
         for (int k = 0; k < E; ++k) v = fma(wv[k * E + lane], bcast(xn, k), v);
         const double k0 = bcast(qk, 4), k1 = bcast(qk, 5), k2 = bcast(qk, 6), k3 = bcast(qk, 7);
         const double kh = (lane >> 4) == 0 ? k0 : (lane >> 4) == 1 ? k1 : (lane >> 4) == 2 ? k2 : k3;
-        skv += kh * v;                    // attention.py:187-188: sum of k'[h] * v[h, d], channel h * 16 + d
-        if (lane < 8) s8 += qk;
+        skv += (kh * wt) * v;             // attention.py:187-188: sum of k'[h] * v[h, d], channel h * 16 + d
+        if (lane < 8) s8 += qk * wt;
         if (lane < 4) a.q[tok * 4 + lane] = qk;
     }
     red[w][lane] = skv;
@@ -78,9 +81,12 @@ __global__ void __launch_bounds__(PT) kp_attn_stats_mfma(StatsArgs a) {
     for (int T = 0; T < 4; ++T) skv[T] = d4{0.0, 0.0, 0.0, 0.0};
     double sq = 0.0, sk = 0.0;
     const int e_end = min(nelem, (ch + 1) * CHUNK_MFMA);
+    // weighted forwards, row attention: site e counts wt times (times 1.0 - exactly - everywhere else)
+    const float* wrow = (a.wt && !a.col) ? a.wt + (size_t)(line / a.P) * a.L : nullptr;
     for (int e0 = ch * CHUNK_MFMA + 16 * w; e0 < e_end; e0 += 64) {
         const int e = e0 + j;
         const bool valid = e < e_end;
+        const double wt = (wrow && valid) ? (double)wrow[e] : 1.0;
         const size_t tok = token_of(a.col, line, valid ? e : e0, a.P, a.L);
         double xn[16];
         {
@@ -103,8 +109,9 @@ __global__ void __launch_bounds__(PT) kp_attn_stats_mfma(StatsArgs a) {
             for (int s = 0; s < 16; ++s) qk = __builtin_amdgcn_mfma_f64_16x16x4f64(a4[s * 64], xn[s], qk, 0, 0, 0);
         }
         const double qp = valid ? elu1(qk[0]) : 0.0, kp = valid ? elu1(qk[1]) : 0.0;     // q'[g], k'[g] of element j
-        sq += qp;
-        sk += kp;
+        const double kpw = kp * wt;
+        sq += qp * wt;
+        sk += kpw;
         if (valid) a.q[tok * 4 + g] = qp;
 #pragma unroll
         for (int T = 0; T < 4; ++T) {
@@ -114,7 +121,7 @@ __global__ void __launch_bounds__(PT) kp_attn_stats_mfma(StatsArgs a) {
             const double* aT = a.w.a72 + (size_t)T * 16 * 64 + lane;
 #pragma unroll 4
             for (int s = 0; s < 16; ++s) v = __builtin_amdgcn_mfma_f64_16x16x4f64(aT[s * 64], xn[s], v, 0, 0, 0);
-            const double kT = __shfl(kp, 16 * T + j, 64);          // k'[T] of element j (0 for an element past the end)
+            const double kT = __shfl(kpw, 16 * T + j, 64);         // k'[T] of element j (0 for an element past the end)
 #pragma unroll
             for (int r = 0; r < 4; ++r) skv[T][r] = fma(kT, v[r], skv[T][r]);   // attention.py:187-188, channel 16 T + g + 4 r
         }
@@ -152,7 +159,8 @@ __global__ void __launch_bounds__(PT) kp_attn_apply(ApplyArgs a) {
     const int line = blockIdx.x / a.nchunk, ch = blockIdx.x - line * a.nchunk;
     const int nelem = a.col ? a.P : a.L;
     const double* s = a.stats + (size_t)line * SROW;
-    if (tid < E) ctx[tid] = s[tid] / s[68 + (tid >> 4)] / (s[64 + (tid >> 4)] / a.count);
+    const double count = (a.wst && !a.col) ? (double)a.wst[(size_t)(line / a.P) * 4] : a.count;
+    if (tid < E) ctx[tid] = s[tid] / s[68 + (tid >> 4)] / (s[64 + (tid >> 4)] / count);
     __syncthreads();
     {
         double m = 0.0;                   // thread (h = w, c = lane)

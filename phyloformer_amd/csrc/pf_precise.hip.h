@@ -59,12 +59,16 @@ struct StatsArgs {
     const double* x; double* q; double* part; AttnW w;
     int col;            // 0: line = (b, p), elements = sites;  1: line = (b, l), elements = pairs
     int P, L, nchunk;
+    const float* wt;    // site weights [B][L] of a weighted forward, or null: a site's
+                        // contribution to the ROW statistics counts wt times (the column reductions run over pairs)
 };
 
 struct ApplyArgs {
     double* x; const double* q; const double* stats; AttnW w;
     int col, P, L, nchunk;
     double count;       // L_total (row attention) or P (column attention): q / q.mean(dim = -2)
+    const float* wst;   // weighted forwards (else null): [B][4], W of the line's alignment at [0] stands for L_total
+                        // in the row attention
 };
 
 struct FfnArgs { double* x; FfnW w; size_t ntok; };

@@ -122,13 +122,24 @@ SIGNATURES = {
                                            C.c_void_p, C.c_void_p, C.c_void_p]),
     "pf_loo_stats_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                       C.c_void_p]),
+    "pf_forward_weighted": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "pf_forward_weighted_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "pf_forward_sites_weighted": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                            C.c_int32, C.c_int32, C.c_void_p]),
+    "pf_bootstrap_weighted": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64,
+                                        C.c_void_p]),
+    "pf_padded_sites": (C.c_int, [C.c_int32, C.c_int32]),
+    "pf_boot_counts": (C.c_int, [C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "pf_compress_sites": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
 }
 
 # Additions to ABI 5 that a library built before them lacks: bound when present; a call through a missing one raises
 # EngineError at call time (loading such a library stays possible).
 CALL_TIME_SYMBOLS = frozenset({"pf_forward_site_map", "pf_forward_site_map_device", "pf_forward_site_profile",
                                "pf_site_moments_device", "pf_gather_taxa_device", "pf_forward_taxa",
-                               "pf_forward_leave_one_out", "pf_loo_stats_device"})
+                               "pf_forward_leave_one_out", "pf_loo_stats_device", "pf_forward_weighted",
+                               "pf_forward_weighted_device", "pf_forward_sites_weighted", "pf_bootstrap_weighted",
+                               "pf_padded_sites", "pf_boot_counts", "pf_compress_sites"})
 
 _lib: Optional[C.CDLL] = None
 
@@ -431,6 +442,65 @@ class Engine:
         ``d_shift [B][N]``, ``d_context [B][P]`` (asynchronous on the handle's stream)."""
         self._check(self._optional("pf_loo_stats_device")(self._h, C.c_void_p(d_full), C.c_void_p(d_loo), B, N,
                                                           C.c_void_p(d_influence), C.c_void_p(d_shift), C.c_void_p(d_context)))
+
+    # -- site weights -----------------------------------------------------------------------
+    @staticmethod
+    def _weights(w, shape, what: str) -> np.ndarray:
+        arr = np.asarray(w)
+        if arr.shape != shape or arr.dtype.kind not in "fiu":
+            raise ValueError(f"{what} must be a real array of shape {list(shape)}, got {arr.dtype} {list(arr.shape)}")
+        return np.ascontiguousarray(arr, dtype=np.float32)
+
+    def forward_weighted(self, idx: np.ndarray, weights: np.ndarray) -> np.ndarray:
+        """Distances of alignments whose site ``l`` counts ``weights[..., l]`` times (``pf_forward_weighted``):
+        ``uint8[B, N, L]``, ``float[B, L]`` → ``float32[B, P]`` (``[N, L]``, ``[L]`` → ``[P]``).  Integer weights give
+        the distances of the alignment with every site repeated that often (to rounding); unit weights give ``forward``'s
+        bits.  Weights must be finite and >= 0 and not all zero, else ``ValueError``."""
+        fn = self._optional("pf_forward_weighted")
+        idx, single = self._sources(idx)
+        B, N, L = idx.shape
+        w = self._weights(np.asarray(weights)[None] if single else weights, (B, L), "weights")
+        out = np.empty((B, N * (N - 1) // 2), dtype=np.float32)
+        self._check(fn(self._h, idx.ctypes.data, B, N, L, w.ctypes.data if w.size else None, out.ctypes.data))
+        return out[0] if single else out
+
+    def forward_weighted_device(self, d_idx: int, B: int, N: int, L: int, d_w: int, d_out: int):
+        """``pf_forward_weighted_device``: device buffers ``d_idx [B][N][L]``, ``d_w float32 [B][L]`` → ``d_out [B][P]``."""
+        self._check(self._optional("pf_forward_weighted_device")(self._h, C.c_void_p(d_idx), B, N, L, C.c_void_p(d_w),
+                                                                 C.c_void_p(d_out)))
+
+    def forward_sites_weighted(self, idx: np.ndarray, sites: np.ndarray, weights: np.ndarray) -> np.ndarray:
+        """``forward_sites`` with a weight per table entry (``pf_forward_sites_weighted``): ``uint8[B, N, L]``,
+        ``int[S, K]``, ``float[S, K]`` → ``float32[B, S, P]``; ``out[b, s]`` is ``forward_weighted`` of
+        ``idx[b][:, sites[s]]`` with ``weights[s]``, bit for bit."""
+        fn = self._optional("pf_forward_sites_weighted")
+        idx, single = self._sources(idx)
+        B, N, L = idx.shape
+        tab = np.asarray(sites)
+        if tab.ndim != 2 or tab.dtype.kind not in "iu":
+            raise ValueError(f"sites must be an integer array [S, K], got {tab.dtype} {tab.shape}")
+        if tab.size and (tab.min() < -2 ** 31 or tab.max() >= 2 ** 31):
+            raise ValueError(f"site {int(tab.max() if tab.max() >= 2 ** 31 else tab.min())} is outside [0, {L})")
+        tab = np.ascontiguousarray(tab, dtype=np.int32)
+        S, K = tab.shape
+        w = self._weights(weights, (S, K), "weights")
+        out = np.empty((B, S, N * (N - 1) // 2), dtype=np.float32)
+        self._check(fn(self._h, idx.ctypes.data, B, N, L, tab.ctypes.data if tab.size else None,
+                       w.ctypes.data if w.size else None, S, K, out.ctypes.data if out.size else None))
+        return out[0] if single else out
+
+    def bootstrap_weighted(self, idx: np.ndarray, replicates: int, seed: int = 0) -> np.ndarray:
+        """``bootstrap`` computed on each replicate's DISTINCT sites with their multiplicities as weights
+        (``pf_bootstrap_weighted``): the same replicates of the same stream, about a third fewer tokens; equal to
+        ``bootstrap`` to rounding, not bit for bit.  ``uint8[B, N, L]`` → ``float32[B, R, P]``."""
+        fn = self._optional("pf_bootstrap_weighted")
+        idx, single = self._sources(idx)
+        B, N, L = idx.shape
+        R = int(replicates)
+        out = np.empty((B, max(R, 0), N * (N - 1) // 2), dtype=np.float32)
+        self._check(fn(self._h, idx.ctypes.data, B, N, L, R, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                       out.ctypes.data if out.size else None))
+        return out[0] if single else out
 
     def forward_sharded(self, idx_local: np.ndarray, l_begin: int, l_end: int, L_total: int) -> np.ndarray:
         """This rank's sites ``[l_begin, l_end)`` of ``uint8[B, N, L_total]`` alignments."""

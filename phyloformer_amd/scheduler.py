@@ -120,8 +120,10 @@ class DirectoryRunner:
 
     def __init__(self, engine, out_dir: str, trees: bool = False, batch: int = 0,
                  io_threads: int = 4, native_io: bool = True, progress=None, bootstrap: int = 0, seed: int = 0,
-                 windows: Optional[Tuple[int, int]] = None, site_profile: bool = False, leave_one_out: bool = False):
+                 windows: Optional[Tuple[int, int]] = None, site_profile: bool = False, leave_one_out: bool = False,
+                 compress_sites: bool = False):
         self.engines = list(engine) if isinstance(engine, (list, tuple)) else [engine]
+        self.compress_sites = bool(compress_sites)   # --compress-sites: distinct columns with their counts as weights
         self.out_dir = out_dir
         self.trees = trees
         self.batch = batch            # 0 = auto per shape
@@ -201,7 +203,8 @@ class DirectoryRunner:
         sub = max(1, BOOT_FLOATS // max(1, self.bootstrap * P))
         for s0 in range(0, len(group), sub):
             t0 = time.perf_counter()
-            reps = engine.bootstrap(batch[s0:s0 + sub], self.bootstrap, self.seed)
+            boot = engine.bootstrap_weighted if self.compress_sites else engine.bootstrap
+            reps = boot(batch[s0:s0 + sub], self.bootstrap, self.seed)
             dt = time.perf_counter() - t0
             part = group[s0:s0 + sub]
             with self._lock:
@@ -359,6 +362,21 @@ class DirectoryRunner:
         for k, (path, (fb, i), _none) in enumerate(group):
             self._write_taxa(path, preds[k], infls[k], shifts[k], ctxs[k], None if loos is None else loos[k], fb.ids(i))
 
+    def _forward_compressed(self, engine, batch: np.ndarray) -> np.ndarray:
+        """``--compress-sites``: every alignment as its distinct columns with their counts as weights, padded to
+        ``padded_sites`` of its own count (site 0, weight 0).  Alignments of one padded size share a launch; a file's
+        distances depend on the file alone."""
+        from . import weights_sites as ws
+        compress = ws.native_compress_sites if self.native_io else ws.compress_sites
+        B, N, L = batch.shape
+        tables = [ws.pad_table(f, c, ws.padded_sites(len(f), L)) for f, c in (compress(a) for a in batch)]
+        preds = np.empty((B, N * (N - 1) // 2), dtype=np.float32)
+        for kp in sorted({len(s) for s, _w in tables}):
+            who = [b for b in range(B) if len(tables[b][0]) == kp]
+            cut = np.stack([batch[b][:, tables[b][0]] for b in who])
+            preds[who] = engine.forward_weighted(cut, np.stack([tables[b][1] for b in who]))
+        return preds
+
     def _launch(self, engine, shape: Tuple[int, int], group: list, writers: ThreadPoolExecutor, pending: deque):
         native = group[0][2] is None              # entries of _feed_native: (path, (FastaBatch, file), None)
         t0 = time.perf_counter()
@@ -374,6 +392,10 @@ class DirectoryRunner:
             # the same distances (forward's, bit for bit), then the N cuts of every alignment and their statistics
             preds, infls, shifts, ctxs, *loos = self._forward_loo(engine, shape, batch)
             loos = loos[0] if loos else None
+        elif self.compress_sites and not self.bootstrap:
+            # (with --bootstrap the whole alignment keeps forward's bits - <stem>.phy, the tree and its branch lengths in
+            # <stem>.sup.nwk are those of a run without the flag - and the R replicates, the cost, run compressed)
+            preds = self._forward_compressed(engine, batch)
         else:
             preds = engine.forward(batch)
         dt = time.perf_counter() - t0
