@@ -10,22 +10,10 @@ infer_alns.py:36-38,100-103) or the run aborts with ``ValueError``; for each
 alignment ``OUTDIR/<stem>.phy`` receives the PHYLIP distance matrix
 (``%.10f``) and, with ``-t``, ``OUTDIR/<stem>.nj.nwk`` a neighbour-joining tree.
 
-Additive flags (not in the reference): ``--device`` / ``--devices 0,1,...`` (one
-process per GPU; ``--shard files`` - the default - deals the files to the GPUs, ``--shard sites``
-spreads every alignment over them: each rank holds a block of sites, RCCL all-reduces inside
-``pf_forward_sharded``, rank 0 writes the outputs), ``--batch`` (same-shape alignments per launch;
-default: fill a token budget per shape), ``--io-threads``, ``--gpu-streams``, ``--precise``, ``--python-io``,
-``--bench`` (print a JSON timing line), ``--bootstrap R`` / ``--seed S`` (``OUTDIR/<stem>.sup.nwk``: the NJ tree with
-site-bootstrap supports, R replicates resampled and inferred on the GPU; not with ``--shard sites``), ``--windows W[:STEP]``
-(a scan along the alignment: ``OUTDIR/<stem>.w<first>-<last>.phy`` - with ``-t`` also ``.nj.nwk`` - per window of W sites,
-1-based inclusive site numbers, and ``OUTDIR/<stem>.windows.tsv`` comparing the windows' NJ trees; the windows are cut and
-inferred on the GPU from one upload of the alignment; not with ``--bootstrap`` or ``--shard sites``), ``--site-profile``
-(``OUTDIR/<stem>.sites.tsv`` and ``OUTDIR/<stem>.se.phy``: every site's share of the distances and every distance's
-standard error over sites, from the forward that computes the distances; not with ``--bootstrap``, ``--windows`` or
-``--shard sites``), ``--leave-one-out`` (``OUTDIR/<stem>.taxa.tsv`` and ``OUTDIR/<stem>.context.phy``: how far removing each
-sequence moves the distances of the others, and how much each distance depends on who else is in the alignment; the N
-cuts of an alignment are made and inferred on the GPU from one upload; not with ``--bootstrap``, ``--windows``,
-``--site-profile`` or ``--shard sites``).  Scheduling lives in
+Additive flags (not in the reference) are described by ``--help``: where the work runs (``--device`` / ``--devices``,
+``--shard``, ``--batch``, ``--io-threads``, ``--gpu-streams``, ``--precise``, ``--python-io``, ``--bench``) and the
+per-alignment analyses, each of which writes further files beside ``<stem>.phy`` and says in its own help text what they
+hold (``phyloformer_amd/analyses.py``: one description per mode, with the combinations it refuses).  Scheduling lives in
 ``phyloformer_amd/scheduler.py``: files are bucketed by shape, parsed ahead of the
 GPU and written behind it.  A directory entry without a FASTA extension, or a file that does
 not parse, has the reference's side effects (infer_alns.py:97-117): every entry in front of it
@@ -39,12 +27,10 @@ import os
 import sys
 import time
 from glob import glob
-from pathlib import Path
 
+from phyloformer_amd import analyses
 
-def has_fasta_ext(alnpath):
-    """Checks if a path ends in .fa or .fasta"""
-    return alnpath.lower().endswith(".fa") or alnpath.lower().endswith(".fasta")
+PRECISE = {"auto": -1, "always": 1, "never": 0}      # --precise -> the engine's option "precise"
 
 
 def build_parser():
@@ -71,45 +57,13 @@ def build_parser():
     parser.add_argument("--gpu-streams", type=int, default=2,
                         help="engines (HIP streams, one host thread each) per GPU; 2 hides the host-side gaps "
                              "of a synchronous forward, 1 = one launch sequence at a time")
-    parser.add_argument("--precise", choices=["auto", "always", "never"], default="auto",
+    parser.add_argument("--precise", choices=list(PRECISE), default="auto",
                         help="float64 kernels: auto = for alignments of fewer than 32 sites or 8,192 pair-site tokens (where the fp32 reference itself is "
                              "ill-conditioned) and, after the fact, for any alignment with a predicted distance above 8 substitutions per "
                              "site (never an alignment; an absolute 1e-4 there is fp32's own rounding level); always = every alignment (3-9 x slower); never = the split-fp16 MFMA kernels "
                              "on every shape")
-    parser.add_argument("--bootstrap", type=int, default=0, metavar="R",
-                        help="site-bootstrap replicates per alignment, resampled and inferred on the GPU: writes "
-                             "<stem>.sup.nwk, the NJ tree of the alignment's distances with the percent of replicate "
-                             "trees that contain each internal branch's split; 0 (default) = off")
-    parser.add_argument("--seed", type=int, default=0,
-                        help="seed of the bootstrap replicate stream (default 0): a file's supports depend on the "
-                             "weights, the alignment, R and the seed only")
-    parser.add_argument("--windows", default=None, metavar="W[:STEP]",
-                        help="scan along every alignment: the distances (with -t the NJ tree) of every window of W sites, "
-                             "STEP sites apart (default STEP = W: non-overlapping; a last window is anchored at L - W so that "
-                             "every site is covered), cut and inferred on the GPU: writes <stem>.w<first>-<last>.phy per "
-                             "window (1-based inclusive sites) and <stem>.windows.tsv (first, last, mean_distance, and the "
-                             "Robinson-Foulds distances of the window's NJ tree to the previous window's and to the whole "
-                             "alignment's); <stem>.phy is unchanged; a file with fewer than W sites is an error")
-    parser.add_argument("--site-profile", action="store_true",
-                        help="site-resolved distances from the same forward: writes <stem>.sites.tsv (site, profile = the "
-                             "mean over pairs of the site's term of the distances, relative = profile / its mean over sites) "
-                             "and <stem>.se.phy, the standard error of every distance's mean over sites as a PHYLIP matrix (a "
-                             "descriptive statistic of the model's own per-site terms, not a calibrated confidence interval); "
-                             "<stem>.phy is unchanged")
-    parser.add_argument("--leave-one-out", action="store_true",
-                        help="taxon influence: every alignment is inferred again without each of its sequences in turn (cut and "
-                             "inferred on the GPU): writes <stem>.taxa.tsv (index, id, influence = RMS move of the other "
-                             "distances when the sequence leaves, shift = their mean move, relative = influence / its mean; with "
-                             "-t rf_pruned = Robinson-Foulds distance of the cut's NJ tree to the whole alignment's NJ tree "
-                             "without that leaf) and <stem>.context.phy, how much each distance depends on the other sequences, "
-                             "as a PHYLIP matrix (descriptive statistics, not a test); <stem>.phy is unchanged; a file with "
-                             "fewer than 3 sequences is an error")
-    parser.add_argument("--compress-sites", action="store_true",
-                        help="site-pattern compression: every alignment is inferred on its distinct columns with their "
-                             "counts as site weights (the same distances to rounding, fewer tokens where columns repeat); "
-                             "with --bootstrap R it is the R replicates that run on their distinct sites with their "
-                             "multiplicities (about a third fewer tokens per replicate; the alignment itself is inferred "
-                             "as without the flag, so only the support values of <stem>.sup.nwk can differ)")
+    for mode in analyses.MODES:
+        mode.add_arguments(parser)
     parser.add_argument("--python-io", action="store_true",
                         help="use the pure-Python FASTA parser and PHYLIP writer instead of the native ones")
     parser.add_argument("--worker", default=None, help=argparse.SUPPRESS)   # "r/W": share r of W of the files
@@ -121,55 +75,7 @@ def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     parser = build_parser()
     args = parser.parse_args(argv)
-    if args.bootstrap < 0:
-        parser.error(f"--bootstrap must be >= 0 (got {args.bootstrap})")
-    if args.bootstrap and args.shard == "sites":
-        parser.error("--bootstrap is not supported with --shard sites (every replicate would need its own collectives); "
-                     "use --shard files")
-
-    windows = None
-    if args.windows is not None:
-        from phyloformer_amd.windows import parse_windows_arg
-        try:
-            windows = parse_windows_arg(args.windows)
-        except ValueError as exc:
-            parser.error(f"--windows: {exc}")
-        if args.bootstrap:
-            parser.error("--windows is not supported with --bootstrap (replicates of windows are out of scope)")
-        if args.shard == "sites":
-            parser.error("--windows is not supported with --shard sites (every window would need its own collectives); "
-                         "use --shard files")
-
-    if args.site_profile:
-        if args.bootstrap:
-            parser.error("--site-profile is not supported with --bootstrap (site maps of replicates are out of scope)")
-        if windows is not None:
-            parser.error("--site-profile is not supported with --windows (site maps of windows are out of scope)")
-        if args.shard == "sites":
-            parser.error("--site-profile is not supported with --shard sites (a rank would hold a slice of the site map); "
-                         "use --shard files")
-
-    if args.leave_one_out:
-        if args.bootstrap:
-            parser.error("--leave-one-out is not supported with --bootstrap (replicates of taxon subsets are out of scope)")
-        if windows is not None:
-            parser.error("--leave-one-out is not supported with --windows (taxon subsets of windows are out of scope)")
-        if args.site_profile:
-            parser.error("--leave-one-out is not supported with --site-profile (site maps of taxon subsets are out of scope)")
-        if args.shard == "sites":
-            parser.error("--leave-one-out is not supported with --shard sites (every cut would need its own collectives); "
-                         "use --shard files")
-
-    if args.compress_sites:
-        if windows is not None:
-            parser.error("--compress-sites is not supported with --windows (a window is a run of sites, not of patterns)")
-        if args.site_profile:
-            parser.error("--compress-sites is not supported with --site-profile (the profile is per site, not per pattern)")
-        if args.leave_one_out:
-            parser.error("--compress-sites is not supported with --leave-one-out (weighted taxon subsets are out of scope)")
-        if args.shard == "sites":
-            parser.error("--compress-sites is not supported with --shard sites (weighted forwards are not site-sharded); "
-                         "use --shard files")
+    modes = analyses.modes_from_args(args, parser.error)
 
     from phyloformer_amd import scheduler
 
@@ -230,9 +136,7 @@ def main(argv=None):
     load_s = time.perf_counter() - t0
 
     if world > 1:
-        for p in paths:
-            if not scheduler.has_fasta_ext(p):
-                raise ValueError("Input files must be fasta files (.fa or .fasta). Got " f"{p}")
+        scheduler.require_fasta_entries(paths)
         paths = scheduler.slice_paths(paths, rank, world)
 
     bar = tqdm(total=len(paths)) if (tqdm is not None and world == 1) else None
@@ -240,7 +144,7 @@ def main(argv=None):
     if args.batch != 1:
         engines += [scheduler.cli_engine(model.weights, args.device) for _ in range(max(1, args.gpu_streams) - 1)]
     for e in engines:
-        e.set_option("precise", {"auto": -1, "always": 1, "never": 0}[args.precise])
+        e.set_option("precise", PRECISE[args.precise])
     if len(engines) > 1:
         # several engines already keep several streams busy; each splitting its batches over two more only adds
         # contention (tools/cli_bench.py, same box: 505 against 498 alignments/s)
@@ -248,23 +152,24 @@ def main(argv=None):
             e.set_option("two_streams", 0)
     runner = scheduler.DirectoryRunner(engines, out_dir, trees=args.trees, batch=args.batch,
                                        io_threads=args.io_threads, native_io=not args.python_io,
-                                       progress=bar.update if bar is not None else None,
-                                       bootstrap=args.bootstrap, seed=args.seed, windows=windows,
-                                       site_profile=args.site_profile, leave_one_out=args.leave_one_out,
-                                       compress_sites=args.compress_sites)
+                                       progress=bar.update if bar is not None else None, modes=modes)
     try:
         stats = runner.run(paths)
     finally:
         if bar is not None:
             bar.close()
-    if args.bench:
-        rep = scheduler.summarize(stats, load_s)
-        rep["device"] = args.device
-        print(json.dumps(rep), file=sys.stderr)
+    print_report(args, stats, load_s)
     for e in engines[1:]:
         e.close()
     model.close()
     return 0
+
+
+def print_report(args, stats, load_s, **more):
+    """``--bench``: the run's JSON timing line on stderr."""
+    if args.bench:
+        from phyloformer_amd import scheduler
+        print(json.dumps({**scheduler.summarize(stats, load_s), "device": args.device, **more}), file=sys.stderr)
 
 
 def run_site_sharded(args, paths, rank, world, out_dir, tqdm):
@@ -280,7 +185,7 @@ def run_site_sharded(args, paths, rank, world, out_dir, tqdm):
     t0 = time.perf_counter()
     weights = load_weights(args.weights)
     engine = scheduler.cli_engine(weights, args.device)
-    engine.set_option("precise", {"auto": -1, "always": 1, "never": 0}[args.precise])
+    engine.set_option("precise", PRECISE[args.precise])
     load_s = time.perf_counter() - t0
     group = None
     try:
@@ -298,17 +203,12 @@ def run_site_sharded(args, paths, rank, world, out_dir, tqdm):
                 if rank == 0:
                     print("infer_alns: site-sharding unavailable (" + "; ".join(w for o, w in seen if not o) +
                           "); sharding the files over the GPUs instead", file=sys.stderr)
-                for p in paths:
-                    if not scheduler.has_fasta_ext(p):
-                        raise ValueError("Input files must be fasta files (.fa or .fasta). Got " f"{p}")
+                scheduler.require_fasta_entries(paths)
                 runner = scheduler.DirectoryRunner([engine], out_dir, trees=args.trees, batch=args.batch,
                                                    io_threads=args.io_threads, native_io=not args.python_io)
                 stats = runner.run(scheduler.slice_paths(paths, rank, world))
                 group.barrier()
-                if args.bench:
-                    rep = scheduler.summarize(stats, load_s)
-                    rep["device"] = args.device
-                    print(json.dumps(rep), file=sys.stderr)
+                print_report(args, stats, load_s)
                 return 0
         else:
             engine.set_option("force_rccl", 1)
@@ -323,11 +223,8 @@ def run_site_sharded(args, paths, rank, world, out_dir, tqdm):
         finally:
             if bar is not None:
                 bar.close()
-        if args.bench:
-            rep = scheduler.summarize(stats, load_s)
-            rep.update({"device": args.device, "site_sharded_over": world, "rank": rank,
-                        "collectives": engine.collective_count() if hasattr(engine, "collective_count") else None})
-            print(json.dumps(rep), file=sys.stderr)
+        print_report(args, stats, load_s, site_sharded_over=world, rank=rank,
+                     collectives=engine.collective_count() if hasattr(engine, "collective_count") else None)
         return 0
     finally:
         if group is not None:

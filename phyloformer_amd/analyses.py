@@ -1,0 +1,356 @@
+"""The CLI's per-alignment analyses (``--bootstrap``, ``--windows``, ``--site-profile``, ``--leave-one-out``,
+``--compress-sites``), each described ONCE: its flag and help, what it refuses to be combined with, the files it
+cannot run on, the stats it reports, its call into the engine and its writer.  ``infer_alns.py`` builds its parser and
+its refusals from ``MODES``; ``scheduler.DirectoryRunner`` drives whatever modes it is given and names none of them.
+
+A mode plays one of two roles in a launch (``DirectoryRunner._launch``):
+
+* it REPLACES the forward (``forward``): the launch's distances plus a payload, one row per alignment, for ``write``;
+* it FOLLOWS the forward (``follow``) in sub-batches of at most ``FLOATS`` result floats, each written behind it.
+"""
+from __future__ import annotations
+
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+
+# Result floats of one engine call behind the launch's forward (16 MiB): the replicate distances of a pf_bootstrap call,
+# the window distances of a pf_forward_windows call, the distances of the cuts (N x P1 floats per alignment) of a
+# pf_forward_leave_one_out call.  This bounds host memory, not GPU work: the results wait in the writer queue (up to
+# 8 x io_threads entries) until their files are written, so the cap keeps that queue to a few hundred MB even at 200
+# taxa (R = 100 x 19,900 floats = 8 MB per alignment).  The GPU stays fed: one alignment's R = 100 replicates at
+# 60 x 500 are already 6 x TOKEN_BUDGET, and the library chunks every one of these calls itself.
+FLOATS = 1 << 22
+
+SHARD_SITES = "--shard sites"
+
+
+def sub_batches(count: int, floats_each: int) -> List[slice]:
+    """``count`` alignments in runs whose results stay within ``FLOATS`` (at least one alignment per run)."""
+    sub = max(1, FLOATS // max(1, floats_each))
+    return [slice(s0, s0 + sub) for s0 in range(0, count, sub)]
+
+
+def _text(tree) -> str:
+    return tree.decode("utf8") if isinstance(tree, bytes) else tree
+
+
+class Analysis:
+    """One mode.  The class is what the command line knows (``flag``, ``help``, ``option``, ``refuses``, ``from_args``);
+    an instance is the mode switched on, with its parameters."""
+    flag = ""
+    help = ""
+    option: dict = {"action": "store_true"}      # argparse keywords besides ``help``
+    refuses: Tuple[Tuple[str, str], ...] = ()    # (other flag or SHARD_SITES, reason), in the order they are reported
+    forward = None                               # forward(runner, engine, shape, batch) -> (preds, payload columns)
+    follow = None                                # follow(engine, batch) -> results [B, ...]
+    write = None                                 # write(runner, shape, entry, pred, *payload row): one file's outputs
+
+    @classmethod
+    def dest(cls) -> str:
+        return cls.flag[2:].replace("-", "_")
+
+    @classmethod
+    def add_arguments(cls, parser):
+        parser.add_argument(cls.flag, help=cls.help, **cls.option)
+
+    @classmethod
+    def from_args(cls, args) -> "Optional[Analysis]":
+        """The mode as ``args`` asks for it, None if it is off; ``ValueError`` carries the text of a usage error."""
+        return cls() if getattr(args, cls.dest()) else None
+
+    @classmethod
+    def refusal(cls, other: str, reason: str) -> str:
+        return f"{cls.flag} is not supported with {other} ({reason})" + ("; use --shard files" if other == SHARD_SITES else "")
+
+    def stats(self) -> dict:
+        """The keys this mode adds to the run's stats."""
+        return {}
+
+    def bind(self, modes: "Sequence[Analysis]"):
+        """Called once with all the modes of the run."""
+
+    def accepts(self, n, l):
+        """Can a file of ``n`` sequences and ``l`` sites be run?  Elementwise: ints or the arrays of a FastaBatch."""
+        return True
+
+    def file_error(self, path: str, n: int, l: int) -> Exception:
+        """What a file that ``accepts`` turns down raises, where the loop reaches it."""
+        raise NotImplementedError
+
+    def floats(self, shape: Tuple[int, int]) -> int:
+        """Result floats of ``follow`` per alignment."""
+        raise NotImplementedError
+
+    def account(self, stats: dict, count: int, shape: Tuple[int, int], seconds: float):
+        """Book one engine call over ``count`` alignments (under the runner's lock)."""
+
+    def jobs(self, runner, shape, part, preds, *payload) -> list:
+        """The writer jobs ``(callable, *args)`` of a (sub-)batch: one per file through the Python writers, one for all
+        of them on the native path, where the ids come out of the ``FastaBatch`` on the writer thread."""
+        rows = list(zip(part, preds, *payload))
+        if runner.native_io:
+            return [(lambda: [self.write(runner, shape, *row) for row in rows],)]
+        return [(self.write, runner, shape, *row) for row in rows]
+
+
+class Bootstrap(Analysis):
+    flag = "--bootstrap"
+    option = {"type": int, "default": 0, "metavar": "R"}
+    help = ("site-bootstrap replicates per alignment, resampled and inferred on the GPU: writes "
+            "<stem>.sup.nwk, the NJ tree of the alignment's distances with the percent of replicate "
+            "trees that contain each internal branch's split; 0 (default) = off")
+    refuses = ((SHARD_SITES, "every replicate would need its own collectives"),)
+    call = "bootstrap"
+
+    def __init__(self, replicates: int, seed: int = 0):
+        self.replicates, self.seed = int(replicates), int(seed)
+
+    @classmethod
+    def add_arguments(cls, parser):
+        super().add_arguments(parser)
+        parser.add_argument("--seed", type=int, default=0,
+                            help="seed of the bootstrap replicate stream (default 0): a file's supports depend on the "
+                                 "weights, the alignment, R and the seed only")
+
+    @classmethod
+    def from_args(cls, args):
+        if args.bootstrap < 0:
+            raise ValueError(f"--bootstrap must be >= 0 (got {args.bootstrap})")
+        return cls(args.bootstrap, args.seed) if args.bootstrap else None
+
+    def stats(self):
+        return {"replicates": self.replicates, "bootstrap_s": 0.0}
+
+    def floats(self, shape):
+        return self.replicates * (shape[0] * (shape[0] - 1) // 2)
+
+    def follow(self, engine, batch):
+        return getattr(engine, self.call)(batch, self.replicates, self.seed)
+
+    def account(self, stats, count, shape, seconds):
+        stats["bootstrap_s"] += seconds
+
+    def write(self, runner, shape, entry, pred, reps):
+        """``<stem>.sup.nwk``: the NJ tree of ``pred`` with the supports of ``reps``."""
+        if runner.native_io:
+            from .hostio import nj_support
+            runner.put(entry.path, "sup.nwk", nj_support(pred, reps, entry.ids(), threads=runner.writer_cap()))
+        else:
+            from .bootstrap import support_newick_py
+            runner.put(entry.path, "sup.nwk", support_newick_py(pred, reps, entry.ids()))
+
+
+class Windows(Analysis):
+    flag = "--windows"
+    option = {"default": None, "metavar": "W[:STEP]"}
+    help = ("scan along every alignment: the distances (with -t the NJ tree) of every window of W sites, "
+            "STEP sites apart (default STEP = W: non-overlapping; a last window is anchored at L - W so that "
+            "every site is covered), cut and inferred on the GPU: writes <stem>.w<first>-<last>.phy per "
+            "window (1-based inclusive sites) and <stem>.windows.tsv (first, last, mean_distance, and the "
+            "Robinson-Foulds distances of the window's NJ tree to the previous window's and to the whole "
+            "alignment's); <stem>.phy is unchanged; a file with fewer than W sites is an error")
+    refuses = (("--bootstrap", "replicates of windows are out of scope"),
+               (SHARD_SITES, "every window would need its own collectives"))
+
+    def __init__(self, width: int, step: int):
+        self.width, self.step = int(width), int(step)
+
+    @classmethod
+    def from_args(cls, args):
+        if args.windows is None:
+            return None
+        from .windows import parse_windows_arg
+        try:
+            return cls(*parse_windows_arg(args.windows))
+        except ValueError as exc:
+            raise ValueError(f"--windows: {exc}") from None
+
+    def stats(self):
+        return {"windows": 0, "windows_s": 0.0}
+
+    def accepts(self, n, l):
+        return l >= self.width
+
+    def file_error(self, path, n, l):
+        return ValueError(f"--windows: {path} has L = {l} sites, fewer than the window width W = {self.width}")
+
+    def starts(self, n_sites: int) -> List[int]:
+        from .windows import window_starts
+        return window_starts(n_sites, self.width, self.step)
+
+    def floats(self, shape):
+        return len(self.starts(shape[1])) * (shape[0] * (shape[0] - 1) // 2)
+
+    def follow(self, engine, batch):
+        """(``pf_forward_windows``: the sources go up once, the windows are cut on the device)"""
+        return engine.forward_windows(batch, self.width, self.step)
+
+    def account(self, stats, count, shape, seconds):
+        stats["windows_s"] += seconds
+        stats["windows"] += count * len(self.starts(shape[1]))
+
+    def suffixes(self, n_sites: int, ext: str) -> List[str]:
+        from .windows import window_label
+        return [f"{window_label(n_sites, st, self.width)}.{ext}" for st in self.starts(n_sites)]
+
+    def write(self, runner, shape, entry, pred, wpred, files: bool = True):
+        """One file's window outputs: ``<stem>.w<first>-<last>.phy`` (``.nj.nwk`` with ``--trees``) per window - unless
+        ``write_native`` has written them - and ``<stem>.windows.tsv``."""
+        from .windows import summary_tsv
+        ids = entry.ids()
+        wtrees = [runner.nj(w, ids) for w in wpred]
+        if files:
+            for phy, nwk, w, tree in zip(self.suffixes(shape[1], "phy"), self.suffixes(shape[1], "nj.nwk"), wpred, wtrees):
+                runner.put(entry.path, phy, runner.phylip(w, ids))
+                if runner.trees:
+                    runner.put(entry.path, nwk, tree)
+        runner.put(entry.path, "windows.tsv", summary_tsv(self.starts(shape[1]), self.width, wpred,
+                                                           [_text(t) for t in wtrees], _text(runner.nj(pred, ids))))
+
+    def write_native(self, runner, shape, part, preds, wpreds):
+        """The same files for a sub-batch: the window matrices (and trees) of all its files in one native call, then
+        the tables."""
+        from .hostio import write_phylip
+        entries = [e.source for e in part for _ in self.starts(shape[1])]
+        outs = [runner.out_path(e.path, s) for e in part for s in self.suffixes(shape[1], "phy")]
+        trees = [runner.out_path(e.path, s) for e in part for s in self.suffixes(shape[1], "nj.nwk")] if runner.trees else None
+        write_phylip(entries, shape[0], wpreds.reshape(len(entries), -1), outs, runner.writer_cap(), trees)
+        for entry, pred, wp in zip(part, preds, wpreds):
+            self.write(runner, shape, entry, pred, wp, files=False)
+
+    def jobs(self, runner, shape, part, preds, wpreds):
+        if runner.native_io:
+            return [(self.write_native, runner, shape, part, preds, wpreds)]
+        return super().jobs(runner, shape, part, preds, wpreds)
+
+
+class SiteProfile(Analysis):
+    flag = "--site-profile"
+    help = ("site-resolved distances from the same forward: writes <stem>.sites.tsv (site, profile = the "
+            "mean over pairs of the site's term of the distances, relative = profile / its mean over sites) "
+            "and <stem>.se.phy, the standard error of every distance's mean over sites as a PHYLIP matrix (a "
+            "descriptive statistic of the model's own per-site terms, not a calibrated confidence interval); "
+            "<stem>.phy is unchanged")
+    refuses = (("--bootstrap", "site maps of replicates are out of scope"),
+               ("--windows", "site maps of windows are out of scope"),
+               (SHARD_SITES, "a rank would hold a slice of the site map"))
+
+    def forward(self, runner, engine, shape, batch):
+        # the same forward (its distances are forward's, bit for bit) also leaves se and the site profile
+        preds, ses, profiles = engine.forward_site_profile(batch)
+        return preds, (ses, profiles)
+
+    def write(self, runner, shape, entry, pred, se, profile):
+        """``<stem>.sites.tsv`` and ``<stem>.se.phy`` of one file (ids and number format of ``<stem>.phy``)."""
+        from .siteprofile import sites_tsv
+        runner.put(entry.path, "sites.tsv", sites_tsv(profile))
+        runner.put(entry.path, "se.phy", runner.phylip(se, entry.ids()))
+
+
+class LeaveOneOut(Analysis):
+    flag = "--leave-one-out"
+    help = ("taxon influence: every alignment is inferred again without each of its sequences in turn (cut and "
+            "inferred on the GPU): writes <stem>.taxa.tsv (index, id, influence = RMS move of the other "
+            "distances when the sequence leaves, shift = their mean move, relative = influence / its mean; with "
+            "-t rf_pruned = Robinson-Foulds distance of the cut's NJ tree to the whole alignment's NJ tree "
+            "without that leaf) and <stem>.context.phy, how much each distance depends on the other sequences, "
+            "as a PHYLIP matrix (descriptive statistics, not a test); <stem>.phy is unchanged; a file with "
+            "fewer than 3 sequences is an error")
+    refuses = (("--bootstrap", "replicates of taxon subsets are out of scope"),
+               ("--windows", "taxon subsets of windows are out of scope"),
+               ("--site-profile", "site maps of taxon subsets are out of scope"),
+               (SHARD_SITES, "every cut would need its own collectives"))
+
+    def stats(self):
+        return {"loo_sets": 0}
+
+    def accepts(self, n, l):
+        return n >= 3
+
+    def file_error(self, path, n, l):
+        """(a file with fewer than 3 sequences has no leave-one-out cut with a pair)"""
+        return ValueError(f"--leave-one-out: {path} has N = {n} sequences, fewer than the 3 a cut with one pair needs")
+
+    def forward(self, runner, engine, shape, batch):
+        """The same distances (forward's, bit for bit), then the N cuts of every alignment and their statistics, in
+        sub-batches; the cuts' distances are kept only for the trees of ``rf_pruned`` (``--trees``)."""
+        N = shape[0]
+        parts = [engine.forward_leave_one_out(batch[s], keep_loo=runner.trees)
+                 for s in sub_batches(len(batch), N * (N - 1) * (N - 2) // 2)]
+        preds, infls, shifts, ctxs, *loos = [np.concatenate([p[k] for p in parts]) for k in range(len(parts[0]))]
+        return preds, (infls, shifts, ctxs, loos[0] if loos else [None] * len(batch))
+
+    def account(self, stats, count, shape, seconds):
+        stats["loo_sets"] += count * shape[0]
+
+    def write(self, runner, shape, entry, pred, infl, shift, ctx, loo):
+        """``<stem>.taxa.tsv`` and ``<stem>.context.phy`` of one file (ids and number format of ``<stem>.phy``); with
+        ``--trees`` the column ``rf_pruned`` from NJ trees on index labels."""
+        from .taxa import rf_pruned, taxa_tsv
+        ids = entry.ids()
+        N = len(ids)
+        rf = None
+        if runner.trees:
+            labels = [str(k) for k in range(N)]
+            rf = ["NA"] * N if N - 1 < 4 else rf_pruned(
+                _text(runner.nj(pred, labels)), [_text(runner.nj(loo[t], labels[:t] + labels[t + 1:])) for t in range(N)], N)
+        runner.put(entry.path, "taxa.tsv", taxa_tsv(ids, infl, shift, rf))
+        runner.put(entry.path, "context.phy", runner.phylip(ctx, ids))
+
+
+class CompressSites(Analysis):
+    flag = "--compress-sites"
+    help = ("site-pattern compression: every alignment is inferred on its distinct columns with their "
+            "counts as site weights (the same distances to rounding, fewer tokens where columns repeat); "
+            "with --bootstrap R it is the R replicates that run on their distinct sites with their "
+            "multiplicities (about a third fewer tokens per replicate; the alignment itself is inferred "
+            "as without the flag, so only the support values of <stem>.sup.nwk can differ)")
+    refuses = (("--windows", "a window is a run of sites, not of patterns"),
+               ("--site-profile", "the profile is per site, not per pattern"),
+               ("--leave-one-out", "weighted taxon subsets are out of scope"),
+               (SHARD_SITES, "weighted forwards are not site-sharded"))
+
+    def bind(self, modes):
+        boot = next((m for m in modes if isinstance(m, Bootstrap)), None)
+        if boot is not None:
+            # (with --bootstrap the whole alignment keeps forward's bits - <stem>.phy, the tree and its branch lengths in
+            # <stem>.sup.nwk are those of a run without the flag - and the R replicates, the cost, run compressed)
+            boot.call = "bootstrap_weighted"
+            self.forward = None
+
+    def forward(self, runner, engine, shape, batch):
+        """Every alignment as its distinct columns with their counts as weights, padded to ``padded_sites`` of its own
+        count (site 0, weight 0).  Alignments of one padded size share a launch; a file's distances depend on the file
+        alone."""
+        from . import weights_sites as ws
+        compress = ws.native_compress_sites if runner.native_io else ws.compress_sites
+        B, N, L = batch.shape
+        tables = [ws.pad_table(f, c, ws.padded_sites(len(f), L)) for f, c in (compress(a) for a in batch)]
+        preds = np.empty((B, N * (N - 1) // 2), dtype=np.float32)
+        for kp in sorted({len(s) for s, _w in tables}):
+            who = [b for b in range(B) if len(tables[b][0]) == kp]
+            cut = np.stack([batch[b][:, tables[b][0]] for b in who])
+            preds[who] = engine.forward_weighted(cut, np.stack([tables[b][1] for b in who]))
+        return preds, ()
+
+
+MODES = (Bootstrap, Windows, SiteProfile, LeaveOneOut, CompressSites)
+
+
+def modes_from_args(args, error) -> List[Analysis]:
+    """The modes ``args`` switches on.  A bad value or a refused combination goes to ``error(text)`` (``parser.error``,
+    which does not return): modes in the order of ``MODES``, each its own value first, then its ``refuses`` in order."""
+    on = {}
+    for cls in MODES:
+        try:
+            mode = cls.from_args(args)
+        except ValueError as exc:
+            error(str(exc))
+        if mode is None:
+            continue
+        for other, reason in cls.refuses:
+            if other in on or (other == SHARD_SITES and args.shard == "sites"):
+                error(cls.refusal(other, reason))
+        on[cls.flag] = mode
+    return list(on.values())

@@ -175,11 +175,6 @@ def build_info(path: Optional[str] = None) -> Dict[str, object]:
     return json.loads(load_library(path).pf_build_info().decode())
 
 
-def _u8(a: np.ndarray) -> np.ndarray:
-    a = np.ascontiguousarray(a, dtype=np.uint8)
-    return a
-
-
 class Engine:
     """One handle = one GPU + one stream + one set of prepared weights."""
 
@@ -258,16 +253,39 @@ class Engine:
         return d.value, b.value, v.value
 
     # -- forward ----------------------------------------------------------------------------
-    def forward(self, idx: np.ndarray) -> np.ndarray:
-        """``uint8[B, N, L]`` (or ``[N, L]``) → ``float32[B, P]`` (or ``[P]``)."""
-        idx = _u8(idx)
+    @staticmethod
+    def _sources(idx: np.ndarray, refuse_single: bool = True):
+        """``uint8[B, N, L]`` (or ``[N, L]``) as contiguous ``[B, N, L]`` bytes, and whether to drop ``B`` again."""
+        idx = np.ascontiguousarray(idx, dtype=np.uint8)
         single = idx.ndim == 2
         if single:
             idx = idx[None]
         if idx.ndim != 3:
             raise ValueError(f"idx must be [B, N, L] or [N, L], got shape {idx.shape}")
+        if refuse_single:
+            _refuse_single_sequence(idx.shape[0], idx.shape[1])
+        return idx, single
+
+    @staticmethod
+    def _table(tab, what: str, entry: str, bound: int) -> np.ndarray:
+        """An integer table (``what``: its name and shape) as contiguous int32; an ``entry`` that int32 cannot hold is
+        outside ``[0, bound)`` before the library sees it."""
+        tab = np.asarray(tab)
+        if tab.ndim != 2 or tab.dtype.kind not in "iu":
+            raise ValueError(f"{what}, got {tab.dtype} {tab.shape}")
+        if tab.size and (tab.min() < -2 ** 31 or tab.max() >= 2 ** 31):
+            raise ValueError(f"{entry} {int(tab.max() if tab.max() >= 2 ** 31 else tab.min())} is outside [0, {bound})")
+        return np.ascontiguousarray(tab, dtype=np.int32)
+
+    @staticmethod
+    def _seed(seed: int) -> int:
+        """Any Python int as the ``uint64_t`` seed of the replicate stream."""
+        return int(seed) & 0xFFFFFFFFFFFFFFFF
+
+    def forward(self, idx: np.ndarray) -> np.ndarray:
+        """``uint8[B, N, L]`` (or ``[N, L]``) → ``float32[B, P]`` (or ``[P]``)."""
+        idx, single = self._sources(idx)
         B, N, L = idx.shape
-        _refuse_single_sequence(B, N)
         out = np.empty((B, N * (N - 1) // 2), dtype=np.float32)
         self._check(self._lib.pf_forward(self._h, idx.ctypes.data, B, N, L, out.ctypes.data))
         return out[0] if single else out
@@ -276,17 +294,11 @@ class Engine:
         """Distances of ``replicates`` site-bootstrap replicates (``pf_bootstrap``): ``uint8[B, N, L]`` →
         ``float32[B, R, P]`` (``[N, L]`` → ``[R, P]``).  Replicate ``r`` of an alignment is
         ``idx[..., bootstrap.resample_sites(L, R, seed)[r]]``; its distances are ``forward`` of those bytes, bit for bit."""
-        idx = _u8(idx)
-        single = idx.ndim == 2
-        if single:
-            idx = idx[None]
-        if idx.ndim != 3:
-            raise ValueError(f"idx must be [B, N, L] or [N, L], got shape {idx.shape}")
+        idx, single = self._sources(idx)
         B, N, L = idx.shape
-        _refuse_single_sequence(B, N)
         R = int(replicates)
         out = np.empty((B, max(R, 0), N * (N - 1) // 2), dtype=np.float32)
-        self._check(self._lib.pf_bootstrap(self._h, idx.ctypes.data, B, N, L, R, int(seed) & 0xFFFFFFFFFFFFFFFF,
+        self._check(self._lib.pf_bootstrap(self._h, idx.ctypes.data, B, N, L, R, self._seed(seed),
                                            out.ctypes.data if out.size else None))
         return out[0] if single else out
 
@@ -294,17 +306,7 @@ class Engine:
         """``pf_resample_sites_device``: replicates ``r_begin .. r_begin + R - 1`` of ``d_src [B][N][L]`` into
         ``d_dst [B][R][N][L]`` (device buffers, asynchronous on the handle's stream)."""
         self._check(self._lib.pf_resample_sites_device(self._h, C.c_void_p(d_src), B, N, L, r_begin, R,
-                                                       int(seed) & 0xFFFFFFFFFFFFFFFF, C.c_void_p(d_dst)))
-
-    def _sources(self, idx: np.ndarray):
-        idx = _u8(idx)
-        single = idx.ndim == 2
-        if single:
-            idx = idx[None]
-        if idx.ndim != 3:
-            raise ValueError(f"idx must be [B, N, L] or [N, L], got shape {idx.shape}")
-        _refuse_single_sequence(idx.shape[0], idx.shape[1])
-        return idx, single
+                                                       self._seed(seed), C.c_void_p(d_dst)))
 
     def forward_sites(self, idx: np.ndarray, sites: np.ndarray) -> np.ndarray:
         """Distances of the alignments cut out of ``idx`` by a site table (``pf_forward_sites``): ``uint8[B, N, L]``,
@@ -312,12 +314,7 @@ class Engine:
         ``idx[b][:, sites[s]]`` (``windows.cut_sites``), bit for bit; entries outside ``[0, L)`` raise ``ValueError``."""
         idx, single = self._sources(idx)
         B, N, L = idx.shape
-        tab = np.asarray(sites)
-        if tab.ndim != 2 or tab.dtype.kind not in "iu":
-            raise ValueError(f"sites must be an integer array [S, K], got {tab.dtype} {tab.shape}")
-        if tab.size and (tab.min() < -2 ** 31 or tab.max() >= 2 ** 31):
-            raise ValueError(f"site {int(tab.max() if tab.max() >= 2 ** 31 else tab.min())} is outside [0, {L})")
-        tab = np.ascontiguousarray(tab, dtype=np.int32)
+        tab = self._table(sites, "sites must be an integer array [S, K]", "site", L)
         S, K = tab.shape
         out = np.empty((B, S, N * (N - 1) // 2), dtype=np.float32)
         self._check(self._lib.pf_forward_sites(self._h, idx.ctypes.data, B, N, L, tab.ctypes.data if tab.size else None,
@@ -399,12 +396,7 @@ class Engine:
         fn = self._optional("pf_forward_taxa")
         idx, single = self._sources(idx)
         B, N, L = idx.shape
-        tab = np.asarray(taxa)
-        if tab.ndim != 2 or tab.dtype.kind not in "iu":
-            raise ValueError(f"taxa must be an integer array [S, M], got {tab.dtype} {tab.shape}")
-        if tab.size and (tab.min() < -2 ** 31 or tab.max() >= 2 ** 31):
-            raise ValueError(f"taxon {int(tab.max() if tab.max() >= 2 ** 31 else tab.min())} is outside [0, {N})")
-        tab = np.ascontiguousarray(tab, dtype=np.int32)
+        tab = self._table(taxa, "taxa must be an integer array [S, M]", "taxon", N)
         S, M = tab.shape
         out = np.empty((B, S, max(M, 0) * max(M - 1, 0) // 2), dtype=np.float32)
         self._check(fn(self._h, idx.ctypes.data, B, N, L, tab.ctypes.data if tab.size else None, S, M,
@@ -476,12 +468,7 @@ class Engine:
         fn = self._optional("pf_forward_sites_weighted")
         idx, single = self._sources(idx)
         B, N, L = idx.shape
-        tab = np.asarray(sites)
-        if tab.ndim != 2 or tab.dtype.kind not in "iu":
-            raise ValueError(f"sites must be an integer array [S, K], got {tab.dtype} {tab.shape}")
-        if tab.size and (tab.min() < -2 ** 31 or tab.max() >= 2 ** 31):
-            raise ValueError(f"site {int(tab.max() if tab.max() >= 2 ** 31 else tab.min())} is outside [0, {L})")
-        tab = np.ascontiguousarray(tab, dtype=np.int32)
+        tab = self._table(sites, "sites must be an integer array [S, K]", "site", L)
         S, K = tab.shape
         w = self._weights(weights, (S, K), "weights")
         out = np.empty((B, S, N * (N - 1) // 2), dtype=np.float32)
@@ -498,18 +485,14 @@ class Engine:
         B, N, L = idx.shape
         R = int(replicates)
         out = np.empty((B, max(R, 0), N * (N - 1) // 2), dtype=np.float32)
-        self._check(fn(self._h, idx.ctypes.data, B, N, L, R, int(seed) & 0xFFFFFFFFFFFFFFFF,
+        self._check(fn(self._h, idx.ctypes.data, B, N, L, R, self._seed(seed),
                        out.ctypes.data if out.size else None))
         return out[0] if single else out
 
     def forward_sharded(self, idx_local: np.ndarray, l_begin: int, l_end: int, L_total: int) -> np.ndarray:
         """This rank's sites ``[l_begin, l_end)`` of ``uint8[B, N, L_total]`` alignments."""
-        idx = _u8(idx_local)
-        single = idx.ndim == 2
-        if single:
-            idx = idx[None]
+        idx, single = self._sources(idx_local)
         B, N, Ll = idx.shape
-        _refuse_single_sequence(B, N)
         if Ll != l_end - l_begin:
             raise ValueError(f"idx has {Ll} sites, expected {l_end - l_begin}")
         out = np.empty((B, N * (N - 1) // 2), dtype=np.float32)
@@ -519,10 +502,7 @@ class Engine:
 
     def forward_shards_emulated(self, idx: np.ndarray, nshards: int) -> np.ndarray:
         """Site-sharded algorithm over ``nshards`` emulated ranks on this one GPU (tests)."""
-        idx = _u8(idx)
-        single = idx.ndim == 2
-        if single:
-            idx = idx[None]
+        idx, single = self._sources(idx, refuse_single=False)      # (N = 1 is the library's PF_EINVAL here)
         B, N, L = idx.shape
         out = np.empty((B, N * (N - 1) // 2), dtype=np.float32)
         self._check(self._lib.pf_forward_shards_emulated(self._h, idx.ctypes.data, B, N, L, nshards,

@@ -43,6 +43,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from .analyses import Analysis, sub_batches
+
 # one launch should carry about this many (pair, site) tokens: 16 alignments of 60 x 500
 # (3.6 GB of residual stream), the size bench.py measures the headline number at
 TOKEN_BUDGET = 16 * 1770 * 500
@@ -53,15 +55,6 @@ TOKEN_BUDGET = 16 * 1770 * 500
 FILES_PER_LOAD = 256
 # a partial shape bucket is launched after this many further load calls (bounds what the native pipeline keeps parsed)
 STALE_LOADS = 16
-# --bootstrap: replicate distances per pf_bootstrap call, in floats (16 MiB).  This bounds host memory, not GPU work:
-# the results wait in the writer queue (up to 8 x io_threads entries) until their supports are written, so the cap
-# keeps that queue to a few hundred MB even at 200 taxa (R = 100 x 19,900 floats = 8 MB per alignment).  The GPU stays
-# fed: one alignment's R = 100 replicates at 60 x 500 are already 6 x TOKEN_BUDGET, and pf_bootstrap chunks them itself.
-BOOT_FLOATS = 1 << 22
-# --windows: the same bound on the window distances of one pf_forward_windows call (pf_forward_windows chunks them itself)
-WINDOW_FLOATS = BOOT_FLOATS
-# --leave-one-out: the same bound on the distances of the cuts (N x P1 floats per alignment) of one pf_forward_leave_one_out call
-LOO_FLOATS = BOOT_FLOATS
 
 
 def auto_batch(n_seqs: int, n_sites: int, max_batch: int = 4096, token_budget: int = TOKEN_BUDGET) -> int:
@@ -97,6 +90,22 @@ def has_fasta_ext(alnpath: str) -> bool:
     return alnpath.lower().endswith(".fa") or alnpath.lower().endswith(".fasta")
 
 
+def non_fasta_entry(paths: Sequence[str]) -> Optional[Tuple[int, ValueError]]:
+    """``(k, error)`` of the first entry without a FASTA extension - the reference's ``ValueError`` for it
+    (infer_alns.py:100-103) - or None."""
+    for k, p in enumerate(paths):
+        if not has_fasta_ext(p):
+            return k, ValueError("Input files must be fasta files (.fa or .fasta). Got " f"{p}")
+    return None
+
+
+def require_fasta_entries(paths: Sequence[str]):
+    """The modes without a counterpart in the reference refuse such a directory up front."""
+    bad = non_fasta_entry(paths)
+    if bad is not None:
+        raise bad[1]
+
+
 def slice_paths(paths: Sequence[str], rank: int, world: int) -> List[str]:
     """Deterministic share of ``paths`` for worker ``rank`` of ``world``: files are sorted by
     (size, name) and dealt round-robin, so every worker sees the same mix of shapes."""
@@ -111,38 +120,46 @@ def slice_paths(paths: Sequence[str], rank: int, world: int) -> List[str]:
     return sorted(paths, key=key)[rank::world]
 
 
+class Entry:
+    """One alignment of a launch group: its file, what the launch batches - the parsed residues (``np.stack``) or, on the
+    native path, ``(FastaBatch, file)`` (``hostio.gather``; residues and ids stay in the library until the launch gathers
+    them / the writer formats them) - and its ids."""
+    __slots__ = ("path", "source", "_ids")
+
+    def __init__(self, path: str, source, ids: Optional[List[str]] = None):
+        self.path, self.source, self._ids = path, source, ids
+
+    def ids(self) -> List[str]:
+        return self.source[0].ids(self.source[1]) if self._ids is None else self._ids
+
+
 class DirectoryRunner:
     """Runs every alignment of a file list through the engine(s) and writes the outputs.
 
     ``engine`` may be one engine or a list: each engine gets its own host thread (one HIP stream each),
     so the host-side gaps of one synchronous ``pf_forward`` (index copy, result copy, Python between
-    calls) are filled by the other's kernels — measured 486 -> 501 alignments/s at 60 x 500 with two."""
+    calls) are filled by the other's kernels — measured 486 -> 501 alignments/s at 60 x 500 with two.
+
+    ``modes`` are the per-alignment analyses of the run (``analyses.Analysis`` instances): at most one of them replaces
+    the launch's forward, the others follow it."""
 
     def __init__(self, engine, out_dir: str, trees: bool = False, batch: int = 0,
-                 io_threads: int = 4, native_io: bool = True, progress=None, bootstrap: int = 0, seed: int = 0,
-                 windows: Optional[Tuple[int, int]] = None, site_profile: bool = False, leave_one_out: bool = False,
-                 compress_sites: bool = False):
+                 io_threads: int = 4, native_io: bool = True, progress=None, modes: Sequence[Analysis] = ()):
         self.engines = list(engine) if isinstance(engine, (list, tuple)) else [engine]
-        self.compress_sites = bool(compress_sites)   # --compress-sites: distinct columns with their counts as weights
         self.out_dir = out_dir
         self.trees = trees
         self.batch = batch            # 0 = auto per shape
         self.io_threads = max(1, io_threads)
         self.native_io = native_io
         self.progress = progress
-        self.bootstrap = max(0, int(bootstrap))   # replicates per alignment (0 = off): <stem>.sup.nwk
-        self.seed = int(seed)
         self.stats = {"alignments": 0, "launches": 0, "forward_s": 0.0, "load_wait_s": 0.0,
                       "write_wait_s": 0.0, "shapes": {}, "gpu_streams": len(self.engines)}
-        if self.bootstrap:
-            self.stats.update({"replicates": self.bootstrap, "bootstrap_s": 0.0})
-        self.windows = (int(windows[0]), int(windows[1])) if windows else None    # (W, step): the --windows scan
-        if self.windows:
-            self.stats.update({"windows": 0, "windows_s": 0.0})
-        self.site_profile = bool(site_profile)    # --site-profile: <stem>.sites.tsv, <stem>.se.phy
-        self.leave_one_out = bool(leave_one_out)  # --leave-one-out: <stem>.taxa.tsv, <stem>.context.phy
-        if self.leave_one_out:
-            self.stats.update({"loo_sets": 0})
+        self.modes = list(modes)
+        for m in self.modes:
+            m.bind(self.modes)
+            self.stats.update(m.stats())
+        self._forwarder = next((m for m in self.modes if m.forward is not None), None)
+        self._followers = [m for m in self.modes if m.follow is not None]
         self._lock = threading.Lock()
 
     # -- stages -----------------------------------------------------------------------------
@@ -153,251 +170,62 @@ class DirectoryRunner:
             from .fasta import load_alignment
         return load_alignment(path)
 
-    def _write(self, path: str, pred: np.ndarray, ids: List[str]):
-        stem = Path(path).stem
+    def phylip(self, vec: np.ndarray, ids: List[str]):
+        """The PHYLIP matrix of a distance vector: bytes from the native formatter, text from the Python one."""
         if self.native_io:
-            from .hostio import format_phylip, nj_newick
-            with open(os.path.join(self.out_dir, f"{stem}.phy"), "wb") as fh:
-                fh.write(format_phylip(pred, ids))
-            if self.trees:                         # (infer_alns.py:120-123)
-                with open(os.path.join(self.out_dir, f"{stem}.nj.nwk"), "wb") as fh:
-                    fh.write(nj_newick(pred, ids))
-            return
+            from .hostio import format_phylip
+            return format_phylip(vec, ids)
         from .phylip import vec_to_phylip
-        dm, text = vec_to_phylip(pred, ids)
-        with open(os.path.join(self.out_dir, f"{stem}.phy"), "w") as fh:
-            fh.write(text)
-        if self.trees:
-            from .nj import neighbor_joining
-            with open(os.path.join(self.out_dir, f"{stem}.nj.nwk"), "w") as fh:
-                fh.write(neighbor_joining(dm.astype("float64"), ids))
+        return vec_to_phylip(vec, ids)[1]
 
-    def _writer_cap(self) -> int:
+    def nj(self, vec: np.ndarray, ids: List[str]):
+        """The neighbour-joining tree of a distance vector, from the same side as ``phylip`` (infer_alns.py:120-123)."""
+        if self.native_io:
+            from .hostio import nj_newick
+            return nj_newick(vec, ids)
+        from .nj import neighbor_joining
+        from .phylip import vec_to_phylip
+        return neighbor_joining(vec_to_phylip(vec, ids)[0].astype("float64"), ids)
+
+    def out_path(self, path: str, suffix: str) -> str:
+        return os.path.join(self.out_dir, f"{Path(path).stem}.{suffix}")
+
+    def put(self, path: str, suffix: str, data):
+        """``<stem>.<suffix>`` of the input ``path``: bytes as they are, text through the locale's encoding."""
+        with open(self.out_path(path, suffix), "wb" if isinstance(data, bytes) else "w") as fh:
+            fh.write(data)
+
+    def _write(self, path: str, pred: np.ndarray, ids: List[str]):
+        self.put(path, "phy", self.phylip(pred, ids))
+        if self.trees:
+            self.put(path, "nj.nwk", self.nj(pred, ids))
+
+    def writer_cap(self) -> int:
         # (at most 4 threads: creating files in ONE directory from 8 / 16 threads is a lock convoy on the directory -
         # 4,096 outputs took 0.98 / 1.19 s instead of 0.01 s, profiles/r05c_cli_bench.txt.  The neighbour joining of
         # --trees rides on the same threads: 64 us per 20-taxon tree, 18 ms at 200 taxa, against 90 us / 22 ms of GPU time
         # per alignment.  PF_WRITER_THREADS moves the cap for experiments, profiles/r06r_cli_bench_overlay_writer_threads.txt.)
         return max(1, min(self.io_threads, int(os.environ.get("PF_WRITER_THREADS", "4"))))
 
-    def _support(self, path: str, pred: np.ndarray, reps: np.ndarray, ids: List[str]):
-        """``<stem>.sup.nwk`` (``--bootstrap``): the NJ tree of ``pred`` with the supports of ``reps``."""
-        out = os.path.join(self.out_dir, f"{Path(path).stem}.sup.nwk")
-        if self.native_io:
-            from .hostio import nj_support
-            with open(out, "wb") as fh:
-                fh.write(nj_support(pred, reps, ids, threads=self._writer_cap()))
-            return
-        from .bootstrap import support_newick_py
-        with open(out, "w") as fh:
-            fh.write(support_newick_py(pred, reps, ids))
+    def _write_native(self, n: int, group: list, preds: np.ndarray):
+        """``<stem>.phy`` - and with ``--trees`` ``<stem>.nj.nwk`` - of a whole launch: formatted (the trees: joined) and
+        written on native threads (infer_alns.py:105-123)."""
+        from .hostio import write_phylip
+        trees = [self.out_path(e.path, "nj.nwk") for e in group] if self.trees else None
+        write_phylip([e.source for e in group], n, preds, [self.out_path(e.path, "phy") for e in group],
+                     self.writer_cap(), trees)
 
-    def _support_native(self, group: list, preds: np.ndarray, reps: np.ndarray):
-        for (path, (fb, i), _none), pred, rep in zip(group, preds, reps):
-            self._support(path, pred, rep, fb.ids(i))
-
-    def _bootstrap(self, engine, shape: Tuple[int, int], group: list, batch: np.ndarray, preds: np.ndarray,
-                   writers: ThreadPoolExecutor, pending: deque, native: bool):
-        """Replicate distances of a launch group, in sub-batches of at most BOOT_FLOATS floats; their supports are
-        computed and written on the writer threads, like the trees."""
-        P = shape[0] * (shape[0] - 1) // 2
-        sub = max(1, BOOT_FLOATS // max(1, self.bootstrap * P))
-        for s0 in range(0, len(group), sub):
-            t0 = time.perf_counter()
-            boot = engine.bootstrap_weighted if self.compress_sites else engine.bootstrap
-            reps = boot(batch[s0:s0 + sub], self.bootstrap, self.seed)
-            dt = time.perf_counter() - t0
-            part = group[s0:s0 + sub]
-            with self._lock:
-                self.stats["bootstrap_s"] += dt
-                if native:
-                    pending.append(writers.submit(self._support_native, part, preds[s0:s0 + sub], reps))
-                else:
-                    for (path, _idx, ids), pred, rep in zip(part, preds[s0:s0 + sub], reps):
-                        pending.append(writers.submit(self._support, path, pred, rep, ids))
-
-    # -- --windows W[:STEP] -------------------------------------------------------------------
-    def _window_error(self, path: str, n_sites: int) -> Optional[Exception]:
-        """A file shorter than the window is an error for that file, raised where the loop reaches it."""
-        if self.windows and n_sites < self.windows[0]:
-            return ValueError(f"--windows: {path} has L = {n_sites} sites, fewer than the window width W = {self.windows[0]}")
-        return None
-
-    def _window_paths(self, path: str, n_sites: int, starts: Sequence[int], ext: str) -> List[str]:
-        from .windows import window_label
-        stem = Path(path).stem
-        return [os.path.join(self.out_dir, f"{stem}.{window_label(n_sites, st, self.windows[0])}.{ext}") for st in starts]
-
-    def _window_table(self, path: str, starts: Sequence[int], wpred: np.ndarray, wtrees: Sequence[str], full_tree: str):
-        from .windows import summary_tsv
-        with open(os.path.join(self.out_dir, f"{Path(path).stem}.windows.tsv"), "w") as fh:
-            fh.write(summary_tsv(starts, self.windows[0], wpred, wtrees, full_tree))
-
-    def _write_windows(self, path: str, n_sites: int, starts: Sequence[int], pred: np.ndarray, wpred: np.ndarray,
-                       ids: List[str]):
-        """One file's window outputs through the Python writers: ``<stem>.w<first>-<last>.phy`` (``.nj.nwk`` with
-        ``--trees``) per window and ``<stem>.windows.tsv``."""
-        from .nj import neighbor_joining
-        from .phylip import vec_to_phylip
-        wtrees = []
-        for out, tree, wp in zip(self._window_paths(path, n_sites, starts, "phy"),
-                                 self._window_paths(path, n_sites, starts, "nj.nwk"), wpred):
-            dm, text = vec_to_phylip(wp, ids)
-            with open(out, "w") as fh:
-                fh.write(text)
-            wtrees.append(neighbor_joining(dm.astype("float64"), ids))
-            if self.trees:
-                with open(tree, "w") as fh:
-                    fh.write(wtrees[-1])
-        dm, _text = vec_to_phylip(pred, ids)
-        self._window_table(path, starts, wpred, wtrees, neighbor_joining(dm.astype("float64"), ids))
-
-    def _write_windows_native(self, n: int, n_sites: int, starts: Sequence[int], part: list, preds: np.ndarray,
-                              wpreds: np.ndarray):
-        """The same files for a sub-batch: the window matrices (and trees) of all its files in one native call, the
-        tables from the native neighbour joining."""
-        from .hostio import nj_newick, write_phylip
-        entries = [g[1] for g in part for _ in starts]
-        outs = [q for g in part for q in self._window_paths(g[0], n_sites, starts, "phy")]
-        trees = [q for g in part for q in self._window_paths(g[0], n_sites, starts, "nj.nwk")] if self.trees else None
-        write_phylip(entries, n, wpreds.reshape(len(entries), -1), outs, self._writer_cap(), trees)
-        for (path, (fb, i), _none), pred, wp in zip(part, preds, wpreds):
-            ids = fb.ids(i)
-            self._window_table(path, starts, wp, [nj_newick(w, ids).decode("utf8") for w in wp],
-                               nj_newick(pred, ids).decode("utf8"))
-
-    def _windows(self, engine, shape: Tuple[int, int], group: list, batch: np.ndarray, preds: np.ndarray,
-                 writers: ThreadPoolExecutor, pending: deque, native: bool):
-        """Window distances of a launch group (``pf_forward_windows``: the sources go up once, the windows are cut on
-        the device), in sub-batches of at most WINDOW_FLOATS floats; written on the writer threads."""
-        from .windows import window_starts
-        W, step = self.windows
-        starts = window_starts(shape[1], W, step)
-        P = shape[0] * (shape[0] - 1) // 2
-        sub = max(1, WINDOW_FLOATS // max(1, len(starts) * P))
-        for s0 in range(0, len(group), sub):
-            t0 = time.perf_counter()
-            wp = engine.forward_windows(batch[s0:s0 + sub], W, step)
-            dt = time.perf_counter() - t0
-            part = group[s0:s0 + sub]
-            with self._lock:
-                self.stats["windows_s"] += dt
-                self.stats["windows"] += len(part) * len(starts)
-                if native:
-                    pending.append(writers.submit(self._write_windows_native, shape[0], shape[1], starts, part,
-                                                  preds[s0:s0 + sub], wp))
-                else:
-                    for (path, _idx, ids), pred, w in zip(part, preds[s0:s0 + sub], wp):
-                        pending.append(writers.submit(self._write_windows, path, shape[1], starts, pred, w, ids))
-
-    # -- --site-profile ---------------------------------------------------------------------
-    def _write_site_profile(self, path: str, se: np.ndarray, profile: np.ndarray, ids: List[str]):
-        """``<stem>.sites.tsv`` and ``<stem>.se.phy`` of one file (ids and number format of ``<stem>.phy``)."""
-        from .siteprofile import se_phylip, sites_tsv
-        stem = Path(path).stem
-        with open(os.path.join(self.out_dir, f"{stem}.sites.tsv"), "w") as fh:
-            fh.write(sites_tsv(profile))
-        if self.native_io:
-            from .hostio import format_phylip
-            with open(os.path.join(self.out_dir, f"{stem}.se.phy"), "wb") as fh:
-                fh.write(format_phylip(se, ids))
-            return
-        with open(os.path.join(self.out_dir, f"{stem}.se.phy"), "w") as fh:
-            fh.write(se_phylip(se, ids))
-
-    def _write_site_profile_native(self, group: list, ses: np.ndarray, profiles: np.ndarray):
-        for (path, (fb, i), _none), se, prof in zip(group, ses, profiles):
-            self._write_site_profile(path, se, prof, fb.ids(i))
-
-    # -- --leave-one-out --------------------------------------------------------------------
-    def _loo_error(self, path: str, n_seqs: int) -> Optional[Exception]:
-        """A file with fewer than 3 sequences has no leave-one-out cut with a pair: an error for that file, raised where
-        the loop reaches it."""
-        if self.leave_one_out and n_seqs < 3:
-            return ValueError(f"--leave-one-out: {path} has N = {n_seqs} sequences, fewer than the 3 a cut with one pair needs")
-        return None
-
-    def _forward_loo(self, engine, shape: Tuple[int, int], batch: np.ndarray):
-        """``forward_leave_one_out`` of a launch group in sub-batches of at most LOO_FLOATS distances of cuts; the cuts'
-        distances are kept only for the trees of ``rf_pruned`` (``--trees``)."""
-        N = shape[0]
-        sub = max(1, LOO_FLOATS // max(1, N * (N - 1) * (N - 2) // 2))
-        parts = [engine.forward_leave_one_out(batch[s0:s0 + sub], keep_loo=self.trees) for s0 in range(0, len(batch), sub)]
-        return [np.concatenate([p[k] for p in parts]) for k in range(len(parts[0]))]
-
-    def _write_taxa(self, path: str, pred: np.ndarray, infl: np.ndarray, shift: np.ndarray, ctx: np.ndarray,
-                    loo: Optional[np.ndarray], ids: List[str]):
-        """``<stem>.taxa.tsv`` and ``<stem>.context.phy`` of one file (ids and number format of ``<stem>.phy``); with
-        ``--trees`` the column ``rf_pruned`` from NJ trees on index labels."""
-        from .taxa import context_phylip, rf_pruned, taxa_tsv
-        stem, N = Path(path).stem, len(ids)
-        rf = None
-        if self.trees:
-            labels = [str(k) for k in range(N)]
-            if N - 1 < 4:
-                rf = ["NA"] * N
-            else:
-                if self.native_io:
-                    from .hostio import nj_newick
-
-                    def nj(vec, names):
-                        return nj_newick(vec, names).decode("utf8")
-                else:
-                    from .nj import neighbor_joining
-                    from .phylip import vec_to_phylip
-
-                    def nj(vec, names):
-                        return neighbor_joining(vec_to_phylip(vec, names)[0].astype("float64"), names)
-                rf = rf_pruned(nj(pred, labels), [nj(loo[t], labels[:t] + labels[t + 1:]) for t in range(N)], N)
-        with open(os.path.join(self.out_dir, f"{stem}.taxa.tsv"), "w") as fh:
-            fh.write(taxa_tsv(ids, infl, shift, rf))
-        if self.native_io:
-            from .hostio import format_phylip
-            with open(os.path.join(self.out_dir, f"{stem}.context.phy"), "wb") as fh:
-                fh.write(format_phylip(ctx, ids))
-            return
-        with open(os.path.join(self.out_dir, f"{stem}.context.phy"), "w") as fh:
-            fh.write(context_phylip(ctx, ids))
-
-    def _write_taxa_native(self, group: list, preds, infls, shifts, ctxs, loos):
-        for k, (path, (fb, i), _none) in enumerate(group):
-            self._write_taxa(path, preds[k], infls[k], shifts[k], ctxs[k], None if loos is None else loos[k], fb.ids(i))
-
-    def _forward_compressed(self, engine, batch: np.ndarray) -> np.ndarray:
-        """``--compress-sites``: every alignment as its distinct columns with their counts as weights, padded to
-        ``padded_sites`` of its own count (site 0, weight 0).  Alignments of one padded size share a launch; a file's
-        distances depend on the file alone."""
-        from . import weights_sites as ws
-        compress = ws.native_compress_sites if self.native_io else ws.compress_sites
-        B, N, L = batch.shape
-        tables = [ws.pad_table(f, c, ws.padded_sites(len(f), L)) for f, c in (compress(a) for a in batch)]
-        preds = np.empty((B, N * (N - 1) // 2), dtype=np.float32)
-        for kp in sorted({len(s) for s, _w in tables}):
-            who = [b for b in range(B) if len(tables[b][0]) == kp]
-            cut = np.stack([batch[b][:, tables[b][0]] for b in who])
-            preds[who] = engine.forward_weighted(cut, np.stack([tables[b][1] for b in who]))
-        return preds
-
-    def _launch(self, engine, shape: Tuple[int, int], group: list, writers: ThreadPoolExecutor, pending: deque):
-        native = group[0][2] is None              # entries of _feed_native: (path, (FastaBatch, file), None)
+    def _launch(self, engine, shape: Tuple[int, int], group: List[Entry], writers: ThreadPoolExecutor, pending: deque):
+        def submit(jobs):
+            pending.extend(writers.submit(*job) for job in jobs)
         t0 = time.perf_counter()
-        if native:
+        if self.native_io:
             from .hostio import gather
-            batch = gather([g[1] for g in group], shape[0], shape[1])
+            batch = gather([e.source for e in group], shape[0], shape[1])
         else:
-            batch = np.stack([g[1] for g in group])
-        if self.site_profile:
-            # the same forward (its distances are forward's, bit for bit) also leaves se and the site profile
-            preds, ses, profiles = engine.forward_site_profile(batch)
-        elif self.leave_one_out:
-            # the same distances (forward's, bit for bit), then the N cuts of every alignment and their statistics
-            preds, infls, shifts, ctxs, *loos = self._forward_loo(engine, shape, batch)
-            loos = loos[0] if loos else None
-        elif self.compress_sites and not self.bootstrap:
-            # (with --bootstrap the whole alignment keeps forward's bits - <stem>.phy, the tree and its branch lengths in
-            # <stem>.sup.nwk are those of a run without the flag - and the R replicates, the cost, run compressed)
-            preds = self._forward_compressed(engine, batch)
-        else:
-            preds = engine.forward(batch)
+            batch = np.stack([e.source for e in group])
+        mode = self._forwarder
+        preds, payload = mode.forward(self, engine, shape, batch) if mode else (engine.forward(batch), ())
         dt = time.perf_counter() - t0
         with self._lock:
             self.stats["forward_s"] += dt
@@ -405,51 +233,38 @@ class DirectoryRunner:
             self.stats["alignments"] += len(group)
             key = f"{shape[0]}x{shape[1]}"
             self.stats["shapes"][key] = self.stats["shapes"].get(key, 0) + len(group)
-            if native:
-                pending.append(writers.submit(self._write_native, shape[0], group, preds))
+            if self.native_io:
+                submit([(self._write_native, shape[0], group, preds)])
             else:
-                for (path, _idx, ids), pred in zip(group, preds):
-                    pending.append(writers.submit(self._write, path, pred, ids))
-            if self.site_profile:
-                if native:
-                    pending.append(writers.submit(self._write_site_profile_native, group, ses, profiles))
-                else:
-                    for (path, _idx, ids), se, prof in zip(group, ses, profiles):
-                        pending.append(writers.submit(self._write_site_profile, path, se, prof, ids))
-            if self.leave_one_out:
-                self.stats["loo_sets"] += len(group) * shape[0]
-                if native:
-                    pending.append(writers.submit(self._write_taxa_native, group, preds, infls, shifts, ctxs, loos))
-                else:
-                    for k, (path, _idx, ids) in enumerate(group):
-                        pending.append(writers.submit(self._write_taxa, path, preds[k], infls[k], shifts[k], ctxs[k],
-                                                      None if loos is None else loos[k], ids))
-            if self.progress is not None and not self.bootstrap and not self.windows:
+                submit([(self._write, e.path, pred, e.ids()) for e, pred in zip(group, preds)])
+            if mode:
+                mode.account(self.stats, len(group), shape, dt)
+                if payload:
+                    submit(mode.jobs(self, shape, group, preds, *payload))
+            if self.progress is not None and not self._followers:
                 self.progress(len(group))
-        if self.bootstrap:
-            self._bootstrap(engine, shape, group, batch, preds, writers, pending, native)
-        if self.windows:
-            self._windows(engine, shape, group, batch, preds, writers, pending, native)
-        if self.progress is not None and (self.bootstrap or self.windows):
+        # the modes behind the forward, in sub-batches; their outputs are computed and written on the writer threads
+        for mode in self._followers:
+            for s in sub_batches(len(group), mode.floats(shape)):
+                t0 = time.perf_counter()
+                res = mode.follow(engine, batch[s])
+                dt = time.perf_counter() - t0
+                with self._lock:
+                    mode.account(self.stats, len(group[s]), shape, dt)
+                    submit(mode.jobs(self, shape, group[s], preds[s], res))
+        if self.progress is not None and self._followers:
             self.progress(len(group))
         with self._lock:
             drain = []
             # bound the write queue so results do not pile up in memory
-            while len(pending) > 8 * self.io_threads + (1 if native else len(group)) * (2 if self.bootstrap or self.windows or self.site_profile or self.leave_one_out else 1):
+            room = (1 if self.native_io else len(group)) * (2 if any(m.write for m in self.modes) else 1)
+            while len(pending) > 8 * self.io_threads + room:
                 drain.append(pending.popleft())
         t0 = time.perf_counter()
         for f in drain:
             f.result()
         with self._lock:
             self.stats["write_wait_s"] += time.perf_counter() - t0
-
-    def _write_native(self, n: int, group: list, preds: np.ndarray):
-        """``<stem>.phy`` - and with ``--trees`` ``<stem>.nj.nwk`` - of a whole launch: formatted (the trees: joined) and
-        written on native threads (infer_alns.py:105-123)."""
-        from .hostio import write_phylip
-        outs = [os.path.join(self.out_dir, f"{Path(g[0]).stem}.phy") for g in group]
-        trees = [os.path.join(self.out_dir, f"{Path(g[0]).stem}.nj.nwk") for g in group] if self.trees else None
-        write_phylip([g[1] for g in group], n, preds, outs, self._writer_cap(), trees)
 
     def _gpu_worker(self, engine, jobs: "queue.Queue", writers, pending, errors: list):
         while True:
@@ -472,11 +287,9 @@ class DirectoryRunner:
         behind it is; then the exception is raised."""
         paths = list(paths)
         deferred: Optional[BaseException] = None
-        for k, p in enumerate(paths):
-            if not has_fasta_ext(p):
-                deferred = ValueError("Input files must be fasta files (.fa or .fasta). Got " f"{p}")
-                paths = paths[:k]
-                break
+        bad_entry = non_fasta_entry(paths)
+        if bad_entry is not None:
+            paths, deferred = paths[:bad_entry[0]], bad_entry[1]
         t_start = time.perf_counter()
         pending: deque = deque()
         errors: list = []
@@ -506,6 +319,15 @@ class DirectoryRunner:
         if deferred is not None:
             raise deferred
         return self.stats
+
+    def _file_error(self, path: str, n_seqs: int, n_sites: int) -> Optional[Exception]:
+        """Why a parsed file cannot be run, if it cannot: the reference's own limits, then the modes' (``accepts``); an
+        error for that file, raised where the loop reaches it."""
+        bad = too_many_seqs(n_seqs)
+        for m in self.modes:
+            if bad is None and not m.accepts(n_seqs, n_sites):
+                bad = m.file_error(path, n_seqs, n_sites)
+        return bad
 
     def _feed_python(self, paths, loaders, jobs, errors) -> Optional[BaseException]:
         """One future per file (``--python-io``, ``-t``): parse ahead, bucket by shape, launch full buckets."""
@@ -537,13 +359,13 @@ class DirectoryRunner:
             finally:
                 self.stats["load_wait_s"] += time.perf_counter() - t0
             shape = (int(idx.shape[0]), int(idx.shape[1]))
-            bad = too_many_seqs(shape[0]) or self._window_error(path, shape[1]) or self._loo_error(path, shape[0])
+            bad = self._file_error(path, *shape)
             if bad is not None:
                 for _p, f in inflight:
                     f.cancel()
                 break
             group = buckets.setdefault(shape, [])
-            group.append((path, idx, ids))
+            group.append(Entry(path, idx, ids))
             if len(group) >= (self.batch or auto_batch(*shape)):
                 jobs.put((shape, group))
                 buckets[shape] = []
@@ -554,8 +376,7 @@ class DirectoryRunner:
 
     def _feed_native(self, paths, loaders, jobs, errors) -> Optional[BaseException]:
         """The fast path: ``FILES_PER_LOAD`` files per native call (read + parsed on ``io_threads`` std::threads,
-        no GIL), two calls in flight ahead of the bucketing; a bucket entry is ``(path, (batch, file), None)``
-        - residues and ids stay in the library until the launch gathers them / the writer formats them."""
+        no GIL), two calls in flight ahead of the bucketing; a bucket entry points into its ``FastaBatch``."""
         from .hostio import FastaBatch
         buckets: "OrderedDict[Tuple[int, int], list]" = OrderedDict()
         born: Dict[Tuple[int, int], int] = {}          # load call that opened each partial bucket
@@ -574,15 +395,11 @@ class DirectoryRunner:
             fb = inflight.popleft().result()
             self.stats["load_wait_s"] += time.perf_counter() - t0
             ok = (fb.status == 0) & (fb.l > 0) & (fb.n <= MAX_SEQS) & (fb.n != 1)
-            if self.windows:
-                ok &= fb.l >= self.windows[0]
-            if self.leave_one_out:
-                ok &= fb.n >= 3
+            for m in self.modes:
+                ok &= m.accepts(fb.n, fb.l)
             stop = len(fb) if ok.all() else int(np.argmin(ok))
             if stop < len(fb):
-                bad = (fb.error(stop) or too_many_seqs(int(fb.n[stop])) or
-                       self._window_error(fb.paths[stop], int(fb.l[stop])) or
-                       self._loo_error(fb.paths[stop], int(fb.n[stop])))
+                bad = fb.error(stop) or self._file_error(fb.paths[stop], int(fb.n[stop]), int(fb.l[stop]))
             ns, ls = fb.n.tolist(), fb.l.tolist()
             for i in range(stop):
                 shape = (ns[i], ls[i])
@@ -590,7 +407,7 @@ class DirectoryRunner:
                 if not group:
                     group = buckets[shape] = []
                     born[shape] = done
-                group.append((fb.paths[i], (fb, i), None))
+                group.append(Entry(fb.paths[i], (fb, i)))
                 if len(group) >= (self.batch or auto_batch(*shape)):
                     jobs.put((shape, group))
                     buckets[shape] = []
@@ -668,9 +485,7 @@ class SiteShardedRunner(DirectoryRunner):
         self._beat()
 
     def run(self, paths: Sequence[str]) -> dict:
-        for p in paths:
-            if not has_fasta_ext(p):
-                raise ValueError("Input files must be fasta files (.fa or .fasta). Got " f"{p}")
+        require_fasta_entries(paths)
         paths = sorted(paths)
         t_start = time.perf_counter()
         buckets: "OrderedDict[Tuple[int, int], list]" = OrderedDict()

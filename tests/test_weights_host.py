@@ -163,3 +163,79 @@ def test_oracle_gives_duplicated_sites_equal_logits(tips):
     diff = float(np.abs(logits[:, 20] - logits[:, -1]).max())
     print(f"oracle: logits of the two copies of a constant column differ by {diff:.3e} (|logit| up to {np.abs(logits).max():.2f})")
     assert diff <= 64 * np.finfo(np.float64).eps * max(1.0, float(np.abs(logits).max()))
+
+
+# ---- infer_alns.py --compress-sites through the oracle engine (no GPU) -----------------------------------------------
+
+@pytest.fixture(scope="module")
+def repeated_alns():
+    """Three small alignments whose columns repeat: 20 and 36 distinct columns among 40 sites (padded tables of 32 and
+    of L = 40 entries in ONE shape bucket) and 12 among 33."""
+    from phyloformer_amd.msa_sim import simulate_batch
+    rng = np.random.default_rng(16)
+    out, padded = {}, {}
+    for stem, (n, sites, distinct, seed) in {"r0": (6, 40, 20, 161), "r1": (6, 40, 36, 175), "r2": (8, 33, 12, 163)}.items():
+        cols = simulate_batch(1, n, distinct, seed=seed)[0]
+        pick = np.concatenate([np.arange(distinct), rng.integers(0, distinct, sites - distinct)])
+        out[stem] = np.ascontiguousarray(cols[:, rng.permutation(pick)])
+        padded[stem] = ws.padded_sites(len(ws.compress_sites(out[stem])[0]), sites)
+    assert padded == {"r0": 32, "r1": 40, "r2": 32}
+    return out
+
+
+def _cli(args, tmp_path):
+    import subprocess
+    import sys
+    env = dict(os.environ, PF_CLI_ENGINE_FACTORY="helpers.oracle_weights_engine:make", TMPDIR=str(tmp_path))
+    env["PYTHONPATH"] = os.pathsep.join([os.path.join(REPO, "tests"), REPO, env.get("PYTHONPATH", "")])
+    return subprocess.run([sys.executable, os.path.join(REPO, "infer_alns.py"), os.path.join(REPO, "models", "pf.ckpt"),
+                           *args], capture_output=True, text=True, cwd=REPO, env=env, timeout=900)
+
+
+def _files(d):
+    return {n: (d / n).read_bytes() for n in sorted(os.listdir(d))}
+
+
+def _upper(data, N):
+    m = np.array([[float(v) for v in row.split()[-N:]] for row in data.decode().splitlines()[1:]])
+    return m[np.triu_indices(N, k=1)]
+
+
+def test_cli_compress_sites_files(repeated_alns, tmp_path, weights):
+    """``--compress-sites`` writes the files of a plain run; native and Python I/O agree byte for byte; the distances
+    are the plain run's to the oracle's own float32 rounding.  The bound: the compressed run forwards the columns in
+    another order (distinct columns in order of first occurrence, each repeated by its count), which the float64 oracle
+    does not notice beyond 64 eps (test_oracle_does_not_know_a_sites_position), so the two float32 results differ by no
+    more than their own distances to the float64 oracle, plus the two files' 10 decimals."""
+    from phyloformer_amd.msa_sim import to_fasta
+    src = tmp_path / "in"
+    src.mkdir()
+    for stem, a in repeated_alns.items():
+        (src / f"{stem}.fa").write_text(to_fasta(a))
+    plain = _cli([str(src), "-o", str(tmp_path / "plain"), "-t"], tmp_path)
+    comp = _cli([str(src), "-o", str(tmp_path / "comp"), "-t", "--compress-sites"], tmp_path)
+    assert plain.returncode == 0 and comp.returncode == 0, plain.stderr[-2000:] + comp.stderr[-3000:]
+    base, files = _files(tmp_path / "plain"), _files(tmp_path / "comp")
+    assert set(files) == set(base) == {f"{s}.{x}" for s in repeated_alns for x in ("phy", "nj.nwk")}
+    w = weights("pf").tensors
+    for stem, a in repeated_alns.items():
+        first, count = ws.compress_sites(a)
+        c = ws.expand(a[:, first], count)                  # what the compressed forward stands for
+        assert c.shape == a.shape
+        a32, a64, c32, c64 = (O.forward(w, x, dtype=dt) for x in (a, c) for dt in (np.float32, np.float64))
+        bound = (float(np.abs(a32 - a64).max()) + float(np.abs(c32 - c64).max())
+                 + 64 * np.finfo(np.float64).eps * max(1.0, float(a64.max())) + 1e-10)
+        diff = float(np.abs(_upper(files[f"{stem}.phy"], len(a)) - _upper(base[f"{stem}.phy"], len(a))).max())
+        print(f"{stem}: --compress-sites vs plain {diff:.3e}, the oracle's float32 rounding allows {bound:.3e}")
+        assert diff <= bound, (stem, diff, bound)
+    p = _cli([str(src), "-o", str(tmp_path / "pyio"), "-t", "--compress-sites", "--python-io"], tmp_path)
+    assert p.returncode == 0, p.stderr[-3000:]
+    assert _files(tmp_path / "pyio") == files
+    # with --bootstrap the alignment itself is forwarded as without the flag; one support tree per input
+    b = _cli([str(src), "-o", str(tmp_path / "boot"), "--bootstrap", "4", "--compress-sites"], tmp_path)
+    assert b.returncode == 0, b.stderr[-3000:]
+    boot = _files(tmp_path / "boot")
+    assert set(boot) == {f"{s}.{x}" for s in repeated_alns for x in ("phy", "sup.nwk")}
+    for stem in repeated_alns:
+        assert boot[f"{stem}.phy"] == base[f"{stem}.phy"], stem
+        assert boot[f"{stem}.sup.nwk"].strip().endswith(b";")
