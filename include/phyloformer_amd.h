@@ -280,6 +280,39 @@ int pf_forward_leave_one_out(pf_handle_t* h, const uint8_t* idx, int32_t B, int3
 int pf_loo_stats_device(pf_handle_t* h, const float* d_full, const float* d_loo, int32_t B, int32_t N, float* d_influence,
                         float* d_shift, float* d_context);
 
+/* ---- query placement: distances of added sequences to a backbone (additive to ABI 5) ----
+ *
+ * "Add one in", the mirror of leave-one-out.  An alignment of M sequences is a backbone - its first N = M - Q rows,
+ * N >= 2 - followed by Q >= 1 queries, where `mafft --add` and its kin put them.  Distances are context dependent, so a
+ * query's distances to the backbone change with whichever other queries share its forward: every query is therefore
+ * forwarded alone with the backbone.  Set q is the rows (0, .., N - 1, N + q), in that order: the query is its row N.
+ * With P_n = n (n - 1) / 2 and pair_n(i, j) the pair order above among n rows:
+ *   out     float [B][P_M]           pf_forward(idx), bit for bit
+ *   base    float [B][P_N]           pf_forward of rows 0 .. N - 1, bit for bit
+ *   sets    float [B][Q][P_{N+1}]    (may be NULL) sets[b][q] = pf_forward_taxa of (0, .., N - 1, N + q), bit for bit
+ *   place   float [B][Q][N]          place[q][i] = sets[q][pair_{N+1}(i, N)]: query q's distance to backbone row i (a copy)
+ *   and, with delta_q(i, j) = sets[q][pair_{N+1}(i, j)] - base[pair_N(i, j)] over the P_N backbone pairs (exact in double),
+ *   disturb float [B][Q]             sqrt( mean delta_q^2 ): how far the query's presence moves the backbone's own distances
+ *   shift   float [B][Q]             mean delta_q: signed
+ *   joint   float [B][Q]             sqrt( mean_i (out[pair_M(i, N + q)] - place[q][i])^2 ): how far the OTHER queries'
+ *                                    presence moves q's distances to the backbone (0 when Q = 1 up to the forward's bits)
+ * Synchronous; the sources are uploaded once; never communicates.  The whole, the backbone and the Q sets each take
+ * the path pf_forward would take for their own shapes (M, L), (N, L), (N + 1, L) (options "precise", "generic",
+ * "ws_limit_mb", "max_seqs" and the range re-check per derived alignment included).  The statistics are reduced on the
+ * device after the range re-check has replaced flagged sets, in double, rounded to float once, no atomics: their bits
+ * are a function of (N, Q, out, base, sets) only, batch invariant.  They are descriptive, not a test statistic.  The
+ * sets run in sub-calls, so that `sets` on the device never exceeds one sub-call.  Refused before any device work,
+ * every output untouched: everything pf_forward checks, at all three shapes (residues > 21 included); Q < 1; M - Q < 2;
+ * NULL buffers other than sets; sizes that overflow size_t; and (PF_ESTATE) a handle whose communicator has more than
+ * one rank. */
+int pf_forward_place(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t M, int32_t L, int32_t Q, float* out, float* base,
+                     float* sets, float* place, float* disturb, float* shift, float* joint);
+/* The reduction alone (k_place_rows, k_place_backbone; csrc/pf_place.hip.h) on device arrays d_whole float [B][P_{N+Q}],
+ * d_base float [B][P_N], d_sets float [B][Q][P_{N+1}] -> d_place [B][Q][N], d_disturb, d_shift, d_joint [B][Q]; async on
+ * the handle's stream.  B >= 1, N >= 2, Q >= 1. */
+int pf_place_stats_device(pf_handle_t* h, const float* d_whole, const float* d_base, const float* d_sets, int32_t B, int32_t N,
+                          int32_t Q, float* d_place, float* d_disturb, float* d_shift, float* d_joint);
+
 /* ---- site weights: weighted forward, pattern compression, bootstrap on distinct sites (additive to ABI 5) ----
  *
  * Nothing in the network depends on a site's position, and every reduction over sites is a plain sum (the row-attention
@@ -408,7 +441,8 @@ int pf_memcpy_d2h(pf_handle_t* h, void* dst, const void* src, size_t bytes);
  * pf_forward_windows / pf_gather_sites_device), "site_moments" (the reduction of pf_forward_site_profile /
  * pf_site_moments_device), "gather_taxa" (k_gather_taxa of pf_forward_taxa / pf_forward_leave_one_out /
  * pf_gather_taxa_device), "loo_stats" (the reduction of pf_forward_leave_one_out / pf_loo_stats_device).
- * "weight_sums" (k_weight_sums of the weighted forwards).  Totals accumulate until reset.  "collectives" returns the number of all-reduces issued since the last reset in
+ * "weight_sums" (k_weight_sums of the weighted forwards), "place_stats" (the reduction of pf_forward_place /
+ * pf_place_stats_device).  Totals accumulate until reset.  "collectives" returns the number of all-reduces issued since the last reset in
  * *launches (counted always, no profiling option needed; *total_ms = 0); "rechecked" likewise the number of
  * alignments the range re-check (option "recheck_above") computed again on the float64 kernels. */
 int pf_profile_reset(pf_handle_t* h);

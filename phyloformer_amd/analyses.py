@@ -1,5 +1,5 @@
 """The CLI's per-alignment analyses (``--bootstrap``, ``--windows``, ``--site-profile``, ``--leave-one-out``,
-``--compress-sites``), each described ONCE: its flag and help, what it refuses to be combined with, the files it
+``--compress-sites``, ``--place``), each described ONCE: its flag and help, what it refuses to be combined with, the files it
 cannot run on, the stats it reports, its call into the engine and its writer.  ``infer_alns.py`` builds its parser and
 its refusals from ``MODES``; ``scheduler.DirectoryRunner`` drives whatever modes it is given and names none of them.
 
@@ -16,7 +16,8 @@ import numpy as np
 
 # Result floats of one engine call behind the launch's forward (16 MiB): the replicate distances of a pf_bootstrap call,
 # the window distances of a pf_forward_windows call, the distances of the cuts (N x P1 floats per alignment) of a
-# pf_forward_leave_one_out call.  This bounds host memory, not GPU work: the results wait in the writer queue (up to
+# pf_forward_leave_one_out call, the distances of the query sets (Q x P_{N+1} floats per alignment) of a pf_forward_place
+# call.  This bounds host memory, not GPU work: the results wait in the writer queue (up to
 # 8 x io_threads entries) until their files are written, so the cap keeps that queue to a few hundred MB even at 200
 # taxa (R = 100 x 19,900 floats = 8 MB per alignment).  The GPU stays fed: one alignment's R = 100 replicates at
 # 60 x 500 are already 6 x TOKEN_BUDGET, and the library chunks every one of these calls itself.
@@ -335,7 +336,76 @@ class CompressSites(Analysis):
         return preds, ()
 
 
-MODES = (Bootstrap, Windows, SiteProfile, LeaveOneOut, CompressSites)
+class Place(Analysis):
+    flag = "--place"
+    option = {"type": int, "default": 0, "metavar": "Q"}
+    help = ("query placement: the last Q sequences of every file are queries, the sequences before them the "
+            "backbone (where `mafft --add` puts added sequences); every query is inferred alone with the backbone "
+            "(cut and inferred on the GPU): writes <stem>.place.dist.tsv (the distances of every query to every "
+            "backbone sequence) and <stem>.place.tsv (index, id, nearest = backbone id of the smallest distance, "
+            "nearest_distance, disturb = RMS move of the backbone's own distances when the query joins, shift = "
+            "their mean move, joint = RMS move of the query's distances when the other queries join too; with -t "
+            "edge, x, pendant, residual = the least-squares placement on the backbone's NJ tree, the edge named "
+            "by the leaves of its smaller side) and with -t <stem>.placed.nwk, that tree with all queries "
+            "attached (descriptive statistics, not a test); <stem>.phy is unchanged; a file with fewer than Q + 2 "
+            "sequences is an error; 0 (default) = off")
+    refuses = (("--bootstrap", "replicates of query sets are out of scope"),
+               ("--windows", "query sets of windows are out of scope"),
+               ("--site-profile", "site maps of query sets are out of scope"),
+               ("--leave-one-out", "cuts of query sets are out of scope"),
+               ("--compress-sites", "weighted query sets are out of scope"),
+               (SHARD_SITES, "every query set would need its own collectives"))
+
+    def __init__(self, queries: int):
+        self.queries = int(queries)
+
+    @classmethod
+    def from_args(cls, args):
+        if args.place < 0:
+            raise ValueError(f"--place must be >= 0 (got {args.place})")
+        return cls(args.place) if args.place else None
+
+    def stats(self):
+        return {"place_sets": 0}
+
+    def accepts(self, n, l):
+        return n >= self.queries + 2
+
+    def file_error(self, path, n, l):
+        """(a backbone needs two sequences: one pair)"""
+        return ValueError(f"--place: {path} has n = {n} sequences, fewer than the Q + 2 = {self.queries + 2} that "
+                          f"Q = {self.queries} queries and a backbone of 2 need")
+
+    def forward(self, runner, engine, shape, batch):
+        """The same distances (forward's, bit for bit), then the backbone's and the Q query sets of every alignment and
+        their statistics, in sub-batches; the sets' distances themselves are not kept."""
+        Q, N = self.queries, shape[0] - self.queries
+        parts = [engine.forward_place(batch[s], Q) for s in sub_batches(len(batch), Q * (N + 1) * N // 2)]
+        preds, *rest = [np.concatenate([p[k] for p in parts]) for k in range(len(parts[0]))]
+        return preds, tuple(rest)
+
+    def account(self, stats, count, shape, seconds):
+        stats["place_sets"] += count * self.queries
+
+    def write(self, runner, shape, entry, pred, base, place, disturb, shift, joint):
+        """``<stem>.place.dist.tsv`` and ``<stem>.place.tsv`` of one file; with ``--trees`` the placement columns and
+        ``<stem>.placed.nwk``, from the backbone's NJ tree on index labels (duplicate ids do not matter)."""
+        from .place import Backbone, graft, ls_place, place_dist_tsv, place_tsv
+        ids = entry.ids()
+        N = len(ids) - self.queries
+        back, queries = ids[:N], ids[N:]
+        cols = None
+        if runner.trees:
+            labels = [str(k) for k in range(N)]
+            bb = Backbone(_text(runner.nj(base, labels)), labels)
+            found = [ls_place(bb, d) for d in place]
+            cols = [("NA",) * 4 if N == 2 else (bb.edge_label(p.edge, back), p.x, p.pendant, p.residual) for p in found]
+            runner.put(entry.path, "placed.nwk", graft(bb, found, queries, back))
+        runner.put(entry.path, "place.dist.tsv", place_dist_tsv(back, queries, place))
+        runner.put(entry.path, "place.tsv", place_tsv(back, queries, place, disturb, shift, joint, cols))
+
+
+MODES = (Bootstrap, Windows, SiteProfile, LeaveOneOut, CompressSites, Place)
 
 
 def modes_from_args(args, error) -> List[Analysis]:

@@ -42,6 +42,7 @@
 #include "pf_sitemap.hip.h"
 #include "pf_sites_host.h"
 #include "pf_taxa.hip.h"
+#include "pf_place.hip.h"
 #include "pf_weights.hip.h"
 #include "pf_weights_host.h"
 #include "pf_host_prep.h"
@@ -143,9 +144,9 @@ struct BlockDev {
 struct ProfSlot { int kid; hipEvent_t a, b; };
 const char* const KNAMES[] = {"embed", "rowfin", "colstats", "colfin", "main", "allreduce",
                               "mha_qkv", "mha_attn", "mha_out", "precise", "generic", "resample", "gather", "site_moments", "gather_taxa", "loo_stats",
-                              "weight_sums"};
+                              "weight_sums", "place_stats"};
 enum { K_EMBED = 0, K_ROWFIN, K_COLSTATS, K_COLFIN, K_MAIN, K_ALLREDUCE, K_MHA_QKV, K_MHA_ATTN, K_MHA_OUT, K_PRECISE, K_GENERIC,
-       K_RESAMPLE, K_GATHER, K_SITE_MOMENTS, K_GATHER_TAXA, K_LOO_STATS, K_WEIGHT_SUMS, K_COUNT };
+       K_RESAMPLE, K_GATHER, K_SITE_MOMENTS, K_GATHER_TAXA, K_LOO_STATS, K_WEIGHT_SUMS, K_PLACE_STATS, K_COUNT };
 
 // what the embed and head kernels (pfg's, for both float64 paths) read: C = 64 (precise) or Ep (generic)
 struct F64Ends {
@@ -227,6 +228,8 @@ struct pf_handle {
     float* d_prof = nullptr; size_t d_prof_bytes = 0;
     // pf_forward_leave_one_out (grow-only): one sub-call's full distances and its influence / shift / context
     float* d_loo = nullptr; size_t d_loo_bytes = 0;
+    // pf_forward_place (grow-only): one sub-call's whole and backbone distances and its place / disturb / shift / joint
+    float* d_place = nullptr; size_t d_place_bytes = 0;
     // weighted forwards (grow-only): the weight rows of a host call or of one chunk of derived alignments, what
     // k_weight_sums made of a call's rows ([..][4], pf_weights.hip.h), and the weight table of pf_forward_sites_weighted
     float* d_w = nullptr; size_t d_w_bytes = 0;
@@ -1293,22 +1296,25 @@ int launch_gather(pf_handle* h, const uint8_t* d_src, int B, int N, int L, const
 // Weighted derived alignments (pf_forward_sites_weighted): wfill(nb, j0, nj, d_wdst) writes the same rectangle's weight
 // rows float [nb][nj][K] into d_wdst on h->stream - a chunk's live in the grow-only h->d_w - and the forward is the
 // weighted one; without wfill nothing changes.
+// Resident sources (pf_forward_place, which forwards several shapes from one upload): d_resident holds the B sources,
+// checked and uploaded by the caller on h->stream; idx is not read, h->d_idx is neither grown nor written.
 template <class Fill, class WFill = std::nullptr_t>
 int forward_derived(pf_handle* h, const uint8_t* idx, int B, int N, int L, int S, int Nd, int K, float* out, const char* what,
-                    Fill&& fill, WFill&& wfill = nullptr) {
+                    Fill&& fill, WFill&& wfill = nullptr, const uint8_t* d_resident = nullptr) {
     constexpr bool weighted = !std::is_same<typename std::decay<WFill>::type, std::nullptr_t>::value;
-    if (!out || !idx) return fail(h, PF_EINVAL, "null buffer");
+    if (!out || (!idx && !d_resident)) return fail(h, PF_EINVAL, "null buffer");
     const int P = Nd * (Nd - 1) / 2;
     size_t nout = 0, nrep = 0;
     if (!mul_size((size_t)B, (size_t)S, (size_t)P * sizeof(float), &nout) || !mul_size((size_t)B, (size_t)S, (size_t)Nd * K, &nrep))
         return fail(h, PF_EINVAL, "B=%d x S=%d %s of %d x %d overflow the address space", B, S, what, Nd, K);
     const size_t nidx = (size_t)B * N * L, per_src = (size_t)N * L, per = (size_t)Nd * K;
-    int rc = check_residues(h, idx, nidx);
+    int rc = d_resident ? PF_OK : check_residues(h, idx, nidx);
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->device));
-    if ((rc = ensure_buffer(h, &h->d_idx, &h->d_idx_bytes, nidx))) return rc;
+    if (!d_resident && (rc = ensure_buffer(h, &h->d_idx, &h->d_idx_bytes, nidx))) return rc;
     if ((rc = ensure_buffer(h, &h->d_out, &h->d_out_bytes, nout))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_idx, idx, nidx, hipMemcpyHostToDevice, h->stream));
+    if (!d_resident) HIPCHK(h, hipMemcpyAsync(h->d_idx, idx, nidx, hipMemcpyHostToDevice, h->stream));
+    const uint8_t* d_all = d_resident ? d_resident : h->d_idx;
     const F64Path* f = f64_path_of(h, Nd, K);
     const int total = (int)std::min<int64_t>((int64_t)B * S, INT32_MAX);
     const int cb = f ? f64_chunk_batch(h, *f, total, P, K) : chunk_batch(h, total, P, K);
@@ -1320,7 +1326,7 @@ int forward_derived(pf_handle* h, const uint8_t* idx, int B, int N, int L, int S
     for (int b0 = 0; b0 < B; b0 += std::max(spc, 1))
         for (int j0 = 0; j0 < S; j0 += jpc) {
             const int nb = spc ? std::min(spc, B - b0) : 1, nj = std::min(jpc, S - j0);
-            if ((rc = fill(h->d_idx + (size_t)b0 * per_src, nb, j0, nj, h->d_rep))) return rc;
+            if ((rc = fill(d_all + (size_t)b0 * per_src, nb, j0, nj, h->d_rep))) return rc;
             if constexpr (weighted) { if ((rc = wfill(nb, j0, nj, h->d_w))) return rc; }
             rc = forward_device_impl(h, h->d_rep, nb * nj, Nd, 0, K, K, h->d_out + ((size_t)b0 * S + j0) * P,
                                      weighted ? h->d_w : nullptr);
@@ -1333,7 +1339,7 @@ int forward_derived(pf_handle* h, const uint8_t* idx, int B, int N, int L, int S
     auto stage = [&](const int* list, size_t k, uint8_t* d_buf) -> int {
         for (size_t i = 0; i < k; ++i) {
             const int b = list[i] / S, j = list[i] % S;
-            int rc2 = fill(h->d_idx + (size_t)b * per_src, 1, j, 1, d_buf + i * per);
+            int rc2 = fill(d_all + (size_t)b * per_src, 1, j, 1, d_buf + i * per);
             if (rc2) return rc2;
             if constexpr (weighted) { if ((rc2 = wfill(1, j, 1, h->d_w + i * (size_t)K))) return rc2; }
         }
@@ -1710,6 +1716,92 @@ int loo_impl(pf_handle* h, const uint8_t* idx, int B, int N, int L, float* out, 
     return PF_OK;
 }
 
+// ---- query placement (pf_forward_place, pf_place_stats_device; pf_place.hip.h) ---------------
+
+int launch_place_stats(pf_handle* h, const float* d_whole, const float* d_base, const float* d_sets, int B, int N, int Q,
+                       float* d_place, float* d_disturb, float* d_shift, float* d_joint) {
+    h->cur = h->stream;
+    ProfScope ps(h, K_PLACE_STATS);
+    const hipError_t e = pfpl::launch_place_stats(h->stream, d_whole, d_base, d_sets, B, N, Q, d_place, d_disturb, d_shift, d_joint);
+    if (e != hipSuccess) return fail(h, PF_EHIP, "k_place_rows / k_place_backbone launch failed: %s", hipGetErrorString(e));
+    return PF_OK;
+}
+
+// pf_forward_place: the B sources [M][L] go up once and stay in h->d_idx; three kinds of derived alignments are cut
+// from them through forward_derived - the whole (rows 0 .. M - 1: pf_forward's bits, and the resident bytes stay
+// intact where pf_forward's own re-check would stage over them), the backbone (rows 0 .. N - 1) and the Q sets
+// (rows 0 .. N - 1, N + q) - each on the path of its own shape.  Their row tables share one upload into h->d_map:
+// [Q][N + 1], then [N], then [M].  The sets run in sub-calls of whole sources holding at most LOO_SUB_FLOATS distances,
+// each followed by its reduction on the device, which reads what the range re-check left (pf_forward_leave_one_out's
+// rule).
+int place_impl(pf_handle* h, const uint8_t* idx, int B, int M, int L, int Q, float* out, float* base, float* sets, float* place,
+               float* disturb, float* shift, float* joint) {
+    int rc = check_dims(h, B, M, L, L);
+    if (rc) return rc;
+    if (Q < 1) return fail(h, PF_EINVAL, "placement needs Q >= 1 queries (got %d)", Q);
+    if (M - Q < 2) return fail(h, PF_EINVAL, "placement needs a backbone of M - Q >= 2 sequences (got M=%d, Q=%d)", M, Q);
+    const int N = M - Q;
+    size_t ntab = 0, n = 0;
+    if ((rc = check_taxa_call(h, B, M, L, Q, N + 1, &ntab))) return rc;        // (N + 1, L); one rank; the sets' sizes
+    if ((rc = check_dims(h, B, N, L, L))) return rc;
+    const size_t PM = (size_t)M * (M - 1) / 2, PN = (size_t)N * (N - 1) / 2, P1 = (size_t)(N + 1) * N / 2;
+    if (!mul_size((size_t)B, PM, sizeof(float), &n) || !mul_size((size_t)B, (size_t)M, (size_t)L, &n))
+        return fail(h, PF_EINVAL, "B=%d alignments of %d x %d overflow the address space", B, M, L);
+    if (!out || !idx || !base || !place || !disturb || !shift || !joint) return fail(h, PF_EINVAL, "null buffer");
+    const size_t nidx = (size_t)B * M * L, per_src = (size_t)M * L, per_set = (size_t)Q * P1;
+    if ((rc = check_residues(h, idx, nidx))) return rc;
+    const int sub = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, LOO_SUB_FLOATS / per_set));
+    const size_t t_base = (size_t)Q * (N + 1), t_whole = t_base + N;
+    std::vector<int32_t> table;
+    std::vector<float> tmp;
+    try {
+        table.resize(t_whole + M);
+        if (!sets) tmp.resize((size_t)sub * per_set);
+    } catch (const std::bad_alloc&) { return fail(h, PF_ENOMEM, "out of host memory for the sets of %d queries", Q); }
+    for (int q = 0; q < Q; ++q) {
+        for (int m = 0; m < N; ++m) table[(size_t)q * (N + 1) + m] = m;
+        table[(size_t)q * (N + 1) + N] = N + q;
+    }
+    for (int m = 0; m < N; ++m) table[t_base + m] = m;
+    for (int m = 0; m < M; ++m) table[t_whole + m] = m;
+    HIPCHK(h, hipSetDevice(h->device));
+    if ((rc = ensure_buffer(h, &h->d_idx, &h->d_idx_bytes, nidx))) return rc;
+    if ((rc = ensure_buffer(h, &h->d_map, &h->d_map_bytes, table.size() * sizeof(int32_t)))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->d_idx, idx, nidx, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_map, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    // rows `t_off ..` of the table, Md to a set
+    auto cut = [&](size_t t_off, int Md) {
+        return [=](const uint8_t* d_src, int nb, int j0, int nj, uint8_t* d_dst) -> int {
+            return launch_gather_taxa(h, d_src, nb, M, L, h->d_map + t_off, j0, nj, Md, d_dst);
+        };
+    };
+    if ((rc = forward_derived(h, nullptr, B, M, L, 1, M, L, out, "alignments", cut(t_whole, M), nullptr, h->d_idx))) return rc;
+    if ((rc = forward_derived(h, nullptr, B, M, L, 1, N, L, base, "backbones", cut(t_base, N), nullptr, h->d_idx))) return rc;
+    for (int b0 = 0; b0 < B; b0 += sub) {
+        const int nb = std::min(sub, B - b0);
+        float* hs = sets ? sets + (size_t)b0 * per_set : tmp.data();
+        const int64_t before = h->rechecked;
+        if ((rc = forward_derived(h, nullptr, nb, M, L, Q, N + 1, L, hs, "query sets", cut(0, N + 1), nullptr,
+                                  h->d_idx + (size_t)b0 * per_src)))
+            return rc;
+        const size_t nwhole = (size_t)nb * PM, nbase = (size_t)nb * PN, nplace = (size_t)nb * Q * N, nrow = (size_t)nb * Q;
+        if (h->rechecked != before)
+            HIPCHK(h, hipMemcpyAsync(h->d_out, hs, (size_t)nb * per_set * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        if ((rc = ensure_buffer(h, &h->d_place, &h->d_place_bytes, (nwhole + nbase + nplace + 3 * nrow) * sizeof(float)))) return rc;
+        float *d_whole = h->d_place, *d_base = d_whole + nwhole, *d_pl = d_base + nbase, *d_dis = d_pl + nplace, *d_sh = d_dis + nrow,
+              *d_jt = d_sh + nrow;
+        HIPCHK(h, hipMemcpyAsync(d_whole, out + (size_t)b0 * PM, nwhole * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(d_base, base + (size_t)b0 * PN, nbase * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        if ((rc = launch_place_stats(h, d_whole, d_base, h->d_out, nb, N, Q, d_pl, d_dis, d_sh, d_jt))) return rc;
+        HIPCHK(h, hipMemcpyAsync(place + (size_t)b0 * Q * N, d_pl, nplace * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(disturb + (size_t)b0 * Q, d_dis, nrow * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(shift + (size_t)b0 * Q, d_sh, nrow * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(joint + (size_t)b0 * Q, d_jt, nrow * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return PF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1860,6 +1952,7 @@ int pf_destroy(pf_handle_t* h) {
     if (h->d_se) hipFree(h->d_se);
     if (h->d_prof) hipFree(h->d_prof);
     if (h->d_loo) hipFree(h->d_loo);
+    if (h->d_place) hipFree(h->d_place);
     if (h->d_w) hipFree(h->d_w);
     if (h->d_wst) hipFree(h->d_wst);
     if (h->d_wtab) hipFree(h->d_wtab);
@@ -2009,6 +2102,26 @@ int pf_loo_stats_device(pf_handle_t* h, const float* d_full, const float* d_loo,
         return fail(h, PF_EINVAL, "B=%d x %d leave-one-out sets of %d sequences overflow the address space", B, N, N - 1);
     HIPCHK(h, hipSetDevice(h->device));
     return launch_loo_stats(h, d_full, d_loo, B, N, d_influence, d_shift, d_context);
+}
+
+int pf_forward_place(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t M, int32_t L, int32_t Q, float* out, float* base,
+                     float* sets, float* place, float* disturb, float* shift, float* joint) {
+    if (!h) return PF_EINVAL;
+    return place_impl(h, idx, B, M, L, Q, out, base, sets, place, disturb, shift, joint);
+}
+
+int pf_place_stats_device(pf_handle_t* h, const float* d_whole, const float* d_base, const float* d_sets, int32_t B, int32_t N,
+                          int32_t Q, float* d_place, float* d_disturb, float* d_shift, float* d_joint) {
+    if (!h) return PF_EINVAL;
+    if (!d_whole || !d_base || !d_sets || !d_place || !d_disturb || !d_shift || !d_joint) return fail(h, PF_EINVAL, "null buffer");
+    if (B < 1 || N < 2 || Q < 1 || (int64_t)N + Q > 32767)
+        return fail(h, PF_EINVAL, "bad dimensions B=%d N=%d Q=%d (placement needs N >= 2, Q >= 1, N + Q <= 32767)", B, N, Q);
+    size_t n = 0;
+    if (!mul_size((size_t)B, (size_t)Q, (size_t)(N + 1) * N / 2 * sizeof(float), &n) ||
+        !mul_size((size_t)B, (size_t)(N + Q) * (N + Q - 1) / 2, sizeof(float), &n))
+        return fail(h, PF_EINVAL, "B=%d x %d query sets of %d sequences overflow the address space", B, Q, N + 1);
+    HIPCHK(h, hipSetDevice(h->device));
+    return launch_place_stats(h, d_whole, d_base, d_sets, B, N, Q, d_place, d_disturb, d_shift, d_joint);
 }
 
 int pf_forward_device(pf_handle_t* h, const uint8_t* d_idx, int32_t B, int32_t N, int32_t L, float* d_out) {

@@ -122,6 +122,10 @@ SIGNATURES = {
                                            C.c_void_p, C.c_void_p, C.c_void_p]),
     "pf_loo_stats_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                       C.c_void_p]),
+    "pf_forward_place": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pf_place_stats_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pf_forward_weighted": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "pf_forward_weighted_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "pf_forward_sites_weighted": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
@@ -139,7 +143,8 @@ CALL_TIME_SYMBOLS = frozenset({"pf_forward_site_map", "pf_forward_site_map_devic
                                "pf_site_moments_device", "pf_gather_taxa_device", "pf_forward_taxa",
                                "pf_forward_leave_one_out", "pf_loo_stats_device", "pf_forward_weighted",
                                "pf_forward_weighted_device", "pf_forward_sites_weighted", "pf_bootstrap_weighted",
-                               "pf_padded_sites", "pf_boot_counts", "pf_compress_sites"})
+                               "pf_padded_sites", "pf_boot_counts", "pf_compress_sites", "pf_forward_place",
+                               "pf_place_stats_device"})
 
 _lib: Optional[C.CDLL] = None
 
@@ -434,6 +439,41 @@ class Engine:
         ``d_shift [B][N]``, ``d_context [B][P]`` (asynchronous on the handle's stream)."""
         self._check(self._optional("pf_loo_stats_device")(self._h, C.c_void_p(d_full), C.c_void_p(d_loo), B, N,
                                                           C.c_void_p(d_influence), C.c_void_p(d_shift), C.c_void_p(d_context)))
+
+    # -- query placement --------------------------------------------------------------------
+    def forward_place(self, idx: np.ndarray, queries: int, keep_sets: bool = False):
+        """Query placement (``pf_forward_place``): ``uint8[B, M, L]`` whose last ``queries`` rows are the queries, the
+        first ``N = M - queries >= 2`` the backbone → ``(dist float32[B, P_M], base float32[B, P_N], place
+        float32[B, Q, N], disturb float32[B, Q], shift float32[B, Q], joint float32[B, Q])``, with ``keep_sets`` a
+        seventh array ``sets float32[B, Q, P_{N+1}]`` (``[M, L]`` drops ``B`` everywhere).  ``dist`` is ``forward``'s,
+        ``base`` is ``forward(idx[:, :N])``, ``sets[b, q]`` is ``forward(place.join_query(idx[b], N, q))``, all bit for
+        bit; the rest is ``place.place_stats(dist, base, sets, N, Q)``, reduced on the GPU."""
+        fn = self._optional("pf_forward_place")
+        idx, single = self._sources(idx)
+        B, M, L = idx.shape
+        Q = int(queries)
+        N = M - Q
+        ok = Q >= 1 and N >= 2                                    # (otherwise the library refuses; nothing is read)
+        pairs = lambda n: n * (n - 1) // 2
+        out = np.empty((B, pairs(M)), dtype=np.float32)
+        base = np.empty((B, pairs(N) if ok else 1), dtype=np.float32)
+        sets = np.empty((B, Q, pairs(N + 1)), dtype=np.float32) if keep_sets and ok else None
+        place = np.empty((B, Q, N) if ok else (B, 1, 1), dtype=np.float32)
+        dis, sh, jt = (np.empty((B, Q if ok else 1), dtype=np.float32) for _ in range(3))
+        self._check(fn(self._h, idx.ctypes.data, B, M, L, Q, out.ctypes.data, base.ctypes.data,
+                       sets.ctypes.data if sets is not None else None, place.ctypes.data, dis.ctypes.data, sh.ctypes.data,
+                       jt.ctypes.data))
+        res = (out, base, place, dis, sh, jt) + ((sets,) if keep_sets else ())
+        return tuple(r[0] for r in res) if single else res
+
+    def place_stats_device(self, d_whole: int, d_base: int, d_sets: int, B: int, N: int, Q: int, d_place: int, d_disturb: int,
+                           d_shift: int, d_joint: int):
+        """``pf_place_stats_device``: device ``whole float32 [B][P_{N+Q}]``, ``base float32 [B][P_N]``, ``sets float32
+        [B][Q][P_{N+1}]`` → ``d_place [B][Q][N]``, ``d_disturb``, ``d_shift``, ``d_joint [B][Q]`` (asynchronous on the
+        handle's stream)."""
+        self._check(self._optional("pf_place_stats_device")(
+            self._h, C.c_void_p(d_whole), C.c_void_p(d_base), C.c_void_p(d_sets), B, N, Q, C.c_void_p(d_place),
+            C.c_void_p(d_disturb), C.c_void_p(d_shift), C.c_void_p(d_joint)))
 
     # -- site weights -----------------------------------------------------------------------
     @staticmethod
