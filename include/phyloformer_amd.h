@@ -313,6 +313,41 @@ int pf_forward_place(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t M, i
 int pf_place_stats_device(pf_handle_t* h, const float* d_whole, const float* d_base, const float* d_sets, int32_t B, int32_t N,
                           int32_t Q, float* d_place, float* d_disturb, float* d_shift, float* d_joint);
 
+/* ---- tiled inference: alignments beyond the sequence cap (additive to ABI 5) ----
+ *
+ * A forward holds P L 64 floats of residual stream and the checkpoints were trained on a few tens of sequences, so an
+ * alignment of N sequences beyond "max_seqs" is not forwarded whole: it is covered by sets of at most M rows - the
+ * CONTEXT a distance is predicted in, which is part of its definition (distances are context dependent).  The plan
+ * (csrc/pf_tile_host.h; phyloformer_amd/tile.py::plan is the Python twin), for 2 <= M and N > M:
+ *   G = ceil(N / floor(M / 2)) groups, G >= 3; group g is the contiguous rows [floor(g N / G), floor((g + 1) N / G)):
+ *   sizes differ by at most one.  Set (g, h), g < h, in lexicographic order, is the rows of group g followed by the rows
+ *   of group h: m = n_g + n_h <= M rows, S = G (G - 1) / 2 sets of at most three distinct sizes.  A cross-group pair
+ *   lies in exactly one set; a within-group pair of group g in the G - 1 sets that contain g.
+ * The sets' token count is about 2 (G - 1) / G times that of the untiled forward; memory stays that of one forward chunk.
+ *   out    float [B][P_N]   cross-group pair: its one value, the bits of pf_forward_taxa of its set.  Within-group
+ *                           pair: the mean of its G - 1 values, added in double in ascending order of the partner
+ *                           group, divided and rounded to float once.
+ *   spread float [B][P_N]   within-group pair: sqrt( sum (d - mean)^2 / (G - 2) ) over those values, in double from the
+ *                           unrounded mean: the standard deviation of the distance over its contexts.  Cross-group
+ *                           pair: exactly 0 - ONE context, so no spread is measured; 0 does not mean "certain".
+ *                           Descriptive, not a test statistic.
+ * Synchronous; the sources are uploaded once; every set takes the path pf_forward takes for its own shape (m, L)
+ * (options "precise", "generic", "ws_limit_mb" and the range re-check per set included); the sets' distances are
+ * combined on the device (k_tile_combine, csrc/pf_tile.hip.h: no atomics, the bits are a function of (N, M, values)
+ * only, batch invariant), in sub-calls of whole sources.  "max_seqs" is checked against M and every set size, NOT
+ * against N.  Refused with PF_EINVAL before any device work, out and spread untouched: M < 2; M > max_seqs while the cap
+ * is on (pf_forward's message); N <= M (call pf_forward); B < 1, L < 1; residues > 21; NULL buffers; sizes that overflow
+ * size_t, or P_N >= 2^31.  PF_ESTATE: a handle whose communicator has more than one rank.  Never communicates. */
+int pf_forward_tiled(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, int32_t L, int32_t M, float* out, float* spread);
+/* The combination alone on device arrays: d_sets float [B][T] - the distances of the S sets of every source in (g, h)
+ * order, each set's m (m - 1) / 2 distances in the pair order above, T their sum - -> d_out, d_spread float [B][P_N];
+ * async on the handle's stream (the plan's tables are rebuilt, behind a synchronisation, only when (N, M) changes). */
+int pf_tile_combine_device(pf_handle_t* h, const float* d_sets, int32_t B, int32_t N, int32_t M, float* d_out, float* d_spread);
+/* The plan's numbers: G, and the first row of group g (0 <= g <= G; g = G gives N); PF_EINVAL for M < 2, N <= M or g
+ * outside [0, G].  No handle, no GPU. */
+int pf_tile_groups(int32_t N, int32_t M);
+int pf_tile_bound(int32_t N, int32_t M, int32_t g);
+
 /* ---- site weights: weighted forward, pattern compression, bootstrap on distinct sites (additive to ABI 5) ----
  *
  * Nothing in the network depends on a site's position, and every reduction over sites is a plain sum (the row-attention
@@ -442,7 +477,7 @@ int pf_memcpy_d2h(pf_handle_t* h, void* dst, const void* src, size_t bytes);
  * pf_site_moments_device), "gather_taxa" (k_gather_taxa of pf_forward_taxa / pf_forward_leave_one_out /
  * pf_gather_taxa_device), "loo_stats" (the reduction of pf_forward_leave_one_out / pf_loo_stats_device).
  * "weight_sums" (k_weight_sums of the weighted forwards), "place_stats" (the reduction of pf_forward_place /
- * pf_place_stats_device).  Totals accumulate until reset.  "collectives" returns the number of all-reduces issued since the last reset in
+ * pf_place_stats_device), "tile_combine" (k_tile_combine of pf_forward_tiled / pf_tile_combine_device).  Totals accumulate until reset.  "collectives" returns the number of all-reduces issued since the last reset in
  * *launches (counted always, no profiling option needed; *total_ms = 0); "rechecked" likewise the number of
  * alignments the range re-check (option "recheck_above") computed again on the float64 kernels. */
 int pf_profile_reset(pf_handle_t* h);

@@ -1,5 +1,5 @@
 """The CLI's per-alignment analyses (``--bootstrap``, ``--windows``, ``--site-profile``, ``--leave-one-out``,
-``--compress-sites``, ``--place``), each described ONCE: its flag and help, what it refuses to be combined with, the files it
+``--compress-sites``, ``--place``, ``--tile``), each described ONCE: its flag and help, what it refuses to be combined with, the files it
 cannot run on, the stats it reports, its call into the engine and its writer.  ``infer_alns.py`` builds its parser and
 its refusals from ``MODES``; ``scheduler.DirectoryRunner`` drives whatever modes it is given and names none of them.
 
@@ -78,6 +78,11 @@ class Analysis:
     def file_error(self, path: str, n: int, l: int) -> Exception:
         """What a file that ``accepts`` turns down raises, where the loop reaches it."""
         raise NotImplementedError
+
+    def lifts_seq_cap(self, n):
+        """Does this mode run a file of ``n`` sequences that exceeds the reference's cap (``scheduler.MAX_SEQS``)?
+        Elementwise, like ``accepts``."""
+        return False
 
     def floats(self, shape: Tuple[int, int]) -> int:
         """Result floats of ``follow`` per alignment."""
@@ -405,7 +410,67 @@ class Place(Analysis):
         runner.put(entry.path, "place.tsv", place_tsv(back, queries, place, disturb, shift, joint, cols))
 
 
-MODES = (Bootstrap, Windows, SiteProfile, LeaveOneOut, CompressSites, Place)
+class Tile(Analysis):
+    flag = "--tile"
+    option = {"type": int, "default": 0, "metavar": "M"}
+    help = ("tiled inference for files with more than M sequences, the model's sequence cap included: the sequences "
+            "are cut, in file order, into groups of at most M / 2, every pair of groups is inferred as one alignment of "
+            "at most M sequences (cut and inferred on the GPU, about twice the tokens of one forward, the memory of "
+            "one context) and the results are combined on the GPU: <stem>.phy holds, for two sequences of different "
+            "groups, the distance of the one context they share and, for two of one group, the mean over all the "
+            "contexts of that group (with -t <stem>.nj.nwk is the NJ tree of these distances; at thousands of "
+            "sequences it takes seconds on a writer thread); writes <stem>.spread.phy, the standard deviation of "
+            "every within-group distance over its contexts (0 across groups: one context, nothing measured; "
+            "descriptive, not a test) and <stem>.tile.tsv (index, id, group); a file with at most M sequences runs "
+            "exactly as without the flag; M must be between 2 and the model's cap of 200; 0 (default) = off")
+    refuses = (("--bootstrap", "replicates of tile sets are out of scope"),
+               ("--windows", "tile sets of windows are out of scope"),
+               ("--site-profile", "site maps of tile sets are out of scope"),
+               ("--leave-one-out", "cuts of tile sets are out of scope"),
+               ("--compress-sites", "weighted tile sets are out of scope"),
+               ("--place", "query sets of tile sets are out of scope"),
+               (SHARD_SITES, "every tile set would need its own collectives"))
+
+    def __init__(self, context: int):
+        self.context = int(context)
+
+    @classmethod
+    def from_args(cls, args):
+        from .scheduler import MAX_SEQS
+        if args.tile and not 2 <= args.tile <= MAX_SEQS:
+            raise ValueError(f"--tile must be 0 (off) or a context of 2 to {MAX_SEQS} sequences (got {args.tile})")
+        return cls(args.tile) if args.tile else None
+
+    def stats(self):
+        return {"tiled": 0, "tile_sets": 0}
+
+    def lifts_seq_cap(self, n):
+        return n > self.context
+
+    def forward(self, runner, engine, shape, batch):
+        """A launch of files with at most M sequences is the plain forward and has no payload: nothing but ``<stem>.phy``
+        (and the tree) is written for them.  Larger files: the tiled distances in place of forward's, and the spread."""
+        if shape[0] <= self.context:
+            return engine.forward(batch), ()
+        out, spread = engine.forward_tiled(batch, self.context)
+        return out, (spread,)
+
+    def account(self, stats, count, shape, seconds):
+        if shape[0] > self.context:
+            from .tile import groups
+            G = groups(shape[0], self.context)
+            stats["tiled"] += count
+            stats["tile_sets"] += count * G * (G - 1) // 2
+
+    def write(self, runner, shape, entry, pred, spread):
+        """``<stem>.spread.phy`` (ids and number format of ``<stem>.phy``) and ``<stem>.tile.tsv`` of one file."""
+        from .tile import tile_tsv
+        ids = entry.ids()
+        runner.put(entry.path, "spread.phy", runner.phylip(spread, ids))
+        runner.put(entry.path, "tile.tsv", tile_tsv(ids, self.context))
+
+
+MODES = (Bootstrap, Windows, SiteProfile, LeaveOneOut, CompressSites, Place, Tile)
 
 
 def modes_from_args(args, error) -> List[Analysis]:

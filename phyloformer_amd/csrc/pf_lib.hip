@@ -43,6 +43,7 @@
 #include "pf_sites_host.h"
 #include "pf_taxa.hip.h"
 #include "pf_place.hip.h"
+#include "pf_tile.hip.h"
 #include "pf_weights.hip.h"
 #include "pf_weights_host.h"
 #include "pf_host_prep.h"
@@ -144,9 +145,9 @@ struct BlockDev {
 struct ProfSlot { int kid; hipEvent_t a, b; };
 const char* const KNAMES[] = {"embed", "rowfin", "colstats", "colfin", "main", "allreduce",
                               "mha_qkv", "mha_attn", "mha_out", "precise", "generic", "resample", "gather", "site_moments", "gather_taxa", "loo_stats",
-                              "weight_sums", "place_stats"};
+                              "weight_sums", "place_stats", "tile_combine"};
 enum { K_EMBED = 0, K_ROWFIN, K_COLSTATS, K_COLFIN, K_MAIN, K_ALLREDUCE, K_MHA_QKV, K_MHA_ATTN, K_MHA_OUT, K_PRECISE, K_GENERIC,
-       K_RESAMPLE, K_GATHER, K_SITE_MOMENTS, K_GATHER_TAXA, K_LOO_STATS, K_WEIGHT_SUMS, K_PLACE_STATS, K_COUNT };
+       K_RESAMPLE, K_GATHER, K_SITE_MOMENTS, K_GATHER_TAXA, K_LOO_STATS, K_WEIGHT_SUMS, K_PLACE_STATS, K_TILE_COMBINE, K_COUNT };
 
 // what the embed and head kernels (pfg's, for both float64 paths) read: C = 64 (precise) or Ep (generic)
 struct F64Ends {
@@ -230,6 +231,11 @@ struct pf_handle {
     float* d_loo = nullptr; size_t d_loo_bytes = 0;
     // pf_forward_place (grow-only): one sub-call's whole and backbone distances and its place / disturb / shift / joint
     float* d_place = nullptr; size_t d_place_bytes = 0;
+    // pf_forward_tiled / pf_tile_combine_device: the plan of the last (N, M) and its device tables (offset int64 [S + 1],
+    // then bounds int32 [G + 1]); one sub-call's set distances [nb][T], then its out and spread [nb][P_N] (grow-only)
+    pftile::Plan tiled_plan;
+    char* d_tiled_tab = nullptr; size_t d_tiled_tab_bytes = 0;
+    float* d_tiled = nullptr; size_t d_tiled_bytes = 0;
     // weighted forwards (grow-only): the weight rows of a host call or of one chunk of derived alignments, what
     // k_weight_sums made of a call's rows ([..][4], pf_weights.hip.h), and the weight table of pf_forward_sites_weighted
     float* d_w = nullptr; size_t d_w_bytes = 0;
@@ -1802,6 +1808,147 @@ int place_impl(pf_handle* h, const uint8_t* idx, int B, int M, int L, int Q, flo
     return PF_OK;
 }
 
+// ---- tiled inference (pf_forward_tiled, pf_tile_combine_device; pf_tile.hip.h, pf_tile_host.h) ----
+
+// The plan of (N, M) in h->tiled_plan and its two tables on the device - offset int64 [S + 1], then bounds int32 [G + 1] -
+// rebuilt only when (N, M) changes.  The stream is drained first: the upload of the previous tables may still be reading
+// the host vectors.  The caller has checked M >= 2 and N > M.
+int ensure_tiled_plan(pf_handle* h, int N, int M) {
+    pftile::Plan& p = h->tiled_plan;
+    if (p.N == N && p.M == M && h->d_tiled_tab) return PF_OK;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    bool ok = false;
+    try { ok = p.build(N, M); } catch (const std::bad_alloc&) {
+        p.N = p.M = 0;
+        return fail(h, PF_ENOMEM, "out of host memory for the tiling plan of N=%d, M=%d", N, M);
+    }
+    if (!ok) return fail(h, PF_EINVAL, "tiling needs 2 <= M < N (got N=%d, M=%d)", N, M);
+    const size_t noff = p.offset.size() * sizeof(int64_t), nbound = p.bounds.size() * sizeof(int32_t);
+    int rc = ensure_buffer(h, &h->d_tiled_tab, &h->d_tiled_tab_bytes, noff + nbound);
+    hipError_t e = hipSuccess;
+    if (!rc) e = hipMemcpyAsync(h->d_tiled_tab, p.offset.data(), noff, hipMemcpyHostToDevice, h->stream);
+    if (!rc && e == hipSuccess) e = hipMemcpyAsync(h->d_tiled_tab + noff, p.bounds.data(), nbound, hipMemcpyHostToDevice, h->stream);
+    if (rc || e != hipSuccess) {
+        p.N = p.M = 0;                                   // (the tables on the device are not this plan's)
+        return rc ? rc : fail(h, PF_EHIP, "upload of the tiling plan failed: %s", hipGetErrorString(e));
+    }
+    return PF_OK;
+}
+
+// d_sets [B][T] -> d_out, d_spread [B][P_N] by the resident plan
+int launch_tile_combine(pf_handle* h, const float* d_sets, int B, float* d_out, float* d_spread) {
+    const pftile::Plan& p = h->tiled_plan;
+    h->cur = h->stream;
+    ProfScope ps(h, K_TILE_COMBINE);
+    const int64_t* d_offset = reinterpret_cast<const int64_t*>(h->d_tiled_tab);
+    const int32_t* d_bounds = reinterpret_cast<const int32_t*>(h->d_tiled_tab + p.offset.size() * sizeof(int64_t));
+    const hipError_t e = pftile::launch_tile_combine(h->stream, d_sets, d_bounds, d_offset, B, p.N, p.G, p.T, d_out, d_spread);
+    if (e != hipSuccess) return fail(h, PF_EHIP, "k_tile_combine launch failed: %s", hipGetErrorString(e));
+    return PF_OK;
+}
+
+// What pf_forward_tiled and pf_tile_combine_device refuse about (B, N, M) beside the handle's own state: the context, the
+// cap - against M, never against N - and the sizes.
+int check_tiled_shape(pf_handle* h, int B, int N, int M) {
+    if (M < 2) return fail(h, PF_EINVAL, "tiling needs a context of M >= 2 sequences (got %d)", M);
+    if (B < 1) return fail(h, PF_EINVAL, "bad dimensions B=%d N=%d M=%d", B, N, M);
+    if (h->max_seqs > 0 && M > h->max_seqs)
+        // (pf_forward's wording: the context is what a forward sees)
+        return fail(h, PF_EINVAL, "n_seqs must be smaller or equal to %lld (or pre-compute a larger global_seq2pair)",
+                    (long long)h->max_seqs);
+    if (M > 32767) return fail(h, PF_EINVAL, "n_seqs %d exceeds the pair-table index range", M);
+    if (N <= M) return fail(h, PF_EINVAL, "N=%d sequences fit one context of M=%d: call pf_forward", N, M);
+    const int64_t PN = (int64_t)N * (N - 1) / 2;
+    size_t n = 0;
+    if (PN >= ((int64_t)1 << 31) || !mul_size((size_t)B, (size_t)PN, 2 * sizeof(float), &n))
+        return fail(h, PF_EINVAL, "B=%d alignments of N=%d sequences: their %lld pairs each overflow a distance vector", B, N, (long long)PN);
+    return PF_OK;
+}
+
+// pf_forward_tiled: the B sources [N][L] go up once and stay in h->d_idx.  The sets of one size - a class, at most three -
+// share a row table [S_c][m_c]; the tables go up once into h->d_map, and every class runs through forward_derived with
+// k_gather_taxa as its fill, so that every set takes pf_forward's path for (m_c, L), range re-check included.  The class
+// results are assembled on the host into the [nb][T] layout of k_tile_combine - after the re-check has replaced flagged
+// sets - uploaded once and combined on the device.  Sub-calls of whole sources keep [nb][T] within LOO_SUB_FLOATS; one
+// source always runs whole.  Nothing is written to out / spread before the first sub-call has succeeded.
+int tiled_impl(pf_handle* h, const uint8_t* idx, int B, int N, int L, int M, float* out, float* spread) {
+    int rc = check_tiled_shape(h, B, N, M);
+    if (rc) return rc;
+    if ((rc = check_dims(h, B, M, L, L))) return rc;                           // the handle's weights, L
+    if (h->world > 1)
+        return fail(h, PF_ESTATE, "tiled inference is not site-sharded: this handle's communicator has %d ranks (use a handle "
+                                  "without a communicator)", h->world);
+    size_t nidx = 0;
+    if (!mul_size((size_t)B, (size_t)N, (size_t)L, &nidx))
+        return fail(h, PF_EINVAL, "B=%d alignments of %d x %d overflow the address space", B, N, L);
+    if (!out || !spread || !idx) return fail(h, PF_EINVAL, "null buffer");
+    if ((rc = check_residues(h, idx, nidx))) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    if ((rc = ensure_tiled_plan(h, N, M))) return rc;
+    const pftile::Plan& p = h->tiled_plan;
+    const size_t T = (size_t)p.T, PN = (size_t)N * (N - 1) / 2, per_src = (size_t)N * L;
+    const int sub = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, LOO_SUB_FLOATS / T));
+    size_t t_off[3] = {0, 0, 0}, pairs[3] = {0, 0, 0}, ntab = 0, ncls = 0, n = 0;
+    for (int c = 0; c < p.n_class; ++c) {
+        const int m = p.class_m[c];
+        if ((rc = check_dims(h, sub, m, L, L))) return rc;                     // every set size against "max_seqs"
+        pairs[c] = (size_t)m * (m - 1) / 2;
+        if (p.class_sets[c] > INT32_MAX || !mul_size((size_t)sub, (size_t)p.class_sets[c], pairs[c] * sizeof(float), &n) ||
+            !mul_size((size_t)sub, (size_t)p.class_sets[c], (size_t)m * L, &n))
+            return fail(h, PF_EINVAL, "%lld tile sets of %d x %d overflow the address space", (long long)p.class_sets[c], m, L);
+        t_off[c] = ntab;
+        ntab += (size_t)p.class_sets[c] * m;
+        ncls = std::max(ncls, (size_t)sub * (size_t)p.class_sets[c] * pairs[c]);
+    }
+    std::vector<int32_t> table;
+    std::vector<int64_t> members[3];           // the sets of every class, in (g, h) order
+    std::vector<float> cls, staged;
+    try {
+        table.resize(ntab);
+        for (int c = 0; c < p.n_class; ++c) members[c].reserve((size_t)p.class_sets[c]);
+        cls.resize(ncls);
+        staged.resize((size_t)sub * T);
+    } catch (const std::bad_alloc&) { return fail(h, PF_ENOMEM, "out of host memory for the %lld tile sets of N=%d, M=%d", (long long)p.S, N, M); }
+    int64_t k = 0;
+    for (int g = 0; g < p.G; ++g)
+        for (int g2 = g + 1; g2 < p.G; ++g2, ++k) {
+            const int c = p.class_of(p.rows(g) + p.rows(g2));
+            int32_t* row = table.data() + t_off[c] + members[c].size() * (size_t)p.class_m[c];
+            for (int r = p.bounds[g]; r < p.bounds[g + 1]; ++r) *row++ = r;
+            for (int r = p.bounds[g2]; r < p.bounds[g2 + 1]; ++r) *row++ = r;
+            members[c].push_back(k);
+        }
+    if ((rc = ensure_buffer(h, &h->d_idx, &h->d_idx_bytes, nidx))) return rc;
+    if ((rc = ensure_buffer(h, &h->d_map, &h->d_map_bytes, ntab * sizeof(int32_t)))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->d_idx, idx, nidx, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_map, table.data(), ntab * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    for (int b0 = 0; b0 < B; b0 += sub) {
+        const int nb = std::min(sub, B - b0);
+        for (int c = 0; c < p.n_class; ++c) {
+            const int m = p.class_m[c], Sc = (int)p.class_sets[c];
+            const size_t off_c = t_off[c];
+            rc = forward_derived(h, nullptr, nb, N, L, Sc, m, L, cls.data(), "tile sets",
+                                 [=](const uint8_t* d_src, int nbc, int j0, int nj, uint8_t* d_dst) -> int {
+                                     return launch_gather_taxa(h, d_src, nbc, N, L, h->d_map + off_c, j0, nj, m, d_dst);
+                                 }, nullptr, h->d_idx + (size_t)b0 * per_src);
+            if (rc) return rc;
+            for (int b = 0; b < nb; ++b)
+                for (int j = 0; j < Sc; ++j)
+                    memcpy(staged.data() + (size_t)b * T + (size_t)p.offset[(size_t)members[c][(size_t)j]],
+                           cls.data() + ((size_t)b * Sc + j) * pairs[c], pairs[c] * sizeof(float));
+        }
+        const size_t nsets = (size_t)nb * T, nres = (size_t)nb * PN;
+        if ((rc = ensure_buffer(h, &h->d_tiled, &h->d_tiled_bytes, (nsets + 2 * nres) * sizeof(float)))) return rc;
+        float *d_sets = h->d_tiled, *d_o = d_sets + nsets, *d_sp = d_o + nres;
+        HIPCHK(h, hipMemcpyAsync(d_sets, staged.data(), nsets * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        if ((rc = launch_tile_combine(h, d_sets, nb, d_o, d_sp))) return rc;
+        HIPCHK(h, hipMemcpyAsync(out + (size_t)b0 * PN, d_o, nres * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(spread + (size_t)b0 * PN, d_sp, nres * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return PF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1953,6 +2100,8 @@ int pf_destroy(pf_handle_t* h) {
     if (h->d_prof) hipFree(h->d_prof);
     if (h->d_loo) hipFree(h->d_loo);
     if (h->d_place) hipFree(h->d_place);
+    if (h->d_tiled_tab) hipFree(h->d_tiled_tab);
+    if (h->d_tiled) hipFree(h->d_tiled);
     if (h->d_w) hipFree(h->d_w);
     if (h->d_wst) hipFree(h->d_wst);
     if (h->d_wtab) hipFree(h->d_wtab);
@@ -2122,6 +2271,35 @@ int pf_place_stats_device(pf_handle_t* h, const float* d_whole, const float* d_b
         return fail(h, PF_EINVAL, "B=%d x %d query sets of %d sequences overflow the address space", B, Q, N + 1);
     HIPCHK(h, hipSetDevice(h->device));
     return launch_place_stats(h, d_whole, d_base, d_sets, B, N, Q, d_place, d_disturb, d_shift, d_joint);
+}
+
+int pf_tile_groups(int32_t N, int32_t M) {
+    const int64_t g = pftile::groups(N, M);
+    return g < 0 ? PF_EINVAL : (int)g;
+}
+
+int pf_tile_bound(int32_t N, int32_t M, int32_t g) {
+    const int64_t G = pftile::groups(N, M);
+    if (G < 0 || g < 0 || g > G) return PF_EINVAL;
+    return (int)pftile::bound(N, G, g);
+}
+
+int pf_forward_tiled(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, int32_t L, int32_t M, float* out, float* spread) {
+    if (!h) return PF_EINVAL;
+    return tiled_impl(h, idx, B, N, L, M, out, spread);
+}
+
+int pf_tile_combine_device(pf_handle_t* h, const float* d_sets, int32_t B, int32_t N, int32_t M, float* d_out, float* d_spread) {
+    if (!h) return PF_EINVAL;
+    if (!d_sets || !d_out || !d_spread) return fail(h, PF_EINVAL, "null buffer");
+    int rc = check_tiled_shape(h, B, N, M);
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    if ((rc = ensure_tiled_plan(h, N, M))) return rc;
+    size_t n = 0;
+    if (!mul_size((size_t)B, (size_t)h->tiled_plan.T, sizeof(float), &n))
+        return fail(h, PF_EINVAL, "B=%d x %lld set distances overflow the address space", B, (long long)h->tiled_plan.T);
+    return launch_tile_combine(h, d_sets, B, d_out, d_spread);
 }
 
 int pf_forward_device(pf_handle_t* h, const uint8_t* d_idx, int32_t B, int32_t N, int32_t L, float* d_out) {

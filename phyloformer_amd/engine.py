@@ -126,6 +126,10 @@ SIGNATURES = {
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pf_place_stats_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pf_forward_tiled": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "pf_tile_combine_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "pf_tile_groups": (C.c_int, [C.c_int32, C.c_int32]),
+    "pf_tile_bound": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
     "pf_forward_weighted": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "pf_forward_weighted_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "pf_forward_sites_weighted": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
@@ -144,7 +148,8 @@ CALL_TIME_SYMBOLS = frozenset({"pf_forward_site_map", "pf_forward_site_map_devic
                                "pf_forward_leave_one_out", "pf_loo_stats_device", "pf_forward_weighted",
                                "pf_forward_weighted_device", "pf_forward_sites_weighted", "pf_bootstrap_weighted",
                                "pf_padded_sites", "pf_boot_counts", "pf_compress_sites", "pf_forward_place",
-                               "pf_place_stats_device"})
+                               "pf_place_stats_device", "pf_forward_tiled", "pf_tile_combine_device", "pf_tile_groups",
+                               "pf_tile_bound"})
 
 _lib: Optional[C.CDLL] = None
 
@@ -474,6 +479,26 @@ class Engine:
         self._check(self._optional("pf_place_stats_device")(
             self._h, C.c_void_p(d_whole), C.c_void_p(d_base), C.c_void_p(d_sets), B, N, Q, C.c_void_p(d_place),
             C.c_void_p(d_disturb), C.c_void_p(d_shift), C.c_void_p(d_joint)))
+
+    # -- tiled inference -------------------------------------------------------------------
+    def forward_tiled(self, idx: np.ndarray, M: int) -> Tuple[np.ndarray, np.ndarray]:
+        """Tiled inference (``pf_forward_tiled``): ``uint8[B, N, L]`` with ``N > M >= 2`` → ``(out float32[B, P_N],
+        spread float32[B, P_N])`` (``[N, L]`` drops ``B``): the sets of ``tile.plan(N, M)`` are cut and forwarded on the
+        GPU, each on the path of its own shape, and combined there; bit for bit ``tile.combine`` of ``forward_taxa`` of
+        every set.  The sequence cap applies to ``M``, not to ``N``; ``N <= M`` raises ``ValueError`` (use ``forward``)."""
+        fn = self._optional("pf_forward_tiled")
+        idx, single = self._sources(idx)
+        B, N, L = idx.shape
+        out = np.empty((B, N * (N - 1) // 2), dtype=np.float32)
+        spread = np.empty_like(out)
+        self._check(fn(self._h, idx.ctypes.data, B, N, L, int(M), out.ctypes.data, spread.ctypes.data))
+        return (out[0], spread[0]) if single else (out, spread)
+
+    def tile_combine_device(self, d_sets: int, B: int, N: int, M: int, d_out: int, d_spread: int):
+        """``pf_tile_combine_device``: device ``sets float32 [B][T]`` (``tile.assemble``'s layout) → ``d_out``, ``d_spread
+        float32 [B][P_N]`` (asynchronous on the handle's stream)."""
+        self._check(self._optional("pf_tile_combine_device")(self._h, C.c_void_p(d_sets), B, N, M, C.c_void_p(d_out),
+                                                             C.c_void_p(d_spread)))
 
     # -- site weights -----------------------------------------------------------------------
     @staticmethod

@@ -74,11 +74,20 @@ def single_sequence_error(batch: int = 1) -> RuntimeError:
                         "dimension size -1 can be any value and is ambiguous")
 
 
-def too_many_seqs(n_seqs: int) -> Optional[Exception]:
+def over_seq_cap(n_seqs, modes: Sequence[Analysis] = ()):
+    """More than ``MAX_SEQS`` sequences, and none of the run's modes lifts the cap for such a file
+    (``Analysis.lifts_seq_cap``)?  Elementwise: an int or the array of a FastaBatch."""
+    over = np.asarray(n_seqs) > MAX_SEQS
+    for m in modes:
+        over = over & ~np.asarray(m.lifts_seq_cap(n_seqs), dtype=bool)
+    return over
+
+
+def too_many_seqs(n_seqs: int, modes: Sequence[Analysis] = ()) -> Optional[Exception]:
     """The reference's forward refuses more than 200 sequences (ValueError, adaptable_seq2pair, model.py:24-28) and fails
     on a single one (RuntimeError, attention.py:193) when the loop reaches that file; the runner raises the same error at
-    the same place in the order - after the files in front of it."""
-    if n_seqs > MAX_SEQS:
+    the same place in the order - after the files in front of it.  The cap is a question to the run's ``modes``."""
+    if over_seq_cap(n_seqs, modes):
         return ValueError(f"n_seqs must be smaller or equal to {MAX_SEQS} (or pre-compute a larger global_seq2pair)")
     if n_seqs == 1:
         return single_sequence_error()
@@ -323,7 +332,7 @@ class DirectoryRunner:
     def _file_error(self, path: str, n_seqs: int, n_sites: int) -> Optional[Exception]:
         """Why a parsed file cannot be run, if it cannot: the reference's own limits, then the modes' (``accepts``); an
         error for that file, raised where the loop reaches it."""
-        bad = too_many_seqs(n_seqs)
+        bad = too_many_seqs(n_seqs, self.modes)
         for m in self.modes:
             if bad is None and not m.accepts(n_seqs, n_sites):
                 bad = m.file_error(path, n_seqs, n_sites)
@@ -394,7 +403,7 @@ class DirectoryRunner:
             t0 = time.perf_counter()
             fb = inflight.popleft().result()
             self.stats["load_wait_s"] += time.perf_counter() - t0
-            ok = (fb.status == 0) & (fb.l > 0) & (fb.n <= MAX_SEQS) & (fb.n != 1)
+            ok = (fb.status == 0) & (fb.l > 0) & ~over_seq_cap(fb.n, self.modes) & (fb.n != 1)
             for m in self.modes:
                 ok &= m.accepts(fb.n, fb.l)
             stop = len(fb) if ok.all() else int(np.argmin(ok))
