@@ -114,6 +114,9 @@ const char* pf_last_error(const pf_handle_t* h);
  *   "debug_keep" int   1 = keep per-layer activations for pf_debug_read
  *   "force_rccl" int   1 = pf_comm_init creates a real RCCL communicator even for one rank (tests)
  *   "ws_limit_mb" int  workspace budget per batch chunk (default 24576)
+ *   "sub_floats" int   distances one sub-call of pf_forward_leave_one_out / pf_forward_place / pf_forward_tiled may
+ *                      hold on the device (default 4194304; <= 0 restores it); sub-calls are whole sources, one source
+ *                      always runs whole, and the results do not depend on it; tests/tuning
  *   "colstats_fine" int k_colstats blocks per pair group (0), per run of a group (1) or chosen from the batch
  *                      size (-1, default): the same summation tree either way, so the same bits; tests/tools
  *   "two_streams" int  0 = a batch runs on one stream; default 1: forwards of >= 2 alignments run as two

@@ -172,6 +172,8 @@ struct GenericWeights {
     std::vector<pfg::FfnW> ffn;
 };
 
+constexpr int64_t SUB_FLOATS_DEFAULT = (int64_t)1 << 22;
+
 }  // namespace
 
 struct pf_handle {
@@ -227,15 +229,14 @@ struct pf_handle {
     double* d_mpart = nullptr; size_t d_mpart_bytes = 0;
     float* d_se = nullptr; size_t d_se_bytes = 0;
     float* d_prof = nullptr; size_t d_prof_bytes = 0;
-    // pf_forward_leave_one_out (grow-only): one sub-call's full distances and its influence / shift / context
-    float* d_loo = nullptr; size_t d_loo_bytes = 0;
-    // pf_forward_place (grow-only): one sub-call's whole and backbone distances and its place / disturb / shift / joint
-    float* d_place = nullptr; size_t d_place_bytes = 0;
+    // the taxon-axis analyses (TaxonCuts: leave-one-out, placement, tiling): what one sub-call's reduction reads beside
+    // h->d_out and what it writes, carved from one grow-only buffer - the three are never live together
+    float* d_sub = nullptr; size_t d_sub_bytes = 0;
+    int64_t sub_floats = SUB_FLOATS_DEFAULT;    // option "sub_floats": distances one sub-call may hold on the device
     // pf_forward_tiled / pf_tile_combine_device: the plan of the last (N, M) and its device tables (offset int64 [S + 1],
-    // then bounds int32 [G + 1]); one sub-call's set distances [nb][T], then its out and spread [nb][P_N] (grow-only)
+    // then bounds int32 [G + 1]) (grow-only)
     pftile::Plan tiled_plan;
     char* d_tiled_tab = nullptr; size_t d_tiled_tab_bytes = 0;
-    float* d_tiled = nullptr; size_t d_tiled_bytes = 0;
     // weighted forwards (grow-only): the weight rows of a host call or of one chunk of derived alignments, what
     // k_weight_sums made of a call's rows ([..][4], pf_weights.hip.h), and the weight table of pf_forward_sites_weighted
     float* d_w = nullptr; size_t d_w_bytes = 0;
@@ -1058,18 +1059,26 @@ int ensure_buffer(pf_handle* h, T** p, size_t* have, size_t bytes) {
     return PF_OK;
 }
 
+// One launch of a small kernel on h->stream: go() is its header's launcher (a hipError_t), `kid` its profile slot,
+// `name` what a failure calls it.
+template <class Go>
+int launch_on_stream(pf_handle* h, int kid, const char* name, Go&& go) {
+    h->cur = h->stream;
+    ProfScope ps(h, kid);
+    const hipError_t e = go();
+    if (e != hipSuccess) return fail(h, PF_EHIP, "%s launch failed: %s", name, hipGetErrorString(e));
+    return PF_OK;
+}
+
 // ---- site weights (pf_forward_weighted*, pf_forward_sites_weighted, pf_bootstrap_weighted) ------
 // What k_weight_sums makes of the weight rows d_w [B][L] of a call, into the grow-only h->d_wst: asynchronous on
 // h->stream, behind whatever read the buffer before.
 int launch_weight_sums(pf_handle* h, const float* d_w, int B, int L, const float** d_wst) {
     int rc = ensure_buffer(h, &h->d_wst, &h->d_wst_bytes, (size_t)B * pfw::WST * sizeof(float));
     if (rc) return rc;
-    h->cur = h->stream;
-    ProfScope ps(h, K_WEIGHT_SUMS);
-    const hipError_t e = pfw::launch_weight_sums(h->stream, d_w, h->d_wst, B, L, h->bad_idx_dev + 2);
-    if (e != hipSuccess) return fail(h, PF_EHIP, "k_weight_sums launch failed: %s", hipGetErrorString(e));
     *d_wst = h->d_wst;
-    return PF_OK;
+    return launch_on_stream(h, K_WEIGHT_SUMS, "k_weight_sums",
+                            [&] { return pfw::launch_weight_sums(h->stream, d_w, h->d_wst, B, L, h->bad_idx_dev + 2); });
 }
 
 // What the weighted entry points refuse beside their unweighted twins, before any device work: a handle whose
@@ -1264,11 +1273,8 @@ int forward_host_impl(pf_handle* h, const uint8_t* idx, int B, int N, int l_begi
 }
 
 int launch_resample(pf_handle* h, const uint8_t* d_src, int B, int N, int L, int r_begin, int R, uint64_t seed, uint8_t* d_dst) {
-    h->cur = h->stream;
-    ProfScope ps(h, K_RESAMPLE);
-    const hipError_t e = pfb::launch_resample(h->stream, d_src, B, N, L, r_begin, R, seed, d_dst);
-    if (e != hipSuccess) return fail(h, PF_EHIP, "k_resample launch failed: %s", hipGetErrorString(e));
-    return PF_OK;
+    return launch_on_stream(h, K_RESAMPLE, "k_resample",
+                            [&] { return pfb::launch_resample(h->stream, d_src, B, N, L, r_begin, R, seed, d_dst); });
 }
 
 // a * b * c as size_t, false on overflow
@@ -1280,15 +1286,13 @@ bool mul_size(size_t a, size_t b, size_t c, size_t* out) {
 // map: device int32 - rows [..][K] of a site table (sites) or window starts [..] (start); sets s_begin .. s_begin + S - 1
 int launch_gather(pf_handle* h, const uint8_t* d_src, int B, int N, int L, const int32_t* d_sites, const int32_t* d_start,
                   int s_begin, int S, int K, uint8_t* d_dst) {
-    h->cur = h->stream;
-    ProfScope ps(h, K_GATHER);
-    const hipError_t e = pfs::launch_gather(h->stream, d_src, B, N, L, d_sites, d_start, s_begin, S, K, d_dst, h->bad_idx_dev + 1);
-    if (e != hipSuccess) return fail(h, PF_EHIP, "k_gather_sites launch failed: %s", hipGetErrorString(e));
-    return PF_OK;
+    return launch_on_stream(h, K_GATHER, "k_gather_sites", [&] {
+        return pfs::launch_gather(h->stream, d_src, B, N, L, d_sites, d_start, s_begin, S, K, d_dst, h->bad_idx_dev + 1);
+    });
 }
 
 // The one loop of every entry point that forwards alignments DERIVED from resident sources (pf_bootstrap,
-// pf_forward_sites, pf_forward_windows, pf_forward_taxa, pf_forward_leave_one_out): source b of idx [B][N][L] has S
+// pf_forward_sites, pf_forward_windows and, through TaxonCuts, the taxon-axis calls): source b of idx [B][N][L] has S
 // derived alignments of Nd x K (Nd = N for everything that cuts the site axis), and
 // fill(d_src, nb, j0, nj, d_dst) builds the derived alignments [j0, j0 + nj) of nb consecutive sources at d_src into
 // d_dst [nb][nj][Nd][K] on h->stream (k_resample for the bootstrap, k_gather_sites for site maps, k_gather_taxa for
@@ -1302,8 +1306,8 @@ int launch_gather(pf_handle* h, const uint8_t* d_src, int B, int N, int L, const
 // Weighted derived alignments (pf_forward_sites_weighted): wfill(nb, j0, nj, d_wdst) writes the same rectangle's weight
 // rows float [nb][nj][K] into d_wdst on h->stream - a chunk's live in the grow-only h->d_w - and the forward is the
 // weighted one; without wfill nothing changes.
-// Resident sources (pf_forward_place, which forwards several shapes from one upload): d_resident holds the B sources,
-// checked and uploaded by the caller on h->stream; idx is not read, h->d_idx is neither grown nor written.
+// Resident sources (TaxonCuts, which forwards several shapes and sub-calls from one upload): d_resident holds the B
+// sources, checked and uploaded by the caller on h->stream; idx is not read, h->d_idx is neither grown nor written.
 template <class Fill, class WFill = std::nullptr_t>
 int forward_derived(pf_handle* h, const uint8_t* idx, int B, int N, int L, int S, int Nd, int K, float* out, const char* what,
                     Fill&& fill, WFill&& wfill = nullptr, const uint8_t* d_resident = nullptr) {
@@ -1475,18 +1479,15 @@ int bootstrap_weighted_impl(pf_handle* h, const uint8_t* idx, int B, int N, int 
 // grow-only h->d_mpart, at most 64 MB of them (or one alignment's): larger batches are reduced in pieces - every
 // alignment's bits are its own, wherever a piece starts.
 int launch_site_moments(pf_handle* h, const float* d_map, int B, int P, int L, float* d_se, float* d_prof) {
-    h->cur = h->stream;
     const size_t per = pfm::part_count(1, P, L) * sizeof(double);
     const int nbc = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(B, 65535), ((size_t)64 << 20) / per));
     int rc = ensure_buffer(h, &h->d_mpart, &h->d_mpart_bytes, (size_t)nbc * per);
-    if (rc) return rc;
-    for (int b0 = 0; b0 < B; b0 += nbc) {
-        ProfScope ps(h, K_SITE_MOMENTS);
-        const hipError_t e = pfm::launch_site_moments(h->stream, d_map + (size_t)b0 * P * L, std::min(nbc, B - b0), P, L, h->d_mpart,
-                                                      d_se + (size_t)b0 * P, d_prof + (size_t)b0 * L);
-        if (e != hipSuccess) return fail(h, PF_EHIP, "k_site_moments launch failed: %s", hipGetErrorString(e));
-    }
-    return PF_OK;
+    for (int b0 = 0; b0 < B && !rc; b0 += nbc)
+        rc = launch_on_stream(h, K_SITE_MOMENTS, "k_site_moments", [&] {
+            return pfm::launch_site_moments(h->stream, d_map + (size_t)b0 * P * L, std::min(nbc, B - b0), P, L, h->d_mpart,
+                                            d_se + (size_t)b0 * P, d_prof + (size_t)b0 * L);
+        });
+    return rc;
 }
 
 // What the site-map entry points refuse beside what pf_forward refuses, before any device work.
@@ -1616,29 +1617,22 @@ int site_host_impl(pf_handle* h, const uint8_t* idx, int B, int N, int L, float*
 // taxa: device int32 [..][M]; sets s_begin .. s_begin + S - 1
 int launch_gather_taxa(pf_handle* h, const uint8_t* d_src, int B, int N, int L, const int32_t* d_taxa, int s_begin, int S, int M,
                        uint8_t* d_dst) {
-    h->cur = h->stream;
-    ProfScope ps(h, K_GATHER_TAXA);
-    const hipError_t e = pft::launch_gather_taxa(h->stream, d_src, B, N, L, d_taxa, s_begin, S, M, d_dst, h->bad_idx_dev + 1);
-    if (e != hipSuccess) return fail(h, PF_EHIP, "k_gather_taxa launch failed: %s", hipGetErrorString(e));
-    return PF_OK;
+    return launch_on_stream(h, K_GATHER_TAXA, "k_gather_taxa", [&] {
+        return pft::launch_gather_taxa(h->stream, d_src, B, N, L, d_taxa, s_begin, S, M, d_dst, h->bad_idx_dev + 1);
+    });
 }
 
 int launch_loo_stats(pf_handle* h, const float* d_full, const float* d_loo, int B, int N, float* d_infl, float* d_shift, float* d_ctx) {
-    h->cur = h->stream;
-    ProfScope ps(h, K_LOO_STATS);
-    const hipError_t e = pft::launch_loo_stats(h->stream, d_full, d_loo, B, N, d_infl, d_shift, d_ctx);
-    if (e != hipSuccess) return fail(h, PF_EHIP, "k_loo_taxon / k_loo_pair launch failed: %s", hipGetErrorString(e));
-    return PF_OK;
+    return launch_on_stream(h, K_LOO_STATS, "k_loo_taxon / k_loo_pair",
+                            [&] { return pft::launch_loo_stats(h->stream, d_full, d_loo, B, N, d_infl, d_shift, d_ctx); });
 }
 
-// What the taxon calls refuse beside what pf_forward refuses at the source's shape, before any device work: the same
-// at the derived shape (M, L), sizes that overflow, and a communicator of more than one rank.
-int check_taxa_call(pf_handle* h, int B, int N, int L, int S, int M, size_t* ntab) {
-    int rc = check_dims(h, B, N, L, L);
+// What every call that forwards S sets of M source rows refuses about the sets, before any device work: what pf_forward
+// refuses at their shape (M, L), a communicator of more than one rank, and sizes that overflow.  ntab: the bytes of a
+// table [S][M].
+int check_taxon_sets(pf_handle* h, int B, int L, int S, int M, size_t* ntab) {
+    int rc = check_dims(h, B, M, L, L);
     if (rc) return rc;
-    if (S < 1) return fail(h, PF_EINVAL, "a taxon table needs S >= 1 sets (got %d)", S);
-    if (M < 2) return fail(h, PF_EINVAL, "a taxon set needs M >= 2 rows (got %d)", M);
-    if ((rc = check_dims(h, B, M, L, L))) return rc;
     if (h->world > 1)
         return fail(h, PF_ESTATE, "taxon subsets are not site-sharded: this handle's communicator has %d ranks (use a handle "
                                   "without a communicator)", h->world);
@@ -1650,19 +1644,80 @@ int check_taxa_call(pf_handle* h, int B, int N, int L, int S, int M, size_t* nta
     return PF_OK;
 }
 
-// the S sets of a validated host table taxa [S][M], uploaded once into the grow-only h->d_map, through forward_derived
-int taxa_derived(pf_handle* h, const uint8_t* idx, int B, int N, int L, const int32_t* taxa, size_t ntab, int S, int M, float* out) {
-    bool uploaded = false;
-    return forward_derived(h, idx, B, N, L, S, M, L, out, "taxon sets", [&](const uint8_t* d_src, int nb, int j0, int nj, uint8_t* d_dst) -> int {
-        if (!uploaded) {
-            const int rc2 = ensure_buffer(h, &h->d_map, &h->d_map_bytes, ntab);
-            if (rc2) return rc2;
-            HIPCHK(h, hipMemcpyAsync(h->d_map, taxa, ntab, hipMemcpyHostToDevice, h->stream));
-            uploaded = true;
-        }
-        return launch_gather_taxa(h, d_src, nb, N, L, h->d_map, j0, nj, M, d_dst);
-    });
+// What the taxon calls refuse beside what pf_forward refuses at the source's shape (N, L), before any device work.
+int check_taxa_call(pf_handle* h, int B, int N, int L, int S, int M, size_t* ntab) {
+    int rc = check_dims(h, B, N, L, L);
+    if (rc) return rc;
+    if (S < 1) return fail(h, PF_EINVAL, "a taxon table needs S >= 1 sets (got %d)", S);
+    if (M < 2) return fail(h, PF_EINVAL, "a taxon set needs M >= 2 rows (got %d)", M);
+    return check_taxon_sets(h, B, L, S, M, ntab);
 }
+
+// whole sources per sub-call: together they hold at most "sub_floats" distances; one source always runs whole
+int sub_sources(const pf_handle* h, int B, size_t per_source) {
+    return (int)std::max<size_t>(1, std::min<size_t>((size_t)B, (size_t)h->sub_floats / per_source));
+}
+
+// The one driver of the host entry points that cut the taxon axis (pf_forward_taxa, pf_forward_leave_one_out,
+// pf_forward_place, pf_forward_tiled); the caller has checked its arguments and the residues.
+// upload() makes the B sources [N][L] resident in h->d_idx and the caller's row table in h->d_map, once per call: nothing
+// that writes h->d_idx (pf_forward's host path) may run after it.  cut() forwards sets of table rows of the current
+// sources: all B, until sub_calls() narrows them to one sub-call [b0, b0 + nb) at a time and drains the stream after each.
+// There carve() hands out the grow-only h->d_sub as consecutive spans, up() fills one from a host array of the sub-call
+// and down() returns one to the batch's host array at b0 * stride.
+struct TaxonCuts {
+    pf_handle* h;
+    int B, N, L;
+    int b0 = 0, nb = B;
+
+    int upload(const uint8_t* idx, const int32_t* table, size_t table_bytes) {
+        const size_t nidx = (size_t)B * N * L;
+        HIPCHK(h, hipSetDevice(h->device));
+        int rc = ensure_buffer(h, &h->d_idx, &h->d_idx_bytes, nidx);
+        if (rc || (rc = ensure_buffer(h, &h->d_map, &h->d_map_bytes, table_bytes))) return rc;
+        HIPCHK(h, hipMemcpyAsync(h->d_idx, idx, nidx, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->d_map, table, table_bytes, hipMemcpyHostToDevice, h->stream));
+        return PF_OK;
+    }
+    // The S sets of M rows each from entry t_off of the table, cut from every current source and forwarded on the path
+    // of (M, L), range re-check included, into host dst [nb][S][P_M].  reduce: a reduction will read them from h->d_out,
+    // so what the re-check replaced on the host goes up again first - the one place that rule is written.
+    int cut(size_t t_off, int S, int M, const char* what, float* dst, bool reduce = false) {
+        const int64_t before = h->rechecked;
+        const int32_t* d_rows = h->d_map + t_off;
+        const int rc = forward_derived(h, nullptr, nb, N, L, S, M, L, dst, what,
+                                       [this, d_rows, M](const uint8_t* d_src, int nbc, int j0, int nj, uint8_t* d_dst) -> int {
+                                           return launch_gather_taxa(h, d_src, nbc, N, L, d_rows, j0, nj, M, d_dst);
+                                       }, nullptr, h->d_idx + (size_t)b0 * N * L);
+        return !rc && reduce && h->rechecked != before ? up(h->d_out, dst, (size_t)S * M * (M - 1) / 2) : rc;
+    }
+    struct Span { float** p; size_t stride; };                  // `stride` floats for every current source
+    int carve(std::initializer_list<Span> spans) {
+        size_t total = 0;
+        for (const Span& s : spans) total += nb * s.stride;
+        if (const int rc = ensure_buffer(h, &h->d_sub, &h->d_sub_bytes, total * sizeof(float))) return rc;
+        float* at = h->d_sub;
+        for (const Span& s : spans) { *s.p = at; at += nb * s.stride; }
+        return PF_OK;
+    }
+    int copy(float* dst, const float* src, size_t stride, hipMemcpyKind kind) {         // the current sources' floats
+        HIPCHK(h, hipMemcpyAsync(dst, src, (size_t)nb * stride * sizeof(float), kind, h->stream));
+        return PF_OK;
+    }
+    float* part(float* host, size_t stride) const { return host + (size_t)b0 * stride; }
+    int up(float* d, const float* host_sub, size_t stride) { return copy(d, host_sub, stride, hipMemcpyHostToDevice); }
+    int down(float* host, const float* d, size_t stride) { return copy(part(host, stride), d, stride, hipMemcpyDeviceToHost); }
+    template <class Body>
+    int sub_calls(size_t per_source, Body&& body) {
+        const int sub = sub_sources(h, B, per_source);
+        for (b0 = 0; b0 < B; b0 += sub) {
+            nb = std::min(sub, B - b0);
+            if (const int rc = body()) return rc;
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+        }
+        return PF_OK;
+    }
+};
 
 int taxa_impl(pf_handle* h, const uint8_t* idx, int B, int N, int L, const int32_t* taxa, int S, int M, float* out) {
     size_t ntab = 0;
@@ -1673,16 +1728,15 @@ int taxa_impl(pf_handle* h, const uint8_t* idx, int B, int N, int L, const int32
     if (at >= 0)
         return fail(h, PF_EINVAL, "taxon %d at set %lld, position %lld is outside [0, %d)", (int)taxa[at], (long long)(at / M),
                     (long long)(at % M), N);
-    // (what is left - the residues - is refused by forward_derived before its first device call)
-    return taxa_derived(h, idx, B, N, L, taxa, ntab, S, M, out);
+    if ((rc = check_residues(h, idx, (size_t)B * N * L))) return rc;
+    TaxonCuts c{h, B, N, L};
+    if ((rc = c.upload(idx, taxa, ntab))) return rc;
+    return c.cut(0, S, M, "taxon sets", out);
 }
 
-// pf_forward_leave_one_out: pf_forward of the B sources, then their N cuts each (row t of the table: 0 .. N - 1 without
-// t) through forward_derived, in sub-calls of whole sources holding at most LOO_SUB_FLOATS distances - what `loo`
-// occupies on the device - and each sub-call's reduction on the device.  The reduction reads what the range re-check
-// left: if it replaced a set on the host, the sub-call's distances go up again first.
-constexpr size_t LOO_SUB_FLOATS = (size_t)1 << 22;
-
+// pf_forward_leave_one_out: pf_forward of the B sources - before the driver's upload, since its range re-check stages
+// into h->d_idx - then their N cuts each (row t of the table: 0 .. N - 1 without t) in sub-calls, each reduced on the
+// device from the cuts in h->d_out.
 int loo_impl(pf_handle* h, const uint8_t* idx, int B, int N, int L, float* out, float* loo, float* influence, float* shift,
              float* context) {
     int rc = check_dims(h, B, N, L, L);
@@ -1693,53 +1747,43 @@ int loo_impl(pf_handle* h, const uint8_t* idx, int B, int N, int L, float* out, 
     if (!out || !idx || !influence || !shift || !context) return fail(h, PF_EINVAL, "null buffer");
     if ((rc = check_residues(h, idx, (size_t)B * N * L))) return rc;
     const size_t P = (size_t)N * (N - 1) / 2, P1 = (size_t)(N - 1) * (N - 2) / 2, per_loo = (size_t)N * P1;
-    const int sub = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, LOO_SUB_FLOATS / per_loo));
     std::vector<int32_t> table;
     std::vector<float> tmp;
     try {
         table.resize((size_t)N * (N - 1));
-        if (!loo) tmp.resize((size_t)sub * per_loo);
+        if (!loo) tmp.resize((size_t)sub_sources(h, B, per_loo) * per_loo);
     } catch (const std::bad_alloc&) { return fail(h, PF_ENOMEM, "out of host memory for the leave-one-out sets of %d sequences", N); }
     for (int t = 0; t < N; ++t)
         for (int m = 0; m < N - 1; ++m) table[(size_t)t * (N - 1) + m] = m + (m >= t ? 1 : 0);
     if ((rc = forward_host_impl(h, idx, B, N, 0, L, L, out))) return rc;
-    for (int b0 = 0; b0 < B; b0 += sub) {
-        const int nb = std::min(sub, B - b0);
-        float* hl = loo ? loo + (size_t)b0 * per_loo : tmp.data();
-        const int64_t before = h->rechecked;
-        if ((rc = taxa_derived(h, idx + (size_t)b0 * N * L, nb, N, L, table.data(), ntab, N, N - 1, hl))) return rc;
-        const size_t nloo = (size_t)nb * per_loo * sizeof(float), nfull = (size_t)nb * P, nrow = (size_t)nb * N;
-        if (h->rechecked != before) HIPCHK(h, hipMemcpyAsync(h->d_out, hl, nloo, hipMemcpyHostToDevice, h->stream));
-        if ((rc = ensure_buffer(h, &h->d_loo, &h->d_loo_bytes, (2 * nfull + 2 * nrow) * sizeof(float)))) return rc;
-        float *d_full = h->d_loo, *d_ctx = d_full + nfull, *d_infl = d_ctx + nfull, *d_shift = d_infl + nrow;
-        HIPCHK(h, hipMemcpyAsync(d_full, out + (size_t)b0 * P, nfull * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        if ((rc = launch_loo_stats(h, d_full, h->d_out, nb, N, d_infl, d_shift, d_ctx))) return rc;
-        HIPCHK(h, hipMemcpyAsync(context + (size_t)b0 * P, d_ctx, nfull * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(influence + (size_t)b0 * N, d_infl, nrow * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(shift + (size_t)b0 * N, d_shift, nrow * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    return PF_OK;
+    TaxonCuts c{h, B, N, L};
+    if ((rc = c.upload(idx, table.data(), ntab))) return rc;
+    return c.sub_calls(per_loo, [&]() -> int {
+        int rc2 = c.cut(0, N, N - 1, "taxon sets", loo ? c.part(loo, per_loo) : tmp.data(), true);
+        if (rc2) return rc2;
+        float *d_full, *d_ctx, *d_infl, *d_shift;
+        if ((rc2 = c.carve({{&d_full, P}, {&d_ctx, P}, {&d_infl, (size_t)N}, {&d_shift, (size_t)N}}))) return rc2;
+        if ((rc2 = c.up(d_full, c.part(out, P), P))) return rc2;
+        if ((rc2 = launch_loo_stats(h, d_full, h->d_out, c.nb, N, d_infl, d_shift, d_ctx))) return rc2;
+        if ((rc2 = c.down(context, d_ctx, P)) || (rc2 = c.down(influence, d_infl, N))) return rc2;
+        return c.down(shift, d_shift, N);
+    });
 }
 
 // ---- query placement (pf_forward_place, pf_place_stats_device; pf_place.hip.h) ---------------
 
 int launch_place_stats(pf_handle* h, const float* d_whole, const float* d_base, const float* d_sets, int B, int N, int Q,
                        float* d_place, float* d_disturb, float* d_shift, float* d_joint) {
-    h->cur = h->stream;
-    ProfScope ps(h, K_PLACE_STATS);
-    const hipError_t e = pfpl::launch_place_stats(h->stream, d_whole, d_base, d_sets, B, N, Q, d_place, d_disturb, d_shift, d_joint);
-    if (e != hipSuccess) return fail(h, PF_EHIP, "k_place_rows / k_place_backbone launch failed: %s", hipGetErrorString(e));
-    return PF_OK;
+    return launch_on_stream(h, K_PLACE_STATS, "k_place_rows / k_place_backbone", [&] {
+        return pfpl::launch_place_stats(h->stream, d_whole, d_base, d_sets, B, N, Q, d_place, d_disturb, d_shift, d_joint);
+    });
 }
 
-// pf_forward_place: the B sources [M][L] go up once and stay in h->d_idx; three kinds of derived alignments are cut
-// from them through forward_derived - the whole (rows 0 .. M - 1: pf_forward's bits, and the resident bytes stay
-// intact where pf_forward's own re-check would stage over them), the backbone (rows 0 .. N - 1) and the Q sets
-// (rows 0 .. N - 1, N + q) - each on the path of its own shape.  Their row tables share one upload into h->d_map:
-// [Q][N + 1], then [N], then [M].  The sets run in sub-calls of whole sources holding at most LOO_SUB_FLOATS distances,
-// each followed by its reduction on the device, which reads what the range re-check left (pf_forward_leave_one_out's
-// rule).
+// pf_forward_place: three kinds of derived alignments are cut from the resident sources [M][L] - the whole (rows
+// 0 .. M - 1: pf_forward's bits, and the resident bytes stay intact where pf_forward's own re-check would stage over
+// them), the backbone (rows 0 .. N - 1) and the Q sets (rows 0 .. N - 1, N + q) - each on the path of its own shape.
+// Their row tables share one upload: [Q][N + 1], then [N], then [M].  The sets run in sub-calls, each reduced on the
+// device from the sets in h->d_out.
 int place_impl(pf_handle* h, const uint8_t* idx, int B, int M, int L, int Q, float* out, float* base, float* sets, float* place,
                float* disturb, float* shift, float* joint) {
     int rc = check_dims(h, B, M, L, L);
@@ -1747,22 +1791,21 @@ int place_impl(pf_handle* h, const uint8_t* idx, int B, int M, int L, int Q, flo
     if (Q < 1) return fail(h, PF_EINVAL, "placement needs Q >= 1 queries (got %d)", Q);
     if (M - Q < 2) return fail(h, PF_EINVAL, "placement needs a backbone of M - Q >= 2 sequences (got M=%d, Q=%d)", M, Q);
     const int N = M - Q;
-    size_t ntab = 0, n = 0;
-    if ((rc = check_taxa_call(h, B, M, L, Q, N + 1, &ntab))) return rc;        // (N + 1, L); one rank; the sets' sizes
+    size_t n = 0;
+    if ((rc = check_taxon_sets(h, B, L, Q, N + 1, &n))) return rc;              // the Q sets of N + 1 rows
     if ((rc = check_dims(h, B, N, L, L))) return rc;
     const size_t PM = (size_t)M * (M - 1) / 2, PN = (size_t)N * (N - 1) / 2, P1 = (size_t)(N + 1) * N / 2;
     if (!mul_size((size_t)B, PM, sizeof(float), &n) || !mul_size((size_t)B, (size_t)M, (size_t)L, &n))
         return fail(h, PF_EINVAL, "B=%d alignments of %d x %d overflow the address space", B, M, L);
     if (!out || !idx || !base || !place || !disturb || !shift || !joint) return fail(h, PF_EINVAL, "null buffer");
-    const size_t nidx = (size_t)B * M * L, per_src = (size_t)M * L, per_set = (size_t)Q * P1;
-    if ((rc = check_residues(h, idx, nidx))) return rc;
-    const int sub = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, LOO_SUB_FLOATS / per_set));
+    const size_t per_set = (size_t)Q * P1, nplace = (size_t)Q * N, nq = (size_t)Q;
+    if ((rc = check_residues(h, idx, (size_t)B * M * L))) return rc;
     const size_t t_base = (size_t)Q * (N + 1), t_whole = t_base + N;
     std::vector<int32_t> table;
     std::vector<float> tmp;
     try {
         table.resize(t_whole + M);
-        if (!sets) tmp.resize((size_t)sub * per_set);
+        if (!sets) tmp.resize((size_t)sub_sources(h, B, per_set) * per_set);
     } catch (const std::bad_alloc&) { return fail(h, PF_ENOMEM, "out of host memory for the sets of %d queries", Q); }
     for (int q = 0; q < Q; ++q) {
         for (int m = 0; m < N; ++m) table[(size_t)q * (N + 1) + m] = m;
@@ -1770,42 +1813,20 @@ int place_impl(pf_handle* h, const uint8_t* idx, int B, int M, int L, int Q, flo
     }
     for (int m = 0; m < N; ++m) table[t_base + m] = m;
     for (int m = 0; m < M; ++m) table[t_whole + m] = m;
-    HIPCHK(h, hipSetDevice(h->device));
-    if ((rc = ensure_buffer(h, &h->d_idx, &h->d_idx_bytes, nidx))) return rc;
-    if ((rc = ensure_buffer(h, &h->d_map, &h->d_map_bytes, table.size() * sizeof(int32_t)))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_idx, idx, nidx, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_map, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    // rows `t_off ..` of the table, Md to a set
-    auto cut = [&](size_t t_off, int Md) {
-        return [=](const uint8_t* d_src, int nb, int j0, int nj, uint8_t* d_dst) -> int {
-            return launch_gather_taxa(h, d_src, nb, M, L, h->d_map + t_off, j0, nj, Md, d_dst);
-        };
-    };
-    if ((rc = forward_derived(h, nullptr, B, M, L, 1, M, L, out, "alignments", cut(t_whole, M), nullptr, h->d_idx))) return rc;
-    if ((rc = forward_derived(h, nullptr, B, M, L, 1, N, L, base, "backbones", cut(t_base, N), nullptr, h->d_idx))) return rc;
-    for (int b0 = 0; b0 < B; b0 += sub) {
-        const int nb = std::min(sub, B - b0);
-        float* hs = sets ? sets + (size_t)b0 * per_set : tmp.data();
-        const int64_t before = h->rechecked;
-        if ((rc = forward_derived(h, nullptr, nb, M, L, Q, N + 1, L, hs, "query sets", cut(0, N + 1), nullptr,
-                                  h->d_idx + (size_t)b0 * per_src)))
-            return rc;
-        const size_t nwhole = (size_t)nb * PM, nbase = (size_t)nb * PN, nplace = (size_t)nb * Q * N, nrow = (size_t)nb * Q;
-        if (h->rechecked != before)
-            HIPCHK(h, hipMemcpyAsync(h->d_out, hs, (size_t)nb * per_set * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        if ((rc = ensure_buffer(h, &h->d_place, &h->d_place_bytes, (nwhole + nbase + nplace + 3 * nrow) * sizeof(float)))) return rc;
-        float *d_whole = h->d_place, *d_base = d_whole + nwhole, *d_pl = d_base + nbase, *d_dis = d_pl + nplace, *d_sh = d_dis + nrow,
-              *d_jt = d_sh + nrow;
-        HIPCHK(h, hipMemcpyAsync(d_whole, out + (size_t)b0 * PM, nwhole * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(d_base, base + (size_t)b0 * PN, nbase * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        if ((rc = launch_place_stats(h, d_whole, d_base, h->d_out, nb, N, Q, d_pl, d_dis, d_sh, d_jt))) return rc;
-        HIPCHK(h, hipMemcpyAsync(place + (size_t)b0 * Q * N, d_pl, nplace * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(disturb + (size_t)b0 * Q, d_dis, nrow * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(shift + (size_t)b0 * Q, d_sh, nrow * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(joint + (size_t)b0 * Q, d_jt, nrow * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    return PF_OK;
+    TaxonCuts c{h, B, M, L};
+    if ((rc = c.upload(idx, table.data(), table.size() * sizeof(int32_t)))) return rc;
+    if ((rc = c.cut(t_whole, 1, M, "alignments", out))) return rc;
+    if ((rc = c.cut(t_base, 1, N, "backbones", base))) return rc;
+    return c.sub_calls(per_set, [&]() -> int {
+        int rc2 = c.cut(0, Q, N + 1, "query sets", sets ? c.part(sets, per_set) : tmp.data(), true);
+        if (rc2) return rc2;
+        float *d_whole, *d_base, *d_pl, *d_dis, *d_sh, *d_jt;
+        if ((rc2 = c.carve({{&d_whole, PM}, {&d_base, PN}, {&d_pl, nplace}, {&d_dis, nq}, {&d_sh, nq}, {&d_jt, nq}}))) return rc2;
+        if ((rc2 = c.up(d_whole, c.part(out, PM), PM)) || (rc2 = c.up(d_base, c.part(base, PN), PN))) return rc2;
+        if ((rc2 = launch_place_stats(h, d_whole, d_base, h->d_out, c.nb, N, Q, d_pl, d_dis, d_sh, d_jt))) return rc2;
+        if ((rc2 = c.down(place, d_pl, nplace)) || (rc2 = c.down(disturb, d_dis, nq)) || (rc2 = c.down(shift, d_sh, nq))) return rc2;
+        return c.down(joint, d_jt, nq);
+    });
 }
 
 // ---- tiled inference (pf_forward_tiled, pf_tile_combine_device; pf_tile.hip.h, pf_tile_host.h) ----
@@ -1838,13 +1859,11 @@ int ensure_tiled_plan(pf_handle* h, int N, int M) {
 // d_sets [B][T] -> d_out, d_spread [B][P_N] by the resident plan
 int launch_tile_combine(pf_handle* h, const float* d_sets, int B, float* d_out, float* d_spread) {
     const pftile::Plan& p = h->tiled_plan;
-    h->cur = h->stream;
-    ProfScope ps(h, K_TILE_COMBINE);
     const int64_t* d_offset = reinterpret_cast<const int64_t*>(h->d_tiled_tab);
     const int32_t* d_bounds = reinterpret_cast<const int32_t*>(h->d_tiled_tab + p.offset.size() * sizeof(int64_t));
-    const hipError_t e = pftile::launch_tile_combine(h->stream, d_sets, d_bounds, d_offset, B, p.N, p.G, p.T, d_out, d_spread);
-    if (e != hipSuccess) return fail(h, PF_EHIP, "k_tile_combine launch failed: %s", hipGetErrorString(e));
-    return PF_OK;
+    return launch_on_stream(h, K_TILE_COMBINE, "k_tile_combine", [&] {
+        return pftile::launch_tile_combine(h->stream, d_sets, d_bounds, d_offset, B, p.N, p.G, p.T, d_out, d_spread);
+    });
 }
 
 // What pf_forward_tiled and pf_tile_combine_device refuse about (B, N, M) beside the handle's own state: the context, the
@@ -1865,12 +1884,11 @@ int check_tiled_shape(pf_handle* h, int B, int N, int M) {
     return PF_OK;
 }
 
-// pf_forward_tiled: the B sources [N][L] go up once and stay in h->d_idx.  The sets of one size - a class, at most three -
-// share a row table [S_c][m_c]; the tables go up once into h->d_map, and every class runs through forward_derived with
-// k_gather_taxa as its fill, so that every set takes pf_forward's path for (m_c, L), range re-check included.  The class
-// results are assembled on the host into the [nb][T] layout of k_tile_combine - after the re-check has replaced flagged
-// sets - uploaded once and combined on the device.  Sub-calls of whole sources keep [nb][T] within LOO_SUB_FLOATS; one
-// source always runs whole.  Nothing is written to out / spread before the first sub-call has succeeded.
+// pf_forward_tiled: the sets of one size - a class, at most three - share a row table [S_c][m_c]; the tables go up
+// together, and every class is one cut, so that every set takes pf_forward's path for (m_c, L), range re-check included.
+// The class results are assembled on the host into the [nb][T] layout of k_tile_combine - after the re-check has
+// replaced flagged sets - uploaded once and combined on the device, T distances per source to a sub-call.  Nothing is
+// written to out / spread before the first sub-call has succeeded.
 int tiled_impl(pf_handle* h, const uint8_t* idx, int B, int N, int L, int M, float* out, float* spread) {
     int rc = check_tiled_shape(h, B, N, M);
     if (rc) return rc;
@@ -1886,8 +1904,8 @@ int tiled_impl(pf_handle* h, const uint8_t* idx, int B, int N, int L, int M, flo
     HIPCHK(h, hipSetDevice(h->device));
     if ((rc = ensure_tiled_plan(h, N, M))) return rc;
     const pftile::Plan& p = h->tiled_plan;
-    const size_t T = (size_t)p.T, PN = (size_t)N * (N - 1) / 2, per_src = (size_t)N * L;
-    const int sub = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, LOO_SUB_FLOATS / T));
+    const size_t T = (size_t)p.T, PN = (size_t)N * (N - 1) / 2;
+    const int sub = sub_sources(h, B, T);
     size_t t_off[3] = {0, 0, 0}, pairs[3] = {0, 0, 0}, ntab = 0, ncls = 0, n = 0;
     for (int c = 0; c < p.n_class; ++c) {
         const int m = p.class_m[c];
@@ -1918,35 +1936,25 @@ int tiled_impl(pf_handle* h, const uint8_t* idx, int B, int N, int L, int M, flo
             for (int r = p.bounds[g2]; r < p.bounds[g2 + 1]; ++r) *row++ = r;
             members[c].push_back(k);
         }
-    if ((rc = ensure_buffer(h, &h->d_idx, &h->d_idx_bytes, nidx))) return rc;
-    if ((rc = ensure_buffer(h, &h->d_map, &h->d_map_bytes, ntab * sizeof(int32_t)))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_idx, idx, nidx, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_map, table.data(), ntab * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    for (int b0 = 0; b0 < B; b0 += sub) {
-        const int nb = std::min(sub, B - b0);
-        for (int c = 0; c < p.n_class; ++c) {
-            const int m = p.class_m[c], Sc = (int)p.class_sets[c];
-            const size_t off_c = t_off[c];
-            rc = forward_derived(h, nullptr, nb, N, L, Sc, m, L, cls.data(), "tile sets",
-                                 [=](const uint8_t* d_src, int nbc, int j0, int nj, uint8_t* d_dst) -> int {
-                                     return launch_gather_taxa(h, d_src, nbc, N, L, h->d_map + off_c, j0, nj, m, d_dst);
-                                 }, nullptr, h->d_idx + (size_t)b0 * per_src);
-            if (rc) return rc;
-            for (int b = 0; b < nb; ++b)
+    TaxonCuts c{h, B, N, L};
+    if ((rc = c.upload(idx, table.data(), ntab * sizeof(int32_t)))) return rc;
+    return c.sub_calls(T, [&]() -> int {
+        for (int cl = 0; cl < p.n_class; ++cl) {
+            const int Sc = (int)p.class_sets[cl];
+            const int rc2 = c.cut(t_off[cl], Sc, p.class_m[cl], "tile sets", cls.data());
+            if (rc2) return rc2;
+            for (int b = 0; b < c.nb; ++b)
                 for (int j = 0; j < Sc; ++j)
-                    memcpy(staged.data() + (size_t)b * T + (size_t)p.offset[(size_t)members[c][(size_t)j]],
-                           cls.data() + ((size_t)b * Sc + j) * pairs[c], pairs[c] * sizeof(float));
+                    memcpy(staged.data() + (size_t)b * T + (size_t)p.offset[(size_t)members[cl][(size_t)j]],
+                           cls.data() + ((size_t)b * Sc + j) * pairs[cl], pairs[cl] * sizeof(float));
         }
-        const size_t nsets = (size_t)nb * T, nres = (size_t)nb * PN;
-        if ((rc = ensure_buffer(h, &h->d_tiled, &h->d_tiled_bytes, (nsets + 2 * nres) * sizeof(float)))) return rc;
-        float *d_sets = h->d_tiled, *d_o = d_sets + nsets, *d_sp = d_o + nres;
-        HIPCHK(h, hipMemcpyAsync(d_sets, staged.data(), nsets * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        if ((rc = launch_tile_combine(h, d_sets, nb, d_o, d_sp))) return rc;
-        HIPCHK(h, hipMemcpyAsync(out + (size_t)b0 * PN, d_o, nres * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(spread + (size_t)b0 * PN, d_sp, nres * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    return PF_OK;
+        float *d_sets, *d_o, *d_sp;
+        int rc2 = c.carve({{&d_sets, T}, {&d_o, PN}, {&d_sp, PN}});
+        if (rc2 || (rc2 = c.up(d_sets, staged.data(), T))) return rc2;
+        if ((rc2 = launch_tile_combine(h, d_sets, c.nb, d_o, d_sp))) return rc2;
+        if ((rc2 = c.down(out, d_o, PN))) return rc2;
+        return c.down(spread, d_sp, PN);
+    });
 }
 
 }  // namespace
@@ -2098,10 +2106,8 @@ int pf_destroy(pf_handle_t* h) {
     if (h->d_mpart) hipFree(h->d_mpart);
     if (h->d_se) hipFree(h->d_se);
     if (h->d_prof) hipFree(h->d_prof);
-    if (h->d_loo) hipFree(h->d_loo);
-    if (h->d_place) hipFree(h->d_place);
+    if (h->d_sub) hipFree(h->d_sub);
     if (h->d_tiled_tab) hipFree(h->d_tiled_tab);
-    if (h->d_tiled) hipFree(h->d_tiled);
     if (h->d_w) hipFree(h->d_w);
     if (h->d_wst) hipFree(h->d_wst);
     if (h->d_wtab) hipFree(h->d_wtab);
@@ -2145,6 +2151,7 @@ int pf_set_option(pf_handle_t* h, const char* key, int64_t value) {
         h->phase_prof_last = value == 2;
     }
     else if (k == "ws_limit_mb") h->ws_limit_bytes = value << 20;
+    else if (k == "sub_floats") h->sub_floats = value > 0 ? value : SUB_FLOATS_DEFAULT;
     else return fail(h, PF_EINVAL, "unknown option '%s'", key);
     return PF_OK;
 }

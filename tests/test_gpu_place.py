@@ -9,6 +9,7 @@ import sys
 import numpy as np
 import pytest
 
+from helpers.profiled import Profiled as _Profiled
 from phyloformer_amd import place as PL
 from phyloformer_amd.engine import Engine
 from phyloformer_amd.msa_sim import simulate_batch
@@ -27,19 +28,6 @@ NAMES = ("out", "base", "place", "disturb", "shift", "joint", "sets")
 
 def _bits(a):
     return np.ascontiguousarray(a).view(np.uint32)
-
-
-class _Profiled:
-    def __init__(self, e):
-        self.e = e
-
-    def __enter__(self):
-        self.e.set_option("profile", 1)
-        self.e.profile_reset()
-        return self.e
-
-    def __exit__(self, *exc):
-        self.e.set_option("profile", 0)
 
 
 @pytest.fixture(scope="module")

@@ -9,6 +9,7 @@ import sys
 import numpy as np
 import pytest
 
+from helpers.profiled import Profiled as _Profiled
 from phyloformer_amd import taxa as T
 from phyloformer_amd.engine import Engine
 from phyloformer_amd.msa_sim import simulate_batch
@@ -36,19 +37,6 @@ def _check_taxa(e, idx, taxa):
 def _subsets(N, S, M, seed):
     rng = np.random.default_rng(seed)
     return np.stack([np.sort(rng.choice(N, size=M, replace=False)) for _ in range(S)]).astype(np.int32)
-
-
-class _Profiled:
-    def __init__(self, e):
-        self.e = e
-
-    def __enter__(self):
-        self.e.set_option("profile", 1)
-        self.e.profile_reset()
-        return self.e
-
-    def __exit__(self, *exc):
-        self.e.set_option("profile", 0)
 
 
 # ---- the gather alone ----------------------------------------------------------------------------------------------

@@ -8,6 +8,7 @@ import sys
 import numpy as np
 import pytest
 
+from helpers.profiled import Profiled as _Profiled
 from phyloformer_amd import tile as TL
 from phyloformer_amd.engine import Engine
 from phyloformer_amd.taxa import pair_index
@@ -56,19 +57,6 @@ def _assert_cross_copies(out, spread, sets, N, M):
                 q = pair_index(i, j, N)
                 assert np.array_equal(_bits(out[:, q]), _bits(sets[k][:, pair_index(a, ng + c, ng + p.rows(h))])), (i, j)
                 assert (_bits(spread[:, q]) == 0).all(), (i, j)          # +0.0 exactly
-
-
-class _Profiled:
-    def __init__(self, e):
-        self.e = e
-
-    def __enter__(self):
-        self.e.set_option("profile", 1)
-        self.e.profile_reset()
-        return self.e
-
-    def __exit__(self, *exc):
-        self.e.set_option("profile", 0)
 
 
 def _tiled(e, idx, M):
