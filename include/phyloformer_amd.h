@@ -351,6 +351,29 @@ int pf_tile_combine_device(pf_handle_t* h, const float* d_sets, int32_t B, int32
 int pf_tile_groups(int32_t N, int32_t M);
 int pf_tile_bound(int32_t N, int32_t M, int32_t g);
 
+/* ---- neighbour joining on the device: trees beyond the sequence cap (additive to ABI 5) ----
+ *
+ * The join sequence of neighbour joining (phyloformer_amd/nj.py::nj_joins; pf_nj_newick_n's nj_core is its host twin)
+ * computed on the GPU, bit for bit: the symmetric double matrix of preds (pf_nj_newick_n's), numpy's pairwise row sums
+ * of the active sub-matrix, q = ((m - 2) d_ab - r_a) - r_b without FMA, its first minimum in row-major order, the branch
+ * lengths and the new node's distances - every float64 operation with the operands and in the order of the host code
+ * (csrc/pf_nj.hip.h, csrc/pf_nj_host.h).  3 (N - 3) + 2 launches per call on the handle's stream,
+ * no copy to the host and no synchronisation between them.  One call with B sources equals B calls with one.
+ *   preds     float  [B][P_N]            pairs i < j in lexicographic order (pf_forward's output)
+ *   slots     int32  [B][2 (N - 3) + 3]  a, b of every join (slot a < slot b; the new cluster takes slot a), then the
+ *                                        three slots i, j, k of the trifurcation
+ *   lengths   double [B][2 (N - 3) + 3]  la, lb of every join, then li, lj, lk
+ *   nonfinite uint8  [B]                 1: the source holds a NaN or an infinity; its slots and lengths are UNSPECIFIED
+ *                                        (the payload of a NaN made on the device is not the host's: run pf_nj_newick_n
+ *                                        for such a source); 0: finite input, the table is nj_joins' bit for bit
+ * pf_nj_joins takes host arrays and is synchronous; pf_nj_joins_device takes device arrays and is asynchronous on the
+ * handle's stream.  The state is B N^2 doubles: sources run side by side in chunks that fit "ws_limit_mb"; one source
+ * always runs whole.  Refused with PF_EINVAL before any device work: N < 3, B < 1; NULL buffers; P_N >= 2^31; an N whose
+ * N^2 doubles alone exceed "ws_limit_mb" (the message names the bytes).  pf_profile_get("nj_joins") counts the calls. */
+int pf_nj_joins(pf_handle_t* h, const float* preds, int32_t B, int32_t N, int32_t* slots, double* lengths, uint8_t* nonfinite);
+int pf_nj_joins_device(pf_handle_t* h, const float* d_preds, int32_t B, int32_t N, int32_t* d_slots, double* d_lengths,
+                       uint8_t* d_nonfinite);
+
 /* ---- site weights: weighted forward, pattern compression, bootstrap on distinct sites (additive to ABI 5) ----
  *
  * Nothing in the network depends on a site's position, and every reduction over sites is a plain sum (the row-attention
@@ -480,7 +503,9 @@ int pf_memcpy_d2h(pf_handle_t* h, void* dst, const void* src, size_t bytes);
  * pf_site_moments_device), "gather_taxa" (k_gather_taxa of pf_forward_taxa / pf_forward_leave_one_out /
  * pf_gather_taxa_device), "loo_stats" (the reduction of pf_forward_leave_one_out / pf_loo_stats_device).
  * "weight_sums" (k_weight_sums of the weighted forwards), "place_stats" (the reduction of pf_forward_place /
- * pf_place_stats_device), "tile_combine" (k_tile_combine of pf_forward_tiled / pf_tile_combine_device).  Totals accumulate until reset.  "collectives" returns the number of all-reduces issued since the last reset in
+ * pf_place_stats_device), "tile_combine" (k_tile_combine of pf_forward_tiled / pf_tile_combine_device).  Totals accumulate until reset.
+ * "nj_joins" returns the number of pf_nj_joins / pf_nj_joins_device calls since the last reset in *launches (counted
+ * always; *total_ms = 0).  "collectives" returns the number of all-reduces issued since the last reset in
  * *launches (counted always, no profiling option needed; *total_ms = 0); "rechecked" likewise the number of
  * alignments the range re-check (option "recheck_above") computed again on the float64 kernels. */
 int pf_profile_reset(pf_handle_t* h);
@@ -586,6 +611,12 @@ int64_t pf_format_phylip_n(const float* preds, int32_t n, const char* const* ids
  * pf_format_phylip (out = NULL, cap = 0 first). */
 int64_t pf_nj_newick_n(const float* preds, int32_t n, const char* const* ids, const int64_t* id_lens, int32_t clamp_negative,
                        char* out, int64_t cap);
+
+/* The Newick text of a join table (pf_nj_joins' slots / lengths [2 (n - 3) + 3] of ONE source, n >= 3): the text
+ * nj.py::newick_of_joins writes for it, hence pf_nj_newick_n's when the table is that of the same distances.  No
+ * device, no handle.  PF_EINVAL also for a slot outside [0, n).  Sizing protocol as pf_format_phylip. */
+int64_t pf_nj_format_joins_n(const int32_t* slots, const double* lengths, int32_t n, const char* const* ids, const int64_t* id_lens,
+                             int32_t clamp_negative, char* out, int64_t cap);
 
 /* ---- many files per call, on native threads (ABI 4; tree_paths: ABI 5) ---------------------------
  *

@@ -10,6 +10,7 @@ A mode plays one of two roles in a launch (``DirectoryRunner._launch``):
 """
 from __future__ import annotations
 
+import time
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -24,6 +25,14 @@ import numpy as np
 FLOATS = 1 << 22
 
 SHARD_SITES = "--shard sites"
+
+# From this many sequences on, a file that ``--tile`` lifts over the cap gets its ``-t`` tree from the device
+# (``Engine.nj_joins``) instead of from the writer thread's host neighbour joining.  A measured constant (DESIGN.md
+# section 20, tools/nj_bench.py, profiles/nj_bench.txt): the smallest measured N at which the device side takes at most
+# half the host's time - it occupies the GPU thread, where the host's overlaps the next launch.  Never below 201: no file
+# that ran before the device path existed changes path.  None = the device path is off.
+NJ_DEVICE_MIN = 256
+assert NJ_DEVICE_MIN is None or NJ_DEVICE_MIN >= 201
 
 
 def sub_batches(count: int, floats_each: int) -> List[slice]:
@@ -82,6 +91,11 @@ class Analysis:
     def lifts_seq_cap(self, n):
         """Does this mode run a file of ``n`` sequences that exceeds the reference's cap (``scheduler.MAX_SEQS``)?
         Elementwise, like ``accepts``."""
+        return False
+
+    def writes_tree(self, shape: Tuple[int, int]) -> bool:
+        """With ``--trees``: does this mode write ``<stem>.nj.nwk`` of a file of this shape itself (``write``)?  The
+        launch's default writer then leaves the tree to it - it is computed once."""
         return False
 
     def floats(self, shape: Tuple[int, int]) -> int:
@@ -418,8 +432,8 @@ class Tile(Analysis):
             "at most M sequences (cut and inferred on the GPU, about twice the tokens of one forward, the memory of "
             "one context) and the results are combined on the GPU: <stem>.phy holds, for two sequences of different "
             "groups, the distance of the one context they share and, for two of one group, the mean over all the "
-            "contexts of that group (with -t <stem>.nj.nwk is the NJ tree of these distances; at thousands of "
-            "sequences it takes seconds on a writer thread); writes <stem>.spread.phy, the standard deviation of "
+            "contexts of that group (with -t <stem>.nj.nwk is the NJ tree of these distances; a file of " + str(NJ_DEVICE_MIN) + " "
+            "sequences or more has it joined on the GPU, the same bytes); writes <stem>.spread.phy, the standard deviation of "
             "every within-group distance over its contexts (0 across groups: one context, nothing measured; "
             "descriptive, not a test) and <stem>.tile.tsv (index, id, group); a file with at most M sequences runs "
             "exactly as without the flag; M must be between 2 and the model's cap of 200; 0 (default) = off")
@@ -442,7 +456,7 @@ class Tile(Analysis):
         return cls(args.tile) if args.tile else None
 
     def stats(self):
-        return {"tiled": 0, "tile_sets": 0}
+        return {"tiled": 0, "tile_sets": 0, "nj_device": 0, "nj_device_s": 0.0}
 
     def lifts_seq_cap(self, n):
         return n > self.context
@@ -453,7 +467,14 @@ class Tile(Analysis):
         if shape[0] <= self.context:
             return engine.forward(batch), ()
         out, spread = engine.forward_tiled(batch, self.context)
-        return out, (spread,)
+        tables = [None] * len(out)
+        if runner.trees and self.writes_tree(shape):
+            # the joins of every file's tree on the device; a file with a non-finite distance keeps the host's
+            t0 = time.perf_counter()
+            slots, lengths, nonfinite = engine.nj_joins(out)
+            tables = [None if bad else (s, l) for s, l, bad in zip(slots, lengths, nonfinite)]
+            runner.book(nj_device=sum(t is not None for t in tables), nj_device_s=time.perf_counter() - t0)
+        return out, (spread, tables)
 
     def account(self, stats, count, shape, seconds):
         if shape[0] > self.context:
@@ -462,12 +483,19 @@ class Tile(Analysis):
             stats["tiled"] += count
             stats["tile_sets"] += count * G * (G - 1) // 2
 
-    def write(self, runner, shape, entry, pred, spread):
-        """``<stem>.spread.phy`` (ids and number format of ``<stem>.phy``) and ``<stem>.tile.tsv`` of one file."""
+    def writes_tree(self, shape):
+        return NJ_DEVICE_MIN is not None and shape[0] > self.context and shape[0] >= NJ_DEVICE_MIN
+
+    def write(self, runner, shape, entry, pred, spread, table):
+        """``<stem>.spread.phy`` (ids and number format of ``<stem>.phy``) and ``<stem>.tile.tsv`` of one file; where the
+        tree is this mode's (``writes_tree``), ``<stem>.nj.nwk`` from the device's join table - the bytes of the host's
+        neighbour joining, which a file without a table (non-finite distances) falls back to."""
         from .tile import tile_tsv
         ids = entry.ids()
         runner.put(entry.path, "spread.phy", runner.phylip(spread, ids))
         runner.put(entry.path, "tile.tsv", tile_tsv(ids, self.context))
+        if runner.trees and self.writes_tree(shape):
+            runner.put(entry.path, "nj.nwk", runner.nj(pred, ids) if table is None else runner.newick_of_joins(*table, ids))
 
 
 MODES = (Bootstrap, Windows, SiteProfile, LeaveOneOut, CompressSites, Place, Tile)

@@ -448,6 +448,28 @@ int64_t pf_nj_newick_n(const float* preds, int32_t n, const char* const* ids, co
     } catch (...) { return PF_ENOMEM; }
 }
 
+// The Newick text of a join table (pf_nj_joins: slots / lengths [2 (n - 3) + 3], n >= 3) through nj_format: the text
+// of nj.py::newick_of_joins, and of pf_nj_newick_n for the table of the same distances.  PF_EINVAL also for a slot
+// outside [0, n).
+int64_t pf_nj_format_joins_n(const int32_t* slots, const double* lengths, int32_t n, const char* const* ids, const int64_t* id_lens,
+                             int32_t clamp_negative, char* out, int64_t cap) {
+    if (!slots || !lengths || n < 3 || !ids || !id_lens || (!out && cap > 0)) return PF_EINVAL;
+    for (int32_t i = 0; i < n; ++i) if (id_lens[i] < 0) return PF_EINVAL;
+    const size_t joins = (size_t)n - 3, len = 2 * joins + 3;
+    for (size_t k = 0; k < len; ++k) if (slots[k] < 0 || slots[k] >= n) return PF_EINVAL;
+    try {
+        NjTree t;
+        t.joins.reserve(joins);
+        for (size_t s = 0; s < joins; ++s) t.joins.push_back({slots[2 * s], slots[2 * s + 1], lengths[2 * s], lengths[2 * s + 1]});
+        t.i = slots[2 * joins]; t.j = slots[2 * joins + 1]; t.k = slots[2 * joins + 2];
+        t.li = lengths[2 * joins]; t.lj = lengths[2 * joins + 1]; t.lk = lengths[2 * joins + 2];
+        std::string text;
+        nj_format(t, n, ids, id_lens, clamp_negative != 0, nullptr, text);
+        if (out && (int64_t)text.size() <= cap) memcpy(out, text.data(), text.size());
+        return (int64_t)text.size();
+    } catch (...) { return PF_ENOMEM; }
+}
+
 }  // extern "C"
 
 extern "C" {

@@ -44,6 +44,7 @@
 #include "pf_taxa.hip.h"
 #include "pf_place.hip.h"
 #include "pf_tile.hip.h"
+#include "pf_nj.hip.h"
 #include "pf_weights.hip.h"
 #include "pf_weights_host.h"
 #include "pf_host_prep.h"
@@ -237,6 +238,11 @@ struct pf_handle {
     // then bounds int32 [G + 1]) (grow-only)
     pftile::Plan tiled_plan;
     char* d_tiled_tab = nullptr; size_t d_tiled_tab_bytes = 0;
+    // pf_nj_joins / pf_nj_joins_device (grow-only): the state of one chunk of sources (d, r, partial minima, active
+    // slots), and the staging of a host call's chunk (lengths, preds, slots, flags)
+    char* d_nj = nullptr; size_t d_nj_bytes = 0;
+    char* d_nj_io = nullptr; size_t d_nj_io_bytes = 0;
+    int64_t nj_calls = 0;        // calls since the last pf_profile_reset ("nj_joins")
     // weighted forwards (grow-only): the weight rows of a host call or of one chunk of derived alignments, what
     // k_weight_sums made of a call's rows ([..][4], pf_weights.hip.h), and the weight table of pf_forward_sites_weighted
     float* d_w = nullptr; size_t d_w_bytes = 0;
@@ -1957,6 +1963,85 @@ int tiled_impl(pf_handle* h, const uint8_t* idx, int B, int N, int L, int M, flo
     });
 }
 
+// ---- neighbour joining on the device (pf_nj_joins, pf_nj_joins_device; pf_nj.hip.h, pf_nj_host.h) ----
+
+// What both entry points refuse about (B, N), and the sources of one chunk: as many as fit "ws_limit_mb" side by side,
+// one at least - a single source's state above the limit is refused.
+int check_nj_shape(pf_handle* h, int B, int N, int* chunk) {
+    if (B < 1) return fail(h, PF_EINVAL, "bad dimensions B=%d N=%d", B, N);
+    if (N < 3) return fail(h, PF_EINVAL, "neighbour joining needs N >= 3 sequences (got %d)", N);
+    const int64_t PN = (int64_t)N * (N - 1) / 2;
+    size_t n = 0;
+    if (PN >= ((int64_t)1 << 31) || !mul_size((size_t)B, (size_t)PN, sizeof(float), &n) ||
+        !mul_size((size_t)B, (size_t)pfnj::table_len(N), sizeof(double), &n))
+        return fail(h, PF_EINVAL, "B=%d alignments of N=%d sequences: their %lld pairs each overflow a distance vector", B, N, (long long)PN);
+    const size_t per = pfnj::state_bytes(N);
+    if ((int64_t)per > h->ws_limit_bytes)
+        return fail(h, PF_EINVAL, "neighbour joining of N=%d sequences needs %zu bytes of state per source (N^2 doubles), above the "
+                                  "workspace limit of %lld bytes (option ws_limit_mb)", N, per, (long long)h->ws_limit_bytes);
+    *chunk = (int)std::min<size_t>(std::min(B, pfnj::NJ_MAX_Y), (size_t)h->ws_limit_bytes / per);
+    return PF_OK;
+}
+
+// the join sequences of nb <= chunk sources on device arrays, enqueued on h->stream
+int launch_nj_chunk(pf_handle* h, const float* d_preds, int nb, int N, int32_t* d_slots, double* d_lengths, uint8_t* d_flag) {
+    const int rc = ensure_buffer(h, &h->d_nj, &h->d_nj_bytes, (size_t)nb * pfnj::state_bytes(N));
+    if (rc) return rc;
+    h->cur = h->stream;
+    const pfnj::Args a = pfnj::carve(h->d_nj, d_preds, nb, N, d_slots, d_lengths, d_flag);
+    const hipError_t e = pfnj::launch_nj(h->stream, a, nb);
+    if (e != hipSuccess) return fail(h, PF_EHIP, "k_nj_* launch failed: %s", hipGetErrorString(e));
+    return PF_OK;
+}
+
+int nj_device_impl(pf_handle* h, const float* d_preds, int B, int N, int32_t* d_slots, double* d_lengths, uint8_t* d_flag) {
+    if (!d_preds || !d_slots || !d_lengths || !d_flag) return fail(h, PF_EINVAL, "null buffer");
+    int chunk = 0;
+    int rc = check_nj_shape(h, B, N, &chunk);
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    ++h->nj_calls;
+    // (chunks follow each other on the stream, so the next one may reuse the state)
+    if ((rc = ensure_buffer(h, &h->d_nj, &h->d_nj_bytes, (size_t)chunk * pfnj::state_bytes(N)))) return rc;
+    const size_t PN = (size_t)N * (N - 1) / 2, T = (size_t)pfnj::table_len(N);
+    for (int b0 = 0; b0 < B; b0 += chunk)
+        if ((rc = launch_nj_chunk(h, d_preds + (size_t)b0 * PN, std::min(chunk, B - b0), N, d_slots + (size_t)b0 * T,
+                                  d_lengths + (size_t)b0 * T, d_flag + b0)))
+            return rc;
+    return PF_OK;
+}
+
+int nj_host_impl(pf_handle* h, const float* preds, int B, int N, int32_t* slots, double* lengths, uint8_t* flag) {
+    if (!preds || !slots || !lengths || !flag) return fail(h, PF_EINVAL, "null buffer");
+    int chunk = 0;
+    int rc = check_nj_shape(h, B, N, &chunk);
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    ++h->nj_calls;
+    const size_t PN = (size_t)N * (N - 1) / 2, T = (size_t)pfnj::table_len(N);
+    // staging of one chunk: lengths double [chunk][T], preds float [chunk][PN], slots int32 [chunk][T], flag uint8 [chunk]
+    const size_t o_len = 0, o_preds = o_len + (size_t)chunk * T * sizeof(double), o_slots = o_preds + (size_t)chunk * PN * sizeof(float),
+                 o_flag = o_slots + (size_t)chunk * T * sizeof(int32_t);
+    if ((rc = ensure_buffer(h, &h->d_nj_io, &h->d_nj_io_bytes, o_flag + (size_t)chunk))) return rc;
+    double* d_len = reinterpret_cast<double*>(h->d_nj_io + o_len);
+    float* d_preds = reinterpret_cast<float*>(h->d_nj_io + o_preds);
+    int32_t* d_slots = reinterpret_cast<int32_t*>(h->d_nj_io + o_slots);
+    uint8_t* d_flag = reinterpret_cast<uint8_t*>(h->d_nj_io + o_flag);
+    for (int b0 = 0; b0 < B; b0 += chunk) {
+        const size_t nb = (size_t)std::min(chunk, B - b0);
+        HIPCHK(h, hipMemcpyAsync(d_preds, preds + (size_t)b0 * PN, nb * PN * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        // (a flagged source's table is unspecified, not uninitialised)
+        HIPCHK(h, hipMemsetAsync(d_len, 0, nb * T * sizeof(double), h->stream));
+        HIPCHK(h, hipMemsetAsync(d_slots, 0, nb * T * sizeof(int32_t), h->stream));
+        if ((rc = launch_nj_chunk(h, d_preds, (int)nb, N, d_slots, d_len, d_flag))) return rc;
+        HIPCHK(h, hipMemcpyAsync(lengths + (size_t)b0 * T, d_len, nb * T * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(slots + (size_t)b0 * T, d_slots, nb * T * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(flag + b0, d_flag, nb, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return PF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2108,6 +2193,8 @@ int pf_destroy(pf_handle_t* h) {
     if (h->d_prof) hipFree(h->d_prof);
     if (h->d_sub) hipFree(h->d_sub);
     if (h->d_tiled_tab) hipFree(h->d_tiled_tab);
+    if (h->d_nj) hipFree(h->d_nj);
+    if (h->d_nj_io) hipFree(h->d_nj_io);
     if (h->d_w) hipFree(h->d_w);
     if (h->d_wst) hipFree(h->d_wst);
     if (h->d_wtab) hipFree(h->d_wtab);
@@ -2307,6 +2394,17 @@ int pf_tile_combine_device(pf_handle_t* h, const float* d_sets, int32_t B, int32
     if (!mul_size((size_t)B, (size_t)h->tiled_plan.T, sizeof(float), &n))
         return fail(h, PF_EINVAL, "B=%d x %lld set distances overflow the address space", B, (long long)h->tiled_plan.T);
     return launch_tile_combine(h, d_sets, B, d_out, d_spread);
+}
+
+int pf_nj_joins(pf_handle_t* h, const float* preds, int32_t B, int32_t N, int32_t* slots, double* lengths, uint8_t* nonfinite) {
+    if (!h) return PF_EINVAL;
+    return nj_host_impl(h, preds, B, N, slots, lengths, nonfinite);
+}
+
+int pf_nj_joins_device(pf_handle_t* h, const float* d_preds, int32_t B, int32_t N, int32_t* d_slots, double* d_lengths,
+                       uint8_t* d_nonfinite) {
+    if (!h) return PF_EINVAL;
+    return nj_device_impl(h, d_preds, B, N, d_slots, d_lengths, d_nonfinite);
 }
 
 int pf_forward_device(pf_handle_t* h, const uint8_t* d_idx, int32_t B, int32_t N, int32_t L, float* d_out) {
@@ -2511,6 +2609,7 @@ int pf_profile_reset(pf_handle_t* h) {
     for (int i = 0; i < K_COUNT; ++i) { h->prof_n[i] = 0; h->prof_ms[i] = 0; }
     h->coll_calls = 0;
     h->rechecked = 0;
+    h->nj_calls = 0;
     return PF_OK;
 }
 
@@ -2524,6 +2623,11 @@ int pf_profile_get(pf_handle_t* h, const char* kernel, int64_t* launches, double
     }
     if (std::strcmp(kernel, "rechecked") == 0) {        // alignments the range re-check sent to the float64 kernels
         if (launches) *launches = h->rechecked;
+        if (total_ms) *total_ms = 0.0;
+        return PF_OK;
+    }
+    if (std::strcmp(kernel, "nj_joins") == 0) {         // pf_nj_joins / pf_nj_joins_device calls
+        if (launches) *launches = h->nj_calls;
         if (total_ms) *total_ms = 0.0;
         return PF_OK;
     }

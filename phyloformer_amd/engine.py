@@ -129,6 +129,10 @@ SIGNATURES = {
     "pf_forward_tiled": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "pf_tile_combine_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "pf_tile_groups": (C.c_int, [C.c_int32, C.c_int32]),
+    "pf_nj_joins": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pf_nj_joins_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pf_nj_format_joins_n": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32,
+                                         C.c_char_p, C.c_int64]),
     "pf_tile_bound": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
     "pf_forward_weighted": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "pf_forward_weighted_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
@@ -149,7 +153,7 @@ CALL_TIME_SYMBOLS = frozenset({"pf_forward_site_map", "pf_forward_site_map_devic
                                "pf_forward_weighted_device", "pf_forward_sites_weighted", "pf_bootstrap_weighted",
                                "pf_padded_sites", "pf_boot_counts", "pf_compress_sites", "pf_forward_place",
                                "pf_place_stats_device", "pf_forward_tiled", "pf_tile_combine_device", "pf_tile_groups",
-                               "pf_tile_bound"})
+                               "pf_tile_bound", "pf_nj_joins", "pf_nj_joins_device", "pf_nj_format_joins_n"})
 
 _lib: Optional[C.CDLL] = None
 
@@ -499,6 +503,42 @@ class Engine:
         float32 [B][P_N]`` (asynchronous on the handle's stream)."""
         self._check(self._optional("pf_tile_combine_device")(self._h, C.c_void_p(d_sets), B, N, M, C.c_void_p(d_out),
                                                              C.c_void_p(d_spread)))
+
+    # -- neighbour joining -------------------------------------------------------------------
+    @staticmethod
+    def _seqs_of_pairs(p: int) -> int:
+        n = (1 + int(round((1 + 8 * p) ** 0.5))) // 2
+        if n < 2 or n * (n - 1) // 2 != p:
+            raise ValueError(f"{p} distances are not the pairs of any number of sequences")
+        return n
+
+    def nj_joins(self, preds: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Neighbour joining on the GPU (``pf_nj_joins``): distances ``float32[B, P_N]`` → ``(slots int32[B, T], lengths
+        float64[B, T], nonfinite bool[B])``, ``T = 2 (N - 3) + 3`` (``[P_N]`` drops ``B``): the joins ``a, b`` / ``la, lb``
+        of ``nj.nj_joins`` on the symmetric matrix of every source, then the trifurcation ``i, j, k`` / ``li, lj, lk`` - bit
+        for bit.  A source with a NaN or an infinity is flagged and its table unspecified (use ``hostio.nj_newick``)."""
+        fn = self._optional("pf_nj_joins")
+        p = np.ascontiguousarray(np.asarray(preds, dtype=np.float32))
+        single = p.ndim == 1
+        if single:
+            p = p[None, :]
+        if p.ndim != 2:
+            raise ValueError(f"expected distances [B, P] or [P], got {p.shape}")
+        B, N = p.shape[0], self._seqs_of_pairs(p.shape[1])
+        T = max(0, 2 * (N - 3) + 3)
+        slots = np.zeros((B, T), dtype=np.int32)
+        lengths = np.zeros((B, T), dtype=np.float64)
+        flag = np.zeros(B, dtype=np.uint8)
+        self._check(fn(self._h, p.ctypes.data if p.size else None, B, N, slots.ctypes.data if T else None,
+                       lengths.ctypes.data if T else None, flag.ctypes.data if B else None))
+        flag = flag.astype(bool)
+        return (slots[0], lengths[0], flag[0]) if single else (slots, lengths, flag)
+
+    def nj_joins_device(self, d_preds: int, B: int, N: int, d_slots: int, d_lengths: int, d_nonfinite: int):
+        """``pf_nj_joins_device``: device ``preds float32 [B][P_N]`` → device ``slots int32`` / ``lengths float64
+        [B][2 (N - 3) + 3]``, ``nonfinite uint8 [B]`` (asynchronous on the handle's stream)."""
+        self._check(self._optional("pf_nj_joins_device")(self._h, C.c_void_p(d_preds), B, N, C.c_void_p(d_slots),
+                                                         C.c_void_p(d_lengths), C.c_void_p(d_nonfinite)))
 
     # -- site weights -----------------------------------------------------------------------
     @staticmethod

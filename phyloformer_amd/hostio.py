@@ -130,6 +130,47 @@ def nj_newick(preds: np.ndarray, ids: Sequence[str], clamp_negative: bool = True
     return buf.raw[:w]
 
 
+def _join_table(slots, lengths, n: int) -> Tuple[np.ndarray, np.ndarray]:
+    """One source's join table (``Engine.nj_joins``) for ``n`` ids, checked: ``2 (n - 3) + 3`` slots in ``[0, n)``."""
+    s = np.ascontiguousarray(np.asarray(slots, dtype=np.int32).reshape(-1))
+    l = np.ascontiguousarray(np.asarray(lengths, dtype=np.float64).reshape(-1))
+    t = 2 * (n - 3) + 3
+    if n < 3 or s.size != t or l.size != t:
+        raise ValueError(f"expected a join table of {max(t, 0)} entries for {n} >= 3 sequences, got {s.size} slots and {l.size} lengths")
+    if s.size and (int(s.min()) < 0 or int(s.max()) >= n):
+        raise ValueError(f"join table names a slot outside [0, {n})")
+    return s, l
+
+
+def newick_of_joins(slots, lengths, ids: Sequence[str], clamp_negative: bool = True) -> bytes:
+    """``pf_nj_format_joins_n``: the Newick text (utf-8 bytes) of one source's join table - ``Engine.nj_joins``'s ``slots``
+    / ``lengths [2 (n - 3) + 3]`` - byte-identical to ``nj.newick_of_joins``; with the table of the same distances it is
+    ``nj_newick``'s text."""
+    lib = load_library()
+    n = len(ids)
+    s, l = _join_table(slots, lengths, n)
+    enc = [i.encode("utf8") for i in ids]
+    arr = (C.c_char_p * n)(*enc)
+    lens = np.array([len(e) for e in enc], dtype=np.int64)
+    need = lib.pf_nj_format_joins_n(s.ctypes.data, l.ctypes.data, n, arr, lens.ctypes.data, int(clamp_negative), None, 0)
+    if need < 0:
+        raise RuntimeError(f"pf_nj_format_joins_n failed with status {need}")
+    buf = C.create_string_buffer(int(need) + 1)
+    w = lib.pf_nj_format_joins_n(s.ctypes.data, l.ctypes.data, n, arr, lens.ctypes.data, int(clamp_negative), buf, need)
+    return buf.raw[:w]
+
+
+def newick_of_joins_py(slots, lengths, ids: Sequence[str], clamp_negative: bool = True) -> str:
+    """The pure-Python equivalent of ``newick_of_joins``: the table handed to ``nj.newick_of_joins``."""
+    from .nj import newick_of_joins as text_of
+    n = len(ids)
+    s, l = _join_table(slots, lengths, n)
+    j = n - 3
+    joins = [(int(s[2 * t]), int(s[2 * t + 1]), float(l[2 * t]), float(l[2 * t + 1])) for t in range(j)]
+    final = (int(s[2 * j]), int(s[2 * j + 1]), int(s[2 * j + 2]), float(l[2 * j]), float(l[2 * j + 1]), float(l[2 * j + 2]))
+    return text_of(ids, joins, final, clamp_negative)
+
+
 def nj_support(preds: np.ndarray, reps: np.ndarray, ids: Sequence[str], clamp_negative: bool = True,
                threads: int = 1) -> bytes:
     """``pf_nj_support_n``: the ``nj_newick`` text of ``preds [P]`` with the bootstrap support of every internal node,

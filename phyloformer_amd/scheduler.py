@@ -196,6 +196,21 @@ class DirectoryRunner:
         from .phylip import vec_to_phylip
         return neighbor_joining(vec_to_phylip(vec, ids)[0].astype("float64"), ids)
 
+    def newick_of_joins(self, slots: np.ndarray, lengths: np.ndarray, ids: List[str]):
+        """The tree text of a join table (``Engine.nj_joins``), from the same side as ``nj``: the same bytes as ``nj`` of
+        the distances the table was joined from."""
+        if self.native_io:
+            from .hostio import newick_of_joins
+            return newick_of_joins(slots, lengths, ids)
+        from .hostio import newick_of_joins_py
+        return newick_of_joins_py(slots, lengths, ids)
+
+    def book(self, **amounts):
+        """Add to the run's stats from inside a mode's own engine call (takes the runner's lock)."""
+        with self._lock:
+            for key, value in amounts.items():
+                self.stats[key] = self.stats.get(key, 0) + value
+
     def out_path(self, path: str, suffix: str) -> str:
         return os.path.join(self.out_dir, f"{Path(path).stem}.{suffix}")
 
@@ -204,9 +219,9 @@ class DirectoryRunner:
         with open(self.out_path(path, suffix), "wb" if isinstance(data, bytes) else "w") as fh:
             fh.write(data)
 
-    def _write(self, path: str, pred: np.ndarray, ids: List[str]):
+    def _write(self, path: str, pred: np.ndarray, ids: List[str], tree: bool = True):
         self.put(path, "phy", self.phylip(pred, ids))
-        if self.trees:
+        if self.trees and tree:
             self.put(path, "nj.nwk", self.nj(pred, ids))
 
     def writer_cap(self) -> int:
@@ -216,11 +231,12 @@ class DirectoryRunner:
         # per alignment.  PF_WRITER_THREADS moves the cap for experiments, profiles/r06r_cli_bench_overlay_writer_threads.txt.)
         return max(1, min(self.io_threads, int(os.environ.get("PF_WRITER_THREADS", "4"))))
 
-    def _write_native(self, n: int, group: list, preds: np.ndarray):
-        """``<stem>.phy`` - and with ``--trees`` ``<stem>.nj.nwk`` - of a whole launch: formatted (the trees: joined) and
-        written on native threads (infer_alns.py:105-123)."""
+    def _write_native(self, n: int, group: list, preds: np.ndarray, tree: bool = True):
+        """``<stem>.phy`` - and with ``--trees`` ``<stem>.nj.nwk``, unless a mode writes the tree of this shape itself
+        (``tree`` = False) - of a whole launch: formatted (the trees: joined) and written on native threads
+        (infer_alns.py:105-123)."""
         from .hostio import write_phylip
-        trees = [self.out_path(e.path, "nj.nwk") for e in group] if self.trees else None
+        trees = [self.out_path(e.path, "nj.nwk") for e in group] if self.trees and tree else None
         write_phylip([e.source for e in group], n, preds, [self.out_path(e.path, "phy") for e in group],
                      self.writer_cap(), trees)
 
@@ -236,6 +252,7 @@ class DirectoryRunner:
         mode = self._forwarder
         preds, payload = mode.forward(self, engine, shape, batch) if mode else (engine.forward(batch), ())
         dt = time.perf_counter() - t0
+        tree = not (mode and self.trees and mode.writes_tree(shape))      # (False: the mode writes the tree itself)
         with self._lock:
             self.stats["forward_s"] += dt
             self.stats["launches"] += 1
@@ -243,9 +260,9 @@ class DirectoryRunner:
             key = f"{shape[0]}x{shape[1]}"
             self.stats["shapes"][key] = self.stats["shapes"].get(key, 0) + len(group)
             if self.native_io:
-                submit([(self._write_native, shape[0], group, preds)])
+                submit([(self._write_native, shape[0], group, preds, tree)])
             else:
-                submit([(self._write, e.path, pred, e.ids()) for e, pred in zip(group, preds)])
+                submit([(self._write, e.path, pred, e.ids(), tree) for e, pred in zip(group, preds)])
             if mode:
                 mode.account(self.stats, len(group), shape, dt)
                 if payload:

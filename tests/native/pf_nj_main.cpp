@@ -1,0 +1,70 @@
+// Stand-alone driver of csrc/pf_nj_host.h for AddressSanitizer / UBSan builds (tests/test_nj_native.py): the bodies of
+// the neighbour-joining kernels, run on the CPU thread by thread and workgroup by workgroup, in the order the launches
+// of pf_nj.hip.h give them, on exactly-sized heap arrays.
+//
+//     pf_nj_main B N threads groups preds.bin result.bin
+//
+// threads: the size of every workgroup; groups: the most workgroups of the minimum of Q (min(m, groups) run).
+// preds.bin: float [B][P_N]; result.bin: slots int32 [B][T], then lengths double [B][T], then flag uint8 [B],
+// T = 2 (N - 3) + 3.  Exit code 0 = done, 2 = usage.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "../../phyloformer_amd/csrc/pf_nj_host.h"
+
+int main(int argc, char** argv) {
+    if (argc != 7) return 2;
+    const int B = atoi(argv[1]), N = atoi(argv[2]), threads = atoi(argv[3]), groups = atoi(argv[4]);
+    if (B < 1 || N < 3 || N > 4096 || threads < 1 || groups < 1) return 2;
+    const size_t PN = (size_t)N * (N - 1) / 2, T = (size_t)pfnj::table_len(N), n = (size_t)N, b = (size_t)B;
+    std::vector<float> preds(b * PN);
+    FILE* f = fopen(argv[5], "rb");
+    if (!f || fread(preds.data(), sizeof(float), preds.size(), f) != preds.size()) return 2;
+    fclose(f);
+    std::vector<double> d(b * n * n), r(b * n), lengths(b * T);
+    std::vector<pfnj::Key> part(b * (size_t)groups), keys((size_t)threads);
+    std::vector<int32_t> active(b * 2 * n), slots(b * T);
+    std::vector<uint8_t> flag(b, 0);
+    pfnj::Args a{};
+    a.preds = preds.data(); a.d = d.data(); a.r = r.data(); a.part = part.data(); a.active = active.data();
+    a.slots = slots.data(); a.lengths = lengths.data(); a.flag = flag.data();
+    a.N = N; a.part_cap = groups; a.PN = (int64_t)PN;
+
+    auto reduce = [&] {
+        for (int s = pfnj::reduce_first_step(threads); s > 0; s >>= 1)
+            for (int tid = 0; tid < threads; ++tid) pfnj::reduce_step(keys.data(), tid, s, threads);
+    };
+    const int init_groups = 2;
+    for (size_t src = 0; src < b; ++src)
+        for (int wg = 0; wg < init_groups; ++wg)
+            for (int tid = 0; tid < threads; ++tid) pfnj::init_elems(a, src, wg, init_groups, tid, threads);
+    for (int t = 0; t < N - 3; ++t) {
+        const int m = N - t, G = m < groups ? m : groups;
+        for (size_t src = 0; src < b; ++src)
+            for (int row = 0; row < m; ++row) pfnj::row_sum(a, m, t, src, row);
+        for (size_t src = 0; src < b; ++src)
+            for (int wg = 0; wg < G; ++wg) {
+                for (int tid = 0; tid < threads; ++tid) keys[(size_t)tid] = pfnj::qmin_thread(a, m, t, src, wg, G, tid, threads);
+                reduce();
+                part[src * (size_t)groups + (size_t)wg] = keys[0];
+            }
+        for (size_t src = 0; src < b; ++src) {
+            for (int tid = 0; tid < threads; ++tid) keys[(size_t)tid] = pfnj::join_thread_key(a, src, G, tid, threads);
+            reduce();
+            const pfnj::Join j = pfnj::join_record(a, m, t, src, keys[0]);
+            for (int tid = 0; tid < threads; ++tid) pfnj::join_update(a, m, t, src, j, tid, threads);
+        }
+    }
+    for (size_t src = 0; src < b; ++src) pfnj::final_record(a, src);
+
+    f = fopen(argv[6], "wb");
+    if (!f || fwrite(slots.data(), sizeof(int32_t), slots.size(), f) != slots.size() ||
+        fwrite(lengths.data(), sizeof(double), lengths.size(), f) != lengths.size() ||
+        fwrite(flag.data(), 1, flag.size(), f) != flag.size())
+        return 2;
+    fclose(f);
+    printf("pf_nj_main: clean, N = %d, joins = %d\n", N, N - 3);
+    return 0;
+}
