@@ -374,6 +374,37 @@ int pf_nj_joins(pf_handle_t* h, const float* preds, int32_t B, int32_t N, int32_
 int pf_nj_joins_device(pf_handle_t* h, const float* d_preds, int32_t B, int32_t N, int32_t* d_slots, double* d_lengths,
                        uint8_t* d_nonfinite);
 
+/* ---- balanced minimum-evolution NNI refinement of a join table (additive to ABI 5) ----
+ *
+ * Balanced nearest-neighbour interchanges (BNNI, FastME's -n B) from a start tree to a local optimum of the balanced
+ * tree length, with balanced branch lengths: phyloformer_amd/bme.py states the algorithm (tree, balanced averages,
+ * moves, the rule delta < -1e-12 on the key (delta, c, k), lengths, the order of the output table) and DESIGN.md
+ * section 21 the device form.
+ *   preds        float  [B][P_N]              as pf_nj_joins
+ *   start_slots  int32  [B][2 (N - 3) + 3]    the slots of a join table (pf_nj_joins' or any valid one; lengths are not
+ *                                             needed): the start tree
+ *   slots, lengths      [B][2 (N - 3) + 3]    the refined tree as a join table in pf_nj_joins' layout (pf_nj_format_joins_n
+ *                                             writes its text): children before parents, a cluster's slot its smallest
+ *                                             sequence; lengths are the balanced branch lengths
+ *   steps        int32  [B]                   moves performed
+ *   tree_length  double [B]                   the sum of the branch lengths = the balanced length of the tree
+ *   status       uint8  [B]                   0 ok; 1 the source holds a NaN or an infinity (its results are zeros: run
+ *                                             pf_bme_newick_n for such a source); 2 stopped at the cap of 16 N moves
+ * pf_bme_nni takes host arrays and is synchronous.  pf_bme_nni_device takes device arrays; it synchronises the handle's
+ * stream once per round of 32 steps (the host reads the flags and rebuilds the depth table of a source that came to
+ * rest), so its results are complete on return too.  pf_bme_nni_host runs the same kernel bodies serially without a
+ * handle or a device: slots, steps and status equal, lengths and tree_length equal bit for bit.  Sources run side by
+ * side in chunks that fit "ws_limit_mb"; one source always runs whole.  Refused with PF_EINVAL before any device work:
+ * N < 3, N > 16384, B < 1; NULL buffers; P_N >= 2^31; an N whose state (its table of 4N - 6 subtrees: about 56 N^2 bytes)
+ * exceeds "ws_limit_mb" (the message names the bytes); a start slot outside [0, N) or a start table that is not a join
+ * table.  pf_profile_get("bme_nni") counts the calls of the two handle entry points. */
+int pf_bme_nni(pf_handle_t* h, const float* preds, const int32_t* start_slots, int32_t B, int32_t N, int32_t* slots, double* lengths,
+               int32_t* steps, double* tree_length, uint8_t* status);
+int pf_bme_nni_device(pf_handle_t* h, const float* d_preds, const int32_t* d_start_slots, int32_t B, int32_t N, int32_t* d_slots,
+                      double* d_lengths, int32_t* d_steps, double* d_tree_length, uint8_t* d_status);
+int pf_bme_nni_host(const float* preds, const int32_t* start_slots, int32_t B, int32_t N, int32_t* slots, double* lengths, int32_t* steps,
+                    double* tree_length, uint8_t* status);
+
 /* ---- site weights: weighted forward, pattern compression, bootstrap on distinct sites (additive to ABI 5) ----
  *
  * Nothing in the network depends on a site's position, and every reduction over sites is a plain sum (the row-attention
@@ -505,7 +536,7 @@ int pf_memcpy_d2h(pf_handle_t* h, void* dst, const void* src, size_t bytes);
  * "weight_sums" (k_weight_sums of the weighted forwards), "place_stats" (the reduction of pf_forward_place /
  * pf_place_stats_device), "tile_combine" (k_tile_combine of pf_forward_tiled / pf_tile_combine_device).  Totals accumulate until reset.
  * "nj_joins" returns the number of pf_nj_joins / pf_nj_joins_device calls since the last reset in *launches (counted
- * always; *total_ms = 0).  "collectives" returns the number of all-reduces issued since the last reset in
+ * always; *total_ms = 0), "bme_nni" likewise that of pf_bme_nni / pf_bme_nni_device calls.  "collectives" returns the number of all-reduces issued since the last reset in
  * *launches (counted always, no profiling option needed; *total_ms = 0); "rechecked" likewise the number of
  * alignments the range re-check (option "recheck_above") computed again on the float64 kernels. */
 int pf_profile_reset(pf_handle_t* h);
@@ -617,6 +648,13 @@ int64_t pf_nj_newick_n(const float* preds, int32_t n, const char* const* ids, co
  * device, no handle.  PF_EINVAL also for a slot outside [0, n).  Sizing protocol as pf_format_phylip. */
 int64_t pf_nj_format_joins_n(const int32_t* slots, const double* lengths, int32_t n, const char* const* ids, const int64_t* id_lens,
                              int32_t clamp_negative, char* out, int64_t cap);
+
+/* The Newick text of the neighbour-joining tree of preds refined by balanced NNIs, with balanced branch lengths (the
+ * CLI's --bme; phyloformer_amd/bme.py::bme_newick_py writes the same bytes): pf_nj_newick_n's tree through
+ * pf_bme_nni_host and pf_nj_format_joins_n.  n < 3 or a NaN / infinity in preds: pf_nj_newick_n's text.  No device, no
+ * handle.  Sizing protocol as pf_format_phylip. */
+int64_t pf_bme_newick_n(const float* preds, int32_t n, const char* const* ids, const int64_t* id_lens, int32_t clamp_negative,
+                        char* out, int64_t cap);
 
 /* ---- many files per call, on native threads (ABI 4; tree_paths: ABI 5) ---------------------------
  *

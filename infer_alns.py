@@ -41,6 +41,11 @@ def build_parser():
                         help="Path to directory where inferred distance matrices will be written")
     parser.add_argument("--trees", "-t", action="store_true",
                         help="Output NJ trees as well as matrices")
+    parser.add_argument("--bme", action="store_true",
+                        help="with -t: also write <stem>.bme.nwk, the NJ tree of the alignment's distances refined by balanced "
+                             "nearest-neighbour interchanges to a local optimum of the balanced minimum-evolution tree length, "
+                             "with balanced branch lengths (the BNNI search of FastME -n B; no SPR moves); every other output "
+                             "keeps its bytes; the trees of windows, cuts and replicates stay NJ")
     parser.add_argument("--device", type=int, default=0, help="HIP device ordinal (default 0)")
     parser.add_argument("--devices", default=None,
                         help="comma-separated HIP device ordinals: shard the files over these GPUs, "
@@ -76,6 +81,10 @@ def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
     modes = analyses.modes_from_args(args, parser.error)
+    if args.bme and not args.trees:
+        parser.error("--bme refines the tree of --trees: give -t as well")
+    if args.bme and args.shard == "sites":
+        parser.error("--bme cannot be combined with --shard sites: the site-sharded runner writes NJ trees only")
 
     from phyloformer_amd import scheduler
 
@@ -152,7 +161,7 @@ def main(argv=None):
             e.set_option("two_streams", 0)
     runner = scheduler.DirectoryRunner(engines, out_dir, trees=args.trees, batch=args.batch,
                                        io_threads=args.io_threads, native_io=not args.python_io,
-                                       progress=bar.update if bar is not None else None, modes=modes)
+                                       progress=bar.update if bar is not None else None, modes=modes, bme=args.bme)
     try:
         stats = runner.run(paths)
     finally:

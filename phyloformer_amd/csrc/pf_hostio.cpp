@@ -24,6 +24,7 @@
 #include <unistd.h>
 
 #include "../../include/phyloformer_amd.h"
+#include "pf_bme_host.h"
 
 namespace {
 
@@ -670,6 +671,93 @@ int pf_phylip_write_batch(const pf_fasta_batch_t* const* batches, const int32_t*
     } catch (...) { return PF_ENOMEM; }
     return PF_OK;
 }
+
+}  // extern "C"
+
+// ---- balanced NNI refinement on the host (pf_bme_nni_host, pf_bme_newick_n; pf_bme_host.h) ------
+namespace {
+
+// one source through the serial run of the kernels' bodies (one workgroup of one thread: the results do not depend on
+// the geometry); false: an invalid start table
+bool bme_one(const float* preds, const int32_t* start, int32_t n, int32_t* slots, double* lengths, int32_t* steps, double* tree_length,
+             uint8_t* status) {
+    pfbme::Serial run;
+    const int epg = (int)pfbme::root_of(n);
+    if (!run.setup(preds, start, 1, n, epg)) return false;
+    run.run(1, epg, 1, true);
+    run.result(0, slots, lengths, steps, tree_length, status);
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pf_bme_nni_host(const float* preds, const int32_t* start_slots, int32_t B, int32_t N, int32_t* slots, double* lengths, int32_t* steps,
+                    double* tree_length, uint8_t* status) {
+    if (!preds || !start_slots || !slots || !lengths || !steps || !tree_length || !status || B < 1 || N < 3 || N > pfbme::MAX_N)
+        return PF_EINVAL;
+    const size_t PN = (size_t)N * ((size_t)N - 1) / 2, T = (size_t)pfnj::table_len(N);
+    if (PN >= ((size_t)1 << 31)) return PF_EINVAL;
+    try {
+        std::vector<int32_t> parent((size_t)pfbme::nodes_of(N)), children((size_t)pfbme::nodes_of(N) * 3);
+        for (int32_t b = 0; b < B; ++b)                          // refused before any work
+            if (!pfbme::tree_of_joins(start_slots + (size_t)b * T, N, parent.data(), children.data())) return PF_EINVAL;
+        for (int32_t b = 0; b < B; ++b)
+            if (!bme_one(preds + (size_t)b * PN, start_slots + (size_t)b * T, N, slots + (size_t)b * T, lengths + (size_t)b * T, steps + b,
+                         tree_length + b, status + b))
+                return PF_EINVAL;
+        return PF_OK;
+    } catch (...) { return PF_ENOMEM; }
+}
+
+// pf_bme_newick_n and the number of moves behind the text (bound by phyloformer_amd/hostio.py::bme_newick; not part of
+// the public header); steps may be NULL
+int64_t pf_bme_newick_steps_n(const float* preds, int32_t n, const char* const* ids, const int64_t* id_lens, int32_t clamp_negative,
+                              char* out, int64_t cap, int32_t* steps_out) {
+    if (steps_out) *steps_out = 0;
+    if (!preds || n < 1 || n > pfbme::MAX_N || !ids || !id_lens || (!out && cap > 0)) return PF_EINVAL;
+    for (int32_t i = 0; i < n; ++i) if (id_lens[i] < 0) return PF_EINVAL;
+    try {
+        std::string text;
+        bool refined = false;
+        if (n >= 3) {
+            NjTree t;
+            nj_core(preds, n, t);
+            const size_t joins = (size_t)n - 3, len = 2 * joins + 3;
+            std::vector<int32_t> start(len), slots(len);
+            std::vector<double> lengths(len);
+            for (size_t s = 0; s < joins; ++s) { start[2 * s] = t.joins[s].a; start[2 * s + 1] = t.joins[s].b; }
+            start[2 * joins] = t.i; start[2 * joins + 1] = t.j; start[2 * joins + 2] = t.k;
+            int32_t steps = 0;
+            double tree_length = 0.0;
+            uint8_t status = 0;
+            // (a NaN in the distances can leave nj_core with a table that is none: the NJ text then, as for a flagged source)
+            if (bme_one(preds, start.data(), n, slots.data(), lengths.data(), &steps, &tree_length, &status) && status != pfbme::ST_NONFINITE) {
+                NjTree r;
+                r.joins.reserve(joins);
+                for (size_t s = 0; s < joins; ++s) r.joins.push_back({slots[2 * s], slots[2 * s + 1], lengths[2 * s], lengths[2 * s + 1]});
+                r.i = slots[2 * joins]; r.j = slots[2 * joins + 1]; r.k = slots[2 * joins + 2];
+                r.li = lengths[2 * joins]; r.lj = lengths[2 * joins + 1]; r.lk = lengths[2 * joins + 2];
+                nj_format(r, n, ids, id_lens, clamp_negative != 0, nullptr, text);
+                refined = true;
+                if (steps_out) *steps_out = steps;
+            }
+        }
+        if (!refined) nj_newick(preds, n, ids, id_lens, clamp_negative != 0, text);
+        if (out && (int64_t)text.size() <= cap) memcpy(out, text.data(), text.size());
+        return (int64_t)text.size();
+    } catch (...) { return PF_ENOMEM; }
+}
+
+int64_t pf_bme_newick_n(const float* preds, int32_t n, const char* const* ids, const int64_t* id_lens, int32_t clamp_negative,
+                        char* out, int64_t cap) {
+    return pf_bme_newick_steps_n(preds, n, ids, id_lens, clamp_negative, out, cap, nullptr);
+}
+
+}  // extern "C"
+
+extern "C" {
 
 // Bootstrap supports (bound by phyloformer_amd/hostio.py::nj_support; not part of the public header): the pf_nj_newick_n
 // text of preds [n(n-1)/2] with, after the ')' of every internal node, the integer percent (200 c + R) / (2 R) of the

@@ -45,6 +45,7 @@
 #include "pf_place.hip.h"
 #include "pf_tile.hip.h"
 #include "pf_nj.hip.h"
+#include "pf_bme.hip.h"
 #include "pf_weights.hip.h"
 #include "pf_weights_host.h"
 #include "pf_host_prep.h"
@@ -243,6 +244,11 @@ struct pf_handle {
     char* d_nj = nullptr; size_t d_nj_bytes = 0;
     char* d_nj_io = nullptr; size_t d_nj_io_bytes = 0;
     int64_t nj_calls = 0;        // calls since the last pf_profile_reset ("nj_joins")
+    // pf_bme_nni / pf_bme_nni_device (grow-only): the state of one chunk of sources (pf_bme.hip.h: carve) and the
+    // staging of the host entry point's distances
+    char* d_bme = nullptr; size_t d_bme_bytes = 0;
+    float* d_bme_preds = nullptr; size_t d_bme_preds_bytes = 0;
+    int64_t bme_calls = 0;       // calls since the last pf_profile_reset ("bme_nni")
     // weighted forwards (grow-only): the weight rows of a host call or of one chunk of derived alignments, what
     // k_weight_sums made of a call's rows ([..][4], pf_weights.hip.h), and the weight table of pf_forward_sites_weighted
     float* d_w = nullptr; size_t d_w_bytes = 0;
@@ -2042,6 +2048,142 @@ int nj_host_impl(pf_handle* h, const float* preds, int B, int N, int32_t* slots,
     return PF_OK;
 }
 
+// ---- balanced NNI refinement on the device (pf_bme_nni, pf_bme_nni_device; pf_bme.hip.h, pf_bme_host.h) ----
+
+// What both entry points refuse about (B, N), and the sources of one chunk: as many as fit "ws_limit_mb" side by side,
+// one at least - a single source's state above the limit is refused.
+int check_bme_shape(pf_handle* h, int B, int N, int* chunk) {
+    if (B < 1) return fail(h, PF_EINVAL, "bad dimensions B=%d N=%d", B, N);
+    if (N < 3) return fail(h, PF_EINVAL, "balanced NNI needs N >= 3 sequences (got %d)", N);
+    if (N > pfbme::MAX_N) return fail(h, PF_EINVAL, "balanced NNI takes at most %d sequences (got %d)", pfbme::MAX_N, N);
+    const int64_t PN = (int64_t)N * (N - 1) / 2;
+    size_t n = 0;
+    if (PN >= ((int64_t)1 << 31) || !mul_size((size_t)B, (size_t)PN, sizeof(float), &n) ||
+        !mul_size((size_t)B, (size_t)pfnj::table_len(N), sizeof(double), &n))
+        return fail(h, PF_EINVAL, "B=%d alignments of N=%d sequences: their %lld pairs each overflow a distance vector", B, N, (long long)PN);
+    const size_t per = pfbme::state_bytes(N);
+    if ((int64_t)per > h->ws_limit_bytes)
+        return fail(h, PF_EINVAL, "balanced NNI of N=%d sequences needs %zu bytes of state per source (its table of 4N-6 subtrees), "
+                                  "above the workspace limit of %lld bytes (option ws_limit_mb)", N, per, (long long)h->ws_limit_bytes);
+    *chunk = (int)std::min<size_t>(std::min(B, pfbme::BME_MAX_Z), (size_t)h->ws_limit_bytes / per);
+    return PF_OK;
+}
+
+// every start table is a join table (slots in [0, N), every join of two live clusters, three distinct live slots last)
+int check_bme_starts(pf_handle* h, const int32_t* start, int B, int N) {
+    std::vector<int32_t> parent((size_t)pfbme::nodes_of(N)), children((size_t)pfbme::nodes_of(N) * 3);
+    for (int b = 0; b < B; ++b)
+        if (!pfbme::tree_of_joins(start + (size_t)b * (size_t)pfnj::table_len(N), N, parent.data(), children.data()))
+            return fail(h, PF_EINVAL, "source %d: the start table is not a join table of N=%d sequences", b, N);
+    return PF_OK;
+}
+
+// The refinement of nb <= chunk sources: distances on the device, start tables and results on the host.  Synchronises
+// h->stream once per round of ROUND_STEPS steps and once at the end.
+int bme_chunk(pf_handle* h, const float* d_preds, const int32_t* start, int nb, int N, int32_t* slots, double* lengths,
+              int32_t* steps, double* tree_length, uint8_t* status) {
+    const size_t b = (size_t)nb, T = (size_t)pfnj::table_len(N), nodes = (size_t)pfbme::nodes_of(N), rows = (size_t)pfbme::rows_of(N),
+                 root = (size_t)pfbme::root_of(N);
+    int rc = ensure_buffer(h, &h->d_bme, &h->d_bme_bytes, b * pfbme::state_bytes(N));
+    if (rc) return rc;
+    h->cur = h->stream;
+    const pfbme::Args a = pfbme::carve(h->d_bme, d_preds, nb, N);
+    std::vector<int32_t> parent(b * nodes), children(b * nodes * 3), nsteps(b, 0), fresh(b, 0);
+    std::vector<int16_t> depth(b * rows * nodes);
+    std::vector<uint8_t> done(b, 0), rebuild(b, 1), st(b, 0);
+    std::vector<double> edge_len(b * root);
+    for (size_t s = 0; s < b; ++s) {
+        pfbme::tree_of_joins(start + s * T, N, &parent[s * nodes], &children[s * nodes * 3]);       // (checked by the caller)
+        pfbme::build_depth(&parent[s * nodes], &children[s * nodes * 3], N, &depth[s * rows * nodes]);
+    }
+    auto up = [&](void* dst, const void* src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream); };
+    auto down = [&](void* dst, const void* src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream); };
+    HIPCHK(h, up(a.parent, parent.data(), parent.size() * sizeof(int32_t)));
+    HIPCHK(h, up(a.children, children.data(), children.size() * sizeof(int32_t)));
+    HIPCHK(h, up(a.depth, depth.data(), depth.size() * sizeof(int16_t)));
+    HIPCHK(h, up(a.rebuild, rebuild.data(), b));
+    HIPCHK(h, hipMemsetAsync(a.steps, 0, b * sizeof(int32_t), h->stream));
+    HIPCHK(h, hipMemsetAsync(a.done, 0, b, h->stream));
+    HIPCHK(h, hipMemsetAsync(a.status, 0, b, h->stream));
+    // (a flagged source's lengths are never written: not uninitialised either)
+    HIPCHK(h, hipMemsetAsync(a.edge_len, 0, b * root * sizeof(double), h->stream));
+    hipError_t e = pfbme::launch_init(h->stream, a, nb);
+    if (e != hipSuccess) return fail(h, PF_EHIP, "k_bme_init launch failed: %s", hipGetErrorString(e));
+    for (;;) {
+        if ((e = pfbme::launch_round(h->stream, a, nb)) != hipSuccess) return fail(h, PF_EHIP, "k_bme_* launch failed: %s", hipGetErrorString(e));
+        HIPCHK(h, down(done.data(), a.done, b));
+        HIPCHK(h, down(nsteps.data(), a.steps, b * sizeof(int32_t)));
+        HIPCHK(h, down(st.data(), a.status, b));
+        HIPCHK(h, down(parent.data(), a.parent, parent.size() * sizeof(int32_t)));
+        HIPCHK(h, down(children.data(), a.children, children.size() * sizeof(int32_t)));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (pfbme::between_rounds(nb, N, parent.data(), children.data(), nsteps.data(), done.data(), st.data(), rebuild.data(), fresh.data(),
+                                  depth.data()))
+            break;
+        HIPCHK(h, up(a.done, done.data(), b));
+        HIPCHK(h, up(a.rebuild, rebuild.data(), b));
+        for (size_t s = 0; s < b; ++s)
+            if (rebuild[s]) HIPCHK(h, up(a.depth + s * rows * nodes, &depth[s * rows * nodes], rows * nodes * sizeof(int16_t)));
+    }
+    if ((e = pfbme::launch_lengths(h->stream, a, nb)) != hipSuccess) return fail(h, PF_EHIP, "k_bme_lengths launch failed: %s", hipGetErrorString(e));
+    HIPCHK(h, down(edge_len.data(), a.edge_len, edge_len.size() * sizeof(double)));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (size_t s = 0; s < b; ++s)
+        pfbme::result_of(N, &children[s * nodes * 3], &edge_len[s * root], nsteps[s], st[s], slots + s * T, lengths + s * T, steps + s,
+                         tree_length + s, status + s);
+    return PF_OK;
+}
+
+// preds / start on the host (device = false) or on the device; the results likewise
+int bme_impl(pf_handle* h, bool device, const float* preds, const int32_t* start, int B, int N, int32_t* slots, double* lengths,
+             int32_t* steps, double* tree_length, uint8_t* status) {
+    if (!preds || !start || !slots || !lengths || !steps || !tree_length || !status) return fail(h, PF_EINVAL, "null buffer");
+    int chunk = 0;
+    int rc = check_bme_shape(h, B, N, &chunk);
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    try {
+        const size_t PN = (size_t)N * (N - 1) / 2, T = (size_t)pfnj::table_len(N), b = (size_t)B;
+        std::vector<int32_t> h_start, h_slots, h_steps;
+        std::vector<double> h_len, h_tl;
+        std::vector<uint8_t> h_st;
+        if (device) {
+            h_start.resize(b * T); h_slots.resize(b * T); h_steps.resize(b); h_len.resize(b * T); h_tl.resize(b); h_st.resize(b);
+            HIPCHK(h, hipMemcpyAsync(h_start.data(), start, b * T * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+        }
+        const int32_t* st_in = device ? h_start.data() : start;
+        if ((rc = check_bme_starts(h, st_in, B, N))) return rc;
+        ++h->bme_calls;
+        int32_t* o_slots = device ? h_slots.data() : slots;
+        double* o_len = device ? h_len.data() : lengths;
+        int32_t* o_steps = device ? h_steps.data() : steps;
+        double* o_tl = device ? h_tl.data() : tree_length;
+        uint8_t* o_st = device ? h_st.data() : status;
+        if (!device && (rc = ensure_buffer(h, &h->d_bme_preds, &h->d_bme_preds_bytes, (size_t)chunk * PN * sizeof(float)))) return rc;
+        for (int b0 = 0; b0 < B; b0 += chunk) {
+            const int nb = std::min(chunk, B - b0);
+            const float* d_preds = preds + (size_t)b0 * PN;
+            if (!device) {
+                HIPCHK(h, hipMemcpyAsync(h->d_bme_preds, d_preds, (size_t)nb * PN * sizeof(float), hipMemcpyHostToDevice, h->stream));
+                d_preds = h->d_bme_preds;
+            }
+            if ((rc = bme_chunk(h, d_preds, st_in + (size_t)b0 * T, nb, N, o_slots + (size_t)b0 * T, o_len + (size_t)b0 * T, o_steps + b0,
+                                o_tl + b0, o_st + b0)))
+                return rc;
+        }
+        if (device) {
+            HIPCHK(h, hipMemcpyAsync(slots, h_slots.data(), b * T * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipMemcpyAsync(lengths, h_len.data(), b * T * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipMemcpyAsync(steps, h_steps.data(), b * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipMemcpyAsync(tree_length, h_tl.data(), b * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipMemcpyAsync(status, h_st.data(), b, hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+        }
+    } catch (const std::bad_alloc&) { return fail(h, PF_ENOMEM, "out of host memory for the tables of N=%d sequences", N); }
+    return PF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2195,6 +2337,8 @@ int pf_destroy(pf_handle_t* h) {
     if (h->d_tiled_tab) hipFree(h->d_tiled_tab);
     if (h->d_nj) hipFree(h->d_nj);
     if (h->d_nj_io) hipFree(h->d_nj_io);
+    if (h->d_bme) hipFree(h->d_bme);
+    if (h->d_bme_preds) hipFree(h->d_bme_preds);
     if (h->d_w) hipFree(h->d_w);
     if (h->d_wst) hipFree(h->d_wst);
     if (h->d_wtab) hipFree(h->d_wtab);
@@ -2407,6 +2551,18 @@ int pf_nj_joins_device(pf_handle_t* h, const float* d_preds, int32_t B, int32_t 
     return nj_device_impl(h, d_preds, B, N, d_slots, d_lengths, d_nonfinite);
 }
 
+int pf_bme_nni(pf_handle_t* h, const float* preds, const int32_t* start_slots, int32_t B, int32_t N, int32_t* slots, double* lengths,
+               int32_t* steps, double* tree_length, uint8_t* status) {
+    if (!h) return PF_EINVAL;
+    return bme_impl(h, false, preds, start_slots, B, N, slots, lengths, steps, tree_length, status);
+}
+
+int pf_bme_nni_device(pf_handle_t* h, const float* d_preds, const int32_t* d_start_slots, int32_t B, int32_t N, int32_t* d_slots,
+                      double* d_lengths, int32_t* d_steps, double* d_tree_length, uint8_t* d_status) {
+    if (!h) return PF_EINVAL;
+    return bme_impl(h, true, d_preds, d_start_slots, B, N, d_slots, d_lengths, d_steps, d_tree_length, d_status);
+}
+
 int pf_forward_device(pf_handle_t* h, const uint8_t* d_idx, int32_t B, int32_t N, int32_t L, float* d_out) {
     if (!h) return PF_EINVAL;
     return forward_device_impl(h, d_idx, B, N, 0, L, L, d_out);
@@ -2610,6 +2766,7 @@ int pf_profile_reset(pf_handle_t* h) {
     h->coll_calls = 0;
     h->rechecked = 0;
     h->nj_calls = 0;
+    h->bme_calls = 0;
     return PF_OK;
 }
 
@@ -2628,6 +2785,11 @@ int pf_profile_get(pf_handle_t* h, const char* kernel, int64_t* launches, double
     }
     if (std::strcmp(kernel, "nj_joins") == 0) {         // pf_nj_joins / pf_nj_joins_device calls
         if (launches) *launches = h->nj_calls;
+        if (total_ms) *total_ms = 0.0;
+        return PF_OK;
+    }
+    if (std::strcmp(kernel, "bme_nni") == 0) {          // pf_bme_nni / pf_bme_nni_device calls
+        if (launches) *launches = h->bme_calls;
         if (total_ms) *total_ms = 0.0;
         return PF_OK;
     }

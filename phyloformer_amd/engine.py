@@ -134,6 +134,13 @@ SIGNATURES = {
     "pf_nj_format_joins_n": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32,
                                          C.c_char_p, C.c_int64]),
     "pf_tile_bound": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
+    "pf_bme_nni": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                             C.c_void_p]),
+    "pf_bme_nni_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
+    "pf_bme_nni_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p]),
+    "pf_bme_newick_n": (C.c_int64, [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32, C.c_char_p, C.c_int64]),
     "pf_forward_weighted": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "pf_forward_weighted_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "pf_forward_sites_weighted": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
@@ -153,7 +160,8 @@ CALL_TIME_SYMBOLS = frozenset({"pf_forward_site_map", "pf_forward_site_map_devic
                                "pf_forward_weighted_device", "pf_forward_sites_weighted", "pf_bootstrap_weighted",
                                "pf_padded_sites", "pf_boot_counts", "pf_compress_sites", "pf_forward_place",
                                "pf_place_stats_device", "pf_forward_tiled", "pf_tile_combine_device", "pf_tile_groups",
-                               "pf_tile_bound", "pf_nj_joins", "pf_nj_joins_device", "pf_nj_format_joins_n"})
+                               "pf_tile_bound", "pf_nj_joins", "pf_nj_joins_device", "pf_nj_format_joins_n", "pf_bme_nni",
+                               "pf_bme_nni_device", "pf_bme_nni_host", "pf_bme_newick_n"})
 
 _lib: Optional[C.CDLL] = None
 
@@ -539,6 +547,46 @@ class Engine:
         [B][2 (N - 3) + 3]``, ``nonfinite uint8 [B]`` (asynchronous on the handle's stream)."""
         self._check(self._optional("pf_nj_joins_device")(self._h, C.c_void_p(d_preds), B, N, C.c_void_p(d_slots),
                                                          C.c_void_p(d_lengths), C.c_void_p(d_nonfinite)))
+
+    # -- balanced NNI refinement -------------------------------------------------------------
+    def bme_nni(self, preds: np.ndarray, start_slots: np.ndarray):
+        """Balanced minimum-evolution NNI refinement on the GPU (``pf_bme_nni``): distances ``float32[B, P_N]`` and start
+        join tables ``int32[B, T]`` (``Engine.nj_joins``' slots, or any valid join table) → ``(slots int32[B, T], lengths
+        float64[B, T], steps int32[B], tree_length float64[B], status uint8[B])`` (``[P_N]`` / ``[T]`` drop ``B``): the
+        tree of ``bme.bme_nni`` - a local optimum of the balanced tree length - as a join table with balanced branch
+        lengths, bit for bit that of ``hostio.bme_nni_host``.  ``status`` 0 = ok, 1 = a NaN or an infinity in the source
+        (its results are zeros: use ``hostio.bme_newick``), 2 = stopped at the cap of ``16 N`` moves."""
+        fn = self._optional("pf_bme_nni")
+        p = np.ascontiguousarray(np.asarray(preds, dtype=np.float32))
+        st = np.ascontiguousarray(np.asarray(start_slots, dtype=np.int32))
+        single = p.ndim == 1
+        if single:
+            p, st = p[None, :], st[None, :] if st.ndim == 1 else st
+        if p.ndim != 2:
+            raise ValueError(f"expected distances [B, P] or [P], got {p.shape}")
+        B, N = p.shape[0], self._seqs_of_pairs(p.shape[1])
+        T = max(0, 2 * (N - 3) + 3)
+        if st.shape != (B, T):
+            raise ValueError(f"expected start tables {[B, T]}, got {list(st.shape)}")
+        slots = np.zeros((B, T), dtype=np.int32)
+        lengths = np.zeros((B, T), dtype=np.float64)
+        steps = np.zeros(B, dtype=np.int32)
+        tree_length = np.zeros(B, dtype=np.float64)
+        status = np.zeros(B, dtype=np.uint8)
+        self._check(fn(self._h, p.ctypes.data if p.size else None, st.ctypes.data if T else None, B, N,
+                       slots.ctypes.data if T else None, lengths.ctypes.data if T else None, steps.ctypes.data if B else None,
+                       tree_length.ctypes.data if B else None, status.ctypes.data if B else None))
+        out = (slots, lengths, steps, tree_length, status)
+        return tuple(x[0] for x in out) if single else out
+
+    def bme_nni_device(self, d_preds: int, d_start_slots: int, B: int, N: int, d_slots: int, d_lengths: int, d_steps: int,
+                       d_tree_length: int, d_status: int):
+        """``pf_bme_nni_device``: device ``preds float32 [B][P_N]`` and ``start_slots int32 [B][T]`` → device ``slots`` /
+        ``lengths [B][T]``, ``steps int32``, ``tree_length float64``, ``status uint8 [B]``.  Synchronises the handle's
+        stream once per round of steps: the results are complete on return."""
+        self._check(self._optional("pf_bme_nni_device")(self._h, C.c_void_p(d_preds), C.c_void_p(d_start_slots), B, N,
+                                                        C.c_void_p(d_slots), C.c_void_p(d_lengths), C.c_void_p(d_steps),
+                                                        C.c_void_p(d_tree_length), C.c_void_p(d_status)))
 
     # -- site weights -----------------------------------------------------------------------
     @staticmethod

@@ -21,6 +21,8 @@ from .engine import load_library
 _PRIVATE = {
     "pf_nj_support_n": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_char_p), C.c_void_p,
                                     C.c_int32, C.c_int32, C.c_char_p, C.c_int64]),
+    "pf_bme_newick_steps_n": (C.c_int64, [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32, C.c_char_p,
+                                          C.c_int64, C.c_void_p]),
 }
 
 
@@ -128,6 +130,56 @@ def nj_newick(preds: np.ndarray, ids: Sequence[str], clamp_negative: bool = True
     buf = C.create_string_buffer(int(need) + 1)
     w = lib.pf_nj_newick_n(p.ctypes.data, n, arr, lens.ctypes.data, int(clamp_negative), buf, need)
     return buf.raw[:w]
+
+
+def bme_newick(preds: np.ndarray, ids: Sequence[str], clamp_negative: bool = True, with_steps: bool = False):
+    """``pf_bme_newick_n``: distance vector ``[P]`` + ids → Newick text (utf-8 bytes) of the neighbour-joining tree refined
+    by balanced NNIs, with balanced branch lengths (the CLI's ``--bme``) - byte-identical to ``bme.bme_newick_py``.
+    ``with_steps``: ``(text, moves)``."""
+    lib = _lib()
+    n = len(ids)
+    p = np.ascontiguousarray(np.asarray(preds, dtype=np.float32).reshape(-1))
+    if p.size != n * (n - 1) // 2:
+        raise ValueError(f"expected {n * (n - 1) // 2} distances for {n} sequences, got {p.shape}")
+    enc = [s.encode("utf8") for s in ids]
+    arr = (C.c_char_p * n)(*enc)
+    lens = np.array([len(e) for e in enc], dtype=np.int64)
+    # (sized by the NJ text plus room for longer numbers: one refinement, not two)
+    cap = int(lens.sum()) + 64 * max(n, 1) + 64
+    buf = C.create_string_buffer(cap)
+    steps = C.c_int32(0)
+    w = lib.pf_bme_newick_steps_n(p.ctypes.data, n, arr, lens.ctypes.data, int(clamp_negative), buf, cap, C.byref(steps))
+    if w > cap:
+        buf = C.create_string_buffer(int(w))
+        w = lib.pf_bme_newick_n(p.ctypes.data, n, arr, lens.ctypes.data, int(clamp_negative), buf, w)
+    if w < 0:
+        raise RuntimeError(f"pf_bme_newick_n failed with status {w}")
+    return (buf.raw[:w], int(steps.value)) if with_steps else buf.raw[:w]
+
+
+def bme_nni_host(preds: np.ndarray, start_slots: np.ndarray):
+    """``pf_bme_nni_host``: ``Engine.bme_nni`` without a device - the same bodies run serially, the same bits.
+    ``float32[B, P_N]``, ``int32[B, T]`` → ``(slots, lengths, steps, tree_length, status)``.  ``ValueError`` for what
+    the library refuses (``N < 3``, an invalid start table)."""
+    lib = load_library()
+    p = np.ascontiguousarray(np.asarray(preds, dtype=np.float32))
+    st = np.ascontiguousarray(np.asarray(start_slots, dtype=np.int32))
+    if p.ndim != 2 or st.ndim != 2 or st.shape[0] != p.shape[0]:
+        raise ValueError(f"expected distances [B, P] and start tables [B, T], got {p.shape} and {st.shape}")
+    b = p.shape[0]
+    n = (1 + int(round((1 + 8 * p.shape[1]) ** 0.5))) // 2
+    t = 2 * (n - 3) + 3
+    if n * (n - 1) // 2 != p.shape[1] or n < 3 or st.shape[1] != t or b < 1:
+        raise ValueError(f"{p.shape[1]} distances and {st.shape[1]} slots are not those of N >= 3 sequences")
+    slots, lengths = np.zeros((b, t), dtype=np.int32), np.zeros((b, t), dtype=np.float64)
+    steps, tree_length, status = np.zeros(b, dtype=np.int32), np.zeros(b, dtype=np.float64), np.zeros(b, dtype=np.uint8)
+    rc = lib.pf_bme_nni_host(p.ctypes.data, st.ctypes.data, b, n, slots.ctypes.data, lengths.ctypes.data, steps.ctypes.data,
+                             tree_length.ctypes.data, status.ctypes.data)
+    if rc == -1:
+        raise ValueError("pf_bme_nni_host refused its arguments (an invalid start table?)")
+    if rc < 0:
+        raise RuntimeError(f"pf_bme_nni_host failed with status {rc}")
+    return slots, lengths, steps, tree_length, status
 
 
 def _join_table(slots, lengths, n: int) -> Tuple[np.ndarray, np.ndarray]:

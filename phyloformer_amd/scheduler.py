@@ -153,16 +153,22 @@ class DirectoryRunner:
     the launch's forward, the others follow it."""
 
     def __init__(self, engine, out_dir: str, trees: bool = False, batch: int = 0,
-                 io_threads: int = 4, native_io: bool = True, progress=None, modes: Sequence[Analysis] = ()):
+                 io_threads: int = 4, native_io: bool = True, progress=None, modes: Sequence[Analysis] = (),
+                 bme: bool = False):
+        if bme and not trees:
+            raise ValueError("--bme refines the tree of --trees: give -t as well")
         self.engines = list(engine) if isinstance(engine, (list, tuple)) else [engine]
         self.out_dir = out_dir
         self.trees = trees
+        self.bme = bme                # with --trees: <stem>.bme.nwk, the NJ tree refined by balanced NNIs, as well
         self.batch = batch            # 0 = auto per shape
         self.io_threads = max(1, io_threads)
         self.native_io = native_io
         self.progress = progress
         self.stats = {"alignments": 0, "launches": 0, "forward_s": 0.0, "load_wait_s": 0.0,
                       "write_wait_s": 0.0, "shapes": {}, "gpu_streams": len(self.engines)}
+        if bme:
+            self.stats.update({"bme": 0, "bme_steps": 0, "bme_device": 0, "bme_device_s": 0.0})
         self.modes = list(modes)
         for m in self.modes:
             m.bind(self.modes)
@@ -204,6 +210,47 @@ class DirectoryRunner:
             return newick_of_joins(slots, lengths, ids)
         from .hostio import newick_of_joins_py
         return newick_of_joins_py(slots, lengths, ids)
+
+    def bme_tree(self, vec: np.ndarray, ids: List[str]):
+        """``(text, moves)`` of the balanced-NNI refinement of the neighbour-joining tree of a distance vector (``--bme``),
+        from the same side as ``nj``."""
+        if self.native_io:
+            from .hostio import bme_newick
+            return bme_newick(vec, ids, with_steps=True)
+        from .bme import bme_tree_py
+        return bme_tree_py(vec, ids)
+
+    def _bme_device(self, engine, n: int, preds: np.ndarray):
+        """On the GPU thread, for a launch of files with at least ``bme.BME_DEVICE_MIN`` sequences: every file's NJ joins
+        and their refinement on the device; ``(slots, lengths, moves)`` per file, None for a file with a non-finite
+        distance (it keeps the host's path) - or None for the launch."""
+        from . import bme
+        if bme.BME_DEVICE_MIN is None or n < max(3, bme.BME_DEVICE_MIN):
+            return None
+        t0 = time.perf_counter()
+        start, _lengths, nonfinite = engine.nj_joins(preds)
+        # (a flagged source's joins are unspecified: any valid start table stands in, its result is not used)
+        start = np.where(np.asarray(nonfinite, dtype=bool)[:, None], bme.caterpillar_slots(n)[None, :], start)
+        slots, lengths, steps, _length, status = engine.bme_nni(preds, start)
+        tables = [None if bad or st == bme.NONFINITE else (s, l, int(k))
+                  for s, l, k, st, bad in zip(slots, lengths, steps, status, nonfinite)]
+        self.book(bme_device=sum(t is not None for t in tables), bme_device_s=time.perf_counter() - t0)
+        return tables
+
+    def _write_bme(self, group: list, preds: np.ndarray, tables):
+        """``<stem>.bme.nwk`` of some files of a launch, on a writer thread: formatted from the device's table where there
+        is one, refined on the host where not."""
+        moves = 0
+        for k, (e, pred) in enumerate(zip(group, preds)):
+            ids = e.ids()
+            table = tables[k] if tables is not None else None
+            if table is None:
+                text, steps = self.bme_tree(pred, ids)
+            else:
+                text, steps = self.newick_of_joins(table[0], table[1], ids), table[2]
+            self.put(e.path, "bme.nwk", text)
+            moves += steps
+        self.book(bme=len(group), bme_steps=moves)
 
     def book(self, **amounts):
         """Add to the run's stats from inside a mode's own engine call (takes the runner's lock)."""
@@ -253,6 +300,11 @@ class DirectoryRunner:
         preds, payload = mode.forward(self, engine, shape, batch) if mode else (engine.forward(batch), ())
         dt = time.perf_counter() - t0
         tree = not (mode and self.trees and mode.writes_tree(shape))      # (False: the mode writes the tree itself)
+        if self.bme:
+            tables = self._bme_device(engine, shape[0], preds)
+            cap = self.writer_cap()
+            submit([(self._write_bme, group[k::cap], preds[k::cap], None if tables is None else tables[k::cap])
+                    for k in range(min(cap, len(group)))])
         with self._lock:
             self.stats["forward_s"] += dt
             self.stats["launches"] += 1
@@ -582,7 +634,8 @@ def summarize(stats: dict, load_s: float = 0.0) -> dict:
             "alignments_per_s_forward_only": round(n * stats.get("gpu_streams", 1) / stats["forward_s"], 3)
             if stats["forward_s"] > 0 else None,
             "replicates": stats.get("replicates", 0), "bootstrap_s": round(stats.get("bootstrap_s", 0.0), 6),
-            "windows": stats.get("windows", 0), "windows_s": round(stats.get("windows_s", 0.0), 6)}
+            "windows": stats.get("windows", 0), "windows_s": round(stats.get("windows_s", 0.0), 6),
+            **({k: round(stats[k], 6) for k in ("bme", "bme_steps", "bme_device", "bme_device_s")} if "bme" in stats else {})}
 
 
 def run_multi_device(script: str, argv: List[str], devices: Sequence[int], shard: str = "files") -> Tuple[int, List[dict]]:
