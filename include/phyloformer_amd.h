@@ -117,6 +117,9 @@ const char* pf_last_error(const pf_handle_t* h);
  *   "sub_floats" int   distances one sub-call of pf_forward_leave_one_out / pf_forward_place / pf_forward_tiled may
  *                      hold on the device (default 4194304; <= 0 restores it); sub-calls are whole sources, one source
  *                      always runs whole, and the results do not depend on it; tests/tuning
+ *   "spr_pairs_simple" int 1 = pf_bme_spr forms its pair table with the one-thread-per-entry kernel instead of the
+ *                      tiled one (default 0): the same bits; the baseline of tools/spr_bench.py
+ *   "spr_step_cap" int moves after which pf_bme_spr caps a source (status 2); <= 0 (default): 16 N; tests
  *   "colstats_fine" int k_colstats blocks per pair group (0), per run of a group (1) or chosen from the batch
  *                      size (-1, default): the same summation tree either way, so the same bits; tests/tools
  *   "two_streams" int  0 = a batch runs on one stream; default 1: forwards of >= 2 alignments run as two
@@ -405,6 +408,24 @@ int pf_bme_nni_device(pf_handle_t* h, const float* d_preds, const int32_t* d_sta
 int pf_bme_nni_host(const float* preds, const int32_t* start_slots, int32_t B, int32_t N, int32_t* slots, double* lengths, int32_t* steps,
                     double* tree_length, uint8_t* status);
 
+/* ---- balanced subtree pruning and regrafting of a join table (additive to ABI 5) ----
+ *
+ * Balanced SPR moves (FastME's -s) from a start tree to a local optimum of the balanced tree length, with balanced
+ * branch lengths: phyloformer_amd/bme.py::bme_spr states the algorithm (pair table, candidates, the rule dL < -1e-12 on
+ * the key (dL, S row, target edge), the chain of swaps) and DESIGN.md section 22 the device form.  Arguments, results,
+ * status codes and refusals are those of the three pf_bme_nni functions above, entry point by entry point; the state of
+ * one source is about 184 N^2 bytes here (the pair table of the 4N - 6 subtrees on top).  Every step forms its table from
+ * scratch on the device; the handle's stream is synchronised once per round of 32 steps.  pf_bme_spr_host runs the same
+ * kernel bodies serially: all results equal bit for bit.  pf_profile_get("bme_spr") counts the calls of the two handle
+ * entry points.  Options: "spr_pairs_simple" (1: the pair table by the one-thread-per-entry kernel, the baseline of
+ * tools/spr_bench.py; the same bits), "spr_step_cap" (> 0: moves after which a source is capped instead of 16 N). */
+int pf_bme_spr(pf_handle_t* h, const float* preds, const int32_t* start_slots, int32_t B, int32_t N, int32_t* slots, double* lengths,
+               int32_t* steps, double* tree_length, uint8_t* status);
+int pf_bme_spr_device(pf_handle_t* h, const float* d_preds, const int32_t* d_start_slots, int32_t B, int32_t N, int32_t* d_slots,
+                      double* d_lengths, int32_t* d_steps, double* d_tree_length, uint8_t* d_status);
+int pf_bme_spr_host(const float* preds, const int32_t* start_slots, int32_t B, int32_t N, int32_t* slots, double* lengths, int32_t* steps,
+                    double* tree_length, uint8_t* status);
+
 /* ---- site weights: weighted forward, pattern compression, bootstrap on distinct sites (additive to ABI 5) ----
  *
  * Nothing in the network depends on a site's position, and every reduction over sites is a plain sum (the row-attention
@@ -534,9 +555,10 @@ int pf_memcpy_d2h(pf_handle_t* h, void* dst, const void* src, size_t bytes);
  * pf_site_moments_device), "gather_taxa" (k_gather_taxa of pf_forward_taxa / pf_forward_leave_one_out /
  * pf_gather_taxa_device), "loo_stats" (the reduction of pf_forward_leave_one_out / pf_loo_stats_device).
  * "weight_sums" (k_weight_sums of the weighted forwards), "place_stats" (the reduction of pf_forward_place /
- * pf_place_stats_device), "tile_combine" (k_tile_combine of pf_forward_tiled / pf_tile_combine_device).  Totals accumulate until reset.
+ * pf_place_stats_device), "tile_combine" (k_tile_combine of pf_forward_tiled / pf_tile_combine_device), "bme_pairs" (the pair table of the first
+ * step of every round of pf_bme_spr / pf_bme_spr_device: k_bme_pairs, or k_bme_pairs_simple under "spr_pairs_simple").  Totals accumulate until reset.
  * "nj_joins" returns the number of pf_nj_joins / pf_nj_joins_device calls since the last reset in *launches (counted
- * always; *total_ms = 0), "bme_nni" likewise that of pf_bme_nni / pf_bme_nni_device calls.  "collectives" returns the number of all-reduces issued since the last reset in
+ * always; *total_ms = 0), "bme_nni" likewise that of pf_bme_nni / pf_bme_nni_device calls, "bme_spr" that of pf_bme_spr / pf_bme_spr_device calls.  "collectives" returns the number of all-reduces issued since the last reset in
  * *launches (counted always, no profiling option needed; *total_ms = 0); "rechecked" likewise the number of
  * alignments the range re-check (option "recheck_above") computed again on the float64 kernels. */
 int pf_profile_reset(pf_handle_t* h);
@@ -655,6 +677,11 @@ int64_t pf_nj_format_joins_n(const int32_t* slots, const double* lengths, int32_
  * handle.  Sizing protocol as pf_format_phylip. */
 int64_t pf_bme_newick_n(const float* preds, int32_t n, const char* const* ids, const int64_t* id_lens, int32_t clamp_negative,
                         char* out, int64_t cap);
+
+/* The same with the tree refined by balanced SPR moves (the CLI's --spr; bme.py::spr_newick_py writes the same bytes):
+ * pf_bme_spr_host in pf_bme_nni_host's place. */
+int64_t pf_bme_spr_newick_n(const float* preds, int32_t n, const char* const* ids, const int64_t* id_lens, int32_t clamp_negative,
+                            char* out, int64_t cap);
 
 /* ---- many files per call, on native threads (ABI 4; tree_paths: ABI 5) ---------------------------
  *

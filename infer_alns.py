@@ -46,6 +46,11 @@ def build_parser():
                              "nearest-neighbour interchanges to a local optimum of the balanced minimum-evolution tree length, "
                              "with balanced branch lengths (the BNNI search of FastME -n B; no SPR moves); every other output "
                              "keeps its bytes; the trees of windows, cuts and replicates stay NJ")
+    parser.add_argument("--spr", action="store_true",
+                        help="with -t: also write <stem>.spr.nwk, the NJ tree refined by balanced subtree-pruning-and-regrafting "
+                             "moves to a local optimum of the balanced minimum-evolution tree length, with balanced branch "
+                             "lengths (the SPR search of FastME -s); independent of --bme (each writes its own file); every "
+                             "other output keeps its bytes; the trees of windows, cuts and replicates stay NJ")
     parser.add_argument("--device", type=int, default=0, help="HIP device ordinal (default 0)")
     parser.add_argument("--devices", default=None,
                         help="comma-separated HIP device ordinals: shard the files over these GPUs, "
@@ -85,6 +90,10 @@ def main(argv=None):
         parser.error("--bme refines the tree of --trees: give -t as well")
     if args.bme and args.shard == "sites":
         parser.error("--bme cannot be combined with --shard sites: the site-sharded runner writes NJ trees only")
+    if args.spr and not args.trees:
+        parser.error("--spr refines the tree of --trees: give -t as well")
+    if args.spr and args.shard == "sites":
+        parser.error("--spr cannot be combined with --shard sites: the site-sharded runner writes NJ trees only")
 
     from phyloformer_amd import scheduler
 
@@ -161,7 +170,7 @@ def main(argv=None):
             e.set_option("two_streams", 0)
     runner = scheduler.DirectoryRunner(engines, out_dir, trees=args.trees, batch=args.batch,
                                        io_threads=args.io_threads, native_io=not args.python_io,
-                                       progress=bar.update if bar is not None else None, modes=modes, bme=args.bme)
+                                       progress=bar.update if bar is not None else None, modes=modes, bme=args.bme, spr=args.spr)
     try:
         stats = runner.run(paths)
     finally:

@@ -162,4 +162,162 @@ inline hipError_t launch_lengths(hipStream_t s, const Args& a, int B) {
     return hipGetLastError();
 }
 
+// ---- balanced subtree pruning and regrafting (pf_bme_spr, pf_bme_spr_device; the bodies and the
+// order of a step are pf_bme_host.h's).  Per step, after k_bme_init once:
+//   k_bme_number        grid (1, sources), one thread: the numbering of the rooted tree
+//   k_bme_depth         grid (ceil(nodes / 256), rows, sources): one thread per (row, node)
+//   k_bme_build         as above: M of every row (a finished source has cleared its `rebuild`)
+//   k_bme_pairs         grid (ceil(rows / 16), ceil(rows / 16), sources): T by 16 x 16 tiles, M and the weights staged
+//                       leaf by leaf of the pairwise sum through LDS (2 x 16 x 129 doubles = 33,024 bytes); a tile whose
+//                       entries all share a leaf writes its zeros and leaves
+//   k_bme_pairs_simple  grid (ceil(rows / 256), rows, sources): T, one thread per entry from global memory (the baseline;
+//                       option "spr_pairs_simple")
+//   k_bme_spr_eval      grid (ceil(edges / SPR_EVAL_EDGES), rows, sources): one thread per (S row, target edge), the
+//                       workgroup's minimum key in LDS
+//   k_bme_spr_move      grid (1, sources): the minimum of the partial minima; one thread decides and moves
+// at the end k_bme_eval and k_bme_lengths as above, on depth and M of the final topology.
+
+constexpr int SPR_EVAL_EDGES = THREADS;      // target edges per workgroup of k_bme_spr_eval: one per thread
+
+__global__ __launch_bounds__(64) void k_bme_number(SprArgs s) {
+    if (threadIdx.x == 0) number_tree(s, (size_t)blockIdx.y);
+}
+
+__global__ __launch_bounds__(THREADS) void k_bme_depth(SprArgs s) {
+    const int v = (int)blockIdx.x * THREADS + (int)threadIdx.x;
+    if (v < (int)nodes_of(s.b.N)) depth_elem(s, (size_t)blockIdx.z, (int64_t)blockIdx.y, v);
+}
+
+__global__ __launch_bounds__(PAIR_TILE * PAIR_TILE) void k_bme_pairs(SprArgs s) {
+    __shared__ double lm[PAIR_TILE * PAIR_STRIDE], lw[PAIR_TILE * PAIR_STRIDE];
+    const size_t src = (size_t)blockIdx.z;
+    const int tx = (int)blockIdx.y, ty = (int)blockIdx.x, tid = (int)threadIdx.x;
+    if (spr_idle(s, src)) return;
+    PairThread t;
+    pairs_tile_begin(s, src, tx, ty, tid, t);
+    if (__syncthreads_or(t.active)) {
+        SumWalk walk;
+        walk.start(s.b.N);
+        int lo = 0, cnt = 0;
+        for (int ev = walk.next(&lo, &cnt); ev; ev = walk.next(&lo, &cnt)) {
+            if (ev == 2) { pairs_tile_add(t); continue; }
+            __syncthreads();                                         // the leaf before has been read
+            pairs_tile_stage(s, src, tx, ty, lo, cnt, tid, PAIR_TILE * PAIR_TILE, lm, lw);
+            __syncthreads();
+            pairs_tile_leaf(cnt, tid, lm, lw, t);
+        }
+    }
+    pairs_tile_end(s, src, tx, ty, tid, t);
+}
+
+__global__ __launch_bounds__(THREADS) void k_bme_pairs_simple(SprArgs s) {
+    const int64_t Y = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+    if (Y < rows_of(s.b.N)) pairs_elem(s, (size_t)blockIdx.z, (int64_t)blockIdx.y, Y);
+}
+
+__global__ __launch_bounds__(THREADS) void k_bme_spr_eval(SprArgs s) {
+    __shared__ SprKey keys[THREADS];
+    const size_t src = (size_t)blockIdx.z;
+    keys[threadIdx.x] = spr_eval_thread(s, src, (int64_t)blockIdx.y, (int)blockIdx.x, (int)threadIdx.x, THREADS);
+    for (int st = pfnj::reduce_first_step(THREADS); st > 0; st >>= 1) {
+        __syncthreads();
+        spr_reduce_step(keys, (int)threadIdx.x, st, THREADS);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) s.spart[src * (size_t)s.spart_cap + (size_t)blockIdx.y * gridDim.x + blockIdx.x] = keys[0];
+}
+
+__global__ __launch_bounds__(THREADS) void k_bme_spr_move(SprArgs s) {
+    __shared__ SprKey keys[THREADS];
+    const size_t src = (size_t)blockIdx.y;
+    keys[threadIdx.x] = spr_move_thread_key(s, src, (int)threadIdx.x, THREADS);
+    for (int st = pfnj::reduce_first_step(THREADS); st > 0; st >>= 1) {
+        __syncthreads();
+        spr_reduce_step(keys, (int)threadIdx.x, st, THREADS);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) spr_decide(s, src, keys[0]);
+}
+
+// bytes of one source's state: balanced NNI's arrays that the search shares (no move, rowh, rowcase), T, the partial
+// minima, the numbering and the path
+struct SprLayout {
+    size_t d, M, q, edge_len, T, part, spart, ints, depth, flags, total;
+    explicit SprLayout(int N) {
+        const size_t n = (size_t)N, nodes = (size_t)nodes_of(N), rows = (size_t)rows_of(N), root = (size_t)root_of(N);
+        auto up8 = [](size_t x) { return (x + 7) / 8 * 8; };
+        d = n * n * sizeof(double);
+        M = rows * n * sizeof(double);
+        q = root * 6 * sizeof(double);
+        edge_len = root * sizeof(double);
+        T = rows * rows * sizeof(double);
+        part = (size_t)eval_groups(N) * sizeof(Key);
+        spart = rows * (size_t)spr_eval_groups(N, SPR_EVAL_EDGES) * sizeof(SprKey);
+        ints = up8(nodes * sizeof(int32_t));                       // parent, tin, tout, ndepth, path: one share each; children: three
+        depth = up8(rows * nodes * sizeof(int16_t));
+        flags = 8;                                                 // done, rebuild, status, sdone: one byte each per source
+        total = d + M + q + edge_len + T + part + spart + 8 * ints + 8 + depth + flags;      // (+ 8: steps)
+    }
+};
+inline size_t spr_state_bytes(int N) { return SprLayout(N).total; }
+
+// the state of B sources carved from `ws` (8-byte aligned, B * spr_state_bytes(N) bytes), array after array
+inline SprArgs spr_carve(char* ws, const float* preds, int B, int N, int64_t cap) {
+    const SprLayout l(N);
+    const size_t b = (size_t)B, nodes = (size_t)nodes_of(N);
+    auto ints = [&](size_t per) { return (b * nodes * per * sizeof(int32_t) + 7) / 8 * 8; };
+    SprArgs s{};
+    Args& a = s.b;
+    a.preds = preds; a.N = N; a.part_cap = eval_groups(N); a.PN = (int64_t)N * (N - 1) / 2;
+    s.cap = cap > 0 ? cap : step_cap(N); s.epg = SPR_EVAL_EDGES;
+    s.spart_cap = (int)(rows_of(N) * spr_eval_groups(N, SPR_EVAL_EDGES));
+    a.d = reinterpret_cast<double*>(ws);            ws += b * l.d;
+    a.M = reinterpret_cast<double*>(ws);            ws += b * l.M;
+    a.q = reinterpret_cast<double*>(ws);            ws += b * l.q;
+    a.edge_len = reinterpret_cast<double*>(ws);     ws += b * l.edge_len;
+    s.T = reinterpret_cast<double*>(ws);            ws += b * l.T;
+    a.part = reinterpret_cast<Key*>(ws);            ws += b * l.part;
+    s.spart = reinterpret_cast<SprKey*>(ws);        ws += b * l.spart;
+    a.parent = reinterpret_cast<int32_t*>(ws);      ws += ints(1);
+    a.children = reinterpret_cast<int32_t*>(ws);    ws += ints(3);
+    s.tin = reinterpret_cast<int32_t*>(ws);         ws += ints(1);
+    s.tout = reinterpret_cast<int32_t*>(ws);        ws += ints(1);
+    s.ndepth = reinterpret_cast<int32_t*>(ws);      ws += ints(1);
+    s.path = reinterpret_cast<int32_t*>(ws);        ws += ints(1);
+    a.steps = reinterpret_cast<int32_t*>(ws);       ws += b * 8;
+    a.depth = reinterpret_cast<int16_t*>(ws);       ws += (b * (size_t)rows_of(N) * nodes * sizeof(int16_t) + 7) / 8 * 8;
+    a.done = reinterpret_cast<uint8_t*>(ws);        ws += b;
+    a.rebuild = reinterpret_cast<uint8_t*>(ws);     ws += b;
+    a.status = reinterpret_cast<uint8_t*>(ws);      ws += b;
+    s.sdone = reinterpret_cast<uint8_t*>(ws);
+    return s;
+}
+
+// asynchronous on `st`: one round of steps; `ev`, when not NULL, two events recorded around the pair table of the first
+inline hipError_t launch_spr_round(hipStream_t st, const SprArgs& s, int B, bool pairs_simple, hipEvent_t* ev = nullptr) {
+    const int N = s.b.N;
+    const unsigned rows = (unsigned)rows_of(N), nodes = (unsigned)nodes_of(N), b = (unsigned)B;
+    const unsigned tiles = (rows + PAIR_TILE - 1) / PAIR_TILE;
+    for (int step = 0; step < ROUND_STEPS; ++step) {
+        hipLaunchKernelGGL(k_bme_number, dim3(1, b), dim3(64), 0, st, s);
+        hipLaunchKernelGGL(k_bme_depth, dim3((nodes + THREADS - 1) / THREADS, rows, b), dim3(THREADS), 0, st, s);
+        hipLaunchKernelGGL(k_bme_build, dim3((unsigned)((N + THREADS - 1) / THREADS), rows, b), dim3(THREADS), 0, st, s.b);
+        if (ev && step == 0) hipEventRecord(ev[0], st);
+        if (pairs_simple) hipLaunchKernelGGL(k_bme_pairs_simple, dim3((rows + THREADS - 1) / THREADS, rows, b), dim3(THREADS), 0, st, s);
+        else hipLaunchKernelGGL(k_bme_pairs, dim3(tiles, tiles, b), dim3(PAIR_TILE * PAIR_TILE), 0, st, s);
+        if (ev && step == 0) hipEventRecord(ev[1], st);
+        hipLaunchKernelGGL(k_bme_spr_eval, dim3((unsigned)spr_eval_groups(N, SPR_EVAL_EDGES), rows, b), dim3(THREADS), 0, st, s);
+        hipLaunchKernelGGL(k_bme_spr_move, dim3(1, b), dim3(THREADS), 0, st, s);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipGetLastError();
+}
+
+// asynchronous on `st`: q and the lengths of the final topologies
+inline hipError_t launch_spr_finish(hipStream_t st, const SprArgs& s, int B) {
+    hipLaunchKernelGGL(k_bme_eval, dim3((unsigned)s.b.part_cap, (unsigned)B), dim3(THREADS), 0, st, s.b);
+    return launch_lengths(st, s.b, B);
+}
+
 }  // namespace pfbme

@@ -1,5 +1,5 @@
 // Balanced minimum-evolution NNI refinement (pf_bme_nni, pf_bme_nni_device, pf_bme_nni_host, pf_bme_newick_n; DESIGN.md
-// section 21): the bodies of the kernels of pf_bme.hip.h as functions of (source, workgroup, thread), the host-side tree
+// section 21; the balanced SPR search of section 22 follows it below and shares its tree, rows and tables): the bodies of the kernels of pf_bme.hip.h as functions of (source, workgroup, thread), the host-side tree
 // bookkeeping, and the serial driver that runs the same bodies without a device.  Plain C++, no HIP:
 // tests/native/pf_bme_main.cpp runs them on the CPU thread by thread under AddressSanitizer / UBSan; pf_bme.hip.h
 // compiles the bodies for the device too (PF_TAXA_HD).  phyloformer_amd/bme.py is the statement of the algorithm: tree,
@@ -172,10 +172,7 @@ inline void build_row(const Args& a, size_t src, int64_t X) {
 
 // what stands around edge e: its parent p, its sibling s (B), A's row, and e's children (-1 for a leaf)
 struct Quartet { int32_t p, s, arow, c1, c2; };
-PF_TAXA_HD inline Quartet quartet_of(const Args& a, size_t src, int e) {
-    const int64_t nodes = nodes_of(a.N), root = root_of(a.N);
-    const int32_t* parent = a.parent + (int64_t)src * nodes;
-    const int32_t* children = a.children + (int64_t)src * nodes * 3;
+PF_TAXA_HD inline Quartet quartet_of(const int32_t* parent, const int32_t* children, int64_t root, int e) {
     Quartet t;
     t.p = parent[e];
     const int32_t* ch = children + (int64_t)t.p * 3;
@@ -189,6 +186,24 @@ PF_TAXA_HD inline Quartet quartet_of(const Args& a, size_t src, int e) {
     t.c1 = children[(int64_t)e * 3];
     t.c2 = children[(int64_t)e * 3 + 1];
     return t;
+}
+PF_TAXA_HD inline Quartet quartet_of(const Args& a, size_t src, int e) {
+    const int64_t nodes = nodes_of(a.N);
+    return quartet_of(a.parent + (int64_t)src * nodes, a.children + (int64_t)src * nodes * 3, root_of(a.N), e);
+}
+
+// bme.py::Tree.swap: the sibling s of internal edge c and child x of c change places (y is c's other child)
+PF_TAXA_HD inline void swap_blocks(int32_t* parent, int32_t* children, int64_t root, int32_t c, int32_t p, int32_t s, int32_t x, int32_t y) {
+    parent[s] = c;
+    parent[x] = p;
+    int32_t* cc = children + (int64_t)c * 3;
+    cc[0] = s < y ? s : y;
+    cc[1] = s < y ? y : s;
+    int32_t* pc = children + (int64_t)p * 3;
+    const int np = p == root ? 3 : 2;
+    for (int i = 0; i < np; ++i) if (pc[i] == s) pc[i] = x;
+    for (int i = 1; i < np; ++i)                                             // two or three entries: insertion sort
+        for (int j = i; j > 0 && pc[j] < pc[j - 1]; --j) { const int32_t tmp = pc[j]; pc[j] = pc[j - 1]; pc[j - 1] = tmp; }
 }
 
 PF_TAXA_HD inline double d_xy(const Args& a, size_t src, int64_t X, int64_t Y) {
@@ -282,16 +297,7 @@ PF_TAXA_HD inline Move move_decide(const Args& a, size_t src, Key best) {
     m.ok = 1; m.c = best.c; m.p = t.p; m.s = t.s; m.arow = t.arow;
     m.x = best.k == 0 ? t.c1 : t.c2;
     m.y = best.k == 0 ? t.c2 : t.c1;
-    parent[m.s] = m.c;
-    parent[m.x] = m.p;
-    int32_t* cc = children + (int64_t)m.c * 3;
-    cc[0] = m.s < m.y ? m.s : m.y;
-    cc[1] = m.s < m.y ? m.y : m.s;
-    int32_t* pc = children + (int64_t)m.p * 3;
-    const int np = m.p == root ? 3 : 2;
-    for (int i = 0; i < np; ++i) if (pc[i] == m.s) pc[i] = m.x;
-    for (int i = 1; i < np; ++i)                                             // two or three entries: insertion sort
-        for (int j = i; j > 0 && pc[j] < pc[j - 1]; --j) { const int32_t tmp = pc[j]; pc[j] = pc[j - 1]; pc[j - 1] = tmp; }
+    swap_blocks(parent, children, root, m.c, m.p, m.s, m.x, m.y);
     a.steps[src] += 1;
     a.move[src] = m;
     return m;
@@ -601,6 +607,454 @@ struct Serial {
         }
         for (size_t src = 0; src < (size_t)B; ++src)
             for (int e = 0; e < (int)root; ++e) edge_length(a, src, e);
+    }
+
+    void result(size_t src, int32_t* slots, double* lengths, int32_t* steps_out, double* tree_length, uint8_t* status_out) const {
+        result_of(N, &children[src * (size_t)nodes_of(N) * 3], &edge_len[src * (size_t)root_of(N)], steps[src], status[src], slots,
+                  lengths, steps_out, tree_length, status_out);
+    }
+};
+
+// ---- balanced subtree pruning and regrafting (pf_bme_spr, pf_bme_spr_device, pf_bme_spr_host, pf_bme_spr_newick_n;
+// DESIGN.md section 22).  bme.py::bme_spr is the statement: pair table, candidates, rule and the chain of swaps are
+// defined there.  One step, everything from scratch, no host copy in between:
+//   number   one thread: entry / exit times and the depth from the root of every node of the rooted tree
+//   depth    one thread per (row, node): below edge e by the interval test; beyond its parent end by climbing from
+//            parent[e] to the first ancestor whose interval holds the node
+//   build    build_elem as it is (M of every row)
+//   pairs    T[X][Y], one pairwise sum per entry, by tiles through the workgroup's scratch (pairs_tile_*) or one thread
+//            per entry (pairs_elem): the same operands in the same order; 0.0 where X and Y share a leaf
+//   eval     one thread per (S row, target edge): it walks its own path from S's attachment node - the next node is the
+//            forward neighbour whose directed subtree holds the target, one depth lookup -, adds the terms in path
+//            order, and the workgroup's minimum key (dL, S, edge) goes to `spart`
+//   move     the minimum of the partial minima; one thread decides (done, capped, or move) and carries the move out as
+//            the swaps along the path
+// A finished source clears its `rebuild`, so that build_elem returns at once for it too, and keeps depth and M of its
+// final topology: the evaluation and the lengths of balanced NNI (eval_q_thread, edge_length) then give q, lengths and
+// tree_length exactly as bme.py::Table does.  Args::done stays 0 throughout (it would idle that evaluation); the
+// search's own flag is `sdone`.
+
+struct SprKey { double v; int32_t s, e; };            // ordered by (v, s, e)
+PF_TAXA_HD inline SprKey spr_key_none() { return SprKey{INFINITY, INT32_MAX, INT32_MAX}; }
+PF_TAXA_HD inline bool spr_key_less(const SprKey& x, const SprKey& y) {
+    return x.v < y.v || (x.v == y.v && (x.s < y.s || (x.s == y.s && x.e < y.e)));
+}
+PF_TAXA_HD inline void spr_reduce_step(SprKey* keys, int tid, int s, int threads) {
+    if (tid < s && tid + s < threads && spr_key_less(keys[tid + s], keys[tid])) keys[tid] = keys[tid + s];
+}
+
+struct SprArgs {
+    Args b;                 // d, depth, M, q, edge_len, part, parent, children, steps, done (0), rebuild, status
+    double* T;              // [B][4N-6][4N-6]
+    SprKey* spart;          // [B][spart_cap]: the minimum of every workgroup of the evaluation
+    int32_t* tin;           // [B][2N-2]: entry time of every node
+    int32_t* tout;          // [B][2N-2]: the last entry time in its subtree
+    int32_t* ndepth;        // [B][2N-2]: edges from the root
+    int32_t* path;          // [B][2N-2]: u_1 .. u_i, t of the move
+    uint8_t* sdone;         // [B]
+    int64_t cap;            // moves after which a source is capped (step_cap(N) but for tests)
+    int spart_cap, epg;     // epg: target edges per workgroup of the evaluation
+};
+
+PF_TAXA_HD inline bool spr_idle(const SprArgs& s, size_t src) { return s.b.status[src] == ST_NONFINITE || s.sdone[src]; }
+PF_TAXA_HD inline int spr_eval_groups(int N, int epg) { return (int)((root_of(N) + epg - 1) / epg); }
+
+PF_TAXA_HD inline void number_tree(const SprArgs& s, size_t src) {
+    if (spr_idle(s, src)) return;
+    const int64_t nodes = nodes_of(s.b.N), root = root_of(s.b.N);
+    const int32_t* parent = s.b.parent + (int64_t)src * nodes;
+    const int32_t* children = s.b.children + (int64_t)src * nodes * 3;
+    int32_t* tin = s.tin + (int64_t)src * nodes;
+    int32_t* tout = s.tout + (int64_t)src * nodes;
+    int32_t* nd = s.ndepth + (int64_t)src * nodes;
+    int32_t t = 0, v = (int32_t)root;
+    nd[v] = 0; tin[v] = t++;
+    for (int64_t guard = 0; guard < 4 * nodes; ++guard) {            // (every edge is walked twice)
+        const int32_t c = children[(int64_t)v * 3];
+        if (c >= 0) { nd[c] = nd[v] + 1; tin[c] = t++; v = c; continue; }
+        for (;;) {                                                   // v is complete: on to its next sibling, or up
+            tout[v] = t - 1;
+            if (v == root) return;
+            const int32_t p = parent[v];
+            const int32_t* pc = children + (int64_t)p * 3;
+            const int32_t next = pc[0] == v ? pc[1] : pc[1] == v ? pc[2] : -1;
+            if (next >= 0) { nd[next] = nd[p] + 1; tin[next] = t++; v = next; break; }
+            v = p;
+        }
+    }
+}
+
+PF_TAXA_HD inline void depth_elem(const SprArgs& s, size_t src, int64_t X, int v) {
+    if (spr_idle(s, src)) return;
+    const int64_t nodes = nodes_of(s.b.N), root = root_of(s.b.N), rows = rows_of(s.b.N);
+    const int32_t* parent = s.b.parent + (int64_t)src * nodes;
+    const int32_t* tin = s.tin + (int64_t)src * nodes;
+    const int32_t* tout = s.tout + (int64_t)src * nodes;
+    const int32_t* nd = s.ndepth + (int64_t)src * nodes;
+    const int32_t tv = tin[v];
+    const int64_t e = X < root ? X : X - root;
+    const bool below = tin[e] <= tv && tv <= tout[e];
+    int out = -1;
+    if (X < root) {
+        if (below) out = nd[v] - nd[e];
+    } else if (!below) {
+        const int32_t p = parent[e];
+        int32_t w = p;
+        while (w != root && !(tin[w] <= tv && tv <= tout[w])) w = parent[w];
+        out = nd[p] + nd[v] - 2 * nd[w];
+    }
+    s.b.depth[((int64_t)src * rows + X) * nodes + v] = (int16_t)out;
+}
+
+// Do rows X and Y share a leaf?  From the numbering alone: "below e" is the interval of e, "beyond e" its complement.
+// Two intervals of a tree are nested or disjoint; a complement meets an interval unless it lies inside the other's
+// interval; two complements always meet (the root has three children, so two subtrees never cover the tree).
+PF_TAXA_HD inline bool rows_share_leaf(const SprArgs& s, size_t src, int64_t X, int64_t Y) {
+    const int64_t nodes = nodes_of(s.b.N), root = root_of(s.b.N);
+    const int32_t* tin = s.tin + (int64_t)src * nodes;
+    const int32_t* tout = s.tout + (int64_t)src * nodes;
+    const int64_t ex = X < root ? X : X - root, ey = Y < root ? Y : Y - root;
+    const bool x_in_y = tin[ey] <= tin[ex] && tout[ex] <= tout[ey], y_in_x = tin[ex] <= tin[ey] && tout[ey] <= tout[ex];
+    if (X < root && Y < root) return x_in_y || y_in_x;
+    if (X < root) return !x_in_y;
+    if (Y < root) return !y_in_x;
+    return true;
+}
+
+// T[X][Y], one thread per entry straight from global memory
+PF_TAXA_HD inline void pairs_elem(const SprArgs& s, size_t src, int64_t X, int64_t Y) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    if (spr_idle(s, src)) return;
+    const int64_t rows = rows_of(s.b.N);
+    double v = 0.0;
+    if (!rows_share_leaf(s, src, X, Y)) {
+        const double* m = M_row(s.b, src, X);
+        const int16_t* dy = depth_row(s.b, src, Y);
+        v = pfnj::pairwise_sum([&](int j) { return weight(dy[j]) * m[j]; }, s.b.N);
+    }
+    s.T[((int64_t)src * rows + X) * rows + Y] = v;
+}
+
+// pfnj::pairwise_sum's walk as a sequence of events, so that a workgroup can take it together: 1 = the leaf (lo, cnt),
+// cnt <= 128, whose pfnj::leaf_sum is pushed; 2 = the two values on top are replaced by their sum (left + right); 0 =
+// the end, the sum is the one value left.  The events depend on n alone.
+struct SumWalk {
+    int w_lo[pfnj::WALK_DEPTH], w_n[pfnj::WALK_DEPTH], sp;
+    PF_TAXA_HD void start(int n) { w_lo[0] = 0; w_n[0] = n; sp = 1; }
+    PF_TAXA_HD int next(int* lo, int* cnt) {
+        while (sp > 0) {
+            --sp;
+            const int l = w_lo[sp], c = w_n[sp];
+            if (c == 0) return 2;
+            if (c <= 128) { *lo = l; *cnt = c; return 1; }
+            int n2 = c / 2;
+            n2 -= n2 % 8;
+            w_lo[sp] = 0; w_n[sp] = 0; ++sp;
+            w_lo[sp] = l + n2; w_n[sp] = c - n2; ++sp;
+            w_lo[sp] = l; w_n[sp] = n2; ++sp;
+        }
+        return 0;
+    }
+};
+
+// T by tiles: a workgroup of PAIR_TILE^2 threads owns the entries (X, Y) of tile (tx, ty), thread tid the entry
+// (tx * PAIR_TILE + tid / PAIR_TILE, ty * PAIR_TILE + tid % PAIR_TILE).  It takes SumWalk's events together: for a leaf,
+// every thread first stages its share of M[X][lo .. lo + cnt) and of w_Y(lo .. lo + cnt) (from depth, once per (Y, j)
+// instead of once per entry) into `lm` / `lw` [PAIR_TILE][PAIR_STRIDE]; after a barrier every thread forms
+// pfnj::leaf_sum of its entry from them and pushes it.  The operands and their order are pairs_elem's.  PAIR_STRIDE =
+// 129 doubles: the PAIR_TILE rows a wave reads at one j lie 2 banks apart.
+constexpr int PAIR_TILE = 16, PAIR_STRIDE = 129;
+struct PairThread {
+    double val[pfnj::WALK_DEPTH];
+    int vp;
+    bool active;            // inside the table and without a common leaf
+};
+PF_TAXA_HD inline void pairs_tile_begin(const SprArgs& s, size_t src, int tx, int ty, int tid, PairThread& t) {
+    const int64_t rows = rows_of(s.b.N), X = (int64_t)tx * PAIR_TILE + tid / PAIR_TILE, Y = (int64_t)ty * PAIR_TILE + tid % PAIR_TILE;
+    t.vp = 0;
+    t.active = X < rows && Y < rows && !rows_share_leaf(s, src, X, Y);
+}
+PF_TAXA_HD inline void pairs_tile_stage(const SprArgs& s, size_t src, int tx, int ty, int lo, int cnt, int tid, int threads, double* lm,
+                                        double* lw) {
+    const int64_t rows = rows_of(s.b.N);
+    for (int i = tid; i < 2 * PAIR_TILE * cnt; i += threads) {
+        const int r = i / cnt % PAIR_TILE, j = i % cnt;
+        if (i < PAIR_TILE * cnt) {
+            const int64_t X = (int64_t)tx * PAIR_TILE + r;
+            lm[r * PAIR_STRIDE + j] = X < rows ? M_row(s.b, src, X)[lo + j] : 0.0;
+        } else {
+            const int64_t Y = (int64_t)ty * PAIR_TILE + r;
+            lw[r * PAIR_STRIDE + j] = Y < rows ? weight(depth_row(s.b, src, Y)[lo + j]) : 0.0;
+        }
+    }
+}
+PF_TAXA_HD inline void pairs_tile_leaf(int cnt, int tid, const double* lm, const double* lw, PairThread& t) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    if (!t.active) return;
+    const double* m = lm + (tid / PAIR_TILE) * PAIR_STRIDE;
+    const double* w = lw + (tid % PAIR_TILE) * PAIR_STRIDE;
+    t.val[t.vp++] = pfnj::leaf_sum([&](int j) { return w[j] * m[j]; }, 0, cnt);
+}
+PF_TAXA_HD inline void pairs_tile_add(PairThread& t) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    if (!t.active) return;
+    const double right = t.val[--t.vp], left = t.val[--t.vp];
+    t.val[t.vp++] = left + right;
+}
+PF_TAXA_HD inline void pairs_tile_end(const SprArgs& s, size_t src, int tx, int ty, int tid, const PairThread& t) {
+    const int64_t rows = rows_of(s.b.N), X = (int64_t)tx * PAIR_TILE + tid / PAIR_TILE, Y = (int64_t)ty * PAIR_TILE + tid % PAIR_TILE;
+    if (X < rows && Y < rows) s.T[((int64_t)src * rows + X) * rows + Y] = t.active ? t.val[0] : 0.0;
+}
+
+// the row of the directed subtree through neighbour v of node u, away from u
+PF_TAXA_HD inline int64_t row_through(const int32_t* parent, int64_t root, int32_t v, int32_t u) { return parent[v] == u ? (int64_t)v : root + u; }
+// the two neighbours of internal node u besides prev
+PF_TAXA_HD inline void forward_of(const int32_t* parent, const int32_t* children, int64_t root, int32_t u, int32_t prev, int32_t* f) {
+    int n = 0;
+    f[0] = f[1] = -1;
+    for (int i = 0; i < 3; ++i) {
+        const int32_t c = children[(int64_t)u * 3 + i];
+        if (c >= 0 && c != prev && n < 2) f[n++] = c;
+    }
+    if (u != root && parent[u] != prev && n < 2) f[n++] = parent[u];
+}
+
+// The candidate (S row, target edge g): its key, or none when S cannot be regrafted there (g inside S, or on S's
+// attachment node, or that node a leaf).  `path`, when not NULL, receives u_1 .. u_i, t and `path_len` their number.
+PF_TAXA_HD inline SprKey spr_candidate(const SprArgs& s, size_t src, int64_t S, int32_t g, int32_t* path, int32_t* path_len) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const int N = s.b.N;
+    const int64_t nodes = nodes_of(N), root = root_of(N), rows = rows_of(N);
+    const int32_t* parent = s.b.parent + (int64_t)src * nodes;
+    const int32_t* children = s.b.children + (int64_t)src * nodes * 3;
+    const double* T = s.T + (int64_t)src * rows * rows;
+    const int32_t e = (int32_t)(S < root ? S : S - root);
+    const int32_t snode = S < root ? e : parent[e], a = S < root ? parent[e] : e;
+    const int32_t pg = parent[g];
+    if (a < N || g == a || pg == a) return spr_key_none();
+    const int16_t* ds = depth_row(s.b, src, S);
+    if (ds[g] >= 0 || ds[pg] >= 0) return spr_key_none();
+    int32_t f[2];
+    forward_of(parent, children, root, a, snode, f);
+    if (f[1] < 0) return spr_key_none();
+    int32_t u = depth_row(s.b, src, row_through(parent, root, f[0], a))[g] >= 0 ? f[0] : f[1];
+    const int64_t R = row_through(parent, root, u == f[0] ? f[1] : f[0], a);
+    double drs = T[R * rows + S], acc = 0.0;
+    int32_t prev = a;
+    for (int i = 1; i < (int)nodes; ++i) {
+        forward_of(parent, children, root, u, prev, f);
+        if (f[1] < 0) break;                                        // (a leaf on the path: never with a valid tree)
+        const bool last = u == g || u == pg;
+        const int32_t next = last ? (u == g ? pg : g) : depth_row(s.b, src, row_through(parent, root, f[0], u))[g] >= 0 ? f[0] : f[1];
+        const int64_t X = row_through(parent, root, f[0] == next ? f[1] : f[0], u), F = row_through(parent, root, next, u),
+                      Bk = row_through(parent, root, prev, u);
+        const double scaled = weight(i) * (T[R * rows + X] - T[S * rows + X]);
+        const double drx = T[Bk * rows + X] + scaled;
+        const double term = 0.25 * ((drx + T[S * rows + F]) - (drs + T[X * rows + F]));
+        acc = acc + term;
+        if (path) path[i - 1] = u;
+        if (last) {
+            if (path) { path[i] = next; *path_len = i + 1; }
+            return SprKey{acc, (int32_t)S, g};
+        }
+        const double half = 0.5 * T[X * rows + S];
+        drs = 0.5 * drs + half;
+        prev = u; u = next;
+    }
+    return spr_key_none();                                          // never with a valid tree
+}
+
+// Thread `tid` of the evaluation's workgroup (S, wg): the target edges wg * epg + tid, + threads, ... below (wg + 1) * epg
+PF_TAXA_HD inline SprKey spr_eval_thread(const SprArgs& s, size_t src, int64_t S, int wg, int tid, int threads) {
+    SprKey best = spr_key_none();
+    if (spr_idle(s, src)) return best;
+    const int64_t root = root_of(s.b.N);
+    for (int64_t g = (int64_t)wg * s.epg + tid; g < ((int64_t)wg + 1) * s.epg && g < root; g += threads) {
+        const SprKey k = spr_candidate(s, src, S, (int32_t)g, nullptr, nullptr);
+        if (spr_key_less(k, best)) best = k;
+    }
+    return best;
+}
+
+PF_TAXA_HD inline SprKey spr_move_thread_key(const SprArgs& s, size_t src, int tid, int threads) {
+    SprKey best = spr_key_none();
+    if (spr_idle(s, src)) return best;
+    const SprKey* part = s.spart + src * (size_t)s.spart_cap;
+    for (int g = tid; g < s.spart_cap; g += threads)
+        if (spr_key_less(part[g], best)) best = part[g];
+    return best;
+}
+
+// One thread: no qualifying candidate - the source is done; the cap reached - done and capped; else the move, as
+// bme.py::spr_move's swaps along the path.
+PF_TAXA_HD inline void spr_decide(const SprArgs& s, size_t src, SprKey best) {
+    if (spr_idle(s, src)) return;
+    const int N = s.b.N;
+    const int64_t nodes = nodes_of(N), root = root_of(N), rows = rows_of(N);
+    if (!(best.v < THRESHOLD)) { s.sdone[src] = 1; s.b.rebuild[src] = 0; return; }
+    if (s.b.steps[src] >= s.cap) { s.b.status[src] = ST_CAPPED; s.sdone[src] = 1; s.b.rebuild[src] = 0; return; }
+    int32_t* path = s.path + (int64_t)src * nodes;
+    int32_t len = 0;
+    if (best.s < 0 || best.s >= rows || best.e < 0 || best.e >= root ||
+        !(spr_candidate(s, src, best.s, best.e, path, &len).v < THRESHOLD)) {            // never with finite input
+        s.b.status[src] = ST_NONFINITE; s.b.rebuild[src] = 0; return;
+    }
+    int32_t* parent = s.b.parent + (int64_t)src * nodes;
+    int32_t* children = s.b.children + (int64_t)src * nodes * 3;
+    const bool below = best.s < root;
+    const int32_t e = (int32_t)(below ? best.s : best.s - root);
+    for (int32_t j = 0; j + 1 < len; ++j) {
+        const int32_t u = path[j], next = path[j + 1], v = below ? parent[e] : e;
+        if (parent[u] == v) {               // down: S stands beside edge u as s or as A, X_j is a child of u
+            const Quartet t = quartet_of(parent, children, root, u);
+            const bool next_first = t.c1 == next;
+            const bool take_next = !(below && t.s == e);
+            const bool first = take_next == next_first;
+            swap_blocks(parent, children, root, u, t.p, t.s, first ? t.c1 : t.c2, first ? t.c2 : t.c1);
+        } else {                            // up: S is child e of v, X_j stands beside edge v as s or as A
+            const Quartet t = quartet_of(parent, children, root, v);
+            const bool e_first = t.c1 == e;
+            const bool take_e = next != t.s;
+            const bool first = take_e == e_first;
+            swap_blocks(parent, children, root, v, t.p, t.s, first ? t.c1 : t.c2, first ? t.c2 : t.c1);
+        }
+    }
+    s.b.steps[src] += 1;
+}
+
+// The state of B sources on the host, exactly sized, and the serial run of the bodies in the order the launches of
+// pf_bme.hip.h give them.
+struct SprSerial {
+    int B, N;
+    std::vector<double> d, M, q, edge_len, T;
+    std::vector<int16_t> depth;
+    std::vector<Key> part;
+    std::vector<SprKey> spart;
+    std::vector<int32_t> parent, children, steps, tin, tout, ndepth, path;
+    std::vector<uint8_t> done, rebuild, status, sdone;
+    bool tiled = false;       // T by pairs_tile_* instead of pairs_elem: the same bits
+    SprArgs s{};
+
+    bool setup(const float* preds, const int32_t* start_slots, int B_, int N_, int epg, int64_t cap = -1) {
+        B = B_; N = N_;
+        const size_t b = (size_t)B, n = (size_t)N, nodes = (size_t)nodes_of(N), rows = (size_t)rows_of(N), root = (size_t)root_of(N);
+        const size_t G = (size_t)spr_eval_groups(N, epg);
+        d.assign(b * n * n, 0.0); M.assign(b * rows * n, 0.0); q.assign(b * root * 6, 0.0); edge_len.assign(b * root, 0.0);
+        T.assign(b * rows * rows, 0.0); depth.assign(b * rows * nodes, -1); part.assign(b, key_none());
+        spart.assign(b * rows * G, spr_key_none());
+        parent.assign(b * nodes, -1); children.assign(b * nodes * 3, -1); steps.assign(b, 0);
+        tin.assign(b * nodes, 0); tout.assign(b * nodes, 0); ndepth.assign(b * nodes, 0); path.assign(b * nodes, 0);
+        done.assign(b, 0); rebuild.assign(b, 1); status.assign(b, ST_OK); sdone.assign(b, 0);
+        for (size_t i = 0; i < b; ++i)
+            if (!tree_of_joins(start_slots + i * (size_t)pfnj::table_len(N), N, &parent[i * nodes], &children[i * nodes * 3])) return false;
+        Args& a = s.b;
+        a.preds = preds; a.d = d.data(); a.depth = depth.data(); a.M = M.data(); a.q = q.data(); a.edge_len = edge_len.data();
+        a.part = part.data(); a.parent = parent.data(); a.children = children.data(); a.move = nullptr; a.rowh = nullptr;
+        a.rowcase = nullptr; a.steps = steps.data(); a.done = done.data(); a.rebuild = rebuild.data(); a.status = status.data();
+        a.N = N; a.part_cap = 1; a.PN = (int64_t)N * (N - 1) / 2;
+        s.T = T.data(); s.spart = spart.data(); s.tin = tin.data(); s.tout = tout.data(); s.ndepth = ndepth.data();
+        s.path = path.data(); s.sdone = sdone.data(); s.cap = cap < 0 ? step_cap(N) : cap;
+        s.spart_cap = (int)(rows * G); s.epg = epg;
+        return true;
+    }
+
+    void init(int threads, int init_groups) {
+        for (size_t src = 0; src < (size_t)B; ++src)
+            for (int wg = 0; wg < init_groups; ++wg)
+                for (int tid = 0; tid < threads; ++tid) init_elems(s.b, src, wg, init_groups, tid, threads);
+    }
+
+    // number, depth, build and pairs of one step (the table the evaluation reads)
+    void table(bool rows_at_once) {
+        const int64_t rows = rows_of(N), nodes = nodes_of(N);
+        for (size_t src = 0; src < (size_t)B; ++src) {
+            number_tree(s, src);
+            for (int64_t X = 0; X < rows; ++X)
+                for (int v = 0; v < (int)nodes; ++v) depth_elem(s, src, X, v);
+            for (int64_t X = 0; X < rows; ++X) {
+                if (rows_at_once) { build_row(s.b, src, X); continue; }
+                for (int j = 0; j < N; ++j) build_elem(s.b, src, X, j);
+            }
+            if (tiled) pairs_tiled(src);
+            else
+                for (int64_t X = 0; X < rows; ++X)
+                    for (int64_t Y = 0; Y < rows; ++Y) pairs_elem(s, src, X, Y);
+        }
+    }
+
+    // the tiled bodies in the order of k_bme_pairs: a tile without an active entry writes its zeros and leaves
+    void pairs_tiled(size_t src) {
+        constexpr int threads = PAIR_TILE * PAIR_TILE;
+        const int tiles = (int)((rows_of(N) + PAIR_TILE - 1) / PAIR_TILE);
+        std::vector<PairThread> t((size_t)threads);
+        std::vector<double> lm((size_t)PAIR_TILE * PAIR_STRIDE), lw((size_t)PAIR_TILE * PAIR_STRIDE);
+        if (spr_idle(s, src)) return;
+        for (int tx = 0; tx < tiles; ++tx)
+            for (int ty = 0; ty < tiles; ++ty) {
+                bool any = false;
+                for (int tid = 0; tid < threads; ++tid) { pairs_tile_begin(s, src, tx, ty, tid, t[(size_t)tid]); any |= t[(size_t)tid].active; }
+                SumWalk walk;
+                walk.start(N);
+                int lo = 0, cnt = 0;
+                for (int ev = any ? walk.next(&lo, &cnt) : 0; ev; ev = walk.next(&lo, &cnt)) {
+                    if (ev == 2) { for (int tid = 0; tid < threads; ++tid) pairs_tile_add(t[(size_t)tid]); continue; }
+                    for (int tid = 0; tid < threads; ++tid) pairs_tile_stage(s, src, tx, ty, lo, cnt, tid, threads, lm.data(), lw.data());
+                    for (int tid = 0; tid < threads; ++tid) pairs_tile_leaf(cnt, tid, lm.data(), lw.data(), t[(size_t)tid]);
+                }
+                for (int tid = 0; tid < threads; ++tid) pairs_tile_end(s, src, tx, ty, tid, t[(size_t)tid]);
+            }
+    }
+
+    void evaluate_and_move(int threads) {
+        const int64_t rows = rows_of(N);
+        const int G = spr_eval_groups(N, s.epg);
+        std::vector<SprKey> keys((size_t)threads);
+        auto reduce = [&] {
+            for (int st = pfnj::reduce_first_step(threads); st > 0; st >>= 1)
+                for (int tid = 0; tid < threads; ++tid) spr_reduce_step(keys.data(), tid, st, threads);
+        };
+        for (size_t src = 0; src < (size_t)B; ++src) {
+            for (int64_t S = 0; S < rows; ++S)
+                for (int wg = 0; wg < G; ++wg) {
+                    for (int tid = 0; tid < threads; ++tid) keys[(size_t)tid] = spr_eval_thread(s, src, S, wg, tid, threads);
+                    reduce();
+                    spart[src * (size_t)s.spart_cap + (size_t)(S * G + wg)] = keys[0];
+                }
+            for (int tid = 0; tid < threads; ++tid) keys[(size_t)tid] = spr_move_thread_key(s, src, tid, threads);
+            reduce();
+            spr_decide(s, src, keys[0]);
+        }
+    }
+
+    bool finished() const {
+        for (size_t src = 0; src < (size_t)B; ++src)
+            if (status[src] != ST_NONFINITE && !sdone[src]) return false;
+        return true;
+    }
+
+    // q and the lengths of the final topology (one workgroup of `threads` threads over all edges)
+    void finish(int threads) {
+        const int epg = (int)root_of(N);
+        std::vector<double> lq((size_t)epg * 6);
+        for (size_t src = 0; src < (size_t)B; ++src) {
+            for (int tid = 0; tid < threads; ++tid) eval_q_thread(s.b, src, 0, epg, tid, threads, lq.data());
+            for (int e = 0; e < epg; ++e) edge_length(s.b, src, e);
+        }
+    }
+
+    void run(int threads, int init_groups, bool rows_at_once = false) {
+        init(threads, init_groups);
+        while (!finished())
+            for (int step = 0; step < ROUND_STEPS; ++step) { table(rows_at_once); evaluate_and_move(threads); }
+        finish(threads);
     }
 
     void result(size_t src, int32_t* slots, double* lengths, int32_t* steps_out, double* tree_length, uint8_t* status_out) const {

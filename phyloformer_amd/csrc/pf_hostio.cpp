@@ -689,12 +689,20 @@ bool bme_one(const float* preds, const int32_t* start, int32_t n, int32_t* slots
     return true;
 }
 
-}  // namespace
+// likewise the balanced SPR search
+bool spr_one(const float* preds, const int32_t* start, int32_t n, int32_t* slots, double* lengths, int32_t* steps, double* tree_length,
+             uint8_t* status) {
+    pfbme::SprSerial run;
+    if (!run.setup(preds, start, 1, n, (int)pfbme::root_of(n))) return false;
+    run.run(1, 1, true);
+    run.result(0, slots, lengths, steps, tree_length, status);
+    return true;
+}
 
-extern "C" {
+using refine_fn = bool (*)(const float*, const int32_t*, int32_t, int32_t*, double*, int32_t*, double*, uint8_t*);
 
-int pf_bme_nni_host(const float* preds, const int32_t* start_slots, int32_t B, int32_t N, int32_t* slots, double* lengths, int32_t* steps,
-                    double* tree_length, uint8_t* status) {
+int refine_host(refine_fn one, const float* preds, const int32_t* start_slots, int32_t B, int32_t N, int32_t* slots, double* lengths,
+                int32_t* steps, double* tree_length, uint8_t* status) {
     if (!preds || !start_slots || !slots || !lengths || !steps || !tree_length || !status || B < 1 || N < 3 || N > pfbme::MAX_N)
         return PF_EINVAL;
     const size_t PN = (size_t)N * ((size_t)N - 1) / 2, T = (size_t)pfnj::table_len(N);
@@ -704,17 +712,30 @@ int pf_bme_nni_host(const float* preds, const int32_t* start_slots, int32_t B, i
         for (int32_t b = 0; b < B; ++b)                          // refused before any work
             if (!pfbme::tree_of_joins(start_slots + (size_t)b * T, N, parent.data(), children.data())) return PF_EINVAL;
         for (int32_t b = 0; b < B; ++b)
-            if (!bme_one(preds + (size_t)b * PN, start_slots + (size_t)b * T, N, slots + (size_t)b * T, lengths + (size_t)b * T, steps + b,
-                         tree_length + b, status + b))
+            if (!one(preds + (size_t)b * PN, start_slots + (size_t)b * T, N, slots + (size_t)b * T, lengths + (size_t)b * T, steps + b,
+                     tree_length + b, status + b))
                 return PF_EINVAL;
         return PF_OK;
     } catch (...) { return PF_ENOMEM; }
 }
 
-// pf_bme_newick_n and the number of moves behind the text (bound by phyloformer_amd/hostio.py::bme_newick; not part of
-// the public header); steps may be NULL
-int64_t pf_bme_newick_steps_n(const float* preds, int32_t n, const char* const* ids, const int64_t* id_lens, int32_t clamp_negative,
-                              char* out, int64_t cap, int32_t* steps_out) {
+}  // namespace
+
+extern "C" {
+
+int pf_bme_nni_host(const float* preds, const int32_t* start_slots, int32_t B, int32_t N, int32_t* slots, double* lengths, int32_t* steps,
+                    double* tree_length, uint8_t* status) {
+    return refine_host(bme_one, preds, start_slots, B, N, slots, lengths, steps, tree_length, status);
+}
+
+int pf_bme_spr_host(const float* preds, const int32_t* start_slots, int32_t B, int32_t N, int32_t* slots, double* lengths, int32_t* steps,
+                    double* tree_length, uint8_t* status) {
+    return refine_host(spr_one, preds, start_slots, B, N, slots, lengths, steps, tree_length, status);
+}
+
+// The text of the NJ tree refined by `one`, and the number of moves behind it (steps_out may be NULL)
+static int64_t refined_newick(refine_fn one, const float* preds, int32_t n, const char* const* ids, const int64_t* id_lens,
+                              int32_t clamp_negative, char* out, int64_t cap, int32_t* steps_out) {
     if (steps_out) *steps_out = 0;
     if (!preds || n < 1 || n > pfbme::MAX_N || !ids || !id_lens || (!out && cap > 0)) return PF_EINVAL;
     for (int32_t i = 0; i < n; ++i) if (id_lens[i] < 0) return PF_EINVAL;
@@ -733,7 +754,7 @@ int64_t pf_bme_newick_steps_n(const float* preds, int32_t n, const char* const* 
             double tree_length = 0.0;
             uint8_t status = 0;
             // (a NaN in the distances can leave nj_core with a table that is none: the NJ text then, as for a flagged source)
-            if (bme_one(preds, start.data(), n, slots.data(), lengths.data(), &steps, &tree_length, &status) && status != pfbme::ST_NONFINITE) {
+            if (one(preds, start.data(), n, slots.data(), lengths.data(), &steps, &tree_length, &status) && status != pfbme::ST_NONFINITE) {
                 NjTree r;
                 r.joins.reserve(joins);
                 for (size_t s = 0; s < joins; ++s) r.joins.push_back({slots[2 * s], slots[2 * s + 1], lengths[2 * s], lengths[2 * s + 1]});
@@ -750,9 +771,27 @@ int64_t pf_bme_newick_steps_n(const float* preds, int32_t n, const char* const* 
     } catch (...) { return PF_ENOMEM; }
 }
 
+// pf_bme_newick_n and the number of moves behind the text (bound by phyloformer_amd/hostio.py::bme_newick; not part of
+// the public header)
+int64_t pf_bme_newick_steps_n(const float* preds, int32_t n, const char* const* ids, const int64_t* id_lens, int32_t clamp_negative,
+                              char* out, int64_t cap, int32_t* steps_out) {
+    return refined_newick(bme_one, preds, n, ids, id_lens, clamp_negative, out, cap, steps_out);
+}
+
 int64_t pf_bme_newick_n(const float* preds, int32_t n, const char* const* ids, const int64_t* id_lens, int32_t clamp_negative,
                         char* out, int64_t cap) {
     return pf_bme_newick_steps_n(preds, n, ids, id_lens, clamp_negative, out, cap, nullptr);
+}
+
+// the same for the balanced SPR search (pf_bme_spr_host); pf_bme_spr_newick_steps_n is bound by hostio.py::spr_newick
+int64_t pf_bme_spr_newick_steps_n(const float* preds, int32_t n, const char* const* ids, const int64_t* id_lens, int32_t clamp_negative,
+                                  char* out, int64_t cap, int32_t* steps_out) {
+    return refined_newick(spr_one, preds, n, ids, id_lens, clamp_negative, out, cap, steps_out);
+}
+
+int64_t pf_bme_spr_newick_n(const float* preds, int32_t n, const char* const* ids, const int64_t* id_lens, int32_t clamp_negative,
+                            char* out, int64_t cap) {
+    return pf_bme_spr_newick_steps_n(preds, n, ids, id_lens, clamp_negative, out, cap, nullptr);
 }
 
 }  // extern "C"

@@ -147,9 +147,9 @@ struct BlockDev {
 struct ProfSlot { int kid; hipEvent_t a, b; };
 const char* const KNAMES[] = {"embed", "rowfin", "colstats", "colfin", "main", "allreduce",
                               "mha_qkv", "mha_attn", "mha_out", "precise", "generic", "resample", "gather", "site_moments", "gather_taxa", "loo_stats",
-                              "weight_sums", "place_stats", "tile_combine"};
+                              "weight_sums", "place_stats", "tile_combine", "bme_pairs"};
 enum { K_EMBED = 0, K_ROWFIN, K_COLSTATS, K_COLFIN, K_MAIN, K_ALLREDUCE, K_MHA_QKV, K_MHA_ATTN, K_MHA_OUT, K_PRECISE, K_GENERIC,
-       K_RESAMPLE, K_GATHER, K_SITE_MOMENTS, K_GATHER_TAXA, K_LOO_STATS, K_WEIGHT_SUMS, K_PLACE_STATS, K_TILE_COMBINE, K_COUNT };
+       K_RESAMPLE, K_GATHER, K_SITE_MOMENTS, K_GATHER_TAXA, K_LOO_STATS, K_WEIGHT_SUMS, K_PLACE_STATS, K_TILE_COMBINE, K_BME_PAIRS, K_COUNT };
 
 // what the embed and head kernels (pfg's, for both float64 paths) read: C = 64 (precise) or Ep (generic)
 struct F64Ends {
@@ -249,6 +249,9 @@ struct pf_handle {
     char* d_bme = nullptr; size_t d_bme_bytes = 0;
     float* d_bme_preds = nullptr; size_t d_bme_preds_bytes = 0;
     int64_t bme_calls = 0;       // calls since the last pf_profile_reset ("bme_nni")
+    int64_t spr_calls = 0;       // likewise pf_bme_spr / pf_bme_spr_device ("bme_spr")
+    bool spr_pairs_simple = false;   // option "spr_pairs_simple": T by k_bme_pairs_simple (the baseline of tools/spr_bench.py)
+    int64_t spr_step_cap = 0;    // option "spr_step_cap": moves after which pf_bme_spr caps a source (0: 16 N)
     // weighted forwards (grow-only): the weight rows of a host call or of one chunk of derived alignments, what
     // k_weight_sums made of a call's rows ([..][4], pf_weights.hip.h), and the weight table of pf_forward_sites_weighted
     float* d_w = nullptr; size_t d_w_bytes = 0;
@@ -2052,19 +2055,21 @@ int nj_host_impl(pf_handle* h, const float* preds, int B, int N, int32_t* slots,
 
 // What both entry points refuse about (B, N), and the sources of one chunk: as many as fit "ws_limit_mb" side by side,
 // one at least - a single source's state above the limit is refused.
-int check_bme_shape(pf_handle* h, int B, int N, int* chunk) {
+int check_bme_shape(pf_handle* h, bool spr, int B, int N, int* chunk) {
+    const char* what = spr ? "balanced SPR" : "balanced NNI";
     if (B < 1) return fail(h, PF_EINVAL, "bad dimensions B=%d N=%d", B, N);
-    if (N < 3) return fail(h, PF_EINVAL, "balanced NNI needs N >= 3 sequences (got %d)", N);
-    if (N > pfbme::MAX_N) return fail(h, PF_EINVAL, "balanced NNI takes at most %d sequences (got %d)", pfbme::MAX_N, N);
+    if (N < 3) return fail(h, PF_EINVAL, "%s needs N >= 3 sequences (got %d)", what, N);
+    if (N > pfbme::MAX_N) return fail(h, PF_EINVAL, "%s takes at most %d sequences (got %d)", what, pfbme::MAX_N, N);
     const int64_t PN = (int64_t)N * (N - 1) / 2;
     size_t n = 0;
     if (PN >= ((int64_t)1 << 31) || !mul_size((size_t)B, (size_t)PN, sizeof(float), &n) ||
         !mul_size((size_t)B, (size_t)pfnj::table_len(N), sizeof(double), &n))
         return fail(h, PF_EINVAL, "B=%d alignments of N=%d sequences: their %lld pairs each overflow a distance vector", B, N, (long long)PN);
-    const size_t per = pfbme::state_bytes(N);
+    const size_t per = spr ? pfbme::spr_state_bytes(N) : pfbme::state_bytes(N);
     if ((int64_t)per > h->ws_limit_bytes)
-        return fail(h, PF_EINVAL, "balanced NNI of N=%d sequences needs %zu bytes of state per source (its table of 4N-6 subtrees), "
-                                  "above the workspace limit of %lld bytes (option ws_limit_mb)", N, per, (long long)h->ws_limit_bytes);
+        return fail(h, PF_EINVAL, "%s of N=%d sequences needs %zu bytes of state per source (its table of 4N-6 subtrees%s), "
+                                  "above the workspace limit of %lld bytes (option ws_limit_mb)", what, N, per,
+                    spr ? " and their pair table" : "", (long long)h->ws_limit_bytes);
     *chunk = (int)std::min<size_t>(std::min(B, pfbme::BME_MAX_Z), (size_t)h->ws_limit_bytes / per);
     return PF_OK;
 }
@@ -2134,12 +2139,64 @@ int bme_chunk(pf_handle* h, const float* d_preds, const int32_t* start, int nb, 
     return PF_OK;
 }
 
-// preds / start on the host (device = false) or on the device; the results likewise
-int bme_impl(pf_handle* h, bool device, const float* preds, const int32_t* start, int B, int N, int32_t* slots, double* lengths,
+// The balanced SPR search of nb <= chunk sources (pf_bme_spr, pf_bme_spr_device): as bme_chunk,
+// but a step forms its whole table on the device, so between two rounds the host reads the flags only.
+int spr_chunk(pf_handle* h, const float* d_preds, const int32_t* start, int nb, int N, int32_t* slots, double* lengths,
+              int32_t* steps, double* tree_length, uint8_t* status) {
+    const size_t b = (size_t)nb, T = (size_t)pfnj::table_len(N), nodes = (size_t)pfbme::nodes_of(N), root = (size_t)pfbme::root_of(N);
+    int rc = ensure_buffer(h, &h->d_bme, &h->d_bme_bytes, b * pfbme::spr_state_bytes(N));
+    if (rc) return rc;
+    h->cur = h->stream;
+    const pfbme::SprArgs s = pfbme::spr_carve(h->d_bme, d_preds, nb, N, h->spr_step_cap);
+    const pfbme::Args& a = s.b;
+    std::vector<int32_t> parent(b * nodes), children(b * nodes * 3), nsteps(b, 0);
+    std::vector<uint8_t> sdone(b, 0), st(b, 0);
+    std::vector<double> edge_len(b * root);
+    for (size_t i = 0; i < b; ++i)
+        pfbme::tree_of_joins(start + i * T, N, &parent[i * nodes], &children[i * nodes * 3]);       // (checked by the caller)
+    auto up = [&](void* dst, const void* src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream); };
+    auto down = [&](void* dst, const void* src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream); };
+    HIPCHK(h, up(a.parent, parent.data(), parent.size() * sizeof(int32_t)));
+    HIPCHK(h, up(a.children, children.data(), children.size() * sizeof(int32_t)));
+    HIPCHK(h, hipMemsetAsync(a.steps, 0, b * sizeof(int32_t), h->stream));
+    HIPCHK(h, hipMemsetAsync(a.done, 0, b, h->stream));
+    HIPCHK(h, hipMemsetAsync(a.rebuild, 1, b, h->stream));
+    HIPCHK(h, hipMemsetAsync(a.status, 0, b, h->stream));
+    HIPCHK(h, hipMemsetAsync(s.sdone, 0, b, h->stream));
+    // (a flagged source's lengths are never written: not uninitialised either)
+    HIPCHK(h, hipMemsetAsync(a.edge_len, 0, b * root * sizeof(double), h->stream));
+    hipError_t e = pfbme::launch_init(h->stream, a, nb);
+    if (e != hipSuccess) return fail(h, PF_EHIP, "k_bme_init launch failed: %s", hipGetErrorString(e));
+    for (bool all = false; !all;) {
+        hipEvent_t ev[2] = {};                          // option "profile": the pair table of the round's first step
+        if (h->profile && !h->profile_main_only) { ev[0] = get_event(h); ev[1] = get_event(h); }
+        e = pfbme::launch_spr_round(h->stream, s, nb, h->spr_pairs_simple, ev[0] ? ev : nullptr);
+        if (ev[0]) h->pending.push_back({K_BME_PAIRS, ev[0], ev[1]});
+        if (e != hipSuccess) return fail(h, PF_EHIP, "k_bme_* launch failed: %s", hipGetErrorString(e));
+        HIPCHK(h, down(sdone.data(), s.sdone, b));
+        HIPCHK(h, down(st.data(), a.status, b));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        all = true;
+        for (size_t i = 0; i < b; ++i) all = all && (sdone[i] || st[i] == pfbme::ST_NONFINITE);
+    }
+    if ((e = pfbme::launch_spr_finish(h->stream, s, nb)) != hipSuccess) return fail(h, PF_EHIP, "k_bme_eval / k_bme_lengths launch failed: %s", hipGetErrorString(e));
+    HIPCHK(h, down(edge_len.data(), a.edge_len, edge_len.size() * sizeof(double)));
+    HIPCHK(h, down(nsteps.data(), a.steps, b * sizeof(int32_t)));
+    HIPCHK(h, down(children.data(), a.children, children.size() * sizeof(int32_t)));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (size_t i = 0; i < b; ++i)
+        pfbme::result_of(N, &children[i * nodes * 3], &edge_len[i * root], nsteps[i], st[i], slots + i * T, lengths + i * T, steps + i,
+                         tree_length + i, status + i);
+    return PF_OK;
+}
+
+// preds / start on the host (device = false) or on the device; the results likewise.  spr: the balanced SPR search
+// (spr_chunk) instead of balanced NNI (bme_chunk).
+int bme_impl(pf_handle* h, bool spr, bool device, const float* preds, const int32_t* start, int B, int N, int32_t* slots, double* lengths,
              int32_t* steps, double* tree_length, uint8_t* status) {
     if (!preds || !start || !slots || !lengths || !steps || !tree_length || !status) return fail(h, PF_EINVAL, "null buffer");
     int chunk = 0;
-    int rc = check_bme_shape(h, B, N, &chunk);
+    int rc = check_bme_shape(h, spr, B, N, &chunk);
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     try {
@@ -2154,7 +2211,7 @@ int bme_impl(pf_handle* h, bool device, const float* preds, const int32_t* start
         }
         const int32_t* st_in = device ? h_start.data() : start;
         if ((rc = check_bme_starts(h, st_in, B, N))) return rc;
-        ++h->bme_calls;
+        ++(spr ? h->spr_calls : h->bme_calls);
         int32_t* o_slots = device ? h_slots.data() : slots;
         double* o_len = device ? h_len.data() : lengths;
         int32_t* o_steps = device ? h_steps.data() : steps;
@@ -2168,8 +2225,8 @@ int bme_impl(pf_handle* h, bool device, const float* preds, const int32_t* start
                 HIPCHK(h, hipMemcpyAsync(h->d_bme_preds, d_preds, (size_t)nb * PN * sizeof(float), hipMemcpyHostToDevice, h->stream));
                 d_preds = h->d_bme_preds;
             }
-            if ((rc = bme_chunk(h, d_preds, st_in + (size_t)b0 * T, nb, N, o_slots + (size_t)b0 * T, o_len + (size_t)b0 * T, o_steps + b0,
-                                o_tl + b0, o_st + b0)))
+            if ((rc = (spr ? spr_chunk : bme_chunk)(h, d_preds, st_in + (size_t)b0 * T, nb, N, o_slots + (size_t)b0 * T, o_len + (size_t)b0 * T,
+                                                    o_steps + b0, o_tl + b0, o_st + b0)))
                 return rc;
         }
         if (device) {
@@ -2382,6 +2439,8 @@ int pf_set_option(pf_handle_t* h, const char* key, int64_t value) {
         h->phase_prof_last = value == 2;
     }
     else if (k == "ws_limit_mb") h->ws_limit_bytes = value << 20;
+    else if (k == "spr_pairs_simple") h->spr_pairs_simple = value != 0;
+    else if (k == "spr_step_cap") h->spr_step_cap = value > 0 ? value : 0;
     else if (k == "sub_floats") h->sub_floats = value > 0 ? value : SUB_FLOATS_DEFAULT;
     else return fail(h, PF_EINVAL, "unknown option '%s'", key);
     return PF_OK;
@@ -2554,13 +2613,25 @@ int pf_nj_joins_device(pf_handle_t* h, const float* d_preds, int32_t B, int32_t 
 int pf_bme_nni(pf_handle_t* h, const float* preds, const int32_t* start_slots, int32_t B, int32_t N, int32_t* slots, double* lengths,
                int32_t* steps, double* tree_length, uint8_t* status) {
     if (!h) return PF_EINVAL;
-    return bme_impl(h, false, preds, start_slots, B, N, slots, lengths, steps, tree_length, status);
+    return bme_impl(h, false, false, preds, start_slots, B, N, slots, lengths, steps, tree_length, status);
 }
 
 int pf_bme_nni_device(pf_handle_t* h, const float* d_preds, const int32_t* d_start_slots, int32_t B, int32_t N, int32_t* d_slots,
                       double* d_lengths, int32_t* d_steps, double* d_tree_length, uint8_t* d_status) {
     if (!h) return PF_EINVAL;
-    return bme_impl(h, true, d_preds, d_start_slots, B, N, d_slots, d_lengths, d_steps, d_tree_length, d_status);
+    return bme_impl(h, false, true, d_preds, d_start_slots, B, N, d_slots, d_lengths, d_steps, d_tree_length, d_status);
+}
+
+int pf_bme_spr(pf_handle_t* h, const float* preds, const int32_t* start_slots, int32_t B, int32_t N, int32_t* slots, double* lengths,
+               int32_t* steps, double* tree_length, uint8_t* status) {
+    if (!h) return PF_EINVAL;
+    return bme_impl(h, true, false, preds, start_slots, B, N, slots, lengths, steps, tree_length, status);
+}
+
+int pf_bme_spr_device(pf_handle_t* h, const float* d_preds, const int32_t* d_start_slots, int32_t B, int32_t N, int32_t* d_slots,
+                      double* d_lengths, int32_t* d_steps, double* d_tree_length, uint8_t* d_status) {
+    if (!h) return PF_EINVAL;
+    return bme_impl(h, true, true, d_preds, d_start_slots, B, N, d_slots, d_lengths, d_steps, d_tree_length, d_status);
 }
 
 int pf_forward_device(pf_handle_t* h, const uint8_t* d_idx, int32_t B, int32_t N, int32_t L, float* d_out) {
@@ -2767,6 +2838,7 @@ int pf_profile_reset(pf_handle_t* h) {
     h->rechecked = 0;
     h->nj_calls = 0;
     h->bme_calls = 0;
+    h->spr_calls = 0;
     return PF_OK;
 }
 
@@ -2790,6 +2862,11 @@ int pf_profile_get(pf_handle_t* h, const char* kernel, int64_t* launches, double
     }
     if (std::strcmp(kernel, "bme_nni") == 0) {          // pf_bme_nni / pf_bme_nni_device calls
         if (launches) *launches = h->bme_calls;
+        if (total_ms) *total_ms = 0.0;
+        return PF_OK;
+    }
+    if (std::strcmp(kernel, "bme_spr") == 0) {          // pf_bme_spr / pf_bme_spr_device calls
+        if (launches) *launches = h->spr_calls;
         if (total_ms) *total_ms = 0.0;
         return PF_OK;
     }

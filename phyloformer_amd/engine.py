@@ -141,6 +141,13 @@ SIGNATURES = {
     "pf_bme_nni_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p]),
     "pf_bme_newick_n": (C.c_int64, [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32, C.c_char_p, C.c_int64]),
+    "pf_bme_spr": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                             C.c_void_p]),
+    "pf_bme_spr_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
+    "pf_bme_spr_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p]),
+    "pf_bme_spr_newick_n": (C.c_int64, [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32, C.c_char_p, C.c_int64]),
     "pf_forward_weighted": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "pf_forward_weighted_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "pf_forward_sites_weighted": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
@@ -161,7 +168,8 @@ CALL_TIME_SYMBOLS = frozenset({"pf_forward_site_map", "pf_forward_site_map_devic
                                "pf_padded_sites", "pf_boot_counts", "pf_compress_sites", "pf_forward_place",
                                "pf_place_stats_device", "pf_forward_tiled", "pf_tile_combine_device", "pf_tile_groups",
                                "pf_tile_bound", "pf_nj_joins", "pf_nj_joins_device", "pf_nj_format_joins_n", "pf_bme_nni",
-                               "pf_bme_nni_device", "pf_bme_nni_host", "pf_bme_newick_n"})
+                               "pf_bme_nni_device", "pf_bme_nni_host", "pf_bme_newick_n", "pf_bme_spr",
+                               "pf_bme_spr_device", "pf_bme_spr_host", "pf_bme_spr_newick_n"})
 
 _lib: Optional[C.CDLL] = None
 
@@ -556,7 +564,10 @@ class Engine:
         tree of ``bme.bme_nni`` - a local optimum of the balanced tree length - as a join table with balanced branch
         lengths, bit for bit that of ``hostio.bme_nni_host``.  ``status`` 0 = ok, 1 = a NaN or an infinity in the source
         (its results are zeros: use ``hostio.bme_newick``), 2 = stopped at the cap of ``16 N`` moves."""
-        fn = self._optional("pf_bme_nni")
+        return self._refine("pf_bme_nni", preds, start_slots)
+
+    def _refine(self, symbol: str, preds: np.ndarray, start_slots: np.ndarray):
+        fn = self._optional(symbol)
         p = np.ascontiguousarray(np.asarray(preds, dtype=np.float32))
         st = np.ascontiguousarray(np.asarray(start_slots, dtype=np.int32))
         single = p.ndim == 1
@@ -585,6 +596,20 @@ class Engine:
         ``lengths [B][T]``, ``steps int32``, ``tree_length float64``, ``status uint8 [B]``.  Synchronises the handle's
         stream once per round of steps: the results are complete on return."""
         self._check(self._optional("pf_bme_nni_device")(self._h, C.c_void_p(d_preds), C.c_void_p(d_start_slots), B, N,
+                                                        C.c_void_p(d_slots), C.c_void_p(d_lengths), C.c_void_p(d_steps),
+                                                        C.c_void_p(d_tree_length), C.c_void_p(d_status)))
+
+    # -- balanced SPR refinement -------------------------------------------------------------
+    def bme_spr(self, preds: np.ndarray, start_slots: np.ndarray):
+        """Balanced subtree pruning and regrafting on the GPU (``pf_bme_spr``): arguments and results as ``bme_nni``'s; the
+        tree is that of ``bme.bme_spr``, bit for bit that of ``hostio.bme_spr_host``.  ``status`` 1: use
+        ``hostio.spr_newick`` for that source."""
+        return self._refine("pf_bme_spr", preds, start_slots)
+
+    def bme_spr_device(self, d_preds: int, d_start_slots: int, B: int, N: int, d_slots: int, d_lengths: int, d_steps: int,
+                       d_tree_length: int, d_status: int):
+        """``pf_bme_spr_device``: ``bme_nni_device``'s arguments; the results are complete on return."""
+        self._check(self._optional("pf_bme_spr_device")(self._h, C.c_void_p(d_preds), C.c_void_p(d_start_slots), B, N,
                                                         C.c_void_p(d_slots), C.c_void_p(d_lengths), C.c_void_p(d_steps),
                                                         C.c_void_p(d_tree_length), C.c_void_p(d_status)))
 

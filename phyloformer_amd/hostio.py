@@ -23,6 +23,8 @@ _PRIVATE = {
                                     C.c_int32, C.c_int32, C.c_char_p, C.c_int64]),
     "pf_bme_newick_steps_n": (C.c_int64, [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32, C.c_char_p,
                                           C.c_int64, C.c_void_p]),
+    "pf_bme_spr_newick_steps_n": (C.c_int64, [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32, C.c_char_p,
+                                              C.c_int64, C.c_void_p]),
 }
 
 
@@ -136,6 +138,16 @@ def bme_newick(preds: np.ndarray, ids: Sequence[str], clamp_negative: bool = Tru
     """``pf_bme_newick_n``: distance vector ``[P]`` + ids → Newick text (utf-8 bytes) of the neighbour-joining tree refined
     by balanced NNIs, with balanced branch lengths (the CLI's ``--bme``) - byte-identical to ``bme.bme_newick_py``.
     ``with_steps``: ``(text, moves)``."""
+    return _refined_newick("pf_bme_newick", preds, ids, clamp_negative, with_steps)
+
+
+def spr_newick(preds: np.ndarray, ids: Sequence[str], clamp_negative: bool = True, with_steps: bool = False):
+    """``pf_bme_spr_newick_n``: as ``bme_newick``, the tree refined by balanced SPR moves (the CLI's ``--spr``) -
+    byte-identical to ``bme.spr_newick_py``."""
+    return _refined_newick("pf_bme_spr_newick", preds, ids, clamp_negative, with_steps)
+
+
+def _refined_newick(stem: str, preds: np.ndarray, ids: Sequence[str], clamp_negative: bool, with_steps: bool):
     lib = _lib()
     n = len(ids)
     p = np.ascontiguousarray(np.asarray(preds, dtype=np.float32).reshape(-1))
@@ -148,12 +160,12 @@ def bme_newick(preds: np.ndarray, ids: Sequence[str], clamp_negative: bool = Tru
     cap = int(lens.sum()) + 64 * max(n, 1) + 64
     buf = C.create_string_buffer(cap)
     steps = C.c_int32(0)
-    w = lib.pf_bme_newick_steps_n(p.ctypes.data, n, arr, lens.ctypes.data, int(clamp_negative), buf, cap, C.byref(steps))
+    w = getattr(lib, stem + "_steps_n")(p.ctypes.data, n, arr, lens.ctypes.data, int(clamp_negative), buf, cap, C.byref(steps))
     if w > cap:
         buf = C.create_string_buffer(int(w))
-        w = lib.pf_bme_newick_n(p.ctypes.data, n, arr, lens.ctypes.data, int(clamp_negative), buf, w)
+        w = getattr(lib, stem + "_n")(p.ctypes.data, n, arr, lens.ctypes.data, int(clamp_negative), buf, w)
     if w < 0:
-        raise RuntimeError(f"pf_bme_newick_n failed with status {w}")
+        raise RuntimeError(f"{stem}_n failed with status {w}")
     return (buf.raw[:w], int(steps.value)) if with_steps else buf.raw[:w]
 
 
@@ -161,6 +173,15 @@ def bme_nni_host(preds: np.ndarray, start_slots: np.ndarray):
     """``pf_bme_nni_host``: ``Engine.bme_nni`` without a device - the same bodies run serially, the same bits.
     ``float32[B, P_N]``, ``int32[B, T]`` → ``(slots, lengths, steps, tree_length, status)``.  ``ValueError`` for what
     the library refuses (``N < 3``, an invalid start table)."""
+    return _refine_host("pf_bme_nni_host", preds, start_slots)
+
+
+def bme_spr_host(preds: np.ndarray, start_slots: np.ndarray):
+    """``pf_bme_spr_host``: ``Engine.bme_spr`` without a device, as ``bme_nni_host`` is ``Engine.bme_nni``'s."""
+    return _refine_host("pf_bme_spr_host", preds, start_slots)
+
+
+def _refine_host(symbol: str, preds: np.ndarray, start_slots: np.ndarray):
     lib = load_library()
     p = np.ascontiguousarray(np.asarray(preds, dtype=np.float32))
     st = np.ascontiguousarray(np.asarray(start_slots, dtype=np.int32))
@@ -173,12 +194,12 @@ def bme_nni_host(preds: np.ndarray, start_slots: np.ndarray):
         raise ValueError(f"{p.shape[1]} distances and {st.shape[1]} slots are not those of N >= 3 sequences")
     slots, lengths = np.zeros((b, t), dtype=np.int32), np.zeros((b, t), dtype=np.float64)
     steps, tree_length, status = np.zeros(b, dtype=np.int32), np.zeros(b, dtype=np.float64), np.zeros(b, dtype=np.uint8)
-    rc = lib.pf_bme_nni_host(p.ctypes.data, st.ctypes.data, b, n, slots.ctypes.data, lengths.ctypes.data, steps.ctypes.data,
-                             tree_length.ctypes.data, status.ctypes.data)
+    rc = getattr(lib, symbol)(p.ctypes.data, st.ctypes.data, b, n, slots.ctypes.data, lengths.ctypes.data, steps.ctypes.data,
+                              tree_length.ctypes.data, status.ctypes.data)
     if rc == -1:
-        raise ValueError("pf_bme_nni_host refused its arguments (an invalid start table?)")
+        raise ValueError(f"{symbol} refused its arguments (an invalid start table?)")
     if rc < 0:
-        raise RuntimeError(f"pf_bme_nni_host failed with status {rc}")
+        raise RuntimeError(f"{symbol} failed with status {rc}")
     return slots, lengths, steps, tree_length, status
 
 

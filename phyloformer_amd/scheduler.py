@@ -154,13 +154,16 @@ class DirectoryRunner:
 
     def __init__(self, engine, out_dir: str, trees: bool = False, batch: int = 0,
                  io_threads: int = 4, native_io: bool = True, progress=None, modes: Sequence[Analysis] = (),
-                 bme: bool = False):
+                 bme: bool = False, spr: bool = False):
         if bme and not trees:
             raise ValueError("--bme refines the tree of --trees: give -t as well")
+        if spr and not trees:
+            raise ValueError("--spr refines the tree of --trees: give -t as well")
         self.engines = list(engine) if isinstance(engine, (list, tuple)) else [engine]
         self.out_dir = out_dir
         self.trees = trees
         self.bme = bme                # with --trees: <stem>.bme.nwk, the NJ tree refined by balanced NNIs, as well
+        self.spr = spr                # with --trees: <stem>.spr.nwk, the NJ tree refined by balanced SPR moves, as well
         self.batch = batch            # 0 = auto per shape
         self.io_threads = max(1, io_threads)
         self.native_io = native_io
@@ -169,6 +172,8 @@ class DirectoryRunner:
                       "write_wait_s": 0.0, "shapes": {}, "gpu_streams": len(self.engines)}
         if bme:
             self.stats.update({"bme": 0, "bme_steps": 0, "bme_device": 0, "bme_device_s": 0.0})
+        if spr:
+            self.stats.update({"spr": 0, "spr_steps": 0, "spr_device": 0, "spr_device_s": 0.0})
         self.modes = list(modes)
         for m in self.modes:
             m.bind(self.modes)
@@ -211,46 +216,54 @@ class DirectoryRunner:
         from .hostio import newick_of_joins_py
         return newick_of_joins_py(slots, lengths, ids)
 
-    def bme_tree(self, vec: np.ndarray, ids: List[str]):
-        """``(text, moves)`` of the balanced-NNI refinement of the neighbour-joining tree of a distance vector (``--bme``),
-        from the same side as ``nj``."""
-        if self.native_io:
-            from .hostio import bme_newick
-            return bme_newick(vec, ids, with_steps=True)
-        from .bme import bme_tree_py
-        return bme_tree_py(vec, ids)
+    # the two refinements of the NJ tree, --bme and --spr: (the library's text, bme.py's text, Engine's search, the
+    # constant of bme.py from which the search runs on the GPU thread)
+    REFINEMENTS = {"bme": ("bme_newick", "bme_tree_py", "bme_nni", "BME_DEVICE_MIN"),
+                   "spr": ("spr_newick", "spr_tree_py", "bme_spr", "SPR_DEVICE_MIN")}
 
-    def _bme_device(self, engine, n: int, preds: np.ndarray):
-        """On the GPU thread, for a launch of files with at least ``bme.BME_DEVICE_MIN`` sequences: every file's NJ joins
-        and their refinement on the device; ``(slots, lengths, moves)`` per file, None for a file with a non-finite
-        distance (it keeps the host's path) - or None for the launch."""
+    def bme_tree(self, vec: np.ndarray, ids: List[str], kind: str = "bme"):
+        """``(text, moves)`` of the balanced-NNI (``--bme``) or balanced-SPR (``kind`` "spr", ``--spr``) refinement of the
+        neighbour-joining tree of a distance vector, from the same side as ``nj``."""
+        native, python, _search, _minimum = self.REFINEMENTS[kind]
+        if self.native_io:
+            from . import hostio
+            return getattr(hostio, native)(vec, ids, with_steps=True)
         from . import bme
-        if bme.BME_DEVICE_MIN is None or n < max(3, bme.BME_DEVICE_MIN):
+        return getattr(bme, python)(vec, ids)
+
+    def _bme_device(self, engine, n: int, preds: np.ndarray, kind: str = "bme"):
+        """On the GPU thread, for a launch of files with at least ``bme.BME_DEVICE_MIN`` (``bme.SPR_DEVICE_MIN``) sequences:
+        every file's NJ joins and their refinement on the device; ``(slots, lengths, moves)`` per file, None for a file
+        with a non-finite distance (it keeps the host's path) - or None for the launch."""
+        from . import bme
+        _native, _python, search, minimum = self.REFINEMENTS[kind]
+        minimum = getattr(bme, minimum)
+        if minimum is None or n < max(3, minimum):
             return None
         t0 = time.perf_counter()
         start, _lengths, nonfinite = engine.nj_joins(preds)
         # (a flagged source's joins are unspecified: any valid start table stands in, its result is not used)
         start = np.where(np.asarray(nonfinite, dtype=bool)[:, None], bme.caterpillar_slots(n)[None, :], start)
-        slots, lengths, steps, _length, status = engine.bme_nni(preds, start)
+        slots, lengths, steps, _length, status = getattr(engine, search)(preds, start)
         tables = [None if bad or st == bme.NONFINITE else (s, l, int(k))
                   for s, l, k, st, bad in zip(slots, lengths, steps, status, nonfinite)]
-        self.book(bme_device=sum(t is not None for t in tables), bme_device_s=time.perf_counter() - t0)
+        self.book(**{f"{kind}_device": sum(t is not None for t in tables), f"{kind}_device_s": time.perf_counter() - t0})
         return tables
 
-    def _write_bme(self, group: list, preds: np.ndarray, tables):
-        """``<stem>.bme.nwk`` of some files of a launch, on a writer thread: formatted from the device's table where there
-        is one, refined on the host where not."""
+    def _write_bme(self, group: list, preds: np.ndarray, tables, kind: str = "bme"):
+        """``<stem>.bme.nwk`` (``<stem>.spr.nwk``) of some files of a launch, on a writer thread: formatted from the
+        device's table where there is one, refined on the host where not."""
         moves = 0
         for k, (e, pred) in enumerate(zip(group, preds)):
             ids = e.ids()
             table = tables[k] if tables is not None else None
             if table is None:
-                text, steps = self.bme_tree(pred, ids)
+                text, steps = self.bme_tree(pred, ids, kind)
             else:
                 text, steps = self.newick_of_joins(table[0], table[1], ids), table[2]
-            self.put(e.path, "bme.nwk", text)
+            self.put(e.path, f"{kind}.nwk", text)
             moves += steps
-        self.book(bme=len(group), bme_steps=moves)
+        self.book(**{kind: len(group), f"{kind}_steps": moves})
 
     def book(self, **amounts):
         """Add to the run's stats from inside a mode's own engine call (takes the runner's lock)."""
@@ -300,10 +313,10 @@ class DirectoryRunner:
         preds, payload = mode.forward(self, engine, shape, batch) if mode else (engine.forward(batch), ())
         dt = time.perf_counter() - t0
         tree = not (mode and self.trees and mode.writes_tree(shape))      # (False: the mode writes the tree itself)
-        if self.bme:
-            tables = self._bme_device(engine, shape[0], preds)
+        for kind in [k for k, on in (("bme", self.bme), ("spr", self.spr)) if on]:
+            tables = self._bme_device(engine, shape[0], preds, kind)
             cap = self.writer_cap()
-            submit([(self._write_bme, group[k::cap], preds[k::cap], None if tables is None else tables[k::cap])
+            submit([(self._write_bme, group[k::cap], preds[k::cap], None if tables is None else tables[k::cap], kind)
                     for k in range(min(cap, len(group)))])
         with self._lock:
             self.stats["forward_s"] += dt
@@ -635,7 +648,8 @@ def summarize(stats: dict, load_s: float = 0.0) -> dict:
             if stats["forward_s"] > 0 else None,
             "replicates": stats.get("replicates", 0), "bootstrap_s": round(stats.get("bootstrap_s", 0.0), 6),
             "windows": stats.get("windows", 0), "windows_s": round(stats.get("windows_s", 0.0), 6),
-            **({k: round(stats[k], 6) for k in ("bme", "bme_steps", "bme_device", "bme_device_s")} if "bme" in stats else {})}
+            **({k: round(stats[k], 6) for k in ("bme", "bme_steps", "bme_device", "bme_device_s")} if "bme" in stats else {}),
+            **({k: round(stats[k], 6) for k in ("spr", "spr_steps", "spr_device", "spr_device_s")} if "spr" in stats else {})}
 
 
 def run_multi_device(script: str, argv: List[str], devices: Sequence[int], shard: str = "files") -> Tuple[int, List[dict]]:
