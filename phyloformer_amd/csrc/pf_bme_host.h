@@ -1,6 +1,8 @@
 // Balanced minimum-evolution NNI refinement (pf_bme_nni, pf_bme_nni_device, pf_bme_nni_host, pf_bme_newick_n; DESIGN.md
-// section 21; the balanced SPR search of section 22 follows it below and shares its tree, rows and tables): the bodies of the kernels of pf_bme.hip.h as functions of (source, workgroup, thread), the host-side tree
-// bookkeeping, and the serial driver that runs the same bodies without a device.  Plain C++, no HIP:
+// section 21; the balanced SPR search of section 22 follows it below and shares its tree, rows and tables): the bodies
+// of the kernels of pf_bme.hip.h as functions of (source, workgroup, thread), the host-side tree bookkeeping, the lists
+// of the arrays of both states (state_arrays, spr_state_arrays: sizes, device spans and host allocations all come from
+// them), and the serial drivers that run the same bodies without a device.  Plain C++, no HIP:
 // tests/native/pf_bme_main.cpp runs them on the CPU thread by thread under AddressSanitizer / UBSan; pf_bme.hip.h
 // compiles the bodies for the device too (PF_TAXA_HD).  phyloformer_amd/bme.py is the statement of the algorithm: tree,
 // rows, balanced averages, moves, rule, lengths and the order of the output table are defined there and not repeated.
@@ -52,17 +54,22 @@ constexpr int ROUND_STEPS = 32;           // steps enqueued between two looks at
 constexpr int MAX_N = 16384;              // depth is int16: 2N - 3 < 32768
 constexpr uint8_t ST_OK = 0, ST_NONFINITE = 1, ST_CAPPED = 2;
 
-// a move and its value; ordered by (v, c, k)
-struct Key { double v; int32_t c, k; };
-PF_TAXA_HD inline Key key_none() { return Key{INFINITY, INT32_MAX, INT32_MAX}; }
-PF_TAXA_HD inline bool key_less(const Key& x, const Key& y) {
-    return x.v < y.v || (x.v == y.v && (x.c < y.c || (x.c == y.c && x.k < y.k)));
-}
+constexpr int THREADS = 256;               // every workgroup of the device
+constexpr int EVAL_EDGES = 32;             // edges per workgroup of k_bme_eval: 192 sums, 64 keys
+constexpr int SPR_EVAL_EDGES = THREADS;    // target edges per workgroup of k_bme_spr_eval: one per thread
+
+// A move and its value, ordered by (v, a, b).  Balanced NNI: a = the internal edge c, b = which of its children (k).
+// Balanced SPR: a = the row of the pruned subtree S, b = the target edge.
+using pfnj::Key;
+using pfnj::key_less;
+using pfnj::key_none;
 
 PF_TAXA_HD inline int64_t nodes_of(int N) { return 2 * (int64_t)N - 2; }
 PF_TAXA_HD inline int64_t root_of(int N) { return 2 * (int64_t)N - 3; }        // the root node = the number of edges
 PF_TAXA_HD inline int64_t rows_of(int N) { return 4 * (int64_t)N - 6; }
 PF_TAXA_HD inline int64_t step_cap(int N) { return 16 * (int64_t)N; }
+// workgroups of an evaluation of `epg` edges each
+PF_TAXA_HD inline int eval_groups(int N, int epg) { return (int)((root_of(N) + epg - 1) / epg); }
 
 // what the move body decides and the update bodies read
 struct Move { int32_t ok, c, p, s, x, y, arow; };
@@ -89,6 +96,20 @@ struct Args {
     int64_t PN;
 };
 
+// balanced SPR (the section further down): balanced NNI's arguments and its own on top
+struct SprArgs {
+    Args b;                 // d, depth, M, q, edge_len, part, parent, children, steps, done (0), rebuild, status
+    double* T;              // [B][4N-6][4N-6]
+    Key* spart;             // [B][spart_cap]: the minimum key (dL, S row, target edge) of every workgroup of the evaluation
+    int32_t* tin;           // [B][2N-2]: entry time of every node
+    int32_t* tout;          // [B][2N-2]: the last entry time in its subtree
+    int32_t* ndepth;        // [B][2N-2]: edges from the root
+    int32_t* path;          // [B][2N-2]: u_1 .. u_i, t of the move
+    uint8_t* sdone;         // [B]
+    int64_t cap;            // moves after which a source is capped (step_cap(N) but for tests)
+    int spart_cap, epg;     // epg: target edges per workgroup of the evaluation
+};
+
 PF_TAXA_HD inline bool idle(const Args& a, size_t src) { return a.status[src] == ST_NONFINITE || a.done[src]; }
 // 2^-dep (0 outside the subtree, dep < 0): exact either way - the device's ldexp is one instruction, the host's a
 // library call, so a normal result is put together from its exponent there
@@ -112,7 +133,7 @@ PF_TAXA_HD inline const double* M_row(const Args& a, size_t src, int64_t X) {
 }
 
 // Thread `tid` of workgroup `wg` of `G`: the elements e = wg * threads + tid, + G * threads, ... of d; a NaN or an
-// infinity flags the source.
+// infinity flags the source.  (The statements of pfnj::init_elems: see the note there.)
 PF_TAXA_HD inline void init_elems(const Args& a, size_t src, int wg, int G, int tid, int threads) {
     const int64_t N = a.N, NN = N * N;
     const float* preds = a.preds + src * (size_t)a.PN;
@@ -234,7 +255,7 @@ PF_TAXA_HD inline Key key_of(int N, int e, int k, const double* q) {
     if (e < N) return key_none();
     const double ab_cd = q[0] + q[1];
     const double v = k == 0 ? 0.5 * ((q[2] + q[5]) - ab_cd) : 0.5 * ((q[3] + q[4]) - ab_cd);
-    return Key{v, e, k};
+    return Key{v, e, k};                                        // (value, edge, child)
 }
 
 // The evaluation's workgroup `wg` covers edges wg * epg .. wg * epg + epg - 1.  First every thread the elements tid,
@@ -264,12 +285,6 @@ PF_TAXA_HD inline Key eval_key_thread(const Args& a, size_t src, int wg, int epg
     return best;
 }
 
-// One step of the minimum of keys[0 .. threads) in a workgroup (a barrier stands between two steps), as
-// pfnj::reduce_step; the first s is pfnj::reduce_first_step(threads).
-PF_TAXA_HD inline void reduce_step(Key* keys, int tid, int s, int threads) {
-    if (tid < s && tid + s < threads && key_less(keys[tid + s], keys[tid])) keys[tid] = keys[tid + s];
-}
-
 // thread `tid` of the move's one workgroup: the minimum of the partial minima tid, tid + threads, ... of G
 PF_TAXA_HD inline Key move_thread_key(const Args& a, size_t src, int G, int tid, int threads) {
     Key best = key_none();
@@ -288,15 +303,15 @@ PF_TAXA_HD inline Move move_decide(const Args& a, size_t src, Key best) {
     const int64_t nodes = nodes_of(a.N), root = root_of(a.N);
     if (!(best.v < THRESHOLD)) { a.done[src] = 1; a.move[src] = m; return m; }
     if (a.steps[src] >= step_cap(a.N)) { a.status[src] = ST_CAPPED; a.done[src] = 1; a.move[src] = m; return m; }
-    if (best.c < a.N || best.c >= root || best.k < 0 || best.k > 1) {       // never with finite input
+    if (best.a < a.N || best.a >= root || best.b < 0 || best.b > 1) {       // (edge, child); never with finite input
         a.status[src] = ST_NONFINITE; a.move[src] = m; return m;
     }
     int32_t* parent = a.parent + (int64_t)src * nodes;
     int32_t* children = a.children + (int64_t)src * nodes * 3;
-    const Quartet t = quartet_of(a, src, best.c);
-    m.ok = 1; m.c = best.c; m.p = t.p; m.s = t.s; m.arow = t.arow;
-    m.x = best.k == 0 ? t.c1 : t.c2;
-    m.y = best.k == 0 ? t.c2 : t.c1;
+    const Quartet t = quartet_of(a, src, best.a);
+    m.ok = 1; m.c = best.a; m.p = t.p; m.s = t.s; m.arow = t.arow;
+    m.x = best.b == 0 ? t.c1 : t.c2;
+    m.y = best.b == 0 ? t.c2 : t.c1;
     swap_blocks(parent, children, root, m.c, m.p, m.s, m.x, m.y);
     a.steps[src] += 1;
     a.move[src] = m;
@@ -525,38 +540,143 @@ inline void result_of(int N, const int32_t* children, const double* edge_len, in
     *tree_length = tree_length_of(edge_len, N);
 }
 
-// The state of B sources on the host, exactly sized, and the serial run of the bodies in the order the launches of
-// pf_bme.hip.h give them: workgroups of `threads` threads, `epg` edges per workgroup of the evaluation.
-struct Serial {
-    int B, N;
-    std::vector<double> d, M, q, edge_len;
-    std::vector<int16_t> depth, rowh;
-    std::vector<Key> part;
-    std::vector<int32_t> parent, children, steps, fresh;
-    std::vector<Move> move;
-    std::vector<int8_t> rowcase;
-    std::vector<uint8_t> done, rebuild, status;
-    int64_t resumes = 0;          // from-scratch tables that offered a move the updated table had not
+// ---- host only: the arrays of the state, listed once (the visitors and the padding rule: pf_nj_host.h) --------------
+
+// the scalars of `a`; the arrays follow by state_arrays / spr_state_arrays
+inline Args args_of(const float* preds, int N, int part_cap) {
     Args a{};
+    a.preds = preds; a.N = N; a.part_cap = part_cap; a.PN = (int64_t)N * (N - 1) / 2;
+    return a;
+}
+
+// balanced NNI
+template <class V>
+inline void state_arrays(V& v, Args& a, size_t B) {
+    const size_t n = (size_t)a.N, nodes = (size_t)nodes_of(a.N), rows = (size_t)rows_of(a.N), root = (size_t)root_of(a.N);
+    v(a.d, B * n * n);
+    v(a.M, B * rows * n);
+    v(a.q, B * root * 6);
+    v(a.edge_len, B * root);
+    v(a.part, B * (size_t)a.part_cap);
+    v(a.move, B);
+    v(a.parent, B * nodes);
+    v(a.children, B * nodes * 3);
+    v(a.steps, B);
+    v(a.depth, B * rows * nodes);
+    v(a.rowh, B * rows);
+    v(a.rowcase, B * rows);
+    v.flags(B, {&a.done, &a.rebuild, &a.status});
+}
+
+// balanced SPR: balanced NNI's arrays that the search shares (no move, rowh, rowcase), T, its partial minima, the
+// numbering and the path
+template <class V>
+inline void spr_state_arrays(V& v, SprArgs& s, size_t B) {
+    Args& a = s.b;
+    const size_t n = (size_t)a.N, nodes = (size_t)nodes_of(a.N), rows = (size_t)rows_of(a.N), root = (size_t)root_of(a.N);
+    v(a.d, B * n * n);
+    v(a.M, B * rows * n);
+    v(a.q, B * root * 6);
+    v(a.edge_len, B * root);
+    v(s.T, B * rows * rows);
+    v(a.part, B * (size_t)a.part_cap);
+    v(s.spart, B * (size_t)s.spart_cap);
+    v(a.parent, B * nodes);
+    v(a.children, B * nodes * 3);
+    v(s.tin, B * nodes);
+    v(s.tout, B * nodes);
+    v(s.ndepth, B * nodes);
+    v(s.path, B * nodes);
+    v(a.steps, B);
+    v(a.depth, B * rows * nodes);
+    v.flags(B, {&a.done, &a.rebuild, &a.status, &s.sdone});
+}
+
+// the scalars of the search
+inline SprArgs spr_args_of(const float* preds, int N, int part_cap, int epg, int64_t cap) {
+    SprArgs s{};
+    s.b = args_of(preds, N, part_cap);
+    s.cap = cap; s.epg = epg;
+    s.spart_cap = (int)(rows_of(N) * eval_groups(N, epg));
+    return s;
+}
+
+// bytes of one source's state on the device, and the state of B sources carved from `ws` (8-byte aligned, B times
+// those bytes): array after array, each [B][its share], so that a source's rows are contiguous
+inline size_t state_bytes(int N) {
+    Args a = args_of(nullptr, N, eval_groups(N, EVAL_EDGES));
+    pfnj::Measure m;
+    state_arrays(m, a, 1);
+    return m.bytes;
+}
+inline Args carve(char* ws, const float* preds, int B, int N) {
+    Args a = args_of(preds, N, eval_groups(N, EVAL_EDGES));
+    pfnj::Carve c{ws};
+    state_arrays(c, a, (size_t)B);
+    return a;
+}
+inline size_t spr_state_bytes(int N) {
+    SprArgs s = spr_args_of(nullptr, N, eval_groups(N, EVAL_EDGES), SPR_EVAL_EDGES, 0);
+    pfnj::Measure m;
+    spr_state_arrays(m, s, 1);
+    return m.bytes;
+}
+inline SprArgs carve_spr(char* ws, const float* preds, int B, int N, int64_t cap) {
+    SprArgs s = spr_args_of(preds, N, eval_groups(N, EVAL_EDGES), SPR_EVAL_EDGES, cap > 0 ? cap : step_cap(N));
+    pfnj::Carve c{ws};
+    spr_state_arrays(c, s, (size_t)B);
+    return s;
+}
+
+// What the two serial drivers share: the state of B sources on the host, one exactly sized allocation per array, the
+// start trees, the distances and the results.  `a` is the state of both; balanced NNI uses nothing else of `s`.
+struct SerialBase {
+    int B = 0, N = 0;
+    pfnj::Allocate mem;
+    SprArgs s{};
+    Args& a = s.b;
+
+    SerialBase() = default;
+    SerialBase(const SerialBase&) = delete;
+
+    // after the arrays: every source's tree and rebuild = 1; false: an invalid start table
+    bool start_trees(const int32_t* start_slots) {
+        const size_t nodes = (size_t)nodes_of(N);
+        std::fill(a.rebuild, a.rebuild + B, (uint8_t)1);
+        for (size_t src = 0; src < (size_t)B; ++src)
+            if (!tree_of_joins(start_slots + src * (size_t)pfnj::table_len(N), N, a.parent + src * nodes, a.children + src * nodes * 3))
+                return false;
+        return true;
+    }
+
+    void init(int threads, int init_groups) {
+        for (size_t src = 0; src < (size_t)B; ++src)
+            for (int wg = 0; wg < init_groups; ++wg)
+                for (int tid = 0; tid < threads; ++tid) init_elems(a, src, wg, init_groups, tid, threads);
+    }
+
+    void result(size_t src, int32_t* slots, double* lengths, int32_t* steps_out, double* tree_length, uint8_t* status_out) const {
+        result_of(N, a.children + src * (size_t)nodes_of(N) * 3, a.edge_len + src * (size_t)root_of(N), a.steps[src], a.status[src],
+                  slots, lengths, steps_out, tree_length, status_out);
+    }
+};
+
+// The serial run of balanced NNI's bodies in the order the launches of pf_bme.hip.h give them: workgroups of `threads`
+// threads, `epg` edges per workgroup of the evaluation.
+struct Serial : SerialBase {
+    std::vector<int32_t> fresh;
+    int64_t resumes = 0;          // from-scratch tables that offered a move the updated table had not
 
     // false: an invalid start table (status is not touched)
     bool setup(const float* preds, const int32_t* start_slots, int B_, int N_, int epg) {
         B = B_; N = N_;
-        const size_t b = (size_t)B, n = (size_t)N, nodes = (size_t)nodes_of(N), rows = (size_t)rows_of(N), root = (size_t)root_of(N);
-        const size_t G = (root + (size_t)epg - 1) / (size_t)epg;
-        d.assign(b * n * n, 0.0); M.assign(b * rows * n, 0.0); q.assign(b * root * 6, 0.0); edge_len.assign(b * root, 0.0);
-        depth.assign(b * rows * nodes, -1); rowh.assign(b * rows, 0); part.assign(b * G, key_none());
-        parent.assign(b * nodes, -1); children.assign(b * nodes * 3, -1); steps.assign(b, 0); fresh.assign(b, 0);
-        move.assign(b, Move{0, 0, 0, 0, 0, 0, 0}); rowcase.assign(b * rows, 0);
-        done.assign(b, 0); rebuild.assign(b, 1); status.assign(b, ST_OK);
-        for (size_t s = 0; s < b; ++s) {
-            if (!tree_of_joins(start_slots + s * (size_t)pfnj::table_len(N), N, &parent[s * nodes], &children[s * nodes * 3])) return false;
-            build_depth(&parent[s * nodes], &children[s * nodes * 3], N, &depth[s * rows * nodes]);
-        }
-        a.preds = preds; a.d = d.data(); a.depth = depth.data(); a.M = M.data(); a.q = q.data(); a.edge_len = edge_len.data();
-        a.part = part.data(); a.parent = parent.data(); a.children = children.data(); a.move = move.data(); a.rowh = rowh.data();
-        a.rowcase = rowcase.data(); a.steps = steps.data(); a.done = done.data(); a.rebuild = rebuild.data(); a.status = status.data();
-        a.N = N; a.part_cap = (int)G; a.PN = (int64_t)N * (N - 1) / 2;
+        a = args_of(preds, N, eval_groups(N, epg));
+        state_arrays(mem, a, (size_t)B);
+        fresh.assign((size_t)B, 0);
+        if (!start_trees(start_slots)) return false;
+        const size_t nodes = (size_t)nodes_of(N), rows = (size_t)rows_of(N);
+        for (size_t src = 0; src < (size_t)B; ++src)
+            build_depth(a.parent + src * nodes, a.children + src * nodes * 3, N, a.depth + src * rows * nodes);
         return true;
     }
 
@@ -566,13 +686,7 @@ struct Serial {
         const int G = a.part_cap;
         std::vector<Key> keys((size_t)threads);
         std::vector<double> lq((size_t)epg * 6);
-        auto reduce = [&] {
-            for (int s = pfnj::reduce_first_step(threads); s > 0; s >>= 1)
-                for (int tid = 0; tid < threads; ++tid) reduce_step(keys.data(), tid, s, threads);
-        };
-        for (size_t src = 0; src < (size_t)B; ++src)
-            for (int wg = 0; wg < init_groups; ++wg)
-                for (int tid = 0; tid < threads; ++tid) init_elems(a, src, wg, init_groups, tid, threads);
+        init(threads, init_groups);
         for (;;) {
             for (size_t src = 0; src < (size_t)B; ++src)
                 for (int64_t X = 0; X < rows; ++X) {
@@ -584,34 +698,27 @@ struct Serial {
                     for (int wg = 0; wg < G; ++wg) {
                         for (int tid = 0; tid < threads; ++tid) eval_q_thread(a, src, wg, epg, tid, threads, lq.data());
                         for (int tid = 0; tid < threads; ++tid) keys[(size_t)tid] = eval_key_thread(a, src, wg, epg, tid, threads, lq.data());
-                        reduce();
-                        part[src * (size_t)G + (size_t)wg] = keys[0];
+                        pfnj::reduce_keys_serial(keys.data(), threads);
+                        a.part[src * (size_t)G + (size_t)wg] = keys[0];
                     }
                 for (size_t src = 0; src < (size_t)B; ++src) {
                     for (int tid = 0; tid < threads; ++tid) keys[(size_t)tid] = move_thread_key(a, src, G, tid, threads);
-                    reduce();
+                    pfnj::reduce_keys_serial(keys.data(), threads);
                     const Move m = move_decide(a, src, keys[0]);
                     for (int tid = 0; tid < threads; ++tid) move_rowcase(a, src, m, tid, threads);
                 }
                 for (size_t src = 0; src < (size_t)B; ++src) {
-                    if (!move[src].ok) continue;                     // (every element returns at once)
+                    if (!a.move[src].ok) continue;                   // (every element returns at once)
                     for (int64_t X = 0; X < rows; ++X) {
-                        if (!rowcase[src * (size_t)rows + (size_t)X]) continue;
+                        if (!a.rowcase[src * (size_t)rows + (size_t)X]) continue;
                         for (int v = 0; v < (int)nodes; ++v) update_elem(a, src, X, v);
                     }
                 }
             }
-            if (between_rounds(B, N, parent.data(), children.data(), steps.data(), done.data(), status.data(), rebuild.data(),
-                               fresh.data(), depth.data(), &resumes))
-                break;
+            if (between_rounds(B, N, a.parent, a.children, a.steps, a.done, a.status, a.rebuild, fresh.data(), a.depth, &resumes)) break;
         }
         for (size_t src = 0; src < (size_t)B; ++src)
             for (int e = 0; e < (int)root; ++e) edge_length(a, src, e);
-    }
-
-    void result(size_t src, int32_t* slots, double* lengths, int32_t* steps_out, double* tree_length, uint8_t* status_out) const {
-        result_of(N, &children[src * (size_t)nodes_of(N) * 3], &edge_len[src * (size_t)root_of(N)], steps[src], status[src], slots,
-                  lengths, steps_out, tree_length, status_out);
     }
 };
 
@@ -634,30 +741,7 @@ struct Serial {
 // tree_length exactly as bme.py::Table does.  Args::done stays 0 throughout (it would idle that evaluation); the
 // search's own flag is `sdone`.
 
-struct SprKey { double v; int32_t s, e; };            // ordered by (v, s, e)
-PF_TAXA_HD inline SprKey spr_key_none() { return SprKey{INFINITY, INT32_MAX, INT32_MAX}; }
-PF_TAXA_HD inline bool spr_key_less(const SprKey& x, const SprKey& y) {
-    return x.v < y.v || (x.v == y.v && (x.s < y.s || (x.s == y.s && x.e < y.e)));
-}
-PF_TAXA_HD inline void spr_reduce_step(SprKey* keys, int tid, int s, int threads) {
-    if (tid < s && tid + s < threads && spr_key_less(keys[tid + s], keys[tid])) keys[tid] = keys[tid + s];
-}
-
-struct SprArgs {
-    Args b;                 // d, depth, M, q, edge_len, part, parent, children, steps, done (0), rebuild, status
-    double* T;              // [B][4N-6][4N-6]
-    SprKey* spart;          // [B][spart_cap]: the minimum of every workgroup of the evaluation
-    int32_t* tin;           // [B][2N-2]: entry time of every node
-    int32_t* tout;          // [B][2N-2]: the last entry time in its subtree
-    int32_t* ndepth;        // [B][2N-2]: edges from the root
-    int32_t* path;          // [B][2N-2]: u_1 .. u_i, t of the move
-    uint8_t* sdone;         // [B]
-    int64_t cap;            // moves after which a source is capped (step_cap(N) but for tests)
-    int spart_cap, epg;     // epg: target edges per workgroup of the evaluation
-};
-
 PF_TAXA_HD inline bool spr_idle(const SprArgs& s, size_t src) { return s.b.status[src] == ST_NONFINITE || s.sdone[src]; }
-PF_TAXA_HD inline int spr_eval_groups(int N, int epg) { return (int)((root_of(N) + epg - 1) / epg); }
 
 PF_TAXA_HD inline void number_tree(const SprArgs& s, size_t src) {
     if (spr_idle(s, src)) return;
@@ -737,7 +821,8 @@ PF_TAXA_HD inline void pairs_elem(const SprArgs& s, size_t src, int64_t X, int64
     s.T[((int64_t)src * rows + X) * rows + Y] = v;
 }
 
-// pfnj::pairwise_sum's walk as a sequence of events, so that a workgroup can take it together: 1 = the leaf (lo, cnt),
+// pfnj::pairwise_sum's walk (a second statement of the same split: see the note there) as a sequence of events, so
+// that a workgroup can take it together: 1 = the leaf (lo, cnt),
 // cnt <= 128, whose pfnj::leaf_sum is pushed; 2 = the two values on top are replaced by their sum (left + right); 0 =
 // the end, the sum is the one value left.  The events depend on n alone.
 struct SumWalk {
@@ -827,7 +912,7 @@ PF_TAXA_HD inline void forward_of(const int32_t* parent, const int32_t* children
 
 // The candidate (S row, target edge g): its key, or none when S cannot be regrafted there (g inside S, or on S's
 // attachment node, or that node a leaf).  `path`, when not NULL, receives u_1 .. u_i, t and `path_len` their number.
-PF_TAXA_HD inline SprKey spr_candidate(const SprArgs& s, size_t src, int64_t S, int32_t g, int32_t* path, int32_t* path_len) {
+PF_TAXA_HD inline Key spr_candidate(const SprArgs& s, size_t src, int64_t S, int32_t g, int32_t* path, int32_t* path_len) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
@@ -839,12 +924,12 @@ PF_TAXA_HD inline SprKey spr_candidate(const SprArgs& s, size_t src, int64_t S, 
     const int32_t e = (int32_t)(S < root ? S : S - root);
     const int32_t snode = S < root ? e : parent[e], a = S < root ? parent[e] : e;
     const int32_t pg = parent[g];
-    if (a < N || g == a || pg == a) return spr_key_none();
+    if (a < N || g == a || pg == a) return key_none();
     const int16_t* ds = depth_row(s.b, src, S);
-    if (ds[g] >= 0 || ds[pg] >= 0) return spr_key_none();
+    if (ds[g] >= 0 || ds[pg] >= 0) return key_none();
     int32_t f[2];
     forward_of(parent, children, root, a, snode, f);
-    if (f[1] < 0) return spr_key_none();
+    if (f[1] < 0) return key_none();
     int32_t u = depth_row(s.b, src, row_through(parent, root, f[0], a))[g] >= 0 ? f[0] : f[1];
     const int64_t R = row_through(parent, root, u == f[0] ? f[1] : f[0], a);
     double drs = T[R * rows + S], acc = 0.0;
@@ -863,39 +948,39 @@ PF_TAXA_HD inline SprKey spr_candidate(const SprArgs& s, size_t src, int64_t S, 
         if (path) path[i - 1] = u;
         if (last) {
             if (path) { path[i] = next; *path_len = i + 1; }
-            return SprKey{acc, (int32_t)S, g};
+            return Key{acc, (int32_t)S, g};                          // (value, S row, target edge)
         }
         const double half = 0.5 * T[X * rows + S];
         drs = 0.5 * drs + half;
         prev = u; u = next;
     }
-    return spr_key_none();                                          // never with a valid tree
+    return key_none();                                              // never with a valid tree
 }
 
 // Thread `tid` of the evaluation's workgroup (S, wg): the target edges wg * epg + tid, + threads, ... below (wg + 1) * epg
-PF_TAXA_HD inline SprKey spr_eval_thread(const SprArgs& s, size_t src, int64_t S, int wg, int tid, int threads) {
-    SprKey best = spr_key_none();
+PF_TAXA_HD inline Key spr_eval_thread(const SprArgs& s, size_t src, int64_t S, int wg, int tid, int threads) {
+    Key best = key_none();
     if (spr_idle(s, src)) return best;
     const int64_t root = root_of(s.b.N);
     for (int64_t g = (int64_t)wg * s.epg + tid; g < ((int64_t)wg + 1) * s.epg && g < root; g += threads) {
-        const SprKey k = spr_candidate(s, src, S, (int32_t)g, nullptr, nullptr);
-        if (spr_key_less(k, best)) best = k;
+        const Key k = spr_candidate(s, src, S, (int32_t)g, nullptr, nullptr);
+        if (key_less(k, best)) best = k;
     }
     return best;
 }
 
-PF_TAXA_HD inline SprKey spr_move_thread_key(const SprArgs& s, size_t src, int tid, int threads) {
-    SprKey best = spr_key_none();
+PF_TAXA_HD inline Key spr_move_thread_key(const SprArgs& s, size_t src, int tid, int threads) {
+    Key best = key_none();
     if (spr_idle(s, src)) return best;
-    const SprKey* part = s.spart + src * (size_t)s.spart_cap;
+    const Key* part = s.spart + src * (size_t)s.spart_cap;
     for (int g = tid; g < s.spart_cap; g += threads)
-        if (spr_key_less(part[g], best)) best = part[g];
+        if (key_less(part[g], best)) best = part[g];
     return best;
 }
 
 // One thread: no qualifying candidate - the source is done; the cap reached - done and capped; else the move, as
 // bme.py::spr_move's swaps along the path.
-PF_TAXA_HD inline void spr_decide(const SprArgs& s, size_t src, SprKey best) {
+PF_TAXA_HD inline void spr_decide(const SprArgs& s, size_t src, Key best) {
     if (spr_idle(s, src)) return;
     const int N = s.b.N;
     const int64_t nodes = nodes_of(N), root = root_of(N), rows = rows_of(N);
@@ -903,14 +988,14 @@ PF_TAXA_HD inline void spr_decide(const SprArgs& s, size_t src, SprKey best) {
     if (s.b.steps[src] >= s.cap) { s.b.status[src] = ST_CAPPED; s.sdone[src] = 1; s.b.rebuild[src] = 0; return; }
     int32_t* path = s.path + (int64_t)src * nodes;
     int32_t len = 0;
-    if (best.s < 0 || best.s >= rows || best.e < 0 || best.e >= root ||
-        !(spr_candidate(s, src, best.s, best.e, path, &len).v < THRESHOLD)) {            // never with finite input
+    if (best.a < 0 || best.a >= rows || best.b < 0 || best.b >= root ||               // (S row, target edge)
+        !(spr_candidate(s, src, best.a, best.b, path, &len).v < THRESHOLD)) {            // never with finite input
         s.b.status[src] = ST_NONFINITE; s.b.rebuild[src] = 0; return;
     }
     int32_t* parent = s.b.parent + (int64_t)src * nodes;
     int32_t* children = s.b.children + (int64_t)src * nodes * 3;
-    const bool below = best.s < root;
-    const int32_t e = (int32_t)(below ? best.s : best.s - root);
+    const bool below = best.a < root;
+    const int32_t e = (int32_t)(below ? best.a : best.a - root);
     for (int32_t j = 0; j + 1 < len; ++j) {
         const int32_t u = path[j], next = path[j + 1], v = below ? parent[e] : e;
         if (parent[u] == v) {               // down: S stands beside edge u as s or as A, X_j is a child of u
@@ -930,46 +1015,28 @@ PF_TAXA_HD inline void spr_decide(const SprArgs& s, size_t src, SprKey best) {
     s.b.steps[src] += 1;
 }
 
-// The state of B sources on the host, exactly sized, and the serial run of the bodies in the order the launches of
-// pf_bme.hip.h give them.
-struct SprSerial {
-    int B, N;
-    std::vector<double> d, M, q, edge_len, T;
-    std::vector<int16_t> depth;
-    std::vector<Key> part;
-    std::vector<SprKey> spart;
-    std::vector<int32_t> parent, children, steps, tin, tout, ndepth, path;
-    std::vector<uint8_t> done, rebuild, status, sdone;
+// an array of the state under its name, as a driver reads it
+template <class T>
+struct ArrayView {
+    T* p = nullptr;
+    T& operator[](size_t i) const { return p[i]; }
+    T* data() const { return p; }
+};
+
+// The serial run of the search's bodies in the order the launches of pf_bme.hip.h give them.
+struct SprSerial : SerialBase {
     bool tiled = false;       // T by pairs_tile_* instead of pairs_elem: the same bits
-    SprArgs s{};
+    // what tests/native/pf_spr_main.cpp compares and writes step by step
+    ArrayView<int32_t> parent, children, steps;
+    ArrayView<int16_t> depth;
+    ArrayView<double> T;
 
     bool setup(const float* preds, const int32_t* start_slots, int B_, int N_, int epg, int64_t cap = -1) {
         B = B_; N = N_;
-        const size_t b = (size_t)B, n = (size_t)N, nodes = (size_t)nodes_of(N), rows = (size_t)rows_of(N), root = (size_t)root_of(N);
-        const size_t G = (size_t)spr_eval_groups(N, epg);
-        d.assign(b * n * n, 0.0); M.assign(b * rows * n, 0.0); q.assign(b * root * 6, 0.0); edge_len.assign(b * root, 0.0);
-        T.assign(b * rows * rows, 0.0); depth.assign(b * rows * nodes, -1); part.assign(b, key_none());
-        spart.assign(b * rows * G, spr_key_none());
-        parent.assign(b * nodes, -1); children.assign(b * nodes * 3, -1); steps.assign(b, 0);
-        tin.assign(b * nodes, 0); tout.assign(b * nodes, 0); ndepth.assign(b * nodes, 0); path.assign(b * nodes, 0);
-        done.assign(b, 0); rebuild.assign(b, 1); status.assign(b, ST_OK); sdone.assign(b, 0);
-        for (size_t i = 0; i < b; ++i)
-            if (!tree_of_joins(start_slots + i * (size_t)pfnj::table_len(N), N, &parent[i * nodes], &children[i * nodes * 3])) return false;
-        Args& a = s.b;
-        a.preds = preds; a.d = d.data(); a.depth = depth.data(); a.M = M.data(); a.q = q.data(); a.edge_len = edge_len.data();
-        a.part = part.data(); a.parent = parent.data(); a.children = children.data(); a.move = nullptr; a.rowh = nullptr;
-        a.rowcase = nullptr; a.steps = steps.data(); a.done = done.data(); a.rebuild = rebuild.data(); a.status = status.data();
-        a.N = N; a.part_cap = 1; a.PN = (int64_t)N * (N - 1) / 2;
-        s.T = T.data(); s.spart = spart.data(); s.tin = tin.data(); s.tout = tout.data(); s.ndepth = ndepth.data();
-        s.path = path.data(); s.sdone = sdone.data(); s.cap = cap < 0 ? step_cap(N) : cap;
-        s.spart_cap = (int)(rows * G); s.epg = epg;
-        return true;
-    }
-
-    void init(int threads, int init_groups) {
-        for (size_t src = 0; src < (size_t)B; ++src)
-            for (int wg = 0; wg < init_groups; ++wg)
-                for (int tid = 0; tid < threads; ++tid) init_elems(s.b, src, wg, init_groups, tid, threads);
+        s = spr_args_of(preds, N, 1, epg, cap < 0 ? step_cap(N) : cap);        // (finish: one workgroup, its minimum unused)
+        spr_state_arrays(mem, s, (size_t)B);
+        parent.p = a.parent; children.p = a.children; steps.p = a.steps; depth.p = a.depth; T.p = s.T;
+        return start_trees(start_slots);
     }
 
     // number, depth, build and pairs of one step (the table the evaluation reads)
@@ -1015,28 +1082,24 @@ struct SprSerial {
 
     void evaluate_and_move(int threads) {
         const int64_t rows = rows_of(N);
-        const int G = spr_eval_groups(N, s.epg);
-        std::vector<SprKey> keys((size_t)threads);
-        auto reduce = [&] {
-            for (int st = pfnj::reduce_first_step(threads); st > 0; st >>= 1)
-                for (int tid = 0; tid < threads; ++tid) spr_reduce_step(keys.data(), tid, st, threads);
-        };
+        const int G = eval_groups(N, s.epg);
+        std::vector<Key> keys((size_t)threads);
         for (size_t src = 0; src < (size_t)B; ++src) {
             for (int64_t S = 0; S < rows; ++S)
                 for (int wg = 0; wg < G; ++wg) {
                     for (int tid = 0; tid < threads; ++tid) keys[(size_t)tid] = spr_eval_thread(s, src, S, wg, tid, threads);
-                    reduce();
-                    spart[src * (size_t)s.spart_cap + (size_t)(S * G + wg)] = keys[0];
+                    pfnj::reduce_keys_serial(keys.data(), threads);
+                    s.spart[src * (size_t)s.spart_cap + (size_t)(S * G + wg)] = keys[0];
                 }
             for (int tid = 0; tid < threads; ++tid) keys[(size_t)tid] = spr_move_thread_key(s, src, tid, threads);
-            reduce();
+            pfnj::reduce_keys_serial(keys.data(), threads);
             spr_decide(s, src, keys[0]);
         }
     }
 
     bool finished() const {
         for (size_t src = 0; src < (size_t)B; ++src)
-            if (status[src] != ST_NONFINITE && !sdone[src]) return false;
+            if (!spr_idle(s, src)) return false;
         return true;
     }
 
@@ -1055,11 +1118,6 @@ struct SprSerial {
         while (!finished())
             for (int step = 0; step < ROUND_STEPS; ++step) { table(rows_at_once); evaluate_and_move(threads); }
         finish(threads);
-    }
-
-    void result(size_t src, int32_t* slots, double* lengths, int32_t* steps_out, double* tree_length, uint8_t* status_out) const {
-        result_of(N, &children[src * (size_t)nodes_of(N) * 3], &edge_len[src * (size_t)root_of(N)], steps[src], status[src], slots,
-                  lengths, steps_out, tree_length, status_out);
     }
 };
 

@@ -1974,21 +1974,30 @@ int tiled_impl(pf_handle* h, const uint8_t* idx, int B, int N, int L, int M, flo
 
 // ---- neighbour joining on the device (pf_nj_joins, pf_nj_joins_device; pf_nj.hip.h, pf_nj_host.h) ----
 
-// What both entry points refuse about (B, N), and the sources of one chunk: as many as fit "ws_limit_mb" side by side,
-// one at least - a single source's state above the limit is refused.
-int check_nj_shape(pf_handle* h, int B, int N, int* chunk) {
+// A tree search as its entry points' check sees it: its name, its largest N (0: none), the bytes of its state per
+// source, the sources of one launch, and what the refusal says the state holds.
+struct TreeSearch { const char* what; int max_n; size_t (*state_bytes)(int); int max_sources; const char* holds; };
+const TreeSearch NJ_SEARCH{"neighbour joining", 0, pfnj::state_bytes, pfnj::NJ_MAX_Y, "N^2 doubles"};
+const TreeSearch NNI_SEARCH{"balanced NNI", pfbme::MAX_N, pfbme::state_bytes, pfbme::BME_MAX_Z, "its table of 4N-6 subtrees"};
+const TreeSearch SPR_SEARCH{"balanced SPR", pfbme::MAX_N, pfbme::spr_state_bytes, pfbme::BME_MAX_Z,
+                            "its table of 4N-6 subtrees and their pair table"};
+
+// What the entry points of a tree search refuse about (B, N), and the sources of one chunk: as many as fit
+// "ws_limit_mb" side by side, one at least - a single source's state above the limit is refused.
+int check_tree_shape(pf_handle* h, const TreeSearch& t, int B, int N, int* chunk) {
     if (B < 1) return fail(h, PF_EINVAL, "bad dimensions B=%d N=%d", B, N);
-    if (N < 3) return fail(h, PF_EINVAL, "neighbour joining needs N >= 3 sequences (got %d)", N);
+    if (N < 3) return fail(h, PF_EINVAL, "%s needs N >= 3 sequences (got %d)", t.what, N);
+    if (t.max_n && N > t.max_n) return fail(h, PF_EINVAL, "%s takes at most %d sequences (got %d)", t.what, t.max_n, N);
     const int64_t PN = (int64_t)N * (N - 1) / 2;
     size_t n = 0;
     if (PN >= ((int64_t)1 << 31) || !mul_size((size_t)B, (size_t)PN, sizeof(float), &n) ||
         !mul_size((size_t)B, (size_t)pfnj::table_len(N), sizeof(double), &n))
         return fail(h, PF_EINVAL, "B=%d alignments of N=%d sequences: their %lld pairs each overflow a distance vector", B, N, (long long)PN);
-    const size_t per = pfnj::state_bytes(N);
+    const size_t per = t.state_bytes(N);
     if ((int64_t)per > h->ws_limit_bytes)
-        return fail(h, PF_EINVAL, "neighbour joining of N=%d sequences needs %zu bytes of state per source (N^2 doubles), above the "
-                                  "workspace limit of %lld bytes (option ws_limit_mb)", N, per, (long long)h->ws_limit_bytes);
-    *chunk = (int)std::min<size_t>(std::min(B, pfnj::NJ_MAX_Y), (size_t)h->ws_limit_bytes / per);
+        return fail(h, PF_EINVAL, "%s of N=%d sequences needs %zu bytes of state per source (%s), above the workspace limit of %lld bytes "
+                                  "(option ws_limit_mb)", t.what, N, per, t.holds, (long long)h->ws_limit_bytes);
+    *chunk = (int)std::min<size_t>(std::min(B, t.max_sources), (size_t)h->ws_limit_bytes / per);
     return PF_OK;
 }
 
@@ -2006,7 +2015,7 @@ int launch_nj_chunk(pf_handle* h, const float* d_preds, int nb, int N, int32_t* 
 int nj_device_impl(pf_handle* h, const float* d_preds, int B, int N, int32_t* d_slots, double* d_lengths, uint8_t* d_flag) {
     if (!d_preds || !d_slots || !d_lengths || !d_flag) return fail(h, PF_EINVAL, "null buffer");
     int chunk = 0;
-    int rc = check_nj_shape(h, B, N, &chunk);
+    int rc = check_tree_shape(h, NJ_SEARCH, B, N, &chunk);
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     ++h->nj_calls;
@@ -2023,7 +2032,7 @@ int nj_device_impl(pf_handle* h, const float* d_preds, int B, int N, int32_t* d_
 int nj_host_impl(pf_handle* h, const float* preds, int B, int N, int32_t* slots, double* lengths, uint8_t* flag) {
     if (!preds || !slots || !lengths || !flag) return fail(h, PF_EINVAL, "null buffer");
     int chunk = 0;
-    int rc = check_nj_shape(h, B, N, &chunk);
+    int rc = check_tree_shape(h, NJ_SEARCH, B, N, &chunk);
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     ++h->nj_calls;
@@ -2053,27 +2062,6 @@ int nj_host_impl(pf_handle* h, const float* preds, int B, int N, int32_t* slots,
 
 // ---- balanced NNI refinement on the device (pf_bme_nni, pf_bme_nni_device; pf_bme.hip.h, pf_bme_host.h) ----
 
-// What both entry points refuse about (B, N), and the sources of one chunk: as many as fit "ws_limit_mb" side by side,
-// one at least - a single source's state above the limit is refused.
-int check_bme_shape(pf_handle* h, bool spr, int B, int N, int* chunk) {
-    const char* what = spr ? "balanced SPR" : "balanced NNI";
-    if (B < 1) return fail(h, PF_EINVAL, "bad dimensions B=%d N=%d", B, N);
-    if (N < 3) return fail(h, PF_EINVAL, "%s needs N >= 3 sequences (got %d)", what, N);
-    if (N > pfbme::MAX_N) return fail(h, PF_EINVAL, "%s takes at most %d sequences (got %d)", what, pfbme::MAX_N, N);
-    const int64_t PN = (int64_t)N * (N - 1) / 2;
-    size_t n = 0;
-    if (PN >= ((int64_t)1 << 31) || !mul_size((size_t)B, (size_t)PN, sizeof(float), &n) ||
-        !mul_size((size_t)B, (size_t)pfnj::table_len(N), sizeof(double), &n))
-        return fail(h, PF_EINVAL, "B=%d alignments of N=%d sequences: their %lld pairs each overflow a distance vector", B, N, (long long)PN);
-    const size_t per = spr ? pfbme::spr_state_bytes(N) : pfbme::state_bytes(N);
-    if ((int64_t)per > h->ws_limit_bytes)
-        return fail(h, PF_EINVAL, "%s of N=%d sequences needs %zu bytes of state per source (its table of 4N-6 subtrees%s), "
-                                  "above the workspace limit of %lld bytes (option ws_limit_mb)", what, N, per,
-                    spr ? " and their pair table" : "", (long long)h->ws_limit_bytes);
-    *chunk = (int)std::min<size_t>(std::min(B, pfbme::BME_MAX_Z), (size_t)h->ws_limit_bytes / per);
-    return PF_OK;
-}
-
 // every start table is a join table (slots in [0, N), every join of two live clusters, three distinct live slots last)
 int check_bme_starts(pf_handle* h, const int32_t* start, int B, int N) {
     std::vector<int32_t> parent((size_t)pfbme::nodes_of(N)), children((size_t)pfbme::nodes_of(N) * 3);
@@ -2083,106 +2071,84 @@ int check_bme_starts(pf_handle* h, const int32_t* start, int B, int N) {
     return PF_OK;
 }
 
-// The refinement of nb <= chunk sources: distances on the device, start tables and results on the host.  Synchronises
-// h->stream once per round of ROUND_STEPS steps and once at the end.
-int bme_chunk(pf_handle* h, const float* d_preds, const int32_t* start, int nb, int N, int32_t* slots, double* lengths,
+// The refinement of nb <= chunk sources by balanced NNI or, `spr`, by balanced SPR (DESIGN.md sections 21, 22):
+// distances on the device, start tables and results on the host.  Synchronises h->stream once per round of ROUND_STEPS
+// steps and once at the end.  The two searches differ at three points: what a round launches; what comes down after it
+// (NNI: the trees too; SPR forms its whole table on the device, so the host reads the flags only, and the trees at the
+// end); and whether the host rebuilds depth between rounds (NNI).
+int bme_chunk(pf_handle* h, bool spr, const float* d_preds, const int32_t* start, int nb, int N, int32_t* slots, double* lengths,
               int32_t* steps, double* tree_length, uint8_t* status) {
     const size_t b = (size_t)nb, T = (size_t)pfnj::table_len(N), nodes = (size_t)pfbme::nodes_of(N), rows = (size_t)pfbme::rows_of(N),
                  root = (size_t)pfbme::root_of(N);
-    int rc = ensure_buffer(h, &h->d_bme, &h->d_bme_bytes, b * pfbme::state_bytes(N));
+    int rc = ensure_buffer(h, &h->d_bme, &h->d_bme_bytes, b * (spr ? pfbme::spr_state_bytes(N) : pfbme::state_bytes(N)));
     if (rc) return rc;
     h->cur = h->stream;
-    const pfbme::Args a = pfbme::carve(h->d_bme, d_preds, nb, N);
+    pfbme::SprArgs s{};                                  // (balanced NNI: s.b alone)
+    if (spr) s = pfbme::carve_spr(h->d_bme, d_preds, nb, N, h->spr_step_cap);
+    else s.b = pfbme::carve(h->d_bme, d_preds, nb, N);
+    const pfbme::Args& a = s.b;
+    uint8_t* const d_done = spr ? s.sdone : a.done;      // the flag the round's last kernel sets (Args::done stays 0 under SPR)
     std::vector<int32_t> parent(b * nodes), children(b * nodes * 3), nsteps(b, 0), fresh(b, 0);
-    std::vector<int16_t> depth(b * rows * nodes);
+    std::vector<int16_t> depth(spr ? 0 : b * rows * nodes);
     std::vector<uint8_t> done(b, 0), rebuild(b, 1), st(b, 0);
     std::vector<double> edge_len(b * root);
-    for (size_t s = 0; s < b; ++s) {
-        pfbme::tree_of_joins(start + s * T, N, &parent[s * nodes], &children[s * nodes * 3]);       // (checked by the caller)
-        pfbme::build_depth(&parent[s * nodes], &children[s * nodes * 3], N, &depth[s * rows * nodes]);
+    for (size_t i = 0; i < b; ++i) {
+        pfbme::tree_of_joins(start + i * T, N, &parent[i * nodes], &children[i * nodes * 3]);       // (checked by the caller)
+        if (!spr) pfbme::build_depth(&parent[i * nodes], &children[i * nodes * 3], N, &depth[i * rows * nodes]);
     }
     auto up = [&](void* dst, const void* src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream); };
     auto down = [&](void* dst, const void* src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream); };
     HIPCHK(h, up(a.parent, parent.data(), parent.size() * sizeof(int32_t)));
     HIPCHK(h, up(a.children, children.data(), children.size() * sizeof(int32_t)));
-    HIPCHK(h, up(a.depth, depth.data(), depth.size() * sizeof(int16_t)));
+    if (!spr) HIPCHK(h, up(a.depth, depth.data(), depth.size() * sizeof(int16_t)));
     HIPCHK(h, up(a.rebuild, rebuild.data(), b));
     HIPCHK(h, hipMemsetAsync(a.steps, 0, b * sizeof(int32_t), h->stream));
     HIPCHK(h, hipMemsetAsync(a.done, 0, b, h->stream));
     HIPCHK(h, hipMemsetAsync(a.status, 0, b, h->stream));
+    if (spr) HIPCHK(h, hipMemsetAsync(s.sdone, 0, b, h->stream));
     // (a flagged source's lengths are never written: not uninitialised either)
     HIPCHK(h, hipMemsetAsync(a.edge_len, 0, b * root * sizeof(double), h->stream));
     hipError_t e = pfbme::launch_init(h->stream, a, nb);
     if (e != hipSuccess) return fail(h, PF_EHIP, "k_bme_init launch failed: %s", hipGetErrorString(e));
     for (;;) {
-        if ((e = pfbme::launch_round(h->stream, a, nb)) != hipSuccess) return fail(h, PF_EHIP, "k_bme_* launch failed: %s", hipGetErrorString(e));
-        HIPCHK(h, down(done.data(), a.done, b));
-        HIPCHK(h, down(nsteps.data(), a.steps, b * sizeof(int32_t)));
+        if (spr) {
+            hipEvent_t ev[2] = {};                      // option "profile": the pair table of the round's first step
+            if (h->profile && !h->profile_main_only) { ev[0] = get_event(h); ev[1] = get_event(h); }
+            e = pfbme::launch_spr_round(h->stream, s, nb, h->spr_pairs_simple, ev[0] ? ev : nullptr);
+            if (ev[0]) h->pending.push_back({K_BME_PAIRS, ev[0], ev[1]});
+        } else {
+            e = pfbme::launch_round(h->stream, a, nb);
+        }
+        if (e != hipSuccess) return fail(h, PF_EHIP, "k_bme_* launch failed: %s", hipGetErrorString(e));
+        HIPCHK(h, down(done.data(), d_done, b));
         HIPCHK(h, down(st.data(), a.status, b));
-        HIPCHK(h, down(parent.data(), a.parent, parent.size() * sizeof(int32_t)));
-        HIPCHK(h, down(children.data(), a.children, children.size() * sizeof(int32_t)));
+        if (!spr) {
+            HIPCHK(h, down(nsteps.data(), a.steps, b * sizeof(int32_t)));
+            HIPCHK(h, down(parent.data(), a.parent, parent.size() * sizeof(int32_t)));
+            HIPCHK(h, down(children.data(), a.children, children.size() * sizeof(int32_t)));
+        }
         HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (spr) {
+            bool all = true;
+            for (size_t i = 0; i < b; ++i) all = all && (done[i] || st[i] == pfbme::ST_NONFINITE);
+            if (all) break;
+            continue;
+        }
         if (pfbme::between_rounds(nb, N, parent.data(), children.data(), nsteps.data(), done.data(), st.data(), rebuild.data(), fresh.data(),
                                   depth.data()))
             break;
         HIPCHK(h, up(a.done, done.data(), b));
         HIPCHK(h, up(a.rebuild, rebuild.data(), b));
-        for (size_t s = 0; s < b; ++s)
-            if (rebuild[s]) HIPCHK(h, up(a.depth + s * rows * nodes, &depth[s * rows * nodes], rows * nodes * sizeof(int16_t)));
+        for (size_t i = 0; i < b; ++i)
+            if (rebuild[i]) HIPCHK(h, up(a.depth + i * rows * nodes, &depth[i * rows * nodes], rows * nodes * sizeof(int16_t)));
     }
-    if ((e = pfbme::launch_lengths(h->stream, a, nb)) != hipSuccess) return fail(h, PF_EHIP, "k_bme_lengths launch failed: %s", hipGetErrorString(e));
+    if ((e = spr ? pfbme::launch_spr_finish(h->stream, s, nb) : pfbme::launch_lengths(h->stream, a, nb)) != hipSuccess)
+        return fail(h, PF_EHIP, "%s launch failed: %s", spr ? "k_bme_eval / k_bme_lengths" : "k_bme_lengths", hipGetErrorString(e));
     HIPCHK(h, down(edge_len.data(), a.edge_len, edge_len.size() * sizeof(double)));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (size_t s = 0; s < b; ++s)
-        pfbme::result_of(N, &children[s * nodes * 3], &edge_len[s * root], nsteps[s], st[s], slots + s * T, lengths + s * T, steps + s,
-                         tree_length + s, status + s);
-    return PF_OK;
-}
-
-// The balanced SPR search of nb <= chunk sources (pf_bme_spr, pf_bme_spr_device): as bme_chunk,
-// but a step forms its whole table on the device, so between two rounds the host reads the flags only.
-int spr_chunk(pf_handle* h, const float* d_preds, const int32_t* start, int nb, int N, int32_t* slots, double* lengths,
-              int32_t* steps, double* tree_length, uint8_t* status) {
-    const size_t b = (size_t)nb, T = (size_t)pfnj::table_len(N), nodes = (size_t)pfbme::nodes_of(N), root = (size_t)pfbme::root_of(N);
-    int rc = ensure_buffer(h, &h->d_bme, &h->d_bme_bytes, b * pfbme::spr_state_bytes(N));
-    if (rc) return rc;
-    h->cur = h->stream;
-    const pfbme::SprArgs s = pfbme::spr_carve(h->d_bme, d_preds, nb, N, h->spr_step_cap);
-    const pfbme::Args& a = s.b;
-    std::vector<int32_t> parent(b * nodes), children(b * nodes * 3), nsteps(b, 0);
-    std::vector<uint8_t> sdone(b, 0), st(b, 0);
-    std::vector<double> edge_len(b * root);
-    for (size_t i = 0; i < b; ++i)
-        pfbme::tree_of_joins(start + i * T, N, &parent[i * nodes], &children[i * nodes * 3]);       // (checked by the caller)
-    auto up = [&](void* dst, const void* src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream); };
-    auto down = [&](void* dst, const void* src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream); };
-    HIPCHK(h, up(a.parent, parent.data(), parent.size() * sizeof(int32_t)));
-    HIPCHK(h, up(a.children, children.data(), children.size() * sizeof(int32_t)));
-    HIPCHK(h, hipMemsetAsync(a.steps, 0, b * sizeof(int32_t), h->stream));
-    HIPCHK(h, hipMemsetAsync(a.done, 0, b, h->stream));
-    HIPCHK(h, hipMemsetAsync(a.rebuild, 1, b, h->stream));
-    HIPCHK(h, hipMemsetAsync(a.status, 0, b, h->stream));
-    HIPCHK(h, hipMemsetAsync(s.sdone, 0, b, h->stream));
-    // (a flagged source's lengths are never written: not uninitialised either)
-    HIPCHK(h, hipMemsetAsync(a.edge_len, 0, b * root * sizeof(double), h->stream));
-    hipError_t e = pfbme::launch_init(h->stream, a, nb);
-    if (e != hipSuccess) return fail(h, PF_EHIP, "k_bme_init launch failed: %s", hipGetErrorString(e));
-    for (bool all = false; !all;) {
-        hipEvent_t ev[2] = {};                          // option "profile": the pair table of the round's first step
-        if (h->profile && !h->profile_main_only) { ev[0] = get_event(h); ev[1] = get_event(h); }
-        e = pfbme::launch_spr_round(h->stream, s, nb, h->spr_pairs_simple, ev[0] ? ev : nullptr);
-        if (ev[0]) h->pending.push_back({K_BME_PAIRS, ev[0], ev[1]});
-        if (e != hipSuccess) return fail(h, PF_EHIP, "k_bme_* launch failed: %s", hipGetErrorString(e));
-        HIPCHK(h, down(sdone.data(), s.sdone, b));
-        HIPCHK(h, down(st.data(), a.status, b));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        all = true;
-        for (size_t i = 0; i < b; ++i) all = all && (sdone[i] || st[i] == pfbme::ST_NONFINITE);
+    if (spr) {
+        HIPCHK(h, down(nsteps.data(), a.steps, b * sizeof(int32_t)));
+        HIPCHK(h, down(children.data(), a.children, children.size() * sizeof(int32_t)));
     }
-    if ((e = pfbme::launch_spr_finish(h->stream, s, nb)) != hipSuccess) return fail(h, PF_EHIP, "k_bme_eval / k_bme_lengths launch failed: %s", hipGetErrorString(e));
-    HIPCHK(h, down(edge_len.data(), a.edge_len, edge_len.size() * sizeof(double)));
-    HIPCHK(h, down(nsteps.data(), a.steps, b * sizeof(int32_t)));
-    HIPCHK(h, down(children.data(), a.children, children.size() * sizeof(int32_t)));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     for (size_t i = 0; i < b; ++i)
         pfbme::result_of(N, &children[i * nodes * 3], &edge_len[i * root], nsteps[i], st[i], slots + i * T, lengths + i * T, steps + i,
@@ -2191,12 +2157,12 @@ int spr_chunk(pf_handle* h, const float* d_preds, const int32_t* start, int nb, 
 }
 
 // preds / start on the host (device = false) or on the device; the results likewise.  spr: the balanced SPR search
-// (spr_chunk) instead of balanced NNI (bme_chunk).
+// instead of balanced NNI.
 int bme_impl(pf_handle* h, bool spr, bool device, const float* preds, const int32_t* start, int B, int N, int32_t* slots, double* lengths,
              int32_t* steps, double* tree_length, uint8_t* status) {
     if (!preds || !start || !slots || !lengths || !steps || !tree_length || !status) return fail(h, PF_EINVAL, "null buffer");
     int chunk = 0;
-    int rc = check_bme_shape(h, spr, B, N, &chunk);
+    int rc = check_tree_shape(h, spr ? SPR_SEARCH : NNI_SEARCH, B, N, &chunk);
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     try {
@@ -2225,7 +2191,7 @@ int bme_impl(pf_handle* h, bool spr, bool device, const float* preds, const int3
                 HIPCHK(h, hipMemcpyAsync(h->d_bme_preds, d_preds, (size_t)nb * PN * sizeof(float), hipMemcpyHostToDevice, h->stream));
                 d_preds = h->d_bme_preds;
             }
-            if ((rc = (spr ? spr_chunk : bme_chunk)(h, d_preds, st_in + (size_t)b0 * T, nb, N, o_slots + (size_t)b0 * T, o_len + (size_t)b0 * T,
+            if ((rc = bme_chunk(h, spr, d_preds, st_in + (size_t)b0 * T, nb, N, o_slots + (size_t)b0 * T, o_len + (size_t)b0 * T,
                                                     o_steps + b0, o_tl + b0, o_st + b0)))
                 return rc;
         }

@@ -1,6 +1,6 @@
 // Neighbour joining on the device (pf_nj_joins, pf_nj_joins_device): float preds [B][P_N] ->
 // the join tables slots int32 / lengths double [B][2 (N - 3) + 3], bit for bit those of nj.py::nj_joins.  The bodies are
-// pf_nj_host.h's, shared with the CPU; this file is the launches.  No atomics, no cooperative launch, no copy to the
+// pf_nj_host.h's, shared with the CPU, as is the list of the state's arrays; this file is the launches.  No atomics, no cooperative launch, no copy to the
 // host and no synchronisation between joins: the host knows m = N - t for every join t and enqueues the whole sequence.
 //   k_nj_init     grid (<= INIT_GROUPS, sources): d [N][N] from preds, the first list of active slots, the flag of a
 //                 source with a NaN or an infinity (every later kernel returns at once for a flagged source)
@@ -26,7 +26,7 @@ namespace pfnj {
 
 constexpr int INIT_THREADS = 256, INIT_GROUPS = 1024;
 constexpr int ROW_THREADS = 64;
-constexpr int Q_THREADS = 256, Q_GROUPS = 256;
+constexpr int Q_THREADS = 256;
 constexpr int JOIN_THREADS = 256;
 constexpr int NJ_MAX_Y = 65535;        // sources per launch (grid y)
 
@@ -39,7 +39,7 @@ __global__ __launch_bounds__(ROW_THREADS) void k_nj_rowsum(Args a, int m, int t)
     if (row < m) row_sum(a, m, t, (size_t)blockIdx.y, row);
 }
 
-// the workgroup's minimum of keys[0 .. THREADS) into keys[0]
+// the workgroup's minimum of keys[0 .. THREADS) into keys[0] (every kernel that takes a minimum, pf_bme.hip.h's too)
 template <int THREADS>
 __device__ inline void reduce_keys(Key* keys) {
     for (int s = reduce_first_step(THREADS); s > 0; s >>= 1) {
@@ -71,23 +71,6 @@ __global__ __launch_bounds__(JOIN_THREADS) void k_nj_join(Args a, int m, int t, 
 __global__ __launch_bounds__(64) void k_nj_final(Args a, int B) {
     const int src = (int)blockIdx.x * 64 + (int)threadIdx.x;
     if (src < B) final_record(a, (size_t)src);
-}
-
-// bytes of the per-source state besides the caller's arrays: d, r, part, active
-inline size_t state_bytes(int N) {
-    return (size_t)N * N * sizeof(double) + (size_t)N * sizeof(double) + (size_t)Q_GROUPS * sizeof(Key) + 2 * (size_t)N * sizeof(int32_t);
-}
-
-// The state of B sources carved from `ws` (8-byte aligned, B * state_bytes(N) bytes).
-inline Args carve(char* ws, const float* preds, int B, int N, int32_t* slots, double* lengths, uint8_t* flag) {
-    Args a{};
-    a.preds = preds; a.slots = slots; a.lengths = lengths; a.flag = flag;
-    a.N = N; a.part_cap = Q_GROUPS; a.PN = (int64_t)N * (N - 1) / 2;
-    a.d = reinterpret_cast<double*>(ws);       ws += (size_t)B * N * N * sizeof(double);
-    a.r = reinterpret_cast<double*>(ws);       ws += (size_t)B * N * sizeof(double);
-    a.part = reinterpret_cast<Key*>(ws);       ws += (size_t)B * Q_GROUPS * sizeof(Key);
-    a.active = reinterpret_cast<int32_t*>(ws);
-    return a;
 }
 
 // Asynchronous on `s`: the whole join sequence of B <= NJ_MAX_Y sources of N >= 3 sequences.

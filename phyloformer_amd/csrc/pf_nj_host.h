@@ -13,16 +13,26 @@
 // and every later body returns at once for it (its table is unspecified).  With finite float32 input nothing here
 // overflows or produces a NaN, so the minimum of Q is the minimum of a total order on (value, a, b): any reduction order
 // gives np.argmin's first minimum in row-major order.
+//
+// Key and its minimum, and the three visitors of a state's list of arrays (Measure, Carve, Allocate), serve balanced NNI
+// and balanced SPR too (pf_bme_host.h).
 #pragma once
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
+#include <initializer_list>
+#include <memory>
+#include <vector>
+
 #include "pf_taxa_host.h"
 
 namespace pfnj {
 
-// an element of Q and where it stands; ordered by (v, a, b)
+constexpr int Q_GROUPS = 256;          // the most workgroups of the minimum of Q: the partial minima of a source
+
+// A value and where it stands; ordered by (v, a, b).  Here an element of Q at (a, b); pf_bme_host.h says at each use
+// what a and b are there.
 struct Key { double v; int32_t a, b; };
 
 PF_TAXA_HD inline Key key_none() { return Key{INFINITY, INT32_MAX, INT32_MAX}; }
@@ -49,7 +59,8 @@ struct Args {
 PF_TAXA_HD inline const int32_t* active_of(const Args& a, size_t src, int t) { return a.active + (src * 2 + (size_t)(t & 1)) * (size_t)a.N; }
 
 // Thread `tid` of workgroup `wg` of `G`: the elements e = (wg * threads + tid), + G * threads, ... of d, and the first
-// list of active slots.
+// list of active slots.  (pfbme::init_elems forms d by the same statements; one shared body compiles to other device
+// code for k_nj_init and k_bme_init, so there are two.)
 PF_TAXA_HD inline void init_elems(const Args& a, size_t src, int wg, int G, int tid, int threads) {
     const int64_t N = a.N, NN = N * N;
     const float* preds = a.preds + src * (size_t)a.PN;
@@ -94,6 +105,8 @@ constexpr int WALK_DEPTH = 32;
 
 // numpy's pairwise sum of at(0) .. at(n - 1): more than 128 elements split at n / 2 - (n / 2) % 8, recursively.  The
 // recursion is walked with an explicit stack (left before right, then their sum): the tree depends on n only.
+// (pf_bme_host.h::SumWalk states the same split as a sequence of events; the two are kept apart because the device
+// code of this one changes when it is written on top of the other.)
 template <class At>
 PF_TAXA_HD inline double pairwise_sum(At&& at, int n) {
     if (n <= 128) return leaf_sum(at, 0, n);
@@ -169,6 +182,11 @@ PF_TAXA_HD inline int reduce_first_step(int threads) {
     while (2 * s < threads) s *= 2;
     return s;
 }
+// the serial drivers' workgroup minimum: the same steps, thread by thread
+inline void reduce_keys_serial(Key* keys, int threads) {
+    for (int s = reduce_first_step(threads); s > 0; s >>= 1)
+        for (int tid = 0; tid < threads; ++tid) reduce_step(keys, tid, s, threads);
+}
 
 // thread `tid` of the join's one workgroup: the minimum of the partial minima tid, tid + threads, ... of G
 PF_TAXA_HD inline Key join_thread_key(const Args& a, size_t src, int G, int tid, int threads) {
@@ -243,6 +261,77 @@ PF_TAXA_HD inline void final_record(const Args& a, size_t src) {
     a.lengths[at] = 0.5 * ((d[i * N + j] + d[i * N + k]) - d[j * N + k]);
     a.lengths[at + 1] = 0.5 * ((d[i * N + j] + d[j * N + k]) - d[i * N + k]);
     a.lengths[at + 2] = 0.5 * ((d[i * N + k] + d[j * N + k]) - d[i * N + j]);
+}
+
+// ---- the arrays of a state, listed once ------------------------------------------------------------------------------
+// A state's list (state_arrays here, pfbme::state_arrays, pfbme::spr_state_arrays) is the one place that names its
+// arrays: it calls v(pointer, elements) for every array of B sources, and v.flags(B, {pointers}) for the one-byte flags
+// of a source, which share one span of 8 bytes per source.  Three visitors drive it.  On the device every array starts
+// a span of its own, a multiple of 8 bytes long, so every span is 8-byte aligned in an 8-byte aligned workspace.  The
+// workspace of B sources is B * Measure's figure for one source, which bounds what Carve hands out for B: an array of
+// x bytes per source takes up8(B x) <= B up8(x).
+inline size_t up8(size_t x) { return (x + 7) / 8 * 8; }
+
+// the bytes of the spans
+struct Measure {
+    size_t bytes = 0;
+    template <class T> void operator()(T*&, size_t count) { bytes += up8(count * sizeof(T)); }
+    void flags(size_t B, std::initializer_list<uint8_t**>) { bytes += 8 * B; }
+};
+
+// spans of a device workspace, one after the other from `at`
+struct Carve {
+    char* at;
+    template <class T> void operator()(T*& p, size_t count) { p = reinterpret_cast<T*>(at); at += up8(count * sizeof(T)); }
+    void flags(size_t B, std::initializer_list<uint8_t**> list) {
+        size_t i = 0;
+        for (uint8_t** p : list) *p = reinterpret_cast<uint8_t*>(at) + B * i++;
+        at += 8 * B;
+    }
+};
+
+// The host's state: one zeroed, exactly sized allocation per array (flags included), so that a sanitizer build has its
+// red zones around every one of them.
+struct Allocate {
+    std::vector<std::unique_ptr<unsigned char[]>> owned;
+    template <class T> void operator()(T*& p, size_t count) {
+        owned.emplace_back(new unsigned char[count * sizeof(T)]());
+        p = reinterpret_cast<T*>(owned.back().get());
+    }
+    void flags(size_t B, std::initializer_list<uint8_t**> list) { for (uint8_t** p : list) (*this)(*p, B); }
+};
+
+// the scalars of `a`; the state besides the caller's arrays (preds, slots, lengths, flag) follows by state_arrays
+inline Args args_of(const float* preds, int N, int part_cap, int32_t* slots, double* lengths, uint8_t* flag) {
+    Args a{};
+    a.preds = preds; a.slots = slots; a.lengths = lengths; a.flag = flag;
+    a.N = N; a.part_cap = part_cap; a.PN = (int64_t)N * (N - 1) / 2;
+    return a;
+}
+
+template <class V>
+inline void state_arrays(V& v, Args& a, size_t B) {
+    const size_t n = (size_t)a.N;
+    v(a.d, B * n * n);
+    v(a.r, B * n);
+    v(a.part, B * (size_t)a.part_cap);
+    v(a.active, B * 2 * n);
+}
+
+// bytes of one source's state on the device
+inline size_t state_bytes(int N) {
+    Args a = args_of(nullptr, N, Q_GROUPS, nullptr, nullptr, nullptr);
+    Measure m;
+    state_arrays(m, a, 1);
+    return m.bytes;
+}
+
+// the state of B sources carved from `ws` (8-byte aligned, B * state_bytes(N) bytes)
+inline Args carve(char* ws, const float* preds, int B, int N, int32_t* slots, double* lengths, uint8_t* flag) {
+    Args a = args_of(preds, N, Q_GROUPS, slots, lengths, flag);
+    Carve c{ws};
+    state_arrays(c, a, (size_t)B);
+    return a;
 }
 
 }  // namespace pfnj

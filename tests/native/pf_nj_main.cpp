@@ -18,24 +18,19 @@ int main(int argc, char** argv) {
     if (argc != 7) return 2;
     const int B = atoi(argv[1]), N = atoi(argv[2]), threads = atoi(argv[3]), groups = atoi(argv[4]);
     if (B < 1 || N < 3 || N > 4096 || threads < 1 || groups < 1) return 2;
-    const size_t PN = (size_t)N * (N - 1) / 2, T = (size_t)pfnj::table_len(N), n = (size_t)N, b = (size_t)B;
+    const size_t PN = (size_t)N * (N - 1) / 2, T = (size_t)pfnj::table_len(N), b = (size_t)B;
     std::vector<float> preds(b * PN);
     FILE* f = fopen(argv[5], "rb");
     if (!f || fread(preds.data(), sizeof(float), preds.size(), f) != preds.size()) return 2;
     fclose(f);
-    std::vector<double> d(b * n * n), r(b * n), lengths(b * T);
-    std::vector<pfnj::Key> part(b * (size_t)groups), keys((size_t)threads);
-    std::vector<int32_t> active(b * 2 * n), slots(b * T);
+    std::vector<double> lengths(b * T);
+    std::vector<int32_t> slots(b * T);
     std::vector<uint8_t> flag(b, 0);
-    pfnj::Args a{};
-    a.preds = preds.data(); a.d = d.data(); a.r = r.data(); a.part = part.data(); a.active = active.data();
-    a.slots = slots.data(); a.lengths = lengths.data(); a.flag = flag.data();
-    a.N = N; a.part_cap = groups; a.PN = (int64_t)PN;
+    std::vector<pfnj::Key> keys((size_t)threads);
+    pfnj::Args a = pfnj::args_of(preds.data(), N, groups, slots.data(), lengths.data(), flag.data());
+    pfnj::Allocate mem;                                  // d, r, part, active: one exactly sized allocation each
+    pfnj::state_arrays(mem, a, b);
 
-    auto reduce = [&] {
-        for (int s = pfnj::reduce_first_step(threads); s > 0; s >>= 1)
-            for (int tid = 0; tid < threads; ++tid) pfnj::reduce_step(keys.data(), tid, s, threads);
-    };
     const int init_groups = 2;
     for (size_t src = 0; src < b; ++src)
         for (int wg = 0; wg < init_groups; ++wg)
@@ -47,12 +42,12 @@ int main(int argc, char** argv) {
         for (size_t src = 0; src < b; ++src)
             for (int wg = 0; wg < G; ++wg) {
                 for (int tid = 0; tid < threads; ++tid) keys[(size_t)tid] = pfnj::qmin_thread(a, m, t, src, wg, G, tid, threads);
-                reduce();
-                part[src * (size_t)groups + (size_t)wg] = keys[0];
+                pfnj::reduce_keys_serial(keys.data(), threads);
+                a.part[src * (size_t)groups + (size_t)wg] = keys[0];
             }
         for (size_t src = 0; src < b; ++src) {
             for (int tid = 0; tid < threads; ++tid) keys[(size_t)tid] = pfnj::join_thread_key(a, src, G, tid, threads);
-            reduce();
+            pfnj::reduce_keys_serial(keys.data(), threads);
             const pfnj::Join j = pfnj::join_record(a, m, t, src, keys[0]);
             for (int tid = 0; tid < threads; ++tid) pfnj::join_update(a, m, t, src, j, tid, threads);
         }

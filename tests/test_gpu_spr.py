@@ -102,7 +102,7 @@ def test_a_lowered_cap_stops_the_search(engines):
 
 
 def test_chunks_under_a_small_workspace_limit(engines):
-    """``ws_limit_mb = 1``: one source of 65 sequences fits (778,216 bytes), so three run in three chunks; 137 are
+    """``ws_limit_mb = 1``: one source of 65 sequences fits (762,384 bytes), so three run in three chunks; 137 are
     refused, with the bytes in the message."""
     eng = eng_of(engines)
     n = 65
@@ -117,6 +117,36 @@ def test_chunks_under_a_small_workspace_limit(engines):
     finally:
         eng.set_option("ws_limit_mb", 24 << 10)
     assert_same(eng.bme_spr(preds, starts), want)
+
+
+def test_the_three_searches_alternate_on_one_workspace(engines):
+    """Balanced SPR, balanced NNI and - in a buffer of its own - neighbour joining carve their states from grow-only
+    buffers of one engine; SPR and NNI share one, with different layouts.  Under ``ws_limit_mb = 1``: SPR (N = 9, B = 3),
+    NNI (N = 65, B = 3: 240,944 bytes per source, so the three fit one chunk where SPR's 762,384 would make three), NJ
+    (N = 65), then the first SPR call again.  Every result has the bytes of its serial twin, the two SPR results those
+    of each other."""
+    from helpers.nj_table import table_of
+    eng = eng_of(engines)
+    small = bc.uniform_preds(9, 909, 3)
+    small_starts = np.stack([bc.caterpillar_slots(9)] * 3)
+    n = 65
+    preds = np.concatenate([bc.uniform_preds(n, 1, 2), bc.random_tree_distances(n, 3)[None, :]])
+    starts = np.stack([bme.nj_start(bme.matrix_of_preds(p, n)) for p in preds])
+    eng.set_option("ws_limit_mb", 1)
+    try:
+        first = eng.bme_spr(small, small_starts)
+        nni = eng.bme_nni(preds, starts)
+        slots, lengths, nonfinite = eng.nj_joins(preds)
+        again = eng.bme_spr(small, small_starts)
+    finally:
+        eng.set_option("ws_limit_mb", 24 << 10)
+    assert_same(first, hostio.bme_spr_host(small, small_starts))
+    assert_same(nni, hostio.bme_nni_host(preds, starts))
+    assert not nonfinite.any()
+    for b in range(3):
+        want_s, want_l = table_of(preds[b], n)
+        assert_same((slots[b], lengths[b]), (want_s, want_l))
+    assert_same(again, first)
 
 
 def test_device_arrays(engines):
