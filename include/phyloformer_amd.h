@@ -426,6 +426,41 @@ int pf_bme_spr_device(pf_handle_t* h, const float* d_preds, const int32_t* d_sta
 int pf_bme_spr_host(const float* preds, const int32_t* start_slots, int32_t B, int32_t N, int32_t* slots, double* lengths, int32_t* steps,
                     double* tree_length, uint8_t* status);
 
+/* ---- split supports of join tables: Felsenstein counts and transfer distances (additive to ABI 5) ----
+ *
+ * How far the R replicate trees of a source carry the splits of its reference tree; every tree is a join table in
+ * pf_nj_joins' layout (pf_nj_joins', pf_bme_nni's or pf_bme_spr's), T = 2 (N - 3) + 3 slots, lengths not needed.
+ * phyloformer_amd/supports.py::split_supports states the definition and DESIGN.md section 23 the device form.  Join t
+ * of a table gives the split of its cluster, taken on the side without sequence 0; k_t sequences, p_t = min(k_t, N - k_t).
+ * The transfer distance of reference split s (depth p) to a replicate with splits q_j is
+ *   delta = min(p - 1, min_j min(h_j, N - h_j)),  h_j = popcount(s xor q_j)
+ * (Lemoine et al. 2018; p - 1 is what the replicate's leaf edges give).  A replicate whose rep_flag is set contributes
+ * delta = p - 1, contains no split, and its table is never read.
+ *   ref_slots  int32 [B][T]        the reference tree of every source
+ *   rep_slots  int32 [B][R][T]     its replicate trees
+ *   rep_flag   uint8 [B][R]|NULL   != 0: the replicate has no tree (pf_nj_joins' nonfinite, status 1 of a refinement)
+ *   count      int32 [B][N - 3]    replicates with delta = 0, i.e. that contain split t: Felsenstein's count
+ *   transfer   int64 [B][N - 3]    the sum of delta over the replicates; the transfer bootstrap expectation is
+ *                                  1 - transfer / (R (p - 1))
+ *   depth      int32 [B][N - 3]    p_t
+ *   status     uint8 [B]           0 ok; 1 a table of the source is no join table (its results are zeros)
+ * Everything is an integer: the results do not depend on B, on the chunking or on the entry point.  pf_join_supports
+ * takes host arrays, validates every table that is read as pf_bme_nni validates a start table (PF_EINVAL) and is
+ * synchronous.  pf_join_supports_device takes device arrays, is asynchronous on the handle's stream and validates in
+ * the kernel: a slot outside [0, N) or a join of a dead slot never indexes memory, the source gets status 1.
+ * pf_join_supports_host runs the same kernel bodies serially without a handle or a device (validation as
+ * pf_join_supports).  Sources run side by side in chunks that fit "ws_limit_mb"; a source whose R + 1 bitset tables
+ * (about N^2 / 8 bytes each) and deltas exceed it runs in chunks of replicates.  Refused with PF_EINVAL before any
+ * device work: N < 4, N > 16384, B < 1, R < 1; NULL buffers (rep_flag may be NULL); a reference table and one replicate
+ * table above "ws_limit_mb" (the message names the bytes).  pf_profile_get("join_supports") counts the calls of the two
+ * handle entry points. */
+int pf_join_supports(pf_handle_t* h, const int32_t* ref_slots, const int32_t* rep_slots, const uint8_t* rep_flag, int32_t B, int32_t R,
+                     int32_t N, int32_t* count, int64_t* transfer, int32_t* depth, uint8_t* status);
+int pf_join_supports_device(pf_handle_t* h, const int32_t* d_ref_slots, const int32_t* d_rep_slots, const uint8_t* d_rep_flag, int32_t B,
+                            int32_t R, int32_t N, int32_t* d_count, int64_t* d_transfer, int32_t* d_depth, uint8_t* d_status);
+int pf_join_supports_host(const int32_t* ref_slots, const int32_t* rep_slots, const uint8_t* rep_flag, int32_t B, int32_t R, int32_t N,
+                          int32_t* count, int64_t* transfer, int32_t* depth, uint8_t* status);
+
 /* ---- site weights: weighted forward, pattern compression, bootstrap on distinct sites (additive to ABI 5) ----
  *
  * Nothing in the network depends on a site's position, and every reduction over sites is a plain sum (the row-attention

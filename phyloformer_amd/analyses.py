@@ -54,6 +54,8 @@ class Analysis:
     refuses: Tuple[Tuple[str, str], ...] = ()    # (other flag or SHARD_SITES, reason), in the order they are reported
     forward = None                               # forward(runner, engine, shape, batch) -> (preds, payload columns)
     follow = None                                # follow(engine, batch) -> results [B, ...]
+    extend = None                                # extend(runner, engine, shape, preds, results) -> the columns of ``jobs``:
+                                                 # further device work behind ``follow``, booked by the mode itself
     write = None                                 # write(runner, shape, entry, pred, *payload row): one file's outputs
 
     @classmethod
@@ -119,12 +121,17 @@ class Bootstrap(Analysis):
     option = {"type": int, "default": 0, "metavar": "R"}
     help = ("site-bootstrap replicates per alignment, resampled and inferred on the GPU: writes "
             "<stem>.sup.nwk, the NJ tree of the alignment's distances with the percent of replicate "
-            "trees that contain each internal branch's split; 0 (default) = off")
+            "trees that contain each internal branch's split (Felsenstein's proportion); with --tbe also "
+            "<stem>.tbe.nwk, the same tree with the transfer bootstrap expectation; with --bootstrap-refined "
+            "the trees of --bme / --spr get their supports too; 0 (default) = off")
     refuses = ((SHARD_SITES, "every replicate would need its own collectives"),)
     call = "bootstrap"
 
-    def __init__(self, replicates: int, seed: int = 0):
+    def __init__(self, replicates: int, seed: int = 0, tbe: bool = False, refined: bool = False):
         self.replicates, self.seed = int(replicates), int(seed)
+        self.tbe, self.refined = bool(tbe), bool(refined)
+        if self.tbe or self.refined:
+            self.extend = self._extend
 
     @classmethod
     def add_arguments(cls, parser):
@@ -132,15 +139,33 @@ class Bootstrap(Analysis):
         parser.add_argument("--seed", type=int, default=0,
                             help="seed of the bootstrap replicate stream (default 0): a file's supports depend on the "
                                  "weights, the alignment, R and the seed only")
+        parser.add_argument("--tbe", action="store_true",
+                            help="with --bootstrap R: also write <stem>.tbe.nwk, the tree of <stem>.sup.nwk labelled with the "
+                                 "transfer bootstrap expectation in percent (Lemoine et al. 2018): per branch and replicate, "
+                                 "how many sequences would have to move for the branch's split to appear in the replicate "
+                                 "tree, against the p - 1 of a split with p sequences on its smaller side; it does not "
+                                 "collapse on deep branches of large trees as Felsenstein's all-or-nothing count does")
+        parser.add_argument("--bootstrap-refined", action="store_true",
+                            help="with --bootstrap R and --bme and / or --spr: also write <stem>.bme.sup.nwk / "
+                                 "<stem>.spr.sup.nwk, the refined tree with the percent of replicate trees - each "
+                                 "replicate's NJ tree refined by the same search - that contain each branch's split (with "
+                                 "--tbe also <stem>.bme.tbe.nwk / <stem>.spr.tbe.nwk); R more searches per file")
 
     @classmethod
     def from_args(cls, args):
         if args.bootstrap < 0:
             raise ValueError(f"--bootstrap must be >= 0 (got {args.bootstrap})")
-        return cls(args.bootstrap, args.seed) if args.bootstrap else None
+        if args.tbe and not args.bootstrap:
+            raise ValueError("--tbe labels the tree of --bootstrap: give --bootstrap R as well")
+        if args.bootstrap_refined and not args.bootstrap:
+            raise ValueError("--bootstrap-refined counts over the replicates of --bootstrap: give --bootstrap R as well")
+        if args.bootstrap_refined and not (args.bme or args.spr):
+            raise ValueError("--bootstrap-refined supports the trees of --bme / --spr: give at least one of them as well")
+        return cls(args.bootstrap, args.seed, args.tbe, args.bootstrap_refined) if args.bootstrap else None
 
     def stats(self):
-        return {"replicates": self.replicates, "bootstrap_s": 0.0}
+        more = {"tbe": 0, "refined_supports": 0, "supports_device": 0, "supports_device_s": 0.0} if self.extend else {}
+        return {"replicates": self.replicates, "bootstrap_s": 0.0, **more}
 
     def floats(self, shape):
         return self.replicates * (shape[0] * (shape[0] - 1) // 2)
@@ -153,12 +178,116 @@ class Bootstrap(Analysis):
 
     def write(self, runner, shape, entry, pred, reps):
         """``<stem>.sup.nwk``: the NJ tree of ``pred`` with the supports of ``reps``."""
+        runner.put(entry.path, "sup.nwk", self._nj_support(runner, pred, reps, entry.ids()))
+
+    @staticmethod
+    def _nj_support(runner, pred, reps, ids):
         if runner.native_io:
             from .hostio import nj_support
-            runner.put(entry.path, "sup.nwk", nj_support(pred, reps, entry.ids(), threads=runner.writer_cap()))
-        else:
-            from .bootstrap import support_newick_py
-            runner.put(entry.path, "sup.nwk", support_newick_py(pred, reps, entry.ids()))
+            return nj_support(pred, reps, ids, threads=runner.writer_cap())
+        from .bootstrap import support_newick_py
+        return support_newick_py(pred, reps, ids)
+
+    # -- --tbe / --bootstrap-refined (supports.py, DESIGN.md section 23) -----------------------------------------------
+    def kinds(self, runner) -> List[str]:
+        """The trees that get supports: NJ (``.sup.nwk``, from the same replicate NJ tables as every other output), and
+        with ``--bootstrap-refined`` those of ``--bme`` / ``--spr``."""
+        return ["nj"] + [k for k in ("bme", "spr") if self.refined and getattr(runner, k)]
+
+    def _extend(self, runner, engine, shape, preds, reps):
+        """On the GPU thread, behind ``follow``: what of the supports runs on the device.  From ``bme.BME_DEVICE_MIN`` /
+        ``bme.SPR_DEVICE_MIN`` sequences on the NJ tables of all ``B (R + 1)`` trees of the sub-batch and their refinement
+        (``Engine.nj_joins`` + ``Engine.bme_nni`` / ``bme_spr``), from ``supports.SUPPORT_DEVICE_MIN`` on the matching
+        (``Engine.join_supports``) of every kind whose tables are the device's (NJ's: joined there for it).  Returns the
+        columns ``(reps, tables)``, ``tables[b][kind]`` = ``(slots, lengths, rep_slots, rep_flag, results or None)`` or
+        absent: that kind of that file runs on its writer thread."""
+        from . import bme, supports
+        B, R, n = len(preds), self.replicates, shape[0]
+        tables = [{} for _ in range(B)]
+
+        def reaches(minimum):
+            return n >= 4 and minimum is not None and n >= minimum
+        kinds = self.kinds(runner)
+        refine = [k for k in kinds if k != "nj" and reaches(getattr(bme, runner.REFINEMENTS[k][3]))]
+        match = reaches(supports.SUPPORT_DEVICE_MIN)
+        if not refine and not match:
+            return reps, tables
+        t0 = time.perf_counter()
+        every = np.concatenate([preds[:, None, :], reps], axis=1).reshape(B * (R + 1), -1)       # own tree first
+        nj_slots, nj_lengths, nonfinite = engine.nj_joins(every)
+        bad = np.asarray(nonfinite, dtype=bool)
+        made = {"nj": (nj_slots, nj_lengths, bad)}               # (joined once: they serve every output)
+        # (a flagged source's joins are unspecified: any valid start table stands in, its result is not used)
+        start = np.where(bad[:, None], bme.caterpillar_slots(n)[None, :], nj_slots)
+        for k in refine:
+            slots, lengths, _steps, _length, status = getattr(engine, runner.REFINEMENTS[k][2])(every, start)
+            made[k] = (slots, lengths, bad | (status == bme.NONFINITE))
+        matched = 0
+        for k, (slots, lengths, flag) in made.items():
+            slots, lengths, flag = (x.reshape(B, R + 1, *x.shape[1:]) for x in (slots, lengths, flag))
+            res = None
+            if match:
+                ref = np.where(flag[:, :1], bme.caterpillar_slots(n)[None, :], slots[:, 0])       # (its result is not used)
+                res = engine.join_supports(ref, slots[:, 1:], flag[:, 1:])
+            for b in range(B):
+                if flag[b, 0]:
+                    continue                                     # no tree of its own: the writer's plain text
+                tables[b][k] = (slots[b, 0], lengths[b, 0], slots[b, 1:], flag[b, 1:], None if res is None else tuple(x[b] for x in res[:3]))
+                matched += res is not None
+        runner.book(supports_device=matched, supports_device_s=time.perf_counter() - t0)
+        return reps, tables
+
+    def _host_tables(self, runner, kind, pred, reps, n):
+        """One file's tables of one kind on a writer thread, by the host twins: ``(slots, lengths, rep_slots, rep_flag)``,
+        or None where the file's own distances are not finite."""
+        from . import bme, hostio, supports
+        if not runner.native_io:
+            slots, lengths, rep_slots, rep_flag = supports.kind_tables(pred, reps, n, kind)
+            return None if slots is None else (slots, lengths, rep_slots, rep_flag)
+        every = np.concatenate([np.asarray(pred, dtype=np.float32).reshape(1, -1), reps])
+        slots, lengths, bad = hostio.nj_joins_host(every)
+        if kind != "nj":
+            start = np.where(bad[:, None], bme.caterpillar_slots(n)[None, :], slots)
+            slots, lengths, _steps, _length, status = getattr(hostio, runner.REFINEMENTS[kind][2] + "_host")(every, start)
+            bad = bad | (status == bme.NONFINITE)
+        return None if bad[0] else (slots[0], lengths[0], slots[1:], bad[1:])
+
+    def write_supports(self, runner, shape, rows):
+        """Some files of a sub-batch on a writer thread: per kind of tree ``<stem>[.<kind>].sup.nwk`` and, with ``--tbe``,
+        ``<stem>[.<kind>].tbe.nwk``.  Tables and results the GPU thread left are formatted; the others come from the host
+        twins first (the serial ``pf_join_supports_host``; with ``--python-io`` ``supports.py`` itself)."""
+        from . import hostio, supports
+        n, R = shape[0], self.replicates
+        for entry, pred, reps, given in rows:
+            ids = entry.ids()
+            for kind in self.kinds(runner):
+                sup, tbe = supports.SUFFIXES[kind]
+                table = None
+                if n >= 4:
+                    table = given.get(kind) or self._host_tables(runner, kind, pred, reps, n)
+                if table is None:       # no split, or no tree of the file's own distances: the kind's plain text
+                    text = self._nj_support(runner, pred, reps, ids) if kind == "nj" else runner.bme_tree(pred, ids, kind)[0]
+                    texts = (text, text)
+                else:
+                    slots, lengths, rep_slots, rep_flag = table[:4]
+                    res = table[4] if len(table) > 4 and table[4] is not None else None
+                    if res is None and runner.native_io:
+                        res = hostio.join_supports_host(slots, rep_slots, rep_flag)[:3]
+                    elif res is None:
+                        res = supports.split_supports(slots, rep_slots, n, rep_flag)
+                    texts = supports.support_texts(slots, lengths, ids, *res, R)
+                runner.put(entry.path, sup, texts[0])
+                if self.tbe:
+                    runner.put(entry.path, tbe, texts[1])
+        kinds = len(self.kinds(runner))
+        runner.book(tbe=len(rows) * kinds if self.tbe else 0, refined_supports=len(rows) * (kinds - 1))
+
+    def jobs(self, runner, shape, part, preds, reps, tables=None):
+        if tables is None:
+            return super().jobs(runner, shape, part, preds, reps)
+        rows = list(zip(part, preds, reps, tables))
+        cap = runner.writer_cap()       # (the host twins of R searches per file: spread over the writers, as _write_bme)
+        return [(self.write_supports, runner, shape, rows[k::cap]) for k in range(min(cap, len(rows)))]
 
 
 class Windows(Analysis):

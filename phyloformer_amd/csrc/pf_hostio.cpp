@@ -25,6 +25,7 @@
 
 #include "../../include/phyloformer_amd.h"
 #include "pf_bme_host.h"
+#include "pf_support_host.h"
 
 namespace {
 
@@ -853,6 +854,70 @@ int64_t pf_nj_support_n(const float* preds, const float* reps, int32_t R, int32_
         }
         if (out && (int64_t)text.size() <= cap) memcpy(out, text.data(), text.size());
         return (int64_t)text.size();
+    } catch (...) { return PF_ENOMEM; }
+}
+
+}  // extern "C"
+
+extern "C" {
+
+// The join tables of pf_nj_joins without a device (bound by phyloformer_amd/hostio.py::nj_joins_host; not part of the
+// public header): nj_core's joins of preds [B][P_N] as slots / lengths [B][2 (N - 3) + 3], on up to `threads` threads.  A
+// source with a NaN or an infinity is flagged and its table zeros.
+int pf_nj_joins_host_n(const float* preds, int32_t B, int32_t N, int32_t threads, int32_t* slots, double* lengths, uint8_t* nonfinite) {
+    if (!preds || !slots || !lengths || !nonfinite || B < 1 || N < 3) return PF_EINVAL;
+    const size_t P = (size_t)N * ((size_t)N - 1) / 2, T = (size_t)pfsup::table_len(N), J = (size_t)N - 3;
+    std::atomic<bool> failed{false};
+    try {
+        run_pool(B, threads, [&](int32_t b) {
+            try {
+                const float* p = preds + (size_t)b * P;
+                int32_t* s = slots + (size_t)b * T;
+                double* l = lengths + (size_t)b * T;
+                bool bad = false;
+                for (size_t e = 0; e < P; ++e) bad |= !(p[e] - p[e] == 0.0f);
+                nonfinite[b] = bad;
+                if (bad) { std::fill(s, s + T, 0); std::fill(l, l + T, 0.0); return; }
+                NjTree t;
+                nj_core(p, N, t);
+                for (size_t j = 0; j < J; ++j) { s[2 * j] = t.joins[j].a; s[2 * j + 1] = t.joins[j].b; l[2 * j] = t.joins[j].la; l[2 * j + 1] = t.joins[j].lb; }
+                s[2 * J] = t.i; s[2 * J + 1] = t.j; s[2 * J + 2] = t.k;
+                l[2 * J] = t.li; l[2 * J + 1] = t.lj; l[2 * J + 2] = t.lk;
+            } catch (...) { failed = true; }
+        });
+    } catch (...) { return PF_ENOMEM; }
+    return failed ? PF_ENOMEM : PF_OK;
+}
+
+// Split supports without a device: the bodies of pf_support.hip.h's kernels run serially, one
+// source at a time - the same integers as pf_join_supports.  Twin of phyloformer_amd/supports.py::split_supports.
+int pf_join_supports_host(const int32_t* ref_slots, const int32_t* rep_slots, const uint8_t* rep_flag, int32_t B, int32_t R, int32_t N,
+                          int32_t* count, int64_t* transfer, int32_t* depth, uint8_t* status) {
+    if (!ref_slots || !rep_slots || !count || !transfer || !depth || !status || B < 1 || R < 1 || N < 4 || N > pfbme::MAX_N)
+        return PF_EINVAL;
+    const size_t T = (size_t)pfsup::table_len(N), S = (size_t)N - 3, W = (size_t)pfsup::words_of(N), b = (size_t)B, r = (size_t)R;
+    size_t total = 0;
+    if (__builtin_mul_overflow(b * r, T * sizeof(int32_t), &total)) return PF_EINVAL;
+    try {
+        std::vector<int32_t> parent((size_t)pfbme::nodes_of(N)), children((size_t)pfbme::nodes_of(N) * 3);
+        for (size_t i = 0; i < b; ++i)                            // refused before any work
+            if (!pfbme::tree_of_joins(ref_slots + i * T, N, parent.data(), children.data())) return PF_EINVAL;
+        for (size_t i = 0; i < b * r; ++i)
+            if (!(rep_flag && rep_flag[i]) && !pfbme::tree_of_joins(rep_slots + i * T, N, parent.data(), children.data())) return PF_EINVAL;
+        // the state of one source with all its replicates, reused from source to source
+        std::vector<uint64_t> bits((r + 1) * S * W), tile((size_t)pfsup::TILE * W);
+        std::vector<int32_t> row((r + 1) * (size_t)N), sizes(S), delta(r * S);
+        std::vector<uint8_t> bad(b * (r + 1), 0);
+        pfsup::Args a{};
+        a.ref_slots = ref_slots; a.rep_slots = rep_slots; a.rep_flag = rep_flag;
+        a.bits = bits.data(); a.row = row.data(); a.sizes = sizes.data(); a.delta = delta.data(); a.bad = bad.data();
+        a.count = count; a.transfer = transfer; a.depth = depth; a.status = status;
+        a.N = N; a.R = R; a.nb = 1; a.r0 = 0; a.rc = R;
+        for (int32_t src = 0; src < B; ++src) {
+            a.b0 = src;
+            pfsup::serial_chunk(a, tile.data(), true);
+        }
+        return PF_OK;
     } catch (...) { return PF_ENOMEM; }
 }
 

@@ -46,6 +46,7 @@
 #include "pf_tile.hip.h"
 #include "pf_nj.hip.h"
 #include "pf_bme.hip.h"
+#include "pf_support.hip.h"
 #include "pf_weights.hip.h"
 #include "pf_weights_host.h"
 #include "pf_host_prep.h"
@@ -252,6 +253,12 @@ struct pf_handle {
     int64_t spr_calls = 0;       // likewise pf_bme_spr / pf_bme_spr_device ("bme_spr")
     bool spr_pairs_simple = false;   // option "spr_pairs_simple": T by k_bme_pairs_simple (the baseline of tools/spr_bench.py)
     int64_t spr_step_cap = 0;    // option "spr_step_cap": moves after which pf_bme_spr caps a source (0: 16 N)
+    // pf_join_supports / pf_join_supports_device (grow-only): the state of one chunk (pf_support.hip.h: carve), the
+    // whole call's tree flags, and the staging of the host entry point's tables and results
+    char* d_sup = nullptr; size_t d_sup_bytes = 0;
+    uint8_t* d_sup_bad = nullptr; size_t d_sup_bad_bytes = 0;
+    char* d_sup_io = nullptr; size_t d_sup_io_bytes = 0;
+    int64_t sup_calls = 0;       // calls since the last pf_profile_reset ("join_supports")
     // weighted forwards (grow-only): the weight rows of a host call or of one chunk of derived alignments, what
     // k_weight_sums made of a call's rows ([..][4], pf_weights.hip.h), and the weight table of pf_forward_sites_weighted
     float* d_w = nullptr; size_t d_w_bytes = 0;
@@ -2207,6 +2214,112 @@ int bme_impl(pf_handle* h, bool spr, bool device, const float* preds, const int3
     return PF_OK;
 }
 
+// ---- split supports of join tables (pf_join_supports, pf_join_supports_device; pf_support.hip.h) ----
+
+static_assert(pfbme::MAX_N <= 64 * pfsup::MAX_W, "k_sup_match keeps TILE splits of MAX_W words in LDS");
+// (state_bytes: the least a call needs - a source's reference table and one replicate table; the plan below sizes chunks)
+const TreeSearch SUP_SEARCH{"split supports", pfbme::MAX_N, pfsup::min_state_bytes, pfsup::SUP_MAX_Y,
+                            "the bitset tables of the reference and of one replicate"};
+
+// The chunks of a call: `nb` whole sources side by side where a source's R + 1 tables and its delta fit the workspace
+// limit, otherwise one source at a time in runs of `rc` replicates.  Refused only where the reference and one replicate
+// do not fit (check_tree_shape names the bytes).
+int plan_supports(pf_handle* h, int B, int R, int N, int* nb, int* rc) {
+    int chunk = 0;
+    const int rc0 = check_tree_shape(h, SUP_SEARCH, B, N, &chunk);
+    if (rc0) return rc0;
+    if (N < 4) return fail(h, PF_EINVAL, "split supports need N >= 4 sequences (got %d): a tree of 3 has no split", N);
+    if (R < 1) return fail(h, PF_EINVAL, "split supports need R >= 1 replicates (got %d)", R);
+    size_t n = 0;
+    if (!mul_size((size_t)B, (size_t)R, (size_t)pfnj::table_len(N) * sizeof(int32_t), &n))
+        return fail(h, PF_EINVAL, "B=%d sources of R=%d replicate tables overflow the address space", B, R);
+    // (a launch's workgroups times their 256 threads stay below 2^32)
+    const int64_t tiles = ((int64_t)N - 3 + pfsup::TILE - 1) / pfsup::TILE, max_trees = std::max<int64_t>(2, ((int64_t)1 << 23) / tiles);
+    const size_t limit = (size_t)h->ws_limit_bytes, per = pfsup::state_bytes(N, R);
+    if (per <= limit && (int64_t)R + 1 <= max_trees && R <= pfsup::SUP_MAX_Y) {
+        *rc = R;
+        *nb = (int)std::min<int64_t>(std::min<int64_t>(B, pfsup::SUP_MAX_Y), std::min<int64_t>((int64_t)(limit / per), max_trees / ((int64_t)R + 1)));
+        return PF_OK;
+    }
+    const size_t tree = pfsup::tree_bytes(N), each = tree + pfsup::sizes_bytes(N);      // (limit >= state_bytes(N, 1): checked)
+    *nb = 1;
+    *rc = (int)std::min<int64_t>(std::min<int64_t>(R, pfsup::SUP_MAX_Y), std::min<int64_t>((int64_t)((limit - tree - pfsup::sizes_bytes(N)) / each), max_trees - 1));
+    return PF_OK;
+}
+
+// all chunks of a call on device arrays, enqueued on h->stream
+int supports_launch(pf_handle* h, const int32_t* d_ref, const int32_t* d_rep, const uint8_t* d_flag, int B, int R, int N, int nb, int rc,
+                    int32_t* d_count, int64_t* d_transfer, int32_t* d_depth, uint8_t* d_status) {
+    int rc2 = ensure_buffer(h, &h->d_sup, &h->d_sup_bytes, (size_t)nb * pfsup::state_bytes(N, rc));
+    if (rc2) return rc2;
+    if ((rc2 = ensure_buffer(h, &h->d_sup_bad, &h->d_sup_bad_bytes, (size_t)B * ((size_t)R + 1)))) return rc2;
+    h->cur = h->stream;
+    HIPCHK(h, hipMemsetAsync(h->d_sup_bad, 0, (size_t)B * ((size_t)R + 1), h->stream));
+    pfsup::Args a{};
+    a.ref_slots = d_ref; a.rep_slots = d_rep; a.rep_flag = d_flag; a.bad = h->d_sup_bad;
+    a.count = d_count; a.transfer = d_transfer; a.depth = d_depth; a.status = d_status;
+    a.N = N; a.R = R;
+    // (chunks follow each other on the stream, so the next one may reuse the state)
+    for (int b0 = 0; b0 < B; b0 += nb)
+        for (int r0 = 0; r0 < R; r0 += rc) {
+            a.b0 = b0; a.nb = std::min(nb, B - b0); a.r0 = r0; a.rc = std::min(rc, R - r0);
+            pfsup::carve(a, h->d_sup);
+            const hipError_t e = pfsup::launch_chunk(h->stream, a, r0 == 0);
+            if (e != hipSuccess) return fail(h, PF_EHIP, "k_sup_* launch failed: %s", hipGetErrorString(e));
+        }
+    return PF_OK;
+}
+
+int supports_device_impl(pf_handle* h, const int32_t* d_ref, const int32_t* d_rep, const uint8_t* d_flag, int B, int R, int N,
+                         int32_t* d_count, int64_t* d_transfer, int32_t* d_depth, uint8_t* d_status) {
+    if (!d_ref || !d_rep || !d_count || !d_transfer || !d_depth || !d_status) return fail(h, PF_EINVAL, "null buffer");
+    int nb = 0, rc = 0;
+    const int rc2 = plan_supports(h, B, R, N, &nb, &rc);
+    if (rc2) return rc2;
+    HIPCHK(h, hipSetDevice(h->device));
+    ++h->sup_calls;
+    return supports_launch(h, d_ref, d_rep, d_flag, B, R, N, nb, rc, d_count, d_transfer, d_depth, d_status);
+}
+
+int supports_host_impl(pf_handle* h, const int32_t* ref, const int32_t* rep, const uint8_t* flag, int B, int R, int N, int32_t* count,
+                       int64_t* transfer, int32_t* depth, uint8_t* status) {
+    if (!ref || !rep || !count || !transfer || !depth || !status) return fail(h, PF_EINVAL, "null buffer");
+    int nb = 0, rc = 0;
+    int rc2 = plan_supports(h, B, R, N, &nb, &rc);
+    if (rc2) return rc2;
+    const size_t T = (size_t)pfnj::table_len(N), S = (size_t)N - 3, b = (size_t)B, r = (size_t)R;
+    try {
+        // validated as a start table is (a replicate passed with its flag is never read: its table may be anything)
+        if ((rc2 = check_bme_starts(h, ref, B, N))) return rc2;
+        std::vector<int32_t> parent((size_t)pfbme::nodes_of(N)), children((size_t)pfbme::nodes_of(N) * 3);
+        for (size_t i = 0; i < b * r; ++i)
+            if (!(flag && flag[i]) && !pfbme::tree_of_joins(rep + i * T, N, parent.data(), children.data()))
+                return fail(h, PF_EINVAL, "source %zu: replicate %zu is not a join table of N=%d sequences", i / r, i % r, N);
+    } catch (const std::bad_alloc&) { return fail(h, PF_ENOMEM, "out of host memory for the tables of N=%d sequences", N); }
+    HIPCHK(h, hipSetDevice(h->device));
+    ++h->sup_calls;
+    // staging of the whole call: transfer int64 [B][S], ref int32 [B][T], rep int32 [B][R][T], count, depth int32 [B][S],
+    // flag uint8 [B][R], status uint8 [B]
+    const size_t o_tr = 0, o_ref = o_tr + b * S * sizeof(int64_t), o_rep = o_ref + b * T * sizeof(int32_t),
+                 o_cnt = o_rep + b * r * T * sizeof(int32_t), o_dep = o_cnt + b * S * sizeof(int32_t), o_flag = o_dep + b * S * sizeof(int32_t),
+                 o_st = o_flag + b * r, end = o_st + b;
+    if ((rc2 = ensure_buffer(h, &h->d_sup_io, &h->d_sup_io_bytes, end))) return rc2;
+    char* io = h->d_sup_io;
+    HIPCHK(h, hipMemcpyAsync(io + o_ref, ref, b * T * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(io + o_rep, rep, b * r * T * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    if (flag) HIPCHK(h, hipMemcpyAsync(io + o_flag, flag, b * r, hipMemcpyHostToDevice, h->stream));
+    if ((rc2 = supports_launch(h, reinterpret_cast<int32_t*>(io + o_ref), reinterpret_cast<int32_t*>(io + o_rep),
+                               flag ? reinterpret_cast<uint8_t*>(io + o_flag) : nullptr, B, R, N, nb, rc, reinterpret_cast<int32_t*>(io + o_cnt),
+                               reinterpret_cast<int64_t*>(io + o_tr), reinterpret_cast<int32_t*>(io + o_dep), reinterpret_cast<uint8_t*>(io + o_st))))
+        return rc2;
+    HIPCHK(h, hipMemcpyAsync(count, io + o_cnt, b * S * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(transfer, io + o_tr, b * S * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(depth, io + o_dep, b * S * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(status, io + o_st, b, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return PF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2362,6 +2475,9 @@ int pf_destroy(pf_handle_t* h) {
     if (h->d_nj_io) hipFree(h->d_nj_io);
     if (h->d_bme) hipFree(h->d_bme);
     if (h->d_bme_preds) hipFree(h->d_bme_preds);
+    if (h->d_sup) hipFree(h->d_sup);
+    if (h->d_sup_bad) hipFree(h->d_sup_bad);
+    if (h->d_sup_io) hipFree(h->d_sup_io);
     if (h->d_w) hipFree(h->d_w);
     if (h->d_wst) hipFree(h->d_wst);
     if (h->d_wtab) hipFree(h->d_wtab);
@@ -2600,6 +2716,18 @@ int pf_bme_spr_device(pf_handle_t* h, const float* d_preds, const int32_t* d_sta
     return bme_impl(h, true, true, d_preds, d_start_slots, B, N, d_slots, d_lengths, d_steps, d_tree_length, d_status);
 }
 
+int pf_join_supports(pf_handle_t* h, const int32_t* ref_slots, const int32_t* rep_slots, const uint8_t* rep_flag, int32_t B, int32_t R,
+                     int32_t N, int32_t* count, int64_t* transfer, int32_t* depth, uint8_t* status) {
+    if (!h) return PF_EINVAL;
+    return supports_host_impl(h, ref_slots, rep_slots, rep_flag, B, R, N, count, transfer, depth, status);
+}
+
+int pf_join_supports_device(pf_handle_t* h, const int32_t* d_ref_slots, const int32_t* d_rep_slots, const uint8_t* d_rep_flag, int32_t B,
+                            int32_t R, int32_t N, int32_t* d_count, int64_t* d_transfer, int32_t* d_depth, uint8_t* d_status) {
+    if (!h) return PF_EINVAL;
+    return supports_device_impl(h, d_ref_slots, d_rep_slots, d_rep_flag, B, R, N, d_count, d_transfer, d_depth, d_status);
+}
+
 int pf_forward_device(pf_handle_t* h, const uint8_t* d_idx, int32_t B, int32_t N, int32_t L, float* d_out) {
     if (!h) return PF_EINVAL;
     return forward_device_impl(h, d_idx, B, N, 0, L, L, d_out);
@@ -2805,6 +2933,7 @@ int pf_profile_reset(pf_handle_t* h) {
     h->nj_calls = 0;
     h->bme_calls = 0;
     h->spr_calls = 0;
+    h->sup_calls = 0;
     return PF_OK;
 }
 
@@ -2833,6 +2962,11 @@ int pf_profile_get(pf_handle_t* h, const char* kernel, int64_t* launches, double
     }
     if (std::strcmp(kernel, "bme_spr") == 0) {          // pf_bme_spr / pf_bme_spr_device calls
         if (launches) *launches = h->spr_calls;
+        if (total_ms) *total_ms = 0.0;
+        return PF_OK;
+    }
+    if (std::strcmp(kernel, "join_supports") == 0) {    // pf_join_supports / pf_join_supports_device calls
+        if (launches) *launches = h->sup_calls;
         if (total_ms) *total_ms = 0.0;
         return PF_OK;
     }

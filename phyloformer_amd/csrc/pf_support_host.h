@@ -1,0 +1,250 @@
+// Split supports of join tables (pf_join_supports, pf_join_supports_device, pf_join_supports_host):
+// the bodies of the kernels of pf_support.hip.h as functions of (tree or source, thread, threads).  Plain C++, no HIP:
+// pf_hostio.cpp runs them serially (one thread) as the CPU twin; pf_support.hip.h compiles them for the device too
+// (PF_TAXA_HD).  phyloformer_amd/supports.py::split_supports is the statement.  Everything is an integer, so any order
+// of the minima and sums gives the same result.
+//
+// Per tree (the reference of a source, or one of its replicates), S = N - 3 splits of W = ceil(N / 64) words:
+//   bits  uint64 [W][S]   WORD-MAJOR: word w of split t at bits[w * S + t].  The matching kernel gives every thread one
+//                         replicate split j and walks its words, so neighbouring lanes (j, j + 1) read neighbouring
+//                         addresses; in the split-major layout they would be W words apart.
+//   row   int32  [N]      the join that last wrote a slot (LEAF: still the single sequence, DEAD: joined away); no
+//                         [N][W] member table: a cluster IS the row of the join that made it.
+//   sizes int32  [S]      the reference only: sequences on the normalised side of every split.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include "pf_taxa_host.h"
+
+namespace pfsup {
+
+constexpr int TILE = 16;               // reference splits of one workgroup of the matching kernel
+constexpr int32_t LEAF = -1, DEAD = -2;
+
+PF_TAXA_HD inline int words_of(int N) { return (N + 63) / 64; }
+PF_TAXA_HD inline int64_t table_len(int N) { return 2 * ((int64_t)N - 3) + 3; }
+PF_TAXA_HD inline int popc(uint64_t x) { return __builtin_popcountll(x); }
+
+// bytes of one tree's bitset table and row list (8-byte multiples)
+inline size_t tree_bytes(int N) {
+    const size_t S = (size_t)N - 3, W = (size_t)words_of(N);
+    return S * W * sizeof(uint64_t) + (((size_t)N + 1) / 2) * 2 * sizeof(int32_t);
+}
+// bytes a source adds for its reference sizes, and one replicate for its row of delta (padded to 8)
+inline size_t sizes_bytes(int N) { return ((((size_t)N - 3) + 1) / 2) * 2 * sizeof(int32_t); }
+// a source with its reference table and rc replicate tables
+inline size_t state_bytes(int N, int64_t rc) { return (size_t)(rc + 1) * tree_bytes(N) + sizes_bytes(N) + (size_t)rc * sizes_bytes(N); }
+// the least a call needs: the reference and one replicate (pf_lib.hip: TreeSearch)
+inline size_t min_state_bytes(int N) { return state_bytes(N, 1); }
+
+struct Args {
+    const int32_t* ref_slots;   // [B][T]
+    const int32_t* rep_slots;   // [B][R][T]
+    const uint8_t* rep_flag;    // [B][R] or null
+    uint64_t* bits;             // [nb][rc + 1][W][S]: tree 0 of a source is its reference
+    int32_t* row;               // [nb][rc + 1][N]
+    int32_t* sizes;             // [nb][S]
+    int32_t* delta;             // [nb][rc][S]
+    uint8_t* bad;               // [B][R + 1], the whole call's: tree k of source b is no join table (zeroed by the caller)
+    int32_t* count;             // [B][S]
+    int64_t* transfer;          // [B][S]
+    int32_t* depth;             // [B][S]
+    uint8_t* status;            // [B]
+    int N, R;                   // R: the call's replicates
+    int b0, nb;                 // the chunk's sources b0 .. b0 + nb - 1
+    int r0, rc;                 // and replicates r0 .. r0 + rc - 1
+};
+
+PF_TAXA_HD inline size_t tree_index(const Args& a, int src, int k) { return (size_t)src * (size_t)(a.rc + 1) + (size_t)k; }
+PF_TAXA_HD inline uint64_t* bits_of(const Args& a, int src, int k) {
+    return a.bits + tree_index(a, src, k) * (size_t)(a.N - 3) * (size_t)words_of(a.N);
+}
+PF_TAXA_HD inline int32_t* row_of(const Args& a, int src, int k) { return a.row + tree_index(a, src, k) * (size_t)a.N; }
+// the join table of tree k of chunk source src
+PF_TAXA_HD inline const int32_t* slots_of(const Args& a, int src, int k) {
+    const size_t T = (size_t)table_len(a.N), b = (size_t)(a.b0 + src);
+    return k == 0 ? a.ref_slots + b * T : a.rep_slots + (b * (size_t)a.R + (size_t)(a.r0 + k - 1)) * T;
+}
+// is replicate k - 1 of the chunk passed with its flag set?  (its table is then never read)
+PF_TAXA_HD inline bool flagged(const Args& a, int src, int k) {
+    return k > 0 && a.rep_flag && a.rep_flag[(size_t)(a.b0 + src) * (size_t)a.R + (size_t)(a.r0 + k - 1)];
+}
+PF_TAXA_HD inline uint8_t* bad_of(const Args& a, int src, int k) {
+    return a.bad + (size_t)(a.b0 + src) * (size_t)(a.R + 1) + (size_t)(k == 0 ? 0 : a.r0 + k);
+}
+
+// ---- k_sup_splits: one workgroup per tree ---------------------------------------------------------------------------
+
+PF_TAXA_HD inline void rows_init(int32_t* row, int N, int tid, int threads) {
+    for (int i = tid; i < N; i += threads) row[i] = LEAF;
+}
+
+// How a body reads `row`: plainly on the CPU; the device (pf_support.hip.h) hands every value over as a scalar, since
+// all threads of a workgroup read the same entries.
+struct PlainRows {
+    const int32_t* row;
+    PF_TAXA_HD int32_t operator()(int32_t slot) const { return row[slot]; }
+};
+
+// May slots sa, sb be joined?  Their rows come back in ra, rb.  Nothing is indexed before the range is known.
+template <class Rows>
+PF_TAXA_HD inline bool join_ok(const Rows& rows, int N, int32_t sa, int32_t sb, int32_t* ra, int32_t* rb) {
+    if (sa < 0 || sa >= N || sb < 0 || sb >= N || sa == sb) return false;
+    *ra = rows(sa);
+    *rb = rows(sb);
+    if (*ra == DEAD) return false;
+    if (*rb == DEAD) return false;
+    return true;
+}
+
+// the three slots of the trifurcation: in range, alive, distinct
+template <class Rows>
+PF_TAXA_HD inline bool final_ok(const Rows& rows, int N, const int32_t* last) {
+    for (int i = 0; i < 3; ++i) {
+        if (last[i] < 0 || last[i] >= N) return false;
+        if (rows(last[i]) == DEAD) return false;
+    }
+    if (last[0] == last[1]) return false;
+    if (last[0] == last[2]) return false;
+    return last[1] != last[2];
+}
+
+PF_TAXA_HD inline uint64_t cluster_word(const uint64_t* bits, int S, int32_t r, int32_t slot, int w) {
+    if (r >= 0) return bits[(size_t)w * (size_t)S + (size_t)r];
+    return (slot >> 6) == w ? (uint64_t)1 << (slot & 63) : 0;
+}
+
+// Row t = the union of the clusters in slots sa (row ra) and sb (row rb); thread tid takes the words tid, tid + threads,
+// ...  A word of a row is written and later read by the same thread, so the rows need no barrier - `row` does.
+PF_TAXA_HD inline void join_words(uint64_t* bits, int S, int W, int t, int32_t sa, int32_t ra, int32_t sb, int32_t rb, int tid, int threads) {
+    for (int w = tid; w < W; w += threads)
+        bits[(size_t)w * (size_t)S + (size_t)t] = cluster_word(bits, S, ra, sa, w) | cluster_word(bits, S, rb, sb, w);
+}
+
+// Splits tid, tid + threads, ...: the side without sequence 0, the tail of the last word clear; sizes (may be null)
+// receives the number of sequences on that side.
+PF_TAXA_HD inline void normalise(uint64_t* bits, int S, int W, int N, int32_t* sizes, int tid, int threads) {
+    const uint64_t tail = (N & 63) ? (((uint64_t)1 << (N & 63)) - 1) : ~(uint64_t)0;
+    for (int t = tid; t < S; t += threads) {
+        const bool flip = bits[t] & 1;
+        int k = 0;
+        for (int w = 0; w < W; ++w) {
+            uint64_t x = bits[(size_t)w * (size_t)S + (size_t)t];
+            if (flip) x = ~x;
+            if (w == W - 1) x &= tail;
+            bits[(size_t)w * (size_t)S + (size_t)t] = x;
+            k += popc(x);
+        }
+        if (sizes) sizes[t] = k;
+    }
+}
+
+// ---- k_sup_match: a tile of reference splits against one replicate ---------------------------------------------------
+
+PF_TAXA_HD inline int depth_of(int k, int N) { return k < N - k ? k : N - k; }
+
+// The tile's reference words into tile[TILE][W] (zeros beyond the last split), thread by thread
+PF_TAXA_HD inline void tile_load(uint64_t* tile, const uint64_t* ref, int S, int W, int t0, int tid, int threads) {
+    for (int e = tid; e < TILE * W; e += threads) {
+        const int k = e / W, w = e % W;
+        tile[e] = t0 + k < S ? ref[(size_t)w * (size_t)S + (size_t)(t0 + k)] : 0;
+    }
+}
+
+// best[k] = min over the replicate splits j = tid, tid + threads, ... of min(h, N - h), h = popcount(ref k xor rep j);
+// every replicate word is loaded once and meets the whole tile.  N where the thread has no split.
+PF_TAXA_HD inline void match_thread(const uint64_t* tile, const uint64_t* rep, int S, int W, int N, int tid, int threads, int* best) {
+    for (int k = 0; k < TILE; ++k) best[k] = N;
+    for (int j = tid; j < S; j += threads) {
+        int h[TILE];
+        for (int k = 0; k < TILE; ++k) h[k] = 0;
+        for (int w = 0; w < W; ++w) {
+            const uint64_t x = rep[(size_t)w * (size_t)S + (size_t)j];
+            for (int k = 0; k < TILE; ++k) h[k] += popc(x ^ tile[k * W + w]);
+        }
+        for (int k = 0; k < TILE; ++k) {
+            const int m = h[k] < N - h[k] ? h[k] : N - h[k];
+            if (m < best[k]) best[k] = m;
+        }
+    }
+}
+
+// delta of reference split t against a replicate whose closest split is `best` away: the leaf edges give p - 1
+PF_TAXA_HD inline int32_t delta_of(int best, int size, int N) {
+    const int cap = depth_of(size, N) - 1;
+    return best < cap ? best : cap;
+}
+
+// ---- k_sup_sum: one thread per (source, split) ------------------------------------------------------------------------
+
+// Adds the chunk's replicates (ascending) to count / transfer of split t of chunk source src (`first`: starts them).  A
+// source with a tree that is no join table - in this chunk or an earlier one - has status 1 and zeros.
+PF_TAXA_HD inline void sum_split(const Args& a, int src, int t, bool first) {
+    const int S = a.N - 3;
+    const size_t b = (size_t)(a.b0 + src), o = b * (size_t)S + (size_t)t;
+    bool bad = false;
+    for (int k = 0; k <= a.R; ++k) bad |= a.bad[b * (size_t)(a.R + 1) + (size_t)k] != 0;
+    if (t == 0) a.status[b] = bad;
+    if (bad) { a.count[o] = 0; a.transfer[o] = 0; a.depth[o] = 0; return; }
+    int32_t c = first ? 0 : a.count[o];
+    int64_t s = first ? 0 : a.transfer[o];
+    const int32_t* d = a.delta + (size_t)src * (size_t)a.rc * (size_t)S + (size_t)t;
+    for (int r = 0; r < a.rc; ++r) {
+        const int32_t x = d[(size_t)r * (size_t)S];
+        c += x == 0;
+        s += x;
+    }
+    a.count[o] = c;
+    a.transfer[o] = s;
+    a.depth[o] = depth_of(a.sizes[(size_t)src * (size_t)S + (size_t)t], a.N);
+}
+
+// ---- the serial run of the bodies (the CPU twin; threads = 1) --------------------------------------------------------
+
+// tree k of chunk source src; false: no join table (the tree's flag is set)
+inline bool serial_tree(const Args& a, int src, int k) {
+    const int N = a.N, S = N - 3, W = words_of(N);
+    const int32_t* slots = slots_of(a, src, k);
+    uint64_t* bits = bits_of(a, src, k);
+    int32_t* row = row_of(a, src, k);
+    rows_init(row, N, 0, 1);
+    bool ok = true;
+    for (int t = 0; t < S && ok; ++t) {
+        const int32_t sa = slots[2 * t], sb = slots[2 * t + 1];
+        int32_t ra = 0, rb = 0;
+        if (!(ok = join_ok(PlainRows{row}, N, sa, sb, &ra, &rb))) break;
+        join_words(bits, S, W, t, sa, ra, sb, rb, 0, 1);
+        row[sa] = t;
+        row[sb] = DEAD;
+    }
+    ok = ok && final_ok(PlainRows{row}, N, slots + 2 * (size_t)S);
+    if (!ok) { *bad_of(a, src, k) = 1; return false; }
+    normalise(bits, S, W, N, k == 0 ? a.sizes + (size_t)src * (size_t)S : nullptr, 0, 1);
+    return true;
+}
+
+// the whole chunk: trees, deltas, sums
+inline void serial_chunk(const Args& a, uint64_t* tile, bool first) {
+    const int N = a.N, S = N - 3, W = words_of(N);
+    for (int src = 0; src < a.nb; ++src) {
+        bool ok = true;
+        for (int k = 0; k <= a.rc; ++k)
+            if (!flagged(a, src, k)) ok = serial_tree(a, src, k) && ok;
+        for (int r = 0; r < a.rc && ok; ++r)
+            for (int t0 = 0; t0 < S; t0 += TILE) {
+                int best[TILE];
+                const bool skip = flagged(a, src, r + 1);
+                if (!skip) {
+                    tile_load(tile, bits_of(a, src, 0), S, W, t0, 0, 1);
+                    match_thread(tile, bits_of(a, src, r + 1), S, W, N, 0, 1, best);
+                }
+                for (int k = 0; k < TILE && t0 + k < S; ++k)
+                    a.delta[((size_t)src * (size_t)a.rc + (size_t)r) * (size_t)S + (size_t)(t0 + k)] =
+                        delta_of(skip ? N : best[k], a.sizes[(size_t)src * (size_t)S + (size_t)(t0 + k)], N);
+            }
+        for (int t = 0; t < S; ++t) sum_split(a, src, t, first);
+    }
+}
+
+}  // namespace pfsup

@@ -148,6 +148,12 @@ SIGNATURES = {
     "pf_bme_spr_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p]),
     "pf_bme_spr_newick_n": (C.c_int64, [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32, C.c_char_p, C.c_int64]),
+    "pf_join_supports": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
+    "pf_join_supports_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pf_join_supports_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
     "pf_forward_weighted": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "pf_forward_weighted_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "pf_forward_sites_weighted": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
@@ -169,7 +175,8 @@ CALL_TIME_SYMBOLS = frozenset({"pf_forward_site_map", "pf_forward_site_map_devic
                                "pf_place_stats_device", "pf_forward_tiled", "pf_tile_combine_device", "pf_tile_groups",
                                "pf_tile_bound", "pf_nj_joins", "pf_nj_joins_device", "pf_nj_format_joins_n", "pf_bme_nni",
                                "pf_bme_nni_device", "pf_bme_nni_host", "pf_bme_newick_n", "pf_bme_spr",
-                               "pf_bme_spr_device", "pf_bme_spr_host", "pf_bme_spr_newick_n"})
+                               "pf_bme_spr_device", "pf_bme_spr_host", "pf_bme_spr_newick_n", "pf_join_supports",
+                               "pf_join_supports_device", "pf_join_supports_host"})
 
 _lib: Optional[C.CDLL] = None
 
@@ -612,6 +619,33 @@ class Engine:
         self._check(self._optional("pf_bme_spr_device")(self._h, C.c_void_p(d_preds), C.c_void_p(d_start_slots), B, N,
                                                         C.c_void_p(d_slots), C.c_void_p(d_lengths), C.c_void_p(d_steps),
                                                         C.c_void_p(d_tree_length), C.c_void_p(d_status)))
+
+    # -- split supports of join tables -------------------------------------------------------
+    def join_supports(self, ref_slots: np.ndarray, rep_slots: np.ndarray, rep_flag: Optional[np.ndarray] = None):
+        """Split supports on the GPU (``pf_join_supports``): reference join tables ``int32[B, T]`` and replicate join tables
+        ``int32[B, R, T]`` (``[T]`` / ``[R, T]`` drop ``B``), ``rep_flag bool[B, R]`` or None → ``(count int32[B, N - 3],
+        transfer int64[B, N - 3], depth int32[B, N - 3], status uint8[B])``: per split of the reference the replicates that
+        contain it, the sum of its transfer distances and its depth - ``supports.split_supports``, the same integers as
+        ``hostio.join_supports_host``.  ``ValueError``-like refusals come as ``EngineError`` (a table that is no join
+        table, ``N < 4``)."""
+        from .hostio import support_arrays
+        fn = self._optional("pf_join_supports")
+        ref, rep, flag, (B, R, N), single = support_arrays(ref_slots, rep_slots, rep_flag)
+        count, transfer, depth, status = (np.zeros((B, N - 3), dtype=np.int32), np.zeros((B, N - 3), dtype=np.int64),
+                                          np.zeros((B, N - 3), dtype=np.int32), np.zeros(B, dtype=np.uint8))
+        self._check(fn(self._h, ref.ctypes.data, rep.ctypes.data, None if flag is None else flag.ctypes.data, B, R, N,
+                       count.ctypes.data, transfer.ctypes.data, depth.ctypes.data, status.ctypes.data))
+        out = (count, transfer, depth, status)
+        return tuple(x[0] for x in out) if single else out
+
+    def join_supports_device(self, d_ref_slots: int, d_rep_slots: int, d_rep_flag: int, B: int, R: int, N: int, d_count: int,
+                             d_transfer: int, d_depth: int, d_status: int):
+        """``pf_join_supports_device``: device ``ref_slots int32 [B][T]``, ``rep_slots int32 [B][R][T]``, ``rep_flag uint8
+        [B][R]`` (0: none) → device ``count int32`` / ``transfer int64`` / ``depth int32 [B][N - 3]``, ``status uint8 [B]``
+        (asynchronous on the handle's stream).  Tables are checked in the kernel: status 1 and zeros, no refusal."""
+        self._check(self._optional("pf_join_supports_device")(
+            self._h, C.c_void_p(d_ref_slots), C.c_void_p(d_rep_slots), C.c_void_p(d_rep_flag) if d_rep_flag else None, B, R, N,
+            C.c_void_p(d_count), C.c_void_p(d_transfer), C.c_void_p(d_depth), C.c_void_p(d_status)))
 
     # -- site weights -----------------------------------------------------------------------
     @staticmethod

@@ -25,6 +25,7 @@ _PRIVATE = {
                                           C.c_int64, C.c_void_p]),
     "pf_bme_spr_newick_steps_n": (C.c_int64, [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32, C.c_char_p,
                                               C.c_int64, C.c_void_p]),
+    "pf_nj_joins_host_n": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 
@@ -201,6 +202,63 @@ def _refine_host(symbol: str, preds: np.ndarray, start_slots: np.ndarray):
     if rc < 0:
         raise RuntimeError(f"{symbol} failed with status {rc}")
     return slots, lengths, steps, tree_length, status
+
+
+def nj_joins_host(preds: np.ndarray, threads: int = 1):
+    """``Engine.nj_joins`` without a device (``pf_nj_joins_host_n``): ``float32[B, P_N]`` → ``(slots int32[B, T], lengths
+    float64[B, T], nonfinite bool[B])``, the table of ``nj.nj_joins`` bit for bit; a flagged source's table is zeros."""
+    lib = _lib()
+    p = np.ascontiguousarray(np.asarray(preds, dtype=np.float32))
+    if p.ndim != 2 or p.shape[0] < 1:
+        raise ValueError(f"expected distances [B >= 1, P], got {p.shape}")
+    b = p.shape[0]
+    n = (1 + int(round((1 + 8 * p.shape[1]) ** 0.5))) // 2
+    if n * (n - 1) // 2 != p.shape[1] or n < 3:
+        raise ValueError(f"{p.shape[1]} distances are not the pairs of N >= 3 sequences")
+    t = 2 * (n - 3) + 3
+    slots, lengths, flag = np.zeros((b, t), dtype=np.int32), np.zeros((b, t), dtype=np.float64), np.zeros(b, dtype=np.uint8)
+    rc = lib.pf_nj_joins_host_n(p.ctypes.data, b, n, int(threads), slots.ctypes.data, lengths.ctypes.data, flag.ctypes.data)
+    if rc < 0:
+        raise RuntimeError(f"pf_nj_joins_host_n failed with status {rc}")
+    return slots, lengths, flag.astype(bool)
+
+
+def support_arrays(ref_slots, rep_slots, rep_flag):
+    """The arguments of the three ``pf_join_supports`` entry points, checked: ``(ref int32[B, T], rep int32[B, R, T], flag
+    uint8[B, R] or None, (B, R, N), single)``."""
+    ref = np.ascontiguousarray(np.asarray(ref_slots, dtype=np.int32))
+    rep = np.ascontiguousarray(np.asarray(rep_slots, dtype=np.int32))
+    single = ref.ndim == 1
+    if single:
+        ref, rep = ref[None, :], rep[None] if rep.ndim == 2 else rep
+    if ref.ndim != 2 or rep.ndim != 3 or rep.shape[0] != ref.shape[0] or rep.shape[2] != ref.shape[1]:
+        raise ValueError(f"expected reference tables [B, T] and replicate tables [B, R, T], got {ref.shape} and {rep.shape}")
+    b, r, t = rep.shape
+    n = (t - 3) // 2 + 3
+    if t < 5 or 2 * (n - 3) + 3 != t or b < 1 or r < 1:
+        raise ValueError(f"{t} slots are not the join table of N >= 4 sequences, or no source or replicate ({b}, {r})")
+    flag = None
+    if rep_flag is not None:
+        flag = np.ascontiguousarray(np.asarray(rep_flag).astype(bool).astype(np.uint8).reshape(b, r))
+    return ref, rep, flag, (b, r, n), single
+
+
+def join_supports_host(ref_slots, rep_slots, rep_flag=None):
+    """``pf_join_supports_host``: ``Engine.join_supports`` without a device - the same bodies run serially, the same
+    integers as ``supports.split_supports``.  ``ValueError`` for what the library refuses (``N < 4``, a table that is no
+    join table)."""
+    lib = load_library()
+    ref, rep, flag, (b, r, n), single = support_arrays(ref_slots, rep_slots, rep_flag)
+    count, transfer, depth, status = (np.zeros((b, n - 3), dtype=np.int32), np.zeros((b, n - 3), dtype=np.int64),
+                                      np.zeros((b, n - 3), dtype=np.int32), np.zeros(b, dtype=np.uint8))
+    rc = lib.pf_join_supports_host(ref.ctypes.data, rep.ctypes.data, None if flag is None else flag.ctypes.data, b, r, n,
+                                   count.ctypes.data, transfer.ctypes.data, depth.ctypes.data, status.ctypes.data)
+    if rc == -1:
+        raise ValueError("pf_join_supports_host refused its arguments (a table that is no join table?)")
+    if rc < 0:
+        raise RuntimeError(f"pf_join_supports_host failed with status {rc}")
+    out = (count, transfer, depth, status)
+    return tuple(x[0] for x in out) if single else out
 
 
 def _join_table(slots, lengths, n: int) -> Tuple[np.ndarray, np.ndarray]:

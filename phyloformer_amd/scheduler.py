@@ -340,9 +340,11 @@ class DirectoryRunner:
                 t0 = time.perf_counter()
                 res = mode.follow(engine, batch[s])
                 dt = time.perf_counter() - t0
+                # (a mode's further device work on the results, booked by itself: Bootstrap's --tbe / --bootstrap-refined)
+                cols = (res,) if mode.extend is None else mode.extend(self, engine, shape, preds[s], res)
                 with self._lock:
                     mode.account(self.stats, len(group[s]), shape, dt)
-                    submit(mode.jobs(self, shape, group[s], preds[s], res))
+                    submit(mode.jobs(self, shape, group[s], preds[s], *cols))
         if self.progress is not None and self._followers:
             self.progress(len(group))
         with self._lock:
@@ -649,7 +651,9 @@ def summarize(stats: dict, load_s: float = 0.0) -> dict:
             "replicates": stats.get("replicates", 0), "bootstrap_s": round(stats.get("bootstrap_s", 0.0), 6),
             "windows": stats.get("windows", 0), "windows_s": round(stats.get("windows_s", 0.0), 6),
             **({k: round(stats[k], 6) for k in ("bme", "bme_steps", "bme_device", "bme_device_s")} if "bme" in stats else {}),
-            **({k: round(stats[k], 6) for k in ("spr", "spr_steps", "spr_device", "spr_device_s")} if "spr" in stats else {})}
+            **({k: round(stats[k], 6) for k in ("spr", "spr_steps", "spr_device", "spr_device_s")} if "spr" in stats else {}),
+            **({k: round(stats[k], 6) for k in ("tbe", "refined_supports", "supports_device", "supports_device_s")}
+               if "tbe" in stats else {})}
 
 
 def run_multi_device(script: str, argv: List[str], devices: Sequence[int], shard: str = "files") -> Tuple[int, List[dict]]:
