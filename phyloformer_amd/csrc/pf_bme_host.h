@@ -605,26 +605,20 @@ inline SprArgs spr_args_of(const float* preds, int N, int part_cap, int epg, int
 // those bytes): array after array, each [B][its share], so that a source's rows are contiguous
 inline size_t state_bytes(int N) {
     Args a = args_of(nullptr, N, eval_groups(N, EVAL_EDGES));
-    pfnj::Measure m;
-    state_arrays(m, a, 1);
-    return m.bytes;
+    return pfspan::measure([&](auto& v) { state_arrays(v, a, 1); });
 }
 inline Args carve(char* ws, const float* preds, int B, int N) {
     Args a = args_of(preds, N, eval_groups(N, EVAL_EDGES));
-    pfnj::Carve c{ws};
-    state_arrays(c, a, (size_t)B);
+    pfspan::carve(ws, [&](auto& v) { state_arrays(v, a, (size_t)B); });
     return a;
 }
 inline size_t spr_state_bytes(int N) {
     SprArgs s = spr_args_of(nullptr, N, eval_groups(N, EVAL_EDGES), SPR_EVAL_EDGES, 0);
-    pfnj::Measure m;
-    spr_state_arrays(m, s, 1);
-    return m.bytes;
+    return pfspan::measure([&](auto& v) { spr_state_arrays(v, s, 1); });
 }
 inline SprArgs carve_spr(char* ws, const float* preds, int B, int N, int64_t cap) {
     SprArgs s = spr_args_of(preds, N, eval_groups(N, EVAL_EDGES), SPR_EVAL_EDGES, cap > 0 ? cap : step_cap(N));
-    pfnj::Carve c{ws};
-    spr_state_arrays(c, s, (size_t)B);
+    pfspan::carve(ws, [&](auto& v) { spr_state_arrays(v, s, (size_t)B); });
     return s;
 }
 

@@ -245,11 +245,9 @@ void f64_carve(char* ws, const size_t off[F64_BUFS], F64Workspace* w) {
 int ensure_f64_workspace(pf_handle* h, const F64Dims& d, int B, int P, int Lloc, F64Workspace* w) {
     size_t off[F64_BUFS];
     const size_t need = f64_bytes(d, B, P, Lloc, off);
-    if (need > h->wsp_bytes) {
-        const int rc = make_room(h, true, need);
-        if (rc) return rc;
-        HIPCHK(h, hipMalloc((void**)&h->wsp, need));
-        h->wsp_bytes = need;
+    if (need > h->wsp.cap) {
+        int rc = make_room(h, true, need);              // (releases wsp, so the reserve below only allocates)
+        if (rc || (rc = h->wsp.reserve(h, need))) return rc;
     }
     f64_carve(h->wsp, off, w);
     return PF_OK;

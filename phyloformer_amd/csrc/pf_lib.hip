@@ -177,6 +177,22 @@ struct GenericWeights {
 
 constexpr int64_t SUB_FLOATS_DEFAULT = (int64_t)1 << 22;
 
+// A grow-only device allocation, pointer and capacity together.  A buffer enters its owner's list
+// (pf_handle::buffers, pf_mha::buffers) when it is constructed and is freed from there: a new one is one member.
+struct DeviceBuffer {
+    void* p = nullptr; size_t cap = 0;
+    explicit DeviceBuffer(std::vector<DeviceBuffer*>& all) { all.push_back(this); }
+    DeviceBuffer(const DeviceBuffer&) = delete;
+    // `bytes` at least afterwards, contents not kept: no HIP call where it fits; the handle's streams drained before a
+    // live allocation is replaced; empty after a failure
+    int reserve(pf_handle* h, size_t bytes);
+    void release() { if (p) hipFree(p); p = nullptr; cap = 0; }
+};
+template <class T> struct Buffer : DeviceBuffer {
+    using DeviceBuffer::DeviceBuffer;
+    operator T*() const { return static_cast<T*>(p); }
+};
+
 }  // namespace
 
 struct pf_handle {
@@ -211,59 +227,51 @@ struct pf_handle {
     float* first_img = nullptr;     // LDS image for k_main<FIRST> (only the row-statistics tail used)
     std::vector<BlockDev> blk;
     std::vector<void*> owned;     // every device allocation made at create
+    std::vector<DeviceBuffer*> buffers;   // every grow-only buffer below
     // pair index tables
     int pair_n = -1;
-    int16_t* pair_i = nullptr;
-    int16_t* pair_j = nullptr;
+    Buffer<int16_t> pair_i{buffers}, pair_j{buffers};
     // workspace (ws2: second half-batch of an overlapped site-sharded forward)
-    size_t ws_bytes = 0;
-    char* ws = nullptr;
-    size_t ws2_bytes = 0;
-    char* ws2 = nullptr;
+    Buffer<char> ws{buffers}, ws2{buffers};
     bool overlap = true;          // option "overlap": two half-batches on two streams when collectives run
     int reserve_cus = 8;          // option "reserve_cus": CUs the persistent kernels leave to RCCL then
-    uint8_t* d_idx = nullptr; size_t d_idx_bytes = 0;
-    float* d_out = nullptr; size_t d_out_bytes = 0;
-    uint8_t* d_rep = nullptr; size_t d_rep_bytes = 0;       // forward_derived: one chunk of derived alignments (grow-only)
-    int32_t* d_map = nullptr; size_t d_map_bytes = 0;       // pf_forward_sites / pf_forward_windows: the site map (grow-only)
+    Buffer<uint8_t> d_idx{buffers};
+    Buffer<float> d_out{buffers};
+    Buffer<uint8_t> d_rep{buffers};       // forward_derived: one chunk of derived alignments (grow-only)
+    Buffer<int32_t> d_map{buffers};       // pf_forward_sites / pf_forward_windows: the site map (grow-only)
     // pf_forward_site_map / pf_forward_site_profile (grow-only): one chunk's map of head terms, the partial column sums
     // of its reduction, and the reduced se [B][P] / profile [B][L] of a host call
-    float* d_smap = nullptr; size_t d_smap_bytes = 0;
-    double* d_mpart = nullptr; size_t d_mpart_bytes = 0;
-    float* d_se = nullptr; size_t d_se_bytes = 0;
-    float* d_prof = nullptr; size_t d_prof_bytes = 0;
+    Buffer<float> d_smap{buffers}, d_se{buffers}, d_prof{buffers};
+    Buffer<double> d_mpart{buffers};
     // the taxon-axis analyses (TaxonCuts: leave-one-out, placement, tiling): what one sub-call's reduction reads beside
     // h->d_out and what it writes, carved from one grow-only buffer - the three are never live together
-    float* d_sub = nullptr; size_t d_sub_bytes = 0;
+    Buffer<char> d_sub{buffers};
     int64_t sub_floats = SUB_FLOATS_DEFAULT;    // option "sub_floats": distances one sub-call may hold on the device
-    // pf_forward_tiled / pf_tile_combine_device: the plan of the last (N, M) and its device tables (offset int64 [S + 1],
-    // then bounds int32 [G + 1]) (grow-only)
+    // pf_forward_tiled / pf_tile_combine_device: the plan of the last (N, M) and its two device tables
+    // (pftile::table_arrays), carved from one grow-only buffer
     pftile::Plan tiled_plan;
-    char* d_tiled_tab = nullptr; size_t d_tiled_tab_bytes = 0;
+    pftile::Tables tiled_tab;
+    Buffer<char> d_tiled_tab{buffers};
     // pf_nj_joins / pf_nj_joins_device (grow-only): the state of one chunk of sources (d, r, partial minima, active
     // slots), and the staging of a host call's chunk (lengths, preds, slots, flags)
-    char* d_nj = nullptr; size_t d_nj_bytes = 0;
-    char* d_nj_io = nullptr; size_t d_nj_io_bytes = 0;
+    Buffer<char> d_nj{buffers}, d_nj_io{buffers};
     int64_t nj_calls = 0;        // calls since the last pf_profile_reset ("nj_joins")
     // pf_bme_nni / pf_bme_nni_device (grow-only): the state of one chunk of sources (pf_bme.hip.h: carve) and the
     // staging of the host entry point's distances
-    char* d_bme = nullptr; size_t d_bme_bytes = 0;
-    float* d_bme_preds = nullptr; size_t d_bme_preds_bytes = 0;
+    Buffer<char> d_bme{buffers};
+    Buffer<float> d_bme_preds{buffers};
     int64_t bme_calls = 0;       // calls since the last pf_profile_reset ("bme_nni")
     int64_t spr_calls = 0;       // likewise pf_bme_spr / pf_bme_spr_device ("bme_spr")
     bool spr_pairs_simple = false;   // option "spr_pairs_simple": T by k_bme_pairs_simple (the baseline of tools/spr_bench.py)
     int64_t spr_step_cap = 0;    // option "spr_step_cap": moves after which pf_bme_spr caps a source (0: 16 N)
     // pf_join_supports / pf_join_supports_device (grow-only): the state of one chunk (pf_support.hip.h: carve), the
     // whole call's tree flags, and the staging of the host entry point's tables and results
-    char* d_sup = nullptr; size_t d_sup_bytes = 0;
-    uint8_t* d_sup_bad = nullptr; size_t d_sup_bad_bytes = 0;
-    char* d_sup_io = nullptr; size_t d_sup_io_bytes = 0;
+    Buffer<char> d_sup{buffers}, d_sup_io{buffers};
+    Buffer<uint8_t> d_sup_bad{buffers};
     int64_t sup_calls = 0;       // calls since the last pf_profile_reset ("join_supports")
     // weighted forwards (grow-only): the weight rows of a host call or of one chunk of derived alignments, what
     // k_weight_sums made of a call's rows ([..][4], pf_weights.hip.h), and the weight table of pf_forward_sites_weighted
-    float* d_w = nullptr; size_t d_w_bytes = 0;
-    float* d_wst = nullptr; size_t d_wst_bytes = 0;
-    float* d_wtab = nullptr; size_t d_wtab_bytes = 0;
+    Buffer<float> d_w{buffers}, d_wst{buffers}, d_wtab{buffers};
     // comm: one RCCL communicator per stream (comm[1] serves stream2), created together by pf_comm_init, so that
     // RCCL never has to order one half-batch's collectives behind the other's with an implicit cross-stream wait
     void* comm[2] = {nullptr, nullptr};
@@ -301,7 +309,7 @@ struct pf_handle {
     char f16_why[160] = {0};
     bool precise_ffn_valu = false;   // option "precise_ffn_valu": the float64 FFN on the VALU instead of the matrix cores (cross-check)
     PreciseWeights pw;
-    char* wsp = nullptr; size_t wsp_bytes = 0;     // workspace of the float64 paths (precise and generic)
+    Buffer<char> wsp{buffers};     // workspace of the float64 paths (precise and generic)
     // generic path (pf_generic.hip.h): arch_generic = the architecture is not (64, 4), every forward runs there;
     // option "generic" = 1 sends a (64, 4) handle's forwards there too (its image is built from blob_copy then)
     bool arch_generic = false;
@@ -343,6 +351,21 @@ int upload(pf_handle* h, const std::vector<T>& v, float** out) {
     h->owned.push_back(p);
     HIPCHK(h, hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     *out = reinterpret_cast<float*>(p);
+    return PF_OK;
+}
+
+int DeviceBuffer::reserve(pf_handle* h, size_t bytes) {
+    if (p && bytes <= cap) return PF_OK;
+    hipError_t e = hipSuccess;
+    if (p) {
+        e = hipStreamSynchronize(h->stream);
+        if (e == hipSuccess && h->stream2) e = hipStreamSynchronize(h->stream2);
+        release();
+    }
+    if (e == hipSuccess && (e = hipMalloc(&p, bytes ? bytes : 1)) != hipSuccess) p = nullptr;
+    if (e != hipSuccess)
+        return fail(h, e == hipErrorOutOfMemory ? PF_ENOMEM : PF_EHIP, "device buffer of %zu bytes: %s", bytes, hipGetErrorString(e));
+    cap = bytes;
     return PF_OK;
 }
 
@@ -512,9 +535,9 @@ int ensure_pairs(pf_handle* h, int N) {
     int k = 0;
     for (int i = 0; i < N; ++i)  // model.py:13-17
         for (int j = i + 1; j < N; ++j) { pi[k] = (int16_t)i; pj[k] = (int16_t)j; ++k; }
-    if (h->pair_i) { hipFree(h->pair_i); hipFree(h->pair_j); h->pair_i = h->pair_j = nullptr; }
-    HIPCHK(h, hipMalloc((void**)&h->pair_i, P * sizeof(int16_t)));
-    HIPCHK(h, hipMalloc((void**)&h->pair_j, P * sizeof(int16_t)));
+    h->pair_n = -1;                      // (a failure below leaves no table that passes for N's)
+    int rc = h->pair_i.reserve(h, P * sizeof(int16_t));
+    if (rc || (rc = h->pair_j.reserve(h, P * sizeof(int16_t)))) return rc;
     HIPCHK(h, hipMemcpyAsync(h->pair_i, pi.data(), P * sizeof(int16_t), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->pair_j, pj.data(), P * sizeof(int16_t), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -570,17 +593,8 @@ void carve_workspace(char* ws, const size_t off[WS_BUFS], Workspace* w) {
 int ensure_workspace(pf_handle* h, int B, int P, int Lloc, Workspace* w, bool second = false) {
     size_t off[WS_BUFS];
     const size_t need = workspace_bytes(h, B, P, Lloc, w, off);
-    char*& ws = second ? h->ws2 : h->ws;
-    size_t& have = second ? h->ws2_bytes : h->ws_bytes;
-    if (need > have) {
-        if (ws) {
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            if (h->stream2) HIPCHK(h, hipStreamSynchronize(h->stream2));
-            hipFree(ws); ws = nullptr; have = 0;
-        }
-        HIPCHK(h, hipMalloc((void**)&ws, need));
-        have = need;
-    }
+    Buffer<char>& ws = second ? h->ws2 : h->ws;
+    if (const int rc = ws.reserve(h, need)) return rc;
     carve_workspace(ws, off, w);
     return PF_OK;
 }
@@ -1007,17 +1021,15 @@ struct ShardStage {
 // whole chunk that now runs as two halves).
 int make_room(pf_handle* h, bool f64, size_t need) {
     const size_t budget = std::max(need, (size_t)h->ws_limit_bytes);
-    auto drop = [](char*& p, size_t& n) { if (p) { hipFree(p); p = nullptr; n = 0; } };
-    if (f64 && h->wsp) { HIPCHK(h, hipStreamSynchronize(h->stream)); drop(h->wsp, h->wsp_bytes); }   // regrown by the caller
-    if (h->ws_bytes + h->ws2_bytes + (f64 ? need : h->wsp_bytes) <= budget) return PF_OK;
+    if (f64 && h->wsp) { HIPCHK(h, hipStreamSynchronize(h->stream)); h->wsp.release(); }   // regrown by the caller
+    if (h->ws.cap + h->ws2.cap + (f64 ? need : h->wsp.cap) <= budget) return PF_OK;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (h->stream2) HIPCHK(h, hipStreamSynchronize(h->stream2));
     if (!f64) {
-        drop(h->wsp, h->wsp_bytes);
-        if (h->ws_bytes + h->ws2_bytes <= budget) return PF_OK;
+        h->wsp.release();
+        if (h->ws.cap + h->ws2.cap <= budget) return PF_OK;
     }
-    drop(h->ws, h->ws_bytes);
-    drop(h->ws2, h->ws2_bytes);
+    h->ws.release(); h->ws2.release();
     return PF_OK;
 }
 
@@ -1070,17 +1082,6 @@ int chunk_batch(pf_handle* h, int B, int P, int Lloc, size_t extra = 0) {
     return lo;
 }
 
-// grow-only device buffer
-template <class T>
-int ensure_buffer(pf_handle* h, T** p, size_t* have, size_t bytes) {
-    if (*p && bytes <= *have) return PF_OK;
-    if (*p) hipFree(*p);
-    *p = nullptr; *have = 0;
-    HIPCHK(h, hipMalloc((void**)p, bytes ? bytes : 1));
-    *have = bytes;
-    return PF_OK;
-}
-
 // One launch of a small kernel on h->stream: go() is its header's launcher (a hipError_t), `kid` its profile slot,
 // `name` what a failure calls it.
 template <class Go>
@@ -1096,7 +1097,7 @@ int launch_on_stream(pf_handle* h, int kid, const char* name, Go&& go) {
 // What k_weight_sums makes of the weight rows d_w [B][L] of a call, into the grow-only h->d_wst: asynchronous on
 // h->stream, behind whatever read the buffer before.
 int launch_weight_sums(pf_handle* h, const float* d_w, int B, int L, const float** d_wst) {
-    int rc = ensure_buffer(h, &h->d_wst, &h->d_wst_bytes, (size_t)B * pfw::WST * sizeof(float));
+    int rc = h->d_wst.reserve(h, (size_t)B * pfw::WST * sizeof(float));
     if (rc) return rc;
     *d_wst = h->d_wst;
     return launch_on_stream(h, K_WEIGHT_SUMS, "k_weight_sums",
@@ -1257,13 +1258,13 @@ int forward_host_impl(pf_handle* h, const uint8_t* idx, int B, int N, int l_begi
     HIPCHK(h, hipSetDevice(h->device));
     const size_t nw = (size_t)B * Lloc * sizeof(float);
     if (weighted) {
-        if ((rc = ensure_buffer(h, &h->d_w, &h->d_w_bytes, nw))) return rc;
+        if ((rc = h->d_w.reserve(h, nw))) return rc;
         HIPCHK(h, hipMemcpyAsync(h->d_w, w, nw, hipMemcpyHostToDevice, h->stream));
     }
     const int P = N * (N - 1) / 2;
-    if ((rc = ensure_buffer(h, &h->d_idx, &h->d_idx_bytes, nidx))) return rc;
+    if ((rc = h->d_idx.reserve(h, nidx))) return rc;
     const size_t nout = (size_t)B * P * sizeof(float);
-    if ((rc = ensure_buffer(h, &h->d_out, &h->d_out_bytes, nout))) return rc;
+    if ((rc = h->d_out.reserve(h, nout))) return rc;
     if (nidx) HIPCHK(h, hipMemcpyAsync(h->d_idx, idx, nidx, hipMemcpyHostToDevice, h->stream));
     const bool default_kernels = !f64_path_of(h, N, L_total);
     rc = forward_device_impl(h, h->d_idx, B, N, l_begin, l_end, L_total, h->d_out, weighted ? h->d_w : nullptr);
@@ -1343,8 +1344,8 @@ int forward_derived(pf_handle* h, const uint8_t* idx, int B, int N, int L, int S
     int rc = d_resident ? PF_OK : check_residues(h, idx, nidx);
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->device));
-    if (!d_resident && (rc = ensure_buffer(h, &h->d_idx, &h->d_idx_bytes, nidx))) return rc;
-    if ((rc = ensure_buffer(h, &h->d_out, &h->d_out_bytes, nout))) return rc;
+    if (!d_resident && (rc = h->d_idx.reserve(h, nidx))) return rc;
+    if ((rc = h->d_out.reserve(h, nout))) return rc;
     if (!d_resident) HIPCHK(h, hipMemcpyAsync(h->d_idx, idx, nidx, hipMemcpyHostToDevice, h->stream));
     const uint8_t* d_all = d_resident ? d_resident : h->d_idx;
     const F64Path* f = f64_path_of(h, Nd, K);
@@ -1353,8 +1354,8 @@ int forward_derived(pf_handle* h, const uint8_t* idx, int B, int N, int L, int S
     const int spc = cb >= S ? cb / S : 0;                  // whole sources per chunk, or
     const int jpc = spc ? S : cb;                          // derived alignments of one source per chunk
     const size_t cap = spc ? (size_t)spc * S : (size_t)jpc;
-    if ((rc = ensure_buffer(h, &h->d_rep, &h->d_rep_bytes, cap * per))) return rc;
-    if (weighted && (rc = ensure_buffer(h, &h->d_w, &h->d_w_bytes, cap * (size_t)K * sizeof(float)))) return rc;
+    if ((rc = h->d_rep.reserve(h, cap * per))) return rc;
+    if (weighted && (rc = h->d_w.reserve(h, cap * (size_t)K * sizeof(float)))) return rc;
     for (int b0 = 0; b0 < B; b0 += std::max(spc, 1))
         for (int j0 = 0; j0 < S; j0 += jpc) {
             const int nb = spc ? std::min(spc, B - b0) : 1, nj = std::min(jpc, S - j0);
@@ -1438,11 +1439,11 @@ int sites_impl(pf_handle* h, const uint8_t* idx, int B, int N, int L, const int3
     bool uploaded = false;
     auto fill = [&](const uint8_t* d_src, int nb, int j0, int nj, uint8_t* d_dst) -> int {
         if (!uploaded) {
-            int rc2 = ensure_buffer(h, &h->d_map, &h->d_map_bytes, nmap);
+            int rc2 = h->d_map.reserve(h, nmap);
             if (rc2) return rc2;
             HIPCHK(h, hipMemcpyAsync(h->d_map, map, nmap, hipMemcpyHostToDevice, h->stream));
             if (weighted) {
-                if ((rc2 = ensure_buffer(h, &h->d_wtab, &h->d_wtab_bytes, nwt))) return rc2;
+                if ((rc2 = h->d_wtab.reserve(h, nwt))) return rc2;
                 HIPCHK(h, hipMemcpyAsync(h->d_wtab, w, nwt, hipMemcpyHostToDevice, h->stream));
             }
             uploaded = true;
@@ -1503,7 +1504,7 @@ int bootstrap_weighted_impl(pf_handle* h, const uint8_t* idx, int B, int N, int 
 int launch_site_moments(pf_handle* h, const float* d_map, int B, int P, int L, float* d_se, float* d_prof) {
     const size_t per = pfm::part_count(1, P, L) * sizeof(double);
     const int nbc = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(B, 65535), ((size_t)64 << 20) / per));
-    int rc = ensure_buffer(h, &h->d_mpart, &h->d_mpart_bytes, (size_t)nbc * per);
+    int rc = h->d_mpart.reserve(h, (size_t)nbc * per);
     for (int b0 = 0; b0 < B && !rc; b0 += nbc)
         rc = launch_on_stream(h, K_SITE_MOMENTS, "k_site_moments", [&] {
             return pfm::launch_site_moments(h->stream, d_map + (size_t)b0 * P * L, std::min(nbc, B - b0), P, L, h->d_mpart,
@@ -1544,7 +1545,7 @@ int forward_sitemap_device(pf_handle* h, const F64Path* f, const uint8_t* d_idx,
         cb = chunk_batch(h, B, P, L, map_per);
         if ((rc = make_room(h, false, chunk_bytes(h, cb, P, L)))) return rc;
     }
-    if (!d_map && (rc = ensure_buffer(h, &h->d_smap, &h->d_smap_bytes, (size_t)cb * map_per))) return rc;
+    if (!d_map && (rc = h->d_smap.reserve(h, (size_t)cb * map_per))) return rc;
     for (int b0 = 0; b0 < B; b0 += cb) {
         const int nb = std::min(cb, B - b0);
         float* dm = d_map ? d_map + (size_t)b0 * P * L : h->d_smap;
@@ -1578,11 +1579,11 @@ int site_host_impl(pf_handle* h, const uint8_t* idx, int B, int N, int L, float*
     if ((rc = check_residues(h, idx, nidx))) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     const size_t nout = (size_t)B * P * sizeof(float), nprof = (size_t)B * L * sizeof(float);
-    if ((rc = ensure_buffer(h, &h->d_idx, &h->d_idx_bytes, nidx))) return rc;
-    if ((rc = ensure_buffer(h, &h->d_out, &h->d_out_bytes, nout))) return rc;
+    if ((rc = h->d_idx.reserve(h, nidx))) return rc;
+    if ((rc = h->d_out.reserve(h, nout))) return rc;
     if (!map) {
-        if ((rc = ensure_buffer(h, &h->d_se, &h->d_se_bytes, nout))) return rc;
-        if ((rc = ensure_buffer(h, &h->d_prof, &h->d_prof_bytes, nprof))) return rc;
+        if ((rc = h->d_se.reserve(h, nout))) return rc;
+        if ((rc = h->d_prof.reserve(h, nprof))) return rc;
     }
     HIPCHK(h, hipMemcpyAsync(h->d_idx, idx, nidx, hipMemcpyHostToDevice, h->stream));
     const F64Path* f = f64_path_of(h, N, L);
@@ -1695,8 +1696,8 @@ struct TaxonCuts {
     int upload(const uint8_t* idx, const int32_t* table, size_t table_bytes) {
         const size_t nidx = (size_t)B * N * L;
         HIPCHK(h, hipSetDevice(h->device));
-        int rc = ensure_buffer(h, &h->d_idx, &h->d_idx_bytes, nidx);
-        if (rc || (rc = ensure_buffer(h, &h->d_map, &h->d_map_bytes, table_bytes))) return rc;
+        int rc = h->d_idx.reserve(h, nidx);
+        if (rc || (rc = h->d_map.reserve(h, table_bytes))) return rc;
         HIPCHK(h, hipMemcpyAsync(h->d_idx, idx, nidx, hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipMemcpyAsync(h->d_map, table, table_bytes, hipMemcpyHostToDevice, h->stream));
         return PF_OK;
@@ -1713,13 +1714,10 @@ struct TaxonCuts {
                                        }, nullptr, h->d_idx + (size_t)b0 * N * L);
         return !rc && reduce && h->rechecked != before ? up(h->d_out, dst, (size_t)S * M * (M - 1) / 2) : rc;
     }
-    struct Span { float** p; size_t stride; };                  // `stride` floats for every current source
-    int carve(std::initializer_list<Span> spans) {
-        size_t total = 0;
-        for (const Span& s : spans) total += nb * s.stride;
-        if (const int rc = ensure_buffer(h, &h->d_sub, &h->d_sub_bytes, total * sizeof(float))) return rc;
-        float* at = h->d_sub;
-        for (const Span& s : spans) { *s.p = at; at += nb * s.stride; }
+    int carve(std::initializer_list<pfspan::FloatSpan> spans) {          // {pointer, floats for every current source}
+        auto list = [&](auto& v) { pfspan::float_spans(v, spans, (size_t)nb); };
+        if (const int rc = h->d_sub.reserve(h, pfspan::measure(list))) return rc;
+        pfspan::carve(h->d_sub, list);
         return PF_OK;
     }
     int copy(float* dst, const float* src, size_t stride, hipMemcpyKind kind) {         // the current sources' floats
@@ -1853,7 +1851,7 @@ int place_impl(pf_handle* h, const uint8_t* idx, int B, int M, int L, int Q, flo
 
 // ---- tiled inference (pf_forward_tiled, pf_tile_combine_device; pf_tile.hip.h, pf_tile_host.h) ----
 
-// The plan of (N, M) in h->tiled_plan and its two tables on the device - offset int64 [S + 1], then bounds int32 [G + 1] -
+// The plan of (N, M) in h->tiled_plan and its two tables on the device (h->tiled_tab),
 // rebuilt only when (N, M) changes.  The stream is drained first: the upload of the previous tables may still be reading
 // the host vectors.  The caller has checked M >= 2 and N > M.
 int ensure_tiled_plan(pf_handle* h, int N, int M) {
@@ -1866,11 +1864,15 @@ int ensure_tiled_plan(pf_handle* h, int N, int M) {
         return fail(h, PF_ENOMEM, "out of host memory for the tiling plan of N=%d, M=%d", N, M);
     }
     if (!ok) return fail(h, PF_EINVAL, "tiling needs 2 <= M < N (got N=%d, M=%d)", N, M);
-    const size_t noff = p.offset.size() * sizeof(int64_t), nbound = p.bounds.size() * sizeof(int32_t);
-    int rc = ensure_buffer(h, &h->d_tiled_tab, &h->d_tiled_tab_bytes, noff + nbound);
+    pftile::Tables& t = h->tiled_tab;
+    auto list = [&](auto& v) { pftile::table_arrays(v, t, p); };
+    int rc = h->d_tiled_tab.reserve(h, pfspan::measure(list));
     hipError_t e = hipSuccess;
-    if (!rc) e = hipMemcpyAsync(h->d_tiled_tab, p.offset.data(), noff, hipMemcpyHostToDevice, h->stream);
-    if (!rc && e == hipSuccess) e = hipMemcpyAsync(h->d_tiled_tab + noff, p.bounds.data(), nbound, hipMemcpyHostToDevice, h->stream);
+    if (!rc) {
+        pfspan::carve(h->d_tiled_tab, list);
+        e = hipMemcpyAsync(t.offset, p.offset.data(), p.offset.size() * sizeof(int64_t), hipMemcpyHostToDevice, h->stream);
+    }
+    if (!rc && e == hipSuccess) e = hipMemcpyAsync(t.bounds, p.bounds.data(), p.bounds.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream);
     if (rc || e != hipSuccess) {
         p.N = p.M = 0;                                   // (the tables on the device are not this plan's)
         return rc ? rc : fail(h, PF_EHIP, "upload of the tiling plan failed: %s", hipGetErrorString(e));
@@ -1881,10 +1883,8 @@ int ensure_tiled_plan(pf_handle* h, int N, int M) {
 // d_sets [B][T] -> d_out, d_spread [B][P_N] by the resident plan
 int launch_tile_combine(pf_handle* h, const float* d_sets, int B, float* d_out, float* d_spread) {
     const pftile::Plan& p = h->tiled_plan;
-    const int64_t* d_offset = reinterpret_cast<const int64_t*>(h->d_tiled_tab);
-    const int32_t* d_bounds = reinterpret_cast<const int32_t*>(h->d_tiled_tab + p.offset.size() * sizeof(int64_t));
     return launch_on_stream(h, K_TILE_COMBINE, "k_tile_combine", [&] {
-        return pftile::launch_tile_combine(h->stream, d_sets, d_bounds, d_offset, B, p.N, p.G, p.T, d_out, d_spread);
+        return pftile::launch_tile_combine(h->stream, d_sets, h->tiled_tab.bounds, h->tiled_tab.offset, B, p.N, p.G, p.T, d_out, d_spread);
     });
 }
 
@@ -2010,7 +2010,7 @@ int check_tree_shape(pf_handle* h, const TreeSearch& t, int B, int N, int* chunk
 
 // the join sequences of nb <= chunk sources on device arrays, enqueued on h->stream
 int launch_nj_chunk(pf_handle* h, const float* d_preds, int nb, int N, int32_t* d_slots, double* d_lengths, uint8_t* d_flag) {
-    const int rc = ensure_buffer(h, &h->d_nj, &h->d_nj_bytes, (size_t)nb * pfnj::state_bytes(N));
+    const int rc = h->d_nj.reserve(h, (size_t)nb * pfnj::state_bytes(N));
     if (rc) return rc;
     h->cur = h->stream;
     const pfnj::Args a = pfnj::carve(h->d_nj, d_preds, nb, N, d_slots, d_lengths, d_flag);
@@ -2026,8 +2026,7 @@ int nj_device_impl(pf_handle* h, const float* d_preds, int B, int N, int32_t* d_
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     ++h->nj_calls;
-    // (chunks follow each other on the stream, so the next one may reuse the state)
-    if ((rc = ensure_buffer(h, &h->d_nj, &h->d_nj_bytes, (size_t)chunk * pfnj::state_bytes(N)))) return rc;
+    // (chunks follow each other on the stream, so the next one reuses the state launch_nj_chunk reserved for the first)
     const size_t PN = (size_t)N * (N - 1) / 2, T = (size_t)pfnj::table_len(N);
     for (int b0 = 0; b0 < B; b0 += chunk)
         if ((rc = launch_nj_chunk(h, d_preds + (size_t)b0 * PN, std::min(chunk, B - b0), N, d_slots + (size_t)b0 * T,
@@ -2044,24 +2043,20 @@ int nj_host_impl(pf_handle* h, const float* preds, int B, int N, int32_t* slots,
     HIPCHK(h, hipSetDevice(h->device));
     ++h->nj_calls;
     const size_t PN = (size_t)N * (N - 1) / 2, T = (size_t)pfnj::table_len(N);
-    // staging of one chunk: lengths double [chunk][T], preds float [chunk][PN], slots int32 [chunk][T], flag uint8 [chunk]
-    const size_t o_len = 0, o_preds = o_len + (size_t)chunk * T * sizeof(double), o_slots = o_preds + (size_t)chunk * PN * sizeof(float),
-                 o_flag = o_slots + (size_t)chunk * T * sizeof(int32_t);
-    if ((rc = ensure_buffer(h, &h->d_nj_io, &h->d_nj_io_bytes, o_flag + (size_t)chunk))) return rc;
-    double* d_len = reinterpret_cast<double*>(h->d_nj_io + o_len);
-    float* d_preds = reinterpret_cast<float*>(h->d_nj_io + o_preds);
-    int32_t* d_slots = reinterpret_cast<int32_t*>(h->d_nj_io + o_slots);
-    uint8_t* d_flag = reinterpret_cast<uint8_t*>(h->d_nj_io + o_flag);
+    pfnj::Staging io{};
+    auto list = [&](auto& v) { pfnj::staging_arrays(v, io, (size_t)chunk, N); };
+    if ((rc = h->d_nj_io.reserve(h, pfspan::measure(list)))) return rc;
+    pfspan::carve(h->d_nj_io, list);
     for (int b0 = 0; b0 < B; b0 += chunk) {
         const size_t nb = (size_t)std::min(chunk, B - b0);
-        HIPCHK(h, hipMemcpyAsync(d_preds, preds + (size_t)b0 * PN, nb * PN * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(io.preds, preds + (size_t)b0 * PN, nb * PN * sizeof(float), hipMemcpyHostToDevice, h->stream));
         // (a flagged source's table is unspecified, not uninitialised)
-        HIPCHK(h, hipMemsetAsync(d_len, 0, nb * T * sizeof(double), h->stream));
-        HIPCHK(h, hipMemsetAsync(d_slots, 0, nb * T * sizeof(int32_t), h->stream));
-        if ((rc = launch_nj_chunk(h, d_preds, (int)nb, N, d_slots, d_len, d_flag))) return rc;
-        HIPCHK(h, hipMemcpyAsync(lengths + (size_t)b0 * T, d_len, nb * T * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(slots + (size_t)b0 * T, d_slots, nb * T * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(flag + b0, d_flag, nb, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemsetAsync(io.lengths, 0, nb * T * sizeof(double), h->stream));
+        HIPCHK(h, hipMemsetAsync(io.slots, 0, nb * T * sizeof(int32_t), h->stream));
+        if ((rc = launch_nj_chunk(h, io.preds, (int)nb, N, io.slots, io.lengths, io.flag))) return rc;
+        HIPCHK(h, hipMemcpyAsync(lengths + (size_t)b0 * T, io.lengths, nb * T * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(slots + (size_t)b0 * T, io.slots, nb * T * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(flag + b0, io.flag, nb, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
     return PF_OK;
@@ -2087,7 +2082,7 @@ int bme_chunk(pf_handle* h, bool spr, const float* d_preds, const int32_t* start
               int32_t* steps, double* tree_length, uint8_t* status) {
     const size_t b = (size_t)nb, T = (size_t)pfnj::table_len(N), nodes = (size_t)pfbme::nodes_of(N), rows = (size_t)pfbme::rows_of(N),
                  root = (size_t)pfbme::root_of(N);
-    int rc = ensure_buffer(h, &h->d_bme, &h->d_bme_bytes, b * (spr ? pfbme::spr_state_bytes(N) : pfbme::state_bytes(N)));
+    int rc = h->d_bme.reserve(h, b * (spr ? pfbme::spr_state_bytes(N) : pfbme::state_bytes(N)));
     if (rc) return rc;
     h->cur = h->stream;
     pfbme::SprArgs s{};                                  // (balanced NNI: s.b alone)
@@ -2174,23 +2169,27 @@ int bme_impl(pf_handle* h, bool spr, bool device, const float* preds, const int3
     HIPCHK(h, hipSetDevice(h->device));
     try {
         const size_t PN = (size_t)N * (N - 1) / 2, T = (size_t)pfnj::table_len(N), b = (size_t)B;
-        std::vector<int32_t> h_start, h_slots, h_steps;
-        std::vector<double> h_len, h_tl;
-        std::vector<uint8_t> h_st;
+        // The device form mirrors the caller's six arrays on the host, one list of {host, device, bytes} for both directions:
+        // the start tables come down before the search, the five outputs go up after it.
+        struct Mirror { void* host; void* device; size_t bytes; };
+        std::vector<Mirror> mir;
+        pfnj::Allocate own;
+        auto mirror = [&](auto* p, size_t count) {
+            auto* const dev = p;
+            if (device) { own(p, count); mir.push_back({p, dev, count * sizeof(*p)}); }
+            return p;
+        };
+        const int32_t* st_in = mirror(const_cast<int32_t*>(start), b * T);
+        int32_t *o_slots = mirror(slots, b * T), *o_steps = mirror(steps, b);
+        double *o_len = mirror(lengths, b * T), *o_tl = mirror(tree_length, b);
+        uint8_t* o_st = mirror(status, b);
         if (device) {
-            h_start.resize(b * T); h_slots.resize(b * T); h_steps.resize(b); h_len.resize(b * T); h_tl.resize(b); h_st.resize(b);
-            HIPCHK(h, hipMemcpyAsync(h_start.data(), start, b * T * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipMemcpyAsync(mir[0].host, mir[0].device, mir[0].bytes, hipMemcpyDeviceToHost, h->stream));
             HIPCHK(h, hipStreamSynchronize(h->stream));
         }
-        const int32_t* st_in = device ? h_start.data() : start;
         if ((rc = check_bme_starts(h, st_in, B, N))) return rc;
         ++(spr ? h->spr_calls : h->bme_calls);
-        int32_t* o_slots = device ? h_slots.data() : slots;
-        double* o_len = device ? h_len.data() : lengths;
-        int32_t* o_steps = device ? h_steps.data() : steps;
-        double* o_tl = device ? h_tl.data() : tree_length;
-        uint8_t* o_st = device ? h_st.data() : status;
-        if (!device && (rc = ensure_buffer(h, &h->d_bme_preds, &h->d_bme_preds_bytes, (size_t)chunk * PN * sizeof(float)))) return rc;
+        if (!device && (rc = h->d_bme_preds.reserve(h, (size_t)chunk * PN * sizeof(float)))) return rc;
         for (int b0 = 0; b0 < B; b0 += chunk) {
             const int nb = std::min(chunk, B - b0);
             const float* d_preds = preds + (size_t)b0 * PN;
@@ -2203,11 +2202,7 @@ int bme_impl(pf_handle* h, bool spr, bool device, const float* preds, const int3
                 return rc;
         }
         if (device) {
-            HIPCHK(h, hipMemcpyAsync(slots, h_slots.data(), b * T * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-            HIPCHK(h, hipMemcpyAsync(lengths, h_len.data(), b * T * sizeof(double), hipMemcpyHostToDevice, h->stream));
-            HIPCHK(h, hipMemcpyAsync(steps, h_steps.data(), b * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-            HIPCHK(h, hipMemcpyAsync(tree_length, h_tl.data(), b * sizeof(double), hipMemcpyHostToDevice, h->stream));
-            HIPCHK(h, hipMemcpyAsync(status, h_st.data(), b, hipMemcpyHostToDevice, h->stream));
+            for (size_t i = 1; i < mir.size(); ++i) HIPCHK(h, hipMemcpyAsync(mir[i].device, mir[i].host, mir[i].bytes, hipMemcpyHostToDevice, h->stream));
             HIPCHK(h, hipStreamSynchronize(h->stream));
         }
     } catch (const std::bad_alloc&) { return fail(h, PF_ENOMEM, "out of host memory for the tables of N=%d sequences", N); }
@@ -2250,9 +2245,9 @@ int plan_supports(pf_handle* h, int B, int R, int N, int* nb, int* rc) {
 // all chunks of a call on device arrays, enqueued on h->stream
 int supports_launch(pf_handle* h, const int32_t* d_ref, const int32_t* d_rep, const uint8_t* d_flag, int B, int R, int N, int nb, int rc,
                     int32_t* d_count, int64_t* d_transfer, int32_t* d_depth, uint8_t* d_status) {
-    int rc2 = ensure_buffer(h, &h->d_sup, &h->d_sup_bytes, (size_t)nb * pfsup::state_bytes(N, rc));
+    int rc2 = h->d_sup.reserve(h, (size_t)nb * pfsup::state_bytes(N, rc));
     if (rc2) return rc2;
-    if ((rc2 = ensure_buffer(h, &h->d_sup_bad, &h->d_sup_bad_bytes, (size_t)B * ((size_t)R + 1)))) return rc2;
+    if ((rc2 = h->d_sup_bad.reserve(h, (size_t)B * ((size_t)R + 1)))) return rc2;
     h->cur = h->stream;
     HIPCHK(h, hipMemsetAsync(h->d_sup_bad, 0, (size_t)B * ((size_t)R + 1), h->stream));
     pfsup::Args a{};
@@ -2298,24 +2293,19 @@ int supports_host_impl(pf_handle* h, const int32_t* ref, const int32_t* rep, con
     } catch (const std::bad_alloc&) { return fail(h, PF_ENOMEM, "out of host memory for the tables of N=%d sequences", N); }
     HIPCHK(h, hipSetDevice(h->device));
     ++h->sup_calls;
-    // staging of the whole call: transfer int64 [B][S], ref int32 [B][T], rep int32 [B][R][T], count, depth int32 [B][S],
-    // flag uint8 [B][R], status uint8 [B]
-    const size_t o_tr = 0, o_ref = o_tr + b * S * sizeof(int64_t), o_rep = o_ref + b * T * sizeof(int32_t),
-                 o_cnt = o_rep + b * r * T * sizeof(int32_t), o_dep = o_cnt + b * S * sizeof(int32_t), o_flag = o_dep + b * S * sizeof(int32_t),
-                 o_st = o_flag + b * r, end = o_st + b;
-    if ((rc2 = ensure_buffer(h, &h->d_sup_io, &h->d_sup_io_bytes, end))) return rc2;
-    char* io = h->d_sup_io;
-    HIPCHK(h, hipMemcpyAsync(io + o_ref, ref, b * T * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(io + o_rep, rep, b * r * T * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    if (flag) HIPCHK(h, hipMemcpyAsync(io + o_flag, flag, b * r, hipMemcpyHostToDevice, h->stream));
-    if ((rc2 = supports_launch(h, reinterpret_cast<int32_t*>(io + o_ref), reinterpret_cast<int32_t*>(io + o_rep),
-                               flag ? reinterpret_cast<uint8_t*>(io + o_flag) : nullptr, B, R, N, nb, rc, reinterpret_cast<int32_t*>(io + o_cnt),
-                               reinterpret_cast<int64_t*>(io + o_tr), reinterpret_cast<int32_t*>(io + o_dep), reinterpret_cast<uint8_t*>(io + o_st))))
+    pfsup::Staging io{};
+    auto list = [&](auto& v) { pfsup::staging_arrays(v, io, b, r, N); };
+    if ((rc2 = h->d_sup_io.reserve(h, pfspan::measure(list)))) return rc2;
+    pfspan::carve(h->d_sup_io, list);
+    HIPCHK(h, hipMemcpyAsync(io.ref, ref, b * T * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(io.rep, rep, b * r * T * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    if (flag) HIPCHK(h, hipMemcpyAsync(io.flag, flag, b * r, hipMemcpyHostToDevice, h->stream));
+    if ((rc2 = supports_launch(h, io.ref, io.rep, flag ? io.flag : nullptr, B, R, N, nb, rc, io.count, io.transfer, io.depth, io.status)))
         return rc2;
-    HIPCHK(h, hipMemcpyAsync(count, io + o_cnt, b * S * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(transfer, io + o_tr, b * S * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(depth, io + o_dep, b * S * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(status, io + o_st, b, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(count, io.count, b * S * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(transfer, io.transfer, b * S * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(depth, io.depth, b * S * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(status, io.status, b, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return PF_OK;
 }
@@ -2453,34 +2443,10 @@ int pf_destroy(pf_handle_t* h) {
     for (auto& s : h->pending) { hipEventDestroy(s.a); hipEventDestroy(s.b); }
     for (auto e : h->free_events) hipEventDestroy(e);
     for (void* p : h->owned) hipFree(p);
-    if (h->pair_i) hipFree(h->pair_i);
-    if (h->pair_j) hipFree(h->pair_j);
-    if (h->ws) hipFree(h->ws);
-    if (h->ws2) hipFree(h->ws2);
-    if (h->wsp) hipFree(h->wsp);
-    if (h->stream2) { hipStreamSynchronize(h->stream2); hipStreamDestroy(h->stream2); }
+    for (DeviceBuffer* b : h->buffers) b->release();
+    if (h->stream2) hipStreamDestroy(h->stream2);
     if (h->ev_fork) hipEventDestroy(h->ev_fork);
     if (h->ev_join) hipEventDestroy(h->ev_join);
-    if (h->d_idx) hipFree(h->d_idx);
-    if (h->d_out) hipFree(h->d_out);
-    if (h->d_rep) hipFree(h->d_rep);
-    if (h->d_map) hipFree(h->d_map);
-    if (h->d_smap) hipFree(h->d_smap);
-    if (h->d_mpart) hipFree(h->d_mpart);
-    if (h->d_se) hipFree(h->d_se);
-    if (h->d_prof) hipFree(h->d_prof);
-    if (h->d_sub) hipFree(h->d_sub);
-    if (h->d_tiled_tab) hipFree(h->d_tiled_tab);
-    if (h->d_nj) hipFree(h->d_nj);
-    if (h->d_nj_io) hipFree(h->d_nj_io);
-    if (h->d_bme) hipFree(h->d_bme);
-    if (h->d_bme_preds) hipFree(h->d_bme_preds);
-    if (h->d_sup) hipFree(h->d_sup);
-    if (h->d_sup_bad) hipFree(h->d_sup_bad);
-    if (h->d_sup_io) hipFree(h->d_sup_io);
-    if (h->d_w) hipFree(h->d_w);
-    if (h->d_wst) hipFree(h->d_wst);
-    if (h->d_wtab) hipFree(h->d_wtab);
     if (h->stream) hipStreamDestroy(h->stream);
     if (h->bad_idx_host) hipHostFree(h->bad_idx_host);
     delete h;
@@ -3090,11 +3056,9 @@ struct pf_mha {
     pf_handle* h = nullptr;
     float* wfrag = nullptr;   // MHA_WTOTAL fragments: Wq, Wk, Wv, Wo as hi / lo
     float* bias = nullptr;    // [4][64]
-    char* ws = nullptr;
-    size_t ws_bytes = 0;
-    float* d_x = nullptr;     // staging for the host-buffer entry point
-    float* d_y = nullptr;
-    size_t d_xy_bytes = 0;
+    std::vector<DeviceBuffer*> buffers;
+    Buffer<char> ws{buffers};                     // pfspan::mha_arrays
+    Buffer<float> d_x{buffers}, d_y{buffers};     // staging for the host-buffer entry point
 };
 
 int pf_mha_create(pf_handle_t* h, const pf_mha_weights_t* w, pf_mha_t** out) {
@@ -3136,9 +3100,7 @@ int pf_mha_destroy(pf_mha_t* m) {
     hipSetDevice(m->h->device);
     hipStreamSynchronize(m->h->stream);
     hipFree(m->wfrag); hipFree(m->bias);
-    if (m->ws) hipFree(m->ws);
-    if (m->d_x) hipFree(m->d_x);
-    if (m->d_y) hipFree(m->d_y);
+    for (DeviceBuffer* b : m->buffers) b->release();
     delete m;
     return PF_OK;
 }
@@ -3153,21 +3115,11 @@ int pf_mha_forward_device(pf_mha_t* m, const float* d_x, int32_t B, int32_t R, i
         return fail(h, PF_EINVAL, "pf_mha_forward: B*R*C too large for one launch");
     const int rows = (int)rows64;
     HIPCHK(h, hipSetDevice(h->device));
-    const size_t qk_bytes = align_up((size_t)2 * rows * MHA_H * ntiles * 32 * 2 * 16, 256);
-    const size_t v_bytes = align_up((size_t)2 * rows * MHA_H * ntiles * 64 * 16, 256);
-    const size_t att_bytes = align_up((size_t)rows * C * E * 4, 256);
-    const size_t need = 2 * qk_bytes + v_bytes + att_bytes;
-    if (need > m->ws_bytes) {
-        if (m->ws) { HIPCHK(h, hipStreamSynchronize(h->stream)); hipFree(m->ws); m->ws = nullptr; m->ws_bytes = 0; }
-        HIPCHK(h, hipMalloc((void**)&m->ws, need));
-        m->ws_bytes = need;
-    }
     MhaArgs a;
+    auto list = [&](auto& v) { pfspan::mha_arrays(v, a.qp, a.kp, a.vp, a.att, (size_t)rows, (size_t)MHA_H, (size_t)ntiles, (size_t)C, (size_t)E); };
+    if (const int rc = m->ws.reserve(h, pfspan::measure(list, 256))) return rc;
+    pfspan::carve(m->ws, list, 256);
     a.x = d_x; a.y = d_y;
-    a.qp = (frag_t*)m->ws;
-    a.kp = (frag_t*)(m->ws + qk_bytes);
-    a.vp = (frag_t*)(m->ws + 2 * qk_bytes);
-    a.att = (float*)(m->ws + 2 * qk_bytes + v_bytes);
     a.wfrag = (const frag_t*)m->wfrag;
     a.bias = m->bias;
     a.rows = rows; a.C = C; a.ntiles = ntiles;
@@ -3201,18 +3153,10 @@ int pf_mha_forward(pf_mha_t* m, const float* x, int32_t B, int32_t R, int32_t C,
     if (B < 1 || R < 1 || C < 1) return fail(h, PF_EINVAL, "pf_mha_forward: need B, R, C >= 1, got %d, %d, %d", B, R, C);
     HIPCHK(h, hipSetDevice(h->device));
     const size_t bytes = (size_t)B * R * C * E * 4;
-    if (bytes > m->d_xy_bytes) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (m->d_x) hipFree(m->d_x);
-        if (m->d_y) hipFree(m->d_y);
-        m->d_x = m->d_y = nullptr; m->d_xy_bytes = 0;
-        HIPCHK(h, hipMalloc((void**)&m->d_x, bytes));
-        HIPCHK(h, hipMalloc((void**)&m->d_y, bytes));
-        m->d_xy_bytes = bytes;
-    }
+    int rc = m->d_x.reserve(h, bytes);
+    if (rc || (rc = m->d_y.reserve(h, bytes))) return rc;
     HIPCHK(h, hipMemcpyAsync(m->d_x, x, bytes, hipMemcpyHostToDevice, h->stream));
-    int rc = pf_mha_forward_device(m, m->d_x, B, R, C, m->d_y);
-    if (rc) return rc;
+    if ((rc = pf_mha_forward_device(m, m->d_x, B, R, C, m->d_y))) return rc;
     HIPCHK(h, hipMemcpyAsync(y, m->d_y, bytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return PF_OK;

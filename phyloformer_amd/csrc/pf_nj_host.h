@@ -14,17 +14,13 @@
 // overflows or produces a NaN, so the minimum of Q is the minimum of a total order on (value, a, b): any reduction order
 // gives np.argmin's first minimum in row-major order.
 //
-// Key and its minimum, and the three visitors of a state's list of arrays (Measure, Carve, Allocate), serve balanced NNI
-// and balanced SPR too (pf_bme_host.h).
+// Key and its minimum serve balanced NNI and balanced SPR too (pf_bme_host.h).
 #pragma once
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
-#include <initializer_list>
-#include <memory>
-#include <vector>
-
+#include "pf_spans.h"
 #include "pf_taxa_host.h"
 
 namespace pfnj {
@@ -263,43 +259,10 @@ PF_TAXA_HD inline void final_record(const Args& a, size_t src) {
     a.lengths[at + 2] = 0.5 * ((d[i * N + k] + d[j * N + k]) - d[i * N + j]);
 }
 
-// ---- the arrays of a state, listed once ------------------------------------------------------------------------------
-// A state's list (state_arrays here, pfbme::state_arrays, pfbme::spr_state_arrays) is the one place that names its
-// arrays: it calls v(pointer, elements) for every array of B sources, and v.flags(B, {pointers}) for the one-byte flags
-// of a source, which share one span of 8 bytes per source.  Three visitors drive it.  On the device every array starts
-// a span of its own, a multiple of 8 bytes long, so every span is 8-byte aligned in an 8-byte aligned workspace.  The
-// workspace of B sources is B * Measure's figure for one source, which bounds what Carve hands out for B: an array of
-// x bytes per source takes up8(B x) <= B up8(x).
-inline size_t up8(size_t x) { return (x + 7) / 8 * 8; }
-
-// the bytes of the spans
-struct Measure {
-    size_t bytes = 0;
-    template <class T> void operator()(T*&, size_t count) { bytes += up8(count * sizeof(T)); }
-    void flags(size_t B, std::initializer_list<uint8_t**>) { bytes += 8 * B; }
-};
-
-// spans of a device workspace, one after the other from `at`
-struct Carve {
-    char* at;
-    template <class T> void operator()(T*& p, size_t count) { p = reinterpret_cast<T*>(at); at += up8(count * sizeof(T)); }
-    void flags(size_t B, std::initializer_list<uint8_t**> list) {
-        size_t i = 0;
-        for (uint8_t** p : list) *p = reinterpret_cast<uint8_t*>(at) + B * i++;
-        at += 8 * B;
-    }
-};
-
-// The host's state: one zeroed, exactly sized allocation per array (flags included), so that a sanitizer build has its
-// red zones around every one of them.
-struct Allocate {
-    std::vector<std::unique_ptr<unsigned char[]>> owned;
-    template <class T> void operator()(T*& p, size_t count) {
-        owned.emplace_back(new unsigned char[count * sizeof(T)]());
-        p = reinterpret_cast<T*>(owned.back().get());
-    }
-    void flags(size_t B, std::initializer_list<uint8_t**> list) { for (uint8_t** p : list) (*this)(*p, B); }
-};
+// ---- the arrays of a state, listed once: state_arrays (pf_spans.h has the visitors); the staging: staging_arrays -------
+using pfspan::Measure;
+using pfspan::Carve;
+using pfspan::Allocate;
 
 // the scalars of `a`; the state besides the caller's arrays (preds, slots, lengths, flag) follows by state_arrays
 inline Args args_of(const float* preds, int N, int part_cap, int32_t* slots, double* lengths, uint8_t* flag) {
@@ -321,17 +284,25 @@ inline void state_arrays(V& v, Args& a, size_t B) {
 // bytes of one source's state on the device
 inline size_t state_bytes(int N) {
     Args a = args_of(nullptr, N, Q_GROUPS, nullptr, nullptr, nullptr);
-    Measure m;
-    state_arrays(m, a, 1);
-    return m.bytes;
+    return pfspan::measure([&](auto& v) { state_arrays(v, a, 1); });
 }
 
 // the state of B sources carved from `ws` (8-byte aligned, B * state_bytes(N) bytes)
 inline Args carve(char* ws, const float* preds, int B, int N, int32_t* slots, double* lengths, uint8_t* flag) {
     Args a = args_of(preds, N, Q_GROUPS, slots, lengths, flag);
-    Carve c{ws};
-    state_arrays(c, a, (size_t)B);
+    pfspan::carve(ws, [&](auto& v) { state_arrays(v, a, (size_t)B); });
     return a;
+}
+
+// The staging of one chunk of a host call (pf_nj_joins): what goes up and what comes down.
+struct Staging { double* lengths; float* preds; int32_t* slots; uint8_t* flag; };
+template <class V>
+inline void staging_arrays(V& v, Staging& s, size_t chunk, int N) {
+    const size_t T = (size_t)table_len(N), PN = (size_t)N * ((size_t)N - 1) / 2;
+    v(s.lengths, chunk * T);
+    v(s.preds, chunk * PN);
+    v(s.slots, chunk * T);
+    v(s.flag, chunk);
 }
 
 }  // namespace pfnj

@@ -102,12 +102,8 @@ __global__ __launch_bounds__(SUM_THREADS) void k_sup_sum(Args a, int first) {
 // The arrays of a chunk of nb sources with rc replicates each inside `base` (nb * state_bytes(N, rc) bytes at least)
 inline void carve(Args& a, char* base) {
     const size_t S = (size_t)a.N - 3, W = (size_t)words_of(a.N), trees = (size_t)a.nb * (size_t)(a.rc + 1);
-    auto up8 = [](size_t n) { return (n + 7) & ~(size_t)7; };
-    size_t at = 0;
-    a.bits = reinterpret_cast<uint64_t*>(base + at); at += trees * S * W * sizeof(uint64_t);
-    a.row = reinterpret_cast<int32_t*>(base + at);   at += up8(trees * (size_t)a.N * sizeof(int32_t));
-    a.sizes = reinterpret_cast<int32_t*>(base + at); at += up8((size_t)a.nb * S * sizeof(int32_t));
-    a.delta = reinterpret_cast<int32_t*>(base + at);
+    pfspan::Carve c{base};
+    c(a.bits, trees * S * W); c(a.row, trees * (size_t)a.N); c(a.sizes, (size_t)a.nb * S); c(a.delta, (size_t)a.nb * (size_t)a.rc * S);
 }
 
 // Asynchronous on `s`: one chunk (nb <= SUP_MAX_Y sources, rc <= SUP_MAX_Y replicates, N >= 4).  `first`: the chunk

@@ -15,6 +15,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "pf_spans.h"
 #include "pf_taxa_host.h"
 
 namespace pfsup {
@@ -55,6 +56,20 @@ struct Args {
     int b0, nb;                 // the chunk's sources b0 .. b0 + nb - 1
     int r0, rc;                 // and replicates r0 .. r0 + rc - 1
 };
+
+// The staging of a whole host call (pf_join_supports): the tables that go up and the results that come down.
+struct Staging { int64_t* transfer; int32_t *ref, *rep, *count, *depth; uint8_t *flag, *status; };
+template <class V>
+inline void staging_arrays(V& v, Staging& s, size_t B, size_t R, int N) {
+    const size_t T = (size_t)table_len(N), S = (size_t)N - 3;
+    v(s.transfer, B * S);
+    v(s.ref, B * T);
+    v(s.rep, B * R * T);
+    v(s.count, B * S);
+    v(s.depth, B * S);
+    v(s.flag, B * R);
+    v(s.status, B);
+}
 
 PF_TAXA_HD inline size_t tree_index(const Args& a, int src, int k) { return (size_t)src * (size_t)(a.rc + 1) + (size_t)k; }
 PF_TAXA_HD inline uint64_t* bits_of(const Args& a, int src, int k) {

@@ -82,6 +82,14 @@ struct Plan {
     }
 };
 
+// the plan's two tables on the device
+struct Tables { int64_t* offset = nullptr; int32_t* bounds = nullptr; };
+template <class V>
+inline void table_arrays(V& v, Tables& t, const Plan& p) {
+    v(t.offset, p.offset.size());
+    v(t.bounds, p.bounds.size());
+}
+
 // What k_tile_combine reads and writes (pf_tile.hip.h has the definitions of out and spread).
 struct CombineArgs {
     const float* sets;       // [B][T]

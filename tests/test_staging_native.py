@@ -1,0 +1,47 @@
+"""AddressSanitizer + UBSan build of the staging lists as a stand-alone program (``tests/native/pf_staging_main.cpp``,
+its own ``main``; nothing is loaded into Python).  What a host entry point carves from one grow-only device buffer - the
+staging of ``pf_nj_joins`` and ``pf_join_supports``, the two tables of the tiling plan, the float spans of leave-one-out
+and placement, the attention operator's workspace - is listed once and driven by the visitors of ``csrc/pf_spans.h``.
+The program checks, for every list and shape, that each array is aligned for its type, lies inside the measured total
+and is disjoint from the others, and that the total is the former offset chain's plus alignment padding only.  No GPU."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+needs_gxx = pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+
+# cases per list: N in {3, 4, 9, 65} x B in {1, 3} (x R in {1, 3}); supports start at N = 4; three tiling plans
+CASES = {"nj": 8, "loo": 8, "supports": 12, "place": 16, "mha": 16, "tiled": 3}
+
+
+@pytest.fixture(scope="module")
+def output(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("staging_native") / "pf_staging_main")
+    cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
+           "-Wall", "-Wextra", "-Werror", os.path.join(REPO, "tests", "native", "pf_staging_main.cpp"), "-o", exe]
+    res = subprocess.run(cmd, capture_output=True, text=True)
+    assert res.returncode == 0, res.stderr[-3000:]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    res = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=600)
+    tail = (res.stdout + res.stderr)[-4000:]
+    assert "AddressSanitizer" not in tail and "runtime error" not in tail, tail
+    return res
+
+
+@needs_gxx
+def test_every_staging_array_is_aligned_disjoint_and_inside_its_total(output):
+    assert output.returncode == 0 and "pf_staging_main: clean" in output.stdout, (output.stdout + output.stderr)[-4000:]
+
+
+@needs_gxx
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_every_shape_ran_and_grew_by_padding_only(output, name):
+    """Lines are ``<list> <N> <B or M> <R> <total> <former>``: 8 bytes per array at most (256 for the attention operator)."""
+    arrays = {"nj": 4, "loo": 4, "supports": 7, "place": 6, "mha": 4, "tiled": 2}[name]
+    rows = [line.split() for line in output.stdout.splitlines() if line.split()[:1] == [name]]
+    assert len(rows) == CASES[name]
+    for _, _n, _b, _r, total, former in rows:
+        assert 0 <= int(total) - int(former) <= arrays * (256 if name == "mha" else 8)
