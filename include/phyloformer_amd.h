@@ -461,6 +461,48 @@ int pf_join_supports_device(pf_handle_t* h, const int32_t* d_ref_slots, const in
 int pf_join_supports_host(const int32_t* ref_slots, const int32_t* rep_slots, const uint8_t* rep_flag, int32_t B, int32_t R, int32_t N,
                           int32_t* count, int64_t* transfer, int32_t* depth, uint8_t* status);
 
+/* ---- majority-rule consensus of replicate join tables, with split frequencies and mean lengths (additive to ABI 5) ----
+ *
+ * The tree the R replicate trees of a source agree on; every tree is a join table in pf_nj_joins' layout, T = 2 (N - 3)
+ * + 3 slots.  phyloformer_amd/consensus.py::join_consensus states the definition and DESIGN.md section 25 the device
+ * form.  The splits of a table are those of pf_join_supports (the side without sequence 0); c(s) is the number of
+ * unflagged replicates that contain s, and s is selected iff 100 c(s) > percent R, strictly.  The M <= N - 3 selected
+ * splits, pairwise disjoint or nested, are ordered by (size, lowest member) ascending.
+ *   rep_slots     int32  [B][R][T]       the replicate trees of every source
+ *   rep_lengths   double [B][R][T]|NULL  their branch lengths (NULL: split_length and leaf_length may be NULL too)
+ *   rep_flag      uint8  [B][R]|NULL     != 0: the replicate has no tree; it is never read, contains no split, counts in R
+ *   percent       50 .. 99               the threshold F
+ *   n_splits      int32  [B]             M
+ *   count, size   int32  [B][N - 3]      c and the number of sequences of selected split i; the first M valid, zeros beyond
+ *   parent        int32  [B][N - 3]      the least j > i whose split contains split i, -1: the root
+ *   split_length  double [B][N - 3]      the mean, over the replicates that contain split i in ascending order, of the
+ *                                        branch above its cluster there
+ *   leaf_parent   int32  [B][N]          the least j whose split holds leaf x, -1: the root (always for leaf 0)
+ *   leaf_length   double [B][N]          the mean of the leaf's branch over the unflagged replicates (0 where there is none)
+ *   status        uint8  [B]             0 ok; 1 an unflagged table of the source is no join table; 2 the hash table or the
+ *                                        selection failed (not for valid input) - every result of the source is then zero
+ * The sums run in a fixed order and hold no product: the results do not depend on B, on the chunking or on the entry
+ * point, bit for bit.  pf_join_consensus takes host arrays, validates every table that is read as pf_bme_nni validates a
+ * start table (PF_EINVAL) and is synchronous.  pf_join_consensus_device takes device arrays, is asynchronous on the
+ * handle's stream and validates in the kernel: a slot outside [0, N) or a join of a dead slot never indexes memory, the
+ * source gets status 1.  pf_join_consensus_host runs the same kernel bodies serially without a handle or a device, with
+ * the kernel's validation (status 1, no refusal).  Sources run side by side in chunks that fit "ws_limit_mb".  A source
+ * always runs whole: its splits are counted in a hash table whose slots point into the replicates' bitset tables, which
+ * therefore have to outlive the counting - chunking one source over replicates is out of scope.  Refused with PF_EINVAL
+ * before any device work: N < 4, N > 16384, B < 1, R < 1, R > 65535 or R (N - 3) > 2^29; percent outside 50 .. 99; NULL
+ * buffers (rep_lengths with its two outputs, and rep_flag, may be NULL); a source whose R bitset tables (about N^2 / 8
+ * bytes each), hash table (12 bytes per slot, at least 2 R (N - 3) slots) and [M][R] lengths exceed "ws_limit_mb" (the
+ * message names the bytes).  pf_profile_get("join_consensus") counts the calls of the two handle entry points. */
+int pf_join_consensus(pf_handle_t* h, const int32_t* rep_slots, const double* rep_lengths, const uint8_t* rep_flag, int32_t B, int32_t R,
+                      int32_t N, int32_t percent, int32_t* n_splits, int32_t* count, int32_t* size, int32_t* parent, double* split_length,
+                      int32_t* leaf_parent, double* leaf_length, uint8_t* status);
+int pf_join_consensus_device(pf_handle_t* h, const int32_t* d_rep_slots, const double* d_rep_lengths, const uint8_t* d_rep_flag, int32_t B,
+                             int32_t R, int32_t N, int32_t percent, int32_t* d_n_splits, int32_t* d_count, int32_t* d_size,
+                             int32_t* d_parent, double* d_split_length, int32_t* d_leaf_parent, double* d_leaf_length, uint8_t* d_status);
+int pf_join_consensus_host(const int32_t* rep_slots, const double* rep_lengths, const uint8_t* rep_flag, int32_t B, int32_t R, int32_t N,
+                           int32_t percent, int32_t* n_splits, int32_t* count, int32_t* size, int32_t* parent, double* split_length,
+                           int32_t* leaf_parent, double* leaf_length, uint8_t* status);
+
 /* ---- site weights: weighted forward, pattern compression, bootstrap on distinct sites (additive to ABI 5) ----
  *
  * Nothing in the network depends on a site's position, and every reduction over sites is a plain sum (the row-attention

@@ -123,14 +123,16 @@ class Bootstrap(Analysis):
             "<stem>.sup.nwk, the NJ tree of the alignment's distances with the percent of replicate "
             "trees that contain each internal branch's split (Felsenstein's proportion); with --tbe also "
             "<stem>.tbe.nwk, the same tree with the transfer bootstrap expectation; with --bootstrap-refined "
-            "the trees of --bme / --spr get their supports too; 0 (default) = off")
+            "the trees of --bme / --spr get their supports too; with --consensus [F] also <stem>.con.nwk, the "
+            "majority-rule consensus of the replicate trees; 0 (default) = off")
     refuses = ((SHARD_SITES, "every replicate would need its own collectives"),)
     call = "bootstrap"
 
-    def __init__(self, replicates: int, seed: int = 0, tbe: bool = False, refined: bool = False):
+    def __init__(self, replicates: int, seed: int = 0, tbe: bool = False, refined: bool = False, consensus: Optional[int] = None):
         self.replicates, self.seed = int(replicates), int(seed)
         self.tbe, self.refined = bool(tbe), bool(refined)
-        if self.tbe or self.refined:
+        self.consensus = None if consensus is None else int(consensus)      # the threshold in percent
+        if self.tbe or self.refined or self.consensus is not None:
             self.extend = self._extend
 
     @classmethod
@@ -150,6 +152,13 @@ class Bootstrap(Analysis):
                                  "<stem>.spr.sup.nwk, the refined tree with the percent of replicate trees - each "
                                  "replicate's NJ tree refined by the same search - that contain each branch's split (with "
                                  "--tbe also <stem>.bme.tbe.nwk / <stem>.spr.tbe.nwk); R more searches per file")
+        parser.add_argument("--consensus", nargs="?", type=int, const=50, default=None, metavar="F",
+                            help="with --bootstrap R: also write <stem>.con.nwk, the majority-rule consensus of the R "
+                                 "replicates' NJ trees: every split found in more than F percent of them (50 to 99, default "
+                                 "50; exactly half is not enough), nested into a multifurcating tree, each internal node "
+                                 "labelled with the percent of replicates that contain its split, branch lengths the means "
+                                 "over the replicates that have the branch; with --bootstrap-refined and --bme / --spr also "
+                                 "<stem>.bme.con.nwk / <stem>.spr.con.nwk, the consensus of the refined replicate trees")
 
     @classmethod
     def from_args(cls, args):
@@ -161,10 +170,16 @@ class Bootstrap(Analysis):
             raise ValueError("--bootstrap-refined counts over the replicates of --bootstrap: give --bootstrap R as well")
         if args.bootstrap_refined and not (args.bme or args.spr):
             raise ValueError("--bootstrap-refined supports the trees of --bme / --spr: give at least one of them as well")
-        return cls(args.bootstrap, args.seed, args.tbe, args.bootstrap_refined) if args.bootstrap else None
+        if args.consensus is not None and not args.bootstrap:
+            raise ValueError("--consensus is the consensus of the replicate trees of --bootstrap: give --bootstrap R as well")
+        if args.consensus is not None and not 50 <= args.consensus <= 99:
+            raise ValueError(f"--consensus takes a threshold of 50 to 99 percent (got {args.consensus})")
+        return cls(args.bootstrap, args.seed, args.tbe, args.bootstrap_refined, args.consensus) if args.bootstrap else None
 
     def stats(self):
         more = {"tbe": 0, "refined_supports": 0, "supports_device": 0, "supports_device_s": 0.0} if self.extend else {}
+        if self.consensus is not None:
+            more.update(consensus=0, consensus_device=0)
         return {"replicates": self.replicates, "bootstrap_s": 0.0, **more}
 
     def floats(self, shape):
@@ -198,10 +213,11 @@ class Bootstrap(Analysis):
         """On the GPU thread, behind ``follow``: what of the supports runs on the device.  From ``bme.BME_DEVICE_MIN`` /
         ``bme.SPR_DEVICE_MIN`` sequences on the NJ tables of all ``B (R + 1)`` trees of the sub-batch and their refinement
         (``Engine.nj_joins`` + ``Engine.bme_nni`` / ``bme_spr``), from ``supports.SUPPORT_DEVICE_MIN`` on the matching
-        (``Engine.join_supports``) of every kind whose tables are the device's (NJ's: joined there for it).  Returns the
-        columns ``(reps, tables)``, ``tables[b][kind]`` = ``(slots, lengths, rep_slots, rep_flag, results or None)`` or
-        absent: that kind of that file runs on its writer thread."""
-        from . import bme, supports
+        (``Engine.join_supports``) of every kind whose tables are the device's (NJ's: joined there for it), from
+        ``consensus.CONSENSUS_DEVICE_MIN`` on their ``--consensus`` (``Engine.join_consensus``).  Returns the
+        columns ``(reps, tables)``, ``tables[b][kind]`` = ``(slots, lengths, rep_slots, rep_flag, results or None,
+        rep_lengths, consensus or None)`` or absent: that kind of that file runs on its writer thread."""
+        from . import bme, consensus, supports
         B, R, n = len(preds), self.replicates, shape[0]
         tables = [{} for _ in range(B)]
 
@@ -210,7 +226,8 @@ class Bootstrap(Analysis):
         kinds = self.kinds(runner)
         refine = [k for k in kinds if k != "nj" and reaches(getattr(bme, runner.REFINEMENTS[k][3]))]
         match = reaches(supports.SUPPORT_DEVICE_MIN)
-        if not refine and not match:
+        agree = self.consensus is not None and reaches(consensus.CONSENSUS_DEVICE_MIN)
+        if not refine and not match and not agree:
             return reps, tables
         t0 = time.perf_counter()
         every = np.concatenate([preds[:, None, :], reps], axis=1).reshape(B * (R + 1), -1)       # own tree first
@@ -222,41 +239,46 @@ class Bootstrap(Analysis):
         for k in refine:
             slots, lengths, _steps, _length, status = getattr(engine, runner.REFINEMENTS[k][2])(every, start)
             made[k] = (slots, lengths, bad | (status == bme.NONFINITE))
-        matched = 0
+        matched = agreed = 0
         for k, (slots, lengths, flag) in made.items():
             slots, lengths, flag = (x.reshape(B, R + 1, *x.shape[1:]) for x in (slots, lengths, flag))
-            res = None
+            res = con = None
             if match:
                 ref = np.where(flag[:, :1], bme.caterpillar_slots(n)[None, :], slots[:, 0])       # (its result is not used)
                 res = engine.join_supports(ref, slots[:, 1:], flag[:, 1:])
+            if agree:
+                con = engine.join_consensus(slots[:, 1:], lengths[:, 1:], flag[:, 1:], self.consensus)
             for b in range(B):
                 if flag[b, 0]:
                     continue                                     # no tree of its own: the writer's plain text
-                tables[b][k] = (slots[b, 0], lengths[b, 0], slots[b, 1:], flag[b, 1:], None if res is None else tuple(x[b] for x in res[:3]))
+                tables[b][k] = (slots[b, 0], lengths[b, 0], slots[b, 1:], flag[b, 1:], None if res is None else tuple(x[b] for x in res[:3]),
+                                lengths[b, 1:], None if con is None else tuple(x[b] for x in con))
                 matched += res is not None
-        runner.book(supports_device=matched, supports_device_s=time.perf_counter() - t0)
+                agreed += con is not None
+        runner.book(supports_device=matched, supports_device_s=time.perf_counter() - t0, **({"consensus_device": agreed} if agree else {}))
         return reps, tables
 
     def _host_tables(self, runner, kind, pred, reps, n):
-        """One file's tables of one kind on a writer thread, by the host twins: ``(slots, lengths, rep_slots, rep_flag)``,
-        or None where the file's own distances are not finite."""
+        """One file's tables of one kind on a writer thread, by the host twins: ``(slots, lengths, rep_slots, rep_flag,
+        None, rep_lengths, None)`` (``_extend``'s layout); ``slots`` None where the file's own distances are not finite."""
         from . import bme, hostio, supports
         if not runner.native_io:
-            slots, lengths, rep_slots, rep_flag = supports.kind_tables(pred, reps, n, kind)
-            return None if slots is None else (slots, lengths, rep_slots, rep_flag)
+            slots, lengths, rep_slots, rep_flag, rep_lengths = supports.kind_tables(pred, reps, n, kind, with_lengths=True)
+            return (slots, lengths, rep_slots, rep_flag, None, rep_lengths, None)
         every = np.concatenate([np.asarray(pred, dtype=np.float32).reshape(1, -1), reps])
         slots, lengths, bad = hostio.nj_joins_host(every)
         if kind != "nj":
             start = np.where(bad[:, None], bme.caterpillar_slots(n)[None, :], slots)
             slots, lengths, _steps, _length, status = getattr(hostio, runner.REFINEMENTS[kind][2] + "_host")(every, start)
             bad = bad | (status == bme.NONFINITE)
-        return None if bad[0] else (slots[0], lengths[0], slots[1:], bad[1:])
+        return (None if bad[0] else slots[0], lengths[0], slots[1:], bad[1:], None, lengths[1:], None)
 
     def write_supports(self, runner, shape, rows):
         """Some files of a sub-batch on a writer thread: per kind of tree ``<stem>[.<kind>].sup.nwk`` and, with ``--tbe``,
         ``<stem>[.<kind>].tbe.nwk``.  Tables and results the GPU thread left are formatted; the others come from the host
-        twins first (the serial ``pf_join_supports_host``; with ``--python-io`` ``supports.py`` itself)."""
-        from . import hostio, supports
+        twins first (the serial ``pf_join_supports_host``; with ``--python-io`` ``supports.py`` itself).  With
+        ``--consensus`` also ``<stem>[.<kind>].con.nwk``, from the same replicate tables (``consensus.py``)."""
+        from . import consensus, hostio, supports
         n, R = shape[0], self.replicates
         for entry, pred, reps, given in rows:
             ids = entry.ids()
@@ -265,12 +287,12 @@ class Bootstrap(Analysis):
                 table = None
                 if n >= 4:
                     table = given.get(kind) or self._host_tables(runner, kind, pred, reps, n)
-                if table is None:       # no split, or no tree of the file's own distances: the kind's plain text
+                if table is None or table[0] is None:       # no split, or no tree of the file's own distances: the kind's plain text
                     text = self._nj_support(runner, pred, reps, ids) if kind == "nj" else runner.bme_tree(pred, ids, kind)[0]
                     texts = (text, text)
                 else:
                     slots, lengths, rep_slots, rep_flag = table[:4]
-                    res = table[4] if len(table) > 4 and table[4] is not None else None
+                    res = table[4]
                     if res is None and runner.native_io:
                         res = hostio.join_supports_host(slots, rep_slots, rep_flag)[:3]
                     elif res is None:
@@ -279,8 +301,25 @@ class Bootstrap(Analysis):
                 runner.put(entry.path, sup, texts[0])
                 if self.tbe:
                     runner.put(entry.path, tbe, texts[1])
+                if self.consensus is not None:
+                    runner.put(entry.path, consensus.SUFFIXES[kind], self._consensus_text(runner, table, ids))
         kinds = len(self.kinds(runner))
-        runner.book(tbe=len(rows) * kinds if self.tbe else 0, refined_supports=len(rows) * (kinds - 1))
+        runner.book(tbe=len(rows) * kinds if self.tbe else 0, refined_supports=len(rows) * (kinds - 1),
+                    **({"consensus": len(rows) * kinds} if self.consensus is not None else {}))
+
+    def _consensus_text(self, runner, table, ids):
+        """``<stem>[.<kind>].con.nwk`` of one file from its replicate tables (None: fewer than four sequences - the star):
+        the GPU thread's results where it left them, else the serial twin's, with ``--python-io`` the statement's."""
+        from . import consensus, hostio
+        n, R = len(ids), self.replicates
+        if table is None:
+            return consensus.newick_of_consensus(ids, consensus.star(n), R)
+        _slots, _lengths, rep_slots, rep_flag, _res, rep_lengths, con = table
+        if con is None and runner.native_io:
+            con = hostio.join_consensus_host(rep_slots, rep_lengths, rep_flag, self.consensus)
+        elif con is None:
+            con = consensus.join_consensus(rep_slots, n, rep_lengths, rep_flag, self.consensus)
+        return consensus.newick_of_consensus(ids, con, R)
 
     def jobs(self, runner, shape, part, preds, reps, tables=None):
         if tables is None:

@@ -26,6 +26,7 @@
 #include "../../include/phyloformer_amd.h"
 #include "pf_bme_host.h"
 #include "pf_support_host.h"
+#include "pf_consensus_host.h"
 
 namespace {
 
@@ -916,6 +917,48 @@ int pf_join_supports_host(const int32_t* ref_slots, const int32_t* rep_slots, co
         for (int32_t src = 0; src < B; ++src) {
             a.b0 = src;
             pfsup::serial_chunk(a, tile.data(), true);
+        }
+        return PF_OK;
+    } catch (...) { return PF_ENOMEM; }
+}
+
+// Majority-rule consensus without a device: the bodies of pf_consensus.hip.h's kernels run
+// serially, one source at a time - the same integers and the same doubles as pf_join_consensus.  Tables are checked by
+// the bodies themselves, as pf_join_consensus_device's are: a source with a table that is no join table gets status 1
+// and zeros.  Twin of phyloformer_amd/consensus.py::join_consensus.
+int pf_join_consensus_host(const int32_t* rep_slots, const double* rep_lengths, const uint8_t* rep_flag, int32_t B, int32_t R, int32_t N,
+                           int32_t percent, int32_t* n_splits, int32_t* count, int32_t* size, int32_t* parent, double* split_length,
+                           int32_t* leaf_parent, double* leaf_length, uint8_t* status) {
+    if (!rep_slots || !n_splits || !count || !size || !parent || !leaf_parent || !status || (rep_lengths && (!split_length || !leaf_length)) ||
+        B < 1 || R < 1 || N < 4 || N > pfbme::MAX_N || percent < 50 || percent > 99 || (int64_t)R * ((int64_t)N - 3) > pfcon::MAX_ENTRIES)
+        return PF_EINVAL;
+    const size_t T = (size_t)pfsup::table_len(N), S = (size_t)N - 3, W = (size_t)pfsup::words_of(N), b = (size_t)B, r = (size_t)R;
+    size_t total = 0;
+    if (__builtin_mul_overflow(b * r, T * sizeof(double), &total)) return PF_EINVAL;
+    try {
+        pfcon::Args a{};
+        a.rep_slots = rep_slots; a.rep_lengths = rep_lengths; a.rep_flag = rep_flag;
+        a.n_splits = n_splits; a.count = count; a.size = size; a.parent = parent; a.leaf_parent = leaf_parent;
+        a.split_length = split_length; a.leaf_length = leaf_length; a.status = status;
+        a.N = N; a.R = R; a.percent = percent; a.nb = 1;
+        a.cap = pfcon::capacity_of((int64_t)(r * S));
+        std::fill(n_splits, n_splits + b, 0);
+        std::fill(count, count + b * S, 0);
+        std::fill(size, size + b * S, 0);
+        std::fill(parent, parent + b * S, 0);
+        std::fill(leaf_parent, leaf_parent + b * (size_t)N, 0);
+        if (rep_lengths) { std::fill(split_length, split_length + b * S, 0.0); std::fill(leaf_length, leaf_length + b * (size_t)N, 0.0); }
+        // the state of one source, reused from source to source
+        std::vector<unsigned char> state(pfcon::state_bytes(N, R, rep_lengths != nullptr));
+        std::vector<uint64_t> tile((size_t)pfcon::TILE * W);
+        pfspan::Carve c{reinterpret_cast<char*>(state.data())};
+        pfcon::state_arrays(c, a, 1, r, N, (size_t)a.cap, rep_lengths != nullptr);
+        char *ones = reinterpret_cast<char*>(a.slot_of), *zeros = reinterpret_cast<char*>(a.tally);
+        for (int32_t src = 0; src < B; ++src) {
+            a.b0 = src;
+            std::fill(ones, zeros, (char)0xff);
+            std::fill(zeros, c.at, (char)0);
+            pfcon::serial_source(a, 0, tile.data());
         }
         return PF_OK;
     } catch (...) { return PF_ENOMEM; }

@@ -47,6 +47,7 @@
 #include "pf_nj.hip.h"
 #include "pf_bme.hip.h"
 #include "pf_support.hip.h"
+#include "pf_consensus.hip.h"
 #include "pf_weights.hip.h"
 #include "pf_weights_host.h"
 #include "pf_host_prep.h"
@@ -269,6 +270,10 @@ struct pf_handle {
     Buffer<char> d_sup{buffers}, d_sup_io{buffers};
     Buffer<uint8_t> d_sup_bad{buffers};
     int64_t sup_calls = 0;       // calls since the last pf_profile_reset ("join_supports")
+    // pf_join_consensus / pf_join_consensus_device (grow-only): the state of one chunk of sources (pf_consensus.hip.h:
+    // carve) and the staging of the host entry point's tables, lengths and results
+    Buffer<char> d_con{buffers}, d_con_io{buffers};
+    int64_t con_calls = 0;       // calls since the last pf_profile_reset ("join_consensus")
     // weighted forwards (grow-only): the weight rows of a host call or of one chunk of derived alignments, what
     // k_weight_sums made of a call's rows ([..][4], pf_weights.hip.h), and the weight table of pf_forward_sites_weighted
     Buffer<float> d_w{buffers}, d_wst{buffers}, d_wtab{buffers};
@@ -2310,6 +2315,127 @@ int supports_host_impl(pf_handle* h, const int32_t* ref, const int32_t* rep, con
     return PF_OK;
 }
 
+// ---- majority-rule consensus of replicate join tables (pf_join_consensus, pf_join_consensus_device; pf_consensus.hip.h,
+// DESIGN.md section 25) ----
+
+static_assert(pfbme::MAX_N <= 64 * pfcon::MAX_W, "k_con_nest keeps TILE splits of MAX_W words in LDS");
+// (state_bytes: the least a call needs - a source of one replicate; the plan below sizes a source of R)
+const TreeSearch CON_SEARCH{"majority-rule consensus", pfbme::MAX_N, pfcon::min_state_bytes, pfcon::CON_MAX_Y,
+                            "the bitset table of one replicate and its hash table"};
+
+// The chunks of a call: `nb` whole sources side by side.  A source always runs whole - the owners' bitsets must outlive
+// the counting -, so one whose R tables, hash table and [M][R] lengths exceed the workspace limit is refused.
+int plan_consensus(pf_handle* h, int B, int R, int N, int percent, int* nb) {
+    int chunk = 0;
+    const int rc0 = check_tree_shape(h, CON_SEARCH, B, N, &chunk);
+    if (rc0) return rc0;
+    if (N < 4) return fail(h, PF_EINVAL, "a consensus needs N >= 4 sequences (got %d): a tree of 3 has no split", N);
+    if (R < 1) return fail(h, PF_EINVAL, "a consensus needs R >= 1 replicates (got %d)", R);
+    if (percent < 50 || percent > 99) return fail(h, PF_EINVAL, "the consensus threshold is a percent from 50 to 99 (got %d)", percent);
+    size_t n = 0;
+    if (!mul_size((size_t)B, (size_t)R, (size_t)pfnj::table_len(N) * sizeof(double), &n))
+        return fail(h, PF_EINVAL, "B=%d sources of R=%d replicate tables overflow the address space", B, R);
+    if ((int64_t)R * ((int64_t)N - 3) > pfcon::MAX_ENTRIES || R > pfcon::CON_MAX_Y)
+        return fail(h, PF_EINVAL, "R=%d replicates of N=%d sequences are more than %d trees or %lld splits of one source", R, N,
+                    pfcon::CON_MAX_Y, (long long)pfcon::MAX_ENTRIES);
+    const size_t per = pfcon::state_bytes(N, R);
+    if ((int64_t)per > h->ws_limit_bytes)
+        return fail(h, PF_EINVAL, "majority-rule consensus of R=%d replicates of N=%d sequences needs %zu bytes of state per source (its "
+                                  "R bitset tables, hash table and [M][R] lengths; a source runs whole), above the workspace limit of "
+                                  "%lld bytes (option ws_limit_mb)", R, N, per, (long long)h->ws_limit_bytes);
+    *nb = (int)std::min<size_t>((size_t)std::min(B, pfcon::CON_MAX_Y), (size_t)h->ws_limit_bytes / per);
+    return PF_OK;
+}
+
+struct ConsensusOut { int32_t *n_splits, *count, *size, *parent; double* split_length; int32_t* leaf_parent; double* leaf_length; uint8_t* status; };
+
+// all chunks of a call on device arrays, enqueued on h->stream
+int consensus_launch(pf_handle* h, const int32_t* d_rep, const double* d_lengths, const uint8_t* d_flag, int B, int R, int N, int percent,
+                     int nb, const ConsensusOut& o) {
+    const int rc2 = h->d_con.reserve(h, (size_t)nb * pfcon::state_bytes(N, R));
+    if (rc2) return rc2;
+    h->cur = h->stream;
+    const size_t S = (size_t)N - 3, b = (size_t)B;
+    // (the first M entries are written; beyond them, and for a source with a status, the results are zeros)
+    HIPCHK(h, hipMemsetAsync(o.n_splits, 0, b * sizeof(int32_t), h->stream));
+    HIPCHK(h, hipMemsetAsync(o.count, 0, b * S * sizeof(int32_t), h->stream));
+    HIPCHK(h, hipMemsetAsync(o.size, 0, b * S * sizeof(int32_t), h->stream));
+    HIPCHK(h, hipMemsetAsync(o.parent, 0, b * S * sizeof(int32_t), h->stream));
+    HIPCHK(h, hipMemsetAsync(o.leaf_parent, 0, b * (size_t)N * sizeof(int32_t), h->stream));
+    if (d_lengths) {
+        HIPCHK(h, hipMemsetAsync(o.split_length, 0, b * S * sizeof(double), h->stream));
+        HIPCHK(h, hipMemsetAsync(o.leaf_length, 0, b * (size_t)N * sizeof(double), h->stream));
+    }
+    pfcon::Args a{};
+    a.rep_slots = d_rep; a.rep_lengths = d_lengths; a.rep_flag = d_flag;
+    a.n_splits = o.n_splits; a.count = o.count; a.size = o.size; a.parent = o.parent; a.leaf_parent = o.leaf_parent;
+    a.split_length = o.split_length; a.leaf_length = o.leaf_length; a.status = o.status;
+    a.N = N; a.R = R; a.percent = percent;
+    a.cap = pfcon::capacity_of((int64_t)R * ((int64_t)N - 3));
+    // (chunks follow each other on the stream, so the next one may reuse the state)
+    for (int b0 = 0; b0 < B; b0 += nb) {
+        a.b0 = b0; a.nb = std::min(nb, B - b0);
+        const pfcon::Fill f = pfcon::carve(a, h->d_con);
+        const hipError_t e = pfcon::launch_chunk(h->stream, a, f);
+        if (e != hipSuccess) return fail(h, PF_EHIP, "k_con_* launch failed: %s", hipGetErrorString(e));
+    }
+    return PF_OK;
+}
+
+int consensus_device_impl(pf_handle* h, const int32_t* d_rep, const double* d_lengths, const uint8_t* d_flag, int B, int R, int N,
+                          int percent, const ConsensusOut& o) {
+    if (!d_rep || !o.n_splits || !o.count || !o.size || !o.parent || !o.leaf_parent || !o.status ||
+        (d_lengths && (!o.split_length || !o.leaf_length)))
+        return fail(h, PF_EINVAL, "null buffer");
+    int nb = 0;
+    const int rc2 = plan_consensus(h, B, R, N, percent, &nb);
+    if (rc2) return rc2;
+    HIPCHK(h, hipSetDevice(h->device));
+    ++h->con_calls;
+    return consensus_launch(h, d_rep, d_lengths, d_flag, B, R, N, percent, nb, o);
+}
+
+int consensus_host_impl(pf_handle* h, const int32_t* rep, const double* lengths, const uint8_t* flag, int B, int R, int N, int percent,
+                        const ConsensusOut& o) {
+    if (!rep || !o.n_splits || !o.count || !o.size || !o.parent || !o.leaf_parent || !o.status ||
+        (lengths && (!o.split_length || !o.leaf_length)))
+        return fail(h, PF_EINVAL, "null buffer");
+    int nb = 0;
+    int rc2 = plan_consensus(h, B, R, N, percent, &nb);
+    if (rc2) return rc2;
+    const size_t T = (size_t)pfnj::table_len(N), S = (size_t)N - 3, b = (size_t)B, r = (size_t)R;
+    try {
+        // validated as a start table is (a replicate passed with its flag is never read: its table may be anything)
+        std::vector<int32_t> parent((size_t)pfbme::nodes_of(N)), children((size_t)pfbme::nodes_of(N) * 3);
+        for (size_t i = 0; i < b * r; ++i)
+            if (!(flag && flag[i]) && !pfbme::tree_of_joins(rep + i * T, N, parent.data(), children.data()))
+                return fail(h, PF_EINVAL, "source %zu: replicate %zu is not a join table of N=%d sequences", i / r, i % r, N);
+    } catch (const std::bad_alloc&) { return fail(h, PF_ENOMEM, "out of host memory for the tables of N=%d sequences", N); }
+    HIPCHK(h, hipSetDevice(h->device));
+    ++h->con_calls;
+    pfcon::Staging io{};
+    auto list = [&](auto& v) { pfcon::staging_arrays(v, io, b, r, N, lengths != nullptr); };
+    if ((rc2 = h->d_con_io.reserve(h, pfspan::measure(list)))) return rc2;
+    pfspan::carve(h->d_con_io, list);
+    HIPCHK(h, hipMemcpyAsync(io.rep, rep, b * r * T * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    if (lengths) HIPCHK(h, hipMemcpyAsync(io.lengths, lengths, b * r * T * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (flag) HIPCHK(h, hipMemcpyAsync(io.flag, flag, b * r, hipMemcpyHostToDevice, h->stream));
+    const ConsensusOut d{io.n_splits, io.count, io.size, io.parent, io.split_length, io.leaf_parent, io.leaf_length, io.status};
+    if ((rc2 = consensus_launch(h, io.rep, lengths ? io.lengths : nullptr, flag ? io.flag : nullptr, B, R, N, percent, nb, d))) return rc2;
+    HIPCHK(h, hipMemcpyAsync(o.n_splits, io.n_splits, b * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(o.count, io.count, b * S * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(o.size, io.size, b * S * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(o.parent, io.parent, b * S * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(o.leaf_parent, io.leaf_parent, b * (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    if (lengths) {
+        HIPCHK(h, hipMemcpyAsync(o.split_length, io.split_length, b * S * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(o.leaf_length, io.leaf_length, b * (size_t)N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(h, hipMemcpyAsync(o.status, io.status, b, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return PF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2694,6 +2820,22 @@ int pf_join_supports_device(pf_handle_t* h, const int32_t* d_ref_slots, const in
     return supports_device_impl(h, d_ref_slots, d_rep_slots, d_rep_flag, B, R, N, d_count, d_transfer, d_depth, d_status);
 }
 
+int pf_join_consensus(pf_handle_t* h, const int32_t* rep_slots, const double* rep_lengths, const uint8_t* rep_flag, int32_t B, int32_t R,
+                      int32_t N, int32_t percent, int32_t* n_splits, int32_t* count, int32_t* size, int32_t* parent, double* split_length,
+                      int32_t* leaf_parent, double* leaf_length, uint8_t* status) {
+    if (!h) return PF_EINVAL;
+    return consensus_host_impl(h, rep_slots, rep_lengths, rep_flag, B, R, N, percent,
+                               ConsensusOut{n_splits, count, size, parent, split_length, leaf_parent, leaf_length, status});
+}
+
+int pf_join_consensus_device(pf_handle_t* h, const int32_t* d_rep_slots, const double* d_rep_lengths, const uint8_t* d_rep_flag, int32_t B,
+                             int32_t R, int32_t N, int32_t percent, int32_t* d_n_splits, int32_t* d_count, int32_t* d_size,
+                             int32_t* d_parent, double* d_split_length, int32_t* d_leaf_parent, double* d_leaf_length, uint8_t* d_status) {
+    if (!h) return PF_EINVAL;
+    return consensus_device_impl(h, d_rep_slots, d_rep_lengths, d_rep_flag, B, R, N, percent,
+                                 ConsensusOut{d_n_splits, d_count, d_size, d_parent, d_split_length, d_leaf_parent, d_leaf_length, d_status});
+}
+
 int pf_forward_device(pf_handle_t* h, const uint8_t* d_idx, int32_t B, int32_t N, int32_t L, float* d_out) {
     if (!h) return PF_EINVAL;
     return forward_device_impl(h, d_idx, B, N, 0, L, L, d_out);
@@ -2900,6 +3042,7 @@ int pf_profile_reset(pf_handle_t* h) {
     h->bme_calls = 0;
     h->spr_calls = 0;
     h->sup_calls = 0;
+    h->con_calls = 0;
     return PF_OK;
 }
 
@@ -2933,6 +3076,11 @@ int pf_profile_get(pf_handle_t* h, const char* kernel, int64_t* launches, double
     }
     if (std::strcmp(kernel, "join_supports") == 0) {    // pf_join_supports / pf_join_supports_device calls
         if (launches) *launches = h->sup_calls;
+        if (total_ms) *total_ms = 0.0;
+        return PF_OK;
+    }
+    if (std::strcmp(kernel, "join_consensus") == 0) {   // pf_join_consensus / pf_join_consensus_device calls
+        if (launches) *launches = h->con_calls;
         if (total_ms) *total_ms = 0.0;
         return PF_OK;
     }

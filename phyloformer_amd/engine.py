@@ -154,6 +154,10 @@ SIGNATURES = {
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "pf_join_supports_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p]),
+    "pf_join_consensus": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 8),
+    "pf_join_consensus_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] +
+                                 [C.c_void_p] * 8),
+    "pf_join_consensus_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 8),
     "pf_forward_weighted": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "pf_forward_weighted_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "pf_forward_sites_weighted": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
@@ -176,7 +180,8 @@ CALL_TIME_SYMBOLS = frozenset({"pf_forward_site_map", "pf_forward_site_map_devic
                                "pf_tile_bound", "pf_nj_joins", "pf_nj_joins_device", "pf_nj_format_joins_n", "pf_bme_nni",
                                "pf_bme_nni_device", "pf_bme_nni_host", "pf_bme_newick_n", "pf_bme_spr",
                                "pf_bme_spr_device", "pf_bme_spr_host", "pf_bme_spr_newick_n", "pf_join_supports",
-                               "pf_join_supports_device", "pf_join_supports_host"})
+                               "pf_join_supports_device", "pf_join_supports_host", "pf_join_consensus",
+                               "pf_join_consensus_device", "pf_join_consensus_host"})
 
 _lib: Optional[C.CDLL] = None
 
@@ -646,6 +651,37 @@ class Engine:
         self._check(self._optional("pf_join_supports_device")(
             self._h, C.c_void_p(d_ref_slots), C.c_void_p(d_rep_slots), C.c_void_p(d_rep_flag) if d_rep_flag else None, B, R, N,
             C.c_void_p(d_count), C.c_void_p(d_transfer), C.c_void_p(d_depth), C.c_void_p(d_status)))
+
+    # -- majority-rule consensus of replicate join tables -----------------------------------
+    def join_consensus(self, rep_slots: np.ndarray, rep_lengths: Optional[np.ndarray] = None,
+                       rep_flag: Optional[np.ndarray] = None, percent: int = 50):
+        """Majority-rule consensus on the GPU (``pf_join_consensus``): replicate join tables ``int32[B, R, T]``, their
+        lengths ``float64[B, R, T]`` or None, ``rep_flag bool[B, R]`` or None (``[R, T]`` / ``[R]`` drop ``B``) and the
+        threshold in percent (50 .. 99) → ``(n_splits int32[B], count, size, parent int32[B, N - 3], split_length
+        float64[B, N - 3] or None, leaf_parent int32[B, N], leaf_length float64[B, N] or None, status uint8[B])`` -
+        ``consensus.join_consensus``, the same integers and the same doubles, bit for bit, as
+        ``hostio.join_consensus_host``.  A table that is no join table is refused (``ValueError``)."""
+        from .hostio import consensus_arrays, consensus_outputs
+        fn = self._optional("pf_join_consensus")
+        rep, lengths, flag, (B, R, N), single = consensus_arrays(rep_slots, rep_lengths, rep_flag)
+        out, ptrs = consensus_outputs(B, N, lengths is not None)
+        self._check(fn(self._h, rep.ctypes.data, None if lengths is None else lengths.ctypes.data,
+                       None if flag is None else flag.ctypes.data, B, R, N, int(percent), *ptrs))
+        return tuple(None if x is None else x[0] for x in out) if single else out
+
+    def join_consensus_device(self, d_rep_slots: int, d_rep_lengths: int, d_rep_flag: int, B: int, R: int, N: int, percent: int,
+                              d_n_splits: int, d_count: int, d_size: int, d_parent: int, d_split_length: int, d_leaf_parent: int,
+                              d_leaf_length: int, d_status: int):
+        """``pf_join_consensus_device``: device ``rep_slots int32 [B][R][T]``, ``rep_lengths float64 [B][R][T]`` (0: none,
+        the two length outputs may then be 0), ``rep_flag uint8 [B][R]`` (0: none) → device ``n_splits int32 [B]``,
+        ``count`` / ``size`` / ``parent int32 [B][N - 3]``, ``split_length float64 [B][N - 3]``, ``leaf_parent int32 [B][N]``,
+        ``leaf_length float64 [B][N]``, ``status uint8 [B]`` (asynchronous on the handle's stream).  Tables are checked in
+        the kernel: status 1 and zeros, no refusal."""
+        opt = lambda p: C.c_void_p(p) if p else None
+        self._check(self._optional("pf_join_consensus_device")(
+            self._h, C.c_void_p(d_rep_slots), opt(d_rep_lengths), opt(d_rep_flag), B, R, N, int(percent), C.c_void_p(d_n_splits),
+            C.c_void_p(d_count), C.c_void_p(d_size), C.c_void_p(d_parent), opt(d_split_length), C.c_void_p(d_leaf_parent),
+            opt(d_leaf_length), C.c_void_p(d_status)))
 
     # -- site weights -----------------------------------------------------------------------
     @staticmethod

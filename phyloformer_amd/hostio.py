@@ -261,6 +261,52 @@ def join_supports_host(ref_slots, rep_slots, rep_flag=None):
     return tuple(x[0] for x in out) if single else out
 
 
+def consensus_arrays(rep_slots, rep_lengths, rep_flag):
+    """The arguments of the three ``pf_join_consensus`` entry points, checked: ``(rep int32[B, R, T], lengths float64[B, R,
+    T] or None, flag uint8[B, R] or None, (B, R, N), single)``."""
+    rep = np.ascontiguousarray(np.asarray(rep_slots, dtype=np.int32))
+    single = rep.ndim == 2
+    if single:
+        rep = rep[None]
+    if rep.ndim != 3:
+        raise ValueError(f"expected replicate tables [B, R, T] or [R, T], got {rep.shape}")
+    b, r, t = rep.shape
+    n = (t - 3) // 2 + 3
+    if t < 5 or 2 * (n - 3) + 3 != t or b < 1 or r < 1:
+        raise ValueError(f"{t} slots are not the join table of N >= 4 sequences, or no source or replicate ({b}, {r})")
+    lengths = flag = None
+    if rep_lengths is not None:
+        lengths = np.ascontiguousarray(np.asarray(rep_lengths, dtype=np.float64).reshape(b, r, t))
+    if rep_flag is not None:
+        flag = np.ascontiguousarray(np.asarray(rep_flag).astype(bool).astype(np.uint8).reshape(b, r))
+    return rep, lengths, flag, (b, r, n), single
+
+
+def consensus_outputs(b: int, n: int, lengths: bool):
+    """The results of a ``pf_join_consensus`` call, zeroed, and their addresses in the order of the C arguments."""
+    s = n - 3
+    out = (np.zeros(b, dtype=np.int32), np.zeros((b, s), dtype=np.int32), np.zeros((b, s), dtype=np.int32),
+           np.zeros((b, s), dtype=np.int32), np.zeros((b, s), dtype=np.float64) if lengths else None,
+           np.zeros((b, n), dtype=np.int32), np.zeros((b, n), dtype=np.float64) if lengths else None, np.zeros(b, dtype=np.uint8))
+    return out, [None if x is None else x.ctypes.data for x in out]
+
+
+def join_consensus_host(rep_slots, rep_lengths=None, rep_flag=None, percent: int = 50):
+    """``pf_join_consensus_host``: ``Engine.join_consensus`` without a device - the same bodies run serially, the integers
+    and (bit for bit) the doubles of ``consensus.join_consensus``; a source with a table that is no join table comes back
+    with status 1 and zeros.  ``ValueError`` for what the library refuses (``N < 4``, a threshold outside 50 .. 99)."""
+    lib = load_library()
+    rep, lengths, flag, (b, r, n), single = consensus_arrays(rep_slots, rep_lengths, rep_flag)
+    out, ptrs = consensus_outputs(b, n, lengths is not None)
+    rc = lib.pf_join_consensus_host(rep.ctypes.data, None if lengths is None else lengths.ctypes.data,
+                                    None if flag is None else flag.ctypes.data, b, r, n, int(percent), *ptrs)
+    if rc == -1:
+        raise ValueError(f"pf_join_consensus_host refused its arguments (a threshold of {percent} percent outside 50 .. 99?)")
+    if rc < 0:
+        raise RuntimeError(f"pf_join_consensus_host failed with status {rc}")
+    return tuple(None if x is None else x[0] for x in out) if single else out
+
+
 def _join_table(slots, lengths, n: int) -> Tuple[np.ndarray, np.ndarray]:
     """One source's join table (``Engine.nj_joins``) for ``n`` ids, checked: ``2 (n - 3) + 3`` slots in ``[0, n)``."""
     s = np.ascontiguousarray(np.asarray(slots, dtype=np.int32).reshape(-1))

@@ -653,7 +653,8 @@ def summarize(stats: dict, load_s: float = 0.0) -> dict:
             **({k: round(stats[k], 6) for k in ("bme", "bme_steps", "bme_device", "bme_device_s")} if "bme" in stats else {}),
             **({k: round(stats[k], 6) for k in ("spr", "spr_steps", "spr_device", "spr_device_s")} if "spr" in stats else {}),
             **({k: round(stats[k], 6) for k in ("tbe", "refined_supports", "supports_device", "supports_device_s")}
-               if "tbe" in stats else {})}
+               if "tbe" in stats else {}),
+            **({k: stats[k] for k in ("consensus", "consensus_device")} if "consensus" in stats else {})}
 
 
 def run_multi_device(script: str, argv: List[str], devices: Sequence[int], shard: str = "files") -> Tuple[int, List[dict]]:

@@ -99,12 +99,12 @@ SEARCHES = {"nj": None, "bme": "bme_nni", "spr": "bme_spr"}
 SUFFIXES = {"nj": ("sup.nwk", "tbe.nwk"), "bme": ("bme.sup.nwk", "bme.tbe.nwk"), "spr": ("spr.sup.nwk", "spr.tbe.nwk")}
 
 
-def kind_tables(preds: np.ndarray, reps: np.ndarray, n: int, kind: str):
+def kind_tables(preds: np.ndarray, reps: np.ndarray, n: int, kind: str, with_lengths: bool = False):
     """The Python twins' join tables behind the supports of one file's ``kind`` tree: ``(slots, lengths) [T]`` of the
     file's own tree (``preds [P]``), ``rep_slots int32 [R][T]`` and ``rep_flag bool [R]`` of its replicates' trees
     (``reps [R][P]``), each the NJ table refined by the kind's search.  A replicate with a non-finite distance is flagged
     (its table: zeros); one stopped at the move cap is used as it stands.  The file's own tree with non-finite distances
-    has no table: ``(None, None, ...)``."""
+    has no table: ``(None, None, ...)``.  ``with_lengths``: ``rep_lengths float64 [R][T]`` as a fifth result."""
     from . import bme
 
     def one(vec):
@@ -121,13 +121,14 @@ def kind_tables(preds: np.ndarray, reps: np.ndarray, n: int, kind: str):
     own = one(preds)
     t = 2 * (n - 3) + 3
     rep_slots, rep_flag = np.zeros((len(reps), t), dtype=np.int32), np.zeros(len(reps), dtype=bool)
+    rep_lengths = np.zeros((len(reps), t), dtype=np.float64)
     for r, rep in enumerate(reps):
         table = one(rep)
         if table is None:
             rep_flag[r] = True
         else:
-            rep_slots[r] = table[0]
-    return (own if own is not None else (None, None)) + (rep_slots, rep_flag)
+            rep_slots[r], rep_lengths[r] = table
+    return (own if own is not None else (None, None)) + (rep_slots, rep_flag) + ((rep_lengths,) if with_lengths else ())
 
 
 def support_newicks(preds: np.ndarray, reps: np.ndarray, ids: Sequence[str], kinds: Sequence[str] = ("nj",),
