@@ -377,6 +377,28 @@ int pf_nj_joins(pf_handle_t* h, const float* preds, int32_t B, int32_t N, int32_
 int pf_nj_joins_device(pf_handle_t* h, const float* d_preds, int32_t B, int32_t N, int32_t* d_slots, double* d_lengths,
                        uint8_t* d_nonfinite);
 
+/* ---- BIONJ on the device: FastME's default start tree (additive to ABI 5) ----
+ *
+ * The join sequence of BIONJ (Gascuel 1997; phyloformer_amd/bionj.py::bionj_joins states it) computed on the GPU, bit
+ * for bit: neighbour joining with a matrix of variances beside the distances and one weight lambda per join.  The pair
+ * of a join is the first of the scan (1,0), (2,0), (2,1), (3,0), ... of active positions whose q lies within 1e-9 of the
+ * exact minimum; the joined cluster takes the row of the later position; lambda's sum is numpy's pairwise sum over the
+ * active positions, by one thread (csrc/pf_bionj.hip.h, csrc/pf_bionj_host.h).  4 (N - 3) + 2
+ * launches per call on the handle's stream, no copy to the host and no synchronisation between them.
+ * Signatures, layouts and the meaning of nonfinite are pf_nj_joins': the table names a cluster by its smallest
+ * sequence (slot a < slot b; the new cluster takes slot a), so pf_nj_format_joins_n, pf_bme_nni, pf_bme_spr,
+ * pf_join_supports and pf_consensus_joins take it unchanged.  pf_bionj_joins takes host arrays and is synchronous;
+ * pf_bionj_joins_device takes device arrays and is asynchronous on the handle's stream; pf_bionj_joins_host runs the
+ * same kernel bodies serially without a handle or a device (a non-finite source's table is zeros there).  The state is
+ * 2 B N^2 doubles: sources run side by side in chunks that fit "ws_limit_mb"; one source always runs whole.  Refused
+ * with PF_EINVAL before any device work: N < 3, B < 1; NULL buffers; P_N >= 2^31; an N whose 2 N^2 doubles alone exceed
+ * "ws_limit_mb" (the message names the bytes).  pf_profile_get("bionj_joins") counts the calls of the two handle entry
+ * points. */
+int pf_bionj_joins(pf_handle_t* h, const float* preds, int32_t B, int32_t N, int32_t* slots, double* lengths, uint8_t* nonfinite);
+int pf_bionj_joins_device(pf_handle_t* h, const float* d_preds, int32_t B, int32_t N, int32_t* d_slots, double* d_lengths,
+                          uint8_t* d_nonfinite);
+int pf_bionj_joins_host(const float* preds, int32_t B, int32_t N, int32_t* slots, double* lengths, uint8_t* nonfinite);
+
 /* ---- balanced minimum-evolution NNI refinement of a join table (additive to ABI 5) ----
  *
  * Balanced nearest-neighbour interchanges (BNNI, FastME's -n B) from a start tree to a local optimum of the balanced
@@ -759,6 +781,12 @@ int64_t pf_bme_newick_n(const float* preds, int32_t n, const char* const* ids, c
  * pf_bme_spr_host in pf_bme_nni_host's place. */
 int64_t pf_bme_spr_newick_n(const float* preds, int32_t n, const char* const* ids, const int64_t* id_lens, int32_t clamp_negative,
                             char* out, int64_t cap);
+
+/* The Newick text of the BIONJ tree of preds (the CLI's --bionj; phyloformer_amd/bionj.py::bionj_newick_py writes the
+ * same bytes): pf_bionj_joins_host's table through pf_nj_format_joins_n's writer.  n < 3 or a NaN / infinity in preds:
+ * pf_nj_newick_n's text.  No device, no handle.  Sizing protocol as pf_format_phylip. */
+int64_t pf_bionj_newick_n(const float* preds, int32_t n, const char* const* ids, const int64_t* id_lens, int32_t clamp_negative,
+                          char* out, int64_t cap);
 
 /* ---- many files per call, on native threads (ABI 4; tree_paths: ABI 5) ---------------------------
  *

@@ -51,6 +51,12 @@ def build_parser():
                              "moves to a local optimum of the balanced minimum-evolution tree length, with balanced branch "
                              "lengths (the SPR search of FastME -s); independent of --bme (each writes its own file); every "
                              "other output keeps its bytes; the trees of windows, cuts and replicates stay NJ")
+    parser.add_argument("--bionj", action="store_true",
+                        help="with -t: also write <stem>.bionj.nwk, the BIONJ tree (Gascuel 1997) of the alignment's distances: "
+                             "FastME's default start tree (fastme -i x.phy); together with --bme and/or --spr also "
+                             "<stem>.bionj.bme.nwk / <stem>.bionj.spr.nwk, the same searches started from the BIONJ tree, as "
+                             "FastME starts them; every other output keeps its bytes; the trees of windows, cuts and "
+                             "replicates stay NJ")
     parser.add_argument("--device", type=int, default=0, help="HIP device ordinal (default 0)")
     parser.add_argument("--devices", default=None,
                         help="comma-separated HIP device ordinals: shard the files over these GPUs, "
@@ -94,6 +100,10 @@ def main(argv=None):
         parser.error("--spr refines the tree of --trees: give -t as well")
     if args.spr and args.shard == "sites":
         parser.error("--spr cannot be combined with --shard sites: the site-sharded runner writes NJ trees only")
+    if args.bionj and not args.trees:
+        parser.error("--bionj writes a tree beside that of --trees: give -t as well")
+    if args.bionj and args.shard == "sites":
+        parser.error("--bionj cannot be combined with --shard sites: the site-sharded runner writes NJ trees only")
 
     from phyloformer_amd import scheduler
 
@@ -170,7 +180,8 @@ def main(argv=None):
             e.set_option("two_streams", 0)
     runner = scheduler.DirectoryRunner(engines, out_dir, trees=args.trees, batch=args.batch,
                                        io_threads=args.io_threads, native_io=not args.python_io,
-                                       progress=bar.update if bar is not None else None, modes=modes, bme=args.bme, spr=args.spr)
+                                       progress=bar.update if bar is not None else None, modes=modes, bme=args.bme, spr=args.spr,
+                                       bionj=args.bionj)
     try:
         stats = runner.run(paths)
     finally:

@@ -25,6 +25,7 @@
 
 #include "../../include/phyloformer_amd.h"
 #include "pf_bme_host.h"
+#include "pf_bionj_host.h"
 #include "pf_support_host.h"
 #include "pf_consensus_host.h"
 
@@ -888,6 +889,54 @@ int pf_nj_joins_host_n(const float* preds, int32_t B, int32_t N, int32_t threads
         });
     } catch (...) { return PF_ENOMEM; }
     return failed ? PF_ENOMEM : PF_OK;
+}
+
+// BIONJ without a device: the bodies of pf_bionj.hip.h's kernels run serially, one source at a
+// time - the same tables as pf_bionj_joins, bit for bit.  Twin of phyloformer_amd/bionj.py::bionj_joins.  A source with
+// a NaN or an infinity is flagged and its table zeros.
+int pf_bionj_joins_host(const float* preds, int32_t B, int32_t N, int32_t* slots, double* lengths, uint8_t* nonfinite) {
+    if (!preds || !slots || !lengths || !nonfinite || B < 1 || N < 3) return PF_EINVAL;
+    const size_t P = (size_t)N * ((size_t)N - 1) / 2, T = (size_t)pfnj::table_len(N);
+    if (P >= ((size_t)1 << 31)) return PF_EINVAL;
+    try {
+        for (int32_t b = 0; b < B; ++b) {
+            int32_t* s = slots + (size_t)b * T;
+            double* l = lengths + (size_t)b * T;
+            std::fill(s, s + T, 0);
+            std::fill(l, l + T, 0.0);
+            pfbionj::run_serial(preds + (size_t)b * P, 1, N, s, l, nonfinite + b);
+        }
+        return PF_OK;
+    } catch (...) { return PF_ENOMEM; }
+}
+
+// preds [n(n-1)/2] -> Newick text of the BIONJ tree, as bionj.py::bionj_newick_py writes it: pf_bionj_joins_host's table
+// through pf_nj_format_joins_n's writer.  n < 3 or a NaN / infinity in preds: pf_nj_newick_n's text.
+int64_t pf_bionj_newick_n(const float* preds, int32_t n, const char* const* ids, const int64_t* id_lens, int32_t clamp_negative,
+                          char* out, int64_t cap) {
+    if (!preds || n < 1 || !ids || !id_lens || (!out && cap > 0)) return PF_EINVAL;
+    for (int32_t i = 0; i < n; ++i) if (id_lens[i] < 0) return PF_EINVAL;
+    try {
+        std::string text;
+        uint8_t bad = 1;
+        if (n >= 3) {
+            const size_t joins = (size_t)n - 3, len = 2 * joins + 3;
+            std::vector<int32_t> slots(len, 0);
+            std::vector<double> lengths(len, 0.0);
+            pfbionj::run_serial(preds, 1, n, slots.data(), lengths.data(), &bad);
+            if (!bad) {
+                NjTree t;
+                t.joins.reserve(joins);
+                for (size_t s = 0; s < joins; ++s) t.joins.push_back({slots[2 * s], slots[2 * s + 1], lengths[2 * s], lengths[2 * s + 1]});
+                t.i = slots[2 * joins]; t.j = slots[2 * joins + 1]; t.k = slots[2 * joins + 2];
+                t.li = lengths[2 * joins]; t.lj = lengths[2 * joins + 1]; t.lk = lengths[2 * joins + 2];
+                nj_format(t, n, ids, id_lens, clamp_negative != 0, nullptr, text);
+            }
+        }
+        if (bad) nj_newick(preds, n, ids, id_lens, clamp_negative != 0, text);
+        if (out && (int64_t)text.size() <= cap) memcpy(out, text.data(), text.size());
+        return (int64_t)text.size();
+    } catch (...) { return PF_ENOMEM; }
 }
 
 // Split supports without a device: the bodies of pf_support.hip.h's kernels run serially, one

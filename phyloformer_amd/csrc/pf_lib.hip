@@ -45,6 +45,7 @@
 #include "pf_place.hip.h"
 #include "pf_tile.hip.h"
 #include "pf_nj.hip.h"
+#include "pf_bionj.hip.h"
 #include "pf_bme.hip.h"
 #include "pf_support.hip.h"
 #include "pf_consensus.hip.h"
@@ -254,9 +255,11 @@ struct pf_handle {
     pftile::Tables tiled_tab;
     Buffer<char> d_tiled_tab{buffers};
     // pf_nj_joins / pf_nj_joins_device (grow-only): the state of one chunk of sources (d, r, partial minima, active
-    // slots), and the staging of a host call's chunk (lengths, preds, slots, flags)
+    // slots), and the staging of a host call's chunk (lengths, preds, slots, flags).  pf_bionj_joins / _device use both
+    // for their own state (pf_bionj_host.h: state_arrays) and the same staging: calls follow each other on the stream.
     Buffer<char> d_nj{buffers}, d_nj_io{buffers};
     int64_t nj_calls = 0;        // calls since the last pf_profile_reset ("nj_joins")
+    int64_t bionj_calls = 0;     // likewise pf_bionj_joins / pf_bionj_joins_device ("bionj_joins")
     // pf_bme_nni / pf_bme_nni_device (grow-only): the state of one chunk of sources (pf_bme.hip.h: carve) and the
     // staging of the host entry point's distances
     Buffer<char> d_bme{buffers};
@@ -1990,6 +1993,7 @@ int tiled_impl(pf_handle* h, const uint8_t* idx, int B, int N, int L, int M, flo
 // source, the sources of one launch, and what the refusal says the state holds.
 struct TreeSearch { const char* what; int max_n; size_t (*state_bytes)(int); int max_sources; const char* holds; };
 const TreeSearch NJ_SEARCH{"neighbour joining", 0, pfnj::state_bytes, pfnj::NJ_MAX_Y, "N^2 doubles"};
+const TreeSearch BIONJ_SEARCH{"BIONJ", 0, pfbionj::state_bytes, pfbionj::BIONJ_MAX_Y, "2 N^2 doubles"};
 const TreeSearch NNI_SEARCH{"balanced NNI", pfbme::MAX_N, pfbme::state_bytes, pfbme::BME_MAX_Z, "its table of 4N-6 subtrees"};
 const TreeSearch SPR_SEARCH{"balanced SPR", pfbme::MAX_N, pfbme::spr_state_bytes, pfbme::BME_MAX_Z,
                             "its table of 4N-6 subtrees and their pair table"};
@@ -2013,40 +2017,41 @@ int check_tree_shape(pf_handle* h, const TreeSearch& t, int B, int N, int* chunk
     return PF_OK;
 }
 
-// the join sequences of nb <= chunk sources on device arrays, enqueued on h->stream
-int launch_nj_chunk(pf_handle* h, const float* d_preds, int nb, int N, int32_t* d_slots, double* d_lengths, uint8_t* d_flag) {
-    const int rc = h->d_nj.reserve(h, (size_t)nb * pfnj::state_bytes(N));
+// the join sequences of nb <= chunk sources on device arrays, enqueued on h->stream: neighbour joining, or BIONJ
+// (pf_bionj.hip.h)
+int launch_nj_chunk(pf_handle* h, bool bionj, const float* d_preds, int nb, int N, int32_t* d_slots, double* d_lengths, uint8_t* d_flag) {
+    const int rc = h->d_nj.reserve(h, (size_t)nb * (bionj ? pfbionj::state_bytes(N) : pfnj::state_bytes(N)));
     if (rc) return rc;
     h->cur = h->stream;
-    const pfnj::Args a = pfnj::carve(h->d_nj, d_preds, nb, N, d_slots, d_lengths, d_flag);
-    const hipError_t e = pfnj::launch_nj(h->stream, a, nb);
-    if (e != hipSuccess) return fail(h, PF_EHIP, "k_nj_* launch failed: %s", hipGetErrorString(e));
+    const hipError_t e = bionj ? pfbionj::launch_bionj(h->stream, pfbionj::carve(h->d_nj, d_preds, nb, N, d_slots, d_lengths, d_flag), nb)
+                               : pfnj::launch_nj(h->stream, pfnj::carve(h->d_nj, d_preds, nb, N, d_slots, d_lengths, d_flag), nb);
+    if (e != hipSuccess) return fail(h, PF_EHIP, "%s launch failed: %s", bionj ? "k_bionj_*" : "k_nj_*", hipGetErrorString(e));
     return PF_OK;
 }
 
-int nj_device_impl(pf_handle* h, const float* d_preds, int B, int N, int32_t* d_slots, double* d_lengths, uint8_t* d_flag) {
+int nj_device_impl(pf_handle* h, bool bionj, const float* d_preds, int B, int N, int32_t* d_slots, double* d_lengths, uint8_t* d_flag) {
     if (!d_preds || !d_slots || !d_lengths || !d_flag) return fail(h, PF_EINVAL, "null buffer");
     int chunk = 0;
-    int rc = check_tree_shape(h, NJ_SEARCH, B, N, &chunk);
+    int rc = check_tree_shape(h, bionj ? BIONJ_SEARCH : NJ_SEARCH, B, N, &chunk);
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->device));
-    ++h->nj_calls;
+    ++(bionj ? h->bionj_calls : h->nj_calls);
     // (chunks follow each other on the stream, so the next one reuses the state launch_nj_chunk reserved for the first)
     const size_t PN = (size_t)N * (N - 1) / 2, T = (size_t)pfnj::table_len(N);
     for (int b0 = 0; b0 < B; b0 += chunk)
-        if ((rc = launch_nj_chunk(h, d_preds + (size_t)b0 * PN, std::min(chunk, B - b0), N, d_slots + (size_t)b0 * T,
+        if ((rc = launch_nj_chunk(h, bionj, d_preds + (size_t)b0 * PN, std::min(chunk, B - b0), N, d_slots + (size_t)b0 * T,
                                   d_lengths + (size_t)b0 * T, d_flag + b0)))
             return rc;
     return PF_OK;
 }
 
-int nj_host_impl(pf_handle* h, const float* preds, int B, int N, int32_t* slots, double* lengths, uint8_t* flag) {
+int nj_host_impl(pf_handle* h, bool bionj, const float* preds, int B, int N, int32_t* slots, double* lengths, uint8_t* flag) {
     if (!preds || !slots || !lengths || !flag) return fail(h, PF_EINVAL, "null buffer");
     int chunk = 0;
-    int rc = check_tree_shape(h, NJ_SEARCH, B, N, &chunk);
+    int rc = check_tree_shape(h, bionj ? BIONJ_SEARCH : NJ_SEARCH, B, N, &chunk);
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->device));
-    ++h->nj_calls;
+    ++(bionj ? h->bionj_calls : h->nj_calls);
     const size_t PN = (size_t)N * (N - 1) / 2, T = (size_t)pfnj::table_len(N);
     pfnj::Staging io{};
     auto list = [&](auto& v) { pfnj::staging_arrays(v, io, (size_t)chunk, N); };
@@ -2058,7 +2063,7 @@ int nj_host_impl(pf_handle* h, const float* preds, int B, int N, int32_t* slots,
         // (a flagged source's table is unspecified, not uninitialised)
         HIPCHK(h, hipMemsetAsync(io.lengths, 0, nb * T * sizeof(double), h->stream));
         HIPCHK(h, hipMemsetAsync(io.slots, 0, nb * T * sizeof(int32_t), h->stream));
-        if ((rc = launch_nj_chunk(h, io.preds, (int)nb, N, io.slots, io.lengths, io.flag))) return rc;
+        if ((rc = launch_nj_chunk(h, bionj, io.preds, (int)nb, N, io.slots, io.lengths, io.flag))) return rc;
         HIPCHK(h, hipMemcpyAsync(lengths + (size_t)b0 * T, io.lengths, nb * T * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipMemcpyAsync(slots + (size_t)b0 * T, io.slots, nb * T * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipMemcpyAsync(flag + b0, io.flag, nb, hipMemcpyDeviceToHost, h->stream));
@@ -2775,13 +2780,24 @@ int pf_tile_combine_device(pf_handle_t* h, const float* d_sets, int32_t B, int32
 
 int pf_nj_joins(pf_handle_t* h, const float* preds, int32_t B, int32_t N, int32_t* slots, double* lengths, uint8_t* nonfinite) {
     if (!h) return PF_EINVAL;
-    return nj_host_impl(h, preds, B, N, slots, lengths, nonfinite);
+    return nj_host_impl(h, false, preds, B, N, slots, lengths, nonfinite);
 }
 
 int pf_nj_joins_device(pf_handle_t* h, const float* d_preds, int32_t B, int32_t N, int32_t* d_slots, double* d_lengths,
                        uint8_t* d_nonfinite) {
     if (!h) return PF_EINVAL;
-    return nj_device_impl(h, d_preds, B, N, d_slots, d_lengths, d_nonfinite);
+    return nj_device_impl(h, false, d_preds, B, N, d_slots, d_lengths, d_nonfinite);
+}
+
+int pf_bionj_joins(pf_handle_t* h, const float* preds, int32_t B, int32_t N, int32_t* slots, double* lengths, uint8_t* nonfinite) {
+    if (!h) return PF_EINVAL;
+    return nj_host_impl(h, true, preds, B, N, slots, lengths, nonfinite);
+}
+
+int pf_bionj_joins_device(pf_handle_t* h, const float* d_preds, int32_t B, int32_t N, int32_t* d_slots, double* d_lengths,
+                          uint8_t* d_nonfinite) {
+    if (!h) return PF_EINVAL;
+    return nj_device_impl(h, true, d_preds, B, N, d_slots, d_lengths, d_nonfinite);
 }
 
 int pf_bme_nni(pf_handle_t* h, const float* preds, const int32_t* start_slots, int32_t B, int32_t N, int32_t* slots, double* lengths,
@@ -3039,6 +3055,7 @@ int pf_profile_reset(pf_handle_t* h) {
     h->coll_calls = 0;
     h->rechecked = 0;
     h->nj_calls = 0;
+    h->bionj_calls = 0;
     h->bme_calls = 0;
     h->spr_calls = 0;
     h->sup_calls = 0;
@@ -3061,6 +3078,11 @@ int pf_profile_get(pf_handle_t* h, const char* kernel, int64_t* launches, double
     }
     if (std::strcmp(kernel, "nj_joins") == 0) {         // pf_nj_joins / pf_nj_joins_device calls
         if (launches) *launches = h->nj_calls;
+        if (total_ms) *total_ms = 0.0;
+        return PF_OK;
+    }
+    if (std::strcmp(kernel, "bionj_joins") == 0) {      // pf_bionj_joins / pf_bionj_joins_device calls
+        if (launches) *launches = h->bionj_calls;
         if (total_ms) *total_ms = 0.0;
         return PF_OK;
     }

@@ -131,6 +131,10 @@ SIGNATURES = {
     "pf_tile_groups": (C.c_int, [C.c_int32, C.c_int32]),
     "pf_nj_joins": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pf_nj_joins_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pf_bionj_joins": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pf_bionj_joins_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pf_bionj_joins_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pf_bionj_newick_n": (C.c_int64, [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32, C.c_char_p, C.c_int64]),
     "pf_nj_format_joins_n": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32,
                                          C.c_char_p, C.c_int64]),
     "pf_tile_bound": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
@@ -181,7 +185,8 @@ CALL_TIME_SYMBOLS = frozenset({"pf_forward_site_map", "pf_forward_site_map_devic
                                "pf_bme_nni_device", "pf_bme_nni_host", "pf_bme_newick_n", "pf_bme_spr",
                                "pf_bme_spr_device", "pf_bme_spr_host", "pf_bme_spr_newick_n", "pf_join_supports",
                                "pf_join_supports_device", "pf_join_supports_host", "pf_join_consensus",
-                               "pf_join_consensus_device", "pf_join_consensus_host"})
+                               "pf_join_consensus_device", "pf_join_consensus_host", "pf_bionj_joins",
+                               "pf_bionj_joins_device", "pf_bionj_joins_host", "pf_bionj_newick_n"})
 
 _lib: Optional[C.CDLL] = None
 
@@ -545,7 +550,10 @@ class Engine:
         float64[B, T], nonfinite bool[B])``, ``T = 2 (N - 3) + 3`` (``[P_N]`` drops ``B``): the joins ``a, b`` / ``la, lb``
         of ``nj.nj_joins`` on the symmetric matrix of every source, then the trifurcation ``i, j, k`` / ``li, lj, lk`` - bit
         for bit.  A source with a NaN or an infinity is flagged and its table unspecified (use ``hostio.nj_newick``)."""
-        fn = self._optional("pf_nj_joins")
+        return self._joins("pf_nj_joins", preds)
+
+    def _joins(self, symbol: str, preds: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        fn = self._optional(symbol)
         p = np.ascontiguousarray(np.asarray(preds, dtype=np.float32))
         single = p.ndim == 1
         if single:
@@ -567,6 +575,19 @@ class Engine:
         [B][2 (N - 3) + 3]``, ``nonfinite uint8 [B]`` (asynchronous on the handle's stream)."""
         self._check(self._optional("pf_nj_joins_device")(self._h, C.c_void_p(d_preds), B, N, C.c_void_p(d_slots),
                                                          C.c_void_p(d_lengths), C.c_void_p(d_nonfinite)))
+
+    # -- BIONJ ------------------------------------------------------------------------------
+    def bionj_joins(self, preds: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """BIONJ on the GPU (``pf_bionj_joins``): arguments and results as ``nj_joins``'; the table is that of
+        ``bionj.bionj_joins`` on the symmetric matrix of every source - FastME's default start tree - bit for bit that of
+        ``hostio.bionj_joins_host``, and a start table for ``bme_nni`` / ``bme_spr``.  A source with a NaN or an infinity
+        is flagged and its table unspecified (use ``hostio.bionj_newick``)."""
+        return self._joins("pf_bionj_joins", preds)
+
+    def bionj_joins_device(self, d_preds: int, B: int, N: int, d_slots: int, d_lengths: int, d_nonfinite: int):
+        """``pf_bionj_joins_device``: ``nj_joins_device``'s arguments (asynchronous on the handle's stream)."""
+        self._check(self._optional("pf_bionj_joins_device")(self._h, C.c_void_p(d_preds), B, N, C.c_void_p(d_slots),
+                                                            C.c_void_p(d_lengths), C.c_void_p(d_nonfinite)))
 
     # -- balanced NNI refinement -------------------------------------------------------------
     def bme_nni(self, preds: np.ndarray, start_slots: np.ndarray):

@@ -135,6 +135,42 @@ def nj_newick(preds: np.ndarray, ids: Sequence[str], clamp_negative: bool = True
     return buf.raw[:w]
 
 
+def bionj_newick(preds: np.ndarray, ids: Sequence[str], clamp_negative: bool = True) -> bytes:
+    """``pf_bionj_newick_n``: distance vector ``[P]`` + ids → Newick text (utf-8 bytes) of the BIONJ tree (the CLI's
+    ``--bionj``) - byte-identical to ``bionj.bionj_newick_py``."""
+    lib = load_library()
+    n = len(ids)
+    p = np.ascontiguousarray(np.asarray(preds, dtype=np.float32).reshape(-1))
+    if p.size != n * (n - 1) // 2:
+        raise ValueError(f"expected {n * (n - 1) // 2} distances for {n} sequences, got {p.shape}")
+    enc = [s.encode("utf8") for s in ids]
+    arr = (C.c_char_p * n)(*enc)
+    lens = np.array([len(e) for e in enc], dtype=np.int64)
+    cap = int(lens.sum()) + 64 * max(n, 1) + 64                  # (as _refined_newick: one run, not two)
+    buf = C.create_string_buffer(cap)
+    w = lib.pf_bionj_newick_n(p.ctypes.data, n, arr, lens.ctypes.data, int(clamp_negative), buf, cap)
+    if w > cap:
+        buf = C.create_string_buffer(int(w))
+        w = lib.pf_bionj_newick_n(p.ctypes.data, n, arr, lens.ctypes.data, int(clamp_negative), buf, w)
+    if w < 0:
+        raise RuntimeError(f"pf_bionj_newick_n failed with status {w}")
+    return buf.raw[:w]
+
+
+def bionj_refined_newick(search: str, preds: np.ndarray, ids: Sequence[str], clamp_negative: bool = True) -> bytes:
+    """``<stem>.bionj.bme.nwk`` / ``<stem>.bionj.spr.nwk`` (``search`` = ``"bme"`` / ``"spr"``): ``pf_bionj_joins_host`` →
+    ``pf_bme_nni_host`` / ``pf_bme_spr_host`` → ``pf_nj_format_joins_n`` - byte-identical to
+    ``bionj.bionj_bme_newick_py`` / ``bionj.bionj_spr_newick_py``.  Fewer than three sequences or non-finite distances:
+    the NJ text."""
+    n = len(ids)
+    p = np.ascontiguousarray(np.asarray(preds, dtype=np.float32).reshape(-1))
+    if n < 3 or not np.isfinite(p).all():
+        return nj_newick(p, ids, clamp_negative)
+    start, _lengths, _flag = bionj_joins_host(p[None, :])
+    slots, lengths, _steps, _length, _status = (bme_nni_host if search == "bme" else bme_spr_host)(p[None, :], start)
+    return newick_of_joins(slots[0], lengths[0], ids, clamp_negative)
+
+
 def bme_newick(preds: np.ndarray, ids: Sequence[str], clamp_negative: bool = True, with_steps: bool = False):
     """``pf_bme_newick_n``: distance vector ``[P]`` + ids → Newick text (utf-8 bytes) of the neighbour-joining tree refined
     by balanced NNIs, with balanced branch lengths (the CLI's ``--bme``) - byte-identical to ``bme.bme_newick_py``.
@@ -220,6 +256,26 @@ def nj_joins_host(preds: np.ndarray, threads: int = 1):
     rc = lib.pf_nj_joins_host_n(p.ctypes.data, b, n, int(threads), slots.ctypes.data, lengths.ctypes.data, flag.ctypes.data)
     if rc < 0:
         raise RuntimeError(f"pf_nj_joins_host_n failed with status {rc}")
+    return slots, lengths, flag.astype(bool)
+
+
+def bionj_joins_host(preds: np.ndarray):
+    """``Engine.bionj_joins`` without a device (``pf_bionj_joins_host``): ``float32[B, P_N]`` → ``(slots int32[B, T],
+    lengths float64[B, T], nonfinite bool[B])``, the table of ``bionj.bionj_joins`` bit for bit; a flagged source's
+    table is zeros.  ``ValueError`` for what the library refuses."""
+    lib = load_library()
+    p = np.ascontiguousarray(np.asarray(preds, dtype=np.float32))
+    if p.ndim != 2 or p.shape[0] < 1:
+        raise ValueError(f"expected distances [B >= 1, P], got {p.shape}")
+    b = p.shape[0]
+    n = (1 + int(round((1 + 8 * p.shape[1]) ** 0.5))) // 2
+    if n * (n - 1) // 2 != p.shape[1] or n < 3:
+        raise ValueError(f"{p.shape[1]} distances are not the pairs of N >= 3 sequences")
+    t = 2 * (n - 3) + 3
+    slots, lengths, flag = np.zeros((b, t), dtype=np.int32), np.zeros((b, t), dtype=np.float64), np.zeros(b, dtype=np.uint8)
+    rc = lib.pf_bionj_joins_host(p.ctypes.data, b, n, slots.ctypes.data, lengths.ctypes.data, flag.ctypes.data)
+    if rc < 0:
+        raise RuntimeError(f"pf_bionj_joins_host failed with status {rc}")
     return slots, lengths, flag.astype(bool)
 
 

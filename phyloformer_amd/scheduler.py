@@ -154,7 +154,9 @@ class DirectoryRunner:
 
     def __init__(self, engine, out_dir: str, trees: bool = False, batch: int = 0,
                  io_threads: int = 4, native_io: bool = True, progress=None, modes: Sequence[Analysis] = (),
-                 bme: bool = False, spr: bool = False):
+                 bme: bool = False, spr: bool = False, bionj: bool = False):
+        if bionj and not trees:
+            raise ValueError("--bionj writes a tree beside that of --trees: give -t as well")
         if bme and not trees:
             raise ValueError("--bme refines the tree of --trees: give -t as well")
         if spr and not trees:
@@ -164,6 +166,9 @@ class DirectoryRunner:
         self.trees = trees
         self.bme = bme                # with --trees: <stem>.bme.nwk, the NJ tree refined by balanced NNIs, as well
         self.spr = spr                # with --trees: <stem>.spr.nwk, the NJ tree refined by balanced SPR moves, as well
+        # with --trees: <stem>.bionj.nwk, the BIONJ tree, as well - and with --bme / --spr <stem>.bionj.bme.nwk /
+        # <stem>.bionj.spr.nwk, the same searches started from it
+        self.bionj = bionj
         self.batch = batch            # 0 = auto per shape
         self.io_threads = max(1, io_threads)
         self.native_io = native_io
@@ -174,6 +179,8 @@ class DirectoryRunner:
             self.stats.update({"bme": 0, "bme_steps": 0, "bme_device": 0, "bme_device_s": 0.0})
         if spr:
             self.stats.update({"spr": 0, "spr_steps": 0, "spr_device": 0, "spr_device_s": 0.0})
+        if bionj:
+            self.stats.update({"bionj": 0, "bionj_device": 0, "bionj_device_s": 0.0})
         self.modes = list(modes)
         for m in self.modes:
             m.bind(self.modes)
@@ -265,6 +272,50 @@ class DirectoryRunner:
             moves += steps
         self.book(**{kind: len(group), f"{kind}_steps": moves})
 
+    def bionj_tree(self, vec: np.ndarray, ids: List[str], kind: Optional[str] = None):
+        """The text of the BIONJ tree of a distance vector (``--bionj``) - ``kind`` "bme" / "spr": of its balanced-NNI /
+        balanced-SPR refinement -, from the same side as ``nj``."""
+        if self.native_io:
+            from . import hostio
+            return hostio.bionj_newick(vec, ids) if kind is None else hostio.bionj_refined_newick(kind, vec, ids)
+        from . import bionj
+        return {None: bionj.bionj_newick_py, "bme": bionj.bionj_bme_newick_py, "spr": bionj.bionj_spr_newick_py}[kind](vec, ids)
+
+    def _bionj_device(self, engine, n: int, preds: np.ndarray, kinds: Sequence[str]) -> dict:
+        """On the GPU thread, for a launch of files with as many sequences as ``bionj.joins_on_device`` asks: every file's BIONJ
+        joins on the device and, from ``bme.BME_DEVICE_MIN`` / ``bme.SPR_DEVICE_MIN`` on, their refinements as
+        ``_bme_device`` runs them from the NJ start.  ``{kind: [(slots, lengths) per file, None for a file with a
+        non-finite distance (it keeps the host's path)]}``, ``kind`` None for the BIONJ tree itself; a kind that is
+        missing keeps the host's path for the whole launch."""
+        from . import bionj, bme
+        if not bionj.joins_on_device(n):
+            return {}
+        t0 = time.perf_counter()
+        start, start_lengths, nonfinite = engine.bionj_joins(preds)
+        nonfinite = np.asarray(nonfinite, dtype=bool)
+        out = {None: [None if bad else (s, l) for s, l, bad in zip(start, start_lengths, nonfinite)]}
+        start = np.where(nonfinite[:, None], bme.caterpillar_slots(n)[None, :], start)
+        for kind in kinds:
+            _native, _python, search, minimum = self.REFINEMENTS[kind]
+            minimum = getattr(bme, minimum)
+            if minimum is None or n < minimum:
+                continue
+            slots, lengths, _steps, _length, status = getattr(engine, search)(preds, start)
+            out[kind] = [None if bad or st == bme.NONFINITE else (s, l) for s, l, st, bad in zip(slots, lengths, status, nonfinite)]
+        self.book(bionj_device=sum(t is not None for t in out[None]), bionj_device_s=time.perf_counter() - t0)
+        return out
+
+    def _write_bionj(self, group: list, preds: np.ndarray, tables, kind: Optional[str] = None):
+        """``<stem>.bionj.nwk`` (``<stem>.bionj.bme.nwk``, ``<stem>.bionj.spr.nwk``) of some files of a launch, on a writer
+        thread: formatted from the device's table where there is one, joined (and refined) on the host where not."""
+        for k, (e, pred) in enumerate(zip(group, preds)):
+            ids = e.ids()
+            table = tables[k] if tables is not None else None
+            text = self.bionj_tree(pred, ids, kind) if table is None else self.newick_of_joins(table[0], table[1], ids)
+            self.put(e.path, "bionj.nwk" if kind is None else f"bionj.{kind}.nwk", text)
+        if kind is None:
+            self.book(bionj=len(group))
+
     def book(self, **amounts):
         """Add to the run's stats from inside a mode's own engine call (takes the runner's lock)."""
         with self._lock:
@@ -318,6 +369,14 @@ class DirectoryRunner:
             cap = self.writer_cap()
             submit([(self._write_bme, group[k::cap], preds[k::cap], None if tables is None else tables[k::cap], kind)
                     for k in range(min(cap, len(group)))])
+        if self.bionj:
+            kinds = [k for k, on in (("bme", self.bme), ("spr", self.spr)) if on]
+            device = self._bionj_device(engine, shape[0], preds, kinds)
+            cap = self.writer_cap()
+            for kind in [None] + kinds:
+                tables = device.get(kind)
+                submit([(self._write_bionj, group[k::cap], preds[k::cap], None if tables is None else tables[k::cap], kind)
+                        for k in range(min(cap, len(group)))])
         with self._lock:
             self.stats["forward_s"] += dt
             self.stats["launches"] += 1
@@ -652,6 +711,7 @@ def summarize(stats: dict, load_s: float = 0.0) -> dict:
             "windows": stats.get("windows", 0), "windows_s": round(stats.get("windows_s", 0.0), 6),
             **({k: round(stats[k], 6) for k in ("bme", "bme_steps", "bme_device", "bme_device_s")} if "bme" in stats else {}),
             **({k: round(stats[k], 6) for k in ("spr", "spr_steps", "spr_device", "spr_device_s")} if "spr" in stats else {}),
+            **({k: round(stats[k], 6) for k in ("bionj", "bionj_device", "bionj_device_s")} if "bionj" in stats else {}),
             **({k: round(stats[k], 6) for k in ("tbe", "refined_supports", "supports_device", "supports_device_s")}
                if "tbe" in stats else {}),
             **({k: stats[k] for k in ("consensus", "consensus_device")} if "consensus" in stats else {})}
