@@ -483,6 +483,38 @@ int pf_join_supports_device(pf_handle_t* h, const int32_t* d_ref_slots, const in
 int pf_join_supports_host(const int32_t* ref_slots, const int32_t* rep_slots, const uint8_t* rep_flag, int32_t B, int32_t R, int32_t N,
                           int32_t* count, int64_t* transfer, int32_t* depth, uint8_t* status);
 
+/* ---- per-taxon transfer counts: which sequences keep a branch from its support (additive to ABI 5) ----
+ *
+ * pf_join_supports, keeping WHICH replicate split is the closest to every reference split, and the sequences that have
+ * to move for it (Lemoine et al. 2018: the per-taxon companion of the transfer bootstrap, an instability score that
+ * singles out rogue taxa).  phyloformer_amd/supports.py::transfer_taxa states the definition and DESIGN.md section 27
+ * the device form.  With h_j, p and delta as above, m_j = min(h_j, N - h_j), side_j = 0 if h_j <= N - h_j else 1, and j*
+ * the j of the least (m_j, j).  If m_j* <= p - 1 the transfer set of (split t, replicate r) is X = s xor q_j*,
+ * complemented within the N sequences if side_j* = 1, and popcount(X) = delta.  Otherwise, or if the replicate is
+ * flagged, the pair is capped: nothing is attributed to any sequence.  The pair is used iff
+ * 100 delta <= cutoff_percent (p - 1); a capped pair is therefore used only at cutoff_percent = 100.
+ *   cutoff_percent  0 .. 100
+ *   count, transfer, depth, status    exactly pf_join_supports' results
+ *   moves         int64 [B][N]             the sum over t of branch_moves[t][x]
+ *   used          int32 [B][N - 3]         used replicates of split t
+ *   capped        int32 [B][N - 3]         used replicates that are capped
+ *   branch_moves  int32 [B][N - 3][N]|NULL used, uncapped replicates with sequence x in X
+ * At cutoff_percent = 100, sum_x branch_moves[t][x] + (p_t - 1) capped[t] = transfer[t].  A source with status 1 has
+ * zeros everywhere.  The three forms are pf_join_supports' (host arrays and PF_EINVAL for a table that is none; device
+ * arrays, asynchronous, validated in the kernel; serial without a handle), chunked as there with one more int32 per
+ * (replicate, split) of state; branch_moves is the caller's array and no part of the workspace.  Refusals are
+ * pf_join_supports' (the message names the bytes), and cutoff_percent outside 0 .. 100.
+ * pf_profile_get("join_transfers") counts the calls of the two handle entry points. */
+int pf_join_transfers(pf_handle_t* h, const int32_t* ref_slots, const int32_t* rep_slots, const uint8_t* rep_flag, int32_t B, int32_t R,
+                      int32_t N, int32_t cutoff_percent, int32_t* count, int64_t* transfer, int32_t* depth, int64_t* moves, int32_t* used,
+                      int32_t* capped, int32_t* branch_moves, uint8_t* status);
+int pf_join_transfers_device(pf_handle_t* h, const int32_t* d_ref_slots, const int32_t* d_rep_slots, const uint8_t* d_rep_flag, int32_t B,
+                             int32_t R, int32_t N, int32_t cutoff_percent, int32_t* d_count, int64_t* d_transfer, int32_t* d_depth,
+                             int64_t* d_moves, int32_t* d_used, int32_t* d_capped, int32_t* d_branch_moves, uint8_t* d_status);
+int pf_join_transfers_host(const int32_t* ref_slots, const int32_t* rep_slots, const uint8_t* rep_flag, int32_t B, int32_t R, int32_t N,
+                           int32_t cutoff_percent, int32_t* count, int64_t* transfer, int32_t* depth, int64_t* moves, int32_t* used,
+                           int32_t* capped, int32_t* branch_moves, uint8_t* status);
+
 /* ---- majority-rule consensus of replicate join tables, with split frequencies and mean lengths (additive to ABI 5) ----
  *
  * The tree the R replicate trees of a source agree on; every tree is a join table in pf_nj_joins' layout, T = 2 (N - 3)

@@ -124,15 +124,18 @@ class Bootstrap(Analysis):
             "trees that contain each internal branch's split (Felsenstein's proportion); with --tbe also "
             "<stem>.tbe.nwk, the same tree with the transfer bootstrap expectation; with --bootstrap-refined "
             "the trees of --bme / --spr get their supports too; with --consensus [F] also <stem>.con.nwk, the "
-            "majority-rule consensus of the replicate trees; 0 (default) = off")
+            "majority-rule consensus of the replicate trees; with --instability [C] also the per-sequence "
+            "transfer counts that single out rogue sequences; 0 (default) = off")
     refuses = ((SHARD_SITES, "every replicate would need its own collectives"),)
     call = "bootstrap"
 
-    def __init__(self, replicates: int, seed: int = 0, tbe: bool = False, refined: bool = False, consensus: Optional[int] = None):
+    def __init__(self, replicates: int, seed: int = 0, tbe: bool = False, refined: bool = False, consensus: Optional[int] = None,
+                 instability: Optional[int] = None):
         self.replicates, self.seed = int(replicates), int(seed)
         self.tbe, self.refined = bool(tbe), bool(refined)
         self.consensus = None if consensus is None else int(consensus)      # the threshold in percent
-        if self.tbe or self.refined or self.consensus is not None:
+        self.instability = None if instability is None else int(instability)      # the cutoff in percent
+        if self.tbe or self.refined or self.consensus is not None or self.instability is not None:
             self.extend = self._extend
 
     @classmethod
@@ -160,6 +163,17 @@ class Bootstrap(Analysis):
                                  "over the replicates that have the branch; with --bootstrap-refined and --bme / --spr also "
                                  "<stem>.bme.con.nwk / <stem>.spr.con.nwk, the consensus of the refined replicate trees")
 
+        parser.add_argument("--instability", nargs="?", type=int, const=30, default=None, metavar="C",
+                            help="with --bootstrap R: also write <stem>.instability.tsv, per sequence how often it is among "
+                                 "those that have to move for a branch of the tree to appear in a replicate tree (the "
+                                 "per-taxon companion of the transfer bootstrap, Lemoine et al. 2018: rogue sequences "
+                                 "collect the moves) and that count per thousand used (branch, replicate) pairs; "
+                                 "<stem>.branches.tsv, per branch its depth, supports, used and capped replicates and its "
+                                 "five most-moved sequences; and <stem>.branches.nwk, the tree labelled with the branch "
+                                 "numbers of that table.  A pair is used if its transfer distance is at most C percent "
+                                 "of the branch's depth - 1 (0 to 100, default 30: a far-away closest split says nothing "
+                                 "about single sequences); with --bootstrap-refined also <stem>.bme.* / <stem>.spr.*")
+
     @classmethod
     def from_args(cls, args):
         if args.bootstrap < 0:
@@ -174,12 +188,18 @@ class Bootstrap(Analysis):
             raise ValueError("--consensus is the consensus of the replicate trees of --bootstrap: give --bootstrap R as well")
         if args.consensus is not None and not 50 <= args.consensus <= 99:
             raise ValueError(f"--consensus takes a threshold of 50 to 99 percent (got {args.consensus})")
-        return cls(args.bootstrap, args.seed, args.tbe, args.bootstrap_refined, args.consensus) if args.bootstrap else None
+        if args.instability is not None and not args.bootstrap:
+            raise ValueError("--instability counts over the replicates of --bootstrap: give --bootstrap R as well")
+        if args.instability is not None and not 0 <= args.instability <= 100:
+            raise ValueError(f"--instability takes a cutoff of 0 to 100 percent (got {args.instability})")
+        return cls(args.bootstrap, args.seed, args.tbe, args.bootstrap_refined, args.consensus, args.instability) if args.bootstrap else None
 
     def stats(self):
         more = {"tbe": 0, "refined_supports": 0, "supports_device": 0, "supports_device_s": 0.0} if self.extend else {}
         if self.consensus is not None:
             more.update(consensus=0, consensus_device=0)
+        if self.instability is not None:
+            more.update(instability=0, transfers_device=0)
         return {"replicates": self.replicates, "bootstrap_s": 0.0, **more}
 
     def floats(self, shape):
@@ -214,7 +234,9 @@ class Bootstrap(Analysis):
         ``bme.SPR_DEVICE_MIN`` sequences on the NJ tables of all ``B (R + 1)`` trees of the sub-batch and their refinement
         (``Engine.nj_joins`` + ``Engine.bme_nni`` / ``bme_spr``), from ``supports.SUPPORT_DEVICE_MIN`` on the matching
         (``Engine.join_supports``) of every kind whose tables are the device's (NJ's: joined there for it), from
-        ``consensus.CONSENSUS_DEVICE_MIN`` on their ``--consensus`` (``Engine.join_consensus``).  Returns the
+        ``consensus.CONSENSUS_DEVICE_MIN`` on their ``--consensus`` (``Engine.join_consensus``).  With ``--instability``
+        the one ``Engine.join_transfers`` call, from ``supports.TRANSFER_DEVICE_MIN`` on, stands in ``join_supports``'
+        place - the matching never runs twice - and ``results`` has its seven arrays.  Returns the
         columns ``(reps, tables)``, ``tables[b][kind]`` = ``(slots, lengths, rep_slots, rep_flag, results or None,
         rep_lengths, consensus or None)`` or absent: that kind of that file runs on its writer thread."""
         from . import bme, consensus, supports
@@ -225,7 +247,8 @@ class Bootstrap(Analysis):
             return n >= 4 and minimum is not None and n >= minimum
         kinds = self.kinds(runner)
         refine = [k for k in kinds if k != "nj" and reaches(getattr(bme, runner.REFINEMENTS[k][3]))]
-        match = reaches(supports.SUPPORT_DEVICE_MIN)
+        moves = self.instability is not None
+        match = reaches(supports.TRANSFER_DEVICE_MIN if moves else supports.SUPPORT_DEVICE_MIN)
         agree = self.consensus is not None and reaches(consensus.CONSENSUS_DEVICE_MIN)
         if not refine and not match and not agree:
             return reps, tables
@@ -245,17 +268,19 @@ class Bootstrap(Analysis):
             res = con = None
             if match:
                 ref = np.where(flag[:, :1], bme.caterpillar_slots(n)[None, :], slots[:, 0])       # (its result is not used)
-                res = engine.join_supports(ref, slots[:, 1:], flag[:, 1:])
+                res = (engine.join_transfers(ref, slots[:, 1:], flag[:, 1:], self.instability)[:7] if moves else
+                       engine.join_supports(ref, slots[:, 1:], flag[:, 1:])[:3])
             if agree:
                 con = engine.join_consensus(slots[:, 1:], lengths[:, 1:], flag[:, 1:], self.consensus)
             for b in range(B):
                 if flag[b, 0]:
                     continue                                     # no tree of its own: the writer's plain text
-                tables[b][k] = (slots[b, 0], lengths[b, 0], slots[b, 1:], flag[b, 1:], None if res is None else tuple(x[b] for x in res[:3]),
+                tables[b][k] = (slots[b, 0], lengths[b, 0], slots[b, 1:], flag[b, 1:], None if res is None else tuple(x[b] for x in res),
                                 lengths[b, 1:], None if con is None else tuple(x[b] for x in con))
                 matched += res is not None
                 agreed += con is not None
-        runner.book(supports_device=matched, supports_device_s=time.perf_counter() - t0, **({"consensus_device": agreed} if agree else {}))
+        runner.book(supports_device=matched, supports_device_s=time.perf_counter() - t0, **({"consensus_device": agreed} if agree else {}),
+                    **({"transfers_device": matched} if moves else {}))
         return reps, tables
 
     def _host_tables(self, runner, kind, pred, reps, n):
@@ -277,7 +302,9 @@ class Bootstrap(Analysis):
         """Some files of a sub-batch on a writer thread: per kind of tree ``<stem>[.<kind>].sup.nwk`` and, with ``--tbe``,
         ``<stem>[.<kind>].tbe.nwk``.  Tables and results the GPU thread left are formatted; the others come from the host
         twins first (the serial ``pf_join_supports_host``; with ``--python-io`` ``supports.py`` itself).  With
-        ``--consensus`` also ``<stem>[.<kind>].con.nwk``, from the same replicate tables (``consensus.py``)."""
+        ``--consensus`` also ``<stem>[.<kind>].con.nwk``, from the same replicate tables (``consensus.py``).  With
+        ``--instability`` the supports are ``join_transfers``' first three arrays and its other results give
+        ``<stem>[.<kind>].instability.tsv``, ``.branches.tsv`` and ``.branches.nwk`` (``supports.instability_texts``)."""
         from . import consensus, hostio, supports
         n, R = shape[0], self.replicates
         for entry, pred, reps, given in rows:
@@ -287,17 +314,27 @@ class Bootstrap(Analysis):
                 table = None
                 if n >= 4:
                     table = given.get(kind) or self._host_tables(runner, kind, pred, reps, n)
+                moved = None
                 if table is None or table[0] is None:       # no split, or no tree of the file's own distances: the kind's plain text
                     text = self._nj_support(runner, pred, reps, ids) if kind == "nj" else runner.bme_tree(pred, ids, kind)[0]
                     texts = (text, text)
+                    if self.instability is not None:
+                        moved = supports.instability_texts(None, None, ids, None, R, _text(text))
                 else:
                     slots, lengths, rep_slots, rep_flag = table[:4]
                     res = table[4]
-                    if res is None and runner.native_io:
+                    if res is None and self.instability is not None:
+                        res = (hostio.join_transfers_host(slots, rep_slots, rep_flag, self.instability)[:7] if runner.native_io else
+                               supports.transfer_tuple(supports.transfer_taxa(slots, rep_slots, n, rep_flag, self.instability)))
+                    elif res is None and runner.native_io:
                         res = hostio.join_supports_host(slots, rep_slots, rep_flag)[:3]
                     elif res is None:
                         res = supports.split_supports(slots, rep_slots, n, rep_flag)
-                    texts = supports.support_texts(slots, lengths, ids, *res, R)
+                    texts = supports.support_texts(slots, lengths, ids, *res[:3], R)
+                    if self.instability is not None:
+                        moved = supports.instability_texts(slots, lengths, ids, res, R)
+                for suffix, text in zip(supports.INSTABILITY_SUFFIXES[kind], moved or ()):
+                    runner.put(entry.path, suffix, text)
                 runner.put(entry.path, sup, texts[0])
                 if self.tbe:
                     runner.put(entry.path, tbe, texts[1])
@@ -305,7 +342,8 @@ class Bootstrap(Analysis):
                     runner.put(entry.path, consensus.SUFFIXES[kind], self._consensus_text(runner, table, ids))
         kinds = len(self.kinds(runner))
         runner.book(tbe=len(rows) * kinds if self.tbe else 0, refined_supports=len(rows) * (kinds - 1),
-                    **({"consensus": len(rows) * kinds} if self.consensus is not None else {}))
+                    **({"consensus": len(rows) * kinds} if self.consensus is not None else {}),
+                    **({"instability": len(rows) * kinds} if self.instability is not None else {}))
 
     def _consensus_text(self, runner, table, ids):
         """``<stem>[.<kind>].con.nwk`` of one file from its replicate tables (None: fewer than four sequences - the star):

@@ -971,6 +971,42 @@ int pf_join_supports_host(const int32_t* ref_slots, const int32_t* rep_slots, co
     } catch (...) { return PF_ENOMEM; }
 }
 
+// Per-taxon transfer counts without a device: pf_join_supports_host's run with the matching that
+// keeps its keys, and k_sup_moves' body after it.  Twin of phyloformer_amd/supports.py::transfer_taxa.
+int pf_join_transfers_host(const int32_t* ref_slots, const int32_t* rep_slots, const uint8_t* rep_flag, int32_t B, int32_t R, int32_t N,
+                           int32_t cutoff_percent, int32_t* count, int64_t* transfer, int32_t* depth, int64_t* moves, int32_t* used,
+                           int32_t* capped, int32_t* branch_moves, uint8_t* status) {
+    if (!ref_slots || !rep_slots || !count || !transfer || !depth || !moves || !used || !capped || !status || B < 1 || R < 1 || N < 4 ||
+        N > pfbme::MAX_N || cutoff_percent < 0 || cutoff_percent > 100)
+        return PF_EINVAL;
+    const size_t T = (size_t)pfsup::table_len(N), S = (size_t)N - 3, W = (size_t)pfsup::words_of(N), b = (size_t)B, r = (size_t)R;
+    size_t total = 0;
+    if (__builtin_mul_overflow(b * r, T * sizeof(int32_t), &total)) return PF_EINVAL;
+    if (branch_moves && __builtin_mul_overflow(b * S, (size_t)N * sizeof(int32_t), &total)) return PF_EINVAL;
+    try {
+        std::vector<int32_t> parent((size_t)pfbme::nodes_of(N)), children((size_t)pfbme::nodes_of(N) * 3);
+        for (size_t i = 0; i < b; ++i)                            // refused before any work
+            if (!pfbme::tree_of_joins(ref_slots + i * T, N, parent.data(), children.data())) return PF_EINVAL;
+        for (size_t i = 0; i < b * r; ++i)
+            if (!(rep_flag && rep_flag[i]) && !pfbme::tree_of_joins(rep_slots + i * T, N, parent.data(), children.data())) return PF_EINVAL;
+        // the state of one source with all its replicates, reused from source to source
+        std::vector<uint64_t> bits((r + 1) * S * W), tile((size_t)pfsup::TILE * W);
+        std::vector<int32_t> row((r + 1) * (size_t)N), sizes(S), delta(r * S), arg(r * S);
+        std::vector<uint8_t> bad(b * (r + 1), 0);
+        pfsup::Args a{};
+        a.ref_slots = ref_slots; a.rep_slots = rep_slots; a.rep_flag = rep_flag;
+        a.bits = bits.data(); a.row = row.data(); a.sizes = sizes.data(); a.delta = delta.data(); a.bad = bad.data();
+        a.count = count; a.transfer = transfer; a.depth = depth; a.status = status;
+        const pfsup::Transfers x{arg.data(), moves, used, capped, branch_moves, cutoff_percent};
+        a.N = N; a.R = R; a.nb = 1; a.r0 = 0; a.rc = R;
+        for (int32_t src = 0; src < B; ++src) {
+            a.b0 = src;
+            pfsup::serial_chunk<true>(a, tile.data(), true, &x);
+        }
+        return PF_OK;
+    } catch (...) { return PF_ENOMEM; }
+}
+
 // Majority-rule consensus without a device: the bodies of pf_consensus.hip.h's kernels run
 // serially, one source at a time - the same integers and the same doubles as pf_join_consensus.  Tables are checked by
 // the bodies themselves, as pf_join_consensus_device's are: a source with a table that is no join table gets status 1

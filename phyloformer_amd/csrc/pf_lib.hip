@@ -273,6 +273,7 @@ struct pf_handle {
     Buffer<char> d_sup{buffers}, d_sup_io{buffers};
     Buffer<uint8_t> d_sup_bad{buffers};
     int64_t sup_calls = 0;       // calls since the last pf_profile_reset ("join_supports")
+    int64_t transfer_calls = 0;  // ("join_transfers": pf_join_transfers / pf_join_transfers_device)
     // pf_join_consensus / pf_join_consensus_device (grow-only): the state of one chunk of sources (pf_consensus.hip.h:
     // carve) and the staging of the host entry point's tables, lengths and results
     Buffer<char> d_con{buffers}, d_con_io{buffers};
@@ -2225,13 +2226,16 @@ static_assert(pfbme::MAX_N <= 64 * pfsup::MAX_W, "k_sup_match keeps TILE splits 
 // (state_bytes: the least a call needs - a source's reference table and one replicate table; the plan below sizes chunks)
 const TreeSearch SUP_SEARCH{"split supports", pfbme::MAX_N, pfsup::min_state_bytes, pfsup::SUP_MAX_Y,
                             "the bitset tables of the reference and of one replicate"};
+// pf_join_transfers: one more int32 per (replicate, split), the key beside the delta
+const TreeSearch TRANSFER_SEARCH{"transfer counts", pfbme::MAX_N, pfsup::min_transfer_state_bytes, pfsup::SUP_MAX_Y,
+                                 "the bitset tables of the reference and of one replicate, its deltas and keys"};
 
 // The chunks of a call: `nb` whole sources side by side where a source's R + 1 tables and its delta fit the workspace
 // limit, otherwise one source at a time in runs of `rc` replicates.  Refused only where the reference and one replicate
 // do not fit (check_tree_shape names the bytes).
-int plan_supports(pf_handle* h, int B, int R, int N, int* nb, int* rc) {
+int plan_supports(pf_handle* h, int B, int R, int N, int* nb, int* rc, bool arg = false) {
     int chunk = 0;
-    const int rc0 = check_tree_shape(h, SUP_SEARCH, B, N, &chunk);
+    const int rc0 = check_tree_shape(h, arg ? TRANSFER_SEARCH : SUP_SEARCH, B, N, &chunk);
     if (rc0) return rc0;
     if (N < 4) return fail(h, PF_EINVAL, "split supports need N >= 4 sequences (got %d): a tree of 3 has no split", N);
     if (R < 1) return fail(h, PF_EINVAL, "split supports need R >= 1 replicates (got %d)", R);
@@ -2240,22 +2244,22 @@ int plan_supports(pf_handle* h, int B, int R, int N, int* nb, int* rc) {
         return fail(h, PF_EINVAL, "B=%d sources of R=%d replicate tables overflow the address space", B, R);
     // (a launch's workgroups times their 256 threads stay below 2^32)
     const int64_t tiles = ((int64_t)N - 3 + pfsup::TILE - 1) / pfsup::TILE, max_trees = std::max<int64_t>(2, ((int64_t)1 << 23) / tiles);
-    const size_t limit = (size_t)h->ws_limit_bytes, per = pfsup::state_bytes(N, R);
+    const size_t limit = (size_t)h->ws_limit_bytes, per = arg ? pfsup::transfer_state_bytes(N, R) : pfsup::state_bytes(N, R);
     if (per <= limit && (int64_t)R + 1 <= max_trees && R <= pfsup::SUP_MAX_Y) {
         *rc = R;
         *nb = (int)std::min<int64_t>(std::min<int64_t>(B, pfsup::SUP_MAX_Y), std::min<int64_t>((int64_t)(limit / per), max_trees / ((int64_t)R + 1)));
         return PF_OK;
     }
-    const size_t tree = pfsup::tree_bytes(N), each = tree + pfsup::sizes_bytes(N);      // (limit >= state_bytes(N, 1): checked)
+    const size_t tree = pfsup::tree_bytes(N), each = tree + (arg ? 2 : 1) * pfsup::sizes_bytes(N);      // (limit >= state_bytes(N, 1): checked)
     *nb = 1;
     *rc = (int)std::min<int64_t>(std::min<int64_t>(R, pfsup::SUP_MAX_Y), std::min<int64_t>((int64_t)((limit - tree - pfsup::sizes_bytes(N)) / each), max_trees - 1));
     return PF_OK;
 }
 
-// all chunks of a call on device arrays, enqueued on h->stream
+// all chunks of a call on device arrays, enqueued on h->stream; `more`: pf_join_transfers' results too
 int supports_launch(pf_handle* h, const int32_t* d_ref, const int32_t* d_rep, const uint8_t* d_flag, int B, int R, int N, int nb, int rc,
-                    int32_t* d_count, int64_t* d_transfer, int32_t* d_depth, uint8_t* d_status) {
-    int rc2 = h->d_sup.reserve(h, (size_t)nb * pfsup::state_bytes(N, rc));
+                    int32_t* d_count, int64_t* d_transfer, int32_t* d_depth, uint8_t* d_status, const pfsup::Transfers* more = nullptr) {
+    int rc2 = h->d_sup.reserve(h, (size_t)nb * (more ? pfsup::transfer_state_bytes(N, rc) : pfsup::state_bytes(N, rc)));
     if (rc2) return rc2;
     if ((rc2 = h->d_sup_bad.reserve(h, (size_t)B * ((size_t)R + 1)))) return rc2;
     h->cur = h->stream;
@@ -2264,12 +2268,14 @@ int supports_launch(pf_handle* h, const int32_t* d_ref, const int32_t* d_rep, co
     a.ref_slots = d_ref; a.rep_slots = d_rep; a.rep_flag = d_flag; a.bad = h->d_sup_bad;
     a.count = d_count; a.transfer = d_transfer; a.depth = d_depth; a.status = d_status;
     a.N = N; a.R = R;
+    pfsup::Transfers x{};
+    if (more) x = *more;
     // (chunks follow each other on the stream, so the next one may reuse the state)
     for (int b0 = 0; b0 < B; b0 += nb)
         for (int r0 = 0; r0 < R; r0 += rc) {
             a.b0 = b0; a.nb = std::min(nb, B - b0); a.r0 = r0; a.rc = std::min(rc, R - r0);
-            pfsup::carve(a, h->d_sup);
-            const hipError_t e = pfsup::launch_chunk(h->stream, a, r0 == 0);
+            pfsup::carve(a, h->d_sup, more ? &x : nullptr);
+            const hipError_t e = pfsup::launch_chunk(h->stream, a, r0 == 0, more ? &x : nullptr);
             if (e != hipSuccess) return fail(h, PF_EHIP, "k_sup_* launch failed: %s", hipGetErrorString(e));
         }
     return PF_OK;
@@ -2286,6 +2292,21 @@ int supports_device_impl(pf_handle* h, const int32_t* d_ref, const int32_t* d_re
     return supports_launch(h, d_ref, d_rep, d_flag, B, R, N, nb, rc, d_count, d_transfer, d_depth, d_status);
 }
 
+// The tables of a host call (pf_join_supports, pf_join_transfers), validated as a start table is (a replicate passed with
+// its flag is never read: its table may be anything)
+int check_join_tables(pf_handle* h, const int32_t* ref, const int32_t* rep, const uint8_t* flag, int B, int R, int N) {
+    const size_t T = (size_t)pfnj::table_len(N), b = (size_t)B, r = (size_t)R;
+    try {
+        const int rc = check_bme_starts(h, ref, B, N);
+        if (rc) return rc;
+        std::vector<int32_t> parent((size_t)pfbme::nodes_of(N)), children((size_t)pfbme::nodes_of(N) * 3);
+        for (size_t i = 0; i < b * r; ++i)
+            if (!(flag && flag[i]) && !pfbme::tree_of_joins(rep + i * T, N, parent.data(), children.data()))
+                return fail(h, PF_EINVAL, "source %zu: replicate %zu is not a join table of N=%d sequences", i / r, i % r, N);
+    } catch (const std::bad_alloc&) { return fail(h, PF_ENOMEM, "out of host memory for the tables of N=%d sequences", N); }
+    return PF_OK;
+}
+
 int supports_host_impl(pf_handle* h, const int32_t* ref, const int32_t* rep, const uint8_t* flag, int B, int R, int N, int32_t* count,
                        int64_t* transfer, int32_t* depth, uint8_t* status) {
     if (!ref || !rep || !count || !transfer || !depth || !status) return fail(h, PF_EINVAL, "null buffer");
@@ -2293,14 +2314,7 @@ int supports_host_impl(pf_handle* h, const int32_t* ref, const int32_t* rep, con
     int rc2 = plan_supports(h, B, R, N, &nb, &rc);
     if (rc2) return rc2;
     const size_t T = (size_t)pfnj::table_len(N), S = (size_t)N - 3, b = (size_t)B, r = (size_t)R;
-    try {
-        // validated as a start table is (a replicate passed with its flag is never read: its table may be anything)
-        if ((rc2 = check_bme_starts(h, ref, B, N))) return rc2;
-        std::vector<int32_t> parent((size_t)pfbme::nodes_of(N)), children((size_t)pfbme::nodes_of(N) * 3);
-        for (size_t i = 0; i < b * r; ++i)
-            if (!(flag && flag[i]) && !pfbme::tree_of_joins(rep + i * T, N, parent.data(), children.data()))
-                return fail(h, PF_EINVAL, "source %zu: replicate %zu is not a join table of N=%d sequences", i / r, i % r, N);
-    } catch (const std::bad_alloc&) { return fail(h, PF_ENOMEM, "out of host memory for the tables of N=%d sequences", N); }
+    if ((rc2 = check_join_tables(h, ref, rep, flag, B, R, N))) return rc2;
     HIPCHK(h, hipSetDevice(h->device));
     ++h->sup_calls;
     pfsup::Staging io{};
@@ -2315,6 +2329,62 @@ int supports_host_impl(pf_handle* h, const int32_t* ref, const int32_t* rep, con
     HIPCHK(h, hipMemcpyAsync(count, io.count, b * S * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(transfer, io.transfer, b * S * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(depth, io.depth, b * S * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(status, io.status, b, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return PF_OK;
+}
+
+// pf_join_transfers' own refusal, before the shared ones
+int check_cutoff(pf_handle* h, int cutoff) {
+    if (cutoff < 0 || cutoff > 100) return fail(h, PF_EINVAL, "the transfer cutoff is a percent from 0 to 100 (got %d)", cutoff);
+    return PF_OK;
+}
+
+int transfers_device_impl(pf_handle* h, const int32_t* d_ref, const int32_t* d_rep, const uint8_t* d_flag, int B, int R, int N, int cutoff,
+                          int32_t* d_count, int64_t* d_transfer, int32_t* d_depth, int64_t* d_moves, int32_t* d_used, int32_t* d_capped,
+                          int32_t* d_branch, uint8_t* d_status) {
+    if (!d_ref || !d_rep || !d_count || !d_transfer || !d_depth || !d_moves || !d_used || !d_capped || !d_status)
+        return fail(h, PF_EINVAL, "null buffer");
+    int nb = 0, rc = 0;
+    int rc2 = check_cutoff(h, cutoff);
+    if (rc2 || (rc2 = plan_supports(h, B, R, N, &nb, &rc, true))) return rc2;
+    HIPCHK(h, hipSetDevice(h->device));
+    ++h->transfer_calls;
+    const pfsup::Transfers more{nullptr, d_moves, d_used, d_capped, d_branch, cutoff};
+    return supports_launch(h, d_ref, d_rep, d_flag, B, R, N, nb, rc, d_count, d_transfer, d_depth, d_status, &more);
+}
+
+int transfers_host_impl(pf_handle* h, const int32_t* ref, const int32_t* rep, const uint8_t* flag, int B, int R, int N, int cutoff,
+                        int32_t* count, int64_t* transfer, int32_t* depth, int64_t* moves, int32_t* used, int32_t* capped, int32_t* branch,
+                        uint8_t* status) {
+    if (!ref || !rep || !count || !transfer || !depth || !moves || !used || !capped || !status) return fail(h, PF_EINVAL, "null buffer");
+    int nb = 0, rc = 0;
+    int rc2 = check_cutoff(h, cutoff);
+    if (rc2 || (rc2 = plan_supports(h, B, R, N, &nb, &rc, true))) return rc2;
+    const size_t T = (size_t)pfnj::table_len(N), S = (size_t)N - 3, b = (size_t)B, r = (size_t)R;
+    size_t n = 0;
+    if (branch && !mul_size(b * S, (size_t)N, sizeof(int32_t), &n))
+        return fail(h, PF_EINVAL, "B=%d tables of branch moves of N=%d sequences overflow the address space", B, N);
+    if ((rc2 = check_join_tables(h, ref, rep, flag, B, R, N))) return rc2;
+    HIPCHK(h, hipSetDevice(h->device));
+    ++h->transfer_calls;
+    pfsup::TransferStaging io{};
+    auto list = [&](auto& v) { pfsup::transfer_staging_arrays(v, io, b, r, N, branch != nullptr); };
+    if ((rc2 = h->d_sup_io.reserve(h, pfspan::measure(list)))) return rc2;
+    pfspan::carve(h->d_sup_io, list);
+    HIPCHK(h, hipMemcpyAsync(io.ref, ref, b * T * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(io.rep, rep, b * r * T * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    if (flag) HIPCHK(h, hipMemcpyAsync(io.flag, flag, b * r, hipMemcpyHostToDevice, h->stream));
+    const pfsup::Transfers more{nullptr, io.moves, io.used, io.capped, branch ? io.branch : nullptr, cutoff};
+    if ((rc2 = supports_launch(h, io.ref, io.rep, flag ? io.flag : nullptr, B, R, N, nb, rc, io.count, io.transfer, io.depth, io.status, &more)))
+        return rc2;
+    HIPCHK(h, hipMemcpyAsync(count, io.count, b * S * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(transfer, io.transfer, b * S * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(depth, io.depth, b * S * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(moves, io.moves, b * (size_t)N * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(used, io.used, b * S * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(capped, io.capped, b * S * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    if (branch) HIPCHK(h, hipMemcpyAsync(branch, io.branch, b * S * (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(status, io.status, b, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return PF_OK;
@@ -2852,6 +2922,22 @@ int pf_join_consensus_device(pf_handle_t* h, const int32_t* d_rep_slots, const d
                                  ConsensusOut{d_n_splits, d_count, d_size, d_parent, d_split_length, d_leaf_parent, d_leaf_length, d_status});
 }
 
+int pf_join_transfers(pf_handle_t* h, const int32_t* ref_slots, const int32_t* rep_slots, const uint8_t* rep_flag, int32_t B, int32_t R,
+                      int32_t N, int32_t cutoff_percent, int32_t* count, int64_t* transfer, int32_t* depth, int64_t* moves, int32_t* used,
+                      int32_t* capped, int32_t* branch_moves, uint8_t* status) {
+    if (!h) return PF_EINVAL;
+    return transfers_host_impl(h, ref_slots, rep_slots, rep_flag, B, R, N, cutoff_percent, count, transfer, depth, moves, used, capped,
+                               branch_moves, status);
+}
+
+int pf_join_transfers_device(pf_handle_t* h, const int32_t* d_ref_slots, const int32_t* d_rep_slots, const uint8_t* d_rep_flag, int32_t B,
+                             int32_t R, int32_t N, int32_t cutoff_percent, int32_t* d_count, int64_t* d_transfer, int32_t* d_depth,
+                             int64_t* d_moves, int32_t* d_used, int32_t* d_capped, int32_t* d_branch_moves, uint8_t* d_status) {
+    if (!h) return PF_EINVAL;
+    return transfers_device_impl(h, d_ref_slots, d_rep_slots, d_rep_flag, B, R, N, cutoff_percent, d_count, d_transfer, d_depth, d_moves,
+                                 d_used, d_capped, d_branch_moves, d_status);
+}
+
 int pf_forward_device(pf_handle_t* h, const uint8_t* d_idx, int32_t B, int32_t N, int32_t L, float* d_out) {
     if (!h) return PF_EINVAL;
     return forward_device_impl(h, d_idx, B, N, 0, L, L, d_out);
@@ -3059,6 +3145,7 @@ int pf_profile_reset(pf_handle_t* h) {
     h->bme_calls = 0;
     h->spr_calls = 0;
     h->sup_calls = 0;
+    h->transfer_calls = 0;
     h->con_calls = 0;
     return PF_OK;
 }
@@ -3098,6 +3185,11 @@ int pf_profile_get(pf_handle_t* h, const char* kernel, int64_t* launches, double
     }
     if (std::strcmp(kernel, "join_supports") == 0) {    // pf_join_supports / pf_join_supports_device calls
         if (launches) *launches = h->sup_calls;
+        if (total_ms) *total_ms = 0.0;
+        return PF_OK;
+    }
+    if (std::strcmp(kernel, "join_transfers") == 0) {   // pf_join_transfers / pf_join_transfers_device calls
+        if (launches) *launches = h->transfer_calls;
         if (total_ms) *total_ms = 0.0;
         return PF_OK;
     }

@@ -2,7 +2,8 @@
 // the bodies of the kernels of pf_support.hip.h as functions of (tree or source, thread, threads).  Plain C++, no HIP:
 // pf_hostio.cpp runs them serially (one thread) as the CPU twin; pf_support.hip.h compiles them for the device too
 // (PF_TAXA_HD).  phyloformer_amd/supports.py::split_supports is the statement.  Everything is an integer, so any order
-// of the minima and sums gives the same result.
+// of the minima and sums gives the same result.  pf_join_transfers (its three forms; DESIGN.md section 27,
+// supports.py::transfer_taxa) adds the matching that keeps WHICH replicate split is the closest, and k_sup_moves' body.
 //
 // Per tree (the reference of a source, or one of its replicates), S = N - 3 splits of W = ceil(N / 64) words:
 //   bits  uint64 [W][S]   WORD-MAJOR: word w of split t at bits[w * S + t].  The matching kernel gives every thread one
@@ -38,6 +39,9 @@ inline size_t sizes_bytes(int N) { return ((((size_t)N - 3) + 1) / 2) * 2 * size
 inline size_t state_bytes(int N, int64_t rc) { return (size_t)(rc + 1) * tree_bytes(N) + sizes_bytes(N) + (size_t)rc * sizes_bytes(N); }
 // the least a call needs: the reference and one replicate (pf_lib.hip: TreeSearch)
 inline size_t min_state_bytes(int N) { return state_bytes(N, 1); }
+// pf_join_transfers: one more row per replicate, the keys beside the deltas
+inline size_t transfer_state_bytes(int N, int64_t rc) { return state_bytes(N, rc) + (size_t)rc * sizes_bytes(N); }
+inline size_t min_transfer_state_bytes(int N) { return transfer_state_bytes(N, 1); }
 
 struct Args {
     const int32_t* ref_slots;   // [B][T]
@@ -57,6 +61,17 @@ struct Args {
     int r0, rc;                 // and replicates r0 .. r0 + rc - 1
 };
 
+// What pf_join_transfers adds: an argument of its own, so that Args - and with it the kernels of
+// pf_join_supports - stay as they are.
+struct Transfers {
+    int32_t* arg;               // [nb][rc][S]: the key of the closest replicate split (key_of), beside Args::delta
+    int64_t* moves;             // [B][N]
+    int32_t* used;              // [B][S]
+    int32_t* capped;            // [B][S]
+    int32_t* branch_moves;      // [B][S][N] or null
+    int cutoff;                 // percent, 0 .. 100
+};
+
 // The staging of a whole host call (pf_join_supports): the tables that go up and the results that come down.
 struct Staging { int64_t* transfer; int32_t *ref, *rep, *count, *depth; uint8_t *flag, *status; };
 template <class V>
@@ -69,6 +84,18 @@ inline void staging_arrays(V& v, Staging& s, size_t B, size_t R, int N) {
     v(s.depth, B * S);
     v(s.flag, B * R);
     v(s.status, B);
+}
+
+// The staging of pf_join_transfers: the same, and the four results more (branch: branch_moves is asked for).
+struct TransferStaging : Staging { int64_t* moves; int32_t *used, *capped, *branch; };
+template <class V>
+inline void transfer_staging_arrays(V& v, TransferStaging& s, size_t B, size_t R, int N, bool branch) {
+    const size_t S = (size_t)N - 3;
+    staging_arrays(v, s, B, R, N);
+    v(s.moves, B * (size_t)N);
+    v(s.used, B * S);
+    v(s.capped, B * S);
+    v(s.branch, branch ? B * S * (size_t)N : 0);
 }
 
 PF_TAXA_HD inline size_t tree_index(const Args& a, int src, int k) { return (size_t)src * (size_t)(a.rc + 1) + (size_t)k; }
@@ -167,10 +194,24 @@ PF_TAXA_HD inline void tile_load(uint64_t* tile, const uint64_t* ref, int S, int
     }
 }
 
+// The running minimum of pf_join_transfers: m << 15 | j << 1 | side of replicate split j, m = min(h, N - h) away, side 1
+// where N - h is the smaller (a tie is side 0).  m <= 8192 and j < 16381: 29 bits.  The least key is the least (m, j) -
+// among equally close splits the earliest join -, and it is unique, so the minimum does not depend on who takes it when.
+constexpr int KEY_M = 15;
+// (unsigned: the table of a tree that is no join table is never built, and its garbage may give any m; such a source's
+// keys are not read, and whatever they are, key_j is a split of the table)
+PF_TAXA_HD inline int32_t key_of(int m, int j, int side) { return (int32_t)((uint32_t)m << KEY_M | (uint32_t)j << 1 | (uint32_t)side); }
+PF_TAXA_HD inline int32_t key_none(int N) { return (int32_t)(N << KEY_M | 0x7fff); }      // no split: m = N, capped at any depth
+PF_TAXA_HD inline int key_m(int32_t key) { return key >> KEY_M; }
+PF_TAXA_HD inline int key_j(int32_t key) { return (key >> 1) & 0x3fff; }
+PF_TAXA_HD inline int key_side(int32_t key) { return key & 1; }
+
 // best[k] = min over the replicate splits j = tid, tid + threads, ... of min(h, N - h), h = popcount(ref k xor rep j);
-// every replicate word is loaded once and meets the whole tile.  N where the thread has no split.
+// every replicate word is loaded once and meets the whole tile.  N where the thread has no split.  ARG: the minimum of
+// key_of instead (key_none where the thread has no split).
+template <bool ARG = false>
 PF_TAXA_HD inline void match_thread(const uint64_t* tile, const uint64_t* rep, int S, int W, int N, int tid, int threads, int* best) {
-    for (int k = 0; k < TILE; ++k) best[k] = N;
+    for (int k = 0; k < TILE; ++k) best[k] = ARG ? key_none(N) : N;
     for (int j = tid; j < S; j += threads) {
         int h[TILE];
         for (int k = 0; k < TILE; ++k) h[k] = 0;
@@ -180,7 +221,8 @@ PF_TAXA_HD inline void match_thread(const uint64_t* tile, const uint64_t* rep, i
         }
         for (int k = 0; k < TILE; ++k) {
             const int m = h[k] < N - h[k] ? h[k] : N - h[k];
-            if (m < best[k]) best[k] = m;
+            const int v = ARG ? key_of(m, j, h[k] > N - h[k]) : m;
+            if (v < best[k]) best[k] = v;
         }
     }
 }
@@ -215,6 +257,79 @@ PF_TAXA_HD inline void sum_split(const Args& a, int src, int t, bool first) {
     a.depth[o] = depth_of(a.sizes[(size_t)src * (size_t)S + (size_t)t], a.N);
 }
 
+// ---- k_sup_moves: one workgroup per (reference split, source) ----------------------------------------------------------
+
+// How a body reads a key: plainly on the CPU; the device hands it over as a scalar (every thread reads the same one).
+struct PlainKeys {
+    PF_TAXA_HD int32_t operator()(const int32_t* p) const { return *p; }
+};
+// moves[x] += c: plainly on the CPU; an integer atomic on the device (the workgroups of a source's splits share moves)
+struct PlainAdd {
+    void operator()(int64_t* p, int32_t c) const { *p += c; }
+};
+
+PF_TAXA_HD inline bool source_bad(const Args& a, size_t b) {
+    bool bad = false;
+    for (int k = 0; k <= a.R; ++k) bad |= a.bad[b * (size_t)(a.R + 1) + (size_t)k] != 0;
+    return bad;
+}
+
+// A replicate whose closest split has `key`, for a reference split with cap = p - 1: 0 not used (further than the
+// cutoff), 1 used and capped (the leaf edges are as close: no transfer set), 2 used with the transfer set of key's split.
+PF_TAXA_HD inline int pair_kind(int32_t key, int cap, int cutoff) {
+    const int m = key_m(key);
+    const bool capped = m > cap;
+    if (100 * (capped ? cap : m) > cutoff * cap) return 0;
+    return capped ? 1 : 2;
+}
+
+// Reference split t of chunk source src over the chunk's replicates (ascending; `first`: starts the counts): thread 0
+// counts used / capped; thread tid takes the sequences x = tid, tid + threads, ... and counts the replicates whose
+// transfer set X = ref t xor rep j*, complemented by side, holds x - into branch_moves[t][x] (where asked for) and, by
+// `add`, into moves[x].  A source with a tree that is no join table has zeros (sum_split gives its status).
+template <class Keys, class Add>
+PF_TAXA_HD inline void moves_thread(const Args& a, const Transfers& m, int src, int t, bool first, int tid, int threads, const Keys& keys,
+                                    const Add& add) {
+    const int N = a.N, S = N - 3;
+    const size_t b = (size_t)(a.b0 + src), o = b * (size_t)S + (size_t)t;
+    int64_t* moves = m.moves + b * (size_t)N;
+    int32_t* row = m.branch_moves ? m.branch_moves + o * (size_t)N : nullptr;
+    if (source_bad(a, b)) {
+        if (tid == 0) { m.used[o] = 0; m.capped[o] = 0; }
+        for (int x = tid; x < N; x += threads) {
+            if (row) row[x] = 0;
+            moves[x] = 0;
+        }
+        return;
+    }
+    const int cap = depth_of(a.sizes[(size_t)src * (size_t)S + (size_t)t], N) - 1;
+    const int32_t* arg = m.arg + (size_t)src * (size_t)a.rc * (size_t)S + (size_t)t;
+    const uint64_t* ref = bits_of(a, src, 0);
+    if (tid == 0) {
+        int32_t u = first ? 0 : m.used[o], c = first ? 0 : m.capped[o];
+        for (int r = 0; r < a.rc; ++r) {
+            const int kind = pair_kind(keys(arg + (size_t)r * (size_t)S), cap, m.cutoff);
+            u += kind != 0;
+            c += kind == 1;
+        }
+        m.used[o] = u;
+        m.capped[o] = c;
+    }
+    for (int x = tid; x < N; x += threads) {
+        const size_t w = (size_t)(x >> 6) * (size_t)S;
+        const uint64_t s = ref[w + (size_t)t];
+        int32_t c = 0;
+        for (int r = 0; r < a.rc; ++r) {
+            const int32_t key = keys(arg + (size_t)r * (size_t)S);
+            if (pair_kind(key, cap, m.cutoff) != 2) continue;
+            const uint64_t X = s ^ bits_of(a, src, r + 1)[w + (size_t)key_j(key)];
+            c += (int32_t)((X >> (x & 63)) & 1) ^ key_side(key);
+        }
+        if (row) row[x] = (first ? 0 : row[x]) + c;
+        if (c) add(moves + x, c);
+    }
+}
+
 // ---- the serial run of the bodies (the CPU twin; threads = 1) --------------------------------------------------------
 
 // tree k of chunk source src; false: no join table (the tree's flag is set)
@@ -239,8 +354,9 @@ inline bool serial_tree(const Args& a, int src, int k) {
     return true;
 }
 
-// the whole chunk: trees, deltas, sums
-inline void serial_chunk(const Args& a, uint64_t* tile, bool first) {
+// the whole chunk: trees, deltas, sums; ARG (pf_join_transfers_host): the keys and the moves too
+template <bool ARG = false>
+inline void serial_chunk(const Args& a, uint64_t* tile, bool first, const Transfers* x = nullptr) {
     const int N = a.N, S = N - 3, W = words_of(N);
     for (int src = 0; src < a.nb; ++src) {
         bool ok = true;
@@ -252,13 +368,21 @@ inline void serial_chunk(const Args& a, uint64_t* tile, bool first) {
                 const bool skip = flagged(a, src, r + 1);
                 if (!skip) {
                     tile_load(tile, bits_of(a, src, 0), S, W, t0, 0, 1);
-                    match_thread(tile, bits_of(a, src, r + 1), S, W, N, 0, 1, best);
+                    match_thread<ARG>(tile, bits_of(a, src, r + 1), S, W, N, 0, 1, best);
                 }
-                for (int k = 0; k < TILE && t0 + k < S; ++k)
-                    a.delta[((size_t)src * (size_t)a.rc + (size_t)r) * (size_t)S + (size_t)(t0 + k)] =
-                        delta_of(skip ? N : best[k], a.sizes[(size_t)src * (size_t)S + (size_t)(t0 + k)], N);
+                for (int k = 0; k < TILE && t0 + k < S; ++k) {
+                    const size_t o = ((size_t)src * (size_t)a.rc + (size_t)r) * (size_t)S + (size_t)(t0 + k);
+                    const int m = skip ? N : ARG ? key_m(best[k]) : best[k];
+                    a.delta[o] = delta_of(m, a.sizes[(size_t)src * (size_t)S + (size_t)(t0 + k)], N);
+                    if (ARG) x->arg[o] = skip ? key_none(N) : best[k];
+                }
             }
         for (int t = 0; t < S; ++t) sum_split(a, src, t, first);
+        if (ARG) {
+            if (first)
+                for (int i = 0; i < N; ++i) x->moves[(size_t)(a.b0 + src) * (size_t)N + (size_t)i] = 0;
+            for (int t = 0; t < S; ++t) moves_thread(a, *x, src, t, first, 0, 1, PlainKeys{}, PlainAdd{});
+        }
     }
 }
 

@@ -158,6 +158,10 @@ SIGNATURES = {
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "pf_join_supports_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p]),
+    "pf_join_transfers": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 8),
+    "pf_join_transfers_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] +
+                                 [C.c_void_p] * 8),
+    "pf_join_transfers_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 8),
     "pf_join_consensus": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 8),
     "pf_join_consensus_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] +
                                  [C.c_void_p] * 8),
@@ -186,7 +190,8 @@ CALL_TIME_SYMBOLS = frozenset({"pf_forward_site_map", "pf_forward_site_map_devic
                                "pf_bme_spr_device", "pf_bme_spr_host", "pf_bme_spr_newick_n", "pf_join_supports",
                                "pf_join_supports_device", "pf_join_supports_host", "pf_join_consensus",
                                "pf_join_consensus_device", "pf_join_consensus_host", "pf_bionj_joins",
-                               "pf_bionj_joins_device", "pf_bionj_joins_host", "pf_bionj_newick_n"})
+                               "pf_bionj_joins_device", "pf_bionj_joins_host", "pf_bionj_newick_n", "pf_join_transfers",
+                               "pf_join_transfers_device", "pf_join_transfers_host"})
 
 _lib: Optional[C.CDLL] = None
 
@@ -672,6 +677,31 @@ class Engine:
         self._check(self._optional("pf_join_supports_device")(
             self._h, C.c_void_p(d_ref_slots), C.c_void_p(d_rep_slots), C.c_void_p(d_rep_flag) if d_rep_flag else None, B, R, N,
             C.c_void_p(d_count), C.c_void_p(d_transfer), C.c_void_p(d_depth), C.c_void_p(d_status)))
+
+    # -- per-taxon transfer counts ------------------------------------------------------------
+    def join_transfers(self, ref_slots: np.ndarray, rep_slots: np.ndarray, rep_flag: Optional[np.ndarray] = None, cutoff: int = 100,
+                       branch_moves: bool = True):
+        """Per-taxon transfer counts on the GPU (``pf_join_transfers``): ``join_supports``' arguments and the cutoff in
+        percent (0 .. 100) → ``(count, transfer, depth, moves int64[B, N], used int32[B, N - 3], capped int32[B, N - 3],
+        branch_moves int32[B, N - 3, N] or None, status uint8[B])`` - ``supports.transfer_taxa``, the same integers as
+        ``hostio.join_transfers_host``; the first three are ``join_supports``'.  Refusals as ``join_supports``."""
+        from .hostio import support_arrays, transfer_outputs
+        fn = self._optional("pf_join_transfers")
+        ref, rep, flag, (B, R, N), single = support_arrays(ref_slots, rep_slots, rep_flag)
+        out, ptrs = transfer_outputs(B, N, branch_moves)
+        self._check(fn(self._h, ref.ctypes.data, rep.ctypes.data, None if flag is None else flag.ctypes.data, B, R, N, int(cutoff), *ptrs))
+        return tuple(None if x is None else x[0] for x in out) if single else out
+
+    def join_transfers_device(self, d_ref_slots: int, d_rep_slots: int, d_rep_flag: int, B: int, R: int, N: int, cutoff: int,
+                              d_count: int, d_transfer: int, d_depth: int, d_moves: int, d_used: int, d_capped: int,
+                              d_branch_moves: int, d_status: int):
+        """``pf_join_transfers_device``: ``join_supports_device``'s arguments, the cutoff, and device ``moves int64
+        [B][N]``, ``used`` / ``capped int32 [B][N - 3]``, ``branch_moves int32 [B][N - 3][N]`` (0: not wanted)
+        (asynchronous on the handle's stream).  Tables are checked in the kernel: status 1 and zeros, no refusal."""
+        self._check(self._optional("pf_join_transfers_device")(
+            self._h, C.c_void_p(d_ref_slots), C.c_void_p(d_rep_slots), C.c_void_p(d_rep_flag) if d_rep_flag else None, B, R, N,
+            int(cutoff), C.c_void_p(d_count), C.c_void_p(d_transfer), C.c_void_p(d_depth), C.c_void_p(d_moves), C.c_void_p(d_used),
+            C.c_void_p(d_capped), C.c_void_p(d_branch_moves) if d_branch_moves else None, C.c_void_p(d_status)))
 
     # -- majority-rule consensus of replicate join tables -----------------------------------
     def join_consensus(self, rep_slots: np.ndarray, rep_lengths: Optional[np.ndarray] = None,

@@ -317,6 +317,31 @@ def join_supports_host(ref_slots, rep_slots, rep_flag=None):
     return tuple(x[0] for x in out) if single else out
 
 
+def transfer_outputs(b: int, n: int, branch_moves: bool = True):
+    """The results of the three ``pf_join_transfers`` entry points, zeroed: ``((count, transfer, depth, moves, used, capped,
+    branch_moves or None, status), pointers)``."""
+    s = n - 3
+    out = (np.zeros((b, s), dtype=np.int32), np.zeros((b, s), dtype=np.int64), np.zeros((b, s), dtype=np.int32),
+           np.zeros((b, n), dtype=np.int64), np.zeros((b, s), dtype=np.int32), np.zeros((b, s), dtype=np.int32),
+           np.zeros((b, s, n), dtype=np.int32) if branch_moves else None, np.zeros(b, dtype=np.uint8))
+    return out, [None if x is None else x.ctypes.data for x in out]
+
+
+def join_transfers_host(ref_slots, rep_slots, rep_flag=None, cutoff: int = 100, branch_moves: bool = True):
+    """``pf_join_transfers_host``: ``Engine.join_transfers`` without a device - the same bodies run serially, the same
+    integers as ``supports.transfer_taxa``.  ``ValueError`` for what the library refuses (``N < 4``, a table that is no
+    join table, a cutoff outside 0 .. 100)."""
+    lib = load_library()
+    ref, rep, flag, (b, r, n), single = support_arrays(ref_slots, rep_slots, rep_flag)
+    out, ptrs = transfer_outputs(b, n, branch_moves)
+    rc = lib.pf_join_transfers_host(ref.ctypes.data, rep.ctypes.data, None if flag is None else flag.ctypes.data, b, r, n, int(cutoff), *ptrs)
+    if rc == -1:
+        raise ValueError("pf_join_transfers_host refused its arguments (a table that is no join table, a cutoff outside 0 .. 100?)")
+    if rc < 0:
+        raise RuntimeError(f"pf_join_transfers_host failed with status {rc}")
+    return tuple(None if x is None else x[0] for x in out) if single else out
+
+
 def consensus_arrays(rep_slots, rep_lengths, rep_flag):
     """The arguments of the three ``pf_join_consensus`` entry points, checked: ``(rep int32[B, R, T], lengths float64[B, R,
     T] or None, flag uint8[B, R] or None, (B, R, N), single)``."""

@@ -714,7 +714,8 @@ def summarize(stats: dict, load_s: float = 0.0) -> dict:
             **({k: round(stats[k], 6) for k in ("bionj", "bionj_device", "bionj_device_s")} if "bionj" in stats else {}),
             **({k: round(stats[k], 6) for k in ("tbe", "refined_supports", "supports_device", "supports_device_s")}
                if "tbe" in stats else {}),
-            **({k: stats[k] for k in ("consensus", "consensus_device")} if "consensus" in stats else {})}
+            **({k: stats[k] for k in ("consensus", "consensus_device")} if "consensus" in stats else {}),
+            **({k: stats[k] for k in ("instability", "transfers_device")} if "instability" in stats else {})}
 
 
 def run_multi_device(script: str, argv: List[str], devices: Sequence[int], shard: str = "files") -> Tuple[int, List[dict]]:

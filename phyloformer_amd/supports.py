@@ -35,6 +35,12 @@ from .nj import join_splits, newick_of_joins
 # takes at most half the host's time at R = 100; None = the device path is off in the CLI (the API stays).
 SUPPORT_DEVICE_MIN = 200
 
+# From this many sequences on the CLI's ``--instability`` counts a sub-batch's transfers on the GPU thread
+# (``Engine.join_transfers``) instead of on the writer threads' serial twin.  The same rule (DESIGN.md section 27,
+# tools/support_bench.py --transfers, profiles/transfer_bench.txt: 36 times the host's speed at N = 200, 1.5 times at 50);
+# None = the device path is off in the CLI.
+TRANSFER_DEVICE_MIN = 200
+
 
 def table_splits(slots: Sequence[int], n: int) -> List[int]:
     """The ``n - 3`` splits of a join table (``ValueError`` if it is none), as ``nj.join_splits`` gives them."""
@@ -74,6 +80,73 @@ def split_supports(ref_slots: Sequence[int], rep_slots: Sequence[Sequence[int]],
     return count, transfer, depth
 
 
+def transfer_taxa(ref_slots: Sequence[int], rep_slots: Sequence[Sequence[int]], n: int,
+                  rep_flag: Optional[Sequence[bool]] = None, cutoff: int = 100) -> Dict[str, list]:
+    """One source: which sequences have to move (the per-taxon companion of the transfer bootstrap,
+    Lemoine et al. 2018).  For reference split ``s`` (join ``t``, depth ``p``) and an unflagged replicate with splits
+    ``q_j`` in join order, ``m_j = min(h_j, n - h_j)`` and ``side_j = 0`` if ``h_j <= n - h_j`` else 1; ``j*`` has the least
+    ``(m_j, j)`` and ``delta = min(p - 1, m_j*)`` as in ``split_supports``.  If ``m_j* <= p - 1`` the transfer set is
+    ``X = s xor q_j*``, complemented within the ``n`` sequences if ``side_j* = 1`` (``popcount(X) = delta``); otherwise,
+    or if the replicate is flagged, the pair is *capped*: the leaf edges give ``p - 1`` and nothing is attributed to any
+    sequence.  The pair is *used* iff ``100 delta <= cutoff (p - 1)``, ``cutoff`` an integer percent.
+
+    Returns ``{"count", "transfer", "depth"}`` as ``split_supports`` and ``"used"[t]`` = used replicates, ``"capped"[t]``
+    = used replicates that are capped, ``"branch_moves"[t][x]`` = used, uncapped replicates with ``x`` in ``X``,
+    ``"moves"[x]`` = the sum of ``branch_moves[t][x]`` over ``t``.  At ``cutoff = 100`` every pair is used and
+    ``sum_x branch_moves[t][x] + (p_t - 1) capped[t] == transfer[t]``."""
+    cutoff = int(cutoff)
+    if not 0 <= cutoff <= 100:
+        raise ValueError(f"the cutoff is a percent from 0 to 100 (got {cutoff})")
+    if len(rep_slots) < 1:
+        raise ValueError("split supports need R >= 1 replicates")
+    flags = [False] * len(rep_slots) if rep_flag is None else [bool(f) for f in rep_flag]
+    if len(flags) != len(rep_slots):
+        raise ValueError(f"expected {len(rep_slots)} replicate flags, got {len(flags)}")
+    ref = table_splits(ref_slots, n)
+    reps = [None if f else table_splits(s, n) for s, f in zip(rep_slots, flags)]
+    everyone = (1 << n) - 1
+    out = {k: [] for k in ("count", "transfer", "depth", "used", "capped", "branch_moves")}
+    out["moves"] = [0] * n
+    for s in ref:
+        k = bin(s).count("1")
+        p = min(k, n - k)
+        c = total = used = capped = 0
+        row = [0] * n
+        for splits in reps:
+            best = None                                          # (m, j, side) of the closest split
+            for j, q in enumerate(splits or ()):
+                h = bin(s ^ q).count("1")
+                key = (min(h, n - h), j, 0 if h <= n - h else 1)
+                if best is None or key < best:
+                    best = key
+            is_capped = best is None or best[0] > p - 1
+            delta = p - 1 if is_capped else best[0]
+            c += delta == 0
+            total += delta
+            if 100 * delta > cutoff * (p - 1):
+                continue
+            used += 1
+            if is_capped:
+                capped += 1
+                continue
+            X = s ^ splits[best[1]]
+            if best[2]:
+                X ^= everyone
+            for x in range(n):
+                row[x] += (X >> x) & 1
+        for name, v in (("count", c), ("transfer", total), ("depth", p), ("used", used), ("capped", capped), ("branch_moves", row)):
+            out[name].append(v)
+        out["moves"] = [a + b for a, b in zip(out["moves"], row)]
+    return out
+
+
+def instability_permille(moves: int, used: int) -> int:
+    """``moves / used`` in permille, rounded half up: how often, per used (reference branch, replicate) pair, the
+    sequence is among those that have to move.  0 where no pair is used."""
+    moves, used = int(moves), int(used)
+    return (2000 * moves + used) // (2 * used) if used else 0
+
+
 def tbe_percent(S: int, R: int, p: int) -> int:
     """``1 - S / (R (p - 1))`` in percent, rounded half up."""
     D = int(R) * (int(p) - 1)
@@ -91,6 +164,45 @@ def support_texts(slots: Sequence[int], lengths: Sequence[float], ids: Sequence[
     joins, final = table_to_joins(slots, lengths)
     fbp, tbe = labels_of(count, transfer, depth, R)
     return (newick_of_joins(ids, joins, final, clamp_negative, fbp), newick_of_joins(ids, joins, final, clamp_negative, tbe))
+
+
+# the files of --instability per kind of tree: per-taxon counts, per-branch counts, the tree labelled with the join t
+INSTABILITY_SUFFIXES = {"nj": ("instability.tsv", "branches.tsv", "branches.nwk"),
+                        "bme": ("bme.instability.tsv", "bme.branches.tsv", "bme.branches.nwk"),
+                        "spr": ("spr.instability.tsv", "spr.branches.tsv", "spr.branches.nwk")}
+TOP_MOVED = 5
+
+
+def instability_texts(slots: Optional[Sequence[int]], lengths, ids: Sequence[str], res, R: int, plain: str = "",
+                      clamp_negative: bool = True) -> Tuple[str, str, str]:
+    """The three files of ``--instability`` for one tree: ``res`` = ``(count, transfer, depth, moves, used, capped,
+    branch_moves)`` of one source (``transfer_taxa``'s or a native entry point's).
+    ``instability.tsv``: ``id``, ``moves``, ``permille`` (``instability_permille`` over the tree's used pairs), in input
+    order.  ``branches.tsv``: per join ``t`` its ``depth``, Felsenstein percent, TBE percent, ``used``, ``capped`` and
+    the (at most) ``TOP_MOVED`` most-moved sequences as ``id:count``, ties in input order, ``-`` if none moved.
+    ``branches.nwk``: the tree with ``t`` after the ``)`` of join ``t``'s node.  A tree without a split (``slots`` None:
+    fewer than four sequences, or non-finite distances): zeros, no branch, and the ``plain`` text."""
+    head = "id\tmoves\tpermille\n"
+    cols = "t\tdepth\tsupport\ttbe\tused\tcapped\tmost_moved\n"
+    if slots is None:
+        return head + "".join(f"{i}\t0\t0\n" for i in ids), cols, plain
+    count, transfer, depth, moves, used, capped, branch_moves = ([int(v) for v in x] if k != 6 else x for k, x in enumerate(res[:7]))
+    total = sum(used)
+    taxa = head + "".join(f"{i}\t{m}\t{instability_permille(m, total)}\n" for i, m in zip(ids, moves))
+    fbp, tbe = labels_of(count, transfer, depth, R)
+    rows = []
+    for t in range(len(count)):
+        row = [int(v) for v in branch_moves[t]]
+        top = sorted((x for x in range(len(row)) if row[x] > 0), key=lambda x: (-row[x], x))[:TOP_MOVED]
+        rows.append(f"{t}\t{depth[t]}\t{fbp[t]}\t{tbe[t]}\t{used[t]}\t{capped[t]}\t" +
+                    (",".join(f"{ids[x]}:{row[x]}" for x in top) or "-") + "\n")
+    joins, final = table_to_joins(slots, lengths)
+    return taxa, cols + "".join(rows), newick_of_joins(ids, joins, final, clamp_negative, list(range(len(count))))
+
+
+def transfer_tuple(out: Dict[str, list]) -> tuple:
+    """``transfer_taxa``'s dict in the order of the native entry points' results (without ``status``)."""
+    return tuple(out[k] for k in ("count", "transfer", "depth", "moves", "used", "capped", "branch_moves"))
 
 
 # the searches behind the trees of the CLI: suffix of the tree's file -> bme.py's search (None: the NJ tree itself)

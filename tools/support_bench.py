@@ -1,6 +1,7 @@
 """split supports on the host against the device, and the constant SUPPORT_DEVICE_MIN.
 
     python tools/support_bench.py [--sizes 50,200,1024,4096] [--replicates 100] [--repeats 3] [--out profiles/support_bench.txt]
+    python tools/support_bench.py --transfers [--cutoff 100] ... [--out profiles/transfer_bench.txt]      (section 27)
 
 Per N: one source, a reference and R replicate join tables of random joins (the work does not depend on the trees: every
 reference split meets every replicate split, word by word).  host = hostio.join_supports_host (the serial twin, what a
@@ -8,7 +9,11 @@ writer thread runs); device = Engine.join_supports (what the GPU thread runs: ta
 down).  The results are compared for equality BEFORE anything is timed; then the best of `repeats` of each, alternating,
 in this one process (a host run of more than 10 s is timed once).  SUPPORT_DEVICE_MIN is the smallest of the sizes at which
 device <= host / 2 (the device side occupies the GPU thread, the host side overlaps the next launch).  Every row is
-printed, and appended to --out, as soon as it is measured."""
+printed, and appended to --out, as soon as it is measured.
+
+--transfers: the same for the per-taxon transfer counts and TRANSFER_DEVICE_MIN - host = hostio.join_transfers_host,
+device = Engine.join_transfers, both with branch_moves as the CLI asks for them, at --cutoff percent (default 100: every
+pair is used, the most work for k_sup_moves)."""
 import argparse
 import os
 import random
@@ -50,6 +55,8 @@ def main():
     ap.add_argument("--replicates", type=int, default=100)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--transfers", action="store_true")
+    ap.add_argument("--cutoff", type=int, default=100)
     args = ap.parse_args()
     sizes = [int(s) for s in args.sizes.split(",")]
     R = args.replicates
@@ -63,38 +70,45 @@ def main():
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     chosen = None
+    name, constant = ("join_transfers", "TRANSFER_DEVICE_MIN") if args.transfers else ("join_supports", "SUPPORT_DEVICE_MIN")
+    more = (None, args.cutoff) if args.transfers else ()
+
+    def host_run(ref, reps):
+        return getattr(hostio, name + "_host")(ref, reps, *more)
     with Engine(load_weights(os.path.join(REPO, "models", "pf.ckpt")), 0) as e:
         info = e.device_info()
-        emit(f"# tools/support_bench.py --sizes {args.sizes} --replicates {R} --repeats {args.repeats}")
+        emit(f"# tools/support_bench.py{f' --transfers --cutoff {args.cutoff}' if args.transfers else ''} --sizes {args.sizes} "
+             f"--replicates {R} --repeats {args.repeats}")
         emit(f"# {info['name']}, kernel_hash {e.build_info().get('kernel_hash')}")
-        emit("# host = hostio.join_supports_host (serial); device = Engine.join_supports (host arrays in, host arrays out); results "
+        emit(f"# host = hostio.{name}_host (serial); device = Engine.{name} (host arrays in, host arrays out); results "
              "compared for equality before timing; best of the repeats, alternating (a host run above 10 s: once)")
         emit(f"{'N':>6} {'R':>4} {'word_ops':>10} {'host_ms':>11} {'device_ms':>10} {'host/device':>12}  same")
         warm = random_tables(8, 3, 0)
-        e.join_supports(warm[0], warm[1:])                          # (first-call costs are not what is compared)
+        device_run = getattr(e, name)
+        device_run(warm[0], warm[1:], *more)                        # (first-call costs are not what is compared)
         for n in sizes:
             tables = random_tables(n, R + 1, n)
             ref, reps = tables[0], tables[1:]
             t0 = time.perf_counter()
-            want = hostio.join_supports_host(ref, reps)
+            want = host_run(ref, reps)
             first = time.perf_counter() - t0
-            got = e.join_supports(ref, reps)
+            got = device_run(ref, reps, *more)
             same = all(np.array_equal(g, w) for g, w in zip(got, want))
             host, dev = [first], []
             for _ in range(args.repeats):
                 if first <= 10.0:
                     t0 = time.perf_counter()
-                    hostio.join_supports_host(ref, reps)
+                    host_run(ref, reps)
                     host.append(time.perf_counter() - t0)
                 t0 = time.perf_counter()
-                e.join_supports(ref, reps)
+                device_run(ref, reps, *more)
                 dev.append(time.perf_counter() - t0)
             h, d = min(host) * 1e3, min(dev) * 1e3
             if chosen is None and same and d <= h / 2:
                 chosen = n
             ops = (n - 3) ** 2 * R * ((n + 63) // 64)
             emit(f"{n:>6} {R:>4} {ops:>10.2e} {h:>11.2f} {d:>10.2f} {h / d:>12.2f}  {same}")
-    emit(f"SUPPORT_DEVICE_MIN = {chosen if chosen is not None else 'none of these sizes qualifies'}")
+    emit(f"{constant} = {chosen if chosen is not None else 'none of these sizes qualifies'}")
 
 
 if __name__ == "__main__":
