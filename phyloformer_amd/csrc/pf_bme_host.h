@@ -540,6 +540,20 @@ inline void result_of(int N, const int32_t* children, const double* edge_len, in
     *tree_length = tree_length_of(edge_len, N);
 }
 
+// The start tables and the results of a call (pf_bme_nni, pf_bme_spr) as the caller holds them, `u`, or - the device
+// forms - their mirror on the host, `s`: the search reads and writes them on the host.
+struct Tables { const int32_t* start; int32_t *slots, *steps; double *lengths, *tree_length; uint8_t* status; };
+template <class V>
+inline void mirror_arrays(V& v, Tables& s, const Tables& u, size_t B, int N) {
+    const size_t T = (size_t)pfnj::table_len(N);
+    v.in(s.start, u.start, B * T);
+    v.out(s.slots, u.slots, B * T);
+    v.out(s.steps, u.steps, B);
+    v.out(s.lengths, u.lengths, B * T);
+    v.out(s.tree_length, u.tree_length, B);
+    v.out(s.status, u.status, B);
+}
+
 // ---- host only: the arrays of the state, listed once (the visitors and the padding rule: pf_nj_host.h) --------------
 
 // the scalars of `a`; the arrays follow by state_arrays / spr_state_arrays

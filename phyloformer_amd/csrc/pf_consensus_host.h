@@ -100,22 +100,28 @@ inline size_t state_bytes(int N, int64_t R, bool lengths = true) {
 }
 inline size_t min_state_bytes(int N) { return state_bytes(N, 1); }
 
-// The staging of a whole host call (pf_join_consensus): what goes up and what comes down.
-struct Staging { double *lengths, *split_length, *leaf_length; int32_t *rep, *n_splits, *count, *size, *parent, *leaf_parent; uint8_t *flag, *status; };
+// The arrays of a call (pf_join_consensus) as the caller or the staging holds them.
+struct Tables {
+    const int32_t* rep; const double* lengths; const uint8_t* flag;
+    int32_t *n_splits, *count, *size, *parent; double* split_length; int32_t* leaf_parent; double* leaf_length; uint8_t* status;
+};
+// The staging `s` of a whole host call with the caller's arrays `u`: what goes up and what comes down.  Without the
+// caller's rep_lengths there are no lengths, with them both length results are required; a null rep_flag keeps its span.
 template <class V>
-inline void staging_arrays(V& v, Staging& s, size_t B, size_t R, int N, bool lengths) {
+inline void staging_arrays(V& v, Tables& s, const Tables& u, size_t B, size_t R, int N) {
     const size_t T = (size_t)table_len(N), S = (size_t)N - 3;
-    v(s.lengths, lengths ? B * R * T : 0);
-    v(s.split_length, lengths ? B * S : 0);
-    v(s.leaf_length, lengths ? B * (size_t)N : 0);
-    v(s.rep, B * R * T);
-    v(s.n_splits, B);
-    v(s.count, B * S);
-    v(s.size, B * S);
-    v(s.parent, B * S);
-    v(s.leaf_parent, B * (size_t)N);
-    v(s.flag, B * R);
-    v(s.status, B);
+    const pfspan::Need lengths = u.lengths ? pfspan::REQUIRED : pfspan::ABSENT;
+    v.in(s.lengths, u.lengths, B * R * T, lengths);
+    v.out(s.split_length, u.split_length, B * S, lengths);
+    v.out(s.leaf_length, u.leaf_length, B * (size_t)N, lengths);
+    v.in(s.rep, u.rep, B * R * T);
+    v.out(s.n_splits, u.n_splits, B);
+    v.out(s.count, u.count, B * S);
+    v.out(s.size, u.size, B * S);
+    v.out(s.parent, u.parent, B * S);
+    v.out(s.leaf_parent, u.leaf_parent, B * (size_t)N);
+    v.in(s.flag, u.flag, B * R, pfspan::OPTIONAL);
+    v.out(s.status, u.status, B);
 }
 
 // ---- where the arrays of chunk source src, replicate r are ------------------------------------------------------------

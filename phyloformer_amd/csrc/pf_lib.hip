@@ -2018,57 +2018,69 @@ int check_tree_shape(pf_handle* h, const TreeSearch& t, int B, int N, int* chunk
     return PF_OK;
 }
 
+// ---- a host entry point on staged arrays.  The list of a call's arrays (pf_spans.h) names each
+// with its staging pointer, the caller's, its elements, its direction and what a null means: nothing here repeats them.
+
+// the list's inputs to their staging (`up`) or its results to the caller, by hipMemcpyAsync on h->stream
+template <class List>
+int list_copy(pf_handle* h, List&& list, bool up, hipMemcpyKind kind) {
+    auto copy = [&](void* to, const void* from, size_t bytes) { return hipMemcpyAsync(to, from, bytes, kind, h->stream); };
+    const hipError_t e = (hipError_t)(up ? pfspan::upload(list, copy) : pfspan::download(list, copy));
+    if (e != hipSuccess)
+        return fail(h, e == hipErrorOutOfMemory ? PF_ENOMEM : PF_EHIP, "hipMemcpyAsync of a call's %s: %s", up ? "inputs" : "results",
+                    hipGetErrorString(e));
+    return PF_OK;
+}
+
+// The call: the list's arrays carved from `buf`, the inputs up, launch() - which reads the staging pointers the list
+// has set -, the results down, one synchronisation.
+template <class List, class Launch>
+int staged_call(pf_handle* h, Buffer<char>& buf, List&& list, Launch&& launch) {
+    int rc = buf.reserve(h, pfspan::measure(list));
+    if (rc) return rc;
+    pfspan::carve(buf, list);
+    if ((rc = list_copy(h, list, true, hipMemcpyHostToDevice)) || (rc = launch()) || (rc = list_copy(h, list, false, hipMemcpyDeviceToHost)))
+        return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return PF_OK;
+}
+
 // the join sequences of nb <= chunk sources on device arrays, enqueued on h->stream: neighbour joining, or BIONJ
 // (pf_bionj.hip.h)
-int launch_nj_chunk(pf_handle* h, bool bionj, const float* d_preds, int nb, int N, int32_t* d_slots, double* d_lengths, uint8_t* d_flag) {
+int launch_nj_chunk(pf_handle* h, bool bionj, const pfnj::Tables& d, int nb, int N) {
     const int rc = h->d_nj.reserve(h, (size_t)nb * (bionj ? pfbionj::state_bytes(N) : pfnj::state_bytes(N)));
     if (rc) return rc;
     h->cur = h->stream;
-    const hipError_t e = bionj ? pfbionj::launch_bionj(h->stream, pfbionj::carve(h->d_nj, d_preds, nb, N, d_slots, d_lengths, d_flag), nb)
-                               : pfnj::launch_nj(h->stream, pfnj::carve(h->d_nj, d_preds, nb, N, d_slots, d_lengths, d_flag), nb);
+    const hipError_t e = bionj ? pfbionj::launch_bionj(h->stream, pfbionj::carve(h->d_nj, d.preds, nb, N, d.slots, d.lengths, d.flag), nb)
+                               : pfnj::launch_nj(h->stream, pfnj::carve(h->d_nj, d.preds, nb, N, d.slots, d.lengths, d.flag), nb);
     if (e != hipSuccess) return fail(h, PF_EHIP, "%s launch failed: %s", bionj ? "k_bionj_*" : "k_nj_*", hipGetErrorString(e));
     return PF_OK;
 }
 
-int nj_device_impl(pf_handle* h, bool bionj, const float* d_preds, int B, int N, int32_t* d_slots, double* d_lengths, uint8_t* d_flag) {
-    if (!d_preds || !d_slots || !d_lengths || !d_flag) return fail(h, PF_EINVAL, "null buffer");
+// The caller's arrays on the device (asynchronous) or on the host: then every chunk is staged, and synchronises once.
+int nj_impl(pf_handle* h, bool bionj, bool device, const pfnj::Tables& user, int B, int N) {
+    pfnj::Tables io{};
+    auto chunk_list = [&](int b0, int nb) {
+        return [&io, N, nb, u = pfnj::chunk_of(user, (size_t)b0, N)](auto& v) { pfnj::staging_arrays(v, io, u, (size_t)nb, N); };
+    };
+    if (pfspan::missing(chunk_list(0, 0))) return fail(h, PF_EINVAL, "null buffer");
     int chunk = 0;
     int rc = check_tree_shape(h, bionj ? BIONJ_SEARCH : NJ_SEARCH, B, N, &chunk);
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     ++(bionj ? h->bionj_calls : h->nj_calls);
-    // (chunks follow each other on the stream, so the next one reuses the state launch_nj_chunk reserved for the first)
-    const size_t PN = (size_t)N * (N - 1) / 2, T = (size_t)pfnj::table_len(N);
-    for (int b0 = 0; b0 < B; b0 += chunk)
-        if ((rc = launch_nj_chunk(h, bionj, d_preds + (size_t)b0 * PN, std::min(chunk, B - b0), N, d_slots + (size_t)b0 * T,
-                                  d_lengths + (size_t)b0 * T, d_flag + b0)))
-            return rc;
-    return PF_OK;
-}
-
-int nj_host_impl(pf_handle* h, bool bionj, const float* preds, int B, int N, int32_t* slots, double* lengths, uint8_t* flag) {
-    if (!preds || !slots || !lengths || !flag) return fail(h, PF_EINVAL, "null buffer");
-    int chunk = 0;
-    int rc = check_tree_shape(h, bionj ? BIONJ_SEARCH : NJ_SEARCH, B, N, &chunk);
-    if (rc) return rc;
-    HIPCHK(h, hipSetDevice(h->device));
-    ++(bionj ? h->bionj_calls : h->nj_calls);
-    const size_t PN = (size_t)N * (N - 1) / 2, T = (size_t)pfnj::table_len(N);
-    pfnj::Staging io{};
-    auto list = [&](auto& v) { pfnj::staging_arrays(v, io, (size_t)chunk, N); };
-    if ((rc = h->d_nj_io.reserve(h, pfspan::measure(list)))) return rc;
-    pfspan::carve(h->d_nj_io, list);
+    // (a flagged source's table is unspecified, not uninitialised: the staged tables are zeroed, the flags always written)
+    auto zero = [&](void*, void* staged, size_t bytes) { return staged == io.flag ? hipSuccess : hipMemsetAsync(staged, 0, bytes, h->stream); };
+    // (chunks follow each other on the stream, so the next one reuses the state launch_nj_chunk reserved for the first,
+    // and the staging the first - the largest - reserved)
     for (int b0 = 0; b0 < B; b0 += chunk) {
-        const size_t nb = (size_t)std::min(chunk, B - b0);
-        HIPCHK(h, hipMemcpyAsync(io.preds, preds + (size_t)b0 * PN, nb * PN * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        // (a flagged source's table is unspecified, not uninitialised)
-        HIPCHK(h, hipMemsetAsync(io.lengths, 0, nb * T * sizeof(double), h->stream));
-        HIPCHK(h, hipMemsetAsync(io.slots, 0, nb * T * sizeof(int32_t), h->stream));
-        if ((rc = launch_nj_chunk(h, bionj, io.preds, (int)nb, N, io.slots, io.lengths, io.flag))) return rc;
-        HIPCHK(h, hipMemcpyAsync(lengths + (size_t)b0 * T, io.lengths, nb * T * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(slots + (size_t)b0 * T, io.slots, nb * T * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(flag + b0, io.flag, nb, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
+        const int nb = std::min(chunk, B - b0);
+        if (device) rc = launch_nj_chunk(h, bionj, pfnj::chunk_of(user, (size_t)b0, N), nb, N);
+        else rc = staged_call(h, h->d_nj_io, chunk_list(b0, nb), [&]() -> int {
+            HIPCHK(h, (hipError_t)pfspan::download(chunk_list(b0, nb), zero));
+            return launch_nj_chunk(h, bionj, io, nb, N);
+        });
+        if (rc) return rc;
     }
     return PF_OK;
 }
@@ -2169,36 +2181,27 @@ int bme_chunk(pf_handle* h, bool spr, const float* d_preds, const int32_t* start
     return PF_OK;
 }
 
-// preds / start on the host (device = false) or on the device; the results likewise.  spr: the balanced SPR search
-// instead of balanced NNI.
-int bme_impl(pf_handle* h, bool spr, bool device, const float* preds, const int32_t* start, int B, int N, int32_t* slots, double* lengths,
-             int32_t* steps, double* tree_length, uint8_t* status) {
-    if (!preds || !start || !slots || !lengths || !steps || !tree_length || !status) return fail(h, PF_EINVAL, "null buffer");
+// preds and the caller's tables on the host (device = false) or on the device.  spr: the balanced SPR search instead
+// of balanced NNI.
+int bme_impl(pf_handle* h, bool spr, bool device, const float* preds, const pfbme::Tables& user, int B, int N) {
+    // The device form mirrors the caller's six arrays on the host, by the list a host form stages with, in the other
+    // direction: the start tables come down before the search, the five results go up after it.
+    pfbme::Tables io = user;
+    auto list = [&](auto& v) { pfbme::mirror_arrays(v, io, user, (size_t)B, N); };
+    if (!preds || pfspan::missing(list)) return fail(h, PF_EINVAL, "null buffer");
     int chunk = 0;
     int rc = check_tree_shape(h, spr ? SPR_SEARCH : NNI_SEARCH, B, N, &chunk);
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     try {
-        const size_t PN = (size_t)N * (N - 1) / 2, T = (size_t)pfnj::table_len(N), b = (size_t)B;
-        // The device form mirrors the caller's six arrays on the host, one list of {host, device, bytes} for both directions:
-        // the start tables come down before the search, the five outputs go up after it.
-        struct Mirror { void* host; void* device; size_t bytes; };
-        std::vector<Mirror> mir;
-        pfnj::Allocate own;
-        auto mirror = [&](auto* p, size_t count) {
-            auto* const dev = p;
-            if (device) { own(p, count); mir.push_back({p, dev, count * sizeof(*p)}); }
-            return p;
-        };
-        const int32_t* st_in = mirror(const_cast<int32_t*>(start), b * T);
-        int32_t *o_slots = mirror(slots, b * T), *o_steps = mirror(steps, b);
-        double *o_len = mirror(lengths, b * T), *o_tl = mirror(tree_length, b);
-        uint8_t* o_st = mirror(status, b);
+        const size_t PN = (size_t)N * (N - 1) / 2, T = (size_t)pfnj::table_len(N);
+        pfspan::Allocate own;
         if (device) {
-            HIPCHK(h, hipMemcpyAsync(mir[0].host, mir[0].device, mir[0].bytes, hipMemcpyDeviceToHost, h->stream));
+            list(own);
+            if ((rc = list_copy(h, list, true, hipMemcpyDeviceToHost))) return rc;
             HIPCHK(h, hipStreamSynchronize(h->stream));
         }
-        if ((rc = check_bme_starts(h, st_in, B, N))) return rc;
+        if ((rc = check_bme_starts(h, io.start, B, N))) return rc;
         ++(spr ? h->spr_calls : h->bme_calls);
         if (!device && (rc = h->d_bme_preds.reserve(h, (size_t)chunk * PN * sizeof(float)))) return rc;
         for (int b0 = 0; b0 < B; b0 += chunk) {
@@ -2208,12 +2211,12 @@ int bme_impl(pf_handle* h, bool spr, bool device, const float* preds, const int3
                 HIPCHK(h, hipMemcpyAsync(h->d_bme_preds, d_preds, (size_t)nb * PN * sizeof(float), hipMemcpyHostToDevice, h->stream));
                 d_preds = h->d_bme_preds;
             }
-            if ((rc = bme_chunk(h, spr, d_preds, st_in + (size_t)b0 * T, nb, N, o_slots + (size_t)b0 * T, o_len + (size_t)b0 * T,
-                                                    o_steps + b0, o_tl + b0, o_st + b0)))
+            if ((rc = bme_chunk(h, spr, d_preds, io.start + (size_t)b0 * T, nb, N, io.slots + (size_t)b0 * T, io.lengths + (size_t)b0 * T,
+                                io.steps + b0, io.tree_length + b0, io.status + b0)))
                 return rc;
         }
         if (device) {
-            for (size_t i = 1; i < mir.size(); ++i) HIPCHK(h, hipMemcpyAsync(mir[i].device, mir[i].host, mir[i].bytes, hipMemcpyHostToDevice, h->stream));
+            if ((rc = list_copy(h, list, false, hipMemcpyHostToDevice))) return rc;
             HIPCHK(h, hipStreamSynchronize(h->stream));
         }
     } catch (const std::bad_alloc&) { return fail(h, PF_ENOMEM, "out of host memory for the tables of N=%d sequences", N); }
@@ -2256,48 +2259,36 @@ int plan_supports(pf_handle* h, int B, int R, int N, int* nb, int* rc, bool arg 
     return PF_OK;
 }
 
-// all chunks of a call on device arrays, enqueued on h->stream; `more`: pf_join_transfers' results too
-int supports_launch(pf_handle* h, const int32_t* d_ref, const int32_t* d_rep, const uint8_t* d_flag, int B, int R, int N, int nb, int rc,
-                    int32_t* d_count, int64_t* d_transfer, int32_t* d_depth, uint8_t* d_status, const pfsup::Transfers* more = nullptr) {
-    int rc2 = h->d_sup.reserve(h, (size_t)nb * (more ? pfsup::transfer_state_bytes(N, rc) : pfsup::state_bytes(N, rc)));
+// all chunks of a call on device arrays `d`, enqueued on h->stream; `transfers`: pf_join_transfers' results too
+int supports_launch(pf_handle* h, const pfsup::Tables& d, int B, int R, int N, int nb, int rc, bool transfers, int cutoff) {
+    int rc2 = h->d_sup.reserve(h, (size_t)nb * (transfers ? pfsup::transfer_state_bytes(N, rc) : pfsup::state_bytes(N, rc)));
     if (rc2) return rc2;
     if ((rc2 = h->d_sup_bad.reserve(h, (size_t)B * ((size_t)R + 1)))) return rc2;
     h->cur = h->stream;
     HIPCHK(h, hipMemsetAsync(h->d_sup_bad, 0, (size_t)B * ((size_t)R + 1), h->stream));
     pfsup::Args a{};
-    a.ref_slots = d_ref; a.rep_slots = d_rep; a.rep_flag = d_flag; a.bad = h->d_sup_bad;
-    a.count = d_count; a.transfer = d_transfer; a.depth = d_depth; a.status = d_status;
+    a.ref_slots = d.ref; a.rep_slots = d.rep; a.rep_flag = d.flag; a.bad = h->d_sup_bad;
+    a.count = d.count; a.transfer = d.transfer; a.depth = d.depth; a.status = d.status;
     a.N = N; a.R = R;
-    pfsup::Transfers x{};
-    if (more) x = *more;
+    pfsup::Transfers x{nullptr, d.moves, d.used, d.capped, d.branch, cutoff};
+    pfsup::Transfers* const more = transfers ? &x : nullptr;
     // (chunks follow each other on the stream, so the next one may reuse the state)
     for (int b0 = 0; b0 < B; b0 += nb)
         for (int r0 = 0; r0 < R; r0 += rc) {
             a.b0 = b0; a.nb = std::min(nb, B - b0); a.r0 = r0; a.rc = std::min(rc, R - r0);
-            pfsup::carve(a, h->d_sup, more ? &x : nullptr);
-            const hipError_t e = pfsup::launch_chunk(h->stream, a, r0 == 0, more ? &x : nullptr);
+            pfsup::carve(a, h->d_sup, more);
+            const hipError_t e = pfsup::launch_chunk(h->stream, a, r0 == 0, more);
             if (e != hipSuccess) return fail(h, PF_EHIP, "k_sup_* launch failed: %s", hipGetErrorString(e));
         }
     return PF_OK;
 }
 
-int supports_device_impl(pf_handle* h, const int32_t* d_ref, const int32_t* d_rep, const uint8_t* d_flag, int B, int R, int N,
-                         int32_t* d_count, int64_t* d_transfer, int32_t* d_depth, uint8_t* d_status) {
-    if (!d_ref || !d_rep || !d_count || !d_transfer || !d_depth || !d_status) return fail(h, PF_EINVAL, "null buffer");
-    int nb = 0, rc = 0;
-    const int rc2 = plan_supports(h, B, R, N, &nb, &rc);
-    if (rc2) return rc2;
-    HIPCHK(h, hipSetDevice(h->device));
-    ++h->sup_calls;
-    return supports_launch(h, d_ref, d_rep, d_flag, B, R, N, nb, rc, d_count, d_transfer, d_depth, d_status);
-}
-
-// The tables of a host call (pf_join_supports, pf_join_transfers), validated as a start table is (a replicate passed with
-// its flag is never read: its table may be anything)
+// The tables of a host call, validated as a start table is (a replicate passed with its flag is never read: its table
+// may be anything); ref: pf_join_supports' and pf_join_transfers' reference tables, null for pf_join_consensus
 int check_join_tables(pf_handle* h, const int32_t* ref, const int32_t* rep, const uint8_t* flag, int B, int R, int N) {
     const size_t T = (size_t)pfnj::table_len(N), b = (size_t)B, r = (size_t)R;
     try {
-        const int rc = check_bme_starts(h, ref, B, N);
+        const int rc = ref ? check_bme_starts(h, ref, B, N) : PF_OK;
         if (rc) return rc;
         std::vector<int32_t> parent((size_t)pfbme::nodes_of(N)), children((size_t)pfbme::nodes_of(N) * 3);
         for (size_t i = 0; i < b * r; ++i)
@@ -2307,87 +2298,31 @@ int check_join_tables(pf_handle* h, const int32_t* ref, const int32_t* rep, cons
     return PF_OK;
 }
 
-int supports_host_impl(pf_handle* h, const int32_t* ref, const int32_t* rep, const uint8_t* flag, int B, int R, int N, int32_t* count,
-                       int64_t* transfer, int32_t* depth, uint8_t* status) {
-    if (!ref || !rep || !count || !transfer || !depth || !status) return fail(h, PF_EINVAL, "null buffer");
-    int nb = 0, rc = 0;
-    int rc2 = plan_supports(h, B, R, N, &nb, &rc);
-    if (rc2) return rc2;
-    const size_t T = (size_t)pfnj::table_len(N), S = (size_t)N - 3, b = (size_t)B, r = (size_t)R;
-    if ((rc2 = check_join_tables(h, ref, rep, flag, B, R, N))) return rc2;
-    HIPCHK(h, hipSetDevice(h->device));
-    ++h->sup_calls;
-    pfsup::Staging io{};
-    auto list = [&](auto& v) { pfsup::staging_arrays(v, io, b, r, N); };
-    if ((rc2 = h->d_sup_io.reserve(h, pfspan::measure(list)))) return rc2;
-    pfspan::carve(h->d_sup_io, list);
-    HIPCHK(h, hipMemcpyAsync(io.ref, ref, b * T * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(io.rep, rep, b * r * T * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    if (flag) HIPCHK(h, hipMemcpyAsync(io.flag, flag, b * r, hipMemcpyHostToDevice, h->stream));
-    if ((rc2 = supports_launch(h, io.ref, io.rep, flag ? io.flag : nullptr, B, R, N, nb, rc, io.count, io.transfer, io.depth, io.status)))
-        return rc2;
-    HIPCHK(h, hipMemcpyAsync(count, io.count, b * S * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(transfer, io.transfer, b * S * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(depth, io.depth, b * S * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(status, io.status, b, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return PF_OK;
-}
-
 // pf_join_transfers' own refusal, before the shared ones
 int check_cutoff(pf_handle* h, int cutoff) {
     if (cutoff < 0 || cutoff > 100) return fail(h, PF_EINVAL, "the transfer cutoff is a percent from 0 to 100 (got %d)", cutoff);
     return PF_OK;
 }
 
-int transfers_device_impl(pf_handle* h, const int32_t* d_ref, const int32_t* d_rep, const uint8_t* d_flag, int B, int R, int N, int cutoff,
-                          int32_t* d_count, int64_t* d_transfer, int32_t* d_depth, int64_t* d_moves, int32_t* d_used, int32_t* d_capped,
-                          int32_t* d_branch, uint8_t* d_status) {
-    if (!d_ref || !d_rep || !d_count || !d_transfer || !d_depth || !d_moves || !d_used || !d_capped || !d_status)
-        return fail(h, PF_EINVAL, "null buffer");
+// pf_join_supports or, `transfers`, pf_join_transfers (the same call with its Transfers part);
+// the caller's arrays on the device (asynchronous) or on the host
+int supports_impl(pf_handle* h, bool transfers, bool device, const pfsup::Tables& user, int B, int R, int N, int cutoff) {
+    pfsup::Tables io{};
+    auto list = [&](auto& v) { pfsup::staging_arrays(v, io, user, (size_t)B, (size_t)R, N, transfers, user.branch != nullptr); };
+    if (pfspan::missing(list)) return fail(h, PF_EINVAL, "null buffer");
     int nb = 0, rc = 0;
-    int rc2 = check_cutoff(h, cutoff);
-    if (rc2 || (rc2 = plan_supports(h, B, R, N, &nb, &rc, true))) return rc2;
+    int rc2 = transfers ? check_cutoff(h, cutoff) : PF_OK;
+    if (rc2 || (rc2 = plan_supports(h, B, R, N, &nb, &rc, transfers))) return rc2;
+    if (!device) {
+        size_t n = 0;
+        if (user.branch && !mul_size((size_t)B * ((size_t)N - 3), (size_t)N, sizeof(int32_t), &n))
+            return fail(h, PF_EINVAL, "B=%d tables of branch moves of N=%d sequences overflow the address space", B, N);
+        if ((rc2 = check_join_tables(h, user.ref, user.rep, user.flag, B, R, N))) return rc2;
+    }
     HIPCHK(h, hipSetDevice(h->device));
-    ++h->transfer_calls;
-    const pfsup::Transfers more{nullptr, d_moves, d_used, d_capped, d_branch, cutoff};
-    return supports_launch(h, d_ref, d_rep, d_flag, B, R, N, nb, rc, d_count, d_transfer, d_depth, d_status, &more);
-}
-
-int transfers_host_impl(pf_handle* h, const int32_t* ref, const int32_t* rep, const uint8_t* flag, int B, int R, int N, int cutoff,
-                        int32_t* count, int64_t* transfer, int32_t* depth, int64_t* moves, int32_t* used, int32_t* capped, int32_t* branch,
-                        uint8_t* status) {
-    if (!ref || !rep || !count || !transfer || !depth || !moves || !used || !capped || !status) return fail(h, PF_EINVAL, "null buffer");
-    int nb = 0, rc = 0;
-    int rc2 = check_cutoff(h, cutoff);
-    if (rc2 || (rc2 = plan_supports(h, B, R, N, &nb, &rc, true))) return rc2;
-    const size_t T = (size_t)pfnj::table_len(N), S = (size_t)N - 3, b = (size_t)B, r = (size_t)R;
-    size_t n = 0;
-    if (branch && !mul_size(b * S, (size_t)N, sizeof(int32_t), &n))
-        return fail(h, PF_EINVAL, "B=%d tables of branch moves of N=%d sequences overflow the address space", B, N);
-    if ((rc2 = check_join_tables(h, ref, rep, flag, B, R, N))) return rc2;
-    HIPCHK(h, hipSetDevice(h->device));
-    ++h->transfer_calls;
-    pfsup::TransferStaging io{};
-    auto list = [&](auto& v) { pfsup::transfer_staging_arrays(v, io, b, r, N, branch != nullptr); };
-    if ((rc2 = h->d_sup_io.reserve(h, pfspan::measure(list)))) return rc2;
-    pfspan::carve(h->d_sup_io, list);
-    HIPCHK(h, hipMemcpyAsync(io.ref, ref, b * T * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(io.rep, rep, b * r * T * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    if (flag) HIPCHK(h, hipMemcpyAsync(io.flag, flag, b * r, hipMemcpyHostToDevice, h->stream));
-    const pfsup::Transfers more{nullptr, io.moves, io.used, io.capped, branch ? io.branch : nullptr, cutoff};
-    if ((rc2 = supports_launch(h, io.ref, io.rep, flag ? io.flag : nullptr, B, R, N, nb, rc, io.count, io.transfer, io.depth, io.status, &more)))
-        return rc2;
-    HIPCHK(h, hipMemcpyAsync(count, io.count, b * S * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(transfer, io.transfer, b * S * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(depth, io.depth, b * S * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(moves, io.moves, b * (size_t)N * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(used, io.used, b * S * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(capped, io.capped, b * S * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    if (branch) HIPCHK(h, hipMemcpyAsync(branch, io.branch, b * S * (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(status, io.status, b, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return PF_OK;
+    ++(transfers ? h->transfer_calls : h->sup_calls);
+    if (device) return supports_launch(h, user, B, R, N, nb, rc, transfers, cutoff);
+    return staged_call(h, h->d_sup_io, list, [&] { return supports_launch(h, io, B, R, N, nb, rc, transfers, cutoff); });
 }
 
 // ---- majority-rule consensus of replicate join tables (pf_join_consensus, pf_join_consensus_device; pf_consensus.hip.h,
@@ -2422,29 +2357,26 @@ int plan_consensus(pf_handle* h, int B, int R, int N, int percent, int* nb) {
     return PF_OK;
 }
 
-struct ConsensusOut { int32_t *n_splits, *count, *size, *parent; double* split_length; int32_t* leaf_parent; double* leaf_length; uint8_t* status; };
-
-// all chunks of a call on device arrays, enqueued on h->stream
-int consensus_launch(pf_handle* h, const int32_t* d_rep, const double* d_lengths, const uint8_t* d_flag, int B, int R, int N, int percent,
-                     int nb, const ConsensusOut& o) {
+// all chunks of a call on device arrays `d`, enqueued on h->stream
+int consensus_launch(pf_handle* h, const pfcon::Tables& d, int B, int R, int N, int percent, int nb) {
     const int rc2 = h->d_con.reserve(h, (size_t)nb * pfcon::state_bytes(N, R));
     if (rc2) return rc2;
     h->cur = h->stream;
     const size_t S = (size_t)N - 3, b = (size_t)B;
     // (the first M entries are written; beyond them, and for a source with a status, the results are zeros)
-    HIPCHK(h, hipMemsetAsync(o.n_splits, 0, b * sizeof(int32_t), h->stream));
-    HIPCHK(h, hipMemsetAsync(o.count, 0, b * S * sizeof(int32_t), h->stream));
-    HIPCHK(h, hipMemsetAsync(o.size, 0, b * S * sizeof(int32_t), h->stream));
-    HIPCHK(h, hipMemsetAsync(o.parent, 0, b * S * sizeof(int32_t), h->stream));
-    HIPCHK(h, hipMemsetAsync(o.leaf_parent, 0, b * (size_t)N * sizeof(int32_t), h->stream));
-    if (d_lengths) {
-        HIPCHK(h, hipMemsetAsync(o.split_length, 0, b * S * sizeof(double), h->stream));
-        HIPCHK(h, hipMemsetAsync(o.leaf_length, 0, b * (size_t)N * sizeof(double), h->stream));
+    HIPCHK(h, hipMemsetAsync(d.n_splits, 0, b * sizeof(int32_t), h->stream));
+    HIPCHK(h, hipMemsetAsync(d.count, 0, b * S * sizeof(int32_t), h->stream));
+    HIPCHK(h, hipMemsetAsync(d.size, 0, b * S * sizeof(int32_t), h->stream));
+    HIPCHK(h, hipMemsetAsync(d.parent, 0, b * S * sizeof(int32_t), h->stream));
+    HIPCHK(h, hipMemsetAsync(d.leaf_parent, 0, b * (size_t)N * sizeof(int32_t), h->stream));
+    if (d.lengths) {
+        HIPCHK(h, hipMemsetAsync(d.split_length, 0, b * S * sizeof(double), h->stream));
+        HIPCHK(h, hipMemsetAsync(d.leaf_length, 0, b * (size_t)N * sizeof(double), h->stream));
     }
     pfcon::Args a{};
-    a.rep_slots = d_rep; a.rep_lengths = d_lengths; a.rep_flag = d_flag;
-    a.n_splits = o.n_splits; a.count = o.count; a.size = o.size; a.parent = o.parent; a.leaf_parent = o.leaf_parent;
-    a.split_length = o.split_length; a.leaf_length = o.leaf_length; a.status = o.status;
+    a.rep_slots = d.rep; a.rep_lengths = d.lengths; a.rep_flag = d.flag;
+    a.n_splits = d.n_splits; a.count = d.count; a.size = d.size; a.parent = d.parent; a.leaf_parent = d.leaf_parent;
+    a.split_length = d.split_length; a.leaf_length = d.leaf_length; a.status = d.status;
     a.N = N; a.R = R; a.percent = percent;
     a.cap = pfcon::capacity_of((int64_t)R * ((int64_t)N - 3));
     // (chunks follow each other on the stream, so the next one may reuse the state)
@@ -2457,59 +2389,20 @@ int consensus_launch(pf_handle* h, const int32_t* d_rep, const double* d_lengths
     return PF_OK;
 }
 
-int consensus_device_impl(pf_handle* h, const int32_t* d_rep, const double* d_lengths, const uint8_t* d_flag, int B, int R, int N,
-                          int percent, const ConsensusOut& o) {
-    if (!d_rep || !o.n_splits || !o.count || !o.size || !o.parent || !o.leaf_parent || !o.status ||
-        (d_lengths && (!o.split_length || !o.leaf_length)))
-        return fail(h, PF_EINVAL, "null buffer");
-    int nb = 0;
-    const int rc2 = plan_consensus(h, B, R, N, percent, &nb);
-    if (rc2) return rc2;
-    HIPCHK(h, hipSetDevice(h->device));
-    ++h->con_calls;
-    return consensus_launch(h, d_rep, d_lengths, d_flag, B, R, N, percent, nb, o);
-}
-
-int consensus_host_impl(pf_handle* h, const int32_t* rep, const double* lengths, const uint8_t* flag, int B, int R, int N, int percent,
-                        const ConsensusOut& o) {
-    if (!rep || !o.n_splits || !o.count || !o.size || !o.parent || !o.leaf_parent || !o.status ||
-        (lengths && (!o.split_length || !o.leaf_length)))
-        return fail(h, PF_EINVAL, "null buffer");
+// the caller's arrays on the device (asynchronous) or on the host
+int consensus_impl(pf_handle* h, bool device, const pfcon::Tables& user, int B, int R, int N, int percent) {
+    pfcon::Tables io{};
+    auto list = [&](auto& v) { pfcon::staging_arrays(v, io, user, (size_t)B, (size_t)R, N); };
+    if (pfspan::missing(list)) return fail(h, PF_EINVAL, "null buffer");
     int nb = 0;
     int rc2 = plan_consensus(h, B, R, N, percent, &nb);
-    if (rc2) return rc2;
-    const size_t T = (size_t)pfnj::table_len(N), S = (size_t)N - 3, b = (size_t)B, r = (size_t)R;
-    try {
-        // validated as a start table is (a replicate passed with its flag is never read: its table may be anything)
-        std::vector<int32_t> parent((size_t)pfbme::nodes_of(N)), children((size_t)pfbme::nodes_of(N) * 3);
-        for (size_t i = 0; i < b * r; ++i)
-            if (!(flag && flag[i]) && !pfbme::tree_of_joins(rep + i * T, N, parent.data(), children.data()))
-                return fail(h, PF_EINVAL, "source %zu: replicate %zu is not a join table of N=%d sequences", i / r, i % r, N);
-    } catch (const std::bad_alloc&) { return fail(h, PF_ENOMEM, "out of host memory for the tables of N=%d sequences", N); }
+    if (rc2 || (!device && (rc2 = check_join_tables(h, nullptr, user.rep, user.flag, B, R, N)))) return rc2;
     HIPCHK(h, hipSetDevice(h->device));
     ++h->con_calls;
-    pfcon::Staging io{};
-    auto list = [&](auto& v) { pfcon::staging_arrays(v, io, b, r, N, lengths != nullptr); };
-    if ((rc2 = h->d_con_io.reserve(h, pfspan::measure(list)))) return rc2;
-    pfspan::carve(h->d_con_io, list);
-    HIPCHK(h, hipMemcpyAsync(io.rep, rep, b * r * T * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    if (lengths) HIPCHK(h, hipMemcpyAsync(io.lengths, lengths, b * r * T * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (flag) HIPCHK(h, hipMemcpyAsync(io.flag, flag, b * r, hipMemcpyHostToDevice, h->stream));
-    const ConsensusOut d{io.n_splits, io.count, io.size, io.parent, io.split_length, io.leaf_parent, io.leaf_length, io.status};
-    if ((rc2 = consensus_launch(h, io.rep, lengths ? io.lengths : nullptr, flag ? io.flag : nullptr, B, R, N, percent, nb, d))) return rc2;
-    HIPCHK(h, hipMemcpyAsync(o.n_splits, io.n_splits, b * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(o.count, io.count, b * S * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(o.size, io.size, b * S * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(o.parent, io.parent, b * S * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(o.leaf_parent, io.leaf_parent, b * (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    if (lengths) {
-        HIPCHK(h, hipMemcpyAsync(o.split_length, io.split_length, b * S * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(o.leaf_length, io.leaf_length, b * (size_t)N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    }
-    HIPCHK(h, hipMemcpyAsync(o.status, io.status, b, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return PF_OK;
+    if (device) return consensus_launch(h, user, B, R, N, percent, nb);
+    return staged_call(h, h->d_con_io, list, [&] { return consensus_launch(h, io, B, R, N, percent, nb); });
 }
+
 
 }  // namespace
 
@@ -2850,92 +2743,92 @@ int pf_tile_combine_device(pf_handle_t* h, const float* d_sets, int32_t B, int32
 
 int pf_nj_joins(pf_handle_t* h, const float* preds, int32_t B, int32_t N, int32_t* slots, double* lengths, uint8_t* nonfinite) {
     if (!h) return PF_EINVAL;
-    return nj_host_impl(h, false, preds, B, N, slots, lengths, nonfinite);
+    return nj_impl(h, false, false, {preds, slots, lengths, nonfinite}, B, N);
 }
 
 int pf_nj_joins_device(pf_handle_t* h, const float* d_preds, int32_t B, int32_t N, int32_t* d_slots, double* d_lengths,
                        uint8_t* d_nonfinite) {
     if (!h) return PF_EINVAL;
-    return nj_device_impl(h, false, d_preds, B, N, d_slots, d_lengths, d_nonfinite);
+    return nj_impl(h, false, true, {d_preds, d_slots, d_lengths, d_nonfinite}, B, N);
 }
 
 int pf_bionj_joins(pf_handle_t* h, const float* preds, int32_t B, int32_t N, int32_t* slots, double* lengths, uint8_t* nonfinite) {
     if (!h) return PF_EINVAL;
-    return nj_host_impl(h, true, preds, B, N, slots, lengths, nonfinite);
+    return nj_impl(h, true, false, {preds, slots, lengths, nonfinite}, B, N);
 }
 
 int pf_bionj_joins_device(pf_handle_t* h, const float* d_preds, int32_t B, int32_t N, int32_t* d_slots, double* d_lengths,
                           uint8_t* d_nonfinite) {
     if (!h) return PF_EINVAL;
-    return nj_device_impl(h, true, d_preds, B, N, d_slots, d_lengths, d_nonfinite);
+    return nj_impl(h, true, true, {d_preds, d_slots, d_lengths, d_nonfinite}, B, N);
 }
 
 int pf_bme_nni(pf_handle_t* h, const float* preds, const int32_t* start_slots, int32_t B, int32_t N, int32_t* slots, double* lengths,
                int32_t* steps, double* tree_length, uint8_t* status) {
     if (!h) return PF_EINVAL;
-    return bme_impl(h, false, false, preds, start_slots, B, N, slots, lengths, steps, tree_length, status);
+    return bme_impl(h, false, false, preds, {start_slots, slots, steps, lengths, tree_length, status}, B, N);
 }
 
 int pf_bme_nni_device(pf_handle_t* h, const float* d_preds, const int32_t* d_start_slots, int32_t B, int32_t N, int32_t* d_slots,
                       double* d_lengths, int32_t* d_steps, double* d_tree_length, uint8_t* d_status) {
     if (!h) return PF_EINVAL;
-    return bme_impl(h, false, true, d_preds, d_start_slots, B, N, d_slots, d_lengths, d_steps, d_tree_length, d_status);
+    return bme_impl(h, false, true, d_preds, {d_start_slots, d_slots, d_steps, d_lengths, d_tree_length, d_status}, B, N);
 }
 
 int pf_bme_spr(pf_handle_t* h, const float* preds, const int32_t* start_slots, int32_t B, int32_t N, int32_t* slots, double* lengths,
                int32_t* steps, double* tree_length, uint8_t* status) {
     if (!h) return PF_EINVAL;
-    return bme_impl(h, true, false, preds, start_slots, B, N, slots, lengths, steps, tree_length, status);
+    return bme_impl(h, true, false, preds, {start_slots, slots, steps, lengths, tree_length, status}, B, N);
 }
 
 int pf_bme_spr_device(pf_handle_t* h, const float* d_preds, const int32_t* d_start_slots, int32_t B, int32_t N, int32_t* d_slots,
                       double* d_lengths, int32_t* d_steps, double* d_tree_length, uint8_t* d_status) {
     if (!h) return PF_EINVAL;
-    return bme_impl(h, true, true, d_preds, d_start_slots, B, N, d_slots, d_lengths, d_steps, d_tree_length, d_status);
+    return bme_impl(h, true, true, d_preds, {d_start_slots, d_slots, d_steps, d_lengths, d_tree_length, d_status}, B, N);
 }
 
 int pf_join_supports(pf_handle_t* h, const int32_t* ref_slots, const int32_t* rep_slots, const uint8_t* rep_flag, int32_t B, int32_t R,
                      int32_t N, int32_t* count, int64_t* transfer, int32_t* depth, uint8_t* status) {
     if (!h) return PF_EINVAL;
-    return supports_host_impl(h, ref_slots, rep_slots, rep_flag, B, R, N, count, transfer, depth, status);
+    return supports_impl(h, false, false, {ref_slots, rep_slots, rep_flag, count, transfer, depth, status}, B, R, N, 0);
 }
 
 int pf_join_supports_device(pf_handle_t* h, const int32_t* d_ref_slots, const int32_t* d_rep_slots, const uint8_t* d_rep_flag, int32_t B,
                             int32_t R, int32_t N, int32_t* d_count, int64_t* d_transfer, int32_t* d_depth, uint8_t* d_status) {
     if (!h) return PF_EINVAL;
-    return supports_device_impl(h, d_ref_slots, d_rep_slots, d_rep_flag, B, R, N, d_count, d_transfer, d_depth, d_status);
+    return supports_impl(h, false, true, {d_ref_slots, d_rep_slots, d_rep_flag, d_count, d_transfer, d_depth, d_status}, B, R, N, 0);
 }
 
 int pf_join_consensus(pf_handle_t* h, const int32_t* rep_slots, const double* rep_lengths, const uint8_t* rep_flag, int32_t B, int32_t R,
                       int32_t N, int32_t percent, int32_t* n_splits, int32_t* count, int32_t* size, int32_t* parent, double* split_length,
                       int32_t* leaf_parent, double* leaf_length, uint8_t* status) {
     if (!h) return PF_EINVAL;
-    return consensus_host_impl(h, rep_slots, rep_lengths, rep_flag, B, R, N, percent,
-                               ConsensusOut{n_splits, count, size, parent, split_length, leaf_parent, leaf_length, status});
+    return consensus_impl(h, false, {rep_slots, rep_lengths, rep_flag, n_splits, count, size, parent, split_length, leaf_parent, leaf_length, status},
+                          B, R, N, percent);
 }
 
 int pf_join_consensus_device(pf_handle_t* h, const int32_t* d_rep_slots, const double* d_rep_lengths, const uint8_t* d_rep_flag, int32_t B,
                              int32_t R, int32_t N, int32_t percent, int32_t* d_n_splits, int32_t* d_count, int32_t* d_size,
                              int32_t* d_parent, double* d_split_length, int32_t* d_leaf_parent, double* d_leaf_length, uint8_t* d_status) {
     if (!h) return PF_EINVAL;
-    return consensus_device_impl(h, d_rep_slots, d_rep_lengths, d_rep_flag, B, R, N, percent,
-                                 ConsensusOut{d_n_splits, d_count, d_size, d_parent, d_split_length, d_leaf_parent, d_leaf_length, d_status});
+    return consensus_impl(h, true, {d_rep_slots, d_rep_lengths, d_rep_flag, d_n_splits, d_count, d_size, d_parent, d_split_length, d_leaf_parent,
+                                    d_leaf_length, d_status}, B, R, N, percent);
 }
 
 int pf_join_transfers(pf_handle_t* h, const int32_t* ref_slots, const int32_t* rep_slots, const uint8_t* rep_flag, int32_t B, int32_t R,
                       int32_t N, int32_t cutoff_percent, int32_t* count, int64_t* transfer, int32_t* depth, int64_t* moves, int32_t* used,
                       int32_t* capped, int32_t* branch_moves, uint8_t* status) {
     if (!h) return PF_EINVAL;
-    return transfers_host_impl(h, ref_slots, rep_slots, rep_flag, B, R, N, cutoff_percent, count, transfer, depth, moves, used, capped,
-                               branch_moves, status);
+    return supports_impl(h, true, false, {ref_slots, rep_slots, rep_flag, count, transfer, depth, status, moves, used, capped, branch_moves},
+                         B, R, N, cutoff_percent);
 }
 
 int pf_join_transfers_device(pf_handle_t* h, const int32_t* d_ref_slots, const int32_t* d_rep_slots, const uint8_t* d_rep_flag, int32_t B,
                              int32_t R, int32_t N, int32_t cutoff_percent, int32_t* d_count, int64_t* d_transfer, int32_t* d_depth,
                              int64_t* d_moves, int32_t* d_used, int32_t* d_capped, int32_t* d_branch_moves, uint8_t* d_status) {
     if (!h) return PF_EINVAL;
-    return transfers_device_impl(h, d_ref_slots, d_rep_slots, d_rep_flag, B, R, N, cutoff_percent, d_count, d_transfer, d_depth, d_moves,
-                                 d_used, d_capped, d_branch_moves, d_status);
+    return supports_impl(h, true, true, {d_ref_slots, d_rep_slots, d_rep_flag, d_count, d_transfer, d_depth, d_status, d_moves, d_used, d_capped,
+                                     d_branch_moves}, B, R, N, cutoff_percent);
 }
 
 int pf_forward_device(pf_handle_t* h, const uint8_t* d_idx, int32_t B, int32_t N, int32_t L, float* d_out) {

@@ -294,15 +294,28 @@ inline Args carve(char* ws, const float* preds, int B, int N, int32_t* slots, do
     return a;
 }
 
-// The staging of one chunk of a host call (pf_nj_joins): what goes up and what comes down.
-struct Staging { double* lengths; float* preds; int32_t* slots; uint8_t* flag; };
+// The arrays of a call (pf_nj_joins, pf_bionj_joins) as the caller or the staging of a chunk holds them, and the caller's
+// from source b0 on.
+struct Tables { const float* preds; int32_t* slots; double* lengths; uint8_t* flag; };
+inline Tables chunk_of(const Tables& u, size_t b0, int N) {
+    const size_t T = (size_t)table_len(N), PN = (size_t)N * ((size_t)N - 1) / 2;
+    return {u.preds + b0 * PN, u.slots + b0 * T, u.lengths + b0 * T, u.flag + b0};
+}
+// The staging `s` of one chunk of a host call with the caller's arrays `u`: what goes up and what comes down.
+template <class V>
+inline void staging_arrays(V& v, Tables& s, const Tables& u, size_t chunk, int N) {
+    const size_t T = (size_t)table_len(N), PN = (size_t)N * ((size_t)N - 1) / 2;
+    v.out(s.lengths, u.lengths, chunk * T);
+    v.in(s.preds, u.preds, chunk * PN);
+    v.out(s.slots, u.slots, chunk * T);
+    v.out(s.flag, u.flag, chunk);
+}
+// the layout alone, for a visitor with operator() only
+using Staging = Tables;
 template <class V>
 inline void staging_arrays(V& v, Staging& s, size_t chunk, int N) {
-    const size_t T = (size_t)table_len(N), PN = (size_t)N * ((size_t)N - 1) / 2;
-    v(s.lengths, chunk * T);
-    v(s.preds, chunk * PN);
-    v(s.slots, chunk * T);
-    v(s.flag, chunk);
+    pfspan::StagingOnly<V> only{v};
+    staging_arrays(only, s, Tables{}, chunk, N);
 }
 
 }  // namespace pfnj

@@ -72,30 +72,44 @@ struct Transfers {
     int cutoff;                 // percent, 0 .. 100
 };
 
-// The staging of a whole host call (pf_join_supports): the tables that go up and the results that come down.
-struct Staging { int64_t* transfer; int32_t *ref, *rep, *count, *depth; uint8_t *flag, *status; };
+// The arrays of a call (pf_join_supports; pf_join_transfers: the last four too) as the caller or the staging holds them.
+struct Tables {
+    const int32_t *ref, *rep;
+    const uint8_t* flag;
+    int32_t* count; int64_t* transfer; int32_t* depth; uint8_t* status;
+    int64_t* moves; int32_t *used, *capped, *branch;
+};
+// The staging `s` of a whole host call with the caller's arrays `u`: the tables that go up and the results that come
+// down; `transfers`: pf_join_transfers' four results more, of which branch_moves where `branch` (the caller asks for
+// it).  A null rep_flag keeps its span.
+template <class V>
+inline void staging_arrays(V& v, Tables& s, const Tables& u, size_t B, size_t R, int N, bool transfers, bool branch) {
+    const size_t T = (size_t)table_len(N), S = (size_t)N - 3;
+    v.out(s.transfer, u.transfer, B * S);
+    v.in(s.ref, u.ref, B * T);
+    v.in(s.rep, u.rep, B * R * T);
+    v.out(s.count, u.count, B * S);
+    v.out(s.depth, u.depth, B * S);
+    v.in(s.flag, u.flag, B * R, pfspan::OPTIONAL);
+    v.out(s.status, u.status, B);
+    if (!transfers) return;
+    v.out(s.moves, u.moves, B * (size_t)N);
+    v.out(s.used, u.used, B * S);
+    v.out(s.capped, u.capped, B * S);
+    v.out(s.branch, u.branch, B * S * (size_t)N, branch ? pfspan::REQUIRED : pfspan::ABSENT);
+}
+// the layouts alone, for a visitor with operator() only: pf_join_supports' and pf_join_transfers'
+using Staging = Tables;
+using TransferStaging = Tables;
 template <class V>
 inline void staging_arrays(V& v, Staging& s, size_t B, size_t R, int N) {
-    const size_t T = (size_t)table_len(N), S = (size_t)N - 3;
-    v(s.transfer, B * S);
-    v(s.ref, B * T);
-    v(s.rep, B * R * T);
-    v(s.count, B * S);
-    v(s.depth, B * S);
-    v(s.flag, B * R);
-    v(s.status, B);
+    pfspan::StagingOnly<V> only{v};
+    staging_arrays(only, s, Tables{}, B, R, N, false, false);
 }
-
-// The staging of pf_join_transfers: the same, and the four results more (branch: branch_moves is asked for).
-struct TransferStaging : Staging { int64_t* moves; int32_t *used, *capped, *branch; };
 template <class V>
 inline void transfer_staging_arrays(V& v, TransferStaging& s, size_t B, size_t R, int N, bool branch) {
-    const size_t S = (size_t)N - 3;
-    staging_arrays(v, s, B, R, N);
-    v(s.moves, B * (size_t)N);
-    v(s.used, B * S);
-    v(s.capped, B * S);
-    v(s.branch, branch ? B * S * (size_t)N : 0);
+    pfspan::StagingOnly<V> only{v};
+    staging_arrays(only, s, Tables{}, B, R, N, true, branch);
 }
 
 PF_TAXA_HD inline size_t tree_index(const Args& a, int src, int k) { return (size_t)src * (size_t)(a.rc + 1) + (size_t)k; }

@@ -5,7 +5,7 @@ import numpy as np
 # (B, N, L, R, (tiled N, tiled M)) of the three visits: the buffers grow at the second and are reused, too large, at the third
 VISITS = ((1, 4, 8, 2, (9, 4)), (2, 9, 40, 5, (5, 2)), (1, 4, 8, 2, (9, 4)))
 NAMES = ("forward", "forward_weighted", "forward_site_profile", "forward_leave_one_out", "forward_place", "forward_tiled",
-         "nj_joins", "bme_nni", "bme_spr", "join_supports")
+         "nj_joins", "bionj_joins", "bme_nni", "bme_spr", "join_supports", "join_transfers", "join_consensus")
 
 
 def random_tables(rng, shape, n: int) -> np.ndarray:
@@ -32,6 +32,7 @@ def calls(visit: int):
     preds = rng.uniform(0.01, 3.0, size=(B, N * (N - 1) // 2)).astype(np.float32)
     start = random_tables(rng, (B,), N)
     ref, rep = random_tables(rng, (B,), N), random_tables(rng, (B, R), N)
+    rep_lengths = rng.uniform(0.01, 1.0, size=rep.shape)
     tup = lambda x: x if isinstance(x, tuple) else (x,)
     return {
         "forward": lambda e: tup(e.forward(idx)),
@@ -41,9 +42,12 @@ def calls(visit: int):
         "forward_place": lambda e: tup(e.forward_place(idx, 1, keep_sets=True)),
         "forward_tiled": lambda e: tup(e.forward_tiled(big, TM)),
         "nj_joins": lambda e: tup(e.nj_joins(preds)),
+        "bionj_joins": lambda e: tup(e.bionj_joins(preds)),
         "bme_nni": lambda e: tup(e.bme_nni(preds, start)),
         "bme_spr": lambda e: tup(e.bme_spr(preds, start)),
         "join_supports": lambda e: tup(e.join_supports(ref, rep)),
+        "join_transfers": lambda e: tup(e.join_transfers(ref, rep, branch_moves=True)),
+        "join_consensus": lambda e: tup(e.join_consensus(rep, rep_lengths)),
     }
 
 
