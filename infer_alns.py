@@ -28,7 +28,7 @@ import sys
 import time
 from glob import glob
 
-from phyloformer_amd import analyses
+from phyloformer_amd import analyses, treekinds
 
 PRECISE = {"auto": -1, "always": 1, "never": 0}      # --precise -> the engine's option "precise"
 
@@ -92,18 +92,10 @@ def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
     modes = analyses.modes_from_args(args, parser.error)
-    if args.bme and not args.trees:
-        parser.error("--bme refines the tree of --trees: give -t as well")
-    if args.bme and args.shard == "sites":
-        parser.error("--bme cannot be combined with --shard sites: the site-sharded runner writes NJ trees only")
-    if args.spr and not args.trees:
-        parser.error("--spr refines the tree of --trees: give -t as well")
-    if args.spr and args.shard == "sites":
-        parser.error("--spr cannot be combined with --shard sites: the site-sharded runner writes NJ trees only")
-    if args.bionj and not args.trees:
-        parser.error("--bionj writes a tree beside that of --trees: give -t as well")
-    if args.bionj and args.shard == "sites":
-        parser.error("--bionj cannot be combined with --shard sites: the site-sharded runner writes NJ trees only")
+    tree_flags = [flag for flag in treekinds.FLAGS if getattr(args, flag[2:])]
+    refused = next(treekinds.refusals(tree_flags, args.trees, args.shard == "sites"), None)
+    if refused is not None:
+        parser.error(refused)
 
     from phyloformer_amd import scheduler
 

@@ -15,6 +15,8 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from .treekinds import NJ, NJ_STARTED, Kind, SupportTables, join_refine, reaches, with_stand_ins
+
 # Result floats of one engine call behind the launch's forward (16 MiB): the replicate distances of a pf_bootstrap call,
 # the window distances of a pf_forward_windows call, the distances of the cuts (N x P1 floats per alignment) of a
 # pf_forward_leave_one_out call, the distances of the query sets (Q x P_{N+1} floats per alignment) of a pf_forward_place
@@ -213,157 +215,108 @@ class Bootstrap(Analysis):
 
     def write(self, runner, shape, entry, pred, reps):
         """``<stem>.sup.nwk``: the NJ tree of ``pred`` with the supports of ``reps``."""
-        runner.put(entry.path, "sup.nwk", self._nj_support(runner, pred, reps, entry.ids()))
-
-    @staticmethod
-    def _nj_support(runner, pred, reps, ids):
-        if runner.native_io:
-            from .hostio import nj_support
-            return nj_support(pred, reps, ids, threads=runner.writer_cap())
-        from .bootstrap import support_newick_py
-        return support_newick_py(pred, reps, ids)
+        runner.put(entry.path, "sup.nwk", runner.host.nj_support(pred, reps, entry.ids(), runner.writer_cap()))
 
     # -- --tbe / --bootstrap-refined (supports.py, DESIGN.md section 23) -----------------------------------------------
-    def kinds(self, runner) -> List[str]:
+    def kinds(self, runner) -> List[Kind]:
         """The trees that get supports: NJ (``.sup.nwk``, from the same replicate NJ tables as every other output), and
         with ``--bootstrap-refined`` those of ``--bme`` / ``--spr``."""
-        return ["nj"] + [k for k in ("bme", "spr") if self.refined and getattr(runner, k)]
+        return [k for k in NJ_STARTED if k.search is None or (self.refined and set(k.flags) <= set(runner.flags))]
+
+    def _match(self, who, ref_slots, rep_slots, rep_flag) -> tuple:
+        """The supports by ``who``, without the status; with ``--instability`` the transfers, whose first three arrays they are."""
+        if self.instability is not None:
+            return who.join_transfers(ref_slots, rep_slots, rep_flag, self.instability)[:-1]
+        return who.join_supports(ref_slots, rep_slots, rep_flag)[:-1]
 
     def _extend(self, runner, engine, shape, preds, reps):
-        """On the GPU thread, behind ``follow``: what of the supports runs on the device.  From ``bme.BME_DEVICE_MIN`` /
-        ``bme.SPR_DEVICE_MIN`` sequences on the NJ tables of all ``B (R + 1)`` trees of the sub-batch and their refinement
-        (``Engine.nj_joins`` + ``Engine.bme_nni`` / ``bme_spr``), from ``supports.SUPPORT_DEVICE_MIN`` on the matching
-        (``Engine.join_supports``) of every kind whose tables are the device's (NJ's: joined there for it), from
-        ``consensus.CONSENSUS_DEVICE_MIN`` on their ``--consensus`` (``Engine.join_consensus``).  With ``--instability``
-        the one ``Engine.join_transfers`` call, from ``supports.TRANSFER_DEVICE_MIN`` on, stands in ``join_supports``'
-        place - the matching never runs twice - and ``results`` has its seven arrays.  Returns the
-        columns ``(reps, tables)``, ``tables[b][kind]`` = ``(slots, lengths, rep_slots, rep_flag, results or None,
-        rep_lengths, consensus or None)`` or absent: that kind of that file runs on its writer thread."""
-        from . import bme, consensus, supports
+        """On the GPU thread, behind ``follow``: from a kind's threshold on the NJ tables of all ``B (R + 1)`` trees of the
+        sub-batch and their refinement, from ``SUPPORT_DEVICE_MIN`` (``--instability``: ``TRANSFER_DEVICE_MIN``) on the matching
+        of every kind whose tables are the device's (NJ's: joined there for it), from ``CONSENSUS_DEVICE_MIN`` on their consensus.
+        Returns the columns ``(reps, tables)``: ``tables[b][kind name]`` is a ``SupportTables``, or absent (the writer's work)."""
+        from . import consensus, supports
         B, R, n = len(preds), self.replicates, shape[0]
         tables = [{} for _ in range(B)]
-
-        def reaches(minimum):
-            return n >= 4 and minimum is not None and n >= minimum
-        kinds = self.kinds(runner)
-        refine = [k for k in kinds if k != "nj" and reaches(getattr(bme, runner.REFINEMENTS[k][3]))]
+        refine = [k for k in self.kinds(runner) if k.search is not None and reaches(k.minimum(), n, 4)]
         moves = self.instability is not None
-        match = reaches(supports.TRANSFER_DEVICE_MIN if moves else supports.SUPPORT_DEVICE_MIN)
-        agree = self.consensus is not None and reaches(consensus.CONSENSUS_DEVICE_MIN)
+        match = reaches(supports.TRANSFER_DEVICE_MIN if moves else supports.SUPPORT_DEVICE_MIN, n, 4)
+        agree = self.consensus is not None and reaches(consensus.CONSENSUS_DEVICE_MIN, n, 4)
         if not refine and not match and not agree:
             return reps, tables
         t0 = time.perf_counter()
         every = np.concatenate([preds[:, None, :], reps], axis=1).reshape(B * (R + 1), -1)       # own tree first
-        nj_slots, nj_lengths, nonfinite = engine.nj_joins(every)
-        bad = np.asarray(nonfinite, dtype=bool)
-        made = {"nj": (nj_slots, nj_lengths, bad)}               # (joined once: they serve every output)
-        # (a flagged source's joins are unspecified: any valid start table stands in, its result is not used)
-        start = np.where(bad[:, None], bme.caterpillar_slots(n)[None, :], nj_slots)
-        for k in refine:
-            slots, lengths, _steps, _length, status = getattr(engine, runner.REFINEMENTS[k][2])(every, start)
-            made[k] = (slots, lengths, bad | (status == bme.NONFINITE))
+        made = join_refine(engine, "nj", [k.search for k in refine], every)      # (joined once: they serve every output)
         matched = agreed = 0
-        for k, (slots, lengths, flag) in made.items():
-            slots, lengths, flag = (x.reshape(B, R + 1, *x.shape[1:]) for x in (slots, lengths, flag))
+        for kind in [NJ] + refine:
+            slots, lengths, _steps, flag = (x.reshape(B, R + 1, *x.shape[1:]) for x in made[kind.search])
             res = con = None
             if match:
-                ref = np.where(flag[:, :1], bme.caterpillar_slots(n)[None, :], slots[:, 0])       # (its result is not used)
-                res = (engine.join_transfers(ref, slots[:, 1:], flag[:, 1:], self.instability)[:7] if moves else
-                       engine.join_supports(ref, slots[:, 1:], flag[:, 1:])[:3])
+                res = self._match(engine, with_stand_ins(slots[:, 0], flag[:, 0]), slots[:, 1:], flag[:, 1:])
             if agree:
                 con = engine.join_consensus(slots[:, 1:], lengths[:, 1:], flag[:, 1:], self.consensus)
             for b in range(B):
                 if flag[b, 0]:
                     continue                                     # no tree of its own: the writer's plain text
-                tables[b][k] = (slots[b, 0], lengths[b, 0], slots[b, 1:], flag[b, 1:], None if res is None else tuple(x[b] for x in res),
-                                lengths[b, 1:], None if con is None else tuple(x[b] for x in con))
+                tables[b][kind.name] = SupportTables(
+                    slots[b, 0], lengths[b, 0], slots[b, 1:], flag[b, 1:], None if res is None else tuple(x[b] for x in res),
+                    lengths[b, 1:], None if con is None else tuple(x[b] for x in con))
                 matched += res is not None
                 agreed += con is not None
         runner.book(supports_device=matched, supports_device_s=time.perf_counter() - t0, **({"consensus_device": agreed} if agree else {}),
                     **({"transfers_device": matched} if moves else {}))
         return reps, tables
 
-    def _host_tables(self, runner, kind, pred, reps, n):
-        """One file's tables of one kind on a writer thread, by the host twins: ``(slots, lengths, rep_slots, rep_flag,
-        None, rep_lengths, None)`` (``_extend``'s layout); ``slots`` None where the file's own distances are not finite."""
-        from . import bme, hostio, supports
-        if not runner.native_io:
-            slots, lengths, rep_slots, rep_flag, rep_lengths = supports.kind_tables(pred, reps, n, kind, with_lengths=True)
-            return (slots, lengths, rep_slots, rep_flag, None, rep_lengths, None)
+    def _host_tables(self, runner, kind, pred, reps) -> SupportTables:
+        """One file's tables of one kind on a writer thread, by the runner's host side."""
         every = np.concatenate([np.asarray(pred, dtype=np.float32).reshape(1, -1), reps])
-        slots, lengths, bad = hostio.nj_joins_host(every)
-        if kind != "nj":
-            start = np.where(bad[:, None], bme.caterpillar_slots(n)[None, :], slots)
-            slots, lengths, _steps, _length, status = getattr(hostio, runner.REFINEMENTS[kind][2] + "_host")(every, start)
-            bad = bad | (status == bme.NONFINITE)
-        return (None if bad[0] else slots[0], lengths[0], slots[1:], bad[1:], None, lengths[1:], None)
+        slots, lengths, _steps, bad = join_refine(runner.host, "nj", [s for s in (kind.search,) if s], every)[kind.search]
+        return SupportTables(None if bad[0] else slots[0], lengths[0], slots[1:], bad[1:], None, lengths[1:], None)
 
     def write_supports(self, runner, shape, rows):
         """Some files of a sub-batch on a writer thread: per kind of tree ``<stem>[.<kind>].sup.nwk`` and, with ``--tbe``,
-        ``<stem>[.<kind>].tbe.nwk``.  Tables and results the GPU thread left are formatted; the others come from the host
-        twins first (the serial ``pf_join_supports_host``; with ``--python-io`` ``supports.py`` itself).  With
-        ``--consensus`` also ``<stem>[.<kind>].con.nwk``, from the same replicate tables (``consensus.py``).  With
-        ``--instability`` the supports are ``join_transfers``' first three arrays and its other results give
-        ``<stem>[.<kind>].instability.tsv``, ``.branches.tsv`` and ``.branches.nwk`` (``supports.instability_texts``)."""
-        from . import consensus, hostio, supports
-        n, R = shape[0], self.replicates
+        ``<stem>[.<kind>].tbe.nwk``.  Tables and results the GPU thread left are formatted; the others come from the
+        runner's host side first.  With ``--consensus`` also ``<stem>[.<kind>].con.nwk``, from the same replicate tables;
+        with ``--instability`` the transfers' other results give the three files of ``supports.instability_texts``."""
+        from . import supports
+        from .consensus import newick_of_consensus, star
+        n, R, host, cap = shape[0], self.replicates, runner.host, runner.writer_cap()
+        kinds = self.kinds(runner)
         for entry, pred, reps, given in rows:
             ids = entry.ids()
-            for kind in self.kinds(runner):
-                sup, tbe = supports.SUFFIXES[kind]
-                table = None
+            for kind in kinds:
+                table = None                                 # (fewer than four sequences: no split)
                 if n >= 4:
-                    table = given.get(kind) or self._host_tables(runner, kind, pred, reps, n)
-                moved = None
-                if table is None or table[0] is None:       # no split, or no tree of the file's own distances: the kind's plain text
-                    text = self._nj_support(runner, pred, reps, ids) if kind == "nj" else runner.bme_tree(pred, ids, kind)[0]
-                    texts = (text, text)
-                    if self.instability is not None:
-                        moved = supports.instability_texts(None, None, ids, None, R, _text(text))
+                    table = given[kind.name] if kind.name in given else self._host_tables(runner, kind, pred, reps)
+                if table is None or table.slots is None:    # no split, or no tree of its own: the plain text
+                    text = host.nj_support(pred, reps, ids, cap) if kind.search is None else host.tree_text(kind, pred, ids)[0]
+                    texts, slots, lengths, res = (text, text), None, None, None
                 else:
-                    slots, lengths, rep_slots, rep_flag = table[:4]
-                    res = table[4]
-                    if res is None and self.instability is not None:
-                        res = (hostio.join_transfers_host(slots, rep_slots, rep_flag, self.instability)[:7] if runner.native_io else
-                               supports.transfer_tuple(supports.transfer_taxa(slots, rep_slots, n, rep_flag, self.instability)))
-                    elif res is None and runner.native_io:
-                        res = hostio.join_supports_host(slots, rep_slots, rep_flag)[:3]
-                    elif res is None:
-                        res = supports.split_supports(slots, rep_slots, n, rep_flag)
+                    slots, lengths = table.slots, table.lengths
+                    res = table.results
+                    if res is None:
+                        res = self._match(host, slots, table.rep_slots, table.rep_flag)
                     texts = supports.support_texts(slots, lengths, ids, *res[:3], R)
-                    if self.instability is not None:
-                        moved = supports.instability_texts(slots, lengths, ids, res, R)
-                for suffix, text in zip(supports.INSTABILITY_SUFFIXES[kind], moved or ()):
+                if self.instability is not None:
+                    moved = supports.instability_texts(slots, lengths, ids, res, R, _text(texts[0]))
+                    for suffix, text in zip(kind.files("instability.tsv", "branches.tsv", "branches.nwk"), moved):
+                        runner.put(entry.path, suffix, text)
+                for suffix, text in zip(kind.files("sup.nwk", "tbe.nwk"), texts[:1 + self.tbe]):
                     runner.put(entry.path, suffix, text)
-                runner.put(entry.path, sup, texts[0])
-                if self.tbe:
-                    runner.put(entry.path, tbe, texts[1])
                 if self.consensus is not None:
-                    runner.put(entry.path, consensus.SUFFIXES[kind], self._consensus_text(runner, table, ids))
-        kinds = len(self.kinds(runner))
-        runner.book(tbe=len(rows) * kinds if self.tbe else 0, refined_supports=len(rows) * (kinds - 1),
-                    **({"consensus": len(rows) * kinds} if self.consensus is not None else {}),
-                    **({"instability": len(rows) * kinds} if self.instability is not None else {}))
-
-    def _consensus_text(self, runner, table, ids):
-        """``<stem>[.<kind>].con.nwk`` of one file from its replicate tables (None: fewer than four sequences - the star):
-        the GPU thread's results where it left them, else the serial twin's, with ``--python-io`` the statement's."""
-        from . import consensus, hostio
-        n, R = len(ids), self.replicates
-        if table is None:
-            return consensus.newick_of_consensus(ids, consensus.star(n), R)
-        _slots, _lengths, rep_slots, rep_flag, _res, rep_lengths, con = table
-        if con is None and runner.native_io:
-            con = hostio.join_consensus_host(rep_slots, rep_lengths, rep_flag, self.consensus)
-        elif con is None:
-            con = consensus.join_consensus(rep_slots, n, rep_lengths, rep_flag, self.consensus)
-        return consensus.newick_of_consensus(ids, con, R)
+                    # (no table: fewer than four sequences - the star; else the GPU thread's results where it left them)
+                    con = star(n) if table is None else table.consensus
+                    if con is None:
+                        con = host.join_consensus(table.rep_slots, table.rep_lengths, table.rep_flag, self.consensus)
+                    runner.put(entry.path, kind.files("con.nwk")[0], newick_of_consensus(ids, con, R))
+        runner.book(tbe=len(rows) * len(kinds) if self.tbe else 0, refined_supports=len(rows) * (len(kinds) - 1),
+                    **({"consensus": len(rows) * len(kinds)} if self.consensus is not None else {}),
+                    **({"instability": len(rows) * len(kinds)} if self.instability is not None else {}))
 
     def jobs(self, runner, shape, part, preds, reps, tables=None):
         if tables is None:
             return super().jobs(runner, shape, part, preds, reps)
         rows = list(zip(part, preds, reps, tables))
-        cap = runner.writer_cap()       # (the host twins of R searches per file: spread over the writers, as _write_bme)
+        cap = runner.writer_cap()       # (the host twins of R searches per file: spread over the writers, as _write_trees)
         return [(self.write_supports, runner, shape, rows[k::cap]) for k in range(min(cap, len(rows)))]
 
 
@@ -550,9 +503,8 @@ class CompressSites(Analysis):
         count (site 0, weight 0).  Alignments of one padded size share a launch; a file's distances depend on the file
         alone."""
         from . import weights_sites as ws
-        compress = ws.native_compress_sites if runner.native_io else ws.compress_sites
         B, N, L = batch.shape
-        tables = [ws.pad_table(f, c, ws.padded_sites(len(f), L)) for f, c in (compress(a) for a in batch)]
+        tables = [ws.pad_table(f, c, ws.padded_sites(len(f), L)) for f, c in (runner.host.compress_sites(a) for a in batch)]
         preds = np.empty((B, N * (N - 1) // 2), dtype=np.float32)
         for kp in sorted({len(s) for s, _w in tables}):
             who = [b for b in range(B) if len(tables[b][0]) == kp]
@@ -676,10 +628,7 @@ class Tile(Analysis):
         tables = [None] * len(out)
         if runner.trees and self.writes_tree(shape):
             # the joins of every file's tree on the device; a file with a non-finite distance keeps the host's
-            t0 = time.perf_counter()
-            slots, lengths, nonfinite = engine.nj_joins(out)
-            tables = [None if bad else (s, l) for s, l, bad in zip(slots, lengths, nonfinite)]
-            runner.book(nj_device=sum(t is not None for t in tables), nj_device_s=time.perf_counter() - t0)
+            tables = runner.device_tables(engine, shape[0], out, [NJ]).get("nj", tables)
         return out, (spread, tables)
 
     def account(self, stats, count, shape, seconds):
@@ -701,7 +650,7 @@ class Tile(Analysis):
         runner.put(entry.path, "spread.phy", runner.phylip(spread, ids))
         runner.put(entry.path, "tile.tsv", tile_tsv(ids, self.context))
         if runner.trees and self.writes_tree(shape):
-            runner.put(entry.path, "nj.nwk", runner.nj(pred, ids) if table is None else runner.newick_of_joins(*table, ids))
+            runner.put(entry.path, "nj.nwk", runner.nj(pred, ids) if table is None else runner.newick_of_joins(table.slots, table.lengths, ids))
 
 
 MODES = (Bootstrap, Windows, SiteProfile, LeaveOneOut, CompressSites, Place, Tile)

@@ -42,7 +42,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .nj import Final, Join, neighbor_joining, newick_of_joins
+from .nj import Final, Join, neighbor_joining, newick_of_joins, table_of_joins
 
 # the window of the pick: the first pair of the scan whose q is within EPS of the exact minimum (absolute, in units of
 # Q: substitutions per site times m - 2).  Every value in [1e-12, 5e-9] reproduces FastME on the test data.
@@ -53,11 +53,6 @@ EPS = 1e-9
 # tools/bionj_bench.py, profiles/bionj_bench.txt): the smallest measured N at which the device takes at most half the
 # host's time, never below 201; None = the device path is off in the CLI (the API stays).
 BIONJ_DEVICE_MIN: Optional[int] = 512
-
-
-def joins_on_device(n: int) -> bool:
-    """Whether the CLI joins the BIONJ trees of a launch of ``n``-sequence files on the GPU thread."""
-    return BIONJ_DEVICE_MIN is not None and n >= max(3, BIONJ_DEVICE_MIN)
 
 
 def pick(q: np.ndarray) -> Tuple[int, int]:
@@ -134,10 +129,7 @@ def bionj_joins(dm: np.ndarray, trace: Optional[list] = None) -> Tuple[List[Join
 
 def bionj_table(dm: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
     """``bionj_joins`` as ``(slots int32, lengths float64) [2 (N - 3) + 3]``, the layout of ``pf_bionj_joins``."""
-    joins, final = bionj_joins(dm)
-    slots = np.array([s for a, b, _la, _lb in joins for s in (a, b)] + list(final[:3]), dtype=np.int32)
-    lengths = np.array([x for _a, _b, la, lb in joins for x in (la, lb)] + list(final[3:]), dtype=np.float64)
-    return slots, lengths
+    return table_of_joins(*bionj_joins(dm))
 
 
 def bionj_start(dm: np.ndarray) -> np.ndarray:

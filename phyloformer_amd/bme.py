@@ -37,7 +37,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .nj import Final, Join, newick_of_joins, nj_joins
+from .nj import Final, Join, newick_of_joins, nj_joins, table_of_joins
 
 # From this many sequences on the CLI refines a launch's trees on the GPU thread (``Engine.nj_joins`` +
 # ``Engine.bme_nni``) instead of on the writer threads' host code.  A measured constant (DESIGN.md section 21,
@@ -246,8 +246,7 @@ def table_to_joins(slots: Sequence[int], lengths: Sequence[float]) -> Tuple[List
 
 def nj_start(dm: np.ndarray) -> np.ndarray:
     """The slots of ``nj.nj_joins``' table of ``dm``."""
-    joins, final = nj_joins(dm)
-    return np.array([s for a, b, _la, _lb in joins for s in (a, b)] + list(final[:3]), dtype=np.int32)
+    return table_of_joins(*nj_joins(dm))[0]
 
 
 def caterpillar_slots(n: int) -> np.ndarray:

@@ -36,6 +36,7 @@ from typing import List, NamedTuple, Optional, Sequence
 
 from .bootstrap import support_percent
 from .supports import table_splits
+from .treekinds import NJ_STARTED
 
 # From this many sequences on the CLI builds a sub-batch's consensus trees on the GPU thread (``Engine.join_consensus``)
 # instead of on the writer threads' serial twin.  A measured constant by ``supports.SUPPORT_DEVICE_MIN``'s rule (DESIGN.md
@@ -45,7 +46,7 @@ CONSENSUS_DEVICE_MIN = 1024
 
 PERCENT_MIN, PERCENT_MAX = 50, 99
 # the file of a kind's consensus tree (supports.SUFFIXES' kinds)
-SUFFIXES = {"nj": "con.nwk", "bme": "bme.con.nwk", "spr": "spr.con.nwk"}
+SUFFIXES = {k.name: k.files("con.nwk")[0] for k in NJ_STARTED}
 
 
 class Consensus(NamedTuple):

@@ -61,6 +61,13 @@ def nj_joins(dm: np.ndarray) -> Tuple[List[Join], Final]:
     return joins, (i, j, k, li, lj, lk)
 
 
+def table_of_joins(joins: Sequence[Join], final: Final) -> Tuple[np.ndarray, np.ndarray]:
+    """A join sequence as ``(slots int32, lengths float64) [2 (N - 3) + 3]``, the layout of ``pf_nj_joins``."""
+    slots = np.array([s for a, b, _la, _lb in joins for s in (a, b)] + list(final[:3]), dtype=np.int32)
+    lengths = np.array([x for _a, _b, la, lb in joins for x in (la, lb)] + list(final[3:]), dtype=np.float64)
+    return slots, lengths
+
+
 def join_splits(joins: Sequence[Join], n: int) -> List[int]:
     """The split every join creates, as a bitmask over sequence indices, normalised to the side without sequence 0."""
     members = [1 << i for i in range(n)]

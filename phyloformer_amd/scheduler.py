@@ -29,6 +29,7 @@ tests/test_cli_gpu.py).
 """
 from __future__ import annotations
 
+import itertools
 import json
 import os
 import queue
@@ -38,12 +39,14 @@ import threading
 import time
 from collections import OrderedDict, deque
 from concurrent.futures import Future, ThreadPoolExecutor
+from contextlib import closing
 from pathlib import Path
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
 from .analyses import Analysis, sub_batches
+from .treekinds import KINDS, JoinTable, Kind, NativeHost, PythonHost, join_refine, reaches, refusals, switched_on
 
 # one launch should carry about this many (pair, site) tokens: 16 alignments of 60 x 500
 # (3.6 GB of residual stream), the size bench.py measures the headline number at
@@ -155,32 +158,25 @@ class DirectoryRunner:
     def __init__(self, engine, out_dir: str, trees: bool = False, batch: int = 0,
                  io_threads: int = 4, native_io: bool = True, progress=None, modes: Sequence[Analysis] = (),
                  bme: bool = False, spr: bool = False, bionj: bool = False):
-        if bionj and not trees:
-            raise ValueError("--bionj writes a tree beside that of --trees: give -t as well")
-        if bme and not trees:
-            raise ValueError("--bme refines the tree of --trees: give -t as well")
-        if spr and not trees:
-            raise ValueError("--spr refines the tree of --trees: give -t as well")
+        # with --trees: <stem>.bme.nwk / .spr.nwk / .bionj.nwk (and .bionj.bme.nwk / .bionj.spr.nwk) as well (treekinds.KINDS)
+        self.flags = [flag for flag, on in (("--bionj", bionj), ("--bme", bme), ("--spr", spr)) if on]
+        if not trees and self.flags:
+            raise ValueError(next(refusals(self.flags, trees)))
+        self.kind_groups = switched_on(self.flags)
         self.engines = list(engine) if isinstance(engine, (list, tuple)) else [engine]
         self.out_dir = out_dir
         self.trees = trees
-        self.bme = bme                # with --trees: <stem>.bme.nwk, the NJ tree refined by balanced NNIs, as well
-        self.spr = spr                # with --trees: <stem>.spr.nwk, the NJ tree refined by balanced SPR moves, as well
-        # with --trees: <stem>.bionj.nwk, the BIONJ tree, as well - and with --bme / --spr <stem>.bionj.bme.nwk /
-        # <stem>.bionj.spr.nwk, the same searches started from it
-        self.bionj = bionj
         self.batch = batch            # 0 = auto per shape
         self.io_threads = max(1, io_threads)
         self.native_io = native_io
+        self.host = NativeHost() if native_io else PythonHost()      # whoever computes on the loader and writer threads
+        # (bytes from the native side, text from the Python one; the table of the distances ``nj`` joins gives ``nj``'s bytes)
+        self._load, self.phylip, self.newick_of_joins = self.host.load_alignment, self.host.phylip, self.host.newick_of_joins
         self.progress = progress
         self.stats = {"alignments": 0, "launches": 0, "forward_s": 0.0, "load_wait_s": 0.0,
                       "write_wait_s": 0.0, "shapes": {}, "gpu_streams": len(self.engines)}
-        if bme:
-            self.stats.update({"bme": 0, "bme_steps": 0, "bme_device": 0, "bme_device_s": 0.0})
-        if spr:
-            self.stats.update({"spr": 0, "spr_steps": 0, "spr_device": 0, "spr_device_s": 0.0})
-        if bionj:
-            self.stats.update({"bionj": 0, "bionj_device": 0, "bionj_device_s": 0.0})
+        for kinds in self.kind_groups:
+            self.stats.update({key: 0.0 if key.endswith("_s") else 0 for key in kinds[0].stats})
         self.modes = list(modes)
         for m in self.modes:
             m.bind(self.modes)
@@ -190,131 +186,38 @@ class DirectoryRunner:
         self._lock = threading.Lock()
 
     # -- stages -----------------------------------------------------------------------------
-    def _load(self, path: str):
-        if self.native_io:
-            from .hostio import load_alignment
-        else:
-            from .fasta import load_alignment
-        return load_alignment(path)
-
-    def phylip(self, vec: np.ndarray, ids: List[str]):
-        """The PHYLIP matrix of a distance vector: bytes from the native formatter, text from the Python one."""
-        if self.native_io:
-            from .hostio import format_phylip
-            return format_phylip(vec, ids)
-        from .phylip import vec_to_phylip
-        return vec_to_phylip(vec, ids)[1]
-
     def nj(self, vec: np.ndarray, ids: List[str]):
         """The neighbour-joining tree of a distance vector, from the same side as ``phylip`` (infer_alns.py:120-123)."""
-        if self.native_io:
-            from .hostio import nj_newick
-            return nj_newick(vec, ids)
-        from .nj import neighbor_joining
-        from .phylip import vec_to_phylip
-        return neighbor_joining(vec_to_phylip(vec, ids)[0].astype("float64"), ids)
+        return self.host.nj(vec, ids)
 
-    def newick_of_joins(self, slots: np.ndarray, lengths: np.ndarray, ids: List[str]):
-        """The tree text of a join table (``Engine.nj_joins``), from the same side as ``nj``: the same bytes as ``nj`` of
-        the distances the table was joined from."""
-        if self.native_io:
-            from .hostio import newick_of_joins
-            return newick_of_joins(slots, lengths, ids)
-        from .hostio import newick_of_joins_py
-        return newick_of_joins_py(slots, lengths, ids)
-
-    # the two refinements of the NJ tree, --bme and --spr: (the library's text, bme.py's text, Engine's search, the
-    # constant of bme.py from which the search runs on the GPU thread)
-    REFINEMENTS = {"bme": ("bme_newick", "bme_tree_py", "bme_nni", "BME_DEVICE_MIN"),
-                   "spr": ("spr_newick", "spr_tree_py", "bme_spr", "SPR_DEVICE_MIN")}
-
-    def bme_tree(self, vec: np.ndarray, ids: List[str], kind: str = "bme"):
-        """``(text, moves)`` of the balanced-NNI (``--bme``) or balanced-SPR (``kind`` "spr", ``--spr``) refinement of the
-        neighbour-joining tree of a distance vector, from the same side as ``nj``."""
-        native, python, _search, _minimum = self.REFINEMENTS[kind]
-        if self.native_io:
-            from . import hostio
-            return getattr(hostio, native)(vec, ids, with_steps=True)
-        from . import bme
-        return getattr(bme, python)(vec, ids)
-
-    def _bme_device(self, engine, n: int, preds: np.ndarray, kind: str = "bme"):
-        """On the GPU thread, for a launch of files with at least ``bme.BME_DEVICE_MIN`` (``bme.SPR_DEVICE_MIN``) sequences:
-        every file's NJ joins and their refinement on the device; ``(slots, lengths, moves)`` per file, None for a file
-        with a non-finite distance (it keeps the host's path) - or None for the launch."""
-        from . import bme
-        _native, _python, search, minimum = self.REFINEMENTS[kind]
-        minimum = getattr(bme, minimum)
-        if minimum is None or n < max(3, minimum):
-            return None
+    def device_tables(self, engine, n: int, preds: np.ndarray, kinds: Sequence[Kind]) -> dict:
+        """On the GPU thread, from the threshold of ``kinds[0]`` on (3 sequences at the least), which books the device's
+        files and seconds: every file's joins of the kinds' start tree and, for each kind from its own threshold on, their
+        refinement.  ``{kind name: [JoinTable, None for a non-finite file]}``; None or missing keeps the host's path."""
+        head = kinds[0]
+        if not reaches(head.minimum(), n, 3):
+            return {}
         t0 = time.perf_counter()
-        start, _lengths, nonfinite = engine.nj_joins(preds)
-        # (a flagged source's joins are unspecified: any valid start table stands in, its result is not used)
-        start = np.where(np.asarray(nonfinite, dtype=bool)[:, None], bme.caterpillar_slots(n)[None, :], start)
-        slots, lengths, steps, _length, status = getattr(engine, search)(preds, start)
-        tables = [None if bad or st == bme.NONFINITE else (s, l, int(k))
-                  for s, l, k, st, bad in zip(slots, lengths, steps, status, nonfinite)]
-        self.book(**{f"{kind}_device": sum(t is not None for t in tables), f"{kind}_device_s": time.perf_counter() - t0})
-        return tables
+        run = [k for k in kinds if k.search is not None and reaches(k.minimum(), n)]
+        made = join_refine(engine, head.start, [k.search for k in run], preds)
+        out = {k.name: [None if bad else JoinTable(s, l, int(moves)) for s, l, moves, bad in zip(*made[k.search])]
+               for k in kinds if k.search is None or k in run}
+        self.book(**{f"{head.name}_device": sum(t is not None for t in out[head.name]), f"{head.name}_device_s": time.perf_counter() - t0})
+        return out
 
-    def _write_bme(self, group: list, preds: np.ndarray, tables, kind: str = "bme"):
-        """``<stem>.bme.nwk`` (``<stem>.spr.nwk``) of some files of a launch, on a writer thread: formatted from the
-        device's table where there is one, refined on the host where not."""
+    def _write_trees(self, group: list, preds: np.ndarray, tables, kind: Kind):
+        """``<stem>.<kind>.nwk`` of some files of a launch, on a writer thread: formatted from the device's table where
+        there is one, joined and refined on the host where not."""
         moves = 0
         for k, (e, pred) in enumerate(zip(group, preds)):
             ids = e.ids()
             table = tables[k] if tables is not None else None
-            if table is None:
-                text, steps = self.bme_tree(pred, ids, kind)
-            else:
-                text, steps = self.newick_of_joins(table[0], table[1], ids), table[2]
-            self.put(e.path, f"{kind}.nwk", text)
+            text, steps = (self.host.tree_text(kind, pred, ids) if table is None else
+                           (self.newick_of_joins(table.slots, table.lengths, ids), table.steps))
+            self.put(e.path, f"{kind.name}.nwk", text)
             moves += steps
-        self.book(**{kind: len(group), f"{kind}_steps": moves})
-
-    def bionj_tree(self, vec: np.ndarray, ids: List[str], kind: Optional[str] = None):
-        """The text of the BIONJ tree of a distance vector (``--bionj``) - ``kind`` "bme" / "spr": of its balanced-NNI /
-        balanced-SPR refinement -, from the same side as ``nj``."""
-        if self.native_io:
-            from . import hostio
-            return hostio.bionj_newick(vec, ids) if kind is None else hostio.bionj_refined_newick(kind, vec, ids)
-        from . import bionj
-        return {None: bionj.bionj_newick_py, "bme": bionj.bionj_bme_newick_py, "spr": bionj.bionj_spr_newick_py}[kind](vec, ids)
-
-    def _bionj_device(self, engine, n: int, preds: np.ndarray, kinds: Sequence[str]) -> dict:
-        """On the GPU thread, for a launch of files with as many sequences as ``bionj.joins_on_device`` asks: every file's BIONJ
-        joins on the device and, from ``bme.BME_DEVICE_MIN`` / ``bme.SPR_DEVICE_MIN`` on, their refinements as
-        ``_bme_device`` runs them from the NJ start.  ``{kind: [(slots, lengths) per file, None for a file with a
-        non-finite distance (it keeps the host's path)]}``, ``kind`` None for the BIONJ tree itself; a kind that is
-        missing keeps the host's path for the whole launch."""
-        from . import bionj, bme
-        if not bionj.joins_on_device(n):
-            return {}
-        t0 = time.perf_counter()
-        start, start_lengths, nonfinite = engine.bionj_joins(preds)
-        nonfinite = np.asarray(nonfinite, dtype=bool)
-        out = {None: [None if bad else (s, l) for s, l, bad in zip(start, start_lengths, nonfinite)]}
-        start = np.where(nonfinite[:, None], bme.caterpillar_slots(n)[None, :], start)
-        for kind in kinds:
-            _native, _python, search, minimum = self.REFINEMENTS[kind]
-            minimum = getattr(bme, minimum)
-            if minimum is None or n < minimum:
-                continue
-            slots, lengths, _steps, _length, status = getattr(engine, search)(preds, start)
-            out[kind] = [None if bad or st == bme.NONFINITE else (s, l) for s, l, st, bad in zip(slots, lengths, status, nonfinite)]
-        self.book(bionj_device=sum(t is not None for t in out[None]), bionj_device_s=time.perf_counter() - t0)
-        return out
-
-    def _write_bionj(self, group: list, preds: np.ndarray, tables, kind: Optional[str] = None):
-        """``<stem>.bionj.nwk`` (``<stem>.bionj.bme.nwk``, ``<stem>.bionj.spr.nwk``) of some files of a launch, on a writer
-        thread: formatted from the device's table where there is one, joined (and refined) on the host where not."""
-        for k, (e, pred) in enumerate(zip(group, preds)):
-            ids = e.ids()
-            table = tables[k] if tables is not None else None
-            text = self.bionj_tree(pred, ids, kind) if table is None else self.newick_of_joins(table[0], table[1], ids)
-            self.put(e.path, "bionj.nwk" if kind is None else f"bionj.{kind}.nwk", text)
-        if kind is None:
-            self.book(bionj=len(group))
+        if kind.stats:
+            self.book(**{kind.name: len(group)}, **({f"{kind.name}_steps": moves} if kind.search else {}))
 
     def book(self, **amounts):
         """Add to the run's stats from inside a mode's own engine call (takes the runner's lock)."""
@@ -364,18 +267,12 @@ class DirectoryRunner:
         preds, payload = mode.forward(self, engine, shape, batch) if mode else (engine.forward(batch), ())
         dt = time.perf_counter() - t0
         tree = not (mode and self.trees and mode.writes_tree(shape))      # (False: the mode writes the tree itself)
-        for kind in [k for k, on in (("bme", self.bme), ("spr", self.spr)) if on]:
-            tables = self._bme_device(engine, shape[0], preds, kind)
-            cap = self.writer_cap()
-            submit([(self._write_bme, group[k::cap], preds[k::cap], None if tables is None else tables[k::cap], kind)
-                    for k in range(min(cap, len(group)))])
-        if self.bionj:
-            kinds = [k for k, on in (("bme", self.bme), ("spr", self.spr)) if on]
-            device = self._bionj_device(engine, shape[0], preds, kinds)
-            cap = self.writer_cap()
-            for kind in [None] + kinds:
-                tables = device.get(kind)
-                submit([(self._write_bionj, group[k::cap], preds[k::cap], None if tables is None else tables[k::cap], kind)
+        cap = self.writer_cap()
+        for kinds in self.kind_groups:
+            device = self.device_tables(engine, shape[0], preds, kinds)
+            for kind in kinds:
+                tables = device.get(kind.name)
+                submit([(self._write_trees, group[k::cap], preds[k::cap], None if tables is None else tables[k::cap], kind)
                         for k in range(min(cap, len(group)))])
         with self._lock:
             self.stats["forward_s"] += dt
@@ -481,46 +378,47 @@ class DirectoryRunner:
                 bad = m.file_error(path, n_seqs, n_sites)
         return bad
 
+    def _parse_ahead(self, paths, loaders, lookahead: int):
+        """``(path, future of its parse)`` in the order of ``paths``, at most ``lookahead`` files submitted ahead of the
+        consumer; closing the generator cancels what is still queued."""
+        inflight: "deque[Tuple[str, Future]]" = deque()
+        it = iter(paths)
+        try:
+            while True:
+                inflight.extend((p, loaders.submit(self._load, p)) for p in itertools.islice(it, lookahead - len(inflight)))
+                if not inflight:
+                    return
+                yield inflight.popleft()
+        finally:
+            for _p, f in inflight:
+                f.cancel()
+
     def _feed_python(self, paths, loaders, jobs, errors) -> Optional[BaseException]:
         """One future per file (``--python-io``, ``-t``): parse ahead, bucket by shape, launch full buckets."""
         buckets: "OrderedDict[Tuple[int, int], list]" = OrderedDict()
-        lookahead = max(64, 4 * (self.batch or 64))
-        inflight: "deque[Tuple[str, Future]]" = deque()
-        it = iter(paths)
-        exhausted = False
         bad: Optional[BaseException] = None
-        while not errors:
-            while not exhausted and len(inflight) < lookahead:
-                try:
-                    p = next(it)
-                except StopIteration:
-                    exhausted = True
-                    break
-                inflight.append((p, loaders.submit(self._load, p)))
-            if not inflight:
+        ahead = self._parse_ahead(paths, loaders, max(64, 4 * (self.batch or 64)))
+        for path, fut in ahead:
+            if errors:
                 break
-            path, fut = inflight.popleft()
             t0 = time.perf_counter()
             try:
                 idx, ids = fut.result()          # parser exceptions surface here, as in the reference
             except Exception as exc:             # noqa: BLE001 - raised by run() once the files in front are written
                 bad = exc
-                for _p, f in inflight:
-                    f.cancel()
                 break
             finally:
                 self.stats["load_wait_s"] += time.perf_counter() - t0
             shape = (int(idx.shape[0]), int(idx.shape[1]))
             bad = self._file_error(path, *shape)
             if bad is not None:
-                for _p, f in inflight:
-                    f.cancel()
                 break
             group = buckets.setdefault(shape, [])
             group.append(Entry(path, idx, ids))
             if len(group) >= (self.batch or auto_batch(*shape)):
                 jobs.put((shape, group))
                 buckets[shape] = []
+        ahead.close()                                # (cancels what is still queued, whichever way the loop ended)
         for shape, group in sorted(buckets.items(), key=lambda kv: -len(kv[1])):
             if group and not errors:
                 jobs.put((shape, group))
@@ -642,23 +540,10 @@ class SiteShardedRunner(DirectoryRunner):
         t_start = time.perf_counter()
         buckets: "OrderedDict[Tuple[int, int], list]" = OrderedDict()
         pending: deque = deque()
-        lookahead = max(16, 2 * (self.batch or 16))
         with ThreadPoolExecutor(self.io_threads, thread_name_prefix="pf-load") as loaders, \
-                ThreadPoolExecutor(self.io_threads, thread_name_prefix="pf-write") as writers:
-            inflight: "deque[Tuple[str, Future]]" = deque()
-            it = iter(paths)
-            exhausted = False
-            while True:
-                while not exhausted and len(inflight) < lookahead:
-                    try:
-                        p = next(it)
-                    except StopIteration:
-                        exhausted = True
-                        break
-                    inflight.append((p, loaders.submit(self._load, p)))
-                if not inflight:
-                    break
-                path, fut = inflight.popleft()
+                ThreadPoolExecutor(self.io_threads, thread_name_prefix="pf-write") as writers, \
+                closing(self._parse_ahead(paths, loaders, max(16, 2 * (self.batch or 16)))) as ahead:
+            for path, fut in ahead:
                 t0 = time.perf_counter()
                 idx, ids = fut.result()
                 self.stats["load_wait_s"] += time.perf_counter() - t0
@@ -709,9 +594,7 @@ def summarize(stats: dict, load_s: float = 0.0) -> dict:
             if stats["forward_s"] > 0 else None,
             "replicates": stats.get("replicates", 0), "bootstrap_s": round(stats.get("bootstrap_s", 0.0), 6),
             "windows": stats.get("windows", 0), "windows_s": round(stats.get("windows_s", 0.0), 6),
-            **({k: round(stats[k], 6) for k in ("bme", "bme_steps", "bme_device", "bme_device_s")} if "bme" in stats else {}),
-            **({k: round(stats[k], 6) for k in ("spr", "spr_steps", "spr_device", "spr_device_s")} if "spr" in stats else {}),
-            **({k: round(stats[k], 6) for k in ("bionj", "bionj_device", "bionj_device_s")} if "bionj" in stats else {}),
+            **{key: round(stats[key], 6) for kind in KINDS if kind.name in stats for key in kind.stats},
             **({k: round(stats[k], 6) for k in ("tbe", "refined_supports", "supports_device", "supports_device_s")}
                if "tbe" in stats else {}),
             **({k: stats[k] for k in ("consensus", "consensus_device")} if "consensus" in stats else {}),

@@ -27,7 +27,8 @@ import numpy as np
 
 from .bme import Tree, table_to_joins
 from .bootstrap import support_percent
-from .nj import join_splits, newick_of_joins
+from .nj import join_splits, newick_of_joins, table_of_joins
+from .treekinds import NJ_STARTED
 
 # From this many sequences on the CLI matches a sub-batch's supports on the GPU thread (``Engine.join_supports``)
 # instead of on the writer threads' serial twin.  A measured constant by ``bme.BME_DEVICE_MIN``'s rule (DESIGN.md
@@ -167,9 +168,7 @@ def support_texts(slots: Sequence[int], lengths: Sequence[float], ids: Sequence[
 
 
 # the files of --instability per kind of tree: per-taxon counts, per-branch counts, the tree labelled with the join t
-INSTABILITY_SUFFIXES = {"nj": ("instability.tsv", "branches.tsv", "branches.nwk"),
-                        "bme": ("bme.instability.tsv", "bme.branches.tsv", "bme.branches.nwk"),
-                        "spr": ("spr.instability.tsv", "spr.branches.tsv", "spr.branches.nwk")}
+INSTABILITY_SUFFIXES = {k.name: k.files("instability.tsv", "branches.tsv", "branches.nwk") for k in NJ_STARTED}
 TOP_MOVED = 5
 
 
@@ -206,41 +205,51 @@ def transfer_tuple(out: Dict[str, list]) -> tuple:
 
 
 # the searches behind the trees of the CLI: suffix of the tree's file -> bme.py's search (None: the NJ tree itself)
-SEARCHES = {"nj": None, "bme": "bme_nni", "spr": "bme_spr"}
+SEARCHES = {k.name: k.search for k in NJ_STARTED}
 # the file of a kind's tree with Felsenstein / TBE labels
-SUFFIXES = {"nj": ("sup.nwk", "tbe.nwk"), "bme": ("bme.sup.nwk", "bme.tbe.nwk"), "spr": ("spr.sup.nwk", "spr.tbe.nwk")}
+SUFFIXES = {k.name: k.files("sup.nwk", "tbe.nwk") for k in NJ_STARTED}
+
+
+def joins_py(start: str, preds: np.ndarray):
+    """``Engine.nj_joins`` (``start`` "nj") / ``Engine.bionj_joins`` ("bionj") by the statements: ``float32 [M, P_N]`` ->
+    ``(slots int32 [M, T], lengths float64 [M, T], nonfinite bool [M])``; a flagged source's table is zeros."""
+    from . import bionj, bme
+    preds = np.asarray(preds, dtype=np.float32)
+    n = (1 + int(round((1 + 8 * preds.shape[1]) ** 0.5))) // 2
+    slots = np.zeros((len(preds), 2 * n - 3), dtype=np.int32)
+    lengths = np.zeros((len(preds), 2 * n - 3), dtype=np.float64)
+    bad = np.zeros(len(preds), dtype=bool)
+    for m, vec in enumerate(preds):
+        dm = bme.matrix_of_preds(vec, n)
+        bad[m] = not np.isfinite(dm).all()
+        if not bad[m]:
+            slots[m], lengths[m] = table_of_joins(*(bme.nj_joins if start == "nj" else bionj.bionj_joins)(dm))
+    return slots, lengths, bad
+
+
+def refine_py(search: str, preds: np.ndarray, start_slots: np.ndarray):
+    """``Engine.bme_nni`` / ``Engine.bme_spr`` by the statements (``bme.py``'s function of that name, source by source):
+    ``(slots [M, T], lengths [M, T], steps [M], tree_length [M], status [M])``."""
+    from . import bme
+    preds = np.asarray(preds, dtype=np.float32)
+    n = (1 + int(round((1 + 8 * preds.shape[1]) ** 0.5))) // 2
+    out = [getattr(bme, search)(bme.matrix_of_preds(vec, n), start) for vec, start in zip(preds, start_slots)]
+    return tuple(np.array(x) for x in zip(*out))
 
 
 def kind_tables(preds: np.ndarray, reps: np.ndarray, n: int, kind: str, with_lengths: bool = False):
     """The Python twins' join tables behind the supports of one file's ``kind`` tree: ``(slots, lengths) [T]`` of the
     file's own tree (``preds [P]``), ``rep_slots int32 [R][T]`` and ``rep_flag bool [R]`` of its replicates' trees
-    (``reps [R][P]``), each the NJ table refined by the kind's search.  A replicate with a non-finite distance is flagged
-    (its table: zeros); one stopped at the move cap is used as it stands.  The file's own tree with non-finite distances
-    has no table: ``(None, None, ...)``.  ``with_lengths``: ``rep_lengths float64 [R][T]`` as a fifth result."""
-    from . import bme
-
-    def one(vec):
-        dm = bme.matrix_of_preds(vec, n)
-        if not np.isfinite(dm).all():
-            return None
-        joins, final = bme.nj_joins(dm)
-        slots = bme.nj_start(dm)
-        lengths = np.array([x for _a, _b, la, lb in joins for x in (la, lb)] + list(final[3:]), dtype=np.float64)
-        if SEARCHES[kind] is not None:
-            slots, lengths, _steps, _length, _status = getattr(bme, SEARCHES[kind])(dm, slots)
-        return np.asarray(slots, dtype=np.int32), lengths
-
-    own = one(preds)
-    t = 2 * (n - 3) + 3
-    rep_slots, rep_flag = np.zeros((len(reps), t), dtype=np.int32), np.zeros(len(reps), dtype=bool)
-    rep_lengths = np.zeros((len(reps), t), dtype=np.float64)
-    for r, rep in enumerate(reps):
-        table = one(rep)
-        if table is None:
-            rep_flag[r] = True
-        else:
-            rep_slots[r], rep_lengths[r] = table
-    return (own if own is not None else (None, None)) + (rep_slots, rep_flag) + ((rep_lengths,) if with_lengths else ())
+    (``reps [R][P]``), each the NJ table refined by the kind's search (``treekinds.join_refine`` on the statements).  A
+    replicate with a non-finite distance is flagged (its table: zeros); one stopped at the move cap is used as it stands.
+    The file's own tree with non-finite distances has no table: ``(None, None, ...)``.  ``with_lengths``: ``rep_lengths
+    float64 [R][T]`` as a fifth result."""
+    from .treekinds import PythonHost, join_refine
+    every = np.concatenate([np.asarray(preds, dtype=np.float32).reshape(1, -1), np.asarray(reps, dtype=np.float32)])
+    search = SEARCHES[kind]
+    slots, lengths, _steps, bad = join_refine(PythonHost(), "nj", [search] if search else [], every)[search]
+    own = (None, None) if bad[0] else (slots[0], lengths[0])
+    return own + (slots[1:], bad[1:]) + ((lengths[1:],) if with_lengths else ())
 
 
 def support_newicks(preds: np.ndarray, reps: np.ndarray, ids: Sequence[str], kinds: Sequence[str] = ("nj",),
