@@ -322,6 +322,48 @@ struct NjTree {
     double li = 0, lj = 0, lk = 0;
 };
 
+// The join table of a tree (pf_nj_joins: slots / lengths [pfnj::table_len(n)], n >= 3: the joins a, b / la, lb, then the
+// trifurcation i, j, k / li, lj, lk) and back: the two places that know the layout
+NjTree tree_of_table(const int32_t* slots, const double* lengths, int32_t n) {
+    const size_t joins = (size_t)n - 3;
+    NjTree t;
+    t.joins.reserve(joins);
+    for (size_t s = 0; s < joins; ++s) t.joins.push_back({slots[2 * s], slots[2 * s + 1], lengths[2 * s], lengths[2 * s + 1]});
+    slots += 2 * joins; lengths += 2 * joins;
+    t.i = slots[0]; t.j = slots[1]; t.k = slots[2];
+    t.li = lengths[0]; t.lj = lengths[1]; t.lk = lengths[2];
+    return t;
+}
+
+void table_of_tree(const NjTree& t, int32_t* slots, double* lengths) {
+    for (const NjJoin& jn : t.joins) { *slots++ = jn.a; *slots++ = jn.b; *lengths++ = jn.la; *lengths++ = jn.lb; }
+    slots[0] = t.i; slots[1] = t.j; slots[2] = t.k;
+    lengths[0] = t.li; lengths[1] = t.lj; lengths[2] = t.lk;
+}
+
+// ids[i] has id_lens[i] bytes (id_lens == NULL: NUL-terminated)
+std::string label_of(const char* const* ids, const int64_t* id_lens, int32_t i) {
+    const char* id = ids[i] ? ids[i] : "";
+    return std::string(id, (size_t)(id_lens ? id_lens[i] : (int64_t)strlen(id)));
+}
+
+// The frame of a text entry point: what every such call refuses, then `fill` (text -> PF_OK or the code to return)
+// under the catch-all, the text copied out where it fits `cap`, and its size - the sizing protocol of pf_format_phylip.
+// What a call refuses beyond this stands at the call: before this where it is tested before the id lengths, in `fill`
+// where after.
+template <class Fill>
+int64_t text_call(int32_t n, const char* const* ids, const int64_t* id_lens, char* out, int64_t cap, Fill&& fill) {
+    if (n < 1 || !ids || !id_lens || (!out && cap > 0)) return PF_EINVAL;
+    for (int32_t i = 0; i < n; ++i) if (id_lens[i] < 0) return PF_EINVAL;
+    try {
+        std::string text;
+        const int rc = fill(text);
+        if (rc != PF_OK) return rc;
+        if (out && (int64_t)text.size() <= cap) memcpy(out, text.data(), text.size());
+        return (int64_t)text.size();
+    } catch (...) { return PF_ENOMEM; }
+}
+
 // n >= 3
 void nj_core(const float* preds, int32_t n, NjTree& t) {
     const size_t N = (size_t)n;
@@ -372,10 +414,7 @@ void nj_core(const float* preds, int32_t n, NjTree& t) {
 void nj_format(const NjTree& t, int32_t n, const char* const* ids, const int64_t* id_lens, bool clamp,
                const int32_t* support, std::string& out) {
     std::vector<std::string> labels((size_t)n);
-    for (int32_t i = 0; i < n; ++i) {
-        const char* id = ids[i] ? ids[i] : "";
-        labels[(size_t)i].assign(id, (size_t)(id_lens ? id_lens[i] : (int64_t)strlen(id)));
-    }
+    for (int32_t i = 0; i < n; ++i) labels[(size_t)i] = label_of(ids, id_lens, i);
     auto fmt = [&](std::string& dst, double x) {
         if (clamp && x < 0) x = 0.0;
         append_repr(dst, x);
@@ -400,10 +439,7 @@ void nj_format(const NjTree& t, int32_t n, const char* const* ids, const int64_t
 // preds [n(n-1)/2] -> Newick text of the neighbour-joining tree, as nj.py::neighbor_joining writes it
 void nj_newick(const float* preds, int32_t n, const char* const* ids, const int64_t* id_lens, bool clamp, std::string& out) {
     out.clear();
-    auto label = [&](int32_t i) {
-        const char* id = ids[i] ? ids[i] : "";
-        return std::string(id, (size_t)(id_lens ? id_lens[i] : (int64_t)strlen(id)));
-    };
+    auto label = [&](int32_t i) { return label_of(ids, id_lens, i); };
     if (n == 1) { out = "(" + label(0) + ");\n"; return; }
     if (n == 2) {
         char num[64];
@@ -442,14 +478,11 @@ extern "C" {
 
 int64_t pf_nj_newick_n(const float* preds, int32_t n, const char* const* ids, const int64_t* id_lens, int32_t clamp_negative,
                        char* out, int64_t cap) {
-    if (!preds || n < 1 || !ids || !id_lens || (!out && cap > 0)) return PF_EINVAL;
-    for (int32_t i = 0; i < n; ++i) if (id_lens[i] < 0) return PF_EINVAL;
-    try {
-        std::string text;
+    if (!preds) return PF_EINVAL;
+    return text_call(n, ids, id_lens, out, cap, [&](std::string& text) {
         nj_newick(preds, n, ids, id_lens, clamp_negative != 0, text);
-        if (out && (int64_t)text.size() <= cap) memcpy(out, text.data(), text.size());
-        return (int64_t)text.size();
-    } catch (...) { return PF_ENOMEM; }
+        return PF_OK;
+    });
 }
 
 // The Newick text of a join table (pf_nj_joins: slots / lengths [2 (n - 3) + 3], n >= 3) through nj_format: the text
@@ -457,21 +490,12 @@ int64_t pf_nj_newick_n(const float* preds, int32_t n, const char* const* ids, co
 // outside [0, n).
 int64_t pf_nj_format_joins_n(const int32_t* slots, const double* lengths, int32_t n, const char* const* ids, const int64_t* id_lens,
                              int32_t clamp_negative, char* out, int64_t cap) {
-    if (!slots || !lengths || n < 3 || !ids || !id_lens || (!out && cap > 0)) return PF_EINVAL;
-    for (int32_t i = 0; i < n; ++i) if (id_lens[i] < 0) return PF_EINVAL;
-    const size_t joins = (size_t)n - 3, len = 2 * joins + 3;
-    for (size_t k = 0; k < len; ++k) if (slots[k] < 0 || slots[k] >= n) return PF_EINVAL;
-    try {
-        NjTree t;
-        t.joins.reserve(joins);
-        for (size_t s = 0; s < joins; ++s) t.joins.push_back({slots[2 * s], slots[2 * s + 1], lengths[2 * s], lengths[2 * s + 1]});
-        t.i = slots[2 * joins]; t.j = slots[2 * joins + 1]; t.k = slots[2 * joins + 2];
-        t.li = lengths[2 * joins]; t.lj = lengths[2 * joins + 1]; t.lk = lengths[2 * joins + 2];
-        std::string text;
-        nj_format(t, n, ids, id_lens, clamp_negative != 0, nullptr, text);
-        if (out && (int64_t)text.size() <= cap) memcpy(out, text.data(), text.size());
-        return (int64_t)text.size();
-    } catch (...) { return PF_ENOMEM; }
+    if (!slots || !lengths || n < 3) return PF_EINVAL;
+    return text_call(n, ids, id_lens, out, cap, [&](std::string& text) {
+        for (int64_t k = 0; k < pfnj::table_len(n); ++k) if (slots[k] < 0 || slots[k] >= n) return PF_EINVAL;
+        nj_format(tree_of_table(slots, lengths, n), n, ids, id_lens, clamp_negative != 0, nullptr, text);
+        return PF_OK;
+    });
 }
 
 }  // extern "C"
@@ -736,49 +760,62 @@ int pf_bme_spr_host(const float* preds, const int32_t* start_slots, int32_t B, i
     return refine_host(spr_one, preds, start_slots, B, N, slots, lengths, steps, tree_length, status);
 }
 
-// The text of the NJ tree refined by `one`, and the number of moves behind it (steps_out may be NULL)
-static int64_t refined_newick(refine_fn one, const float* preds, int32_t n, const char* const* ids, const int64_t* id_lens,
-                              int32_t clamp_negative, char* out, int64_t cap, int32_t* steps_out) {
+}  // extern "C"
+
+namespace {
+
+// the start table of one source; false: a NaN or an infinity in it, and no table
+using start_fn = bool (*)(const float*, int32_t, int32_t*, double*);
+
+bool nj_start(const float* preds, int32_t n, int32_t* slots, double* lengths) {
+    NjTree t;
+    nj_core(preds, n, t);
+    table_of_tree(t, slots, lengths);
+    return true;
+}
+
+bool bionj_start(const float* preds, int32_t n, int32_t* slots, double* lengths) {
+    uint8_t bad = 1;
+    pfbionj::run_serial(preds, 1, n, slots, lengths, &bad);
+    return !bad;
+}
+
+// Start, search (`one`, or none: NULL), and the text of the table that comes out, with the number of moves behind it
+// (steps_out may be NULL).  The NJ text, after no move, where there is no such table: n < 3, a start that flags its
+// source, a search that refuses the start table (a NaN in the distances can leave nj_core with a table that is none) or
+// flags its source.
+int64_t tree_newick(start_fn start, refine_fn one, const float* preds, int32_t n, const char* const* ids, const int64_t* id_lens,
+                    int32_t clamp_negative, char* out, int64_t cap, int32_t* steps_out) {
     if (steps_out) *steps_out = 0;
-    if (!preds || n < 1 || n > pfbme::MAX_N || !ids || !id_lens || (!out && cap > 0)) return PF_EINVAL;
-    for (int32_t i = 0; i < n; ++i) if (id_lens[i] < 0) return PF_EINVAL;
-    try {
-        std::string text;
-        bool refined = false;
-        if (n >= 3) {
-            NjTree t;
-            nj_core(preds, n, t);
-            const size_t joins = (size_t)n - 3, len = 2 * joins + 3;
-            std::vector<int32_t> start(len), slots(len);
-            std::vector<double> lengths(len);
-            for (size_t s = 0; s < joins; ++s) { start[2 * s] = t.joins[s].a; start[2 * s + 1] = t.joins[s].b; }
-            start[2 * joins] = t.i; start[2 * joins + 1] = t.j; start[2 * joins + 2] = t.k;
+    if (!preds || (one && n > pfbme::MAX_N)) return PF_EINVAL;          // (the bound is the searches')
+    return text_call(n, ids, id_lens, out, cap, [&](std::string& text) {
+        const size_t len = n >= 3 ? (size_t)pfnj::table_len(n) : 0;
+        std::vector<int32_t> slots(len, 0), found(one ? len : 0);
+        std::vector<double> lengths(len, 0.0);
+        bool ok = n >= 3 && start(preds, n, slots.data(), lengths.data());
+        if (ok && one) {
             int32_t steps = 0;
             double tree_length = 0.0;
             uint8_t status = 0;
-            // (a NaN in the distances can leave nj_core with a table that is none: the NJ text then, as for a flagged source)
-            if (one(preds, start.data(), n, slots.data(), lengths.data(), &steps, &tree_length, &status) && status != pfbme::ST_NONFINITE) {
-                NjTree r;
-                r.joins.reserve(joins);
-                for (size_t s = 0; s < joins; ++s) r.joins.push_back({slots[2 * s], slots[2 * s + 1], lengths[2 * s], lengths[2 * s + 1]});
-                r.i = slots[2 * joins]; r.j = slots[2 * joins + 1]; r.k = slots[2 * joins + 2];
-                r.li = lengths[2 * joins]; r.lj = lengths[2 * joins + 1]; r.lk = lengths[2 * joins + 2];
-                nj_format(r, n, ids, id_lens, clamp_negative != 0, nullptr, text);
-                refined = true;
-                if (steps_out) *steps_out = steps;
-            }
+            ok = one(preds, slots.data(), n, found.data(), lengths.data(), &steps, &tree_length, &status) && status != pfbme::ST_NONFINITE;
+            if (ok && steps_out) *steps_out = steps;
+            slots.swap(found);
         }
-        if (!refined) nj_newick(preds, n, ids, id_lens, clamp_negative != 0, text);
-        if (out && (int64_t)text.size() <= cap) memcpy(out, text.data(), text.size());
-        return (int64_t)text.size();
-    } catch (...) { return PF_ENOMEM; }
+        if (ok) nj_format(tree_of_table(slots.data(), lengths.data(), n), n, ids, id_lens, clamp_negative != 0, nullptr, text);
+        else nj_newick(preds, n, ids, id_lens, clamp_negative != 0, text);
+        return PF_OK;
+    });
 }
+
+}  // namespace
+
+extern "C" {
 
 // pf_bme_newick_n and the number of moves behind the text (bound by phyloformer_amd/hostio.py::bme_newick; not part of
 // the public header)
 int64_t pf_bme_newick_steps_n(const float* preds, int32_t n, const char* const* ids, const int64_t* id_lens, int32_t clamp_negative,
                               char* out, int64_t cap, int32_t* steps_out) {
-    return refined_newick(bme_one, preds, n, ids, id_lens, clamp_negative, out, cap, steps_out);
+    return tree_newick(nj_start, bme_one, preds, n, ids, id_lens, clamp_negative, out, cap, steps_out);
 }
 
 int64_t pf_bme_newick_n(const float* preds, int32_t n, const char* const* ids, const int64_t* id_lens, int32_t clamp_negative,
@@ -789,7 +826,7 @@ int64_t pf_bme_newick_n(const float* preds, int32_t n, const char* const* ids, c
 // the same for the balanced SPR search (pf_bme_spr_host); pf_bme_spr_newick_steps_n is bound by hostio.py::spr_newick
 int64_t pf_bme_spr_newick_steps_n(const float* preds, int32_t n, const char* const* ids, const int64_t* id_lens, int32_t clamp_negative,
                                   char* out, int64_t cap, int32_t* steps_out) {
-    return refined_newick(spr_one, preds, n, ids, id_lens, clamp_negative, out, cap, steps_out);
+    return tree_newick(nj_start, spr_one, preds, n, ids, id_lens, clamp_negative, out, cap, steps_out);
 }
 
 int64_t pf_bme_spr_newick_n(const float* preds, int32_t n, const char* const* ids, const int64_t* id_lens, int32_t clamp_negative,
@@ -809,10 +846,8 @@ extern "C" {
 // per internal node).
 int64_t pf_nj_support_n(const float* preds, const float* reps, int32_t R, int32_t n, const char* const* ids,
                         const int64_t* id_lens, int32_t clamp_negative, int32_t threads, char* out, int64_t cap) {
-    if (!preds || !reps || R < 1 || n < 1 || !ids || !id_lens || (!out && cap > 0)) return PF_EINVAL;
-    for (int32_t i = 0; i < n; ++i) if (id_lens[i] < 0) return PF_EINVAL;
-    try {
-        std::string text;
+    if (!preds || !reps || R < 1) return PF_EINVAL;
+    return text_call(n, ids, id_lens, out, cap, [&](std::string& text) {
         if (n <= 3) {                               // no internal split
             nj_newick(preds, n, ids, id_lens, clamp_negative != 0, text);
         } else {
@@ -854,9 +889,8 @@ int64_t pf_nj_support_n(const float* preds, const float* reps, int32_t R, int32_
             }
             nj_format(tree, n, ids, id_lens, clamp_negative != 0, support.data(), text);
         }
-        if (out && (int64_t)text.size() <= cap) memcpy(out, text.data(), text.size());
-        return (int64_t)text.size();
-    } catch (...) { return PF_ENOMEM; }
+        return PF_OK;
+    });
 }
 
 }  // extern "C"
@@ -868,7 +902,7 @@ extern "C" {
 // source with a NaN or an infinity is flagged and its table zeros.
 int pf_nj_joins_host_n(const float* preds, int32_t B, int32_t N, int32_t threads, int32_t* slots, double* lengths, uint8_t* nonfinite) {
     if (!preds || !slots || !lengths || !nonfinite || B < 1 || N < 3) return PF_EINVAL;
-    const size_t P = (size_t)N * ((size_t)N - 1) / 2, T = (size_t)pfsup::table_len(N), J = (size_t)N - 3;
+    const size_t P = (size_t)N * ((size_t)N - 1) / 2, T = (size_t)pfnj::table_len(N);
     std::atomic<bool> failed{false};
     try {
         run_pool(B, threads, [&](int32_t b) {
@@ -882,9 +916,7 @@ int pf_nj_joins_host_n(const float* preds, int32_t B, int32_t N, int32_t threads
                 if (bad) { std::fill(s, s + T, 0); std::fill(l, l + T, 0.0); return; }
                 NjTree t;
                 nj_core(p, N, t);
-                for (size_t j = 0; j < J; ++j) { s[2 * j] = t.joins[j].a; s[2 * j + 1] = t.joins[j].b; l[2 * j] = t.joins[j].la; l[2 * j + 1] = t.joins[j].lb; }
-                s[2 * J] = t.i; s[2 * J + 1] = t.j; s[2 * J + 2] = t.k;
-                l[2 * J] = t.li; l[2 * J + 1] = t.lj; l[2 * J + 2] = t.lk;
+                table_of_tree(t, s, l);
             } catch (...) { failed = true; }
         });
     } catch (...) { return PF_ENOMEM; }
@@ -914,38 +946,16 @@ int pf_bionj_joins_host(const float* preds, int32_t B, int32_t N, int32_t* slots
 // through pf_nj_format_joins_n's writer.  n < 3 or a NaN / infinity in preds: pf_nj_newick_n's text.
 int64_t pf_bionj_newick_n(const float* preds, int32_t n, const char* const* ids, const int64_t* id_lens, int32_t clamp_negative,
                           char* out, int64_t cap) {
-    if (!preds || n < 1 || !ids || !id_lens || (!out && cap > 0)) return PF_EINVAL;
-    for (int32_t i = 0; i < n; ++i) if (id_lens[i] < 0) return PF_EINVAL;
-    try {
-        std::string text;
-        uint8_t bad = 1;
-        if (n >= 3) {
-            const size_t joins = (size_t)n - 3, len = 2 * joins + 3;
-            std::vector<int32_t> slots(len, 0);
-            std::vector<double> lengths(len, 0.0);
-            pfbionj::run_serial(preds, 1, n, slots.data(), lengths.data(), &bad);
-            if (!bad) {
-                NjTree t;
-                t.joins.reserve(joins);
-                for (size_t s = 0; s < joins; ++s) t.joins.push_back({slots[2 * s], slots[2 * s + 1], lengths[2 * s], lengths[2 * s + 1]});
-                t.i = slots[2 * joins]; t.j = slots[2 * joins + 1]; t.k = slots[2 * joins + 2];
-                t.li = lengths[2 * joins]; t.lj = lengths[2 * joins + 1]; t.lk = lengths[2 * joins + 2];
-                nj_format(t, n, ids, id_lens, clamp_negative != 0, nullptr, text);
-            }
-        }
-        if (bad) nj_newick(preds, n, ids, id_lens, clamp_negative != 0, text);
-        if (out && (int64_t)text.size() <= cap) memcpy(out, text.data(), text.size());
-        return (int64_t)text.size();
-    } catch (...) { return PF_ENOMEM; }
+    return tree_newick(bionj_start, nullptr, preds, n, ids, id_lens, clamp_negative, out, cap, nullptr);
 }
 
-// Split supports without a device: the bodies of pf_support.hip.h's kernels run serially, one
-// source at a time - the same integers as pf_join_supports.  Twin of phyloformer_amd/supports.py::split_supports.
-int pf_join_supports_host(const int32_t* ref_slots, const int32_t* rep_slots, const uint8_t* rep_flag, int32_t B, int32_t R, int32_t N,
-                          int32_t* count, int64_t* transfer, int32_t* depth, uint8_t* status) {
+// pf_join_supports_host, and with `x` (its arg is set here) pf_join_transfers_host: the bodies of pf_support.hip.h's
+// kernels run serially, one source at a time.  What only the transfers refuse stands at their call.
+static int join_supports_host(const int32_t* ref_slots, const int32_t* rep_slots, const uint8_t* rep_flag, int32_t B, int32_t R, int32_t N,
+                              int32_t* count, int64_t* transfer, int32_t* depth, uint8_t* status, pfsup::Transfers* x) {
     if (!ref_slots || !rep_slots || !count || !transfer || !depth || !status || B < 1 || R < 1 || N < 4 || N > pfbme::MAX_N)
         return PF_EINVAL;
-    const size_t T = (size_t)pfsup::table_len(N), S = (size_t)N - 3, W = (size_t)pfsup::words_of(N), b = (size_t)B, r = (size_t)R;
+    const size_t T = (size_t)pfnj::table_len(N), S = (size_t)N - 3, W = (size_t)pfsup::words_of(N), b = (size_t)B, r = (size_t)R;
     size_t total = 0;
     if (__builtin_mul_overflow(b * r, T * sizeof(int32_t), &total)) return PF_EINVAL;
     try {
@@ -956,19 +966,28 @@ int pf_join_supports_host(const int32_t* ref_slots, const int32_t* rep_slots, co
             if (!(rep_flag && rep_flag[i]) && !pfbme::tree_of_joins(rep_slots + i * T, N, parent.data(), children.data())) return PF_EINVAL;
         // the state of one source with all its replicates, reused from source to source
         std::vector<uint64_t> bits((r + 1) * S * W), tile((size_t)pfsup::TILE * W);
-        std::vector<int32_t> row((r + 1) * (size_t)N), sizes(S), delta(r * S);
+        std::vector<int32_t> row((r + 1) * (size_t)N), sizes(S), delta(r * S), arg(x ? r * S : 0);
         std::vector<uint8_t> bad(b * (r + 1), 0);
         pfsup::Args a{};
         a.ref_slots = ref_slots; a.rep_slots = rep_slots; a.rep_flag = rep_flag;
         a.bits = bits.data(); a.row = row.data(); a.sizes = sizes.data(); a.delta = delta.data(); a.bad = bad.data();
         a.count = count; a.transfer = transfer; a.depth = depth; a.status = status;
         a.N = N; a.R = R; a.nb = 1; a.r0 = 0; a.rc = R;
+        if (x) x->arg = arg.data();
         for (int32_t src = 0; src < B; ++src) {
             a.b0 = src;
-            pfsup::serial_chunk(a, tile.data(), true);
+            if (x) pfsup::serial_chunk<true>(a, tile.data(), true, x);
+            else pfsup::serial_chunk(a, tile.data(), true);
         }
         return PF_OK;
     } catch (...) { return PF_ENOMEM; }
+}
+
+// Split supports without a device: the same integers as pf_join_supports.  Twin of
+// phyloformer_amd/supports.py::split_supports.
+int pf_join_supports_host(const int32_t* ref_slots, const int32_t* rep_slots, const uint8_t* rep_flag, int32_t B, int32_t R, int32_t N,
+                          int32_t* count, int64_t* transfer, int32_t* depth, uint8_t* status) {
+    return join_supports_host(ref_slots, rep_slots, rep_flag, B, R, N, count, transfer, depth, status, nullptr);
 }
 
 // Per-taxon transfer counts without a device: pf_join_supports_host's run with the matching that
@@ -976,35 +995,11 @@ int pf_join_supports_host(const int32_t* ref_slots, const int32_t* rep_slots, co
 int pf_join_transfers_host(const int32_t* ref_slots, const int32_t* rep_slots, const uint8_t* rep_flag, int32_t B, int32_t R, int32_t N,
                            int32_t cutoff_percent, int32_t* count, int64_t* transfer, int32_t* depth, int64_t* moves, int32_t* used,
                            int32_t* capped, int32_t* branch_moves, uint8_t* status) {
-    if (!ref_slots || !rep_slots || !count || !transfer || !depth || !moves || !used || !capped || !status || B < 1 || R < 1 || N < 4 ||
-        N > pfbme::MAX_N || cutoff_percent < 0 || cutoff_percent > 100)
-        return PF_EINVAL;
-    const size_t T = (size_t)pfsup::table_len(N), S = (size_t)N - 3, W = (size_t)pfsup::words_of(N), b = (size_t)B, r = (size_t)R;
-    size_t total = 0;
-    if (__builtin_mul_overflow(b * r, T * sizeof(int32_t), &total)) return PF_EINVAL;
-    if (branch_moves && __builtin_mul_overflow(b * S, (size_t)N * sizeof(int32_t), &total)) return PF_EINVAL;
-    try {
-        std::vector<int32_t> parent((size_t)pfbme::nodes_of(N)), children((size_t)pfbme::nodes_of(N) * 3);
-        for (size_t i = 0; i < b; ++i)                            // refused before any work
-            if (!pfbme::tree_of_joins(ref_slots + i * T, N, parent.data(), children.data())) return PF_EINVAL;
-        for (size_t i = 0; i < b * r; ++i)
-            if (!(rep_flag && rep_flag[i]) && !pfbme::tree_of_joins(rep_slots + i * T, N, parent.data(), children.data())) return PF_EINVAL;
-        // the state of one source with all its replicates, reused from source to source
-        std::vector<uint64_t> bits((r + 1) * S * W), tile((size_t)pfsup::TILE * W);
-        std::vector<int32_t> row((r + 1) * (size_t)N), sizes(S), delta(r * S), arg(r * S);
-        std::vector<uint8_t> bad(b * (r + 1), 0);
-        pfsup::Args a{};
-        a.ref_slots = ref_slots; a.rep_slots = rep_slots; a.rep_flag = rep_flag;
-        a.bits = bits.data(); a.row = row.data(); a.sizes = sizes.data(); a.delta = delta.data(); a.bad = bad.data();
-        a.count = count; a.transfer = transfer; a.depth = depth; a.status = status;
-        const pfsup::Transfers x{arg.data(), moves, used, capped, branch_moves, cutoff_percent};
-        a.N = N; a.R = R; a.nb = 1; a.r0 = 0; a.rc = R;
-        for (int32_t src = 0; src < B; ++src) {
-            a.b0 = src;
-            pfsup::serial_chunk<true>(a, tile.data(), true, &x);
-        }
-        return PF_OK;
-    } catch (...) { return PF_ENOMEM; }
+    if (!moves || !used || !capped || cutoff_percent < 0 || cutoff_percent > 100) return PF_EINVAL;
+    size_t total = 0;       // (B < 1 or N < 4 wrap the product and are refused whatever it gives)
+    if (branch_moves && __builtin_mul_overflow((size_t)B * ((size_t)N - 3), (size_t)N * sizeof(int32_t), &total)) return PF_EINVAL;
+    pfsup::Transfers x{nullptr, moves, used, capped, branch_moves, cutoff_percent};
+    return join_supports_host(ref_slots, rep_slots, rep_flag, B, R, N, count, transfer, depth, status, &x);
 }
 
 // Majority-rule consensus without a device: the bodies of pf_consensus.hip.h's kernels run
@@ -1017,7 +1012,7 @@ int pf_join_consensus_host(const int32_t* rep_slots, const double* rep_lengths, 
     if (!rep_slots || !n_splits || !count || !size || !parent || !leaf_parent || !status || (rep_lengths && (!split_length || !leaf_length)) ||
         B < 1 || R < 1 || N < 4 || N > pfbme::MAX_N || percent < 50 || percent > 99 || (int64_t)R * ((int64_t)N - 3) > pfcon::MAX_ENTRIES)
         return PF_EINVAL;
-    const size_t T = (size_t)pfsup::table_len(N), S = (size_t)N - 3, W = (size_t)pfsup::words_of(N), b = (size_t)B, r = (size_t)R;
+    const size_t T = (size_t)pfnj::table_len(N), S = (size_t)N - 3, W = (size_t)pfsup::words_of(N), b = (size_t)B, r = (size_t)R;
     size_t total = 0;
     if (__builtin_mul_overflow(b * r, T * sizeof(double), &total)) return PF_EINVAL;
     try {

@@ -13,6 +13,8 @@ from typing import Dict, Optional, Tuple
 
 import numpy as np
 
+from .treearrays import (JOINS, REFINE, consensus_arrays, consensus_outputs, ptr, support_arrays, support_outputs, transfer_outputs,
+                         tree_call, unbatched)
 from .weights import ModelWeights
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -543,13 +545,6 @@ class Engine:
                                                              C.c_void_p(d_spread)))
 
     # -- neighbour joining -------------------------------------------------------------------
-    @staticmethod
-    def _seqs_of_pairs(p: int) -> int:
-        n = (1 + int(round((1 + 8 * p) ** 0.5))) // 2
-        if n < 2 or n * (n - 1) // 2 != p:
-            raise ValueError(f"{p} distances are not the pairs of any number of sequences")
-        return n
-
     def nj_joins(self, preds: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """Neighbour joining on the GPU (``pf_nj_joins``): distances ``float32[B, P_N]`` → ``(slots int32[B, T], lengths
         float64[B, T], nonfinite bool[B])``, ``T = 2 (N - 3) + 3`` (``[P_N]`` drops ``B``): the joins ``a, b`` / ``la, lb``
@@ -557,23 +552,21 @@ class Engine:
         for bit.  A source with a NaN or an infinity is flagged and its table unspecified (use ``hostio.nj_newick``)."""
         return self._joins("pf_nj_joins", preds)
 
-    def _joins(self, symbol: str, preds: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-        fn = self._optional(symbol)
-        p = np.ascontiguousarray(np.asarray(preds, dtype=np.float32))
-        single = p.ndim == 1
-        if single:
-            p = p[None, :]
+    @staticmethod
+    def _refuse_distances(p, st, N, T):
+        """What the device forms refuse themselves (``treearrays.tree_call``); two sequences go to the library."""
         if p.ndim != 2:
             raise ValueError(f"expected distances [B, P] or [P], got {p.shape}")
-        B, N = p.shape[0], self._seqs_of_pairs(p.shape[1])
-        T = max(0, 2 * (N - 3) + 3)
-        slots = np.zeros((B, T), dtype=np.int32)
-        lengths = np.zeros((B, T), dtype=np.float64)
-        flag = np.zeros(B, dtype=np.uint8)
-        self._check(fn(self._h, p.ctypes.data if p.size else None, B, N, slots.ctypes.data if T else None,
-                       lengths.ctypes.data if T else None, flag.ctypes.data if B else None))
-        flag = flag.astype(bool)
-        return (slots[0], lengths[0], flag[0]) if single else (slots, lengths, flag)
+        if N < 2:
+            raise ValueError(f"{p.shape[1]} distances are not the pairs of any number of sequences")
+        if st is not None and st.shape != (p.shape[0], T):
+            raise ValueError(f"expected start tables {[p.shape[0], T]}, got {list(st.shape)}")
+
+    def _joins(self, symbol: str, preds: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        fn = self._optional(symbol)
+        p, _, (B, N, _T), single, out = tree_call(preds, JOINS, self._refuse_distances, single_ok=True)
+        self._check(fn(self._h, ptr(p), B, N, *map(ptr, out)))
+        return unbatched((out[0], out[1], out[2].astype(bool)), single)
 
     def nj_joins_device(self, d_preds: int, B: int, N: int, d_slots: int, d_lengths: int, d_nonfinite: int):
         """``pf_nj_joins_device``: device ``preds float32 [B][P_N]`` → device ``slots int32`` / ``lengths float64
@@ -606,27 +599,9 @@ class Engine:
 
     def _refine(self, symbol: str, preds: np.ndarray, start_slots: np.ndarray):
         fn = self._optional(symbol)
-        p = np.ascontiguousarray(np.asarray(preds, dtype=np.float32))
-        st = np.ascontiguousarray(np.asarray(start_slots, dtype=np.int32))
-        single = p.ndim == 1
-        if single:
-            p, st = p[None, :], st[None, :] if st.ndim == 1 else st
-        if p.ndim != 2:
-            raise ValueError(f"expected distances [B, P] or [P], got {p.shape}")
-        B, N = p.shape[0], self._seqs_of_pairs(p.shape[1])
-        T = max(0, 2 * (N - 3) + 3)
-        if st.shape != (B, T):
-            raise ValueError(f"expected start tables {[B, T]}, got {list(st.shape)}")
-        slots = np.zeros((B, T), dtype=np.int32)
-        lengths = np.zeros((B, T), dtype=np.float64)
-        steps = np.zeros(B, dtype=np.int32)
-        tree_length = np.zeros(B, dtype=np.float64)
-        status = np.zeros(B, dtype=np.uint8)
-        self._check(fn(self._h, p.ctypes.data if p.size else None, st.ctypes.data if T else None, B, N,
-                       slots.ctypes.data if T else None, lengths.ctypes.data if T else None, steps.ctypes.data if B else None,
-                       tree_length.ctypes.data if B else None, status.ctypes.data if B else None))
-        out = (slots, lengths, steps, tree_length, status)
-        return tuple(x[0] for x in out) if single else out
+        p, st, (B, N, _T), single, out = tree_call(preds, REFINE, self._refuse_distances, start_slots, single_ok=True)
+        self._check(fn(self._h, ptr(p), ptr(st), B, N, *map(ptr, out)))
+        return unbatched(out, single)
 
     def bme_nni_device(self, d_preds: int, d_start_slots: int, B: int, N: int, d_slots: int, d_lengths: int, d_steps: int,
                        d_tree_length: int, d_status: int):
@@ -659,15 +634,11 @@ class Engine:
         contain it, the sum of its transfer distances and its depth - ``supports.split_supports``, the same integers as
         ``hostio.join_supports_host``.  ``ValueError``-like refusals come as ``EngineError`` (a table that is no join
         table, ``N < 4``)."""
-        from .hostio import support_arrays
         fn = self._optional("pf_join_supports")
         ref, rep, flag, (B, R, N), single = support_arrays(ref_slots, rep_slots, rep_flag)
-        count, transfer, depth, status = (np.zeros((B, N - 3), dtype=np.int32), np.zeros((B, N - 3), dtype=np.int64),
-                                          np.zeros((B, N - 3), dtype=np.int32), np.zeros(B, dtype=np.uint8))
-        self._check(fn(self._h, ref.ctypes.data, rep.ctypes.data, None if flag is None else flag.ctypes.data, B, R, N,
-                       count.ctypes.data, transfer.ctypes.data, depth.ctypes.data, status.ctypes.data))
-        out = (count, transfer, depth, status)
-        return tuple(x[0] for x in out) if single else out
+        out, ptrs = support_outputs(B, N)
+        self._check(fn(self._h, ref.ctypes.data, rep.ctypes.data, ptr(flag), B, R, N, *ptrs))
+        return unbatched(out, single)
 
     def join_supports_device(self, d_ref_slots: int, d_rep_slots: int, d_rep_flag: int, B: int, R: int, N: int, d_count: int,
                              d_transfer: int, d_depth: int, d_status: int):
@@ -685,12 +656,11 @@ class Engine:
         percent (0 .. 100) → ``(count, transfer, depth, moves int64[B, N], used int32[B, N - 3], capped int32[B, N - 3],
         branch_moves int32[B, N - 3, N] or None, status uint8[B])`` - ``supports.transfer_taxa``, the same integers as
         ``hostio.join_transfers_host``; the first three are ``join_supports``'.  Refusals as ``join_supports``."""
-        from .hostio import support_arrays, transfer_outputs
         fn = self._optional("pf_join_transfers")
         ref, rep, flag, (B, R, N), single = support_arrays(ref_slots, rep_slots, rep_flag)
         out, ptrs = transfer_outputs(B, N, branch_moves)
-        self._check(fn(self._h, ref.ctypes.data, rep.ctypes.data, None if flag is None else flag.ctypes.data, B, R, N, int(cutoff), *ptrs))
-        return tuple(None if x is None else x[0] for x in out) if single else out
+        self._check(fn(self._h, ref.ctypes.data, rep.ctypes.data, ptr(flag), B, R, N, int(cutoff), *ptrs))
+        return unbatched(out, single)
 
     def join_transfers_device(self, d_ref_slots: int, d_rep_slots: int, d_rep_flag: int, B: int, R: int, N: int, cutoff: int,
                               d_count: int, d_transfer: int, d_depth: int, d_moves: int, d_used: int, d_capped: int,
@@ -712,13 +682,11 @@ class Engine:
         float64[B, N - 3] or None, leaf_parent int32[B, N], leaf_length float64[B, N] or None, status uint8[B])`` -
         ``consensus.join_consensus``, the same integers and the same doubles, bit for bit, as
         ``hostio.join_consensus_host``.  A table that is no join table is refused (``ValueError``)."""
-        from .hostio import consensus_arrays, consensus_outputs
         fn = self._optional("pf_join_consensus")
         rep, lengths, flag, (B, R, N), single = consensus_arrays(rep_slots, rep_lengths, rep_flag)
         out, ptrs = consensus_outputs(B, N, lengths is not None)
-        self._check(fn(self._h, rep.ctypes.data, None if lengths is None else lengths.ctypes.data,
-                       None if flag is None else flag.ctypes.data, B, R, N, int(percent), *ptrs))
-        return tuple(None if x is None else x[0] for x in out) if single else out
+        self._check(fn(self._h, rep.ctypes.data, ptr(lengths), ptr(flag), B, R, N, int(percent), *ptrs))
+        return unbatched(out, single)
 
     def join_consensus_device(self, d_rep_slots: int, d_rep_lengths: int, d_rep_flag: int, B: int, R: int, N: int, percent: int,
                               d_n_splits: int, d_count: int, d_size: int, d_parent: int, d_split_length: int, d_leaf_parent: int,

@@ -15,6 +15,8 @@ from typing import List, Sequence, Tuple
 import numpy as np
 
 from .engine import load_library
+from .treearrays import (JOINS, REFINE, consensus_arrays, consensus_outputs, ptr, support_arrays, support_outputs,
+                         transfer_outputs, tree_call, unbatched)
 
 # library functions of this module that are not part of include/phyloformer_amd.h (bound here, not in
 # engine.SIGNATURES, whose set must equal the header's)
@@ -29,12 +31,17 @@ _PRIVATE = {
 }
 
 
+_bound = None
+
+
 def _lib():
+    global _bound
     lib = load_library()
-    for name, (res, args) in _PRIVATE.items():
-        fn = getattr(lib, name)
-        if fn.argtypes is None:
+    if lib is not _bound:
+        for name, (res, args) in _PRIVATE.items():
+            fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
+        _bound = lib
     return lib
 
 PF_FASTA_EBYTE, PF_FASTA_ERAGGED, PF_FASTA_ENOHEADER, PF_FASTA_EEMPTY, PF_FASTA_ECAP, PF_FASTA_EUTF8 = -16, -17, -18, -19, -20, -21
@@ -94,67 +101,75 @@ def load_alignment(filepath) -> Tuple[np.ndarray, List[str]]:
         return parse_fasta(fh.read())
 
 
-def format_phylip(preds: np.ndarray, ids: Sequence[str]) -> bytes:
-    """Distance vector ``[P]`` + ids → PHYLIP text (utf-8 bytes), byte-identical to ``vec_to_phylip``."""
-    lib = load_library()
-    n = len(ids)
+def _ids(ids: Sequence[str]):
+    """ids → ``(c_char_p array, int64 byte lengths, the encoded ids)``.  Explicit lengths: an id may hold NUL bytes.  The
+    encoded list must stay referenced during the call."""
+    enc = [s.encode("utf8") for s in ids]
+    return (C.c_char_p * len(enc))(*enc), np.array([len(e) for e in enc], dtype=np.int64), enc
+
+
+def _pair_vector(preds, n: int) -> np.ndarray:
+    """The distances of ``n`` sequences as a contiguous float32 vector ``[n (n - 1) / 2]``."""
     p = np.ascontiguousarray(np.asarray(preds, dtype=np.float32).reshape(-1))
     if p.size != n * (n - 1) // 2:
         raise ValueError(f"expected {n * (n - 1) // 2} distances for {n} sequences, got {p.shape}")
-    enc = [s.encode("utf8") for s in ids]
-    arr = (C.c_char_p * n)(*enc)
-    lens = np.array([len(e) for e in enc], dtype=np.int64)      # explicit lengths: an id may hold NUL bytes
-    cap = int(lens.sum()) + n * (n * 24 + 2) + 32
-    buf = C.create_string_buffer(cap)
-    w = lib.pf_format_phylip_n(p.ctypes.data, n, arr, lens.ctypes.data, buf, cap)
-    if w < 0:
-        raise RuntimeError(f"pf_format_phylip failed with status {w}")
-    if w > cap:                                      # astronomically large distances
+    return p
+
+
+def _check_rc(symbol: str, rc: int, hint: str = ""):
+    """The status of a host call: ``-1`` of a call with a ``hint`` of what it refuses is a ``ValueError``, every other
+    negative code a ``RuntimeError``."""
+    if rc == -1 and hint:
+        raise ValueError(f"{symbol} refused its arguments ({hint}?)")
+    if rc < 0:
+        raise RuntimeError(f"{symbol} failed with status {rc}")
+
+
+def _text_call(symbol: str, lead, trail, cap: int, retry: bool = True, name: str = "") -> bytes:
+    """The sizing protocol of a text call ``symbol(*lead, out, cap, *trail)`` → the text's size: one call with a buffer of
+    ``cap`` bytes (0: none, a query) and, where the text is longer, ``retry`` with the size it returned.  ``name``: what
+    the error calls the function, where that is not ``symbol``."""
+    fn = getattr(_lib(), symbol)
+    buf = C.create_string_buffer(cap) if cap else None
+    w = fn(*lead, buf, cap, *trail)
+    if retry and w > cap:
         cap = int(w)
         buf = C.create_string_buffer(cap)
-        w = lib.pf_format_phylip_n(p.ctypes.data, n, arr, lens.ctypes.data, buf, cap)
-    return buf.raw[:w]
+        w = fn(*lead, buf, cap, *trail)
+    if w < 0 or w > cap:
+        raise RuntimeError(f"{name or symbol} failed with status {w}")
+    return buf.raw[:w] if buf is not None else b""
+
+
+def _newick_call(symbol: str, preds, ids: Sequence[str], clamp_negative: bool, guess: bool, trail=(), name: str = "") -> bytes:
+    """A text call on distances ``[P]`` + ids.  ``guess``: the first buffer has room for the NJ text with longer numbers
+    (one run of an expensive call, not two); else the call is queried first."""
+    n = len(ids)
+    p = _pair_vector(preds, n)
+    arr, lens, _enc = _ids(ids)
+    cap = int(lens.sum()) + 64 * max(n, 1) + 64 if guess else 0
+    return _text_call(symbol, (p.ctypes.data, n, arr, lens.ctypes.data, int(clamp_negative)), trail, cap, name=name)
+
+
+def format_phylip(preds: np.ndarray, ids: Sequence[str]) -> bytes:
+    """Distance vector ``[P]`` + ids → PHYLIP text (utf-8 bytes), byte-identical to ``vec_to_phylip``."""
+    n = len(ids)
+    p = _pair_vector(preds, n)
+    arr, lens, _enc = _ids(ids)
+    cap = int(lens.sum()) + n * (n * 24 + 2) + 32                # (longer only with astronomically large distances)
+    return _text_call("pf_format_phylip_n", (p.ctypes.data, n, arr, lens.ctypes.data), (), cap, name="pf_format_phylip")
 
 
 def nj_newick(preds: np.ndarray, ids: Sequence[str], clamp_negative: bool = True) -> bytes:
     """Distance vector ``[P]`` + ids → Newick text of the neighbour-joining tree (utf-8 bytes), byte-identical to
     ``nj.neighbor_joining`` on the matrix ``vec_to_phylip`` builds (the CLI's ``--trees``, infer_alns.py:120-123)."""
-    lib = load_library()
-    n = len(ids)
-    p = np.ascontiguousarray(np.asarray(preds, dtype=np.float32).reshape(-1))
-    if p.size != n * (n - 1) // 2:
-        raise ValueError(f"expected {n * (n - 1) // 2} distances for {n} sequences, got {p.shape}")
-    enc = [s.encode("utf8") for s in ids]
-    arr = (C.c_char_p * n)(*enc)
-    lens = np.array([len(e) for e in enc], dtype=np.int64)
-    need = lib.pf_nj_newick_n(p.ctypes.data, n, arr, lens.ctypes.data, int(clamp_negative), None, 0)
-    if need < 0:
-        raise RuntimeError(f"pf_nj_newick_n failed with status {need}")
-    buf = C.create_string_buffer(int(need) + 1)
-    w = lib.pf_nj_newick_n(p.ctypes.data, n, arr, lens.ctypes.data, int(clamp_negative), buf, need)
-    return buf.raw[:w]
+    return _newick_call("pf_nj_newick_n", preds, ids, clamp_negative, guess=False)
 
 
 def bionj_newick(preds: np.ndarray, ids: Sequence[str], clamp_negative: bool = True) -> bytes:
     """``pf_bionj_newick_n``: distance vector ``[P]`` + ids → Newick text (utf-8 bytes) of the BIONJ tree (the CLI's
     ``--bionj``) - byte-identical to ``bionj.bionj_newick_py``."""
-    lib = load_library()
-    n = len(ids)
-    p = np.ascontiguousarray(np.asarray(preds, dtype=np.float32).reshape(-1))
-    if p.size != n * (n - 1) // 2:
-        raise ValueError(f"expected {n * (n - 1) // 2} distances for {n} sequences, got {p.shape}")
-    enc = [s.encode("utf8") for s in ids]
-    arr = (C.c_char_p * n)(*enc)
-    lens = np.array([len(e) for e in enc], dtype=np.int64)
-    cap = int(lens.sum()) + 64 * max(n, 1) + 64                  # (as _refined_newick: one run, not two)
-    buf = C.create_string_buffer(cap)
-    w = lib.pf_bionj_newick_n(p.ctypes.data, n, arr, lens.ctypes.data, int(clamp_negative), buf, cap)
-    if w > cap:
-        buf = C.create_string_buffer(int(w))
-        w = lib.pf_bionj_newick_n(p.ctypes.data, n, arr, lens.ctypes.data, int(clamp_negative), buf, w)
-    if w < 0:
-        raise RuntimeError(f"pf_bionj_newick_n failed with status {w}")
-    return buf.raw[:w]
+    return _newick_call("pf_bionj_newick_n", preds, ids, clamp_negative, guess=True)
 
 
 def bionj_refined_newick(search: str, preds: np.ndarray, ids: Sequence[str], clamp_negative: bool = True) -> bytes:
@@ -185,25 +200,23 @@ def spr_newick(preds: np.ndarray, ids: Sequence[str], clamp_negative: bool = Tru
 
 
 def _refined_newick(stem: str, preds: np.ndarray, ids: Sequence[str], clamp_negative: bool, with_steps: bool):
-    lib = _lib()
-    n = len(ids)
-    p = np.ascontiguousarray(np.asarray(preds, dtype=np.float32).reshape(-1))
-    if p.size != n * (n - 1) // 2:
-        raise ValueError(f"expected {n * (n - 1) // 2} distances for {n} sequences, got {p.shape}")
-    enc = [s.encode("utf8") for s in ids]
-    arr = (C.c_char_p * n)(*enc)
-    lens = np.array([len(e) for e in enc], dtype=np.int64)
-    # (sized by the NJ text plus room for longer numbers: one refinement, not two)
-    cap = int(lens.sum()) + 64 * max(n, 1) + 64
-    buf = C.create_string_buffer(cap)
     steps = C.c_int32(0)
-    w = getattr(lib, stem + "_steps_n")(p.ctypes.data, n, arr, lens.ctypes.data, int(clamp_negative), buf, cap, C.byref(steps))
-    if w > cap:
-        buf = C.create_string_buffer(int(w))
-        w = getattr(lib, stem + "_n")(p.ctypes.data, n, arr, lens.ctypes.data, int(clamp_negative), buf, w)
-    if w < 0:
-        raise RuntimeError(f"{stem}_n failed with status {w}")
-    return (buf.raw[:w], int(steps.value)) if with_steps else buf.raw[:w]
+    text = _newick_call(stem + "_steps_n", preds, ids, clamp_negative, guess=True, trail=(C.byref(steps),), name=stem + "_n")
+    return (text, int(steps.value)) if with_steps else text
+
+
+def _refuse_refine(p, st, n, t):
+    if p.ndim != 2 or st.ndim != 2 or st.shape[0] != p.shape[0]:
+        raise ValueError(f"expected distances [B, P] and start tables [B, T], got {p.shape} and {st.shape}")
+    if n < 3 or st.shape[1] != t or p.shape[0] < 1:
+        raise ValueError(f"{p.shape[1]} distances and {st.shape[1]} slots are not those of N >= 3 sequences")
+
+
+def _refuse_joins(p, _st, n, _t):
+    if p.ndim != 2 or p.shape[0] < 1:
+        raise ValueError(f"expected distances [B >= 1, P], got {p.shape}")
+    if n < 3:
+        raise ValueError(f"{p.shape[1]} distances are not the pairs of N >= 3 sequences")
 
 
 def bme_nni_host(preds: np.ndarray, start_slots: np.ndarray):
@@ -219,173 +232,63 @@ def bme_spr_host(preds: np.ndarray, start_slots: np.ndarray):
 
 
 def _refine_host(symbol: str, preds: np.ndarray, start_slots: np.ndarray):
-    lib = load_library()
-    p = np.ascontiguousarray(np.asarray(preds, dtype=np.float32))
-    st = np.ascontiguousarray(np.asarray(start_slots, dtype=np.int32))
-    if p.ndim != 2 or st.ndim != 2 or st.shape[0] != p.shape[0]:
-        raise ValueError(f"expected distances [B, P] and start tables [B, T], got {p.shape} and {st.shape}")
-    b = p.shape[0]
-    n = (1 + int(round((1 + 8 * p.shape[1]) ** 0.5))) // 2
-    t = 2 * (n - 3) + 3
-    if n * (n - 1) // 2 != p.shape[1] or n < 3 or st.shape[1] != t or b < 1:
-        raise ValueError(f"{p.shape[1]} distances and {st.shape[1]} slots are not those of N >= 3 sequences")
-    slots, lengths = np.zeros((b, t), dtype=np.int32), np.zeros((b, t), dtype=np.float64)
-    steps, tree_length, status = np.zeros(b, dtype=np.int32), np.zeros(b, dtype=np.float64), np.zeros(b, dtype=np.uint8)
-    rc = getattr(lib, symbol)(p.ctypes.data, st.ctypes.data, b, n, slots.ctypes.data, lengths.ctypes.data, steps.ctypes.data,
-                              tree_length.ctypes.data, status.ctypes.data)
-    if rc == -1:
-        raise ValueError(f"{symbol} refused its arguments (an invalid start table?)")
-    if rc < 0:
-        raise RuntimeError(f"{symbol} failed with status {rc}")
-    return slots, lengths, steps, tree_length, status
+    p, st, (b, n, _t), _single, out = tree_call(preds, REFINE, _refuse_refine, start_slots)
+    _check_rc(symbol, getattr(_lib(), symbol)(p.ctypes.data, st.ctypes.data, b, n, *map(ptr, out)), "an invalid start table")
+    return out
 
 
 def nj_joins_host(preds: np.ndarray, threads: int = 1):
     """``Engine.nj_joins`` without a device (``pf_nj_joins_host_n``): ``float32[B, P_N]`` → ``(slots int32[B, T], lengths
     float64[B, T], nonfinite bool[B])``, the table of ``nj.nj_joins`` bit for bit; a flagged source's table is zeros."""
-    lib = _lib()
-    p = np.ascontiguousarray(np.asarray(preds, dtype=np.float32))
-    if p.ndim != 2 or p.shape[0] < 1:
-        raise ValueError(f"expected distances [B >= 1, P], got {p.shape}")
-    b = p.shape[0]
-    n = (1 + int(round((1 + 8 * p.shape[1]) ** 0.5))) // 2
-    if n * (n - 1) // 2 != p.shape[1] or n < 3:
-        raise ValueError(f"{p.shape[1]} distances are not the pairs of N >= 3 sequences")
-    t = 2 * (n - 3) + 3
-    slots, lengths, flag = np.zeros((b, t), dtype=np.int32), np.zeros((b, t), dtype=np.float64), np.zeros(b, dtype=np.uint8)
-    rc = lib.pf_nj_joins_host_n(p.ctypes.data, b, n, int(threads), slots.ctypes.data, lengths.ctypes.data, flag.ctypes.data)
-    if rc < 0:
-        raise RuntimeError(f"pf_nj_joins_host_n failed with status {rc}")
-    return slots, lengths, flag.astype(bool)
+    return _joins_host("pf_nj_joins_host_n", preds, int(threads))
 
 
 def bionj_joins_host(preds: np.ndarray):
     """``Engine.bionj_joins`` without a device (``pf_bionj_joins_host``): ``float32[B, P_N]`` → ``(slots int32[B, T],
     lengths float64[B, T], nonfinite bool[B])``, the table of ``bionj.bionj_joins`` bit for bit; a flagged source's
-    table is zeros.  ``ValueError`` for what the library refuses."""
-    lib = load_library()
-    p = np.ascontiguousarray(np.asarray(preds, dtype=np.float32))
-    if p.ndim != 2 or p.shape[0] < 1:
-        raise ValueError(f"expected distances [B >= 1, P], got {p.shape}")
-    b = p.shape[0]
-    n = (1 + int(round((1 + 8 * p.shape[1]) ** 0.5))) // 2
-    if n * (n - 1) // 2 != p.shape[1] or n < 3:
-        raise ValueError(f"{p.shape[1]} distances are not the pairs of N >= 3 sequences")
-    t = 2 * (n - 3) + 3
-    slots, lengths, flag = np.zeros((b, t), dtype=np.int32), np.zeros((b, t), dtype=np.float64), np.zeros(b, dtype=np.uint8)
-    rc = lib.pf_bionj_joins_host(p.ctypes.data, b, n, slots.ctypes.data, lengths.ctypes.data, flag.ctypes.data)
-    if rc < 0:
-        raise RuntimeError(f"pf_bionj_joins_host failed with status {rc}")
+    table is zeros.  ``RuntimeError`` for what the library refuses."""
+    return _joins_host("pf_bionj_joins_host", preds)
+
+
+def _joins_host(symbol: str, preds: np.ndarray, *options):
+    p, _, (b, n, _t), _single, (slots, lengths, flag) = tree_call(preds, JOINS, _refuse_joins)
+    _check_rc(symbol, getattr(_lib(), symbol)(p.ctypes.data, b, n, *options, ptr(slots), ptr(lengths), ptr(flag)))
     return slots, lengths, flag.astype(bool)
-
-
-def support_arrays(ref_slots, rep_slots, rep_flag):
-    """The arguments of the three ``pf_join_supports`` entry points, checked: ``(ref int32[B, T], rep int32[B, R, T], flag
-    uint8[B, R] or None, (B, R, N), single)``."""
-    ref = np.ascontiguousarray(np.asarray(ref_slots, dtype=np.int32))
-    rep = np.ascontiguousarray(np.asarray(rep_slots, dtype=np.int32))
-    single = ref.ndim == 1
-    if single:
-        ref, rep = ref[None, :], rep[None] if rep.ndim == 2 else rep
-    if ref.ndim != 2 or rep.ndim != 3 or rep.shape[0] != ref.shape[0] or rep.shape[2] != ref.shape[1]:
-        raise ValueError(f"expected reference tables [B, T] and replicate tables [B, R, T], got {ref.shape} and {rep.shape}")
-    b, r, t = rep.shape
-    n = (t - 3) // 2 + 3
-    if t < 5 or 2 * (n - 3) + 3 != t or b < 1 or r < 1:
-        raise ValueError(f"{t} slots are not the join table of N >= 4 sequences, or no source or replicate ({b}, {r})")
-    flag = None
-    if rep_flag is not None:
-        flag = np.ascontiguousarray(np.asarray(rep_flag).astype(bool).astype(np.uint8).reshape(b, r))
-    return ref, rep, flag, (b, r, n), single
 
 
 def join_supports_host(ref_slots, rep_slots, rep_flag=None):
     """``pf_join_supports_host``: ``Engine.join_supports`` without a device - the same bodies run serially, the same
     integers as ``supports.split_supports``.  ``ValueError`` for what the library refuses (``N < 4``, a table that is no
     join table)."""
-    lib = load_library()
     ref, rep, flag, (b, r, n), single = support_arrays(ref_slots, rep_slots, rep_flag)
-    count, transfer, depth, status = (np.zeros((b, n - 3), dtype=np.int32), np.zeros((b, n - 3), dtype=np.int64),
-                                      np.zeros((b, n - 3), dtype=np.int32), np.zeros(b, dtype=np.uint8))
-    rc = lib.pf_join_supports_host(ref.ctypes.data, rep.ctypes.data, None if flag is None else flag.ctypes.data, b, r, n,
-                                   count.ctypes.data, transfer.ctypes.data, depth.ctypes.data, status.ctypes.data)
-    if rc == -1:
-        raise ValueError("pf_join_supports_host refused its arguments (a table that is no join table?)")
-    if rc < 0:
-        raise RuntimeError(f"pf_join_supports_host failed with status {rc}")
-    out = (count, transfer, depth, status)
-    return tuple(x[0] for x in out) if single else out
-
-
-def transfer_outputs(b: int, n: int, branch_moves: bool = True):
-    """The results of the three ``pf_join_transfers`` entry points, zeroed: ``((count, transfer, depth, moves, used, capped,
-    branch_moves or None, status), pointers)``."""
-    s = n - 3
-    out = (np.zeros((b, s), dtype=np.int32), np.zeros((b, s), dtype=np.int64), np.zeros((b, s), dtype=np.int32),
-           np.zeros((b, n), dtype=np.int64), np.zeros((b, s), dtype=np.int32), np.zeros((b, s), dtype=np.int32),
-           np.zeros((b, s, n), dtype=np.int32) if branch_moves else None, np.zeros(b, dtype=np.uint8))
-    return out, [None if x is None else x.ctypes.data for x in out]
+    out, ptrs = support_outputs(b, n)
+    _check_rc("pf_join_supports_host", _lib().pf_join_supports_host(ref.ctypes.data, rep.ctypes.data, ptr(flag), b, r, n, *ptrs),
+              "a table that is no join table")
+    return unbatched(out, single)
 
 
 def join_transfers_host(ref_slots, rep_slots, rep_flag=None, cutoff: int = 100, branch_moves: bool = True):
     """``pf_join_transfers_host``: ``Engine.join_transfers`` without a device - the same bodies run serially, the same
     integers as ``supports.transfer_taxa``.  ``ValueError`` for what the library refuses (``N < 4``, a table that is no
     join table, a cutoff outside 0 .. 100)."""
-    lib = load_library()
     ref, rep, flag, (b, r, n), single = support_arrays(ref_slots, rep_slots, rep_flag)
     out, ptrs = transfer_outputs(b, n, branch_moves)
-    rc = lib.pf_join_transfers_host(ref.ctypes.data, rep.ctypes.data, None if flag is None else flag.ctypes.data, b, r, n, int(cutoff), *ptrs)
-    if rc == -1:
-        raise ValueError("pf_join_transfers_host refused its arguments (a table that is no join table, a cutoff outside 0 .. 100?)")
-    if rc < 0:
-        raise RuntimeError(f"pf_join_transfers_host failed with status {rc}")
-    return tuple(None if x is None else x[0] for x in out) if single else out
-
-
-def consensus_arrays(rep_slots, rep_lengths, rep_flag):
-    """The arguments of the three ``pf_join_consensus`` entry points, checked: ``(rep int32[B, R, T], lengths float64[B, R,
-    T] or None, flag uint8[B, R] or None, (B, R, N), single)``."""
-    rep = np.ascontiguousarray(np.asarray(rep_slots, dtype=np.int32))
-    single = rep.ndim == 2
-    if single:
-        rep = rep[None]
-    if rep.ndim != 3:
-        raise ValueError(f"expected replicate tables [B, R, T] or [R, T], got {rep.shape}")
-    b, r, t = rep.shape
-    n = (t - 3) // 2 + 3
-    if t < 5 or 2 * (n - 3) + 3 != t or b < 1 or r < 1:
-        raise ValueError(f"{t} slots are not the join table of N >= 4 sequences, or no source or replicate ({b}, {r})")
-    lengths = flag = None
-    if rep_lengths is not None:
-        lengths = np.ascontiguousarray(np.asarray(rep_lengths, dtype=np.float64).reshape(b, r, t))
-    if rep_flag is not None:
-        flag = np.ascontiguousarray(np.asarray(rep_flag).astype(bool).astype(np.uint8).reshape(b, r))
-    return rep, lengths, flag, (b, r, n), single
-
-
-def consensus_outputs(b: int, n: int, lengths: bool):
-    """The results of a ``pf_join_consensus`` call, zeroed, and their addresses in the order of the C arguments."""
-    s = n - 3
-    out = (np.zeros(b, dtype=np.int32), np.zeros((b, s), dtype=np.int32), np.zeros((b, s), dtype=np.int32),
-           np.zeros((b, s), dtype=np.int32), np.zeros((b, s), dtype=np.float64) if lengths else None,
-           np.zeros((b, n), dtype=np.int32), np.zeros((b, n), dtype=np.float64) if lengths else None, np.zeros(b, dtype=np.uint8))
-    return out, [None if x is None else x.ctypes.data for x in out]
+    _check_rc("pf_join_transfers_host",
+              _lib().pf_join_transfers_host(ref.ctypes.data, rep.ctypes.data, ptr(flag), b, r, n, int(cutoff), *ptrs),
+              "a table that is no join table, a cutoff outside 0 .. 100")
+    return unbatched(out, single)
 
 
 def join_consensus_host(rep_slots, rep_lengths=None, rep_flag=None, percent: int = 50):
     """``pf_join_consensus_host``: ``Engine.join_consensus`` without a device - the same bodies run serially, the integers
     and (bit for bit) the doubles of ``consensus.join_consensus``; a source with a table that is no join table comes back
     with status 1 and zeros.  ``ValueError`` for what the library refuses (``N < 4``, a threshold outside 50 .. 99)."""
-    lib = load_library()
     rep, lengths, flag, (b, r, n), single = consensus_arrays(rep_slots, rep_lengths, rep_flag)
     out, ptrs = consensus_outputs(b, n, lengths is not None)
-    rc = lib.pf_join_consensus_host(rep.ctypes.data, None if lengths is None else lengths.ctypes.data,
-                                    None if flag is None else flag.ctypes.data, b, r, n, int(percent), *ptrs)
-    if rc == -1:
-        raise ValueError(f"pf_join_consensus_host refused its arguments (a threshold of {percent} percent outside 50 .. 99?)")
-    if rc < 0:
-        raise RuntimeError(f"pf_join_consensus_host failed with status {rc}")
-    return tuple(None if x is None else x[0] for x in out) if single else out
+    _check_rc("pf_join_consensus_host",
+              _lib().pf_join_consensus_host(rep.ctypes.data, ptr(lengths), ptr(flag), b, r, n, int(percent), *ptrs),
+              f"a threshold of {percent} percent outside 50 .. 99")
+    return unbatched(out, single)
 
 
 def _join_table(slots, lengths, n: int) -> Tuple[np.ndarray, np.ndarray]:
@@ -404,18 +307,10 @@ def newick_of_joins(slots, lengths, ids: Sequence[str], clamp_negative: bool = T
     """``pf_nj_format_joins_n``: the Newick text (utf-8 bytes) of one source's join table - ``Engine.nj_joins``'s ``slots``
     / ``lengths [2 (n - 3) + 3]`` - byte-identical to ``nj.newick_of_joins``; with the table of the same distances it is
     ``nj_newick``'s text."""
-    lib = load_library()
     n = len(ids)
     s, l = _join_table(slots, lengths, n)
-    enc = [i.encode("utf8") for i in ids]
-    arr = (C.c_char_p * n)(*enc)
-    lens = np.array([len(e) for e in enc], dtype=np.int64)
-    need = lib.pf_nj_format_joins_n(s.ctypes.data, l.ctypes.data, n, arr, lens.ctypes.data, int(clamp_negative), None, 0)
-    if need < 0:
-        raise RuntimeError(f"pf_nj_format_joins_n failed with status {need}")
-    buf = C.create_string_buffer(int(need) + 1)
-    w = lib.pf_nj_format_joins_n(s.ctypes.data, l.ctypes.data, n, arr, lens.ctypes.data, int(clamp_negative), buf, need)
-    return buf.raw[:w]
+    arr, lens, _enc = _ids(ids)
+    return _text_call("pf_nj_format_joins_n", (s.ctypes.data, l.ctypes.data, n, arr, lens.ctypes.data, int(clamp_negative)), (), 0)
 
 
 def newick_of_joins_py(slots, lengths, ids: Sequence[str], clamp_negative: bool = True) -> str:
@@ -434,28 +329,17 @@ def nj_support(preds: np.ndarray, reps: np.ndarray, ids: Sequence[str], clamp_ne
     """``pf_nj_support_n``: the ``nj_newick`` text of ``preds [P]`` with the bootstrap support of every internal node,
     counted over the NJ trees of ``reps [R][P]`` (joined on ``threads`` native threads, GIL released) - byte-identical
     to ``bootstrap.support_newick_py``."""
-    lib = _lib()
     n = len(ids)
-    p = np.ascontiguousarray(np.asarray(preds, dtype=np.float32).reshape(-1))
-    if p.size != n * (n - 1) // 2:
-        raise ValueError(f"expected {n * (n - 1) // 2} distances for {n} sequences, got {p.shape}")
+    p = _pair_vector(preds, n)
     r = np.ascontiguousarray(np.asarray(reps, dtype=np.float32))
     if r.ndim != 2 or r.shape[0] < 1 or r.shape[1] != p.size:
         raise ValueError(f"expected replicates [R >= 1][{p.size}], got {r.shape}")
-    enc = [s.encode("utf8") for s in ids]
-    arr = (C.c_char_p * n)(*enc)
-    lens = np.array([len(e) for e in enc], dtype=np.int64)
-    # one NJ sizes the text: the labels add at most "100" per internal node
-    base = lib.pf_nj_newick_n(p.ctypes.data, n, arr, lens.ctypes.data, int(clamp_negative), None, 0)
-    if base < 0:
-        raise RuntimeError(f"pf_nj_newick_n failed with status {base}")
-    cap = int(base) + 3 * n + 16
-    buf = C.create_string_buffer(cap)
-    w = lib.pf_nj_support_n(p.ctypes.data, r.ctypes.data, r.shape[0], n, arr, lens.ctypes.data, int(clamp_negative),
-                            int(threads), buf, cap)
-    if w < 0 or w > cap:
-        raise RuntimeError(f"pf_nj_support_n failed with status {w}")
-    return buf.raw[:w]
+    arr, lens, _enc = _ids(ids)
+    # one NJ sizes the text: the labels add at most "100" per internal node.  Every call joins all replicates: no retry
+    base = _lib().pf_nj_newick_n(p.ctypes.data, n, arr, lens.ctypes.data, int(clamp_negative), None, 0)
+    _check_rc("pf_nj_newick_n", base)
+    return _text_call("pf_nj_support_n", (p.ctypes.data, r.ctypes.data, r.shape[0], n, arr, lens.ctypes.data, int(clamp_negative),
+                                          int(threads)), (), int(base) + 3 * n + 16, retry=False)
 
 
 class FastaBatch:
