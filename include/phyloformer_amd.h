@@ -119,6 +119,9 @@ const char* pf_last_error(const pf_handle_t* h);
  *                      always runs whole, and the results do not depend on it; tests/tuning
  *   "spr_pairs_simple" int 1 = pf_bme_spr forms its pair table with the one-thread-per-entry kernel instead of the
  *                      tiled one (default 0): the same bits; the baseline of tools/spr_bench.py
+ *   "delta_atomic" int 0 = pf_delta evaluates every quartet six times, once for each of its pairs, without atomics
+ *                      on the pair sums, instead of once with LDS and global atomics (default 1): the same integers;
+ *                      the comparison of tools/delta_bench.py
  *   "spr_step_cap" int moves after which pf_bme_spr caps a source (status 2); <= 0 (default): 16 N; tests
  *   "colstats_fine" int k_colstats blocks per pair group (0), per run of a group (1) or chosen from the batch
  *                      size (-1, default): the same summation tree either way, so the same bits; tests/tools
@@ -398,6 +401,33 @@ int pf_bionj_joins(pf_handle_t* h, const float* preds, int32_t B, int32_t N, int
 int pf_bionj_joins_device(pf_handle_t* h, const float* d_preds, int32_t B, int32_t N, int32_t* d_slots, double* d_lengths,
                           uint8_t* d_nonfinite);
 int pf_bionj_joins_host(const float* preds, int32_t B, int32_t N, int32_t* slots, double* lengths, uint8_t* nonfinite);
+
+/* ---- delta scores: how tree-like the distances are (additive to ABI 5) ----
+ *
+ * The delta plot of Holland, Huber, Dress & Moulton (2002; delta.plot of R's ape) of every source, bit for bit that of
+ * phyloformer_amd/delta.py::delta_py.  For every quartet a < b < c < d of a source's N sequences: the three float64
+ * sums d_ab + d_cd, d_ac + d_bd, d_ad + d_bc of float32 distances, ordered m1 >= m2 >= m3 by comparisons; delta =
+ * (m1 - m2) / (m1 - m3), 0 where m1 == m3 (one correctly rounded float64 division); q = rint(delta 2^30), ties to even,
+ * an integer in [0, 2^30].  A tree's distances give 0 for every quartet.  Everything behind q is integer arithmetic, so
+ * no order of summation shows (csrc/pf_delta.hip.h, csrc/pf_delta_host.h).
+ *   preds     float  [B][P_N]   pf_forward's distances, pairs i < j in lexicographic order
+ *   pair_sum  int64  [B][P_N]   for the pair (i, j): the sum of q over the C(N - 2, 2) quartets that hold both.  The sum
+ *                               over the pairs of sequence i is 3 times the sum of q over the quartets that hold i, the
+ *                               sum over all pairs 6 times the sum over all quartets
+ *   hist      int64  [B][K]     the quartets with min(K - 1, (q K) >> 30) equal to the bin, each counted once
+ *   nonfinite uint8  [B]        1: the source holds a NaN or an infinity; its pair_sum and hist are zeros
+ * pf_delta takes host arrays and is synchronous; pf_delta_device takes device arrays and is asynchronous on the
+ * handle's stream; pf_delta_host visits every quartet once, serially, without a handle or a device.  One call with B
+ * sources equals B calls with one.  The device evaluates every quartet once and adds its q to its six pairs by
+ * integer atomics (option "delta_atomic"); it keeps no state per source; a call's work is cut into launches of a
+ * bounded number of quartet evaluations, all on the handle's stream with no synchronisation between them.  Refused with
+ * PF_EINVAL before any device work, the message naming the value: N < 4 or N > 2,048 (3 C(N - 1, 3) 2^30 must stay below
+ * 2^63); B < 1; K < 1 or K > 64; NULL buffers.  pf_profile_get("delta") counts the calls of the two handle entry
+ * points. */
+int pf_delta(pf_handle_t* h, const float* preds, int32_t B, int32_t N, int32_t K, int64_t* pair_sum, int64_t* hist, uint8_t* nonfinite);
+int pf_delta_device(pf_handle_t* h, const float* d_preds, int32_t B, int32_t N, int32_t K, int64_t* d_pair_sum, int64_t* d_hist,
+                    uint8_t* d_nonfinite);
+int pf_delta_host(const float* preds, int32_t B, int32_t N, int32_t K, int64_t* pair_sum, int64_t* hist, uint8_t* nonfinite);
 
 /* ---- balanced minimum-evolution NNI refinement of a join table (additive to ABI 5) ----
  *

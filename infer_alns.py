@@ -18,7 +18,9 @@ hold (``phyloformer_amd/analyses.py``: one description per mode, with the combin
 GPU and written behind it.  A directory entry without a FASTA extension, or a file that does
 not parse, has the reference's side effects (infer_alns.py:97-117): every entry in front of it
 (in ``glob`` order, as there) gets its output, nothing behind it does, then the reference's
-exception is raised; the multi-GPU modes, which have no counterpart, refuse such a directory up front.
+exception is raised.  ``--delta`` (``phyloformer_amd/delta.py``) is no mode of its own: it asks of every launch's
+distances, whichever mode made them, how tree-like they are, and writes ``<stem>.delta.tsv``, ``<stem>.delta.phy`` and
+``<stem>.delta.hist.tsv``.  The multi-GPU modes, which have no counterpart, refuse such a directory up front.
 The forward pass runs in ``libphyloformer_amd.so``; there is no CPU fallback.
 """
 import argparse
@@ -57,6 +59,14 @@ def build_parser():
                              "<stem>.bionj.bme.nwk / <stem>.bionj.spr.nwk, the same searches started from the BIONJ tree, as "
                              "FastME starts them; every other output keeps its bytes; the trees of windows, cuts and "
                              "replicates stay NJ")
+    parser.add_argument("--delta", action="store_true",
+                        help="tree-likeness of the distances (the delta plot of Holland et al. 2002, delta.plot of R's ape), "
+                             "computed on the GPU for every quartet of sequences: writes <stem>.delta.tsv (per sequence the mean "
+                             "delta over the quartets that hold it, and that relative to the mean over sequences; a leading "
+                             "comment line has the overall mean and the number of quartets), <stem>.delta.phy (per pair the mean "
+                             "delta, a PHYLIP matrix) and <stem>.delta.hist.tsv (quartets per 20 bins of delta); 0 = the "
+                             "distances of a tree; with or without -t and with every analysis; at most 2,048 sequences; every "
+                             "other output keeps its bytes")
     parser.add_argument("--device", type=int, default=0, help="HIP device ordinal (default 0)")
     parser.add_argument("--devices", default=None,
                         help="comma-separated HIP device ordinals: shard the files over these GPUs, "
@@ -98,6 +108,8 @@ def main(argv=None):
         parser.error(refused)
 
     from phyloformer_amd import scheduler
+    if args.delta and args.shard == "sites":
+        parser.error(scheduler.DELTA_SHARD_SITES)
 
     in_dir = os.path.abspath(args.alndir)
     out_dir = os.path.abspath(args.outdir)  # TypeError if omitted, as in the reference (:90)
@@ -173,7 +185,7 @@ def main(argv=None):
     runner = scheduler.DirectoryRunner(engines, out_dir, trees=args.trees, batch=args.batch,
                                        io_threads=args.io_threads, native_io=not args.python_io,
                                        progress=bar.update if bar is not None else None, modes=modes, bme=args.bme, spr=args.spr,
-                                       bionj=args.bionj)
+                                       bionj=args.bionj, delta=args.delta)
     try:
         stats = runner.run(paths)
     finally:

@@ -26,6 +26,7 @@
 #include "../../include/phyloformer_amd.h"
 #include "pf_bme_host.h"
 #include "pf_bionj_host.h"
+#include "pf_delta_host.h"
 #include "pf_support_host.h"
 #include "pf_consensus_host.h"
 
@@ -940,6 +941,17 @@ int pf_bionj_joins_host(const float* preds, int32_t B, int32_t N, int32_t* slots
         }
         return PF_OK;
     } catch (...) { return PF_ENOMEM; }
+}
+
+// Delta scores without a device: every quartet of every source once, serially - the same arrays
+// as pf_delta, bit for bit.  Twin of phyloformer_amd/delta.py::delta_py.  A source with a NaN or an infinity is flagged
+// and its arrays zeros.
+int pf_delta_host(const float* preds, int32_t B, int32_t N, int32_t K, int64_t* pair_sum, int64_t* hist, uint8_t* nonfinite) {
+    if (!preds || !pair_sum || !hist || !nonfinite || pfdelta::refused(B, N, K)) return PF_EINVAL;
+    const size_t P = (size_t)N * ((size_t)N - 1) / 2;
+    for (int32_t b = 0; b < B; ++b)
+        pfdelta::run_serial(preds + (size_t)b * P, N, K, pair_sum + (size_t)b * P, hist + (size_t)b * (size_t)K, nonfinite + b);
+    return PF_OK;
 }
 
 // preds [n(n-1)/2] -> Newick text of the BIONJ tree, as bionj.py::bionj_newick_py writes it: pf_bionj_joins_host's table

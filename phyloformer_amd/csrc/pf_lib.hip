@@ -46,6 +46,7 @@
 #include "pf_tile.hip.h"
 #include "pf_nj.hip.h"
 #include "pf_bionj.hip.h"
+#include "pf_delta.hip.h"
 #include "pf_bme.hip.h"
 #include "pf_support.hip.h"
 #include "pf_consensus.hip.h"
@@ -260,6 +261,10 @@ struct pf_handle {
     Buffer<char> d_nj{buffers}, d_nj_io{buffers};
     int64_t nj_calls = 0;        // calls since the last pf_profile_reset ("nj_joins")
     int64_t bionj_calls = 0;     // likewise pf_bionj_joins / pf_bionj_joins_device ("bionj_joins")
+    // pf_delta (grow-only): the staging of the host entry point's distances and results; the kernels keep no state
+    Buffer<char> d_delta_io{buffers};
+    int64_t delta_calls = 0;     // pf_delta / pf_delta_device calls since the last pf_profile_reset ("delta")
+    bool delta_atomic = true;    // option "delta_atomic": 0 = k_delta_pairs (the comparison of tools/delta_bench.py)
     // pf_bme_nni / pf_bme_nni_device (grow-only): the state of one chunk of sources (pf_bme.hip.h: carve) and the
     // staging of the host entry point's distances
     Buffer<char> d_bme{buffers};
@@ -2085,6 +2090,34 @@ int nj_impl(pf_handle* h, bool bionj, bool device, const pfnj::Tables& user, int
     return PF_OK;
 }
 
+// ---- delta scores on the device (pf_delta, pf_delta_device; pf_delta.hip.h, pf_delta_host.h) ----
+
+// The caller's arrays on the device (asynchronous) or on the host (staged, one synchronisation).  The kernels keep no
+// state per source, so a call is not cut into chunks of sources: its launches are cut by their work (launch_delta).
+int delta_impl(pf_handle* h, bool device, const pfdelta::Tables& user, int B, int N, int K) {
+    pfdelta::Tables io{};
+    auto list = [&](auto& v) { pfdelta::staging_arrays(v, io, user, (size_t)std::max(B, 0), std::max(N, 0), std::max(K, 0)); };
+    if (pfspan::missing(list)) return fail(h, PF_EINVAL, "null buffer");
+    switch (pfdelta::refused(B, N, K)) {
+        case 1: return fail(h, PF_EINVAL, "delta scores take %d <= N <= %d sequences (got %d)", pfdelta::MIN_N, pfdelta::MAX_N, N);
+        case 2: return fail(h, PF_EINVAL, "bad dimensions B=%d N=%d", B, N);
+        case 3: return fail(h, PF_EINVAL, "delta scores take 1 <= K <= %d bins (got %d)", pfdelta::MAX_K, K);
+    }
+    size_t n = 0;
+    if (!mul_size((size_t)B, (size_t)N * (size_t)(N - 1) / 2, sizeof(int64_t), &n))
+        return fail(h, PF_EINVAL, "B=%d sources of N=%d sequences overflow the address space", B, N);
+    HIPCHK(h, hipSetDevice(h->device));
+    ++h->delta_calls;
+    auto launch = [&](const pfdelta::Tables& d) -> int {
+        h->cur = h->stream;
+        const hipError_t e = pfdelta::launch_delta(h->stream, d.preds, B, N, K, d.pair_sum, d.hist, d.flag, h->delta_atomic);
+        if (e != hipSuccess) return fail(h, PF_EHIP, "k_delta_* launch failed: %s", hipGetErrorString(e));
+        return PF_OK;
+    };
+    if (device) return launch(user);
+    return staged_call(h, h->d_delta_io, list, [&] { return launch(io); });
+}
+
 // ---- balanced NNI refinement on the device (pf_bme_nni, pf_bme_nni_device; pf_bme.hip.h, pf_bme_host.h) ----
 
 // every start table is a join table (slots in [0, N), every join of two live clusters, three distinct live slots last)
@@ -2582,6 +2615,7 @@ int pf_set_option(pf_handle_t* h, const char* key, int64_t value) {
     }
     else if (k == "ws_limit_mb") h->ws_limit_bytes = value << 20;
     else if (k == "spr_pairs_simple") h->spr_pairs_simple = value != 0;
+    else if (k == "delta_atomic") h->delta_atomic = value != 0;
     else if (k == "spr_step_cap") h->spr_step_cap = value > 0 ? value : 0;
     else if (k == "sub_floats") h->sub_floats = value > 0 ? value : SUB_FLOATS_DEFAULT;
     else return fail(h, PF_EINVAL, "unknown option '%s'", key);
@@ -2761,6 +2795,17 @@ int pf_bionj_joins_device(pf_handle_t* h, const float* d_preds, int32_t B, int32
                           uint8_t* d_nonfinite) {
     if (!h) return PF_EINVAL;
     return nj_impl(h, true, true, {d_preds, d_slots, d_lengths, d_nonfinite}, B, N);
+}
+
+int pf_delta(pf_handle_t* h, const float* preds, int32_t B, int32_t N, int32_t K, int64_t* pair_sum, int64_t* hist, uint8_t* nonfinite) {
+    if (!h) return PF_EINVAL;
+    return delta_impl(h, false, {preds, pair_sum, hist, nonfinite}, B, N, K);
+}
+
+int pf_delta_device(pf_handle_t* h, const float* d_preds, int32_t B, int32_t N, int32_t K, int64_t* d_pair_sum, int64_t* d_hist,
+                    uint8_t* d_nonfinite) {
+    if (!h) return PF_EINVAL;
+    return delta_impl(h, true, {d_preds, d_pair_sum, d_hist, d_nonfinite}, B, N, K);
 }
 
 int pf_bme_nni(pf_handle_t* h, const float* preds, const int32_t* start_slots, int32_t B, int32_t N, int32_t* slots, double* lengths,
@@ -3035,6 +3080,7 @@ int pf_profile_reset(pf_handle_t* h) {
     h->rechecked = 0;
     h->nj_calls = 0;
     h->bionj_calls = 0;
+    h->delta_calls = 0;
     h->bme_calls = 0;
     h->spr_calls = 0;
     h->sup_calls = 0;
@@ -3063,6 +3109,11 @@ int pf_profile_get(pf_handle_t* h, const char* kernel, int64_t* launches, double
     }
     if (std::strcmp(kernel, "bionj_joins") == 0) {      // pf_bionj_joins / pf_bionj_joins_device calls
         if (launches) *launches = h->bionj_calls;
+        if (total_ms) *total_ms = 0.0;
+        return PF_OK;
+    }
+    if (std::strcmp(kernel, "delta") == 0) {            // pf_delta / pf_delta_device calls
+        if (launches) *launches = h->delta_calls;
         if (total_ms) *total_ms = 0.0;
         return PF_OK;
     }

@@ -136,6 +136,9 @@ SIGNATURES = {
     "pf_bionj_joins": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pf_bionj_joins_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pf_bionj_joins_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pf_delta": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pf_delta_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pf_delta_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pf_bionj_newick_n": (C.c_int64, [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32, C.c_char_p, C.c_int64]),
     "pf_nj_format_joins_n": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32,
                                          C.c_char_p, C.c_int64]),
@@ -193,7 +196,8 @@ CALL_TIME_SYMBOLS = frozenset({"pf_forward_site_map", "pf_forward_site_map_devic
                                "pf_join_supports_device", "pf_join_supports_host", "pf_join_consensus",
                                "pf_join_consensus_device", "pf_join_consensus_host", "pf_bionj_joins",
                                "pf_bionj_joins_device", "pf_bionj_joins_host", "pf_bionj_newick_n", "pf_join_transfers",
-                               "pf_join_transfers_device", "pf_join_transfers_host"})
+                               "pf_join_transfers_device", "pf_join_transfers_host", "pf_delta", "pf_delta_device",
+                               "pf_delta_host"})
 
 _lib: Optional[C.CDLL] = None
 
@@ -586,6 +590,25 @@ class Engine:
         """``pf_bionj_joins_device``: ``nj_joins_device``'s arguments (asynchronous on the handle's stream)."""
         self._check(self._optional("pf_bionj_joins_device")(self._h, C.c_void_p(d_preds), B, N, C.c_void_p(d_slots),
                                                             C.c_void_p(d_lengths), C.c_void_p(d_nonfinite)))
+
+    # -- delta scores -----------------------------------------------------------------------
+    def delta(self, preds: np.ndarray, bins: int = 20) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Delta scores on the GPU (``pf_delta``): distances ``float32[B, P_N]`` → ``(pair_sum int64[B, P_N], hist
+        int64[B, bins], nonfinite uint8[B])`` (``[P_N]`` drops ``B``), ``4 <= N <= 2,048``: for every pair the sum of ``q =
+        rint(delta 2^30)`` over the quartets that hold it, and the quartets per bin of ``q`` - bit for bit
+        ``delta.delta_py`` of every source and ``hostio.delta_host``; ``delta.delta_scores`` derives the means.  A source
+        with a NaN or an infinity is flagged and its arrays are zeros.  ``ValueError`` for what the library refuses."""
+        from .delta import delta_arrays
+        fn = self._optional("pf_delta")
+        p, (B, N), single, out = delta_arrays(preds, bins)
+        self._check(fn(self._h, ptr(p), B, N, int(bins), *map(ptr, out)))
+        return unbatched(out, single)
+
+    def delta_device(self, d_preds: int, B: int, N: int, bins: int, d_pair_sum: int, d_hist: int, d_nonfinite: int):
+        """``pf_delta_device``: device ``preds float32 [B][P_N]`` → device ``pair_sum int64 [B][P_N]``, ``hist int64
+        [B][bins]``, ``nonfinite uint8 [B]`` (asynchronous on the handle's stream)."""
+        self._check(self._optional("pf_delta_device")(self._h, C.c_void_p(d_preds), B, N, bins, C.c_void_p(d_pair_sum),
+                                                      C.c_void_p(d_hist), C.c_void_p(d_nonfinite)))
 
     # -- balanced NNI refinement -------------------------------------------------------------
     def bme_nni(self, preds: np.ndarray, start_slots: np.ndarray):

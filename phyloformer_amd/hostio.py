@@ -250,6 +250,16 @@ def bionj_joins_host(preds: np.ndarray):
     return _joins_host("pf_bionj_joins_host", preds)
 
 
+def delta_host(preds: np.ndarray, n: int = 0, bins: int = 20):
+    """``Engine.delta`` without a device (``pf_delta_host``): ``float32[B, P_n]`` (or ``[P_n]``; ``n`` = 0 takes it from
+    the width) → ``(pair_sum int64[B, P_n], hist int64[B, bins], nonfinite uint8[B])``, every quartet visited once,
+    serially: ``delta.delta_py`` bit for bit.  ``ValueError`` for what the library refuses."""
+    from .delta import delta_arrays
+    p, (b, n), single, out = delta_arrays(preds, bins, n)
+    _check_rc("pf_delta_host", _lib().pf_delta_host(ptr(p), b, n, int(bins), *map(ptr, out)), "N, B or K out of range")
+    return unbatched(out, single)
+
+
 def _joins_host(symbol: str, preds: np.ndarray, *options):
     p, _, (b, n, _t), _single, (slots, lengths, flag) = tree_call(preds, JOINS, _refuse_joins)
     _check_rc(symbol, getattr(_lib(), symbol)(p.ctypes.data, b, n, *options, ptr(slots), ptr(lengths), ptr(flag)))

@@ -66,6 +66,8 @@ def auto_batch(n_seqs: int, n_sites: int, max_batch: int = 4096, token_budget: i
     return int(min(max_batch, max(1, token_budget // tokens)))
 
 
+# the refusal of --delta with --shard sites, in the wording of treekinds.refusals
+DELTA_SHARD_SITES = "--delta cannot be combined with --shard sites: the site-sharded runner writes distances and NJ trees only"
 HEARTBEAT = "#pf-heartbeat"      # stderr line prefix of a site-sharded worker's sign of life (swallowed by the launcher)
 MAX_SEQS = 200     # SEQ2PAIR = seq2pair(200), /root/reference/phyloformer/model.py:39
 
@@ -157,12 +159,13 @@ class DirectoryRunner:
 
     def __init__(self, engine, out_dir: str, trees: bool = False, batch: int = 0,
                  io_threads: int = 4, native_io: bool = True, progress=None, modes: Sequence[Analysis] = (),
-                 bme: bool = False, spr: bool = False, bionj: bool = False):
+                 bme: bool = False, spr: bool = False, bionj: bool = False, delta: bool = False):
         # with --trees: <stem>.bme.nwk / .spr.nwk / .bionj.nwk (and .bionj.bme.nwk / .bionj.spr.nwk) as well (treekinds.KINDS)
         self.flags = [flag for flag, on in (("--bionj", bionj), ("--bme", bme), ("--spr", spr)) if on]
         if not trees and self.flags:
             raise ValueError(next(refusals(self.flags, trees)))
         self.kind_groups = switched_on(self.flags)
+        self.delta = delta            # --delta: <stem>.delta.tsv / .delta.phy / .delta.hist.tsv of every launch's distances
         self.engines = list(engine) if isinstance(engine, (list, tuple)) else [engine]
         self.out_dir = out_dir
         self.trees = trees
@@ -177,6 +180,8 @@ class DirectoryRunner:
                       "write_wait_s": 0.0, "shapes": {}, "gpu_streams": len(self.engines)}
         for kinds in self.kind_groups:
             self.stats.update({key: 0.0 if key.endswith("_s") else 0 for key in kinds[0].stats})
+        if delta:
+            self.stats.update({"delta": 0, "delta_s": 0.0})
         self.modes = list(modes)
         for m in self.modes:
             m.bind(self.modes)
@@ -218,6 +223,33 @@ class DirectoryRunner:
             moves += steps
         if kind.stats:
             self.book(**{kind.name: len(group)}, **({f"{kind.name}_steps": moves} if kind.search else {}))
+
+    def delta_arrays(self, engine, preds: np.ndarray):
+        """``--delta`` on the GPU thread, behind the forward: ``Engine.delta`` of the launch's distances (None below four
+        sequences, which have no quartet); books its seconds."""
+        from .delta import BINS, MIN_SEQS, n_of_pairs
+        if n_of_pairs(preds.shape[1]) < MIN_SEQS:
+            return None
+        t0 = time.perf_counter()
+        arrays = engine.delta(preds, bins=BINS)
+        self.book(delta_s=time.perf_counter() - t0)
+        return arrays
+
+    def _write_delta(self, group: list, arrays):
+        """The three files of ``--delta`` of some files of a launch, on a writer thread: the means derived from the
+        integers (``delta.delta_scores``); ``nan`` and 0 quartets counted for a file without a quartet or whose distances
+        are not finite."""
+        from . import delta as D
+        for k, e in enumerate(group):
+            ids = e.ids()
+            if arrays is None or arrays[2][k]:
+                scores, hist = D.no_scores(len(ids)), np.zeros(D.BINS, dtype=np.int64)
+            else:
+                scores, hist = D.delta_scores(arrays[0][k], arrays[1][k], len(ids)), arrays[1][k]
+            self.put(e.path, "delta.tsv", D.delta_tsv(ids, scores))
+            self.put(e.path, "delta.phy", self.phylip(D.pair_vector(scores), ids))
+            self.put(e.path, "delta.hist.tsv", D.hist_tsv(hist))
+        self.book(delta=len(group))
 
     def book(self, **amounts):
         """Add to the run's stats from inside a mode's own engine call (takes the runner's lock)."""
@@ -274,6 +306,10 @@ class DirectoryRunner:
                 tables = device.get(kind.name)
                 submit([(self._write_trees, group[k::cap], preds[k::cap], None if tables is None else tables[k::cap], kind)
                         for k in range(min(cap, len(group)))])
+        if self.delta:
+            arrays = self.delta_arrays(engine, preds)
+            submit([(self._write_delta, group[k::cap], None if arrays is None else tuple(a[k::cap] for a in arrays))
+                    for k in range(min(cap, len(group)))])
         with self._lock:
             self.stats["forward_s"] += dt
             self.stats["launches"] += 1
@@ -491,6 +527,8 @@ class SiteShardedRunner(DirectoryRunner):
     between ranks is an error on all of them, not a hang."""
 
     def __init__(self, engine, group, rank: int, world: int, out_dir: str, heartbeat_s: Optional[float] = None, **kw):
+        if kw.get("delta"):
+            raise ValueError(DELTA_SHARD_SITES)
         super().__init__([engine], out_dir, **kw)
         self.group, self.rank, self.world = group, rank, world
         self.stats["site_sharded_over"] = world
@@ -598,7 +636,8 @@ def summarize(stats: dict, load_s: float = 0.0) -> dict:
             **({k: round(stats[k], 6) for k in ("tbe", "refined_supports", "supports_device", "supports_device_s")}
                if "tbe" in stats else {}),
             **({k: stats[k] for k in ("consensus", "consensus_device")} if "consensus" in stats else {}),
-            **({k: stats[k] for k in ("instability", "transfers_device")} if "instability" in stats else {})}
+            **({k: stats[k] for k in ("instability", "transfers_device")} if "instability" in stats else {}),
+            **({"delta": stats["delta"], "delta_s": round(stats["delta_s"], 6)} if "delta" in stats else {})}
 
 
 def run_multi_device(script: str, argv: List[str], devices: Sequence[int], shard: str = "files") -> Tuple[int, List[dict]]:
