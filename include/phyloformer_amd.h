@@ -157,6 +157,11 @@ const char* pf_last_error(const pf_handle_t* h);
  *                      refused with PF_EINVAL, and "precise" / "recheck_above" are accepted but have no effect (float64
  *                      throughout needs neither).  Site-sharded runs issue n_blocks + 1 float64 all-reduces on one
  *                      stream; batches are chunked under "ws_limit_mb"; pf_profile_get("generic") counts the launches.
+ *   "site_dedup" int   default 1: the column statistics of the default kernels are computed once per DISTINCT alignment
+ *                      column (k_site_classes finds the classes of equal columns at the start of every forward, sharded,
+ *                      weighted, site-table, taxon, placement and tiled ones included) and read for its repeats: no sum
+ *                      changes its order, the results are the same bits.  0 = every site is its own class (the same
+ *                      kernels over the identity map; A/B runs).  pf_site_classes returns the classes.
  * Test / tool switches, not part of the contract:
  *   "colstats_ring" int  0 = k_colstats prefetches its rows through registers instead of the per-wave LDS ring (the
  *                      same bits; A/B and counter runs)
@@ -632,6 +637,13 @@ int pf_boot_counts(int32_t L, int32_t R, uint64_t seed, int32_t r, int32_t* site
 /* The distinct columns of idx host uint8 [N][L] in order of first occurrence: first[0..K) the site where each first
  * stands, count[0..K) how often it occurs; both buffers hold L entries.  Returns K, PF_EINVAL or PF_ENOMEM. */
 int pf_compress_sites(const uint8_t* idx, int32_t N, int32_t L, int32_t* first, int32_t* count);
+/* The classes of equal columns the default kernels' forward finds for itself (k_site_classes, option "site_dedup"): idx
+ * host uint8 [B][N][L] -> srep host int32 [B][L], the smallest site whose column equals column l (l itself where the
+ * column stands first), and ucount host int32 [B], the number of distinct columns.  Bytes are compared as they are (no
+ * residue check).  The forward computes the column statistics of the ucount[b] first sites only and reads them for the
+ * repeats - the distances keep their bits - so ucount / L tells how much of that kernel an alignment saves.  With
+ * "site_dedup" 0, or L beyond the kernel's table (4096 sites), the identity.  Synchronous.  PF_EINVAL for B, N, L < 1. */
+int pf_site_classes(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, int32_t L, int32_t* srep, int32_t* ucount);
 
 /* ---- site-resolved distances: site map, standard errors, site profile (additive to ABI 5) ----
  *

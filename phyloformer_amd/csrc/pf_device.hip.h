@@ -3,7 +3,8 @@
 // Data layout in HBM (all fp32 unless noted), Lloc = sites held by this rank:
 //   x     [B][P][Lloc][64]   residual stream, token-major (pair, site, channel)
 //   qrow  [B][P][Lloc][4]    q' = elu(q)+1 of the row attention of the next block to run
-//   qcol  [B][P][Lloc][4]    q' of the column attention of the current block
+//   qcol  [B][P][Lloc][4]    q' of the column attention of the current block (written at the first site of every class
+//                            of equal columns, read there for the others: srep, k_site_classes)
 //   srow  [B][P][72]         row statistics: S_kv[64] (no v-bias) | S_q[4] | S_k[4]
 //   mrow  [B][P][4][64]      folded row mix  M[h][c], 4 heads (the bias row, equal for every pair, is not stored)
 //   ctx   [B][Lloc][64]      column context ctx[h*16+d], normalised
@@ -468,6 +469,8 @@ struct MainArgs {
                             //                     head logit, the terms of the site mean (no padding, no trash area)
     const float* w;         // [B][Lloc]           site weights (WEIGHTED launches only): what a site counts in the row
                             //                     statistics and in the head's site sum
+    const int* srep;        // [B][Lloc]           first site with the same column (k_site_classes): where k_colstats left
+                            //                     the site's q' (qcol is written for the first site of every class only)
 };
 
 enum { MODE_FIRST = 0, MODE_MID = 1, MODE_LAST = 2, MODE_MID0 = 3, MODE_LAST_FOLD = 4 };
@@ -662,7 +665,9 @@ __global__ void __launch_bounds__(MAIN_THREADS, MAIN_WAVES / 4) k_main(MainArgs 
                 for (int g = 0; g < 8; ++g) px[g] = xp[2 * g];
             }
             pqr = *reinterpret_cast<const f32x4*>(a.qrow + tk * 4);
-            pqc = *reinterpret_cast<const f32x4*>(a.qcol + tk * 4);
+            // (q' of a repeated column stands at the column's first site, same row: one 4-byte read of an L2-resident map
+            // in front of the 16-byte one, both a tile ahead of their use)
+            pqc = *reinterpret_cast<const f32x4*>(a.qcol + (tk + (size_t)(long)(a.srep[(size_t)pb * a.Lloc + ll] - ll)) * 4);
             if (MODE != MODE_FIRST) {
                 // (h through an opaque copy: hipcc otherwise hoists the per-lane 64-bit base a.ctx + 4 h out of the tile
                 // loop, where it does not find a register pair for it - round 3's build kept it in scratch and
@@ -1340,6 +1345,91 @@ __global__ void k_outsum(const float* outpart, float* out, int npairs, int npart
     out[pr] = acc * (wst ? wst[(size_t)(pr / P) * 4 + 1] : inv_L_total);
 }
 
+// ---- site classes ------------------------------------------------------------------------
+// Nothing in the network depends on a site's position: two equal columns of an alignment carry
+// equal tokens through every block, and the column statistics of a site - a sum over pairs in a tree fixed by (P, L) -
+// come out the same to the bit.  k_site_classes finds the classes of equal columns of every alignment of a run, once per
+// forward; k_colstats then walks the first site of every class only, k_colfin and k_main read a repeated site's
+// partials and q' at its class's first site.  No sum changes its order: the distances keep their bits.
+//   srep[b][l]   the smallest site l' <= l whose column equals column l
+//   ulist[b][k]  the sites with srep == l, ascending (entries from ucount[b] on are not written)
+//   ucount[b]    how many there are (>= 1)
+// One workgroup per alignment: a 32-bit hash per column into LDS, then every site looks through the hashes of the sites
+// in front of it, four per LDS read, for the first equal one - LDS only - and all sites compare their column's bytes
+// with that candidate's at once (the hash only pre-filters: compared inside the search, a wave would walk a column once
+// per lane that found its candidate at another step).  Equal hashes over different bytes send the site on through the
+// remaining hashes, comparing bytes at every further match.  A ballot scan over the "first of its class" flags lays
+// out ulist.  dedup = 0, or more sites than the hash table holds: the identity map (srep[l] = ulist[l] = l,
+// ucount = Lloc) - the same kernels downstream, every site its own class.
+struct SiteClassArgs {
+    const uint8_t* idx;      // [B][N][Lloc]
+    int* srep;               // [B][Lloc]  out
+    int* ulist;              // [B][Lloc]  out
+    int* ucount;             // [B]        out
+    int N, Lloc, dedup;
+};
+constexpr int SC_THREADS = 1024, SC_MAX_SITES = 4096;
+__global__ void __launch_bounds__(SC_THREADS) k_site_classes(SiteClassArgs a) {
+    __shared__ __attribute__((aligned(16))) uint32_t hsh[SC_MAX_SITES];
+    __shared__ int wsum[SC_THREADS / 64];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint8_t* ib = a.idx + (size_t)b * a.N * a.Lloc;
+    int* const srep = a.srep + (size_t)b * a.Lloc;
+    int* const ulist = a.ulist + (size_t)b * a.Lloc;
+    const bool dedup = a.dedup && a.Lloc <= SC_MAX_SITES;
+    // are columns c and l the same bytes?  (no early exit: the loads of a column do not wait for one another)
+    auto same_column = [&](int c, int l) {
+        unsigned diff = 0;
+#pragma unroll 8
+        for (int n = 0; n < a.N; ++n) diff |= (unsigned)(ib[(size_t)n * a.Lloc + c] ^ ib[(size_t)n * a.Lloc + l]);
+        return diff == 0;
+    };
+    if (dedup) {
+        for (int l = tid; l < a.Lloc; l += SC_THREADS) {
+            uint32_t hv = 0x811C9DC5u;                         // FNV-1a over the column's bytes
+#pragma unroll 8
+            for (int n = 0; n < a.N; ++n) hv = (hv ^ ib[(size_t)n * a.Lloc + l]) * 0x01000193u;
+            hsh[l] = hv;
+        }
+        __syncthreads();
+    }
+    int base = 0;                                              // distinct columns in front of this round's sites
+    for (int l0 = 0; l0 < a.Lloc; l0 += SC_THREADS) {          // (uniform bounds: every thread joins every barrier)
+        const int l = l0 + tid;
+        int rep = l;
+        if (dedup && l < a.Lloc) {
+            const uint32_t mine = hsh[l];
+            // sites in front of l in ascending order, so the first equal column found is the smallest; the last vector
+            // may reach past l (inside the table: l < SC_MAX_SITES, a multiple of 4), those entries are skipped
+            int cand = l;
+            for (int c0 = 0; c0 < l && cand == l; c0 += 4) {
+                const u32x4 v = *reinterpret_cast<const u32x4*>(hsh + c0);
+#pragma unroll
+                for (int i = 3; i >= 0; --i)
+                    if (v[i] == mine && c0 + i < l) cand = c0 + i;
+            }
+            if (cand < l) {
+                if (same_column(cand, l)) rep = cand;
+                else
+                    for (int c = cand + 1; c < l && rep == l; ++c)
+                        if (hsh[c] == mine && same_column(c, l)) rep = c;
+            }
+        }
+        const bool first = l < a.Lloc && rep == l;
+        if (l < a.Lloc) srep[l] = rep;
+        const unsigned long long m = __ballot(first);
+        if (lane == 0) wsum[wave] = __popcll(m);
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < SC_THREADS / 64; ++w) { const int n = wsum[w]; total += n; if (w < wave) before += n; }
+        if (first) ulist[base + before + __popcll(m & ((1ull << lane) - 1ull))] = l;
+        base += total;
+        __syncthreads();                                       // (wsum is rewritten in the next round)
+    }
+    if (tid == 0) a.ucount[b] = base;
+}
+
 // ---- column statistics -------------------------------------------------------------------
 struct ColStatsArgs {
     const float* x;      // [B][P][Lloc][64]   (unused by the block-0 variant, which forms x0 from `table`)
@@ -1363,12 +1453,15 @@ struct ColStatsArgs {
     const int16_t* pair_i;   // [P]
     const int16_t* pair_j;
     int N;
+    // the sites the blocks walk (k_site_classes): the first site of every class of equal columns, ascending
+    const int* ulist;        // [B][Lloc]
+    const int* ucount;       // [B]
 };
 constexpr int CPART = 4 * 64 + 8;
 
-// Block = (alignment b, chunk of 32 sites, pair group g); wave w owns sites 8w .. 8w+7 of the chunk and
-// all four waves walk the group's pairs together, so the block reads 8 KB of contiguous x per pair and
-// shares the per-pair row-attention matrix.  Lanes: site = lane >> 3, channels 8*(lane & 7) .. +7 (two
+// Block = (alignment b, chunk of 32 distinct sites, pair group g); wave w owns sites 8w .. 8w+7 of the chunk and
+// all four waves walk the group's pairs together, so the block reads 8 KB of x per pair (contiguous where the
+// sites are) and shares the per-pair row-attention matrix.  Lanes: site = lane >> 3, channels 8*(lane & 7) .. +7 (two
 // 16-byte loads per lane).  Applies the row attention on the fly (it is not materialised in HBM), then
 // LayerNorm -> q', k' -> Z~ += k' x~.  Eight lanes per token: three steps per cross-lane reduction and,
 // after the transposing butterfly, exactly one projection per lane - 24 VALU instructions per token.
@@ -1401,6 +1494,18 @@ __global__ void __launch_bounds__(256, PF_CS_WAVES) k_colstats(ColStatsArgs a) {
     // load (idx byte) instead of two (pair table, then idx byte) - the second level did not fit one iteration
     constexpr int PIJ_CAP = 640;
     __shared__ __attribute__((aligned(16))) float lds_all[LDS_MST + LDS_RING + LDS_EMB + (EMBED ? PIJ_CAP : 0)];
+    int bid = blockIdx.x;
+    int run = 0;
+    if (a.fine) { run = bid % a.S; bid /= a.S; }
+    const int g = bid % a.G; bid /= a.G;
+    const int chunk = bid % a.nchunks;
+    const int b = bid / a.nchunks;
+    // The block's sites are entries chunk * 32 .. + 31 of the alignment's list of DISTINCT columns: a repeated column
+    // would read the same bytes and leave the same partial and q' as its first occurrence (nothing here depends on a
+    // site's position), so k_colfin and k_main read those instead.  A chunk past the list has nothing to do.
+    const int nu = a.ucount[b];
+    if (chunk * 32 >= nu) return;
+    const int* const ul = a.ulist + (size_t)b * a.Lloc;
     float* const mst = lds_all;
     float* const xring = lds_all + LDS_MST;
     float* const emb = lds_all + LDS_MST + LDS_RING;
@@ -1441,15 +1546,11 @@ __global__ void __launch_bounds__(256, PF_CS_WAVES) k_colstats(ColStatsArgs a) {
     // reads per lane and pair (the LDS pipe is what this kernel is closest to)
     const f32x4 br0 = *reinterpret_cast<const f32x4*>(a.brow + 8 * cl), br1 = *reinterpret_cast<const f32x4*>(a.brow + 8 * cl + 4);
     const bool up1 = (cl & 2) != 0, up0 = (cl & 1) != 0;
-    int bid = blockIdx.x;
-    int run = 0;
-    if (a.fine) { run = bid % a.S; bid /= a.S; }
-    const int g = bid % a.G; bid /= a.G;
-    const int chunk = bid % a.nchunks;
-    const int b = bid / a.nchunks;
-    const int l = chunk * 32 + wave * 8 + ts;
-    const bool lvalid = l < a.Lloc;
-    const int lcl = lvalid ? l : a.Lloc - 1;
+    // (slots past the list clamp onto its last site: finite values, masked)
+    const int us = chunk * 32 + wave * 8 + ts;
+    const bool lvalid = us < nu;
+    const int l = ul[min(us, nu - 1)];
+    const int lcl = l;
     const int gp0 = g * per, gp1 = min(a.P, gp0 + per);
     const int p0 = a.fine ? gp0 + run * a.sub : gp0, p1 = a.fine ? min(gp1, p0 + a.sub) : gp1;
     if (p0 >= p1) return;       // a run past the end of the last group (k_colfin does not read its slot)
@@ -1496,7 +1597,7 @@ __global__ void __launch_bounds__(256, PF_CS_WAVES) k_colstats(ColStatsArgs a) {
     // (destination = slot base + lane * 16, the layout each lane reads back), and q' as one dword per lane - lane j < 32
     // fetches q'[site j >> 2][j & 3] (lanes 32..63 repeat them into the spare words) -> q'[8 sites][4] contiguous.
     float* const wring = xring + (RING ? wave * RING * CS_SLOT : 0);
-    const int lq = min(chunk * 32 + wave * 8 + ((lane & 31) >> 2), a.Lloc - 1);      // the site whose q' this lane fetches
+    const int lq = ul[min(chunk * 32 + wave * 8 + ((lane & 31) >> 2), nu - 1)];      // the site whose q' this lane fetches
     auto issue = [&](int p, size_t lane_off) {
         const int pc = min(p, a.P - 1);                       // (past the end: a valid pair nobody uses)
         const size_t row = ((size_t)b * a.P + pc) * a.Lloc;
@@ -1730,6 +1831,7 @@ struct ColFinArgs {
     int B, Lloc, G;
     float P;
     int npairs, sub, S, fine;   // the association tree of ColStatsArgs (fine = 1: part[b][g][s][l], folded here)
+    const int* srep;     // [B][Lloc] first site with the same column: the site whose partials k_colstats wrote
 };
 
 constexpr int COLFIN_THREADS = 320;      // >= CPART: one value per thread
@@ -1737,7 +1839,7 @@ __global__ void __launch_bounds__(COLFIN_THREADS) k_colfin(ColFinArgs a) {
     __shared__ float zs[CPART];
     __shared__ float dp[4][64];
     const int site = blockIdx.x;  // b * Lloc + l
-    const int b = site / a.Lloc, l = site - b * a.Lloc;
+    const int b = site / a.Lloc, l = a.srep[site];      // (a repeated column reads its first occurrence's partials)
     const size_t gs = (size_t)a.Lloc * CPART;
     const int per = (a.npairs + a.G - 1) / a.G;
     const int i = threadIdx.x;

@@ -7,12 +7,14 @@
 //
 // Launch sequence for one batch chunk (nb = n_blocks); a chunk of >= 2 alignments runs it twice, for its two
 // halves, on the two streams (schedule(), driven by forward_chunk and pf_forward_shards_emulated):
+//   k_site_classes                        classes of equal alignment columns: srep, ulist, ucount (option "site_dedup")
 //   k_embed                               row statistics of block 0 and q' by table lookup (x0 is not written)
 //   for k in 0..nb-1:
 //       [k_rowsum, all-reduce srow]       site-sharded runs only
 //       k_rowfin(k)      per-tile row statistics -> row-mix matrices / fragments of every pair
-//       k_colstats(k)    x (block 0: the embedding table), qrow, mrow -> qcol, column partials (groups or runs)
-//       k_colfin(k)      partials -> ctx
+//       k_colstats(k)    x (block 0: the embedding table), qrow, mrow -> qcol, column partials (groups or runs),
+//                        both for the first site of every class only
+//       k_colfin(k)      partials (of the site's class) -> ctx, for every site
 //       k_main<MID0|MID|LAST_FOLD>(k)     row + column attention applied, FFN, next block's row statistics / head
 //   k_outsum                              per-tile head sums -> distances
 //   [all-reduce out]                      site-sharded runs only
@@ -151,9 +153,9 @@ struct BlockDev {
 struct ProfSlot { int kid; hipEvent_t a, b; };
 const char* const KNAMES[] = {"embed", "rowfin", "colstats", "colfin", "main", "allreduce",
                               "mha_qkv", "mha_attn", "mha_out", "precise", "generic", "resample", "gather", "site_moments", "gather_taxa", "loo_stats",
-                              "weight_sums", "place_stats", "tile_combine", "bme_pairs"};
+                              "weight_sums", "place_stats", "tile_combine", "bme_pairs", "site_classes"};
 enum { K_EMBED = 0, K_ROWFIN, K_COLSTATS, K_COLFIN, K_MAIN, K_ALLREDUCE, K_MHA_QKV, K_MHA_ATTN, K_MHA_OUT, K_PRECISE, K_GENERIC,
-       K_RESAMPLE, K_GATHER, K_SITE_MOMENTS, K_GATHER_TAXA, K_LOO_STATS, K_WEIGHT_SUMS, K_PLACE_STATS, K_TILE_COMBINE, K_BME_PAIRS, K_COUNT };
+       K_RESAMPLE, K_GATHER, K_SITE_MOMENTS, K_GATHER_TAXA, K_LOO_STATS, K_WEIGHT_SUMS, K_PLACE_STATS, K_TILE_COMBINE, K_BME_PAIRS, K_SITE_CLASSES, K_COUNT };
 
 // what the embed and head kernels (pfg's, for both float64 paths) read: C = 64 (precise) or Ep (generic)
 struct F64Ends {
@@ -226,6 +228,7 @@ struct pf_handle {
     int colstats_fine = -1;       // option "colstats_fine": k_colstats blocks per run (1) / per group (0) / by batch (-1)
     bool colstats_ring = true;    // option "colstats_ring": x / q' of the next pairs through an LDS ring (1) or registers (0: cross-check)
     bool materialize_x0 = false;  // option "materialize_x0": k_embed writes x0 and block 0 reads it (round-1 path)
+    bool site_dedup = true;       // option "site_dedup": k_colstats walks every distinct column once (0: every site, the identity map)
     float* first_consts = nullptr;  // consts for k_main<FIRST> (only bqk used)
     float* first_img = nullptr;     // LDS image for k_main<FIRST> (only the row-statistics tail used)
     std::vector<BlockDev> blk;
@@ -565,11 +568,12 @@ TilePlan tile_plan(const pf_handle* h, int P, int Lloc) { return tile_plan_core(
 
 struct Workspace {
     float *x, *qrow, *qcol, *srow, *mrow, *part, *ctx, *mfrag, *spart, *outpart, *rq;
+    int *srep, *ulist, *ucount;   // k_site_classes: [B][Lloc], [B][Lloc], [B]
     int G;             // pair groups of k_colstats
     int sub, S, fine;  // runs of `sub` pairs, S per group; fine: one block per run instead of per group
     int nparts() const { return fine ? G * S : G; }
 };
-constexpr int WS_BUFS = 11;
+constexpr int WS_BUFS = 12;
 
 // The column-statistics plan into w and the buffer offsets of a workspace for B alignments of P pairs x Lloc sites.
 // An empty shard (Lloc = 0) is laid out as one site: it launches nothing and only zero-fills srow.
@@ -592,9 +596,10 @@ size_t workspace_bytes(const pf_handle* h, int B, int P, int Lloc, Workspace* w,
     off[8] = o; o = align_up(o + (size_t)B * slots * SROW * 4, 256);   // spart: row statistics per tile part
     off[9] = o; o = align_up(o + (size_t)B * slots * 4, 256);          // outpart: head sums per tile part
     off[10] = o; o = align_up(o + (size_t)B * P * 4 * 4, 256);         // rq: L / S_q per pair and head
+    off[11] = o; o = align_up(o + ((size_t)B * Lloc * 2 + B) * sizeof(int), 256);   // srep | ulist | ucount
     return o;
 }
-void carve_workspace(char* ws, const size_t off[WS_BUFS], Workspace* w) {
+void carve_workspace(char* ws, const size_t off[WS_BUFS], Workspace* w, int B, int Lloc) {
     w->x = (float*)(ws + off[0]); w->qrow = (float*)(ws + off[1]);
     w->qcol = (float*)(ws + off[2]); w->srow = (float*)(ws + off[3]);
     w->mrow = (float*)(ws + off[4]); w->part = (float*)(ws + off[5]);
@@ -602,6 +607,8 @@ void carve_workspace(char* ws, const size_t off[WS_BUFS], Workspace* w) {
     w->mfrag = (float*)(ws + off[7]);
     w->spart = (float*)(ws + off[8]); w->outpart = (float*)(ws + off[9]);
     w->rq = (float*)(ws + off[10]);
+    const size_t nsite = (size_t)B * std::max(Lloc, 1);                // (the shape workspace_bytes laid out)
+    w->srep = (int*)(ws + off[11]); w->ulist = w->srep + nsite; w->ucount = w->ulist + nsite;
 }
 
 int ensure_workspace(pf_handle* h, int B, int P, int Lloc, Workspace* w, bool second = false) {
@@ -609,7 +616,7 @@ int ensure_workspace(pf_handle* h, int B, int P, int Lloc, Workspace* w, bool se
     const size_t need = workspace_bytes(h, B, P, Lloc, w, off);
     Buffer<char>& ws = second ? h->ws2 : h->ws;
     if (const int rc = ws.reserve(h, need)) return rc;
-    carve_workspace(ws, off, w);
+    carve_workspace(ws, off, w, B, Lloc);
     return PF_OK;
 }
 
@@ -716,6 +723,7 @@ MainArgs main_args(pf_handle* h, const ShardRun& r) {
     m.ablate = h->ablate;
     m.prof = h->phase_prof_last ? nullptr : h->phase_prof;
     m.w = r.d_w;
+    m.srep = r.w.srep;
     return m;
 }
 
@@ -723,6 +731,17 @@ MainArgs main_args(pf_handle* h, const ShardRun& r) {
 // requested; the MFMA cross-check kernels and single-block models keep the materialised x0.
 bool x0_on_the_fly(const pf_handle* h) {
     return !h->materialize_x0 && !h->embed_mfma && h->n_blocks > 1;
+}
+
+// The classes of equal columns of the run's alignments (k_site_classes), in front of everything that reads them:
+// once per forward - the indices change from call to call.  Option site_dedup = 0: the identity map, same kernels.
+int launch_site_classes(pf_handle* h, const uint8_t* d_idx, int B, int N, int Lloc, int* srep, int* ulist, int* ucount) {
+    if (!Lloc) return PF_OK;
+    SiteClassArgs a{d_idx, srep, ulist, ucount, N, Lloc, h->site_dedup ? 1 : 0};
+    ProfScope ps(h, K_SITE_CLASSES);
+    hipLaunchKernelGGL(k_site_classes, dim3(B), dim3(SC_THREADS), 0, h->cur, a);
+    HIPCHK(h, hipGetLastError());
+    return PF_OK;
 }
 
 // embedding + pair expansion + row statistics of block 0
@@ -819,7 +838,7 @@ int phase_block(pf_handle* h, const ShardRun& r, int k, RowStats rs) {
     }
     {
         ColStatsArgs a{w.x, w.qrow, w.mrow, w.qcol, w.part, d.col_wqk, d.col_bqk, d.row_bo, B, P, Lloc, w.G, (Lloc + 31) / 32,
-                       w.sub, w.S, w.fine, h->table, r.d_idx, h->pair_i, h->pair_j, r.N};
+                       w.sub, w.S, w.fine, h->table, r.d_idx, h->pair_i, h->pair_j, r.N, w.ulist, w.ucount};
         ProfScope ps(h, K_COLSTATS);
         const unsigned nblk = (unsigned)(B * a.nchunks * w.nparts());
         if (k == 0 && x0_on_the_fly(h))
@@ -831,7 +850,7 @@ int phase_block(pf_handle* h, const ShardRun& r, int k, RowStats rs) {
         HIPCHK(h, hipGetLastError());
     }
     {
-        ColFinArgs a{w.part, w.ctx, d.col_wvT, d.col_bv, B, Lloc, w.G, (float)P, P, w.sub, w.S, w.fine};
+        ColFinArgs a{w.part, w.ctx, d.col_wvT, d.col_bv, B, Lloc, w.G, (float)P, P, w.sub, w.S, w.fine, w.srep};
         ProfScope ps(h, K_COLFIN);
         hipLaunchKernelGGL(k_colfin, dim3(B * Lloc), dim3(COLFIN_THREADS), 0, h->cur, a);
         HIPCHK(h, hipGetLastError());
@@ -914,6 +933,7 @@ int schedule(pf_handle* h, ShardRun* runs, size_t nruns, Reduce reduce) {
     int rc;
     for (ShardRun* r = runs; r != end; ++r) {
         h->cur = r->stream;
+        if ((rc = launch_site_classes(h, r->d_idx, r->B, r->N, r->Lloc, r->w.srep, r->w.ulist, r->w.ucount))) return rc;
         if ((rc = phase_first(h, *r))) return rc;
         r->rs = first_stats(h, *r);
     }
@@ -2598,6 +2618,7 @@ int pf_set_option(pf_handle_t* h, const char* key, int64_t value) {
     else if (k == "head_fold") h->head_fold = value != 0;
     else if (k == "force_rccl") h->force_rccl = value != 0;
     else if (k == "colstats_ring") h->colstats_ring = value != 0;
+    else if (k == "site_dedup") h->site_dedup = value != 0;
     else if (k == "precise") h->precise = value < 0 ? -1 : (value != 0);
     else if (k == "recheck_above") h->recheck_above = value > 0 ? (double)value : 0.0;
     else if (k == "precise_ffn_valu") h->precise_ffn_valu = value != 0;
@@ -2927,6 +2948,26 @@ int pf_compress_sites(const uint8_t* idx, int32_t N, int32_t L, int32_t* first, 
     return pfweights::compress_sites(idx, N, L, first, count, slot.data());
 }
 
+int pf_site_classes(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, int32_t L, int32_t* srep, int32_t* ucount) {
+    if (!h) return PF_EINVAL;
+    if (!idx || !srep || !ucount) return fail(h, PF_EINVAL, "null buffer");
+    if (B < 1 || N < 1 || L < 1) return fail(h, PF_EINVAL, "bad dimensions B=%d N=%d L=%d", B, N, L);
+    size_t nidx = 0;
+    if (!mul_size((size_t)B, (size_t)N, (size_t)L, &nidx)) return fail(h, PF_EINVAL, "B x N x L overflows");
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t nsite = (size_t)B * L;
+    int rc = h->d_idx.reserve(h, nidx);
+    if (rc || (rc = h->d_map.reserve(h, (2 * nsite + B) * sizeof(int32_t)))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->d_idx, idx, nidx, hipMemcpyHostToDevice, h->stream));
+    int32_t* d = h->d_map;
+    h->cur = h->stream;
+    if ((rc = launch_site_classes(h, h->d_idx, B, N, L, d, d + nsite, d + 2 * nsite))) return rc;
+    HIPCHK(h, hipMemcpyAsync(srep, d, nsite * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(ucount, d + 2 * nsite, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return PF_OK;
+}
+
 int pf_forward_site_map(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, int32_t L, float* out, float* map) {
     if (!h) return PF_EINVAL;
     if (!map) return fail(h, PF_EINVAL, "null buffer");
@@ -3219,7 +3260,7 @@ int pf_forward_shards_emulated(pf_handle_t* h, const uint8_t* idx, int32_t B, in
         char* ws = (char*)stage.alloc(workspace_bytes(h, B, P, r.Lloc, &r.w, off));
         r.d_out = (float*)stage.alloc((size_t)B * P * sizeof(float));
         if (!ws || !r.d_out) return fail(h, PF_ENOMEM, "shard workspace allocation failed");
-        carve_workspace(ws, off, &r.w);
+        carve_workspace(ws, off, &r.w, B, r.Lloc);
         runs.push_back(r);
     }
     // the "all-reduced" buffer every emulated rank reads

@@ -180,6 +180,7 @@ SIGNATURES = {
     "pf_padded_sites": (C.c_int, [C.c_int32, C.c_int32]),
     "pf_boot_counts": (C.c_int, [C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p]),
     "pf_compress_sites": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "pf_site_classes": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
 }
 
 # Additions to ABI 5 that a library built before them lacks: bound when present; a call through a missing one raises
@@ -197,7 +198,7 @@ CALL_TIME_SYMBOLS = frozenset({"pf_forward_site_map", "pf_forward_site_map_devic
                                "pf_join_consensus_device", "pf_join_consensus_host", "pf_bionj_joins",
                                "pf_bionj_joins_device", "pf_bionj_joins_host", "pf_bionj_newick_n", "pf_join_transfers",
                                "pf_join_transfers_device", "pf_join_transfers_host", "pf_delta", "pf_delta_device",
-                               "pf_delta_host"})
+                               "pf_delta_host", "pf_site_classes"})
 
 _lib: Optional[C.CDLL] = None
 
@@ -732,6 +733,19 @@ class Engine:
         if arr.shape != shape or arr.dtype.kind not in "fiu":
             raise ValueError(f"{what} must be a real array of shape {list(shape)}, got {arr.dtype} {list(arr.shape)}")
         return np.ascontiguousarray(arr, dtype=np.float32)
+
+    def site_classes(self, idx: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """The classes of equal alignment columns as the forward's own kernel finds them (``pf_site_classes``):
+        ``uint8[B, N, L]`` → ``(srep int32[B, L], ucount int32[B])`` (``[N, L]`` → ``([L], int)``).  ``srep[b, l]`` is the
+        smallest site whose column equals column ``l``; ``ucount[b]`` counts the distinct columns, the sites whose
+        column statistics the forward computes (option ``site_dedup``; with 0 the identity)."""
+        fn = self._optional("pf_site_classes")
+        idx, single = self._sources(idx, refuse_single=False)
+        B, N, L = idx.shape
+        srep = np.empty((B, L), dtype=np.int32)
+        ucount = np.empty(B, dtype=np.int32)
+        self._check(fn(self._h, idx.ctypes.data, B, N, L, srep.ctypes.data, ucount.ctypes.data))
+        return (srep[0], int(ucount[0])) if single else (srep, ucount)
 
     def forward_weighted(self, idx: np.ndarray, weights: np.ndarray) -> np.ndarray:
         """Distances of alignments whose site ``l`` counts ``weights[..., l]`` times (``pf_forward_weighted``):
