@@ -162,6 +162,14 @@ const char* pf_last_error(const pf_handle_t* h);
  *                      weighted, site-table, taxon, placement and tiled ones included) and read for its repeats: no sum
  *                      changes its order, the results are the same bits.  0 = every site is its own class (the same
  *                      kernels over the identity map; A/B runs).  pf_site_classes returns the classes.
+ *   "main_dedup" int   default 1: an alignment with enough repeated columns (k_site_classes; the share is measured,
+ *                      DESIGN.md section 9) runs every block's row apply, column apply and feed-forward once per DISTINCT
+ *                      column: a compact k_main launch over the first sites, then the row statistics (the head: its site
+ *                      sums) over every site in place, so no sum changes its order - the results are the same bits.  The
+ *                      route is decided per alignment on the device, from the alignment's own columns.  0 = every
+ *                      alignment through the fused launch; 2 = every alignment through the split route, even one without a
+ *                      repeat (tests).  Site-sharded and emulated ranks route from the classes of their own site range.
+ *                      Weighted and site-map forwards, "embed_mfma" and "materialize_x0" stay on the fused launch.
  * Test / tool switches, not part of the contract:
  *   "colstats_ring" int  0 = k_colstats prefetches its rows through registers instead of the per-wave LDS ring (the
  *                      same bits; A/B and counter runs)

@@ -471,9 +471,25 @@ struct MainArgs {
                             //                     statistics and in the head's site sum
     const int* srep;        // [B][Lloc]           first site with the same column (k_site_classes): where k_colstats left
                             //                     the site's q' (qcol is written for the first site of every class only)
+    // option "main_dedup" (k_main_plan, ROUTE_LIST / ROUTE_COMPACT launches): the launch's alignments and compact tiles
+    const int* acount;      // [1]                 how many alignments the launch covers
+    const int* alist;       // [acount]            which, ascending
+    const int* cpre;        // [acount + 1]        ROUTE_COMPACT: compact tiles in front of alist[i]
+    const int* ulist;       // [B][Lloc]           ROUTE_COMPACT: the first sites of every alignment (k_site_classes)
+    const int* ucount;      // [B]                 and how many there are
+    float* term;            // [B][P][Lloc]        ROUTE_COMPACT, last block: softplus of the head logit, at first sites
 };
 
-enum { MODE_FIRST = 0, MODE_MID = 1, MODE_LAST = 2, MODE_MID0 = 3, MODE_LAST_FOLD = 4 };
+enum { MODE_FIRST = 0, MODE_MID = 1, MODE_LAST = 2, MODE_MID0 = 3, MODE_LAST_FOLD = 4, MODE_STATS = 5 };
+// Which alignments and tokens a launch walks (option "main_dedup"):
+//   ROUTE_ALL      every alignment of the run, every token (the only route until main_dedup)
+//   ROUTE_LIST     the same tiling over the alignments of a list: the fused launch over the alignments that stay on it,
+//                  MODE_STATS over those on the split route
+//   ROUTE_COMPACT  the compacted tokens (row p, u < ucount[b]) of the split-route alignments, at site ulist[b][u]
+//                  (pf_layout.h, compact_tile): load / gather, both applies, the FFN and the store of x (last block: of
+//                  the head's term); no statistics phase, no head sum - those see every site in place (MODE_STATS,
+//                  k_head_parts)
+enum { ROUTE_ALL = 0, ROUTE_LIST = 1, ROUTE_COMPACT = 2 };
 
 // Two tilings of an alignment's P x L tokens into work items of 32 tokens share the kernel:
 //   row tiling  (flat = 0): every pair row is cut into ceil(L / 32) tiles of its own; the last tile of a row is
@@ -486,18 +502,53 @@ enum { MODE_FIRST = 0, MODE_MID = 1, MODE_LAST = 2, MODE_MID0 = 3, MODE_LAST_FOL
 // Partials: a tile part owns slot (kt + its row) in flat tiling, kt in row tiling; the parts of row p are the
 // consecutive slots part_range() names, summed in slot order by k_rowfin / k_rowsum / k_outsum.  The tiling is
 // per alignment, a function of (P, L) only: an alignment gets the same bits wherever it sits in a batch.
-struct TilePos { int b, kt, r0, l0; };   // alignment, tile inside it, row of its first token, site of that token
-template <bool FLAT>
+// (listed routes: bi = the alignment's place in the list; ROUTE_COMPACT: l0 = compacted index of the first token, K, nt =
+// the alignment's distinct columns and compact tiles)
+struct TilePos { int b, kt, r0, l0, bi, K, nt; };
+__device__ __forceinline__ void compact_enter(const MainArgs& a, TilePos& q) {
+    q.b = a.alist[q.bi];
+    q.K = a.ucount[q.b];
+    q.nt = a.cpre[q.bi + 1] - a.cpre[q.bi];
+}
+template <bool FLAT, int ROUTE>
 __device__ __forceinline__ TilePos tile_pos(const MainArgs& a, int task, int ntiles) {
     TilePos q;
+    if (ROUTE == ROUTE_COMPACT) {
+        int lo = 0, hi = *a.acount - 1;              // the last alignment whose tiles start at or in front of `task`
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (a.cpre[mid] <= task) lo = mid; else hi = mid - 1;
+        }
+        q.bi = lo;
+        compact_enter(a, q);
+        q.kt = task - a.cpre[lo];
+        const CompactTile c = compact_tile(a.P, q.K, q.kt);
+        q.r0 = c.r0; q.l0 = c.u0;
+        return q;
+    }
+    if (ROUTE == ROUTE_LIST) {
+        q.bi = task / a.nt_aln;
+        q.kt = task - q.bi * a.nt_aln;
+        q.b = a.alist[q.bi];
+    } else {
     q.b = task / a.nt_aln;
     q.kt = task - q.b * a.nt_aln;
+    }
     if (FLAT) { const int tok0 = q.kt * 32; q.r0 = tok0 / a.Lloc; q.l0 = tok0 - q.r0 * a.Lloc; }
     else { q.r0 = q.kt / ntiles; q.l0 = (q.kt - q.r0 * ntiles) * 32; }
     return q;
 }
-template <bool FLAT>
+template <bool FLAT, int ROUTE>
 __device__ __forceinline__ TilePos tile_next(const MainArgs& a, TilePos q) {
+    if (ROUTE == ROUTE_COMPACT) {
+        // (behind the launch's last tile there is no alignment to enter: the list's last one again, the tile is not used)
+        if (++q.kt == q.nt) { q.bi = min(q.bi + 1, *a.acount - 1); compact_enter(a, q); q.kt = 0; q.r0 = 0; q.l0 = 0; return q; }
+        compact_next(q.K, &q.r0, &q.l0);
+        return q;
+    }
+    if (ROUTE == ROUTE_LIST) {
+        if (++q.kt == a.nt_aln) { q.bi = min(q.bi + 1, *a.acount - 1); q.b = a.alist[q.bi]; q.kt = 0; q.r0 = 0; q.l0 = 0; return q; }
+    } else
     if (++q.kt == a.nt_aln) { q.b++; q.kt = 0; q.r0 = 0; q.l0 = 0; return q; }
     q.l0 += 32;
     if (q.l0 >= a.Lloc) { q.l0 = FLAT ? q.l0 - a.Lloc : 0; q.r0++; }
@@ -510,10 +561,23 @@ __device__ __forceinline__ TilePos tile_next(const MainArgs& a, TilePos q) {
 // are consecutive in both tilings), nvalid (lanes holding a token; < 32 only in a row's / an alignment's last
 // tile) and wrap (flat tiling: lanes from `wrap` on belong to row r0 + 1; 32 = none).  Per lane that leaves
 // one min for the clamped token offset and a compare + select for the site.
-struct LanePos { size_t tok0; int toff, l, nvalid, wrap; bool valid, in_r1; };
-template <bool FLAT>
+// ROUTE_COMPACT: the lane's token is compacted token l0 + toff of the tile's row(s), at the site ulist names - one
+// 4-byte read of an L2-resident list; tok0 is not used (the tokens of a tile are not consecutive in memory).
+struct LanePos { size_t tok0, tok; int toff, l, nvalid, wrap; bool valid, in_r1; };
+template <bool FLAT, int ROUTE>
 __device__ __forceinline__ LanePos lane_pos(const MainArgs& a, const TilePos& q, int t) {
     LanePos o;
+    if (ROUTE == ROUTE_COMPACT) {
+        o.nvalid = compact_nvalid(a.P, q.K, q.kt);
+        o.wrap = compact_wrap(a.P, q.K, q.r0, q.l0);
+        o.valid = t < o.nvalid;
+        o.toff = min(t, o.nvalid - 1);
+        o.in_r1 = o.toff >= o.wrap;
+        o.l = a.ulist[(size_t)q.b * a.Lloc + (q.l0 + o.toff - (o.in_r1 ? q.K : 0))];
+        o.tok0 = 0;
+        o.tok = ((size_t)q.b * a.P + q.r0 + (o.in_r1 ? 1 : 0)) * a.Lloc + o.l;
+        return o;
+    }
     o.tok0 = ((size_t)q.b * a.P + q.r0) * a.Lloc + q.l0;
     const int left = FLAT ? a.P * a.Lloc - q.kt * 32 : a.Lloc - q.l0;      // tokens from the tile's first one on
     o.nvalid = min(32, left);
@@ -522,6 +586,7 @@ __device__ __forceinline__ LanePos lane_pos(const MainArgs& a, const TilePos& q,
     o.toff = min(t, o.nvalid - 1);
     o.in_r1 = o.toff >= o.wrap;
     o.l = q.l0 + o.toff - (o.in_r1 ? a.Lloc : 0);
+    o.tok = o.tok0 + o.toff;
     return o;
 }
 // Slots [first, first + count) of the partial buffers that hold row p's (pr = b * P + p) parts.
@@ -572,16 +637,29 @@ __device__ __forceinline__ void image_to_lds(const frag_t* src, unsigned char* s
 //               before the part sum.  One 4-byte read per token; everything else - the token's own x, q', the column
 //               attention, the FFN - does not know the weight.  A template parameter for the same reason as SITEMAP;
 //               weight 1 multiplies exactly, so unit weights give the unweighted launch's bits
-template <int MODE, bool FLAT, bool SITEMAP = false, bool WEIGHTED = false>
+//   MODE_STATS: the statistics half of MODE_MID for the split route (option "main_dedup"): x = what the compact launch
+//               left at the first site of the token's class (a.srep), then the statistics phase as MODE_MID runs it,
+//               over the original tiling - q' of every site, the same spart slots, the same lanes: the same bits.
+//               Under the debug taps (store_x_last) it also copies x to the repeated sites
+//   ROUTE     : which alignments and tokens the launch walks (above); ROUTE_ALL instantiations are what they were
+template <int MODE, bool FLAT, bool SITEMAP = false, bool WEIGHTED = false, int ROUTE = ROUTE_ALL>
 __global__ void __launch_bounds__(MAIN_THREADS, MAIN_WAVES / 4) k_main(MainArgs a) {
     constexpr bool LAST = MODE == MODE_LAST || MODE == MODE_LAST_FOLD;
     constexpr bool FOLD = MODE == MODE_LAST_FOLD;
+    constexpr bool COMPACT = ROUTE == ROUTE_COMPACT;
+    constexpr bool STATS = MODE == MODE_STATS;
     static_assert(!SITEMAP || LAST, "the site map is the head's: last block only");
     static_assert(!WEIGHTED || (!SITEMAP && MODE != MODE_FIRST), "weighted launches: blocks' own modes, no site map");
+    static_assert(ROUTE == ROUTE_ALL || (!SITEMAP && !WEIGHTED && MODE != MODE_FIRST), "site-map, weighted and embedding launches are not routed");
+    static_assert(!STATS || ROUTE == ROUTE_LIST, "the statistics launch walks the split-route list in the original tiling");
+    static_assert(!COMPACT || FLAT, "the compact tiling has one instantiation");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     lds_frag_t lw = (lds_frag_t)smem;
     lds_f32_t lc = (lds_f32_t)(smem + FRAG_END * 16);
 
+    // a routed launch without an alignment returns before it asks for its LDS image (the grid is sized on the host from
+    // the upper bound, the routes are decided on the device)
+    if (ROUTE != ROUTE_ALL && *a.acount == 0) return;
     {
         // The LDS image (157 KB per workgroup, L2-resident after the first one) is requested in ONE go:
         // global_load_lds_dwordx4 moves 16 bytes per lane straight into LDS (destination = wave-uniform base +
@@ -596,7 +674,7 @@ __global__ void __launch_bounds__(MAIN_THREADS, MAIN_WAVES / 4) k_main(MainArgs 
             image_to_lds<FRAG_W1, FRAG_W2>(a.wimg, smem);
             image_to_lds<FRAG_WO, FRAG_U + U_FRAGS>(a.wimg, smem);
         } else {
-            image_to_lds<(MODE == MODE_FIRST) ? FRAG_WV : 0, LAST ? FRAG_WV : FRAG_END>(a.wimg, smem);
+            image_to_lds<(MODE == MODE_FIRST || STATS) ? FRAG_WV : 0, LAST ? FRAG_WV : FRAG_END>(a.wimg, smem);
         }
         static_assert(CONST_LEN <= MAIN_THREADS, "one constant per thread");
         if (threadIdx.x < CONST_LEN) reinterpret_cast<float*>(smem + FRAG_END * 16)[threadIdx.x] = cv;
@@ -609,7 +687,8 @@ __global__ void __launch_bounds__(MAIN_THREADS, MAIN_WAVES / 4) k_main(MainArgs 
     const int t = lane & 31;
     const int h = lane >> 5;
     const int ntiles = (a.Lloc + 31) >> 5;
-    const int ntasks = a.B * a.nt_aln;           // < 2^31: the host cuts larger batches into chunks
+    // < 2^31: the host cuts larger batches into chunks
+    const int ntasks = COMPACT ? a.cpre[*a.acount] : (ROUTE == ROUTE_LIST ? *a.acount : a.B) * a.nt_aln;
     // static priority for the second-dispatched half of the workgroup (MI355X_MICROARCH.md, two waves per
     // SIMD, item 4: the younger wave otherwise loses every VALU arbitration): -0.3 % launch time, A/B measured
     if (wave >= MAIN_WAVES / 2) __builtin_amdgcn_s_setprio(1);
@@ -641,7 +720,7 @@ __global__ void __launch_bounds__(MAIN_THREADS, MAIN_WAVES / 4) k_main(MainArgs 
         const int run = max(1, min(PF_RUN_MAX, ntasks / (nwaves * 8)));
         int run0 = (blockIdx.x * MAIN_WAVES + wave) * run;             // first tile of this wave's current run
         const int task0 = run0, task1 = ntasks;
-        TilePos cur = tile_pos<FLAT>(a, min(task0, ntasks - 1), ntiles);
+        TilePos cur = tile_pos<FLAT, ROUTE>(a, min(task0, ntasks - 1), ntiles);
         int frag_row = -1;                          // the row (b * P + p) whose row-mix fragments are in mfr
         frag_t mfr[4];
         f32x4 rqv = {0.f, 0.f, 0.f, 0.f};          // L / S_q[h] of that row (wave-uniform)
@@ -651,9 +730,17 @@ __global__ void __launch_bounds__(MAIN_THREADS, MAIN_WAVES / 4) k_main(MainArgs 
         f32x4 px[8], pctx[8], pqr, pqc;
         int pri = 0, prj = 0;                       // MODE_MID0: residues of the next tile's site in both sequences
         auto prefetch = [&](const TilePos& np) {
-            const LanePos nl = lane_pos<FLAT>(a, np, t);
+            const LanePos nl = lane_pos<FLAT, ROUTE>(a, np, t);
             const int ll = nl.l, pb = np.b;
-            const size_t tk = nl.tok0 + nl.toff;
+            const size_t tk = nl.tok;
+            if (STATS) {
+                // the token's x stands at the first site of its class, same row (the compact launch stored it there)
+                const f32x4* xp = reinterpret_cast<const f32x4*>(
+                    a.x + (tk + (size_t)(long)(a.srep[(size_t)pb * a.Lloc + ll] - ll)) * 64 + 4 * h);
+#pragma unroll
+                for (int g = 0; g < 8; ++g) px[g] = xp[2 * g];
+                return;
+            }
             if (MODE == MODE_MID0) {
                 const uint8_t* ib = a.idx + (size_t)pb * a.N * a.Lloc + ll;
                 const int pp = np.r0 + (nl.in_r1 ? 1 : 0);
@@ -686,13 +773,13 @@ __global__ void __launch_bounds__(MAIN_THREADS, MAIN_WAVES / 4) k_main(MainArgs 
             const int row = b * a.P + cur.r0;          // the tile's (first) row, counted over the batch
             // the tile that follows: the next one of this run, or the first one of the wave's next run
             int ntask = task + 1;
-            TilePos nxt = tile_next<FLAT>(a, cur);
+            TilePos nxt = tile_next<FLAT, ROUTE>(a, cur);
             if (ntask == run0 + run) {
                 run0 += nwaves * run;
                 ntask = run0;
-                if (ntask < task1) nxt = tile_pos<FLAT>(a, ntask, ntiles);
+                if (ntask < task1) nxt = tile_pos<FLAT, ROUTE>(a, ntask, ntiles);
             }
-            const LanePos lp = lane_pos<FLAT>(a, cur, t);
+            const LanePos lp = lane_pos<FLAT, ROUTE>(a, cur, t);
             // flat tiling: does this tile end row r0 and start row r0 + 1 (wave-uniform)?
             const bool straddle = lp.wrap < 32;
             int ai = 0, aj = 0;
@@ -709,16 +796,22 @@ __global__ void __launch_bounds__(MAIN_THREADS, MAIN_WAVES / 4) k_main(MainArgs 
                 frag_row = r;
             };
             // the pair's row-mix fragments are loaded once per row, not once per tile
-            if (MODE != MODE_FIRST && row != frag_row) load_mfr(row);
+            if (MODE != MODE_FIRST && !STATS && row != frag_row) load_mfr(row);
             const bool valid = lp.valid;
             const int lc_ = lp.l;                      // (clamped) site for gathers
-            const size_t tok = lp.tok0 + lp.toff;
+            const size_t tok = lp.tok;
             float x[32];
             float zh[4] = {0.f, 0.f, 0.f, 0.f};        // MODE_LAST_FOLD: the head's pre-activation, four partial chains
             float wt = 1.f;                            // WEIGHTED: the token's site weight (a clamped lane's is masked)
             if (WEIGHTED && LAST) wt = a.w[(size_t)b * a.Lloc + lc_];      // (in flight across the whole tile)
 
-            if (MODE == MODE_FIRST) {
+            if (STATS) {
+#pragma unroll
+                for (int g = 0; g < 8; ++g)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) x[4 * g + i] = px[g][i];
+                if (ntask < task1) prefetch(nxt);              // (lands during this tile's statistics phase)
+            } else if (MODE == MODE_FIRST) {
                 // embedding lookup + pair expansion (model.py:173-175): x = T[a_i] + T[a_j]
                 const int ri = residue(a.idx[((size_t)b * a.N + ai) * a.Lloc + lc_]);
                 const int rj = residue(a.idx[((size_t)b * a.N + aj) * a.Lloc + lc_]);
@@ -920,15 +1013,21 @@ __global__ void __launch_bounds__(MAIN_THREADS, MAIN_WAVES / 4) k_main(MainArgs 
                 // (the first WVLO_LDS of the eight live in LDS - all the image has room for; each fragment taken out of
                 // this stream is 1 KB of L2 reads per tile and wave less)
                 frag_t wl[8];
+                if (!COMPACT) {
 #pragma unroll
                 for (int i = WVLO_LDS; i < 8; ++i) wl[i] = a.wv_lo[i * 64 + lane];
+                }
                 if (WEIGHTED) wt = a.w[(size_t)b * a.Lloc + lc_];      // (arrives with the Wv' lo fragments)
                 __builtin_amdgcn_sched_barrier(0);
-                {
+                // (MODE_STATS: x is where it belongs; under the debug taps the repeated sites get their copy, the taps
+                // stay complete - a wave-uniform switch)
+                if (!STATS || a.store_x_last) {
+                    bool keep = valid;
+                    if (STATS) keep = valid && a.srep[(size_t)b * a.Lloc + lc_] != lc_;
                     // Branch-free store: a divergent `if (valid)` makes hipcc merge the vmcnt state of
                     // both paths and wait for these stores (HBM write acks) at the first Wv' lo use.
                     // Lanes past the end of the row write to a 32-token trash area behind x / qrow.
-                    const size_t stok = valid ? tok : a.trash_tok + t;
+                    const size_t stok = keep ? tok : a.trash_tok + t;
                     f32x4* xo = reinterpret_cast<f32x4*>(a.x + stok * 64 + 4 * h);
 #pragma unroll
                     for (int g = 0; g < 8; ++g) {
@@ -936,7 +1035,8 @@ __global__ void __launch_bounds__(MAIN_THREADS, MAIN_WAVES / 4) k_main(MainArgs 
                         xo[2 * g] = u;
                     }
                 }
-                if (a.ablate & 32) { cur = nxt; task = ntask; continue; }   // perf experiment: copy-only
+                // the compact launch ends here: the statistics see every site in place (MODE_STATS)
+                if (COMPACT || (a.ablate & 32)) { cur = nxt; task = ntask; continue; }   // (32: perf experiment, copy-only)
                 f32x16 va[3];
                 {
                     float xn[32];
@@ -1020,14 +1120,16 @@ __global__ void __launch_bounds__(MAIN_THREADS, MAIN_WAVES / 4) k_main(MainArgs 
                     z = pair_sum(z) + lc[CONST_HB];
                 }
                 const float spz = softplus20(z);
+                // the compact launch keeps the term at the token's (first) site: k_head_parts sums the original tiles
+                if (COMPACT) { if (valid && h == 0) a.term[tok] = spz; }
                 const long slot0 = (long)b * a.slots_aln + cur.kt + (FLAT ? cur.r0 : 0);
-                for (int part = 0; part < (straddle ? 2 : 1); ++part) {
+                for (int part = 0; part < (COMPACT ? 0 : straddle ? 2 : 1); ++part) {
                     const float so = half32_sum((valid && lp.in_r1 == (part == 1)) ? (WEIGHTED ? wt * spz : spz) : 0.f);
                     if (lane == 0) a.outpart[slot0 + part] = so;
                 }
                 // both lanes of a pair_sum pair hold spz: the lower one stores it.  Tokens of a tile are consecutive in
                 // both tilings - one run of up to 128 bytes per tile; lanes without a token store nothing
-                if (SITEMAP && valid && h == 0) a.sitemap[lp.tok0 + lp.toff] = spz;
+                if (SITEMAP && valid && h == 0) a.sitemap[tok] = spz;
                 if (!FOLD && a.store_x_last && valid) {
                     f32x4* xo = reinterpret_cast<f32x4*>(a.x + tok * 64 + 4 * h);
 #pragma unroll
@@ -1343,6 +1445,60 @@ __global__ void k_outsum(const float* outpart, float* out, int npairs, int npart
         for (int q = 0; q < 8; ++q) acc += v[q];
     }
     out[pr] = acc * (wst ? wst[(size_t)(pr / P) * 4 + 1] : inv_L_total);
+}
+
+// ---- option "main_dedup": the routes of a run's alignments, and the head sums of the split route --------------
+// Decided on the device, behind k_site_classes, without a word to the host: alignment b takes the split route iff
+// main_dedup_split(ucount[b], Lloc, mode) - its own columns only, so wherever it sits in a batch.  One wave: a ballot
+// per 64 alignments gives the places in both lists, a shuffle scan the prefix of the compact tile counts
+// (pf_layout.h, main_plan_ints, for the layout).
+__global__ void __launch_bounds__(64) k_main_plan(const int* ucount, int* plan, int B, int P, int Lloc, int mode) {
+    const int lane = threadIdx.x;
+    int* const flist = plan + 4;
+    int* const slist = flist + B;
+    int* const cpre = slist + B;
+    int nf = 0, ns = 0, tiles = 0;
+    for (int b0 = 0; b0 < B; b0 += 64) {
+        const int b = b0 + lane;
+        const int K = b < B ? ucount[b] : 0;
+        const bool split = b < B && main_dedup_split(K, Lloc, mode);
+        const bool fused = b < B && !split;
+        const unsigned long long ms = __ballot(split), mf = __ballot(fused), below = (1ull << lane) - 1ull;
+        int incl = split ? compact_tiles(P, K) : 0;          // inclusive scan of the split alignments' tile counts
+        const int mine = incl;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(incl, d); if (lane >= d) incl += o; }
+        if (split) { const int i = ns + __popcll(ms & below); slist[i] = b; cpre[i] = tiles + incl - mine; }
+        if (fused) flist[nf + __popcll(mf & below)] = b;
+        ns += __popcll(ms);
+        nf += __popcll(mf);
+        tiles += __shfl(incl, 63);
+    }
+    if (lane == 0) { plan[0] = nf; plan[1] = ns; plan[2] = tiles; plan[3] = 0; cpre[ns] = tiles; }
+}
+
+// The head's site sums of the split-route alignments: one wave per ORIGINAL tile forms the tile's outpart slot(s) from
+// the terms the compact launch left at the first sites - the term of a repeated site is its class's, the same bits -
+// with k_main's own mask and half32_sum in k_main's lane arrangement (lanes (t, 0) and (t, 1) both hold token t's term).
+template <bool FLAT>
+__global__ void __launch_bounds__(256) k_head_parts(MainArgs a) {
+    const int ns = *a.acount;
+    if (ns == 0) return;
+    const int lane = threadIdx.x & 63, t = lane & 31;
+    const int ntiles = (a.Lloc + 31) >> 5;
+    const int ntasks = ns * a.nt_aln;
+    for (int task = blockIdx.x * 4 + (threadIdx.x >> 6); task < ntasks; task += gridDim.x * 4) {
+        const TilePos cur = tile_pos<FLAT, ROUTE_LIST>(a, task, ntiles);
+        const LanePos lp = lane_pos<FLAT, ROUTE_LIST>(a, cur, t);
+        const size_t row0 = ((size_t)cur.b * a.P + cur.r0 + (lp.in_r1 ? 1 : 0)) * a.Lloc;
+        const float spz = a.term[row0 + a.srep[(size_t)cur.b * a.Lloc + lp.l]];
+        const bool straddle = lp.wrap < 32;
+        const long slot0 = (long)cur.b * a.slots_aln + cur.kt + (FLAT ? cur.r0 : 0);
+        for (int part = 0; part < (straddle ? 2 : 1); ++part) {
+            const float so = half32_sum((lp.valid && lp.in_r1 == (part == 1)) ? spz : 0.f);
+            if (lane == 0) a.outpart[slot0 + part] = so;
+        }
+    }
 }
 
 // ---- site classes ------------------------------------------------------------------------

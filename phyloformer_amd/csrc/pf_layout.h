@@ -59,4 +59,55 @@ constexpr int MAIN_WAVES = MAIN_THREADS / 64;
 
 constexpr int PAIRTAB_ROWS = 22 * 22, PAIRTAB_W = 72;
 
+// ---- option "main_dedup": the compacted tokens of an alignment and their tiles ----------------------------------
+// An alignment with K distinct columns of L (k_site_classes) has P x K compacted tokens (row p, u), u < K, token u of a
+// row standing at site ulist[u].  k_main's compact launch cuts them into tiles of 32 the way the flat tiling cuts the
+// P x L tokens: 32 CONSECUTIVE compacted tokens per tile, a tile may end row r0 and start row r0 + 1 (K >= 32: never
+// more than two rows), only the alignment's last tile is ragged.  K < 32: one ragged tile per row, as the row tiling
+// has it.  Shared by the kernels and the host (tests/test_main_dedup_layout.py walks it on the CPU).
+#if defined(__HIPCC__)
+#define PF_HD __host__ __device__
+#else
+#define PF_HD
+#endif
+// An alignment takes the split route (compact launch + statistics launch) iff K * DEN <= L * NUM; mode 0: never,
+// mode 2: always (tests).  NUM / DEN is the measured break-even of K / L (DESIGN.md section 9,
+// profiles/main_dedup_threshold.txt).
+#ifndef PF_MAIN_DEDUP_NUM
+#define PF_MAIN_DEDUP_NUM 17         // (A/B builds: tools/build_variant.py lib_x.so -DPF_MAIN_DEDUP_NUM=.. -DPF_MAIN_DEDUP_DEN=..)
+#define PF_MAIN_DEDUP_DEN 20
+#endif
+constexpr int MAIN_DEDUP_NUM = PF_MAIN_DEDUP_NUM, MAIN_DEDUP_DEN = PF_MAIN_DEDUP_DEN;
+PF_HD inline bool main_dedup_split(int K, int L, int mode) {
+    return mode == 2 || (mode == 1 && (long)K * MAIN_DEDUP_DEN <= (long)L * MAIN_DEDUP_NUM);
+}
+PF_HD inline int compact_tiles(int P, int K) { return K >= 32 ? (int)(((long)P * K + 31) >> 5) : P; }
+// tokens of tile kt (1..32), and the lane from which a tile at (r0, u0) belongs to row r0 + 1 (32: none)
+PF_HD inline int compact_nvalid(int P, int K, int kt) {
+    const long left = K >= 32 ? (long)P * K - (long)kt * 32 : K;
+    return left < 32 ? (int)left : 32;
+}
+PF_HD inline int compact_wrap(int P, int K, int r0, int u0) {
+    return (K >= 32 && r0 + 1 < P && K - u0 < 32) ? K - u0 : 32;
+}
+struct CompactTile { int r0, u0, nvalid, wrap; };   // row and compacted index of the first token; see above
+PF_HD inline CompactTile compact_tile(int P, int K, int kt) {
+    CompactTile c;
+    if (K >= 32) { const long tok0 = (long)kt * 32; c.r0 = (int)(tok0 / K); c.u0 = (int)(tok0 - (long)c.r0 * K); }
+    else { c.r0 = kt; c.u0 = 0; }
+    c.nvalid = compact_nvalid(P, K, kt);
+    c.wrap = compact_wrap(P, K, c.r0, c.u0);
+    return c;
+}
+// the tile that follows tile (r0, u0) of the same alignment
+PF_HD inline void compact_next(int K, int* r0, int* u0) {
+    if (K < 32) { ++*r0; return; }
+    *u0 += 32;
+    if (*u0 >= K) { *u0 -= K; ++*r0; }
+}
+// The plan k_main_plan writes per run of B alignments (ints): [0] fused alignments nf, [1] split alignments ns,
+// [2] compact tiles of all split alignments, [3] unused | flist [B] | slist [B] | cpre [B + 1] (tiles in front of
+// split alignment i; cpre[ns] = the total)
+PF_HD inline int main_plan_ints(int B) { return 4 + 3 * B + 1; }
+
 }  // namespace pfk

@@ -8,6 +8,7 @@
 // Launch sequence for one batch chunk (nb = n_blocks); a chunk of >= 2 alignments runs it twice, for its two
 // halves, on the two streams (schedule(), driven by forward_chunk and pf_forward_shards_emulated):
 //   k_site_classes                        classes of equal alignment columns: srep, ulist, ucount (option "site_dedup")
+//   k_main_plan                           which alignments run k_main's per-token work per distinct column (option "main_dedup")
 //   k_embed                               row statistics of block 0 and q' by table lookup (x0 is not written)
 //   for k in 0..nb-1:
 //       [k_rowsum, all-reduce srow]       site-sharded runs only
@@ -15,7 +16,9 @@
 //       k_colstats(k)    x (block 0: the embedding table), qrow, mrow -> qcol, column partials (groups or runs),
 //                        both for the first site of every class only
 //       k_colfin(k)      partials (of the site's class) -> ctx, for every site
-//       k_main<MID0|MID|LAST_FOLD>(k)     row + column attention applied, FFN, next block's row statistics / head
+//       k_main<MID0|MID|LAST_FOLD>(k)     row + column attention applied, FFN, next block's row statistics / head; a routed
+//                                         run: the fused launch over its alignment list, then for the split alignments the
+//                                         compact launch and k_main<STATS> (last block: k_head_parts), launch_main_routed
 //   k_outsum                              per-tile head sums -> distances
 //   [all-reduce out]                      site-sharded runs only
 #include <hip/hip_runtime.h>
@@ -229,6 +232,7 @@ struct pf_handle {
     bool colstats_ring = true;    // option "colstats_ring": x / q' of the next pairs through an LDS ring (1) or registers (0: cross-check)
     bool materialize_x0 = false;  // option "materialize_x0": k_embed writes x0 and block 0 reads it (round-1 path)
     bool site_dedup = true;       // option "site_dedup": k_colstats walks every distinct column once (0: every site, the identity map)
+    int main_dedup = 1;           // option "main_dedup": k_main's per-token work once per distinct column - 1 per alignment, 0 never, 2 always
     float* first_consts = nullptr;  // consts for k_main<FIRST> (only bqk used)
     float* first_img = nullptr;     // LDS image for k_main<FIRST> (only the row-statistics tail used)
     std::vector<BlockDev> blk;
@@ -569,6 +573,7 @@ TilePlan tile_plan(const pf_handle* h, int P, int Lloc) { return tile_plan_core(
 struct Workspace {
     float *x, *qrow, *qcol, *srow, *mrow, *part, *ctx, *mfrag, *spart, *outpart, *rq;
     int *srep, *ulist, *ucount;   // k_site_classes: [B][Lloc], [B][Lloc], [B]
+    int* plan;                    // k_main_plan: the routes of the run's alignments (pf_layout.h, main_plan_ints)
     int G;             // pair groups of k_colstats
     int sub, S, fine;  // runs of `sub` pairs, S per group; fine: one block per run instead of per group
     int nparts() const { return fine ? G * S : G; }
@@ -596,7 +601,7 @@ size_t workspace_bytes(const pf_handle* h, int B, int P, int Lloc, Workspace* w,
     off[8] = o; o = align_up(o + (size_t)B * slots * SROW * 4, 256);   // spart: row statistics per tile part
     off[9] = o; o = align_up(o + (size_t)B * slots * 4, 256);          // outpart: head sums per tile part
     off[10] = o; o = align_up(o + (size_t)B * P * 4 * 4, 256);         // rq: L / S_q per pair and head
-    off[11] = o; o = align_up(o + ((size_t)B * Lloc * 2 + B) * sizeof(int), 256);   // srep | ulist | ucount
+    off[11] = o; o = align_up(o + ((size_t)B * Lloc * 2 + B + main_plan_ints(B)) * sizeof(int), 256);   // srep | ulist | ucount | plan
     return o;
 }
 void carve_workspace(char* ws, const size_t off[WS_BUFS], Workspace* w, int B, int Lloc) {
@@ -609,6 +614,7 @@ void carve_workspace(char* ws, const size_t off[WS_BUFS], Workspace* w, int B, i
     w->rq = (float*)(ws + off[10]);
     const size_t nsite = (size_t)B * std::max(Lloc, 1);                // (the shape workspace_bytes laid out)
     w->srep = (int*)(ws + off[11]); w->ulist = w->srep + nsite; w->ucount = w->ulist + nsite;
+    w->plan = w->ucount + B;
 }
 
 int ensure_workspace(pf_handle* h, int B, int P, int Lloc, Workspace* w, bool second = false) {
@@ -630,7 +636,7 @@ struct ProfScope {
     pf_handle* h; int kid; hipEvent_t a{}, b{};
     bool on;
     ProfScope(pf_handle* h_, int kid_) : h(h_), kid(kid_) {
-        on = h->profile && (!h->profile_main_only || kid_ == K_MAIN);
+        on = kid_ >= 0 && h->profile && (!h->profile_main_only || kid_ == K_MAIN);
         if (on) { a = get_event(h); b = get_event(h); hipEventRecord(a, h->cur); }
     }
     ~ProfScope() {
@@ -674,14 +680,43 @@ int allreduce(pf_handle* h, void* buf, size_t count, int dtype = NCCL_FLOAT) {
     return PF_OK;
 }
 
-template <int MODE, bool SITEMAP = false, bool WEIGHTED = false>
+// kid < 0: the caller brackets the launch itself (a block's routed launches share one K_MAIN pair of events).
+// Routed launches (ROUTE != ROUTE_ALL) size their grid from the same upper bound: the device knows the real count.
+template <int MODE, bool SITEMAP = false, bool WEIGHTED = false, int ROUTE = ROUTE_ALL>
 int launch_main(pf_handle* h, const MainArgs& a, int kid) {
     const long ntasks = (long)a.B * a.nt_aln;                        // one work item per 32-token tile
     const int cus = std::max(1, h->prop.multiProcessorCount - (h->reducing ? h->reserve_cus : 0));
     const int grid = (int)std::max<long>(1, std::min<long>(cus, (ntasks + MAIN_WAVES - 1) / MAIN_WAVES));
     ProfScope ps(h, kid);
-    if (a.flat) hipLaunchKernelGGL((k_main<MODE, true, SITEMAP, WEIGHTED>), dim3(grid), dim3(MAIN_THREADS), MAIN_LDS_BYTES, h->cur, a);
-    else hipLaunchKernelGGL((k_main<MODE, false, SITEMAP, WEIGHTED>), dim3(grid), dim3(MAIN_THREADS), MAIN_LDS_BYTES, h->cur, a);
+    if constexpr (ROUTE == ROUTE_COMPACT)      // (the compact tiling is its own: one instantiation)
+        hipLaunchKernelGGL((k_main<MODE, true, SITEMAP, WEIGHTED, ROUTE>), dim3(grid), dim3(MAIN_THREADS), MAIN_LDS_BYTES, h->cur, a);
+    else if (a.flat) hipLaunchKernelGGL((k_main<MODE, true, SITEMAP, WEIGHTED, ROUTE>), dim3(grid), dim3(MAIN_THREADS), MAIN_LDS_BYTES, h->cur, a);
+    else hipLaunchKernelGGL((k_main<MODE, false, SITEMAP, WEIGHTED, ROUTE>), dim3(grid), dim3(MAIN_THREADS), MAIN_LDS_BYTES, h->cur, a);
+    HIPCHK(h, hipGetLastError());
+    return PF_OK;
+}
+
+// One block's k_main work of a run whose alignments are routed (option "main_dedup"): the fused launch over the
+// alignments that stay on it, and for the others the compact launch followed by what must see every site in place - the
+// statistics launch, or after the last block the head sums.  Each returns at once where its list is empty.
+template <int MODE>
+int launch_main_routed(pf_handle* h, const MainArgs& m, const int* plan) {
+    constexpr bool last = MODE == MODE_LAST || MODE == MODE_LAST_FOLD;
+    int rc;
+    MainArgs f = m;
+    f.acount = plan; f.alist = plan + 4;
+    if ((rc = launch_main<MODE, false, false, ROUTE_LIST>(h, f, -1))) return rc;
+    MainArgs c = m;
+    c.acount = plan + 1; c.alist = plan + 4 + m.B; c.cpre = c.alist + m.B;
+    c.term = m.spart;                   // (dead since k_rowfin read it)
+    c.prof = nullptr;
+    if ((rc = launch_main<MODE, false, false, ROUTE_COMPACT>(h, c, -1))) return rc;
+    if (!last) return launch_main<MODE_STATS, false, false, ROUTE_LIST>(h, c, -1);
+    const long ntasks = (long)m.B * m.nt_aln;
+    const int cus = std::max(1, h->prop.multiProcessorCount - (h->reducing ? h->reserve_cus : 0));
+    const int grid = (int)std::max<long>(1, std::min<long>(8L * cus, (ntasks + 3) / 4));
+    if (m.flat) hipLaunchKernelGGL(k_head_parts<true>, dim3(grid), dim3(256), 0, h->cur, c);
+    else hipLaunchKernelGGL(k_head_parts<false>, dim3(grid), dim3(256), 0, h->cur, c);
     HIPCHK(h, hipGetLastError());
     return PF_OK;
 }
@@ -704,6 +739,7 @@ struct ShardRun {
     float* d_smap = nullptr;   // [B][P][Lloc] site map of the head's terms (pf_forward_site_map*), or null
     const float* d_w = nullptr;     // weighted forwards (unsharded): site weights [B][Lloc] and what k_weight_sums made
     const float* d_wst = nullptr;   // of them, [B][4] (pf_weights.hip.h); null: an unweighted forward
+    bool routed = false;            // option "main_dedup": w.plan holds the alignments' routes (forward_chunk decides)
 };
 
 int zero_fill(pf_handle* h, float* p, size_t n) {
@@ -724,6 +760,7 @@ MainArgs main_args(pf_handle* h, const ShardRun& r) {
     m.prof = h->phase_prof_last ? nullptr : h->phase_prof;
     m.w = r.d_w;
     m.srep = r.w.srep;
+    m.ulist = r.w.ulist; m.ucount = r.w.ucount;
     return m;
 }
 
@@ -733,13 +770,24 @@ bool x0_on_the_fly(const pf_handle* h) {
     return !h->materialize_x0 && !h->embed_mfma && h->n_blocks > 1;
 }
 
+// k_main's work once per distinct column (option "main_dedup"): forwards on block 0's on-the-fly x0, site-sharded and
+// emulated ranks included - a rank routes from the classes of its own site range, its partials feed the same sums;
+// weighted and site-map forwards keep the fused launch.
+bool routes_main(const pf_handle* h, const ShardRun& r) {
+    return h->main_dedup != 0 && !r.d_smap && !r.d_w && x0_on_the_fly(h) && r.Lloc > 0;
+}
+
 // The classes of equal columns of the run's alignments (k_site_classes), in front of everything that reads them:
 // once per forward - the indices change from call to call.  Option site_dedup = 0: the identity map, same kernels.
-int launch_site_classes(pf_handle* h, const uint8_t* d_idx, int B, int N, int Lloc, int* srep, int* ulist, int* ucount) {
+int launch_site_classes(pf_handle* h, const uint8_t* d_idx, int B, int N, int Lloc, int* srep, int* ulist, int* ucount,
+                        int* plan = nullptr, int P = 0) {
     if (!Lloc) return PF_OK;
     SiteClassArgs a{d_idx, srep, ulist, ucount, N, Lloc, h->site_dedup ? 1 : 0};
     ProfScope ps(h, K_SITE_CLASSES);
     hipLaunchKernelGGL(k_site_classes, dim3(B), dim3(SC_THREADS), 0, h->cur, a);
+    HIPCHK(h, hipGetLastError());
+    // the routes of k_main's work follow from the classes, on the device (option "main_dedup")
+    if (plan) hipLaunchKernelGGL(k_main_plan, dim3(1), dim3(64), 0, h->cur, ucount, plan, B, P, Lloc, h->main_dedup);
     HIPCHK(h, hipGetLastError());
     return PF_OK;
 }
@@ -862,10 +910,17 @@ int phase_block(pf_handle* h, const ShardRun& r, int k, RowStats rs) {
     MainArgs m = main_args(h, r);
     m.wimg = reinterpret_cast<const frag_t*>(d.wimg);
     m.consts = d.consts;
+    // a routed run's two or three launches per block stand between ONE pair of events: pf_profile_get("main") keeps
+    // counting one launch per block and run, its time is the block's
+    const int* plan = r.routed ? w.plan : nullptr;
+    const int kid = plan ? -1 : K_MAIN;
+    {
+    ProfScope ps(h, plan ? K_MAIN : -1);
     if (k + 1 < h->n_blocks) {
         m.wv_lo = reinterpret_cast<const frag_t*>(h->blk[k + 1].wv_lo);
         const bool first = k == 0 && x0_on_the_fly(h);
-        if (r.d_w) rc = first ? launch_main<MODE_MID0, false, true>(h, m, K_MAIN) : launch_main<MODE_MID, false, true>(h, m, K_MAIN);
+        if (plan) rc = first ? launch_main_routed<MODE_MID0>(h, m, plan) : launch_main_routed<MODE_MID>(h, m, plan);
+        else if (r.d_w) rc = first ? launch_main<MODE_MID0, false, true>(h, m, K_MAIN) : launch_main<MODE_MID, false, true>(h, m, K_MAIN);
         else rc = first ? launch_main<MODE_MID0>(h, m, K_MAIN) : launch_main<MODE_MID>(h, m, K_MAIN);
         if (rc) return rc;
     } else {
@@ -873,11 +928,14 @@ int phase_block(pf_handle* h, const ShardRun& r, int k, RowStats rs) {
         if (h->phase_prof_last) m.prof = h->phase_prof;
         m.sitemap = r.d_smap;
         if (!h->head_fold) {
+            // (under the debug taps this launch also writes x of every site: all alignments through the fused launch)
             if ((rc = r.d_w      ? launch_main<MODE_LAST, false, true>(h, m, K_MAIN)
-                      : r.d_smap ? launch_main<MODE_LAST, true>(h, m, K_MAIN) : launch_main<MODE_LAST>(h, m, K_MAIN))) return rc;
+                      : r.d_smap ? launch_main<MODE_LAST, true>(h, m, K_MAIN)
+                      : plan && !h->debug_keep ? launch_main_routed<MODE_LAST>(h, m, plan) : launch_main<MODE_LAST>(h, m, kid))) return rc;
         } else {
             if ((rc = r.d_w      ? launch_main<MODE_LAST_FOLD, false, true>(h, m, K_MAIN)
-                      : r.d_smap ? launch_main<MODE_LAST_FOLD, true>(h, m, K_MAIN) : launch_main<MODE_LAST_FOLD>(h, m, K_MAIN)))
+                      : r.d_smap ? launch_main<MODE_LAST_FOLD, true>(h, m, K_MAIN)
+                      : plan     ? launch_main_routed<MODE_LAST_FOLD>(h, m, plan) : launch_main<MODE_LAST_FOLD>(h, m, K_MAIN)))
                 return rc;
             if (h->debug_keep) {
                 // the folded head never forms x6: the full FFN writes it for the tap (in place, after the folded
@@ -885,9 +943,10 @@ int phase_block(pf_handle* h, const ShardRun& r, int k, RowStats rs) {
                 MainArgs md = m;
                 md.outpart = w.spart;
                 md.prof = nullptr;
-                if ((rc = r.d_w ? launch_main<MODE_LAST, false, true>(h, md, K_MAIN) : launch_main<MODE_LAST>(h, md, K_MAIN))) return rc;
+                if ((rc = r.d_w ? launch_main<MODE_LAST, false, true>(h, md, K_MAIN) : launch_main<MODE_LAST>(h, md, kid))) return rc;
             }
         }
+    }
     }
     if (h->debug_keep && (rc = save_tap(h, "x" + std::to_string(k + 1), w.x, (size_t)B * P * Lloc * 64))) return rc;
     return PF_OK;
@@ -933,7 +992,8 @@ int schedule(pf_handle* h, ShardRun* runs, size_t nruns, Reduce reduce) {
     int rc;
     for (ShardRun* r = runs; r != end; ++r) {
         h->cur = r->stream;
-        if ((rc = launch_site_classes(h, r->d_idx, r->B, r->N, r->Lloc, r->w.srep, r->w.ulist, r->w.ucount))) return rc;
+        if ((rc = launch_site_classes(h, r->d_idx, r->B, r->N, r->Lloc, r->w.srep, r->w.ulist, r->w.ucount,
+                                      r->routed ? r->w.plan : nullptr, r->P))) return rc;
         if ((rc = phase_first(h, *r))) return rc;
         r->rs = first_stats(h, *r);
     }
@@ -977,6 +1037,7 @@ int forward_chunk(pf_handle* h, const uint8_t* d_idx, int B, int N, int Lloc, in
                         tile_plan(h, P, Lloc), h->stream, {}};
         if (d_smap) r[i].d_smap = d_smap + (size_t)b0 * P * Lloc;
         if (d_w) { r[i].d_w = d_w + (size_t)b0 * Lloc; r[i].d_wst = d_wst + (size_t)b0 * pfw::WST; }
+        r[i].routed = routes_main(h, r[i]);
         if ((rc = ensure_workspace(h, nb, P, Lloc, &r[i].w, i == 1))) return rc;
         b0 += nb;
     }
@@ -2619,6 +2680,7 @@ int pf_set_option(pf_handle_t* h, const char* key, int64_t value) {
     else if (k == "force_rccl") h->force_rccl = value != 0;
     else if (k == "colstats_ring") h->colstats_ring = value != 0;
     else if (k == "site_dedup") h->site_dedup = value != 0;
+    else if (k == "main_dedup") h->main_dedup = value <= 0 ? 0 : (value >= 2 ? 2 : 1);
     else if (k == "precise") h->precise = value < 0 ? -1 : (value != 0);
     else if (k == "recheck_above") h->recheck_above = value > 0 ? (double)value : 0.0;
     else if (k == "precise_ffn_valu") h->precise_ffn_valu = value != 0;
@@ -3261,6 +3323,7 @@ int pf_forward_shards_emulated(pf_handle_t* h, const uint8_t* idx, int32_t B, in
         r.d_out = (float*)stage.alloc((size_t)B * P * sizeof(float));
         if (!ws || !r.d_out) return fail(h, PF_ENOMEM, "shard workspace allocation failed");
         carve_workspace(ws, off, &r.w, B, r.Lloc);
+        r.routed = routes_main(h, r);
         runs.push_back(r);
     }
     // the "all-reduced" buffer every emulated rank reads
