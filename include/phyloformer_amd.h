@@ -750,6 +750,9 @@ int pf_profile_get(pf_handle_t* h, const char* kernel, int64_t* launches, double
  *             (x0 = embedding + pair expansion, x<k> = output of block k-1)
  *   "srow<k>" float [B][P][72]   row statistics feeding block k
  *   "ctx<k>"  float [B][Lloc][64] column context of block k
+ *   "srep", "ulist" int32 [B][Lloc], "ucount" int32 [B]: the run's classes of equal columns (raw int32 bits in the
+ *             float buffer; a "ulist" row is written up to ucount[b]); "plan" int32 [4 + 3 B + 1]: the routes of option
+ *             "main_dedup" (csrc/pf_layout.h, main_plan_ints) - only after a forward that was routed, else PF_ESTATE
  * (the float64 path keeps only "x<k>", k >= 1, narrowed to float)
  * Returns the number of floats written (<= cap) or a negative status. */
 int64_t pf_debug_read(pf_handle_t* h, const char* name, float* dst, int64_t cap);

@@ -792,6 +792,21 @@ int launch_site_classes(pf_handle* h, const uint8_t* d_idx, int B, int N, int Ll
     return PF_OK;
 }
 
+// Debug taps of what launch_site_classes left for the run (raw int32 bits in the float taps): "srep" and "ulist"
+// [B][Lloc] (ulist: the first ucount[b] entries of a row are written), "ucount" [B], and for a routed run "plan"
+// (pf_layout.h, main_plan_ints) - a run that is not routed leaves no "plan" tap behind.
+int save_route_taps(pf_handle* h, const ShardRun& r) {
+    if (!r.Lloc) return PF_OK;
+    const size_t nsite = (size_t)r.B * r.Lloc;
+    int rc;
+    if ((rc = save_tap(h, "srep", reinterpret_cast<const float*>(r.w.srep), nsite))) return rc;
+    if ((rc = save_tap(h, "ulist", reinterpret_cast<const float*>(r.w.ulist), nsite))) return rc;
+    if ((rc = save_tap(h, "ucount", reinterpret_cast<const float*>(r.w.ucount), (size_t)r.B))) return rc;
+    if (r.routed) return save_tap(h, "plan", reinterpret_cast<const float*>(r.w.plan), (size_t)main_plan_ints(r.B));
+    h->taps.erase("plan");
+    return PF_OK;
+}
+
 // embedding + pair expansion + row statistics of block 0
 int phase_first(pf_handle* h, const ShardRun& r) {
     if (!r.Lloc) return zero_fill(h, r.w.srow, (size_t)r.B * r.P * SROW);
@@ -994,6 +1009,7 @@ int schedule(pf_handle* h, ShardRun* runs, size_t nruns, Reduce reduce) {
         h->cur = r->stream;
         if ((rc = launch_site_classes(h, r->d_idx, r->B, r->N, r->Lloc, r->w.srep, r->w.ulist, r->w.ucount,
                                       r->routed ? r->w.plan : nullptr, r->P))) return rc;
+        if (h->debug_keep && (rc = save_route_taps(h, *r))) return rc;
         if ((rc = phase_first(h, *r))) return rc;
         r->rs = first_stats(h, *r);
     }

@@ -5,7 +5,8 @@ sites only), then the row statistics - after the last block the head's site sums
 changes its order, so everything here is ``np.array_equal`` on the float bits: ``main_dedup`` 0 (every alignment fused),
 1 (routed per alignment) and 2 (every alignment split, even one without a repeat) against each other.
 
-Alignments are built from a pool of columns.  Shapes: (4, 33), (6, 70) and (8, 200) flat tiling, (5, 64) row tiling.
+Alignments are built from a pool of columns (``helpers/dedup_model.py``).  Shapes: (4, 33), (6, 70) and (8, 200) flat
+tiling, (5, 64) row tiling.
 Distinct counts 1, 31, 32, 33, L - 1 and L (below 32 the compact tiling has one ragged tile per row, from 32 on tiles of
 32 consecutive compacted tokens that may cover two rows), with the repeats in front of the other columns' first
 occurrences ("front": the last site is a first occurrence), behind all of them ("behind") or scattered between them
@@ -15,37 +16,10 @@ both routes, whatever the threshold (one distinct column: split; no repeat: fuse
 import numpy as np
 import pytest
 
+from helpers.dedup_model import PLACEMENTS, alignment
+
 pytestmark = pytest.mark.gpu
 SHAPES = [(4, 33), (6, 70), (8, 200), (5, 64)]
-PLACEMENTS = ["front", "behind", "between"]
-
-
-def distinct_columns(rng, n, k):
-    cols = {}
-    while len(cols) < k:
-        c = rng.integers(0, 22, n).astype(np.uint8)
-        cols.setdefault(c.tobytes(), c)
-    return np.stack(list(cols.values()), axis=1)          # [n, k]
-
-
-def alignment(n, l, k, placement, seed=0):
-    """uint8[n, l] with exactly k distinct columns."""
-    rng = np.random.default_rng(100000 * n + 100 * l + k + seed)
-    pool = distinct_columns(rng, n, k)
-    rep = l - k
-    if placement == "front":            # column 0, its repeats, then the other columns' first occurrences
-        pick = np.concatenate([[0], np.zeros(rep, int), np.arange(1, k)])
-    elif placement == "behind":         # every first occurrence, then repeats of any of them
-        pick = np.concatenate([np.arange(k), rng.integers(0, k, rep)])
-    else:                               # repeats scattered between the first occurrences, the last site a first one
-        pick = np.full(l, -1)
-        where = np.array([0]) if k == 1 else np.sort(np.concatenate([[0], rng.permutation(np.arange(1, l - 1))[:k - 2], [l - 1]]))
-        pick[where.astype(int)] = np.arange(k)
-        for s in np.flatnonzero(pick < 0):
-            pick[s] = rng.integers(0, pick[:s].max() + 1)     # a column that stood in front already
-    a = np.ascontiguousarray(pool[:, pick.astype(int)])
-    assert a.shape == (n, l) and len({a[:, s].tobytes() for s in range(l)}) == k
-    return a
 
 
 def counts(l):

@@ -19,7 +19,7 @@ from phyloformer_amd import weights_sites as ws
 
 pytestmark = pytest.mark.gpu
 SHAPES = [(4, 33), (6, 70), (5, 64), (6, 40)]
-PATTERNS = ["none", "all", "big_class", "far", "last_seq", "mixed"]
+PATTERNS = ["none", "all", "big_class", "far", "last_seq", "first_seq", "mixed"]
 
 
 def distinct_columns(rng, n, k):
@@ -46,6 +46,10 @@ def alignment(n, l, pattern, seed=0):
     elif pattern == "last_seq":                             # columns that differ in the last sequence only
         a = np.repeat(pool[:, :1], l, axis=1)
         a[n - 1] = (np.arange(l) * 5) % 22                  # (l > 22: repeats among them)
+        return np.ascontiguousarray(a)
+    elif pattern == "first_seq":                            # ... and in sequence 0 only
+        a = np.repeat(pool[:, :1], l, axis=1)
+        a[0] = (np.arange(l) * 7) % 22
         return np.ascontiguousarray(a)
     elif pattern == "mixed":                                # about l / 2 distinct columns
         pick = rng.integers(0, max(1, l // 2), l)
@@ -88,7 +92,9 @@ def same(a, b):
 
 # ---- the classes ----------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("n,l", SHAPES + [(3, 1100), (3, 4096), (22, 1)])      # two rounds of the kernel's threads; its table full; one site
+# two rounds of the kernel's threads; its table full; one site; the sequence cap (the byte loops are unrolled by 8: 200 is a
+# multiple of it, 9 is not)
+@pytest.mark.parametrize("n,l", SHAPES + [(3, 1100), (3, 4096), (22, 1), (200, 40), (9, 40)])
 def test_site_classes_are_numpys_first_occurrences(eng, n, l):
     alns = [alignment(n, l, p) for p in PATTERNS if l > 2] + [alignment(n, l, "mixed", seed=s) for s in (1, 2)]
     rng = np.random.default_rng(l)
