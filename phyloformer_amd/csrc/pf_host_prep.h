@@ -1,8 +1,8 @@
 // Host-side preparation of the device operands: 16-bit hi/lo MFMA fragment images (fp16; bf16 with PF_F16 = 0), LayerNorm folding, the block-0
-// residue-pair table, the shape-only launch plans (k_main's tiling, k_colstats' summation tree), and the reader of the
-// checkpoint blob (read_blob) with the embedding table all three weight images start from.
+// residue-pair table, the shape-only launch plans (k_main's tiling, k_colstats' summation tree) and workspace list, and the
+// reader of the checkpoint blob (read_blob) with the embedding table all three weight images start from.
 // Plain C++ (no HIP): included by pf_lib.hip, and compiled on its own with g++ -fsanitize=address,undefined for the
-// fuzz tests (tests/test_native_sanitizers.py, tests/native/pf_host_prep_shim.cpp).
+// fuzz tests (tests/test_native_sanitizers.py, tests/native/pf_host_prep_shim.cpp, tests/test_workspace_native.py).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -312,6 +312,36 @@ inline ColPlan colstats_plan_core(int B, int P, int Lloc, int colstats_fine) {
     const bool auto_fine = w->S > 1 && group_blocks < 512;
     w->fine = colstats_fine < 0 ? (int)auto_fine : (colstats_fine && w->S > 1);
     return plan;
+}
+
+// The default kernels' workspace for B alignments of P pairs x Lloc sites and the column-statistics
+// plan of that shape: one list of arrays for pf_spans.h's visitors, align = 256 (tests/native/pf_workspace_main.cpp).
+constexpr int WS_CPART = 4 * 64 + 8;   // floats of a column partial (pf_device.hip.h: CPART; pf_lib.hip asserts the two equal)
+struct Workspace {
+    float *x = nullptr, *qrow = nullptr, *qcol = nullptr, *srow = nullptr, *mrow = nullptr, *part = nullptr, *ctx = nullptr,
+          *mfrag = nullptr, *spart = nullptr, *outpart = nullptr, *rq = nullptr;
+    int *srep = nullptr, *ulist = nullptr, *ucount = nullptr;   // k_site_classes: [B][Lloc], [B][Lloc], [B]
+    int* plan = nullptr;               // k_main_plan: the routes of the run's alignments (pf_layout.h, main_plan_ints)
+    int G = 0, sub = 0, S = 0, fine = 0;   // k_colstats: pair groups, runs of `sub` pairs, S per group; fine: a block per run
+    int nparts() const { return fine ? G * S : G; }
+};
+// An empty shard (Lloc = 0) is laid out as one site: it launches nothing and only zero-fills srow.
+template <class V>
+inline void workspace_arrays(V& v, Workspace& w, int B, int P, int Lloc, int colstats_fine, int tile_force) {
+    Lloc = std::max(Lloc, 1);
+    const ColPlan c = colstats_plan_core(B, P, Lloc, colstats_fine);
+    w.G = c.G; w.sub = c.sub; w.S = c.S; w.fine = c.fine;
+    const size_t pairs = (size_t)B * P, sites = (size_t)B * Lloc, tok = pairs * Lloc;
+    const size_t slots = (size_t)B * tile_plan_core(P, Lloc, tile_force).slots_aln;
+    v(w.x, (tok + 32) * 64);                                  // (+ 32 tokens: the trash area at token B P Lloc)
+    v(w.qrow, (tok + 32) * 4); v(w.qcol, (tok + 32) * 4);     // (+ trash)
+    v(w.srow, pairs * SROW); v(w.mrow, pairs * MROW);
+    v(w.part, sites * w.nparts() * WS_CPART); v(w.ctx, sites * 64);
+    v(w.mfrag, pairs * MFRAG_PER_PAIR * 4);                   // fragments of 16 bytes
+    v(w.spart, slots * SROW); v(w.outpart, slots);            // row statistics, head sums per tile part
+    v(w.rq, pairs * 4);                                       // L / S_q per pair and head
+    v(w.srep, 2 * sites + B + main_plan_ints(B));             // srep | ulist | ucount | plan: one span of ints, cut here
+    if (w.srep) { w.ulist = w.srep + sites; w.ucount = w.ulist + sites; w.plan = w.ucount + B; }   // (null: only measured)
 }
 
 }  // namespace pfhost

@@ -6,21 +6,20 @@
 // (reference: phyloformer/model.py:166-187).
 //
 // Launch sequence for one batch chunk (nb = n_blocks); a chunk of >= 2 alignments runs it twice, for its two
-// halves, on the two streams (schedule(), driven by forward_chunk and pf_forward_shards_emulated):
-//   k_site_classes                        classes of equal alignment columns: srep, ulist, ucount (option "site_dedup")
-//   k_main_plan                           which alignments run k_main's per-token work per distinct column (option "main_dedup")
-//   k_embed                               row statistics of block 0 and q' by table lookup (x0 is not written)
-//   for k in 0..nb-1:
-//       [k_rowsum, all-reduce srow]       site-sharded runs only
-//       k_rowfin(k)      per-tile row statistics -> row-mix matrices / fragments of every pair
-//       k_colstats(k)    x (block 0: the embedding table), qrow, mrow -> qcol, column partials (groups or runs),
-//                        both for the first site of every class only
-//       k_colfin(k)      partials (of the site's class) -> ctx, for every site
-//       k_main<MID0|MID|LAST_FOLD>(k)     row + column attention applied, FFN, next block's row statistics / head; a routed
-//                                         run: the fused launch over its alignment list, then for the split alignments the
-//                                         compact launch and k_main<STATS> (last block: k_head_parts), launch_main_routed
-//   k_outsum                              per-tile head sums -> distances
-//   [all-reduce out]                      site-sharded runs only
+// halves, on the two streams (schedule(), driven by forward_chunk and pf_forward_shards_emulated over shard_run()'s runs):
+//   launch_site_classes   k_site_classes: classes of equal alignment columns: srep, ulist, ucount (option "site_dedup"); a routed
+//                         run: k_main_plan, which alignments run k_main's per-token work per distinct column ("main_dedup")
+//   phase_first           k_embed: row statistics of block 0 and q' by table lookup (x0 is not written)
+//   phase_block(k), k in 0..nb-1:
+//       [launch_rowsum, all-reduce srow]   site-sharded runs only
+//       launch_rowfin      per-tile row statistics -> row-mix matrices / fragments of every pair
+//       launch_colstats    x (block 0: the embedding table), qrow, mrow -> qcol, column partials (groups or runs), both for
+//                          the first site of every class only
+//       launch_colfin      partials (of the site's class) -> ctx, for every site
+//       launch_block_main  k_main<MID0|MID|LAST_FOLD>: row + column attention applied, FFN, next block's row statistics / head;
+//                          block_kind() says which instantiation (main_kernels() is their one table, launch_main their one
+//                          launch) and whether by the run's routes: launch_main_routed
+//   launch_outsum         k_outsum: per-tile head sums -> distances;  [all-reduce out]: site-sharded runs only
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 
@@ -570,59 +569,17 @@ size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 TilePlan tile_plan(const pf_handle* h, int P, int Lloc) { return tile_plan_core(P, Lloc, h->tile_force); }
 
-struct Workspace {
-    float *x, *qrow, *qcol, *srow, *mrow, *part, *ctx, *mfrag, *spart, *outpart, *rq;
-    int *srep, *ulist, *ucount;   // k_site_classes: [B][Lloc], [B][Lloc], [B]
-    int* plan;                    // k_main_plan: the routes of the run's alignments (pf_layout.h, main_plan_ints)
-    int G;             // pair groups of k_colstats
-    int sub, S, fine;  // runs of `sub` pairs, S per group; fine: one block per run instead of per group
-    int nparts() const { return fine ? G * S : G; }
-};
-constexpr int WS_BUFS = 12;
-
-// The column-statistics plan into w and the buffer offsets of a workspace for B alignments of P pairs x Lloc sites.
-// An empty shard (Lloc = 0) is laid out as one site: it launches nothing and only zero-fills srow.
-size_t workspace_bytes(const pf_handle* h, int B, int P, int Lloc, Workspace* w, size_t off[WS_BUFS]) {
-    Lloc = std::max(Lloc, 1);
-    const ColPlan c = colstats_plan_core(B, P, Lloc, h->colstats_fine);
-    w->G = c.G; w->sub = c.sub; w->S = c.S; w->fine = c.fine;
-    const int nparts = w->nparts();
-    const size_t tok = (size_t)B * P * Lloc;
-    size_t o = 0;
-    off[0] = o; o = align_up(o + (tok + 32) * 64 * 4, 256);              // x (+ 32-token trash area)
-    off[1] = o; o = align_up(o + (tok + 32) * 4 * 4, 256);               // qrow (+ trash)
-    off[2] = o; o = align_up(o + (tok + 32) * 4 * 4, 256);               // qcol (+ trash)
-    off[3] = o; o = align_up(o + (size_t)B * P * SROW * 4, 256);         // srow
-    off[4] = o; o = align_up(o + (size_t)B * P * MROW * 4, 256);         // mrow
-    off[5] = o; o = align_up(o + (size_t)B * nparts * Lloc * CPART * 4, 256); // part
-    off[6] = o; o = align_up(o + (size_t)B * Lloc * 64 * 4, 256);        // ctx
-    off[7] = o; o = align_up(o + (size_t)B * P * MFRAG_PER_PAIR * 16, 256); // mfrag
-    const size_t slots = (size_t)tile_plan(h, P, Lloc).slots_aln;
-    off[8] = o; o = align_up(o + (size_t)B * slots * SROW * 4, 256);   // spart: row statistics per tile part
-    off[9] = o; o = align_up(o + (size_t)B * slots * 4, 256);          // outpart: head sums per tile part
-    off[10] = o; o = align_up(o + (size_t)B * P * 4 * 4, 256);         // rq: L / S_q per pair and head
-    off[11] = o; o = align_up(o + ((size_t)B * Lloc * 2 + B + main_plan_ints(B)) * sizeof(int), 256);   // srep | ulist | ucount | plan
-    return o;
-}
-void carve_workspace(char* ws, const size_t off[WS_BUFS], Workspace* w, int B, int Lloc) {
-    w->x = (float*)(ws + off[0]); w->qrow = (float*)(ws + off[1]);
-    w->qcol = (float*)(ws + off[2]); w->srow = (float*)(ws + off[3]);
-    w->mrow = (float*)(ws + off[4]); w->part = (float*)(ws + off[5]);
-    w->ctx = (float*)(ws + off[6]);
-    w->mfrag = (float*)(ws + off[7]);
-    w->spart = (float*)(ws + off[8]); w->outpart = (float*)(ws + off[9]);
-    w->rq = (float*)(ws + off[10]);
-    const size_t nsite = (size_t)B * std::max(Lloc, 1);                // (the shape workspace_bytes laid out)
-    w->srep = (int*)(ws + off[11]); w->ulist = w->srep + nsite; w->ucount = w->ulist + nsite;
-    w->plan = w->ucount + B;
+// The default kernels' workspace as its list (pf_host_prep.h) under the handle's options; it leaves k_colstats' plan in w too.
+static_assert(WS_CPART == CPART, "the workspace list sizes k_colstats' partials");
+auto workspace_list(const pf_handle* h, Workspace& w, int B, int P, int Lloc) {
+    return [=, &w](auto& v) { workspace_arrays(v, w, B, P, Lloc, h->colstats_fine, h->tile_force); };
 }
 
 int ensure_workspace(pf_handle* h, int B, int P, int Lloc, Workspace* w, bool second = false) {
-    size_t off[WS_BUFS];
-    const size_t need = workspace_bytes(h, B, P, Lloc, w, off);
+    auto list = workspace_list(h, *w, B, P, Lloc);
     Buffer<char>& ws = second ? h->ws2 : h->ws;
-    if (const int rc = ws.reserve(h, need)) return rc;
-    carve_workspace(ws, off, w, B, Lloc);
+    if (const int rc = ws.reserve(h, pfspan::measure(list, 256))) return rc;
+    pfspan::carve(ws, list, 256);
     return PF_OK;
 }
 
@@ -635,8 +592,8 @@ hipEvent_t get_event(pf_handle* h) {
 struct ProfScope {
     pf_handle* h; int kid; hipEvent_t a{}, b{};
     bool on;
-    ProfScope(pf_handle* h_, int kid_) : h(h_), kid(kid_) {
-        on = kid_ >= 0 && h->profile && (!h->profile_main_only || kid_ == K_MAIN);
+    ProfScope(pf_handle* h_, int kid_, bool timed = true) : h(h_), kid(kid_) {
+        on = timed && h->profile && (!h->profile_main_only || kid_ == K_MAIN);
         if (on) { a = get_event(h); b = get_event(h); hipEventRecord(a, h->cur); }
     }
     ~ProfScope() {
@@ -680,43 +637,59 @@ int allreduce(pf_handle* h, void* buf, size_t count, int dtype = NCCL_FLOAT) {
     return PF_OK;
 }
 
-// kid < 0: the caller brackets the launch itself (a block's routed launches share one K_MAIN pair of events).
-// Routed launches (ROUTE != ROUTE_ALL) size their grid from the same upper bound: the device knows the real count.
-template <int MODE, bool SITEMAP = false, bool WEIGHTED = false, int ROUTE = ROUTE_ALL>
-int launch_main(pf_handle* h, const MainArgs& a, int kid) {
-    const long ntasks = (long)a.B * a.nt_aln;                        // one work item per 32-token tile
+// ---- k_main's launches ----------------------------------------------------------------------------
+// What a launch instantiates k_main with: the mode, whether it writes the head's site map or reads site weights, the
+// route; the tiling (FLAT) is the run's.  HEAD_PARTS: k_head_parts, no mode of k_main but a kernel on its arguments.
+enum { PLAIN = 0, SITEMAP = 1, WEIGHTED = 2 };
+constexpr int HEAD_PARTS = MODE_STATS + 1;
+struct MainKind { int mode, flavour = PLAIN, route = ROUTE_ALL; };
+using MainKernel = void (*)(MainArgs);
+struct MainRow { MainKind kind; bool flat; MainKernel fn; };
+const std::vector<MainRow>& main_kernels();      // (the table stands behind the launches that name k_embed and k_colstats)
+
+// The kernel of (kind, flat), or null: a combination k_main's static_asserts exclude.
+MainKernel main_kernel(MainKind k, bool flat) {
+    for (const MainRow& r : main_kernels())
+        if (r.kind.mode == k.mode && r.kind.flavour == k.flavour && r.kind.route == k.route && r.flat == flat) return r.fn;
+    return nullptr;
+}
+
+// Blocks of a persistent launch: `per_block` work items each, `per_cu` per CU at the most; `reserve_cus` CUs stay free for collectives.
+int persistent_grid(const pf_handle* h, long ntasks, int per_block, int per_cu) {
     const int cus = std::max(1, h->prop.multiProcessorCount - (h->reducing ? h->reserve_cus : 0));
-    const int grid = (int)std::max<long>(1, std::min<long>(cus, (ntasks + MAIN_WAVES - 1) / MAIN_WAVES));
-    ProfScope ps(h, kid);
-    if constexpr (ROUTE == ROUTE_COMPACT)      // (the compact tiling is its own: one instantiation)
-        hipLaunchKernelGGL((k_main<MODE, true, SITEMAP, WEIGHTED, ROUTE>), dim3(grid), dim3(MAIN_THREADS), MAIN_LDS_BYTES, h->cur, a);
-    else if (a.flat) hipLaunchKernelGGL((k_main<MODE, true, SITEMAP, WEIGHTED, ROUTE>), dim3(grid), dim3(MAIN_THREADS), MAIN_LDS_BYTES, h->cur, a);
-    else hipLaunchKernelGGL((k_main<MODE, false, SITEMAP, WEIGHTED, ROUTE>), dim3(grid), dim3(MAIN_THREADS), MAIN_LDS_BYTES, h->cur, a);
+    return (int)std::max<long>(1, std::min<long>((long)per_cu * cus, (ntasks + per_block - 1) / per_block));
+}
+
+// One k_main launch, one work item per 32-token tile (a routed launch sizes its grid from the same upper bound: the device
+// knows the real count).  timed: its own pair of events, "main" or for MODE_FIRST "embed"; else the caller brackets it.
+int launch_main(pf_handle* h, MainKind kind, const MainArgs& a, bool timed) {
+    const MainKernel fn = main_kernel(kind, kind.route == ROUTE_COMPACT || a.flat);   // (the compact tiling is its own)
+    if (!fn) return fail(h, PF_ESTATE, "no k_main for mode %d, flavour %d, route %d", kind.mode, kind.flavour, kind.route);
+    const int grid = persistent_grid(h, (long)a.B * a.nt_aln, MAIN_WAVES, 1);
+    ProfScope ps(h, kind.mode == MODE_FIRST ? K_EMBED : K_MAIN, timed);
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(MAIN_THREADS), MAIN_LDS_BYTES, h->cur, a);
     HIPCHK(h, hipGetLastError());
     return PF_OK;
 }
 
+// The plan k_main_plan leaves for a run of B alignments, as the host addresses it (pf_layout.h, above main_plan_ints).
+struct MainPlan { const int *nf, *ns, *flist, *slist, *cpre; };
+MainPlan main_plan(const int* plan, int B) { return {&plan[0], &plan[1], &plan[4], &plan[4 + B], &plan[4 + 2 * B]}; }
+
 // One block's k_main work of a run whose alignments are routed (option "main_dedup"): the fused launch over the
 // alignments that stay on it, and for the others the compact launch followed by what must see every site in place - the
 // statistics launch, or after the last block the head sums.  Each returns at once where its list is empty.
-template <int MODE>
-int launch_main_routed(pf_handle* h, const MainArgs& m, const int* plan) {
-    constexpr bool last = MODE == MODE_LAST || MODE == MODE_LAST_FOLD;
+int launch_main_routed(pf_handle* h, int mode, const MainArgs& m, const MainPlan& p) {
     int rc;
-    MainArgs f = m;
-    f.acount = plan; f.alist = plan + 4;
-    if ((rc = launch_main<MODE, false, false, ROUTE_LIST>(h, f, -1))) return rc;
-    MainArgs c = m;
-    c.acount = plan + 1; c.alist = plan + 4 + m.B; c.cpre = c.alist + m.B;
-    c.term = m.spart;                   // (dead since k_rowfin read it)
-    c.prof = nullptr;
-    if ((rc = launch_main<MODE, false, false, ROUTE_COMPACT>(h, c, -1))) return rc;
-    if (!last) return launch_main<MODE_STATS, false, false, ROUTE_LIST>(h, c, -1);
-    const long ntasks = (long)m.B * m.nt_aln;
-    const int cus = std::max(1, h->prop.multiProcessorCount - (h->reducing ? h->reserve_cus : 0));
-    const int grid = (int)std::max<long>(1, std::min<long>(8L * cus, (ntasks + 3) / 4));
-    if (m.flat) hipLaunchKernelGGL(k_head_parts<true>, dim3(grid), dim3(256), 0, h->cur, c);
-    else hipLaunchKernelGGL(k_head_parts<false>, dim3(grid), dim3(256), 0, h->cur, c);
+    MainArgs f = m, c = m;              // the fused launch's; the compact launch's and its followers'
+    f.acount = p.nf; f.alist = p.flist;
+    if ((rc = launch_main(h, {mode, PLAIN, ROUTE_LIST}, f, false))) return rc;
+    c.acount = p.ns; c.alist = p.slist; c.cpre = p.cpre;
+    c.term = m.spart; c.prof = nullptr; // (spart: dead since k_rowfin read it)
+    if ((rc = launch_main(h, {mode, PLAIN, ROUTE_COMPACT}, c, false))) return rc;
+    if (mode != MODE_LAST && mode != MODE_LAST_FOLD) return launch_main(h, {MODE_STATS, PLAIN, ROUTE_LIST}, c, false);
+    hipLaunchKernelGGL(main_kernel({HEAD_PARTS, PLAIN, ROUTE_LIST}, m.flat != 0), dim3(persistent_grid(h, (long)m.B * m.nt_aln, 4, 8)),
+                       dim3(256), 0, h->cur, c);
     HIPCHK(h, hipGetLastError());
     return PF_OK;
 }
@@ -777,17 +750,26 @@ bool routes_main(const pf_handle* h, const ShardRun& r) {
     return h->main_dedup != 0 && !r.d_smap && !r.d_w && x0_on_the_fly(h) && r.Lloc > 0;
 }
 
-// The classes of equal columns of the run's alignments (k_site_classes), in front of everything that reads them:
-// once per forward - the indices change from call to call.  Option site_dedup = 0: the identity map, same kernels.
-int launch_site_classes(pf_handle* h, const uint8_t* d_idx, int B, int N, int Lloc, int* srep, int* ulist, int* ucount,
-                        int* plan = nullptr, int P = 0) {
-    if (!Lloc) return PF_OK;
-    SiteClassArgs a{d_idx, srep, ulist, ucount, N, Lloc, h->site_dedup ? 1 : 0};
+// A run of B alignments over Lloc of L_total sites, on the main stream, its workspace still to be laid out.
+ShardRun shard_run(const pf_handle* h, const uint8_t* d_idx, float* d_out, int B, int N, int Lloc, int L_total,
+                   float* d_smap = nullptr, const float* d_w = nullptr, const float* d_wst = nullptr) {
+    ShardRun r{};
+    r.d_idx = d_idx; r.d_out = d_out; r.d_smap = d_smap; r.d_w = d_w; r.d_wst = d_wst;
+    r.B = B; r.N = N; r.P = N * (N - 1) / 2; r.Lloc = Lloc; r.L_total = L_total;
+    r.tp = tile_plan(h, r.P, Lloc); r.stream = h->stream; r.routed = routes_main(h, r);
+    return r;
+}
+
+// The classes of equal columns of B alignments (k_site_classes), in front of everything that reads them: once per forward -
+// the indices change from call to call.  Option site_dedup = 0: the identity map, same kernels.  With `plan`, the routes of
+// k_main's work over P pairs follow on the device (k_main_plan, option "main_dedup"), inside the same pair of events.
+int launch_site_classes(pf_handle* h, const SiteClassArgs& a, int B, int* plan = nullptr, int P = 0) {
+    if (!a.Lloc) return PF_OK;
     ProfScope ps(h, K_SITE_CLASSES);
     hipLaunchKernelGGL(k_site_classes, dim3(B), dim3(SC_THREADS), 0, h->cur, a);
     HIPCHK(h, hipGetLastError());
-    // the routes of k_main's work follow from the classes, on the device (option "main_dedup")
-    if (plan) hipLaunchKernelGGL(k_main_plan, dim3(1), dim3(64), 0, h->cur, ucount, plan, B, P, Lloc, h->main_dedup);
+    if (!plan) return PF_OK;
+    hipLaunchKernelGGL(k_main_plan, dim3(1), dim3(64), 0, h->cur, a.ucount, plan, B, P, a.Lloc, h->main_dedup);
     HIPCHK(h, hipGetLastError());
     return PF_OK;
 }
@@ -815,8 +797,7 @@ int phase_first(pf_handle* h, const ShardRun& r) {
         MainArgs m = main_args(h, r);
         m.wimg = reinterpret_cast<const frag_t*>(h->first_img); m.consts = h->first_consts;
         m.wv_lo = reinterpret_cast<const frag_t*>(h->blk[0].wv_lo);
-        rc = launch_main<MODE_FIRST>(h, m, K_EMBED);
-        if (rc) return rc;
+        if ((rc = launch_main(h, {MODE_FIRST}, m, true))) return rc;
     } else {
         // x0 is written only for those who read it: the round-1 consumers or the "x0" debug tap
         float* x0 = (x0_on_the_fly(h) && !h->debug_keep) ? nullptr : r.w.x;
@@ -869,101 +850,117 @@ RowStats first_stats(pf_handle* h, const ShardRun& r) {
     return h->embed_mfma ? main_stats(r) : RowStats{r.w.srow, 1, 0};
 }
 
+// row statistics (rs) -> the row-mix matrices / fragments of every pair
+int launch_rowfin(pf_handle* h, const ShardRun& r, int k, const RowStats& rs) {
+    const BlockDev& d = h->blk[k]; const Workspace& w = r.w;
+    RowFinArgs a{rs.p, w.mrow, reinterpret_cast<frag_t*>(w.mfrag), d.row_woT, d.row_bv, d.row_bo, d.col_bo,
+                 r.B * r.P, rs.nparts, (float)r.L_total, rs.flat, r.P, r.Lloc, r.tp.slots_aln, 1};
+    // enough blocks to fill the chip a few times over (8 x 256-thread blocks per CU), each amortising its
+    // out_proj weights over `iters` groups of four pairs
+    const int groups = (r.B * r.P + 3) / 4;
+    a.iters = std::max(1, std::min(16, groups / (4 * 8 * std::max(1, h->prop.multiProcessorCount))));
+    // q' / mean(q') can reach L_total: past 16,384 sites the B side of the row mix is scaled down by a power of
+    // two and the base matrix up (pf_device.hip.h, "fp16 operand ranges"); exact, and 1 for every usual shape
+    a.b_scale = 1.f;
+    for (long lim = 16384; lim < (long)r.L_total && a.b_scale > 1.f / 256.f; lim *= 2) a.b_scale *= 0.5f;
+    a.a_scale = 1.f / a.b_scale;
+    a.rq = w.rq; a.wst = r.d_wst;     // (wst, weighted: W and the scales per alignment (k_weight_sums) instead)
+    ProfScope ps(h, K_ROWFIN);
+    hipLaunchKernelGGL(k_rowfin, dim3((groups + a.iters - 1) / a.iters), dim3(256), 0, h->cur, a);
+    HIPCHK(h, hipGetLastError());
+    return PF_OK;
+}
+
+// x (block 0 on the fly: the embedding table), qrow, mrow -> qcol and the column partials, for the first site of every class
+int launch_colstats(pf_handle* h, const ShardRun& r, int k) {
+    const BlockDev& d = h->blk[k]; const Workspace& w = r.w;
+    ColStatsArgs a{w.x, w.qrow, w.mrow, w.qcol, w.part, d.col_wqk, d.col_bqk, d.row_bo, r.B, r.P, r.Lloc, w.G, tiles_of(r.Lloc),
+                   w.sub, w.S, w.fine, h->table, r.d_idx, h->pair_i, h->pair_j, r.N, w.ulist, w.ucount};
+    ProfScope ps(h, K_COLSTATS);
+    const unsigned nblk = (unsigned)(r.B * a.nchunks * w.nparts());
+    void (*fn)(ColStatsArgs) = k_colstats<true, 0, 16>;   // block 0 on the fly; else by the LDS ring or by registers (named in the code object's order)
+    if (k != 0 || !x0_on_the_fly(h)) fn = h->colstats_ring ? k_colstats<false, PF_CS_RING, PF_CS_MT> : k_colstats<false, 0, 16>;
+    hipLaunchKernelGGL(fn, dim3(nblk), dim3(256), 0, h->cur, a);
+    HIPCHK(h, hipGetLastError());
+    return PF_OK;
+}
+
+// the partials (of the site's class) -> ctx, for every site
+int launch_colfin(pf_handle* h, const ShardRun& r, int k) {
+    const BlockDev& d = h->blk[k]; const Workspace& w = r.w;
+    ColFinArgs a{w.part, w.ctx, d.col_wvT, d.col_bv, r.B, r.Lloc, w.G, (float)r.P, r.P, w.sub, w.S, w.fine, w.srep};
+    ProfScope ps(h, K_COLFIN);
+    hipLaunchKernelGGL(k_colfin, dim3(r.B * r.Lloc), dim3(COLFIN_THREADS), 0, h->cur, a);
+    HIPCHK(h, hipGetLastError());
+    return PF_OK;
+}
+
+// Every kernel on MainArgs: the one place that spells k_main's instantiations.  The rows stand in the order in which the
+// code object lists the kernels - a row moved, added or dropped changes it (profiles/forward_driver_refactor.txt).
+template <int MODE, bool FLAT, int FLAVOUR = PLAIN, int ROUTE = ROUTE_ALL>
+MainRow main_row() { return {{MODE, FLAVOUR, ROUTE}, FLAT, k_main<MODE, FLAT, FLAVOUR == SITEMAP, FLAVOUR == WEIGHTED, ROUTE>}; }
+template <bool FLAT>
+MainRow head_parts_row() { return {{HEAD_PARTS, PLAIN, ROUTE_LIST}, FLAT, k_head_parts<FLAT>}; }
+const std::vector<MainRow>& main_kernels() {
+    static const std::vector<MainRow> rows = {
+        // routed blocks: the fused list launch (flat, by rows), the compact launch, and what follows the first of them
+        main_row<MODE_MID0, true, PLAIN, ROUTE_LIST>(), main_row<MODE_MID0, false, PLAIN, ROUTE_LIST>(), main_row<MODE_MID0, true, PLAIN, ROUTE_COMPACT>(),
+        main_row<MODE_STATS, true, PLAIN, ROUTE_LIST>(), main_row<MODE_STATS, false, PLAIN, ROUTE_LIST>(), head_parts_row<true>(), head_parts_row<false>(),
+        main_row<MODE_MID, true, PLAIN, ROUTE_LIST>(), main_row<MODE_MID, false, PLAIN, ROUTE_LIST>(), main_row<MODE_MID, true, PLAIN, ROUTE_COMPACT>(),
+        main_row<MODE_LAST, true, PLAIN, ROUTE_LIST>(), main_row<MODE_LAST, false, PLAIN, ROUTE_LIST>(), main_row<MODE_LAST, true, PLAIN, ROUTE_COMPACT>(),
+        main_row<MODE_LAST_FOLD, true, PLAIN, ROUTE_LIST>(), main_row<MODE_LAST_FOLD, false, PLAIN, ROUTE_LIST>(), main_row<MODE_LAST_FOLD, true, PLAIN, ROUTE_COMPACT>(),
+        // every alignment of the run, by rows and flat: plain, with the head's site map (last block only), with site weights
+        main_row<MODE_FIRST, false>(), main_row<MODE_MID, false>(), main_row<MODE_MID0, false>(), main_row<MODE_LAST, false>(), main_row<MODE_LAST_FOLD, false>(),
+        main_row<MODE_FIRST, true>(), main_row<MODE_MID, true>(), main_row<MODE_MID0, true>(), main_row<MODE_LAST, true>(), main_row<MODE_LAST_FOLD, true>(),
+        main_row<MODE_LAST, false, SITEMAP>(), main_row<MODE_LAST_FOLD, false, SITEMAP>(), main_row<MODE_LAST, true, SITEMAP>(), main_row<MODE_LAST_FOLD, true, SITEMAP>(),
+        main_row<MODE_MID, false, WEIGHTED>(), main_row<MODE_MID0, false, WEIGHTED>(), main_row<MODE_LAST, false, WEIGHTED>(), main_row<MODE_LAST_FOLD, false, WEIGHTED>(),
+        main_row<MODE_MID, true, WEIGHTED>(), main_row<MODE_MID0, true, WEIGHTED>(), main_row<MODE_LAST, true, WEIGHTED>(), main_row<MODE_LAST_FOLD, true, WEIGHTED>(),
+    };
+    return rows;
+}
+
+// Which k_main launch block k of a run is, and whether it goes by the run's routes.
+struct BlockKind { MainKind kind; bool routed; };
+BlockKind block_kind(const pf_handle* h, const ShardRun& r, int k) {
+    const bool last = k + 1 >= h->n_blocks;
+    const MainKind kind{!last ? (k == 0 && x0_on_the_fly(h) ? MODE_MID0 : MODE_MID) : (h->head_fold ? MODE_LAST_FOLD : MODE_LAST),
+                        r.d_w ? WEIGHTED : (r.d_smap && last) ? SITEMAP : PLAIN};
+    // (under the debug taps the full last block also writes x of every site: all alignments through the fused launch)
+    return {kind, r.routed && !(kind.mode == MODE_LAST && h->debug_keep)};
+}
+
+// row + column attention applied, FFN, the next block's row statistics or the head's sums
+int launch_block_main(pf_handle* h, const ShardRun& r, int k) {
+    const BlockKind b = block_kind(h, r, k);
+    const bool last = k + 1 >= h->n_blocks;
+    MainArgs m = main_args(h, r);
+    m.wimg = reinterpret_cast<const frag_t*>(h->blk[k].wimg); m.consts = h->blk[k].consts;
+    m.wv_lo = last ? nullptr : reinterpret_cast<const frag_t*>(h->blk[k + 1].wv_lo);
+    if (last) { m.sitemap = r.d_smap; if (h->phase_prof_last) m.prof = h->phase_prof; }
+    // a routed run's two or three launches per block stand between ONE pair of events: pf_profile_get("main") keeps
+    // counting one launch per block and run, its time is the block's
+    ProfScope ps(h, K_MAIN, r.routed);
+    int rc = b.routed ? launch_main_routed(h, b.kind.mode, m, main_plan(r.w.plan, r.B)) : launch_main(h, b.kind, m, !r.routed);
+    if (rc || b.kind.mode != MODE_LAST_FOLD || !h->debug_keep) return rc;
+    // the folded head never forms the last x: the full FFN writes it for the tap (in place, after the folded launch
+    // has read its input), its head sums go to spart, dead since k_rowfin - the distances stay the folded ones
+    m.outpart = r.w.spart; m.prof = nullptr;
+    return launch_main(h, {MODE_LAST, r.d_w ? WEIGHTED : PLAIN}, m, !r.routed);
+}
+
 // block k given its row statistics (already reduced over ranks in a site-sharded run)
 int phase_block(pf_handle* h, const ShardRun& r, int k, RowStats rs) {
     if (!r.Lloc) return PF_OK;
-    const BlockDev& d = h->blk[k];
-    const Workspace& w = r.w;
-    const int B = r.B, P = r.P, Lloc = r.Lloc;
+    const std::string tag = std::to_string(k);
+    const size_t pairs = (size_t)r.B * r.P, sites = (size_t)r.B * r.Lloc;
     int rc;
-    if (h->debug_keep) {
-        if ((rc = launch_rowsum(h, r, &rs))) return rc;
-        if ((rc = save_tap(h, "srow" + std::to_string(k), rs.p, (size_t)B * P * SROW))) return rc;
-    }
-    {
-        RowFinArgs a{rs.p, w.mrow, reinterpret_cast<frag_t*>(w.mfrag),
-                     d.row_woT, d.row_bv, d.row_bo, d.col_bo,
-                     B * P, rs.nparts, (float)r.L_total, rs.flat, P, Lloc, r.tp.slots_aln, 1};
-        // enough blocks to fill the chip a few times over (8 x 256-thread blocks per CU), each amortising its
-        // out_proj weights over `iters` groups of four pairs
-        const int groups = (B * P + 3) / 4;
-        a.iters = std::max(1, std::min(16, groups / (4 * 8 * std::max(1, h->prop.multiProcessorCount))));
-        a.rq = w.rq;
-        // q' / mean(q') can reach L_total: past 16,384 sites the B side of the row mix is scaled down by a power of
-        // two and the base matrix up (pf_device.hip.h, "fp16 operand ranges"); exact, and 1 for every usual shape
-        a.b_scale = 1.f;
-        for (long lim = 16384; lim < (long)r.L_total && a.b_scale > 1.f / 256.f; lim *= 2) a.b_scale *= 0.5f;
-        a.a_scale = 1.f / a.b_scale;
-        a.wst = r.d_wst;                  // weighted: W and the scales per alignment (k_weight_sums) instead
-        ProfScope ps(h, K_ROWFIN);
-        hipLaunchKernelGGL(k_rowfin, dim3((groups + a.iters - 1) / a.iters), dim3(256), 0, h->cur, a);
-        HIPCHK(h, hipGetLastError());
-    }
-    {
-        ColStatsArgs a{w.x, w.qrow, w.mrow, w.qcol, w.part, d.col_wqk, d.col_bqk, d.row_bo, B, P, Lloc, w.G, (Lloc + 31) / 32,
-                       w.sub, w.S, w.fine, h->table, r.d_idx, h->pair_i, h->pair_j, r.N, w.ulist, w.ucount};
-        ProfScope ps(h, K_COLSTATS);
-        const unsigned nblk = (unsigned)(B * a.nchunks * w.nparts());
-        if (k == 0 && x0_on_the_fly(h))
-            hipLaunchKernelGGL((k_colstats<true, 0, 16>), dim3(nblk), dim3(256), 0, h->cur, a);
-        else if (h->colstats_ring)
-            hipLaunchKernelGGL((k_colstats<false, PF_CS_RING, PF_CS_MT>), dim3(nblk), dim3(256), 0, h->cur, a);
-        else
-            hipLaunchKernelGGL((k_colstats<false, 0, 16>), dim3(nblk), dim3(256), 0, h->cur, a);
-        HIPCHK(h, hipGetLastError());
-    }
-    {
-        ColFinArgs a{w.part, w.ctx, d.col_wvT, d.col_bv, B, Lloc, w.G, (float)P, P, w.sub, w.S, w.fine, w.srep};
-        ProfScope ps(h, K_COLFIN);
-        hipLaunchKernelGGL(k_colfin, dim3(B * Lloc), dim3(COLFIN_THREADS), 0, h->cur, a);
-        HIPCHK(h, hipGetLastError());
-    }
-    if (h->debug_keep) {
-        if ((rc = save_tap(h, "ctx" + std::to_string(k), w.ctx, (size_t)B * Lloc * 64))) return rc;
-        if ((rc = save_tap(h, "mrow" + std::to_string(k), w.mrow, (size_t)B * P * MROW))) return rc;
-    }
-    MainArgs m = main_args(h, r);
-    m.wimg = reinterpret_cast<const frag_t*>(d.wimg);
-    m.consts = d.consts;
-    // a routed run's two or three launches per block stand between ONE pair of events: pf_profile_get("main") keeps
-    // counting one launch per block and run, its time is the block's
-    const int* plan = r.routed ? w.plan : nullptr;
-    const int kid = plan ? -1 : K_MAIN;
-    {
-    ProfScope ps(h, plan ? K_MAIN : -1);
-    if (k + 1 < h->n_blocks) {
-        m.wv_lo = reinterpret_cast<const frag_t*>(h->blk[k + 1].wv_lo);
-        const bool first = k == 0 && x0_on_the_fly(h);
-        if (plan) rc = first ? launch_main_routed<MODE_MID0>(h, m, plan) : launch_main_routed<MODE_MID>(h, m, plan);
-        else if (r.d_w) rc = first ? launch_main<MODE_MID0, false, true>(h, m, K_MAIN) : launch_main<MODE_MID, false, true>(h, m, K_MAIN);
-        else rc = first ? launch_main<MODE_MID0>(h, m, K_MAIN) : launch_main<MODE_MID>(h, m, K_MAIN);
-        if (rc) return rc;
-    } else {
-        m.wv_lo = nullptr;
-        if (h->phase_prof_last) m.prof = h->phase_prof;
-        m.sitemap = r.d_smap;
-        if (!h->head_fold) {
-            // (under the debug taps this launch also writes x of every site: all alignments through the fused launch)
-            if ((rc = r.d_w      ? launch_main<MODE_LAST, false, true>(h, m, K_MAIN)
-                      : r.d_smap ? launch_main<MODE_LAST, true>(h, m, K_MAIN)
-                      : plan && !h->debug_keep ? launch_main_routed<MODE_LAST>(h, m, plan) : launch_main<MODE_LAST>(h, m, kid))) return rc;
-        } else {
-            if ((rc = r.d_w      ? launch_main<MODE_LAST_FOLD, false, true>(h, m, K_MAIN)
-                      : r.d_smap ? launch_main<MODE_LAST_FOLD, true>(h, m, K_MAIN)
-                      : plan     ? launch_main_routed<MODE_LAST_FOLD>(h, m, plan) : launch_main<MODE_LAST_FOLD>(h, m, K_MAIN)))
-                return rc;
-            if (h->debug_keep) {
-                // the folded head never forms x6: the full FFN writes it for the tap (in place, after the folded
-                // launch has read x5), its head sums go to spart, dead since k_rowfin - the distances stay the folded ones
-                MainArgs md = m;
-                md.outpart = w.spart;
-                md.prof = nullptr;
-                if ((rc = r.d_w ? launch_main<MODE_LAST, false, true>(h, md, K_MAIN) : launch_main<MODE_LAST>(h, md, kid))) return rc;
-            }
-        }
-    }
-    }
-    if (h->debug_keep && (rc = save_tap(h, "x" + std::to_string(k + 1), w.x, (size_t)B * P * Lloc * 64))) return rc;
+    if (h->debug_keep && ((rc = launch_rowsum(h, r, &rs)) || (rc = save_tap(h, "srow" + tag, rs.p, pairs * SROW)))) return rc;
+    if ((rc = launch_rowfin(h, r, k, rs))) return rc;
+    if ((rc = launch_colstats(h, r, k))) return rc;
+    if ((rc = launch_colfin(h, r, k))) return rc;
+    if (h->debug_keep && ((rc = save_tap(h, "ctx" + tag, r.w.ctx, sites * 64)) || (rc = save_tap(h, "mrow" + tag, r.w.mrow, pairs * MROW)))) return rc;
+    if ((rc = launch_block_main(h, r, k))) return rc;
+    if (h->debug_keep) return save_tap(h, "x" + std::to_string(k + 1), r.w.x, pairs * r.Lloc * 64);
     return PF_OK;
 }
 
@@ -1007,8 +1004,8 @@ int schedule(pf_handle* h, ShardRun* runs, size_t nruns, Reduce reduce) {
     int rc;
     for (ShardRun* r = runs; r != end; ++r) {
         h->cur = r->stream;
-        if ((rc = launch_site_classes(h, r->d_idx, r->B, r->N, r->Lloc, r->w.srep, r->w.ulist, r->w.ucount,
-                                      r->routed ? r->w.plan : nullptr, r->P))) return rc;
+        const SiteClassArgs sc{r->d_idx, r->w.srep, r->w.ulist, r->w.ucount, r->N, r->Lloc, h->site_dedup ? 1 : 0};
+        if ((rc = launch_site_classes(h, sc, r->B, r->routed ? r->w.plan : nullptr, r->P))) return rc;
         if (h->debug_keep && (rc = save_route_taps(h, *r))) return rc;
         if ((rc = phase_first(h, *r))) return rc;
         r->rs = first_stats(h, *r);
@@ -1049,11 +1046,9 @@ int forward_chunk(pf_handle* h, const uint8_t* d_idx, int B, int N, int Lloc, in
     int b0 = 0;
     for (int i = 0; i < nh; ++i) {
         const int nb = (nh == 2) ? (i == 0 ? (B + 1) / 2 : B / 2) : B;
-        r[i] = ShardRun{{}, d_idx + (size_t)b0 * N * Lloc, d_out + (size_t)b0 * P, nb, N, P, Lloc, L_total,
-                        tile_plan(h, P, Lloc), h->stream, {}};
-        if (d_smap) r[i].d_smap = d_smap + (size_t)b0 * P * Lloc;
-        if (d_w) { r[i].d_w = d_w + (size_t)b0 * Lloc; r[i].d_wst = d_wst + (size_t)b0 * pfw::WST; }
-        r[i].routed = routes_main(h, r[i]);
+        r[i] = shard_run(h, d_idx + (size_t)b0 * N * Lloc, d_out + (size_t)b0 * P, nb, N, Lloc, L_total,
+                         d_smap ? d_smap + (size_t)b0 * P * Lloc : nullptr, d_w ? d_w + (size_t)b0 * Lloc : nullptr,
+                         d_w ? d_wst + (size_t)b0 * pfw::WST : nullptr);
         if ((rc = ensure_workspace(h, nb, P, Lloc, &r[i].w, i == 1))) return rc;
         b0 += nb;
     }
@@ -1167,14 +1162,13 @@ int check_dims(pf_handle* h, int B, int N, int Lloc, int L_total) {
 // buffers per alignment, not the 32 of a whole-group walk).  Every rank derives the same number: it depends on
 // the shape, the options and the largest shard only.
 size_t chunk_bytes(const pf_handle* h, int cb, int P, int Lloc) {
-    size_t off[WS_BUFS];
     const int nh = halves_of(h, cb);
     const int b0 = nh == 2 ? (cb + 1) / 2 : cb, b1 = nh == 2 ? cb / 2 : 0;
     size_t total = 0;
     for (int nb : {b0, b1}) {
         if (nb < 1) continue;
         Workspace w;
-        total += workspace_bytes(h, nb, P, Lloc, &w, off);
+        total += pfspan::measure(workspace_list(h, w, nb, P, Lloc), 256);
     }
     return total;
 }
@@ -2577,37 +2571,14 @@ static int open_device(int device, pf_handle** out) {
         // Kernels that need more than the default 64 KB of dynamic LDS: the attribute is set here, once per
         // handle and before any launch, so that no launch path carries mutable state shared between handles
         // (the CLI drives two engines per GPU from two host threads).
-        const struct { const void* fn; int bytes; } big_lds[] = {
-            {reinterpret_cast<const void*>(&k_main<MODE_FIRST, false>), MAIN_LDS_BYTES},
-            {reinterpret_cast<const void*>(&k_main<MODE_MID, false>), MAIN_LDS_BYTES},
-            {reinterpret_cast<const void*>(&k_main<MODE_MID0, false>), MAIN_LDS_BYTES},
-            {reinterpret_cast<const void*>(&k_main<MODE_LAST, false>), MAIN_LDS_BYTES},
-            {reinterpret_cast<const void*>(&k_main<MODE_LAST_FOLD, false>), MAIN_LDS_BYTES},
-            {reinterpret_cast<const void*>(&k_main<MODE_FIRST, true>), MAIN_LDS_BYTES},
-            {reinterpret_cast<const void*>(&k_main<MODE_MID, true>), MAIN_LDS_BYTES},
-            {reinterpret_cast<const void*>(&k_main<MODE_MID0, true>), MAIN_LDS_BYTES},
-            {reinterpret_cast<const void*>(&k_main<MODE_LAST, true>), MAIN_LDS_BYTES},
-            {reinterpret_cast<const void*>(&k_main<MODE_LAST_FOLD, true>), MAIN_LDS_BYTES},
-            {reinterpret_cast<const void*>(&k_main<MODE_LAST, false, true>), MAIN_LDS_BYTES},
-            {reinterpret_cast<const void*>(&k_main<MODE_LAST_FOLD, false, true>), MAIN_LDS_BYTES},
-            {reinterpret_cast<const void*>(&k_main<MODE_LAST, true, true>), MAIN_LDS_BYTES},
-            {reinterpret_cast<const void*>(&k_main<MODE_LAST_FOLD, true, true>), MAIN_LDS_BYTES},
-            {reinterpret_cast<const void*>(&k_main<MODE_MID, false, false, true>), MAIN_LDS_BYTES},
-            {reinterpret_cast<const void*>(&k_main<MODE_MID0, false, false, true>), MAIN_LDS_BYTES},
-            {reinterpret_cast<const void*>(&k_main<MODE_LAST, false, false, true>), MAIN_LDS_BYTES},
-            {reinterpret_cast<const void*>(&k_main<MODE_LAST_FOLD, false, false, true>), MAIN_LDS_BYTES},
-            {reinterpret_cast<const void*>(&k_main<MODE_MID, true, false, true>), MAIN_LDS_BYTES},
-            {reinterpret_cast<const void*>(&k_main<MODE_MID0, true, false, true>), MAIN_LDS_BYTES},
-            {reinterpret_cast<const void*>(&k_main<MODE_LAST, true, false, true>), MAIN_LDS_BYTES},
-            {reinterpret_cast<const void*>(&k_main<MODE_LAST_FOLD, true, false, true>), MAIN_LDS_BYTES},
-            {reinterpret_cast<const void*>(&k_embed<false>), EMBED_LDS_BYTES},
-            {reinterpret_cast<const void*>(&k_embed<true>), EMBED_LDS_BYTES},
-        };
-        for (const auto& k : big_lds)
-            if ((e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.bytes)) != hipSuccess) {
+        auto big_lds = [&](const void* fn, int bytes) {
+            if (!rc && (e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes)) != hipSuccess)
                 rc = fail(nullptr, PF_EHIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-                break;
-            }
+        };
+        for (const MainRow& r : main_kernels())       // (k_main over every alignment; the routed launches run without it)
+            if (r.kind.route == ROUTE_ALL) big_lds(reinterpret_cast<const void*>(r.fn), MAIN_LDS_BYTES);
+        big_lds(reinterpret_cast<const void*>(&k_embed<false>), EMBED_LDS_BYTES);
+        big_lds(reinterpret_cast<const void*>(&k_embed<true>), EMBED_LDS_BYTES);
         if (rc) break;
     } while (0);
     if (rc) { pf_destroy(h); return rc; }
@@ -3039,7 +3010,7 @@ int pf_site_classes(pf_handle_t* h, const uint8_t* idx, int32_t B, int32_t N, in
     HIPCHK(h, hipMemcpyAsync(h->d_idx, idx, nidx, hipMemcpyHostToDevice, h->stream));
     int32_t* d = h->d_map;
     h->cur = h->stream;
-    if ((rc = launch_site_classes(h, h->d_idx, B, N, L, d, d + nsite, d + 2 * nsite))) return rc;
+    if ((rc = launch_site_classes(h, SiteClassArgs{h->d_idx, d, d + nsite, d + 2 * nsite, N, L, h->site_dedup ? 1 : 0}, B))) return rc;
     HIPCHK(h, hipMemcpyAsync(srep, d, nsite * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(ucount, d + 2 * nsite, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -3333,13 +3304,12 @@ int pf_forward_shards_emulated(pf_handle_t* h, const uint8_t* idx, int32_t B, in
     if ((rc = stage.upload(idx, B, N, L, nshards))) return rc;
     std::vector<ShardRun> runs;
     for (const ShardStage::Shard& s : stage.shards) {
-        ShardRun r{{}, s.d_idx, nullptr, B, N, P, s.Lloc, L, tile_plan(h, P, s.Lloc), h->stream, {}};
-        size_t off[WS_BUFS];
-        char* ws = (char*)stage.alloc(workspace_bytes(h, B, P, r.Lloc, &r.w, off));
+        ShardRun r = shard_run(h, s.d_idx, nullptr, B, N, s.Lloc, L);
+        auto list = workspace_list(h, r.w, B, P, s.Lloc);
+        char* ws = (char*)stage.alloc(pfspan::measure(list, 256));
         r.d_out = (float*)stage.alloc((size_t)B * P * sizeof(float));
         if (!ws || !r.d_out) return fail(h, PF_ENOMEM, "shard workspace allocation failed");
-        carve_workspace(ws, off, &r.w, B, r.Lloc);
-        r.routed = routes_main(h, r);
+        pfspan::carve(ws, list, 256);
         runs.push_back(r);
     }
     // the "all-reduced" buffer every emulated rank reads
