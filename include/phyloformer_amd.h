@@ -122,6 +122,9 @@ const char* pf_last_error(const pf_handle_t* h);
  *   "delta_atomic" int 0 = pf_delta evaluates every quartet six times, once for each of its pairs, without atomics
  *                      on the pair sums, instead of once with LDS and global atomics (default 1): the same integers;
  *                      the comparison of tools/delta_bench.py
+ *   "fit_lds_bytes" int bytes of LDS in which pf_tree_fit's pair kernel may stage a tree's node arrays (12 bytes a node);
+ *                      <= 0 (default): the 163,840 of a CU, N <= 6,827; a tree above it is read from global memory: the
+ *                      same bits; tests
  *   "spr_step_cap" int moves after which pf_bme_spr caps a source (status 2); <= 0 (default): 16 N; tests
  *   "colstats_fine" int k_colstats blocks per pair group (0), per run of a group (1) or chosen from the batch
  *                      size (-1, default): the same summation tree either way, so the same bits; tests/tools
@@ -441,6 +444,40 @@ int pf_delta(pf_handle_t* h, const float* preds, int32_t B, int32_t N, int32_t K
 int pf_delta_device(pf_handle_t* h, const float* d_preds, int32_t B, int32_t N, int32_t K, int64_t* d_pair_sum, int64_t* d_hist,
                     uint8_t* d_nonfinite);
 int pf_delta_host(const float* preds, int32_t B, int32_t N, int32_t K, int64_t* pair_sum, int64_t* hist, uint8_t* nonfinite);
+
+/* ---- tree fit: how well a tree reproduces the distances it was built from (additive to ABI 5) ----
+ *
+ * The path-length (patristic) distances of join tables (cophenetic.phylo of R's ape) and the sums of their residuals
+ * against the source's distances, bit for bit those of phyloformer_amd/fit.py::tree_fit_py.  A tree is a join table in
+ * pf_nj_joins' layout, whichever of pf_nj_joins, pf_bionj_joins, pf_bme_nni and pf_bme_spr made it; its lengths are taken as
+ * they are (a negative one is not clamped).  Leaves are nodes 0 .. N-1, join t makes node N + t, node 2N - 3 is the parent of
+ * the last three.  T[x, y] = up(x) + up(y), each the float64 sum of the branches from the leaf up to, not beyond, the lowest
+ * common node, added one after the other from +0.0.  e = (double)pred - T.  Per sequence i over j != i: ss = sum e e, fm =
+ * sum (e e) / (d d) (0 where d <= 0), st = sum T, stt = sum T T, sdt = sum d T, worst = max |e| and its j (ties: the
+ * smallest), summed in 64 strided accumulators that are combined pairwise at distances 32, 16, ... 1: the order is part of
+ * the definition (csrc/pf_fit.hip.h, csrc/pf_fit_host.h).
+ *   preds     float  [B][P_N]        pf_forward's distances, pairs i < j in lexicographic order
+ *   slots     int32  [B][M][T]       M join tables per source, T = 2 (N - 3) + 3
+ *   lengths   double [B][M][T]
+ *   patristic double [B][M][P_N]     the tree's distances in preds' pair order; or NULL: they are kept per chunk of trees in the
+ *                                    handle's workspace only (option "ws_limit_mb")
+ *   rows      double [B][M][N][6]    ss, fm, st, stt, sdt, worst of every sequence
+ *   worst_j   int32  [B][M][N]
+ *   status    uint8  [B][M]          0 fine; 1 a NaN or an infinity in the source's distances or the tree's lengths; 2 no join
+ *                                    table (a slot outside [0, N), a slot joined after it left, a == b; checked first).  A
+ *                                    tree with a status has zeros everywhere and is walked by no kernel
+ * pf_tree_fit takes host arrays and is synchronous; pf_tree_fit_device takes device arrays and is asynchronous on the
+ * handle's stream; pf_tree_fit_host is the serial twin, without a handle or a device.  One call with B sources equals B
+ * calls with one.  The node arrays of a tree (12 bytes a node) are staged in LDS up to N = 6,827 and read from global memory
+ * above (option "fit_lds_bytes" lowers the switch).  Refused with PF_EINVAL before any device work, the message naming the
+ * value: N < 3; N > 8,192; B < 1; M < 1; P_N >= 2^31; NULL buffers other than patristic; a tree's state above the workspace
+ * limit.  pf_profile_get("tree_fit") counts the calls of the two handle entry points. */
+int pf_tree_fit(pf_handle_t* h, const float* preds, const int32_t* slots, const double* lengths, int32_t B, int32_t M, int32_t N,
+                double* patristic, double* rows, int32_t* worst_j, uint8_t* status);
+int pf_tree_fit_device(pf_handle_t* h, const float* d_preds, const int32_t* d_slots, const double* d_lengths, int32_t B, int32_t M,
+                       int32_t N, double* d_patristic, double* d_rows, int32_t* d_worst_j, uint8_t* d_status);
+int pf_tree_fit_host(const float* preds, const int32_t* slots, const double* lengths, int32_t B, int32_t M, int32_t N, double* patristic,
+                     double* rows, int32_t* worst_j, uint8_t* status);
 
 /* ---- balanced minimum-evolution NNI refinement of a join table (additive to ABI 5) ----
  *

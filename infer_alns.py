@@ -20,7 +20,8 @@ not parse, has the reference's side effects (infer_alns.py:97-117): every entry 
 (in ``glob`` order, as there) gets its output, nothing behind it does, then the reference's
 exception is raised.  ``--delta`` (``phyloformer_amd/delta.py``) is no mode of its own: it asks of every launch's
 distances, whichever mode made them, how tree-like they are, and writes ``<stem>.delta.tsv``, ``<stem>.delta.phy`` and
-``<stem>.delta.hist.tsv``.  The multi-GPU modes, which have no counterpart, refuse such a directory up front.
+``<stem>.delta.hist.tsv``.  ``--fit`` (``phyloformer_amd/fit.py``) asks of every tree a run with ``-t`` writes how well it
+reproduces those distances: ``<stem>.fit.tsv`` and, per tree, ``<stem>.fit.taxa.tsv`` and ``<stem>.patristic.phy``.  The multi-GPU modes, which have no counterpart, refuse such a directory up front.
 The forward pass runs in ``libphyloformer_amd.so``; there is no CPU fallback.
 """
 import argparse
@@ -67,6 +68,15 @@ def build_parser():
                              "delta, a PHYLIP matrix) and <stem>.delta.hist.tsv (quartets per 20 bins of delta); 0 = the "
                              "distances of a tree; with or without -t and with every analysis; at most 2,048 sequences; every "
                              "other output keeps its bytes")
+    parser.add_argument("--fit", action="store_true",
+                        help="with -t: how well every written tree reproduces the distances it was built from - the NJ tree and "
+                             "those of --bme, --spr and --bionj.  Writes <stem>.fit.tsv (one line per tree: the RMS residual "
+                             "between the distances and the tree's path lengths, the explained variance as FastME reports it, "
+                             "the Fitch-Margoliash sum, the cophenetic correlation, the worst pair and its residual) and, per "
+                             "tree, <stem>.fit.taxa.tsv (per sequence its RMS residual, and that over the mean) and "
+                             "<stem>.patristic.phy (the tree's path-length distances, cophenetic.phylo of R's ape, a PHYLIP "
+                             "matrix); another tree's name stands before the ending (<stem>.bme.fit.taxa.tsv).  Negative branch "
+                             "lengths count as they are; up to 8,192 sequences; every other output keeps its bytes")
     parser.add_argument("--device", type=int, default=0, help="HIP device ordinal (default 0)")
     parser.add_argument("--devices", default=None,
                         help="comma-separated HIP device ordinals: shard the files over these GPUs, "
@@ -110,6 +120,10 @@ def main(argv=None):
     from phyloformer_amd import scheduler
     if args.delta and args.shard == "sites":
         parser.error(scheduler.DELTA_SHARD_SITES)
+    if args.fit and not args.trees:
+        parser.error(scheduler.FIT_NEEDS_TREES)
+    if args.fit and args.shard == "sites":
+        parser.error(scheduler.FIT_SHARD_SITES)
 
     in_dir = os.path.abspath(args.alndir)
     out_dir = os.path.abspath(args.outdir)  # TypeError if omitted, as in the reference (:90)
@@ -185,7 +199,7 @@ def main(argv=None):
     runner = scheduler.DirectoryRunner(engines, out_dir, trees=args.trees, batch=args.batch,
                                        io_threads=args.io_threads, native_io=not args.python_io,
                                        progress=bar.update if bar is not None else None, modes=modes, bme=args.bme, spr=args.spr,
-                                       bionj=args.bionj, delta=args.delta)
+                                       bionj=args.bionj, delta=args.delta, fit=args.fit)
     try:
         stats = runner.run(paths)
     finally:

@@ -27,6 +27,7 @@
 #include "pf_bme_host.h"
 #include "pf_bionj_host.h"
 #include "pf_delta_host.h"
+#include "pf_fit_host.h"
 #include "pf_support_host.h"
 #include "pf_consensus_host.h"
 
@@ -952,6 +953,23 @@ int pf_delta_host(const float* preds, int32_t B, int32_t N, int32_t K, int64_t* 
     for (int32_t b = 0; b < B; ++b)
         pfdelta::run_serial(preds + (size_t)b * P, N, K, pair_sum + (size_t)b * P, hist + (size_t)b * (size_t)K, nonfinite + b);
     return PF_OK;
+}
+
+// Tree fit without a device: every tree of every source serially - the same arrays as pf_tree_fit,
+// bit for bit.  Twin of phyloformer_amd/fit.py::tree_fit_py.  A tree with a status has zeros everywhere.
+int pf_tree_fit_host(const float* preds, const int32_t* slots, const double* lengths, int32_t B, int32_t M, int32_t N, double* patristic,
+                     double* rows, int32_t* worst_j, uint8_t* status) {
+    if (!preds || !slots || !lengths || !rows || !worst_j || !status || pffit::refused(B, M, N)) return PF_EINVAL;
+    try {
+        const size_t n = (size_t)N, P = n * (n - 1) / 2, T = (size_t)pffit::table_len(N);
+        for (size_t b = 0; b < (size_t)B; ++b)
+            for (size_t m = 0; m < (size_t)M; ++m) {
+                const size_t item = b * (size_t)M + m;
+                pffit::run_serial(preds + b * P, slots + item * T, lengths + item * T, N, patristic ? patristic + item * P : nullptr,
+                                  rows + item * n * pffit::COLS, worst_j + item * n, status + item);
+            }
+        return PF_OK;
+    } catch (...) { return PF_ENOMEM; }
 }
 
 // preds [n(n-1)/2] -> Newick text of the BIONJ tree, as bionj.py::bionj_newick_py writes it: pf_bionj_joins_host's table

@@ -51,6 +51,7 @@
 #include "pf_nj.hip.h"
 #include "pf_bionj.hip.h"
 #include "pf_delta.hip.h"
+#include "pf_fit.hip.h"
 #include "pf_bme.hip.h"
 #include "pf_support.hip.h"
 #include "pf_consensus.hip.h"
@@ -271,6 +272,11 @@ struct pf_handle {
     Buffer<char> d_delta_io{buffers};
     int64_t delta_calls = 0;     // pf_delta / pf_delta_device calls since the last pf_profile_reset ("delta")
     bool delta_atomic = true;    // option "delta_atomic": 0 = k_delta_pairs (the comparison of tools/delta_bench.py)
+    // pf_tree_fit / pf_tree_fit_device (grow-only): the node arrays (and, without the caller's patristic, the tree's
+    // distances) of one chunk of trees, and the staging of the host entry point's arrays
+    Buffer<char> d_fit{buffers}, d_fit_io{buffers};
+    int64_t fit_calls = 0;       // pf_tree_fit / pf_tree_fit_device calls since the last pf_profile_reset ("tree_fit")
+    int64_t fit_lds_bytes = pffit::LDS_MAX_BYTES;   // option "fit_lds_bytes": what k_fit_pairs may stage in LDS; tests
     // pf_bme_nni / pf_bme_nni_device (grow-only): the state of one chunk of sources (pf_bme.hip.h: carve) and the
     // staging of the host entry point's distances
     Buffer<char> d_bme{buffers};
@@ -2209,6 +2215,59 @@ int delta_impl(pf_handle* h, bool device, const pfdelta::Tables& user, int B, in
     return staged_call(h, h->d_delta_io, list, [&] { return launch(io); });
 }
 
+// ---- tree fit on the device (pf_tree_fit, pf_tree_fit_device; pf_fit.hip.h, pf_fit_host.h) ----
+
+// The caller's arrays on the device (asynchronous) or on the host (staged, one synchronisation).  The items - the B M
+// trees - are cut into chunks whose node arrays (and, where the caller keeps no patristic, whose distances) fit
+// "ws_limit_mb" side by side; the chunks follow each other on the stream and reuse the workspace.
+int fit_impl(pf_handle* h, bool device, const pffit::Tables& user, int B, int M, int N) {
+    pffit::Tables io{};
+    auto list = [&](auto& v) { pffit::staging_arrays(v, io, user, (size_t)std::max(B, 0), (size_t)std::max(M, 0), N); };
+    if (pfspan::missing(list)) return fail(h, PF_EINVAL, "null buffer");
+    switch (pffit::refused(B, M, N)) {
+        case 1: return fail(h, PF_EINVAL, "tree fit needs N >= %d sequences (got %d)", pffit::MIN_N, N);
+        case 2: return fail(h, PF_EINVAL, "tree fit takes at most %d sequences (got %d)", pffit::MAX_N, N);
+        case 3: return fail(h, PF_EINVAL, "tree fit needs B >= 1 sources (got %d)", B);
+        case 4: return fail(h, PF_EINVAL, "tree fit needs M >= 1 trees per source (got %d)", M);
+        case 5: return fail(h, PF_EINVAL, "N=%d sequences have 2^31 pairs or more", N);
+    }
+    const int64_t P = (int64_t)N * (N - 1) / 2, items = (int64_t)B * M;
+    size_t n = 0;
+    if (!mul_size((size_t)items, (size_t)P, sizeof(double), &n) || !mul_size((size_t)items, (size_t)N, pffit::COLS * sizeof(double), &n))
+        return fail(h, PF_EINVAL, "B=%d sources of M=%d trees of N=%d sequences overflow the address space", B, M, N);
+    const size_t per = pffit::state_bytes(N, !user.patristic);
+    if ((int64_t)per > h->ws_limit_bytes)
+        return fail(h, PF_EINVAL, "tree fit of N=%d sequences needs %zu bytes of state per tree (its node arrays%s), above the workspace "
+                                  "limit of %lld bytes (option ws_limit_mb)", N, per, user.patristic ? "" : " and its distances",
+                    (long long)h->ws_limit_bytes);
+    const int chunk = (int)std::min<int64_t>(std::min(items, pffit::max_items(N)), (int64_t)((size_t)h->ws_limit_bytes / per));
+    HIPCHK(h, hipSetDevice(h->device));
+    ++h->fit_calls;
+    auto launch = [&](const pffit::Tables& d) -> int {
+        const int rc = h->d_fit.reserve(h, (size_t)chunk * per);
+        if (rc) return rc;
+        h->cur = h->stream;
+        // (a tree with a status is walked by no kernel: its results are these zeros)
+        if (d.patristic) HIPCHK(h, hipMemsetAsync(d.patristic, 0, (size_t)items * (size_t)P * sizeof(double), h->stream));
+        HIPCHK(h, hipMemsetAsync(d.rows, 0, (size_t)items * (size_t)N * pffit::COLS * sizeof(double), h->stream));
+        HIPCHK(h, hipMemsetAsync(d.worst_j, 0, (size_t)items * (size_t)N * sizeof(int32_t), h->stream));
+        pffit::Args a{};
+        a.preds = d.preds; a.slots = d.slots; a.lengths = d.lengths;
+        a.rows = d.rows; a.worst_j = d.worst_j; a.status = d.status;
+        a.P = P; a.N = N; a.M = M;
+        for (int64_t item0 = 0; item0 < items; item0 += chunk) {
+            a.item0 = item0; a.nb = (int)std::min<int64_t>(chunk, items - item0);
+            pffit::carve(a, h->d_fit, a.nb, !d.patristic);
+            if (d.patristic) a.tree = d.patristic + (size_t)item0 * (size_t)P;
+            const hipError_t e = pffit::launch_chunk(h->stream, a, (int)h->fit_lds_bytes);
+            if (e != hipSuccess) return fail(h, PF_EHIP, "k_fit_* launch failed: %s", hipGetErrorString(e));
+        }
+        return PF_OK;
+    };
+    if (device) return launch(user);
+    return staged_call(h, h->d_fit_io, list, [&] { return launch(io); });
+}
+
 // ---- balanced NNI refinement on the device (pf_bme_nni, pf_bme_nni_device; pf_bme.hip.h, pf_bme_host.h) ----
 
 // every start table is a join table (slots in [0, N), every join of two live clusters, three distinct live slots last)
@@ -2579,6 +2638,8 @@ static int open_device(int device, pf_handle** out) {
             if (r.kind.route == ROUTE_ALL) big_lds(reinterpret_cast<const void*>(r.fn), MAIN_LDS_BYTES);
         big_lds(reinterpret_cast<const void*>(&k_embed<false>), EMBED_LDS_BYTES);
         big_lds(reinterpret_cast<const void*>(&k_embed<true>), EMBED_LDS_BYTES);
+        big_lds(reinterpret_cast<const void*>(&pffit::k_fit_setup), pffit::SETUP_LDS_MAX);
+        big_lds(reinterpret_cast<const void*>(&pffit::k_fit_pairs<true>), pffit::LDS_MAX_BYTES);
         if (rc) break;
     } while (0);
     if (rc) { pf_destroy(h); return rc; }
@@ -2686,6 +2747,7 @@ int pf_set_option(pf_handle_t* h, const char* key, int64_t value) {
     else if (k == "ws_limit_mb") h->ws_limit_bytes = value << 20;
     else if (k == "spr_pairs_simple") h->spr_pairs_simple = value != 0;
     else if (k == "delta_atomic") h->delta_atomic = value != 0;
+    else if (k == "fit_lds_bytes") h->fit_lds_bytes = value > 0 ? std::min<int64_t>(value, pffit::LDS_MAX_BYTES) : pffit::LDS_MAX_BYTES;
     else if (k == "spr_step_cap") h->spr_step_cap = value > 0 ? value : 0;
     else if (k == "sub_floats") h->sub_floats = value > 0 ? value : SUB_FLOATS_DEFAULT;
     else return fail(h, PF_EINVAL, "unknown option '%s'", key);
@@ -2876,6 +2938,18 @@ int pf_delta_device(pf_handle_t* h, const float* d_preds, int32_t B, int32_t N, 
                     uint8_t* d_nonfinite) {
     if (!h) return PF_EINVAL;
     return delta_impl(h, true, {d_preds, d_pair_sum, d_hist, d_nonfinite}, B, N, K);
+}
+
+int pf_tree_fit(pf_handle_t* h, const float* preds, const int32_t* slots, const double* lengths, int32_t B, int32_t M, int32_t N,
+                double* patristic, double* rows, int32_t* worst_j, uint8_t* status) {
+    if (!h) return PF_EINVAL;
+    return fit_impl(h, false, {preds, slots, lengths, patristic, rows, worst_j, status}, B, M, N);
+}
+
+int pf_tree_fit_device(pf_handle_t* h, const float* d_preds, const int32_t* d_slots, const double* d_lengths, int32_t B, int32_t M,
+                       int32_t N, double* d_patristic, double* d_rows, int32_t* d_worst_j, uint8_t* d_status) {
+    if (!h) return PF_EINVAL;
+    return fit_impl(h, true, {d_preds, d_slots, d_lengths, d_patristic, d_rows, d_worst_j, d_status}, B, M, N);
 }
 
 int pf_bme_nni(pf_handle_t* h, const float* preds, const int32_t* start_slots, int32_t B, int32_t N, int32_t* slots, double* lengths,
@@ -3171,6 +3245,7 @@ int pf_profile_reset(pf_handle_t* h) {
     h->nj_calls = 0;
     h->bionj_calls = 0;
     h->delta_calls = 0;
+    h->fit_calls = 0;
     h->bme_calls = 0;
     h->spr_calls = 0;
     h->sup_calls = 0;
@@ -3204,6 +3279,11 @@ int pf_profile_get(pf_handle_t* h, const char* kernel, int64_t* launches, double
     }
     if (std::strcmp(kernel, "delta") == 0) {            // pf_delta / pf_delta_device calls
         if (launches) *launches = h->delta_calls;
+        if (total_ms) *total_ms = 0.0;
+        return PF_OK;
+    }
+    if (std::strcmp(kernel, "tree_fit") == 0) {         // pf_tree_fit / pf_tree_fit_device calls
+        if (launches) *launches = h->fit_calls;
         if (total_ms) *total_ms = 0.0;
         return PF_OK;
     }

@@ -139,6 +139,12 @@ SIGNATURES = {
     "pf_delta": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pf_delta_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pf_delta_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pf_tree_fit": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.c_void_p]),
+    "pf_tree_fit_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
+    "pf_tree_fit_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
     "pf_bionj_newick_n": (C.c_int64, [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32, C.c_char_p, C.c_int64]),
     "pf_nj_format_joins_n": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32,
                                          C.c_char_p, C.c_int64]),
@@ -198,7 +204,7 @@ CALL_TIME_SYMBOLS = frozenset({"pf_forward_site_map", "pf_forward_site_map_devic
                                "pf_join_consensus_device", "pf_join_consensus_host", "pf_bionj_joins",
                                "pf_bionj_joins_device", "pf_bionj_joins_host", "pf_bionj_newick_n", "pf_join_transfers",
                                "pf_join_transfers_device", "pf_join_transfers_host", "pf_delta", "pf_delta_device",
-                               "pf_delta_host", "pf_site_classes"})
+                               "pf_delta_host", "pf_site_classes", "pf_tree_fit", "pf_tree_fit_device", "pf_tree_fit_host"})
 
 _lib: Optional[C.CDLL] = None
 
@@ -610,6 +616,28 @@ class Engine:
         [B][bins]``, ``nonfinite uint8 [B]`` (asynchronous on the handle's stream)."""
         self._check(self._optional("pf_delta_device")(self._h, C.c_void_p(d_preds), B, N, bins, C.c_void_p(d_pair_sum),
                                                       C.c_void_p(d_hist), C.c_void_p(d_nonfinite)))
+
+    # -- tree fit ----------------------------------------------------------------------------
+    def tree_fit(self, preds: np.ndarray, slots: np.ndarray, lengths: np.ndarray, patristic: bool = True):
+        """Tree fit on the GPU (``pf_tree_fit``): distances ``float32[B, P_N]`` and join tables ``int32 / float64 [B, M, T]``
+        (``[B, T]``: one tree per source, the results drop ``M``; ``[P_N]`` with ``[M, T]`` or ``[T]`` drops ``B``), ``3 <= N <=
+        8,192`` → ``(patristic float64[B, M, P_N], rows float64[B, M, N, 6], worst_j int32[B, M, N], status uint8[B, M])`` - bit
+        for bit ``fit.tree_fit_py`` of every tree and ``hostio.tree_fit_host``; ``fit.fit_scores`` derives what is reported.
+        ``patristic`` = False: None in its place, the tree's distances stay on the device.  A tree with a status (1: not
+        finite, 2: no join table) has zeros.  ``ValueError`` for what the library refuses."""
+        from .fit import fit_arrays, squeezed
+        fn = self._optional("pf_tree_fit")
+        p, s, l, (B, M, N), flags, out = fit_arrays(preds, slots, lengths, patristic)
+        self._check(fn(self._h, ptr(p), ptr(s), ptr(l), B, M, N, *map(ptr, out)))
+        return squeezed(out, flags)
+
+    def tree_fit_device(self, d_preds: int, d_slots: int, d_lengths: int, B: int, M: int, N: int, d_patristic: int, d_rows: int,
+                        d_worst_j: int, d_status: int):
+        """``pf_tree_fit_device``: device arrays in ``pf_tree_fit``'s layouts (``d_patristic`` 0: none), asynchronous on the
+        handle's stream."""
+        self._check(self._optional("pf_tree_fit_device")(self._h, C.c_void_p(d_preds), C.c_void_p(d_slots), C.c_void_p(d_lengths),
+                                                         B, M, N, C.c_void_p(d_patristic or None), C.c_void_p(d_rows),
+                                                         C.c_void_p(d_worst_j), C.c_void_p(d_status)))
 
     # -- balanced NNI refinement -------------------------------------------------------------
     def bme_nni(self, preds: np.ndarray, start_slots: np.ndarray):

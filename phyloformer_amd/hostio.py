@@ -260,6 +260,15 @@ def delta_host(preds: np.ndarray, n: int = 0, bins: int = 20):
     return unbatched(out, single)
 
 
+def tree_fit_host(preds: np.ndarray, slots: np.ndarray, lengths: np.ndarray, patristic: bool = True):
+    """``Engine.tree_fit`` without a device (``pf_tree_fit_host``), its arguments and results: every tree of every source
+    serially, ``fit.tree_fit_py`` bit for bit.  ``ValueError`` for what the library refuses."""
+    from .fit import fit_arrays, squeezed
+    p, s, l, (b, m, n), flags, out = fit_arrays(preds, slots, lengths, patristic)
+    _check_rc("pf_tree_fit_host", _lib().pf_tree_fit_host(ptr(p), ptr(s), ptr(l), b, m, n, *map(ptr, out)), "N, B or M out of range")
+    return squeezed(out, flags)
+
+
 def _joins_host(symbol: str, preds: np.ndarray, *options):
     p, _, (b, n, _t), _single, (slots, lengths, flag) = tree_call(preds, JOINS, _refuse_joins)
     _check_rc(symbol, getattr(_lib(), symbol)(p.ctypes.data, b, n, *options, ptr(slots), ptr(lengths), ptr(flag)))

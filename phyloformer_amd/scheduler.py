@@ -68,6 +68,9 @@ def auto_batch(n_seqs: int, n_sites: int, max_batch: int = 4096, token_budget: i
 
 # the refusal of --delta with --shard sites, in the wording of treekinds.refusals
 DELTA_SHARD_SITES = "--delta cannot be combined with --shard sites: the site-sharded runner writes distances and NJ trees only"
+# the refusals of --fit, in the wording of treekinds.refusals
+FIT_NEEDS_TREES = "--fit measures the trees of --trees: give -t as well"
+FIT_SHARD_SITES = "--fit cannot be combined with --shard sites: the site-sharded runner writes NJ trees only"
 HEARTBEAT = "#pf-heartbeat"      # stderr line prefix of a site-sharded worker's sign of life (swallowed by the launcher)
 MAX_SEQS = 200     # SEQ2PAIR = seq2pair(200), /root/reference/phyloformer/model.py:39
 
@@ -159,13 +162,18 @@ class DirectoryRunner:
 
     def __init__(self, engine, out_dir: str, trees: bool = False, batch: int = 0,
                  io_threads: int = 4, native_io: bool = True, progress=None, modes: Sequence[Analysis] = (),
-                 bme: bool = False, spr: bool = False, bionj: bool = False, delta: bool = False):
+                 bme: bool = False, spr: bool = False, bionj: bool = False, delta: bool = False, fit: bool = False):
         # with --trees: <stem>.bme.nwk / .spr.nwk / .bionj.nwk (and .bionj.bme.nwk / .bionj.spr.nwk) as well (treekinds.KINDS)
         self.flags = [flag for flag, on in (("--bionj", bionj), ("--bme", bme), ("--spr", spr)) if on]
         if not trees and self.flags:
             raise ValueError(next(refusals(self.flags, trees)))
         self.kind_groups = switched_on(self.flags)
+        if fit and not trees:
+            raise ValueError(FIT_NEEDS_TREES)
         self.delta = delta            # --delta: <stem>.delta.tsv / .delta.phy / .delta.hist.tsv of every launch's distances
+        # --fit: <stem>.fit.tsv and, of every written kind, <stem>[.<kind>].fit.taxa.tsv / .patristic.phy (fit.py)
+        self.fit = fit
+        self._made = threading.local()        # the tables device_tables made on this GPU thread for the launch in hand
         self.engines = list(engine) if isinstance(engine, (list, tuple)) else [engine]
         self.out_dir = out_dir
         self.trees = trees
@@ -182,6 +190,8 @@ class DirectoryRunner:
             self.stats.update({key: 0.0 if key.endswith("_s") else 0 for key in kinds[0].stats})
         if delta:
             self.stats.update({"delta": 0, "delta_s": 0.0})
+        if fit:
+            self.stats.update({"fit": 0, "fit_s": 0.0})
         self.modes = list(modes)
         for m in self.modes:
             m.bind(self.modes)
@@ -208,6 +218,7 @@ class DirectoryRunner:
         out = {k.name: [None if bad else JoinTable(s, l, int(moves)) for s, l, moves, bad in zip(*made[k.search])]
                for k in kinds if k.search is None or k in run}
         self.book(**{f"{head.name}_device": sum(t is not None for t in out[head.name]), f"{head.name}_device_s": time.perf_counter() - t0})
+        getattr(self._made, "tables", {}).update(out)
         return out
 
     def _write_trees(self, group: list, preds: np.ndarray, tables, kind: Kind):
@@ -251,6 +262,64 @@ class DirectoryRunner:
             self.put(e.path, "delta.hist.tsv", D.hist_tsv(hist))
         self.book(delta=len(group))
 
+    def written_kinds(self) -> List[Kind]:
+        """The kinds whose trees a run with ``--trees`` writes, in the order of ``KINDS``."""
+        on = {k.name for kinds in self.kind_groups for k in kinds}
+        return [k for k in KINDS if k is KINDS[0] or k.name in on]
+
+    def fit_arrays(self, engine, n: int, preds: np.ndarray) -> dict:
+        """``--fit`` on the GPU thread: ``Engine.tree_fit`` of the launch's distances on the tables that were made on this
+        thread (``device_tables``), one call for all their kinds, from ``fit.FIT_DEVICE_MIN`` sequences on; a file without
+        a table (distances that are not finite) gets a table of zeros, which is none (status 2).  ``{kind name:
+        (patristic, rows, worst_j, status)}``; the other kinds are the writer thread's.  Books its seconds."""
+        from . import fit as F
+        made = {name: tables for name, tables in getattr(self._made, "tables", {}).items() if tables is not None}
+        if not made or not reaches(F.FIT_DEVICE_MIN, n, F.MIN_SEQS):
+            return {}
+        t0 = time.perf_counter()
+        width = F.table_len(n)
+        slots = np.zeros((len(preds), len(made), width), dtype=np.int32)
+        lengths = np.zeros((len(preds), len(made), width), dtype=np.float64)
+        for m, tables in enumerate(made.values()):
+            for b, table in enumerate(tables):
+                if table is not None:
+                    slots[b, m], lengths[b, m] = table.slots, table.lengths
+        out = engine.tree_fit(preds, slots, lengths)
+        self.book(fit_s=time.perf_counter() - t0)
+        return {name: tuple(a[:, m] for a in out) for m, name in enumerate(made)}
+
+    def _write_fit(self, group: list, preds: np.ndarray, tables: dict, fits: dict):
+        """The files of ``--fit`` of some files of a launch, on a writer thread: of every written kind the GPU thread's
+        arrays where it made them (``fits``), else the twin's on its table - the device's (``tables``) or, as the tree's
+        text was, joined and refined on the host; ``nan`` for fewer than three sequences, distances or lengths that are
+        not finite."""
+        from . import fit as F
+        t0 = time.perf_counter()
+        for k, (e, pred) in enumerate(zip(group, preds)):
+            ids = e.ids()
+            n, lines = len(ids), []
+            for kind in self.written_kinds():
+                arrays = None
+                if kind.name in fits:
+                    arrays = tuple(a[k] for a in fits[kind.name])
+                elif n >= F.MIN_SEQS:
+                    table = tables[kind.name][k] if tables.get(kind.name) is not None else None
+                    if table is None and kind.name not in tables:
+                        search = [kind.search] if kind.search else []
+                        slots, lengths, _steps, bad = join_refine(self.host, kind.start, search, pred[None])[kind.search]
+                        table = None if bad[0] else JoinTable(slots[0], lengths[0], 0)
+                    if table is not None:
+                        arrays = self.host.tree_fit(pred, table.slots, table.lengths)
+                if arrays is None or arrays[3]:
+                    scores, tree = F.no_scores(n), np.full(n * (n - 1) // 2, np.nan, dtype=np.float32)
+                else:
+                    scores, tree = F.fit_scores(pred, arrays[1], arrays[2], n), arrays[0].astype(np.float32)
+                lines.append((kind.name, scores))
+                self.put(e.path, kind.files("fit.taxa.tsv")[0], F.taxa_tsv(ids, scores))
+                self.put(e.path, kind.files("patristic.phy")[0], self.phylip(tree, ids))
+            self.put(e.path, "fit.tsv", F.fit_tsv(lines))
+        self.book(fit=len(group), fit_s=time.perf_counter() - t0)
+
     def book(self, **amounts):
         """Add to the run's stats from inside a mode's own engine call (takes the runner's lock)."""
         with self._lock:
@@ -289,6 +358,7 @@ class DirectoryRunner:
     def _launch(self, engine, shape: Tuple[int, int], group: List[Entry], writers: ThreadPoolExecutor, pending: deque):
         def submit(jobs):
             pending.extend(writers.submit(*job) for job in jobs)
+        self._made.tables = {}
         t0 = time.perf_counter()
         if self.native_io:
             from .hostio import gather
@@ -306,6 +376,10 @@ class DirectoryRunner:
                 tables = device.get(kind.name)
                 submit([(self._write_trees, group[k::cap], preds[k::cap], None if tables is None else tables[k::cap], kind)
                         for k in range(min(cap, len(group)))])
+        if self.fit:
+            made, fits = dict(self._made.tables), self.fit_arrays(engine, shape[0], preds)
+            submit([(self._write_fit, group[k::cap], preds[k::cap], {name: None if t is None else t[k::cap] for name, t in made.items()},
+                     {name: tuple(a[k::cap] for a in arrays) for name, arrays in fits.items()}) for k in range(min(cap, len(group)))])
         if self.delta:
             arrays = self.delta_arrays(engine, preds)
             submit([(self._write_delta, group[k::cap], None if arrays is None else tuple(a[k::cap] for a in arrays))
@@ -529,6 +603,8 @@ class SiteShardedRunner(DirectoryRunner):
     def __init__(self, engine, group, rank: int, world: int, out_dir: str, heartbeat_s: Optional[float] = None, **kw):
         if kw.get("delta"):
             raise ValueError(DELTA_SHARD_SITES)
+        if kw.get("fit"):
+            raise ValueError(FIT_SHARD_SITES)
         super().__init__([engine], out_dir, **kw)
         self.group, self.rank, self.world = group, rank, world
         self.stats["site_sharded_over"] = world
@@ -637,7 +713,8 @@ def summarize(stats: dict, load_s: float = 0.0) -> dict:
                if "tbe" in stats else {}),
             **({k: stats[k] for k in ("consensus", "consensus_device")} if "consensus" in stats else {}),
             **({k: stats[k] for k in ("instability", "transfers_device")} if "instability" in stats else {}),
-            **({"delta": stats["delta"], "delta_s": round(stats["delta_s"], 6)} if "delta" in stats else {})}
+            **({"delta": stats["delta"], "delta_s": round(stats["delta_s"], 6)} if "delta" in stats else {}),
+            **({"fit": stats["fit"], "fit_s": round(stats["fit_s"], 6)} if "fit" in stats else {})}
 
 
 def run_multi_device(script: str, argv: List[str], devices: Sequence[int], shard: str = "files") -> Tuple[int, List[dict]]:
