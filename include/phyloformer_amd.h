@@ -36,6 +36,16 @@
  *     (phyloformer/data.py:7); the one-hot tensor of the reference never exists;
  *   - pairs are enumerated (i, j), i < j, lexicographically (model.py:13-17),
  *     P = N(N-1)/2 outputs per alignment.
+ *
+ * Sections and bindings
+ *   - a comment that opens with four dashes is a section banner; a function belongs to the last banner above it (the
+ *     functions above the first banner to none);
+ *   - a function may be missing from a library of this PF_ABI_VERSION if and only if its banner says
+ *     "(additive to ABI n)": a binding resolves such a function when it is called, every other one when the library is
+ *     loaded.  A function added without a new ABI version goes under a banner that says so;
+ *   - phyloformer_amd/cabi.py reads the prototypes, this rule, pf_status and the #defines from this file: a prototype
+ *     is written with its return type and name on one line, in the types int, int32_t, int64_t, uint64_t, size_t, void
+ *     and pointers.
  */
 #ifndef PHYLOFORMER_AMD_H
 #define PHYLOFORMER_AMD_H
@@ -725,6 +735,7 @@ int pf_forward_site_profile(pf_handle_t* h, const uint8_t* idx, int32_t B, int32
 int pf_site_moments_device(pf_handle_t* h, const float* d_map, int32_t B, int32_t P, int32_t L, float* d_se,
                            float* d_profile);
 
+/* ---- site-sharded forward and the RCCL bootstrap ---- */
 /* Site-sharded forward: this rank holds sites [l_begin, l_end) of an alignment
  * with L_total sites.  idx: host uint8 [B][N][l_end - l_begin].  Every rank
  * receives the full result in out [B][P].  The row-attention statistics are all-reduced once per
@@ -758,6 +769,7 @@ int pf_comm_destroy(pf_handle_t* h);
  * runtime as this library can be loaded. */
 int pf_comm_info(char* path_out, size_t path_cap, int32_t* version);
 
+/* ---- streams and device memory, profiling, debug taps, device properties, emulated shards, self test ---- */
 /* Stream / device access for callers that time with HIP events. */
 int pf_synchronize(pf_handle_t* h);
 int pf_get_stream(pf_handle_t* h, void** hip_stream_out);
@@ -886,6 +898,10 @@ int64_t pf_format_phylip_n(const float* preds, int32_t n, const char* const* ids
 int64_t pf_nj_newick_n(const float* preds, int32_t n, const char* const* ids, const int64_t* id_lens, int32_t clamp_negative,
                        char* out, int64_t cap);
 
+/* ---- Newick text of join tables, and of the refined and the BIONJ trees of distances (additive to ABI 5) ----
+ *
+ * Each of the four came with its device twin (pf_nj_joins, pf_bme_nni, pf_bme_spr, pf_bionj_joins): an ABI-5 library
+ * built before that twin lacks it.  pf_nj_newick_n above came with ABI 5 itself and is always there. */
 /* The Newick text of a join table (pf_nj_joins' slots / lengths [2 (n - 3) + 3] of ONE source, n >= 3): the text
  * nj.py::newick_of_joins writes for it, hence pf_nj_newick_n's when the table is that of the same distances.  No
  * device, no handle.  PF_EINVAL also for a slot outside [0, n).  Sizing protocol as pf_format_phylip. */

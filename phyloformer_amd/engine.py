@@ -13,16 +13,18 @@ from typing import Dict, Optional, Tuple
 
 import numpy as np
 
+from . import cabi
 from .treearrays import (JOINS, REFINE, consensus_arrays, consensus_outputs, ptr, support_arrays, support_outputs, transfer_outputs,
                          tree_call, unbatched)
 from .weights import ModelWeights
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libphyloformer_amd.so")
-ABI_VERSION = 5            # PF_ABI_VERSION of include/phyloformer_amd.h this binding was written against
-UNIQUE_ID_BYTES = 256      # PF_UNIQUE_ID_BYTES: two ncclUniqueIds, one per communicator / stream
+ABI_VERSION = cabi.CONSTANTS["PF_ABI_VERSION"]          # of the include/phyloformer_amd.h this tree holds
+UNIQUE_ID_BYTES = cabi.CONSTANTS["PF_UNIQUE_ID_BYTES"]  # two ncclUniqueIds, one per communicator / stream
 
-PF_OK, PF_EINVAL, PF_EHIP, PF_ERCCL, PF_ENOMEM, PF_ESTATE = 0, -1, -2, -3, -4, -5
+PF_OK, PF_EINVAL, PF_EHIP, PF_ERCCL, PF_ENOMEM, PF_ESTATE = (
+    cabi.CONSTANTS[k] for k in ("PF_OK", "PF_EINVAL", "PF_EHIP", "PF_ERCCL", "PF_ENOMEM", "PF_ESTATE"))
 
 
 def _refuse_single_sequence(B: int, N: int):
@@ -47,164 +49,12 @@ class pf_weights_t(C.Structure):
                 ("n_alphabet", C.c_int32), ("blob", C.POINTER(C.c_float)), ("blob_len", C.c_uint64)]
 
 
-# name -> (restype, argtypes); every symbol declared in include/phyloformer_amd.h
+# name -> (restype, argtypes) of every symbol declared in include/phyloformer_amd.h, and the additions to ABI 5 that a
+# library built before them lacks (the header's banners say which): bound when present; a call through a missing one
+# raises EngineError at call time (loading such a library stays possible).  Both are read from the header (cabi.py).
 _H = C.c_void_p
-SIGNATURES = {
-    "pf_abi_version": (C.c_int, []),
-    "pf_build_info": (C.c_char_p, []),
-    "pf_blob_len": (C.c_uint64, [C.c_int32, C.c_int32, C.c_int32]),
-    "pf_create": (C.c_int, [C.POINTER(pf_weights_t), C.c_int, C.POINTER(_H)]),
-    "pf_destroy": (C.c_int, [_H]),
-    "pf_last_error": (C.c_char_p, [_H]),
-    "pf_set_option": (C.c_int, [_H, C.c_char_p, C.c_int64]),
-    "pf_forward": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
-    "pf_forward_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
-    "pf_resample_sites_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                           C.c_uint64, C.c_void_p]),
-    "pf_bootstrap": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p]),
-    "pf_window_count": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
-    "pf_window_start": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
-    "pf_gather_sites_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                                         C.c_int32, C.c_int32, C.c_void_p]),
-    "pf_forward_sites": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
-                                   C.c_void_p]),
-    "pf_forward_windows": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
-                                     C.c_int32]),
-    "pf_forward_sharded": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                     C.c_int32, C.c_void_p]),
-    "pf_forward_sharded_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
-                                            C.c_int32, C.c_int32, C.c_void_p]),
-    "pf_comm_unique_id": (C.c_int, [C.c_void_p]),
-    "pf_comm_init": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32]),
-    "pf_comm_destroy": (C.c_int, [_H]),
-    "pf_comm_info": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(C.c_int32)]),
-    "pf_synchronize": (C.c_int, [_H]),
-    "pf_get_stream": (C.c_int, [_H, C.POINTER(C.c_void_p)]),
-    "pf_device_malloc": (C.c_int, [_H, C.c_size_t, C.POINTER(C.c_void_p)]),
-    "pf_device_free": (C.c_int, [_H, C.c_void_p]),
-    "pf_memcpy_h2d": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_size_t]),
-    "pf_memcpy_d2h": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_size_t]),
-    "pf_profile_reset": (C.c_int, [_H]),
-    "pf_profile_get": (C.c_int, [_H, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
-    "pf_debug_read": (C.c_int64, [_H, C.c_char_p, C.c_void_p, C.c_int64]),
-    "pf_device_info": (C.c_int, [_H, C.c_char_p, C.c_size_t, C.POINTER(C.c_int32),
-                                 C.POINTER(C.c_uint64)]),
-    "pf_device_pci": (C.c_int, [_H, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
-    "pf_selftest": (C.c_int, [_H, C.c_void_p]),
-    "pf_create_bare": (C.c_int, [C.c_int, C.POINTER(_H)]),
-    "pf_mha_create": (C.c_int, [_H, C.c_void_p, C.POINTER(C.c_void_p)]),
-    "pf_mha_destroy": (C.c_int, [C.c_void_p]),
-    "pf_mha_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
-    "pf_mha_forward_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
-    "pf_parse_fasta": (C.c_int, [C.c_char_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
-                                 C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
-    "pf_format_phylip": (C.c_int64, [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_char_p, C.c_int64]),
-    "pf_format_phylip_n": (C.c_int64, [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_void_p, C.c_char_p, C.c_int64]),
-    "pf_fasta_batch_load": (C.c_int, [C.POINTER(C.c_char_p), C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
-    "pf_fasta_batch_free": (None, [C.c_void_p]),
-    "pf_fasta_batch_count": (C.c_int32, [C.c_void_p]),
-    "pf_fasta_batch_infos": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "pf_fasta_batch_id": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
-    "pf_fasta_batch_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
-    "pf_nj_newick_n": (C.c_int64, [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32, C.c_char_p, C.c_int64]),
-    "pf_phylip_write_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
-                                        C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_int32, C.c_void_p]),
-    "pf_forward_shards_emulated": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                             C.c_void_p]),
-    "pf_forward_site_map": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-    "pf_forward_site_map_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-    "pf_forward_site_profile": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                                          C.c_void_p]),
-    "pf_site_moments_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-    "pf_gather_taxa_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
-                                        C.c_void_p]),
-    "pf_forward_taxa": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
-                                  C.c_void_p]),
-    "pf_forward_leave_one_out": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_void_p, C.c_void_p]),
-    "pf_loo_stats_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                                      C.c_void_p]),
-    "pf_forward_place": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "pf_place_stats_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
-                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "pf_forward_tiled": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-    "pf_tile_combine_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-    "pf_tile_groups": (C.c_int, [C.c_int32, C.c_int32]),
-    "pf_nj_joins": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "pf_nj_joins_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "pf_bionj_joins": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "pf_bionj_joins_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "pf_bionj_joins_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "pf_delta": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "pf_delta_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "pf_delta_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "pf_tree_fit": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                              C.c_void_p, C.c_void_p]),
-    "pf_tree_fit_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                                     C.c_void_p, C.c_void_p]),
-    "pf_tree_fit_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                                   C.c_void_p, C.c_void_p]),
-    "pf_bionj_newick_n": (C.c_int64, [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32, C.c_char_p, C.c_int64]),
-    "pf_nj_format_joins_n": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32,
-                                         C.c_char_p, C.c_int64]),
-    "pf_tile_bound": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
-    "pf_bme_nni": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                             C.c_void_p]),
-    "pf_bme_nni_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_void_p, C.c_void_p]),
-    "pf_bme_nni_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                  C.c_void_p]),
-    "pf_bme_newick_n": (C.c_int64, [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32, C.c_char_p, C.c_int64]),
-    "pf_bme_spr": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                             C.c_void_p]),
-    "pf_bme_spr_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_void_p, C.c_void_p]),
-    "pf_bme_spr_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                  C.c_void_p]),
-    "pf_bme_spr_newick_n": (C.c_int64, [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32, C.c_char_p, C.c_int64]),
-    "pf_join_supports": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                                   C.c_void_p, C.c_void_p]),
-    "pf_join_supports_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
-                                          C.c_void_p, C.c_void_p, C.c_void_p]),
-    "pf_join_supports_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_void_p]),
-    "pf_join_transfers": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 8),
-    "pf_join_transfers_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] +
-                                 [C.c_void_p] * 8),
-    "pf_join_transfers_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 8),
-    "pf_join_consensus": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 8),
-    "pf_join_consensus_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] +
-                                 [C.c_void_p] * 8),
-    "pf_join_consensus_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 8),
-    "pf_forward_weighted": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-    "pf_forward_weighted_device": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-    "pf_forward_sites_weighted": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                                            C.c_int32, C.c_int32, C.c_void_p]),
-    "pf_bootstrap_weighted": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64,
-                                        C.c_void_p]),
-    "pf_padded_sites": (C.c_int, [C.c_int32, C.c_int32]),
-    "pf_boot_counts": (C.c_int, [C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p]),
-    "pf_compress_sites": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-    "pf_site_classes": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-}
-
-# Additions to ABI 5 that a library built before them lacks: bound when present; a call through a missing one raises
-# EngineError at call time (loading such a library stays possible).
-CALL_TIME_SYMBOLS = frozenset({"pf_forward_site_map", "pf_forward_site_map_device", "pf_forward_site_profile",
-                               "pf_site_moments_device", "pf_gather_taxa_device", "pf_forward_taxa",
-                               "pf_forward_leave_one_out", "pf_loo_stats_device", "pf_forward_weighted",
-                               "pf_forward_weighted_device", "pf_forward_sites_weighted", "pf_bootstrap_weighted",
-                               "pf_padded_sites", "pf_boot_counts", "pf_compress_sites", "pf_forward_place",
-                               "pf_place_stats_device", "pf_forward_tiled", "pf_tile_combine_device", "pf_tile_groups",
-                               "pf_tile_bound", "pf_nj_joins", "pf_nj_joins_device", "pf_nj_format_joins_n", "pf_bme_nni",
-                               "pf_bme_nni_device", "pf_bme_nni_host", "pf_bme_newick_n", "pf_bme_spr",
-                               "pf_bme_spr_device", "pf_bme_spr_host", "pf_bme_spr_newick_n", "pf_join_supports",
-                               "pf_join_supports_device", "pf_join_supports_host", "pf_join_consensus",
-                               "pf_join_consensus_device", "pf_join_consensus_host", "pf_bionj_joins",
-                               "pf_bionj_joins_device", "pf_bionj_joins_host", "pf_bionj_newick_n", "pf_join_transfers",
-                               "pf_join_transfers_device", "pf_join_transfers_host", "pf_delta", "pf_delta_device",
-                               "pf_delta_host", "pf_site_classes", "pf_tree_fit", "pf_tree_fit_device", "pf_tree_fit_host"})
+SIGNATURES = {name: (p.restype, p.argtypes) for name, p in cabi.PROTOTYPES.items()}
+CALL_TIME_SYMBOLS = frozenset(name for name, p in cabi.PROTOTYPES.items() if p.call_time)
 
 _lib: Optional[C.CDLL] = None
 
@@ -233,6 +83,16 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     return lib
 
 
+def symbol(lib, name: str):
+    """The function ``name`` of a loaded library.  One it lacks (of a library that loaded, only a ``CALL_TIME_SYMBOLS``
+    one can be missing) raises here, when it is called."""
+    fn = getattr(lib, name, None)
+    if fn is None:
+        raise EngineError(PF_ESTATE, f"the loaded native library does not export {name} (it was built before that "
+                          "entry point was added); rebuild with `python -m phyloformer_amd.build --force`")
+    return fn
+
+
 def build_info(path: Optional[str] = None) -> Dict[str, object]:
     """What the loaded library was built from (``pf_build_info``, ABI 4): compiler, flags, the scheduling
     strategy that really compiled the kernels, source and kernel hashes.  Needs no device."""
@@ -247,14 +107,14 @@ class Engine:
         self._lib = load_library()
         self._h = _H()
         blob = weights.blob()
-        expect = self._lib.pf_blob_len(weights.n_blocks, weights.n_heads, weights.embed_dim)
+        expect = self._optional("pf_blob_len")(weights.n_blocks, weights.n_heads, weights.embed_dim)
         if blob.size != expect:
             raise ValueError(f"weight blob has {blob.size} floats, library expects {expect}")
         w = pf_weights_t(weights.n_blocks, weights.n_heads, weights.embed_dim, 22,
                          blob.ctypes.data_as(C.POINTER(C.c_float)), blob.size)
-        rc = self._lib.pf_create(C.byref(w), device, C.byref(self._h))
+        rc = self._optional("pf_create")(C.byref(w), device, C.byref(self._h))
         if rc != PF_OK:
-            msg = (self._lib.pf_last_error(None) or b"").decode()
+            msg = (self._optional("pf_last_error")(None) or b"").decode()
             self._h = _H()
             if rc == PF_EINVAL:
                 raise ValueError(msg)
@@ -271,17 +131,21 @@ class Engine:
         return self._arch
 
     # -- plumbing ---------------------------------------------------------------------------
+    def _optional(self, name: str):
+        """The one way every method reaches a function of the library (``symbol``)."""
+        return symbol(self._lib, name)
+
     def _check(self, rc: int):
         if rc >= 0:
             return rc
-        msg = (self._lib.pf_last_error(self._h) or b"").decode()
+        msg = (self._optional("pf_last_error")(self._h) or b"").decode()
         if rc == PF_EINVAL:
             raise ValueError(msg)   # the reference raises ValueError for N > 200 (model.py:24-28)
         raise EngineError(rc, msg)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
-            self._lib.pf_destroy(self._h)
+            self._optional("pf_destroy")(self._h)
             self._h = _H()
 
     def __del__(self):
@@ -297,24 +161,24 @@ class Engine:
         self.close()
 
     def set_option(self, key: str, value: int):
-        self._check(self._lib.pf_set_option(self._h, key.encode(), int(value)))
+        self._check(self._optional("pf_set_option")(self._h, key.encode(), int(value)))
 
     def device_info(self) -> Dict[str, object]:
         name = C.create_string_buffer(256)
         cu = C.c_int32()
         mem = C.c_uint64()
-        self._check(self._lib.pf_device_info(self._h, name, 256, C.byref(cu), C.byref(mem)))
+        self._check(self._optional("pf_device_info")(self._h, name, 256, C.byref(cu), C.byref(mem)))
         return {"name": name.value.decode(), "cu_count": cu.value, "hbm_bytes": mem.value}
 
     def build_info(self) -> Dict[str, object]:
         """What the library behind this engine was built from (``pf_build_info``)."""
         import json
-        return json.loads(self._lib.pf_build_info().decode())
+        return json.loads(self._optional("pf_build_info")().decode())
 
     def device_pci(self) -> Tuple[int, int, int]:
         """(domain, bus, device) of this engine's GPU - the key rocm_smi finds it by (phyloformer_amd/smi.py)."""
         d, b, v = C.c_int32(), C.c_int32(), C.c_int32()
-        self._check(self._lib.pf_device_pci(self._h, C.byref(d), C.byref(b), C.byref(v)))
+        self._check(self._optional("pf_device_pci")(self._h, C.byref(d), C.byref(b), C.byref(v)))
         return d.value, b.value, v.value
 
     # -- forward ----------------------------------------------------------------------------
@@ -352,7 +216,7 @@ class Engine:
         idx, single = self._sources(idx)
         B, N, L = idx.shape
         out = np.empty((B, N * (N - 1) // 2), dtype=np.float32)
-        self._check(self._lib.pf_forward(self._h, idx.ctypes.data, B, N, L, out.ctypes.data))
+        self._check(self._optional("pf_forward")(self._h, idx.ctypes.data, B, N, L, out.ctypes.data))
         return out[0] if single else out
 
     def bootstrap(self, idx: np.ndarray, replicates: int, seed: int = 0) -> np.ndarray:
@@ -363,15 +227,14 @@ class Engine:
         B, N, L = idx.shape
         R = int(replicates)
         out = np.empty((B, max(R, 0), N * (N - 1) // 2), dtype=np.float32)
-        self._check(self._lib.pf_bootstrap(self._h, idx.ctypes.data, B, N, L, R, self._seed(seed),
-                                           out.ctypes.data if out.size else None))
+        self._check(self._optional("pf_bootstrap")(self._h, idx.ctypes.data, B, N, L, R, self._seed(seed),
+                                                   out.ctypes.data if out.size else None))
         return out[0] if single else out
 
     def resample_sites_device(self, d_src: int, B: int, N: int, L: int, r_begin: int, R: int, seed: int, d_dst: int):
         """``pf_resample_sites_device``: replicates ``r_begin .. r_begin + R - 1`` of ``d_src [B][N][L]`` into
         ``d_dst [B][R][N][L]`` (device buffers, asynchronous on the handle's stream)."""
-        self._check(self._lib.pf_resample_sites_device(self._h, C.c_void_p(d_src), B, N, L, r_begin, R,
-                                                       self._seed(seed), C.c_void_p(d_dst)))
+        self._check(self._optional("pf_resample_sites_device")(self._h, d_src, B, N, L, r_begin, R, self._seed(seed), d_dst))
 
     def forward_sites(self, idx: np.ndarray, sites: np.ndarray) -> np.ndarray:
         """Distances of the alignments cut out of ``idx`` by a site table (``pf_forward_sites``): ``uint8[B, N, L]``,
@@ -382,8 +245,8 @@ class Engine:
         tab = self._table(sites, "sites must be an integer array [S, K]", "site", L)
         S, K = tab.shape
         out = np.empty((B, S, N * (N - 1) // 2), dtype=np.float32)
-        self._check(self._lib.pf_forward_sites(self._h, idx.ctypes.data, B, N, L, tab.ctypes.data if tab.size else None,
-                                               S, K, out.ctypes.data if out.size else None))
+        self._check(self._optional("pf_forward_sites")(self._h, idx.ctypes.data, B, N, L, tab.ctypes.data if tab.size else None,
+                                                       S, K, out.ctypes.data if out.size else None))
         return out[0] if single else out
 
     def forward_windows(self, idx: np.ndarray, W: int, step: "int | None" = None) -> np.ndarray:
@@ -393,27 +256,13 @@ class Engine:
         idx, single = self._sources(idx)
         B, N, L = idx.shape
         W, step = int(W), int(W if step is None else step)
-        S = max(0, self._lib.pf_window_count(L, W, step))
+        S = max(0, self._optional("pf_window_count")(L, W, step))
         out = np.empty((B, S, N * (N - 1) // 2), dtype=np.float32)
-        self._check(self._lib.pf_forward_windows(self._h, idx.ctypes.data, B, N, L, W, step,
-                                                 out.ctypes.data if out.size else None, S))
+        self._check(self._optional("pf_forward_windows")(self._h, idx.ctypes.data, B, N, L, W, step,
+                                                         out.ctypes.data if out.size else None, S))
         return out[0] if single else out
 
-    def gather_sites_device(self, d_src: int, B: int, N: int, L: int, d_sites: "int | None", d_start: "int | None", S: int,
-                            K: int, d_dst: int):
-        """``pf_gather_sites_device``: ``d_src [B][N][L]`` → ``d_dst [B][S][N][K]`` by a device site table ``d_sites
-        int32 [S][K]`` or device window starts ``d_start int32 [S]`` (device buffers, asynchronous on the handle's stream)."""
-        self._check(self._lib.pf_gather_sites_device(self._h, C.c_void_p(d_src), B, N, L, C.c_void_p(d_sites), C.c_void_p(d_start),
-                                                     S, K, C.c_void_p(d_dst)))
-
     # -- site-resolved distances ------------------------------------------------------------
-    def _optional(self, name: str):
-        fn = getattr(self._lib, name, None)
-        if fn is None:
-            raise EngineError(PF_ESTATE, f"the loaded native library does not export {name} (it was built before that "
-                              "entry point was added); rebuild with `python -m phyloformer_amd.build --force`")
-        return fn
-
     def forward_site_map(self, idx: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
         """Distances and their decomposition over sites (``pf_forward_site_map``): ``uint8[B, N, L]`` →
         ``(float32[B, P], float32[B, P, L])`` (``[N, L]`` → ``([P], [P, L])``).  ``map[b, p, l]`` is the softplus of the
@@ -441,17 +290,6 @@ class Engine:
         self._check(fn(self._h, idx.ctypes.data, B, N, L, out.ctypes.data, se.ctypes.data,
                        prof.ctypes.data if prof.size else None))
         return (out[0], se[0], prof[0]) if single else (out, se, prof)
-
-    def forward_site_map_device(self, d_idx: int, B: int, N: int, L: int, d_out: int, d_map: int):
-        """``pf_forward_site_map_device``: device buffers ``d_idx [B][N][L]`` → ``d_out [B][P]``, ``d_map [B][P][L]``."""
-        self._check(self._optional("pf_forward_site_map_device")(self._h, C.c_void_p(d_idx), B, N, L, C.c_void_p(d_out),
-                                                                 C.c_void_p(d_map)))
-
-    def site_moments_device(self, d_map: int, B: int, P: int, L: int, d_se: int, d_profile: int):
-        """``pf_site_moments_device``: device map ``float32 [B][P][L]`` → ``d_se [B][P]``, ``d_profile [B][L]``
-        (asynchronous on the handle's stream)."""
-        self._check(self._optional("pf_site_moments_device")(self._h, C.c_void_p(d_map), B, P, L, C.c_void_p(d_se),
-                                                             C.c_void_p(d_profile)))
 
     # -- the taxon axis ---------------------------------------------------------------------
     def forward_taxa(self, idx: np.ndarray, taxa: np.ndarray) -> np.ndarray:
@@ -488,18 +326,6 @@ class Engine:
         res = (out, infl, shift, ctx) + ((loo,) if keep_loo else ())
         return tuple(r[0] for r in res) if single else res
 
-    def gather_taxa_device(self, d_src: int, B: int, N: int, L: int, d_taxa: int, S: int, M: int, d_dst: int):
-        """``pf_gather_taxa_device``: ``d_src [B][N][L]`` → ``d_dst [B][S][M][L]`` by a device taxon table ``d_taxa int32
-        [S][M]`` (device buffers, asynchronous on the handle's stream)."""
-        self._check(self._optional("pf_gather_taxa_device")(self._h, C.c_void_p(d_src), B, N, L, C.c_void_p(d_taxa), S, M,
-                                                            C.c_void_p(d_dst)))
-
-    def loo_stats_device(self, d_full: int, d_loo: int, B: int, N: int, d_influence: int, d_shift: int, d_context: int):
-        """``pf_loo_stats_device``: device ``full float32 [B][P]``, ``loo float32 [B][N][P1]`` → ``d_influence [B][N]``,
-        ``d_shift [B][N]``, ``d_context [B][P]`` (asynchronous on the handle's stream)."""
-        self._check(self._optional("pf_loo_stats_device")(self._h, C.c_void_p(d_full), C.c_void_p(d_loo), B, N,
-                                                          C.c_void_p(d_influence), C.c_void_p(d_shift), C.c_void_p(d_context)))
-
     # -- query placement --------------------------------------------------------------------
     def forward_place(self, idx: np.ndarray, queries: int, keep_sets: bool = False):
         """Query placement (``pf_forward_place``): ``uint8[B, M, L]`` whose last ``queries`` rows are the queries, the
@@ -526,15 +352,6 @@ class Engine:
         res = (out, base, place, dis, sh, jt) + ((sets,) if keep_sets else ())
         return tuple(r[0] for r in res) if single else res
 
-    def place_stats_device(self, d_whole: int, d_base: int, d_sets: int, B: int, N: int, Q: int, d_place: int, d_disturb: int,
-                           d_shift: int, d_joint: int):
-        """``pf_place_stats_device``: device ``whole float32 [B][P_{N+Q}]``, ``base float32 [B][P_N]``, ``sets float32
-        [B][Q][P_{N+1}]`` → ``d_place [B][Q][N]``, ``d_disturb``, ``d_shift``, ``d_joint [B][Q]`` (asynchronous on the
-        handle's stream)."""
-        self._check(self._optional("pf_place_stats_device")(
-            self._h, C.c_void_p(d_whole), C.c_void_p(d_base), C.c_void_p(d_sets), B, N, Q, C.c_void_p(d_place),
-            C.c_void_p(d_disturb), C.c_void_p(d_shift), C.c_void_p(d_joint)))
-
     # -- tiled inference -------------------------------------------------------------------
     def forward_tiled(self, idx: np.ndarray, M: int) -> Tuple[np.ndarray, np.ndarray]:
         """Tiled inference (``pf_forward_tiled``): ``uint8[B, N, L]`` with ``N > M >= 2`` → ``(out float32[B, P_N],
@@ -548,12 +365,6 @@ class Engine:
         spread = np.empty_like(out)
         self._check(fn(self._h, idx.ctypes.data, B, N, L, int(M), out.ctypes.data, spread.ctypes.data))
         return (out[0], spread[0]) if single else (out, spread)
-
-    def tile_combine_device(self, d_sets: int, B: int, N: int, M: int, d_out: int, d_spread: int):
-        """``pf_tile_combine_device``: device ``sets float32 [B][T]`` (``tile.assemble``'s layout) → ``d_out``, ``d_spread
-        float32 [B][P_N]`` (asynchronous on the handle's stream)."""
-        self._check(self._optional("pf_tile_combine_device")(self._h, C.c_void_p(d_sets), B, N, M, C.c_void_p(d_out),
-                                                             C.c_void_p(d_spread)))
 
     # -- neighbour joining -------------------------------------------------------------------
     def nj_joins(self, preds: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -579,12 +390,6 @@ class Engine:
         self._check(fn(self._h, ptr(p), B, N, *map(ptr, out)))
         return unbatched((out[0], out[1], out[2].astype(bool)), single)
 
-    def nj_joins_device(self, d_preds: int, B: int, N: int, d_slots: int, d_lengths: int, d_nonfinite: int):
-        """``pf_nj_joins_device``: device ``preds float32 [B][P_N]`` → device ``slots int32`` / ``lengths float64
-        [B][2 (N - 3) + 3]``, ``nonfinite uint8 [B]`` (asynchronous on the handle's stream)."""
-        self._check(self._optional("pf_nj_joins_device")(self._h, C.c_void_p(d_preds), B, N, C.c_void_p(d_slots),
-                                                         C.c_void_p(d_lengths), C.c_void_p(d_nonfinite)))
-
     # -- BIONJ ------------------------------------------------------------------------------
     def bionj_joins(self, preds: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """BIONJ on the GPU (``pf_bionj_joins``): arguments and results as ``nj_joins``'; the table is that of
@@ -592,11 +397,6 @@ class Engine:
         ``hostio.bionj_joins_host``, and a start table for ``bme_nni`` / ``bme_spr``.  A source with a NaN or an infinity
         is flagged and its table unspecified (use ``hostio.bionj_newick``)."""
         return self._joins("pf_bionj_joins", preds)
-
-    def bionj_joins_device(self, d_preds: int, B: int, N: int, d_slots: int, d_lengths: int, d_nonfinite: int):
-        """``pf_bionj_joins_device``: ``nj_joins_device``'s arguments (asynchronous on the handle's stream)."""
-        self._check(self._optional("pf_bionj_joins_device")(self._h, C.c_void_p(d_preds), B, N, C.c_void_p(d_slots),
-                                                            C.c_void_p(d_lengths), C.c_void_p(d_nonfinite)))
 
     # -- delta scores -----------------------------------------------------------------------
     def delta(self, preds: np.ndarray, bins: int = 20) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -611,12 +411,6 @@ class Engine:
         self._check(fn(self._h, ptr(p), B, N, int(bins), *map(ptr, out)))
         return unbatched(out, single)
 
-    def delta_device(self, d_preds: int, B: int, N: int, bins: int, d_pair_sum: int, d_hist: int, d_nonfinite: int):
-        """``pf_delta_device``: device ``preds float32 [B][P_N]`` → device ``pair_sum int64 [B][P_N]``, ``hist int64
-        [B][bins]``, ``nonfinite uint8 [B]`` (asynchronous on the handle's stream)."""
-        self._check(self._optional("pf_delta_device")(self._h, C.c_void_p(d_preds), B, N, bins, C.c_void_p(d_pair_sum),
-                                                      C.c_void_p(d_hist), C.c_void_p(d_nonfinite)))
-
     # -- tree fit ----------------------------------------------------------------------------
     def tree_fit(self, preds: np.ndarray, slots: np.ndarray, lengths: np.ndarray, patristic: bool = True):
         """Tree fit on the GPU (``pf_tree_fit``): distances ``float32[B, P_N]`` and join tables ``int32 / float64 [B, M, T]``
@@ -630,14 +424,6 @@ class Engine:
         p, s, l, (B, M, N), flags, out = fit_arrays(preds, slots, lengths, patristic)
         self._check(fn(self._h, ptr(p), ptr(s), ptr(l), B, M, N, *map(ptr, out)))
         return squeezed(out, flags)
-
-    def tree_fit_device(self, d_preds: int, d_slots: int, d_lengths: int, B: int, M: int, N: int, d_patristic: int, d_rows: int,
-                        d_worst_j: int, d_status: int):
-        """``pf_tree_fit_device``: device arrays in ``pf_tree_fit``'s layouts (``d_patristic`` 0: none), asynchronous on the
-        handle's stream."""
-        self._check(self._optional("pf_tree_fit_device")(self._h, C.c_void_p(d_preds), C.c_void_p(d_slots), C.c_void_p(d_lengths),
-                                                         B, M, N, C.c_void_p(d_patristic or None), C.c_void_p(d_rows),
-                                                         C.c_void_p(d_worst_j), C.c_void_p(d_status)))
 
     # -- balanced NNI refinement -------------------------------------------------------------
     def bme_nni(self, preds: np.ndarray, start_slots: np.ndarray):
@@ -655,28 +441,12 @@ class Engine:
         self._check(fn(self._h, ptr(p), ptr(st), B, N, *map(ptr, out)))
         return unbatched(out, single)
 
-    def bme_nni_device(self, d_preds: int, d_start_slots: int, B: int, N: int, d_slots: int, d_lengths: int, d_steps: int,
-                       d_tree_length: int, d_status: int):
-        """``pf_bme_nni_device``: device ``preds float32 [B][P_N]`` and ``start_slots int32 [B][T]`` → device ``slots`` /
-        ``lengths [B][T]``, ``steps int32``, ``tree_length float64``, ``status uint8 [B]``.  Synchronises the handle's
-        stream once per round of steps: the results are complete on return."""
-        self._check(self._optional("pf_bme_nni_device")(self._h, C.c_void_p(d_preds), C.c_void_p(d_start_slots), B, N,
-                                                        C.c_void_p(d_slots), C.c_void_p(d_lengths), C.c_void_p(d_steps),
-                                                        C.c_void_p(d_tree_length), C.c_void_p(d_status)))
-
     # -- balanced SPR refinement -------------------------------------------------------------
     def bme_spr(self, preds: np.ndarray, start_slots: np.ndarray):
         """Balanced subtree pruning and regrafting on the GPU (``pf_bme_spr``): arguments and results as ``bme_nni``'s; the
         tree is that of ``bme.bme_spr``, bit for bit that of ``hostio.bme_spr_host``.  ``status`` 1: use
         ``hostio.spr_newick`` for that source."""
         return self._refine("pf_bme_spr", preds, start_slots)
-
-    def bme_spr_device(self, d_preds: int, d_start_slots: int, B: int, N: int, d_slots: int, d_lengths: int, d_steps: int,
-                       d_tree_length: int, d_status: int):
-        """``pf_bme_spr_device``: ``bme_nni_device``'s arguments; the results are complete on return."""
-        self._check(self._optional("pf_bme_spr_device")(self._h, C.c_void_p(d_preds), C.c_void_p(d_start_slots), B, N,
-                                                        C.c_void_p(d_slots), C.c_void_p(d_lengths), C.c_void_p(d_steps),
-                                                        C.c_void_p(d_tree_length), C.c_void_p(d_status)))
 
     # -- split supports of join tables -------------------------------------------------------
     def join_supports(self, ref_slots: np.ndarray, rep_slots: np.ndarray, rep_flag: Optional[np.ndarray] = None):
@@ -692,15 +462,6 @@ class Engine:
         self._check(fn(self._h, ref.ctypes.data, rep.ctypes.data, ptr(flag), B, R, N, *ptrs))
         return unbatched(out, single)
 
-    def join_supports_device(self, d_ref_slots: int, d_rep_slots: int, d_rep_flag: int, B: int, R: int, N: int, d_count: int,
-                             d_transfer: int, d_depth: int, d_status: int):
-        """``pf_join_supports_device``: device ``ref_slots int32 [B][T]``, ``rep_slots int32 [B][R][T]``, ``rep_flag uint8
-        [B][R]`` (0: none) → device ``count int32`` / ``transfer int64`` / ``depth int32 [B][N - 3]``, ``status uint8 [B]``
-        (asynchronous on the handle's stream).  Tables are checked in the kernel: status 1 and zeros, no refusal."""
-        self._check(self._optional("pf_join_supports_device")(
-            self._h, C.c_void_p(d_ref_slots), C.c_void_p(d_rep_slots), C.c_void_p(d_rep_flag) if d_rep_flag else None, B, R, N,
-            C.c_void_p(d_count), C.c_void_p(d_transfer), C.c_void_p(d_depth), C.c_void_p(d_status)))
-
     # -- per-taxon transfer counts ------------------------------------------------------------
     def join_transfers(self, ref_slots: np.ndarray, rep_slots: np.ndarray, rep_flag: Optional[np.ndarray] = None, cutoff: int = 100,
                        branch_moves: bool = True):
@@ -713,17 +474,6 @@ class Engine:
         out, ptrs = transfer_outputs(B, N, branch_moves)
         self._check(fn(self._h, ref.ctypes.data, rep.ctypes.data, ptr(flag), B, R, N, int(cutoff), *ptrs))
         return unbatched(out, single)
-
-    def join_transfers_device(self, d_ref_slots: int, d_rep_slots: int, d_rep_flag: int, B: int, R: int, N: int, cutoff: int,
-                              d_count: int, d_transfer: int, d_depth: int, d_moves: int, d_used: int, d_capped: int,
-                              d_branch_moves: int, d_status: int):
-        """``pf_join_transfers_device``: ``join_supports_device``'s arguments, the cutoff, and device ``moves int64
-        [B][N]``, ``used`` / ``capped int32 [B][N - 3]``, ``branch_moves int32 [B][N - 3][N]`` (0: not wanted)
-        (asynchronous on the handle's stream).  Tables are checked in the kernel: status 1 and zeros, no refusal."""
-        self._check(self._optional("pf_join_transfers_device")(
-            self._h, C.c_void_p(d_ref_slots), C.c_void_p(d_rep_slots), C.c_void_p(d_rep_flag) if d_rep_flag else None, B, R, N,
-            int(cutoff), C.c_void_p(d_count), C.c_void_p(d_transfer), C.c_void_p(d_depth), C.c_void_p(d_moves), C.c_void_p(d_used),
-            C.c_void_p(d_capped), C.c_void_p(d_branch_moves) if d_branch_moves else None, C.c_void_p(d_status)))
 
     # -- majority-rule consensus of replicate join tables -----------------------------------
     def join_consensus(self, rep_slots: np.ndarray, rep_lengths: Optional[np.ndarray] = None,
@@ -739,20 +489,6 @@ class Engine:
         out, ptrs = consensus_outputs(B, N, lengths is not None)
         self._check(fn(self._h, rep.ctypes.data, ptr(lengths), ptr(flag), B, R, N, int(percent), *ptrs))
         return unbatched(out, single)
-
-    def join_consensus_device(self, d_rep_slots: int, d_rep_lengths: int, d_rep_flag: int, B: int, R: int, N: int, percent: int,
-                              d_n_splits: int, d_count: int, d_size: int, d_parent: int, d_split_length: int, d_leaf_parent: int,
-                              d_leaf_length: int, d_status: int):
-        """``pf_join_consensus_device``: device ``rep_slots int32 [B][R][T]``, ``rep_lengths float64 [B][R][T]`` (0: none,
-        the two length outputs may then be 0), ``rep_flag uint8 [B][R]`` (0: none) → device ``n_splits int32 [B]``,
-        ``count`` / ``size`` / ``parent int32 [B][N - 3]``, ``split_length float64 [B][N - 3]``, ``leaf_parent int32 [B][N]``,
-        ``leaf_length float64 [B][N]``, ``status uint8 [B]`` (asynchronous on the handle's stream).  Tables are checked in
-        the kernel: status 1 and zeros, no refusal."""
-        opt = lambda p: C.c_void_p(p) if p else None
-        self._check(self._optional("pf_join_consensus_device")(
-            self._h, C.c_void_p(d_rep_slots), opt(d_rep_lengths), opt(d_rep_flag), B, R, N, int(percent), C.c_void_p(d_n_splits),
-            C.c_void_p(d_count), C.c_void_p(d_size), C.c_void_p(d_parent), opt(d_split_length), C.c_void_p(d_leaf_parent),
-            opt(d_leaf_length), C.c_void_p(d_status)))
 
     # -- site weights -----------------------------------------------------------------------
     @staticmethod
@@ -787,11 +523,6 @@ class Engine:
         out = np.empty((B, N * (N - 1) // 2), dtype=np.float32)
         self._check(fn(self._h, idx.ctypes.data, B, N, L, w.ctypes.data if w.size else None, out.ctypes.data))
         return out[0] if single else out
-
-    def forward_weighted_device(self, d_idx: int, B: int, N: int, L: int, d_w: int, d_out: int):
-        """``pf_forward_weighted_device``: device buffers ``d_idx [B][N][L]``, ``d_w float32 [B][L]`` → ``d_out [B][P]``."""
-        self._check(self._optional("pf_forward_weighted_device")(self._h, C.c_void_p(d_idx), B, N, L, C.c_void_p(d_w),
-                                                                 C.c_void_p(d_out)))
 
     def forward_sites_weighted(self, idx: np.ndarray, sites: np.ndarray, weights: np.ndarray) -> np.ndarray:
         """``forward_sites`` with a weight per table entry (``pf_forward_sites_weighted``): ``uint8[B, N, L]``,
@@ -828,8 +559,7 @@ class Engine:
         if Ll != l_end - l_begin:
             raise ValueError(f"idx has {Ll} sites, expected {l_end - l_begin}")
         out = np.empty((B, N * (N - 1) // 2), dtype=np.float32)
-        self._check(self._lib.pf_forward_sharded(self._h, idx.ctypes.data, B, N, l_begin, l_end,
-                                                 L_total, out.ctypes.data))
+        self._check(self._optional("pf_forward_sharded")(self._h, idx.ctypes.data, B, N, l_begin, l_end, L_total, out.ctypes.data))
         return out[0] if single else out
 
     def forward_shards_emulated(self, idx: np.ndarray, nshards: int) -> np.ndarray:
@@ -837,53 +567,44 @@ class Engine:
         idx, single = self._sources(idx, refuse_single=False)      # (N = 1 is the library's PF_EINVAL here)
         B, N, L = idx.shape
         out = np.empty((B, N * (N - 1) // 2), dtype=np.float32)
-        self._check(self._lib.pf_forward_shards_emulated(self._h, idx.ctypes.data, B, N, L, nshards,
-                                                         out.ctypes.data))
+        self._check(self._optional("pf_forward_shards_emulated")(self._h, idx.ctypes.data, B, N, L, nshards, out.ctypes.data))
         return out[0] if single else out
 
     # -- device-resident variant (benchmark) ------------------------------------------------
     def malloc(self, nbytes: int) -> int:
         p = C.c_void_p()
-        self._check(self._lib.pf_device_malloc(self._h, nbytes, C.byref(p)))
+        self._check(self._optional("pf_device_malloc")(self._h, nbytes, C.byref(p)))
         return p.value
 
     def free(self, ptr: int):
-        self._check(self._lib.pf_device_free(self._h, C.c_void_p(ptr)))
+        self._check(self._optional("pf_device_free")(self._h, C.c_void_p(ptr)))
 
     def h2d(self, dst: int, src: np.ndarray):
         src = np.ascontiguousarray(src)
-        self._check(self._lib.pf_memcpy_h2d(self._h, C.c_void_p(dst), src.ctypes.data, src.nbytes))
+        self._check(self._optional("pf_memcpy_h2d")(self._h, C.c_void_p(dst), src.ctypes.data, src.nbytes))
 
     def d2h(self, dst: np.ndarray, src: int):
         assert dst.flags["C_CONTIGUOUS"]
-        self._check(self._lib.pf_memcpy_d2h(self._h, dst.ctypes.data, C.c_void_p(src), dst.nbytes))
-
-    def forward_device(self, d_idx: int, B: int, N: int, L: int, d_out: int):
-        self._check(self._lib.pf_forward_device(self._h, C.c_void_p(d_idx), B, N, L, C.c_void_p(d_out)))
-
-    def forward_sharded_device(self, d_idx: int, B: int, N: int, l_begin: int, l_end: int,
-                               L_total: int, d_out: int):
-        self._check(self._lib.pf_forward_sharded_device(
-            self._h, C.c_void_p(d_idx), B, N, l_begin, l_end, L_total, C.c_void_p(d_out)))
+        self._check(self._optional("pf_memcpy_d2h")(self._h, dst.ctypes.data, C.c_void_p(src), dst.nbytes))
 
     def synchronize(self):
-        self._check(self._lib.pf_synchronize(self._h))
+        self._check(self._optional("pf_synchronize")(self._h))
 
     # -- RCCL -------------------------------------------------------------------------------
     def unique_id(self) -> bytes:
         buf = C.create_string_buffer(UNIQUE_ID_BYTES)
-        rc = self._lib.pf_comm_unique_id(buf)
+        rc = self._optional("pf_comm_unique_id")(buf)
         if rc != PF_OK:
-            raise EngineError(rc, (self._lib.pf_last_error(None) or b"").decode())
+            raise EngineError(rc, (self._optional("pf_last_error")(None) or b"").decode())
         return buf.raw
 
     def comm_init(self, unique_id: Optional[bytes], rank: int, world: int):
         buf = C.create_string_buffer(unique_id, UNIQUE_ID_BYTES) if unique_id else None
-        self._check(self._lib.pf_comm_init(self._h, buf, rank, world))
+        self._check(self._optional("pf_comm_init")(self._h, buf, rank, world))
         self.rank, self.world = rank, world
 
     def comm_destroy(self):
-        self._check(self._lib.pf_comm_destroy(self._h))
+        self._check(self._optional("pf_comm_destroy")(self._h))
         self.rank, self.world = 0, 1
 
     def collective_count(self) -> int:
@@ -898,28 +619,48 @@ class Engine:
         """Path and version of the librccl the native library resolved (loads it if necessary)."""
         buf = C.create_string_buffer(512)
         ver = C.c_int32()
-        rc = self._lib.pf_comm_info(buf, 512, C.byref(ver))
+        rc = self._optional("pf_comm_info")(buf, 512, C.byref(ver))
         if rc != PF_OK:
-            raise EngineError(rc, (self._lib.pf_last_error(None) or b"").decode())
+            raise EngineError(rc, (self._optional("pf_last_error")(None) or b"").decode())
         return {"library": buf.value.decode(), "version": int(ver.value)}
 
     # -- profiling / debugging --------------------------------------------------------------
     def profile_reset(self):
-        self._check(self._lib.pf_profile_reset(self._h))
+        self._check(self._optional("pf_profile_reset")(self._h))
 
     def profile_get(self, kernel: str) -> Tuple[int, float]:
         n = C.c_int64()
         ms = C.c_double()
-        self._check(self._lib.pf_profile_get(self._h, kernel.encode(), C.byref(n), C.byref(ms)))
+        self._check(self._optional("pf_profile_get")(self._h, kernel.encode(), C.byref(n), C.byref(ms)))
         return n.value, ms.value
 
     def debug_read(self, name: str) -> np.ndarray:
-        n = self._check(self._lib.pf_debug_read(self._h, name.encode(), None, 0))
+        n = self._check(self._optional("pf_debug_read")(self._h, name.encode(), None, 0))
         out = np.empty(n, dtype=np.float32)
-        self._check(self._lib.pf_debug_read(self._h, name.encode(), out.ctypes.data, n))
+        self._check(self._optional("pf_debug_read")(self._h, name.encode(), out.ctypes.data, n))
         return out
 
     def selftest(self) -> np.ndarray:
         out = np.empty(2304, dtype=np.float32)
-        self._check(self._lib.pf_selftest(self._h, out.ctypes.data))
+        self._check(self._optional("pf_selftest")(self._h, out.ctypes.data))
         return out
+
+
+def _pass_through(symbol: str):
+    """A method that only forwards: its arguments positionally in the header's order behind the handle, device addresses
+    as plain ints (0 or None: NULL), the status through ``_check``.  ctypes refuses a wrong count with ``TypeError``."""
+    def method(self, *args):
+        return self._check(self._optional(symbol)(self._h, *args))
+    method.__name__, method.__qualname__ = symbol[3:], "Engine." + symbol[3:]
+    method.__doc__ = cabi.PROTOTYPES[symbol].text
+    return method
+
+
+# the ``*_device`` forms (device arrays in, device arrays out; include/phyloformer_amd.h has their contracts) - method: symbol
+PASS_THROUGHS = {name: "pf_" + name for name in (
+    "forward_device", "forward_sharded_device", "gather_sites_device", "forward_site_map_device", "site_moments_device",
+    "gather_taxa_device", "loo_stats_device", "place_stats_device", "tile_combine_device", "nj_joins_device", "bionj_joins_device",
+    "delta_device", "tree_fit_device", "bme_nni_device", "bme_spr_device", "join_supports_device", "join_transfers_device",
+    "join_consensus_device", "forward_weighted_device")}
+for _name, _symbol in PASS_THROUGHS.items():
+    setattr(Engine, _name, _pass_through(_symbol))

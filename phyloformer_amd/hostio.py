@@ -14,6 +14,7 @@ from typing import List, Sequence, Tuple
 
 import numpy as np
 
+from .cabi import CONSTANTS
 from .engine import load_library
 from .treearrays import (JOINS, REFINE, consensus_arrays, consensus_outputs, ptr, support_arrays, support_outputs,
                          transfer_outputs, tree_call, unbatched)
@@ -44,10 +45,11 @@ def _lib():
         _bound = lib
     return lib
 
-PF_FASTA_EBYTE, PF_FASTA_ERAGGED, PF_FASTA_ENOHEADER, PF_FASTA_EEMPTY, PF_FASTA_ECAP, PF_FASTA_EUTF8 = -16, -17, -18, -19, -20, -21
 
-
-PF_EIO = -6
+# pf_parse_fasta's codes and pf_status' PF_EIO, as include/phyloformer_amd.h defines them
+PF_FASTA_EBYTE, PF_FASTA_ERAGGED, PF_FASTA_ENOHEADER, PF_FASTA_EEMPTY, PF_FASTA_ECAP, PF_FASTA_EUTF8, PF_EIO = (
+    CONSTANTS[k] for k in ("PF_FASTA_EBYTE", "PF_FASTA_ERAGGED", "PF_FASTA_ENOHEADER", "PF_FASTA_EEMPTY", "PF_FASTA_ECAP",
+                           "PF_FASTA_EUTF8", "PF_EIO"))
 
 
 def parse_error(rc: int, l: int, detail: int, path: str = "", data: bytes = b"") -> "BaseException | None":

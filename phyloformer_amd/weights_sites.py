@@ -92,12 +92,8 @@ def expand(idx: np.ndarray, weights: np.ndarray) -> np.ndarray:
 # ---- the C twins (no GPU needed) ---------------------------------------------------------------------------------
 
 def _fn(name: str):
-    from .engine import EngineError, PF_ESTATE, load_library
-    fn = getattr(load_library(), name, None)
-    if fn is None:
-        raise EngineError(PF_ESTATE, f"the loaded native library does not export {name}; rebuild with "
-                          "`python -m phyloformer_amd.build --force`")
-    return fn
+    from .engine import load_library, symbol
+    return symbol(load_library(), name)
 
 
 def native_padded_sites(K: int, L: int) -> int:
