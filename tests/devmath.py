@@ -59,3 +59,34 @@ def expected_ctx(w, k, x_row):
     P = x_row.shape[0]
     ctx = skv / sk[..., None] * (P / sq)[..., None]
     return ctx.reshape(-1, 64), q
+
+
+def expected_x_row(w, k, x_in, mrow):
+    """The stream after block k's row attention, from the stream entering the block [P][L][64] and the block's row-mix
+    matrices [P][>= 4][64] (rows 0-3; the bias row, if there, is not read): x + sum_h q'[h] * M[h] + b_o."""
+    _s, q = expected_srow(w, k, x_in)
+    bo = w[f"attention_blocks.{k}.row_attention.out_proj.bias"].astype(np.float64)
+    m = np.asarray(mrow, np.float64)[:, :4]
+    return x_in.astype(np.float64) + np.einsum("plh,phc->plc", q, m) + bo
+
+
+def expected_block_out(w, k, x_row, ctx):
+    """The stream leaving block k, from the stream after its row attention [P][L][64] and its column context [L][64]:
+    x_col = x_row + out_proj(q'_col * ctx) + b_o, then x_col + FFN(LN(x_col)) with the oracle's exact-erf GELU."""
+    p = f"attention_blocks.{k}."
+    x_row = x_row.astype(np.float64)
+    _c, q = expected_ctx(w, k, x_row)
+    c = np.asarray(ctx, np.float64).reshape(-1, 4, 16)
+    o = (q[..., None] * c[None]).reshape(x_row.shape[:2] + (64,))
+    x = x_row + O._mm(o, w[p + "col_attention.out_proj.weight"].astype(np.float64)) \
+        + w[p + "col_attention.out_proj.bias"].astype(np.float64)
+    xn = O.layer_norm(x, w[p + "ffn_norm.weight"].astype(np.float64), w[p + "ffn_norm.bias"].astype(np.float64))
+    hid = O.gelu(O._mm(xn, w[p + "ffn.0.weight"].astype(np.float64)) + w[p + "ffn.0.bias"].astype(np.float64))
+    return x + O._mm(hid, w[p + "ffn.3.weight"].astype(np.float64)) + w[p + "ffn.3.bias"].astype(np.float64)
+
+
+def expected_distances(w, x_last):
+    """The head on the stream leaving the last block [P][L][64]: the mean over sites of softplus(x . w_head + b_head)."""
+    hw = w["pwFNN.0.weight"].astype(np.float64).reshape(-1)
+    z = x_last.astype(np.float64) @ hw + w["pwFNN.0.bias"].astype(np.float64)
+    return O.softplus(z).mean(axis=1)

@@ -56,6 +56,12 @@ def _record(case, got, want, f64=None):
         extra = (f"; vs the fp64 evaluation: GPU {_ERRORS[case]['gpu_vs_fp64']:.3e}, "
                  f"fp32 reference {_ERRORS[case]['fp32_reference_vs_fp64']:.3e}")
     print(f"parity {case}: max-abs error {err:.3e} (max |reference| {scale:.3g}){extra}")
+    _dump()
+    return err, scale
+
+
+def _dump():
+    """Write the table so far (tests/test_gpu_taps.py adds its rows to _ERRORS and calls this too)."""
     try:
         import json
         os.makedirs("gpurun_out", exist_ok=True)
@@ -63,7 +69,6 @@ def _record(case, got, want, f64=None):
             json.dump(_ERRORS, fh, indent=1, sort_keys=True)
     except OSError:
         pass
-    return err, scale
 
 
 def _check(err, scale, what=None):
