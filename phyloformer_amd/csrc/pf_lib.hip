@@ -332,7 +332,8 @@ struct pf_handle {
     // column attention's |v| (the column-apply operand is <= P * f16_vmax_col / 16)
     bool f16_ok = true;
     double f16_vmax_col = 0.0;
-    char f16_why[160] = {0};
+    double f16_bounds[5] = {0, 0, 0, 0, 0};   // hidden, row-mix base * 64, weights, out_proj biases, out_proj row sums ("f16_ranges" debug read)
+    char f16_why[320] = {0};
     bool precise_ffn_valu = false;   // option "precise_ffn_valu": the float64 FFN on the VALU instead of the matrix cores (cross-check)
     PreciseWeights pw;
     Buffer<char> wsp{buffers};     // workspace of the float64 paths (precise and generic)
@@ -402,7 +403,21 @@ int DeviceBuffer::reserve(pf_handle* h, size_t bytes) {
 //   column   q' / mean(q') * |v| / 16 <= P * vmax_col / 16                       (checked per shape, f16_range_ok)
 // The five shipped checkpoints sit at 61 / 196 / 30 (P = 19,900 gives 37,600).  A checkpoint outside the range is not
 // refused: its forwards run on the float64 kernels (use_precise).
-struct F16Ranges { double hidden = 0, mbase = 0, vmax_col = 0, wmax = 0; };
+//   biases   |row bo|, |col bo|: k_rowfin splits both out_proj biases into K slots 4 and 5 of the row-mix fragments
+// A NaN passes every std::max and every "<" below, so the blob is also tested entry by entry (finite).
+//
+// The low side.  Below 2^-3 the lo limb is subnormal: the pair carries such a value to an ABSOLUTE 2^-25, whatever its
+// size, and the partner operand multiplies that error.  A checkpoint that holds the same function with v small and
+// out_proj large (or W1 large and W2 small) loses what the shipped balance keeps; measured on MI355X with exact
+// power-of-two rescalings of pf, the error grows in proportion to the partner's bound:
+//   wo_l1    max_c sum_hd |Wo[c][hd]|, row and column out_proj: multiplies the error of v (row: Wv' x~; column:
+//            q' ctx / 16).  Shipped <= 27; at 64 x that the column attention leaves the per-buffer caps (distances
+//            6.3e-5 off), at 4,096 x the row attention's distances are 2.4e-4 off.
+//   vmax_col multiplies the error of a small column out_proj: 1.6e-10 x vmax_col of x's largest entry.  Shipped 30.
+//   hidden   multiplies the error of a small W2: 8.8e-10 x hidden of x's largest entry.  Shipped 61.
+// Limits (F16_LO_*): where the added error stays near 3e-6 of a buffer, a third of what the six blocks may add up to
+// under the 1e-4 caps.  The same verdict as above: outside, the float64 kernels run.
+struct F16Ranges { double hidden = 0, mbase = 0, vmax_col = 0, wmax = 0, bias = 0, wo_l1 = 0; bool finite = true; };
 void f16_note_attn(const std::vector<float>& wv, const std::vector<float>& bv, const float* wo, bool col, F16Ranges* r) {
     double vmax[E];
     for (int hd = 0; hd < E; ++hd) {
@@ -417,6 +432,11 @@ void f16_note_attn(const std::vector<float>& wv, const std::vector<float>& bv, c
             for (int d = 0; d < HD; ++d) { m += std::fabs((double)wo[(size_t)c * E + 16 * hh + d]) * vmax[16 * hh + d]; r->wmax = std::max(r->wmax, std::fabs((double)wo[(size_t)c * E + 16 * hh + d]) * (col ? COLAPPLY_A_SCALE : 1.0)); }
             if (!col) r->mbase = std::max(r->mbase, m);
         }
+    for (int c = 0; c < E; ++c) {
+        double l1 = 0;
+        for (int hd = 0; hd < E; ++hd) l1 += std::fabs((double)wo[(size_t)c * E + hd]);
+        r->wo_l1 = std::max(r->wo_l1, l1);
+    }
 }
 void f16_note_ffn(const std::vector<float>& w1a, const std::vector<float>& b1a, const std::vector<float>& w2s, F16Ranges* r) {
     for (int j = 0; j < FF; ++j) {
@@ -427,13 +447,20 @@ void f16_note_ffn(const std::vector<float>& w1a, const std::vector<float>& b1a, 
     for (float v : w2s) r->wmax = std::max(r->wmax, std::fabs((double)v));
 }
 constexpr double F16_LIMIT = 60000.0;            // (65504 with a margin for the rounding of the bounds themselves)
+constexpr double F16_LO_HIDDEN = 8192.0, F16_LO_VMAX_COL = 16384.0, F16_LO_WO_L1 = 512.0;    // the low side, above
 void check_f16_ranges(pf_handle* h, const F16Ranges& r) {
     h->f16_vmax_col = r.vmax_col;
-    const bool finite = std::isfinite(r.hidden) && std::isfinite(r.mbase) && std::isfinite(r.vmax_col) && std::isfinite(r.wmax);
-    h->f16_ok = !PF_F16 || (finite && r.hidden < F16_LIMIT && r.mbase * 64.0 < F16_LIMIT && r.wmax < F16_LIMIT);
+    h->f16_bounds[0] = r.hidden; h->f16_bounds[1] = r.mbase * 64.0; h->f16_bounds[2] = r.wmax; h->f16_bounds[3] = r.bias;
+    h->f16_bounds[4] = r.wo_l1;
+    const bool finite = r.finite && std::isfinite(r.hidden) && std::isfinite(r.mbase) && std::isfinite(r.vmax_col) &&
+                        std::isfinite(r.wmax) && std::isfinite(r.bias) && std::isfinite(r.wo_l1);
+    const bool range = r.hidden < F16_LIMIT && r.mbase * 64.0 < F16_LIMIT && r.wmax < F16_LIMIT && r.bias < F16_LIMIT;
+    const bool low = r.hidden < F16_LO_HIDDEN && r.vmax_col < F16_LO_VMAX_COL && r.wo_l1 < F16_LO_WO_L1;
+    h->f16_ok = !PF_F16 || (finite && range && low);
     if (!h->f16_ok)
-        snprintf(h->f16_why, sizeof h->f16_why, "fp16 operand bounds: hidden %.3g, row-mix base %.3g, weights %.3g (limit %.0f)",
-                 r.hidden, r.mbase * 64.0, r.wmax, F16_LIMIT);
+        snprintf(h->f16_why, sizeof h->f16_why, "fp16 operands: hidden %.3g (limit %.0f), row-mix base %.3g, weights %.3g, out_proj biases %.3g "
+                 "(limit %.0f), column |v| %.3g (limit %.0f), out_proj row sums %.3g (limit %.0f)%s", r.hidden, F16_LO_HIDDEN, r.mbase * 64.0,
+                 r.wmax, r.bias, F16_LIMIT, r.vmax_col, F16_LO_VMAX_COL, r.wo_l1, F16_LO_WO_L1, r.finite ? "" : "; non-finite entries");
 }
 // per forward: the column-apply operand q' / mean(q') * v / 16 <= P * vmax_col / 16, and q' / mean(q') <= L_total on
 // the row side is covered up to 2^20 sites by k_rowfin's b_scale
@@ -462,6 +489,7 @@ int prepare_weights(pf_handle* h, const BlobView& view, uint64_t blob_len) {
         if ((rc = upload(h, ptab, &h->pair_table))) return rc;
     }
     F16Ranges ranges;
+    for (size_t i = 0; i < view.len; ++i) ranges.finite = ranges.finite && std::isfinite(view.emb_w[i]);   // (the blob starts at emb_w)
     std::vector<std::vector<float>> row_bqk(nb);
     std::vector<std::vector<uint16_t>> row_tail(nb);
     for (int k = 0; k < nb; ++k) {
@@ -474,6 +502,7 @@ int prepare_weights(pf_handle* h, const BlobView& view, uint64_t blob_len) {
         fold(r.wk, r.bk, r.g, r.b, NH, E, wk, bk);
         fold(r.wv, r.bv, r.g, r.b, E, E, wv, bv);
         f16_note_attn(wv, bv, r.wo, false, &ranges);
+        for (int cc = 0; cc < E; ++cc) ranges.bias = std::max({ranges.bias, std::fabs((double)r.bo[cc]), std::fabs((double)c.bo[cc])});
         for (float v : wq) ranges.wmax = std::max(ranges.wmax, std::fabs((double)v));
         for (float v : wk) ranges.wmax = std::max(ranges.wmax, std::fabs((double)v));
         row_tail[k].assign((size_t)(FRAG_END - FRAG_WV) * 8, 0);
@@ -3331,10 +3360,15 @@ int64_t pf_debug_read(pf_handle_t* h, const char* name, float* dst, int64_t cap)
         for (int i = 0; i < 8 && i < cap; ++i) dst[i] = (float)((double)v[i] * 1e-6);   // mega-cycles
         return 8;
     }
-    if (std::strcmp(name, "f16_ranges") == 0) {       // [checkpoint inside the fp16 operand ranges, bound of the column |v|]
+    if (std::strcmp(name, "f16_ranges") == 0) {       // [checkpoint inside the fp16 operand ranges, bound of the column |v|],
+        // and for a caller with room for six: [hidden, row-mix base * 64, weights, out_proj biases], for seven: [the largest
+        // out_proj row sum] (check_f16_ranges)
         if (dst && cap > 0) dst[0] = h->f16_ok ? 1.f : 0.f;
         if (dst && cap > 1) dst[1] = (float)h->f16_vmax_col;
-        return 2;
+        if (!dst || cap < 6) return 2;
+        const int n = cap < 7 ? 6 : 7;
+        for (int i = 0; i + 2 < n; ++i) dst[2 + i] = (float)h->f16_bounds[i];
+        return n;
     }
     auto it = h->taps.find(name);
     if (it == h->taps.end()) return fail(h, PF_ESTATE, "no tap '%s' (set debug_keep=1 and run a forward)", name);

@@ -10,7 +10,8 @@
     the distances from the device's last x.  A kernel is judged on its own arithmetic; a wrong token shows at full size in
     the one buffer it was written to.
 
-The measure of both is the largest absolute error of a buffer (one alignment's) over its largest expected entry.  x0 is a
+The measure of both is the largest absolute error of a buffer (one alignment's) over its largest expected entry; srow's
+two parts, S_kv and S_q | S_k, each over their own.  x0 is a
 gather and one fp32 addition: bit-exact.  A failure names comparison, buffer, block, alignment, pair, site and channel of
 the worst element, and how k_main's tiles and k_colstats' site chunks meet that token.
 """
@@ -142,8 +143,17 @@ def check_taps(w, idx, taps, dist, bounds, *, flat=None, oracle=None, n_blocks=6
         assert got.shape == want.shape, (buffer, got.shape, want.shape)
         diff = np.abs(got - want)
         diff[~np.isfinite(diff)] = np.inf                        # a NaN is the worst element, not an ignored one
-        worst = int(diff.argmax())
-        err = float(diff.reshape(-1)[worst] / np.abs(want).max())
+        # srow holds two quantities of unrelated size, S_kv and S_q | S_k: each is measured against its own largest entry
+        # (a checkpoint with a small v_proj would otherwise hide any error of S_kv behind S_q)
+        parts = (np.s_[:, :64], np.s_[:, 64:]) if kind == "srow" else (np.s_[...],)
+        rel = np.zeros_like(diff)
+        for part in parts:
+            scale = float(np.abs(want[part]).max())
+            # (a buffer that is exactly zero - a zeroed v_proj - has no largest entry to measure against: any difference fails)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                rel[part] = diff[part] / scale if scale > 0 else np.where(diff[part] == 0, 0.0, np.inf)
+        worst = int(rel.argmax())
+        err = float(rel.reshape(-1)[worst])
         rep.buffers[comparison, buffer, b] = err
         rep.errors[comparison, kind] = max(rep.errors.get((comparison, kind), 0.0), err)
         bound = bounds[comparison][kind]

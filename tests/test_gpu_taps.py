@@ -118,23 +118,24 @@ def record(run, rep):
     parity._dump()
 
 
-def read_taps(e):
-    names = [f"x{k}" for k in range(NB + 1)] + [f"{b}{k}" for b in ("srow", "mrow", "ctx") for k in range(NB)]
+def read_taps(e, nb=NB):
+    names = [f"x{k}" for k in range(nb + 1)] + [f"{b}{k}" for b in ("srow", "mrow", "ctx") for k in range(nb)]
     return {name: e.debug_read(name) for name in names}
 
 
-def run_and_check(e, w, idx, orc, flat, run):
+def run_and_check(e, w, idx, orc, flat, run, nb=NB, bounds=BOUNDS):
     """Both head forms under debug_keep 1: the folded head's distances and every tap, then the full head's distances
-    against its own x6."""
+    against its own last x.  nb, bounds: the checkpoint's block count and the bounds to hold it to
+    (tests/test_gpu_ckpt_family.py brings its own)."""
     e.set_option("debug_keep", 1)
     try:
         e.set_option("head_fold", 1)
         dist = e.forward(idx)
-        rep = tap_check.check_taps(w, idx, read_taps(e), dist, BOUNDS, flat=flat, oracle=orc, must_pass=False)
+        rep = tap_check.check_taps(w, idx, read_taps(e, nb), dist, bounds, flat=flat, oracle=orc, n_blocks=nb, must_pass=False)
         e.set_option("head_fold", 0)
         dist0 = e.forward(idx)
-        rep0 = tap_check.check_taps(w, idx, {f"x{NB}": e.debug_read(f"x{NB}")}, dist0, BOUNDS, flat=flat, head_only=True,
-                                    must_pass=False)
+        rep0 = tap_check.check_taps(w, idx, {f"x{nb}": e.debug_read(f"x{nb}")}, dist0, bounds, flat=flat, n_blocks=nb,
+                                    head_only=True, must_pass=False)
     finally:
         e.set_option("head_fold", 1)
         e.set_option("debug_keep", 0)
@@ -143,6 +144,7 @@ def run_and_check(e, w, idx, orc, flat, run):
     assert not rep.failures, rep.message()
     assert not rep0.failures, "head_fold 0: " + rep0.message()
     assert np.isfinite(dist).all() and np.isfinite(dist0).all()
+    return dist, rep
 
 
 @pytest.mark.parametrize("name,variant", RUNS, ids=[n if v is None else f"{n}-{v}" for n, v in RUNS])
