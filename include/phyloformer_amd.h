@@ -489,6 +489,34 @@ int pf_tree_fit_device(pf_handle_t* h, const float* d_preds, const int32_t* d_sl
 int pf_tree_fit_host(const float* preds, const int32_t* slots, const double* lengths, int32_t B, int32_t M, int32_t N, double* patristic,
                      double* rows, int32_t* worst_j, uint8_t* status);
 
+/* ---- least-squares branch lengths of a fixed join table (additive to ABI 5) ----
+ *
+ * The ordinary-least-squares (OLS) branch lengths of join tables: the lengths that minimise the residual sum of squares
+ * pf_tree_fit reports over all length vectors of the table's topology, by the closed form of Rzhetsky & Nei 1993 (FastME's
+ * -w OLS), bit for bit those of phyloformer_amd/ols.py::tree_ols_py.  A tree is a join table in pf_nj_joins' layout; only its
+ * slots are read.  Nodes are pf_tree_fit's; the children of join t are (the node in slot a, the node in slot b), the last node's
+ * are the last three in table order.  W[v][x] is the float64 sum of leaf x's distances to the leaves of node v, added along the
+ * tree (W[v] = W[a] + W[b]; r = (W[c0] + W[c1]) + W[c2]).  Per branch the sums of W over the leaves of the two subtrees below
+ * it and of the sibling subtree - six sums at the most - are formed in 64 strided accumulators over the subtree's leaves in
+ * the tree's leaf order and combined pairwise at distances 32, 16, ... 1; the closed form follows with every product, quotient
+ * and sum rounded where ols.py writes it: the order is part of the definition (csrc/pf_ols.hip.h, csrc/pf_ols_host.h; DESIGN.md
+ * section 34).
+ *   preds     float  [B][P_N]        pf_forward's distances, pairs i < j in lexicographic order
+ *   slots     int32  [B][M][T]       M join tables per source, T = 2 (N - 3) + 3
+ *   ols       double [B][M][T]       the OLS lengths in the positions of the table's own lengths; a negative one is not clamped
+ *   status    uint8  [B][M]          0 fine; 2 no join table (as pf_tree_fit; checked first); 1 a NaN or an infinity in the
+ *                                    source's distances.  A tree with a status has zeros and is walked by no kernel
+ * pf_tree_ols takes host arrays and is synchronous; pf_tree_ols_device takes device arrays and is asynchronous on the
+ * handle's stream; pf_tree_ols_host is the serial twin, without a handle or a device.  One call with B sources equals B
+ * calls with one.  The state of a tree is (2N - 2) N doubles and 7 N int32 (1.07 GB at N = 8,192): trees run side by side in
+ * chunks that fit "ws_limit_mb".  Refused with PF_EINVAL before any device work, the message naming the value: N < 3;
+ * N > 8,192; B < 1; M < 1; NULL buffers; a tree's state above the workspace limit.  pf_profile_get("tree_ols") counts the
+ * calls of the two handle entry points. */
+int pf_tree_ols(pf_handle_t* h, const float* preds, const int32_t* slots, int32_t B, int32_t M, int32_t N, double* ols, uint8_t* status);
+int pf_tree_ols_device(pf_handle_t* h, const float* d_preds, const int32_t* d_slots, int32_t B, int32_t M, int32_t N, double* d_ols,
+                       uint8_t* d_status);
+int pf_tree_ols_host(const float* preds, const int32_t* slots, int32_t B, int32_t M, int32_t N, double* ols, uint8_t* status);
+
 /* ---- balanced minimum-evolution NNI refinement of a join table (additive to ABI 5) ----
  *
  * Balanced nearest-neighbour interchanges (BNNI, FastME's -n B) from a start tree to a local optimum of the balanced

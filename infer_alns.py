@@ -21,7 +21,9 @@ not parse, has the reference's side effects (infer_alns.py:97-117): every entry 
 exception is raised.  ``--delta`` (``phyloformer_amd/delta.py``) is no mode of its own: it asks of every launch's
 distances, whichever mode made them, how tree-like they are, and writes ``<stem>.delta.tsv``, ``<stem>.delta.phy`` and
 ``<stem>.delta.hist.tsv``.  ``--fit`` (``phyloformer_amd/fit.py``) asks of every tree a run with ``-t`` writes how well it
-reproduces those distances: ``<stem>.fit.tsv`` and, per tree, ``<stem>.fit.taxa.tsv`` and ``<stem>.patristic.phy``.  The multi-GPU modes, which have no counterpart, refuse such a directory up front.
+reproduces those distances: ``<stem>.fit.tsv`` and, per tree, ``<stem>.fit.taxa.tsv`` and ``<stem>.patristic.phy``.  ``--ols``
+(``phyloformer_amd/ols.py``) gives every such tree the branch lengths that reproduce them best: ``<stem>.ols.nwk`` per tree and
+``<stem>.ols.tsv``.  The multi-GPU modes, which have no counterpart, refuse such a directory up front.
 The forward pass runs in ``libphyloformer_amd.so``; there is no CPU fallback.
 """
 import argparse
@@ -77,6 +79,15 @@ def build_parser():
                              "<stem>.patristic.phy (the tree's path-length distances, cophenetic.phylo of R's ape, a PHYLIP "
                              "matrix); another tree's name stands before the ending (<stem>.bme.fit.taxa.tsv).  Negative branch "
                              "lengths count as they are; up to 8,192 sequences; every other output keeps its bytes")
+    parser.add_argument("--ols", action="store_true",
+                        help="with -t: the ordinary-least-squares branch lengths of every written tree - the lengths that "
+                             "reproduce the distances best on that tree's topology (Rzhetsky & Nei 1993, FastME -w OLS), "
+                             "computed on the GPU for large files.  Writes per tree <stem>.ols.nwk, the same topology with the "
+                             "least-squares lengths (another tree's name stands before the ending: <stem>.bme.ols.nwk; negative "
+                             "lengths are written as the tree's own are), and <stem>.ols.tsv, one line per tree: the tree length, "
+                             "the RMS residual and the explained variance before and after, the negative branches before and "
+                             "after, the most negative least-squares length and the largest change of a branch, all from the "
+                             "unclamped lengths; up to 8,192 sequences; every other output keeps its bytes")
     parser.add_argument("--device", type=int, default=0, help="HIP device ordinal (default 0)")
     parser.add_argument("--devices", default=None,
                         help="comma-separated HIP device ordinals: shard the files over these GPUs, "
@@ -124,6 +135,10 @@ def main(argv=None):
         parser.error(scheduler.FIT_NEEDS_TREES)
     if args.fit and args.shard == "sites":
         parser.error(scheduler.FIT_SHARD_SITES)
+    if args.ols and not args.trees:
+        parser.error(scheduler.OLS_NEEDS_TREES)
+    if args.ols and args.shard == "sites":
+        parser.error(scheduler.OLS_SHARD_SITES)
 
     in_dir = os.path.abspath(args.alndir)
     out_dir = os.path.abspath(args.outdir)  # TypeError if omitted, as in the reference (:90)
@@ -199,7 +214,7 @@ def main(argv=None):
     runner = scheduler.DirectoryRunner(engines, out_dir, trees=args.trees, batch=args.batch,
                                        io_threads=args.io_threads, native_io=not args.python_io,
                                        progress=bar.update if bar is not None else None, modes=modes, bme=args.bme, spr=args.spr,
-                                       bionj=args.bionj, delta=args.delta, fit=args.fit)
+                                       bionj=args.bionj, delta=args.delta, fit=args.fit, ols=args.ols)
     try:
         stats = runner.run(paths)
     finally:

@@ -28,6 +28,7 @@
 #include "pf_bionj_host.h"
 #include "pf_delta_host.h"
 #include "pf_fit_host.h"
+#include "pf_ols_host.h"
 #include "pf_support_host.h"
 #include "pf_consensus_host.h"
 
@@ -953,6 +954,21 @@ int pf_delta_host(const float* preds, int32_t B, int32_t N, int32_t K, int64_t* 
     for (int32_t b = 0; b < B; ++b)
         pfdelta::run_serial(preds + (size_t)b * P, N, K, pair_sum + (size_t)b * P, hist + (size_t)b * (size_t)K, nonfinite + b);
     return PF_OK;
+}
+
+// Least-squares branch lengths without a device: every tree of every source serially - the same
+// arrays as pf_tree_ols, bit for bit.  Twin of phyloformer_amd/ols.py::tree_ols_py.  A tree with a status has zeros.
+int pf_tree_ols_host(const float* preds, const int32_t* slots, int32_t B, int32_t M, int32_t N, double* ols, uint8_t* status) {
+    if (!preds || !slots || !ols || !status || pfols::refused(B, M, N)) return PF_EINVAL;
+    try {
+        const size_t n = (size_t)N, P = n * (n - 1) / 2, T = (size_t)pfols::table_len(N);
+        for (size_t b = 0; b < (size_t)B; ++b)
+            for (size_t m = 0; m < (size_t)M; ++m) {
+                const size_t item = b * (size_t)M + m;
+                pfols::run_serial(preds + b * P, slots + item * T, N, ols + item * T, status + item);
+            }
+        return PF_OK;
+    } catch (...) { return PF_ENOMEM; }
 }
 
 // Tree fit without a device: every tree of every source serially - the same arrays as pf_tree_fit,

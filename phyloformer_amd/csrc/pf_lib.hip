@@ -52,6 +52,7 @@
 #include "pf_bionj.hip.h"
 #include "pf_delta.hip.h"
 #include "pf_fit.hip.h"
+#include "pf_ols.hip.h"
 #include "pf_bme.hip.h"
 #include "pf_support.hip.h"
 #include "pf_consensus.hip.h"
@@ -277,6 +278,10 @@ struct pf_handle {
     Buffer<char> d_fit{buffers}, d_fit_io{buffers};
     int64_t fit_calls = 0;       // pf_tree_fit / pf_tree_fit_device calls since the last pf_profile_reset ("tree_fit")
     int64_t fit_lds_bytes = pffit::LDS_MAX_BYTES;   // option "fit_lds_bytes": what k_fit_pairs may stage in LDS; tests
+    // pf_tree_ols / pf_tree_ols_device (grow-only): the column sums and the node arrays of one chunk of trees, and the
+    // staging of the host entry point's arrays
+    Buffer<char> d_ols{buffers}, d_ols_io{buffers};
+    int64_t ols_calls = 0;       // pf_tree_ols / pf_tree_ols_device calls since the last pf_profile_reset ("tree_ols")
     // pf_bme_nni / pf_bme_nni_device (grow-only): the state of one chunk of sources (pf_bme.hip.h: carve) and the
     // staging of the host entry point's distances
     Buffer<char> d_bme{buffers};
@@ -2297,6 +2302,54 @@ int fit_impl(pf_handle* h, bool device, const pffit::Tables& user, int B, int M,
     return staged_call(h, h->d_fit_io, list, [&] { return launch(io); });
 }
 
+// ---- least-squares branch lengths on the device (pf_tree_ols, pf_tree_ols_device; pf_ols.hip.h, pf_ols_host.h) ----
+
+// The caller's arrays on the device (asynchronous) or on the host (staged, one synchronisation).  The items - the B M
+// trees - are cut into chunks whose column sums and node arrays fit "ws_limit_mb" side by side; the chunks follow each
+// other on the stream and reuse the workspace.
+int ols_impl(pf_handle* h, bool device, const pfols::Tables& user, int B, int M, int N) {
+    pfols::Tables io{};
+    auto list = [&](auto& v) { pfols::staging_arrays(v, io, user, (size_t)std::max(B, 0), (size_t)std::max(M, 0), N); };
+    if (pfspan::missing(list)) return fail(h, PF_EINVAL, "null buffer");
+    switch (pfols::refused(B, M, N)) {
+        case 1: return fail(h, PF_EINVAL, "tree OLS needs N >= %d sequences (got %d)", pfols::MIN_N, N);
+        case 2: return fail(h, PF_EINVAL, "tree OLS takes at most %d sequences (got %d)", pfols::MAX_N, N);
+        case 3: return fail(h, PF_EINVAL, "tree OLS needs B >= 1 sources (got %d)", B);
+        case 4: return fail(h, PF_EINVAL, "tree OLS needs M >= 1 trees per source (got %d)", M);
+    }
+    const int64_t P = (int64_t)N * (N - 1) / 2, items = (int64_t)B * M;
+    const int T = pfols::table_len(N);
+    size_t n = 0;
+    if (!mul_size((size_t)items, (size_t)T, sizeof(double), &n) || !mul_size((size_t)B, (size_t)P, sizeof(float), &n))
+        return fail(h, PF_EINVAL, "B=%d sources of M=%d trees of N=%d sequences overflow the address space", B, M, N);
+    const size_t per = pfols::state_bytes(N);
+    if ((int64_t)per > h->ws_limit_bytes)
+        return fail(h, PF_EINVAL, "tree OLS of N=%d sequences needs %zu bytes of state per tree (its column sums and node arrays), above "
+                                  "the workspace limit of %lld bytes (option ws_limit_mb)", N, per, (long long)h->ws_limit_bytes);
+    const int chunk = (int)std::min<int64_t>(std::min(items, pfols::max_items(N)), (int64_t)((size_t)h->ws_limit_bytes / per));
+    HIPCHK(h, hipSetDevice(h->device));
+    ++h->ols_calls;
+    auto launch = [&](const pfols::Tables& d) -> int {
+        const int rc = h->d_ols.reserve(h, (size_t)chunk * per);
+        if (rc) return rc;
+        h->cur = h->stream;
+        // (a tree with a status is walked by no kernel: its results are these zeros)
+        HIPCHK(h, hipMemsetAsync(d.ols, 0, (size_t)items * (size_t)T * sizeof(double), h->stream));
+        pfols::Args a{};
+        a.preds = d.preds; a.slots = d.slots; a.ols = d.ols; a.status = d.status;
+        a.P = P; a.N = N; a.M = M;
+        for (int64_t item0 = 0; item0 < items; item0 += chunk) {
+            a.item0 = item0; a.nb = (int)std::min<int64_t>(chunk, items - item0);
+            pfols::carve(a, h->d_ols, a.nb);
+            const hipError_t e = pfols::launch_chunk(h->stream, a);
+            if (e != hipSuccess) return fail(h, PF_EHIP, "k_ols_* launch failed: %s", hipGetErrorString(e));
+        }
+        return PF_OK;
+    };
+    if (device) return launch(user);
+    return staged_call(h, h->d_ols_io, list, [&] { return launch(io); });
+}
+
 // ---- balanced NNI refinement on the device (pf_bme_nni, pf_bme_nni_device; pf_bme.hip.h, pf_bme_host.h) ----
 
 // every start table is a join table (slots in [0, N), every join of two live clusters, three distinct live slots last)
@@ -2669,6 +2722,7 @@ static int open_device(int device, pf_handle** out) {
         big_lds(reinterpret_cast<const void*>(&k_embed<true>), EMBED_LDS_BYTES);
         big_lds(reinterpret_cast<const void*>(&pffit::k_fit_setup), pffit::SETUP_LDS_MAX);
         big_lds(reinterpret_cast<const void*>(&pffit::k_fit_pairs<true>), pffit::LDS_MAX_BYTES);
+        big_lds(reinterpret_cast<const void*>(&pfols::k_ols_setup), pfols::SETUP_LDS_MAX);
         if (rc) break;
     } while (0);
     if (rc) { pf_destroy(h); return rc; }
@@ -2981,6 +3035,17 @@ int pf_tree_fit_device(pf_handle_t* h, const float* d_preds, const int32_t* d_sl
     return fit_impl(h, true, {d_preds, d_slots, d_lengths, d_patristic, d_rows, d_worst_j, d_status}, B, M, N);
 }
 
+int pf_tree_ols(pf_handle_t* h, const float* preds, const int32_t* slots, int32_t B, int32_t M, int32_t N, double* ols, uint8_t* status) {
+    if (!h) return PF_EINVAL;
+    return ols_impl(h, false, {preds, slots, ols, status}, B, M, N);
+}
+
+int pf_tree_ols_device(pf_handle_t* h, const float* d_preds, const int32_t* d_slots, int32_t B, int32_t M, int32_t N, double* d_ols,
+                       uint8_t* d_status) {
+    if (!h) return PF_EINVAL;
+    return ols_impl(h, true, {d_preds, d_slots, d_ols, d_status}, B, M, N);
+}
+
 int pf_bme_nni(pf_handle_t* h, const float* preds, const int32_t* start_slots, int32_t B, int32_t N, int32_t* slots, double* lengths,
                int32_t* steps, double* tree_length, uint8_t* status) {
     if (!h) return PF_EINVAL;
@@ -3275,6 +3340,7 @@ int pf_profile_reset(pf_handle_t* h) {
     h->bionj_calls = 0;
     h->delta_calls = 0;
     h->fit_calls = 0;
+    h->ols_calls = 0;
     h->bme_calls = 0;
     h->spr_calls = 0;
     h->sup_calls = 0;
@@ -3313,6 +3379,11 @@ int pf_profile_get(pf_handle_t* h, const char* kernel, int64_t* launches, double
     }
     if (std::strcmp(kernel, "tree_fit") == 0) {         // pf_tree_fit / pf_tree_fit_device calls
         if (launches) *launches = h->fit_calls;
+        if (total_ms) *total_ms = 0.0;
+        return PF_OK;
+    }
+    if (std::strcmp(kernel, "tree_ols") == 0) {         // pf_tree_ols / pf_tree_ols_device calls
+        if (launches) *launches = h->ols_calls;
         if (total_ms) *total_ms = 0.0;
         return PF_OK;
     }

@@ -425,6 +425,20 @@ class Engine:
         self._check(fn(self._h, ptr(p), ptr(s), ptr(l), B, M, N, *map(ptr, out)))
         return squeezed(out, flags)
 
+    # -- least-squares branch lengths ---------------------------------------------------------
+    def tree_ols(self, preds: np.ndarray, slots: np.ndarray):
+        """Least-squares branch lengths on the GPU (``pf_tree_ols``): distances ``float32[B, P_N]`` and the slots of join tables
+        ``int32[B, M, T]`` (``[B, T]``: one tree per source, the results drop ``M``; ``[P_N]`` with ``[M, T]`` or ``[T]`` drops ``B``), ``3
+        <= N <= 8,192`` → ``(ols float64[B, M, T], status uint8[B, M])``: the lengths that fit the distances best on each
+        table's topology, in the positions of its own lengths, unclamped - bit for bit ``ols.tree_ols_py`` of every tree and
+        ``hostio.tree_ols_host``; ``ols.ols_scores`` derives what is reported.  A tree with a status (1: not finite, 2: no join
+        table) has zeros.  ``ValueError`` for what the library refuses."""
+        from .ols import ols_arrays, squeezed
+        fn = self._optional("pf_tree_ols")
+        p, s, (B, M, N), flags, out = ols_arrays(preds, slots)
+        self._check(fn(self._h, ptr(p), ptr(s), B, M, N, *map(ptr, out)))
+        return squeezed(out, flags)
+
     # -- balanced NNI refinement -------------------------------------------------------------
     def bme_nni(self, preds: np.ndarray, start_slots: np.ndarray):
         """Balanced minimum-evolution NNI refinement on the GPU (``pf_bme_nni``): distances ``float32[B, P_N]`` and start
@@ -664,3 +678,4 @@ PASS_THROUGHS = {name: "pf_" + name for name in (
     "join_consensus_device", "forward_weighted_device")}
 for _name, _symbol in PASS_THROUGHS.items():
     setattr(Engine, _name, _pass_through(_symbol))
+Engine.tree_ols_device = _pass_through("pf_tree_ols_device")      # (beside the list: a later addition to the header)

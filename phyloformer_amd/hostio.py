@@ -271,6 +271,15 @@ def tree_fit_host(preds: np.ndarray, slots: np.ndarray, lengths: np.ndarray, pat
     return squeezed(out, flags)
 
 
+def tree_ols_host(preds: np.ndarray, slots: np.ndarray):
+    """``Engine.tree_ols`` without a device (``pf_tree_ols_host``), its arguments and results: every tree of every source
+    serially, ``ols.tree_ols_py`` bit for bit.  ``ValueError`` for what the library refuses."""
+    from .ols import ols_arrays, squeezed
+    p, s, (b, m, n), flags, out = ols_arrays(preds, slots)
+    _check_rc("pf_tree_ols_host", _lib().pf_tree_ols_host(ptr(p), ptr(s), b, m, n, *map(ptr, out)), "N, B or M out of range")
+    return squeezed(out, flags)
+
+
 def _joins_host(symbol: str, preds: np.ndarray, *options):
     p, _, (b, n, _t), _single, (slots, lengths, flag) = tree_call(preds, JOINS, _refuse_joins)
     _check_rc(symbol, getattr(_lib(), symbol)(p.ctypes.data, b, n, *options, ptr(slots), ptr(lengths), ptr(flag)))

@@ -71,6 +71,9 @@ DELTA_SHARD_SITES = "--delta cannot be combined with --shard sites: the site-sha
 # the refusals of --fit, in the wording of treekinds.refusals
 FIT_NEEDS_TREES = "--fit measures the trees of --trees: give -t as well"
 FIT_SHARD_SITES = "--fit cannot be combined with --shard sites: the site-sharded runner writes NJ trees only"
+# the refusals of --ols, in the same wording
+OLS_NEEDS_TREES = "--ols re-estimates the branch lengths of the trees of --trees: give -t as well"
+OLS_SHARD_SITES = "--ols cannot be combined with --shard sites: the site-sharded runner writes NJ trees only"
 HEARTBEAT = "#pf-heartbeat"      # stderr line prefix of a site-sharded worker's sign of life (swallowed by the launcher)
 MAX_SEQS = 200     # SEQ2PAIR = seq2pair(200), /root/reference/phyloformer/model.py:39
 
@@ -162,7 +165,7 @@ class DirectoryRunner:
 
     def __init__(self, engine, out_dir: str, trees: bool = False, batch: int = 0,
                  io_threads: int = 4, native_io: bool = True, progress=None, modes: Sequence[Analysis] = (),
-                 bme: bool = False, spr: bool = False, bionj: bool = False, delta: bool = False, fit: bool = False):
+                 bme: bool = False, spr: bool = False, bionj: bool = False, delta: bool = False, fit: bool = False, ols: bool = False):
         # with --trees: <stem>.bme.nwk / .spr.nwk / .bionj.nwk (and .bionj.bme.nwk / .bionj.spr.nwk) as well (treekinds.KINDS)
         self.flags = [flag for flag, on in (("--bionj", bionj), ("--bme", bme), ("--spr", spr)) if on]
         if not trees and self.flags:
@@ -173,6 +176,10 @@ class DirectoryRunner:
         self.delta = delta            # --delta: <stem>.delta.tsv / .delta.phy / .delta.hist.tsv of every launch's distances
         # --fit: <stem>.fit.tsv and, of every written kind, <stem>[.<kind>].fit.taxa.tsv / .patristic.phy (fit.py)
         self.fit = fit
+        if ols and not trees:
+            raise ValueError(OLS_NEEDS_TREES)
+        # --ols: <stem>.ols.tsv and, of every written kind, <stem>[.<kind>].ols.nwk: its table with least-squares lengths (ols.py)
+        self.ols = ols
         self._made = threading.local()        # the tables device_tables made on this GPU thread for the launch in hand
         self.engines = list(engine) if isinstance(engine, (list, tuple)) else [engine]
         self.out_dir = out_dir
@@ -192,6 +199,8 @@ class DirectoryRunner:
             self.stats.update({"delta": 0, "delta_s": 0.0})
         if fit:
             self.stats.update({"fit": 0, "fit_s": 0.0})
+        if ols:
+            self.stats.update({"ols": 0, "ols_s": 0.0})
         self.modes = list(modes)
         for m in self.modes:
             m.bind(self.modes)
@@ -267,6 +276,18 @@ class DirectoryRunner:
         on = {k.name for kinds in self.kind_groups for k in kinds}
         return [k for k in KINDS if k is KINDS[0] or k.name in on]
 
+    def table_of(self, kind: Kind, k: int, pred: np.ndarray, tables: dict) -> Optional[JoinTable]:
+        """On a writer thread, the table behind the written tree of ``kind`` of file ``k`` of a group (three sequences at the
+        least): the device's (``tables``) or, as the tree's text was, joined and refined on the host; None for distances that
+        are not finite."""
+        if tables.get(kind.name) is not None:
+            return tables[kind.name][k]
+        if kind.name in tables:
+            return None
+        search = [kind.search] if kind.search else []
+        slots, lengths, _steps, bad = join_refine(self.host, kind.start, search, pred[None])[kind.search]
+        return None if bad[0] else JoinTable(slots[0], lengths[0], 0)
+
     def fit_arrays(self, engine, n: int, preds: np.ndarray) -> dict:
         """``--fit`` on the GPU thread: ``Engine.tree_fit`` of the launch's distances on the tables that were made on this
         thread (``device_tables``), one call for all their kinds, from ``fit.FIT_DEVICE_MIN`` sequences on; a file without
@@ -303,11 +324,7 @@ class DirectoryRunner:
                 if kind.name in fits:
                     arrays = tuple(a[k] for a in fits[kind.name])
                 elif n >= F.MIN_SEQS:
-                    table = tables[kind.name][k] if tables.get(kind.name) is not None else None
-                    if table is None and kind.name not in tables:
-                        search = [kind.search] if kind.search else []
-                        slots, lengths, _steps, bad = join_refine(self.host, kind.start, search, pred[None])[kind.search]
-                        table = None if bad[0] else JoinTable(slots[0], lengths[0], 0)
+                    table = self.table_of(kind, k, pred, tables)
                     if table is not None:
                         arrays = self.host.tree_fit(pred, table.slots, table.lengths)
                 if arrays is None or arrays[3]:
@@ -319,6 +336,62 @@ class DirectoryRunner:
                 self.put(e.path, kind.files("patristic.phy")[0], self.phylip(tree, ids))
             self.put(e.path, "fit.tsv", F.fit_tsv(lines))
         self.book(fit=len(group), fit_s=time.perf_counter() - t0)
+
+    def ols_arrays(self, engine, n: int, preds: np.ndarray) -> dict:
+        """``--ols`` on the GPU thread: ``Engine.tree_ols`` of the launch's distances on the tables that were made on this
+        thread (``device_tables``), one call for all their kinds, from ``ols.OLS_DEVICE_MIN`` sequences on, followed by one
+        ``Engine.tree_fit`` of every table with its own and with the OLS lengths; a file without a table (distances that are
+        not finite) gets a table of zeros, which is none (status 2).  ``{kind name: (ols, status, rows [.., 2, n, 6], worst_j
+        [.., 2, n])}``; the other kinds are the writer thread's.  Books its seconds."""
+        from . import fit as F, ols as O
+        made = {name: tables for name, tables in getattr(self._made, "tables", {}).items() if tables is not None}
+        if not made or not reaches(O.OLS_DEVICE_MIN, n, F.MIN_SEQS):
+            return {}
+        t0 = time.perf_counter()
+        width, m = F.table_len(n), len(made)
+        slots = np.zeros((len(preds), m, width), dtype=np.int32)
+        lengths = np.zeros((len(preds), m, width), dtype=np.float64)
+        for k, tables in enumerate(made.values()):
+            for b, table in enumerate(tables):
+                if table is not None:
+                    slots[b, k], lengths[b, k] = table.slots, table.lengths
+        best, status = engine.tree_ols(preds, slots)
+        _tree, rows, worst_j, _status = engine.tree_fit(preds, np.concatenate([slots, slots], axis=1),
+                                                        np.concatenate([lengths, best], axis=1), patristic=False)
+        self.book(ols_s=time.perf_counter() - t0)
+        return {name: (best[:, k], status[:, k], rows[:, [k, m + k]], worst_j[:, [k, m + k]]) for k, name in enumerate(made)}
+
+    def _write_ols(self, group: list, preds: np.ndarray, tables: dict, made: dict):
+        """The files of ``--ols`` of some files of a launch, on a writer thread: of every written kind the GPU thread's
+        arrays where it made them (``made``), else the host side's on the kind's table (``table_of``).  ``<stem>[.<kind>].ols.nwk``
+        is the table with the OLS lengths through the call that formats the kind's own tree; ``<stem>.ols.tsv`` has
+        ``ols.ols_scores`` of the unclamped tables.  Fewer than three sequences or distances that are not finite: the kind's own
+        text and ``nan``."""
+        from . import fit as F, ols as O
+        t0 = time.perf_counter()
+        for k, (e, pred) in enumerate(zip(group, preds)):
+            ids = e.ids()
+            n, lines = len(ids), []
+            for kind in self.written_kinds():
+                table = self.table_of(kind, k, pred, tables) if n >= F.MIN_SEQS else None
+                arrays = None
+                if table is not None and kind.name in made:
+                    arrays = tuple(a[k] for a in made[kind.name])
+                elif table is not None:
+                    best, status = self.host.tree_ols(pred, table.slots)
+                    _tree, rows, worst_j, _status = self.host.tree_fit(pred, np.stack([table.slots, table.slots]),
+                                                                       np.stack([table.lengths, best]), patristic=False)
+                    arrays = (best, status, rows, worst_j)
+                if arrays is None or arrays[1]:
+                    scores = O.no_scores()
+                    text = self.nj(pred, ids) if kind is KINDS[0] else self.host.tree_text(kind, pred, ids)[0]
+                else:
+                    scores = O.ols_scores(pred, table.lengths, arrays[0], arrays[2], arrays[3], n)
+                    text = self.newick_of_joins(table.slots, arrays[0], ids)
+                lines.append((kind.name, scores))
+                self.put(e.path, kind.files("ols.nwk")[0], text)
+            self.put(e.path, "ols.tsv", O.ols_tsv(lines))
+        self.book(ols=len(group), ols_s=time.perf_counter() - t0)
 
     def book(self, **amounts):
         """Add to the run's stats from inside a mode's own engine call (takes the runner's lock)."""
@@ -380,6 +453,10 @@ class DirectoryRunner:
             made, fits = dict(self._made.tables), self.fit_arrays(engine, shape[0], preds)
             submit([(self._write_fit, group[k::cap], preds[k::cap], {name: None if t is None else t[k::cap] for name, t in made.items()},
                      {name: tuple(a[k::cap] for a in arrays) for name, arrays in fits.items()}) for k in range(min(cap, len(group)))])
+        if self.ols:
+            made, best = dict(self._made.tables), self.ols_arrays(engine, shape[0], preds)
+            submit([(self._write_ols, group[k::cap], preds[k::cap], {name: None if t is None else t[k::cap] for name, t in made.items()},
+                     {name: tuple(a[k::cap] for a in arrays) for name, arrays in best.items()}) for k in range(min(cap, len(group)))])
         if self.delta:
             arrays = self.delta_arrays(engine, preds)
             submit([(self._write_delta, group[k::cap], None if arrays is None else tuple(a[k::cap] for a in arrays))
@@ -605,6 +682,8 @@ class SiteShardedRunner(DirectoryRunner):
             raise ValueError(DELTA_SHARD_SITES)
         if kw.get("fit"):
             raise ValueError(FIT_SHARD_SITES)
+        if kw.get("ols"):
+            raise ValueError(OLS_SHARD_SITES)
         super().__init__([engine], out_dir, **kw)
         self.group, self.rank, self.world = group, rank, world
         self.stats["site_sharded_over"] = world
@@ -714,7 +793,8 @@ def summarize(stats: dict, load_s: float = 0.0) -> dict:
             **({k: stats[k] for k in ("consensus", "consensus_device")} if "consensus" in stats else {}),
             **({k: stats[k] for k in ("instability", "transfers_device")} if "instability" in stats else {}),
             **({"delta": stats["delta"], "delta_s": round(stats["delta_s"], 6)} if "delta" in stats else {}),
-            **({"fit": stats["fit"], "fit_s": round(stats["fit_s"], 6)} if "fit" in stats else {})}
+            **({"fit": stats["fit"], "fit_s": round(stats["fit_s"], 6)} if "fit" in stats else {}),
+            **({"ols": stats["ols"], "ols_s": round(stats["ols_s"], 6)} if "ols" in stats else {})}
 
 
 def run_multi_device(script: str, argv: List[str], devices: Sequence[int], shard: str = "files") -> Tuple[int, List[dict]]:

@@ -34,5 +34,6 @@ rep = [l for l in r.stderr.splitlines() if l.startswith("{")]
 print(json.dumps({"files": a.n, "shape": [a.seqs, a.sites], "trees": a.trees, "extra": a.extra, "process_wall_s": round(wall, 3),
                   "returncode": r.returncode, "report": json.loads(rep[-1]) if rep else r.stderr[-500:]}))
 assert len(os.listdir(outd)) == a.n * ((2 if a.trees else 1) + (3 if "--delta" in a.extra.split() else 0) +
-                                      (3 if "--fit" in a.extra.split() else 0))      # (--fit with -t alone: the NJ tree's three files)
+                                      (3 if "--fit" in a.extra.split() else 0) +     # (--fit with -t alone: the NJ tree's three files)
+                                      (2 if "--ols" in a.extra.split() else 0))      # (--ols likewise: <stem>.ols.nwk and <stem>.ols.tsv)
 shutil.rmtree(tmp)
