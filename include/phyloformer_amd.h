@@ -675,6 +675,40 @@ int pf_join_consensus_host(const int32_t* rep_slots, const double* rep_lengths, 
                            int32_t percent, int32_t* n_splits, int32_t* count, int32_t* size, int32_t* parent, double* split_length,
                            int32_t* leaf_parent, double* leaf_length, uint8_t* status);
 
+/* ---- tree distances: shared splits (Robinson-Foulds), branch score and weighted RF of K join tables (additive to ABI 5) ----
+ *
+ * How far the K trees of a source are from each other; every tree is a join table in pf_nj_joins' layout, T = 2 (N - 3)
+ * + 3 slots.  phyloformer_amd/treedist.py::join_distances_py states the definition and DESIGN.md section 35 the device
+ * form.  The splits of a table are those of pf_join_supports (N - 3 per tree, the side without sequence 0); the branch
+ * above join t's cluster is at the first p > 2 t + 1 with slots[p] == slots[2 t], the branch of leaf x at the first p with
+ * slots[p] == x (as pf_join_consensus reads them).  For every pair i < j of unflagged trees, mirrored to (j, i):
+ *   slots    int32  [B][K][T]       the trees of every source
+ *   lengths  double [B][K][T]|NULL  their branch lengths (NULL: kf and wrf may be NULL too, only shared is computed)
+ *   flag     uint8  [B][K]|NULL     != 0: the tree does not exist; its table is never read
+ *   shared   int32  [B][K][K]       the splits both trees hold: RF = 2 (N - 3) - 2 shared, nRF = RF / (2 (N - 3))
+ *   kf       double [B][K][K]       Kuhner-Felsenstein branch score: the root of the sum of d^2 over the 3 N - 6 terms d of
+ *                                   treedist.py (the splits of i against j, those of j that i lacks, the N leaf branches)
+ *   wrf      double [B][K][K]       weighted RF: the sum of |d| over the same terms
+ *   status   uint8  [B]             0 ok; 1 an unflagged table of the source is no join table; 2 the hash table failed
+ *                                   (not for valid input) - every result of the source is then zero
+ * The diagonal is N - 3 and +0.0; a pair with a flagged tree, and a flagged tree's diagonal, is -1 and NaN.  The sums run
+ * in a fixed order (64 strided accumulators, then halves) without contraction: the results do not depend on B, on the
+ * chunking or on the entry point, bit for bit.  pf_join_distances takes host arrays, validates every table that is read
+ * as pf_bme_nni validates a start table (PF_EINVAL) and is synchronous.  pf_join_distances_device takes device arrays, is
+ * asynchronous on the handle's stream and validates in the kernel: a slot outside [0, N) or a join of a dead slot never
+ * indexes memory, the source gets status 1.  pf_join_distances_host runs the same kernel bodies serially without a handle
+ * or a device, with the kernel's validation.  Sources run side by side in chunks that fit "ws_limit_mb"; a source always
+ * runs whole.  Refused with PF_EINVAL before any device work: N < 4, N > 16384, B < 1, K < 1 or K > 4096 (so K (N - 3) <
+ * 2^29); NULL buffers (lengths with its two outputs, and flag, may be NULL); a source whose K bitset tables (about N^2 / 8
+ * bytes each) and hash table (8 bytes per slot, at least 2 K (N - 3) slots) exceed "ws_limit_mb" (the message names the
+ * bytes).  pf_profile_get("join_distances") counts the calls of the two handle entry points. */
+int pf_join_distances(pf_handle_t* h, const int32_t* slots, const double* lengths, const uint8_t* flag, int32_t B, int32_t K, int32_t N,
+                      int32_t* shared, double* kf, double* wrf, uint8_t* status);
+int pf_join_distances_device(pf_handle_t* h, const int32_t* d_slots, const double* d_lengths, const uint8_t* d_flag, int32_t B, int32_t K,
+                             int32_t N, int32_t* d_shared, double* d_kf, double* d_wrf, uint8_t* d_status);
+int pf_join_distances_host(const int32_t* slots, const double* lengths, const uint8_t* flag, int32_t B, int32_t K, int32_t N,
+                           int32_t* shared, double* kf, double* wrf, uint8_t* status);
+
 /* ---- site weights: weighted forward, pattern compression, bootstrap on distinct sites (additive to ABI 5) ----
  *
  * Nothing in the network depends on a site's position, and every reduction over sites is a plain sum (the row-attention

@@ -79,6 +79,16 @@ def build_parser():
                              "<stem>.patristic.phy (the tree's path-length distances, cophenetic.phylo of R's ape, a PHYLIP "
                              "matrix); another tree's name stands before the ending (<stem>.bme.fit.taxa.tsv).  Negative branch "
                              "lengths count as they are; up to 8,192 sequences; every other output keeps its bytes")
+    parser.add_argument("--treedist", action="store_true",
+                        help="with -t: how far the written trees are from each other.  Writes <stem>.treedist.tsv, one line per "
+                             "pair of the trees of --trees, --bme, --spr and --bionj (and of --treedist-ref): the Robinson-Foulds "
+                             "distance, that over 2 (N - 3), weighted RF and the Kuhner-Felsenstein branch score; NA with a note "
+                             "where a tree is missing.  With --bootstrap R also <stem>.treedist.reps.tsv (per replicate its rf and "
+                             "kf to the NJ tree and its mean rf to the other replicates) and <stem>.treedist.rf.phy (the square RF "
+                             "matrix over nj, rep1 ..., PHYLIP layout); computed on the GPU for large files")
+    parser.add_argument("--treedist-ref", metavar="DIR", default=None,
+                        help="implies --treedist: also compare with the tree DIR/<stem>.nwk (Newick over exactly the "
+                             "alignment's names, binary; a root of two or three children) as `ref`")
     parser.add_argument("--ols", action="store_true",
                         help="with -t: the ordinary-least-squares branch lengths of every written tree - the lengths that "
                              "reproduce the distances best on that tree's topology (Rzhetsky & Nei 1993, FastME -w OLS), "
@@ -139,6 +149,14 @@ def main(argv=None):
         parser.error(scheduler.OLS_NEEDS_TREES)
     if args.ols and args.shard == "sites":
         parser.error(scheduler.OLS_SHARD_SITES)
+    if args.treedist or args.treedist_ref:
+        from phyloformer_amd import treedist
+        if not args.trees:
+            parser.error(treedist.NEEDS_TREES)
+        if args.shard == "sites":
+            parser.error(treedist.SHARD_SITES)
+        if not (tree_flags or args.treedist_ref or args.bootstrap):
+            parser.error(treedist.NOTHING_TO_COMPARE)
 
     in_dir = os.path.abspath(args.alndir)
     out_dir = os.path.abspath(args.outdir)  # TypeError if omitted, as in the reference (:90)
@@ -214,7 +232,8 @@ def main(argv=None):
     runner = scheduler.DirectoryRunner(engines, out_dir, trees=args.trees, batch=args.batch,
                                        io_threads=args.io_threads, native_io=not args.python_io,
                                        progress=bar.update if bar is not None else None, modes=modes, bme=args.bme, spr=args.spr,
-                                       bionj=args.bionj, delta=args.delta, fit=args.fit, ols=args.ols)
+                                       bionj=args.bionj, delta=args.delta, fit=args.fit, ols=args.ols,
+                                       treedist=args.treedist, treedist_ref=args.treedist_ref)
     try:
         stats = runner.run(paths)
     finally:

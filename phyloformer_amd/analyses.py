@@ -130,6 +130,7 @@ class Bootstrap(Analysis):
             "transfer counts that single out rogue sequences; 0 (default) = off")
     refuses = ((SHARD_SITES, "every replicate would need its own collectives"),)
     call = "bootstrap"
+    treedist = False        # set by a runner with --treedist: <stem>.treedist.reps.tsv / .treedist.rf.phy (treedist.py)
 
     def __init__(self, replicates: int, seed: int = 0, tbe: bool = False, refined: bool = False, consensus: Optional[int] = None,
                  instability: Optional[int] = None):
@@ -234,14 +235,15 @@ class Bootstrap(Analysis):
         sub-batch and their refinement, from ``SUPPORT_DEVICE_MIN`` (``--instability``: ``TRANSFER_DEVICE_MIN``) on the matching
         of every kind whose tables are the device's (NJ's: joined there for it), from ``CONSENSUS_DEVICE_MIN`` on their consensus.
         Returns the columns ``(reps, tables)``: ``tables[b][kind name]`` is a ``SupportTables``, or absent (the writer's work)."""
-        from . import consensus, supports
+        from . import consensus, supports, treedist
         B, R, n = len(preds), self.replicates, shape[0]
         tables = [{} for _ in range(B)]
         refine = [k for k in self.kinds(runner) if k.search is not None and reaches(k.minimum(), n, 4)]
         moves = self.instability is not None
         match = reaches(supports.TRANSFER_DEVICE_MIN if moves else supports.SUPPORT_DEVICE_MIN, n, 4)
         agree = self.consensus is not None and reaches(consensus.CONSENSUS_DEVICE_MIN, n, 4)
-        if not refine and not match and not agree:
+        far = self.treedist and reaches(treedist.reps_minimum(R + 1), n, 4)
+        if not refine and not match and not agree and not far:
             return reps, tables
         t0 = time.perf_counter()
         every = np.concatenate([preds[:, None, :], reps], axis=1).reshape(B * (R + 1), -1)       # own tree first
@@ -249,7 +251,9 @@ class Bootstrap(Analysis):
         matched = agreed = 0
         for kind in [NJ] + refine:
             slots, lengths, _steps, flag = (x.reshape(B, R + 1, *x.shape[1:]) for x in made[kind.search])
-            res = con = None
+            res = con = dist = None
+            if far and kind is NJ:          # (a flagged tree - the file's own too - is never read)
+                dist = engine.join_distances(slots, lengths, flag)
             if match:
                 res = self._match(engine, with_stand_ins(slots[:, 0], flag[:, 0]), slots[:, 1:], flag[:, 1:])
             if agree:
@@ -259,7 +263,7 @@ class Bootstrap(Analysis):
                     continue                                     # no tree of its own: the writer's plain text
                 tables[b][kind.name] = SupportTables(
                     slots[b, 0], lengths[b, 0], slots[b, 1:], flag[b, 1:], None if res is None else tuple(x[b] for x in res),
-                    lengths[b, 1:], None if con is None else tuple(x[b] for x in con))
+                    lengths[b, 1:], None if con is None else tuple(x[b] for x in con), None if dist is None else tuple(x[b] for x in dist))
                 matched += res is not None
                 agreed += con is not None
         runner.book(supports_device=matched, supports_device_s=time.perf_counter() - t0, **({"consensus_device": agreed} if agree else {}),
@@ -312,12 +316,36 @@ class Bootstrap(Analysis):
                     **({"consensus": len(rows) * len(kinds)} if self.consensus is not None else {}),
                     **({"instability": len(rows) * len(kinds)} if self.instability is not None else {}))
 
+    def write_treedist(self, runner, shape, rows):
+        """Some files of a sub-batch on a writer thread, with ``--treedist``: ``<stem>.treedist.reps.tsv`` and
+        ``<stem>.treedist.rf.phy`` over ``[nj tree, replicate 1 .. R]`` - the GPU thread's distances where it left them,
+        else the host side's on the NJ tables; ``NA`` throughout for fewer than four sequences."""
+        from . import treedist
+        n, R = shape[0], self.replicates
+        for entry, pred, reps, given in rows:
+            dist = treedist.no_distances(R + 1)
+            if n >= treedist.MIN_SEQS:
+                table = given["nj"] if "nj" in given else self._host_tables(runner, NJ, pred, reps)
+                dist = table.distances
+                if dist is None:
+                    own = table.slots is None
+                    slots = np.concatenate([(np.zeros_like(table.rep_slots[0]) if own else table.slots)[None], table.rep_slots])
+                    dist = runner.host.join_distances(slots, np.concatenate([np.asarray(table.lengths)[None], table.rep_lengths]),
+                                                      np.concatenate([[own], np.asarray(table.rep_flag, dtype=bool)]))
+            runner.put(entry.path, "treedist.reps.tsv", treedist.reps_tsv(n, dist))
+            runner.put(entry.path, "treedist.rf.phy", treedist.rf_phylip(n, dist))
+
     def jobs(self, runner, shape, part, preds, reps, tables=None):
-        if tables is None:
-            return super().jobs(runner, shape, part, preds, reps)
-        rows = list(zip(part, preds, reps, tables))
         cap = runner.writer_cap()       # (the host twins of R searches per file: spread over the writers, as _write_trees)
-        return [(self.write_supports, runner, shape, rows[k::cap]) for k in range(min(cap, len(rows)))]
+        if tables is None:
+            out = super().jobs(runner, shape, part, preds, reps)
+        else:
+            rows = list(zip(part, preds, reps, tables))
+            out = [(self.write_supports, runner, shape, rows[k::cap]) for k in range(min(cap, len(rows)))]
+        if self.treedist:
+            rows = list(zip(part, preds, reps, tables if tables is not None else [{}] * len(part)))
+            out += [(self.write_treedist, runner, shape, rows[k::cap]) for k in range(min(cap, len(rows)))]
+        return out
 
 
 class Windows(Analysis):

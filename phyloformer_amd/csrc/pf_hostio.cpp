@@ -31,6 +31,7 @@
 #include "pf_ols_host.h"
 #include "pf_support_host.h"
 #include "pf_consensus_host.h"
+#include "pf_treedist_host.h"
 
 namespace {
 
@@ -1085,6 +1086,41 @@ int pf_join_consensus_host(const int32_t* rep_slots, const double* rep_lengths, 
             std::fill(ones, zeros, (char)0xff);
             std::fill(zeros, c.at, (char)0);
             pfcon::serial_source(a, 0, tile.data());
+        }
+        return PF_OK;
+    } catch (...) { return PF_ENOMEM; }
+}
+
+// Tree distances without a device: the bodies of pf_treedist.hip.h's kernels run serially, one
+// source at a time - the same integers and the same doubles as pf_join_distances.  Tables are checked by the bodies
+// themselves, as pf_join_distances_device's are: a source with a table that is no join table gets status 1 and zeros.
+// Twin of phyloformer_amd/treedist.py::join_distances_py.
+int pf_join_distances_host(const int32_t* slots, const double* lengths, const uint8_t* flag, int32_t B, int32_t K, int32_t N,
+                           int32_t* shared, double* kf, double* wrf, uint8_t* status) {
+    if (!slots || !shared || !status || (lengths && (!kf || !wrf)) || B < 1 || K < 1 || K > pftd::MAX_K || N < pftd::MIN_N ||
+        N > pftd::MAX_N)
+        return PF_EINVAL;
+    const size_t T = (size_t)pfnj::table_len(N), b = (size_t)B, k = (size_t)K;
+    size_t total = 0;
+    if (__builtin_mul_overflow(b * k, T * sizeof(double), &total) || __builtin_mul_overflow(b * k, k * sizeof(double), &total)) return PF_EINVAL;
+    try {
+        pftd::Args a{};
+        a.c.rep_slots = slots; a.c.rep_lengths = lengths; a.c.rep_flag = flag; a.c.status = status;
+        a.c.N = N; a.c.R = K; a.c.nb = 1;
+        a.c.cap = pfcon::capacity_of((int64_t)K * ((int64_t)N - 3));
+        a.shared = shared; a.kf = kf; a.wrf = wrf;
+        std::fill(shared, shared + b * k * k, 0);
+        if (lengths) { std::fill(kf, kf + b * k * k, 0.0); std::fill(wrf, wrf + b * k * k, 0.0); }
+        // the state of one source, reused from source to source
+        std::vector<unsigned char> state(pftd::state_bytes(N, K));
+        pfspan::Carve c{reinterpret_cast<char*>(state.data())};
+        pftd::state_arrays(c, a, 1, k, N, (size_t)a.c.cap);
+        char *ones = reinterpret_cast<char*>(a.c.slot_of), *zeros = reinterpret_cast<char*>(a.c.tally);
+        for (int32_t src = 0; src < B; ++src) {
+            a.c.b0 = src;
+            std::fill(ones, zeros, (char)0xff);
+            std::fill(zeros, c.at, (char)0);
+            pftd::serial_source(a, 0);
         }
         return PF_OK;
     } catch (...) { return PF_ENOMEM; }

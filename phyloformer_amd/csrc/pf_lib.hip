@@ -56,6 +56,7 @@
 #include "pf_bme.hip.h"
 #include "pf_support.hip.h"
 #include "pf_consensus.hip.h"
+#include "pf_treedist.hip.h"
 #include "pf_weights.hip.h"
 #include "pf_weights_host.h"
 #include "pf_host_prep.h"
@@ -300,6 +301,10 @@ struct pf_handle {
     // carve) and the staging of the host entry point's tables, lengths and results
     Buffer<char> d_con{buffers}, d_con_io{buffers};
     int64_t con_calls = 0;       // calls since the last pf_profile_reset ("join_consensus")
+    // pf_join_distances / pf_join_distances_device (grow-only): the state of one chunk of sources (pf_treedist.hip.h:
+    // carve) and the staging of the host entry point's tables, lengths and results
+    Buffer<char> d_td{buffers}, d_td_io{buffers};
+    int64_t td_calls = 0;        // calls since the last pf_profile_reset ("join_distances")
     // weighted forwards (grow-only): the weight rows of a host call or of one chunk of derived alignments, what
     // k_weight_sums made of a call's rows ([..][4], pf_weights.hip.h), and the weight table of pf_forward_sites_weighted
     Buffer<float> d_w{buffers}, d_wst{buffers}, d_wtab{buffers};
@@ -2668,6 +2673,76 @@ int consensus_impl(pf_handle* h, bool device, const pfcon::Tables& user, int B, 
     return staged_call(h, h->d_con_io, list, [&] { return consensus_launch(h, io, B, R, N, percent, nb); });
 }
 
+// ---- distances between the join tables of a source (pf_join_distances, pf_join_distances_device; pf_treedist.hip.h,
+// DESIGN.md section 35) ----
+
+static_assert(pftd::MAX_N == pfbme::MAX_N, "a table that pf_bme_nni takes is one pf_join_distances takes");
+// (state_bytes: the least a call needs - a source of one tree; the plan below sizes a source of K)
+const TreeSearch TD_SEARCH{"tree distances", pftd::MAX_N, pftd::min_state_bytes, pftd::TD_MAX_Y,
+                           "the bitset table of one tree and its hash table"};
+
+// The chunks of a call: `nb` whole sources side by side.  A source always runs whole - every pair needs both trees'
+// indices into one hash table -, so one whose K tables and hash table exceed the workspace limit is refused.
+int plan_distances(pf_handle* h, int B, int K, int N, int* nb) {
+    if (N < 4) return fail(h, PF_EINVAL, "tree distances need N >= 4 sequences (got %d): a tree of 3 has no split", N);
+    int chunk = 0;
+    const int rc0 = check_tree_shape(h, TD_SEARCH, B, N, &chunk);
+    if (rc0) return rc0;
+    if (K < 1) return fail(h, PF_EINVAL, "tree distances need K >= 1 trees (got %d)", K);
+    if (K > pftd::MAX_K) return fail(h, PF_EINVAL, "tree distances take at most %d trees of one source (got K=%d)", pftd::MAX_K, K);
+    size_t n = 0;
+    if (!mul_size((size_t)B, (size_t)K, (size_t)pfnj::table_len(N) * sizeof(double), &n) ||
+        !mul_size((size_t)B, (size_t)K * (size_t)K, sizeof(double), &n))
+        return fail(h, PF_EINVAL, "B=%d sources of K=%d trees overflow the address space", B, K);
+    const size_t per = pftd::state_bytes(N, K);
+    if ((int64_t)per > h->ws_limit_bytes)
+        return fail(h, PF_EINVAL, "tree distances of K=%d trees of N=%d sequences need %zu bytes of state per source (its K bitset "
+                                  "tables, their indices and the hash table; a source runs whole), above the workspace limit of "
+                                  "%lld bytes (option ws_limit_mb)", K, N, per, (long long)h->ws_limit_bytes);
+    *nb = (int)std::min<size_t>((size_t)std::min(B, pftd::TD_MAX_Y), (size_t)h->ws_limit_bytes / per);
+    return PF_OK;
+}
+
+// all chunks of a call on device arrays `d`, enqueued on h->stream
+int distances_launch(pf_handle* h, const pftd::Tables& d, int B, int K, int N, int nb) {
+    const int rc2 = h->d_td.reserve(h, (size_t)nb * pftd::state_bytes(N, K));
+    if (rc2) return rc2;
+    h->cur = h->stream;
+    const size_t cells = (size_t)B * (size_t)K * (size_t)K;
+    // (a source with a status keeps these zeros)
+    HIPCHK(h, hipMemsetAsync(d.shared, 0, cells * sizeof(int32_t), h->stream));
+    if (d.lengths) {
+        HIPCHK(h, hipMemsetAsync(d.kf, 0, cells * sizeof(double), h->stream));
+        HIPCHK(h, hipMemsetAsync(d.wrf, 0, cells * sizeof(double), h->stream));
+    }
+    pftd::Args a{};
+    a.c.rep_slots = d.slots; a.c.rep_lengths = d.lengths; a.c.rep_flag = d.flag; a.c.status = d.status;
+    a.c.N = N; a.c.R = K;
+    a.c.cap = pfcon::capacity_of((int64_t)K * ((int64_t)N - 3));
+    a.shared = d.shared; a.kf = d.kf; a.wrf = d.wrf;
+    // (chunks follow each other on the stream, so the next one may reuse the state)
+    for (int b0 = 0; b0 < B; b0 += nb) {
+        a.c.b0 = b0; a.c.nb = std::min(nb, B - b0);
+        const pfcon::Fill f = pftd::carve(a, h->d_td);
+        const hipError_t e = pftd::launch_chunk(h->stream, a, f);
+        if (e != hipSuccess) return fail(h, PF_EHIP, "k_td_* launch failed: %s", hipGetErrorString(e));
+    }
+    return PF_OK;
+}
+
+// the caller's arrays on the device (asynchronous) or on the host
+int distances_impl(pf_handle* h, bool device, const pftd::Tables& user, int B, int K, int N) {
+    pftd::Tables io{};
+    auto list = [&](auto& v) { pftd::staging_arrays(v, io, user, (size_t)B, (size_t)K, N); };
+    if (pfspan::missing(list)) return fail(h, PF_EINVAL, "null buffer");
+    int nb = 0;
+    int rc2 = plan_distances(h, B, K, N, &nb);
+    if (rc2 || (!device && (rc2 = check_join_tables(h, nullptr, user.slots, user.flag, B, K, N)))) return rc2;
+    HIPCHK(h, hipSetDevice(h->device));
+    ++h->td_calls;
+    if (device) return distances_launch(h, user, B, K, N, nb);
+    return staged_call(h, h->d_td_io, list, [&] { return distances_launch(h, io, B, K, N, nb); });
+}
 
 }  // namespace
 
@@ -3098,6 +3173,18 @@ int pf_join_consensus_device(pf_handle_t* h, const int32_t* d_rep_slots, const d
                                     d_leaf_length, d_status}, B, R, N, percent);
 }
 
+int pf_join_distances(pf_handle_t* h, const int32_t* slots, const double* lengths, const uint8_t* flag, int32_t B, int32_t K, int32_t N,
+                      int32_t* shared, double* kf, double* wrf, uint8_t* status) {
+    if (!h) return PF_EINVAL;
+    return distances_impl(h, false, {slots, lengths, flag, shared, kf, wrf, status}, B, K, N);
+}
+
+int pf_join_distances_device(pf_handle_t* h, const int32_t* d_slots, const double* d_lengths, const uint8_t* d_flag, int32_t B, int32_t K,
+                             int32_t N, int32_t* d_shared, double* d_kf, double* d_wrf, uint8_t* d_status) {
+    if (!h) return PF_EINVAL;
+    return distances_impl(h, true, {d_slots, d_lengths, d_flag, d_shared, d_kf, d_wrf, d_status}, B, K, N);
+}
+
 int pf_join_transfers(pf_handle_t* h, const int32_t* ref_slots, const int32_t* rep_slots, const uint8_t* rep_flag, int32_t B, int32_t R,
                       int32_t N, int32_t cutoff_percent, int32_t* count, int64_t* transfer, int32_t* depth, int64_t* moves, int32_t* used,
                       int32_t* capped, int32_t* branch_moves, uint8_t* status) {
@@ -3346,6 +3433,7 @@ int pf_profile_reset(pf_handle_t* h) {
     h->sup_calls = 0;
     h->transfer_calls = 0;
     h->con_calls = 0;
+    h->td_calls = 0;
     return PF_OK;
 }
 
@@ -3404,6 +3492,11 @@ int pf_profile_get(pf_handle_t* h, const char* kernel, int64_t* launches, double
     }
     if (std::strcmp(kernel, "join_transfers") == 0) {   // pf_join_transfers / pf_join_transfers_device calls
         if (launches) *launches = h->transfer_calls;
+        if (total_ms) *total_ms = 0.0;
+        return PF_OK;
+    }
+    if (std::strcmp(kernel, "join_distances") == 0) {   // pf_join_distances / pf_join_distances_device calls
+        if (launches) *launches = h->td_calls;
         if (total_ms) *total_ms = 0.0;
         return PF_OK;
     }

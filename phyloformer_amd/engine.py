@@ -14,7 +14,7 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 
 from . import cabi
-from .treearrays import (JOINS, REFINE, consensus_arrays, consensus_outputs, ptr, support_arrays, support_outputs, transfer_outputs,
+from .treearrays import (JOINS, REFINE, consensus_arrays, consensus_outputs, distance_arrays, distance_outputs, ptr, support_arrays, support_outputs, transfer_outputs,
                          tree_call, unbatched)
 from .weights import ModelWeights
 
@@ -504,6 +504,20 @@ class Engine:
         self._check(fn(self._h, rep.ctypes.data, ptr(lengths), ptr(flag), B, R, N, int(percent), *ptrs))
         return unbatched(out, single)
 
+    # -- distances between join tables -------------------------------------------------------
+    def join_distances(self, slots: np.ndarray, lengths: Optional[np.ndarray] = None, flag: Optional[np.ndarray] = None):
+        """Tree distances on the GPU (``pf_join_distances``): join tables ``int32[B, K, T]``, their lengths ``float64[B, K,
+        T]`` or None, ``flag bool[B, K]`` or None (``[K, T]`` / ``[K]`` drop ``B``) → ``(shared int32[B, K, K], kf float64[B,
+        K, K] or None, wrf float64[B, K, K] or None, status uint8[B])``: per pair of a source's trees the splits both hold
+        (``RF = 2 (N - 3) - 2 shared``), the Kuhner-Felsenstein branch score and weighted RF - ``treedist.join_distances_py``,
+        the same integers and the same doubles, bit for bit, as ``hostio.join_distances_host``.  A table that is no join
+        table is refused (``ValueError``)."""
+        fn = self._optional("pf_join_distances")
+        s, l, f, (B, K, N), single = distance_arrays(slots, lengths, flag)
+        out, ptrs = distance_outputs(B, K, l is not None)
+        self._check(fn(self._h, s.ctypes.data, ptr(l), ptr(f), B, K, N, *ptrs))
+        return unbatched(out, single)
+
     # -- site weights -----------------------------------------------------------------------
     @staticmethod
     def _weights(w, shape, what: str) -> np.ndarray:
@@ -679,3 +693,4 @@ PASS_THROUGHS = {name: "pf_" + name for name in (
 for _name, _symbol in PASS_THROUGHS.items():
     setattr(Engine, _name, _pass_through(_symbol))
 Engine.tree_ols_device = _pass_through("pf_tree_ols_device")      # (beside the list: a later addition to the header)
+Engine.join_distances_device = _pass_through("pf_join_distances_device")

@@ -16,7 +16,7 @@ import numpy as np
 
 from .cabi import CONSTANTS
 from .engine import load_library
-from .treearrays import (JOINS, REFINE, consensus_arrays, consensus_outputs, ptr, support_arrays, support_outputs,
+from .treearrays import (JOINS, REFINE, consensus_arrays, consensus_outputs, distance_arrays, distance_outputs, ptr, support_arrays, support_outputs,
                          transfer_outputs, tree_call, unbatched)
 
 # library functions of this module that are not part of include/phyloformer_amd.h (bound here, not in
@@ -318,6 +318,17 @@ def join_consensus_host(rep_slots, rep_lengths=None, rep_flag=None, percent: int
     _check_rc("pf_join_consensus_host",
               _lib().pf_join_consensus_host(rep.ctypes.data, ptr(lengths), ptr(flag), b, r, n, int(percent), *ptrs),
               f"a threshold of {percent} percent outside 50 .. 99")
+    return unbatched(out, single)
+
+
+def join_distances_host(slots, lengths=None, flag=None):
+    """``pf_join_distances_host``: ``Engine.join_distances`` without a device - the same bodies run serially, the integers
+    and (bit for bit) the doubles of ``treedist.join_distances_py``; a source with a table that is no join table comes back
+    with status 1 and zeros.  ``ValueError`` for what the library refuses (``N < 4``, ``K > 4096``)."""
+    s, l, f, (b, k, n), single = distance_arrays(slots, lengths, flag)
+    out, ptrs = distance_outputs(b, k, l is not None)
+    _check_rc("pf_join_distances_host", _lib().pf_join_distances_host(s.ctypes.data, ptr(l), ptr(f), b, k, n, *ptrs),
+              f"K = {k} trees or N = {n} sequences out of range")
     return unbatched(out, single)
 
 

@@ -165,7 +165,8 @@ class DirectoryRunner:
 
     def __init__(self, engine, out_dir: str, trees: bool = False, batch: int = 0,
                  io_threads: int = 4, native_io: bool = True, progress=None, modes: Sequence[Analysis] = (),
-                 bme: bool = False, spr: bool = False, bionj: bool = False, delta: bool = False, fit: bool = False, ols: bool = False):
+                 bme: bool = False, spr: bool = False, bionj: bool = False, delta: bool = False, fit: bool = False, ols: bool = False,
+                 treedist: bool = False, treedist_ref: Optional[str] = None):
         # with --trees: <stem>.bme.nwk / .spr.nwk / .bionj.nwk (and .bionj.bme.nwk / .bionj.spr.nwk) as well (treekinds.KINDS)
         self.flags = [flag for flag, on in (("--bionj", bionj), ("--bme", bme), ("--spr", spr)) if on]
         if not trees and self.flags:
@@ -180,6 +181,18 @@ class DirectoryRunner:
             raise ValueError(OLS_NEEDS_TREES)
         # --ols: <stem>.ols.tsv and, of every written kind, <stem>[.<kind>].ols.nwk: its table with least-squares lengths (ols.py)
         self.ols = ols
+        # --treedist: <stem>.treedist.tsv, every pair of the written kinds and the tree of --treedist-ref DIR (treedist.py)
+        self.treedist, self.treedist_ref = bool(treedist or treedist_ref), treedist_ref
+        if self.treedist:
+            from . import treedist as TD
+            from .analyses import Bootstrap
+            boots = [m for m in modes if isinstance(m, Bootstrap)]
+            if not trees:
+                raise ValueError(TD.NEEDS_TREES)
+            if not self.kind_groups and not treedist_ref and not boots:
+                raise ValueError(TD.NOTHING_TO_COMPARE)
+            for m in boots:
+                m.treedist = True
         self._made = threading.local()        # the tables device_tables made on this GPU thread for the launch in hand
         self.engines = list(engine) if isinstance(engine, (list, tuple)) else [engine]
         self.out_dir = out_dir
@@ -201,6 +214,8 @@ class DirectoryRunner:
             self.stats.update({"fit": 0, "fit_s": 0.0})
         if ols:
             self.stats.update({"ols": 0, "ols_s": 0.0})
+        if self.treedist:
+            self.stats.update({"treedist": 0, "treedist_s": 0.0, "treedist_ref_missing": 0})
         self.modes = list(modes)
         for m in self.modes:
             m.bind(self.modes)
@@ -393,6 +408,87 @@ class DirectoryRunner:
             self.put(e.path, "ols.tsv", O.ols_tsv(lines))
         self.book(ols=len(group), ols_s=time.perf_counter() - t0)
 
+    def compared(self) -> List[str]:
+        """The trees of ``<stem>.treedist.tsv``: every written kind, then ``ref`` with ``--treedist-ref``."""
+        return [k.name for k in self.written_kinds()] + (["ref"] if self.treedist_ref else [])
+
+    def reference_table(self, path: str, ids: List[str]):
+        """``(JoinTable, None)`` of ``DIR/<stem>.nwk``, or ``(None, the reason it has none)``: missing, unreadable, refused."""
+        from . import treedist as TD
+        try:
+            with open(os.path.join(self.treedist_ref, f"{Path(path).stem}.nwk"), errors="replace") as fh:
+                return JoinTable(*TD.table_of_newick(fh.read(), ids), 0), None
+        except OSError as exc:
+            reason = f"no reference tree ({exc.strerror or type(exc).__name__})"
+        except ValueError as exc:
+            reason = " ".join(str(exc).split())
+        self.book(treedist_ref_missing=1)
+        return None, reason
+
+    @staticmethod
+    def treedist_source(tables: list, reasons: list):
+        """The trees of one file for ``join_distances``: a tree without a table is passed flagged, with a table of zeros."""
+        width = next((len(t.slots) for t in tables if t is not None), 0)
+        slots, lengths = np.zeros((len(tables), width), dtype=np.int32), np.zeros((len(tables), width), dtype=np.float64)
+        for m, t in enumerate(tables):
+            if t is not None:
+                slots[m], lengths[m] = t.slots, t.lengths
+        return slots, lengths, np.array([r is not None for r in reasons], dtype=bool)
+
+    def treedist_arrays(self, engine, n: int, preds: np.ndarray, group: list):
+        """``--treedist`` on the GPU thread, from ``treedist.TREEDIST_DEVICE_MIN`` sequences on and where every refined kind's
+        table was made on this thread (``device_tables``): the NJ tables joined here, the reference trees read, one
+        ``Engine.join_distances`` for the launch.  ``(distances [B, ...], reasons [B][K])`` or None: the writer thread's."""
+        from . import treedist as TD
+        made = getattr(self._made, "tables", {})
+        kinds = self.written_kinds()
+        if len(self.compared()) < 2 or not reaches(TD.TREEDIST_DEVICE_MIN, n, TD.MIN_SEQS) or any(made.get(k.name) is None for k in kinds[1:]):
+            return None                  # (one tree has no pair: the header alone, the writer's)
+        t0 = time.perf_counter()
+        slots, lengths, bad = engine.nj_joins(preds)
+        rows, reasons = [], []
+        for b, e in enumerate(group):
+            tables = [None if bad[b] else JoinTable(slots[b], lengths[b], 0)] + [made[k.name][b] for k in kinds[1:]]
+            why = [None if t is not None else TD.NOT_FINITE for t in tables]
+            if self.treedist_ref:
+                ref, reason = self.reference_table(e.path, e.ids())
+                tables.append(ref)
+                why.append(reason)
+            rows.append(self.treedist_source(tables, why))
+            reasons.append(why)
+        if not any(len(r[0][0]) for r in rows):
+            return None
+        width = max(r[0].shape[1] for r in rows)
+        rows = [r if r[0].shape[1] else (np.zeros((len(r[2]), width), np.int32), np.zeros((len(r[2]), width)), r[2]) for r in rows]
+        out = engine.join_distances(*(np.stack(x) for x in zip(*rows)))
+        self.book(treedist_s=time.perf_counter() - t0)
+        return out, reasons
+
+    def _write_treedist(self, group: list, preds: np.ndarray, tables: dict, made):
+        """``<stem>.treedist.tsv`` of some files of a launch, on a writer thread: the GPU thread's distances where it made
+        them (``made``), else the host side's on every kind's table (``table_of``) and the reference tree; ``NA`` with a
+        note for fewer than four sequences, a kind without a table and a reference tree that is missing or refused."""
+        from . import treedist as TD
+        t0 = time.perf_counter()
+        names = self.compared()
+        for k, (e, pred) in enumerate(zip(group, preds)):
+            ids = e.ids()
+            n = len(ids)
+            if n < TD.MIN_SEQS or len(names) < 2:
+                dist, reasons = None, [TD.FEW_SEQUENCES] * len(names)
+            elif made is not None:
+                dist, reasons = tuple(a[k] for a in made[0]), made[1][k]
+            else:
+                trees = [self.table_of(kind, k, pred, tables) for kind in self.written_kinds()]
+                reasons = [None if t is not None else TD.NOT_FINITE for t in trees]
+                if self.treedist_ref:
+                    ref, reason = self.reference_table(e.path, ids)
+                    trees.append(ref)
+                    reasons.append(reason)
+                dist = self.host.join_distances(*self.treedist_source(trees, reasons)) if any(t is not None for t in trees) else None
+            self.put(e.path, "treedist.tsv", TD.treedist_tsv(names, n, dist, reasons))
+        self.book(treedist=len(group), treedist_s=time.perf_counter() - t0)
+
     def book(self, **amounts):
         """Add to the run's stats from inside a mode's own engine call (takes the runner's lock)."""
         with self._lock:
@@ -457,6 +553,10 @@ class DirectoryRunner:
             made, best = dict(self._made.tables), self.ols_arrays(engine, shape[0], preds)
             submit([(self._write_ols, group[k::cap], preds[k::cap], {name: None if t is None else t[k::cap] for name, t in made.items()},
                      {name: tuple(a[k::cap] for a in arrays) for name, arrays in best.items()}) for k in range(min(cap, len(group)))])
+        if self.treedist:
+            made, dists = dict(self._made.tables), self.treedist_arrays(engine, shape[0], preds, group)
+            submit([(self._write_treedist, group[k::cap], preds[k::cap], {name: None if t is None else t[k::cap] for name, t in made.items()},
+                     None if dists is None else (tuple(a[k::cap] for a in dists[0]), dists[1][k::cap])) for k in range(min(cap, len(group)))])
         if self.delta:
             arrays = self.delta_arrays(engine, preds)
             submit([(self._write_delta, group[k::cap], None if arrays is None else tuple(a[k::cap] for a in arrays))
@@ -684,6 +784,9 @@ class SiteShardedRunner(DirectoryRunner):
             raise ValueError(FIT_SHARD_SITES)
         if kw.get("ols"):
             raise ValueError(OLS_SHARD_SITES)
+        if kw.get("treedist") or kw.get("treedist_ref"):
+            from .treedist import SHARD_SITES as TREEDIST_SHARD_SITES
+            raise ValueError(TREEDIST_SHARD_SITES)
         super().__init__([engine], out_dir, **kw)
         self.group, self.rank, self.world = group, rank, world
         self.stats["site_sharded_over"] = world
@@ -794,7 +897,9 @@ def summarize(stats: dict, load_s: float = 0.0) -> dict:
             **({k: stats[k] for k in ("instability", "transfers_device")} if "instability" in stats else {}),
             **({"delta": stats["delta"], "delta_s": round(stats["delta_s"], 6)} if "delta" in stats else {}),
             **({"fit": stats["fit"], "fit_s": round(stats["fit_s"], 6)} if "fit" in stats else {}),
-            **({"ols": stats["ols"], "ols_s": round(stats["ols_s"], 6)} if "ols" in stats else {})}
+            **({"ols": stats["ols"], "ols_s": round(stats["ols_s"], 6)} if "ols" in stats else {}),
+            **({"treedist": stats["treedist"], "treedist_s": round(stats["treedist_s"], 6),
+                "treedist_ref_missing": stats["treedist_ref_missing"]} if "treedist" in stats else {})}
 
 
 def run_multi_device(script: str, argv: List[str], devices: Sequence[int], shard: str = "files") -> Tuple[int, List[dict]]:

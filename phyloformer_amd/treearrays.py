@@ -108,3 +108,31 @@ def consensus_outputs(b: int, n: int, lengths: bool):
            np.zeros((b, s), dtype=np.int32), np.zeros((b, s), dtype=np.float64) if lengths else None,
            np.zeros((b, n), dtype=np.int32), np.zeros((b, n), dtype=np.float64) if lengths else None, np.zeros(b, dtype=np.uint8))
     return out, [ptr(x) for x in out]
+
+
+def distance_arrays(slots, lengths, flag):
+    """The arguments of the three ``pf_join_distances`` entry points, checked: ``(slots int32[B, K, T], lengths float64[B, K,
+    T] or None, flag uint8[B, K] or None, (B, K, N), single)``."""
+    s = np.ascontiguousarray(np.asarray(slots, dtype=np.int32))
+    single = s.ndim == 2
+    if single:
+        s = s[None]
+    if s.ndim != 3:
+        raise ValueError(f"expected join tables [B, K, T] or [K, T], got {s.shape}")
+    b, k, t = s.shape
+    n = (t - 3) // 2 + 3
+    if t < 5 or 2 * (n - 3) + 3 != t or b < 1 or k < 1:
+        raise ValueError(f"{t} slots are not the join table of N >= 4 sequences, or no source or tree ({b}, {k})")
+    l = f = None
+    if lengths is not None:
+        l = np.ascontiguousarray(np.asarray(lengths, dtype=np.float64).reshape(b, k, t))
+    if flag is not None:
+        f = np.ascontiguousarray(np.asarray(flag).astype(bool).astype(np.uint8).reshape(b, k))
+    return s, l, f, (b, k, n), single
+
+
+def distance_outputs(b: int, k: int, lengths: bool):
+    """The results of a ``pf_join_distances`` call, zeroed, and their addresses in the order of the C arguments."""
+    out = (np.zeros((b, k, k), dtype=np.int32), np.zeros((b, k, k), dtype=np.float64) if lengths else None,
+           np.zeros((b, k, k), dtype=np.float64) if lengths else None, np.zeros(b, dtype=np.uint8))
+    return out, [ptr(x) for x in out]

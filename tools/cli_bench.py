@@ -35,5 +35,7 @@ print(json.dumps({"files": a.n, "shape": [a.seqs, a.sites], "trees": a.trees, "e
                   "returncode": r.returncode, "report": json.loads(rep[-1]) if rep else r.stderr[-500:]}))
 assert len(os.listdir(outd)) == a.n * ((2 if a.trees else 1) + (3 if "--delta" in a.extra.split() else 0) +
                                       (3 if "--fit" in a.extra.split() else 0) +     # (--fit with -t alone: the NJ tree's three files)
-                                      (2 if "--ols" in a.extra.split() else 0))      # (--ols likewise: <stem>.ols.nwk and <stem>.ols.tsv)
+                                      (2 if "--ols" in a.extra.split() else 0) +     # (--ols likewise: <stem>.ols.nwk and <stem>.ols.tsv)
+                                      (1 if "--bme" in a.extra.split() else 0) +     # (<stem>.bme.nwk: the second tree of --treedist)
+                                      (1 if "--treedist" in a.extra.split() else 0)) # (<stem>.treedist.tsv)
 shutil.rmtree(tmp)
