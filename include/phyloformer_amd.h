@@ -183,6 +183,12 @@ const char* pf_last_error(const pf_handle_t* h);
  *                      alignment through the fused launch; 2 = every alignment through the split route, even one without a
  *                      repeat (tests).  Site-sharded and emulated ranks route from the classes of their own site range.
  *                      Weighted and site-map forwards, "embed_mfma" and "materialize_x0" stay on the fused launch.
+ *   "stats_dedup" int  default 1: the row statistics of an alignment on the split route ("main_dedup") are formed once per
+ *                      DISTINCT column of a pair row as well - v, q' and k' per distinct token into an on-chip table, then
+ *                      every site reduced in place, in the lanes and partial slots of the original tiling (k_row_stats): no
+ *                      sum changes its order, the results are the same bits.  Alignments with more distinct columns than
+ *                      the table holds (ROW_STATS_KMAX, csrc/pf_layout.h) keep the statistics launch; the choice is made
+ *                      per alignment on the device.  0 = every split alignment through the statistics launch (A/B runs).
  * Test / tool switches, not part of the contract:
  *   "colstats_ring" int  0 = k_colstats prefetches its rows through registers instead of the per-wave LDS ring (the
  *                      same bits; A/B and counter runs)

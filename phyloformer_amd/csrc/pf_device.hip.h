@@ -1501,6 +1501,235 @@ __global__ void __launch_bounds__(256) k_head_parts(MainArgs a) {
     }
 }
 
+// ---- option "stats_dedup": the split route's row statistics, per pair row ---------------------------------------
+// k_main<MODE_STATS> does the whole per-token half of the statistics - 256 B of x, LayerNorm, the hi/lo split, 36 MFMAs,
+// elu + 1 - for every site of every pair, although a token's v, q' and k' are those of its class's first site: only the
+// two transposing reductions and the spart slot depend on where a token sits.  k_row_stats does the per-token half once
+// per distinct column (pf_layout.h, above ROW_STATS_KMAX, for the work item, the LDS and the two phases).  The values do
+// not depend on the MFMA column or the tile a token is computed in (the compact launch and k_head_parts rest on the
+// same), phase 2 puts every site's terms into the lane, the mask and the reductions of the original tiling and stores
+// from the same lanes to the same slots: the same bits as the statistics launch.
+//   One difference without effect: a lane outside the part contributes +0 here; there it contributes 0 * v of the token it
+//   was clamped onto, i.e. a zero of v's sign.  The sign of a zero reaches a sum only where every product of the part
+//   with a token behind it is exactly zero as well (x + (-0) = x for every x but -0).
+// Alignments with more than ROW_STATS_KMAX distinct columns keep the statistics launch (stats_big, below): the two
+// launches cover the split list disjointly, each from ucount[b] alone.
+constexpr int ROW_STATS_THREADS = MAIN_THREADS, ROW_STATS_WAVES = ROW_STATS_THREADS / 64;
+struct RowItem { int b, p, K; bool ok; };
+// The split alignments the statistics launch keeps, for a run that may hold some (Lloc > ROW_STATS_KMAX): big[0] their
+// number, big[1..] the alignments, ascending - an int span of its own (the host lends it outpart, dead until the last
+// block).  One wave, a ballot per 64 entries of the split list, as k_main_plan lays out its lists.
+__global__ void __launch_bounds__(64) k_stats_plan(const int* ucount, const int* plan, int* big, int B) {
+    const int lane = threadIdx.x, ns = plan[1];
+    const int* const slist = plan + 4 + B;
+    int nb = 0;
+    for (int i0 = 0; i0 < ns; i0 += 64) {
+        const int b = i0 + lane < ns ? slist[i0 + lane] : 0;
+        const bool is_big = i0 + lane < ns && ucount[b] > ROW_STATS_KMAX;
+        const unsigned long long m = __ballot(is_big);
+        if (is_big) big[1 + nb + __popcll(m & ((1ull << lane) - 1ull))] = b;
+        nb += __popcll(m);
+    }
+    if (lane == 0) big[0] = nb;
+}
+
+// Under the debug taps the statistics launch also copies x to the repeated sites; behind k_row_stats this does it, for
+// the alignments k_row_stats covers (one thread per 16 bytes of a token, grid-stride over the split list's tokens).
+__global__ void __launch_bounds__(256) k_copy_repeats(MainArgs a) {
+    const int ns = *a.acount;
+    const size_t per = (size_t)a.P * a.Lloc * 16, n = (size_t)ns * per;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const int b = a.alist[i / per];
+        if (a.ucount[b] > ROW_STATS_KMAX) continue;
+        const size_t r = i % per, tok = r >> 4;                  // token inside the alignment: p * Lloc + l
+        const int l = (int)(tok % a.Lloc), rep = a.srep[(size_t)b * a.Lloc + l];
+        if (rep == l) continue;
+        f32x4* const xa = reinterpret_cast<f32x4*>(a.x + (size_t)b * a.P * a.Lloc * 64);
+        xa[(tok * 16) + (r & 15)] = xa[((tok - l + rep) * 16) + (r & 15)];
+    }
+}
+
+__global__ void __launch_bounds__(ROW_STATS_THREADS, ROW_STATS_WAVES / 4) k_row_stats(MainArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int ns = *a.acount;
+    if (ns == 0) return;
+    // Items are dealt round-robin: item i is row i % P of the (i / P)-th split alignment with K <= ROW_STATS_KMAX.  A
+    // workgroup's items ascend, so one cursor over the split list (sj, seen: entries passed, alignments of ours among
+    // them) finds them all; everything here is wave-uniform.
+    int sj = 0, seen = 0;
+    RowItem hit{0, 0, 0, false};         // the last find: the next row of the same alignment costs no load
+    auto find = [&](int item) {
+        RowItem it{0, 0, 0, false};
+        const int qi = item / a.P;
+        if (hit.ok && seen == qi) { it = hit; it.p = item - qi * a.P; return it; }
+        for (; sj < ns; ++sj) {
+            const int b = a.alist[sj], K = a.ucount[b];
+            if (K > ROW_STATS_KMAX) continue;
+            if (seen == qi) { it.b = b; it.p = item - qi * a.P; it.K = K; it.ok = true; hit = it; return it; }
+            ++seen;
+        }
+        hit.ok = false;
+        return it;
+    };
+    int item = blockIdx.x;
+    RowItem cur = find(item);
+    if (!cur.ok) return;                 // nothing to do: no LDS image is requested (as the routed k_main launches)
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int t = lane & 31, h = lane >> 5;
+    const int L = a.Lloc;
+    unsigned short* const map = reinterpret_cast<unsigned short*>(smem + ROW_STATS_OFF_MAP);
+    float* const bqk = reinterpret_cast<float*>(smem + ROW_STATS_OFF_BQK);
+    float* const term = reinterpret_cast<float*>(smem + ROW_STATS_OFF_TERM);
+    // site -> compact index of its class: the first sites from ulist, the others from their first site
+    auto build_map = [&](int b, int K) {
+        const int* const ul = a.ulist + (size_t)b * L;
+        const int* const sr = a.srep + (size_t)b * L;
+        for (int u = threadIdx.x; u < K; u += ROW_STATS_THREADS) map[ul[u]] = (unsigned short)u;
+        __syncthreads();
+        for (int l = threadIdx.x; l < L; l += ROW_STATS_THREADS) { const int r = sr[l]; if (r != l) map[l] = map[r]; }
+    };
+    // the next tile's x, requested a tile (across rows: a whole phase 2) ahead of its use
+    f32x4 px[8];
+    auto prefetch = [&](const RowItem& it, int ct) {
+        const int u = min(32 * ct + t, it.K - 1);               // (ragged tile: clamped onto the row's last token, not kept)
+        const int l = a.ulist[(size_t)it.b * L + u];
+        const f32x4* xp = reinterpret_cast<const f32x4*>(a.x + (((size_t)it.b * a.P + it.p) * L + l) * 64 + 4 * h);
+#pragma unroll
+        for (int g = 0; g < 8; ++g) px[g] = xp[2 * g];
+    };
+    prefetch(cur, wave);
+    {
+        frag_t* const lf = reinterpret_cast<frag_t*>(smem);
+        const frag_t* const img = a.wimg + FRAG_WV;             // Wv' hi and Wq'k' stand together in the block's image
+        for (int f = threadIdx.x; f < ROW_STATS_FRAG_WVLO; f += ROW_STATS_THREADS) lf[f] = img[f];
+        for (int f = threadIdx.x; f < WVLO_FRAGS; f += ROW_STATS_THREADS) lf[ROW_STATS_FRAG_WVLO + f] = a.wv_lo[f];
+        if (threadIdx.x < 8) bqk[threadIdx.x] = a.consts[CONST_BQK + threadIdx.x];
+        static_assert(FRAG_QK - FRAG_WV == ROW_STATS_FRAG_QK && FRAG_WVLO - FRAG_QK == ROW_STATS_FRAG_WVLO - ROW_STATS_FRAG_QK, "one copy");
+    }
+    build_map(cur.b, cur.K);
+    __syncthreads();
+
+    lds_frag_t lw = (lds_frag_t)smem;
+    lds_frag_t qkp = lw + ROW_STATS_FRAG_QK + h * 8 + (t & 7);
+    lds_frag_t wvp = lw + ROW_STATS_FRAG_WV + lane;
+    lds_f32_t lbq = (lds_f32_t)(smem + ROW_STATS_OFF_BQK) + 4 * h;
+    PF_OPAQUE(qkp); PF_OPAQUE(wvp);
+
+    for (;;) {
+        const int b = cur.b, p = cur.p, K = cur.K;
+        // ---- phase 1: the terms of the row's distinct tokens, once each
+        const int nct = row_ctiles(K);
+        item += gridDim.x;
+        const RowItem nxt = find(item);
+        for (int ct = wave;; ct += ROW_STATS_WAVES) {
+            float x[32];
+#pragma unroll
+            for (int g = 0; g < 8; ++g)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) x[4 * g + i] = px[g][i];
+            // The wave's next tile is requested here, whatever it is: the next one of this row, or the first one of its
+            // next row - on its way across the whole of phase 2, so a row never starts by waiting on HBM.  ONE request
+            // site, never skipped (no next row: this row's again, not used; a tile past the row's end reads the row's
+            // last token): behind a branch hipcc merges the two register sets and waits for the loads at the merge.
+            const bool more = ct + ROW_STATS_WAVES < nct;
+            prefetch(more || !nxt.ok ? cur : nxt, more ? ct + ROW_STATS_WAVES : wave);
+            if (ct >= nct) break;            // a wave without a tile of this row
+            f32x16 va[3];
+            {
+                float xn[32];
+                ln_pair(x, xn);
+                frag_t xb_hi[4], xb_lo[4];
+#pragma unroll
+                for (int s = 0; s < 4; ++s) split8(&xn[8 * s], xb_hi[s], xb_lo[s]);
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    // output rows >= 8 are never read: lanes t >= 8 reuse rows t & 7 (finite) unmasked
+                    const frag_t q_hi = qkp[(s * 2) * 16], q_lo = qkp[(s * 2 + 1) * 16];
+                    if (s == 0) mfma3_zero(va[2], q_hi, q_lo, xb_hi[s], xb_lo[s]);
+                    else mfma3(va[2], q_hi, q_lo, xb_hi[s], xb_lo[s]);
+                }
+#pragma unroll
+                for (int s = 0; s < 4; ++s)
+#pragma unroll
+                    for (int T = 0; T < 2; ++T) {
+                        const frag_t f_hi = wvp[(T * 4 + s) * 64];
+                        const frag_t f_lo = wvp[(ROW_STATS_FRAG_WVLO - ROW_STATS_FRAG_WV) + (T * 4 + s) * 64];
+                        if (s == 0) mfma3_zero(va[T], f_hi, f_lo, xb_hi[s], xb_lo[s], T == 1);
+                        else mfma3(va[T], f_hi, f_lo, xb_hi[s], xb_lo[s], T == 1);
+                    }
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) va[2][r] += lbq[r];   // rows 0-3 q, 4-7 k
+            float qk[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) qk[i] = elu1_fast(va[2][i]);
+            const int u = 32 * ct + t;
+            if (u < K) {
+                f32x4* const tr = reinterpret_cast<f32x4*>(term + (size_t)u * ROW_STATS_TERM);
+#pragma unroll
+                for (int g = 0; g < 8; ++g) {
+                    const f32x4 v4 = {va[g >> 2][4 * (g & 3)], va[g >> 2][4 * (g & 3) + 1], va[g >> 2][4 * (g & 3) + 2], va[g >> 2][4 * (g & 3) + 3]};
+                    tr[8 * h + g] = v4;
+                }
+                // lane half 0 holds the token's q' (rows 0-3), half 1 its k' (rows 4-7): each stores its own four - the
+                // statistics launch's pair_other only moves them to the other half, phase 2 reads both
+                const f32x4 own = {qk[0], qk[1], qk[2], qk[3]};
+                tr[16 + h] = own;
+            }
+            if (!more) break;
+        }
+        __syncthreads();
+
+        // ---- phase 2: every site in place, the parts of the original tiling
+        const int nparts = row_parts(a.flat, L, p);
+        for (int j = wave; j < nparts; j += ROW_STATS_WAVES) {
+            const RowPart rp = row_part(a.flat, L, p, j);
+            const int l = rp.l0 + t;
+            const bool valid = l >= 0 && l < L;
+            const int lc_ = min(max(l, 0), L - 1);
+            const f32x4* const tr = reinterpret_cast<const f32x4*>(term + (size_t)map[lc_] * ROW_STATS_TERM);
+            float vv[32];
+#pragma unroll
+            for (int g = 0; g < 8; ++g) {
+                const f32x4 v4 = tr[8 * h + g];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) vv[4 * g + i] = v4[i];
+            }
+            const f32x4 q4 = tr[16], k4 = tr[17];
+            const float qn[4] = {q4[0], q4[1], q4[2], q4[3]}, kn[4] = {k4[0], k4[1], k4[2], k4[3]};
+            if (valid && h == 0) {
+                // (both half-waves hold the same q': the lower one stores it)
+                *reinterpret_cast<f32x4*>(a.qrow + (((size_t)b * a.P + p) * L + l) * 4) = q4;
+            }
+            float* sp = a.spart + (size_t)((long)b * a.slots_aln + rp.slot) * SROW;
+            const float vm = valid ? 1.f : 0.f;
+            float km[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) km[i] = kn[i] * vm;
+            {
+                // S_q | S_k of the part: lane j (mod 8) ends up with the half-wave sum of value j
+                float qk8[8];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { qk8[i] = vm * qn[i]; qk8[4 + i] = km[i]; }
+                const float sqk = treduce8(qk8, t);
+                if (lane < 8) sp[64 + lane] = sqk;
+            }
+            {
+                float kv[32];
+#pragma unroll
+                for (int jj = 0; jj < 32; ++jj) kv[jj] = valid ? km[jj >> 3] * vv[jj] : 0.f;
+                sp[kmap(t, h)] = treduce32(kv, t);      // lane (t, h) owns S_kv[kmap(t, h)]
+            }
+        }
+        if (!nxt.ok) break;
+        __syncthreads();                 // the term table (and the map) are free
+        if (nxt.b != b) { build_map(nxt.b, nxt.K); }
+        cur = nxt;
+    }
+}
+
 // ---- site classes ------------------------------------------------------------------------
 // Nothing in the network depends on a site's position: two equal columns of an alignment carry
 // equal tokens through every block, and the column statistics of a site - a sum over pairs in a tree fixed by (P, L) -
@@ -1525,6 +1754,8 @@ struct SiteClassArgs {
     int N, Lloc, dedup;
 };
 constexpr int SC_THREADS = 1024, SC_MAX_SITES = 4096;
+static_assert(SC_MAX_SITES <= ROW_STATS_MAP_SITES && ROW_STATS_KMAX <= SC_MAX_SITES,
+              "k_row_stats' site map holds every alignment with K <= ROW_STATS_KMAX < L (beyond SC_MAX_SITES: K = L)");
 __global__ void __launch_bounds__(SC_THREADS) k_site_classes(SiteClassArgs a) {
     __shared__ __attribute__((aligned(16))) uint32_t hsh[SC_MAX_SITES];
     __shared__ int wsum[SC_THREADS / 64];

@@ -81,6 +81,10 @@ constexpr int MAIN_DEDUP_NUM = PF_MAIN_DEDUP_NUM, MAIN_DEDUP_DEN = PF_MAIN_DEDUP
 PF_HD inline bool main_dedup_split(int K, int L, int mode) {
     return mode == 2 || (mode == 1 && (long)K * MAIN_DEDUP_DEN <= (long)L * MAIN_DEDUP_NUM);
 }
+// the most distinct columns an alignment of L sites on the split route can have
+PF_HD inline int main_dedup_max_k(int L, int mode) {
+    return mode == 2 ? L : mode == 1 ? (int)((long)L * MAIN_DEDUP_NUM / MAIN_DEDUP_DEN) : 0;
+}
 PF_HD inline int compact_tiles(int P, int K) { return K >= 32 ? (int)(((long)P * K + 31) >> 5) : P; }
 // tokens of tile kt (1..32), and the lane from which a tile at (r0, u0) belongs to row r0 + 1 (32: none)
 PF_HD inline int compact_nvalid(int P, int K, int kt) {
@@ -109,5 +113,47 @@ PF_HD inline void compact_next(int K, int* r0, int* u0) {
 // [2] compact tiles of all split alignments, [3] unused | flist [B] | slist [B] | cpre [B + 1] (tiles in front of
 // split alignment i; cpre[ns] = the total)
 PF_HD inline int main_plan_ints(int B) { return 4 + 3 * B + 1; }
+
+// ---- option "stats_dedup": the split route's row statistics per pair row (k_row_stats) ---------------------------
+// One work item is a pair row p of a split-route alignment with K <= ROW_STATS_KMAX distinct columns.  Phase 1 forms,
+// once per distinct column, what a token gives the statistics before any positional step - v (64), q' (4), k' (4) -
+// over the row's COMPACT tiles (32 consecutive entries of ulist, the last one ragged) and keeps it in an LDS term table;
+// phase 2 walks the row's PARTS of the original tiling (flat or by rows) and reduces the terms of every site in place.
+// LDS of the kernel: Wv' hi | Wq'k' | Wv' lo (all eight fragments) | bqk | site -> compact index | term table.
+constexpr int ROW_STATS_FRAG_WV = 0;                                   // [2 T][4 s][64]
+constexpr int ROW_STATS_FRAG_QK = ROW_STATS_FRAG_WV + 2 * 4 * 64;      // [4 s][2 hi/lo][2 kgrp][8 rows]
+constexpr int ROW_STATS_FRAG_WVLO = ROW_STATS_FRAG_QK + 4 * 2 * 16;    // [2 T][4 s][64]
+constexpr int ROW_STATS_FRAGS = ROW_STATS_FRAG_WVLO + WVLO_FRAGS;
+constexpr int ROW_STATS_MAP_SITES = 4096;    // sites the map holds (k_site_classes finds no classes beyond: K = L there)
+// a token's terms: [2 h][32] v in the lanes' register order | q' [4] | k' [4], padded from 72 to 76 floats: 19 x 16 bytes,
+// an odd count, so that sixteen lanes reading consecutive terms with ds_read_b128 meet sixteen different bank groups
+constexpr int ROW_STATS_TERM = 76;
+constexpr int ROW_STATS_OFF_BQK = ROW_STATS_FRAGS * 16;
+constexpr int ROW_STATS_OFF_MAP = ROW_STATS_OFF_BQK + 8 * 4;
+constexpr int ROW_STATS_OFF_TERM = ROW_STATS_OFF_MAP + ROW_STATS_MAP_SITES * 2;
+constexpr int ROW_STATS_KMAX = 451;          // what the 160 KB leave (a literal: the tests read it out of this line)
+static_assert(ROW_STATS_KMAX == (160 * 1024 - ROW_STATS_OFF_TERM) / (ROW_STATS_TERM * 4), "KMAX is derived from the LDS left");
+constexpr int ROW_STATS_LDS_BYTES = ROW_STATS_OFF_TERM + ROW_STATS_KMAX * ROW_STATS_TERM * 4;
+static_assert(ROW_STATS_KMAX >= 425, "every split-route alignment of 500 sites (K <= 17 / 20 L) fits the term table");
+static_assert(ROW_STATS_OFF_TERM % 16 == 0 && ROW_STATS_LDS_BYTES <= 160 * 1024, "the term table is read 16 bytes at a time");
+// compact tiles of a row and the tokens of tile ct (compacted tokens 32 ct .. of the row)
+PF_HD inline int row_ctiles(int K) { return (K + 31) >> 5; }
+PF_HD inline int row_ctile_nvalid(int K, int ct) { return K - 32 * ct < 32 ? K - 32 * ct : 32; }
+// Part j of row p in the original tiling: tile kt of the alignment, lane t holds site l0 + t of the row (a token of the
+// part iff 0 <= l0 + t < L: l0 < 0 where a flat tile starts in row p - 1), partial slot `slot` of the alignment
+// (pf_device.hip.h, part_range: kt + p flat, kt by rows).
+struct RowPart { int kt, l0, slot; };
+PF_HD inline int row_parts(int flat, int L, int p) {
+    if (!flat) return (L + 31) >> 5;
+    return (int)(((((long)p + 1) * L - 1) >> 5) - (((long)p * L) >> 5)) + 1;
+}
+PF_HD inline RowPart row_part(int flat, int L, int p, int j) {
+    RowPart r;
+    if (!flat) { r.kt = p * ((L + 31) >> 5) + j; r.l0 = 32 * j; r.slot = r.kt; return r; }
+    r.kt = (int)(((long)p * L) >> 5) + j;
+    r.l0 = (int)((long)r.kt * 32 - (long)p * L);
+    r.slot = r.kt + p;
+    return r;
+}
 
 }  // namespace pfk

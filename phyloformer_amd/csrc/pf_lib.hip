@@ -235,6 +235,7 @@ struct pf_handle {
     bool materialize_x0 = false;  // option "materialize_x0": k_embed writes x0 and block 0 reads it (round-1 path)
     bool site_dedup = true;       // option "site_dedup": k_colstats walks every distinct column once (0: every site, the identity map)
     int main_dedup = 1;           // option "main_dedup": k_main's per-token work once per distinct column - 1 per alignment, 0 never, 2 always
+    bool stats_dedup = true;      // option "stats_dedup": the split route's row statistics once per distinct column of a pair row (k_row_stats)
     float* first_consts = nullptr;  // consts for k_main<FIRST> (only bqk used)
     float* first_img = nullptr;     // LDS image for k_main<FIRST> (only the row-statistics tail used)
     std::vector<BlockDev> blk;
@@ -721,6 +722,37 @@ int launch_main(pf_handle* h, MainKind kind, const MainArgs& a, bool timed) {
 struct MainPlan { const int *nf, *ns, *flist, *slist, *cpre; };
 MainPlan main_plan(const int* plan, int B) { return {&plan[0], &plan[1], &plan[4], &plan[4 + B], &plan[4 + 2 * B]}; }
 
+// The split route's statistics (option "stats_dedup", pf_device.hip.h above k_row_stats).  How a run of Lloc sites goes:
+//   ROWS      k_row_stats alone: the shape and the routing rule (main_dedup_max_k) show that no split alignment can have
+//             more than ROW_STATS_KMAX distinct columns - 60 x 500 at option 1: at most 425
+//   ROWS_BIG  k_row_stats, and the statistics launch over the alignments beyond it (k_stats_plan lists them once per run)
+//   LAUNCH    the statistics launch over the whole split list: option 0, or more sites than k_row_stats' map holds (such
+//             a run has no classes: every K = Lloc)
+enum { STATS_ROWS, STATS_ROWS_BIG, STATS_LAUNCH };
+int split_stats_form(const pf_handle* h, int Lloc) {
+    if (!h->stats_dedup || Lloc > ROW_STATS_MAP_SITES) return STATS_LAUNCH;
+    return std::min(Lloc, main_dedup_max_k(Lloc, h->main_dedup)) <= ROW_STATS_KMAX ? STATS_ROWS : STATS_ROWS_BIG;
+}
+// (the list k_stats_plan leaves: count | alignments, in outpart - written by the last block only, behind every statistics launch)
+int* stats_big_list(float* outpart) { return reinterpret_cast<int*>(outpart); }
+
+// c: the compact launch's arguments (the split list).  Under the debug taps x of the repeated sites is filled in behind
+// k_row_stats, as the statistics launch does for its alignments.
+int launch_split_stats(pf_handle* h, const MainArgs& c) {
+    const int form = split_stats_form(h, c.Lloc);
+    if (form == STATS_LAUNCH) return launch_main(h, {MODE_STATS, PLAIN, ROUTE_LIST}, c, false);
+    hipLaunchKernelGGL(k_row_stats, dim3(persistent_grid(h, (long)c.B * c.P, 1, 1)), dim3(ROW_STATS_THREADS), ROW_STATS_LDS_BYTES, h->cur, c);
+    HIPCHK(h, hipGetLastError());
+    if (c.store_x_last) {
+        hipLaunchKernelGGL(k_copy_repeats, dim3(persistent_grid(h, (long)c.B * c.P * c.Lloc * 16, 256, 8)), dim3(256), 0, h->cur, c);
+        HIPCHK(h, hipGetLastError());
+    }
+    if (form == STATS_ROWS) return PF_OK;
+    MainArgs s = c;
+    s.acount = stats_big_list(c.outpart); s.alist = s.acount + 1;
+    return launch_main(h, {MODE_STATS, PLAIN, ROUTE_LIST}, s, false);
+}
+
 // One block's k_main work of a run whose alignments are routed (option "main_dedup"): the fused launch over the
 // alignments that stay on it, and for the others the compact launch followed by what must see every site in place - the
 // statistics launch, or after the last block the head sums.  Each returns at once where its list is empty.
@@ -732,7 +764,7 @@ int launch_main_routed(pf_handle* h, int mode, const MainArgs& m, const MainPlan
     c.acount = p.ns; c.alist = p.slist; c.cpre = p.cpre;
     c.term = m.spart; c.prof = nullptr; // (spart: dead since k_rowfin read it)
     if ((rc = launch_main(h, {mode, PLAIN, ROUTE_COMPACT}, c, false))) return rc;
-    if (mode != MODE_LAST && mode != MODE_LAST_FOLD) return launch_main(h, {MODE_STATS, PLAIN, ROUTE_LIST}, c, false);
+    if (mode != MODE_LAST && mode != MODE_LAST_FOLD) return launch_split_stats(h, c);
     hipLaunchKernelGGL(main_kernel({HEAD_PARTS, PLAIN, ROUTE_LIST}, m.flat != 0), dim3(persistent_grid(h, (long)m.B * m.nt_aln, 4, 8)),
                        dim3(256), 0, h->cur, c);
     HIPCHK(h, hipGetLastError());
@@ -808,13 +840,16 @@ ShardRun shard_run(const pf_handle* h, const uint8_t* d_idx, float* d_out, int B
 // The classes of equal columns of B alignments (k_site_classes), in front of everything that reads them: once per forward -
 // the indices change from call to call.  Option site_dedup = 0: the identity map, same kernels.  With `plan`, the routes of
 // k_main's work over P pairs follow on the device (k_main_plan, option "main_dedup"), inside the same pair of events.
-int launch_site_classes(pf_handle* h, const SiteClassArgs& a, int B, int* plan = nullptr, int P = 0) {
+int launch_site_classes(pf_handle* h, const SiteClassArgs& a, int B, int* plan = nullptr, int P = 0, int* stats_big = nullptr) {
     if (!a.Lloc) return PF_OK;
     ProfScope ps(h, K_SITE_CLASSES);
     hipLaunchKernelGGL(k_site_classes, dim3(B), dim3(SC_THREADS), 0, h->cur, a);
     HIPCHK(h, hipGetLastError());
     if (!plan) return PF_OK;
     hipLaunchKernelGGL(k_main_plan, dim3(1), dim3(64), 0, h->cur, a.ucount, plan, B, P, a.Lloc, h->main_dedup);
+    HIPCHK(h, hipGetLastError());
+    if (!stats_big) return PF_OK;
+    hipLaunchKernelGGL(k_stats_plan, dim3(1), dim3(64), 0, h->cur, a.ucount, plan, stats_big, B);
     HIPCHK(h, hipGetLastError());
     return PF_OK;
 }
@@ -1005,6 +1040,8 @@ int phase_block(pf_handle* h, const ShardRun& r, int k, RowStats rs) {
     if ((rc = launch_colfin(h, r, k))) return rc;
     if (h->debug_keep && ((rc = save_tap(h, "ctx" + tag, r.w.ctx, sites * 64)) || (rc = save_tap(h, "mrow" + tag, r.w.mrow, pairs * MROW)))) return rc;
     if ((rc = launch_block_main(h, r, k))) return rc;
+    // (q' of the next block's row attention, per token: what the statistics phase stored beside its partial sums)
+    if (h->debug_keep && k + 1 < h->n_blocks && (rc = save_tap(h, "qrow" + std::to_string(k + 1), r.w.qrow, pairs * r.Lloc * 4))) return rc;
     if (h->debug_keep) return save_tap(h, "x" + std::to_string(k + 1), r.w.x, pairs * r.Lloc * 64);
     return PF_OK;
 }
@@ -1050,7 +1087,9 @@ int schedule(pf_handle* h, ShardRun* runs, size_t nruns, Reduce reduce) {
     for (ShardRun* r = runs; r != end; ++r) {
         h->cur = r->stream;
         const SiteClassArgs sc{r->d_idx, r->w.srep, r->w.ulist, r->w.ucount, r->N, r->Lloc, h->site_dedup ? 1 : 0};
-        if ((rc = launch_site_classes(h, sc, r->B, r->routed ? r->w.plan : nullptr, r->P))) return rc;
+        // (a routed run that may hold alignments beyond k_row_stats: their list, for the statistics launch)
+        int* const big = r->routed && split_stats_form(h, r->Lloc) == STATS_ROWS_BIG ? stats_big_list(r->w.outpart) : nullptr;
+        if ((rc = launch_site_classes(h, sc, r->B, r->routed ? r->w.plan : nullptr, r->P, big))) return rc;
         if (h->debug_keep && (rc = save_route_taps(h, *r))) return rc;
         if ((rc = phase_first(h, *r))) return rc;
         r->rs = first_stats(h, *r);
@@ -2793,6 +2832,7 @@ static int open_device(int device, pf_handle** out) {
         };
         for (const MainRow& r : main_kernels())       // (k_main over every alignment; the routed launches run without it)
             if (r.kind.route == ROUTE_ALL) big_lds(reinterpret_cast<const void*>(r.fn), MAIN_LDS_BYTES);
+        big_lds(reinterpret_cast<const void*>(&k_row_stats), ROW_STATS_LDS_BYTES);
         big_lds(reinterpret_cast<const void*>(&k_embed<false>), EMBED_LDS_BYTES);
         big_lds(reinterpret_cast<const void*>(&k_embed<true>), EMBED_LDS_BYTES);
         big_lds(reinterpret_cast<const void*>(&pffit::k_fit_setup), pffit::SETUP_LDS_MAX);
@@ -2887,6 +2927,7 @@ int pf_set_option(pf_handle_t* h, const char* key, int64_t value) {
     else if (k == "colstats_ring") h->colstats_ring = value != 0;
     else if (k == "site_dedup") h->site_dedup = value != 0;
     else if (k == "main_dedup") h->main_dedup = value <= 0 ? 0 : (value >= 2 ? 2 : 1);
+    else if (k == "stats_dedup") h->stats_dedup = value != 0;
     else if (k == "precise") h->precise = value < 0 ? -1 : (value != 0);
     else if (k == "recheck_above") h->recheck_above = value > 0 ? (double)value : 0.0;
     else if (k == "precise_ffn_valu") h->precise_ffn_valu = value != 0;

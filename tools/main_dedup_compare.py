@@ -2,7 +2,7 @@
 """Option main_dedup 1 (and 2) against 0, alternated, on one engine: what k_main's per-token work once per distinct
 column buys and costs (the approach of tools/site_dedup_compare.py).
 
-    python tools/main_dedup_compare.py [--repeats 4] [--steps 10] [--modes 1,0] [--batches distinct,bench]
+    python tools/main_dedup_compare.py [--repeats 4] [--steps 10] [--modes 1,0] [--batches distinct,bench] [--option main_dedup]
 
 Two batches of the headline shape, device-resident like bench.py's:
   distinct   every column of every alignment different: the worst case - with option 1 every alignment stays on the
@@ -14,6 +14,9 @@ turn, then - one stream, one pair of HIP events around each block's k_main launc
 repeat is printed: the spread of the repeats is what a difference has to be read against.  The distances of all modes are
 compared bit for bit.  `--modes 2,0` on one stream under `rocprofv3 --kernel-trace --stats` gives the times of the
 compact, statistics and fused launches the threshold is derived from (profiles/main_dedup_threshold.txt).
+`--option stats_dedup` alternates that option instead (main_dedup stays at its default): the split route's statistics by
+k_row_stats against the statistics launch; on the `distinct` batch nothing is split and neither runs
+(profiles/stats_dedup_compare.txt).
 """
 import argparse
 import os
@@ -37,6 +40,7 @@ def main():
     ap.add_argument("--n-sites", type=int, default=500)
     ap.add_argument("--modes", default="1,0")
     ap.add_argument("--batches", default="distinct,bench")
+    ap.add_argument("--option", default="main_dedup", choices=["main_dedup", "stats_dedup"], help="the option the modes are values of")
     ap.add_argument("--one-stream-only", action="store_true", help="skip the two-stream rate (profiler runs)")
     args = ap.parse_args()
     from phyloformer_amd.engine import Engine
@@ -62,7 +66,7 @@ def main():
         outs = {}
         for rep in range(args.repeats):
             for mode in modes:
-                e.set_option("main_dedup", mode)
+                e.set_option(args.option, mode)
                 rate = ""
                 if not args.one_stream_only:
                     e.set_option("two_streams", 1)
@@ -86,10 +90,10 @@ def main():
                 e.d2h(res, d_out)
                 outs[mode] = res
                 ms = "  ".join(f"{k} {v[1] / max(v[0], 1):.4f} (x{v[0] // 3})" for k, v in per.items())
-                print(f"repeat {rep} main_dedup {mode}: {rate}ms per bracket, one stream: {ms}", flush=True)
+                print(f"repeat {rep} {args.option} {mode}: {rate}ms per bracket, one stream: {ms}", flush=True)
         same = all(np.array_equal(outs[m].view(np.uint32), outs[modes[0]].view(np.uint32)) for m in modes)
-        print(f"distances bit-identical across main_dedup {modes}: {same}")
-    e.set_option("main_dedup", 1)
+        print(f"distances bit-identical across {args.option} {modes}: {same}")
+    e.set_option(args.option, 1)
     e.free(d_idx)
     e.free(d_out)
     e.close()
