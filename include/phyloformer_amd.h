@@ -523,6 +523,37 @@ int pf_tree_ols_device(pf_handle_t* h, const float* d_preds, const int32_t* d_sl
                        uint8_t* d_status);
 int pf_tree_ols_host(const float* preds, const int32_t* slots, int32_t B, int32_t M, int32_t N, double* ols, uint8_t* status);
 
+/* ---- tree rooting: MAD and midpoint roots of a join table (additive to ABI 5) ----
+ *
+ * Where the root of an unrooted tree is: per branch the minimal ancestor deviation (MAD; Tria, Landan & Dagan 2017) and the root
+ * position that attains it, and the midpoint of the longest path, bit for bit those of phyloformer_amd/root.py::tree_root_py.  A
+ * tree is a join table in pf_nj_joins' layout; no distances are read.  Nodes and the tree's leaf order are pf_tree_ols'; lengths
+ * are clamped at +0.0.  D[v][x] is the path from node v to leaf x, added along the tree one column at a time; W[b][c] = 1 /
+ * (D[b][c] D[b][c]), 0 where the path is 0.  Per entry k (the branch above its node v): the position lam = clamp(-S1 / (2 S0), 0,
+ * L) from the sums over the pairs the branch separates, then, with t[x] = D[v][x] + lam below v and D[v][x] - lam elsewhere,
+ * ssq[k] = 0.5 sum over ordered pairs of W[q][c] ((t[q] - t[c]) (t[q] - t[c])): one sequential accumulator per leaf q over all c in
+ * the tree's leaf order, the leaves' sums in 64 strided accumulators combined pairwise at distances 32, 16, ... 1.  The order is
+ * part of the definition (csrc/pf_root.hip.h, csrc/pf_root_host.h).
+ *   slots     int32  [B][M][T]       M join tables per source, T = 2 (N - 3) + 3
+ *   lengths   double [B][M][T]       their branch lengths; a negative one counts as 0
+ *   ssq       double [B][M][T]       per entry the sum of squared deviations with the root on its branch; MAD = sqrt(ssq / P_N)
+ *   pos       double [B][M][T]       per entry the root's distance above the branch's lower node
+ *   mid       double [B][M][5]       the midpoint: entry, distance above its lower node, the pair b < c, their distance D[c][b]
+ *   status    uint8  [B][M]          0 fine; 2 no join table (as pf_tree_fit; checked first); 1 a NaN or an infinity among the
+ *                                    lengths.  A tree with a status has zeros and is walked by no kernel
+ * pf_tree_root takes host arrays and is synchronous; pf_tree_root_device takes device arrays and is asynchronous on the
+ * handle's stream; pf_tree_root_host is the serial twin, without a handle or a device.  One call with B sources equals B
+ * calls with one.  The state of a tree is (2N - 2) N + N N doubles and the node arrays (1.61 GB at N = 8,192): trees run side by
+ * side in chunks that fit "ws_limit_mb".  Refused with PF_EINVAL before any device work, the message naming the value: N < 3;
+ * N > 8,192; B < 1; M < 1; NULL buffers; a tree's state above the workspace limit.  pf_profile_get("tree_root") counts the
+ * calls of the two handle entry points. */
+int pf_tree_root(pf_handle_t* h, const int32_t* slots, const double* lengths, int32_t B, int32_t M, int32_t N, double* ssq, double* pos,
+                 double* mid, uint8_t* status);
+int pf_tree_root_device(pf_handle_t* h, const int32_t* d_slots, const double* d_lengths, int32_t B, int32_t M, int32_t N, double* d_ssq,
+                        double* d_pos, double* d_mid, uint8_t* d_status);
+int pf_tree_root_host(const int32_t* slots, const double* lengths, int32_t B, int32_t M, int32_t N, double* ssq, double* pos, double* mid,
+                      uint8_t* status);
+
 /* ---- balanced minimum-evolution NNI refinement of a join table (additive to ABI 5) ----
  *
  * Balanced nearest-neighbour interchanges (BNNI, FastME's -n B) from a start tree to a local optimum of the balanced

@@ -23,7 +23,8 @@ distances, whichever mode made them, how tree-like they are, and writes ``<stem>
 ``<stem>.delta.hist.tsv``.  ``--fit`` (``phyloformer_amd/fit.py``) asks of every tree a run with ``-t`` writes how well it
 reproduces those distances: ``<stem>.fit.tsv`` and, per tree, ``<stem>.fit.taxa.tsv`` and ``<stem>.patristic.phy``.  ``--ols``
 (``phyloformer_amd/ols.py``) gives every such tree the branch lengths that reproduce them best: ``<stem>.ols.nwk`` per tree and
-``<stem>.ols.tsv``.  The multi-GPU modes, which have no counterpart, refuse such a directory up front.
+``<stem>.ols.tsv``.  ``--root`` (``phyloformer_amd/root.py``) roots every such tree by minimal ancestor deviation or at its midpoint:
+``<stem>.rooted.nwk`` per tree and ``<stem>.root.tsv``.  The multi-GPU modes, which have no counterpart, refuse such a directory up front.
 The forward pass runs in ``libphyloformer_amd.so``; there is no CPU fallback.
 """
 import argparse
@@ -98,6 +99,16 @@ def build_parser():
                              "the RMS residual and the explained variance before and after, the negative branches before and "
                              "after, the most negative least-squares length and the largest change of a branch, all from the "
                              "unclamped lengths; up to 8,192 sequences; every other output keeps its bytes")
+    parser.add_argument("--root", choices=["mad", "midpoint"], default=None,
+                        help="with -t: root every written tree, by minimal ancestor deviation (mad; Tria, Landan & Dagan 2017) or "
+                             "at the midpoint of its longest path, computed on the GPU for large files.  Writes per tree "
+                             "<stem>.rooted.nwk, the tree with a root of two children on the chosen branch (another tree's name "
+                             "stands before the ending: <stem>.bme.rooted.nwk; negative lengths count as zero), and "
+                             "<stem>.root.tsv, one line per tree with both rootings whatever the method: the MAD and its "
+                             "ambiguity index, the leaves below the root branch, the root's position on it and the branch's "
+                             "length, the root clock CV, the midpoint pair, its distance, branch, position and clock CV, and "
+                             "whether the two methods choose the same branch; up to 8,192 sequences; every other output keeps "
+                             "its bytes")
     parser.add_argument("--device", type=int, default=0, help="HIP device ordinal (default 0)")
     parser.add_argument("--devices", default=None,
                         help="comma-separated HIP device ordinals: shard the files over these GPUs, "
@@ -149,6 +160,10 @@ def main(argv=None):
         parser.error(scheduler.OLS_NEEDS_TREES)
     if args.ols and args.shard == "sites":
         parser.error(scheduler.OLS_SHARD_SITES)
+    if args.root and not args.trees:
+        parser.error(scheduler.ROOT_NEEDS_TREES)
+    if args.root and args.shard == "sites":
+        parser.error(scheduler.ROOT_SHARD_SITES)
     if args.treedist or args.treedist_ref:
         from phyloformer_amd import treedist
         if not args.trees:
@@ -233,7 +248,7 @@ def main(argv=None):
                                        io_threads=args.io_threads, native_io=not args.python_io,
                                        progress=bar.update if bar is not None else None, modes=modes, bme=args.bme, spr=args.spr,
                                        bionj=args.bionj, delta=args.delta, fit=args.fit, ols=args.ols,
-                                       treedist=args.treedist, treedist_ref=args.treedist_ref)
+                                       treedist=args.treedist, treedist_ref=args.treedist_ref, root=args.root)
     try:
         stats = runner.run(paths)
     finally:

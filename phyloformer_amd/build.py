@@ -47,7 +47,7 @@ UNITS: Dict[str, List[str]] = {
 }
 HEADERS = ["pf_device.hip.h", "pf_mha.hip.h", "pf_precise.hip.h", "pf_generic.hip.h", "pf_f64_common.hip.h",
            "pf_f64_host.hip.h", "pf_boot.hip.h", "pf_bytes.hip.h", "pf_sites.hip.h", "pf_sitemap.hip.h", "pf_sites_host.h", "pf_taxa.hip.h",
-           "pf_taxa_host.h", "pf_place.hip.h", "pf_tile.hip.h", "pf_tile_host.h", "pf_nj.hip.h", "pf_nj_host.h", "pf_bionj.hip.h", "pf_bionj_host.h", "pf_delta.hip.h", "pf_delta_host.h", "pf_fit.hip.h", "pf_fit_host.h", "pf_ols.hip.h", "pf_ols_host.h", "pf_bme.hip.h", "pf_bme_host.h", "pf_support.hip.h", "pf_support_host.h", "pf_consensus.hip.h", "pf_consensus_host.h", "pf_treedist.hip.h", "pf_treedist_host.h", "pf_weights.hip.h", "pf_weights_host.h", "pf_layout.h", "pf_host_prep.h", "pf_spans.h"]
+           "pf_taxa_host.h", "pf_place.hip.h", "pf_tile.hip.h", "pf_tile_host.h", "pf_nj.hip.h", "pf_nj_host.h", "pf_bionj.hip.h", "pf_bionj_host.h", "pf_delta.hip.h", "pf_delta_host.h", "pf_fit.hip.h", "pf_fit_host.h", "pf_ols.hip.h", "pf_ols_host.h", "pf_root.hip.h", "pf_root_host.h", "pf_bme.hip.h", "pf_bme_host.h", "pf_support.hip.h", "pf_support_host.h", "pf_consensus.hip.h", "pf_consensus_host.h", "pf_treedist.hip.h", "pf_treedist_host.h", "pf_weights.hip.h", "pf_weights_host.h", "pf_layout.h", "pf_host_prep.h", "pf_spans.h"]
 # what decides the bits and the speed of the dominant kernels (k_main, k_colstats): the PMC traffic file under
 # profiles/ is tied to this hash (bench.py: a mismatch means the counters are stale -> traffic null)
 KERNEL_FILES = ["pf_device.hip.h", "pf_layout.h"]

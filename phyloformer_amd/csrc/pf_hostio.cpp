@@ -29,6 +29,7 @@
 #include "pf_delta_host.h"
 #include "pf_fit_host.h"
 #include "pf_ols_host.h"
+#include "pf_root_host.h"
 #include "pf_support_host.h"
 #include "pf_consensus_host.h"
 #include "pf_treedist_host.h"
@@ -968,6 +969,19 @@ int pf_tree_ols_host(const float* preds, const int32_t* slots, int32_t B, int32_
                 const size_t item = b * (size_t)M + m;
                 pfols::run_serial(preds + b * P, slots + item * T, N, ols + item * T, status + item);
             }
+        return PF_OK;
+    } catch (...) { return PF_ENOMEM; }
+}
+
+// Tree rooting without a device: every tree serially - the same arrays as pf_tree_root, bit for bit.
+// Twin of phyloformer_amd/root.py::tree_root_py.  A tree with a status has zeros.
+int pf_tree_root_host(const int32_t* slots, const double* lengths, int32_t B, int32_t M, int32_t N, double* ssq, double* pos, double* mid,
+                      uint8_t* status) {
+    if (!slots || !lengths || !ssq || !pos || !mid || !status || pfroot::refused(B, M, N)) return PF_EINVAL;
+    try {
+        const size_t T = (size_t)pfroot::table_len(N), items = (size_t)B * (size_t)M;
+        for (size_t item = 0; item < items; ++item)
+            pfroot::run_serial(slots + item * T, lengths + item * T, N, ssq + item * T, pos + item * T, mid + item * pfroot::MID, status + item);
         return PF_OK;
     } catch (...) { return PF_ENOMEM; }
 }

@@ -53,6 +53,7 @@
 #include "pf_delta.hip.h"
 #include "pf_fit.hip.h"
 #include "pf_ols.hip.h"
+#include "pf_root.hip.h"
 #include "pf_bme.hip.h"
 #include "pf_support.hip.h"
 #include "pf_consensus.hip.h"
@@ -284,6 +285,10 @@ struct pf_handle {
     // staging of the host entry point's arrays
     Buffer<char> d_ols{buffers}, d_ols_io{buffers};
     int64_t ols_calls = 0;       // pf_tree_ols / pf_tree_ols_device calls since the last pf_profile_reset ("tree_ols")
+    // pf_tree_root / pf_tree_root_device (grow-only): the path lengths, the weights and the node arrays of one chunk of trees,
+    // and the staging of the host entry point's arrays
+    Buffer<char> d_root{buffers}, d_root_io{buffers};
+    int64_t root_calls = 0;      // pf_tree_root / pf_tree_root_device calls since the last pf_profile_reset ("tree_root")
     // pf_bme_nni / pf_bme_nni_device (grow-only): the state of one chunk of sources (pf_bme.hip.h: carve) and the
     // staging of the host entry point's distances
     Buffer<char> d_bme{buffers};
@@ -2394,6 +2399,55 @@ int ols_impl(pf_handle* h, bool device, const pfols::Tables& user, int B, int M,
     return staged_call(h, h->d_ols_io, list, [&] { return launch(io); });
 }
 
+// ---- tree rooting on the device (pf_tree_root, pf_tree_root_device; pf_root.hip.h, pf_root_host.h) ----
+
+// ols_impl's forms and chunks: the items - the B M trees - are cut into chunks whose path lengths, weights and node arrays
+// fit "ws_limit_mb" side by side; the chunks follow each other on the stream and reuse the workspace.
+int root_impl(pf_handle* h, bool device, const pfroot::Tables& user, int B, int M, int N) {
+    pfroot::Tables io{};
+    auto list = [&](auto& v) { pfroot::staging_arrays(v, io, user, (size_t)std::max(B, 0), (size_t)std::max(M, 0), N); };
+    if (pfspan::missing(list)) return fail(h, PF_EINVAL, "null buffer");
+    switch (pfroot::refused(B, M, N)) {
+        case 1: return fail(h, PF_EINVAL, "tree root needs N >= %d sequences (got %d)", pfroot::MIN_N, N);
+        case 2: return fail(h, PF_EINVAL, "tree root takes at most %d sequences (got %d)", pfroot::MAX_N, N);
+        case 3: return fail(h, PF_EINVAL, "tree root needs B >= 1 sources (got %d)", B);
+        case 4: return fail(h, PF_EINVAL, "tree root needs M >= 1 trees per source (got %d)", M);
+    }
+    const int64_t items = (int64_t)B * M;
+    const int T = pfroot::table_len(N);
+    size_t n = 0;
+    if (!mul_size((size_t)items, (size_t)T, sizeof(double), &n))
+        return fail(h, PF_EINVAL, "B=%d sources of M=%d trees of N=%d sequences overflow the address space", B, M, N);
+    const size_t per = pfroot::state_bytes(N);
+    if ((int64_t)per > h->ws_limit_bytes)
+        return fail(h, PF_EINVAL, "tree root of N=%d sequences needs %zu bytes of state per tree (its path lengths, weights and node "
+                                  "arrays), above the workspace limit of %lld bytes (option ws_limit_mb)", N, per, (long long)h->ws_limit_bytes);
+    const int chunk = (int)std::min<int64_t>(std::min(items, pfroot::max_items(N)), (int64_t)((size_t)h->ws_limit_bytes / per));
+    HIPCHK(h, hipSetDevice(h->device));
+    ++h->root_calls;
+    auto launch = [&](const pfroot::Tables& d) -> int {
+        const int rc = h->d_root.reserve(h, (size_t)chunk * per);
+        if (rc) return rc;
+        h->cur = h->stream;
+        // (a tree with a status is walked by no kernel: its results are these zeros)
+        HIPCHK(h, hipMemsetAsync(d.ssq, 0, (size_t)items * (size_t)T * sizeof(double), h->stream));
+        HIPCHK(h, hipMemsetAsync(d.pos, 0, (size_t)items * (size_t)T * sizeof(double), h->stream));
+        HIPCHK(h, hipMemsetAsync(d.mid, 0, (size_t)items * pfroot::MID * sizeof(double), h->stream));
+        pfroot::Args a{};
+        a.slots = d.slots; a.lengths = d.lengths; a.ssq = d.ssq; a.pos = d.pos; a.mid = d.mid; a.status = d.status;
+        a.N = N;
+        for (int64_t item0 = 0; item0 < items; item0 += chunk) {
+            a.item0 = item0; a.nb = (int)std::min<int64_t>(chunk, items - item0);
+            pfroot::carve(a, h->d_root, a.nb);
+            const hipError_t e = pfroot::launch_chunk(h->stream, a);
+            if (e != hipSuccess) return fail(h, PF_EHIP, "k_root_* launch failed: %s", hipGetErrorString(e));
+        }
+        return PF_OK;
+    };
+    if (device) return launch(user);
+    return staged_call(h, h->d_root_io, list, [&] { return launch(io); });
+}
+
 // ---- balanced NNI refinement on the device (pf_bme_nni, pf_bme_nni_device; pf_bme.hip.h, pf_bme_host.h) ----
 
 // every start table is a join table (slots in [0, N), every join of two live clusters, three distinct live slots last)
@@ -3162,6 +3216,18 @@ int pf_tree_ols_device(pf_handle_t* h, const float* d_preds, const int32_t* d_sl
     return ols_impl(h, true, {d_preds, d_slots, d_ols, d_status}, B, M, N);
 }
 
+int pf_tree_root(pf_handle_t* h, const int32_t* slots, const double* lengths, int32_t B, int32_t M, int32_t N, double* ssq, double* pos,
+                 double* mid, uint8_t* status) {
+    if (!h) return PF_EINVAL;
+    return root_impl(h, false, {slots, lengths, ssq, pos, mid, status}, B, M, N);
+}
+
+int pf_tree_root_device(pf_handle_t* h, const int32_t* d_slots, const double* d_lengths, int32_t B, int32_t M, int32_t N, double* d_ssq,
+                        double* d_pos, double* d_mid, uint8_t* d_status) {
+    if (!h) return PF_EINVAL;
+    return root_impl(h, true, {d_slots, d_lengths, d_ssq, d_pos, d_mid, d_status}, B, M, N);
+}
+
 int pf_bme_nni(pf_handle_t* h, const float* preds, const int32_t* start_slots, int32_t B, int32_t N, int32_t* slots, double* lengths,
                int32_t* steps, double* tree_length, uint8_t* status) {
     if (!h) return PF_EINVAL;
@@ -3469,6 +3535,7 @@ int pf_profile_reset(pf_handle_t* h) {
     h->delta_calls = 0;
     h->fit_calls = 0;
     h->ols_calls = 0;
+    h->root_calls = 0;
     h->bme_calls = 0;
     h->spr_calls = 0;
     h->sup_calls = 0;
@@ -3513,6 +3580,11 @@ int pf_profile_get(pf_handle_t* h, const char* kernel, int64_t* launches, double
     }
     if (std::strcmp(kernel, "tree_ols") == 0) {         // pf_tree_ols / pf_tree_ols_device calls
         if (launches) *launches = h->ols_calls;
+        if (total_ms) *total_ms = 0.0;
+        return PF_OK;
+    }
+    if (std::strcmp(kernel, "tree_root") == 0) {        // pf_tree_root / pf_tree_root_device calls
+        if (launches) *launches = h->root_calls;
         if (total_ms) *total_ms = 0.0;
         return PF_OK;
     }

@@ -439,6 +439,21 @@ class Engine:
         self._check(fn(self._h, ptr(p), ptr(s), B, M, N, *map(ptr, out)))
         return squeezed(out, flags)
 
+    # -- tree rooting -------------------------------------------------------------------------
+    def tree_root(self, slots: np.ndarray, lengths: np.ndarray):
+        """MAD and midpoint rooting on the GPU (``pf_tree_root``): join tables ``slots int32`` / ``lengths float64 [B, M, T]`` (``[B, T]``:
+        one tree per source, the results drop ``M``; ``[T]`` drops ``B`` too), ``3 <= N <= 8,192`` → ``(ssq float64[B, M, T], pos
+        float64[B, M, T], mid float64[B, M, 5], status uint8[B, M])``: per branch the sum of squared ancestor deviations at its best
+        root position and that position above the branch's lower node, and the midpoint ``(entry, position, b, c, diameter)`` -
+        bit for bit ``root.tree_root_py`` of every tree and ``hostio.tree_root_host``; ``root.root_scores`` derives what is
+        reported.  A tree with a status (1: not finite, 2: no join table) has zeros.  ``ValueError`` for what the library
+        refuses."""
+        from .root import root_arrays, squeezed
+        fn = self._optional("pf_tree_root")
+        s, l, (B, M, N), flags, out = root_arrays(slots, lengths)
+        self._check(fn(self._h, ptr(s), ptr(l), B, M, N, *map(ptr, out)))
+        return squeezed(out, flags)
+
     # -- balanced NNI refinement -------------------------------------------------------------
     def bme_nni(self, preds: np.ndarray, start_slots: np.ndarray):
         """Balanced minimum-evolution NNI refinement on the GPU (``pf_bme_nni``): distances ``float32[B, P_N]`` and start
@@ -692,5 +707,6 @@ PASS_THROUGHS = {name: "pf_" + name for name in (
     "join_consensus_device", "forward_weighted_device")}
 for _name, _symbol in PASS_THROUGHS.items():
     setattr(Engine, _name, _pass_through(_symbol))
+Engine.tree_root_device = _pass_through("pf_tree_root_device")
 Engine.tree_ols_device = _pass_through("pf_tree_ols_device")      # (beside the list: a later addition to the header)
 Engine.join_distances_device = _pass_through("pf_join_distances_device")

@@ -280,6 +280,15 @@ def tree_ols_host(preds: np.ndarray, slots: np.ndarray):
     return squeezed(out, flags)
 
 
+def tree_root_host(slots: np.ndarray, lengths: np.ndarray):
+    """``Engine.tree_root`` without a device (``pf_tree_root_host``), its arguments and results: every tree serially,
+    ``root.tree_root_py`` bit for bit.  ``ValueError`` for what the library refuses."""
+    from .root import root_arrays, squeezed
+    s, l, (b, m, n), flags, out = root_arrays(slots, lengths)
+    _check_rc("pf_tree_root_host", _lib().pf_tree_root_host(ptr(s), ptr(l), b, m, n, *map(ptr, out)), "N, B or M out of range")
+    return squeezed(out, flags)
+
+
 def _joins_host(symbol: str, preds: np.ndarray, *options):
     p, _, (b, n, _t), _single, (slots, lengths, flag) = tree_call(preds, JOINS, _refuse_joins)
     _check_rc(symbol, getattr(_lib(), symbol)(p.ctypes.data, b, n, *options, ptr(slots), ptr(lengths), ptr(flag)))

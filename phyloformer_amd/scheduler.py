@@ -74,6 +74,9 @@ FIT_SHARD_SITES = "--fit cannot be combined with --shard sites: the site-sharded
 # the refusals of --ols, in the same wording
 OLS_NEEDS_TREES = "--ols re-estimates the branch lengths of the trees of --trees: give -t as well"
 OLS_SHARD_SITES = "--ols cannot be combined with --shard sites: the site-sharded runner writes NJ trees only"
+# the refusals of --root, in the same wording
+ROOT_NEEDS_TREES = "--root roots the trees of --trees: give -t as well"
+ROOT_SHARD_SITES = "--root cannot be combined with --shard sites: the site-sharded runner writes NJ trees only"
 HEARTBEAT = "#pf-heartbeat"      # stderr line prefix of a site-sharded worker's sign of life (swallowed by the launcher)
 MAX_SEQS = 200     # SEQ2PAIR = seq2pair(200), /root/reference/phyloformer/model.py:39
 
@@ -166,7 +169,7 @@ class DirectoryRunner:
     def __init__(self, engine, out_dir: str, trees: bool = False, batch: int = 0,
                  io_threads: int = 4, native_io: bool = True, progress=None, modes: Sequence[Analysis] = (),
                  bme: bool = False, spr: bool = False, bionj: bool = False, delta: bool = False, fit: bool = False, ols: bool = False,
-                 treedist: bool = False, treedist_ref: Optional[str] = None):
+                 treedist: bool = False, treedist_ref: Optional[str] = None, root: Optional[str] = None):
         # with --trees: <stem>.bme.nwk / .spr.nwk / .bionj.nwk (and .bionj.bme.nwk / .bionj.spr.nwk) as well (treekinds.KINDS)
         self.flags = [flag for flag, on in (("--bionj", bionj), ("--bme", bme), ("--spr", spr)) if on]
         if not trees and self.flags:
@@ -193,6 +196,14 @@ class DirectoryRunner:
                 raise ValueError(TD.NOTHING_TO_COMPARE)
             for m in boots:
                 m.treedist = True
+        if root and not trees:
+            raise ValueError(ROOT_NEEDS_TREES)
+        if root:
+            from .root import METHODS
+            if root not in METHODS:
+                raise ValueError(f"--root takes one of {', '.join(METHODS)} (got {root})")
+        # --root mad|midpoint: <stem>.root.tsv and, of every written kind, <stem>[.<kind>].rooted.nwk: its table rooted (root.py)
+        self.root = root
         self._made = threading.local()        # the tables device_tables made on this GPU thread for the launch in hand
         self.engines = list(engine) if isinstance(engine, (list, tuple)) else [engine]
         self.out_dir = out_dir
@@ -216,6 +227,8 @@ class DirectoryRunner:
             self.stats.update({"ols": 0, "ols_s": 0.0})
         if self.treedist:
             self.stats.update({"treedist": 0, "treedist_s": 0.0, "treedist_ref_missing": 0})
+        if root:
+            self.stats.update({"root": 0, "root_s": 0.0})
         self.modes = list(modes)
         for m in self.modes:
             m.bind(self.modes)
@@ -408,6 +421,55 @@ class DirectoryRunner:
             self.put(e.path, "ols.tsv", O.ols_tsv(lines))
         self.book(ols=len(group), ols_s=time.perf_counter() - t0)
 
+    def root_arrays(self, engine, n: int, preds: np.ndarray) -> dict:
+        """``--root`` on the GPU thread: ``Engine.tree_root`` of the tables that were made on this thread (``device_tables``), one
+        call for all their kinds, from ``root.ROOT_DEVICE_MIN`` sequences on; a file without a table (distances that are not
+        finite) gets a table of zeros, which is none (status 2).  ``{kind name: (ssq, pos, mid, status)}``; the other kinds are
+        the writer thread's.  Books its seconds."""
+        from . import fit as F, root as R
+        made = {name: tables for name, tables in getattr(self._made, "tables", {}).items() if tables is not None}
+        if not made or not reaches(R.ROOT_DEVICE_MIN, n, F.MIN_SEQS):
+            return {}
+        t0 = time.perf_counter()
+        width, m = F.table_len(n), len(made)
+        slots = np.zeros((len(preds), m, width), dtype=np.int32)
+        lengths = np.zeros((len(preds), m, width), dtype=np.float64)
+        for k, tables in enumerate(made.values()):
+            for b, table in enumerate(tables):
+                if table is not None:
+                    slots[b, k], lengths[b, k] = table.slots, table.lengths
+        out = engine.tree_root(slots, lengths)
+        self.book(root_s=time.perf_counter() - t0)
+        return {name: tuple(a[:, k] for a in out) for k, name in enumerate(made)}
+
+    def _write_root(self, group: list, preds: np.ndarray, tables: dict, made: dict):
+        """The files of ``--root`` of some files of a launch, on a writer thread: of every written kind the GPU thread's arrays
+        where it made them (``made``), else the host side's on the kind's table (``table_of``).  ``<stem>[.<kind>].rooted.nwk`` is
+        the table rooted by the chosen method; ``<stem>.root.tsv`` has ``root.root_scores`` of both rootings.  Fewer than three
+        sequences or lengths that are not finite: the kind's own text and ``nan``."""
+        from . import fit as F, root as R
+        t0 = time.perf_counter()
+        for k, (e, pred) in enumerate(zip(group, preds)):
+            ids = e.ids()
+            n, lines = len(ids), []
+            for kind in self.written_kinds():
+                table = self.table_of(kind, k, pred, tables) if n >= F.MIN_SEQS else None
+                arrays = None
+                if table is not None and kind.name in made:
+                    arrays = tuple(a[k] for a in made[kind.name])
+                elif table is not None:
+                    arrays = self.host.tree_root(table.slots, table.lengths)
+                if arrays is None or arrays[3]:
+                    scores = R.no_scores()
+                    text = self.nj(pred, ids) if kind is KINDS[0] else self.host.tree_text(kind, pred, ids)[0]
+                else:
+                    scores = R.root_scores(table.slots, table.lengths, arrays[0], arrays[1], arrays[2], n)
+                    text = R.rooted_newick(ids, table.slots, table.lengths, *R.root_choice(scores, self.root))
+                lines.append((kind.name, self.root, scores, ids))
+                self.put(e.path, kind.files("rooted.nwk")[0], text)
+            self.put(e.path, "root.tsv", R.root_tsv(lines))
+        self.book(root=len(group), root_s=time.perf_counter() - t0)
+
     def compared(self) -> List[str]:
         """The trees of ``<stem>.treedist.tsv``: every written kind, then ``ref`` with ``--treedist-ref``."""
         return [k.name for k in self.written_kinds()] + (["ref"] if self.treedist_ref else [])
@@ -553,6 +615,10 @@ class DirectoryRunner:
             made, best = dict(self._made.tables), self.ols_arrays(engine, shape[0], preds)
             submit([(self._write_ols, group[k::cap], preds[k::cap], {name: None if t is None else t[k::cap] for name, t in made.items()},
                      {name: tuple(a[k::cap] for a in arrays) for name, arrays in best.items()}) for k in range(min(cap, len(group)))])
+        if self.root:
+            made, roots = dict(self._made.tables), self.root_arrays(engine, shape[0], preds)
+            submit([(self._write_root, group[k::cap], preds[k::cap], {name: None if t is None else t[k::cap] for name, t in made.items()},
+                     {name: tuple(a[k::cap] for a in arrays) for name, arrays in roots.items()}) for k in range(min(cap, len(group)))])
         if self.treedist:
             made, dists = dict(self._made.tables), self.treedist_arrays(engine, shape[0], preds, group)
             submit([(self._write_treedist, group[k::cap], preds[k::cap], {name: None if t is None else t[k::cap] for name, t in made.items()},
@@ -784,6 +850,8 @@ class SiteShardedRunner(DirectoryRunner):
             raise ValueError(FIT_SHARD_SITES)
         if kw.get("ols"):
             raise ValueError(OLS_SHARD_SITES)
+        if kw.get("root"):
+            raise ValueError(ROOT_SHARD_SITES)
         if kw.get("treedist") or kw.get("treedist_ref"):
             from .treedist import SHARD_SITES as TREEDIST_SHARD_SITES
             raise ValueError(TREEDIST_SHARD_SITES)
@@ -898,6 +966,7 @@ def summarize(stats: dict, load_s: float = 0.0) -> dict:
             **({"delta": stats["delta"], "delta_s": round(stats["delta_s"], 6)} if "delta" in stats else {}),
             **({"fit": stats["fit"], "fit_s": round(stats["fit_s"], 6)} if "fit" in stats else {}),
             **({"ols": stats["ols"], "ols_s": round(stats["ols_s"], 6)} if "ols" in stats else {}),
+            **({"root": stats["root"], "root_s": round(stats["root_s"], 6)} if "root" in stats else {}),
             **({"treedist": stats["treedist"], "treedist_s": round(stats["treedist_s"], 6),
                 "treedist_ref_missing": stats["treedist_ref_missing"]} if "treedist" in stats else {})}
 

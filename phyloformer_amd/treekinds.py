@@ -106,7 +106,7 @@ def join_refine(who, start: str, searches, preds: np.ndarray) -> dict:
 
 class Host:
     """A host side answers to the ``Engine``'s names for the computations on join tables (``nj_joins``, ``bionj_joins``,
-    ``bme_nni``, ``bme_spr``, ``join_supports``, ``join_transfers``, ``join_consensus``, ``tree_fit``, ``tree_ols``, ``join_distances``) with its arguments and results,
+    ``bme_nni``, ``bme_spr``, ``join_supports``, ``join_transfers``, ``join_consensus``, ``tree_fit``, ``tree_ols``, ``join_distances``, ``tree_root``) with its arguments and results,
     so an engine serves wherever a side does.  A host side formats as well: ``tree_text`` is ``(text, moves)`` of a kind's
     tree of a distance vector (``texts``; the BIONJ-started searches do not count their moves)."""
 
@@ -124,6 +124,7 @@ class NativeHost(Host):
         self.nj_joins, self.bionj_joins, self.bme_nni, self.bme_spr = h.nj_joins_host, h.bionj_joins_host, h.bme_nni_host, h.bme_spr_host
         self.join_supports, self.join_transfers, self.join_consensus = h.join_supports_host, h.join_transfers_host, h.join_consensus_host
         self.tree_fit, self.tree_ols, self.join_distances = h.tree_fit_host, h.tree_ols_host, h.join_distances_host
+        self.tree_root = h.tree_root_host
         self.nj_support = lambda pred, reps, ids, threads=1: h.nj_support(pred, reps, ids, threads=threads)
         self.texts = {"bme": lambda vec, ids: h.bme_newick(vec, ids, with_steps=True),
                       "spr": lambda vec, ids: h.spr_newick(vec, ids, with_steps=True),
@@ -158,6 +159,10 @@ class PythonHost(Host):
     def tree_ols(self, preds, slots):
         from .ols import tree_ols_batch_py
         return tree_ols_batch_py(preds, slots)
+
+    def tree_root(self, slots, lengths):
+        from .root import tree_root_batch_py
+        return tree_root_batch_py(slots, lengths)
 
     def join_distances(self, slots, lengths=None, flag=None):
         from .treedist import join_distances_batch_py

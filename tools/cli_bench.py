@@ -37,5 +37,6 @@ assert len(os.listdir(outd)) == a.n * ((2 if a.trees else 1) + (3 if "--delta" i
                                       (3 if "--fit" in a.extra.split() else 0) +     # (--fit with -t alone: the NJ tree's three files)
                                       (2 if "--ols" in a.extra.split() else 0) +     # (--ols likewise: <stem>.ols.nwk and <stem>.ols.tsv)
                                       (1 if "--bme" in a.extra.split() else 0) +     # (<stem>.bme.nwk: the second tree of --treedist)
-                                      (1 if "--treedist" in a.extra.split() else 0)) # (<stem>.treedist.tsv)
+                                      (1 if "--treedist" in a.extra.split() else 0) + # (<stem>.treedist.tsv)
+                                      (2 if "--root" in a.extra.split() else 0))     # (--root with -t alone: <stem>.rooted.nwk and <stem>.root.tsv)
 shutil.rmtree(tmp)
